@@ -21,6 +21,13 @@ Workloads (--graph): N = 1 defaults to BASELINE.json config 2 (reddit).  N > 1 (
 default to config 4: every rank owns one 1/8 shard of a papers100M-shaped graph (13.9 M nodes,
 202 M edges, d = 128) -- weak scaling, node-range partition (custom_op_benchmark_amd.dist), halo K/V
 rows and dK/dV partial rows by RCCL all-to-all each step.  `--graph rmat25` is config 5 (d = 256).
+
+A plain run does only what the headline needs: setup, warm-up, the --steps timed steps, the result
+line.  --full adds every secondary measurement, each of which takes runs of its own: the fused op,
+per-kernel times and the roofline figures read from them, the CPU baseline, and on sharded lines the
+single-GPU reference, the exposed exchange time and the per-exchange times.
+--dump-outputs DIR writes what the last timed step returned to its caller (o, dQ, dK, dV, s, a) as
+DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import hashlib
@@ -58,6 +65,7 @@ L2_GATHER_GBS = 30000.0
 PASS_TAGS = ["sddmm_fwd", "softmax_fwd", "spmm_fwd", "spmm_bwd_dedata", "spmm_bwd_dx", "softmax_bwd",
              "sddmm_bwd_dA", "sddmm_bwd_dB"]
 GATHER_TAGS = [t for t in PASS_TAGS if not t.startswith("softmax")]
+DUMP_BYTES = 48 << 20          # --dump-outputs: all files together
 
 
 def pass_bytes(E, N_rows, N_cols, h, d, C, Cc):
@@ -147,6 +155,29 @@ def cpu_baseline(g, Q, K, V, dO, sample_edges, log, incidence=False):
     return out
 
 
+def dump_outputs(outs, out_dir, budget=DUMP_BYTES, seed=0):
+    """--dump-outputs: every array of `outs` as out_dir/<name>.npy, float64 where the step computed fp64, else float32.
+    An array beyond its even share of `budget` is written as a sample of its leading-dimension slices (node rows, edges):
+    sorted indices drawn from a CPU generator with a fixed seed, so every run -- and every build -- writes the same slices
+    of an array of a given length.  Returns {name: number of slices written}."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    share = budget // max(1, len(outs)) - 4096          # (room for the .npy header)
+    written = {}
+    for name, t in outs.items():
+        t = t.detach()
+        t = t if t.dtype == torch.float64 else t.float()
+        n = t.size(0)
+        slice_bytes = max(1, t[0].numel() * t.element_size()) if n else 1
+        if n * slice_bytes > share:
+            idx = torch.randint(0, n, (max(1, share // slice_bytes),), generator=torch.Generator().manual_seed(seed)).unique()
+            t = t.index_select(0, idx.to(t.device))
+        a = t.cpu().numpy()
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+        written[name] = a.shape[0]
+    return written
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -187,8 +218,17 @@ def main():
                     help="capture the step once into a HIP graph and time its replays (single GPU; for the "
                          "launch-bound small shapes -- the headline line is measured with eager API calls)")
     ap.add_argument("--no-fused", action="store_true", help="skip the secondary measurement of the fused op")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the secondary measurements (fused op, per-kernel times + roofline, CPU baseline, sharded "
+                         "lines' single-GPU reference and exchange costs); a plain run times the headline step only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned (o, dQ, dK, dV, s, a; rank 0's shard on "
+                         "sharded lines) as DIR/<name>.npy, at most %d MB in all: a larger array is written as a fixed, "
+                         "seeded sample of its rows / edges" % (DUMP_BYTES >> 20))
     ap.add_argument("--verbose", action="store_true")
     args = ap.parse_args()
+    if args.steps < 1:
+        raise SystemExit("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -311,9 +351,8 @@ def main():
     def step():
         Q.grad = K.grad = V.grad = None
         if runner is None:
-            functions.attention_step(g, Q, K, V, dO)
-        else:
-            runner.step(Q, K, V, dO)
+            return functions.attention_step(g, Q, K, V, dO)
+        return runner.step(Q, K, V, dO)
 
     t0 = time.perf_counter()
     step()                                   # first call builds + caches the per-graph plans
@@ -336,7 +375,7 @@ def main():
     # the GPU), timed in this process before the measured region -- the reference the weak-scaling
     # efficiency of THIS line is taken against
     single_ref_ms = None
-    if runner is not None and world > 1:
+    if runner is not None and world > 1 and args.full:
         runner.emulate = True
         for _ in range(2):
             step()
@@ -361,7 +400,7 @@ def main():
         Q.grad = K.grad = V.grad = None
         hip_graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(hip_graph):
-            functions.attention_step(g, Q, K, V, dO)
+            graph_res = functions.attention_step(g, Q, K, V, dO)      # (static tensors every replay rewrites)
         timed_step = hip_graph.replay
         timed_step()
 
@@ -377,12 +416,21 @@ def main():
     t0 = time.perf_counter()
     evs[0].record()
     for i in range(args.steps):
-        timed_step()
+        res = None             # (a step's outputs are released before the next step runs; the last step's are kept)
+        res = timed_step()
         evs[i + 1].record()
     barrier()
     elapsed = time.perf_counter() - t0
     _lib.check_errors()    # (device already synchronised) a walk kernel whose hand-over timed out: no number is reported
     step_ms = [evs[i].elapsed_time(evs[i + 1]) for i in range(args.steps)]
+    if args.dump_outputs and rank == 0:
+        if args.hip_graph:
+            res = graph_res
+        if runner is None:         # functions.attention_step: (s, a, o) returned, gradients in .grad
+            res = dict(zip(("s", "a", "o"), res), dQ=Q.grad, dK=K.grad, dV=V.grad)
+        written = dump_outputs({k: res[k] for k in ("o", "dQ", "dK", "dV", "s", "a")}, args.dump_outputs)
+        log("outputs of the last timed step written to %s (slices per array: %s)" % (args.dump_outputs, written))
+    res = None
     if world > 1:
         cdev = dev if dist.get_backend() == "nccl" else torch.device("cpu")
         tt = torch.tensor([elapsed], device=cdev, dtype=torch.float64)
@@ -396,6 +444,56 @@ def main():
     ms_per_step = 1e3 * elapsed / args.steps
     value = total_edges * args.steps / elapsed
     plan_mb_step = _lib.plan_memory_bytes() / 2**20      # what the 8-function step alone keeps (before the fused op builds its layouts)
+
+    cfg = {"workload": "%s-shape %s graph, N=%d E=%d per GPU, h=%d d=%d, %s values, chunk_size=%d, int64 CSR both "
+                       "orientations" % (name, gdesc, n_own, g.n_edges, h, d,
+                                         "U[0,1)" if args.values != "normal" else "N(0,1)/sqrt(d)", args.chunk_size),
+           "graph": name, "nodes": n_rows, "edges": total_edges, "heads": h, "d": d,
+           "chunk_size": args.chunk_size, "row_chunks": g.n_row_chunks, "col_chunks": g.n_col_chunks,
+           "parallelism": ("single GPU" if not sharded else "node-range shards x%d, RCCL all-to-all halo" % n_parts)
+                          + (" [one-rank nccl process group, self-halo: the RCCL code path on one GPU]" if args.rccl_self else "")
+                          + (" [TIMING-ONLY rehearsal of shard 0 of %d on one GPU, exchanges = local copies]" % args.emulate_world
+                             if args.emulate_world > 1 and world == 1 else "")}
+    if runner is not None:
+        cfg["weak_scaling_note"] = ("N > 1 runs BASELINE.json config %s (one 1/8 shard of the %s shape per GPU, fixed work per GPU); "
+                                    "the N = 1 default is the Reddit headline (config 2), a different workload: compare "
+                                    "N > 1 values among themselves and with `bench.py --gpus 1 --graph %s` (the same shard "
+                                    "without halo)" % ("4" if name == "papers100m" else "5" if name == "rmat25" else "?", name, name))
+        cfg["halo"] = runner.halo_stats(h * d * 4)
+        cfg["schedule"] = {"kv_packed": bool(cfg["halo"]["kv_packed"]), "columns_fused": bool(runner.fuse_columns),
+                           "forward_split": bool(cfg["halo"]["forward_split"]),
+                           "measured_ms_per_step": schedule,
+                           "how": ("dist.ShardedAttention.autotune: every schedule timed for 2 steps after a warm-up, max over "
+                                   "ranks, fastest adopted by all ranks" if schedule else "default (--no-autotune)")}
+    if world > 1 or args.rccl_self:
+        cfg["world_size"] = dist.get_world_size()
+        cfg["backend"] = dist.get_backend()
+    metric = "edges/sec fwd+bwd (SDDMM+softmax+SpMM) on Reddit d=64; HBM GB/s vs roofline"
+    if not (name == "reddit" and h == 1 and d == 64 and not sharded):
+        # the BASELINE.json metric is quoted on Reddit d=64; any other workload says what it ran
+        metric = ("edges/sec fwd+bwd (SDDMM+softmax+SpMM) on %s%s h=%d d=%d; HBM GB/s vs roofline"
+                  % (name, (" (one 1/%d node-range shard per GPU, BASELINE.json config %s)"
+                            % (graphs.SHARDS_OF.get(name, n_parts), "4" if name == "papers100m" else "5" if name == "rmat25" else "-"))
+                     if sharded else "-shape", h, d))
+    out = {
+        "metric": metric,
+        "value": value, "unit": "edges/s", "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "step_ms": {"median": round(statistics.median(step_ms), 4), "min": round(min(step_ms), 4),
+                    "max": round(max(step_ms), 4), "method": "hipEvents around every timed step on the launch stream"},
+        "config": cfg,
+        "setup": {"graph_build_s": round(t_graph, 2), "first_step_with_plans_s": round(t_first, 3),
+                  "plan_memory_MB_8_function_step": round(plan_mb_step, 1)},
+        "launch": "hip graph replay" if args.hip_graph else "eager API calls",
+    }
+    if not args.full:
+        # the headline line alone: every figure below takes runs of its own (--full)
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1 or args.rccl_self:
+            dist.destroy_process_group()
+        return
 
     # sharded lines: what the exchanges cost the step = this step - the same step with every exchange a no-op (nothing
     # is packed, sent, awaited or added; values involving halo rows are garbage: timing only), measured the same way
@@ -628,26 +726,7 @@ def main():
     except Exception as exc:      # reporting only
         log("mfma report skipped: %r" % (exc,))
 
-    cfg = {"workload": "%s-shape %s graph, N=%d E=%d per GPU, h=%d d=%d, %s values, chunk_size=%d, int64 CSR both "
-                       "orientations" % (name, gdesc, n_own, g.n_edges, h, d,
-                                         "U[0,1)" if args.values != "normal" else "N(0,1)/sqrt(d)", args.chunk_size),
-           "graph": name, "nodes": n_rows, "edges": total_edges, "heads": h, "d": d,
-           "chunk_size": args.chunk_size, "row_chunks": g.n_row_chunks, "col_chunks": g.n_col_chunks,
-           "parallelism": ("single GPU" if not sharded else "node-range shards x%d, RCCL all-to-all halo" % n_parts)
-                          + (" [one-rank nccl process group, self-halo: the RCCL code path on one GPU]" if args.rccl_self else "")
-                          + (" [TIMING-ONLY rehearsal of shard 0 of %d on one GPU, exchanges = local copies]" % args.emulate_world
-                             if args.emulate_world > 1 and world == 1 else "")}
     if runner is not None:
-        cfg["weak_scaling_note"] = ("N > 1 runs BASELINE.json config %s (one 1/8 shard of the %s shape per GPU, fixed work per GPU); "
-                                    "the N = 1 default is the Reddit headline (config 2), a different workload: compare "
-                                    "N > 1 values among themselves and with `bench.py --gpus 1 --graph %s` (the same shard "
-                                    "without halo)" % ("4" if name == "papers100m" else "5" if name == "rmat25" else "?", name, name))
-        cfg["halo"] = runner.halo_stats(h * d * 4)
-        cfg["schedule"] = {"kv_packed": bool(cfg["halo"]["kv_packed"]), "columns_fused": bool(runner.fuse_columns),
-                           "forward_split": bool(cfg["halo"]["forward_split"]),
-                           "measured_ms_per_step": schedule,
-                           "how": ("dist.ShardedAttention.autotune: every schedule timed for 2 steps after a warm-up, max over "
-                                   "ranks, fastest adopted by all ranks" if schedule else "default (--no-autotune)")}
         # per-exchange wall times, measured in a separate pass (their syncs defeat the overlap)
         runner.timers = {}
         for _ in range(2):
@@ -664,32 +743,12 @@ def main():
             cfg["halo"]["exchange_ms_note"] = ("one-rank RCCL process group: all_to_all_single from this GPU to itself (the real "
                                                "collective code path, no xGMI link involved)")
         runner.timers = None
-    metric = "edges/sec fwd+bwd (SDDMM+softmax+SpMM) on Reddit d=64; HBM GB/s vs roofline"
-    if not (name == "reddit" and h == 1 and d == 64 and not sharded):
-        # the BASELINE.json metric is quoted on Reddit d=64; any other workload says what it ran
-        metric = ("edges/sec fwd+bwd (SDDMM+softmax+SpMM) on %s%s h=%d d=%d; HBM GB/s vs roofline"
-                  % (name, (" (one 1/%d node-range shard per GPU, BASELINE.json config %s)"
-                            % (graphs.SHARDS_OF.get(name, n_parts), "4" if name == "papers100m" else "5" if name == "rmat25" else "-"))
-                     if sharded else "-shape", h, d))
-    if world > 1 or args.rccl_self:
-        cfg["world_size"] = dist.get_world_size()
-        cfg["backend"] = dist.get_backend()
-    out = {
-        "metric": metric,
-        "value": value, "unit": "edges/s", "n_gpus": args.gpus, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32", "data": "synthetic",
-        "step_ms": {"median": round(statistics.median(step_ms), 4), "min": round(min(step_ms), 4),
-                    "max": round(max(step_ms), 4), "method": "hipEvents around every timed step on the launch stream"},
-        "config": cfg,
-        "setup": {"graph_build_s": round(t_graph, 2), "first_step_with_plans_s": round(t_first, 3),
-                  "plan_memory_MB": round(_lib.plan_memory_bytes() / 2**20, 1),
-                  "plan_memory_MB_8_function_step": round(plan_mb_step, 1),
-                  "plan_memory_note": "device bytes of both orientations' plans: every layout of the 8-function step AND (plan_memory_MB) "
-                                      "of the fused op measured behind it; a model uses one of the two forms"},
-        "launch": "hip graph replay" if args.hip_graph else "eager API calls",
-        "roofline": roofline,
-    }
+    out["setup"] = {"graph_build_s": round(t_graph, 2), "first_step_with_plans_s": round(t_first, 3),
+                    "plan_memory_MB": round(_lib.plan_memory_bytes() / 2**20, 1),
+                    "plan_memory_MB_8_function_step": round(plan_mb_step, 1),
+                    "plan_memory_note": "device bytes of both orientations' plans: every layout of the 8-function step AND (plan_memory_MB) "
+                                        "of the fused op measured behind it; a model uses one of the two forms"}
+    out["roofline"] = roofline
     if exposed_ms is not None:
         kern_ms = sum(other[t]["ms_per_step"] for t in ("halo_pack", "halo_unpack_add") if t in other)
         out["exposed_exchange_breakdown"] = {"pack_and_add_home_kernels_ms": round(kern_ms, 4),

@@ -237,7 +237,8 @@ def test_bench_line_through_the_rccl_path(dev):
     env = dict(os.environ, MASTER_ADDR="127.0.0.1", MASTER_PORT=str(31500 + os.getpid() % 2000), HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--graph", "custom", "--nodes", "30000",
                         "--edges", "600000", "--d", "64", "--cut", "0.2", "--rccl-self", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--profile-steps", "1"], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+                        "--full", "--no-cpu-baseline", "--profile-steps", "1"], capture_output=True, text=True, timeout=600, env=env,
+                       cwd=root)
     assert r.returncode == 0, (r.stdout[-1500:], r.stderr[-3000:])
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     cfg = line["config"]
