@@ -15,7 +15,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GRAPHOP_LIB") or os.path.join(_HERE, "libgraphop_hip.so")   # override: A/B builds
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 F32, F64 = 0, 1
 _c64 = ctypes.c_int64
@@ -81,6 +81,8 @@ _SIGNATURES = {
     "graphop_interleave_pairs": [ctypes.c_int, _P, _P, _P, _c64, _P],
     "graphop_node_mul_edge_forward": [ctypes.c_int] + [_P] * 6 + [_c64] * 5 + [_P, _P],
     "graphop_node_mul_edge_backward": [ctypes.c_int] + [_P] * 8 + [_c64] * 5 + [_P, _P],
+    "graphop_gat_scores_forward": [ctypes.c_int] + [_P] * 7 + [_c64] * 5 + [ctypes.c_double, _P, _P],
+    "graphop_gat_scores_backward": [ctypes.c_int] + [_P] * 13 + [_c64] * 6 + [ctypes.c_double, _P, _P, _P],
     "graphop_gather_rows": [ctypes.c_int, _P, _P, _P, _c64, _c64, _c64, _P],
     "graphop_scatter_add_rows": [ctypes.c_int, _P, _P, _P, _c64, _c64, _c64, _P],
     "graphop_add_rows_unique": [ctypes.c_int, _P, _P, _P, _c64, _c64, _c64, _P],

@@ -1,0 +1,192 @@
+// GAT additive attention scores (extra op, not one of the reference's eight; include/graphop_hip.h):
+//   forward : y[eid[j], k] = LeakyReLU(el[row[c], k] + er[indices[j], k], negative_slope)
+//   backward: del / der by a row-major and a column-major pass (kernels_gat.h), no per-edge atomics.
+// Host-side dispatch only, in the style of the operator entry points of graphop_hip.hip: validation, zero fills with
+// the library's own fill kernel, and the choice between the fp32 fast kernels (with a plan of the same arrays) and the
+// generic kernels (fp64, other head counts, no plan).
+#include "common.h"
+#include "host.h"
+#include "kernels_gat.h"
+
+namespace graphop {
+namespace {
+
+inline int gat_check(const char* fn, int dtype, i64 C, i64 C2, i64 E, i64 n_l, i64 n_r, i64 h) {
+  GO_TRY(check_async_error(false));   // a kernel of an earlier launch reported a failure: sticky until acknowledged
+  GO_CHECK_ARG(dtype == GRAPHOP_F32 || dtype == GRAPHOP_F64, "%s: dtype must be GRAPHOP_F32 or GRAPHOP_F64", fn);
+  GO_CHECK_ARG(C >= 0 && C2 >= 0 && E >= 0 && n_l >= 0 && n_r >= 0 && h >= 1,
+               "%s: negative size (n_chunks=%lld/%lld n_edges=%lld n_l=%lld n_r=%lld h=%lld)", fn, (long long)C,
+               (long long)C2, (long long)E, (long long)n_l, (long long)n_r, (long long)h);
+  return GRAPHOP_OK;
+}
+
+// A plan of these arrays bounds its row ids and neighbour ids: an operand with too few rows is an error here.
+inline int gat_check_plan(const char* fn, const graphop_plan* p, const char* seg_name, i64 n_seg, const char* idx_name,
+                          i64 n_idx) {
+  if (!p) return GRAPHOP_OK;
+  GO_CHECK_ARG(p->info.max_row < n_seg, "%s: row id %lld but %s has only %lld rows", fn, (long long)p->info.max_row,
+               seg_name, (long long)n_seg);
+  GO_CHECK_ARG(p->info.max_index < n_idx, "%s: neighbour id %lld but %s has only %lld rows", fn,
+               (long long)p->info.max_index, idx_name, (long long)n_idx);
+  return GRAPHOP_OK;
+}
+
+inline bool gat_aligned(const void* p, i64 h) {
+  const uintptr_t a = h >= 4 ? 16 : (uintptr_t)(4 * h);
+  return ((uintptr_t)p % a) == 0;
+}
+
+// fp32 fast kernels: H in {1, 2, 4, 8, 16}, ids that fit 32 bits, value arrays aligned to their item width
+inline bool gat_fast_ok(int dtype, i64 h, i64 E, i64 n_l, i64 n_r, const void* p0, const void* p1, const void* p2,
+                        const void* p3) {
+  if (tuning().force_generic || dtype != GRAPHOP_F32) return false;
+  if (h != 1 && h != 2 && h != 4 && h != 8 && h != 16) return false;
+  if (E >= 0x7fffffffLL || n_l >= 0x7fffffffLL || n_r >= 0x7fffffffLL) return false;
+  return gat_aligned(p0, h) && gat_aligned(p1, h) && gat_aligned(p2, h) && (!p3 || gat_aligned(p3, h));
+}
+
+// chunks per lane group: the tuned cap on big graphs, fewer on small ones so every CU still gets groups
+inline int gat_cpg(i64 n_chunks, int cpg_max, int G) {
+  const i64 groups_wanted = (i64)tuning().n_cu * (kFastBlock / G) * 8;
+  i64 c = n_chunks / (groups_wanted > 0 ? groups_wanted : 1);
+  if (c < 1) c = 1;
+  return (int)(c < cpg_max ? c : cpg_max);
+}
+
+#define GO_DISPATCH_GAT_H(h, ...)                 \
+  switch ((int)(h)) {                             \
+    case 1: { constexpr int H = 1; __VA_ARGS__; } break;   \
+    case 2: { constexpr int H = 2; __VA_ARGS__; } break;   \
+    case 4: { constexpr int H = 4; __VA_ARGS__; } break;   \
+    case 8: { constexpr int H = 8; __VA_ARGS__; } break;   \
+    case 16: { constexpr int H = 16; __VA_ARGS__; } break; \
+    default: break;                               \
+  }
+
+// One backward pass (ROW: del over the row-major chunks; else der over the column-major chunks).
+template <bool ROW>
+int gat_bwd_pass(int dtype, const i64* seg, const i64* indptr, const i64* eid, const i64* indices, const void* el,
+                 const void* er, const void* dy, void* out, i64 C, i64 E, i64 n_l, i64 n_r, i64 h, double slope,
+                 const graphop_plan* plan, hipStream_t st) {
+  if (plan && gat_fast_ok(dtype, h, E, n_l, n_r, el, er, dy, out)) {
+    ProfScope prof(ROW ? "gat_bwd_row" : "gat_bwd_col", st, ROW ? "k_gat_bwd_row_f32" : "k_gat_bwd_col_f32");
+    GO_DISPATCH_GAT_H(h, {
+      constexpr int G = GatCfg<H>::G;
+      const int cpg = gat_cpg(C, tuning().spmm_cpg, G);
+      const unsigned nb = (unsigned)ceil_div(ceil_div(C, cpg), kFastBlock / G);
+      if constexpr (ROW)
+        hipLaunchKernelGGL((k_gat_bwd_row_f32<H>), dim3(nb), dim3(kFastBlock), 0, st, seg, indptr, eid, indices,
+                           (const float*)el, (const float*)er, (const float*)dy, (float*)out, C, cpg, (float)slope);
+      else
+        hipLaunchKernelGGL((k_gat_bwd_col_f32<H>), dim3(nb), dim3(kFastBlock), 0, st, seg, indptr, eid, indices,
+                           (const float*)el, (const float*)er, (const float*)dy, (float*)out, C, cpg, (float)slope);
+    });
+  } else {
+    ProfScope prof(ROW ? "gat_bwd_row" : "gat_bwd_col", st, ROW ? "k_gat_bwd_row_generic" : "k_gat_bwd_col_generic");
+    const unsigned nb = (unsigned)ceil_div(C, kGenericWavesPerBlock);
+    auto go = [&](auto zero) {
+      using T = decltype(zero);
+      if constexpr (ROW)
+        hipLaunchKernelGGL((k_gat_bwd_row_generic<T>), dim3(nb), dim3(kGenericBlock), 0, st, seg, indptr, eid, indices,
+                           (const T*)el, (const T*)er, (const T*)dy, (T*)out, C, h, (T)slope);
+      else
+        hipLaunchKernelGGL((k_gat_bwd_col_generic<T>), dim3(nb), dim3(kGenericBlock), 0, st, seg, indptr, eid, indices,
+                           (const T*)el, (const T*)er, (const T*)dy, (T*)out, C, h, (T)slope);
+    };
+    if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+  }
+  GO_LAUNCH_CHECK();
+  return GRAPHOP_OK;
+}
+
+}  // namespace
+}  // namespace graphop
+
+using namespace graphop;
+
+extern "C" {
+
+int graphop_gat_scores_forward(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                               const int64_t* indices, const void* el, const void* er, void* y, int64_t n_chunks,
+                               int64_t n_edges, int64_t n_l, int64_t n_r, int64_t h, double negative_slope,
+                               const graphop_plan_t* plan, void* stream) {
+  const char* fn = "gat_scores_forward";
+  GO_TRY(gat_check(fn, dtype, n_chunks, 0, n_edges, n_l, n_r, h));
+  hipStream_t st = (hipStream_t)stream;
+  if (n_edges == 0) return GRAPHOP_OK;
+  GO_PTR(fn, y);
+  const graphop_plan* pm = plan_matches_full(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
+                                             (const i64*)indices, n_chunks, n_edges) ? plan : nullptr;
+  GO_TRY(gat_check_plan(fn, pm, "el", n_l, "er", n_r));
+  const bool covered = pm && pm->info.full_coverage && pm->info.eid_identity && pm->info.indptr_monotone;
+  if (!covered) GO_HIP(zero_async(y, esize(dtype) * (size_t)(n_edges * h), st));
+  if (n_chunks == 0) return GRAPHOP_OK;
+  GO_PTR(fn, row); GO_PTR(fn, indptr); GO_PTR(fn, eid); GO_PTR(fn, indices); GO_PTR(fn, el); GO_PTR(fn, er);
+  if (pm && gat_fast_ok(dtype, h, n_edges, n_l, n_r, el, er, y, nullptr)) {
+    ProfScope prof("gat_fwd", st, "k_gat_fwd_f32");
+    GO_DISPATCH_GAT_H(h, {
+      constexpr int G = GatCfg<H>::G;
+      const int cpg = gat_cpg(n_chunks, tuning().sddmm_cpg, G);
+      const unsigned nb = (unsigned)ceil_div(ceil_div(n_chunks, cpg), kFastBlock / G);
+      hipLaunchKernelGGL((k_gat_fwd_f32<H>), dim3(nb), dim3(kFastBlock), 0, st, (const i64*)row, (const i64*)indptr,
+                         (const i64*)eid, (const i64*)indices, (const float*)el, (const float*)er, (float*)y, n_chunks,
+                         cpg, (float)negative_slope);
+    });
+  } else {
+    ProfScope prof("gat_fwd", st, "k_gat_fwd_generic");
+    const unsigned nb = (unsigned)ceil_div(n_chunks, kGenericWavesPerBlock);
+    if (dtype == GRAPHOP_F32)
+      hipLaunchKernelGGL((k_gat_fwd_generic<float>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)row,
+                         (const i64*)indptr, (const i64*)eid, (const i64*)indices, (const float*)el, (const float*)er,
+                         (float*)y, n_chunks, h, (float)negative_slope);
+    else
+      hipLaunchKernelGGL((k_gat_fwd_generic<double>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)row,
+                         (const i64*)indptr, (const i64*)eid, (const i64*)indices, (const double*)el, (const double*)er,
+                         (double*)y, n_chunks, h, negative_slope);
+  }
+  GO_LAUNCH_CHECK();
+  return GRAPHOP_OK;
+}
+
+int graphop_gat_scores_backward(int dtype, const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r,
+                                const int64_t* indices_r, const int64_t* col, const int64_t* indptr_c,
+                                const int64_t* eid_c, const int64_t* indices_c, const void* el, const void* er,
+                                const void* dy, void* del, void* der, int64_t n_row_chunks, int64_t n_col_chunks,
+                                int64_t n_edges, int64_t n_l, int64_t n_r, int64_t h, double negative_slope,
+                                const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream) {
+  const char* fn = "gat_scores_backward";
+  GO_TRY(gat_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_l, n_r, h));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t es = esize(dtype);
+  const graphop_plan* pr = plan_matches_full(plan_r, (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r,
+                                             (const i64*)indices_r, n_row_chunks, n_edges) ? plan_r : nullptr;
+  const graphop_plan* pc = plan_matches_full(plan_c, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c,
+                                             (const i64*)indices_c, n_col_chunks, n_edges) ? plan_c : nullptr;
+  GO_TRY(gat_check_plan(fn, pr, "el / del", n_l, "er", n_r));
+  GO_TRY(gat_check_plan(fn, pc, "er / der", n_r, "el", n_l));
+  // an output whose orientation has no chunks may be NULL: that half of the op is skipped
+  if (n_l > 0 && !(del == nullptr && n_row_chunks == 0)) {
+    GO_PTR(fn, del);
+    GO_HIP(zero_async(del, es * (size_t)(n_l * h), st));
+  }
+  if (n_r > 0 && !(der == nullptr && n_col_chunks == 0)) {
+    GO_PTR(fn, der);
+    GO_HIP(zero_async(der, es * (size_t)(n_r * h), st));
+  }
+  if (n_edges == 0) return GRAPHOP_OK;
+  if (n_row_chunks > 0) {
+    GO_PTR(fn, row); GO_PTR(fn, indptr_r); GO_PTR(fn, eid_r); GO_PTR(fn, indices_r);
+    GO_PTR(fn, el); GO_PTR(fn, er); GO_PTR(fn, dy); GO_PTR(fn, del);
+    GO_TRY(gat_bwd_pass<true>(dtype, (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r, (const i64*)indices_r,
+                              el, er, dy, del, n_row_chunks, n_edges, n_l, n_r, h, negative_slope, pr, st));
+  }
+  if (n_col_chunks > 0) {
+    GO_PTR(fn, col); GO_PTR(fn, indptr_c); GO_PTR(fn, eid_c); GO_PTR(fn, indices_c);
+    GO_PTR(fn, el); GO_PTR(fn, er); GO_PTR(fn, dy); GO_PTR(fn, der);
+    GO_TRY(gat_bwd_pass<false>(dtype, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c, (const i64*)indices_c,
+                               el, er, dy, der, n_col_chunks, n_edges, n_l, n_r, h, negative_slope, pc, st));
+  }
+  return GRAPHOP_OK;
+}
+
+}  // extern "C"

@@ -390,6 +390,58 @@ std::vector<at::Tensor> attention_backward(const at::Tensor& row, const at::Tens
   return {dQ, dK, dV};
 }
 
+// ---- the extra GAT score op (include/graphop_hip.h: graphop_gat_scores_*) ---------------------------------
+int64_t gat_heads(const at::Tensor& el, const at::Tensor& er, const char* fn) {
+  CHECK_SAME_DTYPE(el, er);
+  TORCH_CHECK((el.dim() == 1 || el.dim() == 2) && er.dim() == el.dim() && (el.dim() == 1 || el.size(1) == er.size(1)),
+              fn, ": el (n_src[, h]) and er (n_dst[, h]) must have the same h, got ", el.sizes(), " and ", er.sizes());
+  return el.dim() == 1 ? 1 : el.size(1);
+}
+
+at::Tensor gat_scores_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
+                              const at::Tensor& indices, const at::Tensor& el, const at::Tensor& er,
+                              double negative_slope) {
+  CHECK_INPUT(row); CHECK_INPUT(indptr); CHECK_INPUT(eid); CHECK_INPUT(indices); CHECK_INPUT(el); CHECK_INPUT(er);
+  CHECK_INDEX(row); CHECK_INDEX(indptr); CHECK_INDEX(eid); CHECK_INDEX(indices);
+  const int64_t h = gat_heads(el, er, "gat_scores_forward");
+  DeviceGuard dg(el);
+  const int64_t e = eid.size(0);
+  auto y = edge_out(el, e, h);
+  const auto pp = get_plan(row, indptr, eid, indices, er.size(0));
+  const auto& p = *pp;
+  check(graphop_gat_scores_forward(dtype_code(el), ip(row), ip(indptr), ip(eid), ip(indices), vp(el), vp(er), vp(y),
+                                   row.size(0), e, el.size(0), er.size(0), h, negative_slope, p.plan, stream_of(el)));
+  return y;
+}
+
+std::vector<at::Tensor> gat_scores_backward(const at::Tensor& row, const at::Tensor& indptr_r, const at::Tensor& eid_r,
+                                            const at::Tensor& indices_r, const at::Tensor& col,
+                                            const at::Tensor& indptr_c, const at::Tensor& eid_c,
+                                            const at::Tensor& indices_c, const at::Tensor& el, const at::Tensor& er,
+                                            const at::Tensor& dy_, double negative_slope) {
+  CHECK_INPUT(row); CHECK_INPUT(indptr_r); CHECK_INPUT(eid_r); CHECK_INPUT(indices_r);
+  CHECK_INPUT(col); CHECK_INPUT(indptr_c); CHECK_INPUT(eid_c); CHECK_INPUT(indices_c); CHECK_INPUT(el); CHECK_INPUT(er);
+  CHECK_INDEX(row); CHECK_INDEX(indptr_r); CHECK_INDEX(eid_r); CHECK_INDEX(indices_r);
+  CHECK_INDEX(col); CHECK_INDEX(indptr_c); CHECK_INDEX(eid_c); CHECK_INDEX(indices_c);
+  CHECK_CUDA(dy_);
+  const at::Tensor dy = dy_.contiguous();
+  const int64_t h = gat_heads(el, er, "gat_scores_backward");
+  CHECK_SAME_DTYPE(el, dy);
+  const int64_t e = eid_r.size(0);
+  TORCH_CHECK(dy.numel() == e * h, "gat_scores_backward: dy must hold (n_edges, h) = (", e, ", ", h, ") values, got ",
+              dy.sizes());
+  DeviceGuard dg(el);
+  auto d_el = at::empty_like(el), d_er = at::empty_like(er);
+  const auto ppr = get_plan(row, indptr_r, eid_r, indices_r, er.size(0));
+  const auto ppc = get_plan(col, indptr_c, eid_c, indices_c, el.size(0));
+  const auto &pr = *ppr, &pc = *ppc;
+  check(graphop_gat_scores_backward(dtype_code(el), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col),
+                                    ip(indptr_c), ip(eid_c), ip(indices_c), vp(el), vp(er), vp(dy), vp(d_el), vp(d_er),
+                                    row.size(0), col.size(0), e, el.size(0), er.size(0), h, negative_slope, pr.plan,
+                                    pc.plan, stream_of(el)));
+  return {d_el, d_er};
+}
+
 void clear_plan_cache() {
   std::vector<PlanRef> dead;
   {
@@ -434,6 +486,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("vector_spmm_backward", &vector_spmm_backward, "Vectorized SPMM backward");
   m.def("attention_forward", &attention_forward, "Fused SDDMM -> softmax -> SpMM forward (extra op)");
   m.def("attention_backward", &attention_backward, "Fused attention backward (extra op)");
+  m.def("gat_scores_forward", &gat_scores_forward, "GAT additive attention scores forward (extra op)", py::arg("row"),
+        py::arg("indptr"), py::arg("eid"), py::arg("indices"), py::arg("el"), py::arg("er"), py::arg("negative_slope") = 0.2);
+  m.def("gat_scores_backward", &gat_scores_backward, "GAT additive attention scores backward (extra op)", py::arg("row"),
+        py::arg("indptr_r"), py::arg("eid_r"), py::arg("indices_r"), py::arg("col"), py::arg("indptr_c"), py::arg("eid_c"),
+        py::arg("indices_c"), py::arg("el"), py::arg("er"), py::arg("dy"), py::arg("negative_slope") = 0.2);
   m.def("clear_plan_cache", &clear_plan_cache, "Destroy every cached per-graph plan");
   m.def("release_plans", &release_plans, "Drop the cached plans of the orientation whose chunk list is `row`");
   m.def("plan_cache_size", &plan_cache_size, "Graph orientations in the plan cache");
@@ -451,6 +508,8 @@ TORCH_LIBRARY(graphop, m) {
   m.def("vector_spmm_backward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor col, Tensor indptr_t, Tensor eid_t, Tensor indices_t, Tensor edata, Tensor dy, Tensor x) -> Tensor[]");
   m.def("attention_forward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor Q, Tensor K, Tensor V) -> Tensor[]");
   m.def("attention_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor Q, Tensor K, Tensor V, Tensor o, Tensor stats, Tensor dO) -> Tensor[]");
+  m.def("gat_scores_forward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, float negative_slope=0.2) -> Tensor");
+  m.def("gat_scores_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor dy, float negative_slope=0.2) -> Tensor[]");
 }
 
 TORCH_LIBRARY_IMPL(graphop, CUDA, m) {
@@ -464,6 +523,8 @@ TORCH_LIBRARY_IMPL(graphop, CUDA, m) {
   m.impl("vector_spmm_backward", &vector_spmm_backward);
   m.impl("attention_forward", &attention_forward);
   m.impl("attention_backward", &attention_backward);
+  m.impl("gat_scores_forward", &gat_scores_forward);
+  m.impl("gat_scores_backward", &gat_scores_backward);
 }
 
 TORCH_LIBRARY_IMPL(graphop, CPU, m) {   // there is no CPU implementation: the reference's CHECK_CUDA message
@@ -477,4 +538,6 @@ TORCH_LIBRARY_IMPL(graphop, CPU, m) {   // there is no CPU implementation: the r
   m.impl("vector_spmm_backward", &vector_spmm_backward);
   m.impl("attention_forward", &attention_forward);
   m.impl("attention_backward", &attention_backward);
+  m.impl("gat_scores_forward", &gat_scores_forward);
+  m.impl("gat_scores_backward", &gat_scores_backward);
 }

@@ -77,6 +77,25 @@ class VectorSPMM(Function):
         return None, None, None, None, None, None, None, None, dedata, dx
 
 
+class GATScores(Function):
+    """GAT additive attention scores s = LeakyReLU(el[i] + er[j]) per edge and head (extra op, not in the reference):
+    apply(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, negative_slope).  el (n_src[, h]),
+    er (n_dst[, h]); s is (E) for one head, else (E, h) -- the edge layout SparseSoftmax and VectorSPMM take.  Saves the
+    CSR arrays, el and er only: the backward recomputes the pre-activation per slot."""
+
+    @staticmethod
+    def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, negative_slope):
+        ctx.save_for_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er)
+        ctx.negative_slope = float(negative_slope)
+        return _ops.gat_scores_forward(row, indptr_r, eid_r, indices_r, el, er, ctx.negative_slope)
+
+    @staticmethod
+    def backward(ctx, grad):
+        a8, (el, er) = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
+        d_el, d_er = _ops.gat_scores_backward(*a8, el, er, grad, ctx.negative_slope)
+        return None, None, None, None, None, None, None, None, d_el, d_er, None
+
+
 # FusedAttention over several heads (round 5): "keep" = per head group only a_g (E x hg) survives the forward, the backward's
 # da_g / ds_g are E x hg temporaries -- speed of the 8-function step, about half of its E-sized memory; "recompute" = nothing
 # E-sized survives the forward, the backward recomputes s_g and a_g per group (two more passes per group: ~+17 % time,
@@ -238,4 +257,17 @@ def attention_step(g, Q, K, V, dO):
     # a device-side abort (include/graphop_hip.h: graphop_check_device_errors) of a launch that has already finished is
     # raised HERE, before the gradients leave the step; one still in flight is sticky and fails the next op call
     _lib.check_errors(sync=False)
+    return s, a, o
+
+
+def gat_attention_step(g, el, er, V, dO, negative_slope=0.2):
+    """One fwd+bwd of GAT-style additive attention, the counterpart of attention_step:
+    s = LeakyReLU(el[i] + er[j]); a = row-softmax(s); o = SpMM(a, V); o.backward(dO).
+    el, er, V must be leaf tensors with requires_grad; returns (s, a, o)."""
+    args = g.csr_args()
+    s = GATScores.apply(*args, el, er, negative_slope)
+    a = SparseSoftmax.apply(g.row, g.ptr_r, g.eid_r, s)
+    o = VectorSPMM.apply(*args, a, V)
+    o.backward(dO)
+    _lib.check_errors(sync=False)     # as in attention_step
     return s, a, o

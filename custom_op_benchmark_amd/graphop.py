@@ -28,7 +28,9 @@ __all__ = ["maskedmm_csr_forward", "maskedmm_csr_backward", "node_mul_edge_forwa
            "node_mul_edge_backward", "sparse_softmax_forward", "sparse_softmax_backward",
            "vector_spmm_forward", "vector_spmm_backward"]
 # extra ops (not in the reference's module): the fused attention step, SURVEY.md 8f N2
-EXTRA_OPS = ["attention_forward", "attention_backward", "attention_backward_is_fused"]
+# and the GAT additive attention scores (LeakyReLU(el[i] + er[j]) per edge and head)
+EXTRA_OPS = ["attention_forward", "attention_backward", "attention_backward_is_fused", "gat_scores_forward",
+             "gat_scores_backward"]
 
 _NULL = None
 
@@ -329,6 +331,62 @@ def attention_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, in
     return [dQ, dK, dV]
 
 
+# ---- GAT additive attention scores (extra op) ------------------------------------------------------------
+def _gat_heads(el, er, fn):
+    """h of the (n_src[, h]) / (n_dst[, h]) per-node score tables; they must agree in dtype and h."""
+    _same_dtype(el, er, "el", "er")
+    if el.dim() not in (1, 2) or er.dim() != el.dim() or (el.dim() == 2 and el.size(1) != er.size(1)):
+        raise RuntimeError("%s: el (n_src[, h]) and er (n_dst[, h]) must have the same h, got %s and %s"
+                           % (fn, tuple(el.shape), tuple(er.shape)))
+    return 1 if el.dim() == 1 else el.size(1)
+
+
+def gat_scores_forward(row, indptr, eid, indices, el, er, negative_slope=0.2):
+    """y[eid[j], k] = LeakyReLU(el[row[c], k] + er[indices[j], k], negative_slope); y is (e) if h == 1 else (e, h)"""
+    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices"), (el, "el"), (er, "er")):
+        _check_input(t, n)
+    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices")):
+        _check_index(t, n)
+    h = _gat_heads(el, er, "gat_scores_forward")
+    e = eid.size(0)
+    y = torch.empty((e,) if h == 1 else (e, h), dtype=el.dtype, device=el.device)
+    with _lib.device_guard(el.device):
+        plan = _plan(row, indptr, eid, indices, er.size(0))
+        check(lib().graphop_gat_scores_forward(
+            dtype_code(el), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(el), ptr(er), ptr(y), row.size(0), e,
+            el.size(0), er.size(0), h, float(negative_slope), plan.handle, stream_of(el)))
+    return y
+
+
+def gat_scores_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, dy,
+                        negative_slope=0.2):
+    """-> [del, der] of gat_scores_forward for the score gradient dy (z is recomputed from el and er)"""
+    names = ("row", "indptr_r", "eid_r", "indices_r", "col", "indptr_c", "eid_c", "indices_c")
+    idx = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
+    for t, n in zip(idx + (el, er), names + ("el", "er")):
+        _check_input(t, n)
+    for t, n in zip(idx, names):
+        _check_index(t, n)
+    if not isinstance(dy, torch.Tensor) or not dy.is_cuda:
+        raise RuntimeError("dy must be a CUDA tensor")
+    h = _gat_heads(el, er, "gat_scores_backward")
+    _same_dtype(el, dy, "el", "dy")
+    dy = dy.contiguous()
+    e = eid_r.size(0)
+    if dy.numel() != e * h:
+        raise RuntimeError("gat_scores_backward: dy must hold (n_edges, h) = (%d, %d) values, got %s"
+                           % (e, h, tuple(dy.shape)))
+    d_el, d_er = torch.empty_like(el), torch.empty_like(er)
+    with _lib.device_guard(el.device):
+        plan_r = _plan(row, indptr_r, eid_r, indices_r, er.size(0))
+        plan_c = _plan(col, indptr_c, eid_c, indices_c, el.size(0))
+        check(lib().graphop_gat_scores_backward(
+            dtype_code(el), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c),
+            ptr(eid_c), ptr(indices_c), ptr(el), ptr(er), ptr(dy), ptr(d_el), ptr(d_er), row.size(0), col.size(0),
+            e, el.size(0), er.size(0), h, float(negative_slope), plan_r.handle, plan_c.handle, stream_of(el)))
+    return [d_el, d_er]
+
+
 def prepare(graph, h=1, d=64, dtype=torch.float32, fused=True):
     """Build a graph's plans and window structures ahead of the first op call (see graphs.prepare)."""
     from . import graphs
@@ -353,6 +411,8 @@ _SCHEMAS = {
     "vector_spmm_backward": "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor col, Tensor indptr_t, Tensor eid_t, Tensor indices_t, Tensor edata, Tensor dy, Tensor x) -> Tensor[]",
     "attention_forward": "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor Q, Tensor K, Tensor V) -> Tensor[]",
     "attention_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor Q, Tensor K, Tensor V, Tensor o, Tensor stats, Tensor dO) -> Tensor[]",
+    "gat_scores_forward": "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, float negative_slope=0.2) -> Tensor",
+    "gat_scores_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor dy, float negative_slope=0.2) -> Tensor[]",
 }
 _torch_lib = None
 

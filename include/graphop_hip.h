@@ -49,7 +49,7 @@ extern "C" {
 #define GRAPHOP_API
 #endif
 
-#define GRAPHOP_ABI_VERSION 7
+#define GRAPHOP_ABI_VERSION 8
 
 #define GRAPHOP_F32 0
 #define GRAPHOP_F64 1
@@ -366,6 +366,31 @@ GRAPHOP_API int graphop_node_mul_edge_backward(int dtype, const int64_t* row, co
                                    const void* dy, void* dA, void* dB, int64_t n_chunks,
                                    int64_t n_edges, int64_t n_a, int64_t h, int64_t d,
                                    const graphop_plan_t* plan, void* stream);
+
+/* ---- GAT additive attention scores (ABI 8; EXTRA op, not one of the reference's eight) ------------------
+ * gat_scores_forward(row, indptr, eid, indices, el, er, negative_slope) -> y
+ *   y[eid[j], k] = LeakyReLU(el[row[c], k] + er[indices[j], k]),  LeakyReLU(z) = z > 0 ? z : z * negative_slope
+ *   for every slot j of every chunk c (the slot walk of maskedmm_csr_forward); el: (n_l, h), er: (n_r, h) per-node,
+ *   per-head scalars, y: (n_edges, h).  One add and at most one multiply per value: bitwise equal to torch's
+ *   leaky_relu(el[src] + er[dst]) in the same dtype.
+ * gat_scores_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, dy, negative_slope)
+ *   -> [del, der], with g[e, k] = dy[e, k] * (z > 0 ? 1 : negative_slope) and z = el[i, k] + er[j, k] recomputed
+ *   (the tie z == 0 takes the slope, as torch's leaky_relu_backward):
+ *   del[row[c], k] += sum_j g[eid_r[j], k]   (row-major CSR)      der[col[c], k] += sum_j g[eid_c[j], k]   (column-major CSR)
+ *   del may be NULL when n_row_chunks == 0, der when n_col_chunks == 0 (that half is skipped).
+ * With a plan of the same arrays, fp32 and h in {1, 2, 4, 8, 16} take the fast kernels (csrc/kernels_gat.h); NULL
+ * plans, fp64 and other h take the generic ones.  Any chunk layout works on both. */
+GRAPHOP_API int graphop_gat_scores_forward(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                               const int64_t* indices, const void* el, const void* er, void* y, int64_t n_chunks,
+                               int64_t n_edges, int64_t n_l, int64_t n_r, int64_t h, double negative_slope,
+                               const graphop_plan_t* plan, void* stream);
+GRAPHOP_API int graphop_gat_scores_backward(int dtype, const int64_t* row, const int64_t* indptr_r,
+                                const int64_t* eid_r, const int64_t* indices_r, const int64_t* col,
+                                const int64_t* indptr_c, const int64_t* eid_c, const int64_t* indices_c,
+                                const void* el, const void* er, const void* dy, void* del, void* der,
+                                int64_t n_row_chunks, int64_t n_col_chunks, int64_t n_edges, int64_t n_l,
+                                int64_t n_r, int64_t h, double negative_slope, const graphop_plan_t* plan_r,
+                                const graphop_plan_t* plan_c, void* stream);
 
 /* ---- fused attention step (EXTRA op, not one of the reference's eight) --------------------------
  * The composition the reference harness chains by hand -- MaskedMMCSR -> SparseSoftmax -> VectorSPMM
