@@ -1,0 +1,319 @@
+// Fused GAT attention (extra op, not one of the reference's eight; include/graphop_hip.h):
+//   forward : o[i] = sum_j softmax_j(LeakyReLU(el[i] + er[j])) V[j] per head, leaving only o and the row statistics
+//   backward: del, der, dV from (el, er, V, o, stats, dO), a recomputed per slot (kernels_gat_attn.h).
+// No E-sized tensor exists in either direction.  Host-side dispatch in the style of gat.hip: validation, fills, and the
+// choice between the fp32 fast kernels (a plan of the same arrays, h in {1, 2, 4, 8}, d in {8, 16, 32, 64},
+// h * d in {64, 128, 256}) and the generic ones (fp64, other shapes, NULL plans).
+#include "common.h"
+#include "host.h"
+#include "kernels_gat_attn.h"
+
+namespace graphop {
+namespace {
+
+inline int gat_attn_check(const char* fn, int dtype, i64 C, i64 C2, i64 E, i64 n_l, i64 n_r, i64 h, i64 d) {
+  GO_TRY(check_async_error(false));   // a kernel of an earlier launch reported a failure: sticky until acknowledged
+  GO_CHECK_ARG(dtype == GRAPHOP_F32 || dtype == GRAPHOP_F64, "%s: dtype must be GRAPHOP_F32 or GRAPHOP_F64", fn);
+  GO_CHECK_ARG(C >= 0 && C2 >= 0 && E >= 0 && n_l >= 0 && n_r >= 0 && h >= 1 && d >= 1,
+               "%s: negative size (n_chunks=%lld/%lld n_edges=%lld n_l=%lld n_r=%lld h=%lld d=%lld)", fn,
+               (long long)C, (long long)C2, (long long)E, (long long)n_l, (long long)n_r, (long long)h, (long long)d);
+  return GRAPHOP_OK;
+}
+
+inline int gat_attn_check_plan(const char* fn, const graphop_plan* p, const char* seg_name, i64 n_seg,
+                               const char* idx_name, i64 n_idx) {
+  if (!p) return GRAPHOP_OK;
+  GO_CHECK_ARG(p->info.max_row < n_seg, "%s: row id %lld but %s has only %lld rows", fn, (long long)p->info.max_row,
+               seg_name, (long long)n_seg);
+  GO_CHECK_ARG(p->info.max_index < n_idx, "%s: neighbour id %lld but %s has only %lld rows", fn,
+               (long long)p->info.max_index, idx_name, (long long)n_idx);
+  return GRAPHOP_OK;
+}
+
+inline bool a16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// fp32 fast kernels: the (h, d) pairs below, ids that fit 31 bits, 16-byte-aligned tables
+inline bool gat_attn_fast_ok(int dtype, i64 h, i64 d, i64 E, i64 n_l, i64 n_r, std::initializer_list<const void*> ps) {
+  if (tuning().force_generic || dtype != GRAPHOP_F32) return false;
+  if (h != 1 && h != 2 && h != 4 && h != 8) return false;
+  if (d != 8 && d != 16 && d != 32 && d != 64) return false;
+  if (h * d != 64 && h * d != 128 && h * d != 256) return false;
+  if (E >= 0x7fffffffLL || n_l >= 0x7fffffffLL || n_r >= 0x7fffffffLL) return false;
+  for (const void* p : ps)
+    if (!a16(p)) return false;
+  return true;
+}
+
+#define GO_DISPATCH_GAT_ATTN(h, d, ...)                                 \
+  switch ((int)((h) * 1000 + (d))) {                                    \
+    case 1064: { constexpr int H = 1, D = 64; __VA_ARGS__; } break;     \
+    case 2032: { constexpr int H = 2, D = 32; __VA_ARGS__; } break;     \
+    case 2064: { constexpr int H = 2, D = 64; __VA_ARGS__; } break;     \
+    case 4016: { constexpr int H = 4, D = 16; __VA_ARGS__; } break;     \
+    case 4032: { constexpr int H = 4, D = 32; __VA_ARGS__; } break;     \
+    case 4064: { constexpr int H = 4, D = 64; __VA_ARGS__; } break;     \
+    case 8008: { constexpr int H = 8, D = 8; __VA_ARGS__; } break;      \
+    case 8016: { constexpr int H = 8, D = 16; __VA_ARGS__; } break;     \
+    case 8032: { constexpr int H = 8, D = 32; __VA_ARGS__; } break;     \
+    default: break;                                                     \
+  }
+
+#define GO_DISPATCH_GAT_ATTN_H(h, ...)                  \
+  switch ((int)(h)) {                                   \
+    case 1: { constexpr int H = 1; __VA_ARGS__; } break; \
+    case 2: { constexpr int H = 2; __VA_ARGS__; } break; \
+    case 4: { constexpr int H = 4; __VA_ARGS__; } break; \
+    case 8: { constexpr int H = 8; __VA_ARGS__; } break; \
+    default: break;                                     \
+  }
+
+// chunks per lane group: up to the SpMM cap on big graphs, fewer on small ones so every CU still gets groups
+inline int gat_attn_cpg(i64 n_chunks) {
+  constexpr int G = 16;
+  const i64 groups_wanted = (i64)tuning().n_cu * (kFastBlock / G) * 8;
+  i64 c = n_chunks / (groups_wanted > 0 ? groups_wanted : 1);
+  if (c < 1) c = 1;
+  const int cap = tuning().spmm_cpg > 0 ? tuning().spmm_cpg : 16;
+  return (int)(c < cap ? c : cap);
+}
+
+inline unsigned grid_of(i64 n) {
+  const i64 b = ceil_div(n, 256);
+  return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
+}
+
+// stats = (m, 1 / l) per (row, head); rows without slots keep (-1e9, 0)
+int gat_attn_stats(int dtype, const i64* row, const i64* indptr, const i64* indices, const void* el, const void* er,
+                   void* stats, i64 C, i64 n_l, i64 h, double slope, const graphop_plan* pm, bool fast,
+                   hipStream_t st) {
+  auto init = [&](auto zero) {
+    using T = decltype(zero);
+    hipLaunchKernelGGL((k_gat_attn_stats_init_generic<T>), dim3(grid_of(n_l * h)), dim3(256), 0, st, (T*)stats,
+                       n_l * h);
+  };
+  if (dtype == GRAPHOP_F32) init(0.f); else init(0.0);
+  GO_LAUNCH_CHECK();
+  if (C == 0) return GRAPHOP_OK;
+  if (fast && pm->info.row_owned && pm->seg_chunk) {
+    const i64 S = pm->info.n_segments;
+    if (S == 0) return GRAPHOP_OK;
+    ProfScope prof("gat_attn_stats", st, "k_gat_attn_stats_f32");
+    const int n_long = (int)pm->n_long;
+    const i64 long_len = n_long > 0 ? kLongSegment : ((i64)1 << 62);
+    const bool wide = pm->info.n_edges / S >= 64;   // long rows on average: a wave per segment
+    GO_DISPATCH_GAT_ATTN_H(h, {
+      {
+        const int G = wide ? 64 : 16;
+        const unsigned nbs = (unsigned)ceil_div(S, kFastBlock / G);
+        const dim3 grid(nbs + (unsigned)n_long);
+        if (wide)
+          hipLaunchKernelGGL((k_gat_attn_stats_f32<H, 64>), grid, dim3(kFastBlock), 0, st, row, indptr, indices,
+                             (const i64*)pm->seg_chunk, (const float*)el, (const float*)er, (float2*)stats, S, nbs,
+                             long_len, (const int*)pm->long_segs, (float)slope);
+        else
+          hipLaunchKernelGGL((k_gat_attn_stats_f32<H, 16>), grid, dim3(kFastBlock), 0, st, row, indptr, indices,
+                             (const i64*)pm->seg_chunk, (const float*)el, (const float*)er, (float2*)stats, S, nbs,
+                             long_len, (const int*)pm->long_segs, (float)slope);
+      }
+    });
+    GO_LAUNCH_CHECK();
+    return GRAPHOP_OK;
+  }
+  ProfScope prof("gat_attn_stats", st, "k_gat_attn_stats_generic");
+  const unsigned nb = (unsigned)ceil_div(C, kGenericWavesPerBlock);
+  auto go = [&](auto zero) {
+    using T = decltype(zero);
+    hipLaunchKernelGGL((k_gat_attn_stats_generic<T, false>), dim3(nb), dim3(kGenericBlock), 0, st, row, indptr,
+                       indices, (const T*)el, (const T*)er, (T*)stats, C, h, (T)slope);
+    hipLaunchKernelGGL((k_gat_attn_stats_generic<T, true>), dim3(nb), dim3(kGenericBlock), 0, st, row, indptr,
+                       indices, (const T*)el, (const T*)er, (T*)stats, C, h, (T)slope);
+    hipLaunchKernelGGL((k_gat_attn_stats_fin_generic<T>), dim3(grid_of(n_l * h)), dim3(256), 0, st, (T*)stats,
+                       n_l * h);
+  };
+  if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+  GO_LAUNCH_CHECK();
+  return GRAPHOP_OK;
+}
+
+}  // namespace
+}  // namespace graphop
+
+using namespace graphop;
+
+extern "C" {
+
+int graphop_gat_attention_forward(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                                  const int64_t* indices, const void* el, const void* er, const void* V, void* o,
+                                  void* stats, int64_t n_chunks, int64_t n_edges, int64_t n_l, int64_t n_r,
+                                  int64_t h, int64_t d, double negative_slope, const graphop_plan_t* plan,
+                                  void* stream) {
+  const char* fn = "gat_attention_forward";
+  GO_TRY(gat_attn_check(fn, dtype, n_chunks, 0, n_edges, n_l, n_r, h, d));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t es = esize(dtype);
+  const graphop_plan* pm = plan_matches_full(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
+                                             (const i64*)indices, n_chunks, n_edges) ? plan : nullptr;
+  GO_TRY(gat_attn_check_plan(fn, pm, "el / o", n_l, "er / V", n_r));
+  if (n_l == 0) return GRAPHOP_OK;
+  GO_PTR(fn, o); GO_PTR(fn, stats);
+  GO_HIP(zero_async(o, es * (size_t)(n_l * h * d), st));
+  const bool slots = n_chunks > 0 && n_edges > 0;
+  if (slots) {
+    GO_PTR(fn, row); GO_PTR(fn, indptr); GO_PTR(fn, eid); GO_PTR(fn, indices);
+    GO_PTR(fn, el); GO_PTR(fn, er); GO_PTR(fn, V);
+  }
+  const bool fast = pm && gat_attn_fast_ok(dtype, h, d, n_edges, n_l, n_r, {el, er, V, o, stats});
+  GO_TRY(gat_attn_stats(dtype, (const i64*)row, (const i64*)indptr, (const i64*)indices, el, er, stats,
+                        slots ? n_chunks : 0, n_l, h, negative_slope, pm, fast, st));
+  if (!slots) return GRAPHOP_OK;
+  if (fast) {
+    ProfScope prof("gat_attn_fwd", st, "k_gat_attn_fwd_f32");
+    const int cpg = gat_attn_cpg(n_chunks);
+    const unsigned nb = (unsigned)ceil_div(ceil_div(n_chunks, cpg), kFastBlock / 16);
+    const bool owned = pm->info.rows_sorted != 0;
+    GO_DISPATCH_GAT_ATTN(h, d, {
+      if (owned)
+        hipLaunchKernelGGL((k_gat_attn_fwd_f32<H, D, true>), dim3(nb), dim3(kFastBlock), 0, st, (const i64*)row,
+                           (const i64*)indptr, (const i64*)indices, (const float*)el, (const float*)er,
+                           (const float2*)stats, (const float*)V, (float*)o, n_chunks, cpg, (float)negative_slope);
+      else
+        hipLaunchKernelGGL((k_gat_attn_fwd_f32<H, D, false>), dim3(nb), dim3(kFastBlock), 0, st, (const i64*)row,
+                           (const i64*)indptr, (const i64*)indices, (const float*)el, (const float*)er,
+                           (const float2*)stats, (const float*)V, (float*)o, n_chunks, cpg, (float)negative_slope);
+    });
+  } else {
+    ProfScope prof("gat_attn_fwd", st, "k_gat_attn_fwd_generic");
+    const unsigned nb = (unsigned)ceil_div(n_chunks, kGenericWavesPerBlock);
+    auto go = [&](auto zero) {
+      using T = decltype(zero);
+      hipLaunchKernelGGL((k_gat_attn_fwd_generic<T>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)row,
+                         (const i64*)indptr, (const i64*)indices, (const T*)el, (const T*)er, (const T*)stats,
+                         (const T*)V, (T*)o, n_chunks, h, d, (T)negative_slope);
+    };
+    if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+  }
+  GO_LAUNCH_CHECK();
+  return GRAPHOP_OK;
+}
+
+int graphop_gat_attention_backward(int dtype, const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r,
+                                   const int64_t* indices_r, const int64_t* col, const int64_t* indptr_c,
+                                   const int64_t* eid_c, const int64_t* indices_c, const void* el, const void* er,
+                                   const void* V, const void* o, const void* stats, const void* dO, void* del,
+                                   void* der, void* dV, void* workspace, int64_t workspace_bytes,
+                                   int64_t n_row_chunks, int64_t n_col_chunks, int64_t n_edges, int64_t n_l,
+                                   int64_t n_r, int64_t h, int64_t d, double negative_slope,
+                                   const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream) {
+  const char* fn = "gat_attention_backward";
+  GO_TRY(gat_attn_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_l, n_r, h, d));
+  hipStream_t st = (hipStream_t)stream;
+  const size_t es = esize(dtype);
+  const bool slots = n_edges > 0 && (n_row_chunks > 0 || n_col_chunks > 0);
+  const size_t need = slots ? es * 4 * (size_t)(n_l * h) : 0;   // P: (n_l, h, 4)
+  GO_CHECK_ARG(workspace_bytes >= 0 && (size_t)workspace_bytes >= need,
+               "%s: workspace of %lld bytes needed (n_l * h * 4 values), got %lld", fn, (long long)need,
+               (long long)workspace_bytes);
+  const graphop_plan* pr = plan_matches_full(plan_r, (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r,
+                                             (const i64*)indices_r, n_row_chunks, n_edges) ? plan_r : nullptr;
+  const graphop_plan* pc = plan_matches_full(plan_c, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c,
+                                             (const i64*)indices_c, n_col_chunks, n_edges) ? plan_c : nullptr;
+  GO_TRY(gat_attn_check_plan(fn, pr, "el / del", n_l, "er / V", n_r));
+  GO_TRY(gat_attn_check_plan(fn, pc, "er / der", n_r, "el", n_l));
+  if (n_l > 0 && !(del == nullptr && n_row_chunks == 0)) {
+    GO_PTR(fn, del);
+    GO_HIP(zero_async(del, es * (size_t)(n_l * h), st));
+  }
+  if (n_r > 0 && !(der == nullptr && dV == nullptr && n_col_chunks == 0)) {
+    GO_PTR(fn, der); GO_PTR(fn, dV);
+    GO_HIP(zero_async(der, es * (size_t)(n_r * h), st));
+    GO_HIP(zero_async(dV, es * (size_t)(n_r * h * d), st));
+  }
+  if (!slots || n_l == 0 || n_r == 0) return GRAPHOP_OK;
+  GO_PTR(fn, el); GO_PTR(fn, er); GO_PTR(fn, V); GO_PTR(fn, o); GO_PTR(fn, stats); GO_PTR(fn, dO);
+  GO_PTR(fn, workspace);
+  const bool ok = gat_attn_fast_ok(dtype, h, d, n_edges, n_l, n_r, {el, er, V, o, stats, dO, workspace, dV});
+  const float slope = (float)negative_slope;
+  const int G = 16;
+  {   // P[i, k] = (el, m, 1/l, D)
+    const bool fast = ok && (pr || pc);
+    ProfScope prof("gat_attn_pack", st, fast ? "k_gat_attn_pack_f32" : "k_gat_attn_pack_generic");
+    if (fast) {
+      GO_DISPATCH_GAT_ATTN(h, d, {
+        hipLaunchKernelGGL((k_gat_attn_pack_f32<H, D>), dim3((unsigned)ceil_div(n_l, kFastBlock / G)),
+                           dim3(kFastBlock), 0, st, (const float*)el, (const float2*)stats, (const float*)dO,
+                           (const float*)o, (float4*)workspace, n_l);
+      });
+    } else {
+      auto go = [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL((k_gat_attn_pack_generic<T>), dim3(grid_of(n_l * h)), dim3(256), 0, st, (const T*)el,
+                           (const T*)stats, (const T*)dO, (const T*)o, (T*)workspace, n_l * h, d);
+      };
+      if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+    }
+    GO_LAUNCH_CHECK();
+  }
+  if (n_row_chunks > 0) {
+    GO_PTR(fn, row); GO_PTR(fn, indptr_r); GO_PTR(fn, eid_r); GO_PTR(fn, indices_r);
+    const i64 C = n_row_chunks;
+    if (ok && pr) {
+      ProfScope prof("gat_attn_bwd_row", st, "k_gat_attn_bwd_row_f32");
+      const int cpg = gat_attn_cpg(C);
+      const unsigned nb = (unsigned)ceil_div(ceil_div(C, cpg), kFastBlock / G);
+      GO_DISPATCH_GAT_ATTN(h, d, {
+        if (pr->info.rows_sorted)
+          hipLaunchKernelGGL((k_gat_attn_bwd_row_f32<H, D, true>), dim3(nb), dim3(kFastBlock), 0, st, (const i64*)row,
+                             (const i64*)indptr_r, (const i64*)indices_r, (const float*)er, (const float*)V,
+                             (const float4*)workspace, (const float*)dO, (float*)del, C, cpg, slope);
+        else
+          hipLaunchKernelGGL((k_gat_attn_bwd_row_f32<H, D, false>), dim3(nb), dim3(kFastBlock), 0, st, (const i64*)row,
+                             (const i64*)indptr_r, (const i64*)indices_r, (const float*)er, (const float*)V,
+                             (const float4*)workspace, (const float*)dO, (float*)del, C, cpg, slope);
+      });
+    } else {
+      ProfScope prof("gat_attn_bwd_row", st, "k_gat_attn_bwd_row_generic");
+      auto go = [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL((k_gat_attn_bwd_row_generic<T>), dim3((unsigned)ceil_div(C, kGenericWavesPerBlock)),
+                           dim3(kGenericBlock), 0, st, (const i64*)row, (const i64*)indptr_r, (const i64*)indices_r,
+                           (const T*)er, (const T*)V, (const T*)workspace, (const T*)dO, (T*)del, C, h, d,
+                           (T)negative_slope);
+      };
+      if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+    }
+    GO_LAUNCH_CHECK();
+  }
+  if (n_col_chunks > 0) {
+    GO_PTR(fn, col); GO_PTR(fn, indptr_c); GO_PTR(fn, eid_c); GO_PTR(fn, indices_c);
+    const i64 C = n_col_chunks;
+    if (ok && pc) {
+      ProfScope prof("gat_attn_bwd_col", st, "k_gat_attn_bwd_col_f32");
+      const int cpg = gat_attn_cpg(C);
+      const unsigned nb = (unsigned)ceil_div(ceil_div(C, cpg), kFastBlock / G);
+      GO_DISPATCH_GAT_ATTN(h, d, {
+        if (pc->info.rows_sorted)
+          hipLaunchKernelGGL((k_gat_attn_bwd_col_f32<H, D, true>), dim3(nb), dim3(kFastBlock), 0, st, (const i64*)col,
+                             (const i64*)indptr_c, (const i64*)indices_c, (const float*)er, (const float*)V,
+                             (const float4*)workspace, (const float*)dO, (float*)der, (float*)dV, C, cpg, slope);
+        else
+          hipLaunchKernelGGL((k_gat_attn_bwd_col_f32<H, D, false>), dim3(nb), dim3(kFastBlock), 0, st, (const i64*)col,
+                             (const i64*)indptr_c, (const i64*)indices_c, (const float*)er, (const float*)V,
+                             (const float4*)workspace, (const float*)dO, (float*)der, (float*)dV, C, cpg, slope);
+      });
+    } else {
+      ProfScope prof("gat_attn_bwd_col", st, "k_gat_attn_bwd_col_generic");
+      auto go = [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL((k_gat_attn_bwd_col_generic<T>), dim3((unsigned)ceil_div(C, kGenericWavesPerBlock)),
+                           dim3(kGenericBlock), 0, st, (const i64*)col, (const i64*)indptr_c, (const i64*)indices_c,
+                           (const T*)er, (const T*)V, (const T*)workspace, (const T*)dO, (T*)der, (T*)dV, C, h, d,
+                           (T)negative_slope);
+      };
+      if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+    }
+    GO_LAUNCH_CHECK();
+  }
+  return GRAPHOP_OK;
+}
+
+}  // extern "C"

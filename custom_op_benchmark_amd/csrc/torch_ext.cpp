@@ -442,6 +442,78 @@ std::vector<at::Tensor> gat_scores_backward(const at::Tensor& row, const at::Ten
   return {d_el, d_er};
 }
 
+// ---- the fused GAT attention op (include/graphop_hip.h: graphop_gat_attention_*) -----------------------------------
+std::pair<int64_t, int64_t> gat_attn_shapes(const at::Tensor& el, const at::Tensor& er, const at::Tensor& V,
+                                            const char* fn) {
+  const int64_t h = gat_heads(el, er, fn);
+  CHECK_SAME_DTYPE(el, V);
+  TORCH_CHECK(V.dim() == (el.dim() == 1 ? 2 : 3) && (V.dim() == 2 || V.size(1) == h) && V.size(0) == er.size(0), fn,
+              ": V must be (n_dst, d) for 1-D el / er, else (n_dst, h, d) with the same h and n_dst as er, got V ",
+              V.sizes(), ", er ", er.sizes());
+  return {h, V.size(-1)};
+}
+
+std::vector<at::Tensor> gat_attention_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
+                                              const at::Tensor& indices, const at::Tensor& el, const at::Tensor& er,
+                                              const at::Tensor& V, double negative_slope) {
+  CHECK_INPUT(row); CHECK_INPUT(indptr); CHECK_INPUT(eid); CHECK_INPUT(indices); CHECK_INPUT(el); CHECK_INPUT(er);
+  CHECK_INPUT(V);
+  CHECK_INDEX(row); CHECK_INDEX(indptr); CHECK_INDEX(eid); CHECK_INDEX(indices);
+  const auto hd = gat_attn_shapes(el, er, V, "gat_attention_forward");
+  const int64_t h = hd.first, d = hd.second;
+  DeviceGuard dg(el);
+  const int64_t e = eid.size(0), n_l = el.size(0);
+  std::vector<int64_t> oshape(V.sizes().begin(), V.sizes().end());
+  oshape[0] = n_l;
+  auto o = at::empty(oshape, V.options());
+  auto stats = at::empty({n_l, h, 2}, el.options());
+  const auto pp = get_plan(row, indptr, eid, indices, er.size(0));
+  const auto& p = *pp;
+  check(graphop_gat_attention_forward(dtype_code(el), ip(row), ip(indptr), ip(eid), ip(indices), vp(el), vp(er), vp(V),
+                                      vp(o), vp(stats), row.size(0), e, n_l, er.size(0), h, d, negative_slope, p.plan,
+                                      stream_of(el)));
+  return {o, stats};
+}
+
+std::vector<at::Tensor> gat_attention_backward(const at::Tensor& row, const at::Tensor& indptr_r,
+                                               const at::Tensor& eid_r, const at::Tensor& indices_r,
+                                               const at::Tensor& col, const at::Tensor& indptr_c,
+                                               const at::Tensor& eid_c, const at::Tensor& indices_c,
+                                               const at::Tensor& el, const at::Tensor& er, const at::Tensor& V,
+                                               const at::Tensor& o, const at::Tensor& stats, const at::Tensor& dO_,
+                                               double negative_slope) {
+  CHECK_INPUT(row); CHECK_INPUT(indptr_r); CHECK_INPUT(eid_r); CHECK_INPUT(indices_r);
+  CHECK_INPUT(col); CHECK_INPUT(indptr_c); CHECK_INPUT(eid_c); CHECK_INPUT(indices_c); CHECK_INPUT(el); CHECK_INPUT(er);
+  CHECK_INPUT(V); CHECK_INPUT(o); CHECK_INPUT(stats);
+  CHECK_INDEX(row); CHECK_INDEX(indptr_r); CHECK_INDEX(eid_r); CHECK_INDEX(indices_r);
+  CHECK_INDEX(col); CHECK_INDEX(indptr_c); CHECK_INDEX(eid_c); CHECK_INDEX(indices_c);
+  CHECK_CUDA(dO_);
+  const auto hd = gat_attn_shapes(el, er, V, "gat_attention_backward");
+  const int64_t h = hd.first, d = hd.second;
+  CHECK_SAME_DTYPE(el, o); CHECK_SAME_DTYPE(el, stats); CHECK_SAME_DTYPE(el, dO_);
+  const int64_t n_l = el.size(0);
+  std::vector<int64_t> oshape(V.sizes().begin(), V.sizes().end());
+  oshape[0] = n_l;
+  TORCH_CHECK(o.sizes() == at::IntArrayRef(oshape) && stats.numel() == n_l * h * 2,
+              "gat_attention_backward: o must be ", at::IntArrayRef(oshape), " and stats (n_src, h, 2), got ", o.sizes(),
+              " and ", stats.sizes());
+  const at::Tensor dO = dO_.contiguous();
+  TORCH_CHECK(dO.sizes() == o.sizes(), "gat_attention_backward: dO must match o ", o.sizes(), ", got ", dO.sizes());
+  DeviceGuard dg(el);
+  const int64_t e = eid_r.size(0);
+  auto d_el = at::empty_like(el), d_er = at::empty_like(er), dV = at::empty_like(V);
+  auto ws = at::empty({std::max<int64_t>(n_l * h * 4, 1)}, el.options());   // (el, m, 1 / l, D) per (node, head)
+  const auto ppr = get_plan(row, indptr_r, eid_r, indices_r, er.size(0));
+  const auto ppc = get_plan(col, indptr_c, eid_c, indices_c, n_l);
+  const auto &pr = *ppr, &pc = *ppc;
+  check(graphop_gat_attention_backward(dtype_code(el), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col),
+                                       ip(indptr_c), ip(eid_c), ip(indices_c), vp(el), vp(er), vp(V), vp(o), vp(stats),
+                                       vp(dO), vp(d_el), vp(d_er), vp(dV), vp(ws), ws.numel() * ws.element_size(),
+                                       row.size(0), col.size(0), e, n_l, er.size(0), h, d, negative_slope, pr.plan,
+                                       pc.plan, stream_of(el)));
+  return {d_el, d_er, dV};
+}
+
 void clear_plan_cache() {
   std::vector<PlanRef> dead;
   {
@@ -491,6 +563,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gat_scores_backward", &gat_scores_backward, "GAT additive attention scores backward (extra op)", py::arg("row"),
         py::arg("indptr_r"), py::arg("eid_r"), py::arg("indices_r"), py::arg("col"), py::arg("indptr_c"), py::arg("eid_c"),
         py::arg("indices_c"), py::arg("el"), py::arg("er"), py::arg("dy"), py::arg("negative_slope") = 0.2);
+  m.def("gat_attention_forward", &gat_attention_forward, "Fused GAT attention forward (extra op)", py::arg("row"),
+        py::arg("indptr"), py::arg("eid"), py::arg("indices"), py::arg("el"), py::arg("er"), py::arg("V"),
+        py::arg("negative_slope") = 0.2);
+  m.def("gat_attention_backward", &gat_attention_backward, "Fused GAT attention backward (extra op)", py::arg("row"),
+        py::arg("indptr_r"), py::arg("eid_r"), py::arg("indices_r"), py::arg("col"), py::arg("indptr_c"), py::arg("eid_c"),
+        py::arg("indices_c"), py::arg("el"), py::arg("er"), py::arg("V"), py::arg("o"), py::arg("stats"), py::arg("dO"),
+        py::arg("negative_slope") = 0.2);
   m.def("clear_plan_cache", &clear_plan_cache, "Destroy every cached per-graph plan");
   m.def("release_plans", &release_plans, "Drop the cached plans of the orientation whose chunk list is `row`");
   m.def("plan_cache_size", &plan_cache_size, "Graph orientations in the plan cache");
@@ -510,6 +589,8 @@ TORCH_LIBRARY(graphop, m) {
   m.def("attention_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor Q, Tensor K, Tensor V, Tensor o, Tensor stats, Tensor dO) -> Tensor[]");
   m.def("gat_scores_forward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, float negative_slope=0.2) -> Tensor");
   m.def("gat_scores_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor dy, float negative_slope=0.2) -> Tensor[]");
+  m.def("gat_attention_forward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, Tensor V, float negative_slope=0.2) -> Tensor[]");
+  m.def("gat_attention_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor V, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2) -> Tensor[]");
 }
 
 TORCH_LIBRARY_IMPL(graphop, CUDA, m) {
@@ -525,6 +606,8 @@ TORCH_LIBRARY_IMPL(graphop, CUDA, m) {
   m.impl("attention_backward", &attention_backward);
   m.impl("gat_scores_forward", &gat_scores_forward);
   m.impl("gat_scores_backward", &gat_scores_backward);
+  m.impl("gat_attention_forward", &gat_attention_forward);
+  m.impl("gat_attention_backward", &gat_attention_backward);
 }
 
 TORCH_LIBRARY_IMPL(graphop, CPU, m) {   // there is no CPU implementation: the reference's CHECK_CUDA message
@@ -540,4 +623,6 @@ TORCH_LIBRARY_IMPL(graphop, CPU, m) {   // there is no CPU implementation: the r
   m.impl("attention_backward", &attention_backward);
   m.impl("gat_scores_forward", &gat_scores_forward);
   m.impl("gat_scores_backward", &gat_scores_backward);
+  m.impl("gat_attention_forward", &gat_attention_forward);
+  m.impl("gat_attention_backward", &gat_attention_backward);
 }

@@ -96,6 +96,26 @@ class GATScores(Function):
         return None, None, None, None, None, None, None, None, d_el, d_er, None
 
 
+class FusedGATAttention(Function):
+    """o = VectorSPMM(SparseSoftmax(GATScores(el, er)), V) as ONE autograd node (extra op, not in the reference):
+    apply(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V, negative_slope).  el (n_src[, h]),
+    er (n_dst[, h]), V (n_dst, d) for one head, else (n_dst, h, d); o has n_src rows in V's layout.  Saves (el, er, V, o,
+    row statistics) instead of any (E, h) tensor; the backward recomputes the attention weights per slot."""
+
+    @staticmethod
+    def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V, negative_slope):
+        o, stats = _ops.gat_attention_forward(row, indptr_r, eid_r, indices_r, el, er, V, float(negative_slope))
+        ctx.save_for_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V, o, stats)
+        ctx.negative_slope = float(negative_slope)
+        return o
+
+    @staticmethod
+    def backward(ctx, dO):
+        a8, (el, er, V, o, stats) = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
+        d_el, d_er, dV = _ops.gat_attention_backward(*a8, el, er, V, o, stats, dO, ctx.negative_slope)
+        return None, None, None, None, None, None, None, None, d_el, d_er, dV, None
+
+
 # FusedAttention over several heads (round 5): "keep" = per head group only a_g (E x hg) survives the forward, the backward's
 # da_g / ds_g are E x hg temporaries -- speed of the 8-function step, about half of its E-sized memory; "recompute" = nothing
 # E-sized survives the forward, the backward recomputes s_g and a_g per group (two more passes per group: ~+17 % time,
@@ -271,3 +291,12 @@ def gat_attention_step(g, el, er, V, dO, negative_slope=0.2):
     o.backward(dO)
     _lib.check_errors(sync=False)     # as in attention_step
     return s, a, o
+
+
+def fused_gat_attention_step(g, el, er, V, dO, negative_slope=0.2):
+    """The counterpart of gat_attention_step through FusedGATAttention: o = GAT layer(el, er, V); o.backward(dO).
+    el, er, V must be leaf tensors with requires_grad; returns o (no E-sized tensor is kept or made)."""
+    o = FusedGATAttention.apply(*g.csr_args(), el, er, V, negative_slope)
+    o.backward(dO)
+    _lib.check_errors(sync=False)     # as in attention_step
+    return o

@@ -28,9 +28,9 @@ __all__ = ["maskedmm_csr_forward", "maskedmm_csr_backward", "node_mul_edge_forwa
            "node_mul_edge_backward", "sparse_softmax_forward", "sparse_softmax_backward",
            "vector_spmm_forward", "vector_spmm_backward"]
 # extra ops (not in the reference's module): the fused attention step, SURVEY.md 8f N2
-# and the GAT additive attention scores (LeakyReLU(el[i] + er[j]) per edge and head)
+# the GAT additive attention scores (LeakyReLU(el[i] + er[j]) per edge and head) and the fused GAT attention layer
 EXTRA_OPS = ["attention_forward", "attention_backward", "attention_backward_is_fused", "gat_scores_forward",
-             "gat_scores_backward"]
+             "gat_scores_backward", "gat_attention_forward", "gat_attention_backward"]
 
 _NULL = None
 
@@ -387,6 +387,72 @@ def gat_scores_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, i
     return [d_el, d_er]
 
 
+# ---- fused GAT attention (extra op) -----------------------------------------------------------------------------
+def _gat_attn_shapes(el, er, V, fn):
+    """(h, d) of the fused GAT layer: V is (n_dst, d) with 1-D el / er, else (n_dst, h, d), in their dtype."""
+    h = _gat_heads(el, er, fn)
+    _same_dtype(el, V, "el", "V")
+    if V.dim() != (2 if el.dim() == 1 else 3) or (V.dim() == 3 and V.size(1) != h) or V.size(0) != er.size(0):
+        raise RuntimeError("%s: V must be (n_dst, d) for 1-D el / er, else (n_dst, h, d) with the same h and n_dst as er, "
+                           "got V %s, er %s" % (fn, tuple(V.shape), tuple(er.shape)))
+    return h, V.size(-1)
+
+
+def gat_attention_forward(row, indptr, eid, indices, el, er, V, negative_slope=0.2):
+    """-> [o, stats]: o[i] = sum_j softmax_j(LeakyReLU(el[i] + er[j])) V[j] per head over the row-major CSR, without
+    any E-sized tensor; o has n_src = el.size(0) rows in V's layout, stats (n_src, h, 2) = (row max, 1 / sum exp)."""
+    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices"), (el, "el"), (er, "er"),
+                 (V, "V")):
+        _check_input(t, n)
+    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices")):
+        _check_index(t, n)
+    h, d = _gat_attn_shapes(el, er, V, "gat_attention_forward")
+    e, n_l = eid.size(0), el.size(0)
+    o = torch.empty((n_l,) + tuple(V.shape[1:]), dtype=V.dtype, device=V.device)
+    stats = torch.empty((n_l, h, 2), dtype=el.dtype, device=el.device)
+    with _lib.device_guard(el.device):
+        plan = _plan(row, indptr, eid, indices, er.size(0))
+        check(lib().graphop_gat_attention_forward(
+            dtype_code(el), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(el), ptr(er), ptr(V), ptr(o),
+            ptr(stats), row.size(0), e, n_l, er.size(0), h, d, float(negative_slope), plan.handle, stream_of(el)))
+    return [o, stats]
+
+
+def gat_attention_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V, o, stats,
+                           dO, negative_slope=0.2):
+    """-> [del, der, dV] of gat_attention_forward for the output gradient dO (a recomputed per slot from stats)."""
+    names = ("row", "indptr_r", "eid_r", "indices_r", "col", "indptr_c", "eid_c", "indices_c")
+    idx = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
+    for t, n in zip(idx + (el, er, V, o, stats), names + ("el", "er", "V", "o", "stats")):
+        _check_input(t, n)
+    for t, n in zip(idx, names):
+        _check_index(t, n)
+    if not isinstance(dO, torch.Tensor) or not dO.is_cuda:
+        raise RuntimeError("dO must be a CUDA tensor")
+    h, d = _gat_attn_shapes(el, er, V, "gat_attention_backward")
+    for t, n in ((o, "o"), (stats, "stats"), (dO, "dO")):
+        _same_dtype(el, t, "el", n)
+    n_l = el.size(0)
+    if o.shape != (n_l,) + tuple(V.shape[1:]) or stats.numel() != n_l * h * 2:
+        raise RuntimeError("gat_attention_backward: o must be %s and stats (n_src, h, 2), got %s and %s"
+                           % ((n_l,) + tuple(V.shape[1:]), tuple(o.shape), tuple(stats.shape)))
+    dO = dO.contiguous()
+    if dO.shape != o.shape:
+        raise RuntimeError("gat_attention_backward: dO must match o %s, got %s" % (tuple(o.shape), tuple(dO.shape)))
+    e = eid_r.size(0)
+    d_el, d_er, dV = torch.empty_like(el), torch.empty_like(er), torch.empty_like(V)
+    ws = torch.empty(max(n_l * h * 4, 1), dtype=el.dtype, device=el.device)      # (el, m, 1 / l, D) per (node, head)
+    with _lib.device_guard(el.device):
+        plan_r = _plan(row, indptr_r, eid_r, indices_r, er.size(0))
+        plan_c = _plan(col, indptr_c, eid_c, indices_c, n_l)
+        check(lib().graphop_gat_attention_backward(
+            dtype_code(el), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c),
+            ptr(eid_c), ptr(indices_c), ptr(el), ptr(er), ptr(V), ptr(o), ptr(stats), ptr(dO), ptr(d_el), ptr(d_er),
+            ptr(dV), ptr(ws), ws.numel() * ws.element_size(), row.size(0), col.size(0), e, n_l, er.size(0), h, d,
+            float(negative_slope), plan_r.handle, plan_c.handle, stream_of(el)))
+    return [d_el, d_er, dV]
+
+
 def prepare(graph, h=1, d=64, dtype=torch.float32, fused=True):
     """Build a graph's plans and window structures ahead of the first op call (see graphs.prepare)."""
     from . import graphs
@@ -413,6 +479,8 @@ _SCHEMAS = {
     "attention_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor Q, Tensor K, Tensor V, Tensor o, Tensor stats, Tensor dO) -> Tensor[]",
     "gat_scores_forward": "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, float negative_slope=0.2) -> Tensor",
     "gat_scores_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor dy, float negative_slope=0.2) -> Tensor[]",
+    "gat_attention_forward": "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, Tensor V, float negative_slope=0.2) -> Tensor[]",
+    "gat_attention_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor V, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2) -> Tensor[]",
 }
 _torch_lib = None
 

@@ -392,6 +392,38 @@ GRAPHOP_API int graphop_gat_scores_backward(int dtype, const int64_t* row, const
                                 int64_t n_r, int64_t h, double negative_slope, const graphop_plan_t* plan_r,
                                 const graphop_plan_t* plan_c, void* stream);
 
+/* ---- fused GAT attention (ABI 8, additive; EXTRA op, not one of the reference's eight) -----------------------------
+ * The layer gat_scores_forward -> sparse_softmax_forward -> vector_spmm_forward as one forward and one backward entry,
+ * with no E-sized tensor in either direction.  Per head k, for every slot j of every chunk c with i = row[c]:
+ *   s_ij = LeakyReLU(el[i, k] + er[indices[j], k])      (bitwise what gat_scores_forward computes)
+ *   m_i = max(-1e9, max_j s_ij),  l_i = sum_j exp(s_ij - m_i),  o[i, k, :] = sum_j exp(s_ij - m_i) / l_i * V[indices[j], k, :]
+ *   stats[(i*h + k)*2 + {0,1}] = (m_i, 1 / l_i)   (n_l, h, 2); a row without slots gets o = 0 and stats (-1e9, 0)
+ * gat_attention_forward(row, indptr, eid, indices, el, er, V, negative_slope) -> [o, stats]
+ *   el (n_l, h), er (n_r, h), V (n_r, h, d), o (n_l, h, d), stats (n_l, h, 2).
+ * gat_attention_backward(<8 csr>, el, er, V, o, stats, dO, negative_slope) -> [del, der, dV], a recomputed per slot:
+ *   D_i = <dO_i, o_i>, a_ij = exp(s_ij - m_i) / l_i, ds_ij = a_ij (<dO_i, V_j> - D_i), dz_ij = ds_ij (z > 0 ? 1 : slope)
+ *   del[i] = sum_j dz_ij (row-major CSR),  der[j] = sum_i dz_ij,  dV[j] = sum_i a_ij dO_i (column-major CSR).
+ *   workspace: at least n_l * h * 4 values of `dtype` (the per-(node, head) items (el, m, 1 / l, D) the passes gather);
+ *   a smaller one is GRAPHOP_ERR_INVALID_ARGUMENT.  del may be NULL when n_row_chunks == 0, der and dV when
+ *   n_col_chunks == 0.
+ * eid is validated and used for plan lookup only.  With a plan of the same arrays, fp32, h in {1, 2, 4, 8}, d in
+ * {8, 16, 32, 64}, h * d in {64, 128, 256} and 16-byte-aligned tables the fast kernels run (csrc/kernels_gat_attn.h);
+ * everything else takes the generic ones.  Any chunk layout works on both. */
+GRAPHOP_API int graphop_gat_attention_forward(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                                  const int64_t* indices, const void* el, const void* er, const void* V, void* o,
+                                  void* stats, int64_t n_chunks, int64_t n_edges, int64_t n_l, int64_t n_r,
+                                  int64_t h, int64_t d, double negative_slope, const graphop_plan_t* plan,
+                                  void* stream);
+GRAPHOP_API int graphop_gat_attention_backward(int dtype, const int64_t* row, const int64_t* indptr_r,
+                                   const int64_t* eid_r, const int64_t* indices_r, const int64_t* col,
+                                   const int64_t* indptr_c, const int64_t* eid_c, const int64_t* indices_c,
+                                   const void* el, const void* er, const void* V, const void* o, const void* stats,
+                                   const void* dO, void* del, void* der, void* dV, void* workspace,
+                                   int64_t workspace_bytes, int64_t n_row_chunks, int64_t n_col_chunks,
+                                   int64_t n_edges, int64_t n_l, int64_t n_r, int64_t h, int64_t d,
+                                   double negative_slope, const graphop_plan_t* plan_r,
+                                   const graphop_plan_t* plan_c, void* stream);
+
 /* ---- fused attention step (EXTRA op, not one of the reference's eight) --------------------------
  * The composition the reference harness chains by hand -- MaskedMMCSR -> SparseSoftmax -> VectorSPMM
  * (wrapper.py:20-30, 8-18, 44-55) -- as one forward and one backward entry, so that the E-sized

@@ -1,0 +1,152 @@
+"""CPU tier of the fused GAT attention (graphop_gat_attention_*): the library and both bindings expose the op, arguments
+are validated before anything touches a device, CPU tensors are refused, the new fast kernels fit their register budget,
+and a float64 restatement of the flash-style backward the kernels implement (D, ds, dz) equals autograd through the
+pure-torch GAT layer."""
+import ctypes
+import os
+import re
+import sys
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+from gat_reference import gat_layer
+
+NAMES = ("gat_attention_forward", "gat_attention_backward")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_fused_gat_symbols_resolve_in_the_library_and_the_extension():
+    from custom_op_benchmark_amd import _ext, _lib, graphop
+    l = ctypes.CDLL(_lib.LIB_PATH)
+    for n in NAMES:
+        assert hasattr(l, "graphop_" + n) and "graphop_" + n in _lib.EXPORTED_SYMBOLS
+    assert _lib.ABI_VERSION == 8 and _lib.lib().graphop_abi_version() == 8
+    ext = _ext.load()
+    if ext is None:
+        pytest.skip("graphop_cpp.so not built (run __graft_entry__.build())")
+    assert graphop.cpp_ext is ext
+    for n in NAMES:
+        assert callable(getattr(ext, n)) and hasattr(torch.ops.graphop, n)
+
+
+def test_fused_gat_ops_are_extra_ops_with_an_autograd_class():
+    from custom_op_benchmark_amd import functions, graphop as ops
+    for n in NAMES:
+        assert n in ops.EXTRA_OPS and callable(getattr(ops, n))
+        assert "float negative_slope=0.2" in ops._SCHEMAS[n]
+    assert issubclass(functions.FusedGATAttention, torch.autograd.Function)
+    assert callable(functions.fused_gat_attention_step)
+    assert len(ops.__all__) == 8 and not set(NAMES) & set(ops.__all__)      # the reference's eight names only
+
+
+def _fwd(l, dtype, C, E, n_l, n_r, h, d, p=None):
+    n = ctypes.c_void_p(0)
+    p = p or [n] * 9
+    return l.graphop_gat_attention_forward(dtype, *p, C, E, n_l, n_r, h, d, 0.2, n, n)
+
+
+def _bwd(l, dtype, C, C2, E, n_l, n_r, h, d, ws=None, ws_bytes=0):
+    n = ctypes.c_void_p(0)
+    return l.graphop_gat_attention_backward(dtype, *([n] * 17), ws or n, ws_bytes, C, C2, E, n_l, n_r, h, d, 0.2, n, n,
+                                            n)
+
+
+def test_fused_gat_argument_validation_without_gpu():
+    from custom_op_benchmark_amd import _lib
+    l = _lib.lib()
+    assert _fwd(l, 7, 0, 0, 0, 0, 1, 8) == 1 and b"dtype" in l.graphop_last_error()
+    assert _bwd(l, 7, 0, 0, 0, 0, 0, 1, 8) == 1 and b"dtype" in l.graphop_last_error()
+    assert _fwd(l, 0, -1, 0, 0, 0, 1, 8) == 1 and b"negative" in l.graphop_last_error()
+    assert _fwd(l, 1, 0, 0, 0, -2, 1, 8) == 1 and b"negative" in l.graphop_last_error()
+    assert _bwd(l, 1, 0, -3, 0, 0, 0, 1, 8) == 1 and b"negative" in l.graphop_last_error()
+    for h, d in ((0, 8), (1, 0)):
+        assert _fwd(l, 0, 0, 0, 0, 0, h, d) == 1 and b"negative" in l.graphop_last_error()
+        assert _bwd(l, 0, 0, 0, 0, 0, 0, h, d) == 1 and b"negative" in l.graphop_last_error()
+    # the backward's workspace holds (el, m, 1/l, D) per (node, head): n_l * h * 4 values of dtype
+    assert _bwd(l, 0, 4, 4, 10, 5, 5, 2, 8, ws=ctypes.c_void_p(16), ws_bytes=5 * 2 * 4 * 4 - 4) == 1
+    assert b"workspace" in l.graphop_last_error()
+    assert _bwd(l, 1, 4, 4, 10, 5, 5, 2, 8, ws=ctypes.c_void_p(16), ws_bytes=5 * 2 * 4 * 4) == 1   # fp64: twice that
+    assert b"workspace" in l.graphop_last_error()
+    # empty problems are no-ops that never dereference anything
+    assert _fwd(l, 0, 0, 0, 0, 0, 1, 8) == 0
+    assert _fwd(l, 1, 0, 0, 0, 7, 4, 16) == 0
+    assert _bwd(l, 0, 0, 0, 0, 0, 0, 1, 8) == 0
+    assert _bwd(l, 1, 0, 0, 0, 0, 3, 8, 32) == 0
+
+
+def test_fused_gat_cpu_tensors_are_refused():
+    from custom_op_benchmark_amd import graphop as ops
+    i = torch.zeros(2, dtype=torch.int64)
+    f = torch.zeros(2, 4)
+    v = torch.zeros(2, 4, 8)
+    with pytest.raises(RuntimeError, match="row must be a CUDA tensor"):
+        ops.gat_attention_forward(i, i, i, i, f, f, v)
+    with pytest.raises(RuntimeError, match="row must be a CUDA tensor"):
+        ops.gat_attention_backward(i, i, i, i, i, i, i, i, f, f, v, v, f, v, 0.2)
+    with pytest.raises(RuntimeError, match="no CPU implementation|must be a CUDA tensor"):
+        torch.ops.graphop.gat_attention_forward(i, i, i, i, f, f, v)
+    with pytest.raises(RuntimeError, match="no CPU implementation|must be a CUDA tensor"):
+        torch.ops.graphop.gat_attention_backward(i, i, i, i, i, i, i, i, f, f, v, v, f, v, 0.1)
+
+
+def test_fused_gat_fast_kernels_do_not_spill():
+    """Every fast instantiation (stats, fwd, pack, bwd_row, bwd_col) keeps its loop in registers: no spill, no scratch."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from kernel_resources import kernel_resources
+    res = kernel_resources()
+    fast = {n: r for n, r in res.items() if re.search(r"k_gat_attn_(stats|fwd|pack|bwd_row|bwd_col)_f32<", n)}
+    # 9 (h, d) pairs x {owned, shared} for fwd / bwd_row / bwd_col, 9 packs, 4 head counts x 2 group widths of stats
+    assert len(fast) == 3 * 18 + 9 + 8, sorted(fast)
+    bad = {n: r for n, r in fast.items() if r["spill_vgpr"] or r["scratch"]}
+    assert not bad, "\n".join("%s: %r" % kv for kv in sorted(bad.items()))
+
+
+def _restated(src, dst, n_l, n_r, el, er, V, dO, slope):
+    """The backward as the kernels compute it, in float64: stats, o, D = <dO, o>, a recomputed, ds, dz, then the row-
+    and column-major sums.  el (n, h), er (n, h), V (n_r, h, d), dO (n_l, h, d)."""
+    h = el.size(1)
+    z = el[src] + er[dst]
+    s = F.leaky_relu(z, slope)
+    m = torch.full((n_l, h), -1e9, dtype=s.dtype).scatter_reduce(0, src[:, None].expand(-1, h), s, "amax")
+    ex = torch.exp(s - m[src])
+    lsum = torch.zeros((n_l, h), dtype=s.dtype).index_add(0, src, ex)
+    inv_l = torch.where(lsum > 0, 1 / lsum, torch.zeros_like(lsum))
+    a = ex * inv_l[src]
+    o = torch.zeros((n_l, h, V.size(-1)), dtype=V.dtype).index_add(0, src, a[..., None] * V[dst])
+    D = (dO * o).sum(-1)
+    da = (dO[src] * V[dst]).sum(-1)
+    ds = a * (da - D[src])
+    dz = torch.where(z > 0, ds, ds * slope)
+    d_el = torch.zeros_like(el).index_add(0, src, dz)
+    d_er = torch.zeros_like(er).index_add(0, dst, dz)
+    dV = torch.zeros_like(V).index_add(0, dst, a[..., None] * dO[src])
+    return o, d_el, d_er, dV
+
+
+@pytest.mark.parametrize("slope", [0.2, 0.0, -0.1])
+def test_fused_gat_backward_formulas_match_autograd(slope):
+    """Small rectangular graph with empty rows, z == 0 ties on many edges and a large-magnitude row (|z| ~ 50)."""
+    gen = torch.Generator().manual_seed(3)
+    n_l, n_r, h, d = 23, 17, 3, 5
+    src = torch.randint(0, n_l, (160,), generator=gen)
+    src = src[src % 5 != 0]                       # rows 5, 10, ... have no slots (20 stays empty)
+    dst = torch.randint(0, n_r, (src.numel(),), generator=gen)
+    el = torch.randint(-3, 4, (n_l, h), generator=gen).double()
+    er = torch.randint(-3, 4, (n_r, h), generator=gen).double()
+    er[:n_r] = -el[:n_r]                          # z == 0 wherever src == dst
+    src = torch.cat([src, torch.arange(n_r)])     # ... and make sure there are many such edges
+    dst = torch.cat([dst, torch.arange(n_r)])
+    el[1] += 50.0                                 # row 1: |z| ~ 50
+    assert ((el[src] + er[dst]) == 0).any(-1).float().mean() > 0.1
+    V = torch.randn(n_r, h, d, generator=gen, dtype=torch.float64)
+    dO = torch.randn(n_l, h, d, generator=gen, dtype=torch.float64)
+    r = [x.clone().requires_grad_(True) for x in (el, er, V)]
+    o_ref = gat_layer(src, dst, n_l, r[0], r[1], r[2], slope)
+    o_ref.backward(dO)
+    o, d_el, d_er, dV = _restated(src, dst, n_l, n_r, el, er, V, dO, slope)
+    assert not (src == 20).any() and not o[20].any() and not d_el[20].any()   # an empty row: o = 0, no gradient
+    for name, got, want in (("o", o, o_ref.detach()), ("del", d_el, r[0].grad), ("der", d_er, r[1].grad),
+                            ("dV", dV, r[2].grad)):
+        torch.testing.assert_close(got, want, rtol=1e-12, atol=1e-12, msg=lambda msg: name + ": " + msg)
