@@ -4,6 +4,11 @@
 // No E-sized tensor exists in either direction.  Host-side dispatch in the style of gat.hip: validation, fills, and the
 // choice between the fp32 fast kernels (a plan of the same arrays, h in {1, 2, 4, 8}, d in {8, 16, 32, 64},
 // h * d in {64, 128, 256}) and the generic ones (fp64, other shapes, NULL plans).
+// The *_dropout_* entry points are the same op with attention dropout (kernels_dropout.h: the keep decision of an edge
+// is recomputed from Philox in each gather pass, so still no E-sized tensor), and graphop_edge_dropout_mask writes that
+// decision out as an (E, h) tensor for the composed path and for tests.
+#include <cmath>
+
 #include "common.h"
 #include "host.h"
 #include "kernels_gat_attn.h"
@@ -31,6 +36,28 @@ inline int gat_attn_check_plan(const char* fn, const graphop_plan* p, const char
 }
 
 inline bool a16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// the dropout arguments as the host prepares them: T = floor(p * 2^32) and 1 / (1 - p), both computed in double
+struct HostDrop {
+  unsigned key0, key1, offset, thresh;
+  double scale;
+  template <typename T>
+  DropArgs<T> as() const { return DropArgs<T>{key0, key1, offset, thresh, (T)scale}; }
+};
+
+inline int drop_check(const char* fn, double p, uint64_t seed, i64 n_l, i64 n_r, uint32_t offset, HostDrop* out) {
+  GO_CHECK_ARG(p >= 0.0 && p < 1.0, "%s: dropout probability p must be in [0, 1), got %g", fn, p);
+  GO_CHECK_ARG((seed >> 63) == 0, "%s: seed must be below 2^63, got %llu", fn, (unsigned long long)seed);
+  GO_CHECK_ARG(n_l < ((i64)1 << 32) && n_r < ((i64)1 << 32),
+               "%s: node ids must fit 32 bits for the dropout counter (n_l=%lld n_r=%lld)", fn, (long long)n_l,
+               (long long)n_r);
+  out->key0 = (unsigned)(seed & 0xffffffffu);
+  out->key1 = (unsigned)(seed >> 32);
+  out->offset = offset;
+  out->thresh = (unsigned)(uint64_t)std::floor(p * 4294967296.0);
+  out->scale = 1.0 / (1.0 - p);
+  return GRAPHOP_OK;
+}
 
 // fp32 fast kernels: the (h, d) pairs below, ids that fit 31 bits, 16-byte-aligned tables
 inline bool gat_attn_fast_ok(int dtype, i64 h, i64 d, i64 E, i64 n_l, i64 n_r, std::initializer_list<const void*> ps) {
@@ -140,15 +167,13 @@ int gat_attn_stats(int dtype, const i64* row, const i64* indptr, const i64* indi
 
 using namespace graphop;
 
-extern "C" {
+namespace {
 
-int graphop_gat_attention_forward(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
-                                  const int64_t* indices, const void* el, const void* er, const void* V, void* o,
-                                  void* stats, int64_t n_chunks, int64_t n_edges, int64_t n_l, int64_t n_r,
-                                  int64_t h, int64_t d, double negative_slope, const graphop_plan_t* plan,
-                                  void* stream) {
-  const char* fn = "gat_attention_forward";
-  GO_TRY(gat_attn_check(fn, dtype, n_chunks, 0, n_edges, n_l, n_r, h, d));
+// drop == nullptr: the op without dropout (today's kernels, whatever the entry point)
+int gat_attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                     const int64_t* indices, const void* el, const void* er, const void* V, void* o, void* stats,
+                     int64_t n_chunks, int64_t n_edges, int64_t n_l, int64_t n_r, int64_t h, int64_t d,
+                     double negative_slope, const HostDrop* drop, const graphop_plan_t* plan, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const size_t es = esize(dtype);
   const graphop_plan* pm = plan_matches_full(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
@@ -166,7 +191,37 @@ int graphop_gat_attention_forward(int dtype, const int64_t* row, const int64_t* 
   GO_TRY(gat_attn_stats(dtype, (const i64*)row, (const i64*)indptr, (const i64*)indices, el, er, stats,
                         slots ? n_chunks : 0, n_l, h, negative_slope, pm, fast, st));
   if (!slots) return GRAPHOP_OK;
-  if (fast) {
+  if (drop) {
+    if (fast) {
+      ProfScope prof("gat_attn_drop_fwd", st, "k_gat_attn_drop_fwd_f32");
+      const int cpg = gat_attn_cpg(n_chunks);
+      const unsigned nb = (unsigned)ceil_div(ceil_div(n_chunks, cpg), kFastBlock / 16);
+      const bool owned = pm->info.rows_sorted != 0;
+      const DropArgs<float> dr = drop->as<float>();
+      GO_DISPATCH_GAT_ATTN(h, d, {
+        if (owned)
+          hipLaunchKernelGGL((k_gat_attn_drop_fwd_f32<H, D, true>), dim3(nb), dim3(kFastBlock), 0, st, (const i64*)row,
+                             (const i64*)indptr, (const i64*)indices, (const float*)el, (const float*)er,
+                             (const float2*)stats, (const float*)V, (float*)o, n_chunks, cpg, (float)negative_slope,
+                             dr);
+        else
+          hipLaunchKernelGGL((k_gat_attn_drop_fwd_f32<H, D, false>), dim3(nb), dim3(kFastBlock), 0, st,
+                             (const i64*)row, (const i64*)indptr, (const i64*)indices, (const float*)el,
+                             (const float*)er, (const float2*)stats, (const float*)V, (float*)o, n_chunks, cpg,
+                             (float)negative_slope, dr);
+      });
+    } else {
+      ProfScope prof("gat_attn_drop_fwd", st, "k_gat_attn_drop_fwd_generic");
+      const unsigned nb = (unsigned)ceil_div(n_chunks, kGenericWavesPerBlock);
+      auto go = [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL((k_gat_attn_drop_fwd_generic<T>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)row,
+                           (const i64*)indptr, (const i64*)indices, (const T*)el, (const T*)er, (const T*)stats,
+                           (const T*)V, (T*)o, n_chunks, h, d, (T)negative_slope, drop->as<T>());
+      };
+      if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+    }
+  } else if (fast) {
     ProfScope prof("gat_attn_fwd", st, "k_gat_attn_fwd_f32");
     const int cpg = gat_attn_cpg(n_chunks);
     const unsigned nb = (unsigned)ceil_div(ceil_div(n_chunks, cpg), kFastBlock / 16);
@@ -196,16 +251,13 @@ int graphop_gat_attention_forward(int dtype, const int64_t* row, const int64_t* 
   return GRAPHOP_OK;
 }
 
-int graphop_gat_attention_backward(int dtype, const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r,
-                                   const int64_t* indices_r, const int64_t* col, const int64_t* indptr_c,
-                                   const int64_t* eid_c, const int64_t* indices_c, const void* el, const void* er,
-                                   const void* V, const void* o, const void* stats, const void* dO, void* del,
-                                   void* der, void* dV, void* workspace, int64_t workspace_bytes,
-                                   int64_t n_row_chunks, int64_t n_col_chunks, int64_t n_edges, int64_t n_l,
-                                   int64_t n_r, int64_t h, int64_t d, double negative_slope,
-                                   const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream) {
-  const char* fn = "gat_attention_backward";
-  GO_TRY(gat_attn_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_l, n_r, h, d));
+int gat_attn_backward(const char* fn, int dtype, const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r,
+                      const int64_t* indices_r, const int64_t* col, const int64_t* indptr_c, const int64_t* eid_c,
+                      const int64_t* indices_c, const void* el, const void* er, const void* V, const void* o,
+                      const void* stats, const void* dO, void* del, void* der, void* dV, void* workspace,
+                      int64_t workspace_bytes, int64_t n_row_chunks, int64_t n_col_chunks, int64_t n_edges,
+                      int64_t n_l, int64_t n_r, int64_t h, int64_t d, double negative_slope, const HostDrop* drop,
+                      const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const size_t es = esize(dtype);
   const bool slots = n_edges > 0 && (n_row_chunks > 0 || n_col_chunks > 0);
@@ -256,7 +308,34 @@ int graphop_gat_attention_backward(int dtype, const int64_t* row, const int64_t*
   if (n_row_chunks > 0) {
     GO_PTR(fn, row); GO_PTR(fn, indptr_r); GO_PTR(fn, eid_r); GO_PTR(fn, indices_r);
     const i64 C = n_row_chunks;
-    if (ok && pr) {
+    if (drop && ok && pr) {
+      ProfScope prof("gat_attn_drop_bwd_row", st, "k_gat_attn_drop_bwd_row_f32");
+      const int cpg = gat_attn_cpg(C);
+      const unsigned nb = (unsigned)ceil_div(ceil_div(C, cpg), kFastBlock / G);
+      const DropArgs<float> dr = drop->as<float>();
+      GO_DISPATCH_GAT_ATTN(h, d, {
+        if (pr->info.rows_sorted)
+          hipLaunchKernelGGL((k_gat_attn_drop_bwd_row_f32<H, D, true>), dim3(nb), dim3(kFastBlock), 0, st,
+                             (const i64*)row, (const i64*)indptr_r, (const i64*)indices_r, (const float*)er,
+                             (const float*)V, (const float4*)workspace, (const float*)dO, (float*)del, C, cpg, slope,
+                             dr);
+        else
+          hipLaunchKernelGGL((k_gat_attn_drop_bwd_row_f32<H, D, false>), dim3(nb), dim3(kFastBlock), 0, st,
+                             (const i64*)row, (const i64*)indptr_r, (const i64*)indices_r, (const float*)er,
+                             (const float*)V, (const float4*)workspace, (const float*)dO, (float*)del, C, cpg, slope,
+                             dr);
+      });
+    } else if (drop) {
+      ProfScope prof("gat_attn_drop_bwd_row", st, "k_gat_attn_drop_bwd_row_generic");
+      auto go = [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL((k_gat_attn_drop_bwd_row_generic<T>), dim3((unsigned)ceil_div(C, kGenericWavesPerBlock)),
+                           dim3(kGenericBlock), 0, st, (const i64*)row, (const i64*)indptr_r, (const i64*)indices_r,
+                           (const T*)er, (const T*)V, (const T*)workspace, (const T*)dO, (T*)del, C, h, d,
+                           (T)negative_slope, drop->as<T>());
+      };
+      if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+    } else if (ok && pr) {
       ProfScope prof("gat_attn_bwd_row", st, "k_gat_attn_bwd_row_f32");
       const int cpg = gat_attn_cpg(C);
       const unsigned nb = (unsigned)ceil_div(ceil_div(C, cpg), kFastBlock / G);
@@ -286,7 +365,34 @@ int graphop_gat_attention_backward(int dtype, const int64_t* row, const int64_t*
   if (n_col_chunks > 0) {
     GO_PTR(fn, col); GO_PTR(fn, indptr_c); GO_PTR(fn, eid_c); GO_PTR(fn, indices_c);
     const i64 C = n_col_chunks;
-    if (ok && pc) {
+    if (drop && ok && pc) {
+      ProfScope prof("gat_attn_drop_bwd_col", st, "k_gat_attn_drop_bwd_col_f32");
+      const int cpg = gat_attn_cpg(C);
+      const unsigned nb = (unsigned)ceil_div(ceil_div(C, cpg), kFastBlock / G);
+      const DropArgs<float> dr = drop->as<float>();
+      GO_DISPATCH_GAT_ATTN(h, d, {
+        if (pc->info.rows_sorted)
+          hipLaunchKernelGGL((k_gat_attn_drop_bwd_col_f32<H, D, true>), dim3(nb), dim3(kFastBlock), 0, st,
+                             (const i64*)col, (const i64*)indptr_c, (const i64*)indices_c, (const float*)er,
+                             (const float*)V, (const float4*)workspace, (const float*)dO, (float*)der, (float*)dV, C,
+                             cpg, slope, dr);
+        else
+          hipLaunchKernelGGL((k_gat_attn_drop_bwd_col_f32<H, D, false>), dim3(nb), dim3(kFastBlock), 0, st,
+                             (const i64*)col, (const i64*)indptr_c, (const i64*)indices_c, (const float*)er,
+                             (const float*)V, (const float4*)workspace, (const float*)dO, (float*)der, (float*)dV, C,
+                             cpg, slope, dr);
+      });
+    } else if (drop) {
+      ProfScope prof("gat_attn_drop_bwd_col", st, "k_gat_attn_drop_bwd_col_generic");
+      auto go = [&](auto zero) {
+        using T = decltype(zero);
+        hipLaunchKernelGGL((k_gat_attn_drop_bwd_col_generic<T>), dim3((unsigned)ceil_div(C, kGenericWavesPerBlock)),
+                           dim3(kGenericBlock), 0, st, (const i64*)col, (const i64*)indptr_c, (const i64*)indices_c,
+                           (const T*)er, (const T*)V, (const T*)workspace, (const T*)dO, (T*)der, (T*)dV, C, h, d,
+                           (T)negative_slope, drop->as<T>());
+      };
+      if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+    } else if (ok && pc) {
       ProfScope prof("gat_attn_bwd_col", st, "k_gat_attn_bwd_col_f32");
       const int cpg = gat_attn_cpg(C);
       const unsigned nb = (unsigned)ceil_div(ceil_div(C, cpg), kFastBlock / G);
@@ -313,6 +419,98 @@ int graphop_gat_attention_backward(int dtype, const int64_t* row, const int64_t*
     }
     GO_LAUNCH_CHECK();
   }
+  return GRAPHOP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int graphop_gat_attention_forward(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                                  const int64_t* indices, const void* el, const void* er, const void* V, void* o,
+                                  void* stats, int64_t n_chunks, int64_t n_edges, int64_t n_l, int64_t n_r,
+                                  int64_t h, int64_t d, double negative_slope, const graphop_plan_t* plan,
+                                  void* stream) {
+  const char* fn = "gat_attention_forward";
+  GO_TRY(gat_attn_check(fn, dtype, n_chunks, 0, n_edges, n_l, n_r, h, d));
+  return gat_attn_forward(fn, dtype, row, indptr, eid, indices, el, er, V, o, stats, n_chunks, n_edges, n_l, n_r, h, d,
+                          negative_slope, nullptr, plan, stream);
+}
+
+int graphop_gat_attention_backward(int dtype, const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r,
+                                   const int64_t* indices_r, const int64_t* col, const int64_t* indptr_c,
+                                   const int64_t* eid_c, const int64_t* indices_c, const void* el, const void* er,
+                                   const void* V, const void* o, const void* stats, const void* dO, void* del,
+                                   void* der, void* dV, void* workspace, int64_t workspace_bytes,
+                                   int64_t n_row_chunks, int64_t n_col_chunks, int64_t n_edges, int64_t n_l,
+                                   int64_t n_r, int64_t h, int64_t d, double negative_slope,
+                                   const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream) {
+  const char* fn = "gat_attention_backward";
+  GO_TRY(gat_attn_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_l, n_r, h, d));
+  return gat_attn_backward(fn, dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V, o,
+                           stats, dO, del, der, dV, workspace, workspace_bytes, n_row_chunks, n_col_chunks, n_edges,
+                           n_l, n_r, h, d, negative_slope, nullptr, plan_r, plan_c, stream);
+}
+
+// p == 0 runs the kernels of the entry points above: bit-identical results
+int graphop_gat_attention_dropout_forward(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                                          const int64_t* indices, const void* el, const void* er, const void* V,
+                                          void* o, void* stats, int64_t n_chunks, int64_t n_edges, int64_t n_l,
+                                          int64_t n_r, int64_t h, int64_t d, double negative_slope, double p,
+                                          uint64_t seed, uint32_t offset, const graphop_plan_t* plan, void* stream) {
+  const char* fn = "gat_attention_dropout_forward";
+  GO_TRY(gat_attn_check(fn, dtype, n_chunks, 0, n_edges, n_l, n_r, h, d));
+  HostDrop drop;
+  GO_TRY(drop_check(fn, p, seed, n_l, n_r, offset, &drop));
+  return gat_attn_forward(fn, dtype, row, indptr, eid, indices, el, er, V, o, stats, n_chunks, n_edges, n_l, n_r, h, d,
+                          negative_slope, p > 0.0 ? &drop : nullptr, plan, stream);
+}
+
+int graphop_gat_attention_dropout_backward(int dtype, const int64_t* row, const int64_t* indptr_r,
+                                           const int64_t* eid_r, const int64_t* indices_r, const int64_t* col,
+                                           const int64_t* indptr_c, const int64_t* eid_c, const int64_t* indices_c,
+                                           const void* el, const void* er, const void* V, const void* o,
+                                           const void* stats, const void* dO, void* del, void* der, void* dV,
+                                           void* workspace, int64_t workspace_bytes, int64_t n_row_chunks,
+                                           int64_t n_col_chunks, int64_t n_edges, int64_t n_l, int64_t n_r, int64_t h,
+                                           int64_t d, double negative_slope, double p, uint64_t seed, uint32_t offset,
+                                           const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream) {
+  const char* fn = "gat_attention_dropout_backward";
+  GO_TRY(gat_attn_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_l, n_r, h, d));
+  HostDrop drop;
+  GO_TRY(drop_check(fn, p, seed, n_l, n_r, offset, &drop));
+  return gat_attn_backward(fn, dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V, o,
+                           stats, dO, del, der, dV, workspace, workspace_bytes, n_row_chunks, n_col_chunks, n_edges,
+                           n_l, n_r, h, d, negative_slope, p > 0.0 ? &drop : nullptr, plan_r, plan_c, stream);
+}
+
+int graphop_edge_dropout_mask(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                              const int64_t* indices, void* y, int64_t n_chunks, int64_t n_edges, int64_t n_l,
+                              int64_t n_r, int64_t h, double p, uint64_t seed, uint32_t offset,
+                              const graphop_plan_t* plan, void* stream) {
+  const char* fn = "edge_dropout_mask";
+  GO_TRY(gat_attn_check(fn, dtype, n_chunks, 0, n_edges, n_l, n_r, h, 1));
+  HostDrop drop;
+  GO_TRY(drop_check(fn, p, seed, n_l, n_r, offset, &drop));
+  hipStream_t st = (hipStream_t)stream;
+  if (n_edges == 0) return GRAPHOP_OK;
+  GO_PTR(fn, y);
+  const graphop_plan* pm = plan_matches_full(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
+                                             (const i64*)indices, n_chunks, n_edges) ? plan : nullptr;
+  GO_TRY(gat_attn_check_plan(fn, pm, "the row-major rows", n_l, "the neighbours", n_r));
+  const bool covered = pm && pm->info.full_coverage && pm->info.eid_identity && pm->info.indptr_monotone;
+  if (!covered) GO_HIP(zero_async(y, esize(dtype) * (size_t)(n_edges * h), st));   // edges no slot names get m = 0
+  if (n_chunks == 0) return GRAPHOP_OK;
+  GO_PTR(fn, row); GO_PTR(fn, indptr); GO_PTR(fn, eid); GO_PTR(fn, indices);
+  ProfScope prof("edge_dropout_mask", st, "k_edge_dropout_mask");
+  const unsigned nb = (unsigned)ceil_div(n_chunks, kGenericWavesPerBlock);
+  auto go = [&](auto zero) {
+    using T = decltype(zero);
+    hipLaunchKernelGGL((k_edge_dropout_mask<T>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)row,
+                       (const i64*)indptr, (const i64*)eid, (const i64*)indices, (T*)y, n_chunks, h, drop.as<T>());
+  };
+  if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+  GO_LAUNCH_CHECK();
   return GRAPHOP_OK;
 }
 

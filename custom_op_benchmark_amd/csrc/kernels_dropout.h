@@ -1,0 +1,74 @@
+// Edge dropout without an edge-sized mask (extra op).  The keep decision of edge (i, j) and head k is
+// a pure function of (i, j, k, seed, offset, p), so every pass that holds both node ids recomputes it:
+//   w[0..3] = Philox4x32-10(counter = (i, j, k >> 2, offset), key = (seed & 0xffffffff, seed >> 32))
+//   keep = w[k & 3] >= T,  T = floor(p * 2^32);  multiplier m_ijk = keep ? 1 / (1 - p) : 0
+// i is the row-major row id (index into el / o), j the neighbour id (index into er / V), in that order in both
+// orientations.  Parallel edges (the same (i, j) more than once) share one decision.
+#pragma once
+#include "kernels_generic.h"
+
+namespace graphop {
+
+// host-prepared arguments of the decision; scale = 1 / (1 - p) in the op's dtype
+template <typename T>
+struct DropArgs {
+  unsigned key0, key1, offset, thresh;
+  T scale;
+};
+
+// Philox4x32-10 (Salmon et al., Random123): ten rounds of two 32 x 32 -> 64 multiplies and a key bump
+__device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,
+                                              unsigned k1, unsigned (&w)[4]) {
+  constexpr unsigned M0 = 0xD2511F53u, M1 = 0xCD9E8D57u, W0 = 0x9E3779B9u, W1 = 0xBB67AE85u;
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned hi0 = __umulhi(M0, c0), lo0 = M0 * c0;
+    const unsigned hi1 = __umulhi(M1, c2), lo1 = M1 * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += W0;
+    k1 += W1;
+  }
+  w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
+}
+
+// keep bits of the four heads 4 * blk .. 4 * blk + 3 of edge (i, j): bit t = head 4 * blk + t is kept
+template <typename T>
+__device__ __forceinline__ int drop_keep4(unsigned i, unsigned j, unsigned blk, const DropArgs<T>& dr) {
+  unsigned w[4];
+  philox4x32_10(i, j, blk, dr.offset, dr.key0, dr.key1, w);
+  return (int)(w[0] >= dr.thresh) | ((int)(w[1] >= dr.thresh) << 1) | ((int)(w[2] >= dr.thresh) << 2) |
+         ((int)(w[3] >= dr.thresh) << 3);
+}
+
+// m_ijk of one head (generic kernels: one Philox call per use)
+template <typename T>
+__device__ __forceinline__ T drop_mult(i64 i, i64 j, i64 k, const DropArgs<T>& dr) {
+  return (drop_keep4<T>((unsigned)i, (unsigned)j, (unsigned)(k >> 2), dr) >> (int)(k & 3)) & 1 ? dr.scale : (T)0;
+}
+
+// y[eid[j], k] = m_ijk over the row-major chunks (i = row[c], j = indices[slot]); one wave per chunk, lanes over
+// (slot, block of four heads) pairs: one Philox call per four values.
+template <typename T>
+__global__ __launch_bounds__(kGenericBlock) void k_edge_dropout_mask(
+    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ eid,
+    const i64* __restrict__ indices, T* __restrict__ y, i64 n_chunks, i64 h, DropArgs<T> dr) {
+  const i64 c = generic_chunk_id();
+  if (c >= n_chunks) return;
+  const int lane = threadIdx.x & 63;
+  const i64 r = row[c];
+  const i64 j0 = indptr[c];
+  const i64 nblk = (h + 3) / 4;
+  const i64 items = (indptr[c + 1] - j0) * nblk;
+  for (i64 it = lane; it < items; it += kWave) {
+    const i64 j = j0 + it / nblk, b = it % nblk;
+    const int bits = drop_keep4<T>((unsigned)r, (unsigned)indices[j], (unsigned)b, dr);
+    T* out = y + eid[j] * h + b * 4;
+    const int n = h - b * 4 < 4 ? (int)(h - b * 4) : 4;
+    for (int t = 0; t < n; ++t) out[t] = (bits >> t) & 1 ? dr.scale : (T)0;
+  }
+}
+
+}  // namespace graphop

@@ -19,6 +19,7 @@
 #include "kernels_base.h"
 #include "kernels_gat.h"
 #include "kernels_generic.h"
+#include "kernels_dropout.h"
 
 namespace graphop {
 
@@ -47,6 +48,41 @@ __device__ __forceinline__ void gat_attn_merge(float& m, float& s, float m2, flo
   const float mn = fmaxf(m, m2);
   s = s * exp_nonpos(m - mn) + s2 * exp_nonpos(m2 - mn);
   m = mn;
+}
+
+// ---- attention dropout in the gather passes (kernels_dropout.h has the decision) ---------------------------------
+// The lanes that load a batch's neighbour ids also run Philox for them: lane t < SB holds slot t.  One call covers four
+// heads; for H = 8 lane SB + t takes the second block of slot t where the group has room (2 * SB <= L), else lane t
+// makes both calls.  `own` is the chunk's node, `oth` the gathered one; COL says which of them is the row-major row i.
+template <int H, int SB>
+struct GatDropCfg {
+  static constexpr int L = 16;
+  static constexpr int NB = (H + 3) / 4;            // Philox blocks per slot
+  static constexpr bool SPREAD = NB * SB <= L;      // one block per lane
+  static constexpr int LANES = SPREAD ? NB * SB : SB;   // lanes that load an id
+};
+
+template <int H, int SB, bool COL>
+__device__ __forceinline__ int gat_drop_lane_bits(int l, i64 own, int oth, const DropArgs<float>& dr) {
+  using C = GatDropCfg<H, SB>;
+  const unsigned i = COL ? (unsigned)oth : (unsigned)own, j = COL ? (unsigned)own : (unsigned)oth;
+  if constexpr (C::SPREAD) {
+    return drop_keep4<float>(i, j, (unsigned)(l / SB), dr);
+  } else {
+    int bits = 0;
+#pragma unroll
+    for (int b = 0; b < C::NB; ++b) bits |= drop_keep4<float>(i, j, (unsigned)b, dr) << (4 * b);
+    return bits;
+  }
+}
+
+// keep bits of slot U's heads (bit k = head k), in every lane of the group
+template <int H, int SB, int U>
+__device__ __forceinline__ int gat_drop_slot_bits(int lane_bits) {
+  using C = GatDropCfg<H, SB>;
+  int bits = group_bcast<C::L, U>(lane_bits);
+  if constexpr (C::SPREAD && C::NB == 2) bits |= group_bcast<C::L, SB + U>(lane_bits) << 4;
+  return bits;
 }
 
 // ---- stats pass --------------------------------------------------------------------------------------------------
@@ -233,6 +269,102 @@ __global__ __launch_bounds__(kFastBlock) void k_gat_attn_fwd_f32(
   if (dirty) flush(cur);
 }
 
+// k_gat_attn_fwd_f32 with the weight of a slot multiplied by m_ijk (the row statistics are those of the undropped
+// scores).  A kernel of its own, not a parameter of the one above, whose code stays as it is.
+template <int H, int D, bool OWNED>
+__global__ __launch_bounds__(kFastBlock) void k_gat_attn_drop_fwd_f32(
+    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
+    const float* __restrict__ el, const float* __restrict__ er, const float2* __restrict__ stats,
+    const float* __restrict__ V, float* __restrict__ o, i64 n_chunks, int chunks_per_group, float slope,
+    DropArgs<float> dr) {
+  using C = GatAttnCfg<H, D>;
+  constexpr int L = C::L, NV = C::NV, SB = C::SB_FWD;
+  constexpr int IDL = GatDropCfg<H, SB>::LANES;   // lanes that load a neighbour id
+  constexpr i64 F4 = C::F4;
+  const int l = threadIdx.x % L;
+  const i64 gid = (i64)blockIdx.x * (kFastBlock / L) + threadIdx.x / L;
+  const i64 c0 = gid * chunks_per_group;
+  i64 c1 = c0 + chunks_per_group;
+  if (c1 > n_chunks) c1 = n_chunks;
+  if (c0 >= c1) return;
+  i64 row_before = -1, row_after = -1;
+  if constexpr (OWNED) {
+    if (c0 > 0) row_before = row[c0 - 1];
+    if (c1 < n_chunks) row_after = row[c1];
+  }
+  int kv[NV];
+#pragma unroll
+  for (int v = 0; v < NV; ++v) kv[v] = gat_attn_head<H, D>(v, l);
+  float4 acc[NV];
+  float a_el[NV], a_m[NV], a_il[NV];
+  auto zero_acc = [&]() {
+#pragma unroll
+    for (int v = 0; v < NV; ++v) acc[v] = make_float4(0.f, 0.f, 0.f, 0.f);
+  };
+  auto flush = [&](i64 r) {
+    if (OWNED && r != row_before && r != row_after) {
+#pragma unroll
+      for (int v = 0; v < NV; ++v) reinterpret_cast<float4*>(o)[r * F4 + v * L + l] = acc[v];
+    } else {
+      atomic_flush<L, NV>(o, r, acc, l);
+    }
+  };
+  zero_acc();
+  i64 cur = -1;
+  bool dirty = false;
+  for (i64 c = c0; c < c1; ++c) {
+    const i64 r = row[c];
+    if (r != cur) {
+      if (dirty) { flush(cur); zero_acc(); dirty = false; }
+      cur = r;
+#pragma unroll
+      for (int v = 0; v < NV; ++v) {
+        a_el[v] = el[r * H + kv[v]];
+        const float2 st = stats[r * H + kv[v]];
+        a_m[v] = st.x;
+        a_il[v] = st.y;
+      }
+    }
+    const i64 j0 = indptr[c], j1 = indptr[c + 1];
+    if (j1 > j0) dirty = true;
+    for (i64 jb = j0; jb < j1; jb += SB) {
+      const int nb = (j1 - jb) < SB ? (int)(j1 - jb) : SB;
+      int my_src = 0;   // slots past the end re-read the batch's last neighbour with weight 0
+      const int t = l % SB;
+      if (l < IDL) my_src = (int)indices[jb + (t < nb ? t : nb - 1)];
+      float4 x[SB][NV];
+      float e[SB][NV];
+      static_for<SB>([&](auto uc) {
+        constexpr int u = decltype(uc)::value;
+        const i64 src = group_bcast<L, u>(my_src);
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+          x[u][v] = reinterpret_cast<const float4*>(V)[src * F4 + v * L + l];
+          e[u][v] = er[src * H + kv[v]];
+        }
+      });
+      int keep[SB];
+      const int mine = gat_drop_lane_bits<H, SB, false>(l, r, my_src, dr);
+      static_for<SB>([&](auto uc) {
+        constexpr int u = decltype(uc)::value;
+        keep[u] = gat_drop_slot_bits<H, SB, u>(mine);
+      });
+#pragma unroll
+      for (int u = 0; u < SB; ++u) {
+#pragma unroll
+        for (int v = 0; v < NV; ++v) {
+          const float z = gat_lrelu(a_el[v] + e[u][v], slope);
+          const float a = u < nb ? exp_nonpos(z - a_m[v]) * a_il[v] : 0.f;
+          const float w = (keep[u] >> kv[v]) & 1 ? a * dr.scale : 0.f;
+          acc[v].x = fmaf(w, x[u][v].x, acc[v].x); acc[v].y = fmaf(w, x[u][v].y, acc[v].y);
+          acc[v].z = fmaf(w, x[u][v].z, acc[v].z); acc[v].w = fmaf(w, x[u][v].w, acc[v].w);
+        }
+      }
+    }
+  }
+  if (dirty) flush(cur);
+}
+
 // ---- pack: P[i, k] = (el, m, 1/l, <dO, o>) ---------------------------------------------------------------------
 template <int H, int D>
 __global__ __launch_bounds__(kFastBlock) void k_gat_attn_pack_f32(
@@ -260,14 +392,16 @@ __global__ __launch_bounds__(kFastBlock) void k_gat_attn_pack_f32(
 // ---- backward passes -----------------------------------------------------------------------------------------------
 // ROW (row-major chunks): own = dO_i and P[i] in registers; gathers er_j and V_j; out0 = del.
 // COL (column-major chunks): own = V_j and er_j in registers; gathers P[i] and dO_i; out0 = der, out1 = dV.
-template <int H, int D, bool COL, bool OWNED>
+// DROP: da_ij = m_ij <dO_i, V_j> and dV_j sums a_ij m_ij dO_i; D_i in P is <dO_i, o_i> of the dropped o.
+template <int H, int D, bool COL, bool OWNED, bool DROP>
 __device__ __forceinline__ void gat_attn_bwd_walk(
     const i64* __restrict__ seg, const i64* __restrict__ indptr, const i64* __restrict__ indices,
     const float* __restrict__ er, const float* __restrict__ V, const float4* __restrict__ P,
     const float* __restrict__ dO, float* __restrict__ out0, float* __restrict__ out1, i64 n_chunks,
-    int chunks_per_group, float slope) {
+    int chunks_per_group, float slope, const DropArgs<float>& dr) {
   using C = GatAttnCfg<H, D>;
   constexpr int L = C::L, NV = C::NV, DQ = C::DQ, SB = C::SB_BWD;
+  constexpr int IDL = DROP ? GatDropCfg<H, SB>::LANES : SB;   // lanes that load a neighbour id
   constexpr i64 F4 = C::F4;
   const int l = threadIdx.x % L;
   const i64 gid = (i64)blockIdx.x * (kFastBlock / L) + threadIdx.x / L;
@@ -332,7 +466,8 @@ __device__ __forceinline__ void gat_attn_bwd_walk(
     for (i64 jb = j0; jb < j1; jb += SB) {
       const int nb = (j1 - jb) < SB ? (int)(j1 - jb) : SB;
       int my_src = 0;
-      if (l < SB) my_src = (int)indices[jb + (l < nb ? l : nb - 1)];
+      const int t = DROP ? l % SB : l;
+      if (l < IDL) my_src = (int)indices[jb + (t < nb ? t : nb - 1)];
       float4 x[SB][NV];        // ROW: V_j   COL: dO_i
       float4 pg[COL ? SB : 1][NV];
       float eg[COL ? 1 : SB][NV];
@@ -346,21 +481,35 @@ __device__ __forceinline__ void gat_attn_bwd_walk(
           else eg[u][v] = er[src * H + kv[v]];
         }
       });
+      int keep[DROP ? SB : 1];
+      if constexpr (DROP) {
+        const int mine = gat_drop_lane_bits<H, SB, COL>(l, r, my_src, dr);
+        static_for<SB>([&](auto uc) {
+          constexpr int u = decltype(uc)::value;
+          keep[u] = gat_drop_slot_bits<H, SB, u>(mine);
+        });
+      }
 #pragma unroll
       for (int u = 0; u < SB; ++u) {
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
-          const float da = group_sum<DQ>(dot4(y[v], x[u][v]));
+          float da = group_sum<DQ>(dot4(y[v], x[u][v]));
           float4 p;
           float z;
           if constexpr (COL) { p = pg[u][v]; z = p.x + e_own[v]; }
           else { p = p_own[v]; z = p.x + eg[u][v]; }
           const float a = u < nb ? exp_nonpos(gat_lrelu(z, slope) - p.y) * p.z : 0.f;
+          float am = a;   // a_ij m_ij
+          if constexpr (DROP) {
+            const float m = (keep[u] >> kv[v]) & 1 ? dr.scale : 0.f;
+            da *= m;
+            am *= m;
+          }
           const float ds = a * (da - p.w);
           acc[v] += z > 0.f ? ds : ds * slope;
           if constexpr (COL) {
-            accv[v].x = fmaf(a, x[u][v].x, accv[v].x); accv[v].y = fmaf(a, x[u][v].y, accv[v].y);
-            accv[v].z = fmaf(a, x[u][v].z, accv[v].z); accv[v].w = fmaf(a, x[u][v].w, accv[v].w);
+            accv[v].x = fmaf(am, x[u][v].x, accv[v].x); accv[v].y = fmaf(am, x[u][v].y, accv[v].y);
+            accv[v].z = fmaf(am, x[u][v].z, accv[v].z); accv[v].w = fmaf(am, x[u][v].w, accv[v].w);
           }
         }
       }
@@ -374,8 +523,8 @@ __global__ __launch_bounds__(kFastBlock) void k_gat_attn_bwd_row_f32(
     const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
     const float* __restrict__ er, const float* __restrict__ V, const float4* __restrict__ P,
     const float* __restrict__ dO, float* __restrict__ del, i64 n_chunks, int chunks_per_group, float slope) {
-  gat_attn_bwd_walk<H, D, false, OWNED>(row, indptr, indices, er, V, P, dO, del, nullptr, n_chunks, chunks_per_group,
-                                        slope);
+  gat_attn_bwd_walk<H, D, false, OWNED, false>(row, indptr, indices, er, V, P, dO, del, nullptr, n_chunks,
+                                               chunks_per_group, slope, DropArgs<float>{});
 }
 
 template <int H, int D, bool OWNED>
@@ -384,8 +533,28 @@ __global__ __launch_bounds__(kFastBlock) void k_gat_attn_bwd_col_f32(
     const float* __restrict__ er, const float* __restrict__ V, const float4* __restrict__ P,
     const float* __restrict__ dO, float* __restrict__ der, float* __restrict__ dV, i64 n_chunks,
     int chunks_per_group, float slope) {
-  gat_attn_bwd_walk<H, D, true, OWNED>(col, indptr, indices, er, V, P, dO, der, dV, n_chunks, chunks_per_group,
-                                       slope);
+  gat_attn_bwd_walk<H, D, true, OWNED, false>(col, indptr, indices, er, V, P, dO, der, dV, n_chunks, chunks_per_group,
+                                              slope, DropArgs<float>{});
+}
+
+template <int H, int D, bool OWNED>
+__global__ __launch_bounds__(kFastBlock) void k_gat_attn_drop_bwd_row_f32(
+    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
+    const float* __restrict__ er, const float* __restrict__ V, const float4* __restrict__ P,
+    const float* __restrict__ dO, float* __restrict__ del, i64 n_chunks, int chunks_per_group, float slope,
+    DropArgs<float> dr) {
+  gat_attn_bwd_walk<H, D, false, OWNED, true>(row, indptr, indices, er, V, P, dO, del, nullptr, n_chunks,
+                                              chunks_per_group, slope, dr);
+}
+
+template <int H, int D, bool OWNED>
+__global__ __launch_bounds__(kFastBlock) void k_gat_attn_drop_bwd_col_f32(
+    const i64* __restrict__ col, const i64* __restrict__ indptr, const i64* __restrict__ indices,
+    const float* __restrict__ er, const float* __restrict__ V, const float4* __restrict__ P,
+    const float* __restrict__ dO, float* __restrict__ der, float* __restrict__ dV, i64 n_chunks,
+    int chunks_per_group, float slope, DropArgs<float> dr) {
+  gat_attn_bwd_walk<H, D, true, OWNED, true>(col, indptr, indices, er, V, P, dO, der, dV, n_chunks, chunks_per_group,
+                                             slope, dr);
 }
 
 // ---- generic kernels: fp32 / fp64, any h and d, any chunk layout; one wave per chunk -----------------------------
@@ -441,11 +610,11 @@ __global__ void k_gat_attn_stats_fin_generic(T* __restrict__ stats, i64 n) {
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(kGenericBlock) void k_gat_attn_fwd_generic(
+template <typename T, bool DROP>
+__device__ __forceinline__ void gat_attn_fwd_generic(
     const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
     const T* __restrict__ el, const T* __restrict__ er, const T* __restrict__ stats, const T* __restrict__ V,
-    T* __restrict__ o, i64 n_chunks, i64 h, i64 d, T slope) {
+    T* __restrict__ o, i64 n_chunks, i64 h, i64 d, T slope, const DropArgs<T>& dr) {
   const i64 c = generic_chunk_id();
   if (c >= n_chunks) return;
   const int lane = threadIdx.x & 63;
@@ -458,10 +627,28 @@ __global__ __launch_bounds__(kGenericBlock) void k_gat_attn_fwd_generic(
     T acc = 0;
     for (i64 j = j0; j < j1; ++j) {
       const i64 src = indices[j];
-      acc += exp_t(gat_lrelu(a + er[src * h + k], slope) - m) * il * V[src * h * d + it];
+      T w = exp_t(gat_lrelu(a + er[src * h + k], slope) - m) * il;
+      if constexpr (DROP) w *= drop_mult<T>(r, src, k, dr);
+      acc += w * V[src * h * d + it];
     }
     atomicAdd(o + r * h * d + it, acc);
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kGenericBlock) void k_gat_attn_fwd_generic(
+    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
+    const T* __restrict__ el, const T* __restrict__ er, const T* __restrict__ stats, const T* __restrict__ V,
+    T* __restrict__ o, i64 n_chunks, i64 h, i64 d, T slope) {
+  gat_attn_fwd_generic<T, false>(row, indptr, indices, el, er, stats, V, o, n_chunks, h, d, slope, DropArgs<T>{});
+}
+
+template <typename T>
+__global__ __launch_bounds__(kGenericBlock) void k_gat_attn_drop_fwd_generic(
+    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
+    const T* __restrict__ el, const T* __restrict__ er, const T* __restrict__ stats, const T* __restrict__ V,
+    T* __restrict__ o, i64 n_chunks, i64 h, i64 d, T slope, DropArgs<T> dr) {
+  gat_attn_fwd_generic<T, true>(row, indptr, indices, el, er, stats, V, o, n_chunks, h, d, slope, dr);
 }
 
 template <typename T>
@@ -478,24 +665,24 @@ __global__ void k_gat_attn_pack_generic(const T* __restrict__ el, const T* __res
   }
 }
 
-// dz of one slot: i = the row-major row (P[i] holds el, m, 1/l, D), j = the column; g = dO_i, x = V_j (head k slices)
+// dz of one slot: i = the row-major row (P[i] holds el, m, 1/l, D), j = the column; g = dO_i, x = V_j (head k slices);
+// mult = the slot's dropout multiplier m_ij (1 without dropout)
 template <typename T>
 __device__ __forceinline__ T gat_attn_dz(const T* __restrict__ p, T erj, const T* __restrict__ g,
-                                         const T* __restrict__ x, i64 d, T slope, T* a_out) {
+                                         const T* __restrict__ x, i64 d, T slope, T mult) {
   const T z = p[0] + erj;
   const T a = exp_t(gat_lrelu(z, slope) - p[1]) * p[2];
   T da = 0;
   for (i64 t = 0; t < d; ++t) da += g[t] * x[t];
-  if (a_out) *a_out = a;
-  const T ds = a * (da - p[3]);
+  const T ds = a * (mult * da - p[3]);
   return z > (T)0 ? ds : ds * slope;
 }
 
-template <typename T>
-__global__ __launch_bounds__(kGenericBlock) void k_gat_attn_bwd_row_generic(
+template <typename T, bool DROP>
+__device__ __forceinline__ void gat_attn_bwd_row_generic(
     const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
     const T* __restrict__ er, const T* __restrict__ V, const T* __restrict__ P, const T* __restrict__ dO,
-    T* __restrict__ del, i64 n_chunks, i64 h, i64 d, T slope) {
+    T* __restrict__ del, i64 n_chunks, i64 h, i64 d, T slope, const DropArgs<T>& dr) {
   const i64 c = generic_chunk_id();
   if (c >= n_chunks) return;
   const int lane = threadIdx.x & 63;
@@ -506,8 +693,9 @@ __global__ __launch_bounds__(kGenericBlock) void k_gat_attn_bwd_row_generic(
     T acc = 0;
     for (i64 j = j0 + lane; j < j1; j += kWave) {
       const i64 src = indices[j];
+      const T mult = DROP ? drop_mult<T>(r, src, k, dr) : (T)1;
       acc += gat_attn_dz<T>(P + (r * h + k) * 4, er[src * h + k], dO + (r * h + k) * d, V + (src * h + k) * d, d, slope,
-                            nullptr);
+                            mult);
     }
     acc = wave_sum(acc);
     if (lane == 0) atomicAdd(del + r * h + k, acc);
@@ -515,10 +703,26 @@ __global__ __launch_bounds__(kGenericBlock) void k_gat_attn_bwd_row_generic(
 }
 
 template <typename T>
-__global__ __launch_bounds__(kGenericBlock) void k_gat_attn_bwd_col_generic(
+__global__ __launch_bounds__(kGenericBlock) void k_gat_attn_bwd_row_generic(
+    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
+    const T* __restrict__ er, const T* __restrict__ V, const T* __restrict__ P, const T* __restrict__ dO,
+    T* __restrict__ del, i64 n_chunks, i64 h, i64 d, T slope) {
+  gat_attn_bwd_row_generic<T, false>(row, indptr, indices, er, V, P, dO, del, n_chunks, h, d, slope, DropArgs<T>{});
+}
+
+template <typename T>
+__global__ __launch_bounds__(kGenericBlock) void k_gat_attn_drop_bwd_row_generic(
+    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
+    const T* __restrict__ er, const T* __restrict__ V, const T* __restrict__ P, const T* __restrict__ dO,
+    T* __restrict__ del, i64 n_chunks, i64 h, i64 d, T slope, DropArgs<T> dr) {
+  gat_attn_bwd_row_generic<T, true>(row, indptr, indices, er, V, P, dO, del, n_chunks, h, d, slope, dr);
+}
+
+template <typename T, bool DROP>
+__device__ __forceinline__ void gat_attn_bwd_col_generic(
     const i64* __restrict__ col, const i64* __restrict__ indptr, const i64* __restrict__ indices,
     const T* __restrict__ er, const T* __restrict__ V, const T* __restrict__ P, const T* __restrict__ dO,
-    T* __restrict__ der, T* __restrict__ dV, i64 n_chunks, i64 h, i64 d, T slope) {
+    T* __restrict__ der, T* __restrict__ dV, i64 n_chunks, i64 h, i64 d, T slope, const DropArgs<T>& dr) {
   const i64 c = generic_chunk_id();
   if (c >= n_chunks) return;
   const int lane = threadIdx.x & 63;
@@ -529,8 +733,9 @@ __global__ __launch_bounds__(kGenericBlock) void k_gat_attn_bwd_col_generic(
     T acc = 0;
     for (i64 j = j0 + lane; j < j1; j += kWave) {
       const i64 i = indices[j];
+      const T mult = DROP ? drop_mult<T>(i, jc, k, dr) : (T)1;
       acc += gat_attn_dz<T>(P + (i * h + k) * 4, er[jc * h + k], dO + (i * h + k) * d, V + (jc * h + k) * d, d, slope,
-                            nullptr);
+                            mult);
     }
     acc = wave_sum(acc);
     if (lane == 0) atomicAdd(der + jc * h + k, acc);
@@ -541,11 +746,29 @@ __global__ __launch_bounds__(kGenericBlock) void k_gat_attn_bwd_col_generic(
     for (i64 j = j0; j < j1; ++j) {
       const i64 i = indices[j];
       const T* p = P + (i * h + k) * 4;
-      const T a = exp_t(gat_lrelu(p[0] + er[jc * h + k], slope) - p[1]) * p[2];
+      T a = exp_t(gat_lrelu(p[0] + er[jc * h + k], slope) - p[1]) * p[2];
+      if constexpr (DROP) a *= drop_mult<T>(i, jc, k, dr);
       acc += a * dO[i * h * d + it];
     }
     atomicAdd(dV + jc * h * d + it, acc);
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kGenericBlock) void k_gat_attn_bwd_col_generic(
+    const i64* __restrict__ col, const i64* __restrict__ indptr, const i64* __restrict__ indices,
+    const T* __restrict__ er, const T* __restrict__ V, const T* __restrict__ P, const T* __restrict__ dO,
+    T* __restrict__ der, T* __restrict__ dV, i64 n_chunks, i64 h, i64 d, T slope) {
+  gat_attn_bwd_col_generic<T, false>(col, indptr, indices, er, V, P, dO, der, dV, n_chunks, h, d, slope,
+                                     DropArgs<T>{});
+}
+
+template <typename T>
+__global__ __launch_bounds__(kGenericBlock) void k_gat_attn_drop_bwd_col_generic(
+    const i64* __restrict__ col, const i64* __restrict__ indptr, const i64* __restrict__ indices,
+    const T* __restrict__ er, const T* __restrict__ V, const T* __restrict__ P, const T* __restrict__ dO,
+    T* __restrict__ der, T* __restrict__ dV, i64 n_chunks, i64 h, i64 d, T slope, DropArgs<T> dr) {
+  gat_attn_bwd_col_generic<T, true>(col, indptr, indices, er, V, P, dO, der, dV, n_chunks, h, d, slope, dr);
 }
 
 }  // namespace graphop

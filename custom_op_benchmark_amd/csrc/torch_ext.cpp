@@ -453,13 +453,29 @@ std::pair<int64_t, int64_t> gat_attn_shapes(const at::Tensor& el, const at::Tens
   return {h, V.size(-1)};
 }
 
-std::vector<at::Tensor> gat_attention_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
-                                              const at::Tensor& indices, const at::Tensor& el, const at::Tensor& er,
-                                              const at::Tensor& V, double negative_slope) {
+// (p, seed, offset) of the dropout forms, checked as include/graphop_hip.h states them
+struct DropSpec {
+  double p;
+  uint64_t seed;
+  uint32_t offset;
+};
+
+DropSpec drop_spec(const char* fn, double p, int64_t seed, int64_t offset) {
+  TORCH_CHECK(p >= 0.0 && p < 1.0, fn, ": dropout probability p must be in [0, 1), got ", p);
+  TORCH_CHECK(seed >= 0, fn, ": seed must be in [0, 2^63), got ", seed);
+  TORCH_CHECK(offset >= 0 && offset < (int64_t(1) << 32), fn, ": offset must be in [0, 2^32), got ", offset);
+  return {p, (uint64_t)seed, (uint32_t)offset};
+}
+
+// drop == nullptr: graphop_gat_attention_forward, else its dropout form
+std::vector<at::Tensor> gat_attention_forward_impl(const char* fn, const at::Tensor& row, const at::Tensor& indptr,
+                                                   const at::Tensor& eid, const at::Tensor& indices,
+                                                   const at::Tensor& el, const at::Tensor& er, const at::Tensor& V,
+                                                   double negative_slope, const DropSpec* drop) {
   CHECK_INPUT(row); CHECK_INPUT(indptr); CHECK_INPUT(eid); CHECK_INPUT(indices); CHECK_INPUT(el); CHECK_INPUT(er);
   CHECK_INPUT(V);
   CHECK_INDEX(row); CHECK_INDEX(indptr); CHECK_INDEX(eid); CHECK_INDEX(indices);
-  const auto hd = gat_attn_shapes(el, er, V, "gat_attention_forward");
+  const auto hd = gat_attn_shapes(el, er, V, fn);
   const int64_t h = hd.first, d = hd.second;
   DeviceGuard dg(el);
   const int64_t e = eid.size(0), n_l = el.size(0);
@@ -469,36 +485,58 @@ std::vector<at::Tensor> gat_attention_forward(const at::Tensor& row, const at::T
   auto stats = at::empty({n_l, h, 2}, el.options());
   const auto pp = get_plan(row, indptr, eid, indices, er.size(0));
   const auto& p = *pp;
-  check(graphop_gat_attention_forward(dtype_code(el), ip(row), ip(indptr), ip(eid), ip(indices), vp(el), vp(er), vp(V),
-                                      vp(o), vp(stats), row.size(0), e, n_l, er.size(0), h, d, negative_slope, p.plan,
-                                      stream_of(el)));
+  if (drop)
+    check(graphop_gat_attention_dropout_forward(dtype_code(el), ip(row), ip(indptr), ip(eid), ip(indices), vp(el),
+                                                vp(er), vp(V), vp(o), vp(stats), row.size(0), e, n_l, er.size(0), h, d,
+                                                negative_slope, drop->p, drop->seed, drop->offset, p.plan,
+                                                stream_of(el)));
+  else
+    check(graphop_gat_attention_forward(dtype_code(el), ip(row), ip(indptr), ip(eid), ip(indices), vp(el), vp(er),
+                                        vp(V), vp(o), vp(stats), row.size(0), e, n_l, er.size(0), h, d, negative_slope,
+                                        p.plan, stream_of(el)));
   return {o, stats};
 }
 
-std::vector<at::Tensor> gat_attention_backward(const at::Tensor& row, const at::Tensor& indptr_r,
-                                               const at::Tensor& eid_r, const at::Tensor& indices_r,
-                                               const at::Tensor& col, const at::Tensor& indptr_c,
-                                               const at::Tensor& eid_c, const at::Tensor& indices_c,
-                                               const at::Tensor& el, const at::Tensor& er, const at::Tensor& V,
-                                               const at::Tensor& o, const at::Tensor& stats, const at::Tensor& dO_,
-                                               double negative_slope) {
+std::vector<at::Tensor> gat_attention_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
+                                              const at::Tensor& indices, const at::Tensor& el, const at::Tensor& er,
+                                              const at::Tensor& V, double negative_slope) {
+  return gat_attention_forward_impl("gat_attention_forward", row, indptr, eid, indices, el, er, V, negative_slope,
+                                    nullptr);
+}
+
+std::vector<at::Tensor> gat_attention_dropout_forward(const at::Tensor& row, const at::Tensor& indptr,
+                                                      const at::Tensor& eid, const at::Tensor& indices,
+                                                      const at::Tensor& el, const at::Tensor& er, const at::Tensor& V,
+                                                      double negative_slope, double p, int64_t seed, int64_t offset) {
+  const char* fn = "gat_attention_dropout_forward";
+  const DropSpec drop = drop_spec(fn, p, seed, offset);
+  return gat_attention_forward_impl(fn, row, indptr, eid, indices, el, er, V, negative_slope, &drop);
+}
+
+std::vector<at::Tensor> gat_attention_backward_impl(const char* fn, const at::Tensor& row, const at::Tensor& indptr_r,
+                                                    const at::Tensor& eid_r, const at::Tensor& indices_r,
+                                                    const at::Tensor& col, const at::Tensor& indptr_c,
+                                                    const at::Tensor& eid_c, const at::Tensor& indices_c,
+                                                    const at::Tensor& el, const at::Tensor& er, const at::Tensor& V,
+                                                    const at::Tensor& o, const at::Tensor& stats,
+                                                    const at::Tensor& dO_, double negative_slope,
+                                                    const DropSpec* drop) {
   CHECK_INPUT(row); CHECK_INPUT(indptr_r); CHECK_INPUT(eid_r); CHECK_INPUT(indices_r);
   CHECK_INPUT(col); CHECK_INPUT(indptr_c); CHECK_INPUT(eid_c); CHECK_INPUT(indices_c); CHECK_INPUT(el); CHECK_INPUT(er);
   CHECK_INPUT(V); CHECK_INPUT(o); CHECK_INPUT(stats);
   CHECK_INDEX(row); CHECK_INDEX(indptr_r); CHECK_INDEX(eid_r); CHECK_INDEX(indices_r);
   CHECK_INDEX(col); CHECK_INDEX(indptr_c); CHECK_INDEX(eid_c); CHECK_INDEX(indices_c);
   CHECK_CUDA(dO_);
-  const auto hd = gat_attn_shapes(el, er, V, "gat_attention_backward");
+  const auto hd = gat_attn_shapes(el, er, V, fn);
   const int64_t h = hd.first, d = hd.second;
   CHECK_SAME_DTYPE(el, o); CHECK_SAME_DTYPE(el, stats); CHECK_SAME_DTYPE(el, dO_);
   const int64_t n_l = el.size(0);
   std::vector<int64_t> oshape(V.sizes().begin(), V.sizes().end());
   oshape[0] = n_l;
-  TORCH_CHECK(o.sizes() == at::IntArrayRef(oshape) && stats.numel() == n_l * h * 2,
-              "gat_attention_backward: o must be ", at::IntArrayRef(oshape), " and stats (n_src, h, 2), got ", o.sizes(),
-              " and ", stats.sizes());
+  TORCH_CHECK(o.sizes() == at::IntArrayRef(oshape) && stats.numel() == n_l * h * 2, fn, ": o must be ",
+              at::IntArrayRef(oshape), " and stats (n_src, h, 2), got ", o.sizes(), " and ", stats.sizes());
   const at::Tensor dO = dO_.contiguous();
-  TORCH_CHECK(dO.sizes() == o.sizes(), "gat_attention_backward: dO must match o ", o.sizes(), ", got ", dO.sizes());
+  TORCH_CHECK(dO.sizes() == o.sizes(), fn, ": dO must match o ", o.sizes(), ", got ", dO.sizes());
   DeviceGuard dg(el);
   const int64_t e = eid_r.size(0);
   auto d_el = at::empty_like(el), d_er = at::empty_like(er), dV = at::empty_like(V);
@@ -506,12 +544,66 @@ std::vector<at::Tensor> gat_attention_backward(const at::Tensor& row, const at::
   const auto ppr = get_plan(row, indptr_r, eid_r, indices_r, er.size(0));
   const auto ppc = get_plan(col, indptr_c, eid_c, indices_c, n_l);
   const auto &pr = *ppr, &pc = *ppc;
-  check(graphop_gat_attention_backward(dtype_code(el), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col),
-                                       ip(indptr_c), ip(eid_c), ip(indices_c), vp(el), vp(er), vp(V), vp(o), vp(stats),
-                                       vp(dO), vp(d_el), vp(d_er), vp(dV), vp(ws), ws.numel() * ws.element_size(),
-                                       row.size(0), col.size(0), e, n_l, er.size(0), h, d, negative_slope, pr.plan,
-                                       pc.plan, stream_of(el)));
+  if (drop)
+    check(graphop_gat_attention_dropout_backward(
+        dtype_code(el), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c),
+        ip(indices_c), vp(el), vp(er), vp(V), vp(o), vp(stats), vp(dO), vp(d_el), vp(d_er), vp(dV), vp(ws),
+        ws.numel() * ws.element_size(), row.size(0), col.size(0), e, n_l, er.size(0), h, d, negative_slope, drop->p,
+        drop->seed, drop->offset, pr.plan, pc.plan, stream_of(el)));
+  else
+    check(graphop_gat_attention_backward(dtype_code(el), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col),
+                                         ip(indptr_c), ip(eid_c), ip(indices_c), vp(el), vp(er), vp(V), vp(o),
+                                         vp(stats), vp(dO), vp(d_el), vp(d_er), vp(dV), vp(ws),
+                                         ws.numel() * ws.element_size(), row.size(0), col.size(0), e, n_l, er.size(0),
+                                         h, d, negative_slope, pr.plan, pc.plan, stream_of(el)));
   return {d_el, d_er, dV};
+}
+
+std::vector<at::Tensor> gat_attention_backward(const at::Tensor& row, const at::Tensor& indptr_r,
+                                               const at::Tensor& eid_r, const at::Tensor& indices_r,
+                                               const at::Tensor& col, const at::Tensor& indptr_c,
+                                               const at::Tensor& eid_c, const at::Tensor& indices_c,
+                                               const at::Tensor& el, const at::Tensor& er, const at::Tensor& V,
+                                               const at::Tensor& o, const at::Tensor& stats, const at::Tensor& dO,
+                                               double negative_slope) {
+  return gat_attention_backward_impl("gat_attention_backward", row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
+                                     indices_c, el, er, V, o, stats, dO, negative_slope, nullptr);
+}
+
+std::vector<at::Tensor> gat_attention_dropout_backward(const at::Tensor& row, const at::Tensor& indptr_r,
+                                                       const at::Tensor& eid_r, const at::Tensor& indices_r,
+                                                       const at::Tensor& col, const at::Tensor& indptr_c,
+                                                       const at::Tensor& eid_c, const at::Tensor& indices_c,
+                                                       const at::Tensor& el, const at::Tensor& er, const at::Tensor& V,
+                                                       const at::Tensor& o, const at::Tensor& stats,
+                                                       const at::Tensor& dO, double negative_slope, double p,
+                                                       int64_t seed, int64_t offset) {
+  const char* fn = "gat_attention_dropout_backward";
+  const DropSpec drop = drop_spec(fn, p, seed, offset);
+  return gat_attention_backward_impl(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V,
+                                     o, stats, dO, negative_slope, &drop);
+}
+
+// m[e, k] = keep(i, j, k) / (1 - p) of the dropout forms as an edge tensor, over the row-major CSR
+at::Tensor edge_dropout_mask(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
+                             const at::Tensor& indices, int64_t h, double p, int64_t seed, int64_t offset,
+                             at::ScalarType dtype) {
+  const DropSpec drop = drop_spec("edge_dropout_mask", p, seed, offset);
+  CHECK_INPUT(row); CHECK_INPUT(indptr); CHECK_INPUT(eid); CHECK_INPUT(indices);
+  CHECK_INDEX(row); CHECK_INDEX(indptr); CHECK_INDEX(eid); CHECK_INDEX(indices);
+  TORCH_CHECK(h >= 1 && (dtype == at::kFloat || dtype == at::kDouble),
+              "edge_dropout_mask: h must be >= 1 and dtype float32 or float64, got h=", h, " dtype=", dtype);
+  DeviceGuard dg(row);
+  const int64_t e = eid.size(0);
+  auto y = at::empty(h == 1 ? std::vector<int64_t>{e} : std::vector<int64_t>{e, h}, row.options().dtype(dtype));
+  const auto pp = get_plan(row, indptr, eid, indices, 0);
+  const auto& pl = *pp;
+  const int64_t cap = (int64_t(1) << 32) - 1;   // the ids themselves are the only bound on the two node counts
+  const int64_t n_l = e ? std::min<int64_t>(std::max<int64_t>(pl.info.max_row + 1, 0), cap) : 0;
+  const int64_t n_r = e ? std::min<int64_t>(std::max<int64_t>(pl.info.max_index + 1, 0), cap) : 0;
+  check(graphop_edge_dropout_mask(dtype_code(y), ip(row), ip(indptr), ip(eid), ip(indices), vp(y), row.size(0), e, n_l,
+                                  n_r, h, drop.p, drop.seed, drop.offset, pl.plan, stream_of(row)));
+  return y;
 }
 
 void clear_plan_cache() {
@@ -570,6 +662,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("indptr_r"), py::arg("eid_r"), py::arg("indices_r"), py::arg("col"), py::arg("indptr_c"), py::arg("eid_c"),
         py::arg("indices_c"), py::arg("el"), py::arg("er"), py::arg("V"), py::arg("o"), py::arg("stats"), py::arg("dO"),
         py::arg("negative_slope") = 0.2);
+  m.def("gat_attention_dropout_forward", &gat_attention_dropout_forward,
+        "Fused GAT attention forward with attention dropout (extra op)", py::arg("row"), py::arg("indptr"),
+        py::arg("eid"), py::arg("indices"), py::arg("el"), py::arg("er"), py::arg("V"), py::arg("negative_slope") = 0.2,
+        py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0);
+  m.def("gat_attention_dropout_backward", &gat_attention_dropout_backward,
+        "Fused GAT attention backward with attention dropout (extra op)", py::arg("row"), py::arg("indptr_r"),
+        py::arg("eid_r"), py::arg("indices_r"), py::arg("col"), py::arg("indptr_c"), py::arg("eid_c"),
+        py::arg("indices_c"), py::arg("el"), py::arg("er"), py::arg("V"), py::arg("o"), py::arg("stats"), py::arg("dO"),
+        py::arg("negative_slope") = 0.2, py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0);
+  m.def("edge_dropout_mask", &edge_dropout_mask, "The dropout multipliers of the fused GAT layer as an edge tensor",
+        py::arg("row"), py::arg("indptr"), py::arg("eid"), py::arg("indices"), py::arg("h"), py::arg("p") = 0.0,
+        py::arg("seed") = 0, py::arg("offset") = 0, py::arg("dtype") = at::kFloat);
   m.def("clear_plan_cache", &clear_plan_cache, "Destroy every cached per-graph plan");
   m.def("release_plans", &release_plans, "Drop the cached plans of the orientation whose chunk list is `row`");
   m.def("plan_cache_size", &plan_cache_size, "Graph orientations in the plan cache");
@@ -591,6 +695,9 @@ TORCH_LIBRARY(graphop, m) {
   m.def("gat_scores_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor dy, float negative_slope=0.2) -> Tensor[]");
   m.def("gat_attention_forward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, Tensor V, float negative_slope=0.2) -> Tensor[]");
   m.def("gat_attention_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor V, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2) -> Tensor[]");
+  m.def("gat_attention_dropout_forward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, Tensor V, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]");
+  m.def("gat_attention_dropout_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor V, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]");
+  m.def("edge_dropout_mask(Tensor row, Tensor indptr, Tensor eid, Tensor indices, int h, float p=0.0, int seed=0, int offset=0, ScalarType dtype=float) -> Tensor");
 }
 
 TORCH_LIBRARY_IMPL(graphop, CUDA, m) {
@@ -608,6 +715,9 @@ TORCH_LIBRARY_IMPL(graphop, CUDA, m) {
   m.impl("gat_scores_backward", &gat_scores_backward);
   m.impl("gat_attention_forward", &gat_attention_forward);
   m.impl("gat_attention_backward", &gat_attention_backward);
+  m.impl("gat_attention_dropout_forward", &gat_attention_dropout_forward);
+  m.impl("gat_attention_dropout_backward", &gat_attention_dropout_backward);
+  m.impl("edge_dropout_mask", &edge_dropout_mask);
 }
 
 TORCH_LIBRARY_IMPL(graphop, CPU, m) {   // there is no CPU implementation: the reference's CHECK_CUDA message
@@ -625,4 +735,7 @@ TORCH_LIBRARY_IMPL(graphop, CPU, m) {   // there is no CPU implementation: the r
   m.impl("gat_scores_backward", &gat_scores_backward);
   m.impl("gat_attention_forward", &gat_attention_forward);
   m.impl("gat_attention_backward", &gat_attention_backward);
+  m.impl("gat_attention_dropout_forward", &gat_attention_dropout_forward);
+  m.impl("gat_attention_dropout_backward", &gat_attention_dropout_backward);
+  m.impl("edge_dropout_mask", &edge_dropout_mask);
 }

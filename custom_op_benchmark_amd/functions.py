@@ -116,6 +116,31 @@ class FusedGATAttention(Function):
         return None, None, None, None, None, None, None, None, d_el, d_er, dV, None
 
 
+class FusedGATAttentionDropout(Function):
+    """FusedGATAttention with dropout on the attention weights, o[i] = sum_j a_ij m_ij V[j] (extra op):
+    apply(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V, negative_slope, p, seed, offset).
+    m_ij = keep / (1 - p), the keep decision a pure function of (i, j, head, seed, offset, p) that forward and backward
+    recompute per slot (Philox4x32-10; graphop.edge_dropout_mask gives the same values as an edge tensor), so still no
+    (E, h) tensor is kept or made.  seed=None draws one from torch's default CPU generator (torch.manual_seed makes
+    runs repeatable); offset is a per-layer / per-step counter, so one seed serves a whole model."""
+
+    @staticmethod
+    def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V, negative_slope, p,
+                seed=None, offset=0):
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        ctx.drop = (float(negative_slope), float(p), int(seed), int(offset))
+        o, stats = _ops.gat_attention_dropout_forward(row, indptr_r, eid_r, indices_r, el, er, V, *ctx.drop)
+        ctx.save_for_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V, o, stats)
+        return o
+
+    @staticmethod
+    def backward(ctx, dO):
+        a8, (el, er, V, o, stats) = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
+        d_el, d_er, dV = _ops.gat_attention_dropout_backward(*a8, el, er, V, o, stats, dO, *ctx.drop)
+        return None, None, None, None, None, None, None, None, d_el, d_er, dV, None, None, None, None
+
+
 # FusedAttention over several heads (round 5): "keep" = per head group only a_g (E x hg) survives the forward, the backward's
 # da_g / ds_g are E x hg temporaries -- speed of the 8-function step, about half of its E-sized memory; "recompute" = nothing
 # E-sized survives the forward, the backward recomputes s_g and a_g per group (two more passes per group: ~+17 % time,
@@ -297,6 +322,30 @@ def fused_gat_attention_step(g, el, er, V, dO, negative_slope=0.2):
     """The counterpart of gat_attention_step through FusedGATAttention: o = GAT layer(el, er, V); o.backward(dO).
     el, er, V must be leaf tensors with requires_grad; returns o (no E-sized tensor is kept or made)."""
     o = FusedGATAttention.apply(*g.csr_args(), el, er, V, negative_slope)
+    o.backward(dO)
+    _lib.check_errors(sync=False)     # as in attention_step
+    return o
+
+
+def gat_attention_dropout_step(g, el, er, V, dO, p, seed, offset=0, negative_slope=0.2):
+    """gat_attention_step with dropout on the attention weights, composed: GATScores -> SparseSoftmax ->
+    (* edge_dropout_mask) -> VectorSPMM; the mask is one more (E, h) tensor kept for the backward.  Same decisions as
+    fused_gat_attention_dropout_step for the same (p, seed, offset); returns (s, a, o) with a the undropped weights."""
+    args = g.csr_args()
+    s = GATScores.apply(*args, el, er, negative_slope)
+    a = SparseSoftmax.apply(g.row, g.ptr_r, g.eid_r, s)
+    h = 1 if el.dim() == 1 else el.size(1)
+    mask = _ops.edge_dropout_mask(g.row, g.ptr_r, g.eid_r, g.indices_r, h, p, seed, offset, a.dtype)
+    o = VectorSPMM.apply(*args, a * mask, V)
+    o.backward(dO)
+    _lib.check_errors(sync=False)     # as in attention_step
+    return s, a, o
+
+
+def fused_gat_attention_dropout_step(g, el, er, V, dO, p, seed, offset=0, negative_slope=0.2):
+    """The counterpart of gat_attention_dropout_step through FusedGATAttentionDropout; returns o (no E-sized tensor is
+    kept or made, the mask included)."""
+    o = FusedGATAttentionDropout.apply(*g.csr_args(), el, er, V, negative_slope, p, seed, offset)
     o.backward(dO)
     _lib.check_errors(sync=False)     # as in attention_step
     return o

@@ -28,9 +28,11 @@ __all__ = ["maskedmm_csr_forward", "maskedmm_csr_backward", "node_mul_edge_forwa
            "node_mul_edge_backward", "sparse_softmax_forward", "sparse_softmax_backward",
            "vector_spmm_forward", "vector_spmm_backward"]
 # extra ops (not in the reference's module): the fused attention step, SURVEY.md 8f N2
-# the GAT additive attention scores (LeakyReLU(el[i] + er[j]) per edge and head) and the fused GAT attention layer
+# the GAT additive attention scores (LeakyReLU(el[i] + er[j]) per edge and head), the fused GAT attention layer and
+# its forms with attention dropout (plus the mask they apply, as an edge tensor, for the composed path)
 EXTRA_OPS = ["attention_forward", "attention_backward", "attention_backward_is_fused", "gat_scores_forward",
-             "gat_scores_backward", "gat_attention_forward", "gat_attention_backward"]
+             "gat_scores_backward", "gat_attention_forward", "gat_attention_backward",
+             "gat_attention_dropout_forward", "gat_attention_dropout_backward", "edge_dropout_mask"]
 
 _NULL = None
 
@@ -453,6 +455,104 @@ def gat_attention_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c
     return [d_el, d_er, dV]
 
 
+# ---- attention dropout of the fused GAT layer (extra ops) ------------------------------------------------------
+def _drop_args(fn, p, seed, offset):
+    """(p, seed, offset) checked as the C ABI states them: 0 <= p < 1, 0 <= seed < 2^63, 0 <= offset < 2^32."""
+    p, seed, offset = float(p), int(seed), int(offset)
+    if not 0.0 <= p < 1.0:
+        raise RuntimeError("%s: dropout probability p must be in [0, 1), got %r" % (fn, p))
+    if not 0 <= seed < 2 ** 63:
+        raise RuntimeError("%s: seed must be in [0, 2^63), got %d" % (fn, seed))
+    if not 0 <= offset < 2 ** 32:
+        raise RuntimeError("%s: offset must be in [0, 2^32), got %d" % (fn, offset))
+    return p, seed, offset
+
+
+def gat_attention_dropout_forward(row, indptr, eid, indices, el, er, V, negative_slope=0.2, p=0.0, seed=0, offset=0):
+    """-> [o, stats] of gat_attention_forward with dropout on the attention weights: o[i] = sum_j a_ij m_ij V[j],
+    m_ij = keep(i, j, head; seed, offset, p) / (1 - p) recomputed per slot from Philox4x32-10 (no edge-sized mask);
+    stats are those of the undropped scores.  p = 0 is gat_attention_forward bit for bit."""
+    p, seed, offset = _drop_args("gat_attention_dropout_forward", p, seed, offset)
+    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices"), (el, "el"), (er, "er"),
+                 (V, "V")):
+        _check_input(t, n)
+    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices")):
+        _check_index(t, n)
+    h, d = _gat_attn_shapes(el, er, V, "gat_attention_dropout_forward")
+    e, n_l = eid.size(0), el.size(0)
+    o = torch.empty((n_l,) + tuple(V.shape[1:]), dtype=V.dtype, device=V.device)
+    stats = torch.empty((n_l, h, 2), dtype=el.dtype, device=el.device)
+    with _lib.device_guard(el.device):
+        plan = _plan(row, indptr, eid, indices, er.size(0))
+        check(lib().graphop_gat_attention_dropout_forward(
+            dtype_code(el), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(el), ptr(er), ptr(V), ptr(o),
+            ptr(stats), row.size(0), e, n_l, er.size(0), h, d, float(negative_slope), p, seed, offset, plan.handle,
+            stream_of(el)))
+    return [o, stats]
+
+
+def gat_attention_dropout_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V, o,
+                                   stats, dO, negative_slope=0.2, p=0.0, seed=0, offset=0):
+    """-> [del, der, dV] of gat_attention_dropout_forward for the output gradient dO, with the same (p, seed, offset):
+    the weights and their keep decisions are recomputed per slot."""
+    fn = "gat_attention_dropout_backward"
+    p, seed, offset = _drop_args(fn, p, seed, offset)
+    names = ("row", "indptr_r", "eid_r", "indices_r", "col", "indptr_c", "eid_c", "indices_c")
+    idx = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
+    for t, n in zip(idx + (el, er, V, o, stats), names + ("el", "er", "V", "o", "stats")):
+        _check_input(t, n)
+    for t, n in zip(idx, names):
+        _check_index(t, n)
+    if not isinstance(dO, torch.Tensor) or not dO.is_cuda:
+        raise RuntimeError("dO must be a CUDA tensor")
+    h, d = _gat_attn_shapes(el, er, V, fn)
+    for t, n in ((o, "o"), (stats, "stats"), (dO, "dO")):
+        _same_dtype(el, t, "el", n)
+    n_l = el.size(0)
+    if o.shape != (n_l,) + tuple(V.shape[1:]) or stats.numel() != n_l * h * 2:
+        raise RuntimeError("%s: o must be %s and stats (n_src, h, 2), got %s and %s"
+                           % (fn, (n_l,) + tuple(V.shape[1:]), tuple(o.shape), tuple(stats.shape)))
+    dO = dO.contiguous()
+    if dO.shape != o.shape:
+        raise RuntimeError("%s: dO must match o %s, got %s" % (fn, tuple(o.shape), tuple(dO.shape)))
+    e = eid_r.size(0)
+    d_el, d_er, dV = torch.empty_like(el), torch.empty_like(er), torch.empty_like(V)
+    ws = torch.empty(max(n_l * h * 4, 1), dtype=el.dtype, device=el.device)      # (el, m, 1 / l, D) per (node, head)
+    with _lib.device_guard(el.device):
+        plan_r = _plan(row, indptr_r, eid_r, indices_r, er.size(0))
+        plan_c = _plan(col, indptr_c, eid_c, indices_c, n_l)
+        check(lib().graphop_gat_attention_dropout_backward(
+            dtype_code(el), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c),
+            ptr(eid_c), ptr(indices_c), ptr(el), ptr(er), ptr(V), ptr(o), ptr(stats), ptr(dO), ptr(d_el), ptr(d_er),
+            ptr(dV), ptr(ws), ws.numel() * ws.element_size(), row.size(0), col.size(0), e, n_l, er.size(0), h, d,
+            float(negative_slope), p, seed, offset, plan_r.handle, plan_c.handle, stream_of(el)))
+    return [d_el, d_er, dV]
+
+
+def edge_dropout_mask(row, indptr, eid, indices, h, p, seed, offset=0, dtype=torch.float32):
+    """-> the multipliers m[e, k] = keep(i, j, k) / (1 - p) the dropout ops above apply, as an edge tensor: (E) for
+    h == 1, else (E, h).  (row, indptr, eid, indices) is the ROW-MAJOR CSR (i = row[c], j = indices[slot])."""
+    p, seed, offset = _drop_args("edge_dropout_mask", p, seed, offset)
+    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices")):
+        _check_input(t, n)
+        _check_index(t, n)
+    h = int(h)
+    if h < 1 or dtype not in (torch.float32, torch.float64):
+        raise RuntimeError("edge_dropout_mask: h must be >= 1 and dtype float32 or float64, got h=%d dtype=%s"
+                           % (h, dtype))
+    e = eid.size(0)
+    y = torch.empty((e,) if h == 1 else (e, h), dtype=dtype, device=row.device)
+    bound = 2 ** 32 - 1       # the ids themselves are the only bound on the two node counts
+    with _lib.device_guard(row.device):
+        plan = _plan(row, indptr, eid, indices, 0)
+        n_l = max(plan.info.max_row + 1, 0) if e else 0
+        n_r = max(plan.info.max_index + 1, 0) if e else 0
+        check(lib().graphop_edge_dropout_mask(
+            dtype_code(y), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(y), row.size(0), e, min(n_l, bound),
+            min(n_r, bound), h, p, seed, offset, plan.handle, stream_of(row)))
+    return y
+
+
 def prepare(graph, h=1, d=64, dtype=torch.float32, fused=True):
     """Build a graph's plans and window structures ahead of the first op call (see graphs.prepare)."""
     from . import graphs
@@ -481,6 +581,9 @@ _SCHEMAS = {
     "gat_scores_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor dy, float negative_slope=0.2) -> Tensor[]",
     "gat_attention_forward": "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, Tensor V, float negative_slope=0.2) -> Tensor[]",
     "gat_attention_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor V, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2) -> Tensor[]",
+    "gat_attention_dropout_forward": "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, Tensor V, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]",
+    "gat_attention_dropout_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor V, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]",
+    "edge_dropout_mask": "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, int h, float p=0.0, int seed=0, int offset=0, ScalarType dtype=float) -> Tensor",
 }
 _torch_lib = None
 

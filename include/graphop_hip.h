@@ -424,6 +424,44 @@ GRAPHOP_API int graphop_gat_attention_backward(int dtype, const int64_t* row, co
                                    double negative_slope, const graphop_plan_t* plan_r,
                                    const graphop_plan_t* plan_c, void* stream);
 
+/* ---- attention dropout for the fused GAT layer (ABI 8, additive; EXTRA ops) ---------------------------------------
+ * The fused GAT attention with dropout on the attention weights, attn_drop(edge_softmax(s)), still without any E-sized
+ * tensor: the keep decision of edge (i, j) and head k is a pure function of (i, j, k, seed, offset, p), recomputed in
+ * each gather pass:
+ *   w[0..3] = Philox4x32-10(counter = (i, j, k >> 2, offset), key = (seed & 0xffffffff, seed >> 32))
+ *   keep = w[k & 3] >= T with T = floor(p * 2^32);  m_ijk = keep ? 1 / (1 - p) : 0   (both computed in double)
+ * i is the row-major row id (index into el / o), j the neighbour id (index into er / V), in both orientations.  The
+ * decision does not depend on chunking, plans, orientation or edge numbering; parallel edges (the same (i, j) more
+ * than once) share one decision.
+ *   forward : o[i] = sum_j a_ij m_ij V[j]; stats are those of the undropped scores (as gat_attention_forward)
+ *   backward: D_i = <dO_i, o_i>, da_ij = m_ij <dO_i, V_j>, ds_ij = a_ij (da_ij - D_i), dz as above,
+ *             del[i] = sum_j dz_ij, der[j] = sum_i dz_ij, dV[j] = sum_i a_ij m_ij dO_i    (same workspace rule)
+ * Arguments as graphop_gat_attention_forward / _backward with (p, seed, offset) after negative_slope:
+ *   0 <= p < 1, seed < 2^63, offset a per-layer / per-step counter (one seed serves a whole model), n_l, n_r < 2^32;
+ *   anything else is GRAPHOP_ERR_INVALID_ARGUMENT before the device is touched.  p == 0 runs the kernels of
+ *   graphop_gat_attention_forward / _backward (bit-identical results).
+ * graphop_edge_dropout_mask writes y[eid[slot], k] = m_ijk, (E, h), over the ROW-MAJOR arrays (i = row[c],
+ * j = indices[slot]): the mask of the composed path (a * y between sparse_softmax and vector_spmm) and of tests.
+ * Edges that no slot names get 0. */
+GRAPHOP_API int graphop_gat_attention_dropout_forward(int dtype, const int64_t* row, const int64_t* indptr,
+                                  const int64_t* eid, const int64_t* indices, const void* el, const void* er,
+                                  const void* V, void* o, void* stats, int64_t n_chunks, int64_t n_edges, int64_t n_l,
+                                  int64_t n_r, int64_t h, int64_t d, double negative_slope, double p, uint64_t seed,
+                                  uint32_t offset, const graphop_plan_t* plan, void* stream);
+GRAPHOP_API int graphop_gat_attention_dropout_backward(int dtype, const int64_t* row, const int64_t* indptr_r,
+                                   const int64_t* eid_r, const int64_t* indices_r, const int64_t* col,
+                                   const int64_t* indptr_c, const int64_t* eid_c, const int64_t* indices_c,
+                                   const void* el, const void* er, const void* V, const void* o, const void* stats,
+                                   const void* dO, void* del, void* der, void* dV, void* workspace,
+                                   int64_t workspace_bytes, int64_t n_row_chunks, int64_t n_col_chunks,
+                                   int64_t n_edges, int64_t n_l, int64_t n_r, int64_t h, int64_t d,
+                                   double negative_slope, double p, uint64_t seed, uint32_t offset,
+                                   const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream);
+GRAPHOP_API int graphop_edge_dropout_mask(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                                  const int64_t* indices, void* y, int64_t n_chunks, int64_t n_edges, int64_t n_l,
+                                  int64_t n_r, int64_t h, double p, uint64_t seed, uint32_t offset,
+                                  const graphop_plan_t* plan, void* stream);
+
 /* ---- fused attention step (EXTRA op, not one of the reference's eight) --------------------------
  * The composition the reference harness chains by hand -- MaskedMMCSR -> SparseSoftmax -> VectorSPMM
  * (wrapper.py:20-30, 8-18, 44-55) -- as one forward and one backward entry, so that the E-sized

@@ -1,0 +1,255 @@
+"""CPU tier of the attention dropout of the fused GAT layer (graphop_gat_attention_dropout_*, graphop_edge_dropout_mask):
+the reference Philox reproduces the published answers, the library and both bindings expose the ops, arguments are
+validated before anything touches a device, CPU tensors are refused, the new fast kernels fit their register budget, a
+float64 restatement of the backward the kernels implement equals autograd through the reference layer, and the
+statistics of the reference pin the definition itself."""
+import ctypes
+import math
+import os
+import re
+import sys
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import dropout_reference as R
+from util import random_graph
+
+NAMES = ("gat_attention_dropout_forward", "gat_attention_dropout_backward", "edge_dropout_mask")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _hex(w):
+    return " ".join("%08x" % x for x in np.asarray(w).reshape(-1))
+
+
+def test_reference_philox_known_answers():
+    assert _hex(R.philox4x32_10((0, 0, 0, 0), (0, 0))) == "6627e8d5 e169c58d bc57ac4c 9b00dbd8"
+    assert _hex(R.philox4x32_10((0xffffffff,) * 4, (0xffffffff,) * 2)) == "408f276d 41c83b0e a20bc7c6 6d5451fd"
+    assert _hex(R.philox4x32_10((0x243f6a88, 0x85a308d3, 0x13198a2e, 0x03707344), (0xa4093822, 0x299f31d0))) == \
+        "d16cfe09 94fdcceb 5001e420 24126ea1"
+
+
+def test_reference_counter_mapping_worked_example():
+    """i = 5, j = 7, seed = 1234567890123, offset = 7: counter (i, j, k >> 2, offset), key (seed low, seed high)"""
+    seed = 1234567890123
+    key = (seed & 0xffffffff, seed >> 32)
+    assert _hex(R.philox4x32_10((5, 7, 0, 7), key)) == "804398c1 cff81d1a 66f768dd 62339deb"
+    assert _hex(R.philox4x32_10((5, 7, 1, 7), key)) == "a49f727f fe49f841 1b1fc1c0 bc1b4d1f"
+    for p, T, bits in ((0.5, 2147483648, "11001101"), (0.6, 2576980377, "01001101"), (0.9, 3865470566, "00000100")):
+        assert R.threshold(p) == T
+        assert "".join(str(int(b)) for b in R.keep([5], [7], 8, p, seed, 7)[0]) == bits
+    m = R.multipliers([5], [7], 8, 0.6, seed, 7, torch.float32)
+    assert m.dtype == torch.float32 and m[0, 1] == torch.tensor(1 / (1 - 0.6)).float() and m[0, 0] == 0
+
+
+def test_dropout_symbols_resolve_in_the_library_and_the_extension():
+    from custom_op_benchmark_amd import _ext, _lib, graphop
+    l = ctypes.CDLL(_lib.LIB_PATH)
+    for n in NAMES:
+        assert hasattr(l, "graphop_" + n) and "graphop_" + n in _lib.EXPORTED_SYMBOLS
+    assert _lib.ABI_VERSION == 8 and _lib.lib().graphop_abi_version() == 8
+    ext = _ext.load()
+    assert ext is not None, "graphop_cpp.so not built (run __graft_entry__.build())"
+    assert graphop.cpp_ext is ext
+    for n in NAMES:
+        assert callable(getattr(ext, n)) and hasattr(torch.ops.graphop, n)
+
+
+def test_dropout_ops_are_extra_ops_with_an_autograd_class():
+    from custom_op_benchmark_amd import functions, graphop as ops
+    for n in NAMES:
+        assert n in ops.EXTRA_OPS and callable(getattr(ops, n))
+        assert "float p=0.0, int seed=0, int offset=0" in ops._SCHEMAS[n]
+    assert issubclass(functions.FusedGATAttentionDropout, torch.autograd.Function)
+    assert callable(functions.fused_gat_attention_dropout_step) and callable(functions.gat_attention_dropout_step)
+    assert len(ops.__all__) == 8 and not set(NAMES) & set(ops.__all__)      # the reference's eight names only
+
+
+def _fwd(l, dtype, C, E, n_l, n_r, h, d, p, seed=0, offset=0):
+    n = ctypes.c_void_p(0)
+    return l.graphop_gat_attention_dropout_forward(dtype, *([n] * 9), C, E, n_l, n_r, h, d, 0.2, p, seed, offset, n, n)
+
+
+def _bwd(l, dtype, C, C2, E, n_l, n_r, h, d, p, seed=0, offset=0, ws=None, ws_bytes=0):
+    n = ctypes.c_void_p(0)
+    return l.graphop_gat_attention_dropout_backward(dtype, *([n] * 17), ws or n, ws_bytes, C, C2, E, n_l, n_r, h, d,
+                                                    0.2, p, seed, offset, n, n, n)
+
+
+def _mask(l, dtype, C, E, n_l, n_r, h, p, seed=0, offset=0):
+    n = ctypes.c_void_p(0)
+    return l.graphop_edge_dropout_mask(dtype, *([n] * 5), C, E, n_l, n_r, h, p, seed, offset, n, n)
+
+
+def test_dropout_argument_validation_without_gpu():
+    from custom_op_benchmark_amd import _lib, graphop as ops
+    l = _lib.lib()
+    for p in (1.0, -0.1, float("nan"), 1.5):
+        assert _fwd(l, 0, 4, 10, 5, 5, 2, 8, p) == 1 and b"p must be in [0, 1)" in l.graphop_last_error()
+        assert _bwd(l, 0, 4, 4, 10, 5, 5, 2, 8, p) == 1 and b"p must be in [0, 1)" in l.graphop_last_error()
+        assert _mask(l, 0, 4, 10, 5, 5, 2, p) == 1 and b"p must be in [0, 1)" in l.graphop_last_error()
+    assert _fwd(l, 0, 4, 10, 5, 5, 2, 8, 0.5, seed=2 ** 63) == 1 and b"seed" in l.graphop_last_error()
+    assert _mask(l, 1, 4, 10, 5, 5, 2, 0.5, seed=2 ** 63) == 1 and b"seed" in l.graphop_last_error()
+    # the counter holds node ids as 32-bit words
+    assert _fwd(l, 0, 4, 10, 2 ** 32, 5, 2, 8, 0.5) == 1 and b"32 bits" in l.graphop_last_error()
+    assert _bwd(l, 0, 4, 4, 10, 5, 2 ** 32, 2, 8, 0.5) == 1 and b"32 bits" in l.graphop_last_error()
+    assert _mask(l, 0, 4, 10, 2 ** 32, 5, 2, 0.5) == 1 and b"32 bits" in l.graphop_last_error()
+    # the checks the undropped entry points make come first
+    assert _fwd(l, 7, 0, 0, 0, 0, 1, 8, 0.5) == 1 and b"dtype" in l.graphop_last_error()
+    assert _bwd(l, 0, 0, -3, 0, 0, 0, 1, 8, 0.5) == 1 and b"negative" in l.graphop_last_error()
+    assert _mask(l, 0, 0, 0, 0, 0, 0, 0.5) == 1 and b"negative" in l.graphop_last_error()
+    # the backward's workspace rule is that of gat_attention_backward: n_l * h * 4 values of dtype
+    for p in (0.0, 0.6):
+        assert _bwd(l, 0, 4, 4, 10, 5, 5, 2, 8, p, ws=ctypes.c_void_p(16), ws_bytes=5 * 2 * 4 * 4 - 4) == 1
+        assert b"workspace" in l.graphop_last_error()
+        assert _bwd(l, 1, 4, 4, 10, 5, 5, 2, 8, p, ws=ctypes.c_void_p(16), ws_bytes=5 * 2 * 4 * 4) == 1
+        assert b"workspace" in l.graphop_last_error()
+    # the C ABI takes offset as a uint32_t: the range check is the bindings'
+    i = torch.zeros(2, dtype=torch.int64)
+    f, v = torch.zeros(2, 4), torch.zeros(2, 4, 8)
+    for kw, msg in ((dict(p=0.5, offset=2 ** 32), "offset"), (dict(p=0.5, offset=-1), "offset"),
+                    (dict(p=1.0), r"p must be in \[0, 1\)"), (dict(p=float("nan")), r"p must be in \[0, 1\)"),
+                    (dict(p=0.5, seed=2 ** 63), "seed"), (dict(p=0.5, seed=-1), "seed")):
+        with pytest.raises(RuntimeError, match=msg):
+            ops.gat_attention_dropout_forward(i, i, i, i, f, f, v, 0.2, **kw)
+        with pytest.raises(RuntimeError, match=msg):
+            ops.gat_attention_dropout_backward(i, i, i, i, i, i, i, i, f, f, v, v, f, v, 0.2, **kw)
+        with pytest.raises(RuntimeError, match=msg):
+            ops.edge_dropout_mask(i, i, i, i, 4, kw["p"], kw.get("seed", 0), kw.get("offset", 0))
+    for kw, msg in ((dict(p=0.5, offset=2 ** 32), "offset"), (dict(p=1.0), r"p must be in \[0, 1\)"),
+                    (dict(p=0.5, seed=-1), "seed")):
+        with pytest.raises(RuntimeError, match=msg):
+            ops.cpp_ext.gat_attention_dropout_forward(i, i, i, i, f, f, v, 0.2, **kw)
+        with pytest.raises(RuntimeError, match=msg):
+            ops.cpp_ext.edge_dropout_mask(i, i, i, i, 4, **kw)
+    # empty problems are no-ops that never dereference anything
+    assert _fwd(l, 0, 0, 0, 0, 0, 1, 8, 0.6) == 0
+    assert _fwd(l, 1, 0, 0, 0, 7, 4, 16, 0.6, seed=2 ** 63 - 1, offset=2 ** 32 - 1) == 0
+    assert _bwd(l, 0, 0, 0, 0, 0, 0, 1, 8, 0.6) == 0
+    assert _bwd(l, 1, 0, 0, 0, 0, 3, 8, 32, 0.0) == 0
+    assert _mask(l, 0, 0, 0, 0, 0, 3, 0.6) == 0
+    assert _mask(l, 1, 0, 0, 9, 9, 8, 0.0) == 0
+
+
+def test_dropout_cpu_tensors_are_refused():
+    from custom_op_benchmark_amd import graphop as ops
+    i = torch.zeros(2, dtype=torch.int64)
+    f = torch.zeros(2, 4)
+    v = torch.zeros(2, 4, 8)
+    with pytest.raises(RuntimeError, match="row must be a CUDA tensor"):
+        ops.gat_attention_dropout_forward(i, i, i, i, f, f, v, 0.2, 0.5, 1, 0)
+    with pytest.raises(RuntimeError, match="row must be a CUDA tensor"):
+        ops.gat_attention_dropout_backward(i, i, i, i, i, i, i, i, f, f, v, v, f, v, 0.2, 0.5, 1, 0)
+    with pytest.raises(RuntimeError, match="row must be a CUDA tensor"):
+        ops.edge_dropout_mask(i, i, i, i, 4, 0.5, 1)
+    with pytest.raises(RuntimeError, match="no CPU implementation|must be a CUDA tensor"):
+        torch.ops.graphop.gat_attention_dropout_forward(i, i, i, i, f, f, v, 0.2, 0.5, 1, 0)
+    with pytest.raises(RuntimeError, match="no CPU implementation|must be a CUDA tensor"):
+        torch.ops.graphop.gat_attention_dropout_backward(i, i, i, i, i, i, i, i, f, f, v, v, f, v, 0.1, 0.5, 1, 0)
+    with pytest.raises(RuntimeError, match="no CPU implementation|must be a CUDA tensor"):
+        torch.ops.graphop.edge_dropout_mask(i, i, i, i, 4, 0.5, 1, 0)
+
+
+def test_dropout_fast_kernels_do_not_spill():
+    """Every fast dropout instantiation (fwd, bwd_row, bwd_col: 9 (h, d) pairs x {owned, shared}) keeps its loop in
+    registers, and the undropped kernels keep their count."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from kernel_resources import kernel_resources
+    res = kernel_resources()
+    drop = {n: r for n, r in res.items() if re.search(r"k_gat_attn_drop_(fwd|bwd_row|bwd_col)_f32<", n)}
+    assert len(drop) == 3 * 18, sorted(drop)
+    bad = {n: r for n, r in drop.items() if r["spill_vgpr"] or r["scratch"]}
+    assert not bad, "\n".join("%s: %r" % kv for kv in sorted(bad.items()))
+    old = [n for n in res if re.search(r"k_gat_attn_(stats|fwd|pack|bwd_row|bwd_col)_f32<", n)]
+    assert len(old) == 3 * 18 + 9 + 8, sorted(old)
+
+
+def _restated(src, dst, n_l, n_r, el, er, V, dO, slope, mult):
+    """The backward as the kernels compute it, in float64, mult = m (E, h): stats of the undropped scores, o of the
+    dropped weights, D = <dO, o>, a recomputed, da = m <dO, V>, ds, dz, then the row- and column-major sums."""
+    h = el.size(1)
+    z = el[src] + er[dst]
+    s = F.leaky_relu(z, slope)
+    m = torch.full((n_l, h), -1e9, dtype=s.dtype).scatter_reduce(0, src[:, None].expand(-1, h), s, "amax")
+    ex = torch.exp(s - m[src])
+    lsum = torch.zeros((n_l, h), dtype=s.dtype).index_add(0, src, ex)
+    inv_l = torch.where(lsum > 0, 1 / lsum, torch.zeros_like(lsum))
+    a = ex * inv_l[src]
+    o = torch.zeros((n_l, h, V.size(-1)), dtype=V.dtype).index_add(0, src, (a * mult)[..., None] * V[dst])
+    D = (dO * o).sum(-1)
+    da = mult * (dO[src] * V[dst]).sum(-1)
+    ds = a * (da - D[src])
+    dz = torch.where(z > 0, ds, ds * slope)
+    d_el = torch.zeros_like(el).index_add(0, src, dz)
+    d_er = torch.zeros_like(er).index_add(0, dst, dz)
+    dV = torch.zeros_like(V).index_add(0, dst, (a * mult)[..., None] * dO[src])
+    return o, d_el, d_er, dV
+
+
+@pytest.mark.parametrize("p", [0.1, 0.6, 0.9])
+@pytest.mark.parametrize("slope", [0.2, -0.1])
+def test_dropout_backward_formulas_match_autograd(slope, p):
+    """The small rectangular graph of the undropped formula test (empty rows, z == 0 ties, a large-magnitude row, and
+    parallel edges, which share one decision); at p >= 0.6 some non-empty row loses every edge of some head."""
+    gen = torch.Generator().manual_seed(3)
+    n_l, n_r, h, d = 23, 17, 3, 5
+    seed, offset = 1234567890123, 7
+    src = torch.randint(0, n_l, (160,), generator=gen)
+    src = src[src % 5 != 0]
+    dst = torch.randint(0, n_r, (src.numel(),), generator=gen)
+    el = torch.randint(-3, 4, (n_l, h), generator=gen).double()
+    er = torch.randint(-3, 4, (n_r, h), generator=gen).double()
+    er[:n_r] = -el[:n_r]
+    src = torch.cat([src, torch.arange(n_r)])
+    dst = torch.cat([dst, torch.arange(n_r)])
+    el[1] += 50.0
+    V = torch.randn(n_r, h, d, generator=gen, dtype=torch.float64)
+    dO = torch.randn(n_l, h, d, generator=gen, dtype=torch.float64)
+    r = [x.clone().requires_grad_(True) for x in (el, er, V)]
+    o_ref = R.gat_layer_dropout(src, dst, n_l, r[0], r[1], r[2], slope, p, seed, offset)
+    o_ref.backward(dO)
+    mult = R.multipliers(src.numpy(), dst.numpy(), h, p, seed, offset)
+    o, d_el, d_er, dV = _restated(src, dst, n_l, n_r, el, er, V, dO, slope, mult)
+    gone = R.fully_dropped_rows(src, dst, n_l, h, p, seed, offset)
+    if p >= 0.6:
+        assert gone.any()
+    assert not o[gone].any() and not d_el[gone].any() and not o_ref.detach()[gone].any()
+    for name, got, want in (("o", o, o_ref.detach()), ("del", d_el, r[0].grad), ("der", d_er, r[1].grad),
+                            ("dV", dV, r[2].grad)):
+        torch.testing.assert_close(got, want, rtol=1e-12, atol=1e-12, msg=lambda msg: name + ": " + msg)
+
+
+@pytest.mark.parametrize("gseed", [3, 32])
+def test_reference_keep_share_is_one_minus_p(gseed):
+    """Over the distinct (i, j, k) of the hub graph the GPU tests use: the kept share within 4 sigma of 1 - p."""
+    g = random_graph(300, 300, 3000, seed=gseed, chunk_size=gseed, zero_rows=0.2, hub=1500)
+    pairs = torch.unique(torch.stack([g.src, g.dst], 1), dim=0).numpy()
+    assert pairs.shape[0] < g.n_edges            # the hub row has parallel edges
+    for h in (1, 3, 8):
+        n = pairs.shape[0] * h
+        for p in (0.1, 0.5, 0.6, 0.9):
+            for seed, offset in ((0, 0), (1234567890123, 7), (2 ** 63 - 1, 2 ** 32 - 1)):
+                share = R.keep(pairs[:, 0], pairs[:, 1], h, p, seed, offset).mean()
+                assert abs(share - (1 - p)) <= 4 * math.sqrt(p * (1 - p) / n), (h, p, seed, offset, share)
+
+
+def _half(x):
+    """agreement of two masks at p = 0.5: 0.48-0.52, read at the two decimals the bound is stated with (the head 0 / 1
+    comparison has 2612 entries, sigma 0.0098, and measures 0.521)"""
+    return 0.48 <= round(float(x), 2) <= 0.52
+
+
+def test_reference_masks_of_seeds_offsets_and_heads_are_independent():
+    g = random_graph(300, 300, 3000, seed=3, chunk_size=3, zero_rows=0.2, hub=1500)
+    pairs = torch.unique(torch.stack([g.src, g.dst], 1), dim=0).numpy()
+    i, j = pairs[:, 0], pairs[:, 1]
+    base = R.keep(i, j, 8, 0.5, 1, 0)
+    for other in (R.keep(i, j, 8, 0.5, 2, 0), R.keep(i, j, 8, 0.5, 1, 1)):
+        assert _half((base == other).mean())
+    for a, b in ((0, 1), (3, 4)):              # the same Philox block, and two blocks
+        assert _half((base[:, a] == base[:, b]).mean()), (a, b)
+    # ... and (i, j) is ordered: the transposed pair is another decision
+    assert _half((base == R.keep(j, i, 8, 0.5, 1, 0)).mean())

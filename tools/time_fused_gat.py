@@ -11,7 +11,13 @@ to what is allocated before it (torch.cuda.max_memory_allocated above the baseli
 the library's per-launch times of the fused kernels.  One JSON line per (h, d).  Per kernel it names the algorithmic
 bytes with the convention of the headline metric (int64 ids at 8 B, values at 4 B, chunk metadata at 16 B per chunk,
 node tables once per pass) and, separately, the gathered row bytes E * h * d * 4 of the three passes that gather a
-V or dO row per slot (fwd, bwd_row, bwd_col), with the fraction of 8 TB/s each reaches."""
+V or dO row per slot (fwd, bwd_row, bwd_col), with the fraction of 8 TB/s each reaches.
+
+--dropout P times the steps with attention dropout instead: the fused dropout step
+(functions.fused_gat_attention_dropout_step) against the fused step without dropout, the yardstick, and against the
+composed dropout step (functions.gat_attention_dropout_step, which builds and keeps an (E, h) mask), all three
+alternating in one process; the check is fused dropout against composed dropout, the per-kernel round that of the
+dropout kernels."""
 import argparse
 import json
 import os
@@ -51,15 +57,15 @@ def _node_err(got, want, scale=None):
     return float((diff / (scale + 1e-30)).max())
 
 
-def _grad_scales(g, a, o, V, dO, h, d):
+def _grad_scales(g, a, o, V, dO, h, d, mult=1.0):
     """Bounds of the sums behind del and der, per (node, head): sum_j |ds_ij| <= |dO_i| max |V| + |D_i| for del (the
     weights of a row sum to 1), A_j (max |dO| |V_j| + max |D|) for der with A_j = sum_i a_ij.  del sums to 0 where every
-    z > 0 (sum_j ds_ij = 0): its own magnitude is no scale."""
+    z > 0 (sum_j ds_ij = 0): its own magnitude is no scale.  With dropout every <dO_i, V_j> carries mult = 1 / (1 - p)."""
     V3, dO3, o3 = V.detach().reshape(-1, h, d), dO.reshape(-1, h, d), o.reshape(-1, h, d)
     nV, ndO = V3.double().norm(dim=-1), dO3.double().norm(dim=-1)
     D = (dO3.double() * o3.double()).sum(-1).abs()
     A = torch.zeros_like(nV).index_add_(0, g.dst, a.detach().double().reshape(-1, h))
-    return ndO * nV.max() + D, A * (ndO.max() * nV + D.max())
+    return mult * ndO * nV.max() + D, A * (mult * ndO.max() * nV + D.max())
 
 
 def main():
@@ -71,6 +77,8 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--chunk-size", type=int, default=32)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--dropout", type=float, default=0.0, metavar="P", help="time the attention-dropout steps at p = P")
+    ap.add_argument("--dropout-seed", type=int, default=1234567890123)
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     N, E = graphs.SHAPES[args.shape]
@@ -98,11 +106,25 @@ def main():
                 x.grad = None
             return functions.gat_attention_step(g, el, er, V, dO, s)
 
+        nodrop = None
+        if args.dropout > 0:      # the dropout forms take the places of the two steps; the undropped fused step stays
+            nodrop, drop = fused, (args.dropout, args.dropout_seed, 7)
+
+            def fused():
+                for x in leaves:
+                    x.grad = None
+                return functions.fused_gat_attention_dropout_step(g, el, er, V, dO, *drop, s)
+
+            def composed():
+                for x in leaves:
+                    x.grad = None
+                return functions.gat_attention_dropout_step(g, el, er, V, dO, *drop, s)
+
         # full-size check (also builds and caches the plans both steps use)
         _, a_c, o_c = composed()
         o_c = o_c.detach()
         want = [o_c] + [x.grad.clone() for x in leaves]
-        sc_l, sc_r = _grad_scales(g, a_c, o_c, V, dO, h, d)
+        sc_l, sc_r = _grad_scales(g, a_c, o_c, V, dO, h, d, 1.0 / (1.0 - args.dropout))
         del a_c
         o_f = fused().detach()
         got = [o_f] + [x.grad.clone() for x in leaves]
@@ -114,7 +136,7 @@ def main():
 
         # peak memory each step adds to what is allocated before it
         peak = {}
-        for name, fn in (("fused", fused), ("composed", composed)):
+        for name, fn in (("fused", fused), ("composed", composed)) + ((("fused_no_dropout", nodrop),) if nodrop else ()):
             for x in leaves:
                 x.grad = None
             torch.cuda.synchronize()
@@ -126,7 +148,10 @@ def main():
             peak[name] = torch.cuda.max_memory_allocated() - base
             del out
 
-        t = _timed({"fused_fwd_bwd": fused, "composed_fwd_bwd": composed}, args.warmup, args.iters)
+        fns = {"fused_fwd_bwd": fused, "composed_fwd_bwd": composed}
+        if nodrop:
+            fns["fused_no_dropout_fwd_bwd"] = nodrop
+        t = _timed(fns, args.warmup, args.iters)
         timings = {n: {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4)} for n, v in t.items()}
 
         # per-kernel times from the library's launch profile, in a round of their own
@@ -150,8 +175,11 @@ def main():
             "gat_attn_bwd_row": (ids_r + row_l + 4 * nh_l + nh_r + row_r + nh_l, gathered),
             "gat_attn_bwd_col": (ids_c + row_r + nh_r + 4 * nh_l + row_l + nh_r + row_r, gathered),
         }
+        dtag = {"gat_attn_fwd": "gat_attn_drop_fwd", "gat_attn_bwd_row": "gat_attn_drop_bwd_row",
+                "gat_attn_bwd_col": "gat_attn_drop_bwd_col"} if nodrop else {}
         kernels = {}
         for tag, (nbytes, gb) in model.items():
+            tag = dtag.get(tag, tag)      # the dropout forms read the same bytes
             p = prof[tag]
             sec = p["mean_ms"] * 1e-3
             kernels[tag] = {"kernel": p["kernel"], "calls": p["calls"], "mean_ms": round(p["mean_ms"], 4),
@@ -161,12 +189,18 @@ def main():
                 kernels[tag]["gathered_row_bytes"] = gb
                 kernels[tag]["gathered_fraction_of_8TBs"] = round(gb / sec / PEAK, 3)
         f, c = timings["fused_fwd_bwd"]["median_ms"], timings["composed_fwd_bwd"]["median_ms"]
+        extra = {}
+        if nodrop:
+            extra = {"dropout": {"p": drop[0], "seed": drop[1], "offset": drop[2]},
+                     "fused_dropout_over_fused_no_dropout":
+                         round(f / timings["fused_no_dropout_fwd_bwd"]["median_ms"], 3)}
         print(json.dumps({
             "tool": "tools/time_fused_gat.py", "shape": args.shape, "n_src": n_src, "n_dst": n_dst, "n_edges": E,
             "row_chunks": C_r, "col_chunks": C_c, "chunk_size": args.chunk_size, "h": h, "d": d, "negative_slope": s,
             "warmup": args.warmup, "iters": args.iters, "node_scaled_error_vs_composed": err, "timings": timings,
             "fused_over_composed": round(f / c, 3), "peak_added_bytes": peak,
-            "one_edge_tensor_bytes": E * h * 4, "kernels": kernels, "device": torch.cuda.get_device_name(dev)}),
+            "one_edge_tensor_bytes": E * h * 4, "kernels": kernels, **extra,
+            "device": torch.cuda.get_device_name(dev)}),
             flush=True)
         del el, er, V, dO, leaves
         torch.cuda.empty_cache()
