@@ -45,6 +45,13 @@ struct HostDrop {
   DropArgs<T> as() const { return DropArgs<T>{key0, key1, offset, thresh, (T)scale}; }
 };
 
+// the kernel argument of a DROP instantiation; drop is NULL exactly where DROP is false
+template <bool DROP, typename T>
+inline DropArgsIf<DROP, T> drop_arg(const HostDrop* drop) {
+  if constexpr (DROP) return drop->as<T>();
+  else return NoDrop{};
+}
+
 inline int drop_check(const char* fn, double p, uint64_t seed, i64 n_l, i64 n_r, uint32_t offset, HostDrop* out) {
   GO_CHECK_ARG(p >= 0.0 && p < 1.0, "%s: dropout probability p must be in [0, 1), got %g", fn, p);
   GO_CHECK_ARG((seed >> 63) == 0, "%s: seed must be below 2^63, got %llu", fn, (unsigned long long)seed);
@@ -94,6 +101,22 @@ inline bool gat_attn_fast_ok(int dtype, i64 h, i64 d, i64 E, i64 n_l, i64 n_r, s
     default: break;                                     \
   }
 
+// a run-time bool as the template argument NAME of the statement
+#define GO_DISPATCH_BOOL(b, NAME, ...)                   \
+  if (b) { constexpr bool NAME = true; __VA_ARGS__; }    \
+  else { constexpr bool NAME = false; __VA_ARGS__; }
+
+// ProfScope tag [drop] and kernel label [drop][fast] of a gather pass ("fwd", "bwd_row", "bwd_col").  The drop names
+// are those of the DROP = true instantiations of the pass's one kernel template: they name the path taken.
+struct GatAttnLabels {
+  const char* tag[2];
+  const char* kernel[2][2];
+};
+#define GO_GAT_ATTN_LABELS(pass)                                             \
+  GatAttnLabels{{"gat_attn_" pass, "gat_attn_drop_" pass},                   \
+                {{"k_gat_attn_" pass "_generic", "k_gat_attn_" pass "_f32"}, \
+                 {"k_gat_attn_drop_" pass "_generic", "k_gat_attn_drop_" pass "_f32"}}}
+
 // chunks per lane group: up to the SpMM cap on big graphs, fewer on small ones so every CU still gets groups
 inline int gat_attn_cpg(i64 n_chunks) {
   constexpr int G = 16;
@@ -102,6 +125,11 @@ inline int gat_attn_cpg(i64 n_chunks) {
   if (c < 1) c = 1;
   const int cap = tuning().spmm_cpg > 0 ? tuning().spmm_cpg : 16;
   return (int)(c < cap ? c : cap);
+}
+
+// grid of a fast gather pass: lane groups of 16, cpg chunks each
+inline unsigned gat_attn_grid(i64 n_chunks, int cpg) {
+  return (unsigned)ceil_div(ceil_div(n_chunks, cpg), kFastBlock / 16);
 }
 
 inline unsigned grid_of(i64 n) {
@@ -169,7 +197,7 @@ using namespace graphop;
 
 namespace {
 
-// drop == nullptr: the op without dropout (today's kernels, whatever the entry point)
+// drop == nullptr: the op without dropout (the DROP = false kernels, whatever the entry point)
 int gat_attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
                      const int64_t* indices, const void* el, const void* er, const void* V, void* o, void* stats,
                      int64_t n_chunks, int64_t n_edges, int64_t n_l, int64_t n_r, int64_t h, int64_t d,
@@ -191,59 +219,27 @@ int gat_attn_forward(const char* fn, int dtype, const int64_t* row, const int64_
   GO_TRY(gat_attn_stats(dtype, (const i64*)row, (const i64*)indptr, (const i64*)indices, el, er, stats,
                         slots ? n_chunks : 0, n_l, h, negative_slope, pm, fast, st));
   if (!slots) return GRAPHOP_OK;
-  if (drop) {
-    if (fast) {
-      ProfScope prof("gat_attn_drop_fwd", st, "k_gat_attn_drop_fwd_f32");
-      const int cpg = gat_attn_cpg(n_chunks);
-      const unsigned nb = (unsigned)ceil_div(ceil_div(n_chunks, cpg), kFastBlock / 16);
-      const bool owned = pm->info.rows_sorted != 0;
-      const DropArgs<float> dr = drop->as<float>();
-      GO_DISPATCH_GAT_ATTN(h, d, {
-        if (owned)
-          hipLaunchKernelGGL((k_gat_attn_drop_fwd_f32<H, D, true>), dim3(nb), dim3(kFastBlock), 0, st, (const i64*)row,
-                             (const i64*)indptr, (const i64*)indices, (const float*)el, (const float*)er,
-                             (const float2*)stats, (const float*)V, (float*)o, n_chunks, cpg, (float)negative_slope,
-                             dr);
-        else
-          hipLaunchKernelGGL((k_gat_attn_drop_fwd_f32<H, D, false>), dim3(nb), dim3(kFastBlock), 0, st,
-                             (const i64*)row, (const i64*)indptr, (const i64*)indices, (const float*)el,
-                             (const float*)er, (const float2*)stats, (const float*)V, (float*)o, n_chunks, cpg,
-                             (float)negative_slope, dr);
-      });
-    } else {
-      ProfScope prof("gat_attn_drop_fwd", st, "k_gat_attn_drop_fwd_generic");
-      const unsigned nb = (unsigned)ceil_div(n_chunks, kGenericWavesPerBlock);
-      auto go = [&](auto zero) {
-        using T = decltype(zero);
-        hipLaunchKernelGGL((k_gat_attn_drop_fwd_generic<T>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)row,
-                           (const i64*)indptr, (const i64*)indices, (const T*)el, (const T*)er, (const T*)stats,
-                           (const T*)V, (T*)o, n_chunks, h, d, (T)negative_slope, drop->as<T>());
-      };
-      if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
-    }
-  } else if (fast) {
-    ProfScope prof("gat_attn_fwd", st, "k_gat_attn_fwd_f32");
+  const bool dropped = drop != nullptr;
+  static const GatAttnLabels lab = GO_GAT_ATTN_LABELS("fwd");
+  ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][fast]);
+  if (fast) {
     const int cpg = gat_attn_cpg(n_chunks);
-    const unsigned nb = (unsigned)ceil_div(ceil_div(n_chunks, cpg), kFastBlock / 16);
     const bool owned = pm->info.rows_sorted != 0;
-    GO_DISPATCH_GAT_ATTN(h, d, {
-      if (owned)
-        hipLaunchKernelGGL((k_gat_attn_fwd_f32<H, D, true>), dim3(nb), dim3(kFastBlock), 0, st, (const i64*)row,
-                           (const i64*)indptr, (const i64*)indices, (const float*)el, (const float*)er,
-                           (const float2*)stats, (const float*)V, (float*)o, n_chunks, cpg, (float)negative_slope);
-      else
-        hipLaunchKernelGGL((k_gat_attn_fwd_f32<H, D, false>), dim3(nb), dim3(kFastBlock), 0, st, (const i64*)row,
-                           (const i64*)indptr, (const i64*)indices, (const float*)el, (const float*)er,
-                           (const float2*)stats, (const float*)V, (float*)o, n_chunks, cpg, (float)negative_slope);
-    });
+    GO_DISPATCH_GAT_ATTN(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
+      hipLaunchKernelGGL((k_gat_attn_fwd_f32<H, D, OWNED, DROP>), dim3(gat_attn_grid(n_chunks, cpg)),
+                         dim3(kFastBlock), 0, st, (const i64*)row, (const i64*)indptr, (const i64*)indices,
+                         (const float*)el, (const float*)er, (const float2*)stats, (const float*)V, (float*)o,
+                         n_chunks, cpg, (float)negative_slope, drop_arg<DROP, float>(drop));
+    })));
   } else {
-    ProfScope prof("gat_attn_fwd", st, "k_gat_attn_fwd_generic");
-    const unsigned nb = (unsigned)ceil_div(n_chunks, kGenericWavesPerBlock);
     auto go = [&](auto zero) {
       using T = decltype(zero);
-      hipLaunchKernelGGL((k_gat_attn_fwd_generic<T>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)row,
-                         (const i64*)indptr, (const i64*)indices, (const T*)el, (const T*)er, (const T*)stats,
-                         (const T*)V, (T*)o, n_chunks, h, d, (T)negative_slope);
+      GO_DISPATCH_BOOL(dropped, DROP, {
+        hipLaunchKernelGGL((k_gat_attn_fwd_generic<T, DROP>), dim3((unsigned)ceil_div(n_chunks, kGenericWavesPerBlock)),
+                           dim3(kGenericBlock), 0, st, (const i64*)row, (const i64*)indptr, (const i64*)indices,
+                           (const T*)el, (const T*)er, (const T*)stats, (const T*)V, (T*)o, n_chunks, h, d,
+                           (T)negative_slope, drop_arg<DROP, T>(drop));
+      });
     };
     if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
   }
@@ -285,6 +281,7 @@ int gat_attn_backward(const char* fn, int dtype, const int64_t* row, const int64
   GO_PTR(fn, workspace);
   const bool ok = gat_attn_fast_ok(dtype, h, d, n_edges, n_l, n_r, {el, er, V, o, stats, dO, workspace, dV});
   const float slope = (float)negative_slope;
+  const bool dropped = drop != nullptr;
   const int G = 16;
   {   // P[i, k] = (el, m, 1/l, D)
     const bool fast = ok && (pr || pc);
@@ -308,55 +305,27 @@ int gat_attn_backward(const char* fn, int dtype, const int64_t* row, const int64
   if (n_row_chunks > 0) {
     GO_PTR(fn, row); GO_PTR(fn, indptr_r); GO_PTR(fn, eid_r); GO_PTR(fn, indices_r);
     const i64 C = n_row_chunks;
-    if (drop && ok && pr) {
-      ProfScope prof("gat_attn_drop_bwd_row", st, "k_gat_attn_drop_bwd_row_f32");
+    const bool fast = ok && pr;
+    static const GatAttnLabels lab = GO_GAT_ATTN_LABELS("bwd_row");
+    ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][fast]);
+    if (fast) {
       const int cpg = gat_attn_cpg(C);
-      const unsigned nb = (unsigned)ceil_div(ceil_div(C, cpg), kFastBlock / G);
-      const DropArgs<float> dr = drop->as<float>();
-      GO_DISPATCH_GAT_ATTN(h, d, {
-        if (pr->info.rows_sorted)
-          hipLaunchKernelGGL((k_gat_attn_drop_bwd_row_f32<H, D, true>), dim3(nb), dim3(kFastBlock), 0, st,
-                             (const i64*)row, (const i64*)indptr_r, (const i64*)indices_r, (const float*)er,
-                             (const float*)V, (const float4*)workspace, (const float*)dO, (float*)del, C, cpg, slope,
-                             dr);
-        else
-          hipLaunchKernelGGL((k_gat_attn_drop_bwd_row_f32<H, D, false>), dim3(nb), dim3(kFastBlock), 0, st,
-                             (const i64*)row, (const i64*)indptr_r, (const i64*)indices_r, (const float*)er,
-                             (const float*)V, (const float4*)workspace, (const float*)dO, (float*)del, C, cpg, slope,
-                             dr);
-      });
-    } else if (drop) {
-      ProfScope prof("gat_attn_drop_bwd_row", st, "k_gat_attn_drop_bwd_row_generic");
-      auto go = [&](auto zero) {
-        using T = decltype(zero);
-        hipLaunchKernelGGL((k_gat_attn_drop_bwd_row_generic<T>), dim3((unsigned)ceil_div(C, kGenericWavesPerBlock)),
-                           dim3(kGenericBlock), 0, st, (const i64*)row, (const i64*)indptr_r, (const i64*)indices_r,
-                           (const T*)er, (const T*)V, (const T*)workspace, (const T*)dO, (T*)del, C, h, d,
-                           (T)negative_slope, drop->as<T>());
-      };
-      if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
-    } else if (ok && pr) {
-      ProfScope prof("gat_attn_bwd_row", st, "k_gat_attn_bwd_row_f32");
-      const int cpg = gat_attn_cpg(C);
-      const unsigned nb = (unsigned)ceil_div(ceil_div(C, cpg), kFastBlock / G);
-      GO_DISPATCH_GAT_ATTN(h, d, {
-        if (pr->info.rows_sorted)
-          hipLaunchKernelGGL((k_gat_attn_bwd_row_f32<H, D, true>), dim3(nb), dim3(kFastBlock), 0, st, (const i64*)row,
-                             (const i64*)indptr_r, (const i64*)indices_r, (const float*)er, (const float*)V,
-                             (const float4*)workspace, (const float*)dO, (float*)del, C, cpg, slope);
-        else
-          hipLaunchKernelGGL((k_gat_attn_bwd_row_f32<H, D, false>), dim3(nb), dim3(kFastBlock), 0, st, (const i64*)row,
-                             (const i64*)indptr_r, (const i64*)indices_r, (const float*)er, (const float*)V,
-                             (const float4*)workspace, (const float*)dO, (float*)del, C, cpg, slope);
-      });
+      const bool owned = pr->info.rows_sorted != 0;
+      GO_DISPATCH_GAT_ATTN(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
+        hipLaunchKernelGGL((k_gat_attn_bwd_row_f32<H, D, OWNED, DROP>), dim3(gat_attn_grid(C, cpg)), dim3(kFastBlock),
+                           0, st, (const i64*)row, (const i64*)indptr_r, (const i64*)indices_r, (const float*)er,
+                           (const float*)V, (const float4*)workspace, (const float*)dO, (float*)del, C, cpg, slope,
+                           drop_arg<DROP, float>(drop));
+      })));
     } else {
-      ProfScope prof("gat_attn_bwd_row", st, "k_gat_attn_bwd_row_generic");
       auto go = [&](auto zero) {
         using T = decltype(zero);
-        hipLaunchKernelGGL((k_gat_attn_bwd_row_generic<T>), dim3((unsigned)ceil_div(C, kGenericWavesPerBlock)),
-                           dim3(kGenericBlock), 0, st, (const i64*)row, (const i64*)indptr_r, (const i64*)indices_r,
-                           (const T*)er, (const T*)V, (const T*)workspace, (const T*)dO, (T*)del, C, h, d,
-                           (T)negative_slope);
+        GO_DISPATCH_BOOL(dropped, DROP, {
+          hipLaunchKernelGGL((k_gat_attn_bwd_row_generic<T, DROP>), dim3((unsigned)ceil_div(C, kGenericWavesPerBlock)),
+                             dim3(kGenericBlock), 0, st, (const i64*)row, (const i64*)indptr_r, (const i64*)indices_r,
+                             (const T*)er, (const T*)V, (const T*)workspace, (const T*)dO, (T*)del, C, h, d,
+                             (T)negative_slope, drop_arg<DROP, T>(drop));
+        });
       };
       if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
     }
@@ -365,55 +334,27 @@ int gat_attn_backward(const char* fn, int dtype, const int64_t* row, const int64
   if (n_col_chunks > 0) {
     GO_PTR(fn, col); GO_PTR(fn, indptr_c); GO_PTR(fn, eid_c); GO_PTR(fn, indices_c);
     const i64 C = n_col_chunks;
-    if (drop && ok && pc) {
-      ProfScope prof("gat_attn_drop_bwd_col", st, "k_gat_attn_drop_bwd_col_f32");
+    const bool fast = ok && pc;
+    static const GatAttnLabels lab = GO_GAT_ATTN_LABELS("bwd_col");
+    ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][fast]);
+    if (fast) {
       const int cpg = gat_attn_cpg(C);
-      const unsigned nb = (unsigned)ceil_div(ceil_div(C, cpg), kFastBlock / G);
-      const DropArgs<float> dr = drop->as<float>();
-      GO_DISPATCH_GAT_ATTN(h, d, {
-        if (pc->info.rows_sorted)
-          hipLaunchKernelGGL((k_gat_attn_drop_bwd_col_f32<H, D, true>), dim3(nb), dim3(kFastBlock), 0, st,
-                             (const i64*)col, (const i64*)indptr_c, (const i64*)indices_c, (const float*)er,
-                             (const float*)V, (const float4*)workspace, (const float*)dO, (float*)der, (float*)dV, C,
-                             cpg, slope, dr);
-        else
-          hipLaunchKernelGGL((k_gat_attn_drop_bwd_col_f32<H, D, false>), dim3(nb), dim3(kFastBlock), 0, st,
-                             (const i64*)col, (const i64*)indptr_c, (const i64*)indices_c, (const float*)er,
-                             (const float*)V, (const float4*)workspace, (const float*)dO, (float*)der, (float*)dV, C,
-                             cpg, slope, dr);
-      });
-    } else if (drop) {
-      ProfScope prof("gat_attn_drop_bwd_col", st, "k_gat_attn_drop_bwd_col_generic");
-      auto go = [&](auto zero) {
-        using T = decltype(zero);
-        hipLaunchKernelGGL((k_gat_attn_drop_bwd_col_generic<T>), dim3((unsigned)ceil_div(C, kGenericWavesPerBlock)),
-                           dim3(kGenericBlock), 0, st, (const i64*)col, (const i64*)indptr_c, (const i64*)indices_c,
-                           (const T*)er, (const T*)V, (const T*)workspace, (const T*)dO, (T*)der, (T*)dV, C, h, d,
-                           (T)negative_slope, drop->as<T>());
-      };
-      if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
-    } else if (ok && pc) {
-      ProfScope prof("gat_attn_bwd_col", st, "k_gat_attn_bwd_col_f32");
-      const int cpg = gat_attn_cpg(C);
-      const unsigned nb = (unsigned)ceil_div(ceil_div(C, cpg), kFastBlock / G);
-      GO_DISPATCH_GAT_ATTN(h, d, {
-        if (pc->info.rows_sorted)
-          hipLaunchKernelGGL((k_gat_attn_bwd_col_f32<H, D, true>), dim3(nb), dim3(kFastBlock), 0, st, (const i64*)col,
-                             (const i64*)indptr_c, (const i64*)indices_c, (const float*)er, (const float*)V,
-                             (const float4*)workspace, (const float*)dO, (float*)der, (float*)dV, C, cpg, slope);
-        else
-          hipLaunchKernelGGL((k_gat_attn_bwd_col_f32<H, D, false>), dim3(nb), dim3(kFastBlock), 0, st, (const i64*)col,
-                             (const i64*)indptr_c, (const i64*)indices_c, (const float*)er, (const float*)V,
-                             (const float4*)workspace, (const float*)dO, (float*)der, (float*)dV, C, cpg, slope);
-      });
+      const bool owned = pc->info.rows_sorted != 0;
+      GO_DISPATCH_GAT_ATTN(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
+        hipLaunchKernelGGL((k_gat_attn_bwd_col_f32<H, D, OWNED, DROP>), dim3(gat_attn_grid(C, cpg)), dim3(kFastBlock),
+                           0, st, (const i64*)col, (const i64*)indptr_c, (const i64*)indices_c, (const float*)er,
+                           (const float*)V, (const float4*)workspace, (const float*)dO, (float*)der, (float*)dV, C,
+                           cpg, slope, drop_arg<DROP, float>(drop));
+      })));
     } else {
-      ProfScope prof("gat_attn_bwd_col", st, "k_gat_attn_bwd_col_generic");
       auto go = [&](auto zero) {
         using T = decltype(zero);
-        hipLaunchKernelGGL((k_gat_attn_bwd_col_generic<T>), dim3((unsigned)ceil_div(C, kGenericWavesPerBlock)),
-                           dim3(kGenericBlock), 0, st, (const i64*)col, (const i64*)indptr_c, (const i64*)indices_c,
-                           (const T*)er, (const T*)V, (const T*)workspace, (const T*)dO, (T*)der, (T*)dV, C, h, d,
-                           (T)negative_slope);
+        GO_DISPATCH_BOOL(dropped, DROP, {
+          hipLaunchKernelGGL((k_gat_attn_bwd_col_generic<T, DROP>), dim3((unsigned)ceil_div(C, kGenericWavesPerBlock)),
+                             dim3(kGenericBlock), 0, st, (const i64*)col, (const i64*)indptr_c, (const i64*)indices_c,
+                             (const T*)er, (const T*)V, (const T*)workspace, (const T*)dO, (T*)der, (T*)dV, C, h, d,
+                             (T)negative_slope, drop_arg<DROP, T>(drop));
+        });
       };
       if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
     }

@@ -5,6 +5,8 @@
 // i is the row-major row id (index into el / o), j the neighbour id (index into er / V), in that order in both
 // orientations.  Parallel edges (the same (i, j) more than once) share one decision.
 #pragma once
+#include <type_traits>
+
 #include "kernels_generic.h"
 
 namespace graphop {
@@ -15,6 +17,12 @@ struct DropArgs {
   unsigned key0, key1, offset, thresh;
   T scale;
 };
+
+// the dropout argument of a kernel templated on DROP: nothing to pass without dropout.  Only `if constexpr (DROP)`
+// code may name its members.
+struct NoDrop {};
+template <bool DROP, typename T>
+using DropArgsIf = std::conditional_t<DROP, DropArgs<T>, NoDrop>;
 
 // Philox4x32-10 (Salmon et al., Random123): ten rounds of two 32 x 32 -> 64 multiplies and a key bump
 __device__ __forceinline__ void philox4x32_10(unsigned c0, unsigned c1, unsigned c2, unsigned c3, unsigned k0,

@@ -185,101 +185,16 @@ __global__ __launch_bounds__(kFastBlock) void k_gat_attn_stats_f32(
 }
 
 // ---- forward aggregation ---------------------------------------------------------------------------------------
-template <int H, int D, bool OWNED>
+// DROP: the weight of a slot is multiplied by m_ijk (the row statistics are those of the undropped scores).
+template <int H, int D, bool OWNED, bool DROP>
 __global__ __launch_bounds__(kFastBlock) void k_gat_attn_fwd_f32(
     const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
     const float* __restrict__ el, const float* __restrict__ er, const float2* __restrict__ stats,
-    const float* __restrict__ V, float* __restrict__ o, i64 n_chunks, int chunks_per_group, float slope) {
-  using C = GatAttnCfg<H, D>;
-  constexpr int L = C::L, NV = C::NV, SB = C::SB_FWD;
-  constexpr i64 F4 = C::F4;
-  const int l = threadIdx.x % L;
-  const i64 gid = (i64)blockIdx.x * (kFastBlock / L) + threadIdx.x / L;
-  const i64 c0 = gid * chunks_per_group;
-  i64 c1 = c0 + chunks_per_group;
-  if (c1 > n_chunks) c1 = n_chunks;
-  if (c0 >= c1) return;
-  i64 row_before = -1, row_after = -1;
-  if constexpr (OWNED) {
-    if (c0 > 0) row_before = row[c0 - 1];
-    if (c1 < n_chunks) row_after = row[c1];
-  }
-  int kv[NV];
-#pragma unroll
-  for (int v = 0; v < NV; ++v) kv[v] = gat_attn_head<H, D>(v, l);
-  float4 acc[NV];
-  float a_el[NV], a_m[NV], a_il[NV];
-  auto zero_acc = [&]() {
-#pragma unroll
-    for (int v = 0; v < NV; ++v) acc[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-  };
-  auto flush = [&](i64 r) {
-    if (OWNED && r != row_before && r != row_after) {
-#pragma unroll
-      for (int v = 0; v < NV; ++v) reinterpret_cast<float4*>(o)[r * F4 + v * L + l] = acc[v];
-    } else {
-      atomic_flush<L, NV>(o, r, acc, l);
-    }
-  };
-  zero_acc();
-  i64 cur = -1;
-  bool dirty = false;
-  for (i64 c = c0; c < c1; ++c) {
-    const i64 r = row[c];
-    if (r != cur) {
-      if (dirty) { flush(cur); zero_acc(); dirty = false; }
-      cur = r;
-#pragma unroll
-      for (int v = 0; v < NV; ++v) {
-        a_el[v] = el[r * H + kv[v]];
-        const float2 st = stats[r * H + kv[v]];
-        a_m[v] = st.x;
-        a_il[v] = st.y;
-      }
-    }
-    const i64 j0 = indptr[c], j1 = indptr[c + 1];
-    if (j1 > j0) dirty = true;
-    for (i64 jb = j0; jb < j1; jb += SB) {
-      const int nb = (j1 - jb) < SB ? (int)(j1 - jb) : SB;
-      int my_src = 0;   // slots past the end re-read the batch's last neighbour with weight 0
-      if (l < SB) my_src = (int)indices[jb + (l < nb ? l : nb - 1)];
-      float4 x[SB][NV];
-      float e[SB][NV];
-      static_for<SB>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        const i64 src = group_bcast<L, u>(my_src);
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-          x[u][v] = reinterpret_cast<const float4*>(V)[src * F4 + v * L + l];
-          e[u][v] = er[src * H + kv[v]];
-        }
-      });
-#pragma unroll
-      for (int u = 0; u < SB; ++u) {
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-          const float z = gat_lrelu(a_el[v] + e[u][v], slope);
-          const float w = u < nb ? exp_nonpos(z - a_m[v]) * a_il[v] : 0.f;
-          acc[v].x = fmaf(w, x[u][v].x, acc[v].x); acc[v].y = fmaf(w, x[u][v].y, acc[v].y);
-          acc[v].z = fmaf(w, x[u][v].z, acc[v].z); acc[v].w = fmaf(w, x[u][v].w, acc[v].w);
-        }
-      }
-    }
-  }
-  if (dirty) flush(cur);
-}
-
-// k_gat_attn_fwd_f32 with the weight of a slot multiplied by m_ijk (the row statistics are those of the undropped
-// scores).  A kernel of its own, not a parameter of the one above, whose code stays as it is.
-template <int H, int D, bool OWNED>
-__global__ __launch_bounds__(kFastBlock) void k_gat_attn_drop_fwd_f32(
-    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
-    const float* __restrict__ el, const float* __restrict__ er, const float2* __restrict__ stats,
     const float* __restrict__ V, float* __restrict__ o, i64 n_chunks, int chunks_per_group, float slope,
-    DropArgs<float> dr) {
+    DropArgsIf<DROP, float> dr) {
   using C = GatAttnCfg<H, D>;
   constexpr int L = C::L, NV = C::NV, SB = C::SB_FWD;
-  constexpr int IDL = GatDropCfg<H, SB>::LANES;   // lanes that load a neighbour id
+  constexpr int IDL = DROP ? GatDropCfg<H, SB>::LANES : SB;   // lanes that load a neighbour id
   constexpr i64 F4 = C::F4;
   const int l = threadIdx.x % L;
   const i64 gid = (i64)blockIdx.x * (kFastBlock / L) + threadIdx.x / L;
@@ -330,7 +245,7 @@ __global__ __launch_bounds__(kFastBlock) void k_gat_attn_drop_fwd_f32(
     for (i64 jb = j0; jb < j1; jb += SB) {
       const int nb = (j1 - jb) < SB ? (int)(j1 - jb) : SB;
       int my_src = 0;   // slots past the end re-read the batch's last neighbour with weight 0
-      const int t = l % SB;
+      const int t = DROP ? l % SB : l;
       if (l < IDL) my_src = (int)indices[jb + (t < nb ? t : nb - 1)];
       float4 x[SB][NV];
       float e[SB][NV];
@@ -343,19 +258,21 @@ __global__ __launch_bounds__(kFastBlock) void k_gat_attn_drop_fwd_f32(
           e[u][v] = er[src * H + kv[v]];
         }
       });
-      int keep[SB];
-      const int mine = gat_drop_lane_bits<H, SB, false>(l, r, my_src, dr);
-      static_for<SB>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        keep[u] = gat_drop_slot_bits<H, SB, u>(mine);
-      });
+      int keep[DROP ? SB : 1];
+      if constexpr (DROP) {
+        const int mine = gat_drop_lane_bits<H, SB, false>(l, r, my_src, dr);
+        static_for<SB>([&](auto uc) {
+          constexpr int u = decltype(uc)::value;
+          keep[u] = gat_drop_slot_bits<H, SB, u>(mine);
+        });
+      }
 #pragma unroll
       for (int u = 0; u < SB; ++u) {
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
           const float z = gat_lrelu(a_el[v] + e[u][v], slope);
-          const float a = u < nb ? exp_nonpos(z - a_m[v]) * a_il[v] : 0.f;
-          const float w = (keep[u] >> kv[v]) & 1 ? a * dr.scale : 0.f;
+          float w = u < nb ? exp_nonpos(z - a_m[v]) * a_il[v] : 0.f;
+          if constexpr (DROP) w = (keep[u] >> kv[v]) & 1 ? w * dr.scale : 0.f;
           acc[v].x = fmaf(w, x[u][v].x, acc[v].x); acc[v].y = fmaf(w, x[u][v].y, acc[v].y);
           acc[v].z = fmaf(w, x[u][v].z, acc[v].z); acc[v].w = fmaf(w, x[u][v].w, acc[v].w);
         }
@@ -398,7 +315,7 @@ __device__ __forceinline__ void gat_attn_bwd_walk(
     const i64* __restrict__ seg, const i64* __restrict__ indptr, const i64* __restrict__ indices,
     const float* __restrict__ er, const float* __restrict__ V, const float4* __restrict__ P,
     const float* __restrict__ dO, float* __restrict__ out0, float* __restrict__ out1, i64 n_chunks,
-    int chunks_per_group, float slope, const DropArgs<float>& dr) {
+    int chunks_per_group, float slope, const DropArgsIf<DROP, float>& dr) {
   using C = GatAttnCfg<H, D>;
   constexpr int L = C::L, NV = C::NV, DQ = C::DQ, SB = C::SB_BWD;
   constexpr int IDL = DROP ? GatDropCfg<H, SB>::LANES : SB;   // lanes that load a neighbour id
@@ -518,42 +435,23 @@ __device__ __forceinline__ void gat_attn_bwd_walk(
   if (dirty) flush(cur);
 }
 
-template <int H, int D, bool OWNED>
+template <int H, int D, bool OWNED, bool DROP>
 __global__ __launch_bounds__(kFastBlock) void k_gat_attn_bwd_row_f32(
     const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
     const float* __restrict__ er, const float* __restrict__ V, const float4* __restrict__ P,
-    const float* __restrict__ dO, float* __restrict__ del, i64 n_chunks, int chunks_per_group, float slope) {
-  gat_attn_bwd_walk<H, D, false, OWNED, false>(row, indptr, indices, er, V, P, dO, del, nullptr, n_chunks,
-                                               chunks_per_group, slope, DropArgs<float>{});
+    const float* __restrict__ dO, float* __restrict__ del, i64 n_chunks, int chunks_per_group, float slope,
+    DropArgsIf<DROP, float> dr) {
+  gat_attn_bwd_walk<H, D, false, OWNED, DROP>(row, indptr, indices, er, V, P, dO, del, nullptr, n_chunks,
+                                              chunks_per_group, slope, dr);
 }
 
-template <int H, int D, bool OWNED>
+template <int H, int D, bool OWNED, bool DROP>
 __global__ __launch_bounds__(kFastBlock) void k_gat_attn_bwd_col_f32(
     const i64* __restrict__ col, const i64* __restrict__ indptr, const i64* __restrict__ indices,
     const float* __restrict__ er, const float* __restrict__ V, const float4* __restrict__ P,
     const float* __restrict__ dO, float* __restrict__ der, float* __restrict__ dV, i64 n_chunks,
-    int chunks_per_group, float slope) {
-  gat_attn_bwd_walk<H, D, true, OWNED, false>(col, indptr, indices, er, V, P, dO, der, dV, n_chunks, chunks_per_group,
-                                              slope, DropArgs<float>{});
-}
-
-template <int H, int D, bool OWNED>
-__global__ __launch_bounds__(kFastBlock) void k_gat_attn_drop_bwd_row_f32(
-    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
-    const float* __restrict__ er, const float* __restrict__ V, const float4* __restrict__ P,
-    const float* __restrict__ dO, float* __restrict__ del, i64 n_chunks, int chunks_per_group, float slope,
-    DropArgs<float> dr) {
-  gat_attn_bwd_walk<H, D, false, OWNED, true>(row, indptr, indices, er, V, P, dO, del, nullptr, n_chunks,
-                                              chunks_per_group, slope, dr);
-}
-
-template <int H, int D, bool OWNED>
-__global__ __launch_bounds__(kFastBlock) void k_gat_attn_drop_bwd_col_f32(
-    const i64* __restrict__ col, const i64* __restrict__ indptr, const i64* __restrict__ indices,
-    const float* __restrict__ er, const float* __restrict__ V, const float4* __restrict__ P,
-    const float* __restrict__ dO, float* __restrict__ der, float* __restrict__ dV, i64 n_chunks,
-    int chunks_per_group, float slope, DropArgs<float> dr) {
-  gat_attn_bwd_walk<H, D, true, OWNED, true>(col, indptr, indices, er, V, P, dO, der, dV, n_chunks, chunks_per_group,
+    int chunks_per_group, float slope, DropArgsIf<DROP, float> dr) {
+  gat_attn_bwd_walk<H, D, true, OWNED, DROP>(col, indptr, indices, er, V, P, dO, der, dV, n_chunks, chunks_per_group,
                                              slope, dr);
 }
 
@@ -611,10 +509,10 @@ __global__ void k_gat_attn_stats_fin_generic(T* __restrict__ stats, i64 n) {
 }
 
 template <typename T, bool DROP>
-__device__ __forceinline__ void gat_attn_fwd_generic(
+__global__ __launch_bounds__(kGenericBlock) void k_gat_attn_fwd_generic(
     const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
     const T* __restrict__ el, const T* __restrict__ er, const T* __restrict__ stats, const T* __restrict__ V,
-    T* __restrict__ o, i64 n_chunks, i64 h, i64 d, T slope, const DropArgs<T>& dr) {
+    T* __restrict__ o, i64 n_chunks, i64 h, i64 d, T slope, DropArgsIf<DROP, T> dr) {
   const i64 c = generic_chunk_id();
   if (c >= n_chunks) return;
   const int lane = threadIdx.x & 63;
@@ -633,22 +531,6 @@ __device__ __forceinline__ void gat_attn_fwd_generic(
     }
     atomicAdd(o + r * h * d + it, acc);
   }
-}
-
-template <typename T>
-__global__ __launch_bounds__(kGenericBlock) void k_gat_attn_fwd_generic(
-    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
-    const T* __restrict__ el, const T* __restrict__ er, const T* __restrict__ stats, const T* __restrict__ V,
-    T* __restrict__ o, i64 n_chunks, i64 h, i64 d, T slope) {
-  gat_attn_fwd_generic<T, false>(row, indptr, indices, el, er, stats, V, o, n_chunks, h, d, slope, DropArgs<T>{});
-}
-
-template <typename T>
-__global__ __launch_bounds__(kGenericBlock) void k_gat_attn_drop_fwd_generic(
-    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
-    const T* __restrict__ el, const T* __restrict__ er, const T* __restrict__ stats, const T* __restrict__ V,
-    T* __restrict__ o, i64 n_chunks, i64 h, i64 d, T slope, DropArgs<T> dr) {
-  gat_attn_fwd_generic<T, true>(row, indptr, indices, el, er, stats, V, o, n_chunks, h, d, slope, dr);
 }
 
 template <typename T>
@@ -679,10 +561,10 @@ __device__ __forceinline__ T gat_attn_dz(const T* __restrict__ p, T erj, const T
 }
 
 template <typename T, bool DROP>
-__device__ __forceinline__ void gat_attn_bwd_row_generic(
+__global__ __launch_bounds__(kGenericBlock) void k_gat_attn_bwd_row_generic(
     const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
     const T* __restrict__ er, const T* __restrict__ V, const T* __restrict__ P, const T* __restrict__ dO,
-    T* __restrict__ del, i64 n_chunks, i64 h, i64 d, T slope, const DropArgs<T>& dr) {
+    T* __restrict__ del, i64 n_chunks, i64 h, i64 d, T slope, DropArgsIf<DROP, T> dr) {
   const i64 c = generic_chunk_id();
   if (c >= n_chunks) return;
   const int lane = threadIdx.x & 63;
@@ -693,7 +575,8 @@ __device__ __forceinline__ void gat_attn_bwd_row_generic(
     T acc = 0;
     for (i64 j = j0 + lane; j < j1; j += kWave) {
       const i64 src = indices[j];
-      const T mult = DROP ? drop_mult<T>(r, src, k, dr) : (T)1;
+      T mult = 1;
+      if constexpr (DROP) mult = drop_mult<T>(r, src, k, dr);
       acc += gat_attn_dz<T>(P + (r * h + k) * 4, er[src * h + k], dO + (r * h + k) * d, V + (src * h + k) * d, d, slope,
                             mult);
     }
@@ -702,27 +585,11 @@ __device__ __forceinline__ void gat_attn_bwd_row_generic(
   }
 }
 
-template <typename T>
-__global__ __launch_bounds__(kGenericBlock) void k_gat_attn_bwd_row_generic(
-    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
-    const T* __restrict__ er, const T* __restrict__ V, const T* __restrict__ P, const T* __restrict__ dO,
-    T* __restrict__ del, i64 n_chunks, i64 h, i64 d, T slope) {
-  gat_attn_bwd_row_generic<T, false>(row, indptr, indices, er, V, P, dO, del, n_chunks, h, d, slope, DropArgs<T>{});
-}
-
-template <typename T>
-__global__ __launch_bounds__(kGenericBlock) void k_gat_attn_drop_bwd_row_generic(
-    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
-    const T* __restrict__ er, const T* __restrict__ V, const T* __restrict__ P, const T* __restrict__ dO,
-    T* __restrict__ del, i64 n_chunks, i64 h, i64 d, T slope, DropArgs<T> dr) {
-  gat_attn_bwd_row_generic<T, true>(row, indptr, indices, er, V, P, dO, del, n_chunks, h, d, slope, dr);
-}
-
 template <typename T, bool DROP>
-__device__ __forceinline__ void gat_attn_bwd_col_generic(
+__global__ __launch_bounds__(kGenericBlock) void k_gat_attn_bwd_col_generic(
     const i64* __restrict__ col, const i64* __restrict__ indptr, const i64* __restrict__ indices,
     const T* __restrict__ er, const T* __restrict__ V, const T* __restrict__ P, const T* __restrict__ dO,
-    T* __restrict__ der, T* __restrict__ dV, i64 n_chunks, i64 h, i64 d, T slope, const DropArgs<T>& dr) {
+    T* __restrict__ der, T* __restrict__ dV, i64 n_chunks, i64 h, i64 d, T slope, DropArgsIf<DROP, T> dr) {
   const i64 c = generic_chunk_id();
   if (c >= n_chunks) return;
   const int lane = threadIdx.x & 63;
@@ -733,7 +600,8 @@ __device__ __forceinline__ void gat_attn_bwd_col_generic(
     T acc = 0;
     for (i64 j = j0 + lane; j < j1; j += kWave) {
       const i64 i = indices[j];
-      const T mult = DROP ? drop_mult<T>(i, jc, k, dr) : (T)1;
+      T mult = 1;
+      if constexpr (DROP) mult = drop_mult<T>(i, jc, k, dr);
       acc += gat_attn_dz<T>(P + (i * h + k) * 4, er[jc * h + k], dO + (i * h + k) * d, V + (jc * h + k) * d, d, slope,
                             mult);
     }
@@ -752,23 +620,6 @@ __device__ __forceinline__ void gat_attn_bwd_col_generic(
     }
     atomicAdd(dV + jc * h * d + it, acc);
   }
-}
-
-template <typename T>
-__global__ __launch_bounds__(kGenericBlock) void k_gat_attn_bwd_col_generic(
-    const i64* __restrict__ col, const i64* __restrict__ indptr, const i64* __restrict__ indices,
-    const T* __restrict__ er, const T* __restrict__ V, const T* __restrict__ P, const T* __restrict__ dO,
-    T* __restrict__ der, T* __restrict__ dV, i64 n_chunks, i64 h, i64 d, T slope) {
-  gat_attn_bwd_col_generic<T, false>(col, indptr, indices, er, V, P, dO, der, dV, n_chunks, h, d, slope,
-                                     DropArgs<T>{});
-}
-
-template <typename T>
-__global__ __launch_bounds__(kGenericBlock) void k_gat_attn_drop_bwd_col_generic(
-    const i64* __restrict__ col, const i64* __restrict__ indptr, const i64* __restrict__ indices,
-    const T* __restrict__ er, const T* __restrict__ V, const T* __restrict__ P, const T* __restrict__ dO,
-    T* __restrict__ der, T* __restrict__ dV, i64 n_chunks, i64 h, i64 d, T slope, DropArgs<T> dr) {
-  gat_attn_bwd_col_generic<T, true>(col, indptr, indices, er, V, P, dO, der, dV, n_chunks, h, d, slope, dr);
 }
 
 }  // namespace graphop

@@ -400,103 +400,29 @@ def _gat_attn_shapes(el, er, V, fn):
     return h, V.size(-1)
 
 
-def gat_attention_forward(row, indptr, eid, indices, el, er, V, negative_slope=0.2):
-    """-> [o, stats]: o[i] = sum_j softmax_j(LeakyReLU(el[i] + er[j])) V[j] per head over the row-major CSR, without
-    any E-sized tensor; o has n_src = el.size(0) rows in V's layout, stats (n_src, h, 2) = (row max, 1 / sum exp)."""
+def _gat_attention_forward(fn, row, indptr, eid, indices, el, er, V, negative_slope, drop=()):
+    """gat_attention_forward (drop = ()) or gat_attention_dropout_forward (drop = (p, seed, offset)) as `fn`."""
     for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices"), (el, "el"), (er, "er"),
                  (V, "V")):
         _check_input(t, n)
     for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices")):
         _check_index(t, n)
-    h, d = _gat_attn_shapes(el, er, V, "gat_attention_forward")
+    h, d = _gat_attn_shapes(el, er, V, fn)
     e, n_l = eid.size(0), el.size(0)
     o = torch.empty((n_l,) + tuple(V.shape[1:]), dtype=V.dtype, device=V.device)
     stats = torch.empty((n_l, h, 2), dtype=el.dtype, device=el.device)
     with _lib.device_guard(el.device):
         plan = _plan(row, indptr, eid, indices, er.size(0))
-        check(lib().graphop_gat_attention_forward(
+        check(getattr(lib(), "graphop_" + fn)(
             dtype_code(el), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(el), ptr(er), ptr(V), ptr(o),
-            ptr(stats), row.size(0), e, n_l, er.size(0), h, d, float(negative_slope), plan.handle, stream_of(el)))
-    return [o, stats]
-
-
-def gat_attention_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V, o, stats,
-                           dO, negative_slope=0.2):
-    """-> [del, der, dV] of gat_attention_forward for the output gradient dO (a recomputed per slot from stats)."""
-    names = ("row", "indptr_r", "eid_r", "indices_r", "col", "indptr_c", "eid_c", "indices_c")
-    idx = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
-    for t, n in zip(idx + (el, er, V, o, stats), names + ("el", "er", "V", "o", "stats")):
-        _check_input(t, n)
-    for t, n in zip(idx, names):
-        _check_index(t, n)
-    if not isinstance(dO, torch.Tensor) or not dO.is_cuda:
-        raise RuntimeError("dO must be a CUDA tensor")
-    h, d = _gat_attn_shapes(el, er, V, "gat_attention_backward")
-    for t, n in ((o, "o"), (stats, "stats"), (dO, "dO")):
-        _same_dtype(el, t, "el", n)
-    n_l = el.size(0)
-    if o.shape != (n_l,) + tuple(V.shape[1:]) or stats.numel() != n_l * h * 2:
-        raise RuntimeError("gat_attention_backward: o must be %s and stats (n_src, h, 2), got %s and %s"
-                           % ((n_l,) + tuple(V.shape[1:]), tuple(o.shape), tuple(stats.shape)))
-    dO = dO.contiguous()
-    if dO.shape != o.shape:
-        raise RuntimeError("gat_attention_backward: dO must match o %s, got %s" % (tuple(o.shape), tuple(dO.shape)))
-    e = eid_r.size(0)
-    d_el, d_er, dV = torch.empty_like(el), torch.empty_like(er), torch.empty_like(V)
-    ws = torch.empty(max(n_l * h * 4, 1), dtype=el.dtype, device=el.device)      # (el, m, 1 / l, D) per (node, head)
-    with _lib.device_guard(el.device):
-        plan_r = _plan(row, indptr_r, eid_r, indices_r, er.size(0))
-        plan_c = _plan(col, indptr_c, eid_c, indices_c, n_l)
-        check(lib().graphop_gat_attention_backward(
-            dtype_code(el), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c),
-            ptr(eid_c), ptr(indices_c), ptr(el), ptr(er), ptr(V), ptr(o), ptr(stats), ptr(dO), ptr(d_el), ptr(d_er),
-            ptr(dV), ptr(ws), ws.numel() * ws.element_size(), row.size(0), col.size(0), e, n_l, er.size(0), h, d,
-            float(negative_slope), plan_r.handle, plan_c.handle, stream_of(el)))
-    return [d_el, d_er, dV]
-
-
-# ---- attention dropout of the fused GAT layer (extra ops) ------------------------------------------------------
-def _drop_args(fn, p, seed, offset):
-    """(p, seed, offset) checked as the C ABI states them: 0 <= p < 1, 0 <= seed < 2^63, 0 <= offset < 2^32."""
-    p, seed, offset = float(p), int(seed), int(offset)
-    if not 0.0 <= p < 1.0:
-        raise RuntimeError("%s: dropout probability p must be in [0, 1), got %r" % (fn, p))
-    if not 0 <= seed < 2 ** 63:
-        raise RuntimeError("%s: seed must be in [0, 2^63), got %d" % (fn, seed))
-    if not 0 <= offset < 2 ** 32:
-        raise RuntimeError("%s: offset must be in [0, 2^32), got %d" % (fn, offset))
-    return p, seed, offset
-
-
-def gat_attention_dropout_forward(row, indptr, eid, indices, el, er, V, negative_slope=0.2, p=0.0, seed=0, offset=0):
-    """-> [o, stats] of gat_attention_forward with dropout on the attention weights: o[i] = sum_j a_ij m_ij V[j],
-    m_ij = keep(i, j, head; seed, offset, p) / (1 - p) recomputed per slot from Philox4x32-10 (no edge-sized mask);
-    stats are those of the undropped scores.  p = 0 is gat_attention_forward bit for bit."""
-    p, seed, offset = _drop_args("gat_attention_dropout_forward", p, seed, offset)
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices"), (el, "el"), (er, "er"),
-                 (V, "V")):
-        _check_input(t, n)
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices")):
-        _check_index(t, n)
-    h, d = _gat_attn_shapes(el, er, V, "gat_attention_dropout_forward")
-    e, n_l = eid.size(0), el.size(0)
-    o = torch.empty((n_l,) + tuple(V.shape[1:]), dtype=V.dtype, device=V.device)
-    stats = torch.empty((n_l, h, 2), dtype=el.dtype, device=el.device)
-    with _lib.device_guard(el.device):
-        plan = _plan(row, indptr, eid, indices, er.size(0))
-        check(lib().graphop_gat_attention_dropout_forward(
-            dtype_code(el), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(el), ptr(er), ptr(V), ptr(o),
-            ptr(stats), row.size(0), e, n_l, er.size(0), h, d, float(negative_slope), p, seed, offset, plan.handle,
+            ptr(stats), row.size(0), e, n_l, er.size(0), h, d, float(negative_slope), *drop, plan.handle,
             stream_of(el)))
     return [o, stats]
 
 
-def gat_attention_dropout_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V, o,
-                                   stats, dO, negative_slope=0.2, p=0.0, seed=0, offset=0):
-    """-> [del, der, dV] of gat_attention_dropout_forward for the output gradient dO, with the same (p, seed, offset):
-    the weights and their keep decisions are recomputed per slot."""
-    fn = "gat_attention_dropout_backward"
-    p, seed, offset = _drop_args(fn, p, seed, offset)
+def _gat_attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V, o, stats,
+                            dO, negative_slope, drop=()):
+    """gat_attention_backward (drop = ()) or gat_attention_dropout_backward (drop = (p, seed, offset)) as `fn`."""
     names = ("row", "indptr_r", "eid_r", "indices_r", "col", "indptr_c", "eid_c", "indices_c")
     idx = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
     for t, n in zip(idx + (el, er, V, o, stats), names + ("el", "er", "V", "o", "stats")):
@@ -521,12 +447,56 @@ def gat_attention_dropout_backward(row, indptr_r, eid_r, indices_r, col, indptr_
     with _lib.device_guard(el.device):
         plan_r = _plan(row, indptr_r, eid_r, indices_r, er.size(0))
         plan_c = _plan(col, indptr_c, eid_c, indices_c, n_l)
-        check(lib().graphop_gat_attention_dropout_backward(
+        check(getattr(lib(), "graphop_" + fn)(
             dtype_code(el), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c),
             ptr(eid_c), ptr(indices_c), ptr(el), ptr(er), ptr(V), ptr(o), ptr(stats), ptr(dO), ptr(d_el), ptr(d_er),
             ptr(dV), ptr(ws), ws.numel() * ws.element_size(), row.size(0), col.size(0), e, n_l, er.size(0), h, d,
-            float(negative_slope), p, seed, offset, plan_r.handle, plan_c.handle, stream_of(el)))
+            float(negative_slope), *drop, plan_r.handle, plan_c.handle, stream_of(el)))
     return [d_el, d_er, dV]
+
+
+def gat_attention_forward(row, indptr, eid, indices, el, er, V, negative_slope=0.2):
+    """-> [o, stats]: o[i] = sum_j softmax_j(LeakyReLU(el[i] + er[j])) V[j] per head over the row-major CSR, without
+    any E-sized tensor; o has n_src = el.size(0) rows in V's layout, stats (n_src, h, 2) = (row max, 1 / sum exp)."""
+    return _gat_attention_forward("gat_attention_forward", row, indptr, eid, indices, el, er, V, negative_slope)
+
+
+def gat_attention_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V, o, stats,
+                           dO, negative_slope=0.2):
+    """-> [del, der, dV] of gat_attention_forward for the output gradient dO (a recomputed per slot from stats)."""
+    return _gat_attention_backward("gat_attention_backward", row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
+                                   indices_c, el, er, V, o, stats, dO, negative_slope)
+
+
+# ---- attention dropout of the fused GAT layer (extra ops) ------------------------------------------------------
+def _drop_args(fn, p, seed, offset):
+    """(p, seed, offset) checked as the C ABI states them: 0 <= p < 1, 0 <= seed < 2^63, 0 <= offset < 2^32."""
+    p, seed, offset = float(p), int(seed), int(offset)
+    if not 0.0 <= p < 1.0:
+        raise RuntimeError("%s: dropout probability p must be in [0, 1), got %r" % (fn, p))
+    if not 0 <= seed < 2 ** 63:
+        raise RuntimeError("%s: seed must be in [0, 2^63), got %d" % (fn, seed))
+    if not 0 <= offset < 2 ** 32:
+        raise RuntimeError("%s: offset must be in [0, 2^32), got %d" % (fn, offset))
+    return p, seed, offset
+
+
+def gat_attention_dropout_forward(row, indptr, eid, indices, el, er, V, negative_slope=0.2, p=0.0, seed=0, offset=0):
+    """-> [o, stats] of gat_attention_forward with dropout on the attention weights: o[i] = sum_j a_ij m_ij V[j],
+    m_ij = keep(i, j, head; seed, offset, p) / (1 - p) recomputed per slot from Philox4x32-10 (no edge-sized mask);
+    stats are those of the undropped scores.  p = 0 is gat_attention_forward bit for bit."""
+    fn = "gat_attention_dropout_forward"
+    return _gat_attention_forward(fn, row, indptr, eid, indices, el, er, V, negative_slope,
+                                  _drop_args(fn, p, seed, offset))
+
+
+def gat_attention_dropout_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V, o,
+                                   stats, dO, negative_slope=0.2, p=0.0, seed=0, offset=0):
+    """-> [del, der, dV] of gat_attention_dropout_forward for the output gradient dO, with the same (p, seed, offset):
+    the weights and their keep decisions are recomputed per slot."""
+    fn = "gat_attention_dropout_backward"
+    return _gat_attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V, o,
+                                   stats, dO, negative_slope, _drop_args(fn, p, seed, offset))
 
 
 def edge_dropout_mask(row, indptr, eid, indices, h, p, seed, offset=0, dtype=torch.float32):

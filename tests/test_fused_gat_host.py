@@ -96,7 +96,10 @@ def test_fused_gat_fast_kernels_do_not_spill():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     from kernel_resources import kernel_resources
     res = kernel_resources()
-    fast = {n: r for n, r in res.items() if re.search(r"k_gat_attn_(stats|fwd|pack|bwd_row|bwd_col)_f32<", n)}
+    # the gather kernels without dropout are the DROP = false instantiations (the last template argument)
+    fast = {n: r for n, r in res.items()
+            if re.search(r"k_gat_attn_(stats|pack)_f32<\d+, \d+>\(", n)
+            or re.search(r"k_gat_attn_(fwd|bwd_row|bwd_col)_f32<\d+, \d+, (true|false), false>\(", n)}
     # 9 (h, d) pairs x {owned, shared} for fwd / bwd_row / bwd_col, 9 packs, 4 head counts x 2 group widths of stats
     assert len(fast) == 3 * 18 + 9 + 8, sorted(fast)
     bad = {n: r for n, r in fast.items() if r["spill_vgpr"] or r["scratch"]}

@@ -159,11 +159,14 @@ def test_dropout_fast_kernels_do_not_spill():
     sys.path.insert(0, os.path.join(ROOT, "tools"))
     from kernel_resources import kernel_resources
     res = kernel_resources()
-    drop = {n: r for n, r in res.items() if re.search(r"k_gat_attn_drop_(fwd|bwd_row|bwd_col)_f32<", n)}
+    # the DROP = true instantiations of the gather kernels (the last template argument)
+    drop = {n: r for n, r in res.items()
+            if re.search(r"k_gat_attn_(fwd|bwd_row|bwd_col)_f32<\d+, \d+, (true|false), true>\(", n)}
     assert len(drop) == 3 * 18, sorted(drop)
     bad = {n: r for n, r in drop.items() if r["spill_vgpr"] or r["scratch"]}
     assert not bad, "\n".join("%s: %r" % kv for kv in sorted(bad.items()))
-    old = [n for n in res if re.search(r"k_gat_attn_(stats|fwd|pack|bwd_row|bwd_col)_f32<", n)]
+    old = [n for n in res if re.search(r"k_gat_attn_(stats|pack)_f32<\d+, \d+>\(", n)
+           or re.search(r"k_gat_attn_(fwd|bwd_row|bwd_col)_f32<\d+, \d+, (true|false), false>\(", n)]
     assert len(old) == 3 * 18 + 9 + 8, sorted(old)
 
 
