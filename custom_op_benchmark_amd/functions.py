@@ -96,6 +96,26 @@ class GATScores(Function):
         return None, None, None, None, None, None, None, None, d_el, d_er, None
 
 
+class GATv2Scores(Function):
+    """GATv2 attention scores s = sum_c att[k, c] * LeakyReLU(xl[i, k, c] + xr[j, k, c]) per edge and head (extra op, not in
+    the reference): apply(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, negative_slope).
+    xl (n_src, d), xr (n_dst, d), att (d) for one head, else (n, h, d) and (h, d); s is (E) for one head, else (E, h) --
+    the edge layout SparseSoftmax and VectorSPMM take.  Saves the CSR arrays, xl, xr and att only: the backward
+    recomputes the pre-activation per slot."""
+
+    @staticmethod
+    def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, negative_slope):
+        ctx.save_for_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att)
+        ctx.negative_slope = float(negative_slope)
+        return _ops.gatv2_scores_forward(row, indptr_r, eid_r, indices_r, xl, xr, att, ctx.negative_slope)
+
+    @staticmethod
+    def backward(ctx, grad):
+        a8, (xl, xr, att) = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
+        dxl, dxr, datt = _ops.gatv2_scores_backward(*a8, xl, xr, att, grad, ctx.negative_slope)
+        return None, None, None, None, None, None, None, None, dxl, dxr, datt, None
+
+
 class FusedGATAttention(Function):
     """o = VectorSPMM(SparseSoftmax(GATScores(el, er)), V) as ONE autograd node (extra op, not in the reference):
     apply(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V, negative_slope).  el (n_src[, h]),
@@ -313,6 +333,21 @@ def gat_attention_step(g, el, er, V, dO, negative_slope=0.2):
     s = GATScores.apply(*args, el, er, negative_slope)
     a = SparseSoftmax.apply(g.row, g.ptr_r, g.eid_r, s)
     o = VectorSPMM.apply(*args, a, V)
+    o.backward(dO)
+    _lib.check_errors(sync=False)     # as in attention_step
+    return s, a, o
+
+
+def gatv2_attention_step(g, xl, xr, att, dO, negative_slope=0.2, V=None):
+    """One fwd+bwd of GATv2 attention, the counterpart of gat_attention_step:
+    s = att . LeakyReLU(xl[i] + xr[j]); a = row-softmax(s); o = SpMM(a, V); o.backward(dO).
+    V=None aggregates xr itself (the GATv2Conv convention: the transformed neighbour features serve both the score and
+    the message; autograd then sums the two gradients into xr).  xl, xr, att (and V) must be leaf tensors with
+    requires_grad; returns (s, a, o)."""
+    args = g.csr_args()
+    s = GATv2Scores.apply(*args, xl, xr, att, negative_slope)
+    a = SparseSoftmax.apply(g.row, g.ptr_r, g.eid_r, s)
+    o = VectorSPMM.apply(*args, a, xr if V is None else V)
     o.backward(dO)
     _lib.check_errors(sync=False)     # as in attention_step
     return s, a, o

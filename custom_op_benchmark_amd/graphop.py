@@ -29,10 +29,12 @@ __all__ = ["maskedmm_csr_forward", "maskedmm_csr_backward", "node_mul_edge_forwa
            "vector_spmm_forward", "vector_spmm_backward"]
 # extra ops (not in the reference's module): the fused attention step, SURVEY.md 8f N2
 # the GAT additive attention scores (LeakyReLU(el[i] + er[j]) per edge and head), the fused GAT attention layer and
-# its forms with attention dropout (plus the mask they apply, as an edge tensor, for the composed path)
+# its forms with attention dropout (plus the mask they apply, as an edge tensor, for the composed path), and the GATv2
+# scores (att . LeakyReLU(xl[i] + xr[j]) per edge and head)
 EXTRA_OPS = ["attention_forward", "attention_backward", "attention_backward_is_fused", "gat_scores_forward",
              "gat_scores_backward", "gat_attention_forward", "gat_attention_backward",
-             "gat_attention_dropout_forward", "gat_attention_dropout_backward", "edge_dropout_mask"]
+             "gat_attention_dropout_forward", "gat_attention_dropout_backward", "edge_dropout_mask",
+             "gatv2_scores_forward", "gatv2_scores_backward"]
 
 _NULL = None
 
@@ -389,6 +391,77 @@ def gat_scores_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, i
     return [d_el, d_er]
 
 
+# ---- GATv2 attention scores (extra op) -----------------------------------------------------------------------------
+def _gatv2_shapes(xl, xr, att, fn):
+    """(h, d) of the GATv2 operands: xl (n_src, d), xr (n_dst, d), att (d) for one head, else (n, h, d) and (h, d)."""
+    _same_dtype(xl, xr, "xl", "xr")
+    _same_dtype(xl, att, "xl", "att")
+    if xl.dim() not in (2, 3) or xr.dim() != xl.dim() or (xl.dim() == 3 and xl.size(1) != xr.size(1)):
+        raise RuntimeError("%s: xl (n_src[, h], d) and xr (n_dst[, h], d) must have the same h, got %s and %s"
+                           % (fn, tuple(xl.shape), tuple(xr.shape)))
+    if xl.size(-1) != xr.size(-1):
+        raise RuntimeError("%s: xl and xr must have the same d, got %s and %s" % (fn, tuple(xl.shape), tuple(xr.shape)))
+    if tuple(att.shape) != tuple(xl.shape[1:]):
+        raise RuntimeError("%s: att must be %s (the same h and the same d as xl), got %s"
+                           % (fn, tuple(xl.shape[1:]), tuple(att.shape)))
+    return (1 if xl.dim() == 2 else xl.size(1)), xl.size(-1)
+
+
+def _gatv2_workspace_values(n_row_chunks, h, d):
+    """the workspace minimum of graphop_gatv2_scores_backward (include/graphop_hip.h), in values"""
+    return min((n_row_chunks + 15) // 16, 8192) * h * d
+
+
+def gatv2_scores_forward(row, indptr, eid, indices, xl, xr, att, negative_slope=0.2):
+    """y[eid[j], k] = sum_c att[k, c] * LeakyReLU(xl[row[c], k, c] + xr[indices[j], k, c], negative_slope);
+    xl (n_src, d), xr (n_dst, d), att (d) give y (e); xl (n_src, h, d), xr (n_dst, h, d), att (h, d) give y (e, h)"""
+    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices"), (xl, "xl"), (xr, "xr"),
+                 (att, "att")):
+        _check_input(t, n)
+    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices")):
+        _check_index(t, n)
+    h, d = _gatv2_shapes(xl, xr, att, "gatv2_scores_forward")
+    e = eid.size(0)
+    y = torch.empty((e,) if xl.dim() == 2 else (e, h), dtype=xl.dtype, device=xl.device)
+    with _lib.device_guard(xl.device):
+        plan = _plan(row, indptr, eid, indices, xr.size(0))
+        check(lib().graphop_gatv2_scores_forward(
+            dtype_code(xl), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(xl), ptr(xr), ptr(att), ptr(y),
+            row.size(0), e, xl.size(0), xr.size(0), h, d, float(negative_slope), plan.handle, stream_of(xl)))
+    return y
+
+
+def gatv2_scores_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, dy,
+                          negative_slope=0.2):
+    """-> [dxl, dxr, datt] of gatv2_scores_forward for the score gradient dy (z is recomputed from xl and xr)"""
+    names = ("row", "indptr_r", "eid_r", "indices_r", "col", "indptr_c", "eid_c", "indices_c")
+    idx = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
+    for t, n in zip(idx + (xl, xr, att), names + ("xl", "xr", "att")):
+        _check_input(t, n)
+    for t, n in zip(idx, names):
+        _check_index(t, n)
+    if not isinstance(dy, torch.Tensor) or not dy.is_cuda:
+        raise RuntimeError("dy must be a CUDA tensor")
+    h, d = _gatv2_shapes(xl, xr, att, "gatv2_scores_backward")
+    _same_dtype(xl, dy, "xl", "dy")
+    dy = dy.contiguous()
+    e = eid_r.size(0)
+    if dy.numel() != e * h:
+        raise RuntimeError("gatv2_scores_backward: dy must hold (n_edges, h) = (%d, %d) values, got %s"
+                           % (e, h, tuple(dy.shape)))
+    dxl, dxr, datt = torch.empty_like(xl), torch.empty_like(xr), torch.empty_like(att)
+    ws = torch.empty(max(_gatv2_workspace_values(row.size(0), h, d), 1), dtype=xl.dtype, device=xl.device)
+    with _lib.device_guard(xl.device):
+        plan_r = _plan(row, indptr_r, eid_r, indices_r, xr.size(0))
+        plan_c = _plan(col, indptr_c, eid_c, indices_c, xl.size(0))
+        check(lib().graphop_gatv2_scores_backward(
+            dtype_code(xl), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c),
+            ptr(eid_c), ptr(indices_c), ptr(xl), ptr(xr), ptr(att), ptr(dy), ptr(dxl), ptr(dxr), ptr(datt), ptr(ws),
+            ws.numel() * ws.element_size(), row.size(0), col.size(0), e, xl.size(0), xr.size(0), h, d,
+            float(negative_slope), plan_r.handle, plan_c.handle, stream_of(xl)))
+    return [dxl, dxr, datt]
+
+
 # ---- fused GAT attention (extra op) -----------------------------------------------------------------------------
 def _gat_attn_shapes(el, er, V, fn):
     """(h, d) of the fused GAT layer: V is (n_dst, d) with 1-D el / er, else (n_dst, h, d), in their dtype."""
@@ -554,6 +627,8 @@ _SCHEMAS = {
     "gat_attention_dropout_forward": "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, Tensor V, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]",
     "gat_attention_dropout_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor V, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]",
     "edge_dropout_mask": "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, int h, float p=0.0, int seed=0, int offset=0, ScalarType dtype=float) -> Tensor",
+    "gatv2_scores_forward": "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor xl, Tensor xr, Tensor att, float negative_slope=0.2) -> Tensor",
+    "gatv2_scores_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor dy, float negative_slope=0.2) -> Tensor[]",
 }
 _torch_lib = None
 

@@ -392,6 +392,39 @@ GRAPHOP_API int graphop_gat_scores_backward(int dtype, const int64_t* row, const
                                 int64_t n_r, int64_t h, double negative_slope, const graphop_plan_t* plan_r,
                                 const graphop_plan_t* plan_c, void* stream);
 
+/* ---- GATv2 attention scores (ABI 8, additive; EXTRA op, not one of the reference's eight) -------------------------
+ * The score of GATv2 (Brody et al.; GATv2Conv in PyG and DGL): the attention vector sits outside the non-linearity.
+ * gatv2_scores_forward(row, indptr, eid, indices, xl, xr, att, negative_slope) -> y
+ *   y[eid[j], k] = sum_c att[k, c] * LeakyReLU(xl[row[c], k, c] + xr[indices[j], k, c])
+ *   for every slot j of every chunk c, LeakyReLU(z) = z > 0 ? z : z * negative_slope;  xl: (n_l, h, d), xr: (n_r, h, d),
+ *   att: (h, d), y: (n_edges, h).  Edges that no slot names read 0.  The sum over c runs in the kernel's own order, so y
+ *   is NOT bitwise torch's (leaky_relu(xl[src] + xr[dst]) * att).sum(-1): it agrees to rounding.
+ * gatv2_scores_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, dy, negative_slope)
+ *   -> [dxl, dxr, datt], with z[e, k, c] = xl[i, k, c] + xr[n, k, c] recomputed (nothing E-sized is saved) and
+ *   g[e, k, c] = dy[e, k] * att[k, c] * (z > 0 ? 1 : negative_slope)   (the tie z == 0 takes the slope, as torch's
+ *   leaky_relu_backward):
+ *   dxl[row[c]] += sum_j g[eid_r[j]]   and   datt[k, c] = sum_j dy[eid_r[j], k] * LeakyReLU(z[eid_r[j], k, c])   (row-major CSR)
+ *   dxr[col[c]] += sum_j g[eid_c[j]]                                                                            (column-major CSR)
+ *   dxl and datt may be NULL when n_row_chunks == 0, dxr when n_col_chunks == 0 (that half is skipped).
+ *   workspace: at least min(ceil(n_row_chunks / 16), 8192) * h * d values of `dtype` (per-workgroup partial sums of
+ *   datt, added in a fixed order: datt of the fast path is reproducible bit for bit); a smaller one is
+ *   GRAPHOP_ERR_INVALID_ARGUMENT; it may be NULL when that is 0.
+ * With a plan of the same arrays, fp32, h in {1, 2, 4, 8}, d in {8, 16, 32, 64}, h * d in {64, 128, 256}, ids below
+ * 2^31 and 16-byte-aligned tables the fast kernels run (csrc/kernels_gatv2.h); everything else takes the generic ones
+ * (one atomic per chunk and element at most).  Any chunk layout works on both. */
+GRAPHOP_API int graphop_gatv2_scores_forward(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                                 const int64_t* indices, const void* xl, const void* xr, const void* att, void* y,
+                                 int64_t n_chunks, int64_t n_edges, int64_t n_l, int64_t n_r, int64_t h, int64_t d,
+                                 double negative_slope, const graphop_plan_t* plan, void* stream);
+GRAPHOP_API int graphop_gatv2_scores_backward(int dtype, const int64_t* row, const int64_t* indptr_r,
+                                  const int64_t* eid_r, const int64_t* indices_r, const int64_t* col,
+                                  const int64_t* indptr_c, const int64_t* eid_c, const int64_t* indices_c,
+                                  const void* xl, const void* xr, const void* att, const void* dy, void* dxl,
+                                  void* dxr, void* datt, void* workspace, int64_t workspace_bytes,
+                                  int64_t n_row_chunks, int64_t n_col_chunks, int64_t n_edges, int64_t n_l,
+                                  int64_t n_r, int64_t h, int64_t d, double negative_slope,
+                                  const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream);
+
 /* ---- fused GAT attention (ABI 8, additive; EXTRA op, not one of the reference's eight) -----------------------------
  * The layer gat_scores_forward -> sparse_softmax_forward -> vector_spmm_forward as one forward and one backward entry,
  * with no E-sized tensor in either direction.  Per head k, for every slot j of every chunk c with i = row[c]:
