@@ -510,6 +510,66 @@ std::vector<at::Tensor> gatv2_scores_backward(const at::Tensor& row, const at::T
   return {dxl, dxr, datt};
 }
 
+// ---- the fused GATv2 attention op (include/graphop_hip.h: graphop_gatv2_attention_*) ------------------------------
+std::vector<at::Tensor> gatv2_attention_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
+                                                const at::Tensor& indices, const at::Tensor& xl, const at::Tensor& xr,
+                                                const at::Tensor& att, double negative_slope) {
+  CHECK_INPUT(row); CHECK_INPUT(indptr); CHECK_INPUT(eid); CHECK_INPUT(indices); CHECK_INPUT(xl); CHECK_INPUT(xr);
+  CHECK_INPUT(att);
+  CHECK_INDEX(row); CHECK_INDEX(indptr); CHECK_INDEX(eid); CHECK_INDEX(indices);
+  const auto hd = gatv2_shapes(xl, xr, att, "gatv2_attention_forward");
+  const int64_t h = hd.first, d = hd.second;
+  DeviceGuard dg(xl);
+  const int64_t e = eid.size(0), n_l = xl.size(0);
+  auto o = at::empty_like(xl);
+  auto stats = at::empty({n_l, h, 2}, xl.options());
+  const auto pp = get_plan(row, indptr, eid, indices, xr.size(0));
+  const auto& p = *pp;
+  check(graphop_gatv2_attention_forward(dtype_code(xl), ip(row), ip(indptr), ip(eid), ip(indices), vp(xl), vp(xr),
+                                        vp(att), vp(o), vp(stats), row.size(0), e, n_l, xr.size(0), h, d,
+                                        negative_slope, p.plan, stream_of(xl)));
+  return {o, stats};
+}
+
+std::vector<at::Tensor> gatv2_attention_backward(const at::Tensor& row, const at::Tensor& indptr_r,
+                                                 const at::Tensor& eid_r, const at::Tensor& indices_r,
+                                                 const at::Tensor& col, const at::Tensor& indptr_c,
+                                                 const at::Tensor& eid_c, const at::Tensor& indices_c,
+                                                 const at::Tensor& xl, const at::Tensor& xr, const at::Tensor& att,
+                                                 const at::Tensor& o, const at::Tensor& stats, const at::Tensor& dO_,
+                                                 double negative_slope) {
+  const char* fn = "gatv2_attention_backward";
+  CHECK_INPUT(row); CHECK_INPUT(indptr_r); CHECK_INPUT(eid_r); CHECK_INPUT(indices_r);
+  CHECK_INPUT(col); CHECK_INPUT(indptr_c); CHECK_INPUT(eid_c); CHECK_INPUT(indices_c); CHECK_INPUT(xl); CHECK_INPUT(xr);
+  CHECK_INPUT(att); CHECK_INPUT(o); CHECK_INPUT(stats);
+  CHECK_INDEX(row); CHECK_INDEX(indptr_r); CHECK_INDEX(eid_r); CHECK_INDEX(indices_r);
+  CHECK_INDEX(col); CHECK_INDEX(indptr_c); CHECK_INDEX(eid_c); CHECK_INDEX(indices_c);
+  CHECK_CUDA(dO_);
+  const auto hd = gatv2_shapes(xl, xr, att, fn);
+  const int64_t h = hd.first, d = hd.second;
+  CHECK_SAME_DTYPE(xl, o); CHECK_SAME_DTYPE(xl, stats); CHECK_SAME_DTYPE(xl, dO_);
+  const int64_t n_l = xl.size(0);
+  TORCH_CHECK(o.sizes() == xl.sizes() && stats.numel() == n_l * h * 2, fn, ": o must be ", xl.sizes(),
+              " and stats (n_src, h, 2), got ", o.sizes(), " and ", stats.sizes());
+  const at::Tensor dO = dO_.contiguous();
+  TORCH_CHECK(dO.sizes() == o.sizes(), fn, ": dO must match o ", o.sizes(), ", got ", dO.sizes());
+  DeviceGuard dg(xl);
+  const int64_t e = eid_r.size(0);
+  auto dxl = at::empty_like(xl), dxr = at::empty_like(xr), datt = at::empty_like(att);
+  // the workspace minimum of include/graphop_hip.h: n_l * h * 4 + min(ceil(n_row_chunks / 16), 8192) * h * d values
+  const int64_t ws_values = n_l * h * 4 + std::min<int64_t>((row.size(0) + 15) / 16, 8192) * h * d;
+  auto ws = at::empty({std::max<int64_t>(ws_values, 1)}, xl.options());
+  const auto ppr = get_plan(row, indptr_r, eid_r, indices_r, xr.size(0));
+  const auto ppc = get_plan(col, indptr_c, eid_c, indices_c, n_l);
+  const auto &pr = *ppr, &pc = *ppc;
+  check(graphop_gatv2_attention_backward(dtype_code(xl), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col),
+                                         ip(indptr_c), ip(eid_c), ip(indices_c), vp(xl), vp(xr), vp(att), vp(o),
+                                         vp(stats), vp(dO), vp(dxl), vp(dxr), vp(datt), vp(ws),
+                                         ws.numel() * ws.element_size(), row.size(0), col.size(0), e, n_l, xr.size(0),
+                                         h, d, negative_slope, pr.plan, pc.plan, stream_of(xl)));
+  return {dxl, dxr, datt};
+}
+
 // ---- the fused GAT attention op (include/graphop_hip.h: graphop_gat_attention_*) -----------------------------------
 std::pair<int64_t, int64_t> gat_attn_shapes(const at::Tensor& el, const at::Tensor& er, const at::Tensor& V,
                                             const char* fn) {
@@ -748,6 +808,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gatv2_scores_backward", &gatv2_scores_backward, "GATv2 attention scores backward (extra op)", py::arg("row"),
         py::arg("indptr_r"), py::arg("eid_r"), py::arg("indices_r"), py::arg("col"), py::arg("indptr_c"), py::arg("eid_c"),
         py::arg("indices_c"), py::arg("xl"), py::arg("xr"), py::arg("att"), py::arg("dy"), py::arg("negative_slope") = 0.2);
+  m.def("gatv2_attention_forward", &gatv2_attention_forward, "Fused GATv2 attention forward (extra op)", py::arg("row"),
+        py::arg("indptr"), py::arg("eid"), py::arg("indices"), py::arg("xl"), py::arg("xr"), py::arg("att"),
+        py::arg("negative_slope") = 0.2);
+  m.def("gatv2_attention_backward", &gatv2_attention_backward, "Fused GATv2 attention backward (extra op)",
+        py::arg("row"), py::arg("indptr_r"), py::arg("eid_r"), py::arg("indices_r"), py::arg("col"), py::arg("indptr_c"),
+        py::arg("eid_c"), py::arg("indices_c"), py::arg("xl"), py::arg("xr"), py::arg("att"), py::arg("o"),
+        py::arg("stats"), py::arg("dO"), py::arg("negative_slope") = 0.2);
   m.def("clear_plan_cache", &clear_plan_cache, "Destroy every cached per-graph plan");
   m.def("release_plans", &release_plans, "Drop the cached plans of the orientation whose chunk list is `row`");
   m.def("plan_cache_size", &plan_cache_size, "Graph orientations in the plan cache");
@@ -774,6 +841,8 @@ TORCH_LIBRARY(graphop, m) {
   m.def("edge_dropout_mask(Tensor row, Tensor indptr, Tensor eid, Tensor indices, int h, float p=0.0, int seed=0, int offset=0, ScalarType dtype=float) -> Tensor");
   m.def("gatv2_scores_forward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor xl, Tensor xr, Tensor att, float negative_slope=0.2) -> Tensor");
   m.def("gatv2_scores_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor dy, float negative_slope=0.2) -> Tensor[]");
+  m.def("gatv2_attention_forward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor xl, Tensor xr, Tensor att, float negative_slope=0.2) -> Tensor[]");
+  m.def("gatv2_attention_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2) -> Tensor[]");
 }
 
 TORCH_LIBRARY_IMPL(graphop, CUDA, m) {
@@ -796,6 +865,8 @@ TORCH_LIBRARY_IMPL(graphop, CUDA, m) {
   m.impl("edge_dropout_mask", &edge_dropout_mask);
   m.impl("gatv2_scores_forward", &gatv2_scores_forward);
   m.impl("gatv2_scores_backward", &gatv2_scores_backward);
+  m.impl("gatv2_attention_forward", &gatv2_attention_forward);
+  m.impl("gatv2_attention_backward", &gatv2_attention_backward);
 }
 
 TORCH_LIBRARY_IMPL(graphop, CPU, m) {   // there is no CPU implementation: the reference's CHECK_CUDA message
@@ -818,4 +889,6 @@ TORCH_LIBRARY_IMPL(graphop, CPU, m) {   // there is no CPU implementation: the r
   m.impl("edge_dropout_mask", &edge_dropout_mask);
   m.impl("gatv2_scores_forward", &gatv2_scores_forward);
   m.impl("gatv2_scores_backward", &gatv2_scores_backward);
+  m.impl("gatv2_attention_forward", &gatv2_attention_forward);
+  m.impl("gatv2_attention_backward", &gatv2_attention_backward);
 }

@@ -136,6 +136,27 @@ class FusedGATAttention(Function):
         return None, None, None, None, None, None, None, None, d_el, d_er, dV, None
 
 
+class FusedGATv2Attention(Function):
+    """o = VectorSPMM(SparseSoftmax(GATv2Scores(xl, xr, att)), xr) as ONE autograd node (extra op, not in the reference):
+    apply(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, negative_slope).  xl (n_src, d),
+    xr (n_dst, d), att (d) for one head, else (n, h, d) and (h, d); o has n_src rows in xl's layout.  The aggregated table
+    is xr itself (the GATv2Conv convention; gatv2_attention_step serves a separate V).  Saves the CSR arrays, xl, xr,
+    att, o and the row statistics instead of any (E, h) tensor; the backward recomputes scores and weights per slot."""
+
+    @staticmethod
+    def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, negative_slope):
+        o, stats = _ops.gatv2_attention_forward(row, indptr_r, eid_r, indices_r, xl, xr, att, float(negative_slope))
+        ctx.save_for_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, o, stats)
+        ctx.negative_slope = float(negative_slope)
+        return o
+
+    @staticmethod
+    def backward(ctx, dO):
+        a8, (xl, xr, att, o, stats) = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
+        dxl, dxr, datt = _ops.gatv2_attention_backward(*a8, xl, xr, att, o, stats, dO, ctx.negative_slope)
+        return None, None, None, None, None, None, None, None, dxl, dxr, datt, None
+
+
 class FusedGATAttentionDropout(Function):
     """FusedGATAttention with dropout on the attention weights, o[i] = sum_j a_ij m_ij V[j] (extra op):
     apply(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V, negative_slope, p, seed, offset).
@@ -351,6 +372,15 @@ def gatv2_attention_step(g, xl, xr, att, dO, negative_slope=0.2, V=None):
     o.backward(dO)
     _lib.check_errors(sync=False)     # as in attention_step
     return s, a, o
+
+
+def fused_gatv2_attention_step(g, xl, xr, att, dO, negative_slope=0.2):
+    """The counterpart of gatv2_attention_step(V=None) through FusedGATv2Attention: o = GATv2 layer(xl, xr, att);
+    o.backward(dO).  xl, xr, att must be leaf tensors with requires_grad; returns o (no E-sized tensor is kept or made)."""
+    o = FusedGATv2Attention.apply(*g.csr_args(), xl, xr, att, negative_slope)
+    o.backward(dO)
+    _lib.check_errors(sync=False)     # as in attention_step
+    return o
 
 
 def fused_gat_attention_step(g, el, er, V, dO, negative_slope=0.2):

@@ -34,7 +34,8 @@ __all__ = ["maskedmm_csr_forward", "maskedmm_csr_backward", "node_mul_edge_forwa
 EXTRA_OPS = ["attention_forward", "attention_backward", "attention_backward_is_fused", "gat_scores_forward",
              "gat_scores_backward", "gat_attention_forward", "gat_attention_backward",
              "gat_attention_dropout_forward", "gat_attention_dropout_backward", "edge_dropout_mask",
-             "gatv2_scores_forward", "gatv2_scores_backward"]
+             "gatv2_scores_forward", "gatv2_scores_backward", "gatv2_attention_forward",
+             "gatv2_attention_backward"]
 
 _NULL = None
 
@@ -462,6 +463,70 @@ def gatv2_scores_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
     return [dxl, dxr, datt]
 
 
+# ---- fused GATv2 attention (extra op) ---------------------------------------------------------------------------
+def _gatv2_attention_workspace_values(n_l, n_row_chunks, h, d):
+    """the workspace minimum of graphop_gatv2_attention_backward (include/graphop_hip.h), in values"""
+    return n_l * h * 4 + min((n_row_chunks + 15) // 16, 8192) * h * d
+
+
+def gatv2_attention_forward(row, indptr, eid, indices, xl, xr, att, negative_slope=0.2):
+    """-> [o, stats]: o[i] = sum_j softmax_j(att . LeakyReLU(xl[i] + xr[j])) xr[j] per head over the row-major CSR,
+    without any E-sized tensor; o has n_src = xl.size(0) rows in xl's layout, stats (n_src, h, 2) = (row max, 1 / sum exp)."""
+    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices"), (xl, "xl"), (xr, "xr"),
+                 (att, "att")):
+        _check_input(t, n)
+    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices")):
+        _check_index(t, n)
+    h, d = _gatv2_shapes(xl, xr, att, "gatv2_attention_forward")
+    e, n_l = eid.size(0), xl.size(0)
+    o = torch.empty_like(xl)
+    stats = torch.empty((n_l, h, 2), dtype=xl.dtype, device=xl.device)
+    with _lib.device_guard(xl.device):
+        plan = _plan(row, indptr, eid, indices, xr.size(0))
+        check(lib().graphop_gatv2_attention_forward(
+            dtype_code(xl), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(xl), ptr(xr), ptr(att), ptr(o),
+            ptr(stats), row.size(0), e, n_l, xr.size(0), h, d, float(negative_slope), plan.handle, stream_of(xl)))
+    return [o, stats]
+
+
+def gatv2_attention_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, o, stats,
+                             dO, negative_slope=0.2):
+    """-> [dxl, dxr, datt] of gatv2_attention_forward for the output gradient dO (z, s and a recomputed per slot from
+    xl, xr, att and stats)."""
+    fn = "gatv2_attention_backward"
+    names = ("row", "indptr_r", "eid_r", "indices_r", "col", "indptr_c", "eid_c", "indices_c")
+    idx = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
+    for t, n in zip(idx + (xl, xr, att, o, stats), names + ("xl", "xr", "att", "o", "stats")):
+        _check_input(t, n)
+    for t, n in zip(idx, names):
+        _check_index(t, n)
+    if not isinstance(dO, torch.Tensor) or not dO.is_cuda:
+        raise RuntimeError("dO must be a CUDA tensor")
+    h, d = _gatv2_shapes(xl, xr, att, fn)
+    for t, n in ((o, "o"), (stats, "stats"), (dO, "dO")):
+        _same_dtype(xl, t, "xl", n)
+    n_l = xl.size(0)
+    if o.shape != xl.shape or stats.numel() != n_l * h * 2:
+        raise RuntimeError("%s: o must be %s and stats (n_src, h, 2), got %s and %s"
+                           % (fn, tuple(xl.shape), tuple(o.shape), tuple(stats.shape)))
+    dO = dO.contiguous()
+    if dO.shape != o.shape:
+        raise RuntimeError("%s: dO must match o %s, got %s" % (fn, tuple(o.shape), tuple(dO.shape)))
+    e = eid_r.size(0)
+    dxl, dxr, datt = torch.empty_like(xl), torch.empty_like(xr), torch.empty_like(att)
+    ws = torch.empty(max(_gatv2_attention_workspace_values(n_l, row.size(0), h, d), 1), dtype=xl.dtype,
+                     device=xl.device)
+    with _lib.device_guard(xl.device):
+        plan_r = _plan(row, indptr_r, eid_r, indices_r, xr.size(0))
+        plan_c = _plan(col, indptr_c, eid_c, indices_c, n_l)
+        check(lib().graphop_gatv2_attention_backward(
+            dtype_code(xl), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c),
+            ptr(eid_c), ptr(indices_c), ptr(xl), ptr(xr), ptr(att), ptr(o), ptr(stats), ptr(dO), ptr(dxl), ptr(dxr),
+            ptr(datt), ptr(ws), ws.numel() * ws.element_size(), row.size(0), col.size(0), e, n_l, xr.size(0), h, d,
+            float(negative_slope), plan_r.handle, plan_c.handle, stream_of(xl)))
+    return [dxl, dxr, datt]
+
+
 # ---- fused GAT attention (extra op) -----------------------------------------------------------------------------
 def _gat_attn_shapes(el, er, V, fn):
     """(h, d) of the fused GAT layer: V is (n_dst, d) with 1-D el / er, else (n_dst, h, d), in their dtype."""
@@ -629,6 +694,8 @@ _SCHEMAS = {
     "edge_dropout_mask": "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, int h, float p=0.0, int seed=0, int offset=0, ScalarType dtype=float) -> Tensor",
     "gatv2_scores_forward": "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor xl, Tensor xr, Tensor att, float negative_slope=0.2) -> Tensor",
     "gatv2_scores_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor dy, float negative_slope=0.2) -> Tensor[]",
+    "gatv2_attention_forward": "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor xl, Tensor xr, Tensor att, float negative_slope=0.2) -> Tensor[]",
+    "gatv2_attention_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2) -> Tensor[]",
 }
 _torch_lib = None
 

@@ -425,6 +425,45 @@ GRAPHOP_API int graphop_gatv2_scores_backward(int dtype, const int64_t* row, con
                                   int64_t n_r, int64_t h, int64_t d, double negative_slope,
                                   const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream);
 
+/* ---- fused GATv2 attention (ABI 8, additive; EXTRA op, not one of the reference's eight) ---------------------------
+ * The layer gatv2_scores_forward -> sparse_softmax_forward -> vector_spmm_forward(a, xr) as one forward and one backward
+ * entry, with no E-sized tensor in either direction.  The aggregated table is xr itself (the GATv2Conv convention).  Per
+ * head k, for every slot j of every chunk c with i = row[c], n = indices[j]:
+ *   z_inc = xl[i, k, c] + xr[n, k, c],  s_in = sum_c att[k, c] * LeakyReLU(z_inc)
+ *   m_i = max(-1e9, max_n s_in),  l_i = sum_n exp(s_in - m_i),  a_in = exp(s_in - m_i) / l_i
+ *   o[i, k, :] = sum_n a_in xr[n, k, :],  stats[(i*h + k)*2 + {0,1}] = (m_i, 1 / l_i); a row without slots gets o = 0 and
+ *   stats (-1e9, 0)
+ * gatv2_attention_forward(row, indptr, eid, indices, xl, xr, att, negative_slope) -> [o, stats]
+ *   xl (n_l, h, d), xr (n_r, h, d), att (h, d), o (n_l, h, d), stats (n_l, h, 2).
+ * gatv2_attention_backward(<8 csr>, xl, xr, att, o, stats, dO, negative_slope) -> [dxl, dxr, datt], z, s and a recomputed
+ * per slot:
+ *   D_i = <dO_i, o_i>, da_in = <dO_i, xr_n>, ds_in = a_in (da_in - D_i), t_inc = (z_inc > 0 ? 1 : negative_slope) (the tie
+ *   z == 0 takes the slope)
+ *   dxl[i, k, c] = att[k, c] sum_n ds_in t_inc  and  datt[k, c] = sum_in ds_in LeakyReLU(z_inc)          (row-major CSR)
+ *   dxr[n, k, c] = sum_i (ds_in att[k, c] t_inc + a_in dO[i, k, c])                                     (column-major CSR)
+ *   dxl and datt may be NULL when n_row_chunks == 0, dxr when n_col_chunks == 0 (that half is skipped).
+ *   workspace: at least n_l * h * 4 values of `dtype` (the per-(node, head) items (m, 1 / l, D, 0) the passes read) plus
+ *   min(ceil(n_row_chunks / 16), 8192) * h * d values (per-workgroup partial sums of datt, added in a fixed order: datt
+ *   of the fast path is reproducible bit for bit); a smaller one is GRAPHOP_ERR_INVALID_ARGUMENT.
+ * eid is validated and used for plan lookup only.  With a plan of the same arrays, fp32, h in {1, 2, 4, 8}, d in
+ * {8, 16, 32, 64}, h * d in {64, 128, 256}, ids below 2^31 and 16-byte-aligned tables the fast kernels run
+ * (csrc/kernels_gatv2_attn.h; the forward needs a row_owned plan: sorted chunk list, monotone indptr; it uses no atomics,
+ * so o and stats are reproducible bit for bit); everything else takes the generic ones.  Any chunk layout works on both. */
+GRAPHOP_API int graphop_gatv2_attention_forward(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                                    const int64_t* indices, const void* xl, const void* xr, const void* att, void* o,
+                                    void* stats, int64_t n_chunks, int64_t n_edges, int64_t n_l, int64_t n_r,
+                                    int64_t h, int64_t d, double negative_slope, const graphop_plan_t* plan,
+                                    void* stream);
+GRAPHOP_API int graphop_gatv2_attention_backward(int dtype, const int64_t* row, const int64_t* indptr_r,
+                                     const int64_t* eid_r, const int64_t* indices_r, const int64_t* col,
+                                     const int64_t* indptr_c, const int64_t* eid_c, const int64_t* indices_c,
+                                     const void* xl, const void* xr, const void* att, const void* o, const void* stats,
+                                     const void* dO, void* dxl, void* dxr, void* datt, void* workspace,
+                                     int64_t workspace_bytes, int64_t n_row_chunks, int64_t n_col_chunks,
+                                     int64_t n_edges, int64_t n_l, int64_t n_r, int64_t h, int64_t d,
+                                     double negative_slope, const graphop_plan_t* plan_r,
+                                     const graphop_plan_t* plan_c, void* stream);
+
 /* ---- fused GAT attention (ABI 8, additive; EXTRA op, not one of the reference's eight) -----------------------------
  * The layer gat_scores_forward -> sparse_softmax_forward -> vector_spmm_forward as one forward and one backward entry,
  * with no E-sized tensor in either direction.  Per head k, for every slot j of every chunk c with i = row[c]:
