@@ -87,6 +87,10 @@ _SIGNATURES = {
     "graphop_gatv2_scores_backward": [ctypes.c_int] + [_P] * 16 + [_c64] * 8 + [ctypes.c_double, _P, _P, _P],
     "graphop_gatv2_attention_forward": [ctypes.c_int] + [_P] * 9 + [_c64] * 6 + [ctypes.c_double, _P, _P],
     "graphop_gatv2_attention_backward": [ctypes.c_int] + [_P] * 18 + [_c64] * 8 + [ctypes.c_double, _P, _P, _P],
+    "graphop_gatv2_attention_dropout_forward": [ctypes.c_int] + [_P] * 9 + [_c64] * 6
+    + [ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _P, _P],
+    "graphop_gatv2_attention_dropout_backward": [ctypes.c_int] + [_P] * 18 + [_c64] * 8
+    + [ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _P, _P, _P],
     "graphop_gat_attention_forward": [ctypes.c_int] + [_P] * 9 + [_c64] * 6 + [ctypes.c_double, _P, _P],
     "graphop_gat_attention_backward": [ctypes.c_int] + [_P] * 18 + [_c64] * 8 + [ctypes.c_double, _P, _P, _P],
     "graphop_gat_attention_dropout_forward": [ctypes.c_int] + [_P] * 9 + [_c64] * 6

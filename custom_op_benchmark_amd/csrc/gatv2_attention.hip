@@ -5,8 +5,11 @@
 // validation, fills, and the choice between the fp32 fast kernels (a plan of the same arrays, the (h, d) pairs of the
 // fused GAT layer, ids below 2^31, 16-byte-aligned tables) and the generic ones (fp64, other shapes, NULL plans; the
 // forward also where the plan is not row_owned).
+// The *_dropout_* entry points are the same op with attention dropout (kernels_dropout.h: the keep decision of an edge
+// is recomputed from Philox in each gather pass, so still no E-sized tensor); p == 0 is the op without it.
 #include "common.h"
 #include "host.h"
+#include "host_dropout.h"
 #include "kernels_gatv2_attn.h"
 
 namespace graphop {
@@ -66,6 +69,17 @@ inline bool gv2attn_fast_ok(int dtype, i64 h, i64 d, i64 E, i64 n_l, i64 n_r, st
   if (b) { constexpr bool NAME = true; __VA_ARGS__; }    \
   else { constexpr bool NAME = false; __VA_ARGS__; }
 
+// ProfScope tag [drop] and kernel label [drop][fast] of a gather pass ("fwd", "bwd_row", "bwd_col"), as in
+// gat_attention.hip: the drop names are those of the path taken (the k_gv2drop_* kernels, the generic DROP = true ones)
+struct Gv2AttnLabels {
+  const char* tag[2];
+  const char* kernel[2][2];
+};
+#define GO_GV2ATTN_LABELS(pass)                                            \
+  Gv2AttnLabels{{"gv2attn_" pass, "gv2attn_drop_" pass},                   \
+                {{"k_gv2attn_" pass "_generic", "k_gv2attn_" pass "_f32"}, \
+                 {"k_gv2attn_drop_" pass "_generic", "k_gv2attn_drop_" pass "_f32"}}}
+
 // chunks per lane group: up to the SpMM cap on big graphs, fewer on small ones so every CU still gets groups
 inline i64 gv2attn_cpg(i64 n_chunks) {
   const i64 groups_wanted = (i64)tuning().n_cu * (kFastBlock / kGv2AttnGroup) * 8;
@@ -96,15 +110,13 @@ inline unsigned gv2attn_grid_of(i64 n) {
 
 using namespace graphop;
 
-extern "C" {
+namespace {
 
-int graphop_gatv2_attention_forward(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
-                                    const int64_t* indices, const void* xl, const void* xr, const void* att, void* o,
-                                    void* stats, int64_t n_chunks, int64_t n_edges, int64_t n_l, int64_t n_r,
-                                    int64_t h, int64_t d, double negative_slope, const graphop_plan_t* plan,
-                                    void* stream) {
-  const char* fn = "gatv2_attention_forward";
-  GO_TRY(gv2attn_check(fn, dtype, n_chunks, 0, n_edges, n_l, n_r, h, d));
+// drop == nullptr: the op without dropout (the DROP = false kernels, whatever the entry point)
+int gv2attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                    const int64_t* indices, const void* xl, const void* xr, const void* att, void* o, void* stats,
+                    int64_t n_chunks, int64_t n_edges, int64_t n_l, int64_t n_r, int64_t h, int64_t d,
+                    double negative_slope, const HostDrop* drop, const graphop_plan_t* plan, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const size_t es = esize(dtype);
   const graphop_plan* pm = plan_matches_full(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
@@ -126,23 +138,31 @@ int graphop_gatv2_attention_forward(int dtype, const int64_t* row, const int64_t
   GO_PTR(fn, xl); GO_PTR(fn, xr); GO_PTR(fn, att);
   const bool fast = pm && pm->info.row_owned && pm->seg_chunk &&
                     gv2attn_fast_ok(dtype, h, d, n_edges, n_l, n_r, {xl, xr, att, o, stats});
+  const bool dropped = drop != nullptr;
+  static const Gv2AttnLabels lab = GO_GV2ATTN_LABELS("fwd");
   if (fast) {
     const i64 S = pm->info.n_segments;
     if (S == 0) return GRAPHOP_OK;
-    ProfScope prof("gv2attn_fwd", st, "k_gv2attn_fwd_f32");
+    ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][1]);
     const int n_long = (int)pm->n_long;
     const i64 long_len = n_long > 0 ? kLongSegment : ((i64)1 << 62);
     const unsigned nbs = (unsigned)ceil_div(S, (i64)(kFastBlock / kGv2AttnGroup));
     GO_DISPATCH_GV2ATTN(h, d, {
-      hipLaunchKernelGGL((k_gv2attn_fwd_f32<H, D>), dim3(nbs + (unsigned)n_long), dim3(kFastBlock), 0, st,
-                         (const i64*)row, (const i64*)indptr, (const i64*)indices, (const i64*)pm->seg_chunk,
-                         (const float*)xl, (const float*)xr, (const float*)att, (float*)o, (float2*)stats, S, nbs,
-                         long_len, (const int*)pm->long_segs, (float)negative_slope);
+      if (dropped)
+        hipLaunchKernelGGL((k_gv2drop_fwd_f32<H, D>), dim3(nbs + (unsigned)n_long), dim3(kFastBlock), 0, st,
+                           (const i64*)row, (const i64*)indptr, (const i64*)indices, (const i64*)pm->seg_chunk,
+                           (const float*)xl, (const float*)xr, (const float*)att, (float*)o, (float2*)stats, S, nbs,
+                           long_len, (const int*)pm->long_segs, (float)negative_slope, drop->as<float>());
+      else
+        hipLaunchKernelGGL((k_gv2attn_fwd_f32<H, D>), dim3(nbs + (unsigned)n_long), dim3(kFastBlock), 0, st,
+                           (const i64*)row, (const i64*)indptr, (const i64*)indices, (const i64*)pm->seg_chunk,
+                           (const float*)xl, (const float*)xr, (const float*)att, (float*)o, (float2*)stats, S, nbs,
+                           long_len, (const int*)pm->long_segs, (float)negative_slope, NoDrop{});
     });
     GO_LAUNCH_CHECK();
     return GRAPHOP_OK;
   }
-  ProfScope prof("gv2attn_fwd", st, "k_gv2attn_fwd_generic");
+  ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][0]);
   const unsigned nb = (unsigned)ceil_div(n_chunks, kGenericWavesPerBlock);
   auto go = [&](auto zero) {
     using T = decltype(zero);
@@ -154,25 +174,24 @@ int graphop_gatv2_attention_forward(int dtype, const int64_t* row, const int64_t
                        n_chunks, h, d, (T)negative_slope);
     hipLaunchKernelGGL((k_gv2attn_stats_fin_generic<T>), dim3(gv2attn_grid_of(n_l * h)), dim3(256), 0, st, (T*)stats,
                        n_l * h);
-    hipLaunchKernelGGL((k_gv2attn_fwd_generic<T>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)row,
-                       (const i64*)indptr, (const i64*)indices, (const T*)xl, (const T*)xr, (const T*)att,
-                       (const T*)stats, (T*)o, n_chunks, h, d, (T)negative_slope);
+    GO_DISPATCH_GV2ATTN_BOOL(dropped, DROP, {
+      hipLaunchKernelGGL((k_gv2attn_fwd_generic<T, DROP>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)row,
+                         (const i64*)indptr, (const i64*)indices, (const T*)xl, (const T*)xr, (const T*)att,
+                         (const T*)stats, (T*)o, n_chunks, h, d, (T)negative_slope, drop_arg<DROP, T>(drop));
+    });
   };
   if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
   GO_LAUNCH_CHECK();
   return GRAPHOP_OK;
 }
 
-int graphop_gatv2_attention_backward(int dtype, const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r,
-                                     const int64_t* indices_r, const int64_t* col, const int64_t* indptr_c,
-                                     const int64_t* eid_c, const int64_t* indices_c, const void* xl, const void* xr,
-                                     const void* att, const void* o, const void* stats, const void* dO, void* dxl,
-                                     void* dxr, void* datt, void* workspace, int64_t workspace_bytes,
-                                     int64_t n_row_chunks, int64_t n_col_chunks, int64_t n_edges, int64_t n_l,
-                                     int64_t n_r, int64_t h, int64_t d, double negative_slope,
-                                     const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream) {
-  const char* fn = "gatv2_attention_backward";
-  GO_TRY(gv2attn_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_l, n_r, h, d));
+int gv2attn_backward(const char* fn, int dtype, const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r,
+                     const int64_t* indices_r, const int64_t* col, const int64_t* indptr_c, const int64_t* eid_c,
+                     const int64_t* indices_c, const void* xl, const void* xr, const void* att, const void* o,
+                     const void* stats, const void* dO, void* dxl, void* dxr, void* datt, void* workspace,
+                     int64_t workspace_bytes, int64_t n_row_chunks, int64_t n_col_chunks, int64_t n_edges, int64_t n_l,
+                     int64_t n_r, int64_t h, int64_t d, double negative_slope, const HostDrop* drop,
+                     const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const size_t es = esize(dtype);
   const i64 f = h * d;
@@ -209,6 +228,7 @@ int graphop_gatv2_attention_backward(int dtype, const int64_t* row, const int64_
   GO_PTR(fn, workspace);
   const bool ok = gv2attn_fast_ok(dtype, h, d, n_edges, n_l, n_r, {xl, xr, att, o, stats, dO, workspace});
   const float slope = (float)negative_slope;
+  const bool dropped = drop != nullptr;
   void* part = (char*)workspace + es * (size_t)p_values;
   {   // P[i, k] = (m, 1 / l, D, 0)
     const bool fast = ok && (pr || pc);
@@ -236,17 +256,24 @@ int graphop_gatv2_attention_backward(int dtype, const int64_t* row, const int64_
     if (ok && pr && (((uintptr_t)dxl | (uintptr_t)datt) & 15) == 0) {
       i64 nb;
       {
-        ProfScope prof("gv2attn_bwd_row", st, "k_gv2attn_bwd_row_f32");
+        static const Gv2AttnLabels lab = GO_GV2ATTN_LABELS("bwd_row");
+        ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][1]);
         i64 cpg = gv2attn_cpg(C);
         if (gv2attn_grid(C, cpg) > kGv2AttnMaxRowBlocks)
           cpg = ceil_div(C, kGv2AttnMaxRowBlocks * (kFastBlock / kGv2AttnGroup));
         nb = gv2attn_grid(C, cpg);   // <= gv2attn_part_rows(C): cpg >= 1 and the cap above
         const bool owned = pr->info.rows_sorted != 0;
         GO_DISPATCH_GV2ATTN(h, d, GO_DISPATCH_GV2ATTN_BOOL(owned, OWNED, {
-          hipLaunchKernelGGL((k_gv2attn_bwd_row_f32<H, D, OWNED>), dim3((unsigned)nb), dim3(kFastBlock), 0, st,
-                             (const i64*)row, (const i64*)indptr_r, (const i64*)indices_r, (const float*)xl,
-                             (const float*)xr, (const float*)att, (const float4*)workspace, (const float*)dO,
-                             (float*)dxl, (float4*)part, C, (int)cpg, slope);
+          if (dropped)
+            hipLaunchKernelGGL((k_gv2drop_bwd_row_f32<H, D, OWNED>), dim3((unsigned)nb), dim3(kFastBlock), 0, st,
+                               (const i64*)row, (const i64*)indptr_r, (const i64*)indices_r, (const float*)xl,
+                               (const float*)xr, (const float*)att, (const float4*)workspace, (const float*)dO,
+                               (float*)dxl, (float4*)part, C, (int)cpg, slope, drop->as<float>());
+          else
+            hipLaunchKernelGGL((k_gv2attn_bwd_row_f32<H, D, OWNED>), dim3((unsigned)nb), dim3(kFastBlock), 0, st,
+                               (const i64*)row, (const i64*)indptr_r, (const i64*)indices_r, (const float*)xl,
+                               (const float*)xr, (const float*)att, (const float4*)workspace, (const float*)dO,
+                               (float*)dxl, (float4*)part, C, (int)cpg, slope, NoDrop{});
         }));
         GO_LAUNCH_CHECK();
       }
@@ -254,13 +281,17 @@ int graphop_gatv2_attention_backward(int dtype, const int64_t* row, const int64_
       hipLaunchKernelGGL(k_gv2attn_datt_fin_f32, dim3((unsigned)(f / 4)), dim3(kFastBlock), 0, st,
                          (const float4*)part, (float4*)datt, nb, (int)(f / 4));
     } else {
-      ProfScope prof("gv2attn_bwd_row", st, "k_gv2attn_bwd_row_generic");
+      static const Gv2AttnLabels lab = GO_GV2ATTN_LABELS("bwd_row");
+      ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][0]);
       const unsigned nb = (unsigned)ceil_div(C, kGenericWavesPerBlock);
       auto go = [&](auto zero) {
         using T = decltype(zero);
-        hipLaunchKernelGGL((k_gv2attn_bwd_row_generic<T>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)row,
-                           (const i64*)indptr_r, (const i64*)indices_r, (const T*)xl, (const T*)xr, (const T*)att,
-                           (const T*)workspace, (const T*)dO, (T*)dxl, (T*)datt, C, h, d, (T)negative_slope);
+        GO_DISPATCH_GV2ATTN_BOOL(dropped, DROP, {
+          hipLaunchKernelGGL((k_gv2attn_bwd_row_generic<T, DROP>), dim3(nb), dim3(kGenericBlock), 0, st,
+                             (const i64*)row, (const i64*)indptr_r, (const i64*)indices_r, (const T*)xl, (const T*)xr,
+                             (const T*)att, (const T*)workspace, (const T*)dO, (T*)dxl, (T*)datt, C, h, d,
+                             (T)negative_slope, drop_arg<DROP, T>(drop));
+        });
       };
       if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
     }
@@ -270,30 +301,103 @@ int graphop_gatv2_attention_backward(int dtype, const int64_t* row, const int64_
     GO_PTR(fn, col); GO_PTR(fn, indptr_c); GO_PTR(fn, eid_c); GO_PTR(fn, indices_c);
     GO_PTR(fn, dxr);
     const i64 C = n_col_chunks;
+    static const Gv2AttnLabels lab = GO_GV2ATTN_LABELS("bwd_col");
     if (ok && pc && ((uintptr_t)dxr & 15) == 0) {
-      ProfScope prof("gv2attn_bwd_col", st, "k_gv2attn_bwd_col_f32");
+      ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][1]);
       const i64 cpg = gv2attn_cpg(C);
       const bool owned = pc->info.rows_sorted != 0;
       GO_DISPATCH_GV2ATTN(h, d, GO_DISPATCH_GV2ATTN_BOOL(owned, OWNED, {
-        hipLaunchKernelGGL((k_gv2attn_bwd_col_f32<H, D, OWNED>), dim3((unsigned)gv2attn_grid(C, cpg)),
-                           dim3(kFastBlock), 0, st, (const i64*)col, (const i64*)indptr_c, (const i64*)indices_c,
-                           (const float*)xl, (const float*)xr, (const float*)att, (const float4*)workspace,
-                           (const float*)dO, (float*)dxr, C, (int)cpg, slope);
+        if (dropped)
+          hipLaunchKernelGGL((k_gv2drop_bwd_col_f32<H, D, OWNED>), dim3((unsigned)gv2attn_grid(C, cpg)),
+                             dim3(kFastBlock), 0, st, (const i64*)col, (const i64*)indptr_c, (const i64*)indices_c,
+                             (const float*)xl, (const float*)xr, (const float*)att, (const float4*)workspace,
+                             (const float*)dO, (float*)dxr, C, (int)cpg, slope, drop->as<float>());
+        else
+          hipLaunchKernelGGL((k_gv2attn_bwd_col_f32<H, D, OWNED>), dim3((unsigned)gv2attn_grid(C, cpg)),
+                             dim3(kFastBlock), 0, st, (const i64*)col, (const i64*)indptr_c, (const i64*)indices_c,
+                             (const float*)xl, (const float*)xr, (const float*)att, (const float4*)workspace,
+                             (const float*)dO, (float*)dxr, C, (int)cpg, slope, NoDrop{});
       }));
     } else {
-      ProfScope prof("gv2attn_bwd_col", st, "k_gv2attn_bwd_col_generic");
+      ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][0]);
       const unsigned nb = (unsigned)ceil_div(C, kGenericWavesPerBlock);
       auto go = [&](auto zero) {
         using T = decltype(zero);
-        hipLaunchKernelGGL((k_gv2attn_bwd_col_generic<T>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)col,
-                           (const i64*)indptr_c, (const i64*)indices_c, (const T*)xl, (const T*)xr, (const T*)att,
-                           (const T*)workspace, (const T*)dO, (T*)dxr, C, h, d, (T)negative_slope);
+        GO_DISPATCH_GV2ATTN_BOOL(dropped, DROP, {
+          hipLaunchKernelGGL((k_gv2attn_bwd_col_generic<T, DROP>), dim3(nb), dim3(kGenericBlock), 0, st,
+                             (const i64*)col, (const i64*)indptr_c, (const i64*)indices_c, (const T*)xl, (const T*)xr,
+                             (const T*)att, (const T*)workspace, (const T*)dO, (T*)dxr, C, h, d, (T)negative_slope,
+                             drop_arg<DROP, T>(drop));
+        });
       };
       if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
     }
     GO_LAUNCH_CHECK();
   }
   return GRAPHOP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int graphop_gatv2_attention_forward(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                                    const int64_t* indices, const void* xl, const void* xr, const void* att, void* o,
+                                    void* stats, int64_t n_chunks, int64_t n_edges, int64_t n_l, int64_t n_r,
+                                    int64_t h, int64_t d, double negative_slope, const graphop_plan_t* plan,
+                                    void* stream) {
+  const char* fn = "gatv2_attention_forward";
+  GO_TRY(gv2attn_check(fn, dtype, n_chunks, 0, n_edges, n_l, n_r, h, d));
+  return gv2attn_forward(fn, dtype, row, indptr, eid, indices, xl, xr, att, o, stats, n_chunks, n_edges, n_l, n_r, h, d,
+                         negative_slope, nullptr, plan, stream);
+}
+
+int graphop_gatv2_attention_backward(int dtype, const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r,
+                                     const int64_t* indices_r, const int64_t* col, const int64_t* indptr_c,
+                                     const int64_t* eid_c, const int64_t* indices_c, const void* xl, const void* xr,
+                                     const void* att, const void* o, const void* stats, const void* dO, void* dxl,
+                                     void* dxr, void* datt, void* workspace, int64_t workspace_bytes,
+                                     int64_t n_row_chunks, int64_t n_col_chunks, int64_t n_edges, int64_t n_l,
+                                     int64_t n_r, int64_t h, int64_t d, double negative_slope,
+                                     const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream) {
+  const char* fn = "gatv2_attention_backward";
+  GO_TRY(gv2attn_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_l, n_r, h, d));
+  return gv2attn_backward(fn, dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, o,
+                          stats, dO, dxl, dxr, datt, workspace, workspace_bytes, n_row_chunks, n_col_chunks, n_edges,
+                          n_l, n_r, h, d, negative_slope, nullptr, plan_r, plan_c, stream);
+}
+
+// p == 0 runs the kernels of the entry points above: bit-identical results
+int graphop_gatv2_attention_dropout_forward(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                                            const int64_t* indices, const void* xl, const void* xr, const void* att,
+                                            void* o, void* stats, int64_t n_chunks, int64_t n_edges, int64_t n_l,
+                                            int64_t n_r, int64_t h, int64_t d, double negative_slope, double p,
+                                            uint64_t seed, uint32_t offset, const graphop_plan_t* plan, void* stream) {
+  const char* fn = "gatv2_attention_dropout_forward";
+  GO_TRY(gv2attn_check(fn, dtype, n_chunks, 0, n_edges, n_l, n_r, h, d));
+  HostDrop drop;
+  GO_TRY(drop_check(fn, p, seed, n_l, n_r, offset, &drop));
+  return gv2attn_forward(fn, dtype, row, indptr, eid, indices, xl, xr, att, o, stats, n_chunks, n_edges, n_l, n_r, h, d,
+                         negative_slope, p > 0.0 ? &drop : nullptr, plan, stream);
+}
+
+int graphop_gatv2_attention_dropout_backward(int dtype, const int64_t* row, const int64_t* indptr_r,
+                                             const int64_t* eid_r, const int64_t* indices_r, const int64_t* col,
+                                             const int64_t* indptr_c, const int64_t* eid_c, const int64_t* indices_c,
+                                             const void* xl, const void* xr, const void* att, const void* o,
+                                             const void* stats, const void* dO, void* dxl, void* dxr, void* datt,
+                                             void* workspace, int64_t workspace_bytes, int64_t n_row_chunks,
+                                             int64_t n_col_chunks, int64_t n_edges, int64_t n_l, int64_t n_r,
+                                             int64_t h, int64_t d, double negative_slope, double p, uint64_t seed,
+                                             uint32_t offset, const graphop_plan_t* plan_r,
+                                             const graphop_plan_t* plan_c, void* stream) {
+  const char* fn = "gatv2_attention_dropout_backward";
+  GO_TRY(gv2attn_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_l, n_r, h, d));
+  HostDrop drop;
+  GO_TRY(drop_check(fn, p, seed, n_l, n_r, offset, &drop));
+  return gv2attn_backward(fn, dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, o,
+                          stats, dO, dxl, dxr, datt, workspace, workspace_bytes, n_row_chunks, n_col_chunks, n_edges,
+                          n_l, n_r, h, d, negative_slope, p > 0.0 ? &drop : nullptr, plan_r, plan_c, stream);
 }
 
 }  // extern "C"

@@ -7,6 +7,7 @@
 #pragma once
 #include <type_traits>
 
+#include "kernels_base.h"
 #include "kernels_generic.h"
 
 namespace graphop {
@@ -55,6 +56,41 @@ __device__ __forceinline__ int drop_keep4(unsigned i, unsigned j, unsigned blk, 
 template <typename T>
 __device__ __forceinline__ T drop_mult(i64 i, i64 j, i64 k, const DropArgs<T>& dr) {
   return (drop_keep4<T>((unsigned)i, (unsigned)j, (unsigned)(k >> 2), dr) >> (int)(k & 3)) & 1 ? dr.scale : (T)0;
+}
+
+// ---- the decision in the fast gather passes of the fused GAT and GATv2 layers (16-lane groups) ------------------------
+// The lanes that load a batch's neighbour ids also run Philox for them: lane t < SB holds slot t.  One call covers four
+// heads; for H = 8 lane SB + t takes the second block of slot t where the group has room (2 * SB <= L), else lane t
+// makes both calls.  `own` is the chunk's node, `oth` the gathered one; COL says which of them is the row-major row i.
+template <int H, int SB>
+struct GatDropCfg {
+  static constexpr int L = 16;
+  static constexpr int NB = (H + 3) / 4;            // Philox blocks per slot
+  static constexpr bool SPREAD = NB * SB <= L;      // one block per lane
+  static constexpr int LANES = SPREAD ? NB * SB : SB;   // lanes that load an id
+};
+
+template <int H, int SB, bool COL>
+__device__ __forceinline__ int gat_drop_lane_bits(int l, i64 own, int oth, const DropArgs<float>& dr) {
+  using C = GatDropCfg<H, SB>;
+  const unsigned i = COL ? (unsigned)oth : (unsigned)own, j = COL ? (unsigned)own : (unsigned)oth;
+  if constexpr (C::SPREAD) {
+    return drop_keep4<float>(i, j, (unsigned)(l / SB), dr);
+  } else {
+    int bits = 0;
+#pragma unroll
+    for (int b = 0; b < C::NB; ++b) bits |= drop_keep4<float>(i, j, (unsigned)b, dr) << (4 * b);
+    return bits;
+  }
+}
+
+// keep bits of slot U's heads (bit k = head k), in every lane of the group
+template <int H, int SB, int U>
+__device__ __forceinline__ int gat_drop_slot_bits(int lane_bits) {
+  using C = GatDropCfg<H, SB>;
+  int bits = group_bcast<C::L, U>(lane_bits);
+  if constexpr (C::SPREAD && C::NB == 2) bits |= group_bcast<C::L, SB + U>(lane_bits) << 4;
+  return bits;
 }
 
 // y[eid[j], k] = m_ijk over the row-major chunks (i = row[c], j = indices[slot]); one wave per chunk, lanes over

@@ -50,41 +50,6 @@ __device__ __forceinline__ void gat_attn_merge(float& m, float& s, float m2, flo
   m = mn;
 }
 
-// ---- attention dropout in the gather passes (kernels_dropout.h has the decision) ---------------------------------
-// The lanes that load a batch's neighbour ids also run Philox for them: lane t < SB holds slot t.  One call covers four
-// heads; for H = 8 lane SB + t takes the second block of slot t where the group has room (2 * SB <= L), else lane t
-// makes both calls.  `own` is the chunk's node, `oth` the gathered one; COL says which of them is the row-major row i.
-template <int H, int SB>
-struct GatDropCfg {
-  static constexpr int L = 16;
-  static constexpr int NB = (H + 3) / 4;            // Philox blocks per slot
-  static constexpr bool SPREAD = NB * SB <= L;      // one block per lane
-  static constexpr int LANES = SPREAD ? NB * SB : SB;   // lanes that load an id
-};
-
-template <int H, int SB, bool COL>
-__device__ __forceinline__ int gat_drop_lane_bits(int l, i64 own, int oth, const DropArgs<float>& dr) {
-  using C = GatDropCfg<H, SB>;
-  const unsigned i = COL ? (unsigned)oth : (unsigned)own, j = COL ? (unsigned)own : (unsigned)oth;
-  if constexpr (C::SPREAD) {
-    return drop_keep4<float>(i, j, (unsigned)(l / SB), dr);
-  } else {
-    int bits = 0;
-#pragma unroll
-    for (int b = 0; b < C::NB; ++b) bits |= drop_keep4<float>(i, j, (unsigned)b, dr) << (4 * b);
-    return bits;
-  }
-}
-
-// keep bits of slot U's heads (bit k = head k), in every lane of the group
-template <int H, int SB, int U>
-__device__ __forceinline__ int gat_drop_slot_bits(int lane_bits) {
-  using C = GatDropCfg<H, SB>;
-  int bits = group_bcast<C::L, U>(lane_bits);
-  if constexpr (C::SPREAD && C::NB == 2) bits |= group_bcast<C::L, SB + U>(lane_bits) << 4;
-  return bits;
-}
-
 // ---- stats pass --------------------------------------------------------------------------------------------------
 // Blocks [0, nb_short): lane groups of G lanes, one row segment each (segments above long_len slots are skipped);
 // blocks nb_short + b: the whole workgroup on segment long_segs[b].  Every lane keeps an online (m, l) per head over

@@ -20,10 +20,16 @@
 // adjacent lanes and a per-head sum is a group_sum<DQ>.  Every lane of a head holds the head's score, so the softmax
 // state (m, l) is kept per piece.  The score is evaluated by the same expression in every pass: a recomputed s is
 // bitwise the forward's.
+// Attention dropout (DROP; kernels_dropout.h has the decision): o[i] = sum_j a_ij m_ij xr[j] with the statistics of the
+// undropped scores, da_ij = m_ij <dO_i, xr_j> and dxr[j] sums a_ij m_ij dO_i.  Each gather pass exists ONCE in source,
+// in kernels_gatv2_attn_passes.inc, and is compiled twice: as k_gv2attn_* (DROP = false) and as k_gv2drop_*.  The lanes
+// that load a batch's neighbour ids run Philox for their slot (gat_drop_lane_bits) and the keep
+// bits travel by group_bcast like the id: no pass reads eid or any other new stream.
 #pragma once
 #include "kernels_base.h"
 #include "kernels_gat.h"
 #include "kernels_generic.h"
+#include "kernels_dropout.h"
 
 namespace graphop {
 
@@ -67,128 +73,23 @@ __device__ __forceinline__ void gv2attn_fma4(float4& acc, float w, const float4&
   acc.x = fmaf(w, x.x, acc.x); acc.y = fmaf(w, x.y, acc.y); acc.z = fmaf(w, x.z, acc.z); acc.w = fmaf(w, x.w, acc.w);
 }
 
-// ---- forward -----------------------------------------------------------------------------------------------------
-// Blocks [0, nb_short): lane groups of 16, one row segment each (segments above long_len slots are skipped);
-// blocks nb_short + b: the whole workgroup on segment long_segs[b], its 16 groups taking batches strided and merging
-// their (m, l, acc) through LDS.  xl_i and the lane's pieces of att stay in registers; a batch's SB neighbour ids are
-// loaded by the first lanes and handed round by group_bcast; per batch the running maximum is raised once and
-// (l, acc) rescaled once.
-template <int H, int D>
-__global__ __launch_bounds__(kFastBlock) void k_gv2attn_fwd_f32(
-    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
-    const i64* __restrict__ seg_chunk, const float* __restrict__ xl, const float* __restrict__ xr,
-    const float* __restrict__ att, float* __restrict__ o, float2* __restrict__ stats, i64 n_seg, unsigned nb_short,
-    i64 long_len, const int* __restrict__ long_segs, float slope) {
-  using C = Gv2AttnCfg<H, D>;
-  constexpr int L = C::L, NV = C::NV, DQ = C::DQ, SB = C::SB_FWD;
-  constexpr i64 F4 = C::F4;
-  constexpr int NG = kFastBlock / L;   // lane groups of a workgroup
-  __shared__ float4 red_acc[NG][F4];
-  __shared__ float2 red_ml[NG][H];
-  const int l = threadIdx.x % L, g = threadIdx.x / L;
-  const bool longp = blockIdx.x >= nb_short;   // workgroup-uniform
-  const i64 s = longp ? (i64)long_segs[blockIdx.x - nb_short] : (i64)blockIdx.x * NG + g;
-  const bool have = s < n_seg;
-  i64 r = 0, j0 = 0, j1 = 0;
-  if (have) {
-    const i64 c0 = seg_chunk[s];
-    r = row[c0];
-    j0 = indptr[c0];
-    j1 = indptr[seg_chunk[s + 1]];
-  }
-  const bool work = have && (longp || j1 - j0 <= long_len);   // group-uniform
-  int kv[NV];
-  float4 w[NV], a[NV], acc[NV];
-  float m[NV], ls[NV];
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    kv[v] = (v * L + l) / DQ;
-    acc[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-    m[v] = kGv2AttnFloor;
-    ls[v] = 0.f;
-  }
-  if (work) {
-#pragma unroll
-    for (int v = 0; v < NV; ++v) {
-      w[v] = ld4(att, v * L + l);
-      a[v] = ld4(xl, r * F4 + v * L + l);
-    }
-    const i64 step = longp ? (i64)NG * SB : (i64)SB;
-    for (i64 jb = longp ? j0 + (i64)g * SB : j0; jb < j1; jb += step) {
-      const int nb = (j1 - jb) < SB ? (int)(j1 - jb) : SB;
-      int my_src = 0;   // slots past the end re-read the batch's last neighbour with weight 0
-      if (l < SB) my_src = (int)indices[jb + (l < nb ? l : nb - 1)];
-      float4 x[SB][NV];
-      static_for<SB>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        const i64 src = group_bcast<L, u>(my_src);
-#pragma unroll
-        for (int v = 0; v < NV; ++v) x[u][v] = ld4(xr, src * F4 + v * L + l);
-      });
-      float sc[SB][NV];
-#pragma unroll
-      for (int u = 0; u < SB; ++u)
-#pragma unroll
-        for (int v = 0; v < NV; ++v) sc[u][v] = group_sum<DQ>(gv2attn_dot4(w[v], a[v], x[u][v], slope));
-#pragma unroll
-      for (int v = 0; v < NV; ++v) {
-        float mn = m[v];
-#pragma unroll
-        for (int u = 0; u < SB; ++u) mn = u < nb ? fmaxf(mn, sc[u][v]) : mn;
-        const float f = exp_nonpos(m[v] - mn);
-        m[v] = mn;
-        ls[v] *= f;
-        gv2attn_scale4(acc[v], f);
-#pragma unroll
-        for (int u = 0; u < SB; ++u) {
-          const float p = u < nb ? exp_nonpos(sc[u][v] - mn) : 0.f;
-          ls[v] += p;
-          gv2attn_fma4(acc[v], p, x[u][v]);
-        }
-      }
-    }
-  }
-  if (!longp) {
-    if (work) {
-#pragma unroll
-      for (int v = 0; v < NV; ++v) {
-        const float il = ls[v] > 0.f ? 1.f / ls[v] : 0.f;
-        gv2attn_scale4(acc[v], il);
-        reinterpret_cast<float4*>(o)[r * F4 + v * L + l] = acc[v];
-        if (l % DQ == 0) stats[r * H + kv[v]] = make_float2(m[v], il);
-      }
-    }
-    return;
-  }
-  // long segment (workgroup-uniform branch): every group publishes (m, l) per head and acc per piece (16 KB + 1 KB of
-  // LDS at h * d = 256); thread p < F4 merges piece p
-  // over the groups in a fixed order
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    red_acc[g][v * L + l] = acc[v];
-    if (l % DQ == 0) red_ml[g][kv[v]] = make_float2(m[v], ls[v]);
-  }
-  __syncthreads();
-  if (have && threadIdx.x < F4) {
-    const int p = threadIdx.x, k = p / DQ;
-    float mm = kGv2AttnFloor;
-#pragma unroll
-    for (int q = 0; q < NG; ++q) mm = fmaxf(mm, red_ml[q][k].x);
-    float lsum = 0.f;
-    float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-    for (int q = 0; q < NG; ++q) {
-      const float2 ml = red_ml[q][k];
-      const float f = exp_nonpos(ml.x - mm);
-      lsum = fmaf(ml.y, f, lsum);
-      gv2attn_fma4(t, f, red_acc[q][p]);
-    }
-    const float il = lsum > 0.f ? 1.f / lsum : 0.f;
-    gv2attn_scale4(t, il);
-    reinterpret_cast<float4*>(o)[r * F4 + p] = t;
-    if (p % DQ == 0) stats[r * H + k] = make_float2(mm, il);
-  }
-}
+// ---- the gather passes: kernels_gatv2_attn_passes.inc, once without and once with dropout ------------------------------
+// the dropout argument of a pass: dependent on H so that the undropped text may name its members in discarded branches
+template <int H, bool DROP>
+struct Gv2DropArg {
+  using type = DropArgsIf<DROP, float>;
+};
+
+#define GV2_DROP false
+#define GV2_KERNEL(pass) k_gv2attn_##pass##_f32
+#include "kernels_gatv2_attn_passes.inc"
+#undef GV2_DROP
+#undef GV2_KERNEL
+#define GV2_DROP true
+#define GV2_KERNEL(pass) k_gv2drop_##pass##_f32
+#include "kernels_gatv2_attn_passes.inc"
+#undef GV2_DROP
+#undef GV2_KERNEL
 
 // ---- pack: P[i, k] = (m, 1 / l, <dO_i, o_i>, 0) ---------------------------------------------------------------------
 template <int H, int D>
@@ -210,224 +111,6 @@ __global__ __launch_bounds__(kFastBlock) void k_gv2attn_pack_f32(
       P[i * H + k] = make_float4(st.x, st.y, dsum, 0.f);
     }
   }
-}
-
-// ---- backward passes -------------------------------------------------------------------------------------------------
-// The chunk driver: a lane group takes chunks_per_group adjacent chunks and keeps the own node's rows in registers
-// while the node does not change; sums leave once per (lane group, node): stored where the group owns the node
-// (OWNED: sorted chunk list and the neighbouring groups' chunks name other nodes), added by float atomics otherwise.
-
-// row pass: own = xl_i, dO_i, P[i]; gathered = xr_j.  The row sum is kept as sum_j ds t and multiplied by att when the
-// row leaves.  The lane's pieces of datt are summed over the group's whole run, reduced over the workgroup (shuffles
-// inside a wave, LDS across waves) and written as row blockIdx.x of datt_part (gridDim.x, F4): every workgroup writes
-// its row, groups without chunks add zeros.
-template <int H, int D, bool OWNED>
-__global__ __launch_bounds__(kFastBlock) void k_gv2attn_bwd_row_f32(
-    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
-    const float* __restrict__ xl, const float* __restrict__ xr, const float* __restrict__ att,
-    const float4* __restrict__ P, const float* __restrict__ dO, float* __restrict__ dxl,
-    float4* __restrict__ datt_part, i64 n_chunks, int chunks_per_group, float slope) {
-  using C = Gv2AttnCfg<H, D>;
-  constexpr int L = C::L, NV = C::NV, DQ = C::DQ, SB = C::SB_ROW;
-  constexpr i64 F4 = C::F4;
-  const int l = threadIdx.x % L;
-  const i64 gid = (i64)blockIdx.x * (kFastBlock / L) + threadIdx.x / L;
-  const i64 c0 = gid * chunks_per_group;
-  i64 c1 = c0 + chunks_per_group;
-  if (c1 > n_chunks) c1 = n_chunks;
-  int kv[NV];
-  float4 w[NV], a[NV], g[NV], acc[NV], dw[NV];
-  float pm[NV], pil[NV], pd[NV];
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    kv[v] = (v * L + l) / DQ;
-    w[v] = ld4(att, v * L + l);
-    acc[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-    dw[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  if (c0 < c1) {   // group-uniform
-    i64 row_before = -1, row_after = -1;
-    if constexpr (OWNED) {
-      if (c0 > 0) row_before = row[c0 - 1];
-      if (c1 < n_chunks) row_after = row[c1];
-    }
-    auto flush = [&](i64 r) {
-#pragma unroll
-      for (int v = 0; v < NV; ++v) {
-        acc[v].x *= w[v].x; acc[v].y *= w[v].y; acc[v].z *= w[v].z; acc[v].w *= w[v].w;
-      }
-      if (OWNED && r != row_before && r != row_after) {
-#pragma unroll
-        for (int v = 0; v < NV; ++v) reinterpret_cast<float4*>(dxl)[r * F4 + v * L + l] = acc[v];
-      } else {
-        atomic_flush<L, NV>(dxl, r, acc, l);
-      }
-#pragma unroll
-      for (int v = 0; v < NV; ++v) acc[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-    };
-    i64 cur = -1;
-    bool dirty = false;
-    for (i64 c = c0; c < c1; ++c) {
-      const i64 r = row[c];
-      if (r != cur) {
-        if (dirty) { flush(cur); dirty = false; }
-        cur = r;
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-          a[v] = ld4(xl, r * F4 + v * L + l);
-          g[v] = ld4(dO, r * F4 + v * L + l);
-          const float4 p = P[r * H + kv[v]];
-          pm[v] = p.x; pil[v] = p.y; pd[v] = p.z;
-        }
-      }
-      const i64 j0 = indptr[c], j1 = indptr[c + 1];
-      if (j1 > j0) dirty = true;
-      for (i64 jb = j0; jb < j1; jb += SB) {
-        const int nb = (j1 - jb) < SB ? (int)(j1 - jb) : SB;
-        int my_src = 0;   // slots past the end re-read the batch's last neighbour with weight 0
-        if (l < SB) my_src = (int)indices[jb + (l < nb ? l : nb - 1)];
-        float4 x[SB][NV];
-        static_for<SB>([&](auto uc) {
-          constexpr int u = decltype(uc)::value;
-          const i64 src = group_bcast<L, u>(my_src);
-#pragma unroll
-          for (int v = 0; v < NV; ++v) x[u][v] = ld4(xr, src * F4 + v * L + l);
-        });
-#pragma unroll
-        for (int u = 0; u < SB; ++u) {
-#pragma unroll
-          for (int v = 0; v < NV; ++v) {
-            float s = gv2attn_dot4(w[v], a[v], x[u][v], slope), da = dot4(g[v], x[u][v]);
-            gv2attn_group_sum2<DQ>(s, da);
-            const float aij = u < nb ? exp_nonpos(s - pm[v]) * pil[v] : 0.f;
-            const float ds = aij * (da - pd[v]), dss = ds * slope;
-            const float zx = a[v].x + x[u][v].x, zy = a[v].y + x[u][v].y;
-            const float zz = a[v].z + x[u][v].z, zw = a[v].w + x[u][v].w;
-            acc[v].x += zx > 0.f ? ds : dss;
-            acc[v].y += zy > 0.f ? ds : dss;
-            acc[v].z += zz > 0.f ? ds : dss;
-            acc[v].w += zw > 0.f ? ds : dss;
-            dw[v].x = fmaf(ds, gv2attn_lrelu(zx, slope), dw[v].x);
-            dw[v].y = fmaf(ds, gv2attn_lrelu(zy, slope), dw[v].y);
-            dw[v].z = fmaf(ds, gv2attn_lrelu(zz, slope), dw[v].z);
-            dw[v].w = fmaf(ds, gv2attn_lrelu(zw, slope), dw[v].w);
-          }
-        }
-      }
-    }
-    if (dirty) flush(cur);
-  }
-  // every thread of the workgroup arrives here
-  static_assert(F4 <= kWave, "one thread per piece in the last step");
-  __shared__ float4 red[kFastBlock / kWave][F4];
-  const int lane = threadIdx.x & (kWave - 1), wv = threadIdx.x / kWave;
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    float4 t = dw[v];
-#pragma unroll
-    for (int o = L; o < kWave; o <<= 1) {
-      t.x += __shfl_xor(t.x, o); t.y += __shfl_xor(t.y, o);
-      t.z += __shfl_xor(t.z, o); t.w += __shfl_xor(t.w, o);
-    }
-    if (lane < L) red[wv][v * L + lane] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < F4) {
-    float4 t = red[0][threadIdx.x];
-#pragma unroll
-    for (int q = 1; q < kFastBlock / kWave; ++q) {
-      const float4 o = red[q][threadIdx.x];
-      t.x += o.x; t.y += o.y; t.z += o.z; t.w += o.w;
-    }
-    datt_part[(i64)blockIdx.x * F4 + threadIdx.x] = t;
-  }
-}
-
-// column pass: own = xr_j; gathered = xl_i, dO_i and P[i]; dxr[j] += sum_i (ds att t + a dO_i)
-template <int H, int D, bool OWNED>
-__global__ __launch_bounds__(kFastBlock) void k_gv2attn_bwd_col_f32(
-    const i64* __restrict__ col, const i64* __restrict__ indptr, const i64* __restrict__ indices,
-    const float* __restrict__ xl, const float* __restrict__ xr, const float* __restrict__ att,
-    const float4* __restrict__ P, const float* __restrict__ dO, float* __restrict__ dxr, i64 n_chunks,
-    int chunks_per_group, float slope) {
-  using C = Gv2AttnCfg<H, D>;
-  constexpr int L = C::L, NV = C::NV, DQ = C::DQ, SB = C::SB_COL;
-  constexpr i64 F4 = C::F4;
-  const int l = threadIdx.x % L;
-  const i64 gid = (i64)blockIdx.x * (kFastBlock / L) + threadIdx.x / L;
-  const i64 c0 = gid * chunks_per_group;
-  i64 c1 = c0 + chunks_per_group;
-  if (c1 > n_chunks) c1 = n_chunks;
-  if (c0 >= c1) return;
-  i64 col_before = -1, col_after = -1;
-  if constexpr (OWNED) {
-    if (c0 > 0) col_before = col[c0 - 1];
-    if (c1 < n_chunks) col_after = col[c1];
-  }
-  int kv[NV];
-  float4 w[NV], b[NV], acc[NV];
-#pragma unroll
-  for (int v = 0; v < NV; ++v) {
-    kv[v] = (v * L + l) / DQ;
-    w[v] = ld4(att, v * L + l);
-    acc[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-  auto flush = [&](i64 r) {
-    if (OWNED && r != col_before && r != col_after) {
-#pragma unroll
-      for (int v = 0; v < NV; ++v) reinterpret_cast<float4*>(dxr)[r * F4 + v * L + l] = acc[v];
-    } else {
-      atomic_flush<L, NV>(dxr, r, acc, l);
-    }
-#pragma unroll
-    for (int v = 0; v < NV; ++v) acc[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-  };
-  i64 cur = -1;
-  bool dirty = false;
-  for (i64 c = c0; c < c1; ++c) {
-    const i64 r = col[c];
-    if (r != cur) {
-      if (dirty) { flush(cur); dirty = false; }
-      cur = r;
-#pragma unroll
-      for (int v = 0; v < NV; ++v) b[v] = ld4(xr, r * F4 + v * L + l);
-    }
-    const i64 j0 = indptr[c], j1 = indptr[c + 1];
-    if (j1 > j0) dirty = true;
-    for (i64 jb = j0; jb < j1; jb += SB) {
-      const int nb = (j1 - jb) < SB ? (int)(j1 - jb) : SB;
-      int my_src = 0;   // slots past the end re-read the batch's last neighbour with weight 0
-      if (l < SB) my_src = (int)indices[jb + (l < nb ? l : nb - 1)];
-      float4 x[SB][NV], y[SB][NV], p[SB][NV];   // xl_i, dO_i, P[i, k_v]
-      static_for<SB>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        const i64 src = group_bcast<L, u>(my_src);
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-          x[u][v] = ld4(xl, src * F4 + v * L + l);
-          y[u][v] = ld4(dO, src * F4 + v * L + l);
-          p[u][v] = P[src * H + kv[v]];
-        }
-      });
-#pragma unroll
-      for (int u = 0; u < SB; ++u) {
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-          float s = gv2attn_dot4(w[v], x[u][v], b[v], slope), da = dot4(y[u][v], b[v]);
-          gv2attn_group_sum2<DQ>(s, da);
-          const float aij = u < nb ? exp_nonpos(s - p[u][v].x) * p[u][v].y : 0.f;
-          const float ds = aij * (da - p[u][v].z), dss = ds * slope;
-          const float zx = x[u][v].x + b[v].x, zy = x[u][v].y + b[v].y;
-          const float zz = x[u][v].z + b[v].z, zw = x[u][v].w + b[v].w;
-          acc[v].x = fmaf(zx > 0.f ? ds : dss, w[v].x, fmaf(aij, y[u][v].x, acc[v].x));
-          acc[v].y = fmaf(zy > 0.f ? ds : dss, w[v].y, fmaf(aij, y[u][v].y, acc[v].y));
-          acc[v].z = fmaf(zz > 0.f ? ds : dss, w[v].z, fmaf(aij, y[u][v].z, acc[v].z));
-          acc[v].w = fmaf(zw > 0.f ? ds : dss, w[v].w, fmaf(aij, y[u][v].w, acc[v].w));
-        }
-      }
-    }
-  }
-  if (dirty) flush(cur);
 }
 
 // datt[p] = sum over the n_part rows of the row pass's partials, piece p = blockIdx.x: each thread sums its rows in
@@ -513,12 +196,13 @@ __global__ void k_gv2attn_stats_fin_generic(T* __restrict__ stats, i64 n) {
   }
 }
 
-// lanes over the h * d elements of the row in steps of the wave; one atomic per (chunk, element)
-template <typename T>
+// lanes over the h * d elements of the row in steps of the wave; one atomic per (chunk, element).  DROP (here and in
+// the two backward kernels): one drop_mult per use.
+template <typename T, bool DROP>
 __global__ __launch_bounds__(kGenericBlock) void k_gv2attn_fwd_generic(
     const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
     const T* __restrict__ xl, const T* __restrict__ xr, const T* __restrict__ att, const T* __restrict__ stats,
-    T* __restrict__ o, i64 n_chunks, i64 h, i64 d, T slope) {
+    T* __restrict__ o, i64 n_chunks, i64 h, i64 d, T slope, DropArgsIf<DROP, T> dr) {
   const i64 c = generic_chunk_id();
   if (c >= n_chunks) return;
   const int lane = threadIdx.x & 63;
@@ -533,7 +217,9 @@ __global__ __launch_bounds__(kGenericBlock) void k_gv2attn_fwd_generic(
     for (i64 j = j0; j < j1; ++j) {
       const i64 src = indices[j];
       const T s = gv2attn_score<T>(xl + (r * h + k) * d, xr + (src * h + k) * d, att + k * d, d, slope);
-      acc += exp_t(s - m) * il * xr[src * f + it];
+      T w = exp_t(s - m) * il;
+      if constexpr (DROP) w *= drop_mult<T>(r, src, k, dr);
+      acc += w * xr[src * f + it];
     }
     atomicAdd(o + r * f + it, acc);
   }
@@ -552,24 +238,26 @@ __global__ void k_gv2attn_pack_generic(const T* __restrict__ stats, const T* __r
   }
 }
 
-// ds of one (slot, head): i = the row-major row (P[i, k] holds m, 1 / l, D), j = the column; *a_out = a_ij
+// ds of one (slot, head): i = the row-major row (P[i, k] holds m, 1 / l, D), j = the column; *a_out = a_ij; mult = the
+// slot's dropout multiplier m_ij (1 without dropout)
 template <typename T>
 __device__ __forceinline__ T gv2attn_ds(const T* __restrict__ xl_ik, const T* __restrict__ xr_jk,
                                         const T* __restrict__ att_k, const T* __restrict__ p,
-                                        const T* __restrict__ dO_ik, i64 d, T slope, T* a_out) {
+                                        const T* __restrict__ dO_ik, i64 d, T slope, T mult, T* a_out) {
   const T s = gv2attn_score<T>(xl_ik, xr_jk, att_k, d, slope);
   const T a = exp_t(s - p[0]) * p[1];
   T da = 0;
   for (i64 t = 0; t < d; ++t) da += dO_ik[t] * xr_jk[t];
   *a_out = a;
-  return a * (da - p[2]);
+  return a * (mult * da - p[2]);
 }
 
-template <typename T>
+template <typename T, bool DROP>
 __global__ __launch_bounds__(kGenericBlock) void k_gv2attn_bwd_row_generic(
     const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
     const T* __restrict__ xl, const T* __restrict__ xr, const T* __restrict__ att, const T* __restrict__ P,
-    const T* __restrict__ dO, T* __restrict__ dxl, T* __restrict__ datt, i64 n_chunks, i64 h, i64 d, T slope) {
+    const T* __restrict__ dO, T* __restrict__ dxl, T* __restrict__ datt, i64 n_chunks, i64 h, i64 d, T slope,
+    DropArgsIf<DROP, T> dr) {
   const i64 c = generic_chunk_id();
   if (c >= n_chunks) return;
   const int lane = threadIdx.x & 63;
@@ -583,8 +271,10 @@ __global__ __launch_bounds__(kGenericBlock) void k_gv2attn_bwd_row_generic(
     T acc = 0, dw = 0, aij;
     for (i64 j = j0; j < j1; ++j) {
       const i64 src = indices[j];
+      T mult = 1;
+      if constexpr (DROP) mult = drop_mult<T>(r, src, k, dr);
       const T ds = gv2attn_ds<T>(xl + (r * h + k) * d, xr + (src * h + k) * d, att + k * d, P + (r * h + k) * 4,
-                                 dO + (r * h + k) * d, d, slope, &aij);
+                                 dO + (r * h + k) * d, d, slope, mult, &aij);
       const T z = a + xr[src * f + it];
       acc += gat_lrelu_grad(z, ds, slope);
       dw += ds * gat_lrelu(z, slope);
@@ -594,11 +284,11 @@ __global__ __launch_bounds__(kGenericBlock) void k_gv2attn_bwd_row_generic(
   }
 }
 
-template <typename T>
+template <typename T, bool DROP>
 __global__ __launch_bounds__(kGenericBlock) void k_gv2attn_bwd_col_generic(
     const i64* __restrict__ col, const i64* __restrict__ indptr, const i64* __restrict__ indices,
     const T* __restrict__ xl, const T* __restrict__ xr, const T* __restrict__ att, const T* __restrict__ P,
-    const T* __restrict__ dO, T* __restrict__ dxr, i64 n_chunks, i64 h, i64 d, T slope) {
+    const T* __restrict__ dO, T* __restrict__ dxr, i64 n_chunks, i64 h, i64 d, T slope, DropArgsIf<DROP, T> dr) {
   const i64 c = generic_chunk_id();
   if (c >= n_chunks) return;
   const int lane = threadIdx.x & 63;
@@ -612,8 +302,11 @@ __global__ __launch_bounds__(kGenericBlock) void k_gv2attn_bwd_col_generic(
     T acc = 0, aij;
     for (i64 j = j0; j < j1; ++j) {
       const i64 i = indices[j];
+      T mult = 1;
+      if constexpr (DROP) mult = drop_mult<T>(i, jc, k, dr);
       const T ds = gv2attn_ds<T>(xl + (i * h + k) * d, xr + (jc * h + k) * d, att + k * d, P + (i * h + k) * 4,
-                                 dO + (i * h + k) * d, d, slope, &aij);
+                                 dO + (i * h + k) * d, d, slope, mult, &aij);
+      if constexpr (DROP) aij *= mult;   // a_ij m_ij
       acc += gat_lrelu_grad(xl[i * f + it] + b, ds, slope) * w + aij * dO[i * f + it];
     }
     atomicAdd(dxr + jc * f + it, acc);

@@ -510,14 +510,30 @@ std::vector<at::Tensor> gatv2_scores_backward(const at::Tensor& row, const at::T
   return {dxl, dxr, datt};
 }
 
+// (p, seed, offset) of the dropout forms, checked as include/graphop_hip.h states them
+struct DropSpec {
+  double p;
+  uint64_t seed;
+  uint32_t offset;
+};
+
+DropSpec drop_spec(const char* fn, double p, int64_t seed, int64_t offset) {
+  TORCH_CHECK(p >= 0.0 && p < 1.0, fn, ": dropout probability p must be in [0, 1), got ", p);
+  TORCH_CHECK(seed >= 0, fn, ": seed must be in [0, 2^63), got ", seed);
+  TORCH_CHECK(offset >= 0 && offset < (int64_t(1) << 32), fn, ": offset must be in [0, 2^32), got ", offset);
+  return {p, (uint64_t)seed, (uint32_t)offset};
+}
+
 // ---- the fused GATv2 attention op (include/graphop_hip.h: graphop_gatv2_attention_*) ------------------------------
-std::vector<at::Tensor> gatv2_attention_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
-                                                const at::Tensor& indices, const at::Tensor& xl, const at::Tensor& xr,
-                                                const at::Tensor& att, double negative_slope) {
+// drop == nullptr: graphop_gatv2_attention_forward, else its dropout form
+std::vector<at::Tensor> gatv2_attention_forward_impl(const char* fn, const at::Tensor& row, const at::Tensor& indptr,
+                                                     const at::Tensor& eid, const at::Tensor& indices,
+                                                     const at::Tensor& xl, const at::Tensor& xr, const at::Tensor& att,
+                                                     double negative_slope, const DropSpec* drop) {
   CHECK_INPUT(row); CHECK_INPUT(indptr); CHECK_INPUT(eid); CHECK_INPUT(indices); CHECK_INPUT(xl); CHECK_INPUT(xr);
   CHECK_INPUT(att);
   CHECK_INDEX(row); CHECK_INDEX(indptr); CHECK_INDEX(eid); CHECK_INDEX(indices);
-  const auto hd = gatv2_shapes(xl, xr, att, "gatv2_attention_forward");
+  const auto hd = gatv2_shapes(xl, xr, att, fn);
   const int64_t h = hd.first, d = hd.second;
   DeviceGuard dg(xl);
   const int64_t e = eid.size(0), n_l = xl.size(0);
@@ -525,20 +541,43 @@ std::vector<at::Tensor> gatv2_attention_forward(const at::Tensor& row, const at:
   auto stats = at::empty({n_l, h, 2}, xl.options());
   const auto pp = get_plan(row, indptr, eid, indices, xr.size(0));
   const auto& p = *pp;
-  check(graphop_gatv2_attention_forward(dtype_code(xl), ip(row), ip(indptr), ip(eid), ip(indices), vp(xl), vp(xr),
-                                        vp(att), vp(o), vp(stats), row.size(0), e, n_l, xr.size(0), h, d,
-                                        negative_slope, p.plan, stream_of(xl)));
+  if (drop)
+    check(graphop_gatv2_attention_dropout_forward(dtype_code(xl), ip(row), ip(indptr), ip(eid), ip(indices), vp(xl),
+                                                  vp(xr), vp(att), vp(o), vp(stats), row.size(0), e, n_l, xr.size(0), h,
+                                                  d, negative_slope, drop->p, drop->seed, drop->offset, p.plan,
+                                                  stream_of(xl)));
+  else
+    check(graphop_gatv2_attention_forward(dtype_code(xl), ip(row), ip(indptr), ip(eid), ip(indices), vp(xl), vp(xr),
+                                          vp(att), vp(o), vp(stats), row.size(0), e, n_l, xr.size(0), h, d,
+                                          negative_slope, p.plan, stream_of(xl)));
   return {o, stats};
 }
 
-std::vector<at::Tensor> gatv2_attention_backward(const at::Tensor& row, const at::Tensor& indptr_r,
-                                                 const at::Tensor& eid_r, const at::Tensor& indices_r,
-                                                 const at::Tensor& col, const at::Tensor& indptr_c,
-                                                 const at::Tensor& eid_c, const at::Tensor& indices_c,
-                                                 const at::Tensor& xl, const at::Tensor& xr, const at::Tensor& att,
-                                                 const at::Tensor& o, const at::Tensor& stats, const at::Tensor& dO_,
-                                                 double negative_slope) {
-  const char* fn = "gatv2_attention_backward";
+std::vector<at::Tensor> gatv2_attention_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
+                                                const at::Tensor& indices, const at::Tensor& xl, const at::Tensor& xr,
+                                                const at::Tensor& att, double negative_slope) {
+  return gatv2_attention_forward_impl("gatv2_attention_forward", row, indptr, eid, indices, xl, xr, att, negative_slope,
+                                      nullptr);
+}
+
+std::vector<at::Tensor> gatv2_attention_dropout_forward(const at::Tensor& row, const at::Tensor& indptr,
+                                                        const at::Tensor& eid, const at::Tensor& indices,
+                                                        const at::Tensor& xl, const at::Tensor& xr,
+                                                        const at::Tensor& att, double negative_slope, double p,
+                                                        int64_t seed, int64_t offset) {
+  const char* fn = "gatv2_attention_dropout_forward";
+  const DropSpec drop = drop_spec(fn, p, seed, offset);
+  return gatv2_attention_forward_impl(fn, row, indptr, eid, indices, xl, xr, att, negative_slope, &drop);
+}
+
+std::vector<at::Tensor> gatv2_attention_backward_impl(const char* fn, const at::Tensor& row,
+                                                      const at::Tensor& indptr_r, const at::Tensor& eid_r,
+                                                      const at::Tensor& indices_r, const at::Tensor& col,
+                                                      const at::Tensor& indptr_c, const at::Tensor& eid_c,
+                                                      const at::Tensor& indices_c, const at::Tensor& xl,
+                                                      const at::Tensor& xr, const at::Tensor& att, const at::Tensor& o,
+                                                      const at::Tensor& stats, const at::Tensor& dO_,
+                                                      double negative_slope, const DropSpec* drop) {
   CHECK_INPUT(row); CHECK_INPUT(indptr_r); CHECK_INPUT(eid_r); CHECK_INPUT(indices_r);
   CHECK_INPUT(col); CHECK_INPUT(indptr_c); CHECK_INPUT(eid_c); CHECK_INPUT(indices_c); CHECK_INPUT(xl); CHECK_INPUT(xr);
   CHECK_INPUT(att); CHECK_INPUT(o); CHECK_INPUT(stats);
@@ -562,12 +601,45 @@ std::vector<at::Tensor> gatv2_attention_backward(const at::Tensor& row, const at
   const auto ppr = get_plan(row, indptr_r, eid_r, indices_r, xr.size(0));
   const auto ppc = get_plan(col, indptr_c, eid_c, indices_c, n_l);
   const auto &pr = *ppr, &pc = *ppc;
-  check(graphop_gatv2_attention_backward(dtype_code(xl), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col),
-                                         ip(indptr_c), ip(eid_c), ip(indices_c), vp(xl), vp(xr), vp(att), vp(o),
-                                         vp(stats), vp(dO), vp(dxl), vp(dxr), vp(datt), vp(ws),
-                                         ws.numel() * ws.element_size(), row.size(0), col.size(0), e, n_l, xr.size(0),
-                                         h, d, negative_slope, pr.plan, pc.plan, stream_of(xl)));
+  if (drop)
+    check(graphop_gatv2_attention_dropout_backward(
+        dtype_code(xl), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c),
+        ip(indices_c), vp(xl), vp(xr), vp(att), vp(o), vp(stats), vp(dO), vp(dxl), vp(dxr), vp(datt), vp(ws),
+        ws.numel() * ws.element_size(), row.size(0), col.size(0), e, n_l, xr.size(0), h, d, negative_slope, drop->p,
+        drop->seed, drop->offset, pr.plan, pc.plan, stream_of(xl)));
+  else
+    check(graphop_gatv2_attention_backward(dtype_code(xl), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col),
+                                           ip(indptr_c), ip(eid_c), ip(indices_c), vp(xl), vp(xr), vp(att), vp(o),
+                                           vp(stats), vp(dO), vp(dxl), vp(dxr), vp(datt), vp(ws),
+                                           ws.numel() * ws.element_size(), row.size(0), col.size(0), e, n_l,
+                                           xr.size(0), h, d, negative_slope, pr.plan, pc.plan, stream_of(xl)));
   return {dxl, dxr, datt};
+}
+
+std::vector<at::Tensor> gatv2_attention_backward(const at::Tensor& row, const at::Tensor& indptr_r,
+                                                 const at::Tensor& eid_r, const at::Tensor& indices_r,
+                                                 const at::Tensor& col, const at::Tensor& indptr_c,
+                                                 const at::Tensor& eid_c, const at::Tensor& indices_c,
+                                                 const at::Tensor& xl, const at::Tensor& xr, const at::Tensor& att,
+                                                 const at::Tensor& o, const at::Tensor& stats, const at::Tensor& dO,
+                                                 double negative_slope) {
+  return gatv2_attention_backward_impl("gatv2_attention_backward", row, indptr_r, eid_r, indices_r, col, indptr_c,
+                                       eid_c, indices_c, xl, xr, att, o, stats, dO, negative_slope, nullptr);
+}
+
+std::vector<at::Tensor> gatv2_attention_dropout_backward(const at::Tensor& row, const at::Tensor& indptr_r,
+                                                         const at::Tensor& eid_r, const at::Tensor& indices_r,
+                                                         const at::Tensor& col, const at::Tensor& indptr_c,
+                                                         const at::Tensor& eid_c, const at::Tensor& indices_c,
+                                                         const at::Tensor& xl, const at::Tensor& xr,
+                                                         const at::Tensor& att, const at::Tensor& o,
+                                                         const at::Tensor& stats, const at::Tensor& dO,
+                                                         double negative_slope, double p, int64_t seed,
+                                                         int64_t offset) {
+  const char* fn = "gatv2_attention_dropout_backward";
+  const DropSpec drop = drop_spec(fn, p, seed, offset);
+  return gatv2_attention_backward_impl(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr,
+                                       att, o, stats, dO, negative_slope, &drop);
 }
 
 // ---- the fused GAT attention op (include/graphop_hip.h: graphop_gat_attention_*) -----------------------------------
@@ -579,20 +651,6 @@ std::pair<int64_t, int64_t> gat_attn_shapes(const at::Tensor& el, const at::Tens
               ": V must be (n_dst, d) for 1-D el / er, else (n_dst, h, d) with the same h and n_dst as er, got V ",
               V.sizes(), ", er ", er.sizes());
   return {h, V.size(-1)};
-}
-
-// (p, seed, offset) of the dropout forms, checked as include/graphop_hip.h states them
-struct DropSpec {
-  double p;
-  uint64_t seed;
-  uint32_t offset;
-};
-
-DropSpec drop_spec(const char* fn, double p, int64_t seed, int64_t offset) {
-  TORCH_CHECK(p >= 0.0 && p < 1.0, fn, ": dropout probability p must be in [0, 1), got ", p);
-  TORCH_CHECK(seed >= 0, fn, ": seed must be in [0, 2^63), got ", seed);
-  TORCH_CHECK(offset >= 0 && offset < (int64_t(1) << 32), fn, ": offset must be in [0, 2^32), got ", offset);
-  return {p, (uint64_t)seed, (uint32_t)offset};
 }
 
 // drop == nullptr: graphop_gat_attention_forward, else its dropout form
@@ -815,6 +873,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("row"), py::arg("indptr_r"), py::arg("eid_r"), py::arg("indices_r"), py::arg("col"), py::arg("indptr_c"),
         py::arg("eid_c"), py::arg("indices_c"), py::arg("xl"), py::arg("xr"), py::arg("att"), py::arg("o"),
         py::arg("stats"), py::arg("dO"), py::arg("negative_slope") = 0.2);
+  m.def("gatv2_attention_dropout_forward", &gatv2_attention_dropout_forward,
+        "Fused GATv2 attention forward with attention dropout (extra op)", py::arg("row"), py::arg("indptr"),
+        py::arg("eid"), py::arg("indices"), py::arg("xl"), py::arg("xr"), py::arg("att"),
+        py::arg("negative_slope") = 0.2, py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0);
+  m.def("gatv2_attention_dropout_backward", &gatv2_attention_dropout_backward,
+        "Fused GATv2 attention backward with attention dropout (extra op)", py::arg("row"), py::arg("indptr_r"),
+        py::arg("eid_r"), py::arg("indices_r"), py::arg("col"), py::arg("indptr_c"), py::arg("eid_c"),
+        py::arg("indices_c"), py::arg("xl"), py::arg("xr"), py::arg("att"), py::arg("o"), py::arg("stats"),
+        py::arg("dO"), py::arg("negative_slope") = 0.2, py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0);
   m.def("clear_plan_cache", &clear_plan_cache, "Destroy every cached per-graph plan");
   m.def("release_plans", &release_plans, "Drop the cached plans of the orientation whose chunk list is `row`");
   m.def("plan_cache_size", &plan_cache_size, "Graph orientations in the plan cache");
@@ -843,6 +910,8 @@ TORCH_LIBRARY(graphop, m) {
   m.def("gatv2_scores_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor dy, float negative_slope=0.2) -> Tensor[]");
   m.def("gatv2_attention_forward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor xl, Tensor xr, Tensor att, float negative_slope=0.2) -> Tensor[]");
   m.def("gatv2_attention_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2) -> Tensor[]");
+  m.def("gatv2_attention_dropout_forward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor xl, Tensor xr, Tensor att, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]");
+  m.def("gatv2_attention_dropout_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]");
 }
 
 TORCH_LIBRARY_IMPL(graphop, CUDA, m) {
@@ -867,6 +936,8 @@ TORCH_LIBRARY_IMPL(graphop, CUDA, m) {
   m.impl("gatv2_scores_backward", &gatv2_scores_backward);
   m.impl("gatv2_attention_forward", &gatv2_attention_forward);
   m.impl("gatv2_attention_backward", &gatv2_attention_backward);
+  m.impl("gatv2_attention_dropout_forward", &gatv2_attention_dropout_forward);
+  m.impl("gatv2_attention_dropout_backward", &gatv2_attention_dropout_backward);
 }
 
 TORCH_LIBRARY_IMPL(graphop, CPU, m) {   // there is no CPU implementation: the reference's CHECK_CUDA message
@@ -891,4 +962,6 @@ TORCH_LIBRARY_IMPL(graphop, CPU, m) {   // there is no CPU implementation: the r
   m.impl("gatv2_scores_backward", &gatv2_scores_backward);
   m.impl("gatv2_attention_forward", &gatv2_attention_forward);
   m.impl("gatv2_attention_backward", &gatv2_attention_backward);
+  m.impl("gatv2_attention_dropout_forward", &gatv2_attention_dropout_forward);
+  m.impl("gatv2_attention_dropout_backward", &gatv2_attention_dropout_backward);
 }

@@ -182,6 +182,31 @@ class FusedGATAttentionDropout(Function):
         return None, None, None, None, None, None, None, None, d_el, d_er, dV, None, None, None, None
 
 
+class FusedGATv2AttentionDropout(Function):
+    """FusedGATv2Attention with dropout on the attention weights, o[i] = sum_j a_ij m_ij xr[j] (extra op):
+    apply(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, negative_slope, p, seed, offset).
+    m_ij is the multiplier of FusedGATAttentionDropout (i indexes xl, j indexes xr; graphop.edge_dropout_mask gives the
+    same values as an edge tensor), recomputed per slot by forward and backward, so still no (E, h) tensor is kept or
+    made; saves exactly what FusedGATv2Attention saves.  seed=None draws one from torch's default CPU generator
+    (torch.manual_seed makes runs repeatable); offset is a per-layer / per-step counter."""
+
+    @staticmethod
+    def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, negative_slope, p,
+                seed=None, offset=0):
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        ctx.drop = (float(negative_slope), float(p), int(seed), int(offset))
+        o, stats = _ops.gatv2_attention_dropout_forward(row, indptr_r, eid_r, indices_r, xl, xr, att, *ctx.drop)
+        ctx.save_for_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, o, stats)
+        return o
+
+    @staticmethod
+    def backward(ctx, dO):
+        a8, (xl, xr, att, o, stats) = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
+        dxl, dxr, datt = _ops.gatv2_attention_dropout_backward(*a8, xl, xr, att, o, stats, dO, *ctx.drop)
+        return None, None, None, None, None, None, None, None, dxl, dxr, datt, None, None, None, None
+
+
 # FusedAttention over several heads (round 5): "keep" = per head group only a_g (E x hg) survives the forward, the backward's
 # da_g / ds_g are E x hg temporaries -- speed of the 8-function step, about half of its E-sized memory; "recompute" = nothing
 # E-sized survives the forward, the backward recomputes s_g and a_g per group (two more passes per group: ~+17 % time,
@@ -411,6 +436,30 @@ def fused_gat_attention_dropout_step(g, el, er, V, dO, p, seed, offset=0, negati
     """The counterpart of gat_attention_dropout_step through FusedGATAttentionDropout; returns o (no E-sized tensor is
     kept or made, the mask included)."""
     o = FusedGATAttentionDropout.apply(*g.csr_args(), el, er, V, negative_slope, p, seed, offset)
+    o.backward(dO)
+    _lib.check_errors(sync=False)     # as in attention_step
+    return o
+
+
+def gatv2_attention_dropout_step(g, xl, xr, att, dO, p, seed, offset=0, negative_slope=0.2):
+    """gatv2_attention_step(V=None) with dropout on the attention weights, composed: GATv2Scores -> SparseSoftmax ->
+    (* edge_dropout_mask) -> VectorSPMM(., xr); the mask is one more (E, h) tensor kept for the backward.  Same decisions
+    as fused_gatv2_attention_dropout_step for the same (p, seed, offset); returns (s, a, o) with a the undropped weights."""
+    args = g.csr_args()
+    s = GATv2Scores.apply(*args, xl, xr, att, negative_slope)
+    a = SparseSoftmax.apply(g.row, g.ptr_r, g.eid_r, s)
+    h = 1 if xl.dim() == 2 else xl.size(1)
+    mask = _ops.edge_dropout_mask(g.row, g.ptr_r, g.eid_r, g.indices_r, h, p, seed, offset, a.dtype)
+    o = VectorSPMM.apply(*args, a * mask, xr)
+    o.backward(dO)
+    _lib.check_errors(sync=False)     # as in attention_step
+    return s, a, o
+
+
+def fused_gatv2_attention_dropout_step(g, xl, xr, att, dO, p, seed, offset=0, negative_slope=0.2):
+    """The counterpart of gatv2_attention_dropout_step through FusedGATv2AttentionDropout; returns o (no E-sized tensor
+    is kept or made, the mask included)."""
+    o = FusedGATv2AttentionDropout.apply(*g.csr_args(), xl, xr, att, negative_slope, p, seed, offset)
     o.backward(dO)
     _lib.check_errors(sync=False)     # as in attention_step
     return o

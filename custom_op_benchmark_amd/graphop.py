@@ -35,7 +35,7 @@ EXTRA_OPS = ["attention_forward", "attention_backward", "attention_backward_is_f
              "gat_scores_backward", "gat_attention_forward", "gat_attention_backward",
              "gat_attention_dropout_forward", "gat_attention_dropout_backward", "edge_dropout_mask",
              "gatv2_scores_forward", "gatv2_scores_backward", "gatv2_attention_forward",
-             "gatv2_attention_backward"]
+             "gatv2_attention_backward", "gatv2_attention_dropout_forward", "gatv2_attention_dropout_backward"]
 
 _NULL = None
 
@@ -469,31 +469,29 @@ def _gatv2_attention_workspace_values(n_l, n_row_chunks, h, d):
     return n_l * h * 4 + min((n_row_chunks + 15) // 16, 8192) * h * d
 
 
-def gatv2_attention_forward(row, indptr, eid, indices, xl, xr, att, negative_slope=0.2):
-    """-> [o, stats]: o[i] = sum_j softmax_j(att . LeakyReLU(xl[i] + xr[j])) xr[j] per head over the row-major CSR,
-    without any E-sized tensor; o has n_src = xl.size(0) rows in xl's layout, stats (n_src, h, 2) = (row max, 1 / sum exp)."""
+def _gatv2_attention_forward(fn, row, indptr, eid, indices, xl, xr, att, negative_slope, drop=()):
+    """gatv2_attention_forward (drop = ()) or gatv2_attention_dropout_forward (drop = (p, seed, offset)) as `fn`."""
     for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices"), (xl, "xl"), (xr, "xr"),
                  (att, "att")):
         _check_input(t, n)
     for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices")):
         _check_index(t, n)
-    h, d = _gatv2_shapes(xl, xr, att, "gatv2_attention_forward")
+    h, d = _gatv2_shapes(xl, xr, att, fn)
     e, n_l = eid.size(0), xl.size(0)
     o = torch.empty_like(xl)
     stats = torch.empty((n_l, h, 2), dtype=xl.dtype, device=xl.device)
     with _lib.device_guard(xl.device):
         plan = _plan(row, indptr, eid, indices, xr.size(0))
-        check(lib().graphop_gatv2_attention_forward(
+        check(getattr(lib(), "graphop_" + fn)(
             dtype_code(xl), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(xl), ptr(xr), ptr(att), ptr(o),
-            ptr(stats), row.size(0), e, n_l, xr.size(0), h, d, float(negative_slope), plan.handle, stream_of(xl)))
+            ptr(stats), row.size(0), e, n_l, xr.size(0), h, d, float(negative_slope), *drop, plan.handle,
+            stream_of(xl)))
     return [o, stats]
 
 
-def gatv2_attention_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, o, stats,
-                             dO, negative_slope=0.2):
-    """-> [dxl, dxr, datt] of gatv2_attention_forward for the output gradient dO (z, s and a recomputed per slot from
-    xl, xr, att and stats)."""
-    fn = "gatv2_attention_backward"
+def _gatv2_attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, o,
+                              stats, dO, negative_slope, drop=()):
+    """gatv2_attention_backward (drop = ()) or gatv2_attention_dropout_backward (drop = (p, seed, offset)) as `fn`."""
     names = ("row", "indptr_r", "eid_r", "indices_r", "col", "indptr_c", "eid_c", "indices_c")
     idx = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
     for t, n in zip(idx + (xl, xr, att, o, stats), names + ("xl", "xr", "att", "o", "stats")):
@@ -519,12 +517,26 @@ def gatv2_attention_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid
     with _lib.device_guard(xl.device):
         plan_r = _plan(row, indptr_r, eid_r, indices_r, xr.size(0))
         plan_c = _plan(col, indptr_c, eid_c, indices_c, n_l)
-        check(lib().graphop_gatv2_attention_backward(
+        check(getattr(lib(), "graphop_" + fn)(
             dtype_code(xl), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c),
             ptr(eid_c), ptr(indices_c), ptr(xl), ptr(xr), ptr(att), ptr(o), ptr(stats), ptr(dO), ptr(dxl), ptr(dxr),
             ptr(datt), ptr(ws), ws.numel() * ws.element_size(), row.size(0), col.size(0), e, n_l, xr.size(0), h, d,
-            float(negative_slope), plan_r.handle, plan_c.handle, stream_of(xl)))
+            float(negative_slope), *drop, plan_r.handle, plan_c.handle, stream_of(xl)))
     return [dxl, dxr, datt]
+
+
+def gatv2_attention_forward(row, indptr, eid, indices, xl, xr, att, negative_slope=0.2):
+    """-> [o, stats]: o[i] = sum_j softmax_j(att . LeakyReLU(xl[i] + xr[j])) xr[j] per head over the row-major CSR,
+    without any E-sized tensor; o has n_src = xl.size(0) rows in xl's layout, stats (n_src, h, 2) = (row max, 1 / sum exp)."""
+    return _gatv2_attention_forward("gatv2_attention_forward", row, indptr, eid, indices, xl, xr, att, negative_slope)
+
+
+def gatv2_attention_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, o, stats,
+                             dO, negative_slope=0.2):
+    """-> [dxl, dxr, datt] of gatv2_attention_forward for the output gradient dO (z, s and a recomputed per slot from
+    xl, xr, att and stats)."""
+    return _gatv2_attention_backward("gatv2_attention_backward", row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
+                                     indices_c, xl, xr, att, o, stats, dO, negative_slope)
 
 
 # ---- fused GAT attention (extra op) -----------------------------------------------------------------------------
@@ -637,6 +649,25 @@ def gat_attention_dropout_backward(row, indptr_r, eid_r, indices_r, col, indptr_
                                    stats, dO, negative_slope, _drop_args(fn, p, seed, offset))
 
 
+def gatv2_attention_dropout_forward(row, indptr, eid, indices, xl, xr, att, negative_slope=0.2, p=0.0, seed=0,
+                                    offset=0):
+    """-> [o, stats] of gatv2_attention_forward with dropout on the attention weights: o[i] = sum_j a_ij m_ij xr[j], m_ij
+    the multiplier of gat_attention_dropout_forward (i indexes xl, j indexes xr; no edge-sized mask); stats are those of
+    the undropped scores, bit for bit.  p = 0 is gatv2_attention_forward bit for bit."""
+    fn = "gatv2_attention_dropout_forward"
+    return _gatv2_attention_forward(fn, row, indptr, eid, indices, xl, xr, att, negative_slope,
+                                    _drop_args(fn, p, seed, offset))
+
+
+def gatv2_attention_dropout_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, o,
+                                     stats, dO, negative_slope=0.2, p=0.0, seed=0, offset=0):
+    """-> [dxl, dxr, datt] of gatv2_attention_dropout_forward for the output gradient dO, with the same (p, seed,
+    offset): scores, weights and their keep decisions are recomputed per slot."""
+    fn = "gatv2_attention_dropout_backward"
+    return _gatv2_attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att,
+                                     o, stats, dO, negative_slope, _drop_args(fn, p, seed, offset))
+
+
 def edge_dropout_mask(row, indptr, eid, indices, h, p, seed, offset=0, dtype=torch.float32):
     """-> the multipliers m[e, k] = keep(i, j, k) / (1 - p) the dropout ops above apply, as an edge tensor: (E) for
     h == 1, else (E, h).  (row, indptr, eid, indices) is the ROW-MAJOR CSR (i = row[c], j = indices[slot])."""
@@ -696,6 +727,8 @@ _SCHEMAS = {
     "gatv2_scores_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor dy, float negative_slope=0.2) -> Tensor[]",
     "gatv2_attention_forward": "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor xl, Tensor xr, Tensor att, float negative_slope=0.2) -> Tensor[]",
     "gatv2_attention_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2) -> Tensor[]",
+    "gatv2_attention_dropout_forward": "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor xl, Tensor xr, Tensor att, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]",
+    "gatv2_attention_dropout_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]",
 }
 _torch_lib = None
 

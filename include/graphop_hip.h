@@ -534,6 +534,39 @@ GRAPHOP_API int graphop_edge_dropout_mask(int dtype, const int64_t* row, const i
                                   int64_t n_r, int64_t h, double p, uint64_t seed, uint32_t offset,
                                   const graphop_plan_t* plan, void* stream);
 
+/* ---- attention dropout for the fused GATv2 layer (ABI 8, additive; EXTRA ops) -------------------------------------
+ * The fused GATv2 attention with dropout on the attention weights, attn_drop(edge_softmax(s)), still without any
+ * E-sized tensor.  The keep decision and the multiplier m_ijk are exactly those of the block above (Philox4x32-10 over
+ * (i, j, k >> 2, offset) keyed by the seed, T = floor(p * 2^32), 1 / (1 - p), both computed in double): i is the
+ * row-major row id (index into xl / o), j the neighbour id (index into xr), in that order in both orientations;
+ * parallel edges share one decision; graphop_edge_dropout_mask writes the same values out as an (E, h) tensor.
+ *   forward : o[i, k, :] = sum_n a_in m_in xr[n, k, :]; stats are those of the undropped scores, bit for bit what
+ *             graphop_gatv2_attention_forward leaves (the same expressions in the same order)
+ *   backward: D_i = <dO_i, o_i>, da_in = m_in <dO_i, xr_n>, ds_in = a_in (da_in - D_i), t_inc as above,
+ *             dxl[i, k, c] = att[k, c] sum_n ds_in t_inc,  datt[k, c] = sum_in ds_in LeakyReLU(z_inc),
+ *             dxr[n, k, c] = sum_i (ds_in att[k, c] t_inc + a_in m_in dO[i, k, c])               (same workspace rule)
+ *   A row whose slots are all dropped for a head has o = 0, D = 0 and dxl = 0 there and adds nothing to dxr or datt.
+ * Arguments as graphop_gatv2_attention_forward / _backward with (p, seed, offset) after negative_slope:
+ *   0 <= p < 1, seed < 2^63, offset a per-layer / per-step counter (one seed serves a whole model), n_l, n_r < 2^32;
+ *   anything else is GRAPHOP_ERR_INVALID_ARGUMENT before the device is touched.  p == 0 runs the kernels of
+ *   graphop_gatv2_attention_forward / _backward (bit-identical results, the same profile tags).
+ * Fast and generic kernels are chosen as without dropout (csrc/kernels_gatv2_attn.h: k_gv2drop_*_f32 and the
+ * DROP = true generic ones); the fast forward still uses no atomics, so o and stats stay reproducible bit for bit. */
+GRAPHOP_API int graphop_gatv2_attention_dropout_forward(int dtype, const int64_t* row, const int64_t* indptr,
+                                    const int64_t* eid, const int64_t* indices, const void* xl, const void* xr,
+                                    const void* att, void* o, void* stats, int64_t n_chunks, int64_t n_edges,
+                                    int64_t n_l, int64_t n_r, int64_t h, int64_t d, double negative_slope, double p,
+                                    uint64_t seed, uint32_t offset, const graphop_plan_t* plan, void* stream);
+GRAPHOP_API int graphop_gatv2_attention_dropout_backward(int dtype, const int64_t* row, const int64_t* indptr_r,
+                                     const int64_t* eid_r, const int64_t* indices_r, const int64_t* col,
+                                     const int64_t* indptr_c, const int64_t* eid_c, const int64_t* indices_c,
+                                     const void* xl, const void* xr, const void* att, const void* o, const void* stats,
+                                     const void* dO, void* dxl, void* dxr, void* datt, void* workspace,
+                                     int64_t workspace_bytes, int64_t n_row_chunks, int64_t n_col_chunks,
+                                     int64_t n_edges, int64_t n_l, int64_t n_r, int64_t h, int64_t d,
+                                     double negative_slope, double p, uint64_t seed, uint32_t offset,
+                                     const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream);
+
 /* ---- fused attention step (EXTRA op, not one of the reference's eight) --------------------------
  * The composition the reference harness chains by hand -- MaskedMMCSR -> SparseSoftmax -> VectorSPMM
  * (wrapper.py:20-30, 8-18, 44-55) -- as one forward and one backward entry, so that the E-sized

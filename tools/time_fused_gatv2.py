@@ -12,7 +12,15 @@ rounds read the library's per-launch times: the fused kernels, and the yardstick
 step) and k_gat_attn_bwd_row_f32 (from the fused GAT v1 step) at the same (h, d).  Per gather pass the record names the
 algorithmic bytes (ids 8 E + 16 C, node tables once) and the gathered row bytes (E * h * d * 4 per row gather: one in
 the forward and the row pass, two in the column pass) with the fraction of 8 TB/s each reaches.
-One JSON record per (h, d), printed and collected in --out (default profiles/fused_gatv2_bench.json)."""
+One JSON record per (h, d), printed and collected in --out (default profiles/fused_gatv2_bench.json).
+
+--dropout P times the steps with attention dropout instead: the fused dropout step
+(functions.fused_gatv2_attention_dropout_step) against the fused step without dropout, the yardstick, and against the
+composed dropout step (functions.gatv2_attention_dropout_step, which builds and keeps an (E, h) mask), all three
+alternating in one process; the comparison is fused dropout against composed dropout, the memory condition asks the
+composed step for more than three (E, h) tensors, and the per-kernel rounds are those of the dropout kernels and of the
+undropped fused kernels (the yardstick kernels of the other ops are left out).  --out then defaults to
+profiles/fused_gatv2_dropout_bench.json."""
 import argparse
 import json
 import os
@@ -71,8 +79,13 @@ def main():
     ap.add_argument("--iters", type=int, default=10)
     ap.add_argument("--chunk-size", type=int, default=32)
     ap.add_argument("--seed", type=int, default=0)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "fused_gatv2_bench.json"))
+    ap.add_argument("--dropout", type=float, default=0.0, metavar="P", help="time the attention-dropout steps at p = P")
+    ap.add_argument("--dropout-seed", type=int, default=1234567890123)
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "fused_gatv2_dropout_bench.json" if args.dropout > 0
+                                else "fused_gatv2_bench.json")
     dev = torch.device("cuda:0")
     N, E = graphs.SHAPES[args.shape]
     g = graphs.chung_lu_graph(N, E, alpha=0.5, seed=args.seed, chunk_size=args.chunk_size, device=dev)
@@ -99,6 +112,20 @@ def main():
                 x.grad = None
             return functions.gatv2_attention_step(g, xl, xr, att, dO, s)
 
+        nodrop = None
+        if args.dropout > 0:      # the dropout forms take the places of the two steps; the undropped fused step stays
+            nodrop, drop = fused, (args.dropout, args.dropout_seed, 7)
+
+            def fused():
+                for x in leaves:
+                    x.grad = None
+                return functions.fused_gatv2_attention_dropout_step(g, xl, xr, att, dO, *drop, s)
+
+            def composed():
+                for x in leaves:
+                    x.grad = None
+                return functions.gatv2_attention_dropout_step(g, xl, xr, att, dO, *drop, s)
+
         # full-size comparison (also builds and caches the plans both steps use)
         o_c = composed()[2].detach()
         want = [o_c] + [x.grad.clone() for x in leaves]
@@ -111,7 +138,7 @@ def main():
 
         # peak memory each step adds to what is allocated before it
         peak = {}
-        for name, fn in (("fused", fused), ("composed", composed)):
+        for name, fn in (("fused", fused), ("composed", composed)) + ((("fused_no_dropout", nodrop),) if nodrop else ()):
             for x in leaves:
                 x.grad = None
             torch.cuda.synchronize()
@@ -124,24 +151,29 @@ def main():
             del out
         edge_tensor = E * h * 4
         assert peak["fused"] < edge_tensor, (peak, edge_tensor)
-        assert peak["composed"] > 2 * edge_tensor, (peak, edge_tensor)
+        assert peak["composed"] > (3 if nodrop else 2) * edge_tensor, (peak, edge_tensor)
 
-        t = _timed({"fused_fwd_bwd": fused, "composed_fwd_bwd": composed}, args.warmup, args.iters)
+        fns = {"fused_fwd_bwd": fused, "composed_fwd_bwd": composed}
+        if nodrop:
+            fns["fused_no_dropout_fwd_bwd"] = nodrop
+        t = _timed(fns, args.warmup, args.iters)
         timings = {n: {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4)} for n, v in t.items()}
 
         # per-kernel times from the library's launch profile, in rounds of their own
         prof = _profile(fused, args.iters)
-        prof_c = _profile(composed, args.iters)
-        el = torch.randn((n_src,) if h == 1 else (n_src, h), generator=gen, device=dev).requires_grad_(True)
-        er = torch.randn((n_dst,) if h == 1 else (n_dst, h), generator=gen, device=dev).requires_grad_(True)
-        V = xr.detach().clone().requires_grad_(True)
+        prof_c = prof_v1 = {}
+        if not nodrop:      # the yardstick kernels of the other ops belong to the undropped record
+            prof_c = _profile(composed, args.iters)
+            el = torch.randn((n_src,) if h == 1 else (n_src, h), generator=gen, device=dev).requires_grad_(True)
+            er = torch.randn((n_dst,) if h == 1 else (n_dst, h), generator=gen, device=dev).requires_grad_(True)
+            V = xr.detach().clone().requires_grad_(True)
 
-        def gat_v1():
-            for x in (el, er, V):
-                x.grad = None
-            return functions.fused_gat_attention_step(g, el, er, V, dO, s)
-        prof_v1 = _profile(gat_v1, args.iters)
-        del el, er, V
+            def gat_v1():
+                for x in (el, er, V):
+                    x.grad = None
+                return functions.fused_gat_attention_step(g, el, er, V, dO, s)
+            prof_v1 = _profile(gat_v1, args.iters)
+            del el, er, V
         nh_l = n_src * h * 4                                  # one per-(node, head) scalar table
         row_l, row_r = n_src * h * d * 4, n_dst * h * d * 4   # one node-row table
         ids_r, ids_c = E * 8 + 16 * C_r, E * 8 + 16 * C_c
@@ -153,8 +185,11 @@ def main():
             "gv2attn_bwd_col": (ids_c + row_r + 2 * row_l + 4 * nh_l + row_r, 2),
             "gv2attn_datt_fin": (0, 0),
         }
+        dtag = {"gv2attn_fwd": "gv2attn_drop_fwd", "gv2attn_bwd_row": "gv2attn_drop_bwd_row",
+                "gv2attn_bwd_col": "gv2attn_drop_bwd_col"} if nodrop else {}
         kernels = {}
         for tag, (nbytes, gathers) in model.items():
+            tag = dtag.get(tag, tag)      # the dropout forms read the same bytes
             p = prof[tag]
             sec = p["mean_ms"] * 1e-3
             kernels[tag] = {"kernel": p["kernel"], "calls": p["calls"], "mean_ms": round(p["mean_ms"], 4),
@@ -174,12 +209,20 @@ def main():
                 yard[tag] = {"kernel": p["kernel"], "mean_ms": round(p["mean_ms"], 4), "min_ms": round(p["min_ms"], 4),
                              "gathered_fraction_of_8TBs": round(gathered / (p["mean_ms"] * 1e-3) / PEAK, 3)}
         f, c = timings["fused_fwd_bwd"]["median_ms"], timings["composed_fwd_bwd"]["median_ms"]
+        extra = {"yardstick_kernels": yard}
+        if nodrop:
+            extra = {"dropout": {"p": drop[0], "seed": drop[1], "offset": drop[2]},
+                     "fused_dropout_over_fused_no_dropout":
+                         round(f / timings["fused_no_dropout_fwd_bwd"]["median_ms"], 3),
+                     "kernels_no_dropout": {tag: {"kernel": p["kernel"], "mean_ms": round(p["mean_ms"], 4),
+                                                  "min_ms": round(p["min_ms"], 4)}
+                                            for tag, p in _profile(nodrop, args.iters).items() if tag in model}}
         rec = {
             "tool": "tools/time_fused_gatv2.py", "shape": args.shape, "n_src": n_src, "n_dst": n_dst, "n_edges": E,
             "row_chunks": C_r, "col_chunks": C_c, "chunk_size": args.chunk_size, "h": h, "d": d, "negative_slope": s,
             "warmup": args.warmup, "iters": args.iters, "node_scaled_difference_vs_composed": err, "timings": timings,
             "fused_over_composed": round(f / c, 3), "peak_added_bytes": peak, "one_edge_tensor_bytes": edge_tensor,
-            "kernels": kernels, "yardstick_kernels": yard, "device": torch.cuda.get_device_name(dev)}
+            "kernels": kernels, **extra, "device": torch.cuda.get_device_name(dev)}
         print(json.dumps(rec), flush=True)
         records.append(rec)
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
