@@ -1,20 +1,41 @@
 #!/usr/bin/env python3
-"""Run the randomised parity battery of tests/test_hip_parity.py (shapes, heads, chunk sizes, both
-window orders, forced knobs) over many more seeds than the test suite does:
-    python tools/soak_fuzz.py [first_seed last_seed]      # default 40 340, needs an MI355X"""
+"""Run a randomised battery of the test suite over many more seeds than the suite does (needs an MI355X):
+    python tools/soak_fuzz.py [first_seed last_seed]          # tests/test_hip_parity.py::test_fuzz_shapes_and_paths
+                                                              # (shapes, heads, chunk sizes, both window orders, forced
+                                                              # knobs); default 40 340
+    python tools/soak_fuzz.py --gat [first_seed last_seed]    # tests/test_gat_fuzz.py::test_gat_family_fuzz (the GAT
+                                                              # family, tests/gat_fuzz.py); default 48 348
+A seed that fails its assertions is counted and the run goes on.  Anything else a seed raises (a HIP error, a fault
+reported by the library) stops the run at that seed with exit status 2: nothing more is started on a device that may
+have faulted.  Exit status 1: some seed failed its assertions."""
 import sys, os
 sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "tests"))
 import torch
-import test_hip_parity as T
+
+args = sys.argv[1:]
+gat = bool(args) and args[0] == "--gat"
+if gat:
+    args = args[1:]
+    import test_gat_fuzz as T
+    run, default = T.test_gat_family_fuzz, (48, 348)
+else:
+    import test_hip_parity as T
+    run, default = T.test_fuzz_shapes_and_paths, (40, 340)
 dev = torch.device("cuda:0")
 bad = 0
-lo, hi = (int(sys.argv[1]), int(sys.argv[2])) if len(sys.argv) > 2 else (40, 340)
+lo, hi = (int(args[0]), int(args[1])) if len(args) > 1 else default
 for seed in range(lo, hi):
     try:
-        T.test_fuzz_shapes_and_paths(dev, seed)
-    except Exception as e:
+        run(dev, seed)
+    except AssertionError as e:
         bad += 1
-        print("seed", seed, "FAILED", repr(e)[:300], flush=True)
+        print("seed", seed, "FAILED", repr(e)[:600], flush=True)
+    except BaseException as e:
+        print("seed", seed, "RAISED", repr(e)[:600], "-- stopping, failures so far:", bad, flush=True)
+        sys.exit(2)
+    if gat:
+        T.F.case_data.cache_clear()      # (the suite keeps its 48 cases for the host tier; a soak run need not)
     if seed % 50 == 0:
         print("seed", seed, "ok so far, failures:", bad, flush=True)
 print("done, failures:", bad)
+sys.exit(1 if bad else 0)
