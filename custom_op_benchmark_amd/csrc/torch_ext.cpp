@@ -770,6 +770,83 @@ std::vector<at::Tensor> gat_attention_dropout_backward(const at::Tensor& row, co
                                      o, stats, dO, negative_slope, &drop);
 }
 
+// ---- the fused GAT attention op with an edge term (include/graphop_hip.h: graphop_gat_edge_attention_*) ------------
+void gat_edge_term(const at::Tensor& el, const at::Tensor& ee, int64_t n_edges, int64_t h, const char* fn) {
+  CHECK_INPUT(ee);
+  CHECK_SAME_DTYPE(el, ee);
+  const bool ok = el.dim() == 1 ? (ee.dim() == 1 && ee.size(0) == n_edges)
+                                : (ee.dim() == 2 && ee.size(0) == n_edges && ee.size(1) == h);
+  TORCH_CHECK(ok, fn, ": ee must be (n_edges) for 1-D el / er, else (n_edges, h) with n_edges = ", n_edges, " and h = ",
+              h, ", got ee ", ee.sizes(), ", el ", el.sizes());
+}
+
+std::vector<at::Tensor> gat_edge_attention_forward(const at::Tensor& row, const at::Tensor& indptr,
+                                                   const at::Tensor& eid, const at::Tensor& indices,
+                                                   const at::Tensor& el, const at::Tensor& er, const at::Tensor& ee,
+                                                   const at::Tensor& V, double negative_slope, double p, int64_t seed,
+                                                   int64_t offset) {
+  const char* fn = "gat_edge_attention_forward";
+  const DropSpec drop = drop_spec(fn, p, seed, offset);
+  CHECK_INPUT(row); CHECK_INPUT(indptr); CHECK_INPUT(eid); CHECK_INPUT(indices); CHECK_INPUT(el); CHECK_INPUT(er);
+  CHECK_INPUT(ee); CHECK_INPUT(V);
+  CHECK_INDEX(row); CHECK_INDEX(indptr); CHECK_INDEX(eid); CHECK_INDEX(indices);
+  const auto hd = gat_attn_shapes(el, er, V, fn);
+  const int64_t h = hd.first, d = hd.second;
+  const int64_t e = eid.size(0), n_l = el.size(0);
+  gat_edge_term(el, ee, e, h, fn);
+  DeviceGuard dg(el);
+  std::vector<int64_t> oshape(V.sizes().begin(), V.sizes().end());
+  oshape[0] = n_l;
+  auto o = at::empty(oshape, V.options());
+  auto stats = at::empty({n_l, h, 2}, el.options());
+  const auto pp = get_plan(row, indptr, eid, indices, er.size(0));
+  check(graphop_gat_edge_attention_forward(dtype_code(el), ip(row), ip(indptr), ip(eid), ip(indices), vp(el), vp(er),
+                                           vp(ee), vp(V), vp(o), vp(stats), row.size(0), e, n_l, er.size(0), h, d,
+                                           negative_slope, drop.p, drop.seed, drop.offset, pp->plan, stream_of(el)));
+  return {o, stats};
+}
+
+std::vector<at::Tensor> gat_edge_attention_backward(const at::Tensor& row, const at::Tensor& indptr_r,
+                                                    const at::Tensor& eid_r, const at::Tensor& indices_r,
+                                                    const at::Tensor& col, const at::Tensor& indptr_c,
+                                                    const at::Tensor& eid_c, const at::Tensor& indices_c,
+                                                    const at::Tensor& el, const at::Tensor& er, const at::Tensor& ee,
+                                                    const at::Tensor& V, const at::Tensor& o, const at::Tensor& stats,
+                                                    const at::Tensor& dO_, double negative_slope, double p,
+                                                    int64_t seed, int64_t offset, bool need_dee) {
+  const char* fn = "gat_edge_attention_backward";
+  const DropSpec drop = drop_spec(fn, p, seed, offset);
+  CHECK_INPUT(row); CHECK_INPUT(indptr_r); CHECK_INPUT(eid_r); CHECK_INPUT(indices_r);
+  CHECK_INPUT(col); CHECK_INPUT(indptr_c); CHECK_INPUT(eid_c); CHECK_INPUT(indices_c); CHECK_INPUT(el); CHECK_INPUT(er);
+  CHECK_INPUT(ee); CHECK_INPUT(V); CHECK_INPUT(o); CHECK_INPUT(stats);
+  CHECK_INDEX(row); CHECK_INDEX(indptr_r); CHECK_INDEX(eid_r); CHECK_INDEX(indices_r);
+  CHECK_INDEX(col); CHECK_INDEX(indptr_c); CHECK_INDEX(eid_c); CHECK_INDEX(indices_c);
+  CHECK_CUDA(dO_);
+  const auto hd = gat_attn_shapes(el, er, V, fn);
+  const int64_t h = hd.first, d = hd.second;
+  const int64_t e = eid_r.size(0), n_l = el.size(0);
+  gat_edge_term(el, ee, e, h, fn);
+  CHECK_SAME_DTYPE(el, o); CHECK_SAME_DTYPE(el, stats); CHECK_SAME_DTYPE(el, dO_);
+  std::vector<int64_t> oshape(V.sizes().begin(), V.sizes().end());
+  oshape[0] = n_l;
+  TORCH_CHECK(o.sizes() == at::IntArrayRef(oshape) && stats.numel() == n_l * h * 2, fn, ": o must be ",
+              at::IntArrayRef(oshape), " and stats (n_src, h, 2), got ", o.sizes(), " and ", stats.sizes());
+  const at::Tensor dO = dO_.contiguous();
+  TORCH_CHECK(dO.sizes() == o.sizes(), fn, ": dO must match o ", o.sizes(), ", got ", dO.sizes());
+  DeviceGuard dg(el);
+  auto d_el = at::empty_like(el), d_er = at::empty_like(er), dV = at::empty_like(V);
+  auto d_ee = need_dee ? at::empty_like(ee) : at::empty({0}, ee.options());   // the only edge-sized tensor made
+  auto ws = at::empty({std::max<int64_t>(n_l * h * 4, 1)}, el.options());   // (el, m, 1 / l, D) per (node, head)
+  const auto ppr = get_plan(row, indptr_r, eid_r, indices_r, er.size(0));
+  const auto ppc = get_plan(col, indptr_c, eid_c, indices_c, n_l);
+  check(graphop_gat_edge_attention_backward(
+      dtype_code(el), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c), ip(indices_c),
+      vp(el), vp(er), vp(ee), vp(V), vp(o), vp(stats), vp(dO), vp(d_el), vp(d_er), need_dee ? vp(d_ee) : nullptr,
+      vp(dV), vp(ws), ws.numel() * ws.element_size(), row.size(0), col.size(0), e, n_l, er.size(0), h, d,
+      negative_slope, drop.p, drop.seed, drop.offset, ppr->plan, ppc->plan, stream_of(el)));
+  return {d_el, d_er, d_ee, dV};
+}
+
 // m[e, k] = keep(i, j, k) / (1 - p) of the dropout forms as an edge tensor, over the row-major CSR
 at::Tensor edge_dropout_mask(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
                              const at::Tensor& indices, int64_t h, double p, int64_t seed, int64_t offset,
@@ -882,6 +959,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("eid_r"), py::arg("indices_r"), py::arg("col"), py::arg("indptr_c"), py::arg("eid_c"),
         py::arg("indices_c"), py::arg("xl"), py::arg("xr"), py::arg("att"), py::arg("o"), py::arg("stats"),
         py::arg("dO"), py::arg("negative_slope") = 0.2, py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0);
+  m.def("gat_edge_attention_forward", &gat_edge_attention_forward,
+        "Fused GAT attention with an edge term, forward (extra op)", py::arg("row"), py::arg("indptr"), py::arg("eid"),
+        py::arg("indices"), py::arg("el"), py::arg("er"), py::arg("ee"), py::arg("V"), py::arg("negative_slope") = 0.2,
+        py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0);
+  m.def("gat_edge_attention_backward", &gat_edge_attention_backward,
+        "Fused GAT attention with an edge term, backward (extra op)", py::arg("row"), py::arg("indptr_r"),
+        py::arg("eid_r"), py::arg("indices_r"), py::arg("col"), py::arg("indptr_c"), py::arg("eid_c"),
+        py::arg("indices_c"), py::arg("el"), py::arg("er"), py::arg("ee"), py::arg("V"), py::arg("o"), py::arg("stats"),
+        py::arg("dO"), py::arg("negative_slope") = 0.2, py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0,
+        py::arg("need_dee") = true);
   m.def("clear_plan_cache", &clear_plan_cache, "Destroy every cached per-graph plan");
   m.def("release_plans", &release_plans, "Drop the cached plans of the orientation whose chunk list is `row`");
   m.def("plan_cache_size", &plan_cache_size, "Graph orientations in the plan cache");
@@ -912,6 +999,8 @@ TORCH_LIBRARY(graphop, m) {
   m.def("gatv2_attention_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2) -> Tensor[]");
   m.def("gatv2_attention_dropout_forward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor xl, Tensor xr, Tensor att, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]");
   m.def("gatv2_attention_dropout_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]");
+  m.def("gat_edge_attention_forward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, Tensor ee, Tensor V, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]");
+  m.def("gat_edge_attention_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor ee, Tensor V, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0, bool need_dee=True) -> Tensor[]");
 }
 
 TORCH_LIBRARY_IMPL(graphop, CUDA, m) {
@@ -938,6 +1027,8 @@ TORCH_LIBRARY_IMPL(graphop, CUDA, m) {
   m.impl("gatv2_attention_backward", &gatv2_attention_backward);
   m.impl("gatv2_attention_dropout_forward", &gatv2_attention_dropout_forward);
   m.impl("gatv2_attention_dropout_backward", &gatv2_attention_dropout_backward);
+  m.impl("gat_edge_attention_forward", &gat_edge_attention_forward);
+  m.impl("gat_edge_attention_backward", &gat_edge_attention_backward);
 }
 
 TORCH_LIBRARY_IMPL(graphop, CPU, m) {   // there is no CPU implementation: the reference's CHECK_CUDA message
@@ -964,4 +1055,6 @@ TORCH_LIBRARY_IMPL(graphop, CPU, m) {   // there is no CPU implementation: the r
   m.impl("gatv2_attention_backward", &gatv2_attention_backward);
   m.impl("gatv2_attention_dropout_forward", &gatv2_attention_dropout_forward);
   m.impl("gatv2_attention_dropout_backward", &gatv2_attention_dropout_backward);
+  m.impl("gat_edge_attention_forward", &gat_edge_attention_forward);
+  m.impl("gat_edge_attention_backward", &gat_edge_attention_backward);
 }

@@ -207,6 +207,34 @@ class FusedGATv2AttentionDropout(Function):
         return None, None, None, None, None, None, None, None, dxl, dxr, datt, None, None, None, None
 
 
+class FusedGATEdgeAttention(Function):
+    """The fused GAT layer with a per-edge score term (extra op; GATConv(edge_dim=...) / EGATConv, or a fixed per-edge
+    bias such as log edge weights):
+    apply(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, ee, V, negative_slope, p, seed, offset)
+    -> o[i] = sum_j softmax_j(LeakyReLU(el[i] + er[j] + ee[e])) m_ij V[j] for edge e = (i, j), ee indexed by edge id.
+    m_ij is the multiplier of FusedGATAttentionDropout (1 at p = 0; seed=None draws one from torch's default CPU
+    generator).  Saves the CSR arrays, el, er, ee, V, o and stats only; the backward makes one edge-sized tensor, the
+    gradient of ee, and none when ee does not require grad."""
+
+    @staticmethod
+    def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, ee, V, negative_slope,
+                p=0.0, seed=None, offset=0):
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        ctx.drop = (float(negative_slope), float(p), int(seed), int(offset))
+        o, stats = _ops.gat_edge_attention_forward(row, indptr_r, eid_r, indices_r, el, er, ee, V, *ctx.drop)
+        ctx.save_for_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, ee, V, o, stats)
+        return o
+
+    @staticmethod
+    def backward(ctx, dO):
+        a8, (el, er, ee, V, o, stats) = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
+        need_dee = ctx.needs_input_grad[10]
+        d_el, d_er, d_ee, dV = _ops.gat_edge_attention_backward(*a8, el, er, ee, V, o, stats, dO, *ctx.drop,
+                                                                need_dee=need_dee)
+        return (None,) * 8 + (d_el, d_er, d_ee if need_dee else None, dV, None, None, None, None)
+
+
 # FusedAttention over several heads (round 5): "keep" = per head group only a_g (E x hg) survives the forward, the backward's
 # da_g / ds_g are E x hg temporaries -- speed of the 8-function step, about half of its E-sized memory; "recompute" = nothing
 # E-sized survives the forward, the backward recomputes s_g and a_g per group (two more passes per group: ~+17 % time,
@@ -460,6 +488,34 @@ def fused_gatv2_attention_dropout_step(g, xl, xr, att, dO, p, seed, offset=0, ne
     """The counterpart of gatv2_attention_dropout_step through FusedGATv2AttentionDropout; returns o (no E-sized tensor
     is kept or made, the mask included)."""
     o = FusedGATv2AttentionDropout.apply(*g.csr_args(), xl, xr, att, negative_slope, p, seed, offset)
+    o.backward(dO)
+    _lib.check_errors(sync=False)     # as in attention_step
+    return o
+
+
+def gat_edge_attention_step(g, el, er, ee, V, dO, negative_slope=0.2, p=0.0, seed=0, offset=0):
+    """One fwd+bwd of GAT attention with a per-edge score term, composed from the unfused ops:
+    z = el[i] + er[j] (GATScores at slope 1) + ee; s = LeakyReLU(z); a = row-softmax(s); (* edge_dropout_mask when
+    p > 0); o = SpMM(a, V); o.backward(dO).  Keeps z, z + ee, s and a (and the mask) as (E, h) tensors.  el, er, V must
+    be leaf tensors with requires_grad; returns (s, a, o) with a the undropped weights."""
+    args = g.csr_args()
+    z = GATScores.apply(*args, el, er, 1.0) + ee
+    s = torch.nn.functional.leaky_relu(z, negative_slope)
+    a = SparseSoftmax.apply(g.row, g.ptr_r, g.eid_r, s)
+    w = a
+    if p > 0:
+        h = 1 if el.dim() == 1 else el.size(1)
+        w = a * _ops.edge_dropout_mask(g.row, g.ptr_r, g.eid_r, g.indices_r, h, p, seed, offset, a.dtype)
+    o = VectorSPMM.apply(*args, w, V)
+    o.backward(dO)
+    _lib.check_errors(sync=False)     # as in attention_step
+    return s, a, o
+
+
+def fused_gat_edge_attention_step(g, el, er, ee, V, dO, negative_slope=0.2, p=0.0, seed=0, offset=0):
+    """The counterpart of gat_edge_attention_step through FusedGATEdgeAttention; returns o.  The gradient of ee is the
+    only edge-sized tensor made, and none is when ee does not require grad."""
+    o = FusedGATEdgeAttention.apply(*g.csr_args(), el, er, ee, V, negative_slope, p, seed, offset)
     o.backward(dO)
     _lib.check_errors(sync=False)     # as in attention_step
     return o

@@ -30,12 +30,14 @@ __all__ = ["maskedmm_csr_forward", "maskedmm_csr_backward", "node_mul_edge_forwa
 # extra ops (not in the reference's module): the fused attention step, SURVEY.md 8f N2
 # the GAT additive attention scores (LeakyReLU(el[i] + er[j]) per edge and head), the fused GAT attention layer and
 # its forms with attention dropout (plus the mask they apply, as an edge tensor, for the composed path), and the GATv2
-# scores (att . LeakyReLU(xl[i] + xr[j]) per edge and head)
+# scores (att . LeakyReLU(xl[i] + xr[j]) per edge and head), and the fused GAT layer with a per-edge score term
+# (LeakyReLU(el[i] + er[j] + ee[e]), GATConv(edge_dim=...) / EGATConv)
 EXTRA_OPS = ["attention_forward", "attention_backward", "attention_backward_is_fused", "gat_scores_forward",
              "gat_scores_backward", "gat_attention_forward", "gat_attention_backward",
              "gat_attention_dropout_forward", "gat_attention_dropout_backward", "edge_dropout_mask",
              "gatv2_scores_forward", "gatv2_scores_backward", "gatv2_attention_forward",
-             "gatv2_attention_backward", "gatv2_attention_dropout_forward", "gatv2_attention_dropout_backward"]
+             "gatv2_attention_backward", "gatv2_attention_dropout_forward", "gatv2_attention_dropout_backward",
+             "gat_edge_attention_forward", "gat_edge_attention_backward"]
 
 _NULL = None
 
@@ -692,6 +694,84 @@ def edge_dropout_mask(row, indptr, eid, indices, h, p, seed, offset=0, dtype=tor
     return y
 
 
+# ---- fused GAT attention with an edge term (extra ops) -----------------------------------------------------------
+def _gat_edge_term(el, ee, n_edges, h, fn):
+    """ee checked against the graph and the heads: (n_edges) for 1-D el / er, else (n_edges, h), in el's dtype."""
+    _check_input(ee, "ee")
+    _same_dtype(el, ee, "el", "ee")
+    if tuple(ee.shape) != ((n_edges,) if el.dim() == 1 else (n_edges, h)):
+        raise RuntimeError("%s: ee must be (n_edges) for 1-D el / er, else (n_edges, h) with n_edges = %d and h = %d, "
+                           "got ee %s, el %s" % (fn, n_edges, h, tuple(ee.shape), tuple(el.shape)))
+
+
+def gat_edge_attention_forward(row, indptr, eid, indices, el, er, ee, V, negative_slope=0.2, p=0.0, seed=0, offset=0):
+    """-> [o, stats] of the fused GAT layer with a per-edge score term: for edge e = (i, j),
+    s = LeakyReLU((el[i] + er[j]) + ee[e]), a = row-softmax(s), o[i] = sum_j a_ij m_ij V[j] per head.  ee is indexed by
+    edge id ((n_edges) for 1-D el / er, else (n_edges, h)); m_ij is the multiplier of edge_dropout_mask, 1 at p = 0.
+    stats (n_src, h, 2) = (row max, 1 / sum exp) of the undropped scores.  No edge-sized tensor is made."""
+    fn = "gat_edge_attention_forward"
+    drop = _drop_args(fn, p, seed, offset)
+    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices"), (el, "el"), (er, "er"),
+                 (ee, "ee"), (V, "V")):
+        _check_input(t, n)
+    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices")):
+        _check_index(t, n)
+    h, d = _gat_attn_shapes(el, er, V, fn)
+    e, n_l = eid.size(0), el.size(0)
+    _gat_edge_term(el, ee, e, h, fn)
+    o = torch.empty((n_l,) + tuple(V.shape[1:]), dtype=V.dtype, device=V.device)
+    stats = torch.empty((n_l, h, 2), dtype=el.dtype, device=el.device)
+    with _lib.device_guard(el.device):
+        plan = _plan(row, indptr, eid, indices, er.size(0))
+        check(lib().graphop_gat_edge_attention_forward(
+            dtype_code(el), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(el), ptr(er), ptr(ee), ptr(V), ptr(o),
+            ptr(stats), row.size(0), e, n_l, er.size(0), h, d, float(negative_slope), *drop, plan.handle,
+            stream_of(el)))
+    return [o, stats]
+
+
+def gat_edge_attention_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, ee, V, o,
+                                stats, dO, negative_slope=0.2, p=0.0, seed=0, offset=0, need_dee=True):
+    """-> [del, der, dee, dV] of gat_edge_attention_forward for the output gradient dO, with the same (p, seed, offset):
+    a and the keep decisions are recomputed per slot from stats.  dee[e] = dz_e in ee's shape is the only edge-sized
+    tensor made (edge ids that no row-major slot names get 0); with need_dee=False it is an empty (0,) tensor and
+    nothing edge-sized is written."""
+    fn = "gat_edge_attention_backward"
+    drop = _drop_args(fn, p, seed, offset)
+    names = ("row", "indptr_r", "eid_r", "indices_r", "col", "indptr_c", "eid_c", "indices_c")
+    idx = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
+    for t, n in zip(idx + (el, er, ee, V, o, stats), names + ("el", "er", "ee", "V", "o", "stats")):
+        _check_input(t, n)
+    for t, n in zip(idx, names):
+        _check_index(t, n)
+    if not isinstance(dO, torch.Tensor) or not dO.is_cuda:
+        raise RuntimeError("dO must be a CUDA tensor")
+    h, d = _gat_attn_shapes(el, er, V, fn)
+    e, n_l = eid_r.size(0), el.size(0)
+    _gat_edge_term(el, ee, e, h, fn)
+    for t, n in ((o, "o"), (stats, "stats"), (dO, "dO")):
+        _same_dtype(el, t, "el", n)
+    if o.shape != (n_l,) + tuple(V.shape[1:]) or stats.numel() != n_l * h * 2:
+        raise RuntimeError("%s: o must be %s and stats (n_src, h, 2), got %s and %s"
+                           % (fn, (n_l,) + tuple(V.shape[1:]), tuple(o.shape), tuple(stats.shape)))
+    dO = dO.contiguous()
+    if dO.shape != o.shape:
+        raise RuntimeError("%s: dO must match o %s, got %s" % (fn, tuple(o.shape), tuple(dO.shape)))
+    d_el, d_er, dV = torch.empty_like(el), torch.empty_like(er), torch.empty_like(V)
+    d_ee = torch.empty_like(ee) if need_dee else torch.empty((0,), dtype=ee.dtype, device=ee.device)
+    ws = torch.empty(max(n_l * h * 4, 1), dtype=el.dtype, device=el.device)      # (el, m, 1 / l, D) per (node, head)
+    with _lib.device_guard(el.device):
+        plan_r = _plan(row, indptr_r, eid_r, indices_r, er.size(0))
+        plan_c = _plan(col, indptr_c, eid_c, indices_c, n_l)
+        check(lib().graphop_gat_edge_attention_backward(
+            dtype_code(el), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c),
+            ptr(eid_c), ptr(indices_c), ptr(el), ptr(er), ptr(ee), ptr(V), ptr(o), ptr(stats), ptr(dO), ptr(d_el),
+            ptr(d_er), ptr(d_ee) if need_dee else _NULL, ptr(dV), ptr(ws), ws.numel() * ws.element_size(), row.size(0),
+            col.size(0), e, n_l, er.size(0), h, d, float(negative_slope), *drop, plan_r.handle, plan_c.handle,
+            stream_of(el)))
+    return [d_el, d_er, d_ee, dV]
+
+
 def prepare(graph, h=1, d=64, dtype=torch.float32, fused=True):
     """Build a graph's plans and window structures ahead of the first op call (see graphs.prepare)."""
     from . import graphs
@@ -729,6 +809,8 @@ _SCHEMAS = {
     "gatv2_attention_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2) -> Tensor[]",
     "gatv2_attention_dropout_forward": "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor xl, Tensor xr, Tensor att, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]",
     "gatv2_attention_dropout_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]",
+    "gat_edge_attention_forward": "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, Tensor ee, Tensor V, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]",
+    "gat_edge_attention_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor ee, Tensor V, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0, bool need_dee=True) -> Tensor[]",
 }
 _torch_lib = None
 

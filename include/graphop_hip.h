@@ -567,6 +567,43 @@ GRAPHOP_API int graphop_gatv2_attention_dropout_backward(int dtype, const int64_
                                      double negative_slope, double p, uint64_t seed, uint32_t offset,
                                      const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream);
 
+/* ---- fused GAT attention with an edge term (ABI 8, additive; EXTRA ops) ------------------------------------------
+ * The fused GAT layer for GATConv(edge_dim=...) / EGATConv, and for a fixed per-edge bias such as log edge weights: per
+ * head k, for every slot of every chunk c with i = row[c], j = indices[slot], e = eid[slot],
+ *   z_e = (el[i, k] + er[j, k]) + ee[e, k]   (added in that order),   s_e = LeakyReLU(z_e)
+ *   m_i = max(-1e9, max s),  l_i = sum exp(s - m_i),  a_e = exp(s_e - m_i) / l_i,  o[i, k, :] = sum a_e m_ijk V[j, k, :]
+ *   stats = (m_i, 1 / l_i) of the undropped scores, (n_l, h, 2); a row without slots gets o = 0 and stats (-1e9, 0)
+ * m_ijk is the dropout multiplier of graphop_edge_dropout_mask (a function of (i, j, k, seed, offset, p): parallel edges
+ * share a decision); p == 0 means no dropout and runs the kernels without the decision.
+ * gat_edge_attention_forward(row, indptr, eid, indices, el, er, ee, V, negative_slope, p, seed, offset) -> [o, stats]
+ *   el (n_l, h), er (n_r, h), ee (n_edges, h) indexed by EDGE ID, V (n_r, h, d), o (n_l, h, d), stats (n_l, h, 2).
+ * gat_edge_attention_backward(<8 csr>, el, er, ee, V, o, stats, dO, ...) -> [del, der, dee, dV], a recomputed per slot:
+ *   D_i = <dO_i, o_i>, da_e = m_ijk <dO_i, V_j>, ds_e = a_e (da_e - D_i), dz_e = ds_e (z_e > 0 ? 1 : slope)
+ *   del[i] = sum_j dz_e and dee[e, k] = dz_e (row-major CSR),  der[j] = sum_i dz_e,  dV[j] = sum_i a_e m_ijk dO_i
+ *   (column-major CSR).  dee (n_edges, h) is the only edge-sized tensor written, one plain store per slot and head;
+ *   edge ids that no row-major slot names get 0 (dee is zero-filled unless plan_r proves that every id is written).
+ *   dee may be NULL: then nothing edge-sized is written.  del may be NULL when n_row_chunks == 0, der and dV when
+ *   n_col_chunks == 0.  workspace: at least n_l * h * 4 values of `dtype`, as for graphop_gat_attention_backward.
+ * 0 <= p < 1, seed < 2^63, n_l, n_r < 2^32; anything else is GRAPHOP_ERR_INVALID_ARGUMENT before the device is touched.
+ * The fast kernels run under the conditions of graphop_gat_attention_forward plus ee and dee aligned to their item
+ * width, 4 * min(h, 4) bytes (csrc/kernels_gat_edge_attn.h); everything else takes the generic ones.  Any chunk layout
+ * works on both.  With a row-major plan whose eid is the identity the row-major passes do not read eid. */
+GRAPHOP_API int graphop_gat_edge_attention_forward(int dtype, const int64_t* row, const int64_t* indptr,
+                                   const int64_t* eid, const int64_t* indices, const void* el, const void* er,
+                                   const void* ee, const void* V, void* o, void* stats, int64_t n_chunks,
+                                   int64_t n_edges, int64_t n_l, int64_t n_r, int64_t h, int64_t d,
+                                   double negative_slope, double p, uint64_t seed, uint32_t offset,
+                                   const graphop_plan_t* plan, void* stream);
+GRAPHOP_API int graphop_gat_edge_attention_backward(int dtype, const int64_t* row, const int64_t* indptr_r,
+                                    const int64_t* eid_r, const int64_t* indices_r, const int64_t* col,
+                                    const int64_t* indptr_c, const int64_t* eid_c, const int64_t* indices_c,
+                                    const void* el, const void* er, const void* ee, const void* V, const void* o,
+                                    const void* stats, const void* dO, void* del, void* der, void* dee, void* dV,
+                                    void* workspace, int64_t workspace_bytes, int64_t n_row_chunks,
+                                    int64_t n_col_chunks, int64_t n_edges, int64_t n_l, int64_t n_r, int64_t h,
+                                    int64_t d, double negative_slope, double p, uint64_t seed, uint32_t offset,
+                                    const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream);
+
 /* ---- fused attention step (EXTRA op, not one of the reference's eight) --------------------------
  * The composition the reference harness chains by hand -- MaskedMMCSR -> SparseSoftmax -> VectorSPMM
  * (wrapper.py:20-30, 8-18, 44-55) -- as one forward and one backward entry, so that the E-sized

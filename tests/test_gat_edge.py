@@ -1,0 +1,442 @@
+"""GPU tier of the fused GAT layer with an edge term: graphop.gat_edge_attention_forward / _backward,
+functions.FusedGATEdgeAttention and functions.fused_gat_edge_attention_step against float64 torch autograd on the CPU
+(tests/gat_edge_reference.py) and against the composed gat_edge_attention_step.
+
+Every graph gets permuted edge ids (gat_edge_reference.permute_edge_ids), so a kernel that indexes ee or dee by slot
+instead of by eid fails; the cases named "identity ids" run the unpermuted graph, where the row-major passes skip the
+eid read.  Bounds (none new): rtol 1e-4 / atol 1e-5 for fp32 against float64, 1e-10 for fp64, on o, del, der, dee, dV;
+test_gat_edge_host.py shows that torch's own fp32 evaluation of the reference on these inputs uses less than half."""
+import pytest
+import torch
+
+import gat_edge_reference as E
+import test_gat_launch_geometry as LG
+from custom_op_benchmark_amd import _lib, functions, graphop as ops, graphs
+from gat_reference import reorder_chunks
+from util import random_graph
+
+pytestmark = pytest.mark.gpu
+
+FAST_HD = [(1, 64), (2, 32), (2, 64), (4, 16), (4, 32), (4, 64), (8, 8), (8, 16), (8, 32)]
+TAGS = ("gat_edge_attn_stats", "gat_edge_attn_fwd", "gat_edge_attn_pack", "gat_edge_attn_bwd_row",
+        "gat_edge_attn_bwd_col")
+DROP_TAGS = ("gat_edge_attn_stats", "gat_edge_attn_drop_fwd", "gat_edge_attn_pack", "gat_edge_attn_drop_bwd_row",
+             "gat_edge_attn_drop_bwd_col")
+FAST = ("k_gat_edge_attn_stats_f32", "k_gat_edge_attn_fwd_f32", "k_gat_attn_pack_f32", "k_gat_edge_attn_bwd_row_f32",
+        "k_gat_edge_attn_bwd_col_f32")
+GENERIC = ("k_gat_edge_attn_stats_generic", "k_gat_edge_attn_fwd_generic", "k_gat_attn_pack_generic",
+           "k_gat_edge_attn_bwd_row_generic", "k_gat_edge_attn_bwd_col_generic")
+DROP_FAST = ("k_gat_edge_attn_stats_f32", "k_gat_edge_attn_drop_fwd_f32", "k_gat_attn_pack_f32",
+             "k_gat_edge_attn_drop_bwd_row_f32", "k_gat_edge_attn_drop_bwd_col_f32")
+
+
+def _run(a8, dev, inp, slope, drop=None, need_dee=True):
+    """[o, del, der, dee, dV] and stats of the two ops"""
+    el, er, ee, V, dO = (x.to(dev) for x in inp)
+    drop = drop or (0.0, 0, 0)
+    o, stats = ops.gat_edge_attention_forward(*a8[:4], el, er, ee, V, slope, *drop)
+    grads = ops.gat_edge_attention_backward(*a8, el, er, ee, V, o, stats, dO, slope, *drop, need_dee=need_dee)
+    torch.cuda.synchronize()
+    return [o] + grads, stats
+
+
+def _compare(got, want, dtype, what="", names=E.NAMES):
+    tol = E.TOL32 if dtype == torch.float32 else E.TOL64
+    for name, x, y in zip(E.NAMES, got, want):
+        if name not in names:
+            continue
+        assert x.dtype == dtype and x.shape == y.shape, (what, name, x.shape, y.shape)
+        torch.testing.assert_close(x.cpu().double(), y, **tol, msg=lambda m: "%s %s: %s" % (what, name, m))
+
+
+def _run_case(case, dev, dtypes=(torch.float32,)):
+    name, make, perm_seed, h, d, _, kind, slope, drop = case
+    g, _, _ = E.case_graph(make, perm_seed)
+    a8 = g.to(dev).csr_args()
+    inp = E.case_inputs(case)
+    want = E.case_reference(case, inp)
+    for dtype in dtypes:
+        got, _ = _run(a8, dev, [x.to(dtype) for x in inp], slope, drop)
+        _compare(got, want, dtype, "%s h=%d d=%d %s %s slope=%g" % (name, h, d, kind, dtype, slope))
+
+
+def _profiled(fn):
+    """fn() with the launch profile on -> (its result, {tag: kernel})"""
+    _lib.profile_read()
+    _lib.profile_enable(True)
+    try:
+        out = fn()
+        torch.cuda.synchronize()
+        prof = _lib.profile_read()
+    finally:
+        _lib.profile_enable(False)
+    return out, {t: r["kernel"] for t, r in prof.items() if t.startswith("gat_edge_attn")}
+
+
+# ---- 1. float64 reference parity -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("chunk_size", [3, 32])
+def test_edge_matches_the_float64_reference(dev, chunk_size):
+    """A fifth of the rows empty and one hub row above the long-segment bound (1024 slots): h in {1, 2, 3, 4, 8} x
+    d in {8, 16, 32}, fp32 and fp64, p = 0, permuted edge ids."""
+    cases = [c for c in E.parity_cases() if c[0] == "parity cs=%d" % chunk_size]
+    assert len(cases) == 15
+    for case in cases:
+        _run_case(case, dev, (torch.float32, torch.float64))
+
+
+# ---- 2. slopes, ties and large scores ---------------------------------------------------------------------------------
+@pytest.mark.parametrize("slope", E.SLOPES)
+def test_edge_slopes_ties_and_large_scores(dev, slope):
+    """Fast (8, 16) and generic (3, 8): z == 0 exactly on more than a tenth of the edges (the tie takes the slope), and
+    |z| ~ 65 confined to a few rows, where an exp without the row maximum would overflow fp32."""
+    cases = [c for c in E.slope_cases() if c[7] == slope]
+    assert len(cases) == 4
+    for case in cases:
+        _, src, dst = E.case_graph(case[1], case[2])
+        el, er, ee = E.case_inputs(case)[:3]
+        z = (el[src] + er[dst]) + ee
+        if case[6] == "ties":
+            assert (z == 0).double().mean() > 0.1
+        else:
+            assert z.abs().max() > 60
+        _run_case(case, dev)
+
+
+# ---- 3. fast against generic and composed, by kernel name ------------------------------------------------------------
+def _c_abi(l, g, dev, h, d, t, planned, drop=(0.0, 0, 0)):
+    """forward + backward through ctypes, with the graph's plans or plan = NULL -> ([o, del, der, dee, dV], names)"""
+    P, F32 = _lib.ptr, _lib.F32
+    el, er, ee, V, dO = t
+    a8 = g.csr_args()
+    hr = hc = None
+    if planned:
+        hr = _lib.get_plan(g.row, g.ptr_r, g.eid_r, g.indices_r, g.n_dst).handle
+        hc = _lib.get_plan(g.col, g.ptr_c, g.eid_c, g.indices_c, g.n_src).handle
+
+    def go():
+        o, stats = torch.empty_like(dO), torch.empty((g.n_src, h, 2), device=dev)
+        _lib.check(l.graphop_gat_edge_attention_forward(
+            F32, *(P(x) for x in a8[:4]), P(el), P(er), P(ee), P(V), P(o), P(stats), g.n_row_chunks, g.n_edges, g.n_src,
+            g.n_dst, h, d, 0.2, *drop, hr, _lib.stream_of(el)))
+        d_el, d_er, d_ee, dV = (torch.empty_like(x) for x in (el, er, ee, V))
+        ws = torch.empty(g.n_src * h * 4, device=dev)
+        _lib.check(l.graphop_gat_edge_attention_backward(
+            F32, *(P(x) for x in a8), P(el), P(er), P(ee), P(V), P(o), P(stats), P(dO), P(d_el), P(d_er), P(d_ee),
+            P(dV), P(ws), ws.numel() * 4, g.n_row_chunks, g.n_col_chunks, g.n_edges, g.n_src, g.n_dst, h, d, 0.2,
+            *drop, hr, hc, _lib.stream_of(el)))
+        return [o, d_el, d_er, d_ee, dV]
+    return _profiled(go)
+
+
+def _steps_agree(g, dev, h, d, seed, what):
+    """the fused step against the composed one, and the C ABI with plans (fast kernels) against plan = NULL (generic)"""
+    l = _lib.lib()
+    gen = torch.Generator().manual_seed(seed)
+    ns = (lambda n: (n,) if h == 1 else (n, h))
+    vs = (lambda n: (n, d) if h == 1 else (n, h, d))
+    t = [torch.randn(s, generator=gen).to(dev) for s in (ns(g.n_src), ns(g.n_dst), ns(g.n_edges), vs(g.n_dst),
+                                                         vs(g.n_src))]
+    leaves = [x.clone().requires_grad_(True) for x in t[:4]]
+    _, _, o_ref = functions.gat_edge_attention_step(g, *leaves, t[4])
+    want = [o_ref.detach()] + [x.grad for x in leaves]
+    leaves2 = [x.clone().requires_grad_(True) for x in t[:4]]
+    o = functions.fused_gat_edge_attention_step(g, *leaves2, t[4])
+    got = [o.detach()] + [x.grad for x in leaves2]
+    torch.cuda.synchronize()
+    for name, x, y in zip(E.NAMES, got, want):
+        torch.testing.assert_close(x, y, **E.TOL32, msg=lambda m: "%s %s: %s" % (what, name, m))
+    fast, names = _c_abi(l, g, dev, h, d, t, True)
+    assert tuple(names[k] for k in TAGS) == FAST and len(names) == 5, names
+    slow, names = _c_abi(l, g, dev, h, d, t, False)
+    assert tuple(names[k] for k in TAGS) == GENERIC and len(names) == 5, names
+    for x, y, z in zip(fast, slow, got):
+        torch.testing.assert_close(x, y, **E.TOL32)
+        torch.testing.assert_close(x, z, **E.TOL32)
+
+
+@pytest.mark.parametrize("hd", FAST_HD)
+def test_edge_fast_path_matches_the_composed_step_and_the_generic_kernels(dev, hd):
+    """Every fast (h, d) on a 20k-node Chung-Lu graph with permuted edge ids, fp32; kernel names from the launch
+    profile: all five passes _f32 with plans and _generic without."""
+    g0 = graphs.chung_lu_graph(20000, 200000, alpha=0.5, seed=3)
+    g = E.permute_edge_ids(g0, 31)[0].to(dev)
+    assert not _lib.get_plan(g.row, g.ptr_r, g.eid_r, g.indices_r, g.n_dst).info.eid_identity
+    _steps_agree(g, dev, *hd, seed=sum(hd), what="%s" % (hd,))
+
+
+def test_edge_fast_path_on_identity_edge_ids(dev):
+    """The unpermuted graph: the row-major plan says eid_identity and the row-major passes do not read eid.  Against the
+    composed step and the generic kernels as above, and against the float64 reference on the hub graph."""
+    g = graphs.chung_lu_graph(20000, 200000, alpha=0.5, seed=3).to(dev)
+    assert _lib.get_plan(g.row, g.ptr_r, g.eid_r, g.indices_r, g.n_dst).info.eid_identity
+    _steps_agree(g, dev, 4, 16, seed=5, what="identity")
+    (case,) = [c for c in E.other_cases() if c[0] == "identity ids"]
+    _run_case(case, dev)
+
+
+# ---- 4. dropout --------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("hd", [(4, 32), (3, 8)])
+def test_edge_dropout(dev, hd):
+    """p = 0.3 with a seed above 2^32 and a non-zero offset: against the reference with dropout_reference.multipliers
+    and against the composed step with edge_dropout_mask; stats are those of p = 0 bit for bit; p = 0 launches the
+    kernels without the decision."""
+    (case,) = [c for c in E.dropout_cases() if (c[3], c[4]) == hd]
+    h, d = hd
+    p, seed, offset = case[8]
+    assert seed > 2 ** 32 and offset > 0 and p == 0.3
+    g = E.case_graph(case[1], case[2])[0].to(dev)
+    a8 = g.csr_args()
+    inp64 = E.case_inputs(case)
+    inp = [x.float() for x in inp64]
+    (got, stats), names = _profiled(lambda: _run(a8, dev, inp, 0.2, case[8]))
+    fast = hd in FAST_HD
+    assert tuple(names[k] for k in DROP_TAGS) == (DROP_FAST if fast else tuple(
+        k.replace("_f32", "_generic") for k in DROP_FAST)), names
+    _compare(got, E.case_reference(case, inp64), torch.float32, "dropout %s" % (hd,))
+    (got0, stats0), names0 = _profiled(lambda: _run(a8, dev, inp, 0.2, (0.0, seed, offset)))
+    assert tuple(names0[k] for k in TAGS) == (FAST if fast else GENERIC) and len(names0) == 5, names0
+    assert torch.equal(stats, stats0)
+    assert not torch.equal(got[0], got0[0])
+    leaves = [x.to(dev).requires_grad_(True) for x in inp[:4]]
+    _, _, o_c = functions.gat_edge_attention_step(g, *leaves, inp[4].to(dev), 0.2, p, seed, offset)
+    for name, x, y in zip(E.NAMES, got, [o_c.detach()] + [x.grad for x in leaves]):
+        torch.testing.assert_close(x, y, **E.TOL32, msg=lambda m: "composed %s: %s" % (name, m))
+
+
+# ---- 5. zero edge term -------------------------------------------------------------------------------------------------
+def test_edge_zero_edge_term_is_the_plain_fused_layer(dev):
+    (case,) = [c for c in E.other_cases() if c[0] == "zero edge term"]
+    g = E.case_graph(case[1], case[2])[0].to(dev)
+    a8 = g.csr_args()
+    inp64 = E.case_inputs(case)
+    inp = [x.float() for x in inp64]
+    assert not inp[2].any()
+    got, stats = _run(a8, dev, inp, 0.2)
+    el, er, _, V, dO = (x.to(dev) for x in inp)
+    o, stats1 = ops.gat_attention_forward(*a8[:4], el, er, V, 0.2)
+    d_el, d_er, dV = ops.gat_attention_backward(*a8, el, er, V, o, stats1, dO, 0.2)
+    for name, x, y in zip(("o", "del", "der", "dV", "stats"), (got[0], got[1], got[2], got[4], stats),
+                          (o, d_el, d_er, dV, stats1)):
+        torch.testing.assert_close(x, y, **E.TOL32, msg=lambda m: "%s: %s" % (name, m))
+    _compare(got, E.case_reference(case, inp64), torch.float32, "ee = 0")      # dee = the reference's dz
+
+
+# ---- 6. generic path on hard layouts ---------------------------------------------------------------------------------
+def test_edge_generic_path_shuffled_chunks_rectangular_fp64(dev):
+    """Chunks in random order on both orientations (no row_owned plan), n_src != n_dst, fp64 at h = 3 and fp32 at
+    (4, 16) (the OWNED = false fast kernels with the generic stats pass)."""
+    for case in [c for c in E.other_cases() if c[0] == "hard layouts"]:
+        g = E.case_graph(case[1], case[2])[0]
+        gen = torch.Generator().manual_seed(1)
+        pr = reorder_chunks(g.ptr_r, g.row, g.eid_r, g.indices_r, torch.randperm(g.n_row_chunks, generator=gen))
+        pc = reorder_chunks(g.ptr_c, g.col, g.eid_c, g.indices_c, torch.randperm(g.n_col_chunks, generator=gen))
+        csr = tuple(t.to(dev) for t in (pr[1], pr[0], pr[2], pr[3], pc[1], pc[0], pc[2], pc[3]))
+        assert not _lib.get_plan(*csr[:4], g.n_dst).info.row_owned
+        h, d = case[3], case[4]
+        dtype = torch.float64 if h == 3 else torch.float32
+        inp = [x.to(dtype) for x in E.case_inputs(case)]
+        got, _ = _run(csr, dev, inp, 0.2)
+        assert got[0].shape == (g.n_src, h, d) and g.n_src != g.n_dst
+        _compare(got, E.case_reference(case, inp), dtype, "shuffled h=%d" % h)
+
+
+@pytest.mark.parametrize("hd,dtype", [((4, 16), torch.float32), ((3, 8), torch.float64)])
+def test_edge_uncovered_edge_ids_get_zero_dee(dev, hd, dtype):
+    """A row-major chunk subset: the slots of every fifth chunk move behind the last chunk, so eid / indices keep all E
+    slots and no chunk covers those.  dee, handed in full of NaN, is exactly 0 on their edge ids and the dz of the
+    covered sub-graph elsewhere; o and del are that sub-graph's.  (The column-major arrays still hold every edge, so der
+    and dV are not compared.)"""
+    (case,) = [c for c in E.other_cases() if c[0] == "hard layouts" and (c[3], c[4]) == hd]
+    h, d = hd
+    g, src, dst = E.case_graph(case[1], case[2])
+    keep = [c for c in range(g.n_row_chunks) if c % 5 != 2]
+    drop = [c for c in range(g.n_row_chunks) if c % 5 == 2]
+    ptr, row, eid, idx = reorder_chunks(g.ptr_r, g.row, g.eid_r, g.indices_r, torch.tensor(keep + drop))
+    ptr, row = ptr[:len(keep) + 1].clone(), row[:len(keep)].clone()
+    covered = torch.zeros(g.n_edges, dtype=torch.bool)
+    covered[eid[:int(ptr[-1])]] = True
+    assert 0.1 < (~covered).double().mean() < 0.4
+    a8 = tuple(t.to(dev) for t in (row, ptr, eid, idx, g.col, g.ptr_c, g.eid_c, g.indices_c))
+    plan_r, plan_c = _lib.get_plan(*a8[:4], g.n_dst), _lib.get_plan(*a8[4:], g.n_src)
+    assert not plan_r.info.full_coverage
+    inp = [x.to(dtype) for x in E.case_inputs(case)]
+    el, er, ee, V, dO = (x.to(dev) for x in inp)
+    (o, stats), names = _profiled(lambda: ops.gat_edge_attention_forward(*a8[:4], el, er, ee, V, 0.2))
+    assert names["gat_edge_attn_fwd"] == ("k_gat_edge_attn_fwd_f32" if dtype == torch.float32 else
+                                          "k_gat_edge_attn_fwd_generic")
+    P, l = _lib.ptr, _lib.lib()
+    d_el, d_er, dV = torch.empty_like(el), torch.empty_like(er), torch.empty_like(V)
+    d_ee = torch.full_like(ee, float("nan"))
+    ws = torch.empty(g.n_src * h * 4, dtype=dtype, device=dev)
+    _lib.check(l.graphop_gat_edge_attention_backward(
+        _lib.dtype_code(el), *(P(x) for x in a8), P(el), P(er), P(ee), P(V), P(o), P(stats), P(dO), P(d_el), P(d_er),
+        P(d_ee), P(dV), P(ws), ws.numel() * ws.element_size(), row.numel(), g.n_col_chunks, g.n_edges, g.n_src,
+        g.n_dst, h, d, 0.2, 0.0, 0, 0, plan_r.handle, plan_c.handle, _lib.stream_of(el)))
+    torch.cuda.synchronize()
+    d_ee = d_ee.cpu()
+    assert not d_ee[~covered].any() and not torch.isnan(d_ee).any()
+    ids = torch.nonzero(covered)[:, 0]
+    want = E.reference(src[ids], dst[ids], g.n_src, inp[0], inp[1], inp[2][ids], inp[3], inp[4], 0.2)
+    full_dee = torch.zeros_like(inp[2], dtype=torch.float64)
+    full_dee[ids] = want[3]
+    _compare([o, d_el, d_er, d_ee.to(dev), dV], (want[0], want[1], want[2], full_dee, want[4]), dtype, "subset",
+             names=("o", "del", "dee"))
+
+
+# ---- 7. no edge-sized gradient -----------------------------------------------------------------------------------------
+def test_edge_without_dee(dev):
+    """need_dee=False at the op level and ee.requires_grad == False through the autograd class: del, der and dV stay
+    correct, dee is an empty tensor / None, and the second allocates nothing of E * h values or more."""
+    (case,) = [c for c in E.other_cases() if c[0] == "no dee"]
+    g = E.case_graph(case[1], case[2])[0].to(dev)
+    inp64 = E.case_inputs(case)
+    inp = [x.float() for x in inp64]
+    want = E.case_reference(case, inp64)
+    got, _ = _run(g.csr_args(), dev, inp, 0.2, need_dee=False)
+    assert got[3].shape == (0,) and got[3].dtype == torch.float32
+    _compare(got, want, torch.float32, "need_dee=False", names=("o", "del", "der", "dV"))
+    el, er, ee, V, dO = (x.to(dev) for x in inp)
+    leaves = [x.requires_grad_(True) for x in (el, er, V)]
+    o = functions.FusedGATEdgeAttention.apply(*g.csr_args(), leaves[0], leaves[1], ee, leaves[2], 0.2)
+    o.backward(dO)
+    torch.cuda.synchronize()
+    assert ee.grad is None
+    _compare([o.detach(), el.grad, er.grad, None, V.grad], want, torch.float32, "fixed ee", names=("o", "del", "der", "dV"))
+    # nothing edge-sized: a graph whose E * h is ten times its largest node tensor
+    h, d = 4, 16
+    big = E.permute_edge_ids(graphs.chung_lu_graph(2000, 400000, alpha=0.5, seed=2), 5)[0].to(dev)
+    gen = torch.Generator().manual_seed(0)
+    el, er, V, dO = (torch.randn(s, generator=gen).to(dev) for s in ((2000, h), (2000, h), (2000, h, d), (2000, h, d)))
+    ee = torch.randn(big.n_edges, h, generator=gen).to(dev)
+
+    def peak(ee_grad):
+        leaves = [x.clone().requires_grad_(True) for x in (el, er, V)]
+        e = ee.clone().requires_grad_(ee_grad)
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        functions.fused_gat_edge_attention_step(big, leaves[0], leaves[1], e, leaves[2], dO)
+        torch.cuda.synchronize()
+        return torch.cuda.max_memory_allocated() - base
+
+    peak(False)        # plans of both orientations are built (and cached) here
+    one = big.n_edges * h * 4
+    fixed = peak(False)
+    assert fixed < one, (fixed, one)
+
+
+# ---- 8. gradcheck ------------------------------------------------------------------------------------------------------
+def test_edge_gradcheck(dev):
+    g0 = random_graph(12, 10, 50, seed=4, chunk_size=3, hub=8)
+    g, _, _ = E.permute_edge_ids(g0, 8)
+    g = g.to(dev)
+    for h, d in ((1, 3), (2, 4)):
+        inp = E.inputs(g0.src, g0.dst, g.n_src, g.n_dst, h, d, torch.float64, seed=h)
+        leaves = tuple(x.to(dev).requires_grad_(True) for x in inp[:4])
+        assert torch.autograd.gradcheck(
+            lambda a, b, e, v: functions.FusedGATEdgeAttention.apply(*g.csr_args(), a, b, e, v, 0.2), leaves,
+            nondet_tol=1e-12)   # (split rows are summed by float atomics: the order of the adds may differ)
+
+
+# ---- 9. launch geometry ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("cpg,hd,p", [(2, (8, 8), 0.0), (2, (2, 64), 0.0), (2, (4, 32), 0.3), (16, (1, 64), 0.0)])
+def test_edge_at_cpg(dev, cpg, hd, p):
+    """Chunk-size-1 graphs of test_gat_launch_geometry.py with enough chunks for cpg = 2 and for the spmm_cpg cap (the
+    mirrored cpg asserted first), a clipped last lane group, rows of 1024, 1025 and 2049 slots; permuted edge ids."""
+    key = LG._sweep_key(dev, cpg)
+    g0 = LG._graph(*key)
+    LG._assert_cpg(g0, dev, 16, cpg)          # also: n_chunks % cpg != 0 in both orientations
+    lens = torch.bincount(g0.src, minlength=g0.n_src)
+    for n in (1024, 1025, 2049):
+        assert (lens == n).any(), n
+    g, src, dst = E.permute_edge_ids(g0, 1000 + cpg)
+    h, d = hd
+    inp = E.inputs(src, dst, g.n_src, g.n_dst, h, d, torch.float32, seed=cpg * 10 + h)
+    drop = (p, E.DROP[1], E.DROP[2]) if p > 0 else None
+    gd = g.to(dev)
+    for plan in (_lib.get_plan(gd.row, gd.ptr_r, gd.eid_r, gd.indices_r, gd.n_dst),
+                 _lib.get_plan(gd.col, gd.ptr_c, gd.eid_c, gd.indices_c, gd.n_src)):
+        assert plan.info.row_owned and plan.info.rows_sorted, "the plan does not own its rows: no plain stores"
+    (got, _), names = _profiled(lambda: _run(gd.csr_args(), dev, inp, 0.2, drop))
+    assert tuple(names[k] for k in (DROP_TAGS if p > 0 else TAGS)) == (DROP_FAST if p > 0 else FAST), names
+    want = E.reference(src, dst, g.n_src, *inp, 0.2, *(drop or (0.0, 0, 0)))
+    _compare(got, want, torch.float32, "cpg=%d %s p=%g" % (cpg, hd, p))
+
+
+# ---- 10. bindings and errors -------------------------------------------------------------------------------------------
+def test_edge_bindings_agree_and_errors(dev):
+    ext = ops.cpp_ext
+    assert ext is not None, "graphop_cpp.so not built (run __graft_entry__.build())"
+    g0 = E.BIND_GRAPH()
+    g, src, dst = E.permute_edge_ids(g0, 23)
+    g = g.to(dev)
+    a8 = g.csr_args()
+    dr = (0.3, 77, 5)
+    for h, d in ((1, 64), (4, 16), (3, 8)):
+        el, er, ee, V, dO = (x.to(dev) for x in E.inputs(src, dst, g.n_src, g.n_dst, h, d, torch.float32, seed=h))
+        f0 = ops.gat_edge_attention_forward(*a8[:4], el, er, ee, V, -0.1, *dr)
+        f1 = ext.gat_edge_attention_forward(*a8[:4], el, er, ee, V, negative_slope=-0.1, p=dr[0], seed=dr[1],
+                                            offset=dr[2])
+        f2 = torch.ops.graphop.gat_edge_attention_forward(*a8[:4], el, er, ee, V, -0.1, *dr)
+        for u, v, w in zip(f0, f1, f2):   # (rows split over lane groups are summed by atomics, in any order)
+            torch.testing.assert_close(u, v, rtol=1e-5, atol=1e-6)
+            torch.testing.assert_close(u, w, rtol=1e-5, atol=1e-6)
+        b0 = ops.gat_edge_attention_backward(*a8, el, er, ee, V, *f0, dO, -0.1, *dr)
+        b1 = ext.gat_edge_attention_backward(*a8, el, er, ee, V, *f0, dO, negative_slope=-0.1, p=dr[0], seed=dr[1],
+                                             offset=dr[2])
+        b2 = torch.ops.graphop.gat_edge_attention_backward(*a8, el, er, ee, V, *f0, dO, -0.1, *dr, False)
+        assert b2[2].shape == (0,)
+        for k, (u, v, w) in enumerate(zip(b0, b1, b2)):
+            assert u.shape == ((g.n_edges,) if h == 1 else (g.n_edges, h)) or k != 2
+            torch.testing.assert_close(u, v, rtol=1e-4, atol=1e-5)
+            if k != 2:
+                torch.testing.assert_close(u, w, rtol=1e-4, atol=1e-5)
+    for op in (ops.gat_edge_attention_forward, ext.gat_edge_attention_forward,
+               torch.ops.graphop.gat_edge_attention_forward):
+        with pytest.raises(RuntimeError, match="ee must be"):
+            op(*a8[:4], el, er, ee[:-1], V)
+        with pytest.raises(RuntimeError, match="ee must be"):
+            op(*a8[:4], el, er, ee[:, :2].contiguous(), V)
+        with pytest.raises(RuntimeError, match="ee must be contiguous"):
+            op(*a8[:4], el, er, ee.t().contiguous().t(), V)
+        with pytest.raises(RuntimeError, match="ee must be a CUDA tensor"):
+            op(*a8[:4], el, er, ee.cpu(), V)
+    for op in (ops.gat_edge_attention_backward, ext.gat_edge_attention_backward,
+               torch.ops.graphop.gat_edge_attention_backward):
+        with pytest.raises(RuntimeError, match="dO must match"):
+            op(*a8, el, er, ee, V, *f0, dO[:10])
+        with pytest.raises(RuntimeError, match="ee must be"):
+            op(*a8, el, er, ee[:-1], V, *f0, dO)
+
+
+# ---- 11. memory ----------------------------------------------------------------------------------------------------------
+def test_edge_keeps_no_edge_sized_tensor_but_dee(dev):
+    """h = 8, d = 8 on 8 M edges: one (E, h) fp32 tensor is 256 MB.  The fused fwd+bwd adds less than 1.5 of them with
+    ee requiring grad (dee only) and less than half of one with ee fixed; the composed step adds more than three."""
+    g = graphs.chung_lu_graph(20000, 8_000_000, alpha=0.5, seed=0, device=dev)
+    h, d = 8, 8
+    one = g.n_edges * h * 4
+    gen = torch.Generator().manual_seed(1)
+    el, er, V, dO = (torch.randn(s, generator=gen).to(dev) for s in ((g.n_src, h), (g.n_dst, h), (g.n_dst, h, d),
+                                                                     (g.n_src, h, d)))
+    ee = torch.randn(g.n_edges, h, device=dev)
+
+    def peak(step, ee_grad):
+        leaves = [x.clone().requires_grad_(True) for x in (el, er, V)]
+        e = ee.clone().requires_grad_(ee_grad)
+        torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
+        base = torch.cuda.memory_allocated()
+        out = step(g, leaves[0], leaves[1], e, leaves[2], dO)
+        torch.cuda.synchronize()
+        p = torch.cuda.max_memory_allocated() - base
+        del out, leaves, e
+        return p
+
+    peak(functions.fused_gat_edge_attention_step, False)     # plans of both orientations are built (and cached) here
+    fused = peak(functions.fused_gat_edge_attention_step, True)
+    fixed = peak(functions.fused_gat_edge_attention_step, False)
+    composed = peak(functions.gat_edge_attention_step, True)
+    assert fused < 1.5 * one, (fused, one)
+    assert fixed < 0.5 * one, (fixed, one)
+    assert composed > 3 * one, (composed, one)

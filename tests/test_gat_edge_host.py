@@ -1,0 +1,195 @@
+"""CPU tier of the fused GAT layer with an edge term (graphop_gat_edge_attention_forward / _backward): the library and
+both bindings expose the ops, arguments are validated before anything touches a device, CPU tensors are refused, every
+fast kernel keeps its loop in registers, a float64 restatement of the backward the kernels implement equals autograd
+through the reference layer, and torch's own fp32 evaluation of the reference on the inputs of the GPU tests stays
+within half of their bounds."""
+import ctypes
+import os
+import re
+import sys
+
+import pytest
+import torch
+import torch.nn.functional as F
+
+import gat_edge_reference as E
+
+NAMES = ("gat_edge_attention_forward", "gat_edge_attention_backward")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def test_edge_symbols_resolve_in_the_library_and_the_extension():
+    from custom_op_benchmark_amd import _ext, _lib, graphop
+    l = ctypes.CDLL(_lib.LIB_PATH)
+    for n in NAMES:
+        assert hasattr(l, "graphop_" + n) and "graphop_" + n in _lib.EXPORTED_SYMBOLS
+    assert _lib.ABI_VERSION == 8 and _lib.lib().graphop_abi_version() == 8
+    ext = _ext.load()
+    assert ext is not None, "graphop_cpp.so not built (run __graft_entry__.build())"
+    assert graphop.cpp_ext is ext
+    for n in NAMES:
+        assert callable(getattr(ext, n)) and hasattr(torch.ops.graphop, n)
+
+
+def test_edge_ops_are_extra_ops_with_an_autograd_class():
+    from custom_op_benchmark_amd import functions, graphop as ops
+    src = open(os.path.join(ROOT, "custom_op_benchmark_amd", "csrc", "torch_ext.cpp")).read()
+    for n in NAMES:
+        assert n in ops.EXTRA_OPS and callable(getattr(ops, n))
+        assert "Tensor ee" in ops._SCHEMAS[n] and "float p=0.0, int seed=0, int offset=0" in ops._SCHEMAS[n]
+        assert 'm.def("%s%s");' % (n, ops._SCHEMAS[n]) in src
+    assert "bool need_dee=True" in ops._SCHEMAS[NAMES[1]] and "need_dee" not in ops._SCHEMAS[NAMES[0]]
+    assert issubclass(functions.FusedGATEdgeAttention, torch.autograd.Function)
+    assert callable(functions.fused_gat_edge_attention_step) and callable(functions.gat_edge_attention_step)
+    assert len(ops.__all__) == 8 and not set(NAMES) & set(ops.__all__)      # the reference's eight names only
+
+
+def _fwd(l, dtype, C, E_, n_l, n_r, h, d, p=0.0, seed=0, offset=0):
+    n = ctypes.c_void_p(0)
+    return l.graphop_gat_edge_attention_forward(dtype, *([n] * 10), C, E_, n_l, n_r, h, d, 0.2, p, seed, offset, n, n)
+
+
+def _bwd(l, dtype, C, C2, E_, n_l, n_r, h, d, p=0.0, seed=0, offset=0, ws=None, ws_bytes=0):
+    n = ctypes.c_void_p(0)
+    return l.graphop_gat_edge_attention_backward(dtype, *([n] * 19), ws or n, ws_bytes, C, C2, E_, n_l, n_r, h, d, 0.2,
+                                                 p, seed, offset, n, n, n)
+
+
+def test_edge_argument_validation_without_gpu():
+    from custom_op_benchmark_amd import _lib
+    l = _lib.lib()
+    assert _fwd(l, 7, 0, 0, 0, 0, 1, 8) == 1 and b"dtype" in l.graphop_last_error()
+    assert _bwd(l, 7, 0, 0, 0, 0, 0, 1, 8) == 1 and b"dtype" in l.graphop_last_error()
+    for bad in ((-1, 10, 5, 5, 2, 8), (4, -10, 5, 5, 2, 8), (4, 10, -5, 5, 2, 8), (4, 10, 5, -5, 2, 8),
+                (4, 10, 5, 5, 0, 8), (4, 10, 5, 5, 2, 0)):
+        assert _fwd(l, 0, *bad) == 1 and b"negative size" in l.graphop_last_error(), bad
+        assert _bwd(l, 0, bad[0], 4, *bad[1:]) == 1 and b"negative size" in l.graphop_last_error(), bad
+    assert _bwd(l, 0, 4, -4, 10, 5, 5, 2, 8) == 1 and b"negative size" in l.graphop_last_error()
+    for p in (1.0, -0.1, float("nan"), 1.5):
+        assert _fwd(l, 0, 4, 10, 5, 5, 2, 8, p) == 1 and b"p must be in [0, 1)" in l.graphop_last_error()
+        assert _bwd(l, 0, 4, 4, 10, 5, 5, 2, 8, p) == 1 and b"p must be in [0, 1)" in l.graphop_last_error()
+    assert _fwd(l, 0, 4, 10, 5, 5, 2, 8, 0.5, seed=2 ** 63) == 1 and b"seed" in l.graphop_last_error()
+    assert _bwd(l, 0, 4, 4, 10, 5, 2 ** 32, 2, 8, 0.5) == 1 and b"32 bits" in l.graphop_last_error()
+    # the workspace rule is that of gat_attention_backward: n_l * h * 4 values of dtype
+    for p in (0.0, 0.6):
+        assert _bwd(l, 0, 4, 4, 10, 5, 5, 2, 8, p, ws=ctypes.c_void_p(16), ws_bytes=5 * 2 * 4 * 4 - 4) == 1
+        assert b"workspace" in l.graphop_last_error()
+        assert _bwd(l, 1, 4, 4, 10, 5, 5, 2, 8, p, ws=ctypes.c_void_p(16), ws_bytes=5 * 2 * 4 * 8 - 8) == 1
+        assert b"workspace" in l.graphop_last_error()
+    # empty problems are no-ops that never dereference anything
+    assert _fwd(l, 0, 0, 0, 0, 0, 1, 8) == 0
+    assert _fwd(l, 1, 0, 0, 0, 7, 4, 16, 0.6, seed=2 ** 63 - 1, offset=2 ** 32 - 1) == 0
+    assert _bwd(l, 0, 0, 0, 0, 0, 0, 1, 8, 0.6) == 0
+    assert _bwd(l, 1, 0, 0, 0, 0, 3, 8, 32) == 0
+
+
+def test_edge_python_argument_checks_and_cpu_tensors_are_refused():
+    from custom_op_benchmark_amd import graphop as ops
+    i = torch.zeros(2, dtype=torch.int64)
+    f, e, v = torch.zeros(2, 4), torch.zeros(2, 4), torch.zeros(2, 4, 8)
+    with pytest.raises(RuntimeError, match="row must be a CUDA tensor"):
+        ops.gat_edge_attention_forward(i, i, i, i, f, f, e, v, 0.2)
+    with pytest.raises(RuntimeError, match="row must be a CUDA tensor"):
+        ops.gat_edge_attention_backward(i, i, i, i, i, i, i, i, f, f, e, v, v, f, v, 0.2, need_dee=False)
+    with pytest.raises(RuntimeError, match="no CPU implementation|must be a CUDA tensor"):
+        torch.ops.graphop.gat_edge_attention_forward(i, i, i, i, f, f, e, v, 0.2, 0.5, 1, 0)
+    with pytest.raises(RuntimeError, match="no CPU implementation|must be a CUDA tensor"):
+        torch.ops.graphop.gat_edge_attention_backward(i, i, i, i, i, i, i, i, f, f, e, v, v, f, v, 0.1, 0.5, 1, 0, True)
+    with pytest.raises(RuntimeError, match="must be a CUDA tensor"):
+        ops.cpp_ext.gat_edge_attention_forward(i, i, i, i, f, f, e, v, 0.2)
+    with pytest.raises(RuntimeError, match="must be a CUDA tensor"):
+        ops.cpp_ext.gat_edge_attention_backward(i, i, i, i, i, i, i, i, f, f, e, v, v, f, v, need_dee=False)
+    for kw, msg in ((dict(p=0.5, offset=2 ** 32), "offset"), (dict(p=1.0), r"p must be in \[0, 1\)"),
+                    (dict(p=0.5, seed=-1), "seed")):
+        with pytest.raises(RuntimeError, match=msg):
+            ops.gat_edge_attention_forward(i, i, i, i, f, f, e, v, 0.2, **kw)
+        with pytest.raises(RuntimeError, match=msg):
+            ops.gat_edge_attention_backward(i, i, i, i, i, i, i, i, f, f, e, v, v, f, v, 0.2, **kw)
+        with pytest.raises(RuntimeError, match=msg):
+            ops.cpp_ext.gat_edge_attention_forward(i, i, i, i, f, f, e, v, 0.2, **kw)
+
+
+def test_edge_fast_kernels_do_not_spill():
+    """9 (h, d) pairs x {owned, shared} x {drop, no drop} x {fwd, bwd_row, bwd_col}, and the stats forms (4 head counts x
+    2 group widths): no scratch and no spill in any of them, and no k_gat_edge_attn_*_f32 outside this census."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from kernel_resources import kernel_resources
+    res = kernel_resources()
+    gather = {n: r for n, r in res.items()
+              if re.search(r"k_gat_edge_attn_(fwd|bwd_row|bwd_col)_f32<\d+, \d+, (true|false), (true|false)>\(", n)}
+    assert len(gather) == 9 * 2 * 2 * 3, sorted(gather)
+    stats = {n: r for n, r in res.items() if re.search(r"k_gat_edge_attn_stats_f32<\d+, \d+>\(", n)}
+    assert len(stats) == 4 * 2, sorted(stats)
+    every = {n for n in res if re.search(r"k_gat_edge_attn_\w+_f32", n)}
+    assert every == set(gather) | set(stats), sorted(every - set(gather) - set(stats))
+    bad = {n: r for n, r in {**gather, **stats}.items() if r["spill_vgpr"] or r["spill_sgpr"] or r["scratch"]}
+    assert not bad, "\n".join("%s: %r" % kv for kv in sorted(bad.items()))
+
+
+def _restated(src, dst, n_l, n_r, el, er, ee, V, dO, slope, mult):
+    """The backward as the kernels compute it, in float64: stats of the undropped scores -> a -> o of the dropped
+    weights, D = <dO, o>, da = m <dO, V>, ds, dz, then the four sums and dee = dz."""
+    h = el.size(1)
+    z = (el[src] + er[dst]) + ee
+    s = F.leaky_relu(z, slope)
+    m = torch.full((n_l, h), -1e9, dtype=s.dtype).scatter_reduce(0, src[:, None].expand(-1, h), s, "amax")
+    ex = torch.exp(s - m[src])
+    lsum = torch.zeros((n_l, h), dtype=s.dtype).index_add(0, src, ex)
+    inv_l = torch.where(lsum > 0, 1 / lsum, torch.zeros_like(lsum))
+    a = ex * inv_l[src]
+    o = torch.zeros((n_l, h, V.size(-1)), dtype=V.dtype).index_add(0, src, (a * mult)[..., None] * V[dst])
+    D = (dO * o).sum(-1)
+    da = mult * (dO[src] * V[dst]).sum(-1)
+    ds = a * (da - D[src])
+    dz = torch.where(z > 0, ds, ds * slope)
+    d_el = torch.zeros_like(el).index_add(0, src, dz)
+    d_er = torch.zeros_like(er).index_add(0, dst, dz)
+    dV = torch.zeros_like(V).index_add(0, dst, (a * mult)[..., None] * dO[src])
+    return o, d_el, d_er, dz, dV
+
+
+@pytest.mark.parametrize("p", [0.0, 0.3])
+@pytest.mark.parametrize("slope", [0.2, 0.0, -0.1])
+def test_edge_backward_formulas_match_autograd(slope, p):
+    """A small rectangular graph with empty rows, z == 0 ties (they take the slope), a row at +50 and parallel edges."""
+    gen = torch.Generator().manual_seed(3)
+    n_l, n_r, h, d = 23, 17, 3, 5
+    seed, offset = 1234567890123, 7
+    src = torch.randint(0, n_l, (160,), generator=gen)
+    src = src[src % 5 != 0]                                       # rows 0, 5, 10, ... are empty
+    dst = torch.randint(0, n_r, (src.numel(),), generator=gen)
+    src, dst = torch.cat([src, src[:20]]), torch.cat([dst, dst[:20]])      # parallel edges
+    el = torch.randint(-3, 4, (n_l, h), generator=gen).double()
+    er = torch.randint(-3, 4, (n_r, h), generator=gen).double()
+    ee = torch.randint(-3, 4, (src.numel(), h), generator=gen).double()
+    pick = torch.rand(src.numel(), generator=gen) < 0.3
+    ee[pick] = -(el[src] + er[dst])[pick]
+    assert (((el[src] + er[dst]) + ee) == 0).double().mean() > 0.1
+    ee[src == 1] += 50.0
+    V = torch.randn(n_r, h, d, generator=gen, dtype=torch.float64)
+    dO = torch.randn(n_l, h, d, generator=gen, dtype=torch.float64)
+    want = E.reference(src, dst, n_l, el, er, ee, V, dO, slope, p, seed, offset)
+    mult = E.R.multipliers(src.numpy(), dst.numpy(), h, p, seed, offset) if p > 0 else torch.ones(src.numel(), h).double()
+    got = _restated(src, dst, n_l, n_r, el, er, ee, V, dO, slope, mult)
+    for name, x, y in zip(E.NAMES, got, want):
+        torch.testing.assert_close(x, y, rtol=1e-12, atol=1e-12, msg=lambda msg: name + ": " + msg)
+
+
+def test_edge_fp32_reference_sits_inside_half_the_bounds():
+    """torch's own fp32 evaluation of the reference on every input set the GPU tests compare against float64: the worst
+    |error| / (atol + rtol |want|) stays below 0.5, so the bounds leave the kernels as much room as torch itself uses."""
+    worst = {}
+    for case in E.all_cases():
+        inp = E.case_inputs(case)
+        want = E.case_reference(case, inp)
+        got = E.case_reference(case, [x.float() for x in inp], torch.float32)
+        worst[case[0]] = max(worst.get(case[0], 0.0), E.worst_ratio(got, want))
+        if case[6] in ("ties", "large"):
+            _, src, dst = E.case_graph(case[1], case[2])
+            z = (inp[0][src] + inp[1][dst]) + inp[2]
+            if case[6] == "ties":
+                assert (z == 0).double().mean() > 0.1
+            else:
+                assert 60 < z.abs().max() < 70
+    print(worst)
+    assert max(worst.values()) <= 0.5, worst
