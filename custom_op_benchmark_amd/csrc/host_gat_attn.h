@@ -80,7 +80,8 @@ struct GatAttnLabels {
   GatAttnLabels{{op "_" pass, op "_drop_" pass},                      \
                 {{"k_" op "_" pass "_generic", "k_" op "_" pass "_f32"}, \
                  {"k_" op "_drop_" pass "_generic", "k_" op "_drop_" pass "_f32"}}}
-#define GO_GAT_ATTN_LABELS(pass) GO_GAT_ATTN_LABELS_OF("gat_attn", pass)
+#define GO_GAT_ATTN_LABELS(EDGE, pass) \
+  (EDGE ? GO_GAT_ATTN_LABELS_OF("gat_edge_attn", pass) : GO_GAT_ATTN_LABELS_OF("gat_attn", pass))
 
 // chunks per lane group: up to the SpMM cap on big graphs, fewer on small ones so every CU still gets groups
 inline int gat_attn_cpg(i64 n_chunks) {

@@ -4,8 +4,9 @@
 // kernels_dropout.h (1 without dropout).  The backward is that of kernels_gat_attn.h plus one output:
 //   dz_e = a (da - D) * (z > 0 ? 1 : slope),  del[i] = sum_j dz,  der[j] = sum_i dz,  dV[j] = sum_i a m dO_i,  dee[e] = dz_e
 // dee is the only edge-sized tensor written: one plain store per slot and head from the row-major pass, where every
-// slot is visited once.  The passes are those of kernels_gat_attn.h (its pack kernels are launched unchanged: P =
-// (el, m, 1/l, D) still holds); every gather pass additionally reads the slot's edge id and the h values of ee.
+// slot is visited once.  The passes are the text of kernels_gat_attn_passes.inc compiled a second time, with the edge
+// term: every gather pass additionally reads the slot's edge id and the h values of ee.  The pack kernels and the
+// generic stats init / finish of kernels_gat_attn.h are launched unchanged: P = (el, m, 1/l, D) still holds.
 // A NULL eid means eid[slot] == slot (a plan with eid_identity, as graph_from_coo always yields in row-major order):
 // a kernel-uniform branch, not a second set of instantiations.
 #pragma once
@@ -13,522 +14,12 @@
 
 namespace graphop {
 
-// ---- stats pass: k_gat_attn_stats_f32's segment walk with z = (el_i + er_j) + ee_e ---------------------------------
-template <int H, int G>
-__global__ __launch_bounds__(kFastBlock) void k_gat_edge_attn_stats_f32(
-    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ eid,
-    const i64* __restrict__ indices, const i64* __restrict__ seg_chunk, const float* __restrict__ el,
-    const float* __restrict__ er, const float* __restrict__ ee, float2* __restrict__ stats, i64 n_seg,
-    unsigned nb_short, i64 long_len, const int* __restrict__ long_segs, float slope) {
-  constexpr int W = H >= 4 ? 4 : H;
-  constexpr int NI = H / W;   // items of er / ee per slot
-  __shared__ float red[2][kFastBlock / kWave][H];
-  const bool longp = blockIdx.x >= nb_short;
-  int gl, gw;       // lane and width of the reducing group
-  i64 s;
-  if (longp) {
-    s = long_segs[blockIdx.x - nb_short];
-    gl = threadIdx.x;
-    gw = kFastBlock;
-  } else {
-    s = (i64)blockIdx.x * (kFastBlock / G) + threadIdx.x / G;
-    gl = threadIdx.x % G;
-    gw = G;
-  }
-  const bool have = s < n_seg;
-  i64 r = 0, j0 = 0, j1 = 0;
-  if (have) {
-    const i64 c0 = seg_chunk[s];
-    r = row[c0];
-    j0 = indptr[c0];
-    j1 = indptr[seg_chunk[s + 1]];
-  }
-  const bool work = have && (longp || j1 - j0 <= long_len);
-  float a[H], m[H], l[H];
-  if (work) {
-#pragma unroll
-    for (int k = 0; k < NI; ++k) {
-      const GatItem<W> t = gat_ld<W>(el + r * H + k * W);
-#pragma unroll
-      for (int i = 0; i < W; ++i) a[k * W + i] = t.v[i];
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < H; ++k) { m[k] = kGatAttnFloor; l[k] = 0.f; }
-  if (work) {
-    i64 j = j0 + gl;
-    for (; j + gw < j1; j += 2 * gw) {   // two independent gathers in flight
-      const i64 s0 = indices[j], s1 = indices[j + gw];
-      const i64 e0 = eid ? eid[j] : j, e1 = eid ? eid[j + gw] : j + gw;
-      GatItem<W> b0[NI], b1[NI], g0[NI], g1[NI];
-#pragma unroll
-      for (int k = 0; k < NI; ++k) {
-        b0[k] = gat_ld<W>(er + s0 * H + k * W); b1[k] = gat_ld<W>(er + s1 * H + k * W);
-        g0[k] = gat_ld<W>(ee + e0 * H + k * W); g1[k] = gat_ld<W>(ee + e1 * H + k * W);
-      }
-#pragma unroll
-      for (int k = 0; k < NI; ++k)
-#pragma unroll
-        for (int i = 0; i < W; ++i) {
-          const int hh = k * W + i;
-          const float z0 = gat_lrelu((a[hh] + b0[k].v[i]) + g0[k].v[i], slope);
-          const float z1 = gat_lrelu((a[hh] + b1[k].v[i]) + g1[k].v[i], slope);
-          const float mx = fmaxf(z0, z1);
-          gat_attn_merge(m[hh], l[hh], mx, exp_nonpos(z0 - mx) + exp_nonpos(z1 - mx));
-        }
-    }
-    if (j < j1) {
-      const i64 s0 = indices[j];
-      const i64 e0 = eid ? eid[j] : j;
-#pragma unroll
-      for (int k = 0; k < NI; ++k) {
-        const GatItem<W> b0 = gat_ld<W>(er + s0 * H + k * W);
-        const GatItem<W> g0 = gat_ld<W>(ee + e0 * H + k * W);
-#pragma unroll
-        for (int i = 0; i < W; ++i) {
-          const int hh = k * W + i;
-          gat_attn_merge(m[hh], l[hh], gat_lrelu((a[hh] + b0.v[i]) + g0.v[i], slope), 1.f);
-        }
-      }
-    }
-  }
-  // butterfly over the group's lanes (a wave at most)
-  const int wl = gw < kWave ? gw : kWave;
-#pragma unroll
-  for (int k = 0; k < H; ++k)
-    for (int o = 1; o < wl; o <<= 1) gat_attn_merge(m[k], l[k], __shfl_xor(m[k], o), __shfl_xor(l[k], o));
-  if (longp) {   // workgroup-uniform branch: the waves' results through LDS
-    const int w = threadIdx.x / kWave;
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-#pragma unroll
-      for (int k = 0; k < H; ++k) { red[0][w][k] = m[k]; red[1][w][k] = l[k]; }
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-      for (int k = 0; k < H; ++k)
-        for (int q = 1; q < kFastBlock / kWave; ++q) gat_attn_merge(m[k], l[k], red[0][q][k], red[1][q][k]);
-    }
-  }
-  if (work && gl == 0) {
-#pragma unroll
-    for (int k = 0; k < H; ++k) stats[r * H + k] = make_float2(m[k], l[k] > 0.f ? 1.f / l[k] : 0.f);
-  }
-}
-
-// ---- forward aggregation: k_gat_attn_fwd_f32's chunk driver; the lanes that load a batch's neighbour ids also load
-// its edge ids, and one more scalar per (slot, piece) is gathered ---------------------------------------------------
-template <int H, int D, bool OWNED, bool DROP>
-__global__ __launch_bounds__(kFastBlock) void k_gat_edge_attn_fwd_f32(
-    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ eid,
-    const i64* __restrict__ indices, const float* __restrict__ el, const float* __restrict__ er,
-    const float* __restrict__ ee, const float2* __restrict__ stats, const float* __restrict__ V,
-    float* __restrict__ o, i64 n_chunks, int chunks_per_group, float slope, DropArgsIf<DROP, float> dr) {
-  using C = GatAttnCfg<H, D>;
-  constexpr int L = C::L, NV = C::NV, SB = C::SB_FWD;
-  constexpr int IDL = DROP ? GatDropCfg<H, SB>::LANES : SB;   // lanes that load a neighbour id
-  constexpr i64 F4 = C::F4;
-  const int l = threadIdx.x % L;
-  const i64 gid = (i64)blockIdx.x * (kFastBlock / L) + threadIdx.x / L;
-  const i64 c0 = gid * chunks_per_group;
-  i64 c1 = c0 + chunks_per_group;
-  if (c1 > n_chunks) c1 = n_chunks;
-  if (c0 >= c1) return;
-  i64 row_before = -1, row_after = -1;
-  if constexpr (OWNED) {
-    if (c0 > 0) row_before = row[c0 - 1];
-    if (c1 < n_chunks) row_after = row[c1];
-  }
-  int kv[NV];
-#pragma unroll
-  for (int v = 0; v < NV; ++v) kv[v] = gat_attn_head<H, D>(v, l);
-  float4 acc[NV];
-  float a_el[NV], a_m[NV], a_il[NV];
-  auto zero_acc = [&]() {
-#pragma unroll
-    for (int v = 0; v < NV; ++v) acc[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-  };
-  auto flush = [&](i64 r) {
-    if (OWNED && r != row_before && r != row_after) {
-#pragma unroll
-      for (int v = 0; v < NV; ++v) reinterpret_cast<float4*>(o)[r * F4 + v * L + l] = acc[v];
-    } else {
-      atomic_flush<L, NV>(o, r, acc, l);
-    }
-  };
-  zero_acc();
-  i64 cur = -1;
-  bool dirty = false;
-  for (i64 c = c0; c < c1; ++c) {
-    const i64 r = row[c];
-    if (r != cur) {
-      if (dirty) { flush(cur); zero_acc(); dirty = false; }
-      cur = r;
-#pragma unroll
-      for (int v = 0; v < NV; ++v) {
-        a_el[v] = el[r * H + kv[v]];
-        const float2 st = stats[r * H + kv[v]];
-        a_m[v] = st.x;
-        a_il[v] = st.y;
-      }
-    }
-    const i64 j0 = indptr[c], j1 = indptr[c + 1];
-    if (j1 > j0) dirty = true;
-    for (i64 jb = j0; jb < j1; jb += SB) {
-      const int nb = (j1 - jb) < SB ? (int)(j1 - jb) : SB;
-      int my_src = 0, my_e = 0;   // slots past the end re-read the batch's last slot with weight 0
-      const int t = DROP ? l % SB : l;
-      if (l < IDL) {
-        const i64 j = jb + (t < nb ? t : nb - 1);
-        my_src = (int)indices[j];
-        my_e = eid ? (int)eid[j] : (int)j;
-      }
-      float4 x[SB][NV];
-      float e[SB][NV], g[SB][NV];
-      static_for<SB>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        const i64 src = group_bcast<L, u>(my_src);
-        const i64 ed = group_bcast<L, u>(my_e);
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-          x[u][v] = reinterpret_cast<const float4*>(V)[src * F4 + v * L + l];
-          e[u][v] = er[src * H + kv[v]];
-          g[u][v] = ee[ed * H + kv[v]];
-        }
-      });
-      int keep[DROP ? SB : 1];
-      if constexpr (DROP) {
-        const int mine = gat_drop_lane_bits<H, SB, false>(l, r, my_src, dr);
-        static_for<SB>([&](auto uc) {
-          constexpr int u = decltype(uc)::value;
-          keep[u] = gat_drop_slot_bits<H, SB, u>(mine);
-        });
-      }
-#pragma unroll
-      for (int u = 0; u < SB; ++u) {
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-          const float z = gat_lrelu((a_el[v] + e[u][v]) + g[u][v], slope);
-          float w = u < nb ? exp_nonpos(z - a_m[v]) * a_il[v] : 0.f;
-          if constexpr (DROP) w = (keep[u] >> kv[v]) & 1 ? w * dr.scale : 0.f;
-          acc[v].x = fmaf(w, x[u][v].x, acc[v].x); acc[v].y = fmaf(w, x[u][v].y, acc[v].y);
-          acc[v].z = fmaf(w, x[u][v].z, acc[v].z); acc[v].w = fmaf(w, x[u][v].w, acc[v].w);
-        }
-      }
-    }
-  }
-  if (dirty) flush(cur);
-}
-
-// ---- backward passes: gat_attn_bwd_walk with the edge term -------------------------------------------------------
-// ROW (row-major chunks): own = dO_i and P[i]; gathers er_j, V_j and ee_e; out0 = del, and dee[e] = dz_e where dee is
-//   not NULL: the head's first lane stores it, for the batch's real slots only.
-// COL (column-major chunks): own = V_j and er_j; gathers P[i], dO_i and ee_e (e = eid_c[slot]: a random 4-byte read per
-//   slot and head, inherent while nothing edge-sized may be staged); out0 = der, out1 = dV.
-template <int H, int D, bool COL, bool OWNED, bool DROP>
-__device__ __forceinline__ void gat_edge_attn_bwd_walk(
-    const i64* __restrict__ seg, const i64* __restrict__ indptr, const i64* __restrict__ eid,
-    const i64* __restrict__ indices, const float* __restrict__ er, const float* __restrict__ ee,
-    const float* __restrict__ V, const float4* __restrict__ P, const float* __restrict__ dO,
-    float* __restrict__ out0, float* __restrict__ out1, float* __restrict__ dee, i64 n_chunks, int chunks_per_group,
-    float slope, const DropArgsIf<DROP, float>& dr) {
-  using C = GatAttnCfg<H, D>;
-  constexpr int L = C::L, NV = C::NV, DQ = C::DQ, SB = C::SB_BWD;
-  constexpr int IDL = DROP ? GatDropCfg<H, SB>::LANES : SB;   // lanes that load a neighbour id
-  constexpr i64 F4 = C::F4;
-  const int l = threadIdx.x % L;
-  const i64 gid = (i64)blockIdx.x * (kFastBlock / L) + threadIdx.x / L;
-  const i64 c0 = gid * chunks_per_group;
-  i64 c1 = c0 + chunks_per_group;
-  if (c1 > n_chunks) c1 = n_chunks;
-  if (c0 >= c1) return;
-  i64 row_before = -1, row_after = -1;
-  if constexpr (OWNED) {
-    if (c0 > 0) row_before = seg[c0 - 1];
-    if (c1 < n_chunks) row_after = seg[c1];
-  }
-  int kv[NV];
-#pragma unroll
-  for (int v = 0; v < NV; ++v) kv[v] = gat_attn_head<H, D>(v, l);
-  float4 y[NV];              // ROW: dO_i   COL: V_j
-  float4 p_own[NV];          // ROW: P[i, k_v]
-  float e_own[NV];           // COL: er[j, k_v]
-  float acc[NV];             // dz sums of the piece's head
-  float4 accv[COL ? NV : 1]; // COL: dV_j
-  auto zero_acc = [&]() {
-#pragma unroll
-    for (int v = 0; v < NV; ++v) acc[v] = 0.f;
-#pragma unroll
-    for (int v = 0; v < (COL ? NV : 1); ++v) accv[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-  };
-  auto flush = [&](i64 r) {
-    const bool own = OWNED && r != row_before && r != row_after;
-    if (l % DQ == 0) {
-#pragma unroll
-      for (int v = 0; v < NV; ++v) {
-        if (own) out0[r * H + kv[v]] = acc[v];
-        else atomicAdd(out0 + r * H + kv[v], acc[v]);
-      }
-    }
-    if constexpr (COL) {
-      if (own) {
-#pragma unroll
-        for (int v = 0; v < NV; ++v) reinterpret_cast<float4*>(out1)[r * F4 + v * L + l] = accv[v];
-      } else {
-        atomic_flush<L, NV>(out1, r, accv, l);
-      }
-    }
-  };
-  zero_acc();
-  i64 cur = -1;
-  bool dirty = false;
-  for (i64 c = c0; c < c1; ++c) {
-    const i64 r = seg[c];
-    if (r != cur) {
-      if (dirty) { flush(cur); zero_acc(); dirty = false; }
-      cur = r;
-#pragma unroll
-      for (int v = 0; v < NV; ++v) {
-        y[v] = reinterpret_cast<const float4*>(COL ? V : dO)[r * F4 + v * L + l];
-        if constexpr (COL) e_own[v] = er[r * H + kv[v]];
-        else p_own[v] = P[r * H + kv[v]];
-      }
-    }
-    const i64 j0 = indptr[c], j1 = indptr[c + 1];
-    if (j1 > j0) dirty = true;
-    for (i64 jb = j0; jb < j1; jb += SB) {
-      const int nb = (j1 - jb) < SB ? (int)(j1 - jb) : SB;
-      int my_src = 0, my_e = 0;
-      const int t = DROP ? l % SB : l;
-      if (l < IDL) {
-        const i64 j = jb + (t < nb ? t : nb - 1);
-        my_src = (int)indices[j];
-        my_e = eid ? (int)eid[j] : (int)j;
-      }
-      float4 x[SB][NV];        // ROW: V_j   COL: dO_i
-      float4 pg[COL ? SB : 1][NV];
-      float eg[COL ? 1 : SB][NV];
-      float g[SB][NV];         // ee_e
-      int ed[SB];
-      static_for<SB>([&](auto uc) {
-        constexpr int u = decltype(uc)::value;
-        const i64 src = group_bcast<L, u>(my_src);
-        ed[u] = group_bcast<L, u>(my_e);
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-          x[u][v] = reinterpret_cast<const float4*>(COL ? dO : V)[src * F4 + v * L + l];
-          if constexpr (COL) pg[u][v] = P[src * H + kv[v]];
-          else eg[u][v] = er[src * H + kv[v]];
-          g[u][v] = ee[(i64)ed[u] * H + kv[v]];
-        }
-      });
-      int keep[DROP ? SB : 1];
-      if constexpr (DROP) {
-        const int mine = gat_drop_lane_bits<H, SB, COL>(l, r, my_src, dr);
-        static_for<SB>([&](auto uc) {
-          constexpr int u = decltype(uc)::value;
-          keep[u] = gat_drop_slot_bits<H, SB, u>(mine);
-        });
-      }
-#pragma unroll
-      for (int u = 0; u < SB; ++u) {
-#pragma unroll
-        for (int v = 0; v < NV; ++v) {
-          float da = group_sum<DQ>(dot4(y[v], x[u][v]));
-          float4 p;
-          float z;
-          if constexpr (COL) { p = pg[u][v]; z = (p.x + e_own[v]) + g[u][v]; }
-          else { p = p_own[v]; z = (p.x + eg[u][v]) + g[u][v]; }
-          const float a = u < nb ? exp_nonpos(gat_lrelu(z, slope) - p.y) * p.z : 0.f;
-          float am = a;   // a_ij m_ij
-          if constexpr (DROP) {
-            const float m = (keep[u] >> kv[v]) & 1 ? dr.scale : 0.f;
-            da *= m;
-            am *= m;
-          }
-          const float ds = a * (da - p.w);
-          const float dz = z > 0.f ? ds : ds * slope;
-          acc[v] += dz;
-          if constexpr (COL) {
-            accv[v].x = fmaf(am, x[u][v].x, accv[v].x); accv[v].y = fmaf(am, x[u][v].y, accv[v].y);
-            accv[v].z = fmaf(am, x[u][v].z, accv[v].z); accv[v].w = fmaf(am, x[u][v].w, accv[v].w);
-          } else {
-            if (dee && u < nb && l % DQ == 0) dee[(i64)ed[u] * H + kv[v]] = dz;
-          }
-        }
-      }
-    }
-  }
-  if (dirty) flush(cur);
-}
-
-template <int H, int D, bool OWNED, bool DROP>
-__global__ __launch_bounds__(kFastBlock) void k_gat_edge_attn_bwd_row_f32(
-    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ eid,
-    const i64* __restrict__ indices, const float* __restrict__ er, const float* __restrict__ ee,
-    const float* __restrict__ V, const float4* __restrict__ P, const float* __restrict__ dO, float* __restrict__ del,
-    float* __restrict__ dee, i64 n_chunks, int chunks_per_group, float slope, DropArgsIf<DROP, float> dr) {
-  gat_edge_attn_bwd_walk<H, D, false, OWNED, DROP>(row, indptr, eid, indices, er, ee, V, P, dO, del, nullptr, dee,
-                                                   n_chunks, chunks_per_group, slope, dr);
-}
-
-template <int H, int D, bool OWNED, bool DROP>
-__global__ __launch_bounds__(kFastBlock) void k_gat_edge_attn_bwd_col_f32(
-    const i64* __restrict__ col, const i64* __restrict__ indptr, const i64* __restrict__ eid,
-    const i64* __restrict__ indices, const float* __restrict__ er, const float* __restrict__ ee,
-    const float* __restrict__ V, const float4* __restrict__ P, const float* __restrict__ dO, float* __restrict__ der,
-    float* __restrict__ dV, i64 n_chunks, int chunks_per_group, float slope, DropArgsIf<DROP, float> dr) {
-  gat_edge_attn_bwd_walk<H, D, true, OWNED, DROP>(col, indptr, eid, indices, er, ee, V, P, dO, der, dV, nullptr,
-                                                  n_chunks, chunks_per_group, slope, dr);
-}
-
-// ---- generic kernels: fp32 / fp64, any h and d, any chunk layout; one wave per chunk -----------------------------
-// The stats table is initialised and finished by k_gat_attn_stats_{init,fin}_generic; max and sum arrive by atomics,
-// one per run of consecutive chunks of a row.
-template <typename T, bool SUM>
-__global__ __launch_bounds__(kGenericBlock) void k_gat_edge_attn_stats_generic(
-    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ eid,
-    const i64* __restrict__ indices, const T* __restrict__ el, const T* __restrict__ er, const T* __restrict__ ee,
-    T* __restrict__ stats, i64 n_chunks, i64 h, T slope) {
-  const i64 c = generic_chunk_id();
-  if (c >= n_chunks) return;
-  const int lane = threadIdx.x & 63;
-  const i64 r = row[c];
-  // A run of consecutive chunks of one row belongs to the wave of its first chunk: one atomic per (run, head).  A row
-  // whose chunks are consecutive (any sorted chunk list) is therefore summed in a fixed order, and its statistics are
-  // the same bit for bit from launch to launch; only a row scattered over several runs is added in arrival order.
-  if (c > 0 && row[c - 1] == r) return;   // wave-uniform
-  i64 c1 = c + 1;
-  while (c1 < n_chunks && row[c1] == r) ++c1;
-  const int hp = (h <= kWave && kWave % h == 0) ? (int)h : 1;
-  const int spw = kWave / hp;
-  for (i64 kb = 0; kb < h; kb += hp) {
-    const i64 k = kb + lane % hp;
-    const T a = el[r * h + k];
-    const T m = SUM ? stats[(r * h + k) * 2] : (T)0;
-    T acc = SUM ? (T)0 : (T)-1e9;
-    for (i64 cc = c; cc < c1; ++cc) {
-      const i64 j1 = indptr[cc + 1];
-      for (i64 j = indptr[cc] + lane / hp; j < j1; j += spw) {
-        const T z = gat_lrelu((a + er[indices[j] * h + k]) + ee[eid[j] * h + k], slope);
-        if constexpr (SUM) acc += exp_t(z - m);
-        else acc = z > acc ? z : acc;
-      }
-    }
-    for (int o = hp; o < kWave; o <<= 1) {
-      const T t = __shfl_xor(acc, o);
-      if constexpr (SUM) acc += t;
-      else acc = t > acc ? t : acc;
-    }
-    if (lane < hp) {
-      if constexpr (SUM) atomicAdd(stats + (r * h + k) * 2 + 1, acc);
-      else atomic_max_float(stats + (r * h + k) * 2, acc);
-    }
-  }
-}
-
-template <typename T, bool DROP>
-__global__ __launch_bounds__(kGenericBlock) void k_gat_edge_attn_fwd_generic(
-    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ eid,
-    const i64* __restrict__ indices, const T* __restrict__ el, const T* __restrict__ er, const T* __restrict__ ee,
-    const T* __restrict__ stats, const T* __restrict__ V, T* __restrict__ o, i64 n_chunks, i64 h, i64 d, T slope,
-    DropArgsIf<DROP, T> dr) {
-  const i64 c = generic_chunk_id();
-  if (c >= n_chunks) return;
-  const int lane = threadIdx.x & 63;
-  const i64 r = row[c];
-  const i64 j0 = indptr[c], j1 = indptr[c + 1];
-  if (j1 <= j0) return;
-  for (i64 it = lane; it < h * d; it += kWave) {
-    const i64 k = it / d;
-    const T a = el[r * h + k], m = stats[(r * h + k) * 2], il = stats[(r * h + k) * 2 + 1];
-    T acc = 0;
-    for (i64 j = j0; j < j1; ++j) {
-      const i64 src = indices[j];
-      T w = exp_t(gat_lrelu((a + er[src * h + k]) + ee[eid[j] * h + k], slope) - m) * il;
-      if constexpr (DROP) w *= drop_mult<T>(r, src, k, dr);
-      acc += w * V[src * h * d + it];
-    }
-    atomicAdd(o + r * h * d + it, acc);
-  }
-}
-
-// gat_attn_dz with the edge term: z = (el_i + er_j) + ee_e
-template <typename T>
-__device__ __forceinline__ T gat_edge_attn_dz(const T* __restrict__ p, T erj, T eej, const T* __restrict__ g,
-                                              const T* __restrict__ x, i64 d, T slope, T mult) {
-  const T z = (p[0] + erj) + eej;
-  const T a = exp_t(gat_lrelu(z, slope) - p[1]) * p[2];
-  T da = 0;
-  for (i64 t = 0; t < d; ++t) da += g[t] * x[t];
-  const T ds = a * (mult * da - p[3]);
-  return z > (T)0 ? ds : ds * slope;
-}
-
-template <typename T, bool DROP>
-__global__ __launch_bounds__(kGenericBlock) void k_gat_edge_attn_bwd_row_generic(
-    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ eid,
-    const i64* __restrict__ indices, const T* __restrict__ er, const T* __restrict__ ee, const T* __restrict__ V,
-    const T* __restrict__ P, const T* __restrict__ dO, T* __restrict__ del, T* __restrict__ dee, i64 n_chunks, i64 h,
-    i64 d, T slope, DropArgsIf<DROP, T> dr) {
-  const i64 c = generic_chunk_id();
-  if (c >= n_chunks) return;
-  const int lane = threadIdx.x & 63;
-  const i64 r = row[c];
-  const i64 j0 = indptr[c], j1 = indptr[c + 1];
-  if (j1 <= j0) return;
-  for (i64 k = 0; k < h; ++k) {
-    T acc = 0;
-    for (i64 j = j0 + lane; j < j1; j += kWave) {
-      const i64 src = indices[j], e = eid[j];
-      T mult = 1;
-      if constexpr (DROP) mult = drop_mult<T>(r, src, k, dr);
-      const T dz = gat_edge_attn_dz<T>(P + (r * h + k) * 4, er[src * h + k], ee[e * h + k], dO + (r * h + k) * d,
-                                       V + (src * h + k) * d, d, slope, mult);
-      if (dee) dee[e * h + k] = dz;
-      acc += dz;
-    }
-    acc = wave_sum(acc);
-    if (lane == 0) atomicAdd(del + r * h + k, acc);
-  }
-}
-
-template <typename T, bool DROP>
-__global__ __launch_bounds__(kGenericBlock) void k_gat_edge_attn_bwd_col_generic(
-    const i64* __restrict__ col, const i64* __restrict__ indptr, const i64* __restrict__ eid,
-    const i64* __restrict__ indices, const T* __restrict__ er, const T* __restrict__ ee, const T* __restrict__ V,
-    const T* __restrict__ P, const T* __restrict__ dO, T* __restrict__ der, T* __restrict__ dV, i64 n_chunks, i64 h,
-    i64 d, T slope, DropArgsIf<DROP, T> dr) {
-  const i64 c = generic_chunk_id();
-  if (c >= n_chunks) return;
-  const int lane = threadIdx.x & 63;
-  const i64 jc = col[c];
-  const i64 j0 = indptr[c], j1 = indptr[c + 1];
-  if (j1 <= j0) return;
-  for (i64 k = 0; k < h; ++k) {   // der: lanes over slots
-    T acc = 0;
-    for (i64 j = j0 + lane; j < j1; j += kWave) {
-      const i64 i = indices[j];
-      T mult = 1;
-      if constexpr (DROP) mult = drop_mult<T>(i, jc, k, dr);
-      acc += gat_edge_attn_dz<T>(P + (i * h + k) * 4, er[jc * h + k], ee[eid[j] * h + k], dO + (i * h + k) * d,
-                                 V + (jc * h + k) * d, d, slope, mult);
-    }
-    acc = wave_sum(acc);
-    if (lane == 0) atomicAdd(der + jc * h + k, acc);
-  }
-  for (i64 it = lane; it < h * d; it += kWave) {   // dV: lanes over the row's values
-    const i64 k = it / d;
-    T acc = 0;
-    for (i64 j = j0; j < j1; ++j) {
-      const i64 i = indices[j];
-      const T* p = P + (i * h + k) * 4;
-      T a = exp_t(gat_lrelu((p[0] + er[jc * h + k]) + ee[eid[j] * h + k], slope) - p[1]) * p[2];
-      if constexpr (DROP) a *= drop_mult<T>(i, jc, k, dr);
-      acc += a * dO[i * h * d + it];
-    }
-    atomicAdd(dV + jc * h * d + it, acc);
-  }
-}
+#define GA_EDGE 1
+#define GA_KERNEL(pass, kind) k_gat_edge_attn_##pass##_##kind
+#define GA_FN(name) gat_edge_attn_##name
+#include "kernels_gat_attn_passes.inc"
+#undef GA_EDGE
+#undef GA_KERNEL
+#undef GA_FN
 
 }  // namespace graphop
