@@ -41,10 +41,24 @@ def permute_edge_ids(g, seed):
     (eid_r = arange(E), the eid_identity plans)."""
     if seed is None:
         return g, g.src, g.dst
-    perm = torch.randperm(g.n_edges, generator=torch.Generator().manual_seed(seed))
+    return renumber_edge_ids(g, torch.randperm(g.n_edges, generator=torch.Generator().manual_seed(seed)))
+
+
+def renumber_edge_ids(g, perm):
+    """-> (g', src, dst) as permute_edge_ids, for a given permutation: edge e of g is edge perm[e] of g'"""
     src, dst = torch.empty_like(g.src), torch.empty_like(g.dst)
-    src[perm], dst[perm] = g.src, g.dst           # edge e of g is edge perm[e] of g'
+    src[perm], dst[perm] = g.src, g.dst
     return dataclasses.replace(g, eid_r=perm[g.eid_r], eid_c=perm[g.eid_c]), src, dst
+
+
+def column_identity_edge_ids(g):
+    """-> (g', src, dst): the edges numbered in column-major slot order, eid_c' == arange(E), so that the plan of the
+    COLUMN-major arrays says eid_identity and the row-major ids are a non-trivial permutation (the inverse of eid_c)."""
+    perm = torch.empty_like(g.eid_c)
+    perm[g.eid_c] = torch.arange(g.n_edges, dtype=g.eid_c.dtype)
+    out = renumber_edge_ids(g, perm)
+    assert torch.equal(out[0].eid_c, torch.arange(g.n_edges)) and not torch.equal(out[0].eid_r, torch.arange(g.n_edges))
+    return out
 
 
 def hub_row(src):

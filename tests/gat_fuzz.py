@@ -240,21 +240,31 @@ def as_view(t, view):
     return v
 
 
-def build(case, n_cu):
-    """The case's graph (large stratum: sized for n_cu compute units) and inputs."""
+def drawn_graph(case, n_cu):
+    """The graph of a case (of this battery or of gat_edge_fuzz): large stratum sized for n_cu compute units."""
     if case.large:
         g = profile_graph(int((case.target_cpg + 0.5) * _groups_wanted(n_cu, case.group)), seed=case.graph_seed)
         for C in (g.n_row_chunks, g.n_col_chunks):
             assert _cpg(C, n_cu, case.group, 16) == case.target_cpg and C % case.target_cpg != 0, (case, C)
-    else:
-        g = random_graph(case.n_src, case.n_dst, case.n_edges, seed=case.graph_seed, chunk_size=case.chunk_size,
-                         zero_rows=case.zero_rows, hub=case.hub or None)
-    csr = g.csr_args()
-    if case.shuffled:
-        gen = torch.Generator().manual_seed(case.input_seed)
-        pr = reorder_chunks_vectorised(g.ptr_r, g.row, g.eid_r, g.indices_r, torch.randperm(g.n_row_chunks, generator=gen))
-        pc = reorder_chunks_vectorised(g.ptr_c, g.col, g.eid_c, g.indices_c, torch.randperm(g.n_col_chunks, generator=gen))
-        csr = (pr[1], pr[0], pr[2], pr[3], pc[1], pc[0], pc[2], pc[3])
+        return g
+    return random_graph(case.n_src, case.n_dst, case.n_edges, seed=case.graph_seed, chunk_size=case.chunk_size,
+                        zero_rows=case.zero_rows, hub=case.hub or None)
+
+
+def chunk_lists(case, g):
+    """The eight index arrays the ops get: g's, with the chunk lists of both orientations in random order if drawn so."""
+    if not case.shuffled:
+        return g.csr_args()
+    gen = torch.Generator().manual_seed(case.input_seed)
+    pr = reorder_chunks_vectorised(g.ptr_r, g.row, g.eid_r, g.indices_r, torch.randperm(g.n_row_chunks, generator=gen))
+    pc = reorder_chunks_vectorised(g.ptr_c, g.col, g.eid_c, g.indices_c, torch.randperm(g.n_col_chunks, generator=gen))
+    return (pr[1], pr[0], pr[2], pr[3], pc[1], pc[0], pc[2], pc[3])
+
+
+def build(case, n_cu):
+    """The case's graph (large stratum: sized for n_cu compute units) and inputs."""
+    g = drawn_graph(case, n_cu)
+    csr = chunk_lists(case, g)
     dt = case.torch_dtype
     if case.family == "gat_scores":
         *tables, grad = _gat_inputs(g, case.h, case.input_seed)

@@ -5,7 +5,10 @@ functions.FusedGATEdgeAttention and functions.fused_gat_edge_attention_step agai
 Every graph gets permuted edge ids (gat_edge_reference.permute_edge_ids), so a kernel that indexes ee or dee by slot
 instead of by eid fails; the cases named "identity ids" run the unpermuted graph, where the row-major passes skip the
 eid read.  Bounds (none new): rtol 1e-4 / atol 1e-5 for fp32 against float64, 1e-10 for fp64, on o, del, der, dee, dV;
-test_gat_edge_host.py shows that torch's own fp32 evaluation of the reference on these inputs uses less than half."""
+test_gat_edge_host.py shows that torch's own fp32 evaluation of the reference on these inputs uses less than half.
+Section 12 pins the paths that exist only with the edge term and that a random draw cannot: a NULL eid in the column
+pass, the skipped zero fill of dee, the alignment rule of ee / dee, and the stats kernel at both group widths.  The
+randomised battery of the op is tests/gat_edge_fuzz.py (test_gat_edge_fuzz.py)."""
 import pytest
 import torch
 
@@ -103,28 +106,31 @@ def test_edge_slopes_ties_and_large_scores(dev, slope):
 
 
 # ---- 3. fast against generic and composed, by kernel name ------------------------------------------------------------
-def _c_abi(l, g, dev, h, d, t, planned, drop=(0.0, 0, 0)):
-    """forward + backward through ctypes, with the graph's plans or plan = NULL -> ([o, del, der, dee, dV], names)"""
-    P, F32 = _lib.ptr, _lib.F32
+def _c_abi(l, g, dev, h, d, t, planned, drop=(0.0, 0, 0), d_ee=None):
+    """forward + backward through ctypes -> ([o, del, der, dee, dV], names).  planned: True (the graph's plans), False
+    (plan = NULL) or a pair (row-major plan?, column-major plan?).  The dtype is el's; d_ee, if given, is the buffer
+    the backward writes dee into, as the caller filled and placed it."""
+    P = _lib.ptr
     el, er, ee, V, dO = t
     a8 = g.csr_args()
-    hr = hc = None
-    if planned:
-        hr = _lib.get_plan(g.row, g.ptr_r, g.eid_r, g.indices_r, g.n_dst).handle
-        hc = _lib.get_plan(g.col, g.ptr_c, g.eid_c, g.indices_c, g.n_src).handle
+    use_r, use_c = planned if isinstance(planned, tuple) else (planned, planned)
+    hr = _lib.get_plan(g.row, g.ptr_r, g.eid_r, g.indices_r, g.n_dst).handle if use_r else None
+    hc = _lib.get_plan(g.col, g.ptr_c, g.eid_c, g.indices_c, g.n_src).handle if use_c else None
+    code = _lib.dtype_code(el)
 
     def go():
-        o, stats = torch.empty_like(dO), torch.empty((g.n_src, h, 2), device=dev)
+        o, stats = torch.empty_like(dO), torch.empty((g.n_src, h, 2), dtype=el.dtype, device=dev)
         _lib.check(l.graphop_gat_edge_attention_forward(
-            F32, *(P(x) for x in a8[:4]), P(el), P(er), P(ee), P(V), P(o), P(stats), g.n_row_chunks, g.n_edges, g.n_src,
+            code, *(P(x) for x in a8[:4]), P(el), P(er), P(ee), P(V), P(o), P(stats), g.n_row_chunks, g.n_edges, g.n_src,
             g.n_dst, h, d, 0.2, *drop, hr, _lib.stream_of(el)))
-        d_el, d_er, d_ee, dV = (torch.empty_like(x) for x in (el, er, ee, V))
-        ws = torch.empty(g.n_src * h * 4, device=dev)
+        d_el, d_er, dV = (torch.empty_like(x) for x in (el, er, V))
+        dee = torch.empty_like(ee) if d_ee is None else d_ee
+        ws = torch.empty(g.n_src * h * 4, dtype=el.dtype, device=dev)
         _lib.check(l.graphop_gat_edge_attention_backward(
-            F32, *(P(x) for x in a8), P(el), P(er), P(ee), P(V), P(o), P(stats), P(dO), P(d_el), P(d_er), P(d_ee),
-            P(dV), P(ws), ws.numel() * 4, g.n_row_chunks, g.n_col_chunks, g.n_edges, g.n_src, g.n_dst, h, d, 0.2,
-            *drop, hr, hc, _lib.stream_of(el)))
-        return [o, d_el, d_er, d_ee, dV]
+            code, *(P(x) for x in a8), P(el), P(er), P(ee), P(V), P(o), P(stats), P(dO), P(d_el), P(d_er), P(dee),
+            P(dV), P(ws), ws.numel() * ws.element_size(), g.n_row_chunks, g.n_col_chunks, g.n_edges, g.n_src, g.n_dst,
+            h, d, 0.2, *drop, hr, hc, _lib.stream_of(el)))
+        return [o, d_el, d_er, dee, dV]
     return _profiled(go)
 
 
@@ -440,3 +446,168 @@ def test_edge_keeps_no_edge_sized_tensor_but_dee(dev):
     assert fused < 1.5 * one, (fused, one)
     assert fixed < 0.5 * one, (fixed, one)
     assert composed > 3 * one, (composed, one)
+
+
+# ---- 12. paths that exist only with the edge term ------------------------------------------------------------------------
+def _tol(dtype, p=0.0):
+    """the module's bounds; with dropout atol / (1 - p), as gat_fuzz.bounds (the kept weights are scaled by 1 / (1 - p))"""
+    return dict(E.TOL64) if dtype == torch.float64 else dict(rtol=E.TOL32["rtol"], atol=E.TOL32["atol"] / (1 - p))
+
+
+def _inside(got, want, dtype, what, p=0.0):
+    tol = _tol(dtype, p)
+    print("%s: %.3f of the bound" % (what, E.worst_ratio([x.cpu() for x in got], want, tol)))
+    for name, x, y in zip(E.NAMES, got, want):
+        assert x.dtype == dtype and x.shape == y.shape, (what, name, x.shape, y.shape)
+        torch.testing.assert_close(x.cpu().double(), y, **tol, msg=lambda m: "%s %s: %s" % (what, name, m))
+
+
+def _names(fast, dropped):
+    tags, kernels = (DROP_TAGS, DROP_FAST) if dropped else (TAGS, FAST)
+    return dict(zip(tags, kernels if fast else (k.replace("_f32", "_generic") for k in kernels)))
+
+
+@pytest.mark.parametrize("hd,dtype", [((1, 64), torch.float32), ((8, 8), torch.float32), ((4, 32), torch.float32),
+                                      ((3, 5), torch.float64)])
+def test_edge_column_major_identity_ids(dev, hd, dtype):
+    """The edges numbered in column-major slot order: eid_c == arange(E), so the COLUMN plan says eid_identity and
+    k_gat_edge_attn_bwd_col_f32 runs with eid == NULL (its my_e = j branch), while the row-major passes read a
+    non-trivial eid_r.  p = 0 and p = 0.3; a fifth of the rows empty, a hub row above 1024 slots."""
+    h, d = hd
+    g0, src, dst = E.column_identity_edge_ids(E.HUB_GRAPH[32]())
+    g = g0.to(dev)
+    plan_r = _lib.get_plan(g.row, g.ptr_r, g.eid_r, g.indices_r, g.n_dst)
+    plan_c = _lib.get_plan(g.col, g.ptr_c, g.eid_c, g.indices_c, g.n_src)
+    assert plan_c.info.eid_identity and not plan_r.info.eid_identity
+    inp = E.inputs(src, dst, g.n_src, g.n_dst, h, d, dtype, seed=h * 10 + d)
+    for drop in (None, E.DROP):
+        (got, _), names = _profiled(lambda: _run(g.csr_args(), dev, inp, 0.2, drop))
+        assert names == _names(dtype == torch.float32, drop is not None), names
+        want = E.reference(src, dst, g.n_src, *inp, 0.2, *(drop or (0.0, 0, 0)))
+        _inside(got, want, dtype, "column identity %s p=%g" % (hd, drop[0] if drop else 0))
+
+
+@pytest.mark.parametrize("p", [0.0, 0.9])
+def test_edge_dee_is_fully_written_where_the_fill_is_skipped(dev, p):
+    """The unpermuted hub graph: full_coverage, eid_identity and indptr_monotone, so the backward skips the zero fill of
+    dee and every edge id must be written by the row pass, dropped slots and the padded tail of a batch included.  dee
+    is handed in full of NaN (the marker of an unwritten element) through the C ABI: (4, 16) on the fast kernels, with
+    force_generic, and in fp64; then with plan_r = NULL on the same arrays, where the fill happens."""
+    h, d = 4, 16
+    g0 = E.HUB_GRAPH[32]()
+    g = g0.to(dev)
+    lens = torch.bincount(g0.src, minlength=g0.n_src)
+    assert int((lens == 0).sum()) > 30 and int(lens.max()) > 1024
+    info = _lib.get_plan(g.row, g.ptr_r, g.eid_r, g.indices_r, g.n_dst).info
+    assert info.full_coverage and info.eid_identity and info.indptr_monotone
+    drop = (p, E.DROP[1], E.DROP[2]) if p else (0.0, 0, 0)
+    inp64 = E.inputs(g0.src, g0.dst, g.n_src, g.n_dst, h, d, torch.float64, seed=3)
+    want = E.reference(g0.src, g0.dst, g.n_src, *inp64, 0.2, *drop)
+    l = _lib.lib()
+    try:
+        for what, dtype, planned, force, fast in (("fast", torch.float32, True, 0, True),
+                                                  ("force_generic", torch.float32, True, 1, False),
+                                                  ("fp64", torch.float64, True, 0, False),
+                                                  ("plan_r NULL", torch.float32, (False, True), 0, None)):
+            _lib.tune("force_generic", force)
+            t = [x.to(dtype).to(dev) for x in inp64]
+            d_ee = torch.full_like(t[2], float("nan"))
+            got, names = _c_abi(l, g, dev, h, d, t, planned, drop, d_ee=d_ee)
+            if fast is None:       # only the column plan: pack and the column pass fast, the rest generic
+                expect = _names(False, p > 0)
+                for tag in ("gat_edge_attn_pack", (DROP_TAGS if p else TAGS)[4]):
+                    expect[tag] = _names(True, p > 0)[tag]
+            else:
+                expect = _names(fast, p > 0)
+            assert names == expect, (what, names)
+            assert got[3] is d_ee and not bool(torch.isnan(d_ee).any()), "%s: dee keeps unwritten elements" % what
+            _inside(got, want, dtype, "dee fill %s p=%g" % (what, p), p)
+    finally:
+        _lib.tune_reset()
+
+
+@pytest.mark.parametrize("hd", [(1, 64), (2, 32), (4, 16)])
+def test_edge_misaligned_ee_and_dee(dev, hd):
+    """ee 4 bytes off a 16-byte boundary: the fast kernels read it in items of 4 * min(h, 4) bytes, so h = 1 stays on the
+    five fast kernels and h = 2, 4 fall to the generic ones.  At (4, 16) also dee 4 bytes off, which only the C ABI can
+    produce: a fast forward, then the backward's three passes generic."""
+    h, d = hd
+    g0, src, dst = E.permute_edge_ids(E.BIND_GRAPH(), 23)
+    g = g0.to(dev)
+    inp = E.inputs(src, dst, g.n_src, g.n_dst, h, d, torch.float32, seed=7 + h)
+    want = E.reference(src, dst, g.n_src, *inp, 0.2)
+    el, er, ee, V, dO = (x.to(dev) for x in inp)
+    ee_off = LG._shifted(ee)
+    assert ee_off.data_ptr() % 16 == 4
+    (got, _), names = _profiled(lambda: _run(g.csr_args(), dev, [el, er, ee_off, V, dO], 0.2))
+    assert names == _names(h == 1, False), names
+    _inside(got, want, torch.float32, "ee off %s" % (hd,))
+    if hd == (4, 16):
+        d_ee = LG._shifted(torch.empty_like(ee))
+        got, names = _c_abi(_lib.lib(), g, dev, h, d, [el, er, ee, V, dO], True, d_ee=d_ee)
+        expect = _names(False, False)
+        expect["gat_edge_attn_stats"], expect["gat_edge_attn_fwd"] = FAST[0], FAST[1]
+        assert names == expect, names
+        _inside(got, want, torch.float32, "dee off %s" % (hd,))
+
+
+WIDE_ROWS = (1, 63, 64, 65, 127, 128, 129, 200, 1024, 1025)       # around gw and 2 gw for G = 64, and kLongSegment
+NARROW_ROWS = (1, 15, 16, 17, 31, 32, 33, 47, 48, 49)            # the same for G = 16
+
+
+def _stats_graph(kind):
+    """(g', src, dst): rows of exactly WIDE_ROWS and 24 rows of 100-300 slots, or of NARROW_ROWS and 60 rows of 1-8
+    slots, with three empty rows, in random order; whole rows (graph_from_coo), permuted edge ids"""
+    key = ("stats", kind)
+    if key not in E._GRAPHS:
+        gen = torch.Generator().manual_seed(len(kind))
+        if kind == "wide":
+            lens = torch.cat([torch.tensor(WIDE_ROWS), torch.randint(100, 301, (24,), generator=gen)])
+        else:
+            lens = torch.cat([torch.tensor(NARROW_ROWS), torch.randint(1, 9, (60,), generator=gen)])
+        lens = torch.cat([lens, torch.zeros(3, dtype=torch.int64)])
+        E._GRAPHS[key] = E.permute_edge_ids(LG._from_lengths(lens[torch.randperm(len(lens), generator=gen)], gen, 32), 53)
+    return E._GRAPHS[key]
+
+
+@pytest.mark.parametrize("hd", [(1, 64), (2, 32), (8, 16)])
+@pytest.mark.parametrize("graph,kind", [("wide", "unit"), ("wide", "large"), ("narrow", "unit")])
+def test_edge_stats_kernel_at_both_group_widths(dev, graph, kind, hd):
+    """k_gat_edge_attn_stats_f32<H, 64> (n_edges / n_segments >= 64, one row above kLongSegment for the workgroup form)
+    and <H, 16>, at row lengths around gw and 2 gw, where the two-gathers-in-flight loop ends and the tail begins.
+    stats = (m, 1 / l) per (row, head): m is the maximum of the fp32 scores, one of them, so it is compared exactly
+    with the fp32 scores computed on the CPU; 1 / l at rtol 1e-5 against the float64 sum of exp(s - m).  The "large"
+    kind puts |z| ~ 65 on a few rows: a missed row maximum would overflow.  Then the five outputs."""
+    h, d = hd
+    g0, src, dst = _stats_graph(graph)
+    g = g0.to(dev)
+    lens = torch.bincount(src, minlength=g0.n_src)
+    assert set(WIDE_ROWS if graph == "wide" else NARROW_ROWS) <= set(lens.tolist())
+    info = _lib.get_plan(g.row, g.ptr_r, g.eid_r, g.indices_r, g.n_dst).info
+    assert info.row_owned and not info.eid_identity and info.n_segments == int((lens > 0).sum())
+    if graph == "wide":
+        assert info.n_edges // info.n_segments >= 64 and info.max_segment_len == 1025, (info.n_edges, info.n_segments)
+    else:
+        assert info.n_edges // info.n_segments < 64 and info.max_segment_len == 49, (info.n_edges, info.n_segments)
+    inp = E.inputs(src, dst, g.n_src, g.n_dst, h, d, torch.float32, seed=h + d, kind=kind)
+    el, er, ee = (x.reshape(-1, h) for x in inp[:3])
+    z32 = (el[src] + er[dst]) + ee
+    if kind == "large":
+        assert z32.abs().max() > 60
+    s32 = torch.nn.functional.leaky_relu(z32, 0.2)
+    s64 = torch.nn.functional.leaky_relu((el.double()[src] + er.double()[dst]) + ee.double(), 0.2)
+    idx = src[:, None].expand(-1, h)
+    m = torch.full((g.n_src, h), -1e9).scatter_reduce(0, idx, s32, "amax")
+    den = torch.zeros((g.n_src, h), dtype=torch.float64).index_add(0, src, torch.exp(s64 - m.double()[src]))
+    (got, stats), names = _profiled(lambda: _run(g.csr_args(), dev, inp, 0.2))
+    assert names == _names(True, False), names
+    stats = stats.cpu()
+    empty = lens == 0
+    assert stats.shape == (g.n_src, h, 2) and int(empty.sum()) == 3
+    assert bool((stats[empty][..., 0] == -1e9).all()) and not stats[empty][..., 1].any(), "empty rows moved"
+    assert torch.equal(stats[..., 0], m), "row maxima: %d differ" % int((stats[..., 0] != m).sum())
+    inv_l = 1.0 / den[~empty]
+    print("%s %s %s 1/l: %.3f of rtol 1e-5" % (graph, kind, hd, float(
+        ((stats[~empty][..., 1].double() - inv_l).abs() / (1e-5 * inv_l)).max())))
+    torch.testing.assert_close(stats[~empty][..., 1].double(), inv_l, rtol=1e-5, atol=0.0)
+    _inside(got, E.reference(src, dst, g.n_src, *inp, 0.2), torch.float32, "%s %s %s" % (graph, kind, hd))

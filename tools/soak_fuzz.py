@@ -5,6 +5,9 @@
                                                               # knobs); default 40 340
     python tools/soak_fuzz.py --gat [first_seed last_seed]    # tests/test_gat_fuzz.py::test_gat_family_fuzz (the GAT
                                                               # family, tests/gat_fuzz.py); default 48 348
+    python tools/soak_fuzz.py --gat-edge [first_seed last_seed]   # tests/test_gat_edge_fuzz.py::test_gat_edge_fuzz (the
+                                                              # fused GAT layer with an edge term,
+                                                              # tests/gat_edge_fuzz.py); default 24 174
 A seed that fails its assertions is counted and the run goes on.  Anything else a seed raises (a HIP error, a fault
 reported by the library) stops the run at that seed with exit status 2: nothing more is started on a device that may
 have faulted.  Exit status 1: some seed failed its assertions."""
@@ -13,11 +16,15 @@ sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "t
 import torch
 
 args = sys.argv[1:]
-gat = bool(args) and args[0] == "--gat"
-if gat:
+gat = bool(args) and args[0] in ("--gat", "--gat-edge")
+if gat and args[0] == "--gat-edge":
+    args = args[1:]
+    import test_gat_edge_fuzz as T
+    run, default, cases = T.test_gat_edge_fuzz, (24, 174), T.G.case_data
+elif gat:
     args = args[1:]
     import test_gat_fuzz as T
-    run, default = T.test_gat_family_fuzz, (48, 348)
+    run, default, cases = T.test_gat_family_fuzz, (48, 348), T.F.case_data
 else:
     import test_hip_parity as T
     run, default = T.test_fuzz_shapes_and_paths, (40, 340)
@@ -34,7 +41,7 @@ for seed in range(lo, hi):
         print("seed", seed, "RAISED", repr(e)[:600], "-- stopping, failures so far:", bad, flush=True)
         sys.exit(2)
     if gat:
-        T.F.case_data.cache_clear()      # (the suite keeps its 48 cases for the host tier; a soak run need not)
+        cases.cache_clear()      # (the suite keeps its cases for the host tier; a soak run need not)
     if seed % 50 == 0:
         print("seed", seed, "ok so far, failures:", bad, flush=True)
 print("done, failures:", bad)
