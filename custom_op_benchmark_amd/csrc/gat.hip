@@ -3,38 +3,14 @@
 //   backward: del / der by a row-major and a column-major pass (kernels_gat.h), no per-edge atomics.
 // Host-side dispatch only, in the style of the operator entry points of graphop_hip.hip: validation, zero fills with
 // the library's own fill kernel, and the choice between the fp32 fast kernels (with a plan of the same arrays) and the
-// generic kernels (fp64, other head counts, no plan).
+// generic kernels (fp64, other head counts, no plan).  The checks and the launch geometry are the family's, host_gat.h.
 #include "common.h"
 #include "host.h"
+#include "host_gat.h"
 #include "kernels_gat.h"
 
 namespace graphop {
 namespace {
-
-inline int gat_check(const char* fn, int dtype, i64 C, i64 C2, i64 E, i64 n_l, i64 n_r, i64 h) {
-  GO_TRY(check_async_error(false));   // a kernel of an earlier launch reported a failure: sticky until acknowledged
-  GO_CHECK_ARG(dtype == GRAPHOP_F32 || dtype == GRAPHOP_F64, "%s: dtype must be GRAPHOP_F32 or GRAPHOP_F64", fn);
-  GO_CHECK_ARG(C >= 0 && C2 >= 0 && E >= 0 && n_l >= 0 && n_r >= 0 && h >= 1,
-               "%s: negative size (n_chunks=%lld/%lld n_edges=%lld n_l=%lld n_r=%lld h=%lld)", fn, (long long)C,
-               (long long)C2, (long long)E, (long long)n_l, (long long)n_r, (long long)h);
-  return GRAPHOP_OK;
-}
-
-// A plan of these arrays bounds its row ids and neighbour ids: an operand with too few rows is an error here.
-inline int gat_check_plan(const char* fn, const graphop_plan* p, const char* seg_name, i64 n_seg, const char* idx_name,
-                          i64 n_idx) {
-  if (!p) return GRAPHOP_OK;
-  GO_CHECK_ARG(p->info.max_row < n_seg, "%s: row id %lld but %s has only %lld rows", fn, (long long)p->info.max_row,
-               seg_name, (long long)n_seg);
-  GO_CHECK_ARG(p->info.max_index < n_idx, "%s: neighbour id %lld but %s has only %lld rows", fn,
-               (long long)p->info.max_index, idx_name, (long long)n_idx);
-  return GRAPHOP_OK;
-}
-
-inline bool gat_aligned(const void* p, i64 h) {
-  const uintptr_t a = h >= 4 ? 16 : (uintptr_t)(4 * h);
-  return ((uintptr_t)p % a) == 0;
-}
 
 // fp32 fast kernels: H in {1, 2, 4, 8, 16}, ids that fit 32 bits, value arrays aligned to their item width
 inline bool gat_fast_ok(int dtype, i64 h, i64 E, i64 n_l, i64 n_r, const void* p0, const void* p1, const void* p2,
@@ -43,14 +19,6 @@ inline bool gat_fast_ok(int dtype, i64 h, i64 E, i64 n_l, i64 n_r, const void* p
   if (h != 1 && h != 2 && h != 4 && h != 8 && h != 16) return false;
   if (E >= 0x7fffffffLL || n_l >= 0x7fffffffLL || n_r >= 0x7fffffffLL) return false;
   return gat_aligned(p0, h) && gat_aligned(p1, h) && gat_aligned(p2, h) && (!p3 || gat_aligned(p3, h));
-}
-
-// chunks per lane group: the tuned cap on big graphs, fewer on small ones so every CU still gets groups
-inline int gat_cpg(i64 n_chunks, int cpg_max, int G) {
-  const i64 groups_wanted = (i64)tuning().n_cu * (kFastBlock / G) * 8;
-  i64 c = n_chunks / (groups_wanted > 0 ? groups_wanted : 1);
-  if (c < 1) c = 1;
-  return (int)(c < cpg_max ? c : cpg_max);
 }
 
 #define GO_DISPATCH_GAT_H(h, ...)                 \
@@ -73,7 +41,7 @@ int gat_bwd_pass(int dtype, const i64* seg, const i64* indptr, const i64* eid, c
     GO_DISPATCH_GAT_H(h, {
       constexpr int G = GatCfg<H>::G;
       const int cpg = gat_cpg(C, tuning().spmm_cpg, G);
-      const unsigned nb = (unsigned)ceil_div(ceil_div(C, cpg), kFastBlock / G);
+      const unsigned nb = (unsigned)gat_grid(C, cpg, G);
       if constexpr (ROW)
         hipLaunchKernelGGL((k_gat_bwd_row_f32<H>), dim3(nb), dim3(kFastBlock), 0, st, seg, indptr, eid, indices,
                            (const float*)el, (const float*)er, (const float*)dy, (float*)out, C, cpg, (float)slope);
@@ -127,7 +95,7 @@ int graphop_gat_scores_forward(int dtype, const int64_t* row, const int64_t* ind
     GO_DISPATCH_GAT_H(h, {
       constexpr int G = GatCfg<H>::G;
       const int cpg = gat_cpg(n_chunks, tuning().sddmm_cpg, G);
-      const unsigned nb = (unsigned)ceil_div(ceil_div(n_chunks, cpg), kFastBlock / G);
+      const unsigned nb = (unsigned)gat_grid(n_chunks, cpg, G);
       hipLaunchKernelGGL((k_gat_fwd_f32<H>), dim3(nb), dim3(kFastBlock), 0, st, (const i64*)row, (const i64*)indptr,
                          (const i64*)eid, (const i64*)indices, (const float*)el, (const float*)er, (float*)y, n_chunks,
                          cpg, (float)negative_slope);

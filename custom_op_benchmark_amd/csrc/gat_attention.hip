@@ -22,7 +22,7 @@ int graphop_gat_attention_forward(int dtype, const int64_t* row, const int64_t* 
                                   int64_t h, int64_t d, double negative_slope, const graphop_plan_t* plan,
                                   void* stream) {
   const char* fn = "gat_attention_forward";
-  GO_TRY(gat_attn_check(fn, dtype, n_chunks, 0, n_edges, n_l, n_r, h, d));
+  GO_TRY(gat_check(fn, dtype, n_chunks, 0, n_edges, n_l, n_r, h, d));
   return gat_attn_forward<false>(fn, dtype, row, indptr, eid, indices, el, er, nullptr, V, o, stats, n_chunks, n_edges,
                                  n_l, n_r, h, d, negative_slope, nullptr, plan, stream);
 }
@@ -36,7 +36,7 @@ int graphop_gat_attention_backward(int dtype, const int64_t* row, const int64_t*
                                    int64_t n_r, int64_t h, int64_t d, double negative_slope,
                                    const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream) {
   const char* fn = "gat_attention_backward";
-  GO_TRY(gat_attn_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_l, n_r, h, d));
+  GO_TRY(gat_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_l, n_r, h, d));
   return gat_attn_backward<false>(fn, dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er,
                                   nullptr, V, o, stats, dO, del, der, nullptr, dV, workspace, workspace_bytes,
                                   n_row_chunks, n_col_chunks, n_edges, n_l, n_r, h, d, negative_slope,
@@ -50,7 +50,7 @@ int graphop_gat_attention_dropout_forward(int dtype, const int64_t* row, const i
                                           int64_t n_r, int64_t h, int64_t d, double negative_slope, double p,
                                           uint64_t seed, uint32_t offset, const graphop_plan_t* plan, void* stream) {
   const char* fn = "gat_attention_dropout_forward";
-  GO_TRY(gat_attn_check(fn, dtype, n_chunks, 0, n_edges, n_l, n_r, h, d));
+  GO_TRY(gat_check(fn, dtype, n_chunks, 0, n_edges, n_l, n_r, h, d));
   HostDrop drop;
   GO_TRY(drop_check(fn, p, seed, n_l, n_r, offset, &drop));
   return gat_attn_forward<false>(fn, dtype, row, indptr, eid, indices, el, er, nullptr, V, o, stats, n_chunks, n_edges,
@@ -67,7 +67,7 @@ int graphop_gat_attention_dropout_backward(int dtype, const int64_t* row, const 
                                            int64_t d, double negative_slope, double p, uint64_t seed, uint32_t offset,
                                            const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream) {
   const char* fn = "gat_attention_dropout_backward";
-  GO_TRY(gat_attn_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_l, n_r, h, d));
+  GO_TRY(gat_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_l, n_r, h, d));
   HostDrop drop;
   GO_TRY(drop_check(fn, p, seed, n_l, n_r, offset, &drop));
   return gat_attn_backward<false>(fn, dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er,
@@ -81,7 +81,7 @@ int graphop_edge_dropout_mask(int dtype, const int64_t* row, const int64_t* indp
                               int64_t n_r, int64_t h, double p, uint64_t seed, uint32_t offset,
                               const graphop_plan_t* plan, void* stream) {
   const char* fn = "edge_dropout_mask";
-  GO_TRY(gat_attn_check(fn, dtype, n_chunks, 0, n_edges, n_l, n_r, h, 1));
+  GO_TRY(gat_check(fn, dtype, n_chunks, 0, n_edges, n_l, n_r, h, 1));
   HostDrop drop;
   GO_TRY(drop_check(fn, p, seed, n_l, n_r, offset, &drop));
   hipStream_t st = (hipStream_t)stream;
@@ -89,7 +89,7 @@ int graphop_edge_dropout_mask(int dtype, const int64_t* row, const int64_t* indp
   GO_PTR(fn, y);
   const graphop_plan* pm = plan_matches_full(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
                                              (const i64*)indices, n_chunks, n_edges) ? plan : nullptr;
-  GO_TRY(gat_attn_check_plan(fn, pm, "the row-major rows", n_l, "the neighbours", n_r));
+  GO_TRY(gat_check_plan(fn, pm, "the row-major rows", n_l, "the neighbours", n_r));
   const bool covered = pm && pm->info.full_coverage && pm->info.eid_identity && pm->info.indptr_monotone;
   if (!covered) GO_HIP(zero_async(y, esize(dtype) * (size_t)(n_edges * h), st));   // edges no slot names get m = 0
   if (n_chunks == 0) return GRAPHOP_OK;

@@ -19,7 +19,7 @@ int graphop_gat_edge_attention_forward(int dtype, const int64_t* row, const int6
                                        int64_t n_l, int64_t n_r, int64_t h, int64_t d, double negative_slope, double p,
                                        uint64_t seed, uint32_t offset, const graphop_plan_t* plan, void* stream) {
   const char* fn = "gat_edge_attention_forward";
-  GO_TRY(gat_attn_check(fn, dtype, n_chunks, 0, n_edges, n_l, n_r, h, d));
+  GO_TRY(gat_check(fn, dtype, n_chunks, 0, n_edges, n_l, n_r, h, d));
   HostDrop hd;
   GO_TRY(drop_check(fn, p, seed, n_l, n_r, offset, &hd));
   return gat_attn_forward<true>(fn, dtype, row, indptr, eid, indices, el, er, ee, V, o, stats, n_chunks, n_edges, n_l,
@@ -36,7 +36,7 @@ int graphop_gat_edge_attention_backward(int dtype, const int64_t* row, const int
                                         double negative_slope, double p, uint64_t seed, uint32_t offset,
                                         const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream) {
   const char* fn = "gat_edge_attention_backward";
-  GO_TRY(gat_attn_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_l, n_r, h, d));
+  GO_TRY(gat_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_l, n_r, h, d));
   HostDrop hd;
   GO_TRY(drop_check(fn, p, seed, n_l, n_r, offset, &hd));
   return gat_attn_backward<true>(fn, dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, ee,

@@ -4,85 +4,14 @@
 //             atomics and nothing E-sized besides y and dy.
 // Host-side dispatch only, in the style of gat.hip: validation, zero fills with the library's own fill kernel, and the
 // choice between the fp32 fast kernels (a plan of the same arrays, the (h, d) pairs of the fused GAT layer) and the
-// generic kernels (fp64, other shapes, no plan).
+// generic kernels (fp64, other shapes, no plan).  Checks, fast conditions, dispatch and launch geometry: host_gat.h.
 #include "common.h"
 #include "host.h"
+#include "host_gat.h"
 #include "kernels_gatv2.h"
 
 namespace graphop {
 namespace {
-
-constexpr int kGatv2Group = 16;            // lanes per group of the fast kernels
-constexpr i64 kGatv2MaxRowBlocks = 8192;   // workgroups of the fast row pass at most: bounds the datt partials
-
-inline int gatv2_check(const char* fn, int dtype, i64 C, i64 C2, i64 E, i64 n_l, i64 n_r, i64 h, i64 d) {
-  GO_TRY(check_async_error(false));   // a kernel of an earlier launch reported a failure: sticky until acknowledged
-  GO_CHECK_ARG(dtype == GRAPHOP_F32 || dtype == GRAPHOP_F64, "%s: dtype must be GRAPHOP_F32 or GRAPHOP_F64", fn);
-  GO_CHECK_ARG(C >= 0 && C2 >= 0 && E >= 0 && n_l >= 0 && n_r >= 0 && h >= 1 && d >= 1,
-               "%s: negative size (n_chunks=%lld/%lld n_edges=%lld n_l=%lld n_r=%lld h=%lld d=%lld)", fn,
-               (long long)C, (long long)C2, (long long)E, (long long)n_l, (long long)n_r, (long long)h, (long long)d);
-  return GRAPHOP_OK;
-}
-
-// A plan of these arrays bounds its row ids and neighbour ids: an operand with too few rows is an error here.
-inline int gatv2_check_plan(const char* fn, const graphop_plan* p, const char* seg_name, i64 n_seg,
-                            const char* idx_name, i64 n_idx) {
-  if (!p) return GRAPHOP_OK;
-  GO_CHECK_ARG(p->info.max_row < n_seg, "%s: row id %lld but %s has only %lld rows", fn, (long long)p->info.max_row,
-               seg_name, (long long)n_seg);
-  GO_CHECK_ARG(p->info.max_index < n_idx, "%s: neighbour id %lld but %s has only %lld rows", fn,
-               (long long)p->info.max_index, idx_name, (long long)n_idx);
-  return GRAPHOP_OK;
-}
-
-// fp32 fast kernels: the (h, d) pairs below, ids that fit 31 bits, 16-byte-aligned tables
-inline bool gatv2_fast_ok(int dtype, i64 h, i64 d, i64 E, i64 n_l, i64 n_r, std::initializer_list<const void*> ps) {
-  if (tuning().force_generic || dtype != GRAPHOP_F32) return false;
-  if (h != 1 && h != 2 && h != 4 && h != 8) return false;
-  if (d != 8 && d != 16 && d != 32 && d != 64) return false;
-  if (h * d != 64 && h * d != 128 && h * d != 256) return false;
-  if (E >= 0x7fffffffLL || n_l >= 0x7fffffffLL || n_r >= 0x7fffffffLL) return false;
-  for (const void* p : ps)
-    if (((uintptr_t)p & 15) != 0) return false;
-  return true;
-}
-
-#define GO_DISPATCH_GATV2(h, d, ...)                                    \
-  switch ((int)((h) * 1000 + (d))) {                                    \
-    case 1064: { constexpr int H = 1, D = 64; __VA_ARGS__; } break;     \
-    case 2032: { constexpr int H = 2, D = 32; __VA_ARGS__; } break;     \
-    case 2064: { constexpr int H = 2, D = 64; __VA_ARGS__; } break;     \
-    case 4016: { constexpr int H = 4, D = 16; __VA_ARGS__; } break;     \
-    case 4032: { constexpr int H = 4, D = 32; __VA_ARGS__; } break;     \
-    case 4064: { constexpr int H = 4, D = 64; __VA_ARGS__; } break;     \
-    case 8008: { constexpr int H = 8, D = 8; __VA_ARGS__; } break;      \
-    case 8016: { constexpr int H = 8, D = 16; __VA_ARGS__; } break;     \
-    case 8032: { constexpr int H = 8, D = 32; __VA_ARGS__; } break;     \
-    default: break;                                                     \
-  }
-
-// a run-time bool as the template argument NAME of the statement
-#define GO_DISPATCH_GATV2_BOOL(b, NAME, ...)             \
-  if (b) { constexpr bool NAME = true; __VA_ARGS__; }    \
-  else { constexpr bool NAME = false; __VA_ARGS__; }
-
-// chunks per lane group: up to the tuned cap on big graphs, fewer on small ones so every CU still gets groups
-inline int gatv2_cpg(i64 n_chunks, int cap) {
-  const i64 groups_wanted = (i64)tuning().n_cu * (kFastBlock / kGatv2Group) * 8;
-  i64 c = n_chunks / (groups_wanted > 0 ? groups_wanted : 1);
-  if (c < 1) c = 1;
-  if (cap < 1) cap = 1;
-  return (int)(c < cap ? c : cap);
-}
-
-// grid of a fast pass: lane groups of 16, cpg chunks each
-inline i64 gatv2_grid(i64 n_chunks, i64 cpg) { return ceil_div(ceil_div(n_chunks, cpg), (i64)(kFastBlock / kGatv2Group)); }
-
-// rows of datt partials the fast row pass may write (include/graphop_hip.h states this as the workspace minimum)
-inline i64 gatv2_part_rows(i64 n_row_chunks) {
-  const i64 b = ceil_div(n_row_chunks, (i64)(kFastBlock / kGatv2Group));
-  return b < kGatv2MaxRowBlocks ? b : kGatv2MaxRowBlocks;
-}
 
 // power of two that covers d, a wave at most: the lanes of one head in the generic forward
 inline int gatv2_dp(i64 d) { return d >= kWave ? kWave : (int)pow2ceil(d); }
@@ -99,23 +28,23 @@ int graphop_gatv2_scores_forward(int dtype, const int64_t* row, const int64_t* i
                                  int64_t n_chunks, int64_t n_edges, int64_t n_l, int64_t n_r, int64_t h, int64_t d,
                                  double negative_slope, const graphop_plan_t* plan, void* stream) {
   const char* fn = "gatv2_scores_forward";
-  GO_TRY(gatv2_check(fn, dtype, n_chunks, 0, n_edges, n_l, n_r, h, d));
+  GO_TRY(gat_check(fn, dtype, n_chunks, 0, n_edges, n_l, n_r, h, d));
   hipStream_t st = (hipStream_t)stream;
   if (n_edges == 0) return GRAPHOP_OK;
   GO_PTR(fn, y);
   const graphop_plan* pm = plan_matches_full(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
                                              (const i64*)indices, n_chunks, n_edges) ? plan : nullptr;
-  GO_TRY(gatv2_check_plan(fn, pm, "xl", n_l, "xr", n_r));
+  GO_TRY(gat_check_plan(fn, pm, "xl", n_l, "xr", n_r));
   const bool covered = pm && pm->info.full_coverage && pm->info.eid_identity && pm->info.indptr_monotone;
   if (!covered) GO_HIP(zero_async(y, esize(dtype) * (size_t)(n_edges * h), st));
   if (n_chunks == 0) return GRAPHOP_OK;
   GO_PTR(fn, row); GO_PTR(fn, indptr); GO_PTR(fn, eid); GO_PTR(fn, indices); GO_PTR(fn, xl); GO_PTR(fn, xr);
   GO_PTR(fn, att);
-  if (pm && gatv2_fast_ok(dtype, h, d, n_edges, n_l, n_r, {xl, xr, att})) {
+  if (pm && gat_hd_fast_ok(dtype, h, d, n_edges, n_l, n_r, {xl, xr, att})) {
     ProfScope prof("gatv2_fwd", st, "k_gatv2_fwd_f32");
-    const int cpg = gatv2_cpg(n_chunks, tuning().sddmm_cpg);
-    GO_DISPATCH_GATV2(h, d, {
-      hipLaunchKernelGGL((k_gatv2_fwd_f32<H, D>), dim3((unsigned)gatv2_grid(n_chunks, cpg)), dim3(kFastBlock), 0, st,
+    const int cpg = gat_cpg(n_chunks, tuning().sddmm_cpg);
+    GO_DISPATCH_GAT_HD(h, d, {
+      hipLaunchKernelGGL((k_gatv2_fwd_f32<H, D>), dim3((unsigned)gat_grid(n_chunks, cpg)), dim3(kFastBlock), 0, st,
                          (const i64*)row, (const i64*)indptr, (const i64*)eid, (const i64*)indices, (const float*)xl,
                          (const float*)xr, (const float*)att, (float*)y, n_chunks, cpg, (float)negative_slope);
     });
@@ -143,37 +72,19 @@ int graphop_gatv2_scores_backward(int dtype, const int64_t* row, const int64_t* 
                                   double negative_slope, const graphop_plan_t* plan_r, const graphop_plan_t* plan_c,
                                   void* stream) {
   const char* fn = "gatv2_scores_backward";
-  GO_TRY(gatv2_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_l, n_r, h, d));
+  GO_TRY(gat_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_l, n_r, h, d));
   hipStream_t st = (hipStream_t)stream;
   const size_t es = esize(dtype);
   const i64 f = h * d;
   const bool row_slots = n_edges > 0 && n_row_chunks > 0 && n_l > 0 && n_r > 0;
   const bool col_slots = n_edges > 0 && n_col_chunks > 0 && n_l > 0 && n_r > 0;
-  const size_t need = row_slots ? es * (size_t)(gatv2_part_rows(n_row_chunks) * f) : 0;   // datt partials
+  const size_t need = row_slots ? es * (size_t)(gat_part_rows(n_row_chunks) * f) : 0;   // datt partials
   GO_CHECK_ARG(workspace_bytes >= 0 && (size_t)workspace_bytes >= need,
                "%s: workspace of %lld bytes needed (min(ceil(n_row_chunks / 16), 8192) * h * d values), got %lld", fn,
                (long long)need, (long long)workspace_bytes);
-  const graphop_plan* pr = plan_matches_full(plan_r, (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r,
-                                             (const i64*)indices_r, n_row_chunks, n_edges) ? plan_r : nullptr;
-  const graphop_plan* pc = plan_matches_full(plan_c, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c,
-                                             (const i64*)indices_c, n_col_chunks, n_edges) ? plan_c : nullptr;
-  GO_TRY(gatv2_check_plan(fn, pr, "xl / dxl", n_l, "xr", n_r));
-  GO_TRY(gatv2_check_plan(fn, pc, "xr / dxr", n_r, "xl", n_l));
-  // the outputs of an orientation without chunks may be NULL: that half of the op is skipped
-  const bool row_half = !(dxl == nullptr && datt == nullptr && n_row_chunks == 0);
-  const bool col_half = !(dxr == nullptr && n_col_chunks == 0);
-  if (row_half) {
-    if (n_l > 0) {
-      GO_PTR(fn, dxl);
-      GO_HIP(zero_async(dxl, es * (size_t)(n_l * f), st));
-    }
-    GO_PTR(fn, datt);
-    GO_HIP(zero_async(datt, es * (size_t)f, st));
-  }
-  if (col_half && n_r > 0) {
-    GO_PTR(fn, dxr);
-    GO_HIP(zero_async(dxr, es * (size_t)(n_r * f), st));
-  }
+  const graphop_plan *pr, *pc;
+  GO_TRY(gatv2_bwd_open(fn, dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, dxl, dxr, datt,
+                        n_row_chunks, n_col_chunks, n_edges, n_l, n_r, f, plan_r, plan_c, st, &pr, &pc));
   if (!row_slots && !col_slots) return GRAPHOP_OK;
   GO_PTR(fn, xl); GO_PTR(fn, xr); GO_PTR(fn, att); GO_PTR(fn, dy);
   if (need > 0) GO_PTR(fn, workspace);
@@ -181,21 +92,19 @@ int graphop_gatv2_scores_backward(int dtype, const int64_t* row, const int64_t* 
     GO_PTR(fn, row); GO_PTR(fn, indptr_r); GO_PTR(fn, eid_r); GO_PTR(fn, indices_r);
     GO_PTR(fn, dxl); GO_PTR(fn, datt);
     const i64 C = n_row_chunks;
-    if (pr && gatv2_fast_ok(dtype, h, d, n_edges, n_l, n_r, {xl, xr, att, dxl, datt, workspace})) {
+    if (pr && gat_hd_fast_ok(dtype, h, d, n_edges, n_l, n_r, {xl, xr, att, dxl, datt, workspace})) {
       ProfScope prof("gatv2_bwd_row", st, "k_gatv2_bwd_row_f32");
-      i64 cpg = gatv2_cpg(C, tuning().spmm_cpg);
-      if (gatv2_grid(C, cpg) > kGatv2MaxRowBlocks) cpg = ceil_div(C, kGatv2MaxRowBlocks * (kFastBlock / kGatv2Group));
-      const i64 nb = gatv2_grid(C, cpg);   // <= gatv2_part_rows(C): cpg >= 1 and the cap above
+      const GatRowPass geo = gat_row_pass(C, tuning().spmm_cpg);   // n_blocks <= gat_part_rows(C)
       const bool owned = pr->info.rows_sorted != 0;
-      GO_DISPATCH_GATV2(h, d, GO_DISPATCH_GATV2_BOOL(owned, OWNED, {
-        hipLaunchKernelGGL((k_gatv2_bwd_row_f32<H, D, OWNED>), dim3((unsigned)nb), dim3(kFastBlock), 0, st,
+      GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, {
+        hipLaunchKernelGGL((k_gatv2_bwd_row_f32<H, D, OWNED>), dim3((unsigned)geo.n_blocks), dim3(kFastBlock), 0, st,
                            (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r, (const i64*)indices_r,
                            (const float*)xl, (const float*)xr, (const float*)att, (const float*)dy, (float*)dxl,
-                           (float4*)workspace, C, (int)cpg, (float)negative_slope);
+                           (float4*)workspace, C, geo.cpg, (float)negative_slope);
       }));
       GO_LAUNCH_CHECK();
       hipLaunchKernelGGL(k_gatv2_datt_fin_f32, dim3((unsigned)(f / 4)), dim3(kFastBlock), 0, st,
-                         (const float4*)workspace, (float4*)datt, nb, (int)(f / 4));
+                         (const float4*)workspace, (float4*)datt, geo.n_blocks, (int)(f / 4));
     } else {
       ProfScope prof("gatv2_bwd_row", st, "k_gatv2_bwd_row_generic");
       const unsigned nb = (unsigned)ceil_div(C, kGenericWavesPerBlock);
@@ -213,12 +122,12 @@ int graphop_gatv2_scores_backward(int dtype, const int64_t* row, const int64_t* 
     GO_PTR(fn, col); GO_PTR(fn, indptr_c); GO_PTR(fn, eid_c); GO_PTR(fn, indices_c);
     GO_PTR(fn, dxr);
     const i64 C = n_col_chunks;
-    if (pc && gatv2_fast_ok(dtype, h, d, n_edges, n_l, n_r, {xl, xr, att, dxr})) {
+    if (pc && gat_hd_fast_ok(dtype, h, d, n_edges, n_l, n_r, {xl, xr, att, dxr})) {
       ProfScope prof("gatv2_bwd_col", st, "k_gatv2_bwd_col_f32");
-      const int cpg = gatv2_cpg(C, tuning().spmm_cpg);
+      const int cpg = gat_cpg(C, tuning().spmm_cpg);
       const bool owned = pc->info.rows_sorted != 0;
-      GO_DISPATCH_GATV2(h, d, GO_DISPATCH_GATV2_BOOL(owned, OWNED, {
-        hipLaunchKernelGGL((k_gatv2_bwd_col_f32<H, D, OWNED>), dim3((unsigned)gatv2_grid(C, cpg)), dim3(kFastBlock), 0,
+      GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, {
+        hipLaunchKernelGGL((k_gatv2_bwd_col_f32<H, D, OWNED>), dim3((unsigned)gat_grid(C, cpg)), dim3(kFastBlock), 0,
                            st, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c, (const i64*)indices_c,
                            (const float*)xl, (const float*)xr, (const float*)att, (const float*)dy, (float*)dxr, C, cpg,
                            (float)negative_slope);

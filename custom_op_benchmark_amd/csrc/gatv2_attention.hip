@@ -4,113 +4,36 @@
 // No E-sized tensor exists in either direction.  Host-side dispatch in the style of gatv2.hip and gat_attention.hip:
 // validation, fills, and the choice between the fp32 fast kernels (a plan of the same arrays, the (h, d) pairs of the
 // fused GAT layer, ids below 2^31, 16-byte-aligned tables) and the generic ones (fp64, other shapes, NULL plans; the
-// forward also where the plan is not row_owned).
+// forward also where the plan is not row_owned).  Checks, fast conditions, dispatch and launch geometry: host_gat.h.
 // The *_dropout_* entry points are the same op with attention dropout (kernels_dropout.h: the keep decision of an edge
 // is recomputed from Philox in each gather pass, so still no E-sized tensor); p == 0 is the op without it.
 #include "common.h"
 #include "host.h"
 #include "host_dropout.h"
+#include "host_gat.h"
 #include "kernels_gatv2_attn.h"
-
-namespace graphop {
-namespace {
-
-constexpr int kGv2AttnGroup = 16;            // lanes per group of the fast kernels
-constexpr i64 kGv2AttnMaxRowBlocks = 8192;   // workgroups of the fast row pass at most: bounds the datt partials
-
-inline int gv2attn_check(const char* fn, int dtype, i64 C, i64 C2, i64 E, i64 n_l, i64 n_r, i64 h, i64 d) {
-  GO_TRY(check_async_error(false));   // a kernel of an earlier launch reported a failure: sticky until acknowledged
-  GO_CHECK_ARG(dtype == GRAPHOP_F32 || dtype == GRAPHOP_F64, "%s: dtype must be GRAPHOP_F32 or GRAPHOP_F64", fn);
-  GO_CHECK_ARG(C >= 0 && C2 >= 0 && E >= 0 && n_l >= 0 && n_r >= 0 && h >= 1 && d >= 1,
-               "%s: negative size (n_chunks=%lld/%lld n_edges=%lld n_l=%lld n_r=%lld h=%lld d=%lld)", fn,
-               (long long)C, (long long)C2, (long long)E, (long long)n_l, (long long)n_r, (long long)h, (long long)d);
-  return GRAPHOP_OK;
-}
-
-// A plan of these arrays bounds its row ids and neighbour ids: an operand with too few rows is an error here.
-inline int gv2attn_check_plan(const char* fn, const graphop_plan* p, const char* seg_name, i64 n_seg,
-                              const char* idx_name, i64 n_idx) {
-  if (!p) return GRAPHOP_OK;
-  GO_CHECK_ARG(p->info.max_row < n_seg, "%s: row id %lld but %s has only %lld rows", fn, (long long)p->info.max_row,
-               seg_name, (long long)n_seg);
-  GO_CHECK_ARG(p->info.max_index < n_idx, "%s: neighbour id %lld but %s has only %lld rows", fn,
-               (long long)p->info.max_index, idx_name, (long long)n_idx);
-  return GRAPHOP_OK;
-}
-
-// fp32 fast kernels: the (h, d) pairs below, ids that fit 31 bits, 16-byte-aligned tables
-inline bool gv2attn_fast_ok(int dtype, i64 h, i64 d, i64 E, i64 n_l, i64 n_r, std::initializer_list<const void*> ps) {
-  if (tuning().force_generic || dtype != GRAPHOP_F32) return false;
-  if (h != 1 && h != 2 && h != 4 && h != 8) return false;
-  if (d != 8 && d != 16 && d != 32 && d != 64) return false;
-  if (h * d != 64 && h * d != 128 && h * d != 256) return false;
-  if (E >= 0x7fffffffLL || n_l >= 0x7fffffffLL || n_r >= 0x7fffffffLL) return false;
-  for (const void* p : ps)
-    if (((uintptr_t)p & 15) != 0) return false;
-  return true;
-}
-
-#define GO_DISPATCH_GV2ATTN(h, d, ...)                                  \
-  switch ((int)((h) * 1000 + (d))) {                                    \
-    case 1064: { constexpr int H = 1, D = 64; __VA_ARGS__; } break;     \
-    case 2032: { constexpr int H = 2, D = 32; __VA_ARGS__; } break;     \
-    case 2064: { constexpr int H = 2, D = 64; __VA_ARGS__; } break;     \
-    case 4016: { constexpr int H = 4, D = 16; __VA_ARGS__; } break;     \
-    case 4032: { constexpr int H = 4, D = 32; __VA_ARGS__; } break;     \
-    case 4064: { constexpr int H = 4, D = 64; __VA_ARGS__; } break;     \
-    case 8008: { constexpr int H = 8, D = 8; __VA_ARGS__; } break;      \
-    case 8016: { constexpr int H = 8, D = 16; __VA_ARGS__; } break;     \
-    case 8032: { constexpr int H = 8, D = 32; __VA_ARGS__; } break;     \
-    default: break;                                                     \
-  }
-
-// a run-time bool as the template argument NAME of the statement
-#define GO_DISPATCH_GV2ATTN_BOOL(b, NAME, ...)           \
-  if (b) { constexpr bool NAME = true; __VA_ARGS__; }    \
-  else { constexpr bool NAME = false; __VA_ARGS__; }
-
-// ProfScope tag [drop] and kernel label [drop][fast] of a gather pass ("fwd", "bwd_row", "bwd_col"), as in
-// gat_attention.hip: the drop names are those of the path taken (the k_gv2drop_* kernels, the generic DROP = true ones)
-struct Gv2AttnLabels {
-  const char* tag[2];
-  const char* kernel[2][2];
-};
-#define GO_GV2ATTN_LABELS(pass)                                            \
-  Gv2AttnLabels{{"gv2attn_" pass, "gv2attn_drop_" pass},                   \
-                {{"k_gv2attn_" pass "_generic", "k_gv2attn_" pass "_f32"}, \
-                 {"k_gv2attn_drop_" pass "_generic", "k_gv2attn_drop_" pass "_f32"}}}
-
-// chunks per lane group: up to the SpMM cap on big graphs, fewer on small ones so every CU still gets groups
-inline i64 gv2attn_cpg(i64 n_chunks) {
-  const i64 groups_wanted = (i64)tuning().n_cu * (kFastBlock / kGv2AttnGroup) * 8;
-  i64 c = n_chunks / (groups_wanted > 0 ? groups_wanted : 1);
-  if (c < 1) c = 1;
-  const i64 cap = tuning().spmm_cpg > 0 ? tuning().spmm_cpg : 16;
-  return c < cap ? c : cap;
-}
-
-// grid of a fast gather pass: lane groups of 16, cpg chunks each
-inline i64 gv2attn_grid(i64 n_chunks, i64 cpg) {
-  return ceil_div(ceil_div(n_chunks, cpg), (i64)(kFastBlock / kGv2AttnGroup));
-}
-
-// rows of datt partials the fast row pass may write (include/graphop_hip.h states this as part of the workspace minimum)
-inline i64 gv2attn_part_rows(i64 n_row_chunks) {
-  const i64 b = ceil_div(n_row_chunks, (i64)(kFastBlock / kGv2AttnGroup));
-  return b < kGv2AttnMaxRowBlocks ? b : kGv2AttnMaxRowBlocks;
-}
-
-inline unsigned gv2attn_grid_of(i64 n) {
-  const i64 b = ceil_div(n, 256);
-  return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
-}
-
-}  // namespace
-}  // namespace graphop
 
 using namespace graphop;
 
 namespace {
+
+// The gather passes are compiled twice from one text (kernels_gatv2_attn_passes.inc): k_gv2drop_* with dropout,
+// k_gv2attn_* without.  DROP picks the kernel here, so that each pass is one launch.
+template <int H, int D, bool DROP>
+constexpr auto gv2attn_fwd_kernel() {
+  if constexpr (DROP) return &k_gv2drop_fwd_f32<H, D>;
+  else return &k_gv2attn_fwd_f32<H, D>;
+}
+template <int H, int D, bool OWNED, bool DROP>
+constexpr auto gv2attn_bwd_row_kernel() {
+  if constexpr (DROP) return &k_gv2drop_bwd_row_f32<H, D, OWNED>;
+  else return &k_gv2attn_bwd_row_f32<H, D, OWNED>;
+}
+template <int H, int D, bool OWNED, bool DROP>
+constexpr auto gv2attn_bwd_col_kernel() {
+  if constexpr (DROP) return &k_gv2drop_bwd_col_f32<H, D, OWNED>;
+  else return &k_gv2attn_bwd_col_f32<H, D, OWNED>;
+}
 
 // drop == nullptr: the op without dropout (the DROP = false kernels, whatever the entry point)
 int gv2attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
@@ -121,14 +44,14 @@ int gv2attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t
   const size_t es = esize(dtype);
   const graphop_plan* pm = plan_matches_full(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
                                              (const i64*)indices, n_chunks, n_edges) ? plan : nullptr;
-  GO_TRY(gv2attn_check_plan(fn, pm, "xl / o", n_l, "xr", n_r));
+  GO_TRY(gat_check_plan(fn, pm, "xl / o", n_l, "xr", n_r));
   if (n_l == 0) return GRAPHOP_OK;
   GO_PTR(fn, o); GO_PTR(fn, stats);
   // rows without chunks keep o = 0 and stats = (-1e9, 0)
   GO_HIP(zero_async(o, es * (size_t)(n_l * h * d), st));
   auto init = [&](auto zero) {
     using T = decltype(zero);
-    hipLaunchKernelGGL((k_gv2attn_stats_init_generic<T>), dim3(gv2attn_grid_of(n_l * h)), dim3(256), 0, st, (T*)stats,
+    hipLaunchKernelGGL((k_gv2attn_stats_init_generic<T>), dim3(grid_of(n_l * h)), dim3(256), 0, st, (T*)stats,
                        n_l * h);
   };
   if (dtype == GRAPHOP_F32) init(0.f); else init(0.0);
@@ -137,28 +60,22 @@ int gv2attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t
   GO_PTR(fn, row); GO_PTR(fn, indptr); GO_PTR(fn, eid); GO_PTR(fn, indices);
   GO_PTR(fn, xl); GO_PTR(fn, xr); GO_PTR(fn, att);
   const bool fast = pm && pm->info.row_owned && pm->seg_chunk &&
-                    gv2attn_fast_ok(dtype, h, d, n_edges, n_l, n_r, {xl, xr, att, o, stats});
+                    gat_hd_fast_ok(dtype, h, d, n_edges, n_l, n_r, {xl, xr, att, o, stats});
   const bool dropped = drop != nullptr;
-  static const Gv2AttnLabels lab = GO_GV2ATTN_LABELS("fwd");
+  static const GatLabels lab = GO_GAT_LABELS_OF("gv2attn", "fwd");
   if (fast) {
     const i64 S = pm->info.n_segments;
     if (S == 0) return GRAPHOP_OK;
     ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][1]);
     const int n_long = (int)pm->n_long;
     const i64 long_len = n_long > 0 ? kLongSegment : ((i64)1 << 62);
-    const unsigned nbs = (unsigned)ceil_div(S, (i64)(kFastBlock / kGv2AttnGroup));
-    GO_DISPATCH_GV2ATTN(h, d, {
-      if (dropped)
-        hipLaunchKernelGGL((k_gv2drop_fwd_f32<H, D>), dim3(nbs + (unsigned)n_long), dim3(kFastBlock), 0, st,
-                           (const i64*)row, (const i64*)indptr, (const i64*)indices, (const i64*)pm->seg_chunk,
-                           (const float*)xl, (const float*)xr, (const float*)att, (float*)o, (float2*)stats, S, nbs,
-                           long_len, (const int*)pm->long_segs, (float)negative_slope, drop->as<float>());
-      else
-        hipLaunchKernelGGL((k_gv2attn_fwd_f32<H, D>), dim3(nbs + (unsigned)n_long), dim3(kFastBlock), 0, st,
-                           (const i64*)row, (const i64*)indptr, (const i64*)indices, (const i64*)pm->seg_chunk,
-                           (const float*)xl, (const float*)xr, (const float*)att, (float*)o, (float2*)stats, S, nbs,
-                           long_len, (const int*)pm->long_segs, (float)negative_slope, NoDrop{});
-    });
+    const unsigned nbs = (unsigned)ceil_div(S, (i64)(kFastBlock / kGatGroup));
+    GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(dropped, DROP, {
+      hipLaunchKernelGGL((gv2attn_fwd_kernel<H, D, DROP>()), dim3(nbs + (unsigned)n_long), dim3(kFastBlock), 0, st,
+                         (const i64*)row, (const i64*)indptr, (const i64*)indices, (const i64*)pm->seg_chunk,
+                         (const float*)xl, (const float*)xr, (const float*)att, (float*)o, (float2*)stats, S, nbs,
+                         long_len, (const int*)pm->long_segs, (float)negative_slope, drop_arg<DROP, float>(drop));
+    }));
     GO_LAUNCH_CHECK();
     return GRAPHOP_OK;
   }
@@ -172,9 +89,9 @@ int gv2attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t
     hipLaunchKernelGGL((k_gv2attn_stats_generic<T, true>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)row,
                        (const i64*)indptr, (const i64*)indices, (const T*)xl, (const T*)xr, (const T*)att, (T*)stats,
                        n_chunks, h, d, (T)negative_slope);
-    hipLaunchKernelGGL((k_gv2attn_stats_fin_generic<T>), dim3(gv2attn_grid_of(n_l * h)), dim3(256), 0, st, (T*)stats,
+    hipLaunchKernelGGL((k_gv2attn_stats_fin_generic<T>), dim3(grid_of(n_l * h)), dim3(256), 0, st, (T*)stats,
                        n_l * h);
-    GO_DISPATCH_GV2ATTN_BOOL(dropped, DROP, {
+    GO_DISPATCH_BOOL(dropped, DROP, {
       hipLaunchKernelGGL((k_gv2attn_fwd_generic<T, DROP>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)row,
                          (const i64*)indptr, (const i64*)indices, (const T*)xl, (const T*)xr, (const T*)att,
                          (const T*)stats, (T*)o, n_chunks, h, d, (T)negative_slope, drop_arg<DROP, T>(drop));
@@ -198,35 +115,17 @@ int gv2attn_backward(const char* fn, int dtype, const int64_t* row, const int64_
   const bool slots = n_edges > 0 && (n_row_chunks > 0 || n_col_chunks > 0) && n_l > 0 && n_r > 0;
   const bool row_slots = slots && n_row_chunks > 0, col_slots = slots && n_col_chunks > 0;
   const i64 p_values = n_l * h * 4;   // P: (n_l, h, 4), then the datt partials
-  const size_t need = slots ? es * (size_t)(p_values + gv2attn_part_rows(n_row_chunks) * f) : 0;
+  const size_t need = slots ? es * (size_t)(p_values + gat_part_rows(n_row_chunks) * f) : 0;
   GO_CHECK_ARG(workspace_bytes >= 0 && (size_t)workspace_bytes >= need,
                "%s: workspace of %lld bytes needed (n_l * h * 4 + min(ceil(n_row_chunks / 16), 8192) * h * d values), "
                "got %lld", fn, (long long)need, (long long)workspace_bytes);
-  const graphop_plan* pr = plan_matches_full(plan_r, (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r,
-                                             (const i64*)indices_r, n_row_chunks, n_edges) ? plan_r : nullptr;
-  const graphop_plan* pc = plan_matches_full(plan_c, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c,
-                                             (const i64*)indices_c, n_col_chunks, n_edges) ? plan_c : nullptr;
-  GO_TRY(gv2attn_check_plan(fn, pr, "xl / dxl", n_l, "xr", n_r));
-  GO_TRY(gv2attn_check_plan(fn, pc, "xr / dxr", n_r, "xl", n_l));
-  // the outputs of an orientation without chunks may be NULL: that half of the op is skipped
-  const bool row_half = !(dxl == nullptr && datt == nullptr && n_row_chunks == 0);
-  const bool col_half = !(dxr == nullptr && n_col_chunks == 0);
-  if (row_half) {
-    if (n_l > 0) {
-      GO_PTR(fn, dxl);
-      GO_HIP(zero_async(dxl, es * (size_t)(n_l * f), st));
-    }
-    GO_PTR(fn, datt);
-    GO_HIP(zero_async(datt, es * (size_t)f, st));
-  }
-  if (col_half && n_r > 0) {
-    GO_PTR(fn, dxr);
-    GO_HIP(zero_async(dxr, es * (size_t)(n_r * f), st));
-  }
+  const graphop_plan *pr, *pc;
+  GO_TRY(gatv2_bwd_open(fn, dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, dxl, dxr, datt,
+                        n_row_chunks, n_col_chunks, n_edges, n_l, n_r, f, plan_r, plan_c, st, &pr, &pc));
   if (!slots) return GRAPHOP_OK;
   GO_PTR(fn, xl); GO_PTR(fn, xr); GO_PTR(fn, att); GO_PTR(fn, o); GO_PTR(fn, stats); GO_PTR(fn, dO);
   GO_PTR(fn, workspace);
-  const bool ok = gv2attn_fast_ok(dtype, h, d, n_edges, n_l, n_r, {xl, xr, att, o, stats, dO, workspace});
+  const bool ok = gat_hd_fast_ok(dtype, h, d, n_edges, n_l, n_r, {xl, xr, att, o, stats, dO, workspace});
   const float slope = (float)negative_slope;
   const bool dropped = drop != nullptr;
   void* part = (char*)workspace + es * (size_t)p_values;
@@ -234,15 +133,15 @@ int gv2attn_backward(const char* fn, int dtype, const int64_t* row, const int64_
     const bool fast = ok && (pr || pc);
     ProfScope prof("gv2attn_pack", st, fast ? "k_gv2attn_pack_f32" : "k_gv2attn_pack_generic");
     if (fast) {
-      GO_DISPATCH_GV2ATTN(h, d, {
-        hipLaunchKernelGGL((k_gv2attn_pack_f32<H, D>), dim3((unsigned)ceil_div(n_l, (i64)(kFastBlock / kGv2AttnGroup))),
+      GO_DISPATCH_GAT_HD(h, d, {
+        hipLaunchKernelGGL((k_gv2attn_pack_f32<H, D>), dim3((unsigned)ceil_div(n_l, (i64)(kFastBlock / kGatGroup))),
                            dim3(kFastBlock), 0, st, (const float2*)stats, (const float*)dO, (const float*)o,
                            (float4*)workspace, n_l);
       });
     } else {
       auto go = [&](auto zero) {
         using T = decltype(zero);
-        hipLaunchKernelGGL((k_gv2attn_pack_generic<T>), dim3(gv2attn_grid_of(n_l * h)), dim3(256), 0, st,
+        hipLaunchKernelGGL((k_gv2attn_pack_generic<T>), dim3(grid_of(n_l * h)), dim3(256), 0, st,
                            (const T*)stats, (const T*)dO, (const T*)o, (T*)workspace, n_l * h, d);
       };
       if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
@@ -254,39 +153,30 @@ int gv2attn_backward(const char* fn, int dtype, const int64_t* row, const int64_
     GO_PTR(fn, dxl); GO_PTR(fn, datt);
     const i64 C = n_row_chunks;
     if (ok && pr && (((uintptr_t)dxl | (uintptr_t)datt) & 15) == 0) {
-      i64 nb;
+      const GatRowPass geo = gat_row_pass(C, tuning().spmm_cpg);   // n_blocks <= gat_part_rows(C)
       {
-        static const Gv2AttnLabels lab = GO_GV2ATTN_LABELS("bwd_row");
+        static const GatLabels lab = GO_GAT_LABELS_OF("gv2attn", "bwd_row");
         ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][1]);
-        i64 cpg = gv2attn_cpg(C);
-        if (gv2attn_grid(C, cpg) > kGv2AttnMaxRowBlocks)
-          cpg = ceil_div(C, kGv2AttnMaxRowBlocks * (kFastBlock / kGv2AttnGroup));
-        nb = gv2attn_grid(C, cpg);   // <= gv2attn_part_rows(C): cpg >= 1 and the cap above
         const bool owned = pr->info.rows_sorted != 0;
-        GO_DISPATCH_GV2ATTN(h, d, GO_DISPATCH_GV2ATTN_BOOL(owned, OWNED, {
-          if (dropped)
-            hipLaunchKernelGGL((k_gv2drop_bwd_row_f32<H, D, OWNED>), dim3((unsigned)nb), dim3(kFastBlock), 0, st,
-                               (const i64*)row, (const i64*)indptr_r, (const i64*)indices_r, (const float*)xl,
-                               (const float*)xr, (const float*)att, (const float4*)workspace, (const float*)dO,
-                               (float*)dxl, (float4*)part, C, (int)cpg, slope, drop->as<float>());
-          else
-            hipLaunchKernelGGL((k_gv2attn_bwd_row_f32<H, D, OWNED>), dim3((unsigned)nb), dim3(kFastBlock), 0, st,
-                               (const i64*)row, (const i64*)indptr_r, (const i64*)indices_r, (const float*)xl,
-                               (const float*)xr, (const float*)att, (const float4*)workspace, (const float*)dO,
-                               (float*)dxl, (float4*)part, C, (int)cpg, slope, NoDrop{});
-        }));
+        GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
+          hipLaunchKernelGGL((gv2attn_bwd_row_kernel<H, D, OWNED, DROP>()), dim3((unsigned)geo.n_blocks),
+                             dim3(kFastBlock), 0, st, (const i64*)row, (const i64*)indptr_r, (const i64*)indices_r,
+                             (const float*)xl, (const float*)xr, (const float*)att, (const float4*)workspace,
+                             (const float*)dO, (float*)dxl, (float4*)part, C, geo.cpg, slope,
+                             drop_arg<DROP, float>(drop));
+        })));
         GO_LAUNCH_CHECK();
       }
       ProfScope prof("gv2attn_datt_fin", st, "k_gv2attn_datt_fin_f32");
       hipLaunchKernelGGL(k_gv2attn_datt_fin_f32, dim3((unsigned)(f / 4)), dim3(kFastBlock), 0, st,
-                         (const float4*)part, (float4*)datt, nb, (int)(f / 4));
+                         (const float4*)part, (float4*)datt, geo.n_blocks, (int)(f / 4));
     } else {
-      static const Gv2AttnLabels lab = GO_GV2ATTN_LABELS("bwd_row");
+      static const GatLabels lab = GO_GAT_LABELS_OF("gv2attn", "bwd_row");
       ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][0]);
       const unsigned nb = (unsigned)ceil_div(C, kGenericWavesPerBlock);
       auto go = [&](auto zero) {
         using T = decltype(zero);
-        GO_DISPATCH_GV2ATTN_BOOL(dropped, DROP, {
+        GO_DISPATCH_BOOL(dropped, DROP, {
           hipLaunchKernelGGL((k_gv2attn_bwd_row_generic<T, DROP>), dim3(nb), dim3(kGenericBlock), 0, st,
                              (const i64*)row, (const i64*)indptr_r, (const i64*)indices_r, (const T*)xl, (const T*)xr,
                              (const T*)att, (const T*)workspace, (const T*)dO, (T*)dxl, (T*)datt, C, h, d,
@@ -301,29 +191,23 @@ int gv2attn_backward(const char* fn, int dtype, const int64_t* row, const int64_
     GO_PTR(fn, col); GO_PTR(fn, indptr_c); GO_PTR(fn, eid_c); GO_PTR(fn, indices_c);
     GO_PTR(fn, dxr);
     const i64 C = n_col_chunks;
-    static const Gv2AttnLabels lab = GO_GV2ATTN_LABELS("bwd_col");
+    static const GatLabels lab = GO_GAT_LABELS_OF("gv2attn", "bwd_col");
     if (ok && pc && ((uintptr_t)dxr & 15) == 0) {
       ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][1]);
-      const i64 cpg = gv2attn_cpg(C);
+      const int cpg = gat_cpg(C, tuning().spmm_cpg);
       const bool owned = pc->info.rows_sorted != 0;
-      GO_DISPATCH_GV2ATTN(h, d, GO_DISPATCH_GV2ATTN_BOOL(owned, OWNED, {
-        if (dropped)
-          hipLaunchKernelGGL((k_gv2drop_bwd_col_f32<H, D, OWNED>), dim3((unsigned)gv2attn_grid(C, cpg)),
-                             dim3(kFastBlock), 0, st, (const i64*)col, (const i64*)indptr_c, (const i64*)indices_c,
-                             (const float*)xl, (const float*)xr, (const float*)att, (const float4*)workspace,
-                             (const float*)dO, (float*)dxr, C, (int)cpg, slope, drop->as<float>());
-        else
-          hipLaunchKernelGGL((k_gv2attn_bwd_col_f32<H, D, OWNED>), dim3((unsigned)gv2attn_grid(C, cpg)),
-                             dim3(kFastBlock), 0, st, (const i64*)col, (const i64*)indptr_c, (const i64*)indices_c,
-                             (const float*)xl, (const float*)xr, (const float*)att, (const float4*)workspace,
-                             (const float*)dO, (float*)dxr, C, (int)cpg, slope, NoDrop{});
-      }));
+      GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
+        hipLaunchKernelGGL((gv2attn_bwd_col_kernel<H, D, OWNED, DROP>()), dim3((unsigned)gat_grid(C, cpg)),
+                           dim3(kFastBlock), 0, st, (const i64*)col, (const i64*)indptr_c, (const i64*)indices_c,
+                           (const float*)xl, (const float*)xr, (const float*)att, (const float4*)workspace,
+                           (const float*)dO, (float*)dxr, C, cpg, slope, drop_arg<DROP, float>(drop));
+      })));
     } else {
       ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][0]);
       const unsigned nb = (unsigned)ceil_div(C, kGenericWavesPerBlock);
       auto go = [&](auto zero) {
         using T = decltype(zero);
-        GO_DISPATCH_GV2ATTN_BOOL(dropped, DROP, {
+        GO_DISPATCH_BOOL(dropped, DROP, {
           hipLaunchKernelGGL((k_gv2attn_bwd_col_generic<T, DROP>), dim3(nb), dim3(kGenericBlock), 0, st,
                              (const i64*)col, (const i64*)indptr_c, (const i64*)indices_c, (const T*)xl, (const T*)xr,
                              (const T*)att, (const T*)workspace, (const T*)dO, (T*)dxr, C, h, d, (T)negative_slope,
@@ -347,7 +231,7 @@ int graphop_gatv2_attention_forward(int dtype, const int64_t* row, const int64_t
                                     int64_t h, int64_t d, double negative_slope, const graphop_plan_t* plan,
                                     void* stream) {
   const char* fn = "gatv2_attention_forward";
-  GO_TRY(gv2attn_check(fn, dtype, n_chunks, 0, n_edges, n_l, n_r, h, d));
+  GO_TRY(gat_check(fn, dtype, n_chunks, 0, n_edges, n_l, n_r, h, d));
   return gv2attn_forward(fn, dtype, row, indptr, eid, indices, xl, xr, att, o, stats, n_chunks, n_edges, n_l, n_r, h, d,
                          negative_slope, nullptr, plan, stream);
 }
@@ -361,7 +245,7 @@ int graphop_gatv2_attention_backward(int dtype, const int64_t* row, const int64_
                                      int64_t n_r, int64_t h, int64_t d, double negative_slope,
                                      const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream) {
   const char* fn = "gatv2_attention_backward";
-  GO_TRY(gv2attn_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_l, n_r, h, d));
+  GO_TRY(gat_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_l, n_r, h, d));
   return gv2attn_backward(fn, dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, o,
                           stats, dO, dxl, dxr, datt, workspace, workspace_bytes, n_row_chunks, n_col_chunks, n_edges,
                           n_l, n_r, h, d, negative_slope, nullptr, plan_r, plan_c, stream);
@@ -374,7 +258,7 @@ int graphop_gatv2_attention_dropout_forward(int dtype, const int64_t* row, const
                                             int64_t n_r, int64_t h, int64_t d, double negative_slope, double p,
                                             uint64_t seed, uint32_t offset, const graphop_plan_t* plan, void* stream) {
   const char* fn = "gatv2_attention_dropout_forward";
-  GO_TRY(gv2attn_check(fn, dtype, n_chunks, 0, n_edges, n_l, n_r, h, d));
+  GO_TRY(gat_check(fn, dtype, n_chunks, 0, n_edges, n_l, n_r, h, d));
   HostDrop drop;
   GO_TRY(drop_check(fn, p, seed, n_l, n_r, offset, &drop));
   return gv2attn_forward(fn, dtype, row, indptr, eid, indices, xl, xr, att, o, stats, n_chunks, n_edges, n_l, n_r, h, d,
@@ -392,7 +276,7 @@ int graphop_gatv2_attention_dropout_backward(int dtype, const int64_t* row, cons
                                              uint32_t offset, const graphop_plan_t* plan_r,
                                              const graphop_plan_t* plan_c, void* stream) {
   const char* fn = "gatv2_attention_dropout_backward";
-  GO_TRY(gv2attn_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_l, n_r, h, d));
+  GO_TRY(gat_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_l, n_r, h, d));
   HostDrop drop;
   GO_TRY(drop_check(fn, p, seed, n_l, n_r, offset, &drop));
   return gv2attn_backward(fn, dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, o,

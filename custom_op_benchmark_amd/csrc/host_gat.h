@@ -1,0 +1,175 @@
+// Host-side helpers of the GAT family of entry points (gat.hip, gatv2.hip, gat_attention.hip, gat_edge_attention.hip,
+// gatv2_attention.hip and host_gat_attn_ops.h): argument and plan checks, the conditions of the fp32 fast kernels, the
+// (h, d) dispatch, the profile labels, the launch geometry of the gather passes and the opening of the two GATv2
+// backwards.  Each exists once, here.  Not part of the C ABI.
+#pragma once
+#include <cstdio>
+#include <initializer_list>
+
+#include "common.h"
+#include "host.h"
+
+namespace graphop {
+
+constexpr int kGatGroup = 16;            // lanes per group of the (h, d) fast kernels
+constexpr i64 kGatMaxRowBlocks = 8192;   // workgroups of a fast GATv2 row pass at most: bounds the datt partials
+
+// has_d = false: an op without a feature width (gat_scores), whose message has no d= field
+inline int gat_check(const char* fn, int dtype, i64 C, i64 C2, i64 E, i64 n_l, i64 n_r, i64 h, i64 d,
+                     bool has_d = true) {
+  GO_TRY(check_async_error(false));   // a kernel of an earlier launch reported a failure: sticky until acknowledged
+  GO_CHECK_ARG(dtype == GRAPHOP_F32 || dtype == GRAPHOP_F64, "%s: dtype must be GRAPHOP_F32 or GRAPHOP_F64", fn);
+  char d_field[32] = "";
+  if (has_d) snprintf(d_field, sizeof(d_field), " d=%lld", (long long)d);
+  GO_CHECK_ARG(C >= 0 && C2 >= 0 && E >= 0 && n_l >= 0 && n_r >= 0 && h >= 1 && d >= 1,
+               "%s: negative size (n_chunks=%lld/%lld n_edges=%lld n_l=%lld n_r=%lld h=%lld%s)", fn, (long long)C,
+               (long long)C2, (long long)E, (long long)n_l, (long long)n_r, (long long)h, d_field);
+  return GRAPHOP_OK;
+}
+inline int gat_check(const char* fn, int dtype, i64 C, i64 C2, i64 E, i64 n_l, i64 n_r, i64 h) {
+  return gat_check(fn, dtype, C, C2, E, n_l, n_r, h, 1, false);
+}
+
+// A plan of these arrays bounds its row ids and neighbour ids: an operand with too few rows is an error here.
+inline int gat_check_plan(const char* fn, const graphop_plan* p, const char* seg_name, i64 n_seg, const char* idx_name,
+                          i64 n_idx) {
+  if (!p) return GRAPHOP_OK;
+  GO_CHECK_ARG(p->info.max_row < n_seg, "%s: row id %lld but %s has only %lld rows", fn, (long long)p->info.max_row,
+               seg_name, (long long)n_seg);
+  GO_CHECK_ARG(p->info.max_index < n_idx, "%s: neighbour id %lld but %s has only %lld rows", fn,
+               (long long)p->info.max_index, idx_name, (long long)n_idx);
+  return GRAPHOP_OK;
+}
+
+inline bool a16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// a per-(node or edge, head) array as the fast kernels read and write it: aligned to its item width, 4 * min(h, 4) bytes
+inline bool gat_aligned(const void* p, i64 h) {
+  const uintptr_t a = h >= 4 ? 16 : (uintptr_t)(4 * h);
+  return ((uintptr_t)p % a) == 0;
+}
+
+// fp32 fast kernels of the (h, d) ops: the pairs of GO_DISPATCH_GAT_HD, ids that fit 31 bits, 16-byte-aligned tables
+inline bool gat_hd_fast_ok(int dtype, i64 h, i64 d, i64 E, i64 n_l, i64 n_r, std::initializer_list<const void*> ps) {
+  if (tuning().force_generic || dtype != GRAPHOP_F32) return false;
+  if (h != 1 && h != 2 && h != 4 && h != 8) return false;
+  if (d != 8 && d != 16 && d != 32 && d != 64) return false;
+  if (h * d != 64 && h * d != 128 && h * d != 256) return false;
+  if (E >= 0x7fffffffLL || n_l >= 0x7fffffffLL || n_r >= 0x7fffffffLL) return false;
+  for (const void* p : ps)
+    if (!a16(p)) return false;
+  return true;
+}
+
+#define GO_DISPATCH_GAT_HD(h, d, ...)                                   \
+  switch ((int)((h) * 1000 + (d))) {                                    \
+    case 1064: { constexpr int H = 1, D = 64; __VA_ARGS__; } break;     \
+    case 2032: { constexpr int H = 2, D = 32; __VA_ARGS__; } break;     \
+    case 2064: { constexpr int H = 2, D = 64; __VA_ARGS__; } break;     \
+    case 4016: { constexpr int H = 4, D = 16; __VA_ARGS__; } break;     \
+    case 4032: { constexpr int H = 4, D = 32; __VA_ARGS__; } break;     \
+    case 4064: { constexpr int H = 4, D = 64; __VA_ARGS__; } break;     \
+    case 8008: { constexpr int H = 8, D = 8; __VA_ARGS__; } break;      \
+    case 8016: { constexpr int H = 8, D = 16; __VA_ARGS__; } break;     \
+    case 8032: { constexpr int H = 8, D = 32; __VA_ARGS__; } break;     \
+    default: break;                                                     \
+  }
+
+// the head counts of the fused stats kernel (gat.hip has its own list, which also holds 16)
+#define GO_DISPATCH_GAT_ATTN_H(h, ...)                  \
+  switch ((int)(h)) {                                   \
+    case 1: { constexpr int H = 1; __VA_ARGS__; } break; \
+    case 2: { constexpr int H = 2; __VA_ARGS__; } break; \
+    case 4: { constexpr int H = 4; __VA_ARGS__; } break; \
+    case 8: { constexpr int H = 8; __VA_ARGS__; } break; \
+    default: break;                                     \
+  }
+
+// a run-time bool as the template argument NAME of the statement
+#define GO_DISPATCH_BOOL(b, NAME, ...)                   \
+  if (b) { constexpr bool NAME = true; __VA_ARGS__; }    \
+  else { constexpr bool NAME = false; __VA_ARGS__; }
+
+// ProfScope tag [drop] and kernel label [drop][fast] of a gather pass ("fwd", "bwd_row", "bwd_col") of the fused op
+// `op`.  The drop names are those of the path taken: the DROP = true instantiations, the k_gv2drop_* kernels.
+struct GatLabels {
+  const char* tag[2];
+  const char* kernel[2][2];
+};
+#define GO_GAT_LABELS_OF(op, pass)                                \
+  GatLabels{{op "_" pass, op "_drop_" pass},                      \
+            {{"k_" op "_" pass "_generic", "k_" op "_" pass "_f32"}, \
+             {"k_" op "_drop_" pass "_generic", "k_" op "_drop_" pass "_f32"}}}
+
+// chunks per lane group of G lanes: up to the tuned cap (sddmm_cpg or spmm_cpg; below 1 it counts as 1) on big graphs,
+// fewer on small ones so every CU still gets groups
+inline int gat_cpg(i64 n_chunks, int cap, int G = kGatGroup) {
+  const i64 groups_wanted = (i64)tuning().n_cu * (kFastBlock / G) * 8;
+  i64 c = n_chunks / (groups_wanted > 0 ? groups_wanted : 1);
+  if (cap < 1) cap = 1;
+  if (c > cap) c = cap;
+  return (int)(c < 1 ? 1 : c);
+}
+
+// grid of a fast gather pass: lane groups of G lanes, cpg chunks each
+inline i64 gat_grid(i64 n_chunks, i64 cpg, int G = kGatGroup) {
+  return ceil_div(ceil_div(n_chunks, cpg), (i64)(kFastBlock / G));
+}
+
+// rows of datt partials a fast GATv2 row pass may write (include/graphop_hip.h states this in the workspace minimum)
+inline i64 gat_part_rows(i64 n_row_chunks) {
+  const i64 b = ceil_div(n_row_chunks, (i64)(kFastBlock / kGatGroup));
+  return b < kGatMaxRowBlocks ? b : kGatMaxRowBlocks;
+}
+
+// cpg and grid of a fast GATv2 row pass: gat_cpg, raised where its grid would exceed kGatMaxRowBlocks, so that
+// n_blocks <= gat_part_rows(n_chunks)
+struct GatRowPass {
+  int cpg;
+  i64 n_blocks;
+};
+inline GatRowPass gat_row_pass(i64 n_chunks, int cap) {
+  i64 cpg = gat_cpg(n_chunks, cap);
+  if (gat_grid(n_chunks, cpg) > kGatMaxRowBlocks)
+    cpg = ceil_div(n_chunks, kGatMaxRowBlocks * (kFastBlock / kGatGroup));
+  return {(int)cpg, gat_grid(n_chunks, cpg)};
+}
+
+inline unsigned grid_of(i64 n) {
+  const i64 b = ceil_div(n, 256);
+  return (unsigned)(b < 1 ? 1 : (b > 65536 ? 65536 : b));
+}
+
+// The opening of the two GATv2 backwards (gatv2_scores_backward, gatv2_attention[_dropout]_backward), after their own
+// workspace check: the plans that match the arrays, checked against the operands' row counts, and the zero fills of
+// the outputs.  The outputs of an orientation without chunks may be NULL: that half of the op is skipped.
+inline int gatv2_bwd_open(const char* fn, int dtype, const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r,
+                          const int64_t* indices_r, const int64_t* col, const int64_t* indptr_c, const int64_t* eid_c,
+                          const int64_t* indices_c, void* dxl, void* dxr, void* datt, i64 n_row_chunks,
+                          i64 n_col_chunks, i64 n_edges, i64 n_l, i64 n_r, i64 f, const graphop_plan* plan_r,
+                          const graphop_plan* plan_c, hipStream_t st, const graphop_plan** pr, const graphop_plan** pc) {
+  const size_t es = esize(dtype);
+  *pr = plan_matches_full(plan_r, (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r, (const i64*)indices_r,
+                          n_row_chunks, n_edges) ? plan_r : nullptr;
+  *pc = plan_matches_full(plan_c, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c, (const i64*)indices_c,
+                          n_col_chunks, n_edges) ? plan_c : nullptr;
+  GO_TRY(gat_check_plan(fn, *pr, "xl / dxl", n_l, "xr", n_r));
+  GO_TRY(gat_check_plan(fn, *pc, "xr / dxr", n_r, "xl", n_l));
+  const bool row_half = !(dxl == nullptr && datt == nullptr && n_row_chunks == 0);
+  const bool col_half = !(dxr == nullptr && n_col_chunks == 0);
+  if (row_half) {
+    if (n_l > 0) {
+      GO_PTR(fn, dxl);
+      GO_HIP(zero_async(dxl, es * (size_t)(n_l * f), st));
+    }
+    GO_PTR(fn, datt);
+    GO_HIP(zero_async(datt, es * (size_t)f, st));
+  }
+  if (col_half && n_r > 0) {
+    GO_PTR(fn, dxr);
+    GO_HIP(zero_async(dxr, es * (size_t)(n_r * f), st));
+  }
+  return GRAPHOP_OK;
+}
+
+}  // namespace graphop

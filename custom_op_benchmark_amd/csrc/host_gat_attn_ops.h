@@ -9,16 +9,13 @@
 #include <type_traits>
 
 #include "host_dropout.h"
-#include "host_gat_attn.h"
+#include "host_gat.h"
 #include "kernels_gat_edge_attn.h"
 
 namespace graphop {
 
-// ee / dee as the fast kernels read and write them: aligned to their item width (4 * min(h, 4) bytes)
-inline bool edge_aligned(const void* p, i64 h) {
-  const uintptr_t a = h >= 4 ? 16 : (uintptr_t)(4 * h);
-  return ((uintptr_t)p % a) == 0;
-}
+#define GO_GAT_ATTN_LABELS(EDGE, pass) \
+  (EDGE ? GO_GAT_LABELS_OF("gat_edge_attn", pass) : GO_GAT_LABELS_OF("gat_attn", pass))
 
 // the eid argument of a fast row-major pass: NULL where the plan says eid[slot] == slot
 inline const i64* eid_arg(const graphop_plan* p, const void* eid) {
@@ -95,7 +92,7 @@ int gat_attn_forward(const char* fn, int dtype, const int64_t* row, const int64_
   const size_t es = esize(dtype);
   const graphop_plan* pm = plan_matches_full(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
                                              (const i64*)indices, n_chunks, n_edges) ? plan : nullptr;
-  GO_TRY(gat_attn_check_plan(fn, pm, "el / o", n_l, "er / V", n_r));
+  GO_TRY(gat_check_plan(fn, pm, "el / o", n_l, "er / V", n_r));
   if (n_l == 0) return GRAPHOP_OK;
   GO_PTR(fn, o); GO_PTR(fn, stats);
   GO_HIP(zero_async(o, es * (size_t)(n_l * h * d), st));
@@ -106,19 +103,19 @@ int gat_attn_forward(const char* fn, int dtype, const int64_t* row, const int64_
     if constexpr (EDGE) GO_PTR(fn, ee);
     GO_PTR(fn, V);
   }
-  const bool fast = pm && gat_attn_fast_ok(dtype, h, d, n_edges, n_l, n_r, {el, er, V, o, stats}) &&
-                    (!EDGE || edge_aligned(ee, h));
+  const bool fast = pm && gat_hd_fast_ok(dtype, h, d, n_edges, n_l, n_r, {el, er, V, o, stats}) &&
+                    (!EDGE || gat_aligned(ee, h));
   GO_TRY(gat_attn_stats<EDGE>(dtype, (const i64*)row, (const i64*)indptr, (const i64*)eid, (const i64*)indices, el, er,
                               ee, stats, slots ? n_chunks : 0, n_l, h, negative_slope, pm, fast, st));
   if (!slots) return GRAPHOP_OK;
   const bool dropped = drop != nullptr;
-  static const GatAttnLabels lab = GO_GAT_ATTN_LABELS(EDGE, "fwd");
+  static const GatLabels lab = GO_GAT_ATTN_LABELS(EDGE, "fwd");
   ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][fast]);
   if (fast) {
-    const int cpg = gat_attn_cpg(n_chunks);
+    const int cpg = gat_cpg(n_chunks, tuning().spmm_cpg);
     const bool owned = pm->info.rows_sorted != 0;
-    const dim3 grid(gat_attn_grid(n_chunks, cpg));
-    GO_DISPATCH_GAT_ATTN(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
+    const dim3 grid((unsigned)gat_grid(n_chunks, cpg));
+    GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
       if constexpr (EDGE)
         hipLaunchKernelGGL((k_gat_edge_attn_fwd_f32<H, D, OWNED, DROP>), grid, dim3(kFastBlock), 0, st,
                            (const i64*)row, (const i64*)indptr, eid_arg(pm, eid), (const i64*)indices,
@@ -172,8 +169,8 @@ int gat_attn_backward(const char* fn, int dtype, const int64_t* row, const int64
                                              (const i64*)indices_r, n_row_chunks, n_edges) ? plan_r : nullptr;
   const graphop_plan* pc = plan_matches_full(plan_c, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c,
                                              (const i64*)indices_c, n_col_chunks, n_edges) ? plan_c : nullptr;
-  GO_TRY(gat_attn_check_plan(fn, pr, "el / del", n_l, "er / V", n_r));
-  GO_TRY(gat_attn_check_plan(fn, pc, "er / der", n_r, "el", n_l));
+  GO_TRY(gat_check_plan(fn, pr, "el / del", n_l, "er / V", n_r));
+  GO_TRY(gat_check_plan(fn, pc, "er / der", n_r, "el", n_l));
   if (n_l > 0 && !(del == nullptr && n_row_chunks == 0)) {
     GO_PTR(fn, del);
     GO_HIP(zero_async(del, es * (size_t)(n_l * h), st));
@@ -194,8 +191,8 @@ int gat_attn_backward(const char* fn, int dtype, const int64_t* row, const int64
   if constexpr (EDGE) GO_PTR(fn, ee);
   GO_PTR(fn, V); GO_PTR(fn, o); GO_PTR(fn, stats); GO_PTR(fn, dO);
   GO_PTR(fn, workspace);
-  const bool ok = gat_attn_fast_ok(dtype, h, d, n_edges, n_l, n_r, {el, er, V, o, stats, dO, workspace, dV}) &&
-                  (!EDGE || (edge_aligned(ee, h) && edge_aligned(dee, h)));
+  const bool ok = gat_hd_fast_ok(dtype, h, d, n_edges, n_l, n_r, {el, er, V, o, stats, dO, workspace, dV}) &&
+                  (!EDGE || (gat_aligned(ee, h) && gat_aligned(dee, h)));
   const float slope = (float)negative_slope;
   const bool dropped = drop != nullptr;
   const int G = 16;
@@ -204,7 +201,7 @@ int gat_attn_backward(const char* fn, int dtype, const int64_t* row, const int64
     ProfScope prof(EDGE ? "gat_edge_attn_pack" : "gat_attn_pack", st,
                    fast ? "k_gat_attn_pack_f32" : "k_gat_attn_pack_generic");
     if (fast) {
-      GO_DISPATCH_GAT_ATTN(h, d, {
+      GO_DISPATCH_GAT_HD(h, d, {
         hipLaunchKernelGGL((k_gat_attn_pack_f32<H, D>), dim3((unsigned)ceil_div(n_l, kFastBlock / G)),
                            dim3(kFastBlock), 0, st, (const float*)el, (const float2*)stats, (const float*)dO,
                            (const float*)o, (float4*)workspace, n_l);
@@ -223,13 +220,13 @@ int gat_attn_backward(const char* fn, int dtype, const int64_t* row, const int64
     GO_PTR(fn, row); GO_PTR(fn, indptr_r); GO_PTR(fn, eid_r); GO_PTR(fn, indices_r);
     const i64 C = n_row_chunks;
     const bool fast = ok && pr;
-    static const GatAttnLabels lab = GO_GAT_ATTN_LABELS(EDGE, "bwd_row");
+    static const GatLabels lab = GO_GAT_ATTN_LABELS(EDGE, "bwd_row");
     ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][fast]);
     if (fast) {
-      const int cpg = gat_attn_cpg(C);
+      const int cpg = gat_cpg(C, tuning().spmm_cpg);
       const bool owned = pr->info.rows_sorted != 0;
-      const dim3 grid(gat_attn_grid(C, cpg));
-      GO_DISPATCH_GAT_ATTN(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
+      const dim3 grid((unsigned)gat_grid(C, cpg));
+      GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
         if constexpr (EDGE)
           hipLaunchKernelGGL((k_gat_edge_attn_bwd_row_f32<H, D, OWNED, DROP>), grid, dim3(kFastBlock), 0, st,
                              (const i64*)row, (const i64*)indptr_r, eid_arg(pr, eid_r), (const i64*)indices_r,
@@ -266,13 +263,13 @@ int gat_attn_backward(const char* fn, int dtype, const int64_t* row, const int64
     GO_PTR(fn, col); GO_PTR(fn, indptr_c); GO_PTR(fn, eid_c); GO_PTR(fn, indices_c);
     const i64 C = n_col_chunks;
     const bool fast = ok && pc;
-    static const GatAttnLabels lab = GO_GAT_ATTN_LABELS(EDGE, "bwd_col");
+    static const GatLabels lab = GO_GAT_ATTN_LABELS(EDGE, "bwd_col");
     ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][fast]);
     if (fast) {
-      const int cpg = gat_attn_cpg(C);
+      const int cpg = gat_cpg(C, tuning().spmm_cpg);
       const bool owned = pc->info.rows_sorted != 0;
-      const dim3 grid(gat_attn_grid(C, cpg));
-      GO_DISPATCH_GAT_ATTN(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
+      const dim3 grid((unsigned)gat_grid(C, cpg));
+      GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
         if constexpr (EDGE)
           hipLaunchKernelGGL((k_gat_edge_attn_bwd_col_f32<H, D, OWNED, DROP>), grid, dim3(kFastBlock), 0, st,
                              (const i64*)col, (const i64*)indptr_c, eid_arg(pc, eid_c), (const i64*)indices_c,

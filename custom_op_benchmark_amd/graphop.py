@@ -552,59 +552,70 @@ def _gat_attn_shapes(el, er, V, fn):
     return h, V.size(-1)
 
 
-def _gat_attention_forward(fn, row, indptr, eid, indices, el, er, V, negative_slope, drop=()):
-    """gat_attention_forward (drop = ()) or gat_attention_dropout_forward (drop = (p, seed, offset)) as `fn`."""
+def _gat_attention_forward(fn, row, indptr, eid, indices, el, er, V, negative_slope, drop=(), ee=None):
+    """gat_attention_forward (drop = ()), gat_attention_dropout_forward or, with the edge term ee,
+    gat_edge_attention_forward (drop = (p, seed, offset)) as `fn`."""
+    edge = () if ee is None else ((ee, "ee"),)
     for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices"), (el, "el"), (er, "er"),
-                 (V, "V")):
+                 *edge, (V, "V")):
         _check_input(t, n)
     for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices")):
         _check_index(t, n)
     h, d = _gat_attn_shapes(el, er, V, fn)
     e, n_l = eid.size(0), el.size(0)
+    if edge:
+        _gat_edge_term(el, ee, e, h, fn)
     o = torch.empty((n_l,) + tuple(V.shape[1:]), dtype=V.dtype, device=V.device)
     stats = torch.empty((n_l, h, 2), dtype=el.dtype, device=el.device)
     with _lib.device_guard(el.device):
         plan = _plan(row, indptr, eid, indices, er.size(0))
         check(getattr(lib(), "graphop_" + fn)(
-            dtype_code(el), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(el), ptr(er), ptr(V), ptr(o),
-            ptr(stats), row.size(0), e, n_l, er.size(0), h, d, float(negative_slope), *drop, plan.handle,
-            stream_of(el)))
+            dtype_code(el), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(el), ptr(er), *(ptr(t) for t, _ in edge),
+            ptr(V), ptr(o), ptr(stats), row.size(0), e, n_l, er.size(0), h, d, float(negative_slope), *drop,
+            plan.handle, stream_of(el)))
     return [o, stats]
 
 
 def _gat_attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V, o, stats,
-                            dO, negative_slope, drop=()):
-    """gat_attention_backward (drop = ()) or gat_attention_dropout_backward (drop = (p, seed, offset)) as `fn`."""
+                            dO, negative_slope, drop=(), ee=None, need_dee=True):
+    """gat_attention_backward (drop = ()), gat_attention_dropout_backward or, with the edge term ee,
+    gat_edge_attention_backward (drop = (p, seed, offset)) as `fn`: -> [del, der, dV], with ee [del, der, dee, dV]."""
+    edge = () if ee is None else ((ee, "ee"),)
     names = ("row", "indptr_r", "eid_r", "indices_r", "col", "indptr_c", "eid_c", "indices_c")
     idx = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
-    for t, n in zip(idx + (el, er, V, o, stats), names + ("el", "er", "V", "o", "stats")):
+    for t, n in (*zip(idx, names), (el, "el"), (er, "er"), *edge, (V, "V"), (o, "o"), (stats, "stats")):
         _check_input(t, n)
     for t, n in zip(idx, names):
         _check_index(t, n)
     if not isinstance(dO, torch.Tensor) or not dO.is_cuda:
         raise RuntimeError("dO must be a CUDA tensor")
     h, d = _gat_attn_shapes(el, er, V, fn)
+    e, n_l = eid_r.size(0), el.size(0)
+    if edge:
+        _gat_edge_term(el, ee, e, h, fn)
     for t, n in ((o, "o"), (stats, "stats"), (dO, "dO")):
         _same_dtype(el, t, "el", n)
-    n_l = el.size(0)
     if o.shape != (n_l,) + tuple(V.shape[1:]) or stats.numel() != n_l * h * 2:
         raise RuntimeError("%s: o must be %s and stats (n_src, h, 2), got %s and %s"
                            % (fn, (n_l,) + tuple(V.shape[1:]), tuple(o.shape), tuple(stats.shape)))
     dO = dO.contiguous()
     if dO.shape != o.shape:
         raise RuntimeError("%s: dO must match o %s, got %s" % (fn, tuple(o.shape), tuple(dO.shape)))
-    e = eid_r.size(0)
     d_el, d_er, dV = torch.empty_like(el), torch.empty_like(er), torch.empty_like(V)
+    d_ee = ()       # with ee: [dee], an empty (0,) tensor and a NULL pointer where it is not wanted
+    if edge:
+        d_ee = (torch.empty_like(ee) if need_dee else torch.empty((0,), dtype=ee.dtype, device=ee.device),)
     ws = torch.empty(max(n_l * h * 4, 1), dtype=el.dtype, device=el.device)      # (el, m, 1 / l, D) per (node, head)
     with _lib.device_guard(el.device):
         plan_r = _plan(row, indptr_r, eid_r, indices_r, er.size(0))
         plan_c = _plan(col, indptr_c, eid_c, indices_c, n_l)
         check(getattr(lib(), "graphop_" + fn)(
             dtype_code(el), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c),
-            ptr(eid_c), ptr(indices_c), ptr(el), ptr(er), ptr(V), ptr(o), ptr(stats), ptr(dO), ptr(d_el), ptr(d_er),
-            ptr(dV), ptr(ws), ws.numel() * ws.element_size(), row.size(0), col.size(0), e, n_l, er.size(0), h, d,
+            ptr(eid_c), ptr(indices_c), ptr(el), ptr(er), *(ptr(t) for t, _ in edge), ptr(V), ptr(o), ptr(stats),
+            ptr(dO), ptr(d_el), ptr(d_er), *(ptr(t) if need_dee else _NULL for t in d_ee), ptr(dV), ptr(ws),
+            ws.numel() * ws.element_size(), row.size(0), col.size(0), e, n_l, er.size(0), h, d,
             float(negative_slope), *drop, plan_r.handle, plan_c.handle, stream_of(el)))
-    return [d_el, d_er, dV]
+    return [d_el, d_er, *d_ee, dV]
 
 
 def gat_attention_forward(row, indptr, eid, indices, el, er, V, negative_slope=0.2):
@@ -710,24 +721,8 @@ def gat_edge_attention_forward(row, indptr, eid, indices, el, er, ee, V, negativ
     edge id ((n_edges) for 1-D el / er, else (n_edges, h)); m_ij is the multiplier of edge_dropout_mask, 1 at p = 0.
     stats (n_src, h, 2) = (row max, 1 / sum exp) of the undropped scores.  No edge-sized tensor is made."""
     fn = "gat_edge_attention_forward"
-    drop = _drop_args(fn, p, seed, offset)
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices"), (el, "el"), (er, "er"),
-                 (ee, "ee"), (V, "V")):
-        _check_input(t, n)
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices")):
-        _check_index(t, n)
-    h, d = _gat_attn_shapes(el, er, V, fn)
-    e, n_l = eid.size(0), el.size(0)
-    _gat_edge_term(el, ee, e, h, fn)
-    o = torch.empty((n_l,) + tuple(V.shape[1:]), dtype=V.dtype, device=V.device)
-    stats = torch.empty((n_l, h, 2), dtype=el.dtype, device=el.device)
-    with _lib.device_guard(el.device):
-        plan = _plan(row, indptr, eid, indices, er.size(0))
-        check(lib().graphop_gat_edge_attention_forward(
-            dtype_code(el), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(el), ptr(er), ptr(ee), ptr(V), ptr(o),
-            ptr(stats), row.size(0), e, n_l, er.size(0), h, d, float(negative_slope), *drop, plan.handle,
-            stream_of(el)))
-    return [o, stats]
+    return _gat_attention_forward(fn, row, indptr, eid, indices, el, er, V, negative_slope,
+                                  _drop_args(fn, p, seed, offset), ee)
 
 
 def gat_edge_attention_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, ee, V, o,
@@ -737,39 +732,9 @@ def gat_edge_attention_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, 
     tensor made (edge ids that no row-major slot names get 0); with need_dee=False it is an empty (0,) tensor and
     nothing edge-sized is written."""
     fn = "gat_edge_attention_backward"
-    drop = _drop_args(fn, p, seed, offset)
-    names = ("row", "indptr_r", "eid_r", "indices_r", "col", "indptr_c", "eid_c", "indices_c")
-    idx = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
-    for t, n in zip(idx + (el, er, ee, V, o, stats), names + ("el", "er", "ee", "V", "o", "stats")):
-        _check_input(t, n)
-    for t, n in zip(idx, names):
-        _check_index(t, n)
-    if not isinstance(dO, torch.Tensor) or not dO.is_cuda:
-        raise RuntimeError("dO must be a CUDA tensor")
-    h, d = _gat_attn_shapes(el, er, V, fn)
-    e, n_l = eid_r.size(0), el.size(0)
-    _gat_edge_term(el, ee, e, h, fn)
-    for t, n in ((o, "o"), (stats, "stats"), (dO, "dO")):
-        _same_dtype(el, t, "el", n)
-    if o.shape != (n_l,) + tuple(V.shape[1:]) or stats.numel() != n_l * h * 2:
-        raise RuntimeError("%s: o must be %s and stats (n_src, h, 2), got %s and %s"
-                           % (fn, (n_l,) + tuple(V.shape[1:]), tuple(o.shape), tuple(stats.shape)))
-    dO = dO.contiguous()
-    if dO.shape != o.shape:
-        raise RuntimeError("%s: dO must match o %s, got %s" % (fn, tuple(o.shape), tuple(dO.shape)))
-    d_el, d_er, dV = torch.empty_like(el), torch.empty_like(er), torch.empty_like(V)
-    d_ee = torch.empty_like(ee) if need_dee else torch.empty((0,), dtype=ee.dtype, device=ee.device)
-    ws = torch.empty(max(n_l * h * 4, 1), dtype=el.dtype, device=el.device)      # (el, m, 1 / l, D) per (node, head)
-    with _lib.device_guard(el.device):
-        plan_r = _plan(row, indptr_r, eid_r, indices_r, er.size(0))
-        plan_c = _plan(col, indptr_c, eid_c, indices_c, n_l)
-        check(lib().graphop_gat_edge_attention_backward(
-            dtype_code(el), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c),
-            ptr(eid_c), ptr(indices_c), ptr(el), ptr(er), ptr(ee), ptr(V), ptr(o), ptr(stats), ptr(dO), ptr(d_el),
-            ptr(d_er), ptr(d_ee) if need_dee else _NULL, ptr(dV), ptr(ws), ws.numel() * ws.element_size(), row.size(0),
-            col.size(0), e, n_l, er.size(0), h, d, float(negative_slope), *drop, plan_r.handle, plan_c.handle,
-            stream_of(el)))
-    return [d_el, d_er, d_ee, dV]
+    return _gat_attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V, o,
+                                   stats, dO, negative_slope, _drop_args(fn, p, seed, offset), ee, need_dee)
+
 
 
 def prepare(graph, h=1, d=64, dtype=torch.float32, fused=True):

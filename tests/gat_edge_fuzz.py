@@ -144,7 +144,7 @@ def fast_shape(case):
 
 
 def tables_aligned(case):
-    """el, er and V need 16 bytes; ee its item width, 4 * min(h, 4) bytes (edge_aligned).  The drawn table sits one
+    """el, er and V need 16 bytes; ee its item width, 4 * min(h, 4) bytes (gat_aligned).  The drawn table sits one
     element off: 4 bytes in fp32 (8 in fp64, where nothing is fast anyway)."""
     if case.misaligned < 0:
         return True

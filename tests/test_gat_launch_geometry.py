@@ -41,7 +41,7 @@ CAP_HD = [(1, 64), (4, 32), (8, 32)]           # one shape per row width (64, 12
 LONG_ROWS = (1024, 1025, 2049, 5000)           # around the long-segment bound of the stats kernel (1024 slots)
 BLOCK = 256                                    # threads of a fast workgroup
 DEFAULT_N_CU = 256                             # MI355X: sizes the graphs of the reference check without a GPU
-MAX_ROW_BLOCKS = 8192                          # workgroups of the GATv2 row pass at most (gatv2.hip)
+MAX_ROW_BLOCKS = 8192                          # workgroups of a GATv2 row pass at most (kGatMaxRowBlocks, host_gat.h)
 
 FUSED_FAST = {"gat_attn_stats": "k_gat_attn_stats_f32", "gat_attn_fwd": "k_gat_attn_fwd_f32",
               "gat_attn_pack": "k_gat_attn_pack_f32", "gat_attn_bwd_row": "k_gat_attn_bwd_row_f32",
@@ -65,7 +65,7 @@ def _groups_wanted(n_cu, G):
 
 
 def _cpg(n_chunks, n_cu, G, cap):
-    """gat_cpg (gat.hip), gatv2_cpg (gatv2.hip), gat_attn_cpg (gat_attention.hip)"""
+    """gat_cpg (host_gat.h): the one rule of every pass of the family; a cap below 1 counts as 1"""
     return max(1, min(n_chunks // _groups_wanted(n_cu, G), max(cap, 1)))
 
 
