@@ -28,6 +28,13 @@
 #define CHECK_CONTIGUOUS(x) TORCH_CHECK((x).is_contiguous(), #x " must be contiguous")   // graphop.cpp:5
 #define CHECK_INPUT(x) CHECK_CUDA(x); CHECK_CONTIGUOUS(x)                                // graphop.cpp:6
 #define CHECK_INDEX(x) TORCH_CHECK((x).scalar_type() == at::kLong, "expected scalar type Long but found ", (x).scalar_type(), " (" #x ")")
+// the index arrays of one CSR orientation, with and without `indices`; macros, so that the messages carry the caller's
+// spelling of each argument ("indptr_t must be contiguous", "... (eid_c)")
+#define CHECK_CSR3(row, indptr, eid) \
+  CHECK_INPUT(row); CHECK_INPUT(indptr); CHECK_INPUT(eid); CHECK_INDEX(row); CHECK_INDEX(indptr); CHECK_INDEX(eid)
+#define CHECK_CSR(row, indptr, eid, indices)                                     \
+  CHECK_INPUT(row); CHECK_INPUT(indptr); CHECK_INPUT(eid); CHECK_INPUT(indices); \
+  CHECK_INDEX(row); CHECK_INDEX(indptr); CHECK_INDEX(eid); CHECK_INDEX(indices)
 // every value operand of one call has one dtype (the reference's data<scalar_t>() throws otherwise): the C ABI takes
 // raw pointers plus ONE dtype code, so a mismatch here would be an out-of-bounds access on the device
 #define CHECK_SAME_DTYPE(a, b) TORCH_CHECK((a).scalar_type() == (b).scalar_type(), "expected " #a " and " #b " to have the same dtype, got ", (a).scalar_type(), " and ", (b).scalar_type())
@@ -171,13 +178,35 @@ at::Tensor edge_out(const at::Tensor& like, int64_t e, int64_t h) {   // (e) if 
   return h == 1 ? at::empty({e}, like.options()) : at::empty({e, h}, like.options());
 }
 
+std::vector<int64_t> with_rows(const at::Tensor& V, int64_t n_rows) {   // o of the fused GAT layers: V's layout, n_src rows
+  std::vector<int64_t> shape(V.sizes().begin(), V.sizes().end());
+  shape[0] = n_rows;
+  return shape;
+}
+
+// the row-pass partials of the GATv2 backwards, in values: the workspace minimum of include/graphop_hip.h
+int64_t gatv2_row_pass_values(int64_t n_row_chunks, int64_t h, int64_t d) {
+  return std::min<int64_t>((n_row_chunks + 15) / 16, 8192) * h * d;
+}
+
+// what a fused backward saved from its forward, o (oshape) and stats (n_src, h, 2), and the gradient of o -> that
+// gradient, contiguous
+at::Tensor saved_checked(const char* fn, at::IntArrayRef oshape, int64_t n_src, int64_t h, const at::Tensor& o,
+                         const at::Tensor& stats, const at::Tensor& dO_) {
+  TORCH_CHECK(o.sizes() == oshape && stats.numel() == n_src * h * 2, fn, ": o must be ", oshape,
+              " and stats (n_src, h, 2), got ", o.sizes(), " and ", stats.sizes());
+  at::Tensor dO = dO_.contiguous();
+  TORCH_CHECK(dO.sizes() == o.sizes(), fn, ": dO must match o ", o.sizes(), ", got ", dO.sizes());
+  return dO;
+}
+
 }  // namespace
 
 // ---- the eight functions (graphop.cpp:16-214) ------------------------------------------------------
 at::Tensor maskedmm_csr_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
                                 const at::Tensor& indices, const at::Tensor& A, const at::Tensor& B) {
-  CHECK_INPUT(row); CHECK_INPUT(indptr); CHECK_INPUT(eid); CHECK_INPUT(indices); CHECK_INPUT(A); CHECK_INPUT(B);
-  CHECK_INDEX(row); CHECK_INDEX(indptr); CHECK_INDEX(eid); CHECK_INDEX(indices);
+  CHECK_CSR(row, indptr, eid, indices);
+  CHECK_INPUT(A); CHECK_INPUT(B);
   CHECK_SAME_DTYPE(A, B);
   DeviceGuard dg(A);
   const int64_t e = eid.size(0), d = A.size(-1), h = A.dim() == 2 ? 1 : A.size(1);   // graphop_kernel.cu:282-283
@@ -194,10 +223,9 @@ std::vector<at::Tensor> maskedmm_csr_backward(const at::Tensor& row, const at::T
                                               const at::Tensor& col, const at::Tensor& indptr_c,
                                               const at::Tensor& eid_c, const at::Tensor& indices_c,
                                               const at::Tensor& A, const at::Tensor& B, const at::Tensor& dy_) {
-  CHECK_INPUT(row); CHECK_INPUT(indptr_r); CHECK_INPUT(eid_r); CHECK_INPUT(indices_r);
-  CHECK_INPUT(col); CHECK_INPUT(indptr_c); CHECK_INPUT(eid_c); CHECK_INPUT(indices_c); CHECK_INPUT(A); CHECK_INPUT(B);
-  CHECK_INDEX(row); CHECK_INDEX(indptr_r); CHECK_INDEX(eid_r); CHECK_INDEX(indices_r);
-  CHECK_INDEX(col); CHECK_INDEX(indptr_c); CHECK_INDEX(eid_c); CHECK_INDEX(indices_c);
+  CHECK_CSR(row, indptr_r, eid_r, indices_r);
+  CHECK_CSR(col, indptr_c, eid_c, indices_c);
+  CHECK_INPUT(A); CHECK_INPUT(B);
   CHECK_CUDA(dy_);
   const at::Tensor dy = dy_.contiguous();   // the reference forgets this check (graphop.cpp:120-129)
   CHECK_SAME_DTYPE(A, B); CHECK_SAME_DTYPE(A, dy); CHECK_EDGE_ROWS(dy, eid_r.size(0));
@@ -216,8 +244,8 @@ std::vector<at::Tensor> maskedmm_csr_backward(const at::Tensor& row, const at::T
 
 at::Tensor node_mul_edge_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
                                  const at::Tensor& A, const at::Tensor& B) {
-  CHECK_INPUT(row); CHECK_INPUT(indptr); CHECK_INPUT(eid); CHECK_INPUT(A); CHECK_INPUT(B);
-  CHECK_INDEX(row); CHECK_INDEX(indptr); CHECK_INDEX(eid);
+  CHECK_CSR3(row, indptr, eid);
+  CHECK_INPUT(A); CHECK_INPUT(B);
   CHECK_SAME_DTYPE(A, B);
   DeviceGuard dg(A);
   const int64_t e = eid.size(0), d = A.size(-1), h = A.dim() == 2 ? 1 : A.size(1);
@@ -233,8 +261,8 @@ at::Tensor node_mul_edge_forward(const at::Tensor& row, const at::Tensor& indptr
 std::vector<at::Tensor> node_mul_edge_backward(const at::Tensor& row, const at::Tensor& indptr,
                                                const at::Tensor& eid, const at::Tensor& A, const at::Tensor& B,
                                                const at::Tensor& dy_) {
-  CHECK_INPUT(row); CHECK_INPUT(indptr); CHECK_INPUT(eid); CHECK_INPUT(A); CHECK_INPUT(B);
-  CHECK_INDEX(row); CHECK_INDEX(indptr); CHECK_INDEX(eid);
+  CHECK_CSR3(row, indptr, eid);
+  CHECK_INPUT(A); CHECK_INPUT(B);
   CHECK_CUDA(dy_);
   const at::Tensor dy = dy_.contiguous();
   CHECK_SAME_DTYPE(A, B); CHECK_SAME_DTYPE(A, dy); CHECK_EDGE_ROWS(dy, eid.size(0));
@@ -251,8 +279,8 @@ std::vector<at::Tensor> node_mul_edge_backward(const at::Tensor& row, const at::
 
 at::Tensor sparse_softmax_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
                                   const at::Tensor& x) {
-  CHECK_INPUT(row); CHECK_INPUT(indptr); CHECK_INPUT(eid); CHECK_INPUT(x);
-  CHECK_INDEX(row); CHECK_INDEX(indptr); CHECK_INDEX(eid);
+  CHECK_CSR3(row, indptr, eid);
+  CHECK_INPUT(x);
   CHECK_EDGE_ROWS(x, eid.size(0));
   DeviceGuard dg(x);
   const int64_t h = x.dim() == 2 ? x.size(1) : 1;
@@ -272,8 +300,8 @@ at::Tensor sparse_softmax_forward(const at::Tensor& row, const at::Tensor& indpt
 
 at::Tensor sparse_softmax_backward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
                                    const at::Tensor& y, const at::Tensor& dy_) {
-  CHECK_INPUT(row); CHECK_INPUT(indptr); CHECK_INPUT(eid); CHECK_INPUT(y);
-  CHECK_INDEX(row); CHECK_INDEX(indptr); CHECK_INDEX(eid);
+  CHECK_CSR3(row, indptr, eid);
+  CHECK_INPUT(y);
   CHECK_CUDA(dy_);
   const at::Tensor dy = dy_.contiguous();
   CHECK_SAME_DTYPE(y, dy); CHECK_EDGE_ROWS(y, eid.size(0)); CHECK_EDGE_ROWS(dy, eid.size(0));
@@ -296,8 +324,8 @@ at::Tensor sparse_softmax_backward(const at::Tensor& row, const at::Tensor& indp
 
 at::Tensor vector_spmm_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
                                const at::Tensor& indices, const at::Tensor& edata, const at::Tensor& x) {
-  CHECK_INPUT(row); CHECK_INPUT(indptr); CHECK_INPUT(eid); CHECK_INPUT(indices); CHECK_INPUT(edata); CHECK_INPUT(x);
-  CHECK_INDEX(row); CHECK_INDEX(indptr); CHECK_INDEX(eid); CHECK_INDEX(indices);
+  CHECK_CSR(row, indptr, eid, indices);
+  CHECK_INPUT(edata); CHECK_INPUT(x);
   CHECK_SAME_DTYPE(edata, x); CHECK_EDGE_ROWS(edata, eid.size(0));
   DeviceGuard dg(x);
   const int64_t h = edata.dim() == 2 ? edata.size(1) : 1, d = x.size(-1);   // graphop_kernel.cu:520
@@ -314,11 +342,9 @@ std::vector<at::Tensor> vector_spmm_backward(const at::Tensor& row, const at::Te
                                              const at::Tensor& indptr_t, const at::Tensor& eid_t,
                                              const at::Tensor& indices_t, const at::Tensor& edata,
                                              const at::Tensor& dy, const at::Tensor& x) {   // NB dy before x, graphop.cpp:199-201
-  CHECK_INPUT(row); CHECK_INPUT(indptr); CHECK_INPUT(eid); CHECK_INPUT(indices);
-  CHECK_INPUT(col); CHECK_INPUT(indptr_t); CHECK_INPUT(eid_t); CHECK_INPUT(indices_t);
+  CHECK_CSR(row, indptr, eid, indices);
+  CHECK_CSR(col, indptr_t, eid_t, indices_t);
   CHECK_INPUT(edata); CHECK_INPUT(dy); CHECK_INPUT(x);
-  CHECK_INDEX(row); CHECK_INDEX(indptr); CHECK_INDEX(eid); CHECK_INDEX(indices);
-  CHECK_INDEX(col); CHECK_INDEX(indptr_t); CHECK_INDEX(eid_t); CHECK_INDEX(indices_t);
   CHECK_SAME_DTYPE(edata, x); CHECK_SAME_DTYPE(dy, x); CHECK_EDGE_ROWS(edata, eid.size(0));
   DeviceGuard dg(x);
   const int64_t h = edata.dim() == 2 ? edata.size(1) : 1, d = x.size(-1);
@@ -337,8 +363,8 @@ std::vector<at::Tensor> vector_spmm_backward(const at::Tensor& row, const at::Te
 std::vector<at::Tensor> attention_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
                                           const at::Tensor& indices, const at::Tensor& Q, const at::Tensor& K,
                                           const at::Tensor& V) {
-  CHECK_INPUT(row); CHECK_INPUT(indptr); CHECK_INPUT(eid); CHECK_INPUT(indices); CHECK_INPUT(Q); CHECK_INPUT(K); CHECK_INPUT(V);
-  CHECK_INDEX(row); CHECK_INDEX(indptr); CHECK_INDEX(eid); CHECK_INDEX(indices);
+  CHECK_CSR(row, indptr, eid, indices);
+  CHECK_INPUT(Q); CHECK_INPUT(K); CHECK_INPUT(V);
   TORCH_CHECK(K.sizes() == V.sizes() && Q.sizes().slice(1) == K.sizes().slice(1),
               "attention_forward: Q (n_q,[h,]d), K and V (n_k,[h,]d) expected");
   CHECK_SAME_DTYPE(Q, K); CHECK_SAME_DTYPE(Q, V);
@@ -362,11 +388,9 @@ std::vector<at::Tensor> attention_backward(const at::Tensor& row, const at::Tens
                                            const at::Tensor& indices_c, const at::Tensor& Q, const at::Tensor& K,
                                            const at::Tensor& V, const at::Tensor& o, const at::Tensor& stats,
                                            const at::Tensor& dO_) {
-  CHECK_INPUT(row); CHECK_INPUT(indptr_r); CHECK_INPUT(eid_r); CHECK_INPUT(indices_r);
-  CHECK_INPUT(col); CHECK_INPUT(indptr_c); CHECK_INPUT(eid_c); CHECK_INPUT(indices_c);
+  CHECK_CSR(row, indptr_r, eid_r, indices_r);
+  CHECK_CSR(col, indptr_c, eid_c, indices_c);
   CHECK_INPUT(Q); CHECK_INPUT(K); CHECK_INPUT(V); CHECK_INPUT(o); CHECK_INPUT(stats);
-  CHECK_INDEX(row); CHECK_INDEX(indptr_r); CHECK_INDEX(eid_r); CHECK_INDEX(indices_r);
-  CHECK_INDEX(col); CHECK_INDEX(indptr_c); CHECK_INDEX(eid_c); CHECK_INDEX(indices_c);
   CHECK_CUDA(dO_);
   const at::Tensor dO = dO_.contiguous();
   CHECK_SAME_DTYPE(Q, K); CHECK_SAME_DTYPE(Q, V); CHECK_SAME_DTYPE(Q, o); CHECK_SAME_DTYPE(Q, stats); CHECK_SAME_DTYPE(Q, dO);
@@ -401,8 +425,8 @@ int64_t gat_heads(const at::Tensor& el, const at::Tensor& er, const char* fn) {
 at::Tensor gat_scores_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
                               const at::Tensor& indices, const at::Tensor& el, const at::Tensor& er,
                               double negative_slope) {
-  CHECK_INPUT(row); CHECK_INPUT(indptr); CHECK_INPUT(eid); CHECK_INPUT(indices); CHECK_INPUT(el); CHECK_INPUT(er);
-  CHECK_INDEX(row); CHECK_INDEX(indptr); CHECK_INDEX(eid); CHECK_INDEX(indices);
+  CHECK_CSR(row, indptr, eid, indices);
+  CHECK_INPUT(el); CHECK_INPUT(er);
   const int64_t h = gat_heads(el, er, "gat_scores_forward");
   DeviceGuard dg(el);
   const int64_t e = eid.size(0);
@@ -419,10 +443,9 @@ std::vector<at::Tensor> gat_scores_backward(const at::Tensor& row, const at::Ten
                                             const at::Tensor& indptr_c, const at::Tensor& eid_c,
                                             const at::Tensor& indices_c, const at::Tensor& el, const at::Tensor& er,
                                             const at::Tensor& dy_, double negative_slope) {
-  CHECK_INPUT(row); CHECK_INPUT(indptr_r); CHECK_INPUT(eid_r); CHECK_INPUT(indices_r);
-  CHECK_INPUT(col); CHECK_INPUT(indptr_c); CHECK_INPUT(eid_c); CHECK_INPUT(indices_c); CHECK_INPUT(el); CHECK_INPUT(er);
-  CHECK_INDEX(row); CHECK_INDEX(indptr_r); CHECK_INDEX(eid_r); CHECK_INDEX(indices_r);
-  CHECK_INDEX(col); CHECK_INDEX(indptr_c); CHECK_INDEX(eid_c); CHECK_INDEX(indices_c);
+  CHECK_CSR(row, indptr_r, eid_r, indices_r);
+  CHECK_CSR(col, indptr_c, eid_c, indices_c);
+  CHECK_INPUT(el); CHECK_INPUT(er);
   CHECK_CUDA(dy_);
   const at::Tensor dy = dy_.contiguous();
   const int64_t h = gat_heads(el, er, "gat_scores_backward");
@@ -459,9 +482,8 @@ std::pair<int64_t, int64_t> gatv2_shapes(const at::Tensor& xl, const at::Tensor&
 at::Tensor gatv2_scores_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
                                 const at::Tensor& indices, const at::Tensor& xl, const at::Tensor& xr,
                                 const at::Tensor& att, double negative_slope) {
-  CHECK_INPUT(row); CHECK_INPUT(indptr); CHECK_INPUT(eid); CHECK_INPUT(indices); CHECK_INPUT(xl); CHECK_INPUT(xr);
-  CHECK_INPUT(att);
-  CHECK_INDEX(row); CHECK_INDEX(indptr); CHECK_INDEX(eid); CHECK_INDEX(indices);
+  CHECK_CSR(row, indptr, eid, indices);
+  CHECK_INPUT(xl); CHECK_INPUT(xr); CHECK_INPUT(att);
   const auto hd = gatv2_shapes(xl, xr, att, "gatv2_scores_forward");
   const int64_t h = hd.first, d = hd.second;
   DeviceGuard dg(xl);
@@ -481,11 +503,9 @@ std::vector<at::Tensor> gatv2_scores_backward(const at::Tensor& row, const at::T
                                               const at::Tensor& eid_c, const at::Tensor& indices_c,
                                               const at::Tensor& xl, const at::Tensor& xr, const at::Tensor& att,
                                               const at::Tensor& dy_, double negative_slope) {
-  CHECK_INPUT(row); CHECK_INPUT(indptr_r); CHECK_INPUT(eid_r); CHECK_INPUT(indices_r);
-  CHECK_INPUT(col); CHECK_INPUT(indptr_c); CHECK_INPUT(eid_c); CHECK_INPUT(indices_c); CHECK_INPUT(xl); CHECK_INPUT(xr);
-  CHECK_INPUT(att);
-  CHECK_INDEX(row); CHECK_INDEX(indptr_r); CHECK_INDEX(eid_r); CHECK_INDEX(indices_r);
-  CHECK_INDEX(col); CHECK_INDEX(indptr_c); CHECK_INDEX(eid_c); CHECK_INDEX(indices_c);
+  CHECK_CSR(row, indptr_r, eid_r, indices_r);
+  CHECK_CSR(col, indptr_c, eid_c, indices_c);
+  CHECK_INPUT(xl); CHECK_INPUT(xr); CHECK_INPUT(att);
   CHECK_CUDA(dy_);
   const at::Tensor dy = dy_.contiguous();
   const auto hd = gatv2_shapes(xl, xr, att, "gatv2_scores_backward");
@@ -496,9 +516,7 @@ std::vector<at::Tensor> gatv2_scores_backward(const at::Tensor& row, const at::T
               ") values, got ", dy.sizes());
   DeviceGuard dg(xl);
   auto dxl = at::empty_like(xl), dxr = at::empty_like(xr), datt = at::empty_like(att);
-  // the workspace minimum of include/graphop_hip.h: min(ceil(n_row_chunks / 16), 8192) * h * d values
-  const int64_t ws_values = std::min<int64_t>((row.size(0) + 15) / 16, 8192) * h * d;
-  auto ws = at::empty({std::max<int64_t>(ws_values, 1)}, xl.options());
+  auto ws = at::empty({std::max<int64_t>(gatv2_row_pass_values(row.size(0), h, d), 1)}, xl.options());
   const auto ppr = get_plan(row, indptr_r, eid_r, indices_r, xr.size(0));
   const auto ppc = get_plan(col, indptr_c, eid_c, indices_c, xl.size(0));
   const auto &pr = *ppr, &pc = *ppc;
@@ -530,9 +548,8 @@ std::vector<at::Tensor> gatv2_attention_forward_impl(const char* fn, const at::T
                                                      const at::Tensor& eid, const at::Tensor& indices,
                                                      const at::Tensor& xl, const at::Tensor& xr, const at::Tensor& att,
                                                      double negative_slope, const DropSpec* drop) {
-  CHECK_INPUT(row); CHECK_INPUT(indptr); CHECK_INPUT(eid); CHECK_INPUT(indices); CHECK_INPUT(xl); CHECK_INPUT(xr);
-  CHECK_INPUT(att);
-  CHECK_INDEX(row); CHECK_INDEX(indptr); CHECK_INDEX(eid); CHECK_INDEX(indices);
+  CHECK_CSR(row, indptr, eid, indices);
+  CHECK_INPUT(xl); CHECK_INPUT(xr); CHECK_INPUT(att);
   const auto hd = gatv2_shapes(xl, xr, att, fn);
   const int64_t h = hd.first, d = hd.second;
   DeviceGuard dg(xl);
@@ -578,25 +595,20 @@ std::vector<at::Tensor> gatv2_attention_backward_impl(const char* fn, const at::
                                                       const at::Tensor& xr, const at::Tensor& att, const at::Tensor& o,
                                                       const at::Tensor& stats, const at::Tensor& dO_,
                                                       double negative_slope, const DropSpec* drop) {
-  CHECK_INPUT(row); CHECK_INPUT(indptr_r); CHECK_INPUT(eid_r); CHECK_INPUT(indices_r);
-  CHECK_INPUT(col); CHECK_INPUT(indptr_c); CHECK_INPUT(eid_c); CHECK_INPUT(indices_c); CHECK_INPUT(xl); CHECK_INPUT(xr);
-  CHECK_INPUT(att); CHECK_INPUT(o); CHECK_INPUT(stats);
-  CHECK_INDEX(row); CHECK_INDEX(indptr_r); CHECK_INDEX(eid_r); CHECK_INDEX(indices_r);
-  CHECK_INDEX(col); CHECK_INDEX(indptr_c); CHECK_INDEX(eid_c); CHECK_INDEX(indices_c);
+  CHECK_CSR(row, indptr_r, eid_r, indices_r);
+  CHECK_CSR(col, indptr_c, eid_c, indices_c);
+  CHECK_INPUT(xl); CHECK_INPUT(xr); CHECK_INPUT(att); CHECK_INPUT(o); CHECK_INPUT(stats);
   CHECK_CUDA(dO_);
   const auto hd = gatv2_shapes(xl, xr, att, fn);
   const int64_t h = hd.first, d = hd.second;
   CHECK_SAME_DTYPE(xl, o); CHECK_SAME_DTYPE(xl, stats); CHECK_SAME_DTYPE(xl, dO_);
   const int64_t n_l = xl.size(0);
-  TORCH_CHECK(o.sizes() == xl.sizes() && stats.numel() == n_l * h * 2, fn, ": o must be ", xl.sizes(),
-              " and stats (n_src, h, 2), got ", o.sizes(), " and ", stats.sizes());
-  const at::Tensor dO = dO_.contiguous();
-  TORCH_CHECK(dO.sizes() == o.sizes(), fn, ": dO must match o ", o.sizes(), ", got ", dO.sizes());
+  const at::Tensor dO = saved_checked(fn, xl.sizes(), n_l, h, o, stats, dO_);
   DeviceGuard dg(xl);
   const int64_t e = eid_r.size(0);
   auto dxl = at::empty_like(xl), dxr = at::empty_like(xr), datt = at::empty_like(att);
-  // the workspace minimum of include/graphop_hip.h: n_l * h * 4 + min(ceil(n_row_chunks / 16), 8192) * h * d values
-  const int64_t ws_values = n_l * h * 4 + std::min<int64_t>((row.size(0) + 15) / 16, 8192) * h * d;
+  // the workspace minimum of include/graphop_hip.h: (m, 1 / l, D, 0) per (node, head), then the row-pass partials
+  const int64_t ws_values = n_l * h * 4 + gatv2_row_pass_values(row.size(0), h, d);
   auto ws = at::empty({std::max<int64_t>(ws_values, 1)}, xl.options());
   const auto ppr = get_plan(row, indptr_r, eid_r, indices_r, xr.size(0));
   const auto ppc = get_plan(col, indptr_c, eid_c, indices_c, n_l);
@@ -653,25 +665,39 @@ std::pair<int64_t, int64_t> gat_attn_shapes(const at::Tensor& el, const at::Tens
   return {h, V.size(-1)};
 }
 
-// drop == nullptr: graphop_gat_attention_forward, else its dropout form
+// the edge term of graphop_gat_edge_attention_*: (n_edges) for 1-D el / er, else (n_edges, h), in el's dtype
+void gat_edge_term(const at::Tensor& el, const at::Tensor& ee, int64_t n_edges, int64_t h, const char* fn) {
+  CHECK_INPUT(ee);
+  CHECK_SAME_DTYPE(el, ee);
+  const bool ok = el.dim() == 1 ? (ee.dim() == 1 && ee.size(0) == n_edges)
+                                : (ee.dim() == 2 && ee.size(0) == n_edges && ee.size(1) == h);
+  TORCH_CHECK(ok, fn, ": ee must be (n_edges) for 1-D el / er, else (n_edges, h) with n_edges = ", n_edges, " and h = ",
+              h, ", got ee ", ee.sizes(), ", el ", el.sizes());
+}
+
+// graphop_gat_attention_forward (drop == nullptr), its dropout form or, with the edge term ee (which needs drop),
+// graphop_gat_edge_attention_forward, as `fn`
 std::vector<at::Tensor> gat_attention_forward_impl(const char* fn, const at::Tensor& row, const at::Tensor& indptr,
                                                    const at::Tensor& eid, const at::Tensor& indices,
                                                    const at::Tensor& el, const at::Tensor& er, const at::Tensor& V,
-                                                   double negative_slope, const DropSpec* drop) {
-  CHECK_INPUT(row); CHECK_INPUT(indptr); CHECK_INPUT(eid); CHECK_INPUT(indices); CHECK_INPUT(el); CHECK_INPUT(er);
-  CHECK_INPUT(V);
-  CHECK_INDEX(row); CHECK_INDEX(indptr); CHECK_INDEX(eid); CHECK_INDEX(indices);
+                                                   double negative_slope, const DropSpec* drop,
+                                                   const at::Tensor* ee = nullptr) {
+  CHECK_CSR(row, indptr, eid, indices);
+  CHECK_INPUT(el); CHECK_INPUT(er); CHECK_INPUT(V);
   const auto hd = gat_attn_shapes(el, er, V, fn);
   const int64_t h = hd.first, d = hd.second;
-  DeviceGuard dg(el);
   const int64_t e = eid.size(0), n_l = el.size(0);
-  std::vector<int64_t> oshape(V.sizes().begin(), V.sizes().end());
-  oshape[0] = n_l;
-  auto o = at::empty(oshape, V.options());
+  if (ee) gat_edge_term(el, *ee, e, h, fn);
+  DeviceGuard dg(el);
+  auto o = at::empty(with_rows(V, n_l), V.options());
   auto stats = at::empty({n_l, h, 2}, el.options());
   const auto pp = get_plan(row, indptr, eid, indices, er.size(0));
   const auto& p = *pp;
-  if (drop)
+  if (ee)
+    check(graphop_gat_edge_attention_forward(dtype_code(el), ip(row), ip(indptr), ip(eid), ip(indices), vp(el), vp(er),
+                                             vp(*ee), vp(V), vp(o), vp(stats), row.size(0), e, n_l, er.size(0), h, d,
+                                             negative_slope, drop->p, drop->seed, drop->offset, p.plan, stream_of(el)));
+  else if (drop)
     check(graphop_gat_attention_dropout_forward(dtype_code(el), ip(row), ip(indptr), ip(eid), ip(indices), vp(el),
                                                 vp(er), vp(V), vp(o), vp(stats), row.size(0), e, n_l, er.size(0), h, d,
                                                 negative_slope, drop->p, drop->seed, drop->offset, p.plan,
@@ -699,37 +725,51 @@ std::vector<at::Tensor> gat_attention_dropout_forward(const at::Tensor& row, con
   return gat_attention_forward_impl(fn, row, indptr, eid, indices, el, er, V, negative_slope, &drop);
 }
 
+std::vector<at::Tensor> gat_edge_attention_forward(const at::Tensor& row, const at::Tensor& indptr,
+                                                   const at::Tensor& eid, const at::Tensor& indices,
+                                                   const at::Tensor& el, const at::Tensor& er, const at::Tensor& ee,
+                                                   const at::Tensor& V, double negative_slope, double p, int64_t seed,
+                                                   int64_t offset) {
+  const char* fn = "gat_edge_attention_forward";
+  const DropSpec drop = drop_spec(fn, p, seed, offset);
+  return gat_attention_forward_impl(fn, row, indptr, eid, indices, el, er, V, negative_slope, &drop, &ee);
+}
+
+// graphop_gat_attention_backward (drop == nullptr), its dropout form or, with the edge term ee (which needs drop),
+// graphop_gat_edge_attention_backward, as `fn`: -> {del, der, dV}, with ee {del, der, dee, dV}
 std::vector<at::Tensor> gat_attention_backward_impl(const char* fn, const at::Tensor& row, const at::Tensor& indptr_r,
                                                     const at::Tensor& eid_r, const at::Tensor& indices_r,
                                                     const at::Tensor& col, const at::Tensor& indptr_c,
                                                     const at::Tensor& eid_c, const at::Tensor& indices_c,
                                                     const at::Tensor& el, const at::Tensor& er, const at::Tensor& V,
                                                     const at::Tensor& o, const at::Tensor& stats,
-                                                    const at::Tensor& dO_, double negative_slope,
-                                                    const DropSpec* drop) {
-  CHECK_INPUT(row); CHECK_INPUT(indptr_r); CHECK_INPUT(eid_r); CHECK_INPUT(indices_r);
-  CHECK_INPUT(col); CHECK_INPUT(indptr_c); CHECK_INPUT(eid_c); CHECK_INPUT(indices_c); CHECK_INPUT(el); CHECK_INPUT(er);
-  CHECK_INPUT(V); CHECK_INPUT(o); CHECK_INPUT(stats);
-  CHECK_INDEX(row); CHECK_INDEX(indptr_r); CHECK_INDEX(eid_r); CHECK_INDEX(indices_r);
-  CHECK_INDEX(col); CHECK_INDEX(indptr_c); CHECK_INDEX(eid_c); CHECK_INDEX(indices_c);
+                                                    const at::Tensor& dO_, double negative_slope, const DropSpec* drop,
+                                                    const at::Tensor* ee = nullptr, bool need_dee = true) {
+  CHECK_CSR(row, indptr_r, eid_r, indices_r);
+  CHECK_CSR(col, indptr_c, eid_c, indices_c);
+  CHECK_INPUT(el); CHECK_INPUT(er); CHECK_INPUT(V); CHECK_INPUT(o); CHECK_INPUT(stats);
   CHECK_CUDA(dO_);
   const auto hd = gat_attn_shapes(el, er, V, fn);
   const int64_t h = hd.first, d = hd.second;
+  const int64_t e = eid_r.size(0), n_l = el.size(0);
+  if (ee) gat_edge_term(el, *ee, e, h, fn);
   CHECK_SAME_DTYPE(el, o); CHECK_SAME_DTYPE(el, stats); CHECK_SAME_DTYPE(el, dO_);
-  const int64_t n_l = el.size(0);
-  std::vector<int64_t> oshape(V.sizes().begin(), V.sizes().end());
-  oshape[0] = n_l;
-  TORCH_CHECK(o.sizes() == at::IntArrayRef(oshape) && stats.numel() == n_l * h * 2, fn, ": o must be ",
-              at::IntArrayRef(oshape), " and stats (n_src, h, 2), got ", o.sizes(), " and ", stats.sizes());
-  const at::Tensor dO = dO_.contiguous();
-  TORCH_CHECK(dO.sizes() == o.sizes(), fn, ": dO must match o ", o.sizes(), ", got ", dO.sizes());
+  const at::Tensor dO = saved_checked(fn, with_rows(V, n_l), n_l, h, o, stats, dO_);
   DeviceGuard dg(el);
-  const int64_t e = eid_r.size(0);
   auto d_el = at::empty_like(el), d_er = at::empty_like(er), dV = at::empty_like(V);
   auto ws = at::empty({std::max<int64_t>(n_l * h * 4, 1)}, el.options());   // (el, m, 1 / l, D) per (node, head)
   const auto ppr = get_plan(row, indptr_r, eid_r, indices_r, er.size(0));
   const auto ppc = get_plan(col, indptr_c, eid_c, indices_c, n_l);
   const auto &pr = *ppr, &pc = *ppc;
+  if (ee) {
+    auto d_ee = need_dee ? at::empty_like(*ee) : at::empty({0}, ee->options());   // the only edge-sized tensor made
+    check(graphop_gat_edge_attention_backward(
+        dtype_code(el), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c),
+        ip(indices_c), vp(el), vp(er), vp(*ee), vp(V), vp(o), vp(stats), vp(dO), vp(d_el), vp(d_er),
+        need_dee ? vp(d_ee) : nullptr, vp(dV), vp(ws), ws.numel() * ws.element_size(), row.size(0), col.size(0), e, n_l,
+        er.size(0), h, d, negative_slope, drop->p, drop->seed, drop->offset, pr.plan, pc.plan, stream_of(el)));
+    return {d_el, d_er, d_ee, dV};
+  }
   if (drop)
     check(graphop_gat_attention_dropout_backward(
         dtype_code(el), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c),
@@ -770,81 +810,18 @@ std::vector<at::Tensor> gat_attention_dropout_backward(const at::Tensor& row, co
                                      o, stats, dO, negative_slope, &drop);
 }
 
-// ---- the fused GAT attention op with an edge term (include/graphop_hip.h: graphop_gat_edge_attention_*) ------------
-void gat_edge_term(const at::Tensor& el, const at::Tensor& ee, int64_t n_edges, int64_t h, const char* fn) {
-  CHECK_INPUT(ee);
-  CHECK_SAME_DTYPE(el, ee);
-  const bool ok = el.dim() == 1 ? (ee.dim() == 1 && ee.size(0) == n_edges)
-                                : (ee.dim() == 2 && ee.size(0) == n_edges && ee.size(1) == h);
-  TORCH_CHECK(ok, fn, ": ee must be (n_edges) for 1-D el / er, else (n_edges, h) with n_edges = ", n_edges, " and h = ",
-              h, ", got ee ", ee.sizes(), ", el ", el.sizes());
-}
-
-std::vector<at::Tensor> gat_edge_attention_forward(const at::Tensor& row, const at::Tensor& indptr,
-                                                   const at::Tensor& eid, const at::Tensor& indices,
-                                                   const at::Tensor& el, const at::Tensor& er, const at::Tensor& ee,
-                                                   const at::Tensor& V, double negative_slope, double p, int64_t seed,
-                                                   int64_t offset) {
-  const char* fn = "gat_edge_attention_forward";
-  const DropSpec drop = drop_spec(fn, p, seed, offset);
-  CHECK_INPUT(row); CHECK_INPUT(indptr); CHECK_INPUT(eid); CHECK_INPUT(indices); CHECK_INPUT(el); CHECK_INPUT(er);
-  CHECK_INPUT(ee); CHECK_INPUT(V);
-  CHECK_INDEX(row); CHECK_INDEX(indptr); CHECK_INDEX(eid); CHECK_INDEX(indices);
-  const auto hd = gat_attn_shapes(el, er, V, fn);
-  const int64_t h = hd.first, d = hd.second;
-  const int64_t e = eid.size(0), n_l = el.size(0);
-  gat_edge_term(el, ee, e, h, fn);
-  DeviceGuard dg(el);
-  std::vector<int64_t> oshape(V.sizes().begin(), V.sizes().end());
-  oshape[0] = n_l;
-  auto o = at::empty(oshape, V.options());
-  auto stats = at::empty({n_l, h, 2}, el.options());
-  const auto pp = get_plan(row, indptr, eid, indices, er.size(0));
-  check(graphop_gat_edge_attention_forward(dtype_code(el), ip(row), ip(indptr), ip(eid), ip(indices), vp(el), vp(er),
-                                           vp(ee), vp(V), vp(o), vp(stats), row.size(0), e, n_l, er.size(0), h, d,
-                                           negative_slope, drop.p, drop.seed, drop.offset, pp->plan, stream_of(el)));
-  return {o, stats};
-}
-
 std::vector<at::Tensor> gat_edge_attention_backward(const at::Tensor& row, const at::Tensor& indptr_r,
                                                     const at::Tensor& eid_r, const at::Tensor& indices_r,
                                                     const at::Tensor& col, const at::Tensor& indptr_c,
                                                     const at::Tensor& eid_c, const at::Tensor& indices_c,
                                                     const at::Tensor& el, const at::Tensor& er, const at::Tensor& ee,
                                                     const at::Tensor& V, const at::Tensor& o, const at::Tensor& stats,
-                                                    const at::Tensor& dO_, double negative_slope, double p,
+                                                    const at::Tensor& dO, double negative_slope, double p,
                                                     int64_t seed, int64_t offset, bool need_dee) {
   const char* fn = "gat_edge_attention_backward";
   const DropSpec drop = drop_spec(fn, p, seed, offset);
-  CHECK_INPUT(row); CHECK_INPUT(indptr_r); CHECK_INPUT(eid_r); CHECK_INPUT(indices_r);
-  CHECK_INPUT(col); CHECK_INPUT(indptr_c); CHECK_INPUT(eid_c); CHECK_INPUT(indices_c); CHECK_INPUT(el); CHECK_INPUT(er);
-  CHECK_INPUT(ee); CHECK_INPUT(V); CHECK_INPUT(o); CHECK_INPUT(stats);
-  CHECK_INDEX(row); CHECK_INDEX(indptr_r); CHECK_INDEX(eid_r); CHECK_INDEX(indices_r);
-  CHECK_INDEX(col); CHECK_INDEX(indptr_c); CHECK_INDEX(eid_c); CHECK_INDEX(indices_c);
-  CHECK_CUDA(dO_);
-  const auto hd = gat_attn_shapes(el, er, V, fn);
-  const int64_t h = hd.first, d = hd.second;
-  const int64_t e = eid_r.size(0), n_l = el.size(0);
-  gat_edge_term(el, ee, e, h, fn);
-  CHECK_SAME_DTYPE(el, o); CHECK_SAME_DTYPE(el, stats); CHECK_SAME_DTYPE(el, dO_);
-  std::vector<int64_t> oshape(V.sizes().begin(), V.sizes().end());
-  oshape[0] = n_l;
-  TORCH_CHECK(o.sizes() == at::IntArrayRef(oshape) && stats.numel() == n_l * h * 2, fn, ": o must be ",
-              at::IntArrayRef(oshape), " and stats (n_src, h, 2), got ", o.sizes(), " and ", stats.sizes());
-  const at::Tensor dO = dO_.contiguous();
-  TORCH_CHECK(dO.sizes() == o.sizes(), fn, ": dO must match o ", o.sizes(), ", got ", dO.sizes());
-  DeviceGuard dg(el);
-  auto d_el = at::empty_like(el), d_er = at::empty_like(er), dV = at::empty_like(V);
-  auto d_ee = need_dee ? at::empty_like(ee) : at::empty({0}, ee.options());   // the only edge-sized tensor made
-  auto ws = at::empty({std::max<int64_t>(n_l * h * 4, 1)}, el.options());   // (el, m, 1 / l, D) per (node, head)
-  const auto ppr = get_plan(row, indptr_r, eid_r, indices_r, er.size(0));
-  const auto ppc = get_plan(col, indptr_c, eid_c, indices_c, n_l);
-  check(graphop_gat_edge_attention_backward(
-      dtype_code(el), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c), ip(indices_c),
-      vp(el), vp(er), vp(ee), vp(V), vp(o), vp(stats), vp(dO), vp(d_el), vp(d_er), need_dee ? vp(d_ee) : nullptr,
-      vp(dV), vp(ws), ws.numel() * ws.element_size(), row.size(0), col.size(0), e, n_l, er.size(0), h, d,
-      negative_slope, drop.p, drop.seed, drop.offset, ppr->plan, ppc->plan, stream_of(el)));
-  return {d_el, d_er, d_ee, dV};
+  return gat_attention_backward_impl(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V,
+                                     o, stats, dO, negative_slope, &drop, &ee, need_dee);
 }
 
 // m[e, k] = keep(i, j, k) / (1 - p) of the dropout forms as an edge tensor, over the row-major CSR
@@ -852,8 +829,7 @@ at::Tensor edge_dropout_mask(const at::Tensor& row, const at::Tensor& indptr, co
                              const at::Tensor& indices, int64_t h, double p, int64_t seed, int64_t offset,
                              at::ScalarType dtype) {
   const DropSpec drop = drop_spec("edge_dropout_mask", p, seed, offset);
-  CHECK_INPUT(row); CHECK_INPUT(indptr); CHECK_INPUT(eid); CHECK_INPUT(indices);
-  CHECK_INDEX(row); CHECK_INDEX(indptr); CHECK_INDEX(eid); CHECK_INDEX(indices);
+  CHECK_CSR(row, indptr, eid, indices);
   TORCH_CHECK(h >= 1 && (dtype == at::kFloat || dtype == at::kDouble),
               "edge_dropout_mask: h must be >= 1 and dtype float32 or float64, got h=", h, " dtype=", dtype);
   DeviceGuard dg(row);
@@ -975,86 +951,40 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
 }
 
 // ---- registration 2: torch.ops.graphop.* (schemas + CUDA(HIP) implementations) ------------------------------
-TORCH_LIBRARY(graphop, m) {
-  m.def("maskedmm_csr_forward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor A, Tensor B) -> Tensor");
-  m.def("maskedmm_csr_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor A, Tensor B, Tensor dy) -> Tensor[]");
-  m.def("node_mul_edge_forward(Tensor row, Tensor indptr, Tensor eid, Tensor A, Tensor B) -> Tensor");
-  m.def("node_mul_edge_backward(Tensor row, Tensor indptr, Tensor eid, Tensor A, Tensor B, Tensor dy) -> Tensor[]");
-  m.def("sparse_softmax_forward(Tensor row, Tensor indptr, Tensor eid, Tensor x) -> Tensor");
-  m.def("sparse_softmax_backward(Tensor row, Tensor indptr, Tensor eid, Tensor y, Tensor dy) -> Tensor");
-  m.def("vector_spmm_forward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor edata, Tensor x) -> Tensor");
-  m.def("vector_spmm_backward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor col, Tensor indptr_t, Tensor eid_t, Tensor indices_t, Tensor edata, Tensor dy, Tensor x) -> Tensor[]");
-  m.def("attention_forward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor Q, Tensor K, Tensor V) -> Tensor[]");
-  m.def("attention_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor Q, Tensor K, Tensor V, Tensor o, Tensor stats, Tensor dO) -> Tensor[]");
-  m.def("gat_scores_forward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, float negative_slope=0.2) -> Tensor");
-  m.def("gat_scores_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor dy, float negative_slope=0.2) -> Tensor[]");
-  m.def("gat_attention_forward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, Tensor V, float negative_slope=0.2) -> Tensor[]");
-  m.def("gat_attention_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor V, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2) -> Tensor[]");
-  m.def("gat_attention_dropout_forward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, Tensor V, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]");
-  m.def("gat_attention_dropout_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor V, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]");
-  m.def("edge_dropout_mask(Tensor row, Tensor indptr, Tensor eid, Tensor indices, int h, float p=0.0, int seed=0, int offset=0, ScalarType dtype=float) -> Tensor");
-  m.def("gatv2_scores_forward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor xl, Tensor xr, Tensor att, float negative_slope=0.2) -> Tensor");
-  m.def("gatv2_scores_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor dy, float negative_slope=0.2) -> Tensor[]");
-  m.def("gatv2_attention_forward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor xl, Tensor xr, Tensor att, float negative_slope=0.2) -> Tensor[]");
-  m.def("gatv2_attention_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2) -> Tensor[]");
-  m.def("gatv2_attention_dropout_forward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor xl, Tensor xr, Tensor att, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]");
-  m.def("gatv2_attention_dropout_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]");
-  m.def("gat_edge_attention_forward(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, Tensor ee, Tensor V, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]");
-  m.def("gat_edge_attention_backward(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor ee, Tensor V, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0, bool need_dee=True) -> Tensor[]");
-}
+// One row per op: its name, which is also its function's, and its schema (graphop.py's _SCHEMAS holds the same text
+// for the ctypes binding).  The rows expand into the definitions and into both dispatch keys below.
+#define GRAPHOP_OPS(X) \
+  X(maskedmm_csr_forward, "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor A, Tensor B) -> Tensor") \
+  X(maskedmm_csr_backward, "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor A, Tensor B, Tensor dy) -> Tensor[]") \
+  X(node_mul_edge_forward, "(Tensor row, Tensor indptr, Tensor eid, Tensor A, Tensor B) -> Tensor") \
+  X(node_mul_edge_backward, "(Tensor row, Tensor indptr, Tensor eid, Tensor A, Tensor B, Tensor dy) -> Tensor[]") \
+  X(sparse_softmax_forward, "(Tensor row, Tensor indptr, Tensor eid, Tensor x) -> Tensor") \
+  X(sparse_softmax_backward, "(Tensor row, Tensor indptr, Tensor eid, Tensor y, Tensor dy) -> Tensor") \
+  X(vector_spmm_forward, "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor edata, Tensor x) -> Tensor") \
+  X(vector_spmm_backward, "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor col, Tensor indptr_t, Tensor eid_t, Tensor indices_t, Tensor edata, Tensor dy, Tensor x) -> Tensor[]") \
+  X(attention_forward, "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor Q, Tensor K, Tensor V) -> Tensor[]") \
+  X(attention_backward, "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor Q, Tensor K, Tensor V, Tensor o, Tensor stats, Tensor dO) -> Tensor[]") \
+  X(gat_scores_forward, "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, float negative_slope=0.2) -> Tensor") \
+  X(gat_scores_backward, "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor dy, float negative_slope=0.2) -> Tensor[]") \
+  X(gat_attention_forward, "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, Tensor V, float negative_slope=0.2) -> Tensor[]") \
+  X(gat_attention_backward, "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor V, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2) -> Tensor[]") \
+  X(gat_attention_dropout_forward, "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, Tensor V, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]") \
+  X(gat_attention_dropout_backward, "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor V, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]") \
+  X(edge_dropout_mask, "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, int h, float p=0.0, int seed=0, int offset=0, ScalarType dtype=float) -> Tensor") \
+  X(gatv2_scores_forward, "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor xl, Tensor xr, Tensor att, float negative_slope=0.2) -> Tensor") \
+  X(gatv2_scores_backward, "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor dy, float negative_slope=0.2) -> Tensor[]") \
+  X(gatv2_attention_forward, "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor xl, Tensor xr, Tensor att, float negative_slope=0.2) -> Tensor[]") \
+  X(gatv2_attention_backward, "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2) -> Tensor[]") \
+  X(gatv2_attention_dropout_forward, "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor xl, Tensor xr, Tensor att, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]") \
+  X(gatv2_attention_dropout_backward, "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]") \
+  X(gat_edge_attention_forward, "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, Tensor ee, Tensor V, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]") \
+  X(gat_edge_attention_backward, "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor ee, Tensor V, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0, bool need_dee=True) -> Tensor[]")
+#define GRAPHOP_DEF(name, schema) m.def(#name schema);
+#define GRAPHOP_IMPL(name, schema) m.impl(#name, &name);
 
-TORCH_LIBRARY_IMPL(graphop, CUDA, m) {
-  m.impl("maskedmm_csr_forward", &maskedmm_csr_forward);
-  m.impl("maskedmm_csr_backward", &maskedmm_csr_backward);
-  m.impl("node_mul_edge_forward", &node_mul_edge_forward);
-  m.impl("node_mul_edge_backward", &node_mul_edge_backward);
-  m.impl("sparse_softmax_forward", &sparse_softmax_forward);
-  m.impl("sparse_softmax_backward", &sparse_softmax_backward);
-  m.impl("vector_spmm_forward", &vector_spmm_forward);
-  m.impl("vector_spmm_backward", &vector_spmm_backward);
-  m.impl("attention_forward", &attention_forward);
-  m.impl("attention_backward", &attention_backward);
-  m.impl("gat_scores_forward", &gat_scores_forward);
-  m.impl("gat_scores_backward", &gat_scores_backward);
-  m.impl("gat_attention_forward", &gat_attention_forward);
-  m.impl("gat_attention_backward", &gat_attention_backward);
-  m.impl("gat_attention_dropout_forward", &gat_attention_dropout_forward);
-  m.impl("gat_attention_dropout_backward", &gat_attention_dropout_backward);
-  m.impl("edge_dropout_mask", &edge_dropout_mask);
-  m.impl("gatv2_scores_forward", &gatv2_scores_forward);
-  m.impl("gatv2_scores_backward", &gatv2_scores_backward);
-  m.impl("gatv2_attention_forward", &gatv2_attention_forward);
-  m.impl("gatv2_attention_backward", &gatv2_attention_backward);
-  m.impl("gatv2_attention_dropout_forward", &gatv2_attention_dropout_forward);
-  m.impl("gatv2_attention_dropout_backward", &gatv2_attention_dropout_backward);
-  m.impl("gat_edge_attention_forward", &gat_edge_attention_forward);
-  m.impl("gat_edge_attention_backward", &gat_edge_attention_backward);
-}
+TORCH_LIBRARY(graphop, m) { GRAPHOP_OPS(GRAPHOP_DEF) }
 
-TORCH_LIBRARY_IMPL(graphop, CPU, m) {   // there is no CPU implementation: the reference's CHECK_CUDA message
-  m.impl("maskedmm_csr_forward", &maskedmm_csr_forward);
-  m.impl("maskedmm_csr_backward", &maskedmm_csr_backward);
-  m.impl("node_mul_edge_forward", &node_mul_edge_forward);
-  m.impl("node_mul_edge_backward", &node_mul_edge_backward);
-  m.impl("sparse_softmax_forward", &sparse_softmax_forward);
-  m.impl("sparse_softmax_backward", &sparse_softmax_backward);
-  m.impl("vector_spmm_forward", &vector_spmm_forward);
-  m.impl("vector_spmm_backward", &vector_spmm_backward);
-  m.impl("attention_forward", &attention_forward);
-  m.impl("attention_backward", &attention_backward);
-  m.impl("gat_scores_forward", &gat_scores_forward);
-  m.impl("gat_scores_backward", &gat_scores_backward);
-  m.impl("gat_attention_forward", &gat_attention_forward);
-  m.impl("gat_attention_backward", &gat_attention_backward);
-  m.impl("gat_attention_dropout_forward", &gat_attention_dropout_forward);
-  m.impl("gat_attention_dropout_backward", &gat_attention_dropout_backward);
-  m.impl("edge_dropout_mask", &edge_dropout_mask);
-  m.impl("gatv2_scores_forward", &gatv2_scores_forward);
-  m.impl("gatv2_scores_backward", &gatv2_scores_backward);
-  m.impl("gatv2_attention_forward", &gatv2_attention_forward);
-  m.impl("gatv2_attention_backward", &gatv2_attention_backward);
-  m.impl("gatv2_attention_dropout_forward", &gatv2_attention_dropout_forward);
-  m.impl("gatv2_attention_dropout_backward", &gatv2_attention_dropout_backward);
-  m.impl("gat_edge_attention_forward", &gat_edge_attention_forward);
-  m.impl("gat_edge_attention_backward", &gat_edge_attention_backward);
-}
+TORCH_LIBRARY_IMPL(graphop, CUDA, m) { GRAPHOP_OPS(GRAPHOP_IMPL) }
+
+// there is no CPU implementation: the reference's CHECK_CUDA message
+TORCH_LIBRARY_IMPL(graphop, CPU, m) { GRAPHOP_OPS(GRAPHOP_IMPL) }

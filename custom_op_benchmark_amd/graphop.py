@@ -31,15 +31,15 @@ __all__ = ["maskedmm_csr_forward", "maskedmm_csr_backward", "node_mul_edge_forwa
 # the GAT additive attention scores (LeakyReLU(el[i] + er[j]) per edge and head), the fused GAT attention layer and
 # its forms with attention dropout (plus the mask they apply, as an edge tensor, for the composed path), and the GATv2
 # scores (att . LeakyReLU(xl[i] + xr[j]) per edge and head), and the fused GAT layer with a per-edge score term
-# (LeakyReLU(el[i] + er[j] + ee[e]), GATConv(edge_dim=...) / EGATConv)
-EXTRA_OPS = ["attention_forward", "attention_backward", "attention_backward_is_fused", "gat_scores_forward",
-             "gat_scores_backward", "gat_attention_forward", "gat_attention_backward",
-             "gat_attention_dropout_forward", "gat_attention_dropout_backward", "edge_dropout_mask",
-             "gatv2_scores_forward", "gatv2_scores_backward", "gatv2_attention_forward",
-             "gatv2_attention_backward", "gatv2_attention_dropout_forward", "gatv2_attention_dropout_backward",
-             "gat_edge_attention_forward", "gat_edge_attention_backward"]
+# (LeakyReLU(el[i] + er[j] + ee[e]), GATConv(edge_dim=...) / EGATConv).  EXTRA_OPS lists them, below _SCHEMAS.
 
 _NULL = None
+# the index arrays of a call by argument name: one CSR orientation without and with `indices`, and the two spellings
+# of the backward ops' second orientation
+_CSR3 = ("row", "indptr", "eid")
+_CSR = _CSR3 + ("indices",)
+_CSR_RC = ("row", "indptr_r", "eid_r", "indices_r", "col", "indptr_c", "eid_c", "indices_c")
+_CSR_T = _CSR + ("col", "indptr_t", "eid_t", "indices_t")
 
 
 def _check_input(t, name):
@@ -56,29 +56,48 @@ def _check_index(t, name):
         raise RuntimeError("expected scalar type Long but found %s (%s)" % (t.dtype, name))
 
 
+def _check_csr(tensors, names, *values):
+    """CHECK_INPUT on the index arrays `tensors`, called `names`, and on the value operands, given as (tensor, name)
+    pairs; then CHECK_INDEX on the index arrays."""
+    for t, n in zip(tensors, names):
+        _check_input(t, n)
+    for t, n in values:
+        _check_input(t, n)
+    for t, n in zip(tensors, names):
+        _check_index(t, n)
+
+
+def _check_grad(t, name):
+    # CHECK_CUDA alone: a gradient is made contiguous, not refused
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise RuntimeError("%s must be a CUDA tensor" % name)
+
+
+def _check_edge_rows(t, name, n_edges):
+    # the C ABI takes a raw pointer plus n_edges: fewer rows than edge ids would be read (or written) out of bounds
+    if t.dim() < 1 or t.size(0) < n_edges:
+        raise RuntimeError("%s must hold one entry per edge id: %d rows for %d edges" % (name, t.size(0), n_edges))
+
+
+def _edge_out(e, h, dtype, device):
+    return torch.empty((e,) if h == 1 else (e, h), dtype=dtype, device=device)     # graphop_kernel.cu:284
+
+
 def _same_dtype(a, b, na, nb):
     if a.dtype != b.dtype:
         raise RuntimeError("expected %s and %s to have the same dtype, got %s and %s"
                            % (na, nb, a.dtype, b.dtype))
 
 
-def _plan(row, indptr, eid, indices, bound):
-    return get_plan(row, indptr, eid, indices, bound)
-
-
 def maskedmm_csr_forward(row, indptr, eid, indices, A, B):
     """y[eid[j], k] = <A[row[c], k], B[indices[j], k]>   (graphop.cpp:16-30)"""
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices"),
-                 (A, "A"), (B, "B")):
-        _check_input(t, n)
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices")):
-        _check_index(t, n)
+    _check_csr((row, indptr, eid, indices), _CSR, (A, "A"), (B, "B"))
     _same_dtype(A, B, "A", "B")
     e, d = eid.size(0), A.size(-1)
     h = 1 if A.dim() == 2 else A.size(1)                    # graphop_kernel.cu:283
-    y = torch.empty((e,) if h == 1 else (e, h), dtype=A.dtype, device=A.device)
+    y = _edge_out(e, h, A.dtype, A.device)
     with _lib.device_guard(A.device):
-        plan = _plan(row, indptr, eid, indices, B.size(0))
+        plan = get_plan(row, indptr, eid, indices, B.size(0))
         check(lib().graphop_maskedmm_csr_forward(
             dtype_code(A), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(A), ptr(B), ptr(y),
             row.size(0), e, A.size(0), B.size(0), h, d, plan.handle, stream_of(A)))
@@ -88,23 +107,18 @@ def maskedmm_csr_forward(row, indptr, eid, indices, A, B):
 def maskedmm_csr_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c,
                           A, B, dy):
     """-> [dA, dB]   (graphop.cpp:108-131)"""
-    names = ("row", "indptr_r", "eid_r", "indices_r", "col", "indptr_c", "eid_c", "indices_c")
-    idx = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
-    for t, n in zip(idx + (A, B), names + ("A", "B")):
-        _check_input(t, n)
-    for t, n in zip(idx, names):
-        _check_index(t, n)
-    if not isinstance(dy, torch.Tensor) or not dy.is_cuda:
-        raise RuntimeError("dy must be a CUDA tensor")
+    _check_csr((row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c), _CSR_RC, (A, "A"), (B, "B"))
+    _check_grad(dy, "dy")
     _same_dtype(A, B, "A", "B")
     _same_dtype(A, dy, "A", "dy")
     dy = dy.contiguous()
+    _check_edge_rows(dy, "dy", eid_r.size(0))
     d = A.size(-1)
     h = dy.size(1) if dy.dim() == 2 else 1                  # graphop_kernel.cu:373
     dA, dB = torch.empty_like(A), torch.empty_like(B)
     with _lib.device_guard(A.device):
-        plan_r = _plan(row, indptr_r, eid_r, indices_r, B.size(0))
-        plan_c = _plan(col, indptr_c, eid_c, indices_c, A.size(0))
+        plan_r = get_plan(row, indptr_r, eid_r, indices_r, B.size(0))
+        plan_c = get_plan(col, indptr_c, eid_c, indices_c, A.size(0))
         check(lib().graphop_maskedmm_csr_backward(
             dtype_code(A), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col),
             ptr(indptr_c), ptr(eid_c), ptr(indices_c), ptr(A), ptr(B), ptr(dy), ptr(dA), ptr(dB),
@@ -115,14 +129,12 @@ def maskedmm_csr_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
 
 def sparse_softmax_forward(row, indptr, eid, x):
     """Per-row (per-head) softmax of edge values   (graphop.cpp:59-69)"""
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (x, "x")):
-        _check_input(t, n)
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid")):
-        _check_index(t, n)
+    _check_csr((row, indptr, eid), _CSR3, (x, "x"))
+    _check_edge_rows(x, "x", eid.size(0))
     h = x.size(1) if x.dim() == 2 else 1
     y = torch.empty_like(x)
     with _lib.device_guard(x.device):
-        plan = _plan(row, indptr, eid, None, 0)
+        plan = get_plan(row, indptr, eid, None, 0)
         ws, ws_rows = None, 0
         if not plan.info.row_owned:                          # general layout: atomics + scratch
             ws_rows = plan.info.max_row + 1
@@ -135,18 +147,16 @@ def sparse_softmax_forward(row, indptr, eid, x):
 
 def sparse_softmax_backward(row, indptr, eid, y, dy):
     """dx = dy*y - (sum_row dy*y)*y   (graphop.cpp:163-175)"""
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (y, "y")):
-        _check_input(t, n)
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid")):
-        _check_index(t, n)
-    if not isinstance(dy, torch.Tensor) or not dy.is_cuda:
-        raise RuntimeError("dy must be a CUDA tensor")
+    _check_csr((row, indptr, eid), _CSR3, (y, "y"))
+    _check_grad(dy, "dy")
     _same_dtype(y, dy, "y", "dy")
     dy = dy.contiguous()
+    _check_edge_rows(y, "y", eid.size(0))
+    _check_edge_rows(dy, "dy", eid.size(0))
     h = dy.size(1) if dy.dim() == 2 else 1
     dx = torch.empty_like(dy)
     with _lib.device_guard(y.device):
-        plan = _plan(row, indptr, eid, None, 0)
+        plan = get_plan(row, indptr, eid, None, 0)
         ws, ws_rows = None, 0
         if not plan.info.row_owned:
             ws_rows = plan.info.max_row + 1
@@ -159,17 +169,14 @@ def sparse_softmax_backward(row, indptr, eid, y, dy):
 
 def vector_spmm_forward(row, indptr, eid, indices, edata, x):
     """y[row[c], k] += sum_j edata[eid[j], k] * x[indices[j], k]   (graphop.cpp:79-93)"""
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices"),
-                 (edata, "edata"), (x, "x")):
-        _check_input(t, n)
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices")):
-        _check_index(t, n)
+    _check_csr((row, indptr, eid, indices), _CSR, (edata, "edata"), (x, "x"))
     _same_dtype(edata, x, "edata", "x")
+    _check_edge_rows(edata, "edata", eid.size(0))
     h = edata.size(1) if edata.dim() == 2 else 1            # graphop_kernel.cu:520
     d = x.size(-1)
     y = torch.empty_like(x)                                  # zeros_like(x), :527
     with _lib.device_guard(x.device):
-        plan = _plan(row, indptr, eid, indices, x.size(0))
+        plan = get_plan(row, indptr, eid, indices, x.size(0))
         if plan.info.max_row >= x.size(0):
             raise RuntimeError("vector_spmm_forward: row id %d but y = zeros_like(x) has %d rows"
                                % (plan.info.max_row, x.size(0)))
@@ -182,20 +189,17 @@ def vector_spmm_forward(row, indptr, eid, indices, edata, x):
 
 def vector_spmm_backward(row, indptr, eid, indices, col, indptr_t, eid_t, indices_t, edata, dy, x):
     """-> [dedata, dx]; NB ``dy`` comes before ``x``   (graphop.cpp:190-214)"""
-    names = ("row", "indptr", "eid", "indices", "col", "indptr_t", "eid_t", "indices_t")
-    idx = (row, indptr, eid, indices, col, indptr_t, eid_t, indices_t)
-    for t, n in zip(idx + (edata, dy, x), names + ("edata", "dy", "x")):
-        _check_input(t, n)
-    for t, n in zip(idx, names):
-        _check_index(t, n)
+    _check_csr((row, indptr, eid, indices, col, indptr_t, eid_t, indices_t), _CSR_T,
+               (edata, "edata"), (dy, "dy"), (x, "x"))
     _same_dtype(edata, x, "edata", "x")
     _same_dtype(dy, x, "dy", "x")
+    _check_edge_rows(edata, "edata", eid.size(0))
     h = edata.size(1) if edata.dim() == 2 else 1            # graphop_kernel.cu:560
     d = x.size(-1)
     dedata, dx = torch.empty_like(edata), torch.empty_like(x)
     with _lib.device_guard(x.device):
-        plan_r = _plan(row, indptr, eid, indices, x.size(0))
-        plan_c = _plan(col, indptr_t, eid_t, indices_t, dy.size(0))
+        plan_r = get_plan(row, indptr, eid, indices, x.size(0))
+        plan_c = get_plan(col, indptr_t, eid_t, indices_t, dy.size(0))
         if plan_c.info.max_row >= x.size(0):
             raise RuntimeError("vector_spmm_backward: col id %d but dx has %d rows"
                                % (plan_c.info.max_row, x.size(0)))
@@ -209,18 +213,15 @@ def vector_spmm_backward(row, indptr, eid, indices, col, indptr_t, eid_t, indice
 
 def node_mul_edge_forward(row, indptr, eid, A, B):
     """y[eid[j], k] = <A[row[c], k], B[eid[j]]>   (graphop.cpp:39-51)"""
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (A, "A"), (B, "B")):
-        _check_input(t, n)
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid")):
-        _check_index(t, n)
+    _check_csr((row, indptr, eid), _CSR3, (A, "A"), (B, "B"))
     _same_dtype(A, B, "A", "B")
     e, d = eid.size(0), A.size(-1)
     h = 1 if A.dim() == 2 else A.size(1)
     if B.size(0) < e or B.size(-1) != d:
         raise RuntimeError("node_mul_edge_forward: B must be (n_edges, d)")
-    y = torch.empty((e,) if h == 1 else (e, h), dtype=A.dtype, device=A.device)
+    y = _edge_out(e, h, A.dtype, A.device)
     with _lib.device_guard(A.device):
-        plan = _plan(row, indptr, eid, None, 0)
+        plan = get_plan(row, indptr, eid, None, 0)
         check(lib().graphop_node_mul_edge_forward(
             dtype_code(A), ptr(row), ptr(indptr), ptr(eid), ptr(A), ptr(B), ptr(y), row.size(0), e,
             A.size(0), h, d, plan.handle, stream_of(A)))
@@ -229,23 +230,20 @@ def node_mul_edge_forward(row, indptr, eid, A, B):
 
 def node_mul_edge_backward(row, indptr, eid, A, B, dy):
     """-> [dA, dB]   (graphop.cpp:141-154)"""
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (A, "A"), (B, "B")):
-        _check_input(t, n)
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid")):
-        _check_index(t, n)
-    if not isinstance(dy, torch.Tensor) or not dy.is_cuda:
-        raise RuntimeError("dy must be a CUDA tensor")
+    _check_csr((row, indptr, eid), _CSR3, (A, "A"), (B, "B"))
+    _check_grad(dy, "dy")
     _same_dtype(A, B, "A", "B")
     _same_dtype(A, dy, "A", "dy")
     dy = dy.contiguous()
+    e = eid.size(0)
+    _check_edge_rows(dy, "dy", e)
     d = A.size(-1)
     h = dy.size(1) if dy.dim() == 2 else 1
-    e = eid.size(0)
     if B.size(0) != e or B.size(-1) != d:
         raise RuntimeError("node_mul_edge_backward: B must be (n_edges, d)")
     dA, dB = torch.empty_like(A), torch.empty_like(B)
     with _lib.device_guard(A.device):
-        plan = _plan(row, indptr, eid, None, 0)
+        plan = get_plan(row, indptr, eid, None, 0)
         check(lib().graphop_node_mul_edge_backward(
             dtype_code(A), ptr(row), ptr(indptr), ptr(eid), ptr(A), ptr(B), ptr(dy), ptr(dA),
             ptr(dB), row.size(0), e, A.size(0), h, d, plan.handle, stream_of(A)))
@@ -271,8 +269,8 @@ def attention_backward_is_fused(row, indptr_r, eid_r, indices_r, col, indptr_c, 
     h = 1 if Q.dim() == 2 else Q.size(1)
     out = ctypes.c_int(0)
     with _lib.device_guard(Q.device):
-        plan_r = _plan(row, indptr_r, eid_r, indices_r, K.size(0))
-        plan_c = _plan(col, indptr_c, eid_c, indices_c, Q.size(0))
+        plan_r = get_plan(row, indptr_r, eid_r, indices_r, K.size(0))
+        plan_c = get_plan(col, indptr_c, eid_c, indices_c, Q.size(0))
         check(lib().graphop_attention_backward_is_fused(dtype_code(Q), eid_r.size(0), Q.size(0), K.size(0), h, d,
                                                         plan_r.handle, plan_c.handle, stream_of(Q), ctypes.byref(out)))
     return bool(out.value)
@@ -282,11 +280,7 @@ def attention_forward(row, indptr, eid, indices, Q, K, V):
     """-> [o, stats]: o = vector_spmm(sparse_softmax(maskedmm_csr(Q, K)), V) over the row-major CSR,
     without returning the E-sized s / a.  stats (n_q, h, 2) = (row max, 1 / sum exp) is what
     attention_backward needs to recompute them."""
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices"), (Q, "Q"),
-                 (K, "K"), (V, "V")):
-        _check_input(t, n)
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices")):
-        _check_index(t, n)
+    _check_csr((row, indptr, eid, indices), _CSR, (Q, "Q"), (K, "K"), (V, "V"))
     _same_dtype(Q, K, "Q", "K")
     _same_dtype(Q, V, "Q", "V")
     if K.shape != V.shape or Q.shape[1:] != K.shape[1:]:
@@ -297,7 +291,7 @@ def attention_forward(row, indptr, eid, indices, Q, K, V):
     o = torch.empty_like(Q)
     stats = torch.empty((n_q, h, 2), dtype=Q.dtype, device=Q.device)
     with _lib.device_guard(Q.device):
-        plan = _plan(row, indptr, eid, indices, n_k)
+        plan = get_plan(row, indptr, eid, indices, n_k)
         ws, nbytes = _workspace(Q, dtype_code(Q), False, e, n_q, n_k, h, d, plan, None)
         check(lib().graphop_attention_forward(
             dtype_code(Q), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(Q), ptr(K), ptr(V),
@@ -309,14 +303,9 @@ def attention_forward(row, indptr, eid, indices, Q, K, V):
 def attention_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c,
                        Q, K, V, o, stats, dO):
     """-> [dQ, dK, dV] of the fused step for the output gradient dO."""
-    names = ("row", "indptr_r", "eid_r", "indices_r", "col", "indptr_c", "eid_c", "indices_c")
-    idx = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
-    for t, n in zip(idx + (Q, K, V, o, stats), names + ("Q", "K", "V", "o", "stats")):
-        _check_input(t, n)
-    for t, n in zip(idx, names):
-        _check_index(t, n)
-    if not isinstance(dO, torch.Tensor) or not dO.is_cuda:
-        raise RuntimeError("dO must be a CUDA tensor")
+    _check_csr((row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c), _CSR_RC,
+               (Q, "Q"), (K, "K"), (V, "V"), (o, "o"), (stats, "stats"))
+    _check_grad(dO, "dO")
     for t, n in ((K, "K"), (V, "V"), (o, "o"), (stats, "stats"), (dO, "dO")):
         _same_dtype(Q, t, "Q", n)
     dO = dO.contiguous()
@@ -327,8 +316,8 @@ def attention_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, in
         raise RuntimeError("attention_backward: o, dO must match Q and stats must be (n_q, h, 2)")
     dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
     with _lib.device_guard(Q.device):
-        plan_r = _plan(row, indptr_r, eid_r, indices_r, n_k)
-        plan_c = _plan(col, indptr_c, eid_c, indices_c, n_q)
+        plan_r = get_plan(row, indptr_r, eid_r, indices_r, n_k)
+        plan_c = get_plan(col, indptr_c, eid_c, indices_c, n_q)
         ws, nbytes = _workspace(Q, dtype_code(Q), True, e, n_q, n_k, h, d, plan_r, plan_c)
         check(lib().graphop_attention_backward(
             dtype_code(Q), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col),
@@ -350,15 +339,12 @@ def _gat_heads(el, er, fn):
 
 def gat_scores_forward(row, indptr, eid, indices, el, er, negative_slope=0.2):
     """y[eid[j], k] = LeakyReLU(el[row[c], k] + er[indices[j], k], negative_slope); y is (e) if h == 1 else (e, h)"""
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices"), (el, "el"), (er, "er")):
-        _check_input(t, n)
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices")):
-        _check_index(t, n)
+    _check_csr((row, indptr, eid, indices), _CSR, (el, "el"), (er, "er"))
     h = _gat_heads(el, er, "gat_scores_forward")
     e = eid.size(0)
-    y = torch.empty((e,) if h == 1 else (e, h), dtype=el.dtype, device=el.device)
+    y = _edge_out(e, h, el.dtype, el.device)
     with _lib.device_guard(el.device):
-        plan = _plan(row, indptr, eid, indices, er.size(0))
+        plan = get_plan(row, indptr, eid, indices, er.size(0))
         check(lib().graphop_gat_scores_forward(
             dtype_code(el), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(el), ptr(er), ptr(y), row.size(0), e,
             el.size(0), er.size(0), h, float(negative_slope), plan.handle, stream_of(el)))
@@ -368,14 +354,8 @@ def gat_scores_forward(row, indptr, eid, indices, el, er, negative_slope=0.2):
 def gat_scores_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, dy,
                         negative_slope=0.2):
     """-> [del, der] of gat_scores_forward for the score gradient dy (z is recomputed from el and er)"""
-    names = ("row", "indptr_r", "eid_r", "indices_r", "col", "indptr_c", "eid_c", "indices_c")
-    idx = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
-    for t, n in zip(idx + (el, er), names + ("el", "er")):
-        _check_input(t, n)
-    for t, n in zip(idx, names):
-        _check_index(t, n)
-    if not isinstance(dy, torch.Tensor) or not dy.is_cuda:
-        raise RuntimeError("dy must be a CUDA tensor")
+    _check_csr((row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c), _CSR_RC, (el, "el"), (er, "er"))
+    _check_grad(dy, "dy")
     h = _gat_heads(el, er, "gat_scores_backward")
     _same_dtype(el, dy, "el", "dy")
     dy = dy.contiguous()
@@ -385,8 +365,8 @@ def gat_scores_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, i
                            % (e, h, tuple(dy.shape)))
     d_el, d_er = torch.empty_like(el), torch.empty_like(er)
     with _lib.device_guard(el.device):
-        plan_r = _plan(row, indptr_r, eid_r, indices_r, er.size(0))
-        plan_c = _plan(col, indptr_c, eid_c, indices_c, el.size(0))
+        plan_r = get_plan(row, indptr_r, eid_r, indices_r, er.size(0))
+        plan_c = get_plan(col, indptr_c, eid_c, indices_c, el.size(0))
         check(lib().graphop_gat_scores_backward(
             dtype_code(el), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c),
             ptr(eid_c), ptr(indices_c), ptr(el), ptr(er), ptr(dy), ptr(d_el), ptr(d_er), row.size(0), col.size(0),
@@ -418,16 +398,12 @@ def _gatv2_workspace_values(n_row_chunks, h, d):
 def gatv2_scores_forward(row, indptr, eid, indices, xl, xr, att, negative_slope=0.2):
     """y[eid[j], k] = sum_c att[k, c] * LeakyReLU(xl[row[c], k, c] + xr[indices[j], k, c], negative_slope);
     xl (n_src, d), xr (n_dst, d), att (d) give y (e); xl (n_src, h, d), xr (n_dst, h, d), att (h, d) give y (e, h)"""
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices"), (xl, "xl"), (xr, "xr"),
-                 (att, "att")):
-        _check_input(t, n)
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices")):
-        _check_index(t, n)
+    _check_csr((row, indptr, eid, indices), _CSR, (xl, "xl"), (xr, "xr"), (att, "att"))
     h, d = _gatv2_shapes(xl, xr, att, "gatv2_scores_forward")
     e = eid.size(0)
     y = torch.empty((e,) if xl.dim() == 2 else (e, h), dtype=xl.dtype, device=xl.device)
     with _lib.device_guard(xl.device):
-        plan = _plan(row, indptr, eid, indices, xr.size(0))
+        plan = get_plan(row, indptr, eid, indices, xr.size(0))
         check(lib().graphop_gatv2_scores_forward(
             dtype_code(xl), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(xl), ptr(xr), ptr(att), ptr(y),
             row.size(0), e, xl.size(0), xr.size(0), h, d, float(negative_slope), plan.handle, stream_of(xl)))
@@ -437,14 +413,9 @@ def gatv2_scores_forward(row, indptr, eid, indices, xl, xr, att, negative_slope=
 def gatv2_scores_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, dy,
                           negative_slope=0.2):
     """-> [dxl, dxr, datt] of gatv2_scores_forward for the score gradient dy (z is recomputed from xl and xr)"""
-    names = ("row", "indptr_r", "eid_r", "indices_r", "col", "indptr_c", "eid_c", "indices_c")
-    idx = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
-    for t, n in zip(idx + (xl, xr, att), names + ("xl", "xr", "att")):
-        _check_input(t, n)
-    for t, n in zip(idx, names):
-        _check_index(t, n)
-    if not isinstance(dy, torch.Tensor) or not dy.is_cuda:
-        raise RuntimeError("dy must be a CUDA tensor")
+    _check_csr((row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c), _CSR_RC,
+               (xl, "xl"), (xr, "xr"), (att, "att"))
+    _check_grad(dy, "dy")
     h, d = _gatv2_shapes(xl, xr, att, "gatv2_scores_backward")
     _same_dtype(xl, dy, "xl", "dy")
     dy = dy.contiguous()
@@ -455,14 +426,27 @@ def gatv2_scores_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
     dxl, dxr, datt = torch.empty_like(xl), torch.empty_like(xr), torch.empty_like(att)
     ws = torch.empty(max(_gatv2_workspace_values(row.size(0), h, d), 1), dtype=xl.dtype, device=xl.device)
     with _lib.device_guard(xl.device):
-        plan_r = _plan(row, indptr_r, eid_r, indices_r, xr.size(0))
-        plan_c = _plan(col, indptr_c, eid_c, indices_c, xl.size(0))
+        plan_r = get_plan(row, indptr_r, eid_r, indices_r, xr.size(0))
+        plan_c = get_plan(col, indptr_c, eid_c, indices_c, xl.size(0))
         check(lib().graphop_gatv2_scores_backward(
             dtype_code(xl), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c),
             ptr(eid_c), ptr(indices_c), ptr(xl), ptr(xr), ptr(att), ptr(dy), ptr(dxl), ptr(dxr), ptr(datt), ptr(ws),
             ws.numel() * ws.element_size(), row.size(0), col.size(0), e, xl.size(0), xr.size(0), h, d,
             float(negative_slope), plan_r.handle, plan_c.handle, stream_of(xl)))
     return [dxl, dxr, datt]
+
+
+# ---- the fused layers (extra ops) ---------------------------------------------------------------------------------
+def _saved_checked(fn, oshape, n_src, h, o, stats, dO):
+    """What a fused backward saved from its forward, o (oshape) and stats (n_src, h, 2), and the gradient of o, checked
+    against each other -> that gradient, contiguous."""
+    if o.shape != oshape or stats.numel() != n_src * h * 2:
+        raise RuntimeError("%s: o must be %s and stats (n_src, h, 2), got %s and %s"
+                           % (fn, oshape, tuple(o.shape), tuple(stats.shape)))
+    dO = dO.contiguous()
+    if dO.shape != o.shape:
+        raise RuntimeError("%s: dO must match o %s, got %s" % (fn, tuple(o.shape), tuple(dO.shape)))
+    return dO
 
 
 # ---- fused GATv2 attention (extra op) ---------------------------------------------------------------------------
@@ -473,17 +457,13 @@ def _gatv2_attention_workspace_values(n_l, n_row_chunks, h, d):
 
 def _gatv2_attention_forward(fn, row, indptr, eid, indices, xl, xr, att, negative_slope, drop=()):
     """gatv2_attention_forward (drop = ()) or gatv2_attention_dropout_forward (drop = (p, seed, offset)) as `fn`."""
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices"), (xl, "xl"), (xr, "xr"),
-                 (att, "att")):
-        _check_input(t, n)
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices")):
-        _check_index(t, n)
+    _check_csr((row, indptr, eid, indices), _CSR, (xl, "xl"), (xr, "xr"), (att, "att"))
     h, d = _gatv2_shapes(xl, xr, att, fn)
     e, n_l = eid.size(0), xl.size(0)
     o = torch.empty_like(xl)
     stats = torch.empty((n_l, h, 2), dtype=xl.dtype, device=xl.device)
     with _lib.device_guard(xl.device):
-        plan = _plan(row, indptr, eid, indices, xr.size(0))
+        plan = get_plan(row, indptr, eid, indices, xr.size(0))
         check(getattr(lib(), "graphop_" + fn)(
             dtype_code(xl), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(xl), ptr(xr), ptr(att), ptr(o),
             ptr(stats), row.size(0), e, n_l, xr.size(0), h, d, float(negative_slope), *drop, plan.handle,
@@ -494,31 +474,21 @@ def _gatv2_attention_forward(fn, row, indptr, eid, indices, xl, xr, att, negativ
 def _gatv2_attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, o,
                               stats, dO, negative_slope, drop=()):
     """gatv2_attention_backward (drop = ()) or gatv2_attention_dropout_backward (drop = (p, seed, offset)) as `fn`."""
-    names = ("row", "indptr_r", "eid_r", "indices_r", "col", "indptr_c", "eid_c", "indices_c")
-    idx = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
-    for t, n in zip(idx + (xl, xr, att, o, stats), names + ("xl", "xr", "att", "o", "stats")):
-        _check_input(t, n)
-    for t, n in zip(idx, names):
-        _check_index(t, n)
-    if not isinstance(dO, torch.Tensor) or not dO.is_cuda:
-        raise RuntimeError("dO must be a CUDA tensor")
+    _check_csr((row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c), _CSR_RC,
+               (xl, "xl"), (xr, "xr"), (att, "att"), (o, "o"), (stats, "stats"))
+    _check_grad(dO, "dO")
     h, d = _gatv2_shapes(xl, xr, att, fn)
     for t, n in ((o, "o"), (stats, "stats"), (dO, "dO")):
         _same_dtype(xl, t, "xl", n)
     n_l = xl.size(0)
-    if o.shape != xl.shape or stats.numel() != n_l * h * 2:
-        raise RuntimeError("%s: o must be %s and stats (n_src, h, 2), got %s and %s"
-                           % (fn, tuple(xl.shape), tuple(o.shape), tuple(stats.shape)))
-    dO = dO.contiguous()
-    if dO.shape != o.shape:
-        raise RuntimeError("%s: dO must match o %s, got %s" % (fn, tuple(o.shape), tuple(dO.shape)))
+    dO = _saved_checked(fn, tuple(xl.shape), n_l, h, o, stats, dO)
     e = eid_r.size(0)
     dxl, dxr, datt = torch.empty_like(xl), torch.empty_like(xr), torch.empty_like(att)
     ws = torch.empty(max(_gatv2_attention_workspace_values(n_l, row.size(0), h, d), 1), dtype=xl.dtype,
                      device=xl.device)
     with _lib.device_guard(xl.device):
-        plan_r = _plan(row, indptr_r, eid_r, indices_r, xr.size(0))
-        plan_c = _plan(col, indptr_c, eid_c, indices_c, n_l)
+        plan_r = get_plan(row, indptr_r, eid_r, indices_r, xr.size(0))
+        plan_c = get_plan(col, indptr_c, eid_c, indices_c, n_l)
         check(getattr(lib(), "graphop_" + fn)(
             dtype_code(xl), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c),
             ptr(eid_c), ptr(indices_c), ptr(xl), ptr(xr), ptr(att), ptr(o), ptr(stats), ptr(dO), ptr(dxl), ptr(dxr),
@@ -555,22 +525,18 @@ def _gat_attn_shapes(el, er, V, fn):
 def _gat_attention_forward(fn, row, indptr, eid, indices, el, er, V, negative_slope, drop=(), ee=None):
     """gat_attention_forward (drop = ()), gat_attention_dropout_forward or, with the edge term ee,
     gat_edge_attention_forward (drop = (p, seed, offset)) as `fn`."""
-    edge = () if ee is None else ((ee, "ee"),)
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices"), (el, "el"), (er, "er"),
-                 *edge, (V, "V")):
-        _check_input(t, n)
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices")):
-        _check_index(t, n)
+    edge = () if ee is None else (ee,)
+    _check_csr((row, indptr, eid, indices), _CSR, (el, "el"), (er, "er"), (V, "V"))
     h, d = _gat_attn_shapes(el, er, V, fn)
     e, n_l = eid.size(0), el.size(0)
     if edge:
-        _gat_edge_term(el, ee, e, h, fn)
+        _gat_edge_term(el, ee, e, h, fn)         # checks ee as an input too
     o = torch.empty((n_l,) + tuple(V.shape[1:]), dtype=V.dtype, device=V.device)
     stats = torch.empty((n_l, h, 2), dtype=el.dtype, device=el.device)
     with _lib.device_guard(el.device):
-        plan = _plan(row, indptr, eid, indices, er.size(0))
+        plan = get_plan(row, indptr, eid, indices, er.size(0))
         check(getattr(lib(), "graphop_" + fn)(
-            dtype_code(el), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(el), ptr(er), *(ptr(t) for t, _ in edge),
+            dtype_code(el), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(el), ptr(er), *(ptr(t) for t in edge),
             ptr(V), ptr(o), ptr(stats), row.size(0), e, n_l, er.size(0), h, d, float(negative_slope), *drop,
             plan.handle, stream_of(el)))
     return [o, stats]
@@ -580,38 +546,28 @@ def _gat_attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, 
                             dO, negative_slope, drop=(), ee=None, need_dee=True):
     """gat_attention_backward (drop = ()), gat_attention_dropout_backward or, with the edge term ee,
     gat_edge_attention_backward (drop = (p, seed, offset)) as `fn`: -> [del, der, dV], with ee [del, der, dee, dV]."""
-    edge = () if ee is None else ((ee, "ee"),)
-    names = ("row", "indptr_r", "eid_r", "indices_r", "col", "indptr_c", "eid_c", "indices_c")
-    idx = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
-    for t, n in (*zip(idx, names), (el, "el"), (er, "er"), *edge, (V, "V"), (o, "o"), (stats, "stats")):
-        _check_input(t, n)
-    for t, n in zip(idx, names):
-        _check_index(t, n)
-    if not isinstance(dO, torch.Tensor) or not dO.is_cuda:
-        raise RuntimeError("dO must be a CUDA tensor")
+    edge = () if ee is None else (ee,)
+    _check_csr((row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c), _CSR_RC,
+               (el, "el"), (er, "er"), (V, "V"), (o, "o"), (stats, "stats"))
+    _check_grad(dO, "dO")
     h, d = _gat_attn_shapes(el, er, V, fn)
     e, n_l = eid_r.size(0), el.size(0)
     if edge:
-        _gat_edge_term(el, ee, e, h, fn)
+        _gat_edge_term(el, ee, e, h, fn)         # checks ee as an input too
     for t, n in ((o, "o"), (stats, "stats"), (dO, "dO")):
         _same_dtype(el, t, "el", n)
-    if o.shape != (n_l,) + tuple(V.shape[1:]) or stats.numel() != n_l * h * 2:
-        raise RuntimeError("%s: o must be %s and stats (n_src, h, 2), got %s and %s"
-                           % (fn, (n_l,) + tuple(V.shape[1:]), tuple(o.shape), tuple(stats.shape)))
-    dO = dO.contiguous()
-    if dO.shape != o.shape:
-        raise RuntimeError("%s: dO must match o %s, got %s" % (fn, tuple(o.shape), tuple(dO.shape)))
+    dO = _saved_checked(fn, (n_l,) + tuple(V.shape[1:]), n_l, h, o, stats, dO)
     d_el, d_er, dV = torch.empty_like(el), torch.empty_like(er), torch.empty_like(V)
     d_ee = ()       # with ee: [dee], an empty (0,) tensor and a NULL pointer where it is not wanted
     if edge:
         d_ee = (torch.empty_like(ee) if need_dee else torch.empty((0,), dtype=ee.dtype, device=ee.device),)
     ws = torch.empty(max(n_l * h * 4, 1), dtype=el.dtype, device=el.device)      # (el, m, 1 / l, D) per (node, head)
     with _lib.device_guard(el.device):
-        plan_r = _plan(row, indptr_r, eid_r, indices_r, er.size(0))
-        plan_c = _plan(col, indptr_c, eid_c, indices_c, n_l)
+        plan_r = get_plan(row, indptr_r, eid_r, indices_r, er.size(0))
+        plan_c = get_plan(col, indptr_c, eid_c, indices_c, n_l)
         check(getattr(lib(), "graphop_" + fn)(
             dtype_code(el), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c),
-            ptr(eid_c), ptr(indices_c), ptr(el), ptr(er), *(ptr(t) for t, _ in edge), ptr(V), ptr(o), ptr(stats),
+            ptr(eid_c), ptr(indices_c), ptr(el), ptr(er), *(ptr(t) for t in edge), ptr(V), ptr(o), ptr(stats),
             ptr(dO), ptr(d_el), ptr(d_er), *(ptr(t) if need_dee else _NULL for t in d_ee), ptr(dV), ptr(ws),
             ws.numel() * ws.element_size(), row.size(0), col.size(0), e, n_l, er.size(0), h, d,
             float(negative_slope), *drop, plan_r.handle, plan_c.handle, stream_of(el)))
@@ -685,18 +641,16 @@ def edge_dropout_mask(row, indptr, eid, indices, h, p, seed, offset=0, dtype=tor
     """-> the multipliers m[e, k] = keep(i, j, k) / (1 - p) the dropout ops above apply, as an edge tensor: (E) for
     h == 1, else (E, h).  (row, indptr, eid, indices) is the ROW-MAJOR CSR (i = row[c], j = indices[slot])."""
     p, seed, offset = _drop_args("edge_dropout_mask", p, seed, offset)
-    for t, n in ((row, "row"), (indptr, "indptr"), (eid, "eid"), (indices, "indices")):
-        _check_input(t, n)
-        _check_index(t, n)
+    _check_csr((row, indptr, eid, indices), _CSR)
     h = int(h)
     if h < 1 or dtype not in (torch.float32, torch.float64):
         raise RuntimeError("edge_dropout_mask: h must be >= 1 and dtype float32 or float64, got h=%d dtype=%s"
                            % (h, dtype))
     e = eid.size(0)
-    y = torch.empty((e,) if h == 1 else (e, h), dtype=dtype, device=row.device)
+    y = _edge_out(e, h, dtype, row.device)
     bound = 2 ** 32 - 1       # the ids themselves are the only bound on the two node counts
     with _lib.device_guard(row.device):
-        plan = _plan(row, indptr, eid, indices, 0)
+        plan = get_plan(row, indptr, eid, indices, 0)
         n_l = max(plan.info.max_row + 1, 0) if e else 0
         n_r = max(plan.info.max_index + 1, 0) if e else 0
         check(lib().graphop_edge_dropout_mask(
@@ -777,6 +731,8 @@ _SCHEMAS = {
     "gat_edge_attention_forward": "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, Tensor ee, Tensor V, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]",
     "gat_edge_attention_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor ee, Tensor V, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0, bool need_dee=True) -> Tensor[]",
 }
+# every op beyond the reference's eight, plus the one query that is not an op
+EXTRA_OPS = [n for n in _SCHEMAS if n not in __all__] + ["attention_backward_is_fused"]
 _torch_lib = None
 
 

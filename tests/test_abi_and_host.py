@@ -199,6 +199,48 @@ def test_cpp_extension_mirrors_the_reference_module():
         ext.sparse_softmax_forward(i, i, i)            # positional signature, 4 arguments (graphop.cpp:59-63)
 
 
+def test_registered_schemas_equal_the_python_table():
+    """torch_ext.cpp's op table and graphop.py's _SCHEMAS state the same ops with the same schemas.  Parsed schemas are
+    compared, not text: a registered `float p=0.0` prints as `0.`, `ScalarType dtype=float` as `6`."""
+    from custom_op_benchmark_amd import graphop as ops
+    assert ops.cpp_ext is not None, "graphop_cpp.so not built (run __graft_entry__.build())"
+    for n, schema in ops._SCHEMAS.items():
+        assert torch._C.parse_schema("graphop::" + n + schema) == getattr(torch.ops.graphop, n).default._schema, n
+    registered = {s.name.split("::")[1] for s in torch._C._jit_get_all_schemas() if s.name.startswith("graphop::")}
+    assert registered == set(ops._SCHEMAS)
+
+
+def test_pybind_keywords_follow_the_schemas():
+    """The pybind list of torch_ext.cpp is written by hand: where it names its arguments, their names, which of them
+    have defaults and the int / float / bool default values are the schema's.  The reference's eight and attention_* take
+    positional arguments only, like the reference's module."""
+    import ast
+    from custom_op_benchmark_amd import graphop as ops
+    assert ops.cpp_ext is not None, "graphop_cpp.so not built (run __graft_entry__.build())"
+    positional = set(ops.__all__) | {"attention_forward", "attention_backward"}
+    assert len(positional) == 10
+    for n in ops._SCHEMAS:
+        want = getattr(torch.ops.graphop, n).default._schema.arguments
+        sig = getattr(ops.cpp_ext, n).__doc__.splitlines()[0]
+        assert sig.startswith(n + "(") and ") -> " in sig, sig
+        params = sig[len(n) + 1:sig.rindex(") -> ")].split(", ")
+        assert len(params) == len(want), sig
+        if n in positional:
+            assert [p.split(":")[0] for p in params] == ["arg%d" % k for k in range(len(want))], sig
+            continue
+        for p, a in zip(params, want):
+            name, _, rest = p.partition(": ")
+            _, eq, default = rest.partition(" = ")
+            assert name == a.name and bool(eq) == a.has_default_value(), (n, p)
+            if eq:
+                try:
+                    value = ast.literal_eval(default)
+                except ValueError:          # `torch.float32`: no int / float / bool
+                    assert a.name == "dtype", (n, p)
+                    continue
+                assert type(value) is type(a.default_value) and value == a.default_value, (n, p)
+
+
 def test_head_group_rule_and_labelings():
     """Host logic of round 5: FusedAttention's head-group size (256-B rows, one head per group from d = 64 on, blocking only
     where it saves memory) and the generator's node labelings (bench.py --labeling)."""

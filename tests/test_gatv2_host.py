@@ -88,10 +88,11 @@ def test_gatv2_ops_are_extra_ops_with_an_autograd_class():
 
 def test_gatv2_schemas_of_the_extension_equal_the_python_ones():
     from custom_op_benchmark_amd import graphop as ops
-    src = open(os.path.join(ROOT, "custom_op_benchmark_amd", "csrc", "torch_ext.cpp")).read()
+    assert ops.cpp_ext is not None, "graphop_cpp.so not built (run __graft_entry__.build())"
     for n in NAMES:
-        assert 'm.def("%s%s");' % (n, ops._SCHEMAS[n]) in src
-        assert src.count('m.impl("%s", &%s);' % (n, n)) == 2           # the CUDA key and the refusing CPU key
+        assert torch._C.parse_schema("graphop::" + n + ops._SCHEMAS[n]) == getattr(torch.ops.graphop, n).default._schema
+        assert all(torch._C._dispatch_has_kernel_for_dispatch_key("graphop::" + n, k)
+                   for k in ("CUDA", "CPU"))                           # the CUDA key and the refusing CPU key
 
 
 def test_gatv2_reference_matches_hand_computed_numbers():
