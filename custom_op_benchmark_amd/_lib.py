@@ -103,6 +103,10 @@ _SIGNATURES = {
     + [ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _P, _P],
     "graphop_gat_edge_attention_backward": [ctypes.c_int] + [_P] * 20 + [_c64] * 8
     + [ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _P, _P, _P],
+    "graphop_gatv2_edge_attention_forward": [ctypes.c_int] + [_P] * 10 + [_c64] * 6
+    + [ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _P, _P],
+    "graphop_gatv2_edge_attention_backward": [ctypes.c_int] + [_P] * 20 + [_c64] * 8
+    + [ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _P, _P, _P],
     "graphop_gather_rows": [ctypes.c_int, _P, _P, _P, _c64, _c64, _c64, _P],
     "graphop_scatter_add_rows": [ctypes.c_int, _P, _P, _P, _c64, _c64, _c64, _P],
     "graphop_add_rows_unique": [ctypes.c_int, _P, _P, _P, _c64, _c64, _c64, _P],

@@ -1,5 +1,5 @@
 // Host-side helpers of the GAT family of entry points (gat.hip, gatv2.hip, gat_attention.hip, gat_edge_attention.hip,
-// gatv2_attention.hip and host_gat_attn_ops.h): argument and plan checks, the conditions of the fp32 fast kernels, the
+// gatv2_attention.hip, gatv2_edge_attention.hip, host_gat_attn_ops.h and host_gatv2_attn_ops.h): argument and plan checks, the conditions of the fp32 fast kernels, the
 // (h, d) dispatch, the profile labels, the launch geometry of the gather passes and the opening of the two GATv2
 // backwards.  Each exists once, here.  Not part of the C ABI.
 #pragma once
@@ -42,6 +42,11 @@ inline int gat_check_plan(const char* fn, const graphop_plan* p, const char* seg
 }
 
 inline bool a16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// the eid argument of a fast row-major pass with an edge operand: NULL where the plan says eid[slot] == slot
+inline const i64* eid_arg(const graphop_plan* p, const void* eid) {
+  return p->info.eid_identity ? nullptr : (const i64*)eid;
+}
 
 // a per-(node or edge, head) array as the fast kernels read and write it: aligned to its item width, 4 * min(h, 4) bytes
 inline bool gat_aligned(const void* p, i64 h) {

@@ -17,11 +17,6 @@ namespace graphop {
 #define GO_GAT_ATTN_LABELS(EDGE, pass) \
   (EDGE ? GO_GAT_LABELS_OF("gat_edge_attn", pass) : GO_GAT_LABELS_OF("gat_attn", pass))
 
-// the eid argument of a fast row-major pass: NULL where the plan says eid[slot] == slot
-inline const i64* eid_arg(const graphop_plan* p, const void* eid) {
-  return p->info.eid_identity ? nullptr : (const i64*)eid;
-}
-
 // stats = (m, 1 / l) per (row, head); rows without slots keep (-1e9, 0)
 template <bool EDGE>
 int gat_attn_stats(int dtype, const i64* row, const i64* indptr, const i64* eid, const i64* indices, const void* el,

@@ -7,7 +7,8 @@
 //   D_i = <dO_i, o_i>,  da_ij = <dO_i, xr_j>,  ds_ij = a_ij (da_ij - D_i),  t_ijc = (z_ijc > 0 ? 1 : slope)
 //   dxl[i, k, c] = att[k, c] sum_j ds_ij t_ijc                      datt[k, c] = sum_ij ds_ij LeakyReLU(z_ijc)
 //   dxr[j, k, c] = sum_i (ds_ij att[k, c] t_ijc + a_ij dO[i, k, c])
-// Passes (fp32 fast forms; k_gv2attn_*_generic<T> below cover fp64, other shapes, NULL plans and any chunk order):
+// Passes (fp32 fast forms; k_gv2attn_*_generic<T>, below and in kernels_gatv2_attn_generic.inc, cover fp64, other
+// shapes, NULL plans and any chunk order):
 //   fwd    : one lane group per row segment of a row_owned plan (segments above kLongSegment slots: one workgroup
 //            each), ONE pass with an online softmax: a score needs the whole xr row, so a separate statistics pass
 //            would cost as much as the aggregation.  A row is never split: no atomics, o and stats bit-reproducible.
@@ -80,6 +81,7 @@ struct Gv2DropArg {
   using type = DropArgsIf<DROP, float>;
 };
 
+#define GV2_EDGE 0
 #define GV2_DROP false
 #define GV2_KERNEL(pass) k_gv2attn_##pass##_f32
 #include "kernels_gatv2_attn_passes.inc"
@@ -90,6 +92,7 @@ struct Gv2DropArg {
 #include "kernels_gatv2_attn_passes.inc"
 #undef GV2_DROP
 #undef GV2_KERNEL
+#undef GV2_EDGE
 
 // ---- pack: P[i, k] = (m, 1 / l, <dO_i, o_i>, 0) ---------------------------------------------------------------------
 template <int H, int D>
@@ -113,40 +116,10 @@ __global__ __launch_bounds__(kFastBlock) void k_gv2attn_pack_f32(
   }
 }
 
-// datt[p] = sum over the n_part rows of the row pass's partials, piece p = blockIdx.x: each thread sums its rows in
-// order, then the workgroup's 256 sums are added in a fixed tree
-__global__ __launch_bounds__(kFastBlock) void k_gv2attn_datt_fin_f32(const float4* __restrict__ part,
-                                                                     float4* __restrict__ datt, i64 n_part, int f4) {
-  __shared__ float4 red[kFastBlock / kWave];
-  const int p = blockIdx.x;
-  float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
-  for (i64 i = threadIdx.x; i < n_part; i += kFastBlock) {
-    const float4 o = part[i * f4 + p];
-    t.x += o.x; t.y += o.y; t.z += o.z; t.w += o.w;
-  }
-  t.x = wave_sum(t.x); t.y = wave_sum(t.y); t.z = wave_sum(t.z); t.w = wave_sum(t.w);
-  if ((threadIdx.x & (kWave - 1)) == 0) red[threadIdx.x / kWave] = t;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int q = 1; q < kFastBlock / kWave; ++q) {
-      t.x += red[q].x; t.y += red[q].y; t.z += red[q].z; t.w += red[q].w;
-    }
-    datt[p] = t;
-  }
-}
+// k_gv2attn_datt_fin_f32, which sums the row pass's datt partials, is no template: it is defined in gatv2_attention.hip
+// alone and launched through gv2attn_datt_fin (host_gatv2_attn_ops.h).
 
 // ---- generic kernels: fp32 / fp64, any h and d, any chunk layout; one wave per chunk -----------------------------
-// s of one (slot, head): a = xl[i, k, :], b = xr[j, k, :], w = att[k, :].  Every generic pass evaluates it by this
-// function, so a recomputed score is bitwise the one the statistics were taken from.
-template <typename T>
-__device__ __forceinline__ T gv2attn_score(const T* __restrict__ a, const T* __restrict__ b, const T* __restrict__ w,
-                                           i64 d, T slope) {
-  T s = 0;
-  for (i64 c = 0; c < d; ++c) s += w[c] * gat_lrelu(a[c] + b[c], slope);
-  return s;
-}
-
 // stats (n_l, h, 2) doubles as scratch: filled with (-1e9, 0), atomic max, atomic sum of exp(s - m), then 1 / sum.
 template <typename T>
 __global__ void k_gv2attn_stats_init_generic(T* __restrict__ stats, i64 n) {
@@ -156,72 +129,11 @@ __global__ void k_gv2attn_stats_init_generic(T* __restrict__ stats, i64 n) {
   }
 }
 
-// lanes over the chunk's slots, one head at a time
-template <typename T, bool SUM>
-__global__ __launch_bounds__(kGenericBlock) void k_gv2attn_stats_generic(
-    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
-    const T* __restrict__ xl, const T* __restrict__ xr, const T* __restrict__ att, T* __restrict__ stats,
-    i64 n_chunks, i64 h, i64 d, T slope) {
-  const i64 c = generic_chunk_id();
-  if (c >= n_chunks) return;
-  const int lane = threadIdx.x & 63;
-  const i64 r = row[c];
-  const i64 j0 = indptr[c], j1 = indptr[c + 1];
-  if (j1 <= j0) return;   // wave-uniform
-  for (i64 k = 0; k < h; ++k) {
-    const T m = SUM ? stats[(r * h + k) * 2] : (T)0;
-    T acc = SUM ? (T)0 : (T)-1e9;
-    for (i64 j = j0 + lane; j < j1; j += kWave) {
-      const T s = gv2attn_score<T>(xl + (r * h + k) * d, xr + (indices[j] * h + k) * d, att + k * d, d, slope);
-      if constexpr (SUM) acc += exp_t(s - m);
-      else acc = s > acc ? s : acc;
-    }
-    for (int o = 1; o < kWave; o <<= 1) {
-      const T t = __shfl_xor(acc, o);
-      if constexpr (SUM) acc += t;
-      else acc = t > acc ? t : acc;
-    }
-    if (lane == 0) {
-      if constexpr (SUM) atomicAdd(stats + (r * h + k) * 2 + 1, acc);
-      else atomic_max_float(stats + (r * h + k) * 2, acc);
-    }
-  }
-}
-
 template <typename T>
 __global__ void k_gv2attn_stats_fin_generic(T* __restrict__ stats, i64 n) {
   for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (i64)gridDim.x * blockDim.x) {
     const T s = stats[2 * i + 1];
     stats[2 * i + 1] = s > (T)0 ? (T)1 / s : (T)0;
-  }
-}
-
-// lanes over the h * d elements of the row in steps of the wave; one atomic per (chunk, element).  DROP (here and in
-// the two backward kernels): one drop_mult per use.
-template <typename T, bool DROP>
-__global__ __launch_bounds__(kGenericBlock) void k_gv2attn_fwd_generic(
-    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
-    const T* __restrict__ xl, const T* __restrict__ xr, const T* __restrict__ att, const T* __restrict__ stats,
-    T* __restrict__ o, i64 n_chunks, i64 h, i64 d, T slope, DropArgsIf<DROP, T> dr) {
-  const i64 c = generic_chunk_id();
-  if (c >= n_chunks) return;
-  const int lane = threadIdx.x & 63;
-  const i64 r = row[c];
-  const i64 j0 = indptr[c], j1 = indptr[c + 1];
-  if (j1 <= j0) return;
-  const i64 f = h * d;
-  for (i64 it = lane; it < f; it += kWave) {
-    const i64 k = it / d;
-    const T m = stats[(r * h + k) * 2], il = stats[(r * h + k) * 2 + 1];
-    T acc = 0;
-    for (i64 j = j0; j < j1; ++j) {
-      const i64 src = indices[j];
-      const T s = gv2attn_score<T>(xl + (r * h + k) * d, xr + (src * h + k) * d, att + k * d, d, slope);
-      T w = exp_t(s - m) * il;
-      if constexpr (DROP) w *= drop_mult<T>(r, src, k, dr);
-      acc += w * xr[src * f + it];
-    }
-    atomicAdd(o + r * f + it, acc);
   }
 }
 
@@ -238,79 +150,13 @@ __global__ void k_gv2attn_pack_generic(const T* __restrict__ stats, const T* __r
   }
 }
 
-// ds of one (slot, head): i = the row-major row (P[i, k] holds m, 1 / l, D), j = the column; *a_out = a_ij; mult = the
-// slot's dropout multiplier m_ij (1 without dropout)
-template <typename T>
-__device__ __forceinline__ T gv2attn_ds(const T* __restrict__ xl_ik, const T* __restrict__ xr_jk,
-                                        const T* __restrict__ att_k, const T* __restrict__ p,
-                                        const T* __restrict__ dO_ik, i64 d, T slope, T mult, T* a_out) {
-  const T s = gv2attn_score<T>(xl_ik, xr_jk, att_k, d, slope);
-  const T a = exp_t(s - p[0]) * p[1];
-  T da = 0;
-  for (i64 t = 0; t < d; ++t) da += dO_ik[t] * xr_jk[t];
-  *a_out = a;
-  return a * (mult * da - p[2]);
-}
-
-template <typename T, bool DROP>
-__global__ __launch_bounds__(kGenericBlock) void k_gv2attn_bwd_row_generic(
-    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
-    const T* __restrict__ xl, const T* __restrict__ xr, const T* __restrict__ att, const T* __restrict__ P,
-    const T* __restrict__ dO, T* __restrict__ dxl, T* __restrict__ datt, i64 n_chunks, i64 h, i64 d, T slope,
-    DropArgsIf<DROP, T> dr) {
-  const i64 c = generic_chunk_id();
-  if (c >= n_chunks) return;
-  const int lane = threadIdx.x & 63;
-  const i64 r = row[c];
-  const i64 j0 = indptr[c], j1 = indptr[c + 1];
-  if (j1 <= j0) return;
-  const i64 f = h * d;
-  for (i64 it = lane; it < f; it += kWave) {
-    const i64 k = it / d;
-    const T a = xl[r * f + it];
-    T acc = 0, dw = 0, aij;
-    for (i64 j = j0; j < j1; ++j) {
-      const i64 src = indices[j];
-      T mult = 1;
-      if constexpr (DROP) mult = drop_mult<T>(r, src, k, dr);
-      const T ds = gv2attn_ds<T>(xl + (r * h + k) * d, xr + (src * h + k) * d, att + k * d, P + (r * h + k) * 4,
-                                 dO + (r * h + k) * d, d, slope, mult, &aij);
-      const T z = a + xr[src * f + it];
-      acc += gat_lrelu_grad(z, ds, slope);
-      dw += ds * gat_lrelu(z, slope);
-    }
-    atomicAdd(dxl + r * f + it, acc * att[it]);
-    atomicAdd(datt + it, dw);
-  }
-}
-
-template <typename T, bool DROP>
-__global__ __launch_bounds__(kGenericBlock) void k_gv2attn_bwd_col_generic(
-    const i64* __restrict__ col, const i64* __restrict__ indptr, const i64* __restrict__ indices,
-    const T* __restrict__ xl, const T* __restrict__ xr, const T* __restrict__ att, const T* __restrict__ P,
-    const T* __restrict__ dO, T* __restrict__ dxr, i64 n_chunks, i64 h, i64 d, T slope, DropArgsIf<DROP, T> dr) {
-  const i64 c = generic_chunk_id();
-  if (c >= n_chunks) return;
-  const int lane = threadIdx.x & 63;
-  const i64 jc = col[c];
-  const i64 j0 = indptr[c], j1 = indptr[c + 1];
-  if (j1 <= j0) return;
-  const i64 f = h * d;
-  for (i64 it = lane; it < f; it += kWave) {
-    const i64 k = it / d;
-    const T b = xr[jc * f + it], w = att[it];
-    T acc = 0, aij;
-    for (i64 j = j0; j < j1; ++j) {
-      const i64 i = indices[j];
-      T mult = 1;
-      if constexpr (DROP) mult = drop_mult<T>(i, jc, k, dr);
-      const T ds = gv2attn_ds<T>(xl + (i * h + k) * d, xr + (jc * h + k) * d, att + k * d, P + (i * h + k) * 4,
-                                 dO + (i * h + k) * d, d, slope, mult, &aij);
-      if constexpr (DROP) aij *= mult;   // a_ij m_ij
-      acc += gat_lrelu_grad(xl[i * f + it] + b, ds, slope) * w + aij * dO[i * f + it];
-    }
-    atomicAdd(dxr + jc * f + it, acc);
-  }
-}
+// ---- the generic gather passes: kernels_gatv2_attn_generic.inc (kernels_gatv2_edge_attn.h includes it with the edge row)
+#define GV2_EDGE 0
+#define GV2_GKERNEL(pass) k_gv2attn_##pass##_generic
+#define GV2_GFN(name) gv2attn_##name
+#include "kernels_gatv2_attn_generic.inc"
+#undef GV2_EDGE
+#undef GV2_GKERNEL
+#undef GV2_GFN
 
 }  // namespace graphop

@@ -4,6 +4,26 @@
 // DROP cannot be a template parameter of one __global__, and a shared __forceinline__ body reschedules every undropped
 // kernel (DESIGN.md 4.5g); the text compiled twice leaves them instruction for instruction what they were.  `dr` is an
 // empty NoDrop without dropout; only `if constexpr (DROP)` code names its members.
+// GV2_EDGE (0 / 1; kernels_gatv2_edge_attn.h includes this file twice more with 1, as k_gv2edge_* and k_gv2edrop_*) adds
+// the edge row: z = (xl_i + xr_j) + xe_e for edge e = eid[slot].  GV2_IF_EDGE(...) is its arguments with the edge row and
+// nothing without, and `#if GV2_EDGE` picks between the two forms of z; with GV2_EDGE 0 the text is the one before the
+// edge row existed.  The lanes that load a batch's neighbour ids also load its edge ids, which travel by one more
+// group_bcast; a NULL eid in a row-major pass means eid[slot] == slot (a plan with eid_identity): a kernel-uniform
+// branch.  xe_e is consumed where z is formed (gv2edge_z4, then gv2edge_dot4 in every pass), so no pass keeps a second
+// [SB][NV] array; the row pass also stores dxe[e] = ds att t, one float4 per lane and real slot, where dxe is not NULL.
+#if GV2_EDGE
+#define GV2_IF_EDGE(...) __VA_ARGS__
+// the edge id of the lane's slot, loaded by the lanes that load its neighbour id; eo[u] = the 64-bit row offset e * F4
+#define GV2_EDGE_IDS(slot)                        \
+  int my_e = 0;                                   \
+  i64 eo[SB];                                     \
+  if (l < IDL) {                                  \
+    const i64 js = (slot);                        \
+    my_e = eid ? (int)eid[js] : (int)js;          \
+  }
+#else
+#define GV2_IF_EDGE(...)
+#endif
 
 // ---- forward -----------------------------------------------------------------------------------------------------
 // Blocks [0, nb_short): lane groups of 16, one row segment each (segments above long_len slots are skipped);
@@ -14,9 +34,9 @@
 // from the same expressions in the same order as without dropout.
 template <int H, int D>
 __global__ __launch_bounds__(kFastBlock) void GV2_KERNEL(fwd)(
-    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
-    const i64* __restrict__ seg_chunk, const float* __restrict__ xl, const float* __restrict__ xr,
-    const float* __restrict__ att, float* __restrict__ o, float2* __restrict__ stats, i64 n_seg, unsigned nb_short,
+    const i64* __restrict__ row, const i64* __restrict__ indptr, GV2_IF_EDGE(const i64* __restrict__ eid,)
+    const i64* __restrict__ indices, const i64* __restrict__ seg_chunk, const float* __restrict__ xl,
+    const float* __restrict__ xr, GV2_IF_EDGE(const float* __restrict__ xe,) const float* __restrict__ att, float* __restrict__ o, float2* __restrict__ stats, i64 n_seg, unsigned nb_short,
     i64 long_len, const int* __restrict__ long_segs, float slope, typename Gv2DropArg<H, GV2_DROP>::type dr) {
   constexpr bool DROP = GV2_DROP;
   using C = Gv2AttnCfg<H, D>;
@@ -60,10 +80,12 @@ __global__ __launch_bounds__(kFastBlock) void GV2_KERNEL(fwd)(
       int my_src = 0;   // slots past the end re-read the batch's last neighbour with weight 0
       const int t = DROP ? l % SB : l;
       if (l < IDL) my_src = (int)indices[jb + (t < nb ? t : nb - 1)];
+      GV2_IF_EDGE(GV2_EDGE_IDS(jb + (t < nb ? t : nb - 1));)
       float4 x[SB][NV];
       static_for<SB>([&](auto uc) {
         constexpr int u = decltype(uc)::value;
         const i64 src = group_bcast<L, u>(my_src);
+        GV2_IF_EDGE(eo[u] = (i64)group_bcast<L, u>(my_e) * F4;)
 #pragma unroll
         for (int v = 0; v < NV; ++v) x[u][v] = ld4(xr, src * F4 + v * L + l);
       });
@@ -79,7 +101,13 @@ __global__ __launch_bounds__(kFastBlock) void GV2_KERNEL(fwd)(
 #pragma unroll
       for (int u = 0; u < SB; ++u)
 #pragma unroll
-        for (int v = 0; v < NV; ++v) sc[u][v] = group_sum<DQ>(gv2attn_dot4(w[v], a[v], x[u][v], slope));
+        for (int v = 0; v < NV; ++v)
+#if GV2_EDGE
+          sc[u][v] = group_sum<DQ>(
+              gv2edge_dot4(w[v], gv2edge_z4(a[v], x[u][v], ld4_nt(xe, eo[u] + v * L + l)), slope));
+#else
+          sc[u][v] = group_sum<DQ>(gv2attn_dot4(w[v], a[v], x[u][v], slope));
+#endif
 #pragma unroll
       for (int v = 0; v < NV; ++v) {
         float mn = m[v];
@@ -152,9 +180,10 @@ __global__ __launch_bounds__(kFastBlock) void GV2_KERNEL(fwd)(
 // its row, groups without chunks add zeros.  DROP: da_ij = m_ij <dO_i, xr_j>; D_i in P is <dO_i, o_i> of the dropped o.
 template <int H, int D, bool OWNED>
 __global__ __launch_bounds__(kFastBlock) void GV2_KERNEL(bwd_row)(
-    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
-    const float* __restrict__ xl, const float* __restrict__ xr, const float* __restrict__ att,
-    const float4* __restrict__ P, const float* __restrict__ dO, float* __restrict__ dxl,
+    const i64* __restrict__ row, const i64* __restrict__ indptr, GV2_IF_EDGE(const i64* __restrict__ eid,)
+    const i64* __restrict__ indices, const float* __restrict__ xl, const float* __restrict__ xr,
+    GV2_IF_EDGE(const float* __restrict__ xe,) const float* __restrict__ att, const float4* __restrict__ P,
+    const float* __restrict__ dO, float* __restrict__ dxl, GV2_IF_EDGE(float* __restrict__ dxe,)
     float4* __restrict__ datt_part, i64 n_chunks, int chunks_per_group, float slope,
     typename Gv2DropArg<H, GV2_DROP>::type dr) {
   constexpr bool DROP = GV2_DROP;
@@ -219,10 +248,12 @@ __global__ __launch_bounds__(kFastBlock) void GV2_KERNEL(bwd_row)(
         int my_src = 0;   // slots past the end re-read the batch's last neighbour with weight 0
         const int t = DROP ? l % SB : l;
         if (l < IDL) my_src = (int)indices[jb + (t < nb ? t : nb - 1)];
+        GV2_IF_EDGE(GV2_EDGE_IDS(jb + (t < nb ? t : nb - 1));)
         float4 x[SB][NV];
         static_for<SB>([&](auto uc) {
           constexpr int u = decltype(uc)::value;
           const i64 src = group_bcast<L, u>(my_src);
+          GV2_IF_EDGE(eo[u] = (i64)group_bcast<L, u>(my_e) * F4;)
 #pragma unroll
           for (int v = 0; v < NV; ++v) x[u][v] = ld4(xr, src * F4 + v * L + l);
         });
@@ -238,13 +269,26 @@ __global__ __launch_bounds__(kFastBlock) void GV2_KERNEL(bwd_row)(
         for (int u = 0; u < SB; ++u) {
 #pragma unroll
           for (int v = 0; v < NV; ++v) {
+#if GV2_EDGE
+            const float4 z = gv2edge_z4(a[v], x[u][v], ld4_nt(xe, eo[u] + v * L + l));
+            float s = gv2edge_dot4(w[v], z, slope), da = dot4(g[v], x[u][v]);   // x[u][v] is dead from here: z lives on
+#else
             float s = gv2attn_dot4(w[v], a[v], x[u][v], slope), da = dot4(g[v], x[u][v]);
+#endif
             gv2attn_group_sum2<DQ>(s, da);
             if constexpr (DROP) da = (keep[u] >> kv[v]) & 1 ? da * dr.scale : 0.f;
             const float aij = u < nb ? exp_nonpos(s - pm[v]) * pil[v] : 0.f;
             const float ds = aij * (da - pd[v]), dss = ds * slope;
+#if GV2_EDGE
+            const float zx = z.x, zy = z.y, zz = z.z, zw = z.w;
+            if (dxe != nullptr && u < nb)   // the row-major orientation visits a slot once: a plain store
+              reinterpret_cast<float4*>(dxe)[eo[u] + v * L + l] =
+                  make_float4((zx > 0.f ? ds : dss) * w[v].x, (zy > 0.f ? ds : dss) * w[v].y,
+                              (zz > 0.f ? ds : dss) * w[v].z, (zw > 0.f ? ds : dss) * w[v].w);
+#else
             const float zx = a[v].x + x[u][v].x, zy = a[v].y + x[u][v].y;
             const float zz = a[v].z + x[u][v].z, zw = a[v].w + x[u][v].w;
+#endif
             acc[v].x += zx > 0.f ? ds : dss;
             acc[v].y += zy > 0.f ? ds : dss;
             acc[v].z += zz > 0.f ? ds : dss;
@@ -289,9 +333,10 @@ __global__ __launch_bounds__(kFastBlock) void GV2_KERNEL(bwd_row)(
 // counter stays (i, j) = (gathered id, own column); da_ij = m_ij <dO_i, xr_j> and the second term is a_ij m_ij dO_i.
 template <int H, int D, bool OWNED>
 __global__ __launch_bounds__(kFastBlock) void GV2_KERNEL(bwd_col)(
-    const i64* __restrict__ col, const i64* __restrict__ indptr, const i64* __restrict__ indices,
-    const float* __restrict__ xl, const float* __restrict__ xr, const float* __restrict__ att,
-    const float4* __restrict__ P, const float* __restrict__ dO, float* __restrict__ dxr, i64 n_chunks,
+    const i64* __restrict__ col, const i64* __restrict__ indptr, GV2_IF_EDGE(const i64* __restrict__ eid,)
+    const i64* __restrict__ indices, const float* __restrict__ xl, const float* __restrict__ xr,
+    GV2_IF_EDGE(const float* __restrict__ xe,) const float* __restrict__ att, const float4* __restrict__ P,
+    const float* __restrict__ dO, float* __restrict__ dxr, i64 n_chunks,
     int chunks_per_group, float slope, typename Gv2DropArg<H, GV2_DROP>::type dr) {
   constexpr bool DROP = GV2_DROP;
   using C = Gv2AttnCfg<H, D>;
@@ -344,10 +389,12 @@ __global__ __launch_bounds__(kFastBlock) void GV2_KERNEL(bwd_col)(
       int my_src = 0;   // slots past the end re-read the batch's last neighbour with weight 0
       const int t = DROP ? l % SB : l;
       if (l < IDL) my_src = (int)indices[jb + (t < nb ? t : nb - 1)];
+      GV2_IF_EDGE(GV2_EDGE_IDS(jb + (t < nb ? t : nb - 1));)
       float4 x[SB][NV], y[SB][NV], p[SB][NV];   // xl_i, dO_i, P[i, k_v]
       static_for<SB>([&](auto uc) {
         constexpr int u = decltype(uc)::value;
         const i64 src = group_bcast<L, u>(my_src);
+        GV2_IF_EDGE(eo[u] = (i64)group_bcast<L, u>(my_e) * F4;)
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
           x[u][v] = ld4(xl, src * F4 + v * L + l);
@@ -367,7 +414,12 @@ __global__ __launch_bounds__(kFastBlock) void GV2_KERNEL(bwd_col)(
       for (int u = 0; u < SB; ++u) {
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
+#if GV2_EDGE
+          const float4 z = gv2edge_z4(x[u][v], b[v], ld4(xe, eo[u] + v * L + l));   // a random row read: e = eid_c[slot]
+          float s = gv2edge_dot4(w[v], z, slope), da = dot4(y[u][v], b[v]);
+#else
           float s = gv2attn_dot4(w[v], x[u][v], b[v], slope), da = dot4(y[u][v], b[v]);
+#endif
           gv2attn_group_sum2<DQ>(s, da);
           const float aij = u < nb ? exp_nonpos(s - p[u][v].x) * p[u][v].y : 0.f;
           float am = aij;   // a_ij m_ij
@@ -377,8 +429,12 @@ __global__ __launch_bounds__(kFastBlock) void GV2_KERNEL(bwd_col)(
             am *= m;
           }
           const float ds = aij * (da - p[u][v].z), dss = ds * slope;
+#if GV2_EDGE
+          const float zx = z.x, zy = z.y, zz = z.z, zw = z.w;
+#else
           const float zx = x[u][v].x + b[v].x, zy = x[u][v].y + b[v].y;
           const float zz = x[u][v].z + b[v].z, zw = x[u][v].w + b[v].w;
+#endif
           acc[v].x = fmaf(zx > 0.f ? ds : dss, w[v].x, fmaf(am, y[u][v].x, acc[v].x));
           acc[v].y = fmaf(zy > 0.f ? ds : dss, w[v].y, fmaf(am, y[u][v].y, acc[v].y));
           acc[v].z = fmaf(zz > 0.f ? ds : dss, w[v].z, fmaf(am, y[u][v].z, acc[v].z));
@@ -389,3 +445,8 @@ __global__ __launch_bounds__(kFastBlock) void GV2_KERNEL(bwd_col)(
   }
   if (dirty) flush(cur);
 }
+
+#undef GV2_IF_EDGE
+#if GV2_EDGE
+#undef GV2_EDGE_IDS
+#endif

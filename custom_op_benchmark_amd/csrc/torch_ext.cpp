@@ -543,22 +543,42 @@ DropSpec drop_spec(const char* fn, double p, int64_t seed, int64_t offset) {
 }
 
 // ---- the fused GATv2 attention op (include/graphop_hip.h: graphop_gatv2_attention_*) ------------------------------
-// drop == nullptr: graphop_gatv2_attention_forward, else its dropout form
+// the edge rows of graphop_gatv2_edge_attention_*: (n_edges, d) for 2-D xl / xr, else (n_edges, h, d), in xl's dtype
+void gatv2_edge_rows(const at::Tensor& xl, const at::Tensor& xe, int64_t n_edges, int64_t h, int64_t d,
+                     const char* fn) {
+  CHECK_INPUT(xe);
+  CHECK_SAME_DTYPE(xl, xe);
+  const bool tail = xl.dim() == 2 ? (xe.dim() == 2 && xe.size(1) == d)
+                                  : (xe.dim() == 3 && xe.size(1) == h && xe.size(2) == d);
+  if (tail) CHECK_EDGE_ROWS(xe, n_edges);
+  TORCH_CHECK(tail && xe.size(0) == n_edges, fn, ": xe must be (n_edges, d) for 2-D xl / xr, else (n_edges, h, d) with "
+              "n_edges = ", n_edges, ", h = ", h, " and d = ", d, ", got xe ", xe.sizes(), ", xl ", xl.sizes());
+}
+
+// drop == nullptr: graphop_gatv2_attention_forward, else its dropout form or, with the edge rows xe (which need drop),
+// graphop_gatv2_edge_attention_forward, as `fn`
 std::vector<at::Tensor> gatv2_attention_forward_impl(const char* fn, const at::Tensor& row, const at::Tensor& indptr,
                                                      const at::Tensor& eid, const at::Tensor& indices,
                                                      const at::Tensor& xl, const at::Tensor& xr, const at::Tensor& att,
-                                                     double negative_slope, const DropSpec* drop) {
+                                                     double negative_slope, const DropSpec* drop,
+                                                     const at::Tensor* xe = nullptr) {
   CHECK_CSR(row, indptr, eid, indices);
   CHECK_INPUT(xl); CHECK_INPUT(xr); CHECK_INPUT(att);
   const auto hd = gatv2_shapes(xl, xr, att, fn);
   const int64_t h = hd.first, d = hd.second;
-  DeviceGuard dg(xl);
   const int64_t e = eid.size(0), n_l = xl.size(0);
+  if (xe) gatv2_edge_rows(xl, *xe, e, h, d, fn);
+  DeviceGuard dg(xl);
   auto o = at::empty_like(xl);
   auto stats = at::empty({n_l, h, 2}, xl.options());
   const auto pp = get_plan(row, indptr, eid, indices, xr.size(0));
   const auto& p = *pp;
-  if (drop)
+  if (xe)
+    check(graphop_gatv2_edge_attention_forward(dtype_code(xl), ip(row), ip(indptr), ip(eid), ip(indices), vp(xl), vp(xr),
+                                               vp(*xe), vp(att), vp(o), vp(stats), row.size(0), e, n_l, xr.size(0), h, d,
+                                               negative_slope, drop->p, drop->seed, drop->offset, p.plan,
+                                               stream_of(xl)));
+  else if (drop)
     check(graphop_gatv2_attention_dropout_forward(dtype_code(xl), ip(row), ip(indptr), ip(eid), ip(indices), vp(xl),
                                                   vp(xr), vp(att), vp(o), vp(stats), row.size(0), e, n_l, xr.size(0), h,
                                                   d, negative_slope, drop->p, drop->seed, drop->offset, p.plan,
@@ -581,10 +601,12 @@ std::vector<at::Tensor> gatv2_attention_dropout_forward(const at::Tensor& row, c
                                                         const at::Tensor& eid, const at::Tensor& indices,
                                                         const at::Tensor& xl, const at::Tensor& xr,
                                                         const at::Tensor& att, double negative_slope, double p,
-                                                        int64_t seed, int64_t offset) {
+                                                        int64_t seed, int64_t offset,
+                                                        const c10::optional<at::Tensor>& xe) {
   const char* fn = "gatv2_attention_dropout_forward";
   const DropSpec drop = drop_spec(fn, p, seed, offset);
-  return gatv2_attention_forward_impl(fn, row, indptr, eid, indices, xl, xr, att, negative_slope, &drop);
+  return gatv2_attention_forward_impl(fn, row, indptr, eid, indices, xl, xr, att, negative_slope, &drop,
+                                      xe.has_value() ? &*xe : nullptr);
 }
 
 std::vector<at::Tensor> gatv2_attention_backward_impl(const char* fn, const at::Tensor& row,
@@ -594,18 +616,19 @@ std::vector<at::Tensor> gatv2_attention_backward_impl(const char* fn, const at::
                                                       const at::Tensor& indices_c, const at::Tensor& xl,
                                                       const at::Tensor& xr, const at::Tensor& att, const at::Tensor& o,
                                                       const at::Tensor& stats, const at::Tensor& dO_,
-                                                      double negative_slope, const DropSpec* drop) {
+                                                      double negative_slope, const DropSpec* drop,
+                                                      const at::Tensor* xe = nullptr, bool need_dxe = true) {
   CHECK_CSR(row, indptr_r, eid_r, indices_r);
   CHECK_CSR(col, indptr_c, eid_c, indices_c);
   CHECK_INPUT(xl); CHECK_INPUT(xr); CHECK_INPUT(att); CHECK_INPUT(o); CHECK_INPUT(stats);
   CHECK_CUDA(dO_);
   const auto hd = gatv2_shapes(xl, xr, att, fn);
   const int64_t h = hd.first, d = hd.second;
+  const int64_t e = eid_r.size(0), n_l = xl.size(0);
+  if (xe) gatv2_edge_rows(xl, *xe, e, h, d, fn);
   CHECK_SAME_DTYPE(xl, o); CHECK_SAME_DTYPE(xl, stats); CHECK_SAME_DTYPE(xl, dO_);
-  const int64_t n_l = xl.size(0);
   const at::Tensor dO = saved_checked(fn, xl.sizes(), n_l, h, o, stats, dO_);
   DeviceGuard dg(xl);
-  const int64_t e = eid_r.size(0);
   auto dxl = at::empty_like(xl), dxr = at::empty_like(xr), datt = at::empty_like(att);
   // the workspace minimum of include/graphop_hip.h: (m, 1 / l, D, 0) per (node, head), then the row-pass partials
   const int64_t ws_values = n_l * h * 4 + gatv2_row_pass_values(row.size(0), h, d);
@@ -613,6 +636,15 @@ std::vector<at::Tensor> gatv2_attention_backward_impl(const char* fn, const at::
   const auto ppr = get_plan(row, indptr_r, eid_r, indices_r, xr.size(0));
   const auto ppc = get_plan(col, indptr_c, eid_c, indices_c, n_l);
   const auto &pr = *ppr, &pc = *ppc;
+  if (xe) {
+    auto dxe = need_dxe ? at::empty_like(*xe) : at::empty({0}, xe->options());   // the only edge-sized tensor made
+    check(graphop_gatv2_edge_attention_backward(
+        dtype_code(xl), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c),
+        ip(indices_c), vp(xl), vp(xr), vp(*xe), vp(att), vp(o), vp(stats), vp(dO), vp(dxl), vp(dxr),
+        need_dxe ? vp(dxe) : nullptr, vp(datt), vp(ws), ws.numel() * ws.element_size(), row.size(0), col.size(0), e,
+        n_l, xr.size(0), h, d, negative_slope, drop->p, drop->seed, drop->offset, pr.plan, pc.plan, stream_of(xl)));
+    return {dxl, dxr, datt, dxe};
+  }
   if (drop)
     check(graphop_gatv2_attention_dropout_backward(
         dtype_code(xl), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c),
@@ -647,11 +679,13 @@ std::vector<at::Tensor> gatv2_attention_dropout_backward(const at::Tensor& row, 
                                                          const at::Tensor& att, const at::Tensor& o,
                                                          const at::Tensor& stats, const at::Tensor& dO,
                                                          double negative_slope, double p, int64_t seed,
-                                                         int64_t offset) {
+                                                         int64_t offset, const c10::optional<at::Tensor>& xe,
+                                                         bool need_dxe) {
   const char* fn = "gatv2_attention_dropout_backward";
   const DropSpec drop = drop_spec(fn, p, seed, offset);
   return gatv2_attention_backward_impl(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr,
-                                       att, o, stats, dO, negative_slope, &drop);
+                                       att, o, stats, dO, negative_slope, &drop, xe.has_value() ? &*xe : nullptr,
+                                       need_dxe);
 }
 
 // ---- the fused GAT attention op (include/graphop_hip.h: graphop_gat_attention_*) -----------------------------------
@@ -929,12 +963,14 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("gatv2_attention_dropout_forward", &gatv2_attention_dropout_forward,
         "Fused GATv2 attention forward with attention dropout (extra op)", py::arg("row"), py::arg("indptr"),
         py::arg("eid"), py::arg("indices"), py::arg("xl"), py::arg("xr"), py::arg("att"),
-        py::arg("negative_slope") = 0.2, py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0);
+        py::arg("negative_slope") = 0.2, py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0,
+        py::arg("xe") = py::none());
   m.def("gatv2_attention_dropout_backward", &gatv2_attention_dropout_backward,
         "Fused GATv2 attention backward with attention dropout (extra op)", py::arg("row"), py::arg("indptr_r"),
         py::arg("eid_r"), py::arg("indices_r"), py::arg("col"), py::arg("indptr_c"), py::arg("eid_c"),
         py::arg("indices_c"), py::arg("xl"), py::arg("xr"), py::arg("att"), py::arg("o"), py::arg("stats"),
-        py::arg("dO"), py::arg("negative_slope") = 0.2, py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0);
+        py::arg("dO"), py::arg("negative_slope") = 0.2, py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0,
+        py::arg("xe") = py::none(), py::arg("need_dxe") = true);
   m.def("gat_edge_attention_forward", &gat_edge_attention_forward,
         "Fused GAT attention with an edge term, forward (extra op)", py::arg("row"), py::arg("indptr"), py::arg("eid"),
         py::arg("indices"), py::arg("el"), py::arg("er"), py::arg("ee"), py::arg("V"), py::arg("negative_slope") = 0.2,
@@ -975,8 +1011,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   X(gatv2_scores_backward, "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor dy, float negative_slope=0.2) -> Tensor[]") \
   X(gatv2_attention_forward, "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor xl, Tensor xr, Tensor att, float negative_slope=0.2) -> Tensor[]") \
   X(gatv2_attention_backward, "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2) -> Tensor[]") \
-  X(gatv2_attention_dropout_forward, "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor xl, Tensor xr, Tensor att, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]") \
-  X(gatv2_attention_dropout_backward, "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]") \
+  X(gatv2_attention_dropout_forward, "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor xl, Tensor xr, Tensor att, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0, Tensor? xe=None) -> Tensor[]") \
+  X(gatv2_attention_dropout_backward, "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0, Tensor? xe=None, bool need_dxe=True) -> Tensor[]") \
   X(gat_edge_attention_forward, "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, Tensor ee, Tensor V, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]") \
   X(gat_edge_attention_backward, "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor ee, Tensor V, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0, bool need_dee=True) -> Tensor[]")
 #define GRAPHOP_DEF(name, schema) m.def(#name schema);

@@ -235,6 +235,33 @@ class FusedGATEdgeAttention(Function):
         return (None,) * 8 + (d_el, d_er, d_ee if need_dee else None, dV, None, None, None, None)
 
 
+class FusedGATv2EdgeAttention(Function):
+    """The fused GATv2 layer with edge features (extra op; GATv2Conv(edge_dim=...)):
+    apply(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, xe, att, negative_slope, p, seed, offset)
+    -> o[i] = sum_j softmax_j(att . LeakyReLU(xl[i] + xr[j] + xe[e])) m_ij xr[j] for edge e = (i, j), xe indexed by edge
+    id: (n_edges, d) for 2-D xl / xr, else (n_edges, h, d).  m_ij is the multiplier of FusedGATAttentionDropout (1 at
+    p = 0; seed=None draws one from torch's default CPU generator).  Saves the CSR arrays, xl, xr, xe, att, o and stats
+    only; the backward makes one edge-sized tensor, the gradient of xe, and none when xe does not require grad."""
+
+    @staticmethod
+    def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, xe, att, negative_slope,
+                p=0.0, seed=None, offset=0):
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        ctx.drop = (float(negative_slope), float(p), int(seed), int(offset))
+        o, stats = _ops.gatv2_attention_dropout_forward(row, indptr_r, eid_r, indices_r, xl, xr, att, *ctx.drop, xe=xe)
+        ctx.save_for_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, xe, att, o, stats)
+        return o
+
+    @staticmethod
+    def backward(ctx, dO):
+        a8, (xl, xr, xe, att, o, stats) = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
+        need_dxe = ctx.needs_input_grad[10]
+        dxl, dxr, datt, dxe = _ops.gatv2_attention_dropout_backward(*a8, xl, xr, att, o, stats, dO, *ctx.drop, xe=xe,
+                                                                    need_dxe=need_dxe)
+        return (None,) * 8 + (dxl, dxr, dxe if need_dxe else None, datt, None, None, None, None)
+
+
 # FusedAttention over several heads (round 5): "keep" = per head group only a_g (E x hg) survives the forward, the backward's
 # da_g / ds_g are E x hg temporaries -- speed of the 8-function step, about half of its E-sized memory; "recompute" = nothing
 # E-sized survives the forward, the backward recomputes s_g and a_g per group (two more passes per group: ~+17 % time,
@@ -516,6 +543,36 @@ def fused_gat_edge_attention_step(g, el, er, ee, V, dO, negative_slope=0.2, p=0.
     """The counterpart of gat_edge_attention_step through FusedGATEdgeAttention; returns o.  The gradient of ee is the
     only edge-sized tensor made, and none is when ee does not require grad."""
     o = FusedGATEdgeAttention.apply(*g.csr_args(), el, er, ee, V, negative_slope, p, seed, offset)
+    o.backward(dO)
+    _lib.check_errors(sync=False)     # as in attention_step
+    return o
+
+
+def gatv2_edge_attention_step(g, xl, xr, xe, att, dO, negative_slope=0.2, p=0.0, seed=0, offset=0):
+    """One fwd+bwd of GATv2 attention with edge features, composed: the score in plain torch (index_select of xl and xr
+    over the row-major slots, + xe[eid], leaky_relu, (. * att).sum(-1), put back in edge-id order), then SparseSoftmax,
+    (* edge_dropout_mask when p > 0) and VectorSPMM(., xr); o.backward(dO).  Keeps xl[src], xr[dst], z and LeakyReLU(z)
+    as (E, h, d) tensors and s, a (and the mask) as (E, h) ones.  The operands that need a gradient must be leaf tensors
+    with requires_grad; returns (s, a, o) with a the undropped weights."""
+    z = (xl.index_select(0, g.src) + xr.index_select(0, g.dst)) + xe.index_select(0, g.eid_r)
+    s_slot = (torch.nn.functional.leaky_relu(z, negative_slope) * att).sum(-1)
+    s = torch.zeros((g.n_edges,) + tuple(s_slot.shape[1:]), dtype=s_slot.dtype,
+                    device=s_slot.device).index_copy(0, g.eid_r, s_slot)
+    a = SparseSoftmax.apply(g.row, g.ptr_r, g.eid_r, s)
+    w = a
+    if p > 0:
+        h = 1 if xl.dim() == 2 else xl.size(1)
+        w = a * _ops.edge_dropout_mask(g.row, g.ptr_r, g.eid_r, g.indices_r, h, p, seed, offset, a.dtype)
+    o = VectorSPMM.apply(*g.csr_args(), w, xr)
+    o.backward(dO)
+    _lib.check_errors(sync=False)     # as in attention_step
+    return s, a, o
+
+
+def fused_gatv2_edge_attention_step(g, xl, xr, xe, att, dO, negative_slope=0.2, p=0.0, seed=0, offset=0):
+    """The counterpart of gatv2_edge_attention_step through FusedGATv2EdgeAttention; returns o.  The gradient of xe is the
+    only edge-sized tensor made, and none is when xe does not require grad."""
+    o = FusedGATv2EdgeAttention.apply(*g.csr_args(), xl, xr, xe, att, negative_slope, p, seed, offset)
     o.backward(dO)
     _lib.check_errors(sync=False)     # as in attention_step
     return o

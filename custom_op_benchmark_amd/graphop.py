@@ -31,7 +31,9 @@ __all__ = ["maskedmm_csr_forward", "maskedmm_csr_backward", "node_mul_edge_forwa
 # the GAT additive attention scores (LeakyReLU(el[i] + er[j]) per edge and head), the fused GAT attention layer and
 # its forms with attention dropout (plus the mask they apply, as an edge tensor, for the composed path), and the GATv2
 # scores (att . LeakyReLU(xl[i] + xr[j]) per edge and head), and the fused GAT layer with a per-edge score term
-# (LeakyReLU(el[i] + er[j] + ee[e]), GATConv(edge_dim=...) / EGATConv).  EXTRA_OPS lists them, below _SCHEMAS.
+# (LeakyReLU(el[i] + er[j] + ee[e]), GATConv(edge_dim=...) / EGATConv), and the fused GATv2 layer with edge features
+# (att . LeakyReLU(xl[i] + xr[j] + xe[e]), GATv2Conv(edge_dim=...)): the optional xe / need_dxe arguments of the two
+# gatv2_attention_dropout_* ops.  EXTRA_OPS lists them, below _SCHEMAS.
 
 _NULL = None
 # the index arrays of a call by argument name: one CSR orientation without and with `indices`, and the two spellings
@@ -455,46 +457,70 @@ def _gatv2_attention_workspace_values(n_l, n_row_chunks, h, d):
     return n_l * h * 4 + min((n_row_chunks + 15) // 16, 8192) * h * d
 
 
-def _gatv2_attention_forward(fn, row, indptr, eid, indices, xl, xr, att, negative_slope, drop=()):
-    """gatv2_attention_forward (drop = ()) or gatv2_attention_dropout_forward (drop = (p, seed, offset)) as `fn`."""
+def _gatv2_edge_rows(xl, xe, n_edges, h, d, fn):
+    """xe checked against the graph and xl: (n_edges, d) for 2-D xl / xr, else (n_edges, h, d), in xl's dtype."""
+    _check_input(xe, "xe")
+    _same_dtype(xl, xe, "xl", "xe")
+    want = (n_edges, d) if xl.dim() == 2 else (n_edges, h, d)
+    if xe.dim() == len(want) and tuple(xe.shape[1:]) == want[1:]:
+        _check_edge_rows(xe, "xe", n_edges)
+    if tuple(xe.shape) != want:
+        raise RuntimeError("%s: xe must be (n_edges, d) for 2-D xl / xr, else (n_edges, h, d) with n_edges = %d, h = %d "
+                           "and d = %d, got xe %s, xl %s" % (fn, n_edges, h, d, tuple(xe.shape), tuple(xl.shape)))
+
+
+def _gatv2_attention_forward(fn, row, indptr, eid, indices, xl, xr, att, negative_slope, drop=(), xe=None):
+    """gatv2_attention_forward (drop = ()) or gatv2_attention_dropout_forward (drop = (p, seed, offset)) as `fn`; with the
+    edge rows xe (which need drop) the C entry point is graphop_gatv2_edge_attention_forward."""
+    edge = () if xe is None else (xe,)
     _check_csr((row, indptr, eid, indices), _CSR, (xl, "xl"), (xr, "xr"), (att, "att"))
     h, d = _gatv2_shapes(xl, xr, att, fn)
     e, n_l = eid.size(0), xl.size(0)
+    if edge:
+        _gatv2_edge_rows(xl, xe, e, h, d, fn)         # checks xe as an input too
     o = torch.empty_like(xl)
     stats = torch.empty((n_l, h, 2), dtype=xl.dtype, device=xl.device)
     with _lib.device_guard(xl.device):
         plan = get_plan(row, indptr, eid, indices, xr.size(0))
-        check(getattr(lib(), "graphop_" + fn)(
-            dtype_code(xl), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(xl), ptr(xr), ptr(att), ptr(o),
-            ptr(stats), row.size(0), e, n_l, xr.size(0), h, d, float(negative_slope), *drop, plan.handle,
-            stream_of(xl)))
+        check(getattr(lib(), "graphop_gatv2_edge_attention_forward" if edge else "graphop_" + fn)(
+            dtype_code(xl), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(xl), ptr(xr), *(ptr(t) for t in edge),
+            ptr(att), ptr(o), ptr(stats), row.size(0), e, n_l, xr.size(0), h, d, float(negative_slope), *drop,
+            plan.handle, stream_of(xl)))
     return [o, stats]
 
 
 def _gatv2_attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, o,
-                              stats, dO, negative_slope, drop=()):
-    """gatv2_attention_backward (drop = ()) or gatv2_attention_dropout_backward (drop = (p, seed, offset)) as `fn`."""
+                              stats, dO, negative_slope, drop=(), xe=None, need_dxe=True):
+    """gatv2_attention_backward (drop = ()) or gatv2_attention_dropout_backward (drop = (p, seed, offset)) as `fn`:
+    -> [dxl, dxr, datt]; with the edge rows xe (which need drop) the C entry point is
+    graphop_gatv2_edge_attention_backward: -> [dxl, dxr, datt, dxe]."""
+    edge = () if xe is None else (xe,)
     _check_csr((row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c), _CSR_RC,
                (xl, "xl"), (xr, "xr"), (att, "att"), (o, "o"), (stats, "stats"))
     _check_grad(dO, "dO")
     h, d = _gatv2_shapes(xl, xr, att, fn)
+    e, n_l = eid_r.size(0), xl.size(0)
+    if edge:
+        _gatv2_edge_rows(xl, xe, e, h, d, fn)         # checks xe as an input too
     for t, n in ((o, "o"), (stats, "stats"), (dO, "dO")):
         _same_dtype(xl, t, "xl", n)
-    n_l = xl.size(0)
     dO = _saved_checked(fn, tuple(xl.shape), n_l, h, o, stats, dO)
-    e = eid_r.size(0)
     dxl, dxr, datt = torch.empty_like(xl), torch.empty_like(xr), torch.empty_like(att)
+    dxe = ()        # with xe: [dxe], an empty (0,) tensor and a NULL pointer where it is not wanted
+    if edge:
+        dxe = (torch.empty_like(xe) if need_dxe else torch.empty((0,), dtype=xe.dtype, device=xe.device),)
     ws = torch.empty(max(_gatv2_attention_workspace_values(n_l, row.size(0), h, d), 1), dtype=xl.dtype,
                      device=xl.device)
     with _lib.device_guard(xl.device):
         plan_r = get_plan(row, indptr_r, eid_r, indices_r, xr.size(0))
         plan_c = get_plan(col, indptr_c, eid_c, indices_c, n_l)
-        check(getattr(lib(), "graphop_" + fn)(
+        check(getattr(lib(), "graphop_gatv2_edge_attention_backward" if edge else "graphop_" + fn)(
             dtype_code(xl), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c),
-            ptr(eid_c), ptr(indices_c), ptr(xl), ptr(xr), ptr(att), ptr(o), ptr(stats), ptr(dO), ptr(dxl), ptr(dxr),
-            ptr(datt), ptr(ws), ws.numel() * ws.element_size(), row.size(0), col.size(0), e, n_l, xr.size(0), h, d,
+            ptr(eid_c), ptr(indices_c), ptr(xl), ptr(xr), *(ptr(t) for t in edge), ptr(att), ptr(o), ptr(stats),
+            ptr(dO), ptr(dxl), ptr(dxr), *(ptr(t) if need_dxe else _NULL for t in dxe), ptr(datt), ptr(ws),
+            ws.numel() * ws.element_size(), row.size(0), col.size(0), e, n_l, xr.size(0), h, d,
             float(negative_slope), *drop, plan_r.handle, plan_c.handle, stream_of(xl)))
-    return [dxl, dxr, datt]
+    return [dxl, dxr, datt, *dxe]
 
 
 def gatv2_attention_forward(row, indptr, eid, indices, xl, xr, att, negative_slope=0.2):
@@ -619,22 +645,28 @@ def gat_attention_dropout_backward(row, indptr_r, eid_r, indices_r, col, indptr_
 
 
 def gatv2_attention_dropout_forward(row, indptr, eid, indices, xl, xr, att, negative_slope=0.2, p=0.0, seed=0,
-                                    offset=0):
+                                    offset=0, xe=None):
     """-> [o, stats] of gatv2_attention_forward with dropout on the attention weights: o[i] = sum_j a_ij m_ij xr[j], m_ij
     the multiplier of gat_attention_dropout_forward (i indexes xl, j indexes xr; no edge-sized mask); stats are those of
-    the undropped scores, bit for bit.  p = 0 is gatv2_attention_forward bit for bit."""
+    the undropped scores, bit for bit.  p = 0 is gatv2_attention_forward bit for bit.
+    xe: edge features (GATv2Conv(edge_dim=...)), indexed by edge id: (n_edges, d) for 2-D xl / xr, else (n_edges, h, d).
+    For edge e = (i, j) the score is att . LeakyReLU((xl[i] + xr[j]) + xe[e]); xe is streamed once and nothing else
+    edge-sized is made.  xe=None is the op without them, bit for bit."""
     fn = "gatv2_attention_dropout_forward"
     return _gatv2_attention_forward(fn, row, indptr, eid, indices, xl, xr, att, negative_slope,
-                                    _drop_args(fn, p, seed, offset))
+                                    _drop_args(fn, p, seed, offset), xe)
 
 
 def gatv2_attention_dropout_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, o,
-                                     stats, dO, negative_slope=0.2, p=0.0, seed=0, offset=0):
+                                     stats, dO, negative_slope=0.2, p=0.0, seed=0, offset=0, xe=None, need_dxe=True):
     """-> [dxl, dxr, datt] of gatv2_attention_dropout_forward for the output gradient dO, with the same (p, seed,
-    offset): scores, weights and their keep decisions are recomputed per slot."""
+    offset): scores, weights and their keep decisions are recomputed per slot.
+    With the edge features xe of the forward: -> [dxl, dxr, datt, dxe]; dxe[e] = ds att t in xe's shape is the only
+    edge-sized tensor made (edge ids that no row-major slot names get 0); with need_dxe=False it is an empty (0,) tensor
+    and nothing edge-sized is written."""
     fn = "gatv2_attention_dropout_backward"
     return _gatv2_attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att,
-                                     o, stats, dO, negative_slope, _drop_args(fn, p, seed, offset))
+                                     o, stats, dO, negative_slope, _drop_args(fn, p, seed, offset), xe, need_dxe)
 
 
 def edge_dropout_mask(row, indptr, eid, indices, h, p, seed, offset=0, dtype=torch.float32):
@@ -726,8 +758,8 @@ _SCHEMAS = {
     "gatv2_scores_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor dy, float negative_slope=0.2) -> Tensor[]",
     "gatv2_attention_forward": "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor xl, Tensor xr, Tensor att, float negative_slope=0.2) -> Tensor[]",
     "gatv2_attention_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2) -> Tensor[]",
-    "gatv2_attention_dropout_forward": "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor xl, Tensor xr, Tensor att, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]",
-    "gatv2_attention_dropout_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]",
+    "gatv2_attention_dropout_forward": "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor xl, Tensor xr, Tensor att, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0, Tensor? xe=None) -> Tensor[]",
+    "gatv2_attention_dropout_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor xl, Tensor xr, Tensor att, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0, Tensor? xe=None, bool need_dxe=True) -> Tensor[]",
     "gat_edge_attention_forward": "(Tensor row, Tensor indptr, Tensor eid, Tensor indices, Tensor el, Tensor er, Tensor ee, Tensor V, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0) -> Tensor[]",
     "gat_edge_attention_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor ee, Tensor V, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0, bool need_dee=True) -> Tensor[]",
 }

@@ -604,6 +604,44 @@ GRAPHOP_API int graphop_gat_edge_attention_backward(int dtype, const int64_t* ro
                                     int64_t d, double negative_slope, double p, uint64_t seed, uint32_t offset,
                                     const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream);
 
+/* ---- fused GATv2 attention with edge features (ABI 8, additive; EXTRA ops) -----------------------------------------
+ * The fused GATv2 layer for GATv2Conv(edge_dim=...): per head k, for every slot of every chunk c with i = row[c],
+ * j = indices[slot], e = eid[slot],
+ *   z_ec = (xl[i, k, c] + xr[j, k, c]) + xe[e, k, c]   (added in that order),   s_e = sum_c att[k, c] LeakyReLU(z_ec)
+ *   m_i = max(-1e9, max s),  l_i = sum exp(s - m_i),  a_e = exp(s_e - m_i) / l_i,  o[i, k, :] = sum a_e m_ijk xr[j, k, :]
+ *   stats = (m_i, 1 / l_i) of the undropped scores, (n_l, h, 2); a row without slots gets o = 0 and stats (-1e9, 0)
+ * m_ijk is the dropout multiplier of graphop_edge_dropout_mask (a function of (i, j, k, seed, offset, p): parallel edges
+ * share a decision but each has its own xe row); p == 0 means no dropout and runs the kernels without the decision.
+ * gatv2_edge_attention_forward(row, indptr, eid, indices, xl, xr, xe, att, ...) -> [o, stats]
+ *   xl (n_l, h, d), xr (n_r, h, d), xe (n_edges, h, d) indexed by EDGE ID, att (h, d), o (n_l, h, d), stats (n_l, h, 2).
+ * gatv2_edge_attention_backward(<8 csr>, xl, xr, xe, att, o, stats, dO, ...) -> [dxl, dxr, dxe, datt], recomputed per slot:
+ *   D_i = <dO_i, o_i>, da_e = m_ijk <dO_i, xr_j>, ds_e = a_e (da_e - D_i), t_ec = (z_ec > 0 ? 1 : slope)
+ *   dxl[i, k, c] = att[k, c] sum_j ds_e t_ec,  datt[k, c] = sum_e ds_e LeakyReLU(z_ec),  dxe[e, k, c] = ds_e att[k, c] t_ec
+ *   (row-major CSR),  dxr[j, k, c] = sum_i (ds_e att[k, c] t_ec + a_e m_ijk dO[i, k, c])  (column-major CSR).
+ *   dxe (n_edges, h, d) is the only edge-sized tensor written, one plain store per slot and element; edge ids that no
+ *   row-major slot names get 0 (dxe is zero-filled unless plan_r proves that every id is written).  dxe may be NULL:
+ *   then nothing edge-sized is written.  dxl and datt may be NULL when n_row_chunks == 0, dxr when n_col_chunks == 0.
+ *   workspace: as for graphop_gatv2_attention_backward.
+ * 0 <= p < 1, seed < 2^63, n_l, n_r < 2^32; anything else is GRAPHOP_ERR_INVALID_ARGUMENT before the device is touched.
+ * The fast kernels run under the conditions of graphop_gatv2_attention_forward plus xe and dxe aligned to 16 bytes
+ * (csrc/kernels_gatv2_edge_attn.h); everything else takes the generic ones.  Any chunk layout works on both.  With a
+ * row-major plan whose eid is the identity the row-major passes do not read eid. */
+GRAPHOP_API int graphop_gatv2_edge_attention_forward(int dtype, const int64_t* row, const int64_t* indptr,
+                                     const int64_t* eid, const int64_t* indices, const void* xl, const void* xr,
+                                     const void* xe, const void* att, void* o, void* stats, int64_t n_chunks,
+                                     int64_t n_edges, int64_t n_l, int64_t n_r, int64_t h, int64_t d,
+                                     double negative_slope, double p, uint64_t seed, uint32_t offset,
+                                     const graphop_plan_t* plan, void* stream);
+GRAPHOP_API int graphop_gatv2_edge_attention_backward(int dtype, const int64_t* row, const int64_t* indptr_r,
+                                      const int64_t* eid_r, const int64_t* indices_r, const int64_t* col,
+                                      const int64_t* indptr_c, const int64_t* eid_c, const int64_t* indices_c,
+                                      const void* xl, const void* xr, const void* xe, const void* att, const void* o,
+                                      const void* stats, const void* dO, void* dxl, void* dxr, void* dxe, void* datt,
+                                      void* workspace, int64_t workspace_bytes, int64_t n_row_chunks,
+                                      int64_t n_col_chunks, int64_t n_edges, int64_t n_l, int64_t n_r, int64_t h,
+                                      int64_t d, double negative_slope, double p, uint64_t seed, uint32_t offset,
+                                      const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream);
+
 /* ---- fused attention step (EXTRA op, not one of the reference's eight) --------------------------
  * The composition the reference harness chains by hand -- MaskedMMCSR -> SparseSoftmax -> VectorSPMM
  * (wrapper.py:20-30, 8-18, 44-55) -- as one forward and one backward entry, so that the E-sized

@@ -4,7 +4,7 @@ E-sized tensor) on the Reddit shape against the composed step (functions.gatv2_a
 -> SparseSoftmax -> VectorSPMM over xr).
 
 At full size both steps are first compared: o, dxl, dxr with the error of every node scaled by the node's largest value in
-the composed result, datt by its own largest value.  Then, in one process and alternating, device events time the fused
+the composed result, datt (and with --edge dxe) by its own largest value.  Then, in one process and alternating, device events time the fused
 and the composed fwd+bwd (--warmup untimed rounds, median and min of --iters), and the peak memory each step adds to
 what is allocated before it (torch.cuda.max_memory_allocated above the baseline).  The only assertion is the memory
 condition: the fused step adds less than one (E, h) fp32 tensor, the composed one more than two.  Separate profiled
@@ -20,7 +20,16 @@ composed dropout step (functions.gatv2_attention_dropout_step, which builds and 
 alternating in one process; the comparison is fused dropout against composed dropout, the memory condition asks the
 composed step for more than three (E, h) tensors, and the per-kernel rounds are those of the dropout kernels and of the
 undropped fused kernels (the yardstick kernels of the other ops are left out).  --out then defaults to
-profiles/fused_gatv2_dropout_bench.json."""
+profiles/fused_gatv2_dropout_bench.json.
+
+--edge times the layer with edge features instead: three steps alternate in one process, the fused
+edge step (functions.fused_gatv2_edge_attention_step), the fused dropout step without xe (yardstick 1) and the composed
+edge step (functions.gatv2_edge_attention_step, yardstick 2; --no-composed leaves it out where its (E, h, d)
+temporaries do not fit).  --dropout P applies to all three (default 0).  Reported: median and min, the peak memory each
+step adds, and per kernel the time with the bytes of the model of 4.5i: every pass streams E h d 4 bytes of xe and 8 E
+of eid (none where the row-major plan says eid_identity), the row pass writes E h d 4 of dxe.  --edges N replaces the
+shape's edge count (the record names the graph).  Nothing is asserted on a time.  --out defaults to
+profiles/fused_gatv2_edge_bench.json."""
 import argparse
 import json
 import os
@@ -70,6 +79,120 @@ def _profile(fn, iters):
         _lib.profile_enable(False)
 
 
+def edge_records(args, g, dev):
+    """the records of --edge, one per (h, d)"""
+    E, n_src, n_dst, C_r, C_c = g.n_edges, g.n_src, g.n_dst, g.n_row_chunks, g.n_col_chunks
+    s, drop = args.slope, (args.dropout, args.dropout_seed, 7)
+    identity = bool(_lib.get_plan(g.row, g.ptr_r, g.eid_r, g.indices_r, n_dst).info.eid_identity)
+    records = []
+    for hd in args.hd.split(","):
+        h, d = (int(x) for x in hd.split("x"))
+        gen = torch.Generator(device=dev).manual_seed(args.seed + h * 100 + d)
+        ns = (lambda n: (n, d) if h == 1 else (n, h, d))
+        xl = torch.randn(ns(n_src), generator=gen, device=dev).requires_grad_(True)
+        xr = torch.randn(ns(n_dst), generator=gen, device=dev).requires_grad_(True)
+        xe = torch.randn(ns(E), generator=gen, device=dev).requires_grad_(True)
+        att = (torch.randn(ns(1)[1:], generator=gen, device=dev) / d ** 0.5).requires_grad_(True)
+        dO = torch.randn(ns(n_src), generator=gen, device=dev)
+        leaves = (xl, xr, xe, att)
+
+        def clear():
+            for x in leaves:
+                x.grad = None
+
+        def fused_edge():
+            clear()
+            return functions.fused_gatv2_edge_attention_step(g, xl, xr, xe, att, dO, s, *drop)
+
+        def fused_no_edge():
+            clear()
+            return functions.fused_gatv2_attention_dropout_step(g, xl, xr, att, dO, *drop, s)
+
+        def composed_edge():
+            clear()
+            return functions.gatv2_edge_attention_step(g, xl, xr, xe, att, dO, s, *drop)
+
+        fns = {"fused_edge_fwd_bwd": fused_edge, "fused_no_edge_fwd_bwd": fused_no_edge}
+        if not args.no_composed:
+            fns["composed_edge_fwd_bwd"] = composed_edge
+        err = None
+        if not args.no_composed:      # full-size comparison (also builds and caches the plans)
+            o_c = composed_edge()[2].detach()
+            want = [o_c] + [x.grad.clone() for x in leaves]
+            o_f = fused_edge().detach()
+            got = [o_f] + [x.grad.clone() for x in leaves]
+            torch.cuda.synchronize()
+            err = {n: _node_err(x, y) for n, x, y in zip(("o", "dxl", "dxr"), got, want)}
+            for n, k in (("dxe", 3), ("datt", 4)):      # by the tensor's largest value: an edge's own row may be ~0
+                err[n] = float((got[k] - want[k]).abs().max() / want[k].abs().max())
+            del o_c, o_f, want, got
+        peak = {}
+        for name, fn in fns.items():
+            clear()
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            torch.cuda.reset_peak_memory_stats()
+            base = torch.cuda.memory_allocated()
+            out = fn()
+            torch.cuda.synchronize()
+            peak[name] = torch.cuda.max_memory_allocated() - base
+            del out
+        clear()
+        t = _timed(fns, args.warmup, args.iters)
+        timings = {n: {"median_ms": round(statistics.median(v), 4), "min_ms": round(min(v), 4)} for n, v in t.items()}
+        prof = _profile(fused_edge, args.iters)
+        prof0 = _profile(fused_no_edge, args.iters)
+        nh_l = n_src * h * 4
+        row_l, row_r = n_src * h * d * 4, n_dst * h * d * 4
+        ids_r, ids_c = E * 8 + 16 * C_r, E * 8 + 16 * C_c
+        rows = E * h * d * 4                                    # one (E, h, d) stream: a row gather, xe or dxe
+        eid_r = 0 if identity else 8 * E
+        dropped = args.dropout > 0
+        tags = {"fwd": "gv2edge_drop_fwd" if dropped else "gv2edge_fwd",
+                "bwd_row": "gv2edge_drop_bwd_row" if dropped else "gv2edge_bwd_row",
+                "bwd_col": "gv2edge_drop_bwd_col" if dropped else "gv2edge_bwd_col"}
+        model = {   # pass: (algorithmic bytes without the gathers, row gathers per slot, edge-stream bytes)
+            "fwd": (ids_r + row_l + row_r + row_l + 2 * nh_l, 1, rows + eid_r),
+            "bwd_row": (ids_r + 2 * row_l + 4 * nh_l + row_r + row_l, 1, 2 * rows + eid_r),
+            "bwd_col": (ids_c + row_r + 2 * row_l + 4 * nh_l + row_r, 2, rows + 8 * E),
+        }
+        kernels = {}
+        for name, (nbytes, gathers, edge_bytes) in model.items():
+            q = prof[tags[name]]
+            q0 = prof0.get(tags[name].replace("gv2edge", "gv2attn"))
+            sec = q["mean_ms"] * 1e-3
+            kernels[tags[name]] = {
+                "kernel": q["kernel"], "calls": q["calls"], "mean_ms": round(q["mean_ms"], 4),
+                "min_ms": round(q["min_ms"], 4), "algorithmic_bytes": nbytes, "gathered_row_bytes": gathers * rows,
+                "edge_stream_bytes": edge_bytes,
+                "edge_stream_fraction_of_8TBs": round(edge_bytes / sec / PEAK, 3),
+                "all_bytes_fraction_of_8TBs": round((nbytes + gathers * rows + edge_bytes) / sec / PEAK, 3),
+                "no_edge_mean_ms": round(q0["mean_ms"], 4) if q0 else None}
+        for tag in ("gv2attn_pack", "gv2attn_datt_fin"):
+            kernels[tag] = {"kernel": prof[tag]["kernel"], "mean_ms": round(prof[tag]["mean_ms"], 4)}
+        f = timings["fused_edge_fwd_bwd"]["median_ms"]
+        rec = {
+            "tool": "tools/time_fused_gatv2.py --edge", "graph": "chung_lu_graph(%d, %d, alpha=0.5, seed=%d)" % (
+                n_src, E, args.seed), "shape": args.shape, "n_src": n_src, "n_dst": n_dst, "n_edges": E,
+            "row_chunks": C_r, "col_chunks": C_c, "chunk_size": args.chunk_size, "h": h, "d": d, "negative_slope": s,
+            "dropout": {"p": drop[0], "seed": drop[1], "offset": drop[2]}, "eid_identity": identity,
+            "warmup": args.warmup, "iters": args.iters, "node_scaled_difference_vs_composed": err, "timings": timings,
+            "fused_edge_over_fused_no_edge": round(f / timings["fused_no_edge_fwd_bwd"]["median_ms"], 3),
+            "fused_edge_over_composed_edge": (round(f / timings["composed_edge_fwd_bwd"]["median_ms"], 3)
+                                              if not args.no_composed else None),
+            "peak_added_bytes": peak, "one_edge_row_tensor_bytes": rows, "kernels": kernels,
+            "device": torch.cuda.get_device_name(dev)}
+        print(json.dumps(rec), flush=True)
+        records.append(rec)
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as fh:      # rewritten after every shape: a run that is cut short keeps what it has
+            json.dump(records, fh, indent=1)
+            fh.write("\n")
+        del xl, xr, xe, att, dO, leaves
+        torch.cuda.empty_cache()
+    _lib.check_errors()
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--shape", default="reddit", choices=sorted(graphs.SHAPES))
@@ -81,14 +204,21 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--dropout", type=float, default=0.0, metavar="P", help="time the attention-dropout steps at p = P")
     ap.add_argument("--dropout-seed", type=int, default=1234567890123)
+    ap.add_argument("--edge", action="store_true", help="time the layer with edge features (xe) instead")
+    ap.add_argument("--edges", type=int, default=None, metavar="N", help="with --edge: N edges instead of the shape's")
+    ap.add_argument("--no-composed", action="store_true", help="with --edge: leave the composed edge step out")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "fused_gatv2_dropout_bench.json" if args.dropout > 0
-                                else "fused_gatv2_bench.json")
+        args.out = os.path.join(ROOT, "profiles", "fused_gatv2_edge_bench.json" if args.edge else
+                                "fused_gatv2_dropout_bench.json" if args.dropout > 0 else "fused_gatv2_bench.json")
     dev = torch.device("cuda:0")
     N, E = graphs.SHAPES[args.shape]
+    if args.edge and args.edges:
+        E = args.edges
     g = graphs.chung_lu_graph(N, E, alpha=0.5, seed=args.seed, chunk_size=args.chunk_size, device=dev)
+    if args.edge:
+        return edge_records(args, g, dev)
     n_src, n_dst, C_r, C_c = g.n_src, g.n_dst, g.n_row_chunks, g.n_col_chunks
     s = args.slope
     records = []
