@@ -52,16 +52,14 @@ int gat_bwd_pass(int dtype, const i64* seg, const i64* indptr, const i64* eid, c
   } else {
     ProfScope prof(ROW ? "gat_bwd_row" : "gat_bwd_col", st, ROW ? "k_gat_bwd_row_generic" : "k_gat_bwd_col_generic");
     const unsigned nb = (unsigned)ceil_div(C, kGenericWavesPerBlock);
-    auto go = [&](auto zero) {
-      using T = decltype(zero);
+    GO_DISPATCH_FLOAT(dtype, T, {
       if constexpr (ROW)
         hipLaunchKernelGGL((k_gat_bwd_row_generic<T>), dim3(nb), dim3(kGenericBlock), 0, st, seg, indptr, eid, indices,
                            (const T*)el, (const T*)er, (const T*)dy, (T*)out, C, h, (T)slope);
       else
         hipLaunchKernelGGL((k_gat_bwd_col_generic<T>), dim3(nb), dim3(kGenericBlock), 0, st, seg, indptr, eid, indices,
                            (const T*)el, (const T*)er, (const T*)dy, (T*)out, C, h, (T)slope);
-    };
-    if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+    });
   }
   GO_LAUNCH_CHECK();
   return GRAPHOP_OK;

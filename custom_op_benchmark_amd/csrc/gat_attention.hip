@@ -96,12 +96,10 @@ int graphop_edge_dropout_mask(int dtype, const int64_t* row, const int64_t* indp
   GO_PTR(fn, row); GO_PTR(fn, indptr); GO_PTR(fn, eid); GO_PTR(fn, indices);
   ProfScope prof("edge_dropout_mask", st, "k_edge_dropout_mask");
   const unsigned nb = (unsigned)ceil_div(n_chunks, kGenericWavesPerBlock);
-  auto go = [&](auto zero) {
-    using T = decltype(zero);
+  GO_DISPATCH_FLOAT(dtype, T, {
     hipLaunchKernelGGL((k_edge_dropout_mask<T>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)row,
                        (const i64*)indptr, (const i64*)eid, (const i64*)indices, (T*)y, n_chunks, h, drop.as<T>());
-  };
-  if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+  });
   GO_LAUNCH_CHECK();
   return GRAPHOP_OK;
 }

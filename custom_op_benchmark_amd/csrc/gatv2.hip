@@ -51,13 +51,11 @@ int graphop_gatv2_scores_forward(int dtype, const int64_t* row, const int64_t* i
   } else {
     ProfScope prof("gatv2_fwd", st, "k_gatv2_fwd_generic");
     const unsigned nb = (unsigned)ceil_div(n_chunks, kGenericWavesPerBlock);
-    auto go = [&](auto zero) {
-      using T = decltype(zero);
+    GO_DISPATCH_FLOAT(dtype, T, {
       hipLaunchKernelGGL((k_gatv2_fwd_generic<T>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)row,
                          (const i64*)indptr, (const i64*)eid, (const i64*)indices, (const T*)xl, (const T*)xr,
                          (const T*)att, (T*)y, n_chunks, h, d, gatv2_dp(d), (T)negative_slope);
-    };
-    if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+    });
   }
   GO_LAUNCH_CHECK();
   return GRAPHOP_OK;
@@ -108,13 +106,11 @@ int graphop_gatv2_scores_backward(int dtype, const int64_t* row, const int64_t* 
     } else {
       ProfScope prof("gatv2_bwd_row", st, "k_gatv2_bwd_row_generic");
       const unsigned nb = (unsigned)ceil_div(C, kGenericWavesPerBlock);
-      auto go = [&](auto zero) {
-        using T = decltype(zero);
+      GO_DISPATCH_FLOAT(dtype, T, {
         hipLaunchKernelGGL((k_gatv2_bwd_row_generic<T>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)row,
                            (const i64*)indptr_r, (const i64*)eid_r, (const i64*)indices_r, (const T*)xl, (const T*)xr,
                            (const T*)att, (const T*)dy, (T*)dxl, (T*)datt, C, h, d, (T)negative_slope);
-      };
-      if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+      });
     }
     GO_LAUNCH_CHECK();
   }
@@ -135,13 +131,11 @@ int graphop_gatv2_scores_backward(int dtype, const int64_t* row, const int64_t* 
     } else {
       ProfScope prof("gatv2_bwd_col", st, "k_gatv2_bwd_col_generic");
       const unsigned nb = (unsigned)ceil_div(C, kGenericWavesPerBlock);
-      auto go = [&](auto zero) {
-        using T = decltype(zero);
+      GO_DISPATCH_FLOAT(dtype, T, {
         hipLaunchKernelGGL((k_gatv2_bwd_col_generic<T>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)col,
                            (const i64*)indptr_c, (const i64*)eid_c, (const i64*)indices_c, (const T*)xl, (const T*)xr,
                            (const T*)att, (const T*)dy, (T*)dxr, C, h, d, (T)negative_slope);
-      };
-      if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+      });
     }
     GO_LAUNCH_CHECK();
   }

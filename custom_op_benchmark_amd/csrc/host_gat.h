@@ -1,10 +1,13 @@
 // Host-side helpers of the GAT family of entry points (gat.hip, gatv2.hip, gat_attention.hip, gat_edge_attention.hip,
-// gatv2_attention.hip, gatv2_edge_attention.hip, host_gat_attn_ops.h and host_gatv2_attn_ops.h): argument and plan checks, the conditions of the fp32 fast kernels, the
-// (h, d) dispatch, the profile labels, the launch geometry of the gather passes and the opening of the two GATv2
-// backwards.  Each exists once, here.  Not part of the C ABI.
+// gatv2_attention.hip, gatv2_edge_attention.hip, host_gat_attn_ops.h and host_gatv2_attn_ops.h): argument and plan
+// checks, the conditions of the fp32 fast kernels, the (h, d), bool and fp32 / fp64 dispatch, the one launch statement
+// of a kernel with and without edge term (go_launch, arg_if, GO_EDGE_KERNEL), the profile labels, the launch geometry
+// of the gather passes and the opening of the two GATv2 backwards.  Each exists once, here.  Not part of the C ABI.
 #pragma once
 #include <cstdio>
 #include <initializer_list>
+#include <tuple>
+#include <type_traits>
 
 #include "common.h"
 #include "host.h"
@@ -94,6 +97,34 @@ inline bool gat_hd_fast_ok(int dtype, i64 h, i64 d, i64 E, i64 n_l, i64 n_r, std
 #define GO_DISPATCH_BOOL(b, NAME, ...)                   \
   if (b) { constexpr bool NAME = true; __VA_ARGS__; }    \
   else { constexpr bool NAME = false; __VA_ARGS__; }
+
+// the run-time dtype (GRAPHOP_F32 or GRAPHOP_F64: gat_check) as the type NAME of the statement
+#define GO_DISPATCH_FLOAT(dtype, NAME, ...)                         \
+  if ((dtype) == GRAPHOP_F32) { using NAME = float; __VA_ARGS__; } \
+  else { using NAME = double; __VA_ARGS__; }
+
+// One launch statement for a kernel and its edge form, whose parameter list is the plain one with the edge arguments
+// spliced in (eid, ee / xe, dee / dxe): the call lists every argument in the edge kernel's order and wraps those that
+// only the edge kernel takes in arg_if<EDGE>(...).  arg_if<false>(x) adds nothing to the list (x is still evaluated).
+template <bool ON, class T> struct ArgIf { T v; };
+template <bool ON, class T> ArgIf<ON, T> arg_if(T v) { return {v}; }
+template <class T> std::tuple<T> launch_arg(T v) { return {v}; }
+template <class T> std::tuple<T> launch_arg(ArgIf<true, T> a) { return {a.v}; }
+template <class T> std::tuple<> launch_arg(ArgIf<false, T>) { return {}; }
+template <class K, class... A>
+void go_launch(K kernel, dim3 grid, dim3 block, hipStream_t st, A... args) {
+  std::apply([&](auto... a) { hipLaunchKernelGGL(kernel, grid, block, 0, st, a...); },
+             std::tuple_cat(launch_arg(args)...));
+}
+static_assert(std::is_same_v<decltype(std::tuple_cat(launch_arg(arg_if<false>(1)), launch_arg(2.f))),
+                             std::tuple<float>>, "arg_if<false> drops its argument");
+static_assert(std::is_same_v<decltype(std::tuple_cat(launch_arg(arg_if<true>(1)), launch_arg(2.f))),
+                             std::tuple<int, float>>, "arg_if<true> keeps its argument, in place");
+
+// &plain<...> or, with the edge term, &edge<...>: only the chosen one is instantiated, so a translation unit compiles
+// only its own EDGE's kernels.  The template arguments must be constants usable without capture (H, D, OWNED, DROP, T).
+#define GO_EDGE_KERNEL(EDGE, plain, edge, ...) \
+  ([] { if constexpr (EDGE) return &edge<__VA_ARGS__>; else return &plain<__VA_ARGS__>; }())
 
 // ProfScope tag [drop] and kernel label [drop][fast] of a gather pass ("fwd", "bwd_row", "bwd_col") of the fused op
 // `op`.  The drop names are those of the path taken: the DROP = true instantiations, the k_gv2drop_* kernels.

@@ -4,7 +4,10 @@
 // choice between the fp32 fast kernels and the generic ones, the launch geometry and the profile tags are the same for
 // both; with the edge term ee / dee must also be aligned for the fast kernels, a plan with eid_identity passes them a
 // NULL eid, and dee is zero-filled unless the plan proves every edge id is written.  A translation unit instantiates
-// only its own EDGE, so only its own kernels; ee and dee are ignored without the edge term.  Not part of the C ABI.
+// only its own EDGE, so only its own kernels; ee and dee are ignored without the edge term.  Every launch is written
+// once, with the edge kernel's argument list: GO_EDGE_KERNEL names the kernel of this EDGE, and the arguments that only
+// the edge kernels take (eid, ee, dee) stand in arg_if<EDGE>(...), which drops them without the edge term (host_gat.h).
+// Not part of the C ABI.
 #pragma once
 #include <type_traits>
 
@@ -22,12 +25,10 @@ template <bool EDGE>
 int gat_attn_stats(int dtype, const i64* row, const i64* indptr, const i64* eid, const i64* indices, const void* el,
                    const void* er, const void* ee, void* stats, i64 C, i64 n_l, i64 h, double slope,
                    const graphop_plan* pm, bool fast, hipStream_t st) {
-  auto init = [&](auto zero) {
-    using T = decltype(zero);
+  GO_DISPATCH_FLOAT(dtype, T, {
     hipLaunchKernelGGL((k_gat_attn_stats_init_generic<T>), dim3(grid_of(n_l * h)), dim3(256), 0, st, (T*)stats,
                        n_l * h);
-  };
-  if (dtype == GRAPHOP_F32) init(0.f); else init(0.0);
+  });
   GO_LAUNCH_CHECK();
   if (C == 0) return GRAPHOP_OK;
   const char* tag = EDGE ? "gat_edge_attn_stats" : "gat_attn_stats";
@@ -42,37 +43,28 @@ int gat_attn_stats(int dtype, const i64* row, const i64* indptr, const i64* eid,
       constexpr int G = WIDE ? 64 : 16;
       const unsigned nbs = (unsigned)ceil_div(S, kFastBlock / G);
       const dim3 grid(nbs + (unsigned)n_long);
-      if constexpr (EDGE)
-        hipLaunchKernelGGL((k_gat_edge_attn_stats_f32<H, G>), grid, dim3(kFastBlock), 0, st, row, indptr,
-                           eid_arg(pm, eid), indices, (const i64*)pm->seg_chunk, (const float*)el, (const float*)er,
-                           (const float*)ee, (float2*)stats, S, nbs, long_len, (const int*)pm->long_segs, (float)slope);
-      else
-        hipLaunchKernelGGL((k_gat_attn_stats_f32<H, G>), grid, dim3(kFastBlock), 0, st, row, indptr, indices,
-                           (const i64*)pm->seg_chunk, (const float*)el, (const float*)er, (float2*)stats, S, nbs,
-                           long_len, (const int*)pm->long_segs, (float)slope);
+      go_launch(GO_EDGE_KERNEL(EDGE, k_gat_attn_stats_f32, k_gat_edge_attn_stats_f32, H, G), grid, dim3(kFastBlock), st,
+                row, indptr, arg_if<EDGE>(eid_arg(pm, eid)), indices, (const i64*)pm->seg_chunk, (const float*)el,
+                (const float*)er, arg_if<EDGE>((const float*)ee), (float2*)stats, S, nbs, long_len,
+                (const int*)pm->long_segs, (float)slope);
     }));
     GO_LAUNCH_CHECK();
     return GRAPHOP_OK;
   }
   ProfScope prof(tag, st, EDGE ? "k_gat_edge_attn_stats_generic" : "k_gat_attn_stats_generic");
   const dim3 grid((unsigned)ceil_div(C, kGenericWavesPerBlock));
-  auto go = [&](auto zero) {
-    using T = decltype(zero);
+  GO_DISPATCH_FLOAT(dtype, T, {
     auto pass = [&](auto sum) {
       constexpr bool SUM = decltype(sum)::value;
-      if constexpr (EDGE)
-        hipLaunchKernelGGL((k_gat_edge_attn_stats_generic<T, SUM>), grid, dim3(kGenericBlock), 0, st, row, indptr, eid,
-                           indices, (const T*)el, (const T*)er, (const T*)ee, (T*)stats, C, h, (T)slope);
-      else
-        hipLaunchKernelGGL((k_gat_attn_stats_generic<T, SUM>), grid, dim3(kGenericBlock), 0, st, row, indptr, indices,
-                           (const T*)el, (const T*)er, (T*)stats, C, h, (T)slope);
+      go_launch(GO_EDGE_KERNEL(EDGE, k_gat_attn_stats_generic, k_gat_edge_attn_stats_generic, T, SUM), grid,
+                dim3(kGenericBlock), st, row, indptr, arg_if<EDGE>(eid), indices, (const T*)el, (const T*)er,
+                arg_if<EDGE>((const T*)ee), (T*)stats, C, h, (T)slope);
     };
     pass(std::false_type{});   // the maxima
     pass(std::true_type{});    // the sums of exp(s - m)
     hipLaunchKernelGGL((k_gat_attn_stats_fin_generic<T>), dim3(grid_of(n_l * h)), dim3(256), 0, st, (T*)stats,
                        n_l * h);
-  };
-  if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+  });
   GO_LAUNCH_CHECK();
   return GRAPHOP_OK;
 }
@@ -111,35 +103,20 @@ int gat_attn_forward(const char* fn, int dtype, const int64_t* row, const int64_
     const bool owned = pm->info.rows_sorted != 0;
     const dim3 grid((unsigned)gat_grid(n_chunks, cpg));
     GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
-      if constexpr (EDGE)
-        hipLaunchKernelGGL((k_gat_edge_attn_fwd_f32<H, D, OWNED, DROP>), grid, dim3(kFastBlock), 0, st,
-                           (const i64*)row, (const i64*)indptr, eid_arg(pm, eid), (const i64*)indices,
-                           (const float*)el, (const float*)er, (const float*)ee, (const float2*)stats,
-                           (const float*)V, (float*)o, n_chunks, cpg, (float)negative_slope,
-                           drop_arg<DROP, float>(drop));
-      else
-        hipLaunchKernelGGL((k_gat_attn_fwd_f32<H, D, OWNED, DROP>), grid, dim3(kFastBlock), 0, st, (const i64*)row,
-                           (const i64*)indptr, (const i64*)indices, (const float*)el, (const float*)er,
-                           (const float2*)stats, (const float*)V, (float*)o, n_chunks, cpg, (float)negative_slope,
-                           drop_arg<DROP, float>(drop));
+      go_launch(GO_EDGE_KERNEL(EDGE, k_gat_attn_fwd_f32, k_gat_edge_attn_fwd_f32, H, D, OWNED, DROP), grid,
+                dim3(kFastBlock), st, (const i64*)row, (const i64*)indptr, arg_if<EDGE>(eid_arg(pm, eid)),
+                (const i64*)indices, (const float*)el, (const float*)er, arg_if<EDGE>((const float*)ee),
+                (const float2*)stats, (const float*)V, (float*)o, n_chunks, cpg, (float)negative_slope,
+                drop_arg<DROP, float>(drop));
     })));
   } else {
     const dim3 grid((unsigned)ceil_div(n_chunks, kGenericWavesPerBlock));
-    auto go = [&](auto zero) {
-      using T = decltype(zero);
-      GO_DISPATCH_BOOL(dropped, DROP, {
-        if constexpr (EDGE)
-          hipLaunchKernelGGL((k_gat_edge_attn_fwd_generic<T, DROP>), grid, dim3(kGenericBlock), 0, st, (const i64*)row,
-                             (const i64*)indptr, (const i64*)eid, (const i64*)indices, (const T*)el, (const T*)er,
-                             (const T*)ee, (const T*)stats, (const T*)V, (T*)o, n_chunks, h, d, (T)negative_slope,
-                             drop_arg<DROP, T>(drop));
-        else
-          hipLaunchKernelGGL((k_gat_attn_fwd_generic<T, DROP>), grid, dim3(kGenericBlock), 0, st, (const i64*)row,
-                             (const i64*)indptr, (const i64*)indices, (const T*)el, (const T*)er, (const T*)stats,
-                             (const T*)V, (T*)o, n_chunks, h, d, (T)negative_slope, drop_arg<DROP, T>(drop));
-      });
-    };
-    if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+    GO_DISPATCH_FLOAT(dtype, T, GO_DISPATCH_BOOL(dropped, DROP, {
+      go_launch(GO_EDGE_KERNEL(EDGE, k_gat_attn_fwd_generic, k_gat_edge_attn_fwd_generic, T, DROP), grid,
+                dim3(kGenericBlock), st, (const i64*)row, (const i64*)indptr, arg_if<EDGE>((const i64*)eid),
+                (const i64*)indices, (const T*)el, (const T*)er, arg_if<EDGE>((const T*)ee), (const T*)stats,
+                (const T*)V, (T*)o, n_chunks, h, d, (T)negative_slope, drop_arg<DROP, T>(drop));
+    }));
   }
   GO_LAUNCH_CHECK();
   return GRAPHOP_OK;
@@ -202,12 +179,10 @@ int gat_attn_backward(const char* fn, int dtype, const int64_t* row, const int64
                            (const float*)o, (float4*)workspace, n_l);
       });
     } else {
-      auto go = [&](auto zero) {
-        using T = decltype(zero);
+      GO_DISPATCH_FLOAT(dtype, T, {
         hipLaunchKernelGGL((k_gat_attn_pack_generic<T>), dim3(grid_of(n_l * h)), dim3(256), 0, st, (const T*)el,
                            (const T*)stats, (const T*)dO, (const T*)o, (T*)workspace, n_l * h, d);
-      };
-      if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+      });
     }
     GO_LAUNCH_CHECK();
   }
@@ -222,35 +197,20 @@ int gat_attn_backward(const char* fn, int dtype, const int64_t* row, const int64
       const bool owned = pr->info.rows_sorted != 0;
       const dim3 grid((unsigned)gat_grid(C, cpg));
       GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
-        if constexpr (EDGE)
-          hipLaunchKernelGGL((k_gat_edge_attn_bwd_row_f32<H, D, OWNED, DROP>), grid, dim3(kFastBlock), 0, st,
-                             (const i64*)row, (const i64*)indptr_r, eid_arg(pr, eid_r), (const i64*)indices_r,
-                             (const float*)er, (const float*)ee, (const float*)V, (const float4*)workspace,
-                             (const float*)dO, (float*)del, (float*)dee, C, cpg, slope, drop_arg<DROP, float>(drop));
-        else
-          hipLaunchKernelGGL((k_gat_attn_bwd_row_f32<H, D, OWNED, DROP>), grid, dim3(kFastBlock), 0, st,
-                             (const i64*)row, (const i64*)indptr_r, (const i64*)indices_r, (const float*)er,
-                             (const float*)V, (const float4*)workspace, (const float*)dO, (float*)del, C, cpg, slope,
-                             drop_arg<DROP, float>(drop));
+        go_launch(GO_EDGE_KERNEL(EDGE, k_gat_attn_bwd_row_f32, k_gat_edge_attn_bwd_row_f32, H, D, OWNED, DROP), grid,
+                  dim3(kFastBlock), st, (const i64*)row, (const i64*)indptr_r, arg_if<EDGE>(eid_arg(pr, eid_r)),
+                  (const i64*)indices_r, (const float*)er, arg_if<EDGE>((const float*)ee), (const float*)V,
+                  (const float4*)workspace, (const float*)dO, (float*)del, arg_if<EDGE>((float*)dee), C, cpg, slope,
+                  drop_arg<DROP, float>(drop));
       })));
     } else {
       const dim3 grid((unsigned)ceil_div(C, kGenericWavesPerBlock));
-      auto go = [&](auto zero) {
-        using T = decltype(zero);
-        GO_DISPATCH_BOOL(dropped, DROP, {
-          if constexpr (EDGE)
-            hipLaunchKernelGGL((k_gat_edge_attn_bwd_row_generic<T, DROP>), grid, dim3(kGenericBlock), 0, st,
-                               (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r, (const i64*)indices_r,
-                               (const T*)er, (const T*)ee, (const T*)V, (const T*)workspace, (const T*)dO, (T*)del,
-                               (T*)dee, C, h, d, (T)negative_slope, drop_arg<DROP, T>(drop));
-          else
-            hipLaunchKernelGGL((k_gat_attn_bwd_row_generic<T, DROP>), grid, dim3(kGenericBlock), 0, st,
-                               (const i64*)row, (const i64*)indptr_r, (const i64*)indices_r, (const T*)er,
-                               (const T*)V, (const T*)workspace, (const T*)dO, (T*)del, C, h, d, (T)negative_slope,
-                               drop_arg<DROP, T>(drop));
-        });
-      };
-      if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+      GO_DISPATCH_FLOAT(dtype, T, GO_DISPATCH_BOOL(dropped, DROP, {
+        go_launch(GO_EDGE_KERNEL(EDGE, k_gat_attn_bwd_row_generic, k_gat_edge_attn_bwd_row_generic, T, DROP), grid,
+                  dim3(kGenericBlock), st, (const i64*)row, (const i64*)indptr_r, arg_if<EDGE>((const i64*)eid_r),
+                  (const i64*)indices_r, (const T*)er, arg_if<EDGE>((const T*)ee), (const T*)V, (const T*)workspace,
+                  (const T*)dO, (T*)del, arg_if<EDGE>((T*)dee), C, h, d, (T)negative_slope, drop_arg<DROP, T>(drop));
+      }));
     }
     GO_LAUNCH_CHECK();
   }
@@ -265,35 +225,20 @@ int gat_attn_backward(const char* fn, int dtype, const int64_t* row, const int64
       const bool owned = pc->info.rows_sorted != 0;
       const dim3 grid((unsigned)gat_grid(C, cpg));
       GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
-        if constexpr (EDGE)
-          hipLaunchKernelGGL((k_gat_edge_attn_bwd_col_f32<H, D, OWNED, DROP>), grid, dim3(kFastBlock), 0, st,
-                             (const i64*)col, (const i64*)indptr_c, eid_arg(pc, eid_c), (const i64*)indices_c,
-                             (const float*)er, (const float*)ee, (const float*)V, (const float4*)workspace,
-                             (const float*)dO, (float*)der, (float*)dV, C, cpg, slope, drop_arg<DROP, float>(drop));
-        else
-          hipLaunchKernelGGL((k_gat_attn_bwd_col_f32<H, D, OWNED, DROP>), grid, dim3(kFastBlock), 0, st,
-                             (const i64*)col, (const i64*)indptr_c, (const i64*)indices_c, (const float*)er,
-                             (const float*)V, (const float4*)workspace, (const float*)dO, (float*)der, (float*)dV, C,
-                             cpg, slope, drop_arg<DROP, float>(drop));
+        go_launch(GO_EDGE_KERNEL(EDGE, k_gat_attn_bwd_col_f32, k_gat_edge_attn_bwd_col_f32, H, D, OWNED, DROP), grid,
+                  dim3(kFastBlock), st, (const i64*)col, (const i64*)indptr_c, arg_if<EDGE>(eid_arg(pc, eid_c)),
+                  (const i64*)indices_c, (const float*)er, arg_if<EDGE>((const float*)ee), (const float*)V,
+                  (const float4*)workspace, (const float*)dO, (float*)der, (float*)dV, C, cpg, slope,
+                  drop_arg<DROP, float>(drop));
       })));
     } else {
       const dim3 grid((unsigned)ceil_div(C, kGenericWavesPerBlock));
-      auto go = [&](auto zero) {
-        using T = decltype(zero);
-        GO_DISPATCH_BOOL(dropped, DROP, {
-          if constexpr (EDGE)
-            hipLaunchKernelGGL((k_gat_edge_attn_bwd_col_generic<T, DROP>), grid, dim3(kGenericBlock), 0, st,
-                               (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c, (const i64*)indices_c,
-                               (const T*)er, (const T*)ee, (const T*)V, (const T*)workspace, (const T*)dO, (T*)der,
-                               (T*)dV, C, h, d, (T)negative_slope, drop_arg<DROP, T>(drop));
-          else
-            hipLaunchKernelGGL((k_gat_attn_bwd_col_generic<T, DROP>), grid, dim3(kGenericBlock), 0, st,
-                               (const i64*)col, (const i64*)indptr_c, (const i64*)indices_c, (const T*)er,
-                               (const T*)V, (const T*)workspace, (const T*)dO, (T*)der, (T*)dV, C, h, d,
-                               (T)negative_slope, drop_arg<DROP, T>(drop));
-        });
-      };
-      if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+      GO_DISPATCH_FLOAT(dtype, T, GO_DISPATCH_BOOL(dropped, DROP, {
+        go_launch(GO_EDGE_KERNEL(EDGE, k_gat_attn_bwd_col_generic, k_gat_edge_attn_bwd_col_generic, T, DROP), grid,
+                  dim3(kGenericBlock), st, (const i64*)col, (const i64*)indptr_c, arg_if<EDGE>((const i64*)eid_c),
+                  (const i64*)indices_c, (const T*)er, arg_if<EDGE>((const T*)ee), (const T*)V, (const T*)workspace,
+                  (const T*)dO, (T*)der, (T*)dV, C, h, d, (T)negative_slope, drop_arg<DROP, T>(drop));
+      }));
     }
     GO_LAUNCH_CHECK();
   }

@@ -5,8 +5,10 @@
 // and the workspace are the same for both.  With the edge row, xe / dxe must also be 16-byte aligned for the fast
 // kernels, xe must not be NULL, a row-major plan with eid_identity passes the kernels a NULL eid, dxe is zero-filled
 // unless the plan proves every edge id is written, and the profile labels start with gv2edge.  A translation unit
-// instantiates only its own EDGE, so only its own kernels; xe and dxe are ignored without the edge row.  Not part of
-// the C ABI.
+// instantiates only its own EDGE, so only its own kernels; xe and dxe are ignored without the edge row.  Every launch
+// is written once, with the edge kernel's argument list: the gv2attn_*_kernel selectors below (fast) and GO_EDGE_KERNEL
+// (generic) name the kernel of this EDGE, and the arguments that only the edge kernels take (eid, xe, dxe) stand in
+// arg_if<EDGE>(...), which drops them without the edge row (host_gat.h).  Not part of the C ABI.
 #pragma once
 #include "host_dropout.h"
 #include "host_gat.h"
@@ -69,12 +71,10 @@ int gv2attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t
   GO_PTR(fn, o); GO_PTR(fn, stats);
   // rows without chunks keep o = 0 and stats = (-1e9, 0)
   GO_HIP(zero_async(o, es * (size_t)(n_l * h * d), st));
-  auto init = [&](auto zero) {
-    using T = decltype(zero);
+  GO_DISPATCH_FLOAT(dtype, T, {
     hipLaunchKernelGGL((k_gv2attn_stats_init_generic<T>), dim3(grid_of(n_l * h)), dim3(256), 0, st, (T*)stats,
                        n_l * h);
-  };
-  if (dtype == GRAPHOP_F32) init(0.f); else init(0.0);
+  });
   GO_LAUNCH_CHECK();
   if (n_chunks == 0 || n_edges == 0 || n_r == 0) return GRAPHOP_OK;
   GO_PTR(fn, row); GO_PTR(fn, indptr); GO_PTR(fn, eid); GO_PTR(fn, indices);
@@ -94,53 +94,36 @@ int gv2attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t
     const unsigned nbs = (unsigned)ceil_div(S, (i64)(kFastBlock / kGatGroup));
     const dim3 grid(nbs + (unsigned)n_long);
     GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(dropped, DROP, {
-      if constexpr (EDGE)
-        hipLaunchKernelGGL((gv2attn_fwd_kernel<H, D, DROP, EDGE>()), grid, dim3(kFastBlock), 0, st, (const i64*)row,
-                           (const i64*)indptr, eid_arg(pm, eid), (const i64*)indices, (const i64*)pm->seg_chunk,
-                           (const float*)xl, (const float*)xr, (const float*)xe, (const float*)att, (float*)o,
-                           (float2*)stats, S, nbs, long_len, (const int*)pm->long_segs, (float)negative_slope,
-                           drop_arg<DROP, float>(drop));
-      else
-        hipLaunchKernelGGL((gv2attn_fwd_kernel<H, D, DROP, EDGE>()), grid, dim3(kFastBlock), 0, st, (const i64*)row,
-                           (const i64*)indptr, (const i64*)indices, (const i64*)pm->seg_chunk, (const float*)xl,
-                           (const float*)xr, (const float*)att, (float*)o, (float2*)stats, S, nbs, long_len,
-                           (const int*)pm->long_segs, (float)negative_slope, drop_arg<DROP, float>(drop));
+      go_launch(gv2attn_fwd_kernel<H, D, DROP, EDGE>(), grid, dim3(kFastBlock), st, (const i64*)row,
+                (const i64*)indptr, arg_if<EDGE>(eid_arg(pm, eid)), (const i64*)indices, (const i64*)pm->seg_chunk,
+                (const float*)xl, (const float*)xr, arg_if<EDGE>((const float*)xe), (const float*)att, (float*)o,
+                (float2*)stats, S, nbs, long_len, (const int*)pm->long_segs, (float)negative_slope,
+                drop_arg<DROP, float>(drop));
     }));
     GO_LAUNCH_CHECK();
     return GRAPHOP_OK;
   }
   ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][0]);
   const dim3 grid((unsigned)ceil_div(n_chunks, kGenericWavesPerBlock));
-  auto go = [&](auto zero) {
-    using T = decltype(zero);
+  GO_DISPATCH_FLOAT(dtype, T, {
     auto pass = [&](auto sum) {
       constexpr bool SUM = decltype(sum)::value;
-      if constexpr (EDGE)
-        hipLaunchKernelGGL((k_gv2edge_stats_generic<T, SUM>), grid, dim3(kGenericBlock), 0, st, (const i64*)row,
-                           (const i64*)indptr, (const i64*)eid, (const i64*)indices, (const T*)xl, (const T*)xr,
-                           (const T*)xe, (const T*)att, (T*)stats, n_chunks, h, d, (T)negative_slope);
-      else
-        hipLaunchKernelGGL((k_gv2attn_stats_generic<T, SUM>), grid, dim3(kGenericBlock), 0, st, (const i64*)row,
-                           (const i64*)indptr, (const i64*)indices, (const T*)xl, (const T*)xr, (const T*)att,
-                           (T*)stats, n_chunks, h, d, (T)negative_slope);
+      go_launch(GO_EDGE_KERNEL(EDGE, k_gv2attn_stats_generic, k_gv2edge_stats_generic, T, SUM), grid,
+                dim3(kGenericBlock), st, (const i64*)row, (const i64*)indptr, arg_if<EDGE>((const i64*)eid),
+                (const i64*)indices, (const T*)xl, (const T*)xr, arg_if<EDGE>((const T*)xe), (const T*)att, (T*)stats,
+                n_chunks, h, d, (T)negative_slope);
     };
     pass(std::false_type{});   // the maxima
     pass(std::true_type{});    // the sums of exp(s - m)
     hipLaunchKernelGGL((k_gv2attn_stats_fin_generic<T>), dim3(grid_of(n_l * h)), dim3(256), 0, st, (T*)stats,
                        n_l * h);
     GO_DISPATCH_BOOL(dropped, DROP, {
-      if constexpr (EDGE)
-        hipLaunchKernelGGL((k_gv2edge_fwd_generic<T, DROP>), grid, dim3(kGenericBlock), 0, st, (const i64*)row,
-                           (const i64*)indptr, (const i64*)eid, (const i64*)indices, (const T*)xl, (const T*)xr,
-                           (const T*)xe, (const T*)att, (const T*)stats, (T*)o, n_chunks, h, d, (T)negative_slope,
-                           drop_arg<DROP, T>(drop));
-      else
-        hipLaunchKernelGGL((k_gv2attn_fwd_generic<T, DROP>), grid, dim3(kGenericBlock), 0, st, (const i64*)row,
-                           (const i64*)indptr, (const i64*)indices, (const T*)xl, (const T*)xr, (const T*)att,
-                           (const T*)stats, (T*)o, n_chunks, h, d, (T)negative_slope, drop_arg<DROP, T>(drop));
+      go_launch(GO_EDGE_KERNEL(EDGE, k_gv2attn_fwd_generic, k_gv2edge_fwd_generic, T, DROP), grid, dim3(kGenericBlock),
+                st, (const i64*)row, (const i64*)indptr, arg_if<EDGE>((const i64*)eid), (const i64*)indices,
+                (const T*)xl, (const T*)xr, arg_if<EDGE>((const T*)xe), (const T*)att, (const T*)stats, (T*)o, n_chunks,
+                h, d, (T)negative_slope, drop_arg<DROP, T>(drop));
     });
-  };
-  if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+  });
   GO_LAUNCH_CHECK();
   return GRAPHOP_OK;
 }
@@ -191,12 +174,10 @@ int gv2attn_backward(const char* fn, int dtype, const int64_t* row, const int64_
                            (float4*)workspace, n_l);
       });
     } else {
-      auto go = [&](auto zero) {
-        using T = decltype(zero);
+      GO_DISPATCH_FLOAT(dtype, T, {
         hipLaunchKernelGGL((k_gv2attn_pack_generic<T>), dim3(grid_of(n_l * h)), dim3(256), 0, st,
                            (const T*)stats, (const T*)dO, (const T*)o, (T*)workspace, n_l * h, d);
-      };
-      if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+      });
     }
     GO_LAUNCH_CHECK();
   }
@@ -212,17 +193,11 @@ int gv2attn_backward(const char* fn, int dtype, const int64_t* row, const int64_
         const bool owned = pr->info.rows_sorted != 0;
         const dim3 grid((unsigned)geo.n_blocks);
         GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
-          if constexpr (EDGE)
-            hipLaunchKernelGGL((gv2attn_bwd_row_kernel<H, D, OWNED, DROP, EDGE>()), grid, dim3(kFastBlock), 0, st,
-                               (const i64*)row, (const i64*)indptr_r, eid_arg(pr, eid_r), (const i64*)indices_r,
-                               (const float*)xl, (const float*)xr, (const float*)xe, (const float*)att,
-                               (const float4*)workspace, (const float*)dO, (float*)dxl, (float*)dxe, (float4*)part, C,
-                               geo.cpg, slope, drop_arg<DROP, float>(drop));
-          else
-            hipLaunchKernelGGL((gv2attn_bwd_row_kernel<H, D, OWNED, DROP, EDGE>()), grid, dim3(kFastBlock), 0, st,
-                               (const i64*)row, (const i64*)indptr_r, (const i64*)indices_r, (const float*)xl,
-                               (const float*)xr, (const float*)att, (const float4*)workspace, (const float*)dO,
-                               (float*)dxl, (float4*)part, C, geo.cpg, slope, drop_arg<DROP, float>(drop));
+          go_launch(gv2attn_bwd_row_kernel<H, D, OWNED, DROP, EDGE>(), grid, dim3(kFastBlock), st, (const i64*)row,
+                    (const i64*)indptr_r, arg_if<EDGE>(eid_arg(pr, eid_r)), (const i64*)indices_r, (const float*)xl,
+                    (const float*)xr, arg_if<EDGE>((const float*)xe), (const float*)att, (const float4*)workspace,
+                    (const float*)dO, (float*)dxl, arg_if<EDGE>((float*)dxe), (float4*)part, C, geo.cpg, slope,
+                    drop_arg<DROP, float>(drop));
         })));
         GO_LAUNCH_CHECK();
       }
@@ -231,23 +206,13 @@ int gv2attn_backward(const char* fn, int dtype, const int64_t* row, const int64_
     } else {
       ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][0]);
       const dim3 grid((unsigned)ceil_div(C, kGenericWavesPerBlock));
-      auto go = [&](auto zero) {
-        using T = decltype(zero);
-        GO_DISPATCH_BOOL(dropped, DROP, {
-          if constexpr (EDGE)
-            hipLaunchKernelGGL((k_gv2edge_bwd_row_generic<T, DROP>), grid, dim3(kGenericBlock), 0, st,
-                               (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r, (const i64*)indices_r,
-                               (const T*)xl, (const T*)xr, (const T*)xe, (const T*)att, (const T*)workspace,
-                               (const T*)dO, (T*)dxl, (T*)dxe, (T*)datt, C, h, d, (T)negative_slope,
-                               drop_arg<DROP, T>(drop));
-          else
-            hipLaunchKernelGGL((k_gv2attn_bwd_row_generic<T, DROP>), grid, dim3(kGenericBlock), 0, st,
-                               (const i64*)row, (const i64*)indptr_r, (const i64*)indices_r, (const T*)xl, (const T*)xr,
-                               (const T*)att, (const T*)workspace, (const T*)dO, (T*)dxl, (T*)datt, C, h, d,
-                               (T)negative_slope, drop_arg<DROP, T>(drop));
-        });
-      };
-      if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+      GO_DISPATCH_FLOAT(dtype, T, GO_DISPATCH_BOOL(dropped, DROP, {
+        go_launch(GO_EDGE_KERNEL(EDGE, k_gv2attn_bwd_row_generic, k_gv2edge_bwd_row_generic, T, DROP), grid,
+                  dim3(kGenericBlock), st, (const i64*)row, (const i64*)indptr_r, arg_if<EDGE>((const i64*)eid_r),
+                  (const i64*)indices_r, (const T*)xl, (const T*)xr, arg_if<EDGE>((const T*)xe), (const T*)att,
+                  (const T*)workspace, (const T*)dO, (T*)dxl, arg_if<EDGE>((T*)dxe), (T*)datt, C, h, d,
+                  (T)negative_slope, drop_arg<DROP, T>(drop));
+      }));
     }
     GO_LAUNCH_CHECK();
   }
@@ -262,37 +227,21 @@ int gv2attn_backward(const char* fn, int dtype, const int64_t* row, const int64_
       const bool owned = pc->info.rows_sorted != 0;
       const dim3 grid((unsigned)gat_grid(C, cpg));
       GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
-        if constexpr (EDGE)   // the column pass always reads eid_c
-          hipLaunchKernelGGL((gv2attn_bwd_col_kernel<H, D, OWNED, DROP, EDGE>()), grid, dim3(kFastBlock), 0, st,
-                             (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c, (const i64*)indices_c,
-                             (const float*)xl, (const float*)xr, (const float*)xe, (const float*)att,
-                             (const float4*)workspace, (const float*)dO, (float*)dxr, C, cpg, slope,
-                             drop_arg<DROP, float>(drop));
-        else
-          hipLaunchKernelGGL((gv2attn_bwd_col_kernel<H, D, OWNED, DROP, EDGE>()), grid, dim3(kFastBlock), 0, st,
-                             (const i64*)col, (const i64*)indptr_c, (const i64*)indices_c, (const float*)xl,
-                             (const float*)xr, (const float*)att, (const float4*)workspace, (const float*)dO,
-                             (float*)dxr, C, cpg, slope, drop_arg<DROP, float>(drop));
+        // with the edge row the column pass always reads eid_c: no eid_arg here
+        go_launch(gv2attn_bwd_col_kernel<H, D, OWNED, DROP, EDGE>(), grid, dim3(kFastBlock), st, (const i64*)col,
+                  (const i64*)indptr_c, arg_if<EDGE>((const i64*)eid_c), (const i64*)indices_c, (const float*)xl,
+                  (const float*)xr, arg_if<EDGE>((const float*)xe), (const float*)att, (const float4*)workspace,
+                  (const float*)dO, (float*)dxr, C, cpg, slope, drop_arg<DROP, float>(drop));
       })));
     } else {
       ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][0]);
       const dim3 grid((unsigned)ceil_div(C, kGenericWavesPerBlock));
-      auto go = [&](auto zero) {
-        using T = decltype(zero);
-        GO_DISPATCH_BOOL(dropped, DROP, {
-          if constexpr (EDGE)
-            hipLaunchKernelGGL((k_gv2edge_bwd_col_generic<T, DROP>), grid, dim3(kGenericBlock), 0, st,
-                               (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c, (const i64*)indices_c,
-                               (const T*)xl, (const T*)xr, (const T*)xe, (const T*)att, (const T*)workspace,
-                               (const T*)dO, (T*)dxr, C, h, d, (T)negative_slope, drop_arg<DROP, T>(drop));
-          else
-            hipLaunchKernelGGL((k_gv2attn_bwd_col_generic<T, DROP>), grid, dim3(kGenericBlock), 0, st,
-                               (const i64*)col, (const i64*)indptr_c, (const i64*)indices_c, (const T*)xl, (const T*)xr,
-                               (const T*)att, (const T*)workspace, (const T*)dO, (T*)dxr, C, h, d, (T)negative_slope,
-                               drop_arg<DROP, T>(drop));
-        });
-      };
-      if (dtype == GRAPHOP_F32) go(0.f); else go(0.0);
+      GO_DISPATCH_FLOAT(dtype, T, GO_DISPATCH_BOOL(dropped, DROP, {
+        go_launch(GO_EDGE_KERNEL(EDGE, k_gv2attn_bwd_col_generic, k_gv2edge_bwd_col_generic, T, DROP), grid,
+                  dim3(kGenericBlock), st, (const i64*)col, (const i64*)indptr_c, arg_if<EDGE>((const i64*)eid_c),
+                  (const i64*)indices_c, (const T*)xl, (const T*)xr, arg_if<EDGE>((const T*)xe), (const T*)att,
+                  (const T*)workspace, (const T*)dO, (T*)dxr, C, h, d, (T)negative_slope, drop_arg<DROP, T>(drop));
+      }));
     }
     GO_LAUNCH_CHECK();
   }

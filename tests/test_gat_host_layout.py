@@ -12,8 +12,9 @@ from test_gat_launch_geometry import FAST_HD, MAX_ROW_BLOCKS, _cpg, _grid
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "custom_op_benchmark_amd", "csrc")
-FAMILY = ("gat.hip", "gatv2.hip", "gat_attention.hip", "gat_edge_attention.hip", "gatv2_attention.hip", "host_gat.h",
-          "host_gat_attn_ops.h")
+FAMILY = ("gat.hip", "gatv2.hip", "gat_attention.hip", "gat_edge_attention.hip", "gatv2_attention.hip",
+          "gatv2_edge_attention.hip", "host_gat.h", "host_gat_attn_ops.h", "host_gatv2_attn_ops.h")
+OPS_HEADERS = ("host_gat_attn_ops.h", "host_gatv2_attn_ops.h")
 OLD_NAMES = ("gv2attn_check", "gatv2_check_plan", "gv2attn_fast_ok", "gatv2_fast_ok", "GO_DISPATCH_GV2ATTN",
              "GO_DISPATCH_GATV2", "gv2attn_cpg", "gatv2_cpg", "gat_attn_cpg", "gv2attn_grid_of", "edge_aligned")
 N_CHUNKS = (0, 1, 15, 16, 17, 4095, 4096, 10 ** 6, 8192 * 16 * 3 + 1)
@@ -46,6 +47,13 @@ def test_no_private_copy_of_a_helper_is_left():
     for name in OLD_NAMES:
         assert [n for n, text in _sources().items() if name in text] == [], name
     assert "host_gat_attn.h" not in _sources()
+
+
+def test_a_launch_is_written_once_for_both_edge_forms_and_both_dtypes():
+    for name in OPS_HEADERS:
+        assert re.search(r"if constexpr \(EDGE\)\s+(hipLaunchKernelGGL|go_launch)", _sources()[name]) is None, name
+        assert "go_launch(" in _sources()[name] and "arg_if<EDGE>(" in _sources()[name], name
+    assert [n for n in FAMILY if "go(0.f)" in _sources()[n]] == []
 
 
 @functools.lru_cache(maxsize=None)
