@@ -116,6 +116,12 @@ _SIGNATURES = {
     "graphop_attention_backward_is_fused": [ctypes.c_int] + [_c64] * 5 + [_P, _P, _P, ctypes.POINTER(ctypes.c_int)],
     "graphop_attention_forward": [ctypes.c_int] + [_P] * 9 + [_c64] * 6 + [_P, _c64, _P, _P],
     "graphop_attention_backward": [ctypes.c_int] + [_P] * 17 + [_c64] * 7 + [_P, _c64, _P, _P, _P],
+    "graphop_attention_dropout_workspace_bytes": [ctypes.c_int, ctypes.c_int] + [_c64] * 5 + [_P, _P, _P,
+                                                                                               ctypes.POINTER(_c64)],
+    "graphop_attention_dropout_forward": [ctypes.c_int] + [_P] * 9 + [_c64] * 6 + [_P, _c64, _P, _P]
+    + [ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _c64],
+    "graphop_attention_dropout_backward": [ctypes.c_int] + [_P] * 17 + [_c64] * 7 + [_P, _c64, _P, _P, _P]
+    + [ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _c64],
 }
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ["graphop_abi_version", "graphop_last_error",
                                                "graphop_plan_destroy", "graphop_memory_bytes", "graphop_tune_key"])

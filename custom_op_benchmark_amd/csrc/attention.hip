@@ -6,9 +6,14 @@
 //             beyond the L2 make column windows pay, chunk drivers otherwise; when neither applies
 //             (no plan, fp64, several heads) the same result comes from the composition of the
 //             unfused entry points, with the intermediates in the workspace.
+// Attention dropout (graphop_attention_dropout_*): o = sum_j a_ij m_ij V_j with the multiplier of
+// kernels_dropout.h recomputed per slot.  The forms are chosen by the rules of the undropped op; the fused kernels run
+// their DROP instantiations, the composed path multiplies a (and the gradient that comes back) by m with
+// k_attn_drop_apply.  drop == nullptr below is the undropped op: the same kernels and launches as before.
 // Reference composition: wrapper.py:20-30 (MaskedMMCSR), :8-18 (SparseSoftmax), :44-55 (VectorSPMM).
 #include "common.h"
 #include "host.h"
+#include "host_dropout.h"
 #include "kernels_attn.h"
 
 namespace graphop {
@@ -19,6 +24,10 @@ namespace {
 constexpr int attn_bpc(int NV, bool col) { return col ? (NV >= 4 ? 2 : 3) : (NV >= 2 ? 3 : 4); }
 // with the ids staged through LDS (4 more VGPRs, 1 KB more LDS per group) the one-row pass runs 3 per CU
 constexpr int attn_bpc_staged(int NV, bool col) { return col ? (NV >= 4 ? 2 : 3) : 3; }
+// With dropout the d = 128 row pass (L = 32, NV = 1) would spill at its 4 workgroups per CU (128 VGPRs, all in use
+// without dropout): that DROP instantiation alone is compiled for one fewer.  The launch geometry stays the undropped
+// one; the task queue hands the surplus workgroups whatever is left when they start.
+constexpr int attn_bpc_drop(int L, int NV, bool col) { return attn_bpc(NV, col) - ((L == 32 && NV == 1 && !col) ? 1 : 0); }
 inline bool attn_staged(int L, int NV) { return (tuning().staged_ids & 4) && L == 16 && NV == 1; }   // d = 64: the other widths would spill in the column pass
 
 inline size_t align_up(size_t v) { return (v + 255) & ~(size_t)255; }
@@ -101,11 +110,19 @@ bool attn_rows_ok(int dtype, i64 h, i64 d, i64 n_edges, i64 n_q, i64 n_k, const 
          plan_c->info.max_index < n_q;
 }
 
-template <bool COL>
+// the kernel argument of a DROP instantiation; drop is NULL exactly where DROP is false
+template <bool DROP>
+inline AttnDropIf<DROP> attn_drop_arg(const AttnDrop* drop) {
+  if constexpr (DROP) return *drop;
+  else return NoDrop{};
+}
+
+template <bool COL, bool DROP>
 int launch_attn_rows(const char* tag, const graphop_plan* plan, i64 n_chunks, int F, const float* own,
-                     const float* xt, const float4* st4, float* out0, float* out1, hipStream_t st) {
+                     const float* xt, const float4* st4, float* out0, float* out1, const AttnDrop* drop,
+                     hipStream_t st) {
   if (n_chunks == 0) return GRAPHOP_OK;
-  ProfScope prof(tag, st, "k_attn_bwd_rows_f32");
+  ProfScope prof(tag, st, DROP ? "k_attn_bwd_rows_f32<DROP>" : "k_attn_bwd_rows_f32");
   const bool owned = plan->info.rows_sorted != 0;
   GO_DISPATCH_LNV(F, {
     constexpr int GPB = kFastBlock / L;
@@ -114,13 +131,13 @@ int launch_attn_rows(const char* tag, const graphop_plan* plan, i64 n_chunks, in
     cpg = cpg < 1 ? 1 : (cpg > 16 ? 16 : cpg);
     const unsigned nb = (unsigned)ceil_div(ceil_div(n_chunks, cpg), GPB);
     if (owned)
-      hipLaunchKernelGGL((k_attn_bwd_rows_f32<L, NV, COL, true>), dim3(nb), dim3(kFastBlock), 0, st,
+      hipLaunchKernelGGL((k_attn_bwd_rows_f32<L, NV, COL, true, DROP>), dim3(nb), dim3(kFastBlock), 0, st,
                          (const i64*)plan->row, (const i64*)plan->indptr, (const i64*)plan->indices, own, xt,
-                         st4, out0, out1, n_chunks, (int)cpg);
+                         st4, out0, out1, n_chunks, (int)cpg, attn_drop_arg<DROP>(drop));
     else
-      hipLaunchKernelGGL((k_attn_bwd_rows_f32<L, NV, COL, false>), dim3(nb), dim3(kFastBlock), 0, st,
+      hipLaunchKernelGGL((k_attn_bwd_rows_f32<L, NV, COL, false, DROP>), dim3(nb), dim3(kFastBlock), 0, st,
                          (const i64*)plan->row, (const i64*)plan->indptr, (const i64*)plan->indices, own, xt,
-                         st4, out0, out1, n_chunks, (int)cpg);
+                         st4, out0, out1, n_chunks, (int)cpg, attn_drop_arg<DROP>(drop));
   });
   GO_LAUNCH_CHECK();
   return GRAPHOP_OK;
@@ -137,12 +154,13 @@ struct FastWs {
   }
 };
 
-// E-sized intermediates of the composed path: n_arrays of n_edges*h values + the softmax scratch
+// E-sized intermediates of the composed path: n_arrays of n_edges*h values + the softmax scratch (the fifth array is
+// the masked weights a * m of the backward with dropout)
 struct SlowWs {
-  char* arr[4]; char* soft; size_t total;
+  char* arr[5]; char* soft; size_t total;
   SlowWs(char* base, int n_arrays, size_t es, i64 E, i64 h, i64 soft_rows) {
     size_t off = 0;
-    for (int i = 0; i < 4; ++i) {
+    for (int i = 0; i < 5; ++i) {
       arr[i] = at_offset(base, off);
       if (i < n_arrays) off += align_up(es * (size_t)(E * h));
     }
@@ -155,34 +173,36 @@ inline i64 soft_rows_of(const graphop_plan* plan_r, i64 n_q) {
   return (plan_r && plan_r->info.row_owned) ? 0 : n_q;   // general softmax path: max / sum per row
 }
 
-template <bool COL>
+template <bool COL, bool DROP>
 int launch_attn_pass(const char* tag, const SweepLaunch& sl, int F, i64 n_gathered, const float* own,
-                     const float* xt, const float4* st4, float* out0, float* out1, hipStream_t st) {
-  ProfScope prof(tag, st, "k_attn_bwd_wown_f32");
+                     const float* xt, const float4* st4, float* out0, float* out1, const AttnDrop* drop,
+                     hipStream_t st) {
+  ProfScope prof(tag, st, DROP ? "k_attn_bwd_wown_f32<DROP>" : "k_attn_bwd_wown_f32");
   const dim3 grid(sl.blocks), block(kFastBlock);
+  const AttnDropIf<DROP> dr = attn_drop_arg<DROP>(drop);
   GO_DISPATCH_LNV(F, {
     const bool off32 = n_gathered * 2 * 16LL * L * NV < (1LL << 32);
-    constexpr int BPC = attn_bpc(NV, COL);
+    constexpr int BPC = DROP ? attn_bpc_drop(L, NV, COL) : attn_bpc(NV, COL);
     bool staged = false;
     if constexpr (L == 16 && NV == 1) {
       if (sl.view.rec != nullptr) {
         constexpr int BPS = attn_bpc_staged(NV, COL);
         staged = true;
         if (off32)
-          hipLaunchKernelGGL((k_attn_bwd_wown_f32<L, NV, COL, true, BPS, true>), grid, block, sl.lds_bytes, st,
-                             sl.view, own, xt, st4, out0, out1);
+          hipLaunchKernelGGL((k_attn_bwd_wown_f32<L, NV, COL, true, BPS, true, DROP>), grid, block, sl.lds_bytes, st,
+                             sl.view, own, xt, st4, out0, out1, dr);
         else
-          hipLaunchKernelGGL((k_attn_bwd_wown_f32<L, NV, COL, false, BPS, true>), grid, block, sl.lds_bytes, st,
-                             sl.view, own, xt, st4, out0, out1);
+          hipLaunchKernelGGL((k_attn_bwd_wown_f32<L, NV, COL, false, BPS, true, DROP>), grid, block, sl.lds_bytes, st,
+                             sl.view, own, xt, st4, out0, out1, dr);
       }
     }
     if (staged) {
     } else if (off32)
-      hipLaunchKernelGGL((k_attn_bwd_wown_f32<L, NV, COL, true, BPC>), grid, block, sl.lds_bytes, st,
-                         sl.view, own, xt, st4, out0, out1);
+      hipLaunchKernelGGL((k_attn_bwd_wown_f32<L, NV, COL, true, BPC, false, DROP>), grid, block, sl.lds_bytes, st,
+                         sl.view, own, xt, st4, out0, out1, dr);
     else
-      hipLaunchKernelGGL((k_attn_bwd_wown_f32<L, NV, COL, false, BPC>), grid, block, sl.lds_bytes, st,
-                         sl.view, own, xt, st4, out0, out1);
+      hipLaunchKernelGGL((k_attn_bwd_wown_f32<L, NV, COL, false, BPC, false, DROP>), grid, block, sl.lds_bytes, st,
+                         sl.view, own, xt, st4, out0, out1, dr);
   });
   GO_LAUNCH_CHECK();
   return GRAPHOP_OK;
@@ -205,13 +225,55 @@ int attn_prepare_plan(const graphop_plan* plan, i64 n_table_rows, i64 d, bool co
 
 using namespace graphop;
 
-extern "C" {
+namespace {
 
-int graphop_attention_workspace_bytes(int dtype, int backward, int64_t n_edges, int64_t n_q,
-                                      int64_t n_k, int64_t h, int64_t d,
-                                      const graphop_plan_t* plan_r, const graphop_plan_t* plan_c,
-                                      void* stream, int64_t* bytes_out) {
-  const char* fn = "attention_workspace_bytes";
+// the checks every entry point of the op makes first, stated once
+int attn_check(const char* fn, int dtype, i64 n_row_chunks, i64 n_col_chunks, i64 n_edges, i64 n_q, i64 n_k, i64 h,
+               i64 d) {
+  GO_CHECK_ARG(dtype == GRAPHOP_F32 || dtype == GRAPHOP_F64, "%s: bad dtype", fn);
+  GO_CHECK_ARG(n_row_chunks >= 0 && n_col_chunks >= 0 && n_edges >= 0 && n_q >= 0 && n_k >= 0 && h >= 1 && d >= 0,
+               "%s: negative size", fn);
+  return GRAPHOP_OK;
+}
+
+// the dropout arguments of the *_dropout_* entry points as they arrive; checked after the checks above
+struct DropIn {
+  double p;
+  uint64_t seed;
+  uint32_t offset;
+  i64 head0;
+};
+
+int attn_drop_check(const char* fn, const DropIn& in, i64 n_q, i64 n_k, HostDrop* out) {
+  GO_TRY(drop_check(fn, in.p, in.seed, n_q, n_k, in.offset, out));
+  GO_CHECK_ARG(in.head0 >= 0 && in.head0 < ((i64)1 << 32), "%s: head0 must be in [0, 2^32), got %lld", fn,
+               (long long)in.head0);
+  return GRAPHOP_OK;
+}
+
+// y = x * m over the row-major chunks (k_attn_drop_apply), in place or not
+int attn_drop_apply(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid, const int64_t* indices,
+                    const void* x, void* y, i64 n_chunks, i64 n_edges, i64 h, i64 head0, const HostDrop& drop,
+                    hipStream_t st) {
+  if (n_chunks == 0 || n_edges * h == 0) return GRAPHOP_OK;
+  ProfScope prof("attn_drop_apply", st, "k_attn_drop_apply");
+  const unsigned nb = (unsigned)ceil_div(n_chunks, kGenericWavesPerBlock);
+  auto launch = [&](auto zero) {
+    using T = decltype(zero);
+    hipLaunchKernelGGL((k_attn_drop_apply<T>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)row,
+                       (const i64*)indptr, (const i64*)eid, (const i64*)indices, (const T*)x, (T*)y, n_chunks, h, head0,
+                       drop.as<T>());
+  };
+  if (dtype == GRAPHOP_F32) launch(0.f);
+  else launch(0.0);
+  GO_LAUNCH_CHECK();
+  return GRAPHOP_OK;
+}
+
+// bwd_arrays: E-sized arrays of the composed backward (4; 5 with dropout: the masked weights)
+int attn_workspace_bytes(const char* fn, int dtype, int backward, int64_t n_edges, int64_t n_q, int64_t n_k, int64_t h,
+                         int64_t d, const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream,
+                         int bwd_arrays, int64_t* bytes_out) {
   GO_CHECK_ARG(bytes_out != nullptr, "%s: bytes_out is NULL", fn);
   GO_CHECK_ARG(dtype == GRAPHOP_F32 || dtype == GRAPHOP_F64, "%s: bad dtype", fn);
   GO_CHECK_ARG(n_edges >= 0 && n_q >= 0 && n_k >= 0 && h >= 1 && d >= 0, "%s: negative size", fn);
@@ -233,8 +295,190 @@ int graphop_attention_workspace_bytes(int dtype, int backward, int64_t n_edges, 
   if (fast < 0) return -fast;
   if (fast == 1 || attn_rows_ok(dtype, h, d, n_edges, n_q, n_k, plan_r, plan_c, (hipStream_t)stream))
     *bytes_out = (int64_t)FastWs(nullptr, n_q, n_k, h * d).total;
-  else *bytes_out = (int64_t)SlowWs(nullptr, 4, es, n_edges, h, soft_rows_of(plan_r, n_q)).total;
+  else *bytes_out = (int64_t)SlowWs(nullptr, bwd_arrays, es, n_edges, h, soft_rows_of(plan_r, n_q)).total;
   return GRAPHOP_OK;
+}
+
+// the one-head decision of the fused kernels for the call's first head
+inline AttnDrop attn_head_drop(const HostDrop& drop, i64 head0) {
+  return AttnDrop{drop.as<float>(), (unsigned)(head0 >> 2), (int)(head0 & 3)};
+}
+
+// din == nullptr: graphop_attention_forward, else its dropout form (p == 0: the undropped op), as `fn`
+int attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t* indptr,
+                 const int64_t* eid, const int64_t* indices, const void* Q, const void* K, const void* V, void* o,
+                 void* stats, int64_t n_chunks, int64_t n_edges, int64_t n_q, int64_t n_k, int64_t h, int64_t d,
+                 void* workspace, int64_t workspace_bytes, const DropIn* din, const graphop_plan_t* plan,
+                 void* stream) {
+  GO_TRY(check_async_error(false));
+  GO_TRY(attn_check(fn, dtype, n_chunks, 0, n_edges, n_q, n_k, h, d));
+  HostDrop hdrop;
+  if (din) GO_TRY(attn_drop_check(fn, *din, n_q, n_k, &hdrop));
+  const HostDrop* drop = (din && din->p > 0.0) ? &hdrop : nullptr;
+  const int64_t head0 = din ? din->head0 : 0;
+  const char* ws_fn = drop ? "attention_dropout_workspace_bytes" : "attention_workspace_bytes";
+  hipStream_t st = (hipStream_t)stream;
+  AttnDrop hd{};
+  if (drop) hd = attn_head_drop(*drop, head0);
+  const size_t es = esize(dtype);
+  if (n_q * h > 0) {
+    GO_PTR(fn, stats);
+    GO_HIP(zero_async(stats, es * (size_t)(n_q * h * 2), st));   // rows without edges: (0, 0)
+  }
+  const graphop_plan* pm = plan_matches_full(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
+                                             (const i64*)indices, n_chunks, n_edges) ? plan : nullptr;
+  // ONE walk-style pass where it applies (kernels_attn_walk.h): s and a never leave the chip; its workspace (piece
+  // records of the rows that bins share) is what graphop_attention_workspace_bytes reported for this call
+  if (pm && n_edges * h > 0) {
+    GO_PTR(fn, Q); GO_PTR(fn, K); GO_PTR(fn, V); GO_PTR(fn, o);
+    size_t need = 0;
+    const int ok = attn_fwd_walk(pm, n_q, n_k, h, d, dtype, Q, K, V, o, stats, nullptr, 0, st, /*dry_run=*/true, &need);
+    if (ok < 0) return -ok;
+    if (ok == 1) {
+      GO_CHECK_ARG(workspace != nullptr && (size_t)workspace_bytes >= need,
+                   "%s: workspace of %lld bytes needed (graphop_%s), got %lld", fn,
+                   (long long)need, ws_fn, (long long)workspace_bytes);
+      const int fw = attn_fwd_walk(pm, n_q, n_k, h, d, dtype, Q, K, V, o, stats, workspace, workspace_bytes, st,
+                                   /*dry_run=*/false, nullptr, drop ? &hd : nullptr);
+      if (fw < 0) return -fw;
+      if (fw == 1) return GRAPHOP_OK;
+    }
+  }
+  const i64 soft_rows = soft_rows_of(pm, n_q);
+  SlowWs ws((char*)workspace, 2, es, n_edges, h, soft_rows);
+  GO_CHECK_ARG(n_edges * h == 0 || (workspace != nullptr && (size_t)workspace_bytes >= ws.total),
+               "%s: workspace of %lld bytes needed (graphop_%s), got %lld", fn,
+               (long long)ws.total, ws_fn, (long long)workspace_bytes);
+  void* s = ws.arr[0];
+  void* a = ws.arr[1];
+  GO_TRY(graphop_maskedmm_csr_forward(dtype, row, indptr, eid, indices, Q, K, s, n_chunks, n_edges, n_q,
+                                      n_k, h, d, pm, stream));
+  if (n_edges * h > 0)
+    GO_TRY(softmax_forward_stats(dtype, (const i64*)row, (const i64*)indptr, (const i64*)eid, s, a,
+                                 n_chunks, n_edges, h, soft_rows ? ws.soft : nullptr, soft_rows, pm, st,
+                                 stats));
+  if (drop) GO_TRY(attn_drop_apply(dtype, row, indptr, eid, indices, a, a, n_chunks, n_edges, h, head0, *drop, st));
+  return graphop_vector_spmm_forward(dtype, row, indptr, eid, indices, a, V, o, n_chunks, n_edges, n_k,
+                                     n_q, h, d, pm, stream);
+}
+
+// din == nullptr: graphop_attention_backward, else its dropout form (p == 0: the undropped op), as `fn`
+int attn_backward(const char* fn, int dtype, const int64_t* row, const int64_t* indptr_r,
+                  const int64_t* eid_r, const int64_t* indices_r, const int64_t* col, const int64_t* indptr_c,
+                  const int64_t* eid_c, const int64_t* indices_c, const void* Q, const void* K, const void* V,
+                  const void* o, const void* stats, const void* dO, void* dQ, void* dK, void* dV,
+                  int64_t n_row_chunks, int64_t n_col_chunks, int64_t n_edges, int64_t n_q, int64_t n_k, int64_t h,
+                  int64_t d, void* workspace, int64_t workspace_bytes, const DropIn* din,
+                  const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream) {
+  GO_TRY(check_async_error(false));
+  GO_TRY(attn_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_q, n_k, h, d));
+  HostDrop hdrop;
+  if (din) GO_TRY(attn_drop_check(fn, *din, n_q, n_k, &hdrop));
+  const HostDrop* drop = (din && din->p > 0.0) ? &hdrop : nullptr;
+  const int64_t head0 = din ? din->head0 : 0;
+  const char* ws_fn = drop ? "attention_dropout_workspace_bytes" : "attention_workspace_bytes";
+  hipStream_t st = (hipStream_t)stream;
+  AttnDrop hd{};
+  if (drop) hd = attn_head_drop(*drop, head0);
+  const size_t es = esize(dtype);
+  const graphop_plan* pr = plan_matches_full(plan_r, (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r,
+                                             (const i64*)indices_r, n_row_chunks, n_edges) ? plan_r : nullptr;
+  const graphop_plan* pc = plan_matches_full(plan_c, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c,
+                                             (const i64*)indices_c, n_col_chunks, n_edges) ? plan_c : nullptr;
+  AttnFast af;
+  const int fast = attn_fast_plan(dtype, h, d, n_edges, n_q, n_k, pr, pc, st, /*dry_run=*/false, &af);
+  if (fast < 0) return -fast;
+  const bool rows_path = fast != 1 && attn_rows_ok(dtype, h, d, n_edges, n_q, n_k, pr, pc, st);
+  if (fast == 1 || rows_path) {
+    const i64 F = d;   // h == 1
+    FastWs ws((char*)workspace, n_q, n_k, F);
+    GO_CHECK_ARG(workspace != nullptr && (size_t)workspace_bytes >= ws.total,
+                 "%s: workspace of %lld bytes needed (graphop_%s), got %lld", fn,
+                 (long long)ws.total, ws_fn, (long long)workspace_bytes);
+    GO_PTR(fn, Q); GO_PTR(fn, K); GO_PTR(fn, V); GO_PTR(fn, o); GO_PTR(fn, stats); GO_PTR(fn, dO);
+    GO_PTR(fn, dQ); GO_PTR(fn, dK); GO_PTR(fn, dV);
+    GO_HIP(zero_async(dQ, sizeof(float) * (size_t)(n_q * F), st));
+    GO_HIP(zero_async(dK, sizeof(float) * (size_t)(n_k * F), st));
+    GO_HIP(zero_async(dV, sizeof(float) * (size_t)(n_k * F), st));
+    {
+      ProfScope prof("attn_pack", st, "k_attn_pack");
+      GO_DISPATCH_LNV((int)F, {
+        constexpr int RPB = kFastBlock / L;
+        hipLaunchKernelGGL((k_attn_pack<L, NV, false>), dim3((unsigned)ceil_div(n_k, RPB)), dim3(kFastBlock),
+                           0, st, (const float*)K, (const float*)V, ws.kv, n_k, (const float*)nullptr,
+                           (const float*)nullptr, (float4*)nullptr);
+        hipLaunchKernelGGL((k_attn_pack<L, NV, true>), dim3((unsigned)ceil_div(n_q, RPB)), dim3(kFastBlock),
+                           0, st, (const float*)Q, (const float*)dO, ws.qdo, n_q, (const float*)o,
+                           (const float*)stats, ws.st4);
+      });
+      GO_LAUNCH_CHECK();
+    }
+    // each launch is written once: DROP picks the instantiation, the arguments are the same
+    auto passes = [&](auto drop_c) -> int {
+      constexpr bool DROP = decltype(drop_c)::value;
+      if (rows_path) {
+        GO_TRY((launch_attn_rows<false, DROP>("attn_rows_row", pr, n_row_chunks, (int)F, ws.qdo, ws.kv, ws.st4,
+                                              (float*)dQ, nullptr, &hd, st)));
+        GO_TRY((launch_attn_rows<true, DROP>("attn_rows_col", pc, n_col_chunks, (int)F, ws.kv, ws.qdo, ws.st4,
+                                             (float*)dK, (float*)dV, &hd, st)));
+        return GRAPHOP_OK;
+      }
+      GO_TRY((launch_attn_pass<false, DROP>("attn_bwd_row", af.r, (int)F, n_k, ws.qdo, ws.kv, ws.st4, (float*)dQ,
+                                            nullptr, &hd, st)));
+      GO_TRY((launch_attn_pass<true, DROP>("attn_bwd_col", af.c, (int)F, n_q, ws.kv, ws.qdo, ws.st4, (float*)dK,
+                                           (float*)dV, &hd, st)));
+      return GRAPHOP_OK;
+    };
+    return drop ? passes(std::true_type{}) : passes(std::false_type{});
+  }
+  // composition of the unfused entry points: recompute s and a, then the three backward ops
+  const i64 soft_rows = soft_rows_of(pr, n_q);
+  SlowWs ws((char*)workspace, drop ? 5 : 4, es, n_edges, h, soft_rows);
+  GO_CHECK_ARG(n_edges * h == 0 || (workspace != nullptr && (size_t)workspace_bytes >= ws.total),
+               "%s: workspace of %lld bytes needed (graphop_%s), got %lld", fn,
+               (long long)ws.total, ws_fn, (long long)workspace_bytes);
+  void* s = ws.arr[0];
+  void* a = ws.arr[1];
+  void* da = ws.arr[2];
+  void* ds = ws.arr[3];
+  GO_TRY(graphop_maskedmm_csr_forward(dtype, row, indptr_r, eid_r, indices_r, Q, K, s, n_row_chunks,
+                                      n_edges, n_q, n_k, h, d, pr, stream));
+  GO_TRY(graphop_sparse_softmax_forward(dtype, row, indptr_r, eid_r, s, a, n_row_chunks, n_edges, h,
+                                        soft_rows ? ws.soft : nullptr, soft_rows, pr, stream));
+  // with dropout: am = a * m feeds the SpMM backward, and the gradient that comes back is that of am: da = d_am * m
+  const void* w = a;
+  if (drop) {
+    GO_TRY(attn_drop_apply(dtype, row, indptr_r, eid_r, indices_r, a, ws.arr[4], n_row_chunks, n_edges, h, head0, *drop, st));
+    w = ws.arr[4];
+  }
+  GO_TRY(graphop_vector_spmm_backward(dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
+                                      indices_c, w, dO, V, da, dV, n_row_chunks, n_col_chunks, n_edges,
+                                      n_k, n_q, h, d, pr, pc, stream));
+  if (drop) GO_TRY(attn_drop_apply(dtype, row, indptr_r, eid_r, indices_r, da, da, n_row_chunks, n_edges, h, head0, *drop, st));
+  GO_TRY(graphop_sparse_softmax_backward(dtype, row, indptr_r, eid_r, a, da, ds, n_row_chunks, n_edges, h,
+                                         soft_rows ? ws.soft : nullptr, soft_rows, pr, stream));
+  return graphop_maskedmm_csr_backward(dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
+                                       indices_c, Q, K, ds, dQ, dK, n_row_chunks, n_col_chunks, n_edges,
+                                       n_q, n_k, h, d, pr, pc, stream);
+}
+
+}  // namespace
+
+extern "C" {
+
+int graphop_attention_workspace_bytes(int dtype, int backward, int64_t n_edges, int64_t n_q,
+                                      int64_t n_k, int64_t h, int64_t d,
+                                      const graphop_plan_t* plan_r, const graphop_plan_t* plan_c,
+                                      void* stream, int64_t* bytes_out) {
+  return attn_workspace_bytes("attention_workspace_bytes", dtype, backward, n_edges, n_q, n_k, h, d, plan_r, plan_c,
+                              stream, 4, bytes_out);
+}
+
+int graphop_attention_dropout_workspace_bytes(int dtype, int backward, int64_t n_edges, int64_t n_q, int64_t n_k,
+                                              int64_t h, int64_t d, const graphop_plan_t* plan_r,
+                                              const graphop_plan_t* plan_c, void* stream, int64_t* bytes_out) {
+  return attn_workspace_bytes("attention_dropout_workspace_bytes", dtype, backward, n_edges, n_q, n_k, h, d, plan_r,
+                              plan_c, stream, 5, bytes_out);
 }
 
 int graphop_attention_backward_is_fused(int dtype, int64_t n_edges, int64_t n_q, int64_t n_k, int64_t h,
@@ -254,51 +498,8 @@ int graphop_attention_forward(int dtype, const int64_t* row, const int64_t* indp
                               void* o, void* stats, int64_t n_chunks, int64_t n_edges, int64_t n_q,
                               int64_t n_k, int64_t h, int64_t d, void* workspace,
                               int64_t workspace_bytes, const graphop_plan_t* plan, void* stream) {
-  const char* fn = "attention_forward";
-  GO_TRY(check_async_error(false));
-  GO_CHECK_ARG(dtype == GRAPHOP_F32 || dtype == GRAPHOP_F64, "%s: bad dtype", fn);
-  GO_CHECK_ARG(n_chunks >= 0 && n_edges >= 0 && n_q >= 0 && n_k >= 0 && h >= 1 && d >= 0,
-               "%s: negative size", fn);
-  hipStream_t st = (hipStream_t)stream;
-  const size_t es = esize(dtype);
-  if (n_q * h > 0) {
-    GO_PTR(fn, stats);
-    GO_HIP(zero_async(stats, es * (size_t)(n_q * h * 2), st));   // rows without edges: (0, 0)
-  }
-  const graphop_plan* pm = plan_matches_full(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
-                                             (const i64*)indices, n_chunks, n_edges) ? plan : nullptr;
-  // ONE walk-style pass where it applies (kernels_attn_walk.h): s and a never leave the chip; its workspace (piece
-  // records of the rows that bins share) is what graphop_attention_workspace_bytes reported for this call
-  if (pm && n_edges * h > 0) {
-    GO_PTR(fn, Q); GO_PTR(fn, K); GO_PTR(fn, V); GO_PTR(fn, o);
-    size_t need = 0;
-    const int ok = attn_fwd_walk(pm, n_q, n_k, h, d, dtype, Q, K, V, o, stats, nullptr, 0, st, /*dry_run=*/true, &need);
-    if (ok < 0) return -ok;
-    if (ok == 1) {
-      GO_CHECK_ARG(workspace != nullptr && (size_t)workspace_bytes >= need,
-                   "%s: workspace of %lld bytes needed (graphop_attention_workspace_bytes), got %lld", fn,
-                   (long long)need, (long long)workspace_bytes);
-      const int fw = attn_fwd_walk(pm, n_q, n_k, h, d, dtype, Q, K, V, o, stats, workspace, workspace_bytes, st,
-                                   /*dry_run=*/false, nullptr);
-      if (fw < 0) return -fw;
-      if (fw == 1) return GRAPHOP_OK;
-    }
-  }
-  const i64 soft_rows = soft_rows_of(pm, n_q);
-  SlowWs ws((char*)workspace, 2, es, n_edges, h, soft_rows);
-  GO_CHECK_ARG(n_edges * h == 0 || (workspace != nullptr && (size_t)workspace_bytes >= ws.total),
-               "%s: workspace of %lld bytes needed (graphop_attention_workspace_bytes), got %lld", fn,
-               (long long)ws.total, (long long)workspace_bytes);
-  void* s = ws.arr[0];
-  void* a = ws.arr[1];
-  GO_TRY(graphop_maskedmm_csr_forward(dtype, row, indptr, eid, indices, Q, K, s, n_chunks, n_edges, n_q,
-                                      n_k, h, d, pm, stream));
-  if (n_edges * h > 0)
-    GO_TRY(softmax_forward_stats(dtype, (const i64*)row, (const i64*)indptr, (const i64*)eid, s, a,
-                                 n_chunks, n_edges, h, soft_rows ? ws.soft : nullptr, soft_rows, pm, st,
-                                 stats));
-  return graphop_vector_spmm_forward(dtype, row, indptr, eid, indices, a, V, o, n_chunks, n_edges, n_k,
-                                     n_q, h, d, pm, stream);
+  return attn_forward("attention_forward", dtype, row, indptr, eid, indices, Q, K, V, o, stats, n_chunks, n_edges, n_q,
+                      n_k, h, d, workspace, workspace_bytes, nullptr, plan, stream);
 }
 
 int graphop_attention_backward(int dtype, const int64_t* row, const int64_t* indptr_r,
@@ -310,80 +511,36 @@ int graphop_attention_backward(int dtype, const int64_t* row, const int64_t* ind
                                int64_t n_q, int64_t n_k, int64_t h, int64_t d, void* workspace,
                                int64_t workspace_bytes, const graphop_plan_t* plan_r,
                                const graphop_plan_t* plan_c, void* stream) {
-  const char* fn = "attention_backward";
-  GO_TRY(check_async_error(false));
-  GO_CHECK_ARG(dtype == GRAPHOP_F32 || dtype == GRAPHOP_F64, "%s: bad dtype", fn);
-  GO_CHECK_ARG(n_row_chunks >= 0 && n_col_chunks >= 0 && n_edges >= 0 && n_q >= 0 && n_k >= 0 &&
-               h >= 1 && d >= 0, "%s: negative size", fn);
-  hipStream_t st = (hipStream_t)stream;
-  const size_t es = esize(dtype);
-  const graphop_plan* pr = plan_matches_full(plan_r, (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r,
-                                             (const i64*)indices_r, n_row_chunks, n_edges) ? plan_r : nullptr;
-  const graphop_plan* pc = plan_matches_full(plan_c, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c,
-                                             (const i64*)indices_c, n_col_chunks, n_edges) ? plan_c : nullptr;
-  AttnFast af;
-  const int fast = attn_fast_plan(dtype, h, d, n_edges, n_q, n_k, pr, pc, st, /*dry_run=*/false, &af);
-  if (fast < 0) return -fast;
-  const bool rows_path = fast != 1 && attn_rows_ok(dtype, h, d, n_edges, n_q, n_k, pr, pc, st);
-  if (fast == 1 || rows_path) {
-    const i64 F = d;   // h == 1
-    FastWs ws((char*)workspace, n_q, n_k, F);
-    GO_CHECK_ARG(workspace != nullptr && (size_t)workspace_bytes >= ws.total,
-                 "%s: workspace of %lld bytes needed (graphop_attention_workspace_bytes), got %lld", fn,
-                 (long long)ws.total, (long long)workspace_bytes);
-    GO_PTR(fn, Q); GO_PTR(fn, K); GO_PTR(fn, V); GO_PTR(fn, o); GO_PTR(fn, stats); GO_PTR(fn, dO);
-    GO_PTR(fn, dQ); GO_PTR(fn, dK); GO_PTR(fn, dV);
-    GO_HIP(zero_async(dQ, sizeof(float) * (size_t)(n_q * F), st));
-    GO_HIP(zero_async(dK, sizeof(float) * (size_t)(n_k * F), st));
-    GO_HIP(zero_async(dV, sizeof(float) * (size_t)(n_k * F), st));
-    {
-      ProfScope prof("attn_pack", st, "k_attn_pack");
-      GO_DISPATCH_LNV((int)F, {
-        constexpr int RPB = kFastBlock / L;
-        hipLaunchKernelGGL((k_attn_pack<L, NV, false>), dim3((unsigned)ceil_div(n_k, RPB)), dim3(kFastBlock),
-                           0, st, (const float*)K, (const float*)V, ws.kv, n_k, (const float*)nullptr,
-                           (const float*)nullptr, (float4*)nullptr);
-        hipLaunchKernelGGL((k_attn_pack<L, NV, true>), dim3((unsigned)ceil_div(n_q, RPB)), dim3(kFastBlock),
-                           0, st, (const float*)Q, (const float*)dO, ws.qdo, n_q, (const float*)o,
-                           (const float*)stats, ws.st4);
-      });
-      GO_LAUNCH_CHECK();
-    }
-    if (rows_path) {
-      GO_TRY(launch_attn_rows<false>("attn_rows_row", pr, n_row_chunks, (int)F, ws.qdo, ws.kv, ws.st4, (float*)dQ,
-                                     nullptr, st));
-      GO_TRY(launch_attn_rows<true>("attn_rows_col", pc, n_col_chunks, (int)F, ws.kv, ws.qdo, ws.st4, (float*)dK,
-                                    (float*)dV, st));
-      return GRAPHOP_OK;
-    }
-    GO_TRY(launch_attn_pass<false>("attn_bwd_row", af.r, (int)F, n_k, ws.qdo, ws.kv, ws.st4, (float*)dQ,
-                                   nullptr, st));
-    GO_TRY(launch_attn_pass<true>("attn_bwd_col", af.c, (int)F, n_q, ws.kv, ws.qdo, ws.st4, (float*)dK,
-                                  (float*)dV, st));
-    return GRAPHOP_OK;
-  }
-  // composition of the unfused entry points: recompute s and a, then the three backward ops
-  const i64 soft_rows = soft_rows_of(pr, n_q);
-  SlowWs ws((char*)workspace, 4, es, n_edges, h, soft_rows);
-  GO_CHECK_ARG(n_edges * h == 0 || (workspace != nullptr && (size_t)workspace_bytes >= ws.total),
-               "%s: workspace of %lld bytes needed (graphop_attention_workspace_bytes), got %lld", fn,
-               (long long)ws.total, (long long)workspace_bytes);
-  void* s = ws.arr[0];
-  void* a = ws.arr[1];
-  void* da = ws.arr[2];
-  void* ds = ws.arr[3];
-  GO_TRY(graphop_maskedmm_csr_forward(dtype, row, indptr_r, eid_r, indices_r, Q, K, s, n_row_chunks,
-                                      n_edges, n_q, n_k, h, d, pr, stream));
-  GO_TRY(graphop_sparse_softmax_forward(dtype, row, indptr_r, eid_r, s, a, n_row_chunks, n_edges, h,
-                                        soft_rows ? ws.soft : nullptr, soft_rows, pr, stream));
-  GO_TRY(graphop_vector_spmm_backward(dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
-                                      indices_c, a, dO, V, da, dV, n_row_chunks, n_col_chunks, n_edges,
-                                      n_k, n_q, h, d, pr, pc, stream));
-  GO_TRY(graphop_sparse_softmax_backward(dtype, row, indptr_r, eid_r, a, da, ds, n_row_chunks, n_edges, h,
-                                         soft_rows ? ws.soft : nullptr, soft_rows, pr, stream));
-  return graphop_maskedmm_csr_backward(dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
-                                       indices_c, Q, K, ds, dQ, dK, n_row_chunks, n_col_chunks, n_edges,
-                                       n_q, n_k, h, d, pr, pc, stream);
+  return attn_backward("attention_backward", dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c,
+                       Q, K, V, o, stats, dO, dQ, dK, dV, n_row_chunks, n_col_chunks, n_edges, n_q, n_k, h, d, workspace,
+                       workspace_bytes, nullptr, plan_r, plan_c, stream);
+}
+
+// p == 0 is the entry point above: the same kernels, bit-identical results
+int graphop_attention_dropout_forward(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                                      const int64_t* indices, const void* Q, const void* K, const void* V, void* o,
+                                      void* stats, int64_t n_chunks, int64_t n_edges, int64_t n_q, int64_t n_k,
+                                      int64_t h, int64_t d, void* workspace, int64_t workspace_bytes,
+                                      const graphop_plan_t* plan, void* stream, double p, uint64_t seed,
+                                      uint32_t offset, int64_t head0) {
+  const DropIn din{p, seed, offset, head0};
+  return attn_forward("attention_dropout_forward", dtype, row, indptr, eid, indices, Q, K, V, o, stats, n_chunks,
+                      n_edges, n_q, n_k, h, d, workspace, workspace_bytes, &din, plan, stream);
+}
+
+int graphop_attention_dropout_backward(int dtype, const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r,
+                                       const int64_t* indices_r, const int64_t* col, const int64_t* indptr_c,
+                                       const int64_t* eid_c, const int64_t* indices_c, const void* Q, const void* K,
+                                       const void* V, const void* o, const void* stats, const void* dO, void* dQ,
+                                       void* dK, void* dV, int64_t n_row_chunks, int64_t n_col_chunks,
+                                       int64_t n_edges, int64_t n_q, int64_t n_k, int64_t h, int64_t d,
+                                       void* workspace, int64_t workspace_bytes, const graphop_plan_t* plan_r,
+                                       const graphop_plan_t* plan_c, void* stream, double p, uint64_t seed,
+                                       uint32_t offset, int64_t head0) {
+  const DropIn din{p, seed, offset, head0};
+  return attn_backward("attention_dropout_backward", dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
+                       indices_c, Q, K, V, o, stats, dO, dQ, dK, dV, n_row_chunks, n_col_chunks, n_edges, n_q, n_k, h, d,
+                       workspace, workspace_bytes, &din, plan_r, plan_c, stream);
 }
 
 }  // extern "C"

@@ -397,7 +397,7 @@ int try_spmm_walk(const char* tag, int dtype, const graphop_plan* plan, i64 n_ta
 // identity eid, tables < 4 GiB.  Workspace: piece records of the rows that bins share + two n_q-sized merge arrays.
 int attn_fwd_walk(const graphop_plan* plan, i64 n_q, i64 n_k, i64 h, i64 d, int dtype, const void* Q, const void* K,
                   const void* V, void* o, void* stats, void* ws, i64 ws_bytes, hipStream_t st, bool dry_run,
-                  size_t* ws_needed) {
+                  size_t* ws_needed, const AttnDrop* drop) {
   constexpr int L = 16;
   const Tuning& t = tuning();
   if (ws_needed) *ws_needed = 0;
@@ -437,10 +437,15 @@ int attn_fwd_walk(const graphop_plan* plan, i64 n_q, i64 n_k, i64 h, i64 d, int 
     WalkDebug dbg;
     dbg.arm(&wl, "attn_fwd", st, kWalkWorkers / kWave);
     wl.view.launch_id = walk_launch_id("attn_fwd");
-    ProfScope prof("attn_fwd", st, "k_attn_fwd_walk_f32");
-    allow_full_lds((const void*)k_attn_fwd_walk_f32<L>);
+    ProfScope prof("attn_fwd", st, drop ? "k_attn_fwd_walk_f32<DROP>" : "k_attn_fwd_walk_f32");   // (the profile tells the instantiations apart)
     const size_t lds_bytes = (size_t)(kWalkWorkers / L) * attn_walk_group_bytes<L>(KR);
-    hipLaunchKernelGGL((k_attn_fwd_walk_f32<L>), dim3(wl.blocks), dim3(kWalkThreads), lds_bytes, st, wl.view, a);
+    if (drop) {
+      allow_full_lds((const void*)k_attn_fwd_walk_f32<L, true>);
+      hipLaunchKernelGGL((k_attn_fwd_walk_f32<L, true>), dim3(wl.blocks), dim3(kWalkThreads), lds_bytes, st, wl.view, a, *drop);
+    } else {
+      allow_full_lds((const void*)k_attn_fwd_walk_f32<L, false>);
+      hipLaunchKernelGGL((k_attn_fwd_walk_f32<L, false>), dim3(wl.blocks), dim3(kWalkThreads), lds_bytes, st, wl.view, a, NoDrop{});
+    }
   }
   {
     ProfScope prof("attn_fwd_merge", st, "k_attn_piece_add");

@@ -188,9 +188,12 @@ int attn_prepare_plan(const graphop_plan* plan, i64 n_table_rows, i64 d, bool co
 
 // Fused attention forward on the walk (graphop_hip.hip; kernels_attn_walk.h): 1 = launched, 0 = does not apply,
 // < 0 = error (negated).  dry_run: only decide / build the layout and report the workspace it needs.
+// drop: the attention dropout of the call's head (kernels_attn.h), NULL = none; it changes neither the decision nor
+// the workspace.
+struct AttnDrop;
 int attn_fwd_walk(const graphop_plan* plan, i64 n_q, i64 n_k, i64 h, i64 d, int dtype, const void* Q, const void* K,
                   const void* V, void* o, void* stats, void* ws, i64 ws_bytes, hipStream_t st, bool dry_run,
-                  size_t* ws_needed);
+                  size_t* ws_needed, const AttnDrop* drop = nullptr);
 
 int softmax_forward_stats(int dtype, const i64* row, const i64* indptr, const i64* eid, const void* x,
                           void* y, i64 C, i64 E, i64 h, void* ws, i64 ws_rows,

@@ -16,10 +16,63 @@
 // streams, no transposed scalar gather.  The two operands of a pass are PACKED side by side
 // ([n][2F] floats, built per call by k_attn_pack: 2 x N x F x 4 B), so one slot is one contiguous
 // 2F*4-byte fetch and both halves share the id -> offset arithmetic.
+// Attention dropout (DROP; kernels_dropout.h has the decision): o_i = sum_j a_ij m_ij V_j with the
+// statistics of the undropped scores.  D_i = <dO_i, o_i> still equals sum_j a_ij da_ij with da_ij = m_ij <dO_i, V_j>, so
+// the (m, linv, D) table is unchanged; per slot only  da *= m  and the dV weight  a * m  differ.  The lane that holds
+// a slot's two node ids makes one Philox call per batch.
 #pragma once
+#include "kernels_dropout.h"
 #include "kernels_fast.h"
 
 namespace graphop {
+
+// the decision of ONE head (the fused kernels run one head per call): Philox block and word of the global head
+struct AttnDrop {
+  DropArgs<float> d;
+  unsigned blk;   // head0 >> 2
+  int bit;        // head0 & 3
+};
+template <bool DROP>
+using AttnDropIf = std::conditional_t<DROP, AttnDrop, NoDrop>;
+
+// the multiplier from the four Philox words of the head's block
+__device__ __forceinline__ float attn_drop_pick(const unsigned (&w)[4], const AttnDrop& dr) {
+  const unsigned wk = dr.bit == 0 ? w[0] : (dr.bit == 1 ? w[1] : (dr.bit == 2 ? w[2] : w[3]));
+  return wk >= dr.d.thresh ? dr.d.scale : 0.f;
+}
+
+// m_ij of the call's head; i indexes Q / o, j indexes K / V
+// The key schedule is held in two VGPRs: left uniform, the ten bumped key pairs are hoisted out of the batch loop into
+// twenty SGPRs, which these kernels (at the 106-SGPR ceiling already) would spill.
+__device__ __forceinline__ float attn_drop_mult(unsigned i, unsigned j, const AttnDrop& dr) {
+  unsigned k0 = dr.d.key0, k1 = dr.d.key1;
+  asm volatile("" : "+v"(k0), "+v"(k1));
+  unsigned w[4];
+  philox4x32_10(i, j, dr.blk, dr.d.offset, k0, k1, w);
+  return attn_drop_pick(w, dr);
+}
+
+// The same decision (philox4x32_10 of kernels_dropout.h, restated) with the round constants in VGPRs as well: for the
+// one-pass forward, which spills SGPRs without dropout already, so that every uniform value the decision would keep
+// live across its batch loop is one more spill there.  The caller passes an AttnDrop whose words are VGPR-held.
+__device__ __forceinline__ float attn_drop_mult_v(unsigned i, unsigned j, const AttnDrop& dr) {
+  unsigned c0 = i, c1 = j, c2 = dr.blk, c3 = dr.d.offset, k0 = dr.d.key0, k1 = dr.d.key1;
+  unsigned m0 = 0xD2511F53u, m1 = 0xCD9E8D57u, w0 = 0x9E3779B9u, w1 = 0xBB67AE85u;
+  asm volatile("" : "+v"(m0), "+v"(m1), "+v"(w0), "+v"(w1));
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned hi0 = __umulhi(m0, c0), lo0 = m0 * c0;
+    const unsigned hi1 = __umulhi(m1, c2), lo1 = m1 * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += w0;
+    k1 += w1;
+  }
+  const unsigned w[4] = {c0, c1, c2, c3};
+  return attn_drop_pick(w, dr);
+}
 
 template <int L, int NV>
 struct AttnCfg {
@@ -56,13 +109,16 @@ __global__ __launch_bounds__(kFastBlock) void k_attn_pack(
 // receives the finished sums of granule k (group-uniform call): acc0 = sum ds * X0, acc1 = sum a * X1.
 // STAGED: the neighbour ids come from the dealt layout through IdStage (kernels_fast.h) -- idx32 is
 // then ids_w, pos0 the strip's start in it and idbuf the group's LDS ring.
-template <int L, int NV, bool COL, bool OFF32, bool STAGED, typename Sink, typename Stage>
+// DROP: own_row_l = lane k holds the node id of the group's k-th own row (the id the decision needs next to the
+// gathered one).
+template <int L, int NV, bool COL, bool OFF32, bool STAGED, bool DROP, typename Sink, typename Stage>
 __device__ __forceinline__ void attn_bwd_strip(Sink&& sink, Stage&& stage_rows,
                                                const float4* __restrict__ own, int lo_l, int n_l,
                                                const int* __restrict__ idx32,
                                                const float* __restrict__ XT,
                                                const float4* __restrict__ stats4, float4 own_st,
-                                               int l, int pos0 = 0, int* __restrict__ idbuf = nullptr) {
+                                               int l, const AttnDropIf<DROP>& dr, int own_row_l, int pos0 = 0,
+                                               int* __restrict__ idbuf = nullptr) {
   constexpr int SB = AttnCfg<L, NV>::SB;
   constexpr int F4 = L * NV;
   constexpr unsigned ROWB = 2u * F4 * 16u;   // bytes of a packed row
@@ -150,6 +206,11 @@ __device__ __forceinline__ void attn_bwd_strip(Sink&& sink, Stage&& stage_rows,
     } else {
       stage_a(jb + SB, p1);
     }
+    float mult = 1.f;
+    if constexpr (DROP) {   // lane u < SB holds slot u's ids: one Philox call per batch, behind the row requests
+      const unsigned own_id = (unsigned)__shfl(own_row_l, cur.k, L);
+      if (cur.live) mult = COL ? attn_drop_mult((unsigned)cur.src, own_id, dr) : attn_drop_mult(own_id, (unsigned)cur.src, dr);
+    }
     float ps[SB], pd[SB];
     static_for<SB>([&](auto uc) {
       constexpr int u = decltype(uc)::value;
@@ -165,7 +226,8 @@ __device__ __forceinline__ void attn_bwd_strip(Sink&& sink, Stage&& stage_rows,
       ps[u] = p; pd[u] = q;
     });
     const float my_s = group_dots_to_owner<L, SB>(ps, l);
-    const float my_da = group_dots_to_owner<L, SB>(pd, l);
+    float my_da = group_dots_to_owner<L, SB>(pd, l);
+    if constexpr (DROP) my_da *= mult;
     // lane u < SB owns slot u: one exp per slot, then broadcast
     float st_m, st_linv, st_D;
     if constexpr (COL) {
@@ -177,6 +239,7 @@ __device__ __forceinline__ void attn_bwd_strip(Sink&& sink, Stage&& stage_rows,
     if (cur.live) {
       a_l = expf(my_s - st_m) * st_linv;
       ds_l = a_l * (my_da - st_D);
+      if constexpr (DROP && COL) a_l *= mult;   // from here on a_l only weights dV
     }
     static_for<SB>([&](auto uc) {
       constexpr int u = decltype(uc)::value;
@@ -212,10 +275,10 @@ __device__ __forceinline__ void attn_bwd_strip(Sink&& sink, Stage&& stage_rows,
 //   COL = false: OWN = (Q | dO) packed [n_rows][2F], XT = (K | V) packed, out0 = dQ
 //   COL = true : OWN = (K | V) packed [n_cols][2F], XT = (Q | dO) packed, out0 = dK, out1 = dV
 // stats4[i] = (m_i, linv_i, D_i, 0) per ROW i of the attention matrix in both passes.
-template <int L, int NV, bool COL, bool OFF32, int BPC, bool STAGED = false>
+template <int L, int NV, bool COL, bool OFF32, int BPC, bool STAGED = false, bool DROP = false>
 __global__ __launch_bounds__(kFastBlock, BPC) void k_attn_bwd_wown_f32(
     SweepView s, const float* __restrict__ OWN, const float* __restrict__ XT,
-    const float4* __restrict__ stats4, float* __restrict__ out0, float* __restrict__ out1) {
+    const float4* __restrict__ stats4, float* __restrict__ out0, float* __restrict__ out1, AttnDropIf<DROP> dr) {
   extern __shared__ float4 lds[];
   constexpr i64 F4 = (i64)L * NV;
   constexpr int GW = kWave / L;
@@ -261,11 +324,11 @@ __global__ __launch_bounds__(kFastBlock, BPC) void k_attn_bwd_wown_f32(
 #endif
     };
     if constexpr (STAGED)
-      attn_bwd_strip<L, NV, COL, OFF32, true>(to_out, stage_rows, mine, cur.lo, cur.hi - cur.lo, s.ids_w, XT,
-                                              stats4, own_st, l, __shfl(cur.pos, 0, L), idbuf);
+      attn_bwd_strip<L, NV, COL, OFF32, true, DROP>(to_out, stage_rows, mine, cur.lo, cur.hi - cur.lo, s.ids_w, XT,
+                                                    stats4, own_st, l, dr, row_l, __shfl(cur.pos, 0, L), idbuf);
     else
-      attn_bwd_strip<L, NV, COL, OFF32, false>(to_out, stage_rows, mine, cur.lo, cur.hi - cur.lo, s.idx32, XT,
-                                               stats4, own_st, l);
+      attn_bwd_strip<L, NV, COL, OFF32, false, DROP>(to_out, stage_rows, mine, cur.lo, cur.hi - cur.lo, s.idx32, XT,
+                                                     stats4, own_st, l, dr, row_l);
     cur = nxt;
     more = more_n;
   }
@@ -280,11 +343,11 @@ __global__ __launch_bounds__(kFastBlock, BPC) void k_attn_bwd_wown_f32(
 // atomically adds the sums.  Same per-slot arithmetic as the strips; the dot products are reduced
 // slot by slot in the chunk drivers' order (group_sum), which is the order the forward's SDDMM
 // used on these graphs.
-template <int L, int NV, bool COL, bool OWNED>
+template <int L, int NV, bool COL, bool OWNED, bool DROP = false>
 __global__ __launch_bounds__(kFastBlock) void k_attn_bwd_rows_f32(
     const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ indices,
     const float* __restrict__ OWN, const float* __restrict__ XT, const float4* __restrict__ stats4,
-    float* __restrict__ out0, float* __restrict__ out1, i64 n_chunks, int chunks_per_group) {
+    float* __restrict__ out0, float* __restrict__ out1, i64 n_chunks, int chunks_per_group, AttnDropIf<DROP> dr) {
   constexpr int SB = AttnCfg<L, NV>::SB;
   constexpr i64 F4 = (i64)L * NV;
   const int l = threadIdx.x % L;
@@ -344,6 +407,11 @@ __global__ __launch_bounds__(kFastBlock) void k_attn_bwd_rows_f32(
         my_src = indices[jb + (l < nb ? l : nb - 1)];
         if constexpr (COL) st = stats4[my_src];
       }
+      float mult = 1.f;
+      if constexpr (DROP) {   // lane u < nb holds slot u's ids: one Philox call per batch
+        if (l < nb) mult = COL ? attn_drop_mult((unsigned)my_src, (unsigned)cur_row, dr)
+                               : attn_drop_mult((unsigned)cur_row, (unsigned)my_src, dr);
+      }
       float4 x0[SB][NV], x1[SB][NV];
 #pragma unroll
       for (int u = 0; u < SB; ++u) {
@@ -365,7 +433,9 @@ __global__ __launch_bounds__(kFastBlock) void k_attn_bwd_rows_f32(
       float a_l = 0.f, ds_l = 0.f;
       if (l < nb) {
         a_l = expf(my_s - st.x) * st.y;
+        if constexpr (DROP) my_da *= mult;
         ds_l = a_l * (my_da - st.z);
+        if constexpr (DROP && COL) a_l *= mult;   // from here on a_l only weights dV
       }
 #pragma unroll
       for (int u = 0; u < SB; ++u) {

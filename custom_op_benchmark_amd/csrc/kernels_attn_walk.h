@@ -17,6 +17,7 @@
 // (k_attn_piece_max / _add / _fin): a softmax cannot be merged by float atomics alone.
 // Padding slots of a run's last chunk carry the row-in-bin 63: they gather a valid row and contribute nothing.
 #pragma once
+#include "kernels_attn.h"
 #include "kernels_walk.h"
 
 namespace graphop {
@@ -49,9 +50,18 @@ __host__ __device__ constexpr int attn_walk_rows() {
 
 __device__ __forceinline__ float attn_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896341f); }   // x <= 0
 
-template <int L>
-__device__ __forceinline__ void attn_fwd_walk_body(const WalkView& s, const AttnWalkArgs& a) {
+// DROP (attention dropout, kernels_attn.h / DESIGN.md 4.5j): the multiplier m_ij scales only the exp(s - mn) * V_j term
+// folded into o; the running (m, l) are those of the undropped scores.  Lane u < 8 holds slot u's row-in-bin and
+// neighbour id and makes the batch's Philox call; the global row id comes from the bin's row list.
+template <int L, bool DROP>
+__device__ __forceinline__ void attn_fwd_walk_body(const WalkView& s, const AttnWalkArgs& a, const AttnDropIf<DROP>& dr) {
   static_assert(L == 16, "256-B rows (d = 64): 8-slot batches reduced by the 16-lane transpose tree");
+  // DROP: the seven words of the decision live in VGPRs (this kernel has them to spare at its occupancy and is at the
+  // SGPR ceiling without them)
+  AttnDropIf<DROP> drv = dr;
+  if constexpr (DROP)
+    asm volatile("" : "+v"(drv.d.key0), "+v"(drv.d.key1), "+v"(drv.d.offset), "+v"(drv.d.thresh), "+v"(drv.d.scale),
+                      "+v"(drv.blk), "+v"(drv.bit));
   extern __shared__ float4 lds_raw[];
   constexpr int GPB = kWalkWorkers / L;
   constexpr int SB = 8;                       // slots per batch: two gathered rows per slot, 64 VGPRs in flight
@@ -178,6 +188,10 @@ __device__ __forceinline__ void attn_fwd_walk_body(const WalkView& s, const Attn
     float2* ml = reinterpret_cast<float2*>(accO + K * L);             // [K] (running max, running sum)
     const int* ring = ring_of(bin);
     const i64 tb = walk_bin_index_of<GPB>(s, r, bin);
+    int bin_row_l = 0;   // DROP: lane k holds the global id of the bin's k-th row
+    if constexpr (DROP) {
+      if (l < K) bin_row_l = s.bin_rows[tb * K + l] & kWalkRowMask;
+    }
     int total, step_len;
     if (sidx == 0) {                                  // the bin's round starts: state to zero, Q rows into LDS
       total = s.bin_cum[tb];
@@ -278,6 +292,11 @@ __device__ __forceinline__ void attn_fwd_walk_body(const WalkView& s, const Attn
           part[u] = dot4(qv, x0[u]);
         });
         const float s_mine = group_dots_to_owner<L, SB>(part, l);
+        float mult = 1.f;
+        if constexpr (DROP) {   // lanes u and u + 8 hold slot u: (row of the bin's mc.k-th row, neighbour id); a padding slot's is unused
+          const unsigned i = (unsigned)__shfl(bin_row_l, mc.k & (L - 1), L);
+          mult = attn_drop_mult_v(i, off_c / ROWB, drv);
+        }
         static_for<SB>([&](auto uc) {
           constexpr int u = decltype(uc)::value;
           const int kt = group_bcast<L, u>(mc.k);
@@ -291,8 +310,16 @@ __device__ __forceinline__ void attn_fwd_walk_body(const WalkView& s, const Attn
           l_c = fmaf(l_c, sc, p);
           // (a select, not 0 * V: a padding slot gathers SOME valid row, and a non-finite value there must not reach this row)
           const float4 xv = pad ? make_float4(0.f, 0.f, 0.f, 0.f) : x1[u];
-          o_c.x = fmaf(o_c.x, sc, p * xv.x); o_c.y = fmaf(o_c.y, sc, p * xv.y);
-          o_c.z = fmaf(o_c.z, sc, p * xv.z); o_c.w = fmaf(o_c.w, sc, p * xv.w);
+          // (two branches on purpose: the undropped one keeps its statements as they were -- routing p through a
+          // variable that DROP alone rescales swaps the two packed FMA pairs of the undropped kernel)
+          if constexpr (DROP) {
+            const float pm = p * group_bcast<L, u>(mult);
+            o_c.x = fmaf(o_c.x, sc, pm * xv.x); o_c.y = fmaf(o_c.y, sc, pm * xv.y);
+            o_c.z = fmaf(o_c.z, sc, pm * xv.z); o_c.w = fmaf(o_c.w, sc, pm * xv.w);
+          } else {
+            o_c.x = fmaf(o_c.x, sc, p * xv.x); o_c.y = fmaf(o_c.y, sc, p * xv.y);
+            o_c.z = fmaf(o_c.z, sc, p * xv.z); o_c.w = fmaf(o_c.w, sc, p * xv.w);
+          }
           m_c = mx;
         });
         mc = mn; off_c = off_n;
@@ -340,9 +367,9 @@ __device__ __forceinline__ void attn_fwd_walk_body(const WalkView& s, const Attn
   pacer.report(s.dbg, t_start);
 }
 
-template <int L>
-__global__ __launch_bounds__(kWalkThreads, 3) void k_attn_fwd_walk_f32(WalkView s, AttnWalkArgs a) {
-  attn_fwd_walk_body<L>(s, a);
+template <int L, bool DROP = false>
+__global__ __launch_bounds__(kWalkThreads, 3) void k_attn_fwd_walk_f32(WalkView s, AttnWalkArgs a, AttnDropIf<DROP> dr) {
+  attn_fwd_walk_body<L, DROP>(s, a, dr);
 }
 
 // ---- merge of the shared rows' pieces (three tiny launches over 2 * bins records) ------------------------------

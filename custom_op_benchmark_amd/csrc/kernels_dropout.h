@@ -115,4 +115,47 @@ __global__ __launch_bounds__(kGenericBlock) void k_edge_dropout_mask(
   }
 }
 
+// y[eid[slot], k] = x[eid[slot], k] * m_{i j (head0 + k)} for the call's heads k < h over the row-major chunks (the
+// composed path of the fused attention op with dropout); x == y is allowed.  Lanes over (slot, Philox
+// block) pairs like k_edge_dropout_mask: the blocks are those the GLOBAL heads head0 .. head0 + h - 1 fall into, so a
+// head0 that is no multiple of 4 costs one more call per slot, not one per value.  A dropped value is written as 0
+// whatever x holds.
+template <typename T>
+__global__ __launch_bounds__(kGenericBlock) void k_attn_drop_apply(
+    const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ eid,
+    const i64* __restrict__ indices, const T* x, T* y, i64 n_chunks, i64 h, i64 head0, DropArgs<T> dr) {
+  const i64 c = generic_chunk_id();
+  if (c >= n_chunks) return;
+  const int lane = threadIdx.x & 63;
+  const i64 r = row[c];
+  const i64 j0 = indptr[c];
+  const i64 b0 = head0 >> 2;
+  const i64 nblk = ((head0 + h + 3) >> 2) - b0;
+  const i64 len = indptr[c + 1] - j0;
+  if (nblk == 1) {   // the call's heads share one Philox block (every head group of up to four aligned heads): no division
+    for (i64 s = lane; s < len; s += kWave) {
+      const i64 j = j0 + s;
+      const int bits = drop_keep4<T>((unsigned)r, (unsigned)indices[j], (unsigned)b0, dr);
+      const i64 base = eid[j] * h;
+#pragma unroll
+      for (int t = 0; t < 4; ++t) {
+        const i64 k = b0 * 4 + t - head0;
+        if (k >= 0 && k < h) y[base + k] = (bits >> t) & 1 ? x[base + k] * dr.scale : (T)0;
+      }
+    }
+    return;
+  }
+  const i64 items = len * nblk;
+  for (i64 it = lane; it < items; it += kWave) {
+    const i64 j = j0 + it / nblk, b = b0 + it % nblk;
+    const int bits = drop_keep4<T>((unsigned)r, (unsigned)indices[j], (unsigned)b, dr);
+    const i64 base = eid[j] * h;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+      const i64 k = b * 4 + t - head0;
+      if (k >= 0 && k < h) y[base + k] = (bits >> t) & 1 ? x[base + k] * dr.scale : (T)0;
+    }
+  }
+}
+
 }  // namespace graphop

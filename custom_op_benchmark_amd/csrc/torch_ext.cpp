@@ -359,14 +359,30 @@ std::vector<at::Tensor> vector_spmm_backward(const at::Tensor& row, const at::Te
   return {dedata, dx};   // graphop_kernel.cu:599
 }
 
+// (p, seed, offset) of the dropout forms, checked as include/graphop_hip.h states them
+struct DropSpec {
+  double p;
+  uint64_t seed;
+  uint32_t offset;
+};
+
+DropSpec drop_spec(const char* fn, double p, int64_t seed, int64_t offset) {
+  TORCH_CHECK(p >= 0.0 && p < 1.0, fn, ": dropout probability p must be in [0, 1), got ", p);
+  TORCH_CHECK(seed >= 0, fn, ": seed must be in [0, 2^63), got ", seed);
+  TORCH_CHECK(offset >= 0 && offset < (int64_t(1) << 32), fn, ": offset must be in [0, 2^32), got ", offset);
+  return {p, (uint64_t)seed, (uint32_t)offset};
+}
+
 // ---- the extra fused op (include/graphop_hip.h: graphop_attention_*) ------------------------------
-std::vector<at::Tensor> attention_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
-                                          const at::Tensor& indices, const at::Tensor& Q, const at::Tensor& K,
-                                          const at::Tensor& V) {
+// drop == nullptr: graphop_attention_forward, else its dropout form for the heads head0 .. head0 + h - 1, as `fn`
+std::vector<at::Tensor> attention_forward_impl(const char* fn, const at::Tensor& row, const at::Tensor& indptr,
+                                               const at::Tensor& eid, const at::Tensor& indices, const at::Tensor& Q,
+                                               const at::Tensor& K, const at::Tensor& V, const DropSpec* drop,
+                                               int64_t head0) {
   CHECK_CSR(row, indptr, eid, indices);
   CHECK_INPUT(Q); CHECK_INPUT(K); CHECK_INPUT(V);
   TORCH_CHECK(K.sizes() == V.sizes() && Q.sizes().slice(1) == K.sizes().slice(1),
-              "attention_forward: Q (n_q,[h,]d), K and V (n_k,[h,]d) expected");
+              fn, ": Q (n_q,[h,]d), K and V (n_k,[h,]d) expected");
   CHECK_SAME_DTYPE(Q, K); CHECK_SAME_DTYPE(Q, V);
   DeviceGuard dg(Q);
   const int64_t e = eid.size(0), d = Q.size(-1), h = Q.dim() == 2 ? 1 : Q.size(1), n_q = Q.size(0), n_k = K.size(0);
@@ -375,19 +391,48 @@ std::vector<at::Tensor> attention_forward(const at::Tensor& row, const at::Tenso
   const auto pp = get_plan(row, indptr, eid, indices, n_k);
   const auto& p = *pp;
   int64_t nbytes = 0;
-  check(graphop_attention_workspace_bytes(dtype_code(Q), 0, e, n_q, n_k, h, d, p.plan, nullptr, stream_of(Q), &nbytes));
+  check((drop ? graphop_attention_dropout_workspace_bytes : graphop_attention_workspace_bytes)(
+      dtype_code(Q), 0, e, n_q, n_k, h, d, p.plan, nullptr, stream_of(Q), &nbytes));
   auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, Q.options().dtype(at::kByte));
-  check(graphop_attention_forward(dtype_code(Q), ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(V), vp(o),
-                                  vp(stats), row.size(0), e, n_q, n_k, h, d, ws.data_ptr(), nbytes, p.plan, stream_of(Q)));
+  if (drop)
+    check(graphop_attention_dropout_forward(dtype_code(Q), ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(V),
+                                            vp(o), vp(stats), row.size(0), e, n_q, n_k, h, d, ws.data_ptr(), nbytes,
+                                            p.plan, stream_of(Q), drop->p, drop->seed, drop->offset, head0));
+  else
+    check(graphop_attention_forward(dtype_code(Q), ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(V), vp(o),
+                                    vp(stats), row.size(0), e, n_q, n_k, h, d, ws.data_ptr(), nbytes, p.plan, stream_of(Q)));
   return {o, stats};
 }
 
-std::vector<at::Tensor> attention_backward(const at::Tensor& row, const at::Tensor& indptr_r, const at::Tensor& eid_r,
-                                           const at::Tensor& indices_r, const at::Tensor& col,
-                                           const at::Tensor& indptr_c, const at::Tensor& eid_c,
-                                           const at::Tensor& indices_c, const at::Tensor& Q, const at::Tensor& K,
-                                           const at::Tensor& V, const at::Tensor& o, const at::Tensor& stats,
-                                           const at::Tensor& dO_) {
+std::vector<at::Tensor> attention_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
+                                          const at::Tensor& indices, const at::Tensor& Q, const at::Tensor& K,
+                                          const at::Tensor& V) {
+  return attention_forward_impl("attention_forward", row, indptr, eid, indices, Q, K, V, nullptr, 0);
+}
+
+// head0 of the dropout forms: the global index of the call's first head
+int64_t head0_checked(const char* fn, int64_t head0) {
+  TORCH_CHECK(head0 >= 0 && head0 < (int64_t(1) << 32), fn, ": head0 must be in [0, 2^32), got ", head0);
+  return head0;
+}
+
+std::vector<at::Tensor> attention_dropout_forward(const at::Tensor& row, const at::Tensor& indptr,
+                                                  const at::Tensor& eid, const at::Tensor& indices, const at::Tensor& Q,
+                                                  const at::Tensor& K, const at::Tensor& V, double p, int64_t seed,
+                                                  int64_t offset, int64_t head0) {
+  const char* fn = "attention_dropout_forward";
+  const DropSpec drop = drop_spec(fn, p, seed, offset);
+  return attention_forward_impl(fn, row, indptr, eid, indices, Q, K, V, &drop, head0_checked(fn, head0));
+}
+
+// drop == nullptr: graphop_attention_backward, else its dropout form, as `fn`
+std::vector<at::Tensor> attention_backward_impl(const char* fn, const at::Tensor& row, const at::Tensor& indptr_r,
+                                                const at::Tensor& eid_r, const at::Tensor& indices_r,
+                                                const at::Tensor& col, const at::Tensor& indptr_c,
+                                                const at::Tensor& eid_c, const at::Tensor& indices_c,
+                                                const at::Tensor& Q, const at::Tensor& K, const at::Tensor& V,
+                                                const at::Tensor& o, const at::Tensor& stats, const at::Tensor& dO_,
+                                                const DropSpec* drop, int64_t head0) {
   CHECK_CSR(row, indptr_r, eid_r, indices_r);
   CHECK_CSR(col, indptr_c, eid_c, indices_c);
   CHECK_INPUT(Q); CHECK_INPUT(K); CHECK_INPUT(V); CHECK_INPUT(o); CHECK_INPUT(stats);
@@ -395,23 +440,53 @@ std::vector<at::Tensor> attention_backward(const at::Tensor& row, const at::Tens
   const at::Tensor dO = dO_.contiguous();
   CHECK_SAME_DTYPE(Q, K); CHECK_SAME_DTYPE(Q, V); CHECK_SAME_DTYPE(Q, o); CHECK_SAME_DTYPE(Q, stats); CHECK_SAME_DTYPE(Q, dO);
   TORCH_CHECK(K.sizes() == V.sizes() && Q.sizes().slice(1) == K.sizes().slice(1),
-              "attention_backward: Q (n_q,[h,]d), K and V (n_k,[h,]d) expected");
+              fn, ": Q (n_q,[h,]d), K and V (n_k,[h,]d) expected");
   DeviceGuard dg(Q);
   const int64_t e = eid_r.size(0), d = Q.size(-1), h = Q.dim() == 2 ? 1 : Q.size(1), n_q = Q.size(0), n_k = K.size(0);
   TORCH_CHECK(o.sizes() == Q.sizes() && dO.sizes() == Q.sizes() && stats.numel() == n_q * h * 2,
-              "attention_backward: o, dO must match Q and stats must be (n_q, h, 2)");
+              fn, ": o, dO must match Q and stats must be (n_q, h, 2)");
   auto dQ = at::empty_like(Q), dK = at::empty_like(K), dV = at::empty_like(V);
   const auto ppr = get_plan(row, indptr_r, eid_r, indices_r, n_k);
   const auto ppc = get_plan(col, indptr_c, eid_c, indices_c, n_q);
   const auto &pr = *ppr, &pc = *ppc;
   int64_t nbytes = 0;
-  check(graphop_attention_workspace_bytes(dtype_code(Q), 1, e, n_q, n_k, h, d, pr.plan, pc.plan, stream_of(Q), &nbytes));
+  check((drop ? graphop_attention_dropout_workspace_bytes : graphop_attention_workspace_bytes)(
+      dtype_code(Q), 1, e, n_q, n_k, h, d, pr.plan, pc.plan, stream_of(Q), &nbytes));
   auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, Q.options().dtype(at::kByte));
-  check(graphop_attention_backward(dtype_code(Q), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c),
-                                   ip(eid_c), ip(indices_c), vp(Q), vp(K), vp(V), vp(o), vp(stats), vp(dO), vp(dQ),
-                                   vp(dK), vp(dV), row.size(0), col.size(0), e, n_q, n_k, h, d, ws.data_ptr(), nbytes,
-                                   pr.plan, pc.plan, stream_of(Q)));
+  if (drop)
+    check(graphop_attention_dropout_backward(
+        dtype_code(Q), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c), ip(indices_c),
+        vp(Q), vp(K), vp(V), vp(o), vp(stats), vp(dO), vp(dQ), vp(dK), vp(dV), row.size(0), col.size(0), e, n_q, n_k, h, d,
+        ws.data_ptr(), nbytes, pr.plan, pc.plan, stream_of(Q), drop->p, drop->seed, drop->offset, head0));
+  else
+    check(graphop_attention_backward(dtype_code(Q), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c),
+                                     ip(eid_c), ip(indices_c), vp(Q), vp(K), vp(V), vp(o), vp(stats), vp(dO), vp(dQ),
+                                     vp(dK), vp(dV), row.size(0), col.size(0), e, n_q, n_k, h, d, ws.data_ptr(), nbytes,
+                                     pr.plan, pc.plan, stream_of(Q)));
   return {dQ, dK, dV};
+}
+
+std::vector<at::Tensor> attention_backward(const at::Tensor& row, const at::Tensor& indptr_r, const at::Tensor& eid_r,
+                                           const at::Tensor& indices_r, const at::Tensor& col,
+                                           const at::Tensor& indptr_c, const at::Tensor& eid_c,
+                                           const at::Tensor& indices_c, const at::Tensor& Q, const at::Tensor& K,
+                                           const at::Tensor& V, const at::Tensor& o, const at::Tensor& stats,
+                                           const at::Tensor& dO) {
+  return attention_backward_impl("attention_backward", row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c,
+                                 Q, K, V, o, stats, dO, nullptr, 0);
+}
+
+std::vector<at::Tensor> attention_dropout_backward(const at::Tensor& row, const at::Tensor& indptr_r,
+                                                   const at::Tensor& eid_r, const at::Tensor& indices_r,
+                                                   const at::Tensor& col, const at::Tensor& indptr_c,
+                                                   const at::Tensor& eid_c, const at::Tensor& indices_c,
+                                                   const at::Tensor& Q, const at::Tensor& K, const at::Tensor& V,
+                                                   const at::Tensor& o, const at::Tensor& stats, const at::Tensor& dO,
+                                                   double p, int64_t seed, int64_t offset, int64_t head0) {
+  const char* fn = "attention_dropout_backward";
+  const DropSpec drop = drop_spec(fn, p, seed, offset);
+  return attention_backward_impl(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, o, stats,
+                                 dO, &drop, head0_checked(fn, head0));
 }
 
 // ---- the extra GAT score op (include/graphop_hip.h: graphop_gat_scores_*) ---------------------------------
@@ -526,20 +601,6 @@ std::vector<at::Tensor> gatv2_scores_backward(const at::Tensor& row, const at::T
                                       col.size(0), e, xl.size(0), xr.size(0), h, d, negative_slope, pr.plan, pc.plan,
                                       stream_of(xl)));
   return {dxl, dxr, datt};
-}
-
-// (p, seed, offset) of the dropout forms, checked as include/graphop_hip.h states them
-struct DropSpec {
-  double p;
-  uint64_t seed;
-  uint32_t offset;
-};
-
-DropSpec drop_spec(const char* fn, double p, int64_t seed, int64_t offset) {
-  TORCH_CHECK(p >= 0.0 && p < 1.0, fn, ": dropout probability p must be in [0, 1), got ", p);
-  TORCH_CHECK(seed >= 0, fn, ": seed must be in [0, 2^63), got ", seed);
-  TORCH_CHECK(offset >= 0 && offset < (int64_t(1) << 32), fn, ": offset must be in [0, 2^32), got ", offset);
-  return {p, (uint64_t)seed, (uint32_t)offset};
 }
 
 // ---- the fused GATv2 attention op (include/graphop_hip.h: graphop_gatv2_attention_*) ------------------------------
@@ -923,6 +984,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("vector_spmm_backward", &vector_spmm_backward, "Vectorized SPMM backward");
   m.def("attention_forward", &attention_forward, "Fused SDDMM -> softmax -> SpMM forward (extra op)");
   m.def("attention_backward", &attention_backward, "Fused attention backward (extra op)");
+  // (the dropout form of the fused step is bound here and by ctypes; it is not in the torch.ops.graphop table below)
+  m.def("attention_dropout_forward", &attention_dropout_forward,
+        "Fused attention forward with attention dropout (extra op)", py::arg("row"), py::arg("indptr"), py::arg("eid"),
+        py::arg("indices"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("p") = 0.0, py::arg("seed") = 0,
+        py::arg("offset") = 0, py::arg("head0") = 0);
+  m.def("attention_dropout_backward", &attention_dropout_backward,
+        "Fused attention backward with attention dropout (extra op)", py::arg("row"), py::arg("indptr_r"),
+        py::arg("eid_r"), py::arg("indices_r"), py::arg("col"), py::arg("indptr_c"), py::arg("eid_c"),
+        py::arg("indices_c"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("o"), py::arg("stats"), py::arg("dO"),
+        py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0, py::arg("head0") = 0);
   m.def("gat_scores_forward", &gat_scores_forward, "GAT additive attention scores forward (extra op)", py::arg("row"),
         py::arg("indptr"), py::arg("eid"), py::arg("indices"), py::arg("el"), py::arg("er"), py::arg("negative_slope") = 0.2);
   m.def("gat_scores_backward", &gat_scores_backward, "GAT additive attention scores backward (extra op)", py::arg("row"),

@@ -305,20 +305,7 @@ class FusedAttention(Function):
         hg = _head_group(h, Q.size(-1), eid_r.numel(), max(Q.size(0), K.size(0))) if h > 1 else 1
         ctx.groups = None
         if h > 1 and hg < h:
-            import os
-            mode = os.environ.get("GRAPHOP_FUSED_HEADS", FUSED_HEADS_MODE)
-            ctx.groups = (h, hg, mode)
-            o = Q.new_empty((Q.size(0),) + tuple(V.shape[1:]))
-            kept = []
-            for g0 in range(0, h, hg):
-                Qg, Kg, Vg = (_head_slice(x, g0, hg) for x in (Q, K, V))
-                og, keep = _group_forward(a8, Qg, Kg, Vg, mode)
-                _head_store(o, og, g0, hg)
-                kept.append(keep)
-                del Qg, Kg, Vg, og
-            ctx.kept = kept               # per group: ("fused", o_g, stats_g) | ("keep", a_g) | ("recompute",)
-            ctx.save_for_backward(*a8, Q, K, V)
-            return o
+            return _groups_forward(ctx, a8, Q, K, V, h, hg)
         ctx.fused = _ops.attention_backward_is_fused(*a8, Q, K)
         if ctx.fused:
             o, stats = _ops.attention_forward(row, indptr_r, eid_r, indices_r, Q, K, V)
@@ -340,16 +327,7 @@ class FusedAttention(Function):
         a8, rest = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
         row, indptr_r, eid_r = a8[:3]
         if ctx.groups is not None:
-            h, hg, mode = ctx.groups
-            Q, K, V = rest
-            dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
-            for gi, g0 in enumerate(range(0, h, hg)):
-                Qg, Kg, Vg, dOg = (_head_slice(x, g0, hg) for x in (Q, K, V, dO))
-                dQg, dKg, dVg = _group_backward(a8, Qg, Kg, Vg, dOg, ctx.kept[gi])
-                for full, part in ((dQ, dQg), (dK, dKg), (dV, dVg)):
-                    _head_store(full, part, g0, hg)
-                del Qg, Kg, Vg, dOg, dQg, dKg, dVg
-            return None, None, None, None, None, None, None, None, dQ, dK, dV
+            return (None,) * 8 + _groups_backward(ctx, a8, *rest, dO)
         if ctx.fused:
             Q, K, V, o, stats = rest
             dQ, dK, dV = _ops.attention_backward(*a8, Q, K, V, o, stats, dO)
@@ -360,6 +338,49 @@ class FusedAttention(Function):
             del da
             dQ, dK = _ops.maskedmm_csr_backward(*a8, Q, K, ds)
         return None, None, None, None, None, None, None, None, dQ, dK, dV
+
+
+class FusedAttentionDropout(Function):
+    """FusedAttention with dropout on the attention weights, o[i] = sum_j softmax_j(<Q_i, K_j>) m_ij V[j] (extra op;
+    TransformerConv(dropout=...), DotGatConv):
+    apply(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, p, seed, offset).
+    m_ij = keep / (1 - p) is the multiplier of FusedGATAttentionDropout (i indexes Q, j indexes K / V; head k of a
+    several-head call is head k of graphop.edge_dropout_mask), recomputed per slot by forward and backward: no (E, h)
+    mask, and nothing else edge-sized, is kept between them.  Saves (Q, K, V, o, row statistics).  There is no
+    1 / sqrt(d) scale argument: fold it into Q.  seed=None draws one from torch's default CPU generator; offset is a
+    per-layer / per-step counter.  p = 0 is FusedAttention itself.
+    Several heads run in FusedAttention's head groups (_head_group) and each group's call names its first head, so a
+    grouped call makes the decisions of an ungrouped one.  FUSED_HEADS_MODE is honoured as far as it can be: a group the
+    fused kernels do not take recomputes s and a in the backward in both modes (keeping a would not spare the mask)."""
+
+    @staticmethod
+    def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, p, seed=None, offset=0):
+        a8 = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
+        ctx.drop = None
+        if float(p) == 0.0:
+            return FusedAttention.forward(ctx, *a8, Q, K, V)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        ctx.drop = (float(p), int(seed), int(offset))
+        h = Q.size(1) if Q.dim() == 3 else 1
+        hg = _head_group(h, Q.size(-1), eid_r.numel(), max(Q.size(0), K.size(0))) if h > 1 else 1
+        ctx.groups = None
+        if h > 1 and hg < h:
+            return _groups_forward(ctx, a8, Q, K, V, h, hg, ctx.drop)
+        o, stats = _ops.attention_dropout_forward(row, indptr_r, eid_r, indices_r, Q, K, V, *ctx.drop, 0)
+        ctx.save_for_backward(*a8, Q, K, V, o, stats)
+        return o
+
+    @staticmethod
+    def backward(ctx, dO):
+        if ctx.drop is None:
+            return FusedAttention.backward(ctx, dO) + (None, None, None)
+        a8, rest = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
+        if ctx.groups is not None:
+            return (None,) * 8 + _groups_backward(ctx, a8, *rest, dO, ctx.drop) + (None, None, None)
+        Q, K, V, o, stats = rest
+        dQ, dK, dV = _ops.attention_dropout_backward(*a8, Q, K, V, o, stats, dO, *ctx.drop, 0)
+        return (None,) * 8 + (dQ, dK, dV, None, None, None)
 
 
 def _head_slice(x, g0, hg):
@@ -374,8 +395,45 @@ def _head_store(full, part, g0, hg):
     full[:, g0:g0 + hg, :].copy_(part[:full.size(0)].reshape(full.size(0), hg, full.size(2)))
 
 
-def _group_forward(a8, Qg, Kg, Vg, mode):
+def _groups_forward(ctx, a8, Q, K, V, h, hg, drop=None):
+    """The head-group loop of FusedAttention and FusedAttentionDropout (drop = (p, seed, offset)): each group through
+    _group_forward, its o written into the heads' slice; ctx keeps what the groups' backwards need."""
+    import os
+    mode = os.environ.get("GRAPHOP_FUSED_HEADS", FUSED_HEADS_MODE)
+    ctx.groups = (h, hg, mode)
+    o = Q.new_empty((Q.size(0),) + tuple(V.shape[1:]))
+    kept = []
+    for g0 in range(0, h, hg):
+        Qg, Kg, Vg = (_head_slice(x, g0, hg) for x in (Q, K, V))
+        og, keep = _group_forward(a8, Qg, Kg, Vg, mode, drop, g0)
+        _head_store(o, og, g0, hg)
+        kept.append(keep)
+        del Qg, Kg, Vg, og
+    ctx.kept = kept               # per group: ("fused", o_g, stats_g) | ("keep", a_g) | ("recompute",) | ("drop", o_g, stats_g)
+    ctx.save_for_backward(*a8, Q, K, V)
+    return o
+
+
+def _groups_backward(ctx, a8, Q, K, V, dO, drop=None):
+    """-> (dQ, dK, dV) of _groups_forward"""
+    h, hg, mode = ctx.groups
+    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+    for gi, g0 in enumerate(range(0, h, hg)):
+        Qg, Kg, Vg, dOg = (_head_slice(x, g0, hg) for x in (Q, K, V, dO))
+        dQg, dKg, dVg = _group_backward(a8, Qg, Kg, Vg, dOg, ctx.kept[gi], drop, g0)
+        for full, part in ((dQ, dQg), (dK, dKg), (dV, dVg)):
+            _head_store(full, part, g0, hg)
+        del Qg, Kg, Vg, dOg, dQg, dKg, dVg
+    return dQ, dK, dV
+
+
+def _group_forward(a8, Qg, Kg, Vg, mode, drop=None, head0=0):
+    """One head group's forward -> (o_g, what its backward needs).  drop = (p, seed, offset) with p > 0: the group through
+    attention_dropout_forward as the heads head0 .. head0 + hg - 1 of the whole call."""
     row, indptr_r, eid_r, indices_r = a8[:4]
+    if drop is not None:
+        og, stats = _ops.attention_dropout_forward(row, indptr_r, eid_r, indices_r, Qg, Kg, Vg, *drop, head0)
+        return og, ("drop", og, stats)
     if _ops.attention_backward_is_fused(*a8, Qg, Kg):
         og, stats = _ops.attention_forward(row, indptr_r, eid_r, indices_r, Qg, Kg, Vg)
         return og, ("fused", og, stats)
@@ -386,8 +444,10 @@ def _group_forward(a8, Qg, Kg, Vg, mode):
     return og, (("keep", a) if mode != "recompute" else ("recompute",))
 
 
-def _group_backward(a8, Qg, Kg, Vg, dOg, kept):
+def _group_backward(a8, Qg, Kg, Vg, dOg, kept, drop=None, head0=0):
     row, indptr_r, eid_r, indices_r = a8[:4]
+    if kept[0] == "drop":
+        return _ops.attention_dropout_backward(*a8, Qg, Kg, Vg, kept[1], kept[2], dOg, *drop, head0)
     if kept[0] == "fused":
         return _ops.attention_backward(*a8, Qg, Kg, Vg, kept[1], kept[2], dOg)
     if kept[0] == "keep":
@@ -409,6 +469,31 @@ def fused_attention_step(g, Q, K, V, dO):
     o.backward(dO)
     _lib.check_errors(sync=False)     # as in attention_step
     return o
+
+
+def fused_attention_dropout_step(g, Q, K, V, dO, p, seed, offset=0):
+    """fused_attention_step with dropout on the attention weights, through FusedAttentionDropout; returns o (no E-sized
+    tensor is kept, the mask included)."""
+    o = FusedAttentionDropout.apply(*g.csr_args(), Q, K, V, p, seed, offset)
+    o.backward(dO)
+    _lib.check_errors(sync=False)     # as in attention_step
+    return o
+
+
+def attention_dropout_step(g, Q, K, V, dO, p, seed, offset=0):
+    """attention_step with dropout on the attention weights, composed: MaskedMMCSR -> SparseSoftmax ->
+    (* edge_dropout_mask) -> VectorSPMM; a, the mask and their product are (E, h) tensors kept for the backward.  Same
+    decisions as fused_attention_dropout_step for the same (p, seed, offset); returns (s, a, o) with a the undropped
+    weights."""
+    args = g.csr_args()
+    s = MaskedMMCSR.apply(*args, Q, K)
+    a = SparseSoftmax.apply(g.row, g.ptr_r, g.eid_r, s)
+    h = 1 if Q.dim() == 2 else Q.size(1)
+    mask = _ops.edge_dropout_mask(g.row, g.ptr_r, g.eid_r, g.indices_r, h, p, seed, offset, a.dtype)
+    o = VectorSPMM.apply(*args, a * mask, V)
+    o.backward(dO)
+    _lib.check_errors(sync=False)     # as in attention_step
+    return s, a, o
 
 
 def attention_step(g, Q, K, V, dO):

@@ -27,7 +27,8 @@ from ._lib import check, dtype_code, get_plan, lib, ptr, stream_of
 __all__ = ["maskedmm_csr_forward", "maskedmm_csr_backward", "node_mul_edge_forward",
            "node_mul_edge_backward", "sparse_softmax_forward", "sparse_softmax_backward",
            "vector_spmm_forward", "vector_spmm_backward"]
-# extra ops (not in the reference's module): the fused attention step, SURVEY.md 8f N2
+# extra ops (not in the reference's module): the fused attention step, SURVEY.md 8f N2, and its form with attention
+# dropout (attention_dropout_forward / _backward),
 # the GAT additive attention scores (LeakyReLU(el[i] + er[j]) per edge and head), the fused GAT attention layer and
 # its forms with attention dropout (plus the mask they apply, as an edge tensor, for the composed path), and the GATv2
 # scores (att . LeakyReLU(xl[i] + xr[j]) per edge and head), and the fused GAT layer with a per-edge score term
@@ -253,10 +254,11 @@ def node_mul_edge_backward(row, indptr, eid, A, B, dy):
 
 
 # ---- fused attention step (extra op; the composition wrapper.py:20-30, 8-18, 44-55) ------------------
-def _workspace(like, dtype, backward, e, n_q, n_k, h, d, plan_r, plan_c):
+def _workspace(like, dtype, backward, e, n_q, n_k, h, d, plan_r, plan_c, dropout=False):
     import ctypes
     nbytes = ctypes.c_int64(0)
-    check(lib().graphop_attention_workspace_bytes(
+    query = lib().graphop_attention_dropout_workspace_bytes if dropout else lib().graphop_attention_workspace_bytes
+    check(query(
         dtype, 1 if backward else 0, e, n_q, n_k, h, d, plan_r.handle if plan_r is not None else _NULL,
         plan_c.handle if plan_c is not None else _NULL, stream_of(like), ctypes.byref(nbytes)))
     return torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=like.device), nbytes.value
@@ -278,15 +280,13 @@ def attention_backward_is_fused(row, indptr_r, eid_r, indices_r, col, indptr_c, 
     return bool(out.value)
 
 
-def attention_forward(row, indptr, eid, indices, Q, K, V):
-    """-> [o, stats]: o = vector_spmm(sparse_softmax(maskedmm_csr(Q, K)), V) over the row-major CSR,
-    without returning the E-sized s / a.  stats (n_q, h, 2) = (row max, 1 / sum exp) is what
-    attention_backward needs to recompute them."""
+def _attention_forward(fn, row, indptr, eid, indices, Q, K, V, drop=()):
+    """attention_forward (drop = ()) or attention_dropout_forward (drop = (p, seed, offset, head0)) as `fn`"""
     _check_csr((row, indptr, eid, indices), _CSR, (Q, "Q"), (K, "K"), (V, "V"))
     _same_dtype(Q, K, "Q", "K")
     _same_dtype(Q, V, "Q", "V")
     if K.shape != V.shape or Q.shape[1:] != K.shape[1:]:
-        raise RuntimeError("attention_forward: Q (n_q,[h,]d), K and V (n_k,[h,]d) expected")
+        raise RuntimeError("%s: Q (n_q,[h,]d), K and V (n_k,[h,]d) expected" % fn)
     e, d = eid.size(0), Q.size(-1)
     h = 1 if Q.dim() == 2 else Q.size(1)
     n_q, n_k = Q.size(0), K.size(0)
@@ -294,17 +294,24 @@ def attention_forward(row, indptr, eid, indices, Q, K, V):
     stats = torch.empty((n_q, h, 2), dtype=Q.dtype, device=Q.device)
     with _lib.device_guard(Q.device):
         plan = get_plan(row, indptr, eid, indices, n_k)
-        ws, nbytes = _workspace(Q, dtype_code(Q), False, e, n_q, n_k, h, d, plan, None)
-        check(lib().graphop_attention_forward(
+        ws, nbytes = _workspace(Q, dtype_code(Q), False, e, n_q, n_k, h, d, plan, None, bool(drop))
+        check(getattr(lib(), "graphop_" + fn)(
             dtype_code(Q), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(Q), ptr(K), ptr(V),
             ptr(o), ptr(stats), row.size(0), e, n_q, n_k, h, d, ptr(ws), nbytes, plan.handle,
-            stream_of(Q)))
+            stream_of(Q), *drop))
     return [o, stats]
 
 
-def attention_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c,
-                       Q, K, V, o, stats, dO):
-    """-> [dQ, dK, dV] of the fused step for the output gradient dO."""
+def attention_forward(row, indptr, eid, indices, Q, K, V):
+    """-> [o, stats]: o = vector_spmm(sparse_softmax(maskedmm_csr(Q, K)), V) over the row-major CSR,
+    without returning the E-sized s / a.  stats (n_q, h, 2) = (row max, 1 / sum exp) is what
+    attention_backward needs to recompute them."""
+    return _attention_forward("attention_forward", row, indptr, eid, indices, Q, K, V)
+
+
+def _attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c,
+                        Q, K, V, o, stats, dO, drop=()):
+    """attention_backward (drop = ()) or attention_dropout_backward (drop = (p, seed, offset, head0)) as `fn`"""
     _check_csr((row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c), _CSR_RC,
                (Q, "Q"), (K, "K"), (V, "V"), (o, "o"), (stats, "stats"))
     _check_grad(dO, "dO")
@@ -315,18 +322,25 @@ def attention_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, in
     h = 1 if Q.dim() == 2 else Q.size(1)
     n_q, n_k = Q.size(0), K.size(0)
     if o.shape != Q.shape or dO.shape != Q.shape or stats.numel() != n_q * h * 2:
-        raise RuntimeError("attention_backward: o, dO must match Q and stats must be (n_q, h, 2)")
+        raise RuntimeError("%s: o, dO must match Q and stats must be (n_q, h, 2)" % fn)
     dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
     with _lib.device_guard(Q.device):
         plan_r = get_plan(row, indptr_r, eid_r, indices_r, n_k)
         plan_c = get_plan(col, indptr_c, eid_c, indices_c, n_q)
-        ws, nbytes = _workspace(Q, dtype_code(Q), True, e, n_q, n_k, h, d, plan_r, plan_c)
-        check(lib().graphop_attention_backward(
+        ws, nbytes = _workspace(Q, dtype_code(Q), True, e, n_q, n_k, h, d, plan_r, plan_c, bool(drop))
+        check(getattr(lib(), "graphop_" + fn)(
             dtype_code(Q), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col),
             ptr(indptr_c), ptr(eid_c), ptr(indices_c), ptr(Q), ptr(K), ptr(V), ptr(o), ptr(stats),
             ptr(dO), ptr(dQ), ptr(dK), ptr(dV), row.size(0), col.size(0), e, n_q, n_k, h, d,
-            ptr(ws), nbytes, plan_r.handle, plan_c.handle, stream_of(Q)))
+            ptr(ws), nbytes, plan_r.handle, plan_c.handle, stream_of(Q), *drop))
     return [dQ, dK, dV]
+
+
+def attention_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c,
+                       Q, K, V, o, stats, dO):
+    """-> [dQ, dK, dV] of the fused step for the output gradient dO."""
+    return _attention_backward("attention_backward", row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c,
+                               Q, K, V, o, stats, dO)
 
 
 # ---- GAT additive attention scores (extra op) ------------------------------------------------------------
@@ -691,6 +705,33 @@ def edge_dropout_mask(row, indptr, eid, indices, h, p, seed, offset=0, dtype=tor
     return y
 
 
+# ---- attention dropout of the fused attention step (extra ops) -----------------------------------------------------
+def _head0(fn, head0):
+    head0 = int(head0)
+    if not 0 <= head0 < 2 ** 32:
+        raise RuntimeError("%s: head0 must be in [0, 2^32), got %d" % (fn, head0))
+    return head0
+
+
+def attention_dropout_forward(row, indptr, eid, indices, Q, K, V, p=0.0, seed=0, offset=0, head0=0):
+    """-> [o, stats] of attention_forward with dropout on the attention weights: o[i] = sum_j a_ij m_ij V[j], m_ij the
+    multiplier of edge_dropout_mask (i indexes Q, j indexes K / V) recomputed per slot, so no edge-sized mask exists;
+    stats are those of the undropped scores.  head0 is the global index of the call's first head: head k of this call
+    decides as head head0 + k of edge_dropout_mask (the head groups of FusedAttentionDropout pass their first head).
+    p = 0 is attention_forward bit for bit.  There is no 1 / sqrt(d) scale argument: fold it into Q."""
+    fn = "attention_dropout_forward"
+    return _attention_forward(fn, row, indptr, eid, indices, Q, K, V, _drop_args(fn, p, seed, offset) + (_head0(fn, head0),))
+
+
+def attention_dropout_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, o, stats, dO,
+                               p=0.0, seed=0, offset=0, head0=0):
+    """-> [dQ, dK, dV] of attention_dropout_forward for the output gradient dO, with the same (p, seed, offset, head0):
+    the weights and their keep decisions are recomputed per slot."""
+    fn = "attention_dropout_backward"
+    return _attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, o, stats,
+                               dO, _drop_args(fn, p, seed, offset) + (_head0(fn, head0),))
+
+
 # ---- fused GAT attention with an edge term (extra ops) -----------------------------------------------------------
 def _gat_edge_term(el, ee, n_edges, h, fn):
     """ee checked against the graph and the heads: (n_edges) for 1-D el / er, else (n_edges, h), in el's dtype."""
@@ -764,7 +805,10 @@ _SCHEMAS = {
     "gat_edge_attention_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor ee, Tensor V, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0, bool need_dee=True) -> Tensor[]",
 }
 # every op beyond the reference's eight, plus the one query that is not an op
-EXTRA_OPS = [n for n in _SCHEMAS if n not in __all__] + ["attention_backward_is_fused"]
+# ... and the dropout form of the fused attention step: bound here and in the compiled extension, not registered under
+# torch.ops.graphop (the registered set is the table above)
+EXTRA_OPS = [n for n in _SCHEMAS if n not in __all__] + ["attention_backward_is_fused", "attention_dropout_forward",
+                                                         "attention_dropout_backward"]
 _torch_lib = None
 
 

@@ -684,6 +684,44 @@ GRAPHOP_API int graphop_attention_backward(int dtype, const int64_t* row, const 
                                int64_t workspace_bytes, const graphop_plan_t* plan_r,
                                const graphop_plan_t* plan_c, void* stream);
 
+/* ---- attention dropout for the fused attention step (ABI 8, additive; EXTRA ops) ------------------------------------
+ * The fused step with dropout on the attention weights, attn_drop(softmax(Q K^T)) (TransformerConv(dropout=...),
+ * DotGatConv), still without any E-sized mask.  For edge (i, j) -- i indexes Q / o, j indexes K / V -- and GLOBAL head k
+ * the multiplier is that of the fused GAT layer, unchanged: m_ijk = keep ? 1 / (1 - p) : 0 with keep from
+ * Philox4x32-10 on the counter (i, j, k >> 2, offset) and the key seed (graphop_edge_dropout_mask writes the same values
+ * out).  Parallel edges share one decision.
+ *   forward : o[i] = sum_j a_ij m_ij V[j]; stats are those of the undropped scores (as graphop_attention_forward)
+ *   backward: D_i = <dO_i, o_i>, da_ij = m_ij <dO_i, V_j>, ds_ij = a_ij (da_ij - D_i);
+ *             dQ_i = sum_j ds_ij K_j, dK_j = sum_i ds_ij Q_i, dV_j = sum_i a_ij m_ij dO_i
+ * A row whose edges are all dropped has o = 0 and dQ = 0 and adds nothing to dK or dV.
+ * Arguments as graphop_attention_forward / _backward, then (p, seed, offset, head0) after the stream:
+ *   0 <= p < 1, seed < 2^63, n_q and n_k < 2^32 (GRAPHOP_ERR_ARG otherwise).  head0 is the global index of the call's
+ *   first head: local head k decides as global head head0 + k, so a caller that hands over one group of heads at a time
+ *   makes the decisions of one call over all heads.  p == 0 runs the kernels of graphop_attention_forward / _backward
+ *   (bit-identical results).  There is no 1 / sqrt(d) scale argument: fold it into Q.
+ * The fused forms (one-pass forward, window-owner and chunk-driver backward) are chosen by the rules of the undropped
+ * op and recompute the decision per slot; everything else composes the unfused entry points and multiplies a (and the
+ * gradient that comes back) by m in the workspace.  workspace: graphop_attention_dropout_workspace_bytes(...) bytes --
+ * the composed backward holds one E-sized array more (a * m) than graphop_attention_workspace_bytes reports. */
+GRAPHOP_API int graphop_attention_dropout_workspace_bytes(int dtype, int backward, int64_t n_edges, int64_t n_q,
+                                              int64_t n_k, int64_t h, int64_t d, const graphop_plan_t* plan_r,
+                                              const graphop_plan_t* plan_c, void* stream, int64_t* bytes_out);
+GRAPHOP_API int graphop_attention_dropout_forward(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                                      const int64_t* indices, const void* Q, const void* K, const void* V, void* o,
+                                      void* stats, int64_t n_chunks, int64_t n_edges, int64_t n_q, int64_t n_k,
+                                      int64_t h, int64_t d, void* workspace, int64_t workspace_bytes,
+                                      const graphop_plan_t* plan, void* stream, double p, uint64_t seed,
+                                      uint32_t offset, int64_t head0);
+GRAPHOP_API int graphop_attention_dropout_backward(int dtype, const int64_t* row, const int64_t* indptr_r,
+                                       const int64_t* eid_r, const int64_t* indices_r, const int64_t* col,
+                                       const int64_t* indptr_c, const int64_t* eid_c, const int64_t* indices_c,
+                                       const void* Q, const void* K, const void* V, const void* o,
+                                       const void* stats, const void* dO, void* dQ, void* dK, void* dV,
+                                       int64_t n_row_chunks, int64_t n_col_chunks, int64_t n_edges, int64_t n_q,
+                                       int64_t n_k, int64_t h, int64_t d, void* workspace, int64_t workspace_bytes,
+                                       const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream,
+                                       double p, uint64_t seed, uint32_t offset, int64_t head0);
+
 /* ---- halo pack / unpack of the node-range sharded step (not in the reference: single GPU) --------
  * gather_rows:      dst[i, :] = src[idx[i], :]          (send buffer of the rows peers gather from)
  * scatter_add_rows: dst[idx[i], :] += src[i, :]         (partial gradient rows coming home; idx may
