@@ -10,11 +10,16 @@
 // kernels_dropout.h recomputed per slot.  The forms are chosen by the rules of the undropped op; the fused kernels run
 // their DROP instantiations, the composed path multiplies a (and the gradient that comes back) by m with
 // k_attn_drop_apply.  drop == nullptr below is the undropped op: the same kernels and launches as before.
+// Per-edge score bias (graphop_attention_bias_*): s_e = <Q_i, K_j> + b[e] with b indexed by edge id, db =
+// ds.  The composed path adds b to s with k_attn_bias_add and lets the softmax backward write ds into db; the fused
+// backward is the chunk-driver form with the bias (k_attn_bias_bwd_rows_f32) wherever the undropped op would run either
+// fused form, the fused forward the chunk-driver pass of kernels_attn_bias_fwd.h.  bias == nullptr below is the op
+// without a bias: the same kernels and launches as before.
 // Reference composition: wrapper.py:20-30 (MaskedMMCSR), :8-18 (SparseSoftmax), :44-55 (VectorSPMM).
 #include "common.h"
 #include "host.h"
 #include "host_dropout.h"
-#include "kernels_attn.h"
+#include "kernels_attn_bias.h"
 
 namespace graphop {
 namespace {
@@ -143,6 +148,33 @@ int launch_attn_rows(const char* tag, const graphop_plan* plan, i64 n_chunks, in
   return GRAPHOP_OK;
 }
 
+// the same launch geometry for k_attn_bias_bwd_rows_f32; eid == nullptr: the plan has eid_identity
+template <bool COL, bool DROP>
+int launch_attn_bias_rows(const char* tag, const graphop_plan* plan, const i64* eid, i64 n_chunks, int F, const float* own,
+                          const float* xt, const float4* st4, const float* b, float* out0, float* out1, float* db,
+                          const AttnDrop* drop, hipStream_t st) {
+  if (n_chunks == 0) return GRAPHOP_OK;
+  ProfScope prof(tag, st, DROP ? "k_attn_bias_bwd_rows_f32<DROP>" : "k_attn_bias_bwd_rows_f32");
+  const bool owned = plan->info.rows_sorted != 0;
+  GO_DISPATCH_LNV(F, {
+    constexpr int GPB = kFastBlock / L;
+    const i64 groups_wanted = (i64)tuning().n_cu * GPB * 8;
+    i64 cpg = n_chunks / (groups_wanted > 0 ? groups_wanted : 1);
+    cpg = cpg < 1 ? 1 : (cpg > 16 ? 16 : cpg);
+    const unsigned nb = (unsigned)ceil_div(ceil_div(n_chunks, cpg), GPB);
+    if (owned)
+      hipLaunchKernelGGL((k_attn_bias_bwd_rows_f32<L, NV, COL, true, DROP>), dim3(nb), dim3(kFastBlock), 0, st,
+                         (const i64*)plan->row, (const i64*)plan->indptr, eid, (const i64*)plan->indices, own, xt, st4, b,
+                         out0, out1, db, n_chunks, (int)cpg, attn_drop_arg<DROP>(drop));
+    else
+      hipLaunchKernelGGL((k_attn_bias_bwd_rows_f32<L, NV, COL, false, DROP>), dim3(nb), dim3(kFastBlock), 0, st,
+                         (const i64*)plan->row, (const i64*)plan->indptr, eid, (const i64*)plan->indices, own, xt, st4, b,
+                         out0, out1, db, n_chunks, (int)cpg, attn_drop_arg<DROP>(drop));
+  });
+  GO_LAUNCH_CHECK();
+  return GRAPHOP_OK;
+}
+
 struct FastWs {
   float* kv; float* qdo; float4* st4; size_t total;
   FastWs(char* base, i64 n_q, i64 n_k, i64 F) {
@@ -251,6 +283,39 @@ int attn_drop_check(const char* fn, const DropIn& in, i64 n_q, i64 n_k, HostDrop
   return GRAPHOP_OK;
 }
 
+// the bias arguments of the *_bias_* entry points as they arrive; checked after the dropout arguments
+struct BiasIn {
+  const void* b;   // (n_edges, h) by edge id
+  void* db;        // backward: NULL = the gradient of b is not wanted (nothing edge-sized is then written)
+};
+
+int attn_bias_check(const char* fn, const BiasIn& in, i64 n_edges, i64 h) {
+  GO_CHECK_ARG(n_edges * h == 0 || in.b != nullptr, "%s: b is NULL", fn);
+  return GRAPHOP_OK;
+}
+
+// the chunk-driver fused backward with a bias: wherever the undropped op would run either of its fused forms
+bool attn_bias_rows_ok(int fast, int dtype, i64 h, i64 d, i64 n_edges, i64 n_q, i64 n_k, const graphop_plan* plan_r,
+                       const graphop_plan* plan_c, hipStream_t st) {
+  if (!tuning().attn_rows) return false;
+  if (attn_rows_ok(dtype, h, d, n_edges, n_q, n_k, plan_r, plan_c, st)) return true;
+  return fast == 1 && plan_r->indices && plan_c->indices;   // (attn_fast_plan checked the id ranges)
+}
+
+// s += b, both (n_edges, h) by edge id
+int attn_bias_add(int dtype, void* s, const void* b, i64 n, hipStream_t st) {
+  if (n == 0) return GRAPHOP_OK;
+  ProfScope prof("attn_bias_add", st, "k_attn_bias_add");
+  const i64 want = ceil_div(n, kGenericBlock);
+  const unsigned nb = (unsigned)(want > 65536 ? 65536 : want);
+  if (dtype == GRAPHOP_F32)
+    hipLaunchKernelGGL((k_attn_bias_add<float>), dim3(nb), dim3(kGenericBlock), 0, st, (float*)s, (const float*)b, n);
+  else
+    hipLaunchKernelGGL((k_attn_bias_add<double>), dim3(nb), dim3(kGenericBlock), 0, st, (double*)s, (const double*)b, n);
+  GO_LAUNCH_CHECK();
+  return GRAPHOP_OK;
+}
+
 // y = x * m over the row-major chunks (k_attn_drop_apply), in place or not
 int attn_drop_apply(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid, const int64_t* indices,
                     const void* x, void* y, i64 n_chunks, i64 n_edges, i64 h, i64 head0, const HostDrop& drop,
@@ -270,20 +335,24 @@ int attn_drop_apply(int dtype, const int64_t* row, const int64_t* indptr, const 
   return GRAPHOP_OK;
 }
 
-// bwd_arrays: E-sized arrays of the composed backward (4; 5 with dropout: the masked weights)
+// bwd_arrays: E-sized arrays of the composed backward (4; 5 with dropout: the masked weights; with a bias one fewer
+// where db takes the place of ds).  bias: the forms of the op with a bias are the ones decided on.
 int attn_workspace_bytes(const char* fn, int dtype, int backward, int64_t n_edges, int64_t n_q, int64_t n_k, int64_t h,
                          int64_t d, const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream,
-                         int bwd_arrays, int64_t* bytes_out) {
+                         int bwd_arrays, int64_t* bytes_out, bool bias = false) {
   GO_CHECK_ARG(bytes_out != nullptr, "%s: bytes_out is NULL", fn);
   GO_CHECK_ARG(dtype == GRAPHOP_F32 || dtype == GRAPHOP_F64, "%s: bad dtype", fn);
   GO_CHECK_ARG(n_edges >= 0 && n_q >= 0 && n_k >= 0 && h >= 1 && d >= 0, "%s: negative size", fn);
   const size_t es = esize(dtype);
   if (!backward) {
     size_t need = 0;
-    const int fw = (plan_r && n_edges * h > 0)
-                       ? attn_fwd_walk(plan_r, n_q, n_k, h, d, dtype, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
-                                       (hipStream_t)stream, /*dry_run=*/true, &need)
-                       : 0;
+    int fw = 0;
+    if (plan_r && n_edges * h > 0)
+      fw = bias ? attn_bias_fwd_rows(plan_r, nullptr, plan_r->info.n_chunks, n_edges, n_q, n_k, h, d, dtype, nullptr,
+                                     nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream,
+                                     /*dry_run=*/true, &need)
+                : attn_fwd_walk(plan_r, n_q, n_k, h, d, dtype, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
+                                (hipStream_t)stream, /*dry_run=*/true, &need);
     if (fw < 0) return -fw;
     // the one-pass forward only needs the piece records of shared rows; the composed forward keeps s and a here
     *bytes_out = fw == 1 ? (int64_t)need : (int64_t)SlowWs(nullptr, 2, es, n_edges, h, soft_rows_of(plan_r, n_q)).total;
@@ -293,8 +362,9 @@ int attn_workspace_bytes(const char* fn, int dtype, int backward, int64_t n_edge
   const int fast = attn_fast_plan(dtype, h, d, n_edges, n_q, n_k, plan_r, plan_c, (hipStream_t)stream,
                                   /*dry_run=*/true, &af);
   if (fast < 0) return -fast;
-  if (fast == 1 || attn_rows_ok(dtype, h, d, n_edges, n_q, n_k, plan_r, plan_c, (hipStream_t)stream))
-    *bytes_out = (int64_t)FastWs(nullptr, n_q, n_k, h * d).total;
+  const bool fused = bias ? attn_bias_rows_ok(fast, dtype, h, d, n_edges, n_q, n_k, plan_r, plan_c, (hipStream_t)stream)
+                          : (fast == 1 || attn_rows_ok(dtype, h, d, n_edges, n_q, n_k, plan_r, plan_c, (hipStream_t)stream));
+  if (fused) *bytes_out = (int64_t)FastWs(nullptr, n_q, n_k, h * d).total;
   else *bytes_out = (int64_t)SlowWs(nullptr, bwd_arrays, es, n_edges, h, soft_rows_of(plan_r, n_q)).total;
   return GRAPHOP_OK;
 }
@@ -304,19 +374,22 @@ inline AttnDrop attn_head_drop(const HostDrop& drop, i64 head0) {
   return AttnDrop{drop.as<float>(), (unsigned)(head0 >> 2), (int)(head0 & 3)};
 }
 
-// din == nullptr: graphop_attention_forward, else its dropout form (p == 0: the undropped op), as `fn`
+// din == nullptr: graphop_attention_forward, else its dropout form (p == 0: the undropped op), as `fn`;
+// bias != nullptr: the form with a per-edge score bias
 int attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t* indptr,
                  const int64_t* eid, const int64_t* indices, const void* Q, const void* K, const void* V, void* o,
                  void* stats, int64_t n_chunks, int64_t n_edges, int64_t n_q, int64_t n_k, int64_t h, int64_t d,
                  void* workspace, int64_t workspace_bytes, const DropIn* din, const graphop_plan_t* plan,
-                 void* stream) {
+                 void* stream, const BiasIn* bias = nullptr) {
   GO_TRY(check_async_error(false));
   GO_TRY(attn_check(fn, dtype, n_chunks, 0, n_edges, n_q, n_k, h, d));
   HostDrop hdrop;
   if (din) GO_TRY(attn_drop_check(fn, *din, n_q, n_k, &hdrop));
+  if (bias) GO_TRY(attn_bias_check(fn, *bias, n_edges, h));
   const HostDrop* drop = (din && din->p > 0.0) ? &hdrop : nullptr;
   const int64_t head0 = din ? din->head0 : 0;
-  const char* ws_fn = drop ? "attention_dropout_workspace_bytes" : "attention_workspace_bytes";
+  const char* ws_fn = bias ? "attention_bias_workspace_bytes"
+                           : (drop ? "attention_dropout_workspace_bytes" : "attention_workspace_bytes");
   hipStream_t st = (hipStream_t)stream;
   AttnDrop hd{};
   if (drop) hd = attn_head_drop(*drop, head0);
@@ -332,14 +405,21 @@ int attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t* i
   if (pm && n_edges * h > 0) {
     GO_PTR(fn, Q); GO_PTR(fn, K); GO_PTR(fn, V); GO_PTR(fn, o);
     size_t need = 0;
-    const int ok = attn_fwd_walk(pm, n_q, n_k, h, d, dtype, Q, K, V, o, stats, nullptr, 0, st, /*dry_run=*/true, &need);
+    // with a bias: the chunk-driver pass of kernels_attn_bias_fwd.h (the walk's layouts carry no edge id)
+    auto fused_fwd = [&](void* w, int64_t w_bytes, bool dry_run, size_t* needed) {
+      if (bias)
+        return attn_bias_fwd_rows(pm, (const i64*)eid, n_chunks, n_edges, n_q, n_k, h, d, dtype, Q, K, V, bias->b, o, stats,
+                                  w, w_bytes, st, dry_run, needed, drop ? &hd : nullptr);
+      return attn_fwd_walk(pm, n_q, n_k, h, d, dtype, Q, K, V, o, stats, w, w_bytes, st, dry_run, needed,
+                           drop ? &hd : nullptr);
+    };
+    const int ok = fused_fwd(nullptr, 0, /*dry_run=*/true, &need);
     if (ok < 0) return -ok;
     if (ok == 1) {
       GO_CHECK_ARG(workspace != nullptr && (size_t)workspace_bytes >= need,
                    "%s: workspace of %lld bytes needed (graphop_%s), got %lld", fn,
                    (long long)need, ws_fn, (long long)workspace_bytes);
-      const int fw = attn_fwd_walk(pm, n_q, n_k, h, d, dtype, Q, K, V, o, stats, workspace, workspace_bytes, st,
-                                   /*dry_run=*/false, nullptr, drop ? &hd : nullptr);
+      const int fw = fused_fwd(workspace, workspace_bytes, /*dry_run=*/false, nullptr);
       if (fw < 0) return -fw;
       if (fw == 1) return GRAPHOP_OK;
     }
@@ -353,6 +433,7 @@ int attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t* i
   void* a = ws.arr[1];
   GO_TRY(graphop_maskedmm_csr_forward(dtype, row, indptr, eid, indices, Q, K, s, n_chunks, n_edges, n_q,
                                       n_k, h, d, pm, stream));
+  if (bias) GO_TRY(attn_bias_add(dtype, s, bias->b, n_edges * h, st));
   if (n_edges * h > 0)
     GO_TRY(softmax_forward_stats(dtype, (const i64*)row, (const i64*)indptr, (const i64*)eid, s, a,
                                  n_chunks, n_edges, h, soft_rows ? ws.soft : nullptr, soft_rows, pm, st,
@@ -362,21 +443,25 @@ int attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t* i
                                      n_q, h, d, pm, stream);
 }
 
-// din == nullptr: graphop_attention_backward, else its dropout form (p == 0: the undropped op), as `fn`
+// din == nullptr: graphop_attention_backward, else its dropout form (p == 0: the undropped op), as `fn`;
+// bias != nullptr: the form with a per-edge score bias
 int attn_backward(const char* fn, int dtype, const int64_t* row, const int64_t* indptr_r,
                   const int64_t* eid_r, const int64_t* indices_r, const int64_t* col, const int64_t* indptr_c,
                   const int64_t* eid_c, const int64_t* indices_c, const void* Q, const void* K, const void* V,
                   const void* o, const void* stats, const void* dO, void* dQ, void* dK, void* dV,
                   int64_t n_row_chunks, int64_t n_col_chunks, int64_t n_edges, int64_t n_q, int64_t n_k, int64_t h,
                   int64_t d, void* workspace, int64_t workspace_bytes, const DropIn* din,
-                  const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream) {
+                  const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream,
+                  const BiasIn* bias = nullptr) {
   GO_TRY(check_async_error(false));
   GO_TRY(attn_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_q, n_k, h, d));
   HostDrop hdrop;
   if (din) GO_TRY(attn_drop_check(fn, *din, n_q, n_k, &hdrop));
+  if (bias) GO_TRY(attn_bias_check(fn, *bias, n_edges, h));
   const HostDrop* drop = (din && din->p > 0.0) ? &hdrop : nullptr;
   const int64_t head0 = din ? din->head0 : 0;
-  const char* ws_fn = drop ? "attention_dropout_workspace_bytes" : "attention_workspace_bytes";
+  const char* ws_fn = bias ? "attention_bias_workspace_bytes"
+                           : (drop ? "attention_dropout_workspace_bytes" : "attention_workspace_bytes");
   hipStream_t st = (hipStream_t)stream;
   AttnDrop hd{};
   if (drop) hd = attn_head_drop(*drop, head0);
@@ -386,10 +471,13 @@ int attn_backward(const char* fn, int dtype, const int64_t* row, const int64_t* 
   const graphop_plan* pc = plan_matches_full(plan_c, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c,
                                              (const i64*)indices_c, n_col_chunks, n_edges) ? plan_c : nullptr;
   AttnFast af;
-  const int fast = attn_fast_plan(dtype, h, d, n_edges, n_q, n_k, pr, pc, st, /*dry_run=*/false, &af);
+  // (with a bias the window-owner passes are never launched: only their decision is asked for, no task queue taken)
+  const int fast = attn_fast_plan(dtype, h, d, n_edges, n_q, n_k, pr, pc, st, /*dry_run=*/bias != nullptr, &af);
   if (fast < 0) return -fast;
-  const bool rows_path = fast != 1 && attn_rows_ok(dtype, h, d, n_edges, n_q, n_k, pr, pc, st);
-  if (fast == 1 || rows_path) {
+  // with a bias the chunk-driver form runs wherever either fused form would (the window layouts carry no edge id)
+  const bool rows_path = bias ? attn_bias_rows_ok(fast, dtype, h, d, n_edges, n_q, n_k, pr, pc, st)
+                              : (fast != 1 && attn_rows_ok(dtype, h, d, n_edges, n_q, n_k, pr, pc, st));
+  if (bias ? rows_path : (fast == 1 || rows_path)) {
     const i64 F = d;   // h == 1
     FastWs ws((char*)workspace, n_q, n_k, F);
     GO_CHECK_ARG(workspace != nullptr && (size_t)workspace_bytes >= ws.total,
@@ -416,6 +504,15 @@ int attn_backward(const char* fn, int dtype, const int64_t* row, const int64_t* 
     // each launch is written once: DROP picks the instantiation, the arguments are the same
     auto passes = [&](auto drop_c) -> int {
       constexpr bool DROP = decltype(drop_c)::value;
+      if (bias) {
+        GO_TRY((launch_attn_bias_rows<false, DROP>("attn_bias_rows_row", pr, pr->info.eid_identity ? nullptr : (const i64*)eid_r,
+                                                   n_row_chunks, (int)F, ws.qdo, ws.kv, ws.st4, (const float*)bias->b,
+                                                   (float*)dQ, nullptr, (float*)bias->db, &hd, st)));
+        GO_TRY((launch_attn_bias_rows<true, DROP>("attn_bias_rows_col", pc, pc->info.eid_identity ? nullptr : (const i64*)eid_c,
+                                                  n_col_chunks, (int)F, ws.kv, ws.qdo, ws.st4, (const float*)bias->b,
+                                                  (float*)dK, (float*)dV, nullptr, &hd, st)));
+        return GRAPHOP_OK;
+      }
       if (rows_path) {
         GO_TRY((launch_attn_rows<false, DROP>("attn_rows_row", pr, n_row_chunks, (int)F, ws.qdo, ws.kv, ws.st4,
                                               (float*)dQ, nullptr, &hd, st)));
@@ -432,24 +529,28 @@ int attn_backward(const char* fn, int dtype, const int64_t* row, const int64_t* 
     return drop ? passes(std::true_type{}) : passes(std::false_type{});
   }
   // composition of the unfused entry points: recompute s and a, then the three backward ops
+  // with a bias and db given, the softmax backward writes ds straight into db: one E-sized array fewer
   const i64 soft_rows = soft_rows_of(pr, n_q);
-  SlowWs ws((char*)workspace, drop ? 5 : 4, es, n_edges, h, soft_rows);
+  const bool ds_is_db = bias && bias->db != nullptr;
+  SlowWs ws((char*)workspace, (bias || drop ? 5 : 4) - (ds_is_db ? 1 : 0), es, n_edges, h, soft_rows);
   GO_CHECK_ARG(n_edges * h == 0 || (workspace != nullptr && (size_t)workspace_bytes >= ws.total),
                "%s: workspace of %lld bytes needed (graphop_%s), got %lld", fn,
                (long long)ws.total, ws_fn, (long long)workspace_bytes);
   void* s = ws.arr[0];
   void* a = ws.arr[1];
   void* da = ws.arr[2];
-  void* ds = ws.arr[3];
+  void* ds = ds_is_db ? bias->db : ws.arr[3];
+  void* am = ds_is_db ? ws.arr[3] : ws.arr[4];   // a * m of the dropout form
   GO_TRY(graphop_maskedmm_csr_forward(dtype, row, indptr_r, eid_r, indices_r, Q, K, s, n_row_chunks,
                                       n_edges, n_q, n_k, h, d, pr, stream));
+  if (bias) GO_TRY(attn_bias_add(dtype, s, bias->b, n_edges * h, st));
   GO_TRY(graphop_sparse_softmax_forward(dtype, row, indptr_r, eid_r, s, a, n_row_chunks, n_edges, h,
                                         soft_rows ? ws.soft : nullptr, soft_rows, pr, stream));
   // with dropout: am = a * m feeds the SpMM backward, and the gradient that comes back is that of am: da = d_am * m
   const void* w = a;
   if (drop) {
-    GO_TRY(attn_drop_apply(dtype, row, indptr_r, eid_r, indices_r, a, ws.arr[4], n_row_chunks, n_edges, h, head0, *drop, st));
-    w = ws.arr[4];
+    GO_TRY(attn_drop_apply(dtype, row, indptr_r, eid_r, indices_r, a, am, n_row_chunks, n_edges, h, head0, *drop, st));
+    w = am;
   }
   GO_TRY(graphop_vector_spmm_backward(dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
                                       indices_c, w, dO, V, da, dV, n_row_chunks, n_col_chunks, n_edges,
@@ -541,6 +642,41 @@ int graphop_attention_dropout_backward(int dtype, const int64_t* row, const int6
   return attn_backward("attention_dropout_backward", dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
                        indices_c, Q, K, V, o, stats, dO, dQ, dK, dV, n_row_chunks, n_col_chunks, n_edges, n_q, n_k, h, d,
                        workspace, workspace_bytes, &din, plan_r, plan_c, stream);
+}
+
+// b == NULL is not an error only for empty problems; p == 0 takes no Philox path
+int graphop_attention_bias_workspace_bytes(int dtype, int backward, int64_t n_edges, int64_t n_q, int64_t n_k, int64_t h,
+                                           int64_t d, const graphop_plan_t* plan_r, const graphop_plan_t* plan_c,
+                                           void* stream, int with_db, int64_t* bytes_out) {
+  return attn_workspace_bytes("attention_bias_workspace_bytes", dtype, backward, n_edges, n_q, n_k, h, d, plan_r, plan_c,
+                              stream, with_db ? 4 : 5, bytes_out, /*bias=*/true);
+}
+
+int graphop_attention_bias_forward(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                                   const int64_t* indices, const void* Q, const void* K, const void* V, const void* b,
+                                   void* o, void* stats, int64_t n_chunks, int64_t n_edges, int64_t n_q, int64_t n_k,
+                                   int64_t h, int64_t d, void* workspace, int64_t workspace_bytes,
+                                   const graphop_plan_t* plan, void* stream, double p, uint64_t seed, uint32_t offset,
+                                   int64_t head0) {
+  const DropIn din{p, seed, offset, head0};
+  const BiasIn bin{b, nullptr};
+  return attn_forward("attention_bias_forward", dtype, row, indptr, eid, indices, Q, K, V, o, stats, n_chunks, n_edges,
+                      n_q, n_k, h, d, workspace, workspace_bytes, &din, plan, stream, &bin);
+}
+
+int graphop_attention_bias_backward(int dtype, const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r,
+                                    const int64_t* indices_r, const int64_t* col, const int64_t* indptr_c,
+                                    const int64_t* eid_c, const int64_t* indices_c, const void* Q, const void* K,
+                                    const void* V, const void* b, const void* o, const void* stats, const void* dO,
+                                    void* dQ, void* dK, void* dV, void* db, int64_t n_row_chunks, int64_t n_col_chunks,
+                                    int64_t n_edges, int64_t n_q, int64_t n_k, int64_t h, int64_t d, void* workspace,
+                                    int64_t workspace_bytes, const graphop_plan_t* plan_r, const graphop_plan_t* plan_c,
+                                    void* stream, double p, uint64_t seed, uint32_t offset, int64_t head0) {
+  const DropIn din{p, seed, offset, head0};
+  const BiasIn bin{b, db};
+  return attn_backward("attention_bias_backward", dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
+                       indices_c, Q, K, V, o, stats, dO, dQ, dK, dV, n_row_chunks, n_col_chunks, n_edges, n_q, n_k, h, d,
+                       workspace, workspace_bytes, &din, plan_r, plan_c, stream, &bin);
 }
 
 }  // extern "C"

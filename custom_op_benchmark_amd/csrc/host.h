@@ -195,6 +195,15 @@ int attn_fwd_walk(const graphop_plan* plan, i64 n_q, i64 n_k, i64 h, i64 d, int 
                   const void* V, void* o, void* stats, void* ws, i64 ws_bytes, hipStream_t st, bool dry_run,
                   size_t* ws_needed, const AttnDrop* drop = nullptr);
 
+// Fused attention forward WITH a per-edge score bias b (indexed by edge id), chunk-driver form (graphop_hip.hip;
+// kernels_attn_bias.h): a lane group walks consecutive chunks of a rows_sorted plan with an online
+// softmax; rows that groups share leave as piece records merged by the walk's piece kernels.  Same return values and
+// dry_run meaning as attn_fwd_walk.  eid: the call's edge ids (the plan's), unused where the plan has eid_identity.
+int attn_bias_fwd_rows(const graphop_plan* plan, const i64* eid, i64 n_chunks, i64 n_edges, i64 n_q, i64 n_k, i64 h,
+                       i64 d, int dtype, const void* Q, const void* K, const void* V, const void* b, void* o,
+                       void* stats, void* ws, i64 ws_bytes, hipStream_t st, bool dry_run, size_t* ws_needed,
+                       const AttnDrop* drop = nullptr);
+
 int softmax_forward_stats(int dtype, const i64* row, const i64* indptr, const i64* eid, const void* x,
                           void* y, i64 C, i64 E, i64 h, void* ws, i64 ws_rows,
                           const graphop_plan* plan, hipStream_t st, void* stats);

@@ -374,13 +374,24 @@ DropSpec drop_spec(const char* fn, double p, int64_t seed, int64_t offset) {
 }
 
 // ---- the extra fused op (include/graphop_hip.h: graphop_attention_*) ------------------------------
-// drop == nullptr: graphop_attention_forward, else its dropout form for the heads head0 .. head0 + h - 1, as `fn`
+void check_attn_bias_input(const at::Tensor& b) { CHECK_INPUT(b); }
+// b of the forms with a per-edge score bias: (n_edges) for 2-D Q / K / V, else (n_edges, h), in Q's dtype
+void check_attn_bias(const char* fn, const at::Tensor& b, const at::Tensor& Q, int64_t e, int64_t h) {
+  CHECK_SAME_DTYPE(Q, b); CHECK_EDGE_ROWS(b, e);
+  TORCH_CHECK(Q.dim() == 2 ? (b.dim() == 1 && b.size(0) == e) : (b.dim() == 2 && b.size(0) == e && b.size(1) == h),
+              fn, ": b must be (n_edges) for 2-D Q / K / V, else (n_edges, h) with n_edges = ", e, " and h = ", h,
+              ", got b ", b.sizes(), ", Q ", Q.sizes());
+}
+
+// drop == nullptr: graphop_attention_forward, else its dropout form for the heads head0 .. head0 + h - 1, as `fn`;
+// b != nullptr (with drop given): the form with a per-edge score bias
 std::vector<at::Tensor> attention_forward_impl(const char* fn, const at::Tensor& row, const at::Tensor& indptr,
                                                const at::Tensor& eid, const at::Tensor& indices, const at::Tensor& Q,
                                                const at::Tensor& K, const at::Tensor& V, const DropSpec* drop,
-                                               int64_t head0) {
+                                               int64_t head0, const at::Tensor* b = nullptr) {
   CHECK_CSR(row, indptr, eid, indices);
   CHECK_INPUT(Q); CHECK_INPUT(K); CHECK_INPUT(V);
+  if (b) check_attn_bias_input(*b);
   TORCH_CHECK(K.sizes() == V.sizes() && Q.sizes().slice(1) == K.sizes().slice(1),
               fn, ": Q (n_q,[h,]d), K and V (n_k,[h,]d) expected");
   CHECK_SAME_DTYPE(Q, K); CHECK_SAME_DTYPE(Q, V);
@@ -391,10 +402,19 @@ std::vector<at::Tensor> attention_forward_impl(const char* fn, const at::Tensor&
   const auto pp = get_plan(row, indptr, eid, indices, n_k);
   const auto& p = *pp;
   int64_t nbytes = 0;
-  check((drop ? graphop_attention_dropout_workspace_bytes : graphop_attention_workspace_bytes)(
-      dtype_code(Q), 0, e, n_q, n_k, h, d, p.plan, nullptr, stream_of(Q), &nbytes));
+  if (b) {
+    check_attn_bias(fn, *b, Q, e, h);
+    check(graphop_attention_bias_workspace_bytes(dtype_code(Q), 0, e, n_q, n_k, h, d, p.plan, nullptr, stream_of(Q), 0, &nbytes));
+  } else {
+    check((drop ? graphop_attention_dropout_workspace_bytes : graphop_attention_workspace_bytes)(
+        dtype_code(Q), 0, e, n_q, n_k, h, d, p.plan, nullptr, stream_of(Q), &nbytes));
+  }
   auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, Q.options().dtype(at::kByte));
-  if (drop)
+  if (b)
+    check(graphop_attention_bias_forward(dtype_code(Q), ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(V),
+                                         vp(*b), vp(o), vp(stats), row.size(0), e, n_q, n_k, h, d, ws.data_ptr(), nbytes,
+                                         p.plan, stream_of(Q), drop->p, drop->seed, drop->offset, head0));
+  else if (drop)
     check(graphop_attention_dropout_forward(dtype_code(Q), ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(V),
                                             vp(o), vp(stats), row.size(0), e, n_q, n_k, h, d, ws.data_ptr(), nbytes,
                                             p.plan, stream_of(Q), drop->p, drop->seed, drop->offset, head0));
@@ -425,17 +445,30 @@ std::vector<at::Tensor> attention_dropout_forward(const at::Tensor& row, const a
   return attention_forward_impl(fn, row, indptr, eid, indices, Q, K, V, &drop, head0_checked(fn, head0));
 }
 
-// drop == nullptr: graphop_attention_backward, else its dropout form, as `fn`
+std::vector<at::Tensor> attention_bias_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
+                                               const at::Tensor& indices, const at::Tensor& Q, const at::Tensor& K,
+                                               const at::Tensor& V, const at::Tensor& b, double p, int64_t seed,
+                                               int64_t offset, int64_t head0) {
+  const char* fn = "attention_bias_forward";
+  const DropSpec drop = drop_spec(fn, p, seed, offset);
+  return attention_forward_impl(fn, row, indptr, eid, indices, Q, K, V, &drop, head0_checked(fn, head0), &b);
+}
+
+// drop == nullptr: graphop_attention_backward, else its dropout form, as `fn`; b != nullptr (with drop given): the form
+// with a per-edge score bias, which returns db as a fourth tensor (empty with need_db == false)
 std::vector<at::Tensor> attention_backward_impl(const char* fn, const at::Tensor& row, const at::Tensor& indptr_r,
                                                 const at::Tensor& eid_r, const at::Tensor& indices_r,
                                                 const at::Tensor& col, const at::Tensor& indptr_c,
                                                 const at::Tensor& eid_c, const at::Tensor& indices_c,
                                                 const at::Tensor& Q, const at::Tensor& K, const at::Tensor& V,
                                                 const at::Tensor& o, const at::Tensor& stats, const at::Tensor& dO_,
-                                                const DropSpec* drop, int64_t head0) {
+                                                const DropSpec* drop, int64_t head0, const at::Tensor* b = nullptr,
+                                                bool need_db = true) {
   CHECK_CSR(row, indptr_r, eid_r, indices_r);
   CHECK_CSR(col, indptr_c, eid_c, indices_c);
-  CHECK_INPUT(Q); CHECK_INPUT(K); CHECK_INPUT(V); CHECK_INPUT(o); CHECK_INPUT(stats);
+  CHECK_INPUT(Q); CHECK_INPUT(K); CHECK_INPUT(V);
+  if (b) check_attn_bias_input(*b);
+  CHECK_INPUT(o); CHECK_INPUT(stats);
   CHECK_CUDA(dO_);
   const at::Tensor dO = dO_.contiguous();
   CHECK_SAME_DTYPE(Q, K); CHECK_SAME_DTYPE(Q, V); CHECK_SAME_DTYPE(Q, o); CHECK_SAME_DTYPE(Q, stats); CHECK_SAME_DTYPE(Q, dO);
@@ -450,9 +483,25 @@ std::vector<at::Tensor> attention_backward_impl(const char* fn, const at::Tensor
   const auto ppc = get_plan(col, indptr_c, eid_c, indices_c, n_q);
   const auto &pr = *ppr, &pc = *ppc;
   int64_t nbytes = 0;
-  check((drop ? graphop_attention_dropout_workspace_bytes : graphop_attention_workspace_bytes)(
-      dtype_code(Q), 1, e, n_q, n_k, h, d, pr.plan, pc.plan, stream_of(Q), &nbytes));
+  if (b) {
+    check_attn_bias(fn, *b, Q, e, h);
+    check(graphop_attention_bias_workspace_bytes(dtype_code(Q), 1, e, n_q, n_k, h, d, pr.plan, pc.plan, stream_of(Q),
+                                                 need_db ? 1 : 0, &nbytes));
+  } else {
+    check((drop ? graphop_attention_dropout_workspace_bytes : graphop_attention_workspace_bytes)(
+        dtype_code(Q), 1, e, n_q, n_k, h, d, pr.plan, pc.plan, stream_of(Q), &nbytes));
+  }
   auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, Q.options().dtype(at::kByte));
+  if (b) {
+    // db[e] is written once per row-major slot: only a chunk list that leaves slots out needs the zeros
+    auto db = !need_db ? at::empty({0}, b->options()) : (pr.info.full_coverage ? at::empty_like(*b) : at::zeros_like(*b));
+    check(graphop_attention_bias_backward(
+        dtype_code(Q), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c), ip(indices_c),
+        vp(Q), vp(K), vp(V), vp(*b), vp(o), vp(stats), vp(dO), vp(dQ), vp(dK), vp(dV), need_db ? vp(db) : nullptr,
+        row.size(0), col.size(0), e, n_q, n_k, h, d, ws.data_ptr(), nbytes, pr.plan, pc.plan, stream_of(Q), drop->p,
+        drop->seed, drop->offset, head0));
+    return {dQ, dK, dV, db};
+  }
   if (drop)
     check(graphop_attention_dropout_backward(
         dtype_code(Q), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c), ip(indices_c),
@@ -487,6 +536,19 @@ std::vector<at::Tensor> attention_dropout_backward(const at::Tensor& row, const 
   const DropSpec drop = drop_spec(fn, p, seed, offset);
   return attention_backward_impl(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, o, stats,
                                  dO, &drop, head0_checked(fn, head0));
+}
+
+std::vector<at::Tensor> attention_bias_backward(const at::Tensor& row, const at::Tensor& indptr_r,
+                                                const at::Tensor& eid_r, const at::Tensor& indices_r,
+                                                const at::Tensor& col, const at::Tensor& indptr_c,
+                                                const at::Tensor& eid_c, const at::Tensor& indices_c, const at::Tensor& Q,
+                                                const at::Tensor& K, const at::Tensor& V, const at::Tensor& b,
+                                                const at::Tensor& o, const at::Tensor& stats, const at::Tensor& dO,
+                                                double p, int64_t seed, int64_t offset, int64_t head0, bool need_db) {
+  const char* fn = "attention_bias_backward";
+  const DropSpec drop = drop_spec(fn, p, seed, offset);
+  return attention_backward_impl(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, o, stats,
+                                 dO, &drop, head0_checked(fn, head0), &b, need_db);
 }
 
 // ---- the extra GAT score op (include/graphop_hip.h: graphop_gat_scores_*) ---------------------------------
@@ -994,6 +1056,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("eid_r"), py::arg("indices_r"), py::arg("col"), py::arg("indptr_c"), py::arg("eid_c"),
         py::arg("indices_c"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("o"), py::arg("stats"), py::arg("dO"),
         py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0, py::arg("head0") = 0);
+  // (likewise its form with a per-edge score bias)
+  m.def("attention_bias_forward", &attention_bias_forward,
+        "Fused attention forward with a per-edge score bias (extra op)", py::arg("row"), py::arg("indptr"), py::arg("eid"),
+        py::arg("indices"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("b"), py::arg("p") = 0.0,
+        py::arg("seed") = 0, py::arg("offset") = 0, py::arg("head0") = 0);
+  m.def("attention_bias_backward", &attention_bias_backward,
+        "Fused attention backward with a per-edge score bias (extra op)", py::arg("row"), py::arg("indptr_r"),
+        py::arg("eid_r"), py::arg("indices_r"), py::arg("col"), py::arg("indptr_c"), py::arg("eid_c"),
+        py::arg("indices_c"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("b"), py::arg("o"), py::arg("stats"),
+        py::arg("dO"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0, py::arg("head0") = 0,
+        py::arg("need_db") = true);
   m.def("gat_scores_forward", &gat_scores_forward, "GAT additive attention scores forward (extra op)", py::arg("row"),
         py::arg("indptr"), py::arg("eid"), py::arg("indices"), py::arg("el"), py::arg("er"), py::arg("negative_slope") = 0.2);
   m.def("gat_scores_backward", &gat_scores_backward, "GAT additive attention scores backward (extra op)", py::arg("row"),

@@ -383,6 +383,49 @@ class FusedAttentionDropout(Function):
         return (None,) * 8 + (dQ, dK, dV, None, None, None)
 
 
+class FusedAttentionBias(Function):
+    """FusedAttentionDropout with a term per edge inside the softmax (extra op): for edge e = (i, j)
+    and head k,  s_e = <Q_i, K_j> + b[e, k],  o[i] = sum_e softmax_e(s) m_e V[j]:
+    apply(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, b, p=0.0, seed=None, offset=0).
+    b is indexed by edge id -- (E) with 2-D Q / K / V, (E, h) with 3-D ones -- in their dtype.  Uses: a Graphormer-type
+    bias (spatial and edge encodings), a relative positional bias, a weighted graph with b = log w, and the key-side
+    edge term of TransformerConv(edge_dim=...), b = node_mul_edge_forward(Q, xe) (through NodeMulEdge, so that its
+    backward turns db into the gradients of Q and xe).  b must be finite: a bias at or below the -1e9 floor of the row
+    maximum is not a mask.  Saves (Q, K, V, b, o, row statistics) and nothing edge-sized but b; the backward makes db
+    = ds only where b needs a gradient.  m_e is FusedAttentionDropout's multiplier (1 at p = 0: no dropout); seed=None
+    draws one from torch's default CPU generator.  There is no 1 / sqrt(d) scale argument: fold it into Q.
+    Several heads run in FusedAttention's head groups (_head_group): a group gets the contiguous slice b[:, g0:g0 + hg]
+    (an (E, hg) copy), writes its db into its slice of one (E, h) result and names its first head."""
+
+    @staticmethod
+    def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, b, p=0.0, seed=None,
+                offset=0):
+        a8 = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item()) if float(p) > 0.0 else 0
+        ctx.drop = (float(p), int(seed), int(offset))
+        h = Q.size(1) if Q.dim() == 3 else 1
+        hg = _head_group(h, Q.size(-1), eid_r.numel(), max(Q.size(0), K.size(0))) if h > 1 else 1
+        ctx.groups = None
+        if h > 1 and hg < h:
+            return _groups_forward(ctx, a8, Q, K, V, h, hg, ctx.drop, b)
+        o, stats = _ops.attention_bias_forward(row, indptr_r, eid_r, indices_r, Q, K, V, b, *ctx.drop, 0)
+        ctx.save_for_backward(*a8, Q, K, V, b, o, stats)
+        return o
+
+    @staticmethod
+    def backward(ctx, dO):
+        a8, rest = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
+        need_db = ctx.needs_input_grad[11]
+        if ctx.groups is not None:
+            Q, K, V, b = rest
+            dQ, dK, dV, db = _groups_backward(ctx, a8, Q, K, V, dO, ctx.drop, b, need_db)
+        else:
+            Q, K, V, b, o, stats = rest
+            dQ, dK, dV, db = _ops.attention_bias_backward(*a8, Q, K, V, b, o, stats, dO, *ctx.drop, 0, need_db)
+        return (None,) * 8 + (dQ, dK, dV, db if need_db else None, None, None, None)
+
+
 def _head_slice(x, g0, hg):
     """Heads [g0, g0 + hg) of a (n, h, d) tensor as a contiguous (n, hg, d) tensor ((n, d) for one head: the one-head
     kernels and the fused passes take that form)."""
@@ -395,9 +438,16 @@ def _head_store(full, part, g0, hg):
     full[:, g0:g0 + hg, :].copy_(part[:full.size(0)].reshape(full.size(0), hg, full.size(2)))
 
 
-def _groups_forward(ctx, a8, Q, K, V, h, hg, drop=None):
-    """The head-group loop of FusedAttention and FusedAttentionDropout (drop = (p, seed, offset)): each group through
-    _group_forward, its o written into the heads' slice; ctx keeps what the groups' backwards need."""
+def _bias_slice(b, g0, hg):
+    """Heads [g0, g0 + hg) of the (E, h) score bias as a contiguous (E, hg) tensor ((E) for one head)"""
+    part = b[:, g0:g0 + hg]
+    return part.reshape(b.size(0)).contiguous() if hg == 1 else part.contiguous()
+
+
+def _groups_forward(ctx, a8, Q, K, V, h, hg, drop=None, b=None):
+    """The head-group loop of FusedAttention, FusedAttentionDropout (drop = (p, seed, offset)) and FusedAttentionBias
+    (drop and the (E, h) score bias b): each group through _group_forward, its o written into the heads' slice; ctx
+    keeps what the groups' backwards need."""
     import os
     mode = os.environ.get("GRAPHOP_FUSED_HEADS", FUSED_HEADS_MODE)
     ctx.groups = (h, hg, mode)
@@ -405,32 +455,41 @@ def _groups_forward(ctx, a8, Q, K, V, h, hg, drop=None):
     kept = []
     for g0 in range(0, h, hg):
         Qg, Kg, Vg = (_head_slice(x, g0, hg) for x in (Q, K, V))
-        og, keep = _group_forward(a8, Qg, Kg, Vg, mode, drop, g0)
+        og, keep = _group_forward(a8, Qg, Kg, Vg, mode, drop, g0, None if b is None else _bias_slice(b, g0, hg))
         _head_store(o, og, g0, hg)
         kept.append(keep)
         del Qg, Kg, Vg, og
-    ctx.kept = kept               # per group: ("fused", o_g, stats_g) | ("keep", a_g) | ("recompute",) | ("drop", o_g, stats_g)
-    ctx.save_for_backward(*a8, Q, K, V)
+    # per group: ("fused", o_g, stats_g) | ("keep", a_g) | ("recompute",) | ("drop", o_g, stats_g) | ("bias", o_g, stats_g)
+    ctx.kept = kept
+    ctx.save_for_backward(*a8, Q, K, V, *(() if b is None else (b,)))
     return o
 
 
-def _groups_backward(ctx, a8, Q, K, V, dO, drop=None):
-    """-> (dQ, dK, dV) of _groups_forward"""
+def _groups_backward(ctx, a8, Q, K, V, dO, drop=None, b=None, need_db=True):
+    """-> (dQ, dK, dV) of _groups_forward; with the score bias b -> (dQ, dK, dV, db), db (E, h) or None"""
     h, hg, mode = ctx.groups
     dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+    db = torch.empty_like(b) if b is not None and need_db else None
     for gi, g0 in enumerate(range(0, h, hg)):
         Qg, Kg, Vg, dOg = (_head_slice(x, g0, hg) for x in (Q, K, V, dO))
-        dQg, dKg, dVg = _group_backward(a8, Qg, Kg, Vg, dOg, ctx.kept[gi], drop, g0)
+        bg = None if b is None else _bias_slice(b, g0, hg)
+        dQg, dKg, dVg, *dbg = _group_backward(a8, Qg, Kg, Vg, dOg, ctx.kept[gi], drop, g0, bg, need_db)
         for full, part in ((dQ, dQg), (dK, dKg), (dV, dVg)):
             _head_store(full, part, g0, hg)
-        del Qg, Kg, Vg, dOg, dQg, dKg, dVg
-    return dQ, dK, dV
+        if db is not None:
+            db[:, g0:g0 + hg].copy_(dbg[0].reshape(db.size(0), hg))
+        del Qg, Kg, Vg, dOg, dQg, dKg, dVg, bg, dbg
+    return (dQ, dK, dV) if b is None else (dQ, dK, dV, db)
 
 
-def _group_forward(a8, Qg, Kg, Vg, mode, drop=None, head0=0):
+def _group_forward(a8, Qg, Kg, Vg, mode, drop=None, head0=0, bg=None):
     """One head group's forward -> (o_g, what its backward needs).  drop = (p, seed, offset) with p > 0: the group through
-    attention_dropout_forward as the heads head0 .. head0 + hg - 1 of the whole call."""
+    attention_dropout_forward as the heads head0 .. head0 + hg - 1 of the whole call; with the group's score bias bg
+    (drop given, any p): through attention_bias_forward."""
     row, indptr_r, eid_r, indices_r = a8[:4]
+    if bg is not None:
+        og, stats = _ops.attention_bias_forward(row, indptr_r, eid_r, indices_r, Qg, Kg, Vg, bg, *drop, head0)
+        return og, ("bias", og, stats)
     if drop is not None:
         og, stats = _ops.attention_dropout_forward(row, indptr_r, eid_r, indices_r, Qg, Kg, Vg, *drop, head0)
         return og, ("drop", og, stats)
@@ -444,8 +503,10 @@ def _group_forward(a8, Qg, Kg, Vg, mode, drop=None, head0=0):
     return og, (("keep", a) if mode != "recompute" else ("recompute",))
 
 
-def _group_backward(a8, Qg, Kg, Vg, dOg, kept, drop=None, head0=0):
+def _group_backward(a8, Qg, Kg, Vg, dOg, kept, drop=None, head0=0, bg=None, need_db=True):
     row, indptr_r, eid_r, indices_r = a8[:4]
+    if kept[0] == "bias":
+        return _ops.attention_bias_backward(*a8, Qg, Kg, Vg, bg, kept[1], kept[2], dOg, *drop, head0, need_db)
     if kept[0] == "drop":
         return _ops.attention_dropout_backward(*a8, Qg, Kg, Vg, kept[1], kept[2], dOg, *drop, head0)
     if kept[0] == "fused":
@@ -478,6 +539,33 @@ def fused_attention_dropout_step(g, Q, K, V, dO, p, seed, offset=0):
     o.backward(dO)
     _lib.check_errors(sync=False)     # as in attention_step
     return o
+
+
+def fused_attention_bias_step(g, Q, K, V, b, dO, p=0.0, seed=0, offset=0):
+    """fused_attention_dropout_step with the per-edge score bias b, through FusedAttentionBias; returns o (nothing
+    edge-sized is kept but b, and b.grad where b requires it)."""
+    o = FusedAttentionBias.apply(*g.csr_args(), Q, K, V, b, p, seed, offset)
+    o.backward(dO)
+    _lib.check_errors(sync=False)     # as in attention_step
+    return o
+
+
+def attention_bias_step(g, Q, K, V, b, dO, p=0.0, seed=0, offset=0):
+    """The composed yardstick of fused_attention_bias_step: MaskedMMCSR -> s + b -> SparseSoftmax ->
+    (* edge_dropout_mask) -> VectorSPMM; s, a, the mask and their product are (E, h) tensors kept for the backward.
+    Same decisions for the same (p, seed, offset); returns (s, a, o) with s the biased scores and a the undropped
+    weights."""
+    args = g.csr_args()
+    s = MaskedMMCSR.apply(*args, Q, K) + b
+    a = SparseSoftmax.apply(g.row, g.ptr_r, g.eid_r, s)
+    w = a
+    if p > 0:
+        h = 1 if Q.dim() == 2 else Q.size(1)
+        w = a * _ops.edge_dropout_mask(g.row, g.ptr_r, g.eid_r, g.indices_r, h, p, seed, offset, a.dtype)
+    o = VectorSPMM.apply(*args, w, V)
+    o.backward(dO)
+    _lib.check_errors(sync=False)     # as in attention_step
+    return s, a, o
 
 
 def attention_dropout_step(g, Q, K, V, dO, p, seed, offset=0):

@@ -28,7 +28,8 @@ __all__ = ["maskedmm_csr_forward", "maskedmm_csr_backward", "node_mul_edge_forwa
            "node_mul_edge_backward", "sparse_softmax_forward", "sparse_softmax_backward",
            "vector_spmm_forward", "vector_spmm_backward"]
 # extra ops (not in the reference's module): the fused attention step, SURVEY.md 8f N2, and its form with attention
-# dropout (attention_dropout_forward / _backward),
+# dropout (attention_dropout_forward / _backward) and with a per-edge score bias (attention_bias_forward /
+# _backward),
 # the GAT additive attention scores (LeakyReLU(el[i] + er[j]) per edge and head), the fused GAT attention layer and
 # its forms with attention dropout (plus the mask they apply, as an edge tensor, for the composed path), and the GATv2
 # scores (att . LeakyReLU(xl[i] + xr[j]) per edge and head), and the fused GAT layer with a per-edge score term
@@ -254,13 +255,17 @@ def node_mul_edge_backward(row, indptr, eid, A, B, dy):
 
 
 # ---- fused attention step (extra op; the composition wrapper.py:20-30, 8-18, 44-55) ------------------
-def _workspace(like, dtype, backward, e, n_q, n_k, h, d, plan_r, plan_c, dropout=False):
+def _workspace(like, dtype, backward, e, n_q, n_k, h, d, plan_r, plan_c, dropout=False, bias=None):
+    """bias: None, or whether the call with a score bias is a backward that writes db"""
     import ctypes
     nbytes = ctypes.c_int64(0)
     query = lib().graphop_attention_dropout_workspace_bytes if dropout else lib().graphop_attention_workspace_bytes
+    extra = ()
+    if bias is not None:
+        query, extra = lib().graphop_attention_bias_workspace_bytes, (1 if bias else 0,)
     check(query(
         dtype, 1 if backward else 0, e, n_q, n_k, h, d, plan_r.handle if plan_r is not None else _NULL,
-        plan_c.handle if plan_c is not None else _NULL, stream_of(like), ctypes.byref(nbytes)))
+        plan_c.handle if plan_c is not None else _NULL, stream_of(like), *extra, ctypes.byref(nbytes)))
     return torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=like.device), nbytes.value
 
 
@@ -280,9 +285,19 @@ def attention_backward_is_fused(row, indptr_r, eid_r, indices_r, col, indptr_c, 
     return bool(out.value)
 
 
-def _attention_forward(fn, row, indptr, eid, indices, Q, K, V, drop=()):
-    """attention_forward (drop = ()) or attention_dropout_forward (drop = (p, seed, offset, head0)) as `fn`"""
-    _check_csr((row, indptr, eid, indices), _CSR, (Q, "Q"), (K, "K"), (V, "V"))
+def _attn_bias(fn, b, Q, n_edges, h):
+    """b checked against the graph and the heads: (n_edges) for 2-D Q / K / V, else (n_edges, h), in Q's dtype"""
+    _same_dtype(Q, b, "Q", "b")
+    _check_edge_rows(b, "b", n_edges)
+    if tuple(b.shape) != ((n_edges,) if Q.dim() == 2 else (n_edges, h)):
+        raise RuntimeError("%s: b must be (n_edges) for 2-D Q / K / V, else (n_edges, h) with n_edges = %d and h = %d, "
+                           "got b %s, Q %s" % (fn, n_edges, h, tuple(b.shape), tuple(Q.shape)))
+
+
+def _attention_forward(fn, row, indptr, eid, indices, Q, K, V, drop=(), b=None):
+    """attention_forward (drop = ()), attention_dropout_forward (drop = (p, seed, offset, head0)) or, with the score
+    bias b, attention_bias_forward as `fn`"""
+    _check_csr((row, indptr, eid, indices), _CSR, (Q, "Q"), (K, "K"), (V, "V"), *(((b, "b"),) if b is not None else ()))
     _same_dtype(Q, K, "Q", "K")
     _same_dtype(Q, V, "Q", "V")
     if K.shape != V.shape or Q.shape[1:] != K.shape[1:]:
@@ -290,13 +305,18 @@ def _attention_forward(fn, row, indptr, eid, indices, Q, K, V, drop=()):
     e, d = eid.size(0), Q.size(-1)
     h = 1 if Q.dim() == 2 else Q.size(1)
     n_q, n_k = Q.size(0), K.size(0)
+    bias = ()
+    if b is not None:
+        _attn_bias(fn, b, Q, e, h)
+        bias = (ptr(b),)
     o = torch.empty_like(Q)
     stats = torch.empty((n_q, h, 2), dtype=Q.dtype, device=Q.device)
     with _lib.device_guard(Q.device):
         plan = get_plan(row, indptr, eid, indices, n_k)
-        ws, nbytes = _workspace(Q, dtype_code(Q), False, e, n_q, n_k, h, d, plan, None, bool(drop))
+        ws, nbytes = _workspace(Q, dtype_code(Q), False, e, n_q, n_k, h, d, plan, None, bool(drop),
+                                False if b is not None else None)
         check(getattr(lib(), "graphop_" + fn)(
-            dtype_code(Q), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(Q), ptr(K), ptr(V),
+            dtype_code(Q), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(Q), ptr(K), ptr(V), *bias,
             ptr(o), ptr(stats), row.size(0), e, n_q, n_k, h, d, ptr(ws), nbytes, plan.handle,
             stream_of(Q), *drop))
     return [o, stats]
@@ -310,10 +330,11 @@ def attention_forward(row, indptr, eid, indices, Q, K, V):
 
 
 def _attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c,
-                        Q, K, V, o, stats, dO, drop=()):
-    """attention_backward (drop = ()) or attention_dropout_backward (drop = (p, seed, offset, head0)) as `fn`"""
+                        Q, K, V, o, stats, dO, drop=(), b=None, need_db=True):
+    """attention_backward (drop = ()), attention_dropout_backward (drop = (p, seed, offset, head0)) or, with the score
+    bias b, attention_bias_backward as `fn`: then -> [dQ, dK, dV, db], db an empty (0,) tensor with need_db=False"""
     _check_csr((row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c), _CSR_RC,
-               (Q, "Q"), (K, "K"), (V, "V"), (o, "o"), (stats, "stats"))
+               (Q, "Q"), (K, "K"), (V, "V"), *(((b, "b"),) if b is not None else ()), (o, "o"), (stats, "stats"))
     _check_grad(dO, "dO")
     for t, n in ((K, "K"), (V, "V"), (o, "o"), (stats, "stats"), (dO, "dO")):
         _same_dtype(Q, t, "Q", n)
@@ -324,16 +345,25 @@ def _attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_
     if o.shape != Q.shape or dO.shape != Q.shape or stats.numel() != n_q * h * 2:
         raise RuntimeError("%s: o, dO must match Q and stats must be (n_q, h, 2)" % fn)
     dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+    if b is not None:
+        _attn_bias(fn, b, Q, e, h)
     with _lib.device_guard(Q.device):
         plan_r = get_plan(row, indptr_r, eid_r, indices_r, n_k)
         plan_c = get_plan(col, indptr_c, eid_c, indices_c, n_q)
-        ws, nbytes = _workspace(Q, dtype_code(Q), True, e, n_q, n_k, h, d, plan_r, plan_c, bool(drop))
+        bias = dbias = ()
+        if b is not None:
+            # db[e] is written once per row-major slot: only a chunk list that leaves slots out needs the zeros
+            db = (torch.empty_like(b) if plan_r.info.full_coverage else torch.zeros_like(b)) if need_db \
+                else torch.empty((0,), dtype=b.dtype, device=b.device)
+            bias, dbias = (ptr(b),), (ptr(db) if need_db else _NULL,)
+        ws, nbytes = _workspace(Q, dtype_code(Q), True, e, n_q, n_k, h, d, plan_r, plan_c, bool(drop),
+                                bool(need_db) if b is not None else None)
         check(getattr(lib(), "graphop_" + fn)(
             dtype_code(Q), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col),
-            ptr(indptr_c), ptr(eid_c), ptr(indices_c), ptr(Q), ptr(K), ptr(V), ptr(o), ptr(stats),
-            ptr(dO), ptr(dQ), ptr(dK), ptr(dV), row.size(0), col.size(0), e, n_q, n_k, h, d,
+            ptr(indptr_c), ptr(eid_c), ptr(indices_c), ptr(Q), ptr(K), ptr(V), *bias, ptr(o), ptr(stats),
+            ptr(dO), ptr(dQ), ptr(dK), ptr(dV), *dbias, row.size(0), col.size(0), e, n_q, n_k, h, d,
             ptr(ws), nbytes, plan_r.handle, plan_c.handle, stream_of(Q), *drop))
-    return [dQ, dK, dV]
+    return [dQ, dK, dV] if b is None else [dQ, dK, dV, db]
 
 
 def attention_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c,
@@ -732,6 +762,31 @@ def attention_dropout_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, e
                                dO, _drop_args(fn, p, seed, offset) + (_head0(fn, head0),))
 
 
+# ---- per-edge score bias of the fused attention step (extra ops) ------------------------------------
+def attention_bias_forward(row, indptr, eid, indices, Q, K, V, b, p=0.0, seed=0, offset=0, head0=0):
+    """-> [o, stats] of attention_dropout_forward with a term per edge inside the softmax: for edge e = (i, j),
+    s_e = <Q_i, K_j> + b[e], a = row-softmax(s), o[i] = sum_e a_e m_e V[j].  b is indexed by edge id ((n_edges) for 2-D
+    Q / K / V, else (n_edges, h)), has their dtype and is contiguous: a Graphormer-type spatial / edge encoding, a
+    relative positional bias, log w of a weighted graph, or node_mul_edge_forward(Q, xe) for the key-side edge term of
+    TransformerConv(edge_dim=...).  b must be finite: a bias at or below the -1e9 floor of the row maximum is not a mask.
+    stats are those of the biased, undropped scores; (p, seed, offset, head0) as attention_dropout_forward, p = 0: no
+    dropout.  There is no 1 / sqrt(d) scale argument: fold it into Q."""
+    fn = "attention_bias_forward"
+    return _attention_forward(fn, row, indptr, eid, indices, Q, K, V,
+                              _drop_args(fn, p, seed, offset) + (_head0(fn, head0),), b)
+
+
+def attention_bias_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, b, o, stats, dO,
+                            p=0.0, seed=0, offset=0, head0=0, need_db=True):
+    """-> [dQ, dK, dV, db] of attention_bias_forward for the output gradient dO, with the same (p, seed, offset, head0):
+    the weights and their keep decisions are recomputed per slot.  db[e] = ds_e in b's shape is the only edge-sized
+    tensor made; with need_db=False it is an empty (0,) tensor and nothing edge-sized is written.  b must be finite (a
+    bias at or below the -1e9 floor is not a mask)."""
+    fn = "attention_bias_backward"
+    return _attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, o, stats,
+                               dO, _drop_args(fn, p, seed, offset) + (_head0(fn, head0),), b, need_db)
+
+
 # ---- fused GAT attention with an edge term (extra ops) -----------------------------------------------------------
 def _gat_edge_term(el, ee, n_edges, h, fn):
     """ee checked against the graph and the heads: (n_edges) for 1-D el / er, else (n_edges, h), in el's dtype."""
@@ -805,10 +860,11 @@ _SCHEMAS = {
     "gat_edge_attention_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor ee, Tensor V, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0, bool need_dee=True) -> Tensor[]",
 }
 # every op beyond the reference's eight, plus the one query that is not an op
-# ... and the dropout form of the fused attention step: bound here and in the compiled extension, not registered under
-# torch.ops.graphop (the registered set is the table above)
+# ... and the dropout form of the fused attention step and its form with a per-edge score bias: bound here and in the
+# compiled extension, not registered under torch.ops.graphop (the registered set is the table above)
 EXTRA_OPS = [n for n in _SCHEMAS if n not in __all__] + ["attention_backward_is_fused", "attention_dropout_forward",
-                                                         "attention_dropout_backward"]
+                                                         "attention_dropout_backward", "attention_bias_forward",
+                                                         "attention_bias_backward"]
 _torch_lib = None
 
 

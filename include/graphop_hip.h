@@ -722,6 +722,46 @@ GRAPHOP_API int graphop_attention_dropout_backward(int dtype, const int64_t* row
                                        const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream,
                                        double p, uint64_t seed, uint32_t offset, int64_t head0);
 
+/* ---- per-edge score bias for the fused attention step (ABI 8, additive; EXTRA ops) ----------------------------------
+ * The fused step with a term per edge inside the softmax (Graphormer-type spatial / edge encodings, relative positional
+ * biases, weighted graphs with b = log w, the key-side edge term <Q_i, We x_e> of TransformerConv(edge_dim=...), which
+ * graphop_node_mul_edge_forward produces).  For edge e = (i, j) -- i indexes Q / o, j indexes K / V -- and head k, with b
+ * indexed by EDGE ID ((n_edges, h), the dtype of Q, contiguous):
+ *   s_e  = <Q_i, K_j> + b[e, k]                 (one add, after the dot product's reduction)
+ *   a_e  = exp(s_e - m_i) * linv_i              m_i = max(-1e9, row max of s), linv_i = 1 / sum exp(s - m_i)
+ *   o_i  = sum_e a_e m_e V_j                    m_e: the multiplier of graphop_attention_dropout_* (1 at p == 0)
+ *   ds_e = a_e (m_e <dO_i, V_j> - D_i), D_i = <dO_i, o_i>;  db[e, k] = ds_e;  dQ, dK, dV from ds_e and a_e m_e as without b
+ * stats are those of the biased, undropped scores.  b must be FINITE: a bias at or below the -1e9 floor of the row
+ * maximum is not a mask (a row whose scores all lie below the floor does not normalise).  No 1 / sqrt(d) argument.
+ * Arguments as graphop_attention_dropout_forward / _backward with b after V and, in the backward, db after dV.
+ * db == NULL: the gradient of b is not wanted; nothing edge-sized is then written and no kernel stores it.  Otherwise
+ * db[e] is written for every edge id a row-major slot names (each once; the others are left untouched).  The checks of
+ * the undropped op run first, then those of the dropout arguments, then b != NULL (unless n_edges * h == 0).  p == 0
+ * takes no Philox path; empty problems are no-ops that dereference nothing.
+ * Forms: where graphop_attention_backward would run either fused form (and GRAPHOP_ATTN_ROWS is not 0) the backward is
+ * the chunk-driver form with the bias (k_attn_bias_bwd_rows_f32: b and db addressed through the plans' edge ids); the
+ * forward is one chunk-driver pass (k_attn_bias_fwd_rows_f32) for fp32, h == 1, d a power of two in 16..1024 and a
+ * matching plan with sorted rows.  Everything else composes the unfused entry points: s += b after the SDDMM, and the
+ * softmax backward writes ds into db.  workspace: graphop_attention_bias_workspace_bytes(..., with_db, ...) bytes;
+ * with_db != 0 names a backward call with db given, whose composed form holds one E-sized array fewer. */
+GRAPHOP_API int graphop_attention_bias_workspace_bytes(int dtype, int backward, int64_t n_edges, int64_t n_q, int64_t n_k,
+                                           int64_t h, int64_t d, const graphop_plan_t* plan_r,
+                                           const graphop_plan_t* plan_c, void* stream, int with_db, int64_t* bytes_out);
+GRAPHOP_API int graphop_attention_bias_forward(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                                   const int64_t* indices, const void* Q, const void* K, const void* V, const void* b,
+                                   void* o, void* stats, int64_t n_chunks, int64_t n_edges, int64_t n_q, int64_t n_k,
+                                   int64_t h, int64_t d, void* workspace, int64_t workspace_bytes,
+                                   const graphop_plan_t* plan, void* stream, double p, uint64_t seed, uint32_t offset,
+                                   int64_t head0);
+GRAPHOP_API int graphop_attention_bias_backward(int dtype, const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r,
+                                    const int64_t* indices_r, const int64_t* col, const int64_t* indptr_c,
+                                    const int64_t* eid_c, const int64_t* indices_c, const void* Q, const void* K,
+                                    const void* V, const void* b, const void* o, const void* stats, const void* dO,
+                                    void* dQ, void* dK, void* dV, void* db, int64_t n_row_chunks, int64_t n_col_chunks,
+                                    int64_t n_edges, int64_t n_q, int64_t n_k, int64_t h, int64_t d, void* workspace,
+                                    int64_t workspace_bytes, const graphop_plan_t* plan_r, const graphop_plan_t* plan_c,
+                                    void* stream, double p, uint64_t seed, uint32_t offset, int64_t head0);
+
 /* ---- halo pack / unpack of the node-range sharded step (not in the reference: single GPU) --------
  * gather_rows:      dst[i, :] = src[idx[i], :]          (send buffer of the rows peers gather from)
  * scatter_add_rows: dst[idx[i], :] += src[i, :]         (partial gradient rows coming home; idx may
