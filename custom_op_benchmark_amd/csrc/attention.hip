@@ -15,6 +15,10 @@
 // backward is the chunk-driver form with the bias (k_attn_bias_bwd_rows_f32) wherever the undropped op would run either
 // fused form, the fused forward the chunk-driver pass of kernels_attn_bias_fwd.h.  bias == nullptr below is the op
 // without a bias: the same kernels and launches as before.
+// Several heads: where attention_heads.hip's conditions hold (fp32, (h, d) one of its pairs, plans with
+// neighbour ids, the knobs) all three ops run chunk-driver passes over all heads of a row at once
+// (kernels_attn_heads.h), asked for first by attn_forward / attn_backward; h == 1 and every other several-head call go
+// on as before.
 // Reference composition: wrapper.py:20-30 (MaskedMMCSR), :8-18 (SparseSoftmax), :44-55 (VectorSPMM).
 #include "common.h"
 #include "host.h"
@@ -347,7 +351,10 @@ int attn_workspace_bytes(const char* fn, int dtype, int backward, int64_t n_edge
   if (!backward) {
     size_t need = 0;
     int fw = 0;
-    if (plan_r && n_edges * h > 0)
+    if (plan_r && n_edges * h > 0 && h > 1)   // several heads: the form of kernels_attn_heads.h, with or without a bias
+      fw = attn_heads_fwd_rows(plan_r, nullptr, plan_r->info.n_chunks, n_edges, n_q, n_k, h, d, dtype, nullptr, nullptr,
+                               nullptr, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, /*dry_run=*/true, &need);
+    else if (plan_r && n_edges * h > 0)
       fw = bias ? attn_bias_fwd_rows(plan_r, nullptr, plan_r->info.n_chunks, n_edges, n_q, n_k, h, d, dtype, nullptr,
                                      nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream,
                                      /*dry_run=*/true, &need)
@@ -356,6 +363,10 @@ int attn_workspace_bytes(const char* fn, int dtype, int backward, int64_t n_edge
     if (fw < 0) return -fw;
     // the one-pass forward only needs the piece records of shared rows; the composed forward keeps s and a here
     *bytes_out = fw == 1 ? (int64_t)need : (int64_t)SlowWs(nullptr, 2, es, n_edges, h, soft_rows_of(plan_r, n_q)).total;
+    return GRAPHOP_OK;
+  }
+  if (attn_heads_bwd_ok(dtype, h, d, n_edges, n_q, n_k, plan_r, plan_c, (hipStream_t)stream)) {
+    *bytes_out = (int64_t)attn_heads_bwd_workspace(n_q, n_k, h, d);
     return GRAPHOP_OK;
   }
   AttnFast af;
@@ -407,6 +418,9 @@ int attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t* i
     size_t need = 0;
     // with a bias: the chunk-driver pass of kernels_attn_bias_fwd.h (the walk's layouts carry no edge id)
     auto fused_fwd = [&](void* w, int64_t w_bytes, bool dry_run, size_t* needed) {
+      if (h > 1)   // several heads: one chunk-driver pass over all of them (kernels_attn_heads.h)
+        return attn_heads_fwd_rows(pm, (const i64*)eid, n_chunks, n_edges, n_q, n_k, h, d, dtype, Q, K, V,
+                                   bias ? bias->b : nullptr, o, stats, w, w_bytes, st, dry_run, needed, drop, head0);
       if (bias)
         return attn_bias_fwd_rows(pm, (const i64*)eid, n_chunks, n_edges, n_q, n_k, h, d, dtype, Q, K, V, bias->b, o, stats,
                                   w, w_bytes, st, dry_run, needed, drop ? &hd : nullptr);
@@ -470,6 +484,18 @@ int attn_backward(const char* fn, int dtype, const int64_t* row, const int64_t* 
                                              (const i64*)indices_r, n_row_chunks, n_edges) ? plan_r : nullptr;
   const graphop_plan* pc = plan_matches_full(plan_c, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c,
                                              (const i64*)indices_c, n_col_chunks, n_edges) ? plan_c : nullptr;
+  // several heads: the chunk-driver passes over all heads of a row (kernels_attn_heads.h), with or without a bias
+  if (attn_heads_bwd_ok(dtype, h, d, n_edges, n_q, n_k, pr, pc, st)) {
+    const size_t need = attn_heads_bwd_workspace(n_q, n_k, h, d);
+    GO_CHECK_ARG(workspace != nullptr && (size_t)workspace_bytes >= need,
+                 "%s: workspace of %lld bytes needed (graphop_%s), got %lld", fn, (long long)need, ws_fn,
+                 (long long)workspace_bytes);
+    GO_PTR(fn, Q); GO_PTR(fn, K); GO_PTR(fn, V); GO_PTR(fn, o); GO_PTR(fn, stats); GO_PTR(fn, dO);
+    GO_PTR(fn, dQ); GO_PTR(fn, dK); GO_PTR(fn, dV);
+    return attn_heads_backward(pr, pc, (const i64*)eid_r, (const i64*)eid_c, n_row_chunks, n_col_chunks, n_q, n_k, h, d, Q,
+                               K, V, bias ? bias->b : nullptr, o, stats, dO, dQ, dK, dV, bias ? bias->db : nullptr,
+                               workspace, st, drop, head0);
+  }
   AttnFast af;
   // (with a bias the window-owner passes are never launched: only their decision is asked for, no task queue taken)
   const int fast = attn_fast_plan(dtype, h, d, n_edges, n_q, n_k, pr, pc, st, /*dry_run=*/bias != nullptr, &af);
@@ -586,6 +612,10 @@ int graphop_attention_backward_is_fused(int dtype, int64_t n_edges, int64_t n_q,
                                         int64_t d, const graphop_plan_t* plan_r,
                                         const graphop_plan_t* plan_c, void* stream, int* fused_out) {
   GO_CHECK_ARG(fused_out != nullptr, "attention_backward_is_fused: fused_out is NULL");
+  if (attn_heads_bwd_ok(dtype, h, d, n_edges, n_q, n_k, plan_r, plan_c, (hipStream_t)stream)) {
+    *fused_out = 1;
+    return GRAPHOP_OK;
+  }
   AttnFast af;
   const int fast = attn_fast_plan(dtype, h, d, n_edges, n_q, n_k, plan_r, plan_c, (hipStream_t)stream,
                                   /*dry_run=*/true, &af);

@@ -50,6 +50,8 @@ struct Tuning {
   int attn_max_d;         // widest row (floats) the fused window passes are chosen for: beyond 64 the two-row gathers
                           // dominate and the passes measure slower than the unfused ones (d=128: 18.9 vs 16.8 ms)
   int attn_rows;          // chunk-driver fused backward: -1 = by the cost rule, 0 = never, 1 = whenever legal
+  int attn_heads;         // several-head fused forms (kernels_attn_heads.h): -1 = by the cost rule, 0 = never (head groups /
+                          // the composed path as before), 1 = wherever the conditions allow
   int touch_sddmm;        // SDDMM strips: per-task id-line touches (kernels_fast.h: LineTouch): bit 0 ids, bit 1 edge ids
   int walk;               // walk drivers (kernels_walk.h): bit 1 SpMM-type passes over identity-eid (row-major) slots,
                           // bit 2 SpMM-type over permuted (column-major) slots (bit 0 was the SDDMM-type walk kernel of
@@ -94,6 +96,7 @@ struct Tuning {
     attn_k = env_int("GRAPHOP_ATTN_K", 0);
     attn_bpc = env_int("GRAPHOP_ATTN_BPC", 0);
     attn_rows = env_int("GRAPHOP_ATTN_ROWS", -1);
+    attn_heads = env_int("GRAPHOP_ATTN_HEADS", -1);
     attn_max_d = env_int("GRAPHOP_ATTN_MAX_D", 64);
     staged_ids = env_int("GRAPHOP_STAGED_IDS", 7);
     touch_sddmm = env_int("GRAPHOP_TOUCH_SDDMM", 1);
@@ -203,6 +206,23 @@ int attn_bias_fwd_rows(const graphop_plan* plan, const i64* eid, i64 n_chunks, i
                        i64 d, int dtype, const void* Q, const void* K, const void* V, const void* b, void* o,
                        void* stats, void* ws, i64 ws_bytes, hipStream_t st, bool dry_run, size_t* ws_needed,
                        const AttnDrop* drop = nullptr);
+
+// Several-head forms of the fused attention passes (attention_heads.hip; kernels_attn_heads.h): fp32,
+// (h, d) a several-head pair of GO_DISPATCH_GAT_HD, plans with neighbour ids whose id ranges lie inside the tables.
+// attn_heads_fwd_rows: attn_bias_fwd_rows' contract (return values, dry_run, workspace) for h > 1; b == NULL: no bias.
+// attn_heads_bwd_ok: will attn_heads_backward run for this call?  Its workspace is attn_heads_bwd_workspace bytes.
+struct HostDrop;   // host_dropout.h; drop == NULL: no dropout, else the call's heads are the global heads head0 .. head0 + h - 1
+int attn_heads_fwd_rows(const graphop_plan* plan, const i64* eid, i64 n_chunks, i64 n_edges, i64 n_q, i64 n_k, i64 h,
+                        i64 d, int dtype, const void* Q, const void* K, const void* V, const void* b, void* o,
+                        void* stats, void* ws, i64 ws_bytes, hipStream_t st, bool dry_run, size_t* ws_needed,
+                        const HostDrop* drop = nullptr, i64 head0 = 0);
+bool attn_heads_bwd_ok(int dtype, i64 h, i64 d, i64 n_edges, i64 n_q, i64 n_k, const graphop_plan* plan_r,
+                       const graphop_plan* plan_c, hipStream_t st);
+size_t attn_heads_bwd_workspace(i64 n_q, i64 n_k, i64 h, i64 d);
+int attn_heads_backward(const graphop_plan* pr, const graphop_plan* pc, const i64* eid_r, const i64* eid_c,
+                        i64 n_row_chunks, i64 n_col_chunks, i64 n_q, i64 n_k, i64 h, i64 d, const void* Q, const void* K,
+                        const void* V, const void* b, const void* o, const void* stats, const void* dO, void* dQ, void* dK,
+                        void* dV, void* db, void* ws, hipStream_t st, const HostDrop* drop, i64 head0);
 
 int softmax_forward_stats(int dtype, const i64* row, const i64* indptr, const i64* eid, const void* x,
                           void* y, i64 C, i64 E, i64 h, void* ws, i64 ws_rows,

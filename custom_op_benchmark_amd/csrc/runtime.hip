@@ -232,7 +232,7 @@ std::vector<TuneEntry> tune_table() {
       {"dense_detect_min_fill", &t.dense_detect_min_fill},
       {"attn_fused", &t.attn_fused},
       {"attn_window_scale", &t.attn_window_scale}, {"attn_k", &t.attn_k}, {"attn_bpc", &t.attn_bpc},
-      {"attn_rows", &t.attn_rows}, {"attn_fwd_walk", &t.attn_fwd_walk}, {"spmm_selfzero", &t.spmm_selfzero},
+      {"attn_rows", &t.attn_rows}, {"attn_heads", &t.attn_heads}, {"attn_fwd_walk", &t.attn_fwd_walk}, {"spmm_selfzero", &t.spmm_selfzero},
       {"spmm_selfzero_min_mb", &t.spmm_selfzero_min_mb}, {"spmm_flat", &t.spmm_flat},
       {"spmm_flat_cpg", &t.spmm_flat_cpg}, {"spmm_flat_max_mean", &t.spmm_flat_max_mean},
       {"spmm_flat_min_chunks", &t.spmm_flat_min_chunks}, {"staged_ids", &t.staged_ids}, {"attn_max_d", &t.attn_max_d},

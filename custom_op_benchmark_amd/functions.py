@@ -287,6 +287,17 @@ def _head_group(h, d, n_edges=None, n_nodes=None):
     return hg
 
 
+def _heads_per_call(a8, Q, K, h):
+    """Heads per call of the three fused attention classes.  Where the whole (n, h, d) call takes the several-head
+    kernels (attention_backward_is_fused says so for h > 1) that is h: ONE call, no head slices, db
+    written straight into one (E, h) tensor.  Otherwise _head_group's value, as before."""
+    if h <= 1:
+        return 1
+    if _ops.attention_backward_is_fused(*a8, Q, K):
+        return h
+    return _head_group(h, Q.size(-1), a8[2].numel(), max(Q.size(0), K.size(0)))
+
+
 class FusedAttention(Function):
     """o = VectorSPMM(SparseSoftmax(MaskedMMCSR(Q, K)), V) as ONE autograd node (extra op, not in the
     reference): apply(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V).
@@ -296,13 +307,15 @@ class FusedAttention(Function):
     are processed in HEAD GROUPS (round 5): a group's heads are copied to contiguous (n, hg, d) tensors (node-sized
     copies), run through this op's one-group form -- the fused kernels where they apply (one head of d <= 64), the
     unfused entry points otherwise -- and written back into the heads' slices of o / dQ / dK / dV.  No (E, h) tensor
-    ever exists: the E-sized temporaries are (E, hg), one group at a time (FUSED_HEADS_MODE)."""
+    ever exists: the E-sized temporaries are (E, hg), one group at a time (FUSED_HEADS_MODE).
+    Where the several-head kernels apply (fp32, (h, d) one of their pairs) the whole call is ONE fused
+    call instead (_heads_per_call): no head groups, no slices, nothing edge-sized at all."""
 
     @staticmethod
     def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V):
         a8 = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
         h = Q.size(1) if Q.dim() == 3 else 1
-        hg = _head_group(h, Q.size(-1), eid_r.numel(), max(Q.size(0), K.size(0))) if h > 1 else 1
+        hg = _heads_per_call(a8, Q, K, h)
         ctx.groups = None
         if h > 1 and hg < h:
             return _groups_forward(ctx, a8, Q, K, V, h, hg)
@@ -349,8 +362,9 @@ class FusedAttentionDropout(Function):
     mask, and nothing else edge-sized, is kept between them.  Saves (Q, K, V, o, row statistics).  There is no
     1 / sqrt(d) scale argument: fold it into Q.  seed=None draws one from torch's default CPU generator; offset is a
     per-layer / per-step counter.  p = 0 is FusedAttention itself.
-    Several heads run in FusedAttention's head groups (_head_group) and each group's call names its first head, so a
-    grouped call makes the decisions of an ungrouped one.  FUSED_HEADS_MODE is honoured as far as it can be: a group the
+    Several heads take the several-head kernels in one call where they apply (_heads_per_call), else they run in
+    FusedAttention's head groups (_head_group) and each group's call names its first head, so a grouped call makes the
+    decisions of an ungrouped one.  FUSED_HEADS_MODE is honoured as far as it can be: a group the
     fused kernels do not take recomputes s and a in the backward in both modes (keeping a would not spare the mask)."""
 
     @staticmethod
@@ -363,7 +377,7 @@ class FusedAttentionDropout(Function):
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
         ctx.drop = (float(p), int(seed), int(offset))
         h = Q.size(1) if Q.dim() == 3 else 1
-        hg = _head_group(h, Q.size(-1), eid_r.numel(), max(Q.size(0), K.size(0))) if h > 1 else 1
+        hg = _heads_per_call(a8, Q, K, h)
         ctx.groups = None
         if h > 1 and hg < h:
             return _groups_forward(ctx, a8, Q, K, V, h, hg, ctx.drop)
@@ -394,8 +408,10 @@ class FusedAttentionBias(Function):
     maximum is not a mask.  Saves (Q, K, V, b, o, row statistics) and nothing edge-sized but b; the backward makes db
     = ds only where b needs a gradient.  m_e is FusedAttentionDropout's multiplier (1 at p = 0: no dropout); seed=None
     draws one from torch's default CPU generator.  There is no 1 / sqrt(d) scale argument: fold it into Q.
-    Several heads run in FusedAttention's head groups (_head_group): a group gets the contiguous slice b[:, g0:g0 + hg]
-    (an (E, hg) copy), writes its db into its slice of one (E, h) result and names its first head."""
+    Several heads take the several-head kernels in one call where they apply (_heads_per_call: no slices, db written
+    once into one (E, h) tensor); else they run in FusedAttention's head groups (_head_group): a group gets the
+    contiguous slice b[:, g0:g0 + hg] (an (E, hg) copy), writes its db into its slice of one (E, h) result and names
+    its first head."""
 
     @staticmethod
     def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, b, p=0.0, seed=None,
@@ -405,7 +421,7 @@ class FusedAttentionBias(Function):
             seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item()) if float(p) > 0.0 else 0
         ctx.drop = (float(p), int(seed), int(offset))
         h = Q.size(1) if Q.dim() == 3 else 1
-        hg = _head_group(h, Q.size(-1), eid_r.numel(), max(Q.size(0), K.size(0))) if h > 1 else 1
+        hg = _heads_per_call(a8, Q, K, h)
         ctx.groups = None
         if h > 1 and hg < h:
             return _groups_forward(ctx, a8, Q, K, V, h, hg, ctx.drop, b)

@@ -271,7 +271,8 @@ def _workspace(like, dtype, backward, e, n_q, n_k, h, d, plan_r, plan_c, dropout
 
 def attention_backward_is_fused(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K):
     """True when attention_backward will run its fused window passes for this graph and these
-    shapes (fp32, one head, sweepable plans, tables beyond the L2); False when it would compose
+    shapes (fp32, one head, sweepable plans, tables beyond the L2), its chunk-driver passes, or -- several
+    heads of a supported (h, d), DESIGN.md 4.5l -- the several-head passes; False when it would compose
     the unfused ops, recomputing s and a."""
     import ctypes
     d = Q.size(-1)

@@ -742,7 +742,15 @@ GRAPHOP_API int graphop_attention_dropout_backward(int dtype, const int64_t* row
  * the chunk-driver form with the bias (k_attn_bias_bwd_rows_f32: b and db addressed through the plans' edge ids); the
  * forward is one chunk-driver pass (k_attn_bias_fwd_rows_f32) for fp32, h == 1, d a power of two in 16..1024 and a
  * matching plan with sorted rows.  Everything else composes the unfused entry points: s += b after the SDDMM, and the
- * softmax backward writes ds into db.  workspace: graphop_attention_bias_workspace_bytes(..., with_db, ...) bytes;
+ * softmax backward writes ds into db.
+ * Several heads (this op, graphop_attention_* and graphop_attention_dropout_*): fp32 calls whose (h, d) is one of
+ * (2,32) (2,64) (4,16) (4,32) (4,64) (8,8) (8,16) (8,32), with matching plans that carry neighbour ids and id ranges
+ * inside the tables, run chunk-driver passes over all heads of a row at once (k_attn_heads_fwd_rows_f32 -- the
+ * forward also wants sorted rows -- and k_attn_heads_bwd_rows_f32): b and db are then the only edge-sized arrays of the
+ * whole call.  Knob attn_heads (GRAPHOP_ATTN_HEADS): -1 by a cost rule (default), 0 never, 1 wherever these
+ * conditions hold; GRAPHOP_ATTN_ROWS = 0 forbids this form too.  graphop_attention_backward_is_fused answers 1 for
+ * such a call and the three workspace queries report what it needs.
+ * workspace: graphop_attention_bias_workspace_bytes(..., with_db, ...) bytes;
  * with_db != 0 names a backward call with db given, whose composed form holds one E-sized array fewer. */
 GRAPHOP_API int graphop_attention_bias_workspace_bytes(int dtype, int backward, int64_t n_edges, int64_t n_q, int64_t n_k,
                                            int64_t h, int64_t d, const graphop_plan_t* plan_r,
