@@ -129,6 +129,13 @@ _SIGNATURES = {
     + [ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _c64],
     "graphop_attention_bias_backward": [ctypes.c_int] + [_P] * 19 + [_c64] * 7 + [_P, _c64, _P, _P, _P]
     + [ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _c64],
+    # ... with edge features: xe where b is, dxe where db is; the query has no with_db
+    "graphop_attention_edge_workspace_bytes": [ctypes.c_int, ctypes.c_int] + [_c64] * 5 + [_P, _P, _P,
+                                                                                            ctypes.POINTER(_c64)],
+    "graphop_attention_edge_forward": [ctypes.c_int] + [_P] * 10 + [_c64] * 6 + [_P, _c64, _P, _P]
+    + [ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _c64],
+    "graphop_attention_edge_backward": [ctypes.c_int] + [_P] * 19 + [_c64] * 7 + [_P, _c64, _P, _P, _P]
+    + [ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _c64],
 }
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ["graphop_abi_version", "graphop_last_error",
                                                "graphop_plan_destroy", "graphop_memory_bytes", "graphop_tune_key"])

@@ -551,6 +551,84 @@ std::vector<at::Tensor> attention_bias_backward(const at::Tensor& row, const at:
                                  dO, &drop, head0_checked(fn, head0), &b, need_db);
 }
 
+// ---- edge features of the fused attention step (include/graphop_hip.h: graphop_attention_edge_*) ------------------------
+// xe: a contiguous device tensor (n_edges, d) for 2-D Q / K / V, else (n_edges, h, d), in Q's dtype
+void check_attn_edge_rows(const char* fn, const at::Tensor& xe, const at::Tensor& Q, int64_t e) {
+  CHECK_SAME_DTYPE(Q, xe);
+  TORCH_CHECK(xe.dim() == Q.dim() && xe.size(0) == e && xe.sizes().slice(1) == Q.sizes().slice(1),
+              fn, ": xe must be (n_edges, d) for 2-D Q / K / V, else (n_edges, h, d) with n_edges = ", e, ", got xe ",
+              xe.sizes(), ", Q ", Q.sizes());
+  CHECK_CONTIGUOUS(xe); CHECK_CUDA(xe);
+}
+
+std::vector<at::Tensor> attention_edge_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
+                                               const at::Tensor& indices, const at::Tensor& Q, const at::Tensor& K,
+                                               const at::Tensor& V, const at::Tensor& xe, double p, int64_t seed,
+                                               int64_t offset, int64_t head0) {
+  const char* fn = "attention_edge_forward";
+  const DropSpec drop = drop_spec(fn, p, seed, offset);
+  head0_checked(fn, head0);
+  CHECK_CSR(row, indptr, eid, indices);
+  CHECK_INPUT(Q); CHECK_INPUT(K); CHECK_INPUT(V);
+  TORCH_CHECK(K.sizes() == V.sizes() && Q.sizes().slice(1) == K.sizes().slice(1),
+              fn, ": Q (n_q,[h,]d), K and V (n_k,[h,]d) expected");
+  CHECK_SAME_DTYPE(Q, K); CHECK_SAME_DTYPE(Q, V);
+  const int64_t e = eid.size(0), d = Q.size(-1), h = Q.dim() == 2 ? 1 : Q.size(1), n_q = Q.size(0), n_k = K.size(0);
+  check_attn_edge_rows(fn, xe, Q, e);
+  DeviceGuard dg(Q);
+  auto o = at::empty_like(Q);
+  auto stats = at::empty({n_q, h, 2}, Q.options());
+  const auto pp = get_plan(row, indptr, eid, indices, n_k);
+  const auto& pl = *pp;
+  int64_t nbytes = 0;
+  check(graphop_attention_edge_workspace_bytes(dtype_code(Q), 0, e, n_q, n_k, h, d, pl.plan, nullptr, stream_of(Q), &nbytes));
+  auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, Q.options().dtype(at::kByte));
+  check(graphop_attention_edge_forward(dtype_code(Q), ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(V),
+                                       vp(xe), vp(o), vp(stats), row.size(0), e, n_q, n_k, h, d, ws.data_ptr(), nbytes,
+                                       pl.plan, stream_of(Q), drop.p, drop.seed, drop.offset, head0));
+  return {o, stats};
+}
+
+std::vector<at::Tensor> attention_edge_backward(const at::Tensor& row, const at::Tensor& indptr_r,
+                                                const at::Tensor& eid_r, const at::Tensor& indices_r,
+                                                const at::Tensor& col, const at::Tensor& indptr_c,
+                                                const at::Tensor& eid_c, const at::Tensor& indices_c, const at::Tensor& Q,
+                                                const at::Tensor& K, const at::Tensor& V, const at::Tensor& xe,
+                                                const at::Tensor& o, const at::Tensor& stats, const at::Tensor& dO_,
+                                                double p, int64_t seed, int64_t offset, int64_t head0, bool need_dxe) {
+  const char* fn = "attention_edge_backward";
+  const DropSpec drop = drop_spec(fn, p, seed, offset);
+  head0_checked(fn, head0);
+  CHECK_CSR(row, indptr_r, eid_r, indices_r);
+  CHECK_CSR(col, indptr_c, eid_c, indices_c);
+  CHECK_INPUT(Q); CHECK_INPUT(K); CHECK_INPUT(V); CHECK_INPUT(o); CHECK_INPUT(stats);
+  CHECK_CUDA(dO_);
+  const at::Tensor dO = dO_.contiguous();
+  CHECK_SAME_DTYPE(Q, K); CHECK_SAME_DTYPE(Q, V); CHECK_SAME_DTYPE(Q, o); CHECK_SAME_DTYPE(Q, stats); CHECK_SAME_DTYPE(Q, dO);
+  TORCH_CHECK(K.sizes() == V.sizes() && Q.sizes().slice(1) == K.sizes().slice(1),
+              fn, ": Q (n_q,[h,]d), K and V (n_k,[h,]d) expected");
+  const int64_t e = eid_r.size(0), d = Q.size(-1), h = Q.dim() == 2 ? 1 : Q.size(1), n_q = Q.size(0), n_k = K.size(0);
+  TORCH_CHECK(o.sizes() == Q.sizes() && dO.sizes() == Q.sizes() && stats.numel() == n_q * h * 2,
+              fn, ": o, dO must match Q and stats must be (n_q, h, 2)");
+  check_attn_edge_rows(fn, xe, Q, e);
+  DeviceGuard dg(Q);
+  auto dQ = at::empty_like(Q), dK = at::empty_like(K), dV = at::empty_like(V);
+  const auto ppr = get_plan(row, indptr_r, eid_r, indices_r, n_k);
+  const auto ppc = get_plan(col, indptr_c, eid_c, indices_c, n_q);
+  const auto &pr = *ppr, &pc = *ppc;
+  int64_t nbytes = 0;
+  check(graphop_attention_edge_workspace_bytes(dtype_code(Q), 1, e, n_q, n_k, h, d, pr.plan, pc.plan, stream_of(Q), &nbytes));
+  auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, Q.options().dtype(at::kByte));
+  // dxe[e] is written once per row-major slot: only a chunk list that leaves slots out needs the zeros
+  auto dxe = !need_dxe ? at::empty({0}, xe.options()) : (pr.info.full_coverage ? at::empty_like(xe) : at::zeros_like(xe));
+  check(graphop_attention_edge_backward(
+      dtype_code(Q), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c), ip(indices_c),
+      vp(Q), vp(K), vp(V), vp(xe), vp(o), vp(stats), vp(dO), vp(dQ), vp(dK), vp(dV), need_dxe ? vp(dxe) : nullptr,
+      row.size(0), col.size(0), e, n_q, n_k, h, d, ws.data_ptr(), nbytes, pr.plan, pc.plan, stream_of(Q), drop.p,
+      drop.seed, drop.offset, head0));
+  return {dQ, dK, dV, dxe};
+}
+
 // ---- the extra GAT score op (include/graphop_hip.h: graphop_gat_scores_*) ---------------------------------
 int64_t gat_heads(const at::Tensor& el, const at::Tensor& er, const char* fn) {
   CHECK_SAME_DTYPE(el, er);
@@ -1067,6 +1145,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("indices_c"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("b"), py::arg("o"), py::arg("stats"),
         py::arg("dO"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0, py::arg("head0") = 0,
         py::arg("need_db") = true);
+  // (likewise its form with edge features: K_j + xe[e], V_j + xe[e])
+  m.def("attention_edge_forward", &attention_edge_forward,
+        "Fused attention forward with edge features in key and value (extra op)", py::arg("row"), py::arg("indptr"),
+        py::arg("eid"), py::arg("indices"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("xe"), py::arg("p") = 0.0,
+        py::arg("seed") = 0, py::arg("offset") = 0, py::arg("head0") = 0);
+  m.def("attention_edge_backward", &attention_edge_backward,
+        "Fused attention backward with edge features in key and value (extra op)", py::arg("row"), py::arg("indptr_r"),
+        py::arg("eid_r"), py::arg("indices_r"), py::arg("col"), py::arg("indptr_c"), py::arg("eid_c"),
+        py::arg("indices_c"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("xe"), py::arg("o"), py::arg("stats"),
+        py::arg("dO"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0, py::arg("head0") = 0,
+        py::arg("need_dxe") = true);
   m.def("gat_scores_forward", &gat_scores_forward, "GAT additive attention scores forward (extra op)", py::arg("row"),
         py::arg("indptr"), py::arg("eid"), py::arg("indices"), py::arg("el"), py::arg("er"), py::arg("negative_slope") = 0.2);
   m.def("gat_scores_backward", &gat_scores_backward, "GAT additive attention scores backward (extra op)", py::arg("row"),

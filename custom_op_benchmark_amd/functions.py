@@ -404,7 +404,8 @@ class FusedAttentionBias(Function):
     b is indexed by edge id -- (E) with 2-D Q / K / V, (E, h) with 3-D ones -- in their dtype.  Uses: a Graphormer-type
     bias (spatial and edge encodings), a relative positional bias, a weighted graph with b = log w, and the key-side
     edge term of TransformerConv(edge_dim=...), b = node_mul_edge_forward(Q, xe) (through NodeMulEdge, so that its
-    backward turns db into the gradients of Q and xe).  b must be finite: a bias at or below the -1e9 floor of the row
+    backward turns db into the gradients of Q and xe) -- the key side ALONE: that layer also adds the edge row to the
+    value, which no bias can express; FusedAttentionEdge has both terms.  b must be finite: a bias at or below the -1e9 floor of the row
     maximum is not a mask.  Saves (Q, K, V, b, o, row statistics) and nothing edge-sized but b; the backward makes db
     = ds only where b needs a gradient.  m_e is FusedAttentionDropout's multiplier (1 at p = 0: no dropout); seed=None
     draws one from torch's default CPU generator.  There is no 1 / sqrt(d) scale argument: fold it into Q.
@@ -440,6 +441,36 @@ class FusedAttentionBias(Function):
             Q, K, V, b, o, stats = rest
             dQ, dK, dV, db = _ops.attention_bias_backward(*a8, Q, K, V, b, o, stats, dO, *ctx.drop, 0, need_db)
         return (None,) * 8 + (dQ, dK, dV, db if need_db else None, None, None, None)
+
+
+class FusedAttentionEdge(Function):
+    """FusedAttentionDropout with a feature row per edge added to the key AND the value (extra op): for
+    edge e = (i, j) and head k,  kx = K[j] + xe[e],  vx = V[j] + xe[e],  s_e = <Q_i, kx_e>,  o[i] = sum_e softmax_e(s) m_e vx_e:
+    apply(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, xe, p=0.0, seed=None, offset=0).
+    xe is indexed by edge id -- (E, d) with 2-D Q / K / V, (E, h, d) with 3-D ones -- in their dtype, contiguous: the
+    projected edge_attr of TransformerConv(edge_dim=...), of the Dwivedi-Bresson graph transformer, of GraphGPS.  Saves
+    the CSR arrays, (Q, K, V, xe, o, row statistics) and nothing else; the backward makes dxe = ds Q_i + a m dO_i, the only
+    edge-sized tensor, and only where xe needs a gradient.  m_e is FusedAttentionDropout's multiplier (1 at p = 0: no
+    dropout); seed=None draws one from torch's default CPU generator.  There is no 1 / sqrt(d) scale argument: fold it
+    into Q.  One call whatever h: there are no head groups."""
+
+    @staticmethod
+    def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, xe, p=0.0, seed=None,
+                offset=0):
+        a8 = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item()) if float(p) > 0.0 else 0
+        ctx.drop = (float(p), int(seed), int(offset))
+        o, stats = _ops.attention_edge_forward(row, indptr_r, eid_r, indices_r, Q, K, V, xe, *ctx.drop, 0)
+        ctx.save_for_backward(*a8, Q, K, V, xe, o, stats)
+        return o
+
+    @staticmethod
+    def backward(ctx, dO):
+        a8, (Q, K, V, xe, o, stats) = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
+        need_dxe = ctx.needs_input_grad[11]
+        dQ, dK, dV, dxe = _ops.attention_edge_backward(*a8, Q, K, V, xe, o, stats, dO, *ctx.drop, 0, need_dxe)
+        return (None,) * 8 + (dQ, dK, dV, dxe if need_dxe else None, None, None, None)
 
 
 def _head_slice(x, g0, hg):
@@ -579,6 +610,39 @@ def attention_bias_step(g, Q, K, V, b, dO, p=0.0, seed=0, offset=0):
         h = 1 if Q.dim() == 2 else Q.size(1)
         w = a * _ops.edge_dropout_mask(g.row, g.ptr_r, g.eid_r, g.indices_r, h, p, seed, offset, a.dtype)
     o = VectorSPMM.apply(*args, w, V)
+    o.backward(dO)
+    _lib.check_errors(sync=False)     # as in attention_step
+    return s, a, o
+
+
+def fused_attention_edge_step(g, Q, K, V, xe, dO, p=0.0, seed=0, offset=0):
+    """fused_attention_dropout_step with the edge rows xe in key and value, through FusedAttentionEdge; returns o
+    (nothing edge-sized is kept but xe, and xe.grad where xe requires it)."""
+    o = FusedAttentionEdge.apply(*g.csr_args(), Q, K, V, xe, p, seed, offset)
+    o.backward(dO)
+    _lib.check_errors(sync=False)     # as in attention_step
+    return o
+
+
+def attention_edge_step(g, Q, K, V, xe, dO, p=0.0, seed=0, offset=0):
+    """The composed yardstick of fused_attention_edge_step, for tests and timing only: torch index_selects of Q, K and V
+    by slot, + xe[eid], SparseSoftmax, (* edge_dropout_mask), a segment sum -- K[dst] + xe, V[dst] + xe and their
+    products are (E, h, d) tensors kept for the backward.  The chunk list must name every slot.  Same decisions as the
+    fused step for the same (p, seed, offset); returns (s, a, o) with s, a (E, h) by edge id, a the undropped weights."""
+    shape = Q.shape
+    h = 1 if Q.dim() == 2 else Q.size(1)
+    q3, k3, v3, xe3 = (x.reshape(x.size(0), h, x.size(-1)) for x in (Q, K, V, xe))
+    slot_row = torch.repeat_interleave(g.row, g.ptr_r[1:] - g.ptr_r[:-1])
+    xs = xe3.index_select(0, g.eid_r)
+    kx = k3.index_select(0, g.indices_r) + xs
+    vx = v3.index_select(0, g.indices_r) + xs
+    s_slot = (q3.index_select(0, slot_row) * kx).sum(-1)
+    s = torch.zeros_like(s_slot).index_copy(0, g.eid_r, s_slot)
+    a = SparseSoftmax.apply(g.row, g.ptr_r, g.eid_r, s)
+    w = a
+    if p > 0:
+        w = a * _ops.edge_dropout_mask(g.row, g.ptr_r, g.eid_r, g.indices_r, h, p, seed, offset, a.dtype).reshape(a.shape)
+    o = torch.zeros_like(q3).index_add(0, slot_row, w.index_select(0, g.eid_r).unsqueeze(-1) * vx).reshape(shape)
     o.backward(dO)
     _lib.check_errors(sync=False)     # as in attention_step
     return s, a, o

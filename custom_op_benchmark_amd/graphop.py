@@ -29,7 +29,7 @@ __all__ = ["maskedmm_csr_forward", "maskedmm_csr_backward", "node_mul_edge_forwa
            "vector_spmm_forward", "vector_spmm_backward"]
 # extra ops (not in the reference's module): the fused attention step, SURVEY.md 8f N2, and its form with attention
 # dropout (attention_dropout_forward / _backward) and with a per-edge score bias (attention_bias_forward /
-# _backward),
+# _backward) and with edge features in key and value (attention_edge_forward / _backward),
 # the GAT additive attention scores (LeakyReLU(el[i] + er[j]) per edge and head), the fused GAT attention layer and
 # its forms with attention dropout (plus the mask they apply, as an edge tensor, for the composed path), and the GATv2
 # scores (att . LeakyReLU(xl[i] + xr[j]) per edge and head), and the fused GAT layer with a per-edge score term
@@ -769,7 +769,8 @@ def attention_bias_forward(row, indptr, eid, indices, Q, K, V, b, p=0.0, seed=0,
     s_e = <Q_i, K_j> + b[e], a = row-softmax(s), o[i] = sum_e a_e m_e V[j].  b is indexed by edge id ((n_edges) for 2-D
     Q / K / V, else (n_edges, h)), has their dtype and is contiguous: a Graphormer-type spatial / edge encoding, a
     relative positional bias, log w of a weighted graph, or node_mul_edge_forward(Q, xe) for the key-side edge term of
-    TransformerConv(edge_dim=...).  b must be finite: a bias at or below the -1e9 floor of the row maximum is not a mask.
+    TransformerConv(edge_dim=...) alone (that layer also adds the edge row to the value: attention_edge_forward has both
+    terms).  b must be finite: a bias at or below the -1e9 floor of the row maximum is not a mask.
     stats are those of the biased, undropped scores; (p, seed, offset, head0) as attention_dropout_forward, p = 0: no
     dropout.  There is no 1 / sqrt(d) scale argument: fold it into Q."""
     fn = "attention_bias_forward"
@@ -786,6 +787,98 @@ def attention_bias_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_
     fn = "attention_bias_backward"
     return _attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, o, stats,
                                dO, _drop_args(fn, p, seed, offset) + (_head0(fn, head0),), b, need_db)
+
+
+# ---- edge features of the fused attention step: K_j + xe[e], V_j + xe[e] (extra ops) ----------------
+def _attn_edge_rows(fn, xe, Q, n_edges):
+    """xe checked against the graph and Q: a contiguous device tensor (n_edges, d) for 2-D Q / K / V, else
+    (n_edges, h, d), in Q's dtype.  The C ABI takes a raw pointer: each of these would read out of bounds or garbage."""
+    _same_dtype(Q, xe, "Q", "xe")
+    if tuple(xe.shape) != (n_edges,) + tuple(Q.shape[1:]):
+        raise RuntimeError("%s: xe must be (n_edges, d) for 2-D Q / K / V, else (n_edges, h, d) with n_edges = %d, "
+                           "got xe %s, Q %s" % (fn, n_edges, tuple(xe.shape), tuple(Q.shape)))
+    if not xe.is_contiguous():
+        raise RuntimeError("xe must be contiguous")
+    if not xe.is_cuda:
+        raise RuntimeError("xe must be a CUDA tensor")
+
+
+def _attn_edge_workspace(like, backward, e, n_q, n_k, h, d, plan_r, plan_c):
+    import ctypes
+    nbytes = ctypes.c_int64(0)
+    check(lib().graphop_attention_edge_workspace_bytes(
+        dtype_code(like), 1 if backward else 0, e, n_q, n_k, h, d, plan_r.handle,
+        plan_c.handle if plan_c is not None else _NULL, stream_of(like), ctypes.byref(nbytes)))
+    return torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=like.device), nbytes.value
+
+
+def attention_edge_forward(row, indptr, eid, indices, Q, K, V, xe, p=0.0, seed=0, offset=0, head0=0):
+    """-> [o, stats] of the fused attention step with a feature row per edge added to the key AND the value: for edge
+    e = (i, j),  kx = K[j] + xe[e],  vx = V[j] + xe[e],  s_e = <Q_i, kx_e>,  a = row-softmax(s),  o[i] = sum_e a_e m_e vx_e
+    (TransformerConv(edge_dim=...): out = alpha * (value_j + edge_attr); the Dwivedi-Bresson and GraphGPS edge-featured
+    graph transformers).  xe is indexed by edge id ((n_edges, d) for 2-D Q / K / V, else (n_edges, h, d)), has their
+    dtype and is contiguous; parallel edges share a dropout decision and have each their own row.  stats (n_q, h, 2) =
+    (row max floored at -1e9, 1 / sum exp) of the undropped scores, (-1e9, 0) and o = 0 for rows without edges;
+    (p, seed, offset, head0) as attention_dropout_forward, p = 0: no dropout.  Nothing edge-sized is made.  There is no
+    1 / sqrt(d) scale argument (fold it into Q) and no bias argument."""
+    fn = "attention_edge_forward"
+    drop = _drop_args(fn, p, seed, offset) + (_head0(fn, head0),)
+    _check_csr((row, indptr, eid, indices), _CSR, (Q, "Q"), (K, "K"), (V, "V"))
+    _same_dtype(Q, K, "Q", "K")
+    _same_dtype(Q, V, "Q", "V")
+    if K.shape != V.shape or Q.shape[1:] != K.shape[1:]:
+        raise RuntimeError("%s: Q (n_q,[h,]d), K and V (n_k,[h,]d) expected" % fn)
+    e, d = eid.size(0), Q.size(-1)
+    h = 1 if Q.dim() == 2 else Q.size(1)
+    n_q, n_k = Q.size(0), K.size(0)
+    _attn_edge_rows(fn, xe, Q, e)
+    o = torch.empty_like(Q)
+    stats = torch.empty((n_q, h, 2), dtype=Q.dtype, device=Q.device)
+    with _lib.device_guard(Q.device):
+        plan = get_plan(row, indptr, eid, indices, n_k)
+        ws, nbytes = _attn_edge_workspace(Q, False, e, n_q, n_k, h, d, plan, None)
+        check(lib().graphop_attention_edge_forward(
+            dtype_code(Q), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(Q), ptr(K), ptr(V), ptr(xe),
+            ptr(o), ptr(stats), row.size(0), e, n_q, n_k, h, d, ptr(ws), nbytes, plan.handle, stream_of(Q), *drop))
+    return [o, stats]
+
+
+def attention_edge_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, xe, o, stats, dO,
+                            p=0.0, seed=0, offset=0, head0=0, need_dxe=True):
+    """-> [dQ, dK, dV, dxe] of attention_edge_forward for the output gradient dO, with the same (p, seed, offset,
+    head0): the weights and their keep decisions are recomputed per slot.  dxe[e] = ds_e Q_i + a_e m_e dO_i in xe's
+    shape is the only edge-sized tensor made (edge ids that no row-major slot names get 0); with need_dxe=False it is
+    an empty (0,) tensor and nothing edge-sized is written."""
+    fn = "attention_edge_backward"
+    drop = _drop_args(fn, p, seed, offset) + (_head0(fn, head0),)
+    _check_csr((row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c), _CSR_RC,
+               (Q, "Q"), (K, "K"), (V, "V"), (o, "o"), (stats, "stats"))
+    _check_grad(dO, "dO")
+    for t, n in ((K, "K"), (V, "V"), (o, "o"), (stats, "stats"), (dO, "dO")):
+        _same_dtype(Q, t, "Q", n)
+    dO = dO.contiguous()
+    if K.shape != V.shape or Q.shape[1:] != K.shape[1:]:
+        raise RuntimeError("%s: Q (n_q,[h,]d), K and V (n_k,[h,]d) expected" % fn)
+    e, d = eid_r.size(0), Q.size(-1)
+    h = 1 if Q.dim() == 2 else Q.size(1)
+    n_q, n_k = Q.size(0), K.size(0)
+    if o.shape != Q.shape or dO.shape != Q.shape or stats.numel() != n_q * h * 2:
+        raise RuntimeError("%s: o, dO must match Q and stats must be (n_q, h, 2)" % fn)
+    _attn_edge_rows(fn, xe, Q, e)
+    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+    with _lib.device_guard(Q.device):
+        plan_r = get_plan(row, indptr_r, eid_r, indices_r, n_k)
+        plan_c = get_plan(col, indptr_c, eid_c, indices_c, n_q)
+        # dxe[e] is written once per row-major slot: only a chunk list that leaves slots out needs the zeros
+        dxe = (torch.empty_like(xe) if plan_r.info.full_coverage else torch.zeros_like(xe)) if need_dxe \
+            else torch.empty((0,), dtype=xe.dtype, device=xe.device)
+        ws, nbytes = _attn_edge_workspace(Q, True, e, n_q, n_k, h, d, plan_r, plan_c)
+        check(lib().graphop_attention_edge_backward(
+            dtype_code(Q), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c), ptr(eid_c),
+            ptr(indices_c), ptr(Q), ptr(K), ptr(V), ptr(xe), ptr(o), ptr(stats), ptr(dO), ptr(dQ), ptr(dK), ptr(dV),
+            ptr(dxe) if need_dxe else _NULL, row.size(0), col.size(0), e, n_q, n_k, h, d, ptr(ws), nbytes,
+            plan_r.handle, plan_c.handle, stream_of(Q), *drop))
+    return [dQ, dK, dV, dxe]
 
 
 # ---- fused GAT attention with an edge term (extra ops) -----------------------------------------------------------
@@ -861,11 +954,12 @@ _SCHEMAS = {
     "gat_edge_attention_backward": "(Tensor row, Tensor indptr_r, Tensor eid_r, Tensor indices_r, Tensor col, Tensor indptr_c, Tensor eid_c, Tensor indices_c, Tensor el, Tensor er, Tensor ee, Tensor V, Tensor o, Tensor stats, Tensor dO, float negative_slope=0.2, float p=0.0, int seed=0, int offset=0, bool need_dee=True) -> Tensor[]",
 }
 # every op beyond the reference's eight, plus the one query that is not an op
-# ... and the dropout form of the fused attention step and its form with a per-edge score bias: bound here and in the
-# compiled extension, not registered under torch.ops.graphop (the registered set is the table above)
+# ... and the dropout form of the fused attention step and its forms with a per-edge score bias and with edge features
+# (attention_edge_*): bound here and in the compiled extension, not registered under torch.ops.graphop (the registered set is the table above)
 EXTRA_OPS = [n for n in _SCHEMAS if n not in __all__] + ["attention_backward_is_fused", "attention_dropout_forward",
                                                          "attention_dropout_backward", "attention_bias_forward",
-                                                         "attention_bias_backward"]
+                                                         "attention_bias_backward", "attention_edge_forward",
+                                                         "attention_edge_backward"]
 _torch_lib = None
 
 

@@ -770,6 +770,52 @@ GRAPHOP_API int graphop_attention_bias_backward(int dtype, const int64_t* row, c
                                     int64_t workspace_bytes, const graphop_plan_t* plan_r, const graphop_plan_t* plan_c,
                                     void* stream, double p, uint64_t seed, uint32_t offset, int64_t head0);
 
+/* ---- edge features in the fused attention step: K_j + xe[e], V_j + xe[e] (ABI 8, additive; EXTRA ops) --------------
+ * The fused step with a feature row per edge added to the key AND the value (TransformerConv(edge_dim=...):
+ * out = alpha * (value_j + edge_attr); the Dwivedi-Bresson and GraphGPS edge-featured graph transformers).  For edge
+ * e = (i, j) -- i indexes Q / o, j indexes K / V -- and head k, with xe indexed by EDGE ID ((n_edges, h, d), the dtype
+ * of Q / K / V, contiguous):
+ *   kx_e = K_j + xe[e]        vx_e = V_j + xe[e]
+ *   s_e  = <Q_i, kx_e>        m_i = max(-1e9, row max of s)   linv_i = 1 / sum_e exp(s_e - m_i)   a_e = exp(s_e - m_i) linv_i
+ *   o_i  = sum_e a_e mult_e vx_e           mult_e: the multiplier of graphop_attention_dropout_* for (i, j, head0 + k), 1 at p == 0
+ *   D_i  = <dO_i, o_i>        da_e = mult_e <dO_i, vx_e>      ds_e = a_e (da_e - D_i)
+ *   dQ_i = sum_e ds_e kx_e    dK_j = sum_e ds_e Q_i           dV_j = sum_e a_e mult_e dO_i
+ *   dxe[e] = ds_e Q_i + a_e mult_e dO_i
+ * stats (n_q, h, 2) = (m_i, linv_i) of the undropped scores; rows without edges get o = 0 and stats = (-1e9, 0).
+ * Parallel edges share a dropout decision and have each their own xe row.  No 1 / sqrt(d) argument (fold it into Q), no
+ * bias argument.  Arguments as graphop_attention_bias_forward / _backward with xe where b is and dxe where db is.
+ * dxe is the only edge-sized array made.  dxe == NULL: the gradient of xe is not wanted; nothing edge-sized is then
+ * written and no kernel stores it.  Otherwise dxe[e] is written for every edge id a row-major slot names (each once; the
+ * others are left untouched: zero-fill dxe first where the chunk list may leave slots out).  The checks of
+ * graphop_attention_forward run first, then those of the dropout arguments (head0 included), then xe != NULL (unless
+ * n_edges * h * d == 0), then the workspace.  p == 0 takes no Philox path; empty problems are no-ops that dereference
+ * nothing.  A plan must bound the ids by n_q and n_k (an error otherwise).
+ * Forms: fp32 calls whose (h, d) is one of (1,64) (2,32) (2,64) (4,16) (4,32) (4,64) (8,8) (8,16) (8,32), with 16-byte
+ * aligned operands and ids below 2^31, run the chunk-driver passes of the several-head kernels with the edge row streamed
+ * per slot (kernels_attn_edge.h): the forward (k_attn_edge_fwd_rows_f32) with a matching plan with sorted rows and
+ * neighbour ids, each backward pass (k_attn_edge_bwd_rows_f32) with a matching plan of its orientation.  Everything else
+ * (fp64, other shapes, no plan, shuffled chunks in the forward, misaligned xe / dxe, GRAPHOP_FORCE_GENERIC) runs the
+ * generic kernels k_attn_edge_*_generic, one wave per chunk: the op works for every valid call and never composes.
+ * workspace: graphop_attention_edge_workspace_bytes bytes (forward: the piece records of rows that lane groups share;
+ * backward: the packed operand tables and the per-(row, head) statistics). */
+GRAPHOP_API int graphop_attention_edge_workspace_bytes(int dtype, int backward, int64_t n_edges, int64_t n_q, int64_t n_k,
+                                           int64_t h, int64_t d, const graphop_plan_t* plan_r,
+                                           const graphop_plan_t* plan_c, void* stream, int64_t* bytes_out);
+GRAPHOP_API int graphop_attention_edge_forward(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                                   const int64_t* indices, const void* Q, const void* K, const void* V, const void* xe,
+                                   void* o, void* stats, int64_t n_chunks, int64_t n_edges, int64_t n_q, int64_t n_k,
+                                   int64_t h, int64_t d, void* workspace, int64_t workspace_bytes,
+                                   const graphop_plan_t* plan, void* stream, double p, uint64_t seed, uint32_t offset,
+                                   int64_t head0);
+GRAPHOP_API int graphop_attention_edge_backward(int dtype, const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r,
+                                    const int64_t* indices_r, const int64_t* col, const int64_t* indptr_c,
+                                    const int64_t* eid_c, const int64_t* indices_c, const void* Q, const void* K,
+                                    const void* V, const void* xe, const void* o, const void* stats, const void* dO,
+                                    void* dQ, void* dK, void* dV, void* dxe, int64_t n_row_chunks, int64_t n_col_chunks,
+                                    int64_t n_edges, int64_t n_q, int64_t n_k, int64_t h, int64_t d, void* workspace,
+                                    int64_t workspace_bytes, const graphop_plan_t* plan_r, const graphop_plan_t* plan_c,
+                                    void* stream, double p, uint64_t seed, uint32_t offset, int64_t head0);
+
 /* ---- halo pack / unpack of the node-range sharded step (not in the reference: single GPU) --------
  * gather_rows:      dst[i, :] = src[idx[i], :]          (send buffer of the rows peers gather from)
  * scatter_add_rows: dst[idx[i], :] += src[i, :]         (partial gradient rows coming home; idx may
