@@ -22,6 +22,7 @@
 // Reference composition: wrapper.py:20-30 (MaskedMMCSR), :8-18 (SparseSoftmax), :44-55 (VectorSPMM).
 #include "common.h"
 #include "host.h"
+#include "host_attn_rows.h"
 #include "host_dropout.h"
 #include "kernels_attn_bias.h"
 
@@ -263,31 +264,8 @@ using namespace graphop;
 
 namespace {
 
-// the checks every entry point of the op makes first, stated once
-int attn_check(const char* fn, int dtype, i64 n_row_chunks, i64 n_col_chunks, i64 n_edges, i64 n_q, i64 n_k, i64 h,
-               i64 d) {
-  GO_CHECK_ARG(dtype == GRAPHOP_F32 || dtype == GRAPHOP_F64, "%s: bad dtype", fn);
-  GO_CHECK_ARG(n_row_chunks >= 0 && n_col_chunks >= 0 && n_edges >= 0 && n_q >= 0 && n_k >= 0 && h >= 1 && d >= 0,
-               "%s: negative size", fn);
-  return GRAPHOP_OK;
-}
-
-// the dropout arguments of the *_dropout_* entry points as they arrive; checked after the checks above
-struct DropIn {
-  double p;
-  uint64_t seed;
-  uint32_t offset;
-  i64 head0;
-};
-
-int attn_drop_check(const char* fn, const DropIn& in, i64 n_q, i64 n_k, HostDrop* out) {
-  GO_TRY(drop_check(fn, in.p, in.seed, n_q, n_k, in.offset, out));
-  GO_CHECK_ARG(in.head0 >= 0 && in.head0 < ((i64)1 << 32), "%s: head0 must be in [0, 2^32), got %lld", fn,
-               (long long)in.head0);
-  return GRAPHOP_OK;
-}
-
-// the bias arguments of the *_bias_* entry points as they arrive; checked after the dropout arguments
+// the bias arguments of the *_bias_* entry points as they arrive; checked after the dropout arguments (attn_check and
+// attn_drop_check, host_attn_rows.h, come first)
 struct BiasIn {
   const void* b;   // (n_edges, h) by edge id
   void* db;        // backward: NULL = the gradient of b is not wanted (nothing edge-sized is then written)

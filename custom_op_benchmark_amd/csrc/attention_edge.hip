@@ -9,6 +9,7 @@
 // force_generic selects the generic kernels.  p == 0 takes the kernels without the keep decision.
 #include "common.h"
 #include "host.h"
+#include "host_attn_rows.h"
 #include "host_dropout.h"
 #include "host_gat.h"
 #include "kernels_attn_edge.h"
@@ -16,34 +17,6 @@
 using namespace graphop;
 
 namespace {
-
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
-// attn_check of attention.hip, restated: the checks every entry point of the attention ops makes first
-int edge_check(const char* fn, int dtype, i64 n_row_chunks, i64 n_col_chunks, i64 n_edges, i64 n_q, i64 n_k, i64 h, i64 d) {
-  GO_CHECK_ARG(dtype == GRAPHOP_F32 || dtype == GRAPHOP_F64, "%s: bad dtype", fn);
-  GO_CHECK_ARG(n_row_chunks >= 0 && n_col_chunks >= 0 && n_edges >= 0 && n_q >= 0 && n_k >= 0 && h >= 1 && d >= 0,
-               "%s: negative size", fn);
-  return GRAPHOP_OK;
-}
-
-// attn_drop_check of attention.hip, restated: the dropout arguments, head0 included
-int edge_drop_check(const char* fn, double p, uint64_t seed, uint32_t offset, i64 head0, i64 n_q, i64 n_k, HostDrop* out) {
-  GO_TRY(drop_check(fn, p, seed, n_q, n_k, offset, out));
-  GO_CHECK_ARG(head0 >= 0 && head0 < ((i64)1 << 32), "%s: head0 must be in [0, 2^32), got %lld", fn, (long long)head0);
-  return GRAPHOP_OK;
-}
-
-// attn_heads_geometry's rule (attention_heads.hip keeps it in its anonymous namespace): chunks per lane group and lane
-// groups of a pass over n_chunks chunks, four rounds of resident workgroups wanted
-inline void edge_geometry(i64 n_chunks, i64* cpg_out, i64* groups_out) {
-  constexpr int GPB = kFastBlock / kGatGroup;
-  const i64 groups_wanted = (i64)tuning().n_cu * GPB * 4;
-  i64 cpg = n_chunks / (groups_wanted > 0 ? groups_wanted : 1);
-  cpg = cpg < 1 ? 1 : (cpg > 16 ? 16 : cpg);
-  *cpg_out = cpg;
-  *groups_out = ceil_div(n_chunks, cpg);
-}
 
 // what the fast kernels ask of the shape (the pointers are checked where they are known: gat_hd_fast_ok)
 inline bool edge_shape_ok(int dtype, i64 h, i64 d, i64 n_edges, i64 n_q, i64 n_k) {
@@ -54,18 +27,6 @@ inline bool edge_shape_ok(int dtype, i64 h, i64 d, i64 n_edges, i64 n_q, i64 n_k
 inline bool edge_plan_ok(const graphop_plan* plan, i64 n_own, i64 n_tab) {
   return plan && plan->indices && plan->info.max_row < n_own && plan->info.max_index < n_tab;
 }
-
-struct EdgeFwdWs {
-  size_t o_row, o_ml, o_po, o_m, o_l, total;
-  EdgeFwdWs(i64 np, i64 n_q, i64 h, i64 F) {
-    o_row = 0;
-    o_ml = o_row + up256(sizeof(int) * (size_t)np);
-    o_po = o_ml + up256(sizeof(float) * 2 * (size_t)(np * h));
-    o_m = o_po + up256(sizeof(float) * (size_t)(np * F));
-    o_l = o_m + up256(sizeof(float) * (size_t)(n_q * h));
-    total = o_l + up256(sizeof(float) * (size_t)(n_q * h));
-  }
-};
 
 // fast: (K | V), (Q | dO) packed and stats4 per (row, head); generic: P (n_q, h, 4) alone, at offset 0
 struct EdgeBwdWs {
@@ -83,7 +44,7 @@ inline bool edge_fwd_fast_shape(int dtype, i64 h, i64 d, i64 n_edges, i64 n_q, i
                                 i64 n_chunks, i64* cpg, i64* groups) {
   if (!edge_shape_ok(dtype, h, d, n_edges, n_q, n_k) || !edge_plan_ok(plan, n_q, n_k)) return false;
   if (!plan->info.rows_sorted || n_q >= kWalkRowMask || n_chunks == 0) return false;
-  edge_geometry(n_chunks, cpg, groups);
+  attn_rows_geometry(n_chunks, cpg, groups);
   return 2 * *groups < 0x7fffffffLL;
 }
 
@@ -104,7 +65,7 @@ int launch_edge_rows(const char* tag, const graphop_plan* plan, const i64* eid, 
   ProfScope prof(tag, st, "k_attn_edge_bwd_rows_f32");
   const bool owned = plan->info.rows_sorted != 0, dropped = drop != nullptr;
   i64 cpg, groups;
-  edge_geometry(n_chunks, &cpg, &groups);
+  attn_rows_geometry(n_chunks, &cpg, &groups);
   const unsigned nb = (unsigned)ceil_div(groups, kFastBlock / kGatGroup);
   GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
     hipLaunchKernelGGL((k_attn_edge_bwd_rows_f32<H, D, COL, OWNED, DROP>), dim3(nb), dim3(kFastBlock), 0, st,
@@ -132,7 +93,7 @@ int graphop_attention_edge_workspace_bytes(int dtype, int backward, int64_t n_ed
   if (!backward) {
     i64 cpg, groups;   // the generic forward keeps its sums in stats: no workspace
     if (plan_r && edge_fwd_fast_shape(dtype, h, d, n_edges, n_q, n_k, plan_r, plan_r->info.n_chunks, &cpg, &groups))
-      *bytes_out = (int64_t)EdgeFwdWs(2 * groups, n_q, h, h * d).total;
+      *bytes_out = (int64_t)AttnRowsFwdWs(2 * groups, n_q, h, h * d).total;
     return GRAPHOP_OK;
   }
   const bool fast = edge_shape_ok(dtype, h, d, n_edges, n_q, n_k) &&
@@ -149,9 +110,9 @@ int graphop_attention_edge_forward(int dtype, const int64_t* row, const int64_t*
                                    int64_t head0) {
   const char* fn = "attention_edge_forward";
   GO_TRY(check_async_error(false));
-  GO_TRY(edge_check(fn, dtype, n_chunks, 0, n_edges, n_q, n_k, h, d));
+  GO_TRY(attn_check(fn, dtype, n_chunks, 0, n_edges, n_q, n_k, h, d));
   HostDrop hdrop;
-  GO_TRY(edge_drop_check(fn, p, seed, offset, head0, n_q, n_k, &hdrop));
+  GO_TRY(attn_drop_check(fn, DropIn{p, seed, offset, head0}, n_q, n_k, &hdrop));
   GO_CHECK_ARG(n_edges * h * d == 0 || xe != nullptr, "%s: xe is NULL", fn);
   const HostDrop* drop = p > 0.0 ? &hdrop : nullptr;
   hipStream_t st = (hipStream_t)stream;
@@ -166,7 +127,7 @@ int graphop_attention_edge_forward(int dtype, const int64_t* row, const int64_t*
               edge_fwd_fast_shape(dtype, h, d, n_edges, n_q, n_k, pm, n_chunks, &cpg, &groups) &&
               gat_hd_fast_ok(dtype, h, d, n_edges, n_q, n_k, {Q, K, V, xe, o, stats, workspace});
   const i64 np = 2 * groups;
-  const EdgeFwdWs w(np, n_q, h, F);
+  const AttnRowsFwdWs w(np, n_q, h, F);
   if (fast)
     GO_CHECK_ARG(workspace != nullptr && workspace_bytes >= 0 && (size_t)workspace_bytes >= w.total,
                  "%s: workspace of %lld bytes needed (graphop_attention_edge_workspace_bytes), got %lld", fn,
@@ -200,7 +161,7 @@ int graphop_attention_edge_forward(int dtype, const int64_t* row, const int64_t*
       const i64 most = np > n_q * h ? np : n_q * h;
       const unsigned fb = (unsigned)(ceil_div(most, 256) > 4096 ? 4096 : ceil_div(most, 256));
       hipLaunchKernelGGL((k_fill<int>), dim3(fb), dim3(256), 0, st, a.p_row, np, -1);
-      hipLaunchKernelGGL((k_fill<float>), dim3(fb), dim3(256), 0, st, Mtmp, n_q * h, kAttnEdgeNegBig);
+      hipLaunchKernelGGL((k_fill<float>), dim3(fb), dim3(256), 0, st, Mtmp, n_q * h, kAttnRowsNegBig);
       hipLaunchKernelGGL((k_fill<float>), dim3(fb), dim3(256), 0, st, Ltmp, n_q * h, 0.f);
       GO_LAUNCH_CHECK();
     }
@@ -263,9 +224,9 @@ int graphop_attention_edge_backward(int dtype, const int64_t* row, const int64_t
                                     void* stream, double p, uint64_t seed, uint32_t offset, int64_t head0) {
   const char* fn = "attention_edge_backward";
   GO_TRY(check_async_error(false));
-  GO_TRY(edge_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_q, n_k, h, d));
+  GO_TRY(attn_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_q, n_k, h, d));
   HostDrop hdrop;
-  GO_TRY(edge_drop_check(fn, p, seed, offset, head0, n_q, n_k, &hdrop));
+  GO_TRY(attn_drop_check(fn, DropIn{p, seed, offset, head0}, n_q, n_k, &hdrop));
   GO_CHECK_ARG(n_edges * h * d == 0 || xe != nullptr, "%s: xe is NULL", fn);
   const HostDrop* drop = p > 0.0 ? &hdrop : nullptr;
   hipStream_t st = (hipStream_t)stream;

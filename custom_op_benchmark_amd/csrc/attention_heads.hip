@@ -3,6 +3,7 @@
 // entry points, their arguments and the C ABI are unchanged.
 #include "common.h"
 #include "host.h"
+#include "host_attn_rows.h"
 #include "host_dropout.h"
 #include "host_gat.h"
 #include "kernels_attn_heads.h"
@@ -10,26 +11,11 @@
 namespace graphop {
 namespace {
 
-inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
-
 // the several-head entries of GO_DISPATCH_GAT_HD
 inline bool attn_heads_shape(i64 h, i64 d) {
   bool in_set = false;
   if (h > 1) GO_DISPATCH_GAT_HD(h, d, { in_set = (H == h && D == d); });
   return in_set;
-}
-
-// Chunks per lane group and lane groups of a pass over n_chunks chunks: launch_attn_rows' rule for 16-lane groups, with
-// four (not eight) rounds of resident workgroups wanted -- these kernels hold 150 to 240 VGPRs, two workgroups per CU
-// where the one-head kernels hold four, so the same number of rounds per resident slot needs half the groups, and
-// every group of the forward costs two piece records of (1 + 2 h + F) words.
-inline void attn_heads_geometry(i64 n_chunks, i64* cpg_out, i64* groups_out) {
-  constexpr int GPB = kFastBlock / 16;
-  const i64 groups_wanted = (i64)tuning().n_cu * GPB * 4;
-  i64 cpg = n_chunks / (groups_wanted > 0 ? groups_wanted : 1);
-  cpg = cpg < 1 ? 1 : (cpg > 16 ? 16 : cpg);
-  *cpg_out = cpg;
-  *groups_out = ceil_div(n_chunks, cpg);
 }
 
 // what both directions ask of the knobs, the shape and ONE plan (own rows n_own, gathered table n_tab)
@@ -73,18 +59,6 @@ inline AttnHeadsDropIf<DROP> heads_drop_arg(const AttnHeadsDrop* drop) {
   else return NoDrop{};
 }
 
-struct HeadsFwdWs {
-  size_t o_row, o_ml, o_po, o_m, o_l, total;
-  HeadsFwdWs(i64 np, i64 n_q, i64 h, i64 F) {
-    o_row = 0;
-    o_ml = o_row + up256(sizeof(int) * (size_t)np);
-    o_po = o_ml + up256(sizeof(float) * 2 * (size_t)(np * h));
-    o_m = o_po + up256(sizeof(float) * (size_t)(np * F));
-    o_l = o_m + up256(sizeof(float) * (size_t)(n_q * h));
-    total = o_l + up256(sizeof(float) * (size_t)(n_q * h));
-  }
-};
-
 struct HeadsBwdWs {
   size_t o_kv, o_qdo, o_st4, total;
   HeadsBwdWs(i64 n_q, i64 n_k, i64 h, i64 F) {
@@ -104,7 +78,7 @@ int launch_heads_rows(const char* tag, const graphop_plan* plan, const i64* eid,
   ProfScope prof(tag, st, "k_attn_heads_bwd_rows_f32");
   const bool owned = plan->info.rows_sorted != 0, dropped = drop != nullptr, biased = b != nullptr;
   i64 cpg, groups;
-  attn_heads_geometry(n_chunks, &cpg, &groups);
+  attn_rows_geometry(n_chunks, &cpg, &groups);
   const unsigned nb = (unsigned)ceil_div(groups, kFastBlock / 16);
   GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, GO_DISPATCH_BOOL(biased, BIAS, {
     if constexpr (H > 1)
@@ -142,10 +116,10 @@ int attn_heads_fwd_rows(const graphop_plan* plan, const i64* eid, i64 n_chunks, 
   if (tuning().attn_heads < 0 && !attn_heads_auto_ok(h, d, n_edges, n_q, n_k, plan, st)) return 0;
   const i64 F = h * d;
   i64 cpg, groups;
-  attn_heads_geometry(n_chunks, &cpg, &groups);
+  attn_rows_geometry(n_chunks, &cpg, &groups);
   const i64 np = 2 * groups;
   if (np >= 0x7fffffffLL) return 0;
-  const HeadsFwdWs w(np, n_q, h, F);
+  const AttnRowsFwdWs w(np, n_q, h, F);
   if (ws_needed) *ws_needed = w.total;
   if (dry_run) return 1;
   if (!ws || (size_t)ws_bytes < w.total) return 0;
@@ -162,7 +136,7 @@ int attn_heads_fwd_rows(const graphop_plan* plan, const i64* eid, i64 n_chunks, 
     const i64 most = np > n_q * h ? np : n_q * h;
     const unsigned fb = (unsigned)(ceil_div(most, 256) > 4096 ? 4096 : ceil_div(most, 256));
     hipLaunchKernelGGL((k_fill<int>), dim3(fb), dim3(256), 0, st, a.p_row, np, -1);
-    hipLaunchKernelGGL((k_fill<float>), dim3(fb), dim3(256), 0, st, Mtmp, n_q * h, kAttnHeadsNegBig);
+    hipLaunchKernelGGL((k_fill<float>), dim3(fb), dim3(256), 0, st, Mtmp, n_q * h, kAttnRowsNegBig);
     hipLaunchKernelGGL((k_fill<float>), dim3(fb), dim3(256), 0, st, Ltmp, n_q * h, 0.f);
   }
   const i64* eids = plan->info.eid_identity ? nullptr : eid;
