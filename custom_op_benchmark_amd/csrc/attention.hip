@@ -17,13 +17,14 @@
 // without a bias: the same kernels and launches as before.
 // Several heads: where attention_heads.hip's conditions hold (fp32, (h, d) one of its pairs, plans with
 // neighbour ids, the knobs) all three ops run chunk-driver passes over all heads of a row at once
-// (kernels_attn_heads.h), asked for first by attn_forward / attn_backward; h == 1 and every other several-head call go
-// on as before.
+// (kernels_attn_heads.h), asked for first by attn_fused_forward / attn_backward_form; h == 1 and every other
+// several-head call go on as before.
 // Reference composition: wrapper.py:20-30 (MaskedMMCSR), :8-18 (SparseSoftmax), :44-55 (VectorSPMM).
 #include "common.h"
 #include "host.h"
 #include "host_attn_rows.h"
 #include "host_dropout.h"
+#include "host_gat.h"
 #include "kernels_attn_bias.h"
 
 namespace graphop {
@@ -120,62 +121,28 @@ bool attn_rows_ok(int dtype, i64 h, i64 d, i64 n_edges, i64 n_q, i64 n_k, const 
          plan_c->info.max_index < n_q;
 }
 
-// the kernel argument of a DROP instantiation; drop is NULL exactly where DROP is false
-template <bool DROP>
-inline AttnDropIf<DROP> attn_drop_arg(const AttnDrop* drop) {
-  if constexpr (DROP) return *drop;
-  else return NoDrop{};
-}
-
-template <bool COL, bool DROP>
-int launch_attn_rows(const char* tag, const graphop_plan* plan, i64 n_chunks, int F, const float* own,
-                     const float* xt, const float4* st4, float* out0, float* out1, const AttnDrop* drop,
-                     hipStream_t st) {
+// The one-head chunk-driver backward pass over one orientation's chunks: k_attn_bwd_rows_f32, with BIAS
+// k_attn_bias_bwd_rows_f32 (b and db by edge id; eid == nullptr: the plan has eid_identity).  Without BIAS eid, b and
+// db are not read.
+template <bool COL, bool DROP, bool BIAS>
+int launch_attn_rows(const char* tag, const graphop_plan* plan, const i64* eid, i64 n_chunks, int F, const float* own,
+                     const float* xt, const float4* st4, const float* b, float* out0, float* out1, float* db,
+                     const AttnDrop* drop, hipStream_t st) {
   if (n_chunks == 0) return GRAPHOP_OK;
-  ProfScope prof(tag, st, DROP ? "k_attn_bwd_rows_f32<DROP>" : "k_attn_bwd_rows_f32");
-  const bool owned = plan->info.rows_sorted != 0;
-  GO_DISPATCH_LNV(F, {
-    constexpr int GPB = kFastBlock / L;
-    const i64 groups_wanted = (i64)tuning().n_cu * GPB * 8;
-    i64 cpg = n_chunks / (groups_wanted > 0 ? groups_wanted : 1);
-    cpg = cpg < 1 ? 1 : (cpg > 16 ? 16 : cpg);
-    const unsigned nb = (unsigned)ceil_div(ceil_div(n_chunks, cpg), GPB);
-    if (owned)
-      hipLaunchKernelGGL((k_attn_bwd_rows_f32<L, NV, COL, true, DROP>), dim3(nb), dim3(kFastBlock), 0, st,
-                         (const i64*)plan->row, (const i64*)plan->indptr, (const i64*)plan->indices, own, xt,
-                         st4, out0, out1, n_chunks, (int)cpg, attn_drop_arg<DROP>(drop));
+  ProfScope prof(tag, st, BIAS ? (DROP ? "k_attn_bias_bwd_rows_f32<DROP>" : "k_attn_bias_bwd_rows_f32")
+                               : (DROP ? "k_attn_bwd_rows_f32<DROP>" : "k_attn_bwd_rows_f32"));
+  const ChunkGeometry geo = attn_one_head_geometry(n_chunks, F);
+  const dim3 grid(geo.blocks), block(kFastBlock);
+  GO_DISPATCH_LNV(F, GO_DISPATCH_BOOL(plan->info.rows_sorted != 0, OWNED, {
+    if constexpr (BIAS)
+      hipLaunchKernelGGL((k_attn_bias_bwd_rows_f32<L, NV, COL, OWNED, DROP>), grid, block, 0, st, (const i64*)plan->row,
+                         (const i64*)plan->indptr, eid, (const i64*)plan->indices, own, xt, st4, b, out0, out1, db,
+                         n_chunks, (int)geo.cpg, drop_if_arg<DROP>(drop));
     else
-      hipLaunchKernelGGL((k_attn_bwd_rows_f32<L, NV, COL, false, DROP>), dim3(nb), dim3(kFastBlock), 0, st,
-                         (const i64*)plan->row, (const i64*)plan->indptr, (const i64*)plan->indices, own, xt,
-                         st4, out0, out1, n_chunks, (int)cpg, attn_drop_arg<DROP>(drop));
-  });
-  GO_LAUNCH_CHECK();
-  return GRAPHOP_OK;
-}
-
-// the same launch geometry for k_attn_bias_bwd_rows_f32; eid == nullptr: the plan has eid_identity
-template <bool COL, bool DROP>
-int launch_attn_bias_rows(const char* tag, const graphop_plan* plan, const i64* eid, i64 n_chunks, int F, const float* own,
-                          const float* xt, const float4* st4, const float* b, float* out0, float* out1, float* db,
-                          const AttnDrop* drop, hipStream_t st) {
-  if (n_chunks == 0) return GRAPHOP_OK;
-  ProfScope prof(tag, st, DROP ? "k_attn_bias_bwd_rows_f32<DROP>" : "k_attn_bias_bwd_rows_f32");
-  const bool owned = plan->info.rows_sorted != 0;
-  GO_DISPATCH_LNV(F, {
-    constexpr int GPB = kFastBlock / L;
-    const i64 groups_wanted = (i64)tuning().n_cu * GPB * 8;
-    i64 cpg = n_chunks / (groups_wanted > 0 ? groups_wanted : 1);
-    cpg = cpg < 1 ? 1 : (cpg > 16 ? 16 : cpg);
-    const unsigned nb = (unsigned)ceil_div(ceil_div(n_chunks, cpg), GPB);
-    if (owned)
-      hipLaunchKernelGGL((k_attn_bias_bwd_rows_f32<L, NV, COL, true, DROP>), dim3(nb), dim3(kFastBlock), 0, st,
-                         (const i64*)plan->row, (const i64*)plan->indptr, eid, (const i64*)plan->indices, own, xt, st4, b,
-                         out0, out1, db, n_chunks, (int)cpg, attn_drop_arg<DROP>(drop));
-    else
-      hipLaunchKernelGGL((k_attn_bias_bwd_rows_f32<L, NV, COL, false, DROP>), dim3(nb), dim3(kFastBlock), 0, st,
-                         (const i64*)plan->row, (const i64*)plan->indptr, eid, (const i64*)plan->indices, own, xt, st4, b,
-                         out0, out1, db, n_chunks, (int)cpg, attn_drop_arg<DROP>(drop));
-  });
+      hipLaunchKernelGGL((k_attn_bwd_rows_f32<L, NV, COL, OWNED, DROP>), grid, block, 0, st, (const i64*)plan->row,
+                         (const i64*)plan->indptr, (const i64*)plan->indices, own, xt, st4, out0, out1, n_chunks,
+                         (int)geo.cpg, drop_if_arg<DROP>(drop));
+  }));
   GO_LAUNCH_CHECK();
   return GRAPHOP_OK;
 }
@@ -216,7 +183,7 @@ int launch_attn_pass(const char* tag, const SweepLaunch& sl, int F, i64 n_gather
                      hipStream_t st) {
   ProfScope prof(tag, st, DROP ? "k_attn_bwd_wown_f32<DROP>" : "k_attn_bwd_wown_f32");
   const dim3 grid(sl.blocks), block(kFastBlock);
-  const AttnDropIf<DROP> dr = attn_drop_arg<DROP>(drop);
+  const AttnDropIf<DROP> dr = drop_if_arg<DROP>(drop);
   GO_DISPATCH_LNV(F, {
     const bool off32 = n_gathered * 2 * 16LL * L * NV < (1LL << 32);
     constexpr int BPC = DROP ? attn_bpc_drop(L, NV, COL) : attn_bpc(NV, COL);
@@ -317,50 +284,101 @@ int attn_drop_apply(int dtype, const int64_t* row, const int64_t* indptr, const 
   return GRAPHOP_OK;
 }
 
+// The fused forward of a call where one applies: several heads in one chunk-driver pass (kernels_attn_heads.h, with or
+// without a bias); one head with a bias in the chunk-driver pass of kernels_attn_bias_fwd.h (the walk's layouts carry no
+// edge id); one head without on the walk (kernels_attn_walk.h).  The contract of the three: 1 = launched (dry_run:
+// applies), 0 = does not apply, < 0 = error, *needed = the workspace.  biased with b == NULL: a dry run of the op with a
+// bias.  Needs a plan of the call's arrays and n_edges * h > 0.
+int attn_fused_forward(const graphop_plan* pm, const i64* eid, i64 n_chunks, i64 n_edges, i64 n_q, i64 n_k, i64 h, i64 d,
+                       int dtype, const void* Q, const void* K, const void* V, bool biased, const void* b, void* o,
+                       void* stats, void* ws, i64 ws_bytes, hipStream_t st, bool dry_run, size_t* needed,
+                       const HostDrop* drop = nullptr, i64 head0 = 0, const AttnDrop* hd = nullptr) {
+  if (h > 1)
+    return attn_heads_fwd_rows(pm, eid, n_chunks, n_edges, n_q, n_k, h, d, dtype, Q, K, V, b, o, stats, ws, ws_bytes, st,
+                               dry_run, needed, drop, head0);
+  if (biased)
+    return attn_bias_fwd_rows(pm, eid, n_chunks, n_edges, n_q, n_k, h, d, dtype, Q, K, V, b, o, stats, ws, ws_bytes, st,
+                              dry_run, needed, hd);
+  return attn_fwd_walk(pm, n_q, n_k, h, d, dtype, Q, K, V, o, stats, ws, ws_bytes, st, dry_run, needed, hd);
+}
+
+// The form of a call's backward: the several-head chunk-driver passes (attention_heads.hip), the window-owner passes
+// (launch geometry in *af), the one-head chunk-driver passes, or the composition of the unfused entry points.  With a
+// bias the chunk-driver form runs wherever either one-head fused form would (the window layouts carry no edge id), and
+// the window-owner passes are only asked for their decision.  dry_run: only decide; else a Windows answer has taken its
+// task queues.
+enum class AttnBwd { Composed, Heads, Windows, Rows };
+
+int attn_backward_form(bool biased, bool dry_run, int dtype, i64 h, i64 d, i64 n_edges, i64 n_q, i64 n_k,
+                       const graphop_plan* pr, const graphop_plan* pc, hipStream_t st, AttnFast* af, AttnBwd* form) {
+  *form = AttnBwd::Heads;
+  if (attn_heads_bwd_ok(dtype, h, d, n_edges, n_q, n_k, pr, pc, st)) return GRAPHOP_OK;
+  const int fast = attn_fast_plan(dtype, h, d, n_edges, n_q, n_k, pr, pc, st, dry_run || biased, af);
+  if (fast < 0) return -fast;
+  if (biased) *form = attn_bias_rows_ok(fast, dtype, h, d, n_edges, n_q, n_k, pr, pc, st) ? AttnBwd::Rows : AttnBwd::Composed;
+  else if (fast == 1) *form = AttnBwd::Windows;
+  else *form = attn_rows_ok(dtype, h, d, n_edges, n_q, n_k, pr, pc, st) ? AttnBwd::Rows : AttnBwd::Composed;
+  return GRAPHOP_OK;
+}
+
 // bwd_arrays: E-sized arrays of the composed backward (4; 5 with dropout: the masked weights; with a bias one fewer
 // where db takes the place of ds).  bias: the forms of the op with a bias are the ones decided on.
 int attn_workspace_bytes(const char* fn, int dtype, int backward, int64_t n_edges, int64_t n_q, int64_t n_k, int64_t h,
                          int64_t d, const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream,
                          int bwd_arrays, int64_t* bytes_out, bool bias = false) {
   GO_CHECK_ARG(bytes_out != nullptr, "%s: bytes_out is NULL", fn);
-  GO_CHECK_ARG(dtype == GRAPHOP_F32 || dtype == GRAPHOP_F64, "%s: bad dtype", fn);
-  GO_CHECK_ARG(n_edges >= 0 && n_q >= 0 && n_k >= 0 && h >= 1 && d >= 0, "%s: negative size", fn);
+  GO_TRY(attn_check(fn, dtype, 0, 0, n_edges, n_q, n_k, h, d));
   const size_t es = esize(dtype);
+  hipStream_t st = (hipStream_t)stream;
   if (!backward) {
     size_t need = 0;
     int fw = 0;
-    if (plan_r && n_edges * h > 0 && h > 1)   // several heads: the form of kernels_attn_heads.h, with or without a bias
-      fw = attn_heads_fwd_rows(plan_r, nullptr, plan_r->info.n_chunks, n_edges, n_q, n_k, h, d, dtype, nullptr, nullptr,
-                               nullptr, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream, /*dry_run=*/true, &need);
-    else if (plan_r && n_edges * h > 0)
-      fw = bias ? attn_bias_fwd_rows(plan_r, nullptr, plan_r->info.n_chunks, n_edges, n_q, n_k, h, d, dtype, nullptr,
-                                     nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, (hipStream_t)stream,
-                                     /*dry_run=*/true, &need)
-                : attn_fwd_walk(plan_r, n_q, n_k, h, d, dtype, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0,
-                                (hipStream_t)stream, /*dry_run=*/true, &need);
+    if (plan_r && n_edges * h > 0)
+      fw = attn_fused_forward(plan_r, nullptr, plan_r->info.n_chunks, n_edges, n_q, n_k, h, d, dtype, nullptr, nullptr,
+                              nullptr, bias, nullptr, nullptr, nullptr, nullptr, 0, st, /*dry_run=*/true, &need);
     if (fw < 0) return -fw;
     // the one-pass forward only needs the piece records of shared rows; the composed forward keeps s and a here
     *bytes_out = fw == 1 ? (int64_t)need : (int64_t)SlowWs(nullptr, 2, es, n_edges, h, soft_rows_of(plan_r, n_q)).total;
     return GRAPHOP_OK;
   }
-  if (attn_heads_bwd_ok(dtype, h, d, n_edges, n_q, n_k, plan_r, plan_c, (hipStream_t)stream)) {
-    *bytes_out = (int64_t)attn_heads_bwd_workspace(n_q, n_k, h, d);
-    return GRAPHOP_OK;
-  }
   AttnFast af;
-  const int fast = attn_fast_plan(dtype, h, d, n_edges, n_q, n_k, plan_r, plan_c, (hipStream_t)stream,
-                                  /*dry_run=*/true, &af);
-  if (fast < 0) return -fast;
-  const bool fused = bias ? attn_bias_rows_ok(fast, dtype, h, d, n_edges, n_q, n_k, plan_r, plan_c, (hipStream_t)stream)
-                          : (fast == 1 || attn_rows_ok(dtype, h, d, n_edges, n_q, n_k, plan_r, plan_c, (hipStream_t)stream));
-  if (fused) *bytes_out = (int64_t)FastWs(nullptr, n_q, n_k, h * d).total;
-  else *bytes_out = (int64_t)SlowWs(nullptr, bwd_arrays, es, n_edges, h, soft_rows_of(plan_r, n_q)).total;
+  AttnBwd form;
+  GO_TRY(attn_backward_form(bias, /*dry_run=*/true, dtype, h, d, n_edges, n_q, n_k, plan_r, plan_c, st, &af, &form));
+  if (form == AttnBwd::Heads) *bytes_out = (int64_t)attn_heads_bwd_workspace(n_q, n_k, h, d);
+  else if (form == AttnBwd::Composed)
+    *bytes_out = (int64_t)SlowWs(nullptr, bwd_arrays, es, n_edges, h, soft_rows_of(plan_r, n_q)).total;
+  else *bytes_out = (int64_t)FastWs(nullptr, n_q, n_k, h * d).total;
   return GRAPHOP_OK;
 }
 
-// the one-head decision of the fused kernels for the call's first head
-inline AttnDrop attn_head_drop(const HostDrop& drop, i64 head0) {
-  return AttnDrop{drop.as<float>(), (unsigned)(head0 >> 2), (int)(head0 & 3)};
+// What attn_forward and attn_backward establish first: the checks, then the call's dropout as the forms take it.
+struct AttnCall {
+  HostDrop hdrop;
+  const HostDrop* drop = nullptr;   // NULL: no dropout arguments, or p == 0 (the undropped op)
+  i64 head0 = 0;
+  AttnDrop hd{};                    // the one-head kernels' record for the call's first head ...
+  const AttnDrop* hdp = nullptr;    // ... NULL exactly where drop is
+  const char* ws_fn;                // the query that reports this call's workspace
+  hipStream_t st;
+};
+
+// din == nullptr: the op without dropout arguments; bias != nullptr: the form with a per-edge score bias
+int attn_open(const char* fn, int dtype, i64 n_row_chunks, i64 n_col_chunks, i64 n_edges, i64 n_q, i64 n_k, i64 h, i64 d,
+              const DropIn* din, const BiasIn* bias, void* stream, AttnCall* c) {
+  GO_TRY(check_async_error(false));
+  GO_TRY(attn_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_q, n_k, h, d));
+  if (din) GO_TRY(attn_drop_check(fn, *din, n_q, n_k, &c->hdrop));
+  if (bias) GO_TRY(attn_bias_check(fn, *bias, n_edges, h));
+  c->st = (hipStream_t)stream;
+  c->head0 = din ? din->head0 : 0;
+  if (din && din->p > 0.0) {
+    c->drop = &c->hdrop;
+    c->hd = AttnDrop{c->hdrop.as<float>(), (unsigned)(c->head0 >> 2), (int)(c->head0 & 3)};   // Philox block and word
+    c->hdp = &c->hd;
+  }
+  c->ws_fn = bias ? "attention_bias_workspace_bytes"
+                  : (c->drop ? "attention_dropout_workspace_bytes" : "attention_workspace_bytes");
+  return GRAPHOP_OK;
 }
 
 // din == nullptr: graphop_attention_forward, else its dropout form (p == 0: the undropped op), as `fn`;
@@ -370,18 +388,11 @@ int attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t* i
                  void* stats, int64_t n_chunks, int64_t n_edges, int64_t n_q, int64_t n_k, int64_t h, int64_t d,
                  void* workspace, int64_t workspace_bytes, const DropIn* din, const graphop_plan_t* plan,
                  void* stream, const BiasIn* bias = nullptr) {
-  GO_TRY(check_async_error(false));
-  GO_TRY(attn_check(fn, dtype, n_chunks, 0, n_edges, n_q, n_k, h, d));
-  HostDrop hdrop;
-  if (din) GO_TRY(attn_drop_check(fn, *din, n_q, n_k, &hdrop));
-  if (bias) GO_TRY(attn_bias_check(fn, *bias, n_edges, h));
-  const HostDrop* drop = (din && din->p > 0.0) ? &hdrop : nullptr;
-  const int64_t head0 = din ? din->head0 : 0;
-  const char* ws_fn = bias ? "attention_bias_workspace_bytes"
-                           : (drop ? "attention_dropout_workspace_bytes" : "attention_workspace_bytes");
-  hipStream_t st = (hipStream_t)stream;
-  AttnDrop hd{};
-  if (drop) hd = attn_head_drop(*drop, head0);
+  AttnCall c;
+  GO_TRY(attn_open(fn, dtype, n_chunks, 0, n_edges, n_q, n_k, h, d, din, bias, stream, &c));
+  const HostDrop* drop = c.drop;
+  const int64_t head0 = c.head0;
+  hipStream_t st = c.st;
   const size_t es = esize(dtype);
   if (n_q * h > 0) {
     GO_PTR(fn, stats);
@@ -389,28 +400,19 @@ int attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t* i
   }
   const graphop_plan* pm = plan_matches_full(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
                                              (const i64*)indices, n_chunks, n_edges) ? plan : nullptr;
-  // ONE walk-style pass where it applies (kernels_attn_walk.h): s and a never leave the chip; its workspace (piece
-  // records of the rows that bins share) is what graphop_attention_workspace_bytes reported for this call
+  // ONE fused pass where it applies: s and a never leave the chip; its workspace (piece records of the rows that bins or
+  // lane groups share) is what the call's workspace query reported
   if (pm && n_edges * h > 0) {
     GO_PTR(fn, Q); GO_PTR(fn, K); GO_PTR(fn, V); GO_PTR(fn, o);
     size_t need = 0;
-    // with a bias: the chunk-driver pass of kernels_attn_bias_fwd.h (the walk's layouts carry no edge id)
     auto fused_fwd = [&](void* w, int64_t w_bytes, bool dry_run, size_t* needed) {
-      if (h > 1)   // several heads: one chunk-driver pass over all of them (kernels_attn_heads.h)
-        return attn_heads_fwd_rows(pm, (const i64*)eid, n_chunks, n_edges, n_q, n_k, h, d, dtype, Q, K, V,
-                                   bias ? bias->b : nullptr, o, stats, w, w_bytes, st, dry_run, needed, drop, head0);
-      if (bias)
-        return attn_bias_fwd_rows(pm, (const i64*)eid, n_chunks, n_edges, n_q, n_k, h, d, dtype, Q, K, V, bias->b, o, stats,
-                                  w, w_bytes, st, dry_run, needed, drop ? &hd : nullptr);
-      return attn_fwd_walk(pm, n_q, n_k, h, d, dtype, Q, K, V, o, stats, w, w_bytes, st, dry_run, needed,
-                           drop ? &hd : nullptr);
+      return attn_fused_forward(pm, (const i64*)eid, n_chunks, n_edges, n_q, n_k, h, d, dtype, Q, K, V, bias != nullptr,
+                                bias ? bias->b : nullptr, o, stats, w, w_bytes, st, dry_run, needed, drop, head0, c.hdp);
     };
     const int ok = fused_fwd(nullptr, 0, /*dry_run=*/true, &need);
     if (ok < 0) return -ok;
     if (ok == 1) {
-      GO_CHECK_ARG(workspace != nullptr && (size_t)workspace_bytes >= need,
-                   "%s: workspace of %lld bytes needed (graphop_%s), got %lld", fn,
-                   (long long)need, ws_fn, (long long)workspace_bytes);
+      GO_TRY(attn_ws_check(fn, c.ws_fn, true, need, workspace, workspace_bytes));
       const int fw = fused_fwd(workspace, workspace_bytes, /*dry_run=*/false, nullptr);
       if (fw < 0) return -fw;
       if (fw == 1) return GRAPHOP_OK;
@@ -418,9 +420,7 @@ int attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t* i
   }
   const i64 soft_rows = soft_rows_of(pm, n_q);
   SlowWs ws((char*)workspace, 2, es, n_edges, h, soft_rows);
-  GO_CHECK_ARG(n_edges * h == 0 || (workspace != nullptr && (size_t)workspace_bytes >= ws.total),
-               "%s: workspace of %lld bytes needed (graphop_%s), got %lld", fn,
-               (long long)ws.total, ws_fn, (long long)workspace_bytes);
+  GO_TRY(attn_ws_check(fn, c.ws_fn, n_edges * h != 0, ws.total, workspace, workspace_bytes));
   void* s = ws.arr[0];
   void* a = ws.arr[1];
   GO_TRY(graphop_maskedmm_csr_forward(dtype, row, indptr, eid, indices, Q, K, s, n_chunks, n_edges, n_q,
@@ -445,50 +445,31 @@ int attn_backward(const char* fn, int dtype, const int64_t* row, const int64_t* 
                   int64_t d, void* workspace, int64_t workspace_bytes, const DropIn* din,
                   const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream,
                   const BiasIn* bias = nullptr) {
-  GO_TRY(check_async_error(false));
-  GO_TRY(attn_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_q, n_k, h, d));
-  HostDrop hdrop;
-  if (din) GO_TRY(attn_drop_check(fn, *din, n_q, n_k, &hdrop));
-  if (bias) GO_TRY(attn_bias_check(fn, *bias, n_edges, h));
-  const HostDrop* drop = (din && din->p > 0.0) ? &hdrop : nullptr;
-  const int64_t head0 = din ? din->head0 : 0;
-  const char* ws_fn = bias ? "attention_bias_workspace_bytes"
-                           : (drop ? "attention_dropout_workspace_bytes" : "attention_workspace_bytes");
-  hipStream_t st = (hipStream_t)stream;
-  AttnDrop hd{};
-  if (drop) hd = attn_head_drop(*drop, head0);
+  AttnCall c;
+  GO_TRY(attn_open(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_q, n_k, h, d, din, bias, stream, &c));
+  const HostDrop* drop = c.drop;
+  const int64_t head0 = c.head0;
+  hipStream_t st = c.st;
   const size_t es = esize(dtype);
   const graphop_plan* pr = plan_matches_full(plan_r, (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r,
                                              (const i64*)indices_r, n_row_chunks, n_edges) ? plan_r : nullptr;
   const graphop_plan* pc = plan_matches_full(plan_c, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c,
                                              (const i64*)indices_c, n_col_chunks, n_edges) ? plan_c : nullptr;
-  // several heads: the chunk-driver passes over all heads of a row (kernels_attn_heads.h), with or without a bias
-  if (attn_heads_bwd_ok(dtype, h, d, n_edges, n_q, n_k, pr, pc, st)) {
-    const size_t need = attn_heads_bwd_workspace(n_q, n_k, h, d);
-    GO_CHECK_ARG(workspace != nullptr && (size_t)workspace_bytes >= need,
-                 "%s: workspace of %lld bytes needed (graphop_%s), got %lld", fn, (long long)need, ws_fn,
-                 (long long)workspace_bytes);
-    GO_PTR(fn, Q); GO_PTR(fn, K); GO_PTR(fn, V); GO_PTR(fn, o); GO_PTR(fn, stats); GO_PTR(fn, dO);
-    GO_PTR(fn, dQ); GO_PTR(fn, dK); GO_PTR(fn, dV);
-    return attn_heads_backward(pr, pc, (const i64*)eid_r, (const i64*)eid_c, n_row_chunks, n_col_chunks, n_q, n_k, h, d, Q,
-                               K, V, bias ? bias->b : nullptr, o, stats, dO, dQ, dK, dV, bias ? bias->db : nullptr,
-                               workspace, st, drop, head0);
-  }
   AttnFast af;
-  // (with a bias the window-owner passes are never launched: only their decision is asked for, no task queue taken)
-  const int fast = attn_fast_plan(dtype, h, d, n_edges, n_q, n_k, pr, pc, st, /*dry_run=*/bias != nullptr, &af);
-  if (fast < 0) return -fast;
-  // with a bias the chunk-driver form runs wherever either fused form would (the window layouts carry no edge id)
-  const bool rows_path = bias ? attn_bias_rows_ok(fast, dtype, h, d, n_edges, n_q, n_k, pr, pc, st)
-                              : (fast != 1 && attn_rows_ok(dtype, h, d, n_edges, n_q, n_k, pr, pc, st));
-  if (bias ? rows_path : (fast == 1 || rows_path)) {
-    const i64 F = d;   // h == 1
-    FastWs ws((char*)workspace, n_q, n_k, F);
-    GO_CHECK_ARG(workspace != nullptr && (size_t)workspace_bytes >= ws.total,
-                 "%s: workspace of %lld bytes needed (graphop_%s), got %lld", fn,
-                 (long long)ws.total, ws_fn, (long long)workspace_bytes);
+  AttnBwd form;
+  GO_TRY(attn_backward_form(bias != nullptr, /*dry_run=*/false, dtype, h, d, n_edges, n_q, n_k, pr, pc, st, &af, &form));
+  const float* b = bias ? (const float*)bias->b : nullptr;
+  float* db = bias ? (float*)bias->db : nullptr;
+  if (form != AttnBwd::Composed) {
+    const i64 F = h * d;
+    FastWs ws((char*)workspace, n_q, n_k, F);   // (the one-head forms; attn_heads_backward lays out its own)
+    GO_TRY(attn_ws_check(fn, c.ws_fn, true, form == AttnBwd::Heads ? attn_heads_bwd_workspace(n_q, n_k, h, d) : ws.total,
+                         workspace, workspace_bytes));
     GO_PTR(fn, Q); GO_PTR(fn, K); GO_PTR(fn, V); GO_PTR(fn, o); GO_PTR(fn, stats); GO_PTR(fn, dO);
     GO_PTR(fn, dQ); GO_PTR(fn, dK); GO_PTR(fn, dV);
+    if (form == AttnBwd::Heads)
+      return attn_heads_backward(pr, pc, (const i64*)eid_r, (const i64*)eid_c, n_row_chunks, n_col_chunks, n_q, n_k, h, d, Q,
+                                 K, V, b, o, stats, dO, dQ, dK, dV, db, workspace, st, drop, head0);
     GO_HIP(zero_async(dQ, sizeof(float) * (size_t)(n_q * F), st));
     GO_HIP(zero_async(dK, sizeof(float) * (size_t)(n_k * F), st));
     GO_HIP(zero_async(dV, sizeof(float) * (size_t)(n_k * F), st));
@@ -505,41 +486,32 @@ int attn_backward(const char* fn, int dtype, const int64_t* row, const int64_t* 
       });
       GO_LAUNCH_CHECK();
     }
-    // each launch is written once: DROP picks the instantiation, the arguments are the same
-    auto passes = [&](auto drop_c) -> int {
-      constexpr bool DROP = decltype(drop_c)::value;
-      if (bias) {
-        GO_TRY((launch_attn_bias_rows<false, DROP>("attn_bias_rows_row", pr, pr->info.eid_identity ? nullptr : (const i64*)eid_r,
-                                                   n_row_chunks, (int)F, ws.qdo, ws.kv, ws.st4, (const float*)bias->b,
-                                                   (float*)dQ, nullptr, (float*)bias->db, &hd, st)));
-        GO_TRY((launch_attn_bias_rows<true, DROP>("attn_bias_rows_col", pc, pc->info.eid_identity ? nullptr : (const i64*)eid_c,
-                                                  n_col_chunks, (int)F, ws.kv, ws.qdo, ws.st4, (const float*)bias->b,
-                                                  (float*)dK, (float*)dV, nullptr, &hd, st)));
+    // each launch is written once: DROP and BIAS pick the instantiation, the arguments are the same
+    GO_DISPATCH_BOOL(drop != nullptr, DROP, {
+      if (form == AttnBwd::Windows) {
+        GO_TRY((launch_attn_pass<false, DROP>("attn_bwd_row", af.r, (int)F, n_k, ws.qdo, ws.kv, ws.st4, (float*)dQ,
+                                              nullptr, c.hdp, st)));
+        GO_TRY((launch_attn_pass<true, DROP>("attn_bwd_col", af.c, (int)F, n_q, ws.kv, ws.qdo, ws.st4, (float*)dK,
+                                             (float*)dV, c.hdp, st)));
         return GRAPHOP_OK;
       }
-      if (rows_path) {
-        GO_TRY((launch_attn_rows<false, DROP>("attn_rows_row", pr, n_row_chunks, (int)F, ws.qdo, ws.kv, ws.st4,
-                                              (float*)dQ, nullptr, &hd, st)));
-        GO_TRY((launch_attn_rows<true, DROP>("attn_rows_col", pc, n_col_chunks, (int)F, ws.kv, ws.qdo, ws.st4,
-                                             (float*)dK, (float*)dV, &hd, st)));
-        return GRAPHOP_OK;
-      }
-      GO_TRY((launch_attn_pass<false, DROP>("attn_bwd_row", af.r, (int)F, n_k, ws.qdo, ws.kv, ws.st4, (float*)dQ,
-                                            nullptr, &hd, st)));
-      GO_TRY((launch_attn_pass<true, DROP>("attn_bwd_col", af.c, (int)F, n_q, ws.kv, ws.qdo, ws.st4, (float*)dK,
-                                           (float*)dV, &hd, st)));
-      return GRAPHOP_OK;
-    };
-    return drop ? passes(std::true_type{}) : passes(std::false_type{});
+      GO_DISPATCH_BOOL(bias != nullptr, BIAS, {
+        GO_TRY((launch_attn_rows<false, DROP, BIAS>(BIAS ? "attn_bias_rows_row" : "attn_rows_row", pr, eid_arg(pr, eid_r),
+                                                    n_row_chunks, (int)F, ws.qdo, ws.kv, ws.st4, b, (float*)dQ, nullptr,
+                                                    db, c.hdp, st)));
+        GO_TRY((launch_attn_rows<true, DROP, BIAS>(BIAS ? "attn_bias_rows_col" : "attn_rows_col", pc, eid_arg(pc, eid_c),
+                                                   n_col_chunks, (int)F, ws.kv, ws.qdo, ws.st4, b, (float*)dK, (float*)dV,
+                                                   nullptr, c.hdp, st)));
+      });
+    });
+    return GRAPHOP_OK;
   }
   // composition of the unfused entry points: recompute s and a, then the three backward ops
   // with a bias and db given, the softmax backward writes ds straight into db: one E-sized array fewer
   const i64 soft_rows = soft_rows_of(pr, n_q);
   const bool ds_is_db = bias && bias->db != nullptr;
   SlowWs ws((char*)workspace, (bias || drop ? 5 : 4) - (ds_is_db ? 1 : 0), es, n_edges, h, soft_rows);
-  GO_CHECK_ARG(n_edges * h == 0 || (workspace != nullptr && (size_t)workspace_bytes >= ws.total),
-               "%s: workspace of %lld bytes needed (graphop_%s), got %lld", fn,
-               (long long)ws.total, ws_fn, (long long)workspace_bytes);
+  GO_TRY(attn_ws_check(fn, c.ws_fn, n_edges * h != 0, ws.total, workspace, workspace_bytes));
   void* s = ws.arr[0];
   void* a = ws.arr[1];
   void* da = ws.arr[2];
@@ -590,15 +562,11 @@ int graphop_attention_backward_is_fused(int dtype, int64_t n_edges, int64_t n_q,
                                         int64_t d, const graphop_plan_t* plan_r,
                                         const graphop_plan_t* plan_c, void* stream, int* fused_out) {
   GO_CHECK_ARG(fused_out != nullptr, "attention_backward_is_fused: fused_out is NULL");
-  if (attn_heads_bwd_ok(dtype, h, d, n_edges, n_q, n_k, plan_r, plan_c, (hipStream_t)stream)) {
-    *fused_out = 1;
-    return GRAPHOP_OK;
-  }
   AttnFast af;
-  const int fast = attn_fast_plan(dtype, h, d, n_edges, n_q, n_k, plan_r, plan_c, (hipStream_t)stream,
-                                  /*dry_run=*/true, &af);
-  if (fast < 0) return -fast;
-  *fused_out = (fast == 1 || attn_rows_ok(dtype, h, d, n_edges, n_q, n_k, plan_r, plan_c, (hipStream_t)stream)) ? 1 : 0;
+  AttnBwd form;
+  GO_TRY(attn_backward_form(/*biased=*/false, /*dry_run=*/true, dtype, h, d, n_edges, n_q, n_k, plan_r, plan_c,
+                            (hipStream_t)stream, &af, &form));
+  *fused_out = form != AttnBwd::Composed ? 1 : 0;
   return GRAPHOP_OK;
 }
 

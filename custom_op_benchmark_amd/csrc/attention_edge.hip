@@ -41,21 +41,15 @@ struct EdgeBwdWs {
 
 // the fast forward applies to this plan and these sizes: its launch geometry and piece records
 inline bool edge_fwd_fast_shape(int dtype, i64 h, i64 d, i64 n_edges, i64 n_q, i64 n_k, const graphop_plan* plan,
-                                i64 n_chunks, i64* cpg, i64* groups) {
+                                i64 n_chunks, ChunkGeometry* geo) {
   if (!edge_shape_ok(dtype, h, d, n_edges, n_q, n_k) || !edge_plan_ok(plan, n_q, n_k)) return false;
   if (!plan->info.rows_sorted || n_q >= kWalkRowMask || n_chunks == 0) return false;
-  attn_rows_geometry(n_chunks, cpg, groups);
-  return 2 * *groups < 0x7fffffffLL;
+  *geo = attn_rows_geometry(n_chunks);
+  return 2 * geo->groups < 0x7fffffffLL;
 }
 
 inline bool edge_has_slots(i64 n_chunks, i64 n_edges, i64 n_q, i64 n_k, i64 h, i64 d) {
   return n_chunks > 0 && n_edges * h * d > 0 && n_q > 0 && n_k > 0;
-}
-
-template <bool DROP>
-inline AttnEdgeDropIf<DROP> edge_drop_arg(const AttnEdgeDrop* drop) {
-  if constexpr (DROP) return *drop;
-  else return NoDrop{};
 }
 
 template <bool COL>
@@ -64,13 +58,11 @@ int launch_edge_rows(const char* tag, const graphop_plan* plan, const i64* eid, 
                      float* dxe, const AttnEdgeDrop* drop, hipStream_t st) {
   ProfScope prof(tag, st, "k_attn_edge_bwd_rows_f32");
   const bool owned = plan->info.rows_sorted != 0, dropped = drop != nullptr;
-  i64 cpg, groups;
-  attn_rows_geometry(n_chunks, &cpg, &groups);
-  const unsigned nb = (unsigned)ceil_div(groups, kFastBlock / kGatGroup);
+  const ChunkGeometry geo = attn_rows_geometry(n_chunks);
   GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
-    hipLaunchKernelGGL((k_attn_edge_bwd_rows_f32<H, D, COL, OWNED, DROP>), dim3(nb), dim3(kFastBlock), 0, st,
+    hipLaunchKernelGGL((k_attn_edge_bwd_rows_f32<H, D, COL, OWNED, DROP>), dim3(geo.blocks), dim3(kFastBlock), 0, st,
                        (const i64*)plan->row, (const i64*)plan->indptr, eid, (const i64*)plan->indices, own, xt, st4, xe,
-                       out0, out1, dxe, n_chunks, (int)cpg, edge_drop_arg<DROP>(drop));
+                       out0, out1, dxe, n_chunks, (int)geo.cpg, drop_if_arg<DROP>(drop));
   })));
   GO_LAUNCH_CHECK();
   return GRAPHOP_OK;
@@ -91,9 +83,9 @@ int graphop_attention_edge_workspace_bytes(int dtype, int backward, int64_t n_ed
   *bytes_out = 0;
   if (n_edges * h * d == 0 || n_q == 0 || n_k == 0) return GRAPHOP_OK;
   if (!backward) {
-    i64 cpg, groups;   // the generic forward keeps its sums in stats: no workspace
-    if (plan_r && edge_fwd_fast_shape(dtype, h, d, n_edges, n_q, n_k, plan_r, plan_r->info.n_chunks, &cpg, &groups))
-      *bytes_out = (int64_t)AttnRowsFwdWs(2 * groups, n_q, h, h * d).total;
+    ChunkGeometry geo;   // the generic forward keeps its sums in stats: no workspace
+    if (plan_r && edge_fwd_fast_shape(dtype, h, d, n_edges, n_q, n_k, plan_r, plan_r->info.n_chunks, &geo))
+      *bytes_out = (int64_t)AttnRowsFwdWs(nullptr, 2 * geo.groups, n_q, h, h * d).total;
     return GRAPHOP_OK;
   }
   const bool fast = edge_shape_ok(dtype, h, d, n_edges, n_q, n_k) &&
@@ -122,16 +114,12 @@ int graphop_attention_edge_forward(int dtype, const int64_t* row, const int64_t*
                                              (const i64*)indices, n_chunks, n_edges) ? plan : nullptr;
   GO_TRY(gat_check_plan(fn, pm, "Q / o", n_q, "K / V", n_k));
   const bool slots = edge_has_slots(n_chunks, n_edges, n_q, n_k, h, d);
-  i64 cpg = 0, groups = 0;
+  ChunkGeometry geo{};
   bool fast = slots && !(drop && head0 + h >= 0x7fffffffLL) &&
-              edge_fwd_fast_shape(dtype, h, d, n_edges, n_q, n_k, pm, n_chunks, &cpg, &groups) &&
+              edge_fwd_fast_shape(dtype, h, d, n_edges, n_q, n_k, pm, n_chunks, &geo) &&
               gat_hd_fast_ok(dtype, h, d, n_edges, n_q, n_k, {Q, K, V, xe, o, stats, workspace});
-  const i64 np = 2 * groups;
-  const AttnRowsFwdWs w(np, n_q, h, F);
-  if (fast)
-    GO_CHECK_ARG(workspace != nullptr && workspace_bytes >= 0 && (size_t)workspace_bytes >= w.total,
-                 "%s: workspace of %lld bytes needed (graphop_attention_edge_workspace_bytes), got %lld", fn,
-                 (long long)w.total, (long long)workspace_bytes);
+  const AttnRowsFwdWs w(workspace, 2 * geo.groups, n_q, h, F);
+  GO_TRY(attn_ws_check(fn, "attention_edge_workspace_bytes", fast, w.total, workspace, workspace_bytes));
   if (n_q == 0) return GRAPHOP_OK;
   // rows without slots keep o = 0 and stats = (-1e9, 0)
   GO_PTR(fn, stats);
@@ -149,46 +137,39 @@ int graphop_attention_edge_forward(int dtype, const int64_t* row, const int64_t*
   const bool dropped = drop != nullptr;
   if (fast) {
     const AttnEdgeDrop hd{drop ? drop->as<float>() : DropArgs<float>{}, (int)head0};
-    char* base = (char*)workspace;
     AttnEdgeFwdArgs a;
     a.Q = (const float*)Q; a.K = (const float*)K; a.V = (const float*)V; a.xe = (const float*)xe;
     a.o = (float*)o; a.stats = (float*)stats;
-    a.p_row = (int*)(base + w.o_row); a.p_ml = (float*)(base + w.o_ml); a.p_o = (float*)(base + w.o_po);
-    float* Mtmp = (float*)(base + w.o_m);
-    float* Ltmp = (float*)(base + w.o_l);
-    {
-      ProfScope prof("attn_edge_fwd_setup", st, "k_fill");
-      const i64 most = np > n_q * h ? np : n_q * h;
-      const unsigned fb = (unsigned)(ceil_div(most, 256) > 4096 ? 4096 : ceil_div(most, 256));
-      hipLaunchKernelGGL((k_fill<int>), dim3(fb), dim3(256), 0, st, a.p_row, np, -1);
-      hipLaunchKernelGGL((k_fill<float>), dim3(fb), dim3(256), 0, st, Mtmp, n_q * h, kAttnRowsNegBig);
-      hipLaunchKernelGGL((k_fill<float>), dim3(fb), dim3(256), 0, st, Ltmp, n_q * h, 0.f);
-      GO_LAUNCH_CHECK();
-    }
-    constexpr int GPB = kFastBlock / kGatGroup;
+    a.p_row = w.p_row; a.p_ml = w.p_ml; a.p_o = w.p_o;
+    attn_pieces_fill("attn_edge_fwd_setup", w, kAttnNegBig, st);
+    GO_LAUNCH_CHECK();
     {
       ProfScope prof("attn_edge_fwd_rows", st, "k_attn_edge_fwd_rows_f32");
-      const unsigned nb = (unsigned)ceil_div(groups, GPB);
       GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(dropped, DROP, {
-        hipLaunchKernelGGL((k_attn_edge_fwd_rows_f32<H, D, DROP>), dim3(nb), dim3(kFastBlock), 0, st,
+        hipLaunchKernelGGL((k_attn_edge_fwd_rows_f32<H, D, DROP>), dim3(geo.blocks), dim3(kFastBlock), 0, st,
                            (const i64*)pm->row, (const i64*)pm->indptr, eid_arg(pm, eid), (const i64*)pm->indices, a,
-                           n_chunks, (int)cpg, edge_drop_arg<DROP>(drop ? &hd : nullptr));
+                           n_chunks, (int)geo.cpg, drop_if_arg<DROP>(drop ? &hd : nullptr));
       }));
       GO_LAUNCH_CHECK();
     }
-    {
-      ProfScope prof("attn_edge_fwd_merge", st, "k_attn_edge_piece_add");
-      hipLaunchKernelGGL(k_attn_edge_piece_max, dim3((unsigned)ceil_div(np * h, 256)), dim3(256), 0, st, a.p_row, a.p_ml,
-                         Mtmp, np * h, (int)h);
-      const unsigned gb = (unsigned)ceil_div(np, GPB);
-      GO_DISPATCH_GAT_HD(h, d, {
-        hipLaunchKernelGGL((k_attn_edge_piece_add<H, D>), dim3(gb), dim3(kFastBlock), 0, st, a.p_row, a.p_ml, a.p_o, Mtmp,
-                           Ltmp, a.o, np);
-        hipLaunchKernelGGL((k_attn_edge_piece_fin<H, D>), dim3(gb), dim3(kFastBlock), 0, st, a.p_row, Mtmp, Ltmp, a.o,
-                           a.stats, np);
-      });
-      GO_LAUNCH_CHECK();
-    }
+    attn_pieces_merge(
+        "attn_edge_fwd_merge", "k_attn_edge_piece_add", w, geo.lanes, st,
+        [&](dim3 grid, dim3 block) {
+          hipLaunchKernelGGL(k_attn_edge_piece_max, grid, block, 0, st, w.p_row, w.p_ml, w.Mtmp, w.np * h, (int)h);
+        },
+        [&](dim3 grid, dim3 block) {
+          GO_DISPATCH_GAT_HD(h, d, {
+            hipLaunchKernelGGL((k_attn_edge_piece_add<H, D>), grid, block, 0, st, w.p_row, w.p_ml, w.p_o, w.Mtmp, w.Ltmp,
+                               a.o, w.np);
+          });
+        },
+        [&](dim3 grid, dim3 block) {
+          GO_DISPATCH_GAT_HD(h, d, {
+            hipLaunchKernelGGL((k_attn_edge_piece_fin<H, D>), grid, block, 0, st, w.p_row, w.Mtmp, w.Ltmp, a.o, a.stats,
+                               w.np);
+          });
+        });
+    GO_LAUNCH_CHECK();
     return GRAPHOP_OK;
   }
   const dim3 grid((unsigned)ceil_div(n_chunks, kGenericWavesPerBlock));
@@ -247,9 +228,7 @@ int graphop_attention_edge_backward(int dtype, const int64_t* row, const int64_t
   const bool fast_r = ok && row_slots && edge_plan_ok(pr, n_q, n_k);
   const bool fast_c = ok && col_slots && edge_plan_ok(pc, n_k, n_q);
   const EdgeBwdWs w(fast_r || fast_c, es, n_q, n_k, h, F);
-  GO_CHECK_ARG(!slots || (workspace != nullptr && workspace_bytes >= 0 && (size_t)workspace_bytes >= w.total),
-               "%s: workspace of %lld bytes needed (graphop_attention_edge_workspace_bytes), got %lld", fn,
-               (long long)w.total, (long long)workspace_bytes);
+  GO_TRY(attn_ws_check(fn, "attention_edge_workspace_bytes", slots, w.total, workspace, workspace_bytes));
   if (n_q * F > 0) { GO_PTR(fn, dQ); GO_HIP(zero_async(dQ, es * (size_t)(n_q * F), st)); }
   if (n_k * F > 0) {
     GO_PTR(fn, dK); GO_PTR(fn, dV);

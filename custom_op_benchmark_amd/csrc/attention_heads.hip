@@ -53,12 +53,6 @@ bool attn_heads_auto_ok(i64 h, i64 d, i64 n_edges, i64 n_q, i64 n_k, const graph
   return windows == 0;
 }
 
-template <bool DROP>
-inline AttnHeadsDropIf<DROP> heads_drop_arg(const AttnHeadsDrop* drop) {
-  if constexpr (DROP) return *drop;
-  else return NoDrop{};
-}
-
 struct HeadsBwdWs {
   size_t o_kv, o_qdo, o_st4, total;
   HeadsBwdWs(i64 n_q, i64 n_k, i64 h, i64 F) {
@@ -77,14 +71,12 @@ int launch_heads_rows(const char* tag, const graphop_plan* plan, const i64* eid,
   if (n_chunks == 0) return GRAPHOP_OK;
   ProfScope prof(tag, st, "k_attn_heads_bwd_rows_f32");
   const bool owned = plan->info.rows_sorted != 0, dropped = drop != nullptr, biased = b != nullptr;
-  i64 cpg, groups;
-  attn_rows_geometry(n_chunks, &cpg, &groups);
-  const unsigned nb = (unsigned)ceil_div(groups, kFastBlock / 16);
+  const ChunkGeometry geo = attn_rows_geometry(n_chunks);
   GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, GO_DISPATCH_BOOL(biased, BIAS, {
     if constexpr (H > 1)
-      hipLaunchKernelGGL((k_attn_heads_bwd_rows_f32<H, D, COL, OWNED, DROP, BIAS>), dim3(nb), dim3(kFastBlock), 0, st,
-                         (const i64*)plan->row, (const i64*)plan->indptr, eid, (const i64*)plan->indices, own, xt, st4, b,
-                         out0, out1, db, n_chunks, (int)cpg, heads_drop_arg<DROP>(drop));
+      hipLaunchKernelGGL((k_attn_heads_bwd_rows_f32<H, D, COL, OWNED, DROP, BIAS>), dim3(geo.blocks), dim3(kFastBlock), 0,
+                         st, (const i64*)plan->row, (const i64*)plan->indptr, eid, (const i64*)plan->indices, own, xt, st4,
+                         b, out0, out1, db, n_chunks, (int)geo.cpg, drop_if_arg<DROP>(drop));
   }))));
   GO_LAUNCH_CHECK();
   return GRAPHOP_OK;
@@ -115,57 +107,48 @@ int attn_heads_fwd_rows(const graphop_plan* plan, const i64* eid, i64 n_chunks, 
   if (!plan->info.rows_sorted || n_q >= kWalkRowMask) return 0;
   if (tuning().attn_heads < 0 && !attn_heads_auto_ok(h, d, n_edges, n_q, n_k, plan, st)) return 0;
   const i64 F = h * d;
-  i64 cpg, groups;
-  attn_rows_geometry(n_chunks, &cpg, &groups);
-  const i64 np = 2 * groups;
-  if (np >= 0x7fffffffLL) return 0;
-  const AttnRowsFwdWs w(np, n_q, h, F);
+  const ChunkGeometry geo = attn_rows_geometry(n_chunks);
+  if (2 * geo.groups >= 0x7fffffffLL) return 0;
+  const AttnRowsFwdWs w(ws, 2 * geo.groups, n_q, h, F);
   if (ws_needed) *ws_needed = w.total;
   if (dry_run) return 1;
   if (!ws || (size_t)ws_bytes < w.total) return 0;
-  char* base = (char*)ws;
   AttnHeadsFwdArgs a;
   a.Q = (const float*)Q; a.K = (const float*)K; a.V = (const float*)V; a.b = (const float*)b;
   a.o = (float*)o; a.stats = (float*)stats;
-  a.p_row = (int*)(base + w.o_row); a.p_ml = (float*)(base + w.o_ml); a.p_o = (float*)(base + w.o_po);
-  float* Mtmp = (float*)(base + w.o_m);
-  float* Ltmp = (float*)(base + w.o_l);
+  a.p_row = w.p_row; a.p_ml = w.p_ml; a.p_o = w.p_o;
   if (zero_async(o, sizeof(float) * (size_t)(n_q * F), st) != hipSuccess) return -GRAPHOP_ERR_HIP;
-  {
-    ProfScope prof("attn_heads_fwd_setup", st, "k_fill");
-    const i64 most = np > n_q * h ? np : n_q * h;
-    const unsigned fb = (unsigned)(ceil_div(most, 256) > 4096 ? 4096 : ceil_div(most, 256));
-    hipLaunchKernelGGL((k_fill<int>), dim3(fb), dim3(256), 0, st, a.p_row, np, -1);
-    hipLaunchKernelGGL((k_fill<float>), dim3(fb), dim3(256), 0, st, Mtmp, n_q * h, kAttnRowsNegBig);
-    hipLaunchKernelGGL((k_fill<float>), dim3(fb), dim3(256), 0, st, Ltmp, n_q * h, 0.f);
-  }
+  attn_pieces_fill("attn_heads_fwd_setup", w, kAttnNegBig, st);
   const i64* eids = plan->info.eid_identity ? nullptr : eid;
   const bool dropped = drop != nullptr, biased = b != nullptr;
-  constexpr int GPB = kFastBlock / 16;
   {
     ProfScope prof("attn_heads_fwd_rows", st, "k_attn_heads_fwd_rows_f32");
-    const unsigned nb = (unsigned)ceil_div(groups, GPB);
     GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(dropped, DROP, GO_DISPATCH_BOOL(biased, BIAS, {
       if constexpr (H > 1)
-        hipLaunchKernelGGL((k_attn_heads_fwd_rows_f32<H, D, DROP, BIAS>), dim3(nb), dim3(kFastBlock), 0, st,
+        hipLaunchKernelGGL((k_attn_heads_fwd_rows_f32<H, D, DROP, BIAS>), dim3(geo.blocks), dim3(kFastBlock), 0, st,
                            (const i64*)plan->row, (const i64*)plan->indptr, eids, (const i64*)plan->indices, a, n_chunks,
-                           (int)cpg, heads_drop_arg<DROP>(drop));
+                           (int)geo.cpg, drop_if_arg<DROP>(drop));
     })));
   }
-  {
-    ProfScope prof("attn_heads_fwd_merge", st, "k_attn_heads_piece_add");
-    hipLaunchKernelGGL(k_attn_heads_piece_max, dim3((unsigned)ceil_div(np * h, 256)), dim3(256), 0, st, a.p_row, a.p_ml,
-                       Mtmp, np * h, (int)h);
-    const unsigned gb = (unsigned)ceil_div(np, GPB);
-    GO_DISPATCH_GAT_HD(h, d, {
-      if constexpr (H > 1) {
-        hipLaunchKernelGGL((k_attn_heads_piece_add<H, D>), dim3(gb), dim3(kFastBlock), 0, st, a.p_row, a.p_ml, a.p_o, Mtmp,
-                           Ltmp, a.o, np);
-        hipLaunchKernelGGL((k_attn_heads_piece_fin<H, D>), dim3(gb), dim3(kFastBlock), 0, st, a.p_row, Mtmp, Ltmp, a.o,
-                           a.stats, np);
-      }
-    });
-  }
+  attn_pieces_merge(
+      "attn_heads_fwd_merge", "k_attn_heads_piece_add", w, geo.lanes, st,
+      [&](dim3 grid, dim3 block) {
+        hipLaunchKernelGGL(k_attn_heads_piece_max, grid, block, 0, st, w.p_row, w.p_ml, w.Mtmp, w.np * h, (int)h);
+      },
+      [&](dim3 grid, dim3 block) {
+        GO_DISPATCH_GAT_HD(h, d, {
+          if constexpr (H > 1)
+            hipLaunchKernelGGL((k_attn_heads_piece_add<H, D>), grid, block, 0, st, w.p_row, w.p_ml, w.p_o, w.Mtmp, w.Ltmp,
+                               a.o, w.np);
+        });
+      },
+      [&](dim3 grid, dim3 block) {
+        GO_DISPATCH_GAT_HD(h, d, {
+          if constexpr (H > 1)
+            hipLaunchKernelGGL((k_attn_heads_piece_fin<H, D>), grid, block, 0, st, w.p_row, w.Mtmp, w.Ltmp, a.o, a.stats,
+                               w.np);
+        });
+      });
   if (hipGetLastError() != hipSuccess) return -GRAPHOP_ERR_HIP;
   return 1;
 }

@@ -13,6 +13,7 @@
 
 #include "common.h"
 #include "host.h"
+#include "host_attn_rows.h"
 #include "kernels_fast.h"
 #include "kernels_walk.h"
 #include "kernels_attn_walk.h"
@@ -25,15 +26,9 @@ namespace graphop {
 
 namespace {
 
-// Chunks per lane group of the chunk drivers: the tuned value amortises row switches on big graphs,
-// but a small graph (Cora-shape: 2.8 K chunks) must still put a few lane groups on every CU --
-// 16 chunks per group there left 13 workgroups walking chunks serially (33 us per pass).
+// chunks per lane group of the core ops' chunk drivers: a float4 per lane, 64 lanes at most
 inline int cpg_for(i64 n_chunks, int cpg_max, int F) {
-  const int lanes = F >= 256 ? 64 : (F / 4 > 0 ? F / 4 : 1);
-  const i64 groups_wanted = (i64)tuning().n_cu * (kFastBlock / lanes) * 8;
-  i64 c = n_chunks / (groups_wanted > 0 ? groups_wanted : 1);
-  if (c < 1) c = 1;
-  return (int)(c < cpg_max ? c : cpg_max);
+  return (int)chunks_per_group(n_chunks, F >= 256 ? 64 : (F / 4 > 0 ? F / 4 : 1), cpg_max);
 }
 
 inline unsigned blocks_for(i64 work, i64 per_block) {
@@ -412,28 +407,16 @@ int attn_fwd_walk(const graphop_plan* plan, i64 n_q, i64 n_k, i64 h, i64 d, int 
   if (use != 1) return use;
   // one pacing step per window (the SpMM walk's two per window measured 1 % slower here: 11.93 vs 11.78 ms per fused step)
   if (t.walk_steps > 1 && wl.view.steps >= 2 * t.walk_steps) wl.view.steps /= t.walk_steps;
-  const i64 bins = (i64)wl.view.groups * wl.view.rounds, np = 2 * bins, F = 4 * L;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_row = 0, o_ml = o_row + up(sizeof(int) * (size_t)np), o_po = o_ml + up(sizeof(float) * 2 * (size_t)np);
-  const size_t o_m = o_po + up(sizeof(float) * (size_t)(np * F)), o_l = o_m + up(sizeof(float) * (size_t)n_q);
-  const size_t need = o_l + up(sizeof(float) * (size_t)n_q);
-  if (ws_needed) *ws_needed = need;
+  const i64 bins = (i64)wl.view.groups * wl.view.rounds, F = 4 * L;
+  const AttnRowsFwdWs w(ws, 2 * bins, n_q, 1, F);
+  if (ws_needed) *ws_needed = w.total;
   if (dry_run) return 1;
-  if (!ws || (size_t)ws_bytes < need) return 0;    // (the caller sized the workspace for the composed path: always larger)
-  char* base = (char*)ws;
+  if (!ws || (size_t)ws_bytes < w.total) return 0;    // (the caller sized the workspace for the composed path: always larger)
   AttnWalkArgs a;
   a.Q = (const float*)Q; a.K = (const float*)K; a.V = (const float*)V; a.o = (float*)o; a.stats = (float*)stats;
-  a.p_row = (int*)(base + o_row); a.p_ml = (float*)(base + o_ml); a.p_o = (float*)(base + o_po);
-  float* Mtmp = (float*)(base + o_m);
-  float* Ltmp = (float*)(base + o_l);
+  a.p_row = w.p_row; a.p_ml = w.p_ml; a.p_o = w.p_o;
   if (zero_async(o, sizeof(float) * (size_t)(n_q * F), st) != hipSuccess) return -GRAPHOP_ERR_HIP;
-  {
-    ProfScope prof("attn_fwd_setup", st, "k_fill");
-    const unsigned fb = (unsigned)(ceil_div(np > n_q ? np : n_q, 256) > 4096 ? 4096 : ceil_div(np > n_q ? np : n_q, 256));
-    hipLaunchKernelGGL((k_fill<int>), dim3(fb), dim3(256), 0, st, a.p_row, np, -1);
-    hipLaunchKernelGGL((k_fill<float>), dim3(fb), dim3(256), 0, st, Mtmp, n_q, kAttnNegBig);
-    hipLaunchKernelGGL((k_fill<float>), dim3(fb), dim3(256), 0, st, Ltmp, n_q, 0.f);
-  }
+  attn_pieces_fill("attn_fwd_setup", w, kAttnNegBig, st);
   {
     WalkDebug dbg;
     dbg.arm(&wl, "attn_fwd", st, kWalkWorkers / kWave);
@@ -448,21 +431,22 @@ int attn_fwd_walk(const graphop_plan* plan, i64 n_q, i64 n_k, i64 h, i64 d, int 
       hipLaunchKernelGGL((k_attn_fwd_walk_f32<L, false>), dim3(wl.blocks), dim3(kWalkThreads), lds_bytes, st, wl.view, a, NoDrop{});
     }
   }
-  {
-    ProfScope prof("attn_fwd_merge", st, "k_attn_piece_add");
-    hipLaunchKernelGGL(k_attn_piece_max, dim3((unsigned)ceil_div(np, 256)), dim3(256), 0, st, a.p_row, a.p_ml, Mtmp, np);
-    const unsigned gb = (unsigned)ceil_div(np, kFastBlock / L);
-    hipLaunchKernelGGL((k_attn_piece_add<L>), dim3(gb), dim3(kFastBlock), 0, st, a.p_row, a.p_ml, a.p_o, Mtmp, Ltmp, a.o, np);
-    hipLaunchKernelGGL((k_attn_piece_fin<L>), dim3(gb), dim3(kFastBlock), 0, st, a.p_row, Mtmp, Ltmp, a.o, a.stats, np);
-  }
+  attn_pieces_merge(
+      "attn_fwd_merge", "k_attn_piece_add", w, L, st,
+      [&](dim3 grid, dim3 block) { hipLaunchKernelGGL(k_attn_piece_max, grid, block, 0, st, w.p_row, w.p_ml, w.Mtmp, w.np); },
+      [&](dim3 grid, dim3 block) {
+        hipLaunchKernelGGL((k_attn_piece_add<L>), grid, block, 0, st, w.p_row, w.p_ml, w.p_o, w.Mtmp, w.Ltmp, a.o, w.np);
+      },
+      [&](dim3 grid, dim3 block) {
+        hipLaunchKernelGGL((k_attn_piece_fin<L>), grid, block, 0, st, w.p_row, w.Mtmp, w.Ltmp, a.o, a.stats, w.np);
+      });
   if (hipGetLastError() != hipSuccess) return -GRAPHOP_ERR_HIP;
   return 1;
 }
 
 // Fused attention forward with a per-edge score bias, chunk-driver form (kernels_attn_bias_fwd.h): fp32, one head, d a
-// power of two in 16..1024, a plan with sorted rows and its neighbour ids, id ranges inside the tables.  The chunks per
-// lane group and the grid are those of the chunk-driver backward (attention.hip: launch_attn_rows).  Workspace: 2 x
-// groups piece records + two n_q-sized merge arrays.
+// power of two in 16..1024, a plan with sorted rows and its neighbour ids, id ranges inside the tables.  Launch geometry:
+// attn_one_head_geometry, the chunk-driver backward's.  Workspace: 2 x groups piece records (AttnRowsFwdWs).
 int attn_bias_fwd_rows(const graphop_plan* plan, const i64* eid, i64 n_chunks, i64 n_edges, i64 n_q, i64 n_k, i64 h,
                        i64 d, int dtype, const void* Q, const void* K, const void* V, const void* b, void* o,
                        void* stats, void* ws, i64 ws_bytes, hipStream_t st, bool dry_run, size_t* ws_needed,
@@ -474,60 +458,47 @@ int attn_bias_fwd_rows(const graphop_plan* plan, const i64* eid, i64 n_chunks, i
   if (!plan->info.rows_sorted || !plan->indices) return 0;
   if (plan->info.max_row >= n_q || plan->info.max_index >= n_k || n_q >= kWalkRowMask) return 0;
   const i64 F = d;
-  const int Lg = (int)(F / 4 < 64 ? F / 4 : 64), GPB = kFastBlock / Lg;
-  const i64 groups_wanted = (i64)t.n_cu * GPB * 8;
-  i64 cpg = n_chunks / (groups_wanted > 0 ? groups_wanted : 1);
-  cpg = cpg < 1 ? 1 : (cpg > 16 ? 16 : cpg);
-  const i64 groups = ceil_div(n_chunks, cpg), np = 2 * groups;
-  if (np >= 0x7fffffffLL) return 0;
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t o_row = 0, o_ml = o_row + up(sizeof(int) * (size_t)np), o_po = o_ml + up(sizeof(float) * 2 * (size_t)np);
-  const size_t o_m = o_po + up(sizeof(float) * (size_t)(np * F)), o_l = o_m + up(sizeof(float) * (size_t)n_q);
-  const size_t need = o_l + up(sizeof(float) * (size_t)n_q);
-  if (ws_needed) *ws_needed = need;
+  const ChunkGeometry geo = attn_one_head_geometry(n_chunks, F);
+  if (2 * geo.groups >= 0x7fffffffLL) return 0;
+  const AttnRowsFwdWs w(ws, 2 * geo.groups, n_q, 1, F);
+  if (ws_needed) *ws_needed = w.total;
   if (dry_run) return 1;
-  if (!ws || (size_t)ws_bytes < need) return 0;
-  char* base = (char*)ws;
+  if (!ws || (size_t)ws_bytes < w.total) return 0;
   AttnBiasFwdArgs a;
   a.Q = (const float*)Q; a.K = (const float*)K; a.V = (const float*)V; a.b = (const float*)b;
   a.o = (float*)o; a.stats = (float*)stats;
-  a.p_row = (int*)(base + o_row); a.p_ml = (float*)(base + o_ml); a.p_o = (float*)(base + o_po);
-  float* Mtmp = (float*)(base + o_m);
-  float* Ltmp = (float*)(base + o_l);
+  a.p_row = w.p_row; a.p_ml = w.p_ml; a.p_o = w.p_o;
   if (zero_async(o, sizeof(float) * (size_t)(n_q * F), st) != hipSuccess) return -GRAPHOP_ERR_HIP;
-  {
-    ProfScope prof("attn_bias_fwd_setup", st, "k_fill");
-    const unsigned fb = (unsigned)(ceil_div(np > n_q ? np : n_q, 256) > 4096 ? 4096 : ceil_div(np > n_q ? np : n_q, 256));
-    hipLaunchKernelGGL((k_fill<int>), dim3(fb), dim3(256), 0, st, a.p_row, np, -1);
-    hipLaunchKernelGGL((k_fill<float>), dim3(fb), dim3(256), 0, st, Mtmp, n_q, kAttnNegBig);
-    hipLaunchKernelGGL((k_fill<float>), dim3(fb), dim3(256), 0, st, Ltmp, n_q, 0.f);
-  }
+  attn_pieces_fill("attn_bias_fwd_setup", w, kAttnNegBig, st);
   const i64* eids = plan->info.eid_identity ? nullptr : eid;
-  const unsigned nb = (unsigned)ceil_div(groups, GPB);
   {
     ProfScope prof("attn_bias_fwd_rows", st, drop ? "k_attn_bias_fwd_rows_f32<DROP>" : "k_attn_bias_fwd_rows_f32");
     GO_DISPATCH_LNV((int)F, {
       if (drop)
-        hipLaunchKernelGGL((k_attn_bias_fwd_rows_f32<L, NV, true>), dim3(nb), dim3(kFastBlock), 0, st,
+        hipLaunchKernelGGL((k_attn_bias_fwd_rows_f32<L, NV, true>), dim3(geo.blocks), dim3(kFastBlock), 0, st,
                            (const i64*)plan->row, (const i64*)plan->indptr, eids, (const i64*)plan->indices, a, n_chunks,
-                           (int)cpg, *drop);
+                           (int)geo.cpg, *drop);
       else
-        hipLaunchKernelGGL((k_attn_bias_fwd_rows_f32<L, NV, false>), dim3(nb), dim3(kFastBlock), 0, st,
+        hipLaunchKernelGGL((k_attn_bias_fwd_rows_f32<L, NV, false>), dim3(geo.blocks), dim3(kFastBlock), 0, st,
                            (const i64*)plan->row, (const i64*)plan->indptr, eids, (const i64*)plan->indices, a, n_chunks,
-                           (int)cpg, NoDrop{});
+                           (int)geo.cpg, NoDrop{});
     });
   }
-  {
-    ProfScope prof("attn_bias_fwd_merge", st, "k_attn_bias_piece_add");
-    hipLaunchKernelGGL(k_attn_piece_max, dim3((unsigned)ceil_div(np, 256)), dim3(256), 0, st, a.p_row, a.p_ml, Mtmp, np);
-    const unsigned gb = (unsigned)ceil_div(np, GPB);
-    GO_DISPATCH_LNV((int)F, {
-      hipLaunchKernelGGL((k_attn_bias_piece_add<L, NV>), dim3(gb), dim3(kFastBlock), 0, st, a.p_row, a.p_ml, a.p_o, Mtmp,
-                         Ltmp, a.o, np);
-      hipLaunchKernelGGL((k_attn_bias_piece_fin<L, NV>), dim3(gb), dim3(kFastBlock), 0, st, a.p_row, Mtmp, Ltmp, a.o,
-                         a.stats, np);
-    });
-  }
+  attn_pieces_merge(
+      "attn_bias_fwd_merge", "k_attn_bias_piece_add", w, geo.lanes, st,
+      [&](dim3 grid, dim3 block) { hipLaunchKernelGGL(k_attn_piece_max, grid, block, 0, st, w.p_row, w.p_ml, w.Mtmp, w.np); },
+      [&](dim3 grid, dim3 block) {
+        GO_DISPATCH_LNV((int)F, {
+          hipLaunchKernelGGL((k_attn_bias_piece_add<L, NV>), grid, block, 0, st, w.p_row, w.p_ml, w.p_o, w.Mtmp, w.Ltmp,
+                             a.o, w.np);
+        });
+      },
+      [&](dim3 grid, dim3 block) {
+        GO_DISPATCH_LNV((int)F, {
+          hipLaunchKernelGGL((k_attn_bias_piece_fin<L, NV>), grid, block, 0, st, w.p_row, w.Mtmp, w.Ltmp, a.o, a.stats,
+                             w.np);
+        });
+      });
   if (hipGetLastError() != hipSuccess) return -GRAPHOP_ERR_HIP;
   return 1;
 }

@@ -136,6 +136,27 @@ struct SweepView;   // kernels_fast.h
 
 namespace graphop {
 
+// Chunks per lane group of a chunk-driver pass whose lane groups have `lanes` lanes: the cap (a tuned value or a
+// kernel's own) amortises row switches on big graphs, but a small graph must still put `rounds` rounds of resident lane
+// groups on every CU -- Cora-shape, 2.8 K chunks: 16 chunks per group left 13 workgroups walking chunks serially (33 us
+// per pass).  Every launch of such a pass and every workspace size that follows from one takes the value from here.
+inline i64 chunks_per_group(i64 n_chunks, int lanes, i64 cap, int rounds = 8) {
+  const i64 groups_wanted = (i64)tuning().n_cu * (kFastBlock / lanes) * rounds;
+  const i64 c = n_chunks / (groups_wanted > 0 ? groups_wanted : 1);
+  return c < 1 ? 1 : (c < cap ? c : cap);
+}
+
+// ... with the lane groups and the workgroups of kFastBlock threads that follow from it
+struct ChunkGeometry {
+  i64 cpg, groups;
+  unsigned blocks;
+  int lanes;
+};
+inline ChunkGeometry chunk_geometry(i64 n_chunks, int lanes, i64 cap, int rounds = 8) {
+  const i64 cpg = chunks_per_group(n_chunks, lanes, cap, rounds), groups = ceil_div(n_chunks, cpg);
+  return {cpg, groups, (unsigned)ceil_div(groups, (i64)(kFastBlock / lanes)), lanes};
+}
+
 struct SweepLaunch {
   SweepView view;
   unsigned blocks;

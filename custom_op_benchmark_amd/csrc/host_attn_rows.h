@@ -1,7 +1,10 @@
-// Host side of the fused dot-product attention ops, stated once: the argument checks every entry point makes first
-// (attention.hip, attention_edge.hip) and the launch geometry and forward workspace of the several-head chunk-driver
-// passes (attention_heads.hip, attention_edge.hip; kernels_attn_rows_passes.inc).
+// Host side of the fused dot-product attention ops, stated once: the argument checks every entry point makes first, the
+// workspace check, the launch geometry of the chunk-driver passes, and the piece-record forward -- its workspace, its
+// fills and its merge -- that attn_fwd_walk, attn_bias_fwd_rows (graphop_hip.hip), attn_heads_fwd_rows
+// (attention_heads.hip) and graphop_attention_edge_forward (attention_edge.hip) run around their own pass.
 #pragma once
+#include <type_traits>
+
 #include "common.h"
 #include "host.h"
 #include "host_dropout.h"
@@ -34,30 +37,80 @@ inline int attn_drop_check(const char* fn, const DropIn& in, i64 n_q, i64 n_k, H
   return GRAPHOP_OK;
 }
 
-// Chunks per lane group and lane groups of a pass over n_chunks chunks: launch_attn_rows' rule for 16-lane groups, with
-// four (not eight) rounds of resident workgroups wanted -- these kernels hold 150 to 240 VGPRs, two workgroups per CU
-// where the one-head kernels hold four, so the same number of rounds per resident slot needs half the groups, and
-// every group of the forward costs two piece records of (1 + 2 h + F) words.
-inline void attn_rows_geometry(i64 n_chunks, i64* cpg_out, i64* groups_out) {
-  constexpr int GPB = kFastBlock / 16;
-  const i64 groups_wanted = (i64)tuning().n_cu * GPB * 4;
-  i64 cpg = n_chunks / (groups_wanted > 0 ? groups_wanted : 1);
-  cpg = cpg < 1 ? 1 : (cpg > 16 ? 16 : cpg);
-  *cpg_out = cpg;
-  *groups_out = ceil_div(n_chunks, cpg);
+// the workspace a form needs against the one the caller brought; query: the graphop_*_workspace_bytes that reports it
+inline int attn_ws_check(const char* fn, const char* query, bool needed, size_t need, const void* workspace,
+                         i64 workspace_bytes) {
+  GO_CHECK_ARG(!needed || (workspace != nullptr && workspace_bytes >= 0 && (size_t)workspace_bytes >= need),
+               "%s: workspace of %lld bytes needed (graphop_%s), got %lld", fn, (long long)need, query,
+               (long long)workspace_bytes);
+  return GRAPHOP_OK;
 }
 
-// the forward's workspace: np = 2 * groups piece records (row, (m, l) per head, o) and (Mtmp, Ltmp) per (row, head)
+// the kernel argument of a DROP instantiation from the pass's dropout record (AttnDrop, AttnHeadsDrop, AttnEdgeDrop);
+// drop is NULL exactly where DROP is false
+template <bool DROP, class D>
+inline std::conditional_t<DROP, D, NoDrop> drop_if_arg(const D* drop) {
+  if constexpr (DROP) return *drop;
+  else return NoDrop{};
+}
+
+// The one-head chunk-driver passes (k_attn_bwd_rows_f32, k_attn_bias_bwd_rows_f32, k_attn_bias_fwd_rows_f32): lane groups
+// of GO_DISPATCH_LNV's L lanes for rows of F floats, at most 16 chunks each.
+inline ChunkGeometry attn_one_head_geometry(i64 n_chunks, i64 F) {
+  return chunk_geometry(n_chunks, (int)(F / 4 < 64 ? F / 4 : 64), 16);
+}
+
+// The several-head and edge passes (kernels_attn_rows_passes.inc): 16-lane groups and four (not eight) rounds of resident
+// workgroups wanted -- these kernels hold 150 to 240 VGPRs, two workgroups per CU where the one-head kernels hold four,
+// so the same number of rounds per resident slot needs half the groups, and every group of the forward costs two piece
+// records of (1 + 2 h + F) words.
+inline ChunkGeometry attn_rows_geometry(i64 n_chunks) { return chunk_geometry(n_chunks, 16, 16, /*rounds=*/4); }
+
+// The workspace of a piece-record forward.  A pass whose lane groups (or bins) share rows leaves what it saw of a shared
+// row as a piece record -- the row word, (m, l) per head, the o row of F floats -- and np records are merged into o and
+// stats through (Mtmp, Ltmp) per (row, head).  base == NULL: the size query, only `total` means anything.
 struct AttnRowsFwdWs {
-  size_t o_row, o_ml, o_po, o_m, o_l, total;
-  AttnRowsFwdWs(i64 np, i64 n_q, i64 h, i64 F) {
-    o_row = 0;
-    o_ml = o_row + up256(sizeof(int) * (size_t)np);
-    o_po = o_ml + up256(sizeof(float) * 2 * (size_t)(np * h));
-    o_m = o_po + up256(sizeof(float) * (size_t)(np * F));
-    o_l = o_m + up256(sizeof(float) * (size_t)(n_q * h));
-    total = o_l + up256(sizeof(float) * (size_t)(n_q * h));
+  int* p_row;
+  float *p_ml, *p_o, *Mtmp, *Ltmp;
+  size_t total = 0;
+  i64 np, h, n_ml;   // records; heads; (row, head) pairs
+  AttnRowsFwdWs(void* base, i64 np_, i64 n_q, i64 h_, i64 F) : np(np_), h(h_), n_ml(n_q * h_) {
+    auto take = [&](size_t bytes) {
+      void* p = base ? (char*)base + total : nullptr;
+      total += up256(bytes);
+      return p;
+    };
+    p_row = (int*)take(sizeof(int) * (size_t)np);
+    p_ml = (float*)take(sizeof(float) * 2 * (size_t)(np * h));
+    p_o = (float*)take(sizeof(float) * (size_t)(np * F));
+    Mtmp = (float*)take(sizeof(float) * (size_t)n_ml);
+    Ltmp = (float*)take(sizeof(float) * (size_t)n_ml);
   }
 };
+
+// before the pass: no record, no score yet (the kernels' kAttnNegBig), empty sums.  Ws = AttnRowsFwdWs: a template, as
+// the merge is, so that only the translation units that run a forward instantiate k_fill.
+template <class Ws>
+inline void attn_pieces_fill(const char* tag, const Ws& w, float no_score, hipStream_t st) {
+  ProfScope prof(tag, st, "k_fill");
+  const i64 most = w.np > w.n_ml ? w.np : w.n_ml;
+  const unsigned fb = (unsigned)(ceil_div(most, 256) > 4096 ? 4096 : ceil_div(most, 256));
+  hipLaunchKernelGGL((k_fill<int>), dim3(fb), dim3(256), 0, st, w.p_row, w.np, -1);
+  hipLaunchKernelGGL((k_fill<float>), dim3(fb), dim3(256), 0, st, w.Mtmp, w.n_ml, no_score);
+  hipLaunchKernelGGL((k_fill<float>), dim3(fb), dim3(256), 0, st, w.Ltmp, w.n_ml, 0.f);
+}
+
+// after the pass: the maxima per (record, head), then the sums and the division by lane groups of `lanes` lanes.  The
+// three kernels are the caller's (each family's piece_max has no template and lives in one translation unit); each
+// callable launches its kernel on the (grid, block) it is given.
+template <class Max, class Add, class Fin>
+inline void attn_pieces_merge(const char* tag, const char* label, const AttnRowsFwdWs& w, int lanes, hipStream_t st,
+                              Max piece_max, Add piece_add, Fin piece_fin) {
+  ProfScope prof(tag, st, label);
+  piece_max(dim3((unsigned)ceil_div(w.np * w.h, 256)), dim3(256));
+  const dim3 grid((unsigned)ceil_div(w.np, (i64)(kFastBlock / lanes))), block(kFastBlock);
+  piece_add(grid, block);
+  piece_fin(grid, block);
+}
 
 }  // namespace graphop

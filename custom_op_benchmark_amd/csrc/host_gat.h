@@ -137,14 +137,9 @@ struct GatLabels {
             {{"k_" op "_" pass "_generic", "k_" op "_" pass "_f32"}, \
              {"k_" op "_drop_" pass "_generic", "k_" op "_drop_" pass "_f32"}}}
 
-// chunks per lane group of G lanes: up to the tuned cap (sddmm_cpg or spmm_cpg; below 1 it counts as 1) on big graphs,
-// fewer on small ones so every CU still gets groups
+// chunks per lane group of G lanes (chunks_per_group) with the tuned cap, sddmm_cpg or spmm_cpg; below 1 it counts as 1
 inline int gat_cpg(i64 n_chunks, int cap, int G = kGatGroup) {
-  const i64 groups_wanted = (i64)tuning().n_cu * (kFastBlock / G) * 8;
-  i64 c = n_chunks / (groups_wanted > 0 ? groups_wanted : 1);
-  if (cap < 1) cap = 1;
-  if (c > cap) c = cap;
-  return (int)(c < 1 ? 1 : c);
+  return (int)chunks_per_group(n_chunks, G, cap < 1 ? 1 : cap);
 }
 
 // grid of a fast gather pass: lane groups of G lanes, cpg chunks each

@@ -7,7 +7,7 @@
 
 namespace graphop {
 
-constexpr float kAttnRowsNegBig = -3.0e38f;   // "no score yet" (finite: differences of two of them are 0, not NaN)
+constexpr float kAttnNegBig = -3.0e38f;   // "no score yet" (finite: differences of two of them are 0, not NaN)
 __device__ __forceinline__ float attn_rows_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896341f); }   // x <= 0
 
 __device__ __forceinline__ float4 attn_rows_add4(const float4& a, const float4& b) {

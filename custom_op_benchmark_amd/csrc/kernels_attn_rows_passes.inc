@@ -130,7 +130,7 @@ __global__ __launch_bounds__(kFastBlock) void AR_KERNEL(fwd_rows_f32)(
       for (int v = 0; v < NV; ++v) {
         q[v] = ld4(a.Q, r * F4 + v * L + l);
         o_c[v] = make_float4(0.f, 0.f, 0.f, 0.f);
-        m_c[v] = kAttnRowsNegBig;
+        m_c[v] = kAttnNegBig;
         l_c[v] = 0.f;
       }
     }
@@ -210,7 +210,7 @@ __global__ __launch_bounds__(kFastBlock) void AR_KERNEL(fwd_rows_f32)(
 }
 
 // ---- merge of the shared rows' pieces: the walk's three kernels with (m, l) per (piece, head) -----------------------
-// Mtmp[row, k] starts at kAttnRowsNegBig, Ltmp[row, k] at 0, o is zero where pieces will be added.
+// Mtmp[row, k] starts at kAttnNegBig, Ltmp[row, k] at 0, o is zero where pieces will be added.
 __global__ void AR_KERNEL(piece_max)(const int* __restrict__ p_row, const float* __restrict__ p_ml,
                                      float* __restrict__ Mtmp, i64 n, int h) {   // n = pieces * h
   const i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x;
