@@ -136,6 +136,8 @@ _SIGNATURES = {
     + [ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _c64],
     "graphop_attention_edge_backward": [ctypes.c_int] + [_P] * 19 + [_c64] * 7 + [_P, _c64, _P, _P, _P]
     + [ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _c64],
+    # the weights of those ops from their row statistics: Q, K, stats, b | NULL, xe | NULL, a; no workspace
+    "graphop_attention_weights": [ctypes.c_int] + [_P] * 10 + [_c64] * 6 + [_P, _P],
 }
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ["graphop_abi_version", "graphop_last_error",
                                                "graphop_plan_destroy", "graphop_memory_bytes", "graphop_tune_key"])

@@ -629,6 +629,35 @@ std::vector<at::Tensor> attention_edge_backward(const at::Tensor& row, const at:
   return {dQ, dK, dV, dxe};
 }
 
+// ---- the weights of the fused attention ops from their row statistics (include/graphop_hip.h: graphop_attention_weights)
+at::Tensor attention_weights(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
+                             const at::Tensor& indices, const at::Tensor& Q, const at::Tensor& K, const at::Tensor& stats,
+                             const c10::optional<at::Tensor>& b, const c10::optional<at::Tensor>& xe) {
+  const char* fn = "attention_weights";
+  CHECK_CSR(row, indptr, eid, indices);
+  CHECK_INPUT(Q); CHECK_INPUT(K); CHECK_INPUT(stats);
+  if (b) check_attn_bias_input(*b);
+  TORCH_CHECK(!(b && xe), fn, ": at most one of b and xe may be given");
+  CHECK_SAME_DTYPE(Q, K); CHECK_SAME_DTYPE(Q, stats);
+  TORCH_CHECK((Q.dim() == 2 || Q.dim() == 3) && Q.sizes().slice(1) == K.sizes().slice(1),
+              fn, ": Q (n_q,[h,]d) and K (n_k,[h,]d) expected");
+  const int64_t e = eid.size(0), d = Q.size(-1), h = Q.dim() == 2 ? 1 : Q.size(1), n_q = Q.size(0), n_k = K.size(0);
+  TORCH_CHECK(stats.dim() == 3 && stats.size(0) == n_q && stats.size(1) == h && stats.size(2) == 2,
+              fn, ": stats must be (n_q, h, 2) = (", n_q, ", ", h, ", 2), got ", stats.sizes());
+  if (b) check_attn_bias(fn, *b, Q, e, h);
+  if (xe) check_attn_edge_rows(fn, *xe, Q, e);
+  DeviceGuard dg(Q);
+  const auto pp = get_plan(row, indptr, eid, indices, n_k);
+  const auto& pl = *pp;
+  // a[e] is written once per row-major slot: only a chunk list that leaves slots out needs the zeros
+  const std::vector<int64_t> shape = Q.dim() == 2 ? std::vector<int64_t>{e} : std::vector<int64_t>{e, h};
+  auto a = pl.info.full_coverage ? at::empty(shape, Q.options()) : at::zeros(shape, Q.options());
+  check(graphop_attention_weights(dtype_code(Q), ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(stats),
+                                  b ? vp(*b) : nullptr, xe ? vp(*xe) : nullptr, vp(a), row.size(0), e, n_q, n_k, h, d,
+                                  pl.plan, stream_of(Q)));
+  return a;
+}
+
 // ---- the extra GAT score op (include/graphop_hip.h: graphop_gat_scores_*) ---------------------------------
 int64_t gat_heads(const at::Tensor& el, const at::Tensor& er, const char* fn) {
   CHECK_SAME_DTYPE(el, er);
@@ -1156,6 +1185,11 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("indices_c"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("xe"), py::arg("o"), py::arg("stats"),
         py::arg("dO"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0, py::arg("head0") = 0,
         py::arg("need_dxe") = true);
+  // (and the weights of all of these from their row statistics)
+  m.def("attention_weights", &attention_weights,
+        "Attention weights of the fused attention ops from their row statistics (extra op)", py::arg("row"),
+        py::arg("indptr"), py::arg("eid"), py::arg("indices"), py::arg("Q"), py::arg("K"), py::arg("stats"),
+        py::arg("b") = py::none(), py::arg("xe") = py::none());
   m.def("gat_scores_forward", &gat_scores_forward, "GAT additive attention scores forward (extra op)", py::arg("row"),
         py::arg("indptr"), py::arg("eid"), py::arg("indices"), py::arg("el"), py::arg("er"), py::arg("negative_slope") = 0.2);
   m.def("gat_scores_backward", &gat_scores_backward, "GAT additive attention scores backward (extra op)", py::arg("row"),

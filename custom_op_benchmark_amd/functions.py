@@ -473,6 +473,88 @@ class FusedAttentionEdge(Function):
         return (None,) * 8 + (dQ, dK, dV, dxe if need_dxe else None, None, None, None)
 
 
+class FusedAttentionWeights(Function):
+    """The fused dot-product attention layer that also returns its attention weights (extra op; PyG's
+    return_attention_weights=True, DGL's get_attention=True):
+    apply(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, b=None, xe=None, p=0.0, seed=None,
+    offset=0) -> (o, a).  The mode follows the optional operand: neither is FusedAttentionDropout, b is
+    FusedAttentionBias, xe is FusedAttentionEdge (b and xe together are refused); o is that class's o.  a holds the
+    UNDROPPED weights by edge id -- (E) with 2-D Q / K / V, else (E, h), SparseSoftmax's layout -- computed from the row
+    statistics the forward left (graphop.attention_weights): one SDDMM and one stream pass, or one gather pass with xe,
+    not a second softmax.  The effective weights are a * graphop.edge_dropout_mask(...).
+    One call of the raw forward whatever h: there are no head groups (a is (E, h) anyway, so they would save nothing).
+    Saves the CSR arrays, (Q, K, V, [b | xe], o, row statistics) and NOT a.  The backward takes (dO, ga), either of which
+    may be None.  dO goes through the mode's fused backward; without it no fused pass is launched.  In the plain and
+    bias modes ga goes through a recomputed a: ds' = a (ga - sum_row a ga) (sparse_softmax_backward; exact, because
+    a = softmax(s) whatever produced (m, l)), dQ', dK' = maskedmm_csr_backward(ds'), db' = ds'; the edge-sized
+    temporaries a, ga and ds' are inherent once a is an output.  Without ga nothing beyond the fused backward runs.
+    With xe, a is marked non-differentiable: its gradient would need sum_e ds'_e xe[e] into dQ and ds'_e Q_i into dxe,
+    which nothing in the library does without (E, h, d) temporaries.  seed=None draws one from torch's default CPU
+    generator; there is no 1 / sqrt(d) scale argument: fold it into Q."""
+
+    @staticmethod
+    def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, b=None, xe=None, p=0.0,
+                seed=None, offset=0):
+        a8 = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
+        if b is not None and xe is not None:
+            raise RuntimeError("FusedAttentionWeights: at most one of b and xe may be given")
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item()) if float(p) > 0.0 else 0
+        ctx.drop = (float(p), int(seed), int(offset))
+        ctx.set_materialize_grads(False)
+        ctx.mode = "edge" if xe is not None else ("bias" if b is not None else "plain")
+        csr = a8[:4]
+        if xe is not None:
+            o, stats = _ops.attention_edge_forward(*csr, Q, K, V, xe, *ctx.drop, 0)
+        elif b is not None:
+            o, stats = _ops.attention_bias_forward(*csr, Q, K, V, b, *ctx.drop, 0)
+        else:
+            o, stats = _ops.attention_dropout_forward(*csr, Q, K, V, *ctx.drop, 0)
+        a = _ops.attention_weights(*csr, Q, K, stats, b, xe)
+        extra = () if ctx.mode == "plain" else ((xe,) if xe is not None else (b,))
+        ctx.save_for_backward(*a8, Q, K, V, *extra, o, stats)
+        if xe is not None:
+            ctx.mark_non_differentiable(a)
+        return o, a
+
+    @staticmethod
+    def backward(ctx, dO, ga):
+        a8, rest = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
+        row, indptr_r, eid_r, indices_r = a8[:4]
+        need_db, need_dxe = ctx.needs_input_grad[11], ctx.needs_input_grad[12]
+        db = dxe = None
+        if ctx.mode == "edge":
+            Q, K, V, xe, o, stats = rest
+            if dO is not None:
+                dQ, dK, dV, dxe = _ops.attention_edge_backward(*a8, Q, K, V, xe, o, stats, dO, *ctx.drop, 0, need_dxe)
+            else:
+                dQ, dK, dV = torch.zeros_like(Q), torch.zeros_like(K), torch.zeros_like(V)
+                dxe = torch.zeros_like(xe)
+            return (None,) * 8 + (dQ, dK, dV, None, dxe if need_dxe else None, None, None, None)
+        if ctx.mode == "bias":
+            Q, K, V, b, o, stats = rest
+        else:
+            (Q, K, V, o, stats), b = rest, None
+        if dO is None:
+            dQ, dK, dV = torch.zeros_like(Q), torch.zeros_like(K), torch.zeros_like(V)
+        elif b is not None:
+            dQ, dK, dV, db = _ops.attention_bias_backward(*a8, Q, K, V, b, o, stats, dO, *ctx.drop, 0, need_db)
+        else:
+            dQ, dK, dV = _ops.attention_dropout_backward(*a8, Q, K, V, o, stats, dO, *ctx.drop, 0)
+        if ga is not None:
+            a = _ops.attention_weights(row, indptr_r, eid_r, indices_r, Q, K, stats, b)
+            ds = _ops.sparse_softmax_backward(row, indptr_r, eid_r, a, ga.reshape(a.shape))
+            del a
+            dQ2, dK2 = _ops.maskedmm_csr_backward(*a8, Q, K, ds)
+            dQ += dQ2
+            dK += dK2
+            if need_db:
+                db = ds.reshape(b.shape) if dO is None else db.add_(ds.reshape(b.shape))
+        elif need_db and dO is None:
+            db = torch.zeros_like(b)
+        return (None,) * 8 + (dQ, dK, dV, db if need_db else None, None, None, None, None)
+
+
 def _head_slice(x, g0, hg):
     """Heads [g0, g0 + hg) of a (n, h, d) tensor as a contiguous (n, hg, d) tensor ((n, d) for one head: the one-head
     kernels and the fused passes take that form)."""
@@ -644,6 +726,59 @@ def attention_edge_step(g, Q, K, V, xe, dO, p=0.0, seed=0, offset=0):
         w = a * _ops.edge_dropout_mask(g.row, g.ptr_r, g.eid_r, g.indices_r, h, p, seed, offset, a.dtype).reshape(a.shape)
     o = torch.zeros_like(q3).index_add(0, slot_row, w.index_select(0, g.eid_r).unsqueeze(-1) * vx).reshape(shape)
     o.backward(dO)
+    _lib.check_errors(sync=False)     # as in attention_step
+    return s, a, o
+
+
+def _backward_pairs(pairs):
+    """backward of the outputs whose gradient is given: pairs of (output, gradient or None)"""
+    outs = [(t, g) for t, g in pairs if g is not None]
+    if outs:
+        torch.autograd.backward([t for t, _ in outs], [g for _, g in outs])
+
+
+def fused_attention_weights_step(g, Q, K, V, dO, ga=None, b=None, xe=None, p=0.0, seed=0, offset=0):
+    """The fused step that also returns its attention weights, through FusedAttentionWeights: backward of
+    <o, dO> + <a, ga> (either gradient may be None; ga needs the plain or the bias mode); returns (o, a)."""
+    o, a = FusedAttentionWeights.apply(*g.csr_args(), Q, K, V, b, xe, p, seed, offset)
+    _backward_pairs(((o, dO), (a, ga)))
+    _lib.check_errors(sync=False)     # as in attention_step
+    return o, a
+
+
+def attention_weights_step(g, Q, K, V, dO, ga=None, b=None, xe=None, p=0.0, seed=0, offset=0):
+    """The composed yardstick of fused_attention_weights_step, for tests and timing only: the unfused ops (torch gathers
+    with xe, as attention_edge_step: (E, h, d) temporaries, the chunk list must name every slot), a from SparseSoftmax --
+    a second softmax with its own statistics -- and autograd through everything, the ga term included in every mode.
+    Same decisions for the same (p, seed, offset); returns (s, a, o) with s, a by edge id, a the undropped weights."""
+    args = g.csr_args()
+    h = 1 if Q.dim() == 2 else Q.size(1)
+    if xe is not None:
+        q3, k3, v3, xe3 = (x.reshape(x.size(0), h, x.size(-1)) for x in (Q, K, V, xe))
+        slot_row = torch.repeat_interleave(g.row, g.ptr_r[1:] - g.ptr_r[:-1])
+        xs = xe3.index_select(0, g.eid_r)
+        kx = k3.index_select(0, g.indices_r) + xs
+        vx = v3.index_select(0, g.indices_r) + xs
+        s_slot = (q3.index_select(0, slot_row) * kx).sum(-1)
+        s = torch.zeros_like(s_slot).index_copy(0, g.eid_r, s_slot)
+        if Q.dim() == 2:
+            s = s.reshape(-1)
+    else:
+        s = MaskedMMCSR.apply(*args, Q, K)
+        if b is not None:
+            s = s + b
+    a = SparseSoftmax.apply(g.row, g.ptr_r, g.eid_r, s)
+    w = a
+    if p > 0:
+        w = a * _ops.edge_dropout_mask(g.row, g.ptr_r, g.eid_r, g.indices_r, h, p, seed, offset, a.dtype).reshape(a.shape)
+    if xe is not None:
+        o = torch.zeros_like(q3).index_add(0, slot_row, w.reshape(-1, h).index_select(0, g.eid_r).unsqueeze(-1) * vx)
+        o = o.reshape(Q.shape)
+    else:
+        o = VectorSPMM.apply(*args, w, V)
+        if o.size(0) != Q.size(0):          # the unfused SpMM returns zeros_like(x) rows
+            o = o[:Q.size(0)]
+    _backward_pairs(((o, dO), (a, ga)))
     _lib.check_errors(sync=False)     # as in attention_step
     return s, a, o
 

@@ -30,6 +30,7 @@ __all__ = ["maskedmm_csr_forward", "maskedmm_csr_backward", "node_mul_edge_forwa
 # extra ops (not in the reference's module): the fused attention step, SURVEY.md 8f N2, and its form with attention
 # dropout (attention_dropout_forward / _backward) and with a per-edge score bias (attention_bias_forward /
 # _backward) and with edge features in key and value (attention_edge_forward / _backward),
+# the attention weights of all of these from the row statistics they return (attention_weights),
 # the GAT additive attention scores (LeakyReLU(el[i] + er[j]) per edge and head), the fused GAT attention layer and
 # its forms with attention dropout (plus the mask they apply, as an edge tensor, for the composed path), and the GATv2
 # scores (att . LeakyReLU(xl[i] + xr[j]) per edge and head), and the fused GAT layer with a per-edge score term
@@ -881,6 +882,53 @@ def attention_edge_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_
     return [dQ, dK, dV, dxe]
 
 
+# ---- the weights of the fused attention ops from their row statistics (extra op) ---------------------
+def _attn_weights_operands(fn, Q, K, stats, b, xe, n_edges):
+    """-> (h, d): the mode (at most one of b and xe), then Q, K and stats against each other, then b or xe against the
+    graph and Q in the words of the ops that take them"""
+    if b is not None and xe is not None:
+        raise RuntimeError("%s: at most one of b and xe may be given" % fn)
+    _same_dtype(Q, K, "Q", "K")
+    _same_dtype(Q, stats, "Q", "stats")
+    if Q.dim() not in (2, 3) or Q.shape[1:] != K.shape[1:]:
+        raise RuntimeError("%s: Q (n_q,[h,]d) and K (n_k,[h,]d) expected" % fn)
+    h = 1 if Q.dim() == 2 else Q.size(1)
+    if tuple(stats.shape) != (Q.size(0), h, 2):
+        raise RuntimeError("%s: stats must be (n_q, h, 2) = (%d, %d, 2), got %s"
+                           % (fn, Q.size(0), h, tuple(stats.shape)))
+    if b is not None:
+        _attn_bias(fn, b, Q, n_edges, h)
+    if xe is not None:
+        _attn_edge_rows(fn, xe, Q, n_edges)
+    return h, Q.size(-1)
+
+
+def attention_weights(row, indptr, eid, indices, Q, K, stats, b=None, xe=None):
+    """-> a, the attention weights of attention_forward / attention_dropout_forward (neither b nor xe),
+    attention_bias_forward (b) or attention_edge_forward (xe) from the stats (n_q, h, 2) = (m_i, 1 / l_i) that op
+    returned: for edge e = (i, j),  s_e = <Q_i, K_j> (+ b[e]) or <Q_i, K_j + xe[e]>,  a_e = exp(min(s_e - m_i, 0)) / l_i.
+    a is indexed by edge id, (n_edges) for 2-D Q / K, else (n_edges, h): the layout of sparse_softmax_forward's result
+    (PyG's return_attention_weights=True, DGL's get_attention=True).  These are the UNDROPPED weights; the effective
+    ones are a * edge_dropout_mask(...).  The clamp keeps a <= 1 whichever forward produced the statistics.  Edge ids
+    that no slot names read 0; giving b and xe together is an error.  One SDDMM plus one stream pass over a (plain,
+    bias) or one gather pass (xe): no second softmax, no workspace, nothing of size (n_edges, h, d)."""
+    fn = "attention_weights"
+    _check_csr((row, indptr, eid, indices), _CSR, (Q, "Q"), (K, "K"), (stats, "stats"),
+               *(((b, "b"),) if b is not None else ()))
+    e, n_q, n_k = eid.size(0), Q.size(0), K.size(0)
+    h, d = _attn_weights_operands(fn, Q, K, stats, b, xe, e)
+    with _lib.device_guard(Q.device):
+        plan = get_plan(row, indptr, eid, indices, n_k)
+        # a[e] is written once per row-major slot: only a chunk list that leaves slots out needs the zeros
+        shape = (e,) if Q.dim() == 2 else (e, h)
+        a = (torch.empty if plan.info.full_coverage else torch.zeros)(shape, dtype=Q.dtype, device=Q.device)
+        check(lib().graphop_attention_weights(
+            dtype_code(Q), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(Q), ptr(K), ptr(stats),
+            ptr(b) if b is not None else _NULL, ptr(xe) if xe is not None else _NULL, ptr(a), row.size(0), e, n_q, n_k,
+            h, d, plan.handle, stream_of(Q)))
+    return a
+
+
 # ---- fused GAT attention with an edge term (extra ops) -----------------------------------------------------------
 def _gat_edge_term(el, ee, n_edges, h, fn):
     """ee checked against the graph and the heads: (n_edges) for 1-D el / er, else (n_edges, h), in el's dtype."""
@@ -955,11 +1003,11 @@ _SCHEMAS = {
 }
 # every op beyond the reference's eight, plus the one query that is not an op
 # ... and the dropout form of the fused attention step and its forms with a per-edge score bias and with edge features
-# (attention_edge_*): bound here and in the compiled extension, not registered under torch.ops.graphop (the registered set is the table above)
+# (attention_edge_*) and the weights of all of them (attention_weights): bound here and in the compiled extension, not registered under torch.ops.graphop (the registered set is the table above)
 EXTRA_OPS = [n for n in _SCHEMAS if n not in __all__] + ["attention_backward_is_fused", "attention_dropout_forward",
                                                          "attention_dropout_backward", "attention_bias_forward",
                                                          "attention_bias_backward", "attention_edge_forward",
-                                                         "attention_edge_backward"]
+                                                         "attention_edge_backward", "attention_weights"]
 _torch_lib = None
 
 

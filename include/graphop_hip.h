@@ -816,6 +816,36 @@ GRAPHOP_API int graphop_attention_edge_backward(int dtype, const int64_t* row, c
                                     int64_t workspace_bytes, const graphop_plan_t* plan_r, const graphop_plan_t* plan_c,
                                     void* stream, double p, uint64_t seed, uint32_t offset, int64_t head0);
 
+/* ---- attention weights of the fused dot-product attention ops (not in the reference) --------------
+ * The weights the layer used, as an edge tensor (PyG's return_attention_weights=True, DGL's get_attention=True), from
+ * the row statistics stats (n_q, h, 2) = (m_i, linv_i) that graphop_attention_forward / _dropout_forward /
+ * _bias_forward / _edge_forward left.  Edge e = (i, j), head k; i indexes Q and stats, j indexes K; b, xe and a are
+ * indexed by EDGE ID.  Three modes, chosen by which optional operand is given:
+ *   plain:  s_e = <Q_i, K_j>                  b == NULL and xe == NULL
+ *   bias :  s_e = <Q_i, K_j> + b[e]           b  (n_edges, h)
+ *   edge :  s_e = <Q_i, K_j + xe[e]>          xe (n_edges, h, d); K_j + xe[e] formed once, as in attention_edge_forward
+ *   a_e = exp(min(s_e - m_i, 0)) * linv_i     a  (n_edges, h), the edge layout of sparse_softmax / vector_spmm
+ * a holds the UNDROPPED weights (the effective ones are a * graphop_edge_dropout_mask).  The min(..., 0) is deliberate:
+ * the statistics may come from a kernel that summed the score in another order (the walk forward, the several-head
+ * forward, a generic one), and the clamp keeps a_e <= linv_i <= 1 whichever forward made them.  b and xe together are an
+ * error: no forward produces such statistics.  Rows without edges own no slot, so nothing is written for them.  a[e] is
+ * written once for every edge id a row-major slot names; other entries are left untouched (zero-fill a first where the
+ * chunk list may leave slots out).  No atomics and no workspace in any mode: the result is reproducible bit for bit.
+ * Checks, all before anything touches a device, in this order: dtype and sizes; b and xe both given; stats or a NULL
+ * (unless the problem is empty); a matching plan must bound the ids by n_q / n_k (an error, not a fall-back).  Empty
+ * problems (n_chunks, n_edges, n_q, n_k or h * d zero) return OK and dereference nothing.
+ * Forms: plain and bias are composed inside the library -- graphop_maskedmm_csr_forward (with a plan that covers every
+ * edge id; else its _partial form, which fills nothing) writes s into a with the SDDMM driver its own dispatch picks, and
+ * k_attn_weights_norm normalises a in place: one stream pass over (n_edges, h), any dtype, h, d, plan or chunk order.
+ * Edge mode gathers: k_attn_weights_xe_f32 for fp32 calls whose (h, d) is one of (1,64) (2,32) (2,64) (4,16) (4,32)
+ * (4,64) (8,8) (8,16) (8,32) with a matching plan, 16-byte aligned Q, K, stats, xe, a and ids below 2^31;
+ * k_attn_weights_xe_generic (one wave per chunk) for everything else (fp64, other shapes, no plan, misaligned operands,
+ * GRAPHOP_FORCE_GENERIC). */
+GRAPHOP_API int graphop_attention_weights(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                              const int64_t* indices, const void* Q, const void* K, const void* stats, const void* b,
+                              const void* xe, void* a, int64_t n_chunks, int64_t n_edges, int64_t n_q, int64_t n_k,
+                              int64_t h, int64_t d, const graphop_plan_t* plan, void* stream);
+
 /* ---- halo pack / unpack of the node-range sharded step (not in the reference: single GPU) --------
  * gather_rows:      dst[i, :] = src[idx[i], :]          (send buffer of the rows peers gather from)
  * scatter_add_rows: dst[idx[i], :] += src[i, :]         (partial gradient rows coming home; idx may
