@@ -1,9 +1,11 @@
 // The several-head chunk-driver passes of the fused dot-product attention ops, with a per-edge score bias or with an edge
-// row added to K and V.  Included twice, inside namespace graphop (after kernels_attn_rows.h):
+// row added to K and V.  Included three times, inside namespace graphop (after kernels_attn_rows.h):
 //   kernels_attn_heads.h  AR_EDGE 0  s = <Q_i, K_j> (+ b[e, k], `bool BIAS`)       k_attn_heads_*, AttnHeads*, attn_heads_*
 //   kernels_attn_edge.h   AR_EDGE 1  s = <Q_i, K_j + xe[e]>, V_j + xe[e] for V_j   k_attn_edge_*,  AttnEdge*,  attn_edge_*
+//   kernels_attn_etype.h  AR_EDGE 2  the same with xe[e] := R[etype[e]]            k_attn_etype_*, AttnEtype*, attn_etype_*
 // The includer defines AR_EDGE, AR_KERNEL(pass), AR_TYPE(Name) and AR_FN(name), and undefines them afterwards.
-// AR_IF_BIAS(...) is its arguments in the first inclusion and nothing in the second, AR_IF_EDGE(...) the converse; the
+// AR_IF_BIAS(...) is its arguments in the first inclusion and nothing in the others, AR_IF_EDGE(...) the converse;
+// AR_IF_XE(...) stands in the second alone, AR_IF_TABLE(...) in the third alone, AR_IF_NO_TABLE(...) in the first two; the
 // spots of several lines stand under `#if AR_EDGE`.  What differs: the trailing `bool BIAS` of the template lists (the
 // edge kernels keep <H, D, DROP> and <H, D, COL, OWNED, DROP>), b / db against xe / dxe in the parameters, the load of a
 // slot's edge id (under BIAS, or always), the slots' h bias values against their edge row offsets, where the term enters
@@ -19,12 +21,30 @@
 // xe[e * F4 + p] is one float4 per (lane, slot, piece), read once with a non-temporal load and added into the K and V
 // pieces where they are consumed: kx = K_j + xe[e], vx = V_j + xe[e], each formed once per piece, in this order.
 // A NULL eid means eid[slot] == slot (a plan with eid_identity): a kernel-uniform branch.
+// With the type table (DESIGN.md 4.5o) the slot's edge row is R[t * F4 + p], t = min(etype[e], tmax) as unsigned values:
+// the lane that holds the slot's ids loads the type behind the edge id and from there on carries it where the second
+// inclusion carries the edge id, and the piece is an ordinary cached load (the table is 4 T F bytes).  The row pass sums
+// dR in a workgroup-wide LDS table tab[t][component][piece] -- a lane group's 16 lanes add into 16 adjacent words -- and
+// at its end adds the table's nonzero words into the replica of dR that blockIdx.x % nrep names.  Its groups past the
+// last chunk walk no chunk instead of leaving, so that every thread meets the barriers.
 #if AR_EDGE
 #define AR_IF_EDGE(...) __VA_ARGS__
 #define AR_IF_BIAS(...)
 #else
 #define AR_IF_EDGE(...)
 #define AR_IF_BIAS(...) __VA_ARGS__
+#endif
+#if AR_EDGE == 1
+#define AR_IF_XE(...) __VA_ARGS__
+#else
+#define AR_IF_XE(...)
+#endif
+#if AR_EDGE == 2
+#define AR_IF_TABLE(...) __VA_ARGS__
+#define AR_IF_NO_TABLE(...)
+#else
+#define AR_IF_TABLE(...)
+#define AR_IF_NO_TABLE(...) __VA_ARGS__
 #endif
 
 // the dropout decision of the call's heads: global head of local head k is head0 + k
@@ -61,7 +81,8 @@ struct AR_TYPE(FwdArgs) {
   const float* K;       // [n_k][H][D]   gathered
   const float* V;       // [n_k][H][D]   gathered
   AR_IF_BIAS(const float* b;)    // [n_edges][H]     by edge id (BIAS)
-  AR_IF_EDGE(const float* xe;)   // [n_edges][H][D]  by edge id, streamed
+  AR_IF_XE(const float* xe;)     // [n_edges][H][D]  by edge id, streamed
+  AR_IF_TABLE(const float* R; const int* etype; unsigned tmax;)   // [tmax + 1][H][D]; [n_edges] by edge id
   float* o;             // [n_q][H][D]   zero-filled by the caller (pieces are added)
   float* stats;         // [n_q][H][2]   (m, 1 / l); rows without slots keep the caller's fill: (0, 0) of the ops with a
                         //               bias, (-1e9, 0) of the op with an edge term
@@ -143,6 +164,7 @@ __global__ __launch_bounds__(kFastBlock) void AR_KERNEL(fwd_rows_f32)(
       const int my_src = (int)indices[j];
       int my_e = 0;
       AR_IF_BIAS(if constexpr (BIAS)) my_e = eid ? (int)eid[j] : (int)j;   // kernel-uniform branch
+      AR_IF_TABLE(my_e = (int)min((unsigned)a.etype[my_e], a.tmax);)       // from here on the slot's type, clamped
       float4 x0[SB][NV], x1[SB][NV];
       AR_IF_BIAS(float bb[BIAS ? SB : 1][NV];)
       AR_IF_EDGE(i64 eo[SB];)   // the slots' edge rows: e * F4 is 64-bit
@@ -181,7 +203,7 @@ __global__ __launch_bounds__(kFastBlock) void AR_KERNEL(fwd_rows_f32)(
         for (int u = 0; u < SB; ++u) {
 #if AR_EDGE
           // the edge piece goes into the gathered pieces here: kx in place of K_j, vx in place of V_j
-          const float4 xe4 = ld4_nt(a.xe, eo[u] + v * L + l);
+          const float4 xe4 = AR_IF_XE(ld4_nt(a.xe, eo[u] + v * L + l)) AR_IF_TABLE(ld4(a.R, eo[u] + v * L + l));
           x0[u][v] = attn_rows_add4(x0[u][v], xe4);
           x1[u][v] = attn_rows_add4(x1[u][v], xe4);
 #endif
@@ -309,18 +331,25 @@ template <int H, int D, bool COL, bool OWNED, bool DROP AR_IF_BIAS(, bool BIAS)>
 __global__ __launch_bounds__(kFastBlock) void AR_KERNEL(bwd_rows_f32)(
     const i64* __restrict__ row, const i64* __restrict__ indptr, const i64* __restrict__ eid,
     const i64* __restrict__ indices, const float* __restrict__ OWN, const float* __restrict__ XT,
-    const float4* __restrict__ stats4, const float* __restrict__ AR_IF_BIAS(b) AR_IF_EDGE(xe), float* __restrict__ out0,
-    float* __restrict__ out1, float* __restrict__ AR_IF_BIAS(db) AR_IF_EDGE(dxe), i64 n_chunks, int chunks_per_group,
-    AR_TYPE(DropIf)<DROP> dr) {
+    const float4* __restrict__ stats4, const float* __restrict__ AR_IF_BIAS(b) AR_IF_XE(xe) AR_IF_TABLE(R),
+    AR_IF_TABLE(const int* __restrict__ etype, unsigned tmax, int nrep,) float* __restrict__ out0,
+    float* __restrict__ out1, float* __restrict__ AR_IF_BIAS(db) AR_IF_XE(dxe) AR_IF_TABLE(dR), i64 n_chunks,
+    int chunks_per_group, AR_TYPE(DropIf)<DROP> dr) {
   using C = AttnRowsCfg<H, D>;
   constexpr int L = C::L, NV = C::NV, DQ = C::DQ, SB = C::SB;
   constexpr i64 F4 = C::F4;
   const int l = threadIdx.x % L;
   const i64 gid = (i64)blockIdx.x * (kFastBlock / L) + threadIdx.x / L;
-  const i64 c0 = gid * chunks_per_group;
+  const i64 c0 = AR_IF_NO_TABLE(gid * chunks_per_group) AR_IF_TABLE(min(gid * chunks_per_group, n_chunks));
   i64 c1 = c0 + chunks_per_group;
   if (c1 > n_chunks) c1 = n_chunks;
-  if (c0 >= c1) return;
+  AR_IF_NO_TABLE(if (c0 >= c1) return;)
+#if AR_EDGE == 2
+  extern __shared__ float tab[];   // [tmax + 1][4][F4], row pass with dR alone (the launch gives it no byte otherwise)
+  const int n_tab = COL || dR == nullptr ? 0 : (int)(tmax + 1) * (int)(4 * F4);   // kernel-uniform
+  for (int i = threadIdx.x; i < n_tab; i += kFastBlock) tab[i] = 0.f;
+  if (n_tab) __syncthreads();
+#endif
   i64 row_before = -1, row_after = -1;
   if constexpr (OWNED) {
     if (c0 > 0) row_before = row[c0 - 1];
@@ -374,6 +403,7 @@ __global__ __launch_bounds__(kFastBlock) void AR_KERNEL(bwd_rows_f32)(
       const int my_src = (int)indices[j];
       int my_e = 0;
       AR_IF_BIAS(if constexpr (BIAS)) my_e = eid ? (int)eid[j] : (int)j;   // kernel-uniform branch
+      AR_IF_TABLE(my_e = (int)min((unsigned)etype[my_e], tmax);)           // from here on the slot's type, clamped
       float4 x0[SB][NV], x1[SB][NV];
       float4 stg[COL ? SB : 1][NV];   // COL: the gathered row's statistics
       AR_IF_BIAS(float bb[BIAS ? SB : 1][NV]; int ed[BIAS ? SB : 1];)
@@ -414,7 +444,7 @@ __global__ __launch_bounds__(kFastBlock) void AR_KERNEL(bwd_rows_f32)(
 #pragma unroll
         for (int v = 0; v < NV; ++v) {
 #if AR_EDGE
-          const float4 xe4 = ld4_nt(xe, eo[u] + v * L + l);
+          const float4 xe4 = AR_IF_XE(ld4_nt(xe, eo[u] + v * L + l)) AR_IF_TABLE(ld4(R, eo[u] + v * L + l));
           float4 kx, vx;   // K_j + xe[e], V_j + xe[e]: of the gathered row in the row pass, of the own row in the column pass
           float s, da;
           if constexpr (COL) {
@@ -455,10 +485,15 @@ __global__ __launch_bounds__(kFastBlock) void AR_KERNEL(bwd_rows_f32)(
 #endif
             attn_rows_fma4(acc0[v], ds, AR_IF_BIAS(x0[u][v]) AR_IF_EDGE(kx));   // dQ += ds K_j, or ds kx
 #if AR_EDGE
-            if (dxe != nullptr && u < nb) {   // one plain float4 per lane and real slot
+            // dxe: one plain float4 per lane and real slot; dR: four LDS adds, lane groups may meet in a type
+            if (AR_IF_XE(dxe) AR_IF_TABLE(dR) != nullptr && u < nb) {
               float4 g = make_float4(ds * y0[v].x, ds * y0[v].y, ds * y0[v].z, ds * y0[v].w);
               attn_rows_fma4(g, av, y1[v]);
-              reinterpret_cast<float4*>(dxe)[eo[u] + v * L + l] = g;
+              AR_IF_XE(reinterpret_cast<float4*>(dxe)[eo[u] + v * L + l] = g;)
+#if AR_EDGE == 2
+              float* tp = tab + eo[u] * 4 + v * L + l;
+              atomicAdd(tp, g.x); atomicAdd(tp + F4, g.y); atomicAdd(tp + 2 * F4, g.z); atomicAdd(tp + 3 * F4, g.w);
+#endif
             }
 #endif
           }
@@ -467,7 +502,21 @@ __global__ __launch_bounds__(kFastBlock) void AR_KERNEL(bwd_rows_f32)(
     }
   }
   if (dirty) flush(cur_row);
+#if AR_EDGE == 2
+  if (n_tab) {   // element i = (t, piece, component) of dR from word (t, component, piece) of the table
+    __syncthreads();
+    float* rep = dR + (i64)(blockIdx.x % nrep) * n_tab;
+    for (int i = threadIdx.x; i < n_tab; i += kFastBlock) {
+      const int f = i % (int)(4 * F4);
+      const float g = tab[i - f + (f % 4) * (int)F4 + f / 4];
+      if (g != 0.f) atomicAdd(rep + i, g);   // a type this workgroup met in no slot adds nothing
+    }
+  }
+#endif
 }
 
 #undef AR_IF_EDGE
 #undef AR_IF_BIAS
+#undef AR_IF_XE
+#undef AR_IF_TABLE
+#undef AR_IF_NO_TABLE

@@ -629,6 +629,95 @@ std::vector<at::Tensor> attention_edge_backward(const at::Tensor& row, const at:
   return {dQ, dK, dV, dxe};
 }
 
+// ---- edge-type embeddings of the fused attention step (include/graphop_hip.h: graphop_attention_etype_*) ---------------
+// R: a contiguous device tensor (n_types, d) for 2-D Q / K / V, else (n_types, h, d), in Q's dtype, n_types >= 1 unless
+// the graph has no edge; etype: a contiguous device int32 tensor (n_edges).  The values of etype are not looked at (that
+// would synchronise): the kernels clamp them.
+void check_attn_etype_table(const char* fn, const at::Tensor& R, const at::Tensor& etype, const at::Tensor& Q, int64_t e) {
+  CHECK_SAME_DTYPE(Q, R);
+  TORCH_CHECK(R.dim() == Q.dim() && R.sizes().slice(1) == Q.sizes().slice(1),
+              fn, ": R must be (n_types, d) for 2-D Q / K / V, else (n_types, h, d), got R ", R.sizes(), ", Q ", Q.sizes());
+  TORCH_CHECK(R.size(0) > 0 || e == 0, fn, ": R must hold at least one type (n_edges = ", e, ")");
+  TORCH_CHECK(etype.scalar_type() == at::kInt, fn, ": etype must be torch.int32, got ", etype.scalar_type());
+  TORCH_CHECK(etype.dim() == 1 && etype.size(0) == e,
+              fn, ": etype must be (n_edges) with n_edges = ", e, ", got ", etype.sizes());
+  CHECK_CONTIGUOUS(R); CHECK_CUDA(R);
+  CHECK_CONTIGUOUS(etype); CHECK_CUDA(etype);
+}
+
+std::vector<at::Tensor> attention_etype_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
+                                                const at::Tensor& indices, const at::Tensor& Q, const at::Tensor& K,
+                                                const at::Tensor& V, const at::Tensor& R, const at::Tensor& etype,
+                                                double p, int64_t seed, int64_t offset, int64_t head0) {
+  const char* fn = "attention_etype_forward";
+  const DropSpec drop = drop_spec(fn, p, seed, offset);
+  head0_checked(fn, head0);
+  CHECK_CSR(row, indptr, eid, indices);
+  CHECK_INPUT(Q); CHECK_INPUT(K); CHECK_INPUT(V);
+  TORCH_CHECK(K.sizes() == V.sizes() && Q.sizes().slice(1) == K.sizes().slice(1),
+              fn, ": Q (n_q,[h,]d), K and V (n_k,[h,]d) expected");
+  CHECK_SAME_DTYPE(Q, K); CHECK_SAME_DTYPE(Q, V);
+  const int64_t e = eid.size(0), d = Q.size(-1), h = Q.dim() == 2 ? 1 : Q.size(1), n_q = Q.size(0), n_k = K.size(0);
+  check_attn_etype_table(fn, R, etype, Q, e);
+  const int64_t n_types = R.size(0);
+  DeviceGuard dg(Q);
+  auto o = at::empty_like(Q);
+  auto stats = at::empty({n_q, h, 2}, Q.options());
+  const auto pp = get_plan(row, indptr, eid, indices, n_k);
+  const auto& pl = *pp;
+  int64_t nbytes = 0;
+  check(graphop_attention_etype_workspace_bytes(dtype_code(Q), 0, e, n_q, n_k, h, d, n_types, pl.plan, nullptr,
+                                                stream_of(Q), &nbytes));
+  auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, Q.options().dtype(at::kByte));
+  check(graphop_attention_etype_forward(dtype_code(Q), ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(V),
+                                        vp(R), etype.data_ptr<int32_t>(), vp(o), vp(stats), row.size(0), e, n_q, n_k, h,
+                                        d, n_types, ws.data_ptr(), nbytes, pl.plan, stream_of(Q), drop.p, drop.seed,
+                                        drop.offset, head0));
+  return {o, stats};
+}
+
+std::vector<at::Tensor> attention_etype_backward(const at::Tensor& row, const at::Tensor& indptr_r,
+                                                 const at::Tensor& eid_r, const at::Tensor& indices_r,
+                                                 const at::Tensor& col, const at::Tensor& indptr_c,
+                                                 const at::Tensor& eid_c, const at::Tensor& indices_c, const at::Tensor& Q,
+                                                 const at::Tensor& K, const at::Tensor& V, const at::Tensor& R,
+                                                 const at::Tensor& etype, const at::Tensor& o, const at::Tensor& stats,
+                                                 const at::Tensor& dO_, double p, int64_t seed, int64_t offset,
+                                                 int64_t head0, bool need_dR) {
+  const char* fn = "attention_etype_backward";
+  const DropSpec drop = drop_spec(fn, p, seed, offset);
+  head0_checked(fn, head0);
+  CHECK_CSR(row, indptr_r, eid_r, indices_r);
+  CHECK_CSR(col, indptr_c, eid_c, indices_c);
+  CHECK_INPUT(Q); CHECK_INPUT(K); CHECK_INPUT(V); CHECK_INPUT(o); CHECK_INPUT(stats);
+  CHECK_CUDA(dO_);
+  const at::Tensor dO = dO_.contiguous();
+  CHECK_SAME_DTYPE(Q, K); CHECK_SAME_DTYPE(Q, V); CHECK_SAME_DTYPE(Q, o); CHECK_SAME_DTYPE(Q, stats); CHECK_SAME_DTYPE(Q, dO);
+  TORCH_CHECK(K.sizes() == V.sizes() && Q.sizes().slice(1) == K.sizes().slice(1),
+              fn, ": Q (n_q,[h,]d), K and V (n_k,[h,]d) expected");
+  const int64_t e = eid_r.size(0), d = Q.size(-1), h = Q.dim() == 2 ? 1 : Q.size(1), n_q = Q.size(0), n_k = K.size(0);
+  TORCH_CHECK(o.sizes() == Q.sizes() && dO.sizes() == Q.sizes() && stats.numel() == n_q * h * 2,
+              fn, ": o, dO must match Q and stats must be (n_q, h, 2)");
+  check_attn_etype_table(fn, R, etype, Q, e);
+  const int64_t n_types = R.size(0);
+  DeviceGuard dg(Q);
+  auto dQ = at::empty_like(Q), dK = at::empty_like(K), dV = at::empty_like(V);
+  const auto ppr = get_plan(row, indptr_r, eid_r, indices_r, n_k);
+  const auto ppc = get_plan(col, indptr_c, eid_c, indices_c, n_q);
+  const auto &pr = *ppr, &pc = *ppc;
+  int64_t nbytes = 0;
+  check(graphop_attention_etype_workspace_bytes(dtype_code(Q), 1, e, n_q, n_k, h, d, n_types, pr.plan, pc.plan,
+                                                stream_of(Q), &nbytes));
+  auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, Q.options().dtype(at::kByte));
+  auto dR = need_dR ? at::empty_like(R) : at::empty({0}, R.options());   // the call fills it
+  check(graphop_attention_etype_backward(
+      dtype_code(Q), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c), ip(indices_c),
+      vp(Q), vp(K), vp(V), vp(R), etype.data_ptr<int32_t>(), vp(o), vp(stats), vp(dO), vp(dQ), vp(dK), vp(dV),
+      need_dR ? vp(dR) : nullptr, row.size(0), col.size(0), e, n_q, n_k, h, d, n_types, ws.data_ptr(), nbytes, pr.plan,
+      pc.plan, stream_of(Q), drop.p, drop.seed, drop.offset, head0));
+  return {dQ, dK, dV, dR};
+}
+
 // ---- the weights of the fused attention ops from their row statistics (include/graphop_hip.h: graphop_attention_weights)
 at::Tensor attention_weights(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
                              const at::Tensor& indices, const at::Tensor& Q, const at::Tensor& K, const at::Tensor& stats,
@@ -1185,6 +1274,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("indices_c"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("xe"), py::arg("o"), py::arg("stats"),
         py::arg("dO"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0, py::arg("head0") = 0,
         py::arg("need_dxe") = true);
+  // (likewise its form with edge-type embeddings: K_j + R[etype[e]], V_j + R[etype[e]])
+  m.def("attention_etype_forward", &attention_etype_forward,
+        "Fused attention forward with edge-type embeddings in key and value (extra op)", py::arg("row"),
+        py::arg("indptr"), py::arg("eid"), py::arg("indices"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("R"),
+        py::arg("etype"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0, py::arg("head0") = 0);
+  m.def("attention_etype_backward", &attention_etype_backward,
+        "Fused attention backward with edge-type embeddings in key and value (extra op)", py::arg("row"),
+        py::arg("indptr_r"), py::arg("eid_r"), py::arg("indices_r"), py::arg("col"), py::arg("indptr_c"),
+        py::arg("eid_c"), py::arg("indices_c"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("R"), py::arg("etype"),
+        py::arg("o"), py::arg("stats"), py::arg("dO"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0,
+        py::arg("head0") = 0, py::arg("need_dR") = true);
   // (and the weights of all of these from their row statistics)
   m.def("attention_weights", &attention_weights,
         "Attention weights of the fused attention ops from their row statistics (extra op)", py::arg("row"),

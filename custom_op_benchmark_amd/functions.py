@@ -452,7 +452,9 @@ class FusedAttentionEdge(Function):
     the CSR arrays, (Q, K, V, xe, o, row statistics) and nothing else; the backward makes dxe = ds Q_i + a m dO_i, the only
     edge-sized tensor, and only where xe needs a gradient.  m_e is FusedAttentionDropout's multiplier (1 at p = 0: no
     dropout); seed=None draws one from torch's default CPU generator.  There is no 1 / sqrt(d) scale argument: fold it
-    into Q.  One call whatever h: there are no head groups."""
+    into Q.  One call whatever h: there are no head groups.  For a CATEGORICAL edge feature (xe = R[etype]: relations,
+    bond types, clipped relative positions) use FusedAttentionEdgeType, which takes the table and the types and makes
+    neither xe nor dxe."""
 
     @staticmethod
     def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, xe, p=0.0, seed=None,
@@ -471,6 +473,39 @@ class FusedAttentionEdge(Function):
         need_dxe = ctx.needs_input_grad[11]
         dQ, dK, dV, dxe = _ops.attention_edge_backward(*a8, Q, K, V, xe, o, stats, dO, *ctx.drop, 0, need_dxe)
         return (None,) * 8 + (dQ, dK, dV, dxe if need_dxe else None, None, None, None)
+
+
+class FusedAttentionEdgeType(Function):
+    """FusedAttentionEdge for a categorical edge feature (extra op): edge e = (i, j) carries the type
+    t = etype[e] and the row R[t] of a learned table is added to its key AND its value,  kx = K[j] + R[t],
+    vx = V[j] + R[t],  s_e = <Q_i, kx_e>,  o[i] = sum_e softmax_e(s) m_e vx_e:
+    apply(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, R, etype, p=0.0, seed=None, offset=0).
+    etype is (E) torch.int32 by edge id with values in [0, n_types); R is (n_types, d) with 2-D Q / K / V, (n_types, h, d)
+    with 3-D ones, in their dtype, contiguous: an nn.Embedding's weight (relation-aware attention, Shaw-type relative
+    positions, TransformerConv(edge_dim=...) behind an embedding).  It is FusedAttentionEdge on R[etype.long()] without
+    that (E, h, d) tensor and without its gradient: R.grad[t] = sum over the edges of type t of (ds Q_i + a m dO_i) is
+    summed on chip, and only where R needs a gradient.  Saves the CSR arrays, (Q, K, V, R, etype, o, row statistics) and
+    nothing else; etype gets no gradient.  Types outside [0, n_types) are not detected (that would synchronise): the
+    kernels clamp them, so they give undefined values and touch no memory outside R / R.grad.  m_e, seed=None and the
+    missing 1 / sqrt(d) argument: as FusedAttentionEdge.  One call whatever h."""
+
+    @staticmethod
+    def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, R, etype, p=0.0,
+                seed=None, offset=0):
+        a8 = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
+        if seed is None:
+            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item()) if float(p) > 0.0 else 0
+        ctx.drop = (float(p), int(seed), int(offset))
+        o, stats = _ops.attention_etype_forward(row, indptr_r, eid_r, indices_r, Q, K, V, R, etype, *ctx.drop, 0)
+        ctx.save_for_backward(*a8, Q, K, V, R, etype, o, stats)
+        return o
+
+    @staticmethod
+    def backward(ctx, dO):
+        a8, (Q, K, V, R, etype, o, stats) = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
+        need_dR = ctx.needs_input_grad[11]
+        dQ, dK, dV, dR = _ops.attention_etype_backward(*a8, Q, K, V, R, etype, o, stats, dO, *ctx.drop, 0, need_dR)
+        return (None,) * 8 + (dQ, dK, dV, dR if need_dR else None, None, None, None, None)
 
 
 class FusedAttentionWeights(Function):
@@ -728,6 +763,22 @@ def attention_edge_step(g, Q, K, V, xe, dO, p=0.0, seed=0, offset=0):
     o.backward(dO)
     _lib.check_errors(sync=False)     # as in attention_step
     return s, a, o
+
+
+def fused_attention_etype_step(g, Q, K, V, R, etype, dO, p=0.0, seed=0, offset=0):
+    """fused_attention_edge_step for a categorical edge feature, through FusedAttentionEdgeType: the table R and the
+    int32 types etype (by edge id) stand where xe = R[etype] would; returns o (nothing of size (E, h, d) exists, and
+    R.grad where R requires it has R's shape)."""
+    o = FusedAttentionEdgeType.apply(*g.csr_args(), Q, K, V, R, etype, p, seed, offset)
+    o.backward(dO)
+    _lib.check_errors(sync=False)     # as in attention_step
+    return o
+
+
+def attention_etype_step(g, Q, K, V, R, etype, dO, p=0.0, seed=0, offset=0):
+    """The composed yardstick of fused_attention_etype_step, for tests and timing only: attention_edge_step on the
+    materialised R[etype.long()] under autograd, which index_adds the (E, h, d) gradient back into R.grad."""
+    return attention_edge_step(g, Q, K, V, R.index_select(0, etype.long()), dO, p, seed, offset)
 
 
 def _backward_pairs(pairs):

@@ -31,6 +31,7 @@ __all__ = ["maskedmm_csr_forward", "maskedmm_csr_backward", "node_mul_edge_forwa
 # dropout (attention_dropout_forward / _backward) and with a per-edge score bias (attention_bias_forward /
 # _backward) and with edge features in key and value (attention_edge_forward / _backward),
 # the attention weights of all of these from the row statistics they return (attention_weights),
+# the edge-feature form for a categorical feature: a table and an int32 type per edge (attention_etype_*),
 # the GAT additive attention scores (LeakyReLU(el[i] + er[j]) per edge and head), the fused GAT attention layer and
 # its forms with attention dropout (plus the mask they apply, as an edge tensor, for the composed path), and the GATv2
 # scores (att . LeakyReLU(xl[i] + xr[j]) per edge and head), and the fused GAT layer with a per-edge score term
@@ -882,6 +883,112 @@ def attention_edge_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_
     return [dQ, dK, dV, dxe]
 
 
+# ---- edge-type embeddings of the fused attention step: K_j + R[t_e], V_j + R[t_e] (extra ops) --------
+def _attn_etype_table(fn, R, etype, Q, n_edges):
+    """R and etype checked against the graph and Q: R a contiguous device tensor (n_types, d) for 2-D Q / K / V, else
+    (n_types, h, d), in Q's dtype, with n_types >= 1 unless the graph has no edge; etype a contiguous device int32
+    tensor (n_edges).  The C ABI takes raw pointers: each of these would read out of bounds or garbage.  The VALUES of
+    etype are not looked at (that would synchronise): the kernels clamp them."""
+    _same_dtype(Q, R, "Q", "R")
+    if R.dim() != Q.dim() or tuple(R.shape[1:]) != tuple(Q.shape[1:]):
+        raise RuntimeError("%s: R must be (n_types, d) for 2-D Q / K / V, else (n_types, h, d), got R %s, Q %s"
+                           % (fn, tuple(R.shape), tuple(Q.shape)))
+    if R.size(0) == 0 and n_edges > 0:
+        raise RuntimeError("%s: R must hold at least one type (n_edges = %d)" % (fn, n_edges))
+    if etype.dtype != torch.int32:
+        raise RuntimeError("%s: etype must be torch.int32, got %s" % (fn, etype.dtype))
+    if tuple(etype.shape) != (n_edges,):
+        raise RuntimeError("%s: etype must be (n_edges) with n_edges = %d, got %s" % (fn, n_edges, tuple(etype.shape)))
+    for t, n in ((R, "R"), (etype, "etype")):
+        if not t.is_contiguous():
+            raise RuntimeError("%s must be contiguous" % n)
+        if not t.is_cuda:
+            raise RuntimeError("%s must be a CUDA tensor" % n)
+
+
+def _attn_etype_workspace(like, backward, e, n_q, n_k, h, d, n_types, plan_r, plan_c):
+    import ctypes
+    nbytes = ctypes.c_int64(0)
+    check(lib().graphop_attention_etype_workspace_bytes(
+        dtype_code(like), 1 if backward else 0, e, n_q, n_k, h, d, n_types, plan_r.handle,
+        plan_c.handle if plan_c is not None else _NULL, stream_of(like), ctypes.byref(nbytes)))
+    return torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=like.device), nbytes.value
+
+
+def attention_etype_forward(row, indptr, eid, indices, Q, K, V, R, etype, p=0.0, seed=0, offset=0, head0=0):
+    """-> [o, stats] of attention_edge_forward for a categorical edge feature: edge e = (i, j) carries the type
+    t = etype[e] and the table row R[t] is added to its key AND its value,  kx = K[j] + R[t],  vx = V[j] + R[t],
+    s_e = <Q_i, kx_e>,  a = row-softmax(s),  o[i] = sum_e a_e m_e vx_e  (relation-aware attention, Shaw-type relative
+    positions, TransformerConv(edge_dim=...) behind an nn.Embedding).  etype is (n_edges) torch.int32, contiguous,
+    indexed by edge id, with values in [0, n_types); R is (n_types, d) for 2-D Q / K / V, else (n_types, h, d), in their
+    dtype and contiguous.  Nothing of size (n_edges, h, d) is made or read: this is attention_edge_forward on
+    R[etype.long()] without that tensor.  Parallel edges share a dropout decision and may differ in type.
+    Out-of-range types: etype is not scanned (a scan would synchronise the stream and break its capture); every kernel
+    clamps a type into [0, n_types - 1] before it forms an address, so a type outside [0, n_types) gives an undefined
+    value and never touches memory outside R.  stats, (p, seed, offset, head0), the missing 1 / sqrt(d) and bias
+    arguments: as attention_edge_forward."""
+    fn = "attention_etype_forward"
+    drop = _drop_args(fn, p, seed, offset) + (_head0(fn, head0),)
+    _check_csr((row, indptr, eid, indices), _CSR, (Q, "Q"), (K, "K"), (V, "V"))
+    _same_dtype(Q, K, "Q", "K")
+    _same_dtype(Q, V, "Q", "V")
+    if K.shape != V.shape or Q.shape[1:] != K.shape[1:]:
+        raise RuntimeError("%s: Q (n_q,[h,]d), K and V (n_k,[h,]d) expected" % fn)
+    e, d = eid.size(0), Q.size(-1)
+    h = 1 if Q.dim() == 2 else Q.size(1)
+    n_q, n_k = Q.size(0), K.size(0)
+    _attn_etype_table(fn, R, etype, Q, e)
+    n_types = R.size(0)
+    o = torch.empty_like(Q)
+    stats = torch.empty((n_q, h, 2), dtype=Q.dtype, device=Q.device)
+    with _lib.device_guard(Q.device):
+        plan = get_plan(row, indptr, eid, indices, n_k)
+        ws, nbytes = _attn_etype_workspace(Q, False, e, n_q, n_k, h, d, n_types, plan, None)
+        check(lib().graphop_attention_etype_forward(
+            dtype_code(Q), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(Q), ptr(K), ptr(V), ptr(R), ptr(etype),
+            ptr(o), ptr(stats), row.size(0), e, n_q, n_k, h, d, n_types, ptr(ws), nbytes, plan.handle, stream_of(Q),
+            *drop))
+    return [o, stats]
+
+
+def attention_etype_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, R, etype, o,
+                             stats, dO, p=0.0, seed=0, offset=0, head0=0, need_dR=True):
+    """-> [dQ, dK, dV, dR] of attention_etype_forward for the output gradient dO, with the same (p, seed, offset,
+    head0): the weights and their keep decisions are recomputed per slot.  dR[t] = sum over the edges of type t of
+    (ds_e Q_i + a_e m_e dO_i) in R's shape is summed on chip -- no (n_edges, h, d) gradient exists -- and is 0 for a type
+    no edge carries; with need_dR=False it is an empty (0,) tensor and nothing is accumulated.  Out-of-range types are
+    clamped as in the forward: they never touch memory outside R / dR."""
+    fn = "attention_etype_backward"
+    drop = _drop_args(fn, p, seed, offset) + (_head0(fn, head0),)
+    _check_csr((row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c), _CSR_RC,
+               (Q, "Q"), (K, "K"), (V, "V"), (o, "o"), (stats, "stats"))
+    _check_grad(dO, "dO")
+    for t, n in ((K, "K"), (V, "V"), (o, "o"), (stats, "stats"), (dO, "dO")):
+        _same_dtype(Q, t, "Q", n)
+    dO = dO.contiguous()
+    if K.shape != V.shape or Q.shape[1:] != K.shape[1:]:
+        raise RuntimeError("%s: Q (n_q,[h,]d), K and V (n_k,[h,]d) expected" % fn)
+    e, d = eid_r.size(0), Q.size(-1)
+    h = 1 if Q.dim() == 2 else Q.size(1)
+    n_q, n_k = Q.size(0), K.size(0)
+    if o.shape != Q.shape or dO.shape != Q.shape or stats.numel() != n_q * h * 2:
+        raise RuntimeError("%s: o, dO must match Q and stats must be (n_q, h, 2)" % fn)
+    _attn_etype_table(fn, R, etype, Q, e)
+    n_types = R.size(0)
+    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
+    dR = torch.empty_like(R) if need_dR else torch.empty((0,), dtype=R.dtype, device=R.device)   # the call fills it
+    with _lib.device_guard(Q.device):
+        plan_r = get_plan(row, indptr_r, eid_r, indices_r, n_k)
+        plan_c = get_plan(col, indptr_c, eid_c, indices_c, n_q)
+        ws, nbytes = _attn_etype_workspace(Q, True, e, n_q, n_k, h, d, n_types, plan_r, plan_c)
+        check(lib().graphop_attention_etype_backward(
+            dtype_code(Q), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c), ptr(eid_c),
+            ptr(indices_c), ptr(Q), ptr(K), ptr(V), ptr(R), ptr(etype), ptr(o), ptr(stats), ptr(dO), ptr(dQ), ptr(dK),
+            ptr(dV), ptr(dR) if need_dR else _NULL, row.size(0), col.size(0), e, n_q, n_k, h, d, n_types, ptr(ws),
+            nbytes, plan_r.handle, plan_c.handle, stream_of(Q), *drop))
+    return [dQ, dK, dV, dR]
+
+
 # ---- the weights of the fused attention ops from their row statistics (extra op, DESIGN.md 4.5n) ---------------------
 def _attn_weights_operands(fn, Q, K, stats, b, xe, n_edges):
     """-> (h, d): the mode (at most one of b and xe), then Q, K and stats against each other, then b or xe against the
@@ -1007,7 +1114,9 @@ _SCHEMAS = {
 EXTRA_OPS = [n for n in _SCHEMAS if n not in __all__] + ["attention_backward_is_fused", "attention_dropout_forward",
                                                          "attention_dropout_backward", "attention_bias_forward",
                                                          "attention_bias_backward", "attention_edge_forward",
-                                                         "attention_edge_backward", "attention_weights"]
+                                                         "attention_edge_backward", "attention_weights",
+                                                         # edge-type embeddings (attention_etype_*)
+                                                         "attention_etype_forward", "attention_etype_backward"]
 _torch_lib = None
 
 

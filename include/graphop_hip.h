@@ -816,6 +816,55 @@ GRAPHOP_API int graphop_attention_edge_backward(int dtype, const int64_t* row, c
                                     int64_t workspace_bytes, const graphop_plan_t* plan_r, const graphop_plan_t* plan_c,
                                     void* stream, double p, uint64_t seed, uint32_t offset, int64_t head0);
 
+/* ---- edge-type embeddings in the fused attention step: K_j + R[t_e], V_j + R[t_e] (ABI 8, additive; EXTRA ops) ------
+ * The step of graphop_attention_edge_* for a CATEGORICAL edge feature (a bond type, a relation of a knowledge graph, a
+ * clipped relative position, a hop distance; relation-aware attention, Shaw-type relative positions,
+ * TransformerConv(edge_dim=...) behind an nn.Embedding): edge e carries the type t_e = etype[e] and the table row
+ * R[t_e] is added to its key AND its value.  etype is (n_edges) int32, contiguous, indexed by EDGE ID, with values in
+ * [0, n_types); R is (n_types, h, d) in the dtype of Q / K / V, contiguous.  DESIGN.md 4.5o.
+ *   kx_e = K_j + R[t_e]       vx_e = V_j + R[t_e]
+ *   every other line of graphop_attention_edge_* with xe[e] := R[t_e]
+ *   dR[t] = sum over the edges e with t_e = t of (ds_e Q_i + a_e mult_e dO_i);  types no edge carries get dR[t] = 0
+ * Nothing edge-sized is made in either direction: etype is the only edge-sized operand.  Parallel edges share a dropout
+ * decision and may differ in type.  No 1 / sqrt(d) argument, no bias argument, no xe together with R.
+ * OUT-OF-RANGE TYPES: etype is NOT scanned (a scan would synchronise the stream and break its capture in a graph).
+ * Every kernel clamps the type it loads into [0, n_types - 1], as an unsigned value, before it forms an address: a type
+ * outside [0, n_types) gives an undefined value (that of some type of the table) and never touches memory outside R / dR.
+ * Arguments as graphop_attention_edge_* with (R, etype) where xe is, dR where dxe is and n_types after d.  dR == NULL:
+ * the gradient of R is not wanted; nothing is accumulated for it.  Otherwise the call itself writes every element of dR
+ * (as it zero-fills dQ, dK, dV and what it accumulates into, with stream-ordered fills: a step can be captured).
+ * Checks, all before anything touches a device: those of graphop_attention_forward, then the dropout arguments (head0
+ * included), then n_types >= 1 (unless n_edges == 0), then R != NULL and etype != NULL (unless n_edges * h * d == 0),
+ * then the workspace.  Empty problems fill what they must and dereference nothing.  A matching plan must bound the ids by
+ * n_q and n_k (an error otherwise).
+ * Forms, chosen pass by pass: fp32 calls whose (h, d) is one of (1,64) (2,32) (2,64) (4,16) (4,32) (4,64) (8,8) (8,16)
+ * (8,32), with 16-byte aligned operands and ids below 2^31, run the chunk-driver passes of graphop_attention_edge_* with
+ * the edge piece read from the table (k_attn_etype_fwd_rows_f32, k_attn_etype_bwd_rows_f32) under the same conditions on
+ * the plans.  The row pass with dR != NULL sums dR in 4 n_types h d bytes of LDS and so needs that to be at most 16 KiB
+ * (n_types <= 4096 / (h d): 64 types at h d = 64, 16 at h d = 256); beyond it that pass alone is the generic one.
+ * Everything else runs the generic kernels k_attn_etype_*_generic, one wave per chunk.
+ * workspace: graphop_attention_etype_workspace_bytes bytes.  Backward with a fast form and a table that fits: its LAST
+ * up256(64 * 4 n_types h d) bytes (up256: rounded up to 256) hold the 64 replicas of dR the row pass's workgroups add
+ * into; with dR == NULL they are not touched. */
+GRAPHOP_API int graphop_attention_etype_workspace_bytes(int dtype, int backward, int64_t n_edges, int64_t n_q, int64_t n_k,
+                                            int64_t h, int64_t d, int64_t n_types, const graphop_plan_t* plan_r,
+                                            const graphop_plan_t* plan_c, void* stream, int64_t* bytes_out);
+GRAPHOP_API int graphop_attention_etype_forward(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                                    const int64_t* indices, const void* Q, const void* K, const void* V, const void* R,
+                                    const int32_t* etype, void* o, void* stats, int64_t n_chunks, int64_t n_edges,
+                                    int64_t n_q, int64_t n_k, int64_t h, int64_t d, int64_t n_types, void* workspace,
+                                    int64_t workspace_bytes, const graphop_plan_t* plan, void* stream, double p,
+                                    uint64_t seed, uint32_t offset, int64_t head0);
+GRAPHOP_API int graphop_attention_etype_backward(int dtype, const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r,
+                                     const int64_t* indices_r, const int64_t* col, const int64_t* indptr_c,
+                                     const int64_t* eid_c, const int64_t* indices_c, const void* Q, const void* K,
+                                     const void* V, const void* R, const int32_t* etype, const void* o, const void* stats,
+                                     const void* dO, void* dQ, void* dK, void* dV, void* dR, int64_t n_row_chunks,
+                                     int64_t n_col_chunks, int64_t n_edges, int64_t n_q, int64_t n_k, int64_t h, int64_t d,
+                                     int64_t n_types, void* workspace, int64_t workspace_bytes,
+                                     const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream, double p,
+                                     uint64_t seed, uint32_t offset, int64_t head0);
+
 /* ---- attention weights of the fused dot-product attention ops (not in the reference) --------------
  * The weights the layer used, as an edge tensor (PyG's return_attention_weights=True, DGL's get_attention=True), from
  * the row statistics stats (n_q, h, 2) = (m_i, linv_i) that graphop_attention_forward / _dropout_forward /
