@@ -319,7 +319,9 @@ class FusedAttention(Function):
         ctx.groups = None
         if h > 1 and hg < h:
             return _groups_forward(ctx, a8, Q, K, V, h, hg)
-        ctx.fused = _ops.attention_backward_is_fused(*a8, Q, K)
+        # (fewer key rows than query rows: the unfused SpMM returns zeros_like(V) and cannot hold o; the raw op can, and
+        #  composes inside the library where no fused form applies)
+        ctx.fused = _ops.attention_backward_is_fused(*a8, Q, K) or K.size(0) < Q.size(0)
         if ctx.fused:
             o, stats = _ops.attention_forward(row, indptr_r, eid_r, indices_r, Q, K, V)
             ctx.save_for_backward(*a8, Q, K, V, o, stats)
@@ -657,7 +659,7 @@ def _group_forward(a8, Qg, Kg, Vg, mode, drop=None, head0=0, bg=None):
     if drop is not None:
         og, stats = _ops.attention_dropout_forward(row, indptr_r, eid_r, indices_r, Qg, Kg, Vg, *drop, head0)
         return og, ("drop", og, stats)
-    if _ops.attention_backward_is_fused(*a8, Qg, Kg):
+    if _ops.attention_backward_is_fused(*a8, Qg, Kg) or Kg.size(0) < Qg.size(0):      # (as in FusedAttention.forward)
         og, stats = _ops.attention_forward(row, indptr_r, eid_r, indices_r, Qg, Kg, Vg)
         return og, ("fused", og, stats)
     s = _ops.maskedmm_csr_forward(row, indptr_r, eid_r, indices_r, Qg, Kg)

@@ -14,8 +14,27 @@ def head_multipliers(src, dst, g0, hg, p, seed, offset=0, dtype=torch.float64):
     """m[e, k] for the global heads g0 .. g0 + hg - 1, stated through dropout_reference.keep over all g0 + hg heads: what
     a call that handles one group of heads (head0 = g0) must apply."""
     scale = torch.tensor(1.0 / (1.0 - float(p)), dtype=torch.float64).to(dtype)
-    k = torch.from_numpy(R.keep(src, dst, g0 + hg, p, seed, offset)[:, g0:g0 + hg])
+    # heads below 4 * (g0 // 4) fill whole Philox blocks of their own: leaving those blocks out shifts the block index
+    # (the counter's third word) and nothing else, so a call with a large g0 need not state a million heads
+    skip = g0 // 4 if g0 + hg > 64 else 0
+    lo = g0 - 4 * skip
+    k = torch.from_numpy(_keep_from_block(src, dst, skip, lo + hg, p, seed, offset)[:, lo:lo + hg])
     return torch.where(k, scale, torch.zeros((), dtype=dtype))
+
+
+def _keep_from_block(src, dst, block0, h, p, seed, offset):
+    """dropout_reference.keep for the heads 4 * block0 .. 4 * block0 + h - 1: the same counters, blocks block0, block0 + 1, ..."""
+    import numpy as np
+    if block0 == 0:
+        return R.keep(src, dst, h, p, seed, offset)
+    src, dst = np.asarray(src, dtype=np.uint64), np.asarray(dst, dtype=np.uint64)
+    assert 0 <= p < 1 and 0 <= int(seed) < 2 ** 63 and 0 <= offset < 2 ** 32 and 0 <= block0 + (h + 3) // 4 <= 2 ** 32
+    out = np.empty((src.shape[0], h), dtype=bool)
+    for b in range((h + 3) // 4):
+        w = R.philox4x32_10((src, dst, block0 + b, offset), (int(seed) & R.MASK, int(seed) >> 32))
+        n = min(4, h - 4 * b)
+        out[:, 4 * b:4 * b + n] = w[:, :n].astype(np.uint64) >= np.uint64(R.threshold(p))
+    return out
 
 
 def _three(x):

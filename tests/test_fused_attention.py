@@ -334,6 +334,25 @@ def test_fused_fuzz_shapes_and_paths(dev, seed):
         _lib.clear_plan_cache()
 
 
+@pytest.mark.parametrize("h,d,dtype", [(3, 5, torch.float64), (2, 6, torch.float32), (1, 20, torch.float32), (8, 64, torch.float32)])
+def test_fused_step_with_fewer_key_rows_than_query_rows(dev, h, d, dtype):
+    """n_k < n_q where no fused form applies (seed 30 of tests/attention_fuzz.py: 3 x 5 in fp64 on 685+ rows and 545
+    keys): FusedAttention used to take the unfused SpMM there, whose result has the row count of V, and raised.  One
+    call and head groups, against the float64 statement of the definition."""
+    import attention_dropout_reference as A
+    g = random_graph(700, 545, 7000, seed=30, chunk_size=7, zero_rows=0.2, hub=300)
+    assert int(g.src.max()) >= g.n_dst
+    gen = torch.Generator().manual_seed(5)
+    shape = (lambda n: (n, d) if h == 1 else (n, h, d))
+    Q, dO = (torch.randn(*shape(g.n_src), generator=gen, dtype=torch.float64).to(dtype) / d ** 0.5 for _ in range(2))
+    K, V = (torch.randn(*shape(g.n_dst), generator=gen, dtype=torch.float64).to(dtype) for _ in range(2))
+    want = A.reference_step(g.src, g.dst, g.n_src, Q, K, V, dO, 0.0, 0)
+    got = fused_step(g.to(dev), Q.to(dev), K.to(dev), V.to(dev), dO.to(dev))
+    for key in ("o", "dQ", "dK", "dV"):
+        assert got[key].shape == want[key].shape and got[key].dtype == dtype
+        torch.testing.assert_close(got[key].cpu().double(), want[key], **TOL[dtype], msg=lambda m: "%s: %s" % (key, m))
+
+
 @pytest.fixture
 def force_fwd_walk():
     _lib.tune_reset()

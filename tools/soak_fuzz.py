@@ -8,6 +8,9 @@
     python tools/soak_fuzz.py --gat-edge [first_seed last_seed]   # tests/test_gat_edge_fuzz.py::test_gat_edge_fuzz (the
                                                               # fused GAT layer with an edge term,
                                                               # tests/gat_edge_fuzz.py); default 24 174
+    python tools/soak_fuzz.py --attention [first_seed last_seed]  # tests/test_attention_fuzz.py::
+                                                              # test_attention_family_fuzz (the fused dot-product
+                                                              # attention family, tests/attention_fuzz.py); default 48 348
 A seed that fails its assertions is counted and the run goes on.  Anything else a seed raises (a HIP error, a fault
 reported by the library) stops the run at that seed with exit status 2: nothing more is started on a device that may
 have faulted.  Exit status 1: some seed failed its assertions."""
@@ -16,8 +19,12 @@ sys.path.insert(0, os.getcwd()); sys.path.insert(0, os.path.join(os.getcwd(), "t
 import torch
 
 args = sys.argv[1:]
-gat = bool(args) and args[0] in ("--gat", "--gat-edge")
-if gat and args[0] == "--gat-edge":
+gat = bool(args) and args[0] in ("--gat", "--gat-edge", "--attention")
+if gat and args[0] == "--attention":
+    args = args[1:]
+    import test_attention_fuzz as T
+    run, default, cases = T.test_attention_family_fuzz, (48, 348), T.F.case_data
+elif gat and args[0] == "--gat-edge":
     args = args[1:]
     import test_gat_edge_fuzz as T
     run, default, cases = T.test_gat_edge_fuzz, (24, 174), T.G.case_data
