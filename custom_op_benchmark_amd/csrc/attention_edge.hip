@@ -6,67 +6,38 @@
 // fast kernels (kernels_attn_edge.h: the chunk-driver passes of the several-head kernels with the edge row streamed per
 // slot) run for the (h, d) pairs of GO_DISPATCH_GAT_HD with 16-byte aligned operands and matching plans; the generic
 // kernels of the same header run for everything else, pass by pass.  There is no composed form and no knob of its own:
-// force_generic selects the generic kernels.  p == 0 takes the kernels without the keep decision.
-#include "common.h"
-#include "host.h"
-#include "host_attn_rows.h"
-#include "host_dropout.h"
-#include "host_gat.h"
+// force_generic selects the generic kernels.  p == 0 takes the kernels without the keep decision.  The host side is
+// host_attn_edge_ops.h, shared with attention_etype.hip: this file states the form and the entry points.
 #include "kernels_attn_edge.h"
+#include "host_attn_edge_ops.h"
 
 using namespace graphop;
 
 namespace {
 
-// what the fast kernels ask of the shape (the pointers are checked where they are known: gat_hd_fast_ok)
-inline bool edge_shape_ok(int dtype, i64 h, i64 d, i64 n_edges, i64 n_q, i64 n_k) {
-  return gat_hd_fast_ok(dtype, h, d, n_edges, n_q, n_k, {});
-}
-
-// ONE plan of the fast kernels: neighbour ids, id ranges inside the tables (own rows n_own, gathered table n_tab)
-inline bool edge_plan_ok(const graphop_plan* plan, i64 n_own, i64 n_tab) {
-  return plan && plan->indices && plan->info.max_row < n_own && plan->info.max_index < n_tab;
-}
-
-// fast: (K | V), (Q | dO) packed and stats4 per (row, head); generic: P (n_q, h, 4) alone, at offset 0
-struct EdgeBwdWs {
-  size_t o_st4, o_kv, o_qdo, total;
-  EdgeBwdWs(bool fast, size_t es, i64 n_q, i64 n_k, i64 h, i64 F) {
-    o_st4 = 0;
-    o_kv = o_st4 + up256(es * 4 * (size_t)(n_q * h));
-    o_qdo = o_kv + (fast ? up256(sizeof(float) * (size_t)(n_k * 2 * F)) : 0);
-    total = o_qdo + (fast ? up256(sizeof(float) * (size_t)(n_q * 2 * F)) : 0);
+struct EdgeForm {
+  GO_ATTN_EDGE_FORM_NAMES(edge, Edge);
+  struct Rows {
+    const void* xe;
+    void* dxe;   // NULL: not wanted; the binding clears what the row pass does not write
+  };
+  static int check(const char* fn, const Rows& x, i64 n_edges, i64 h, i64 d) {
+    GO_CHECK_ARG(n_edges * h * d == 0 || x.xe != nullptr, "%s: xe is NULL", fn);
+    return GRAPHOP_OK;
   }
+  static bool fast_ok(const Rows& x, i64, bool backward) { return a16(x.xe) && (!backward || a16(x.dxe)); }
+  static bool row_fast_ok(const Rows&, i64) { return true; }
+  static size_t ws_tail(const Rows&, i64) { return 0; }
+  static int grad_fill(const Rows&, size_t, i64, bool, hipStream_t) { return GRAPHOP_OK; }
+  static void set_fwd(FwdArgs& a, const Rows& x) { a.xe = (const float*)x.xe; }
+  static auto rows_args(const Rows& x) { return std::make_tuple((const float*)x.xe); }
+  template <class T> static auto generic_args(const Rows& x) { return std::make_tuple((const T*)x.xe); }
+  static float* row_grad(const Rows& x, bool, void*) { return (float*)x.dxe; }
+  static void* grad(const Rows& x) { return x.dxe; }
+  static size_t row_lds(const Rows&, const float*, i64) { return 0; }
+  static int row_open(const Rows&, float*, i64, hipStream_t) { return GRAPHOP_OK; }
+  static int row_close(const Rows&, float*, i64, hipStream_t) { return GRAPHOP_OK; }
 };
-
-// the fast forward applies to this plan and these sizes: its launch geometry and piece records
-inline bool edge_fwd_fast_shape(int dtype, i64 h, i64 d, i64 n_edges, i64 n_q, i64 n_k, const graphop_plan* plan,
-                                i64 n_chunks, ChunkGeometry* geo) {
-  if (!edge_shape_ok(dtype, h, d, n_edges, n_q, n_k) || !edge_plan_ok(plan, n_q, n_k)) return false;
-  if (!plan->info.rows_sorted || n_q >= kWalkRowMask || n_chunks == 0) return false;
-  *geo = attn_rows_geometry(n_chunks);
-  return 2 * geo->groups < 0x7fffffffLL;
-}
-
-inline bool edge_has_slots(i64 n_chunks, i64 n_edges, i64 n_q, i64 n_k, i64 h, i64 d) {
-  return n_chunks > 0 && n_edges * h * d > 0 && n_q > 0 && n_k > 0;
-}
-
-template <bool COL>
-int launch_edge_rows(const char* tag, const graphop_plan* plan, const i64* eid, i64 n_chunks, i64 h, i64 d,
-                     const float* own, const float* xt, const float4* st4, const float* xe, float* out0, float* out1,
-                     float* dxe, const AttnEdgeDrop* drop, hipStream_t st) {
-  ProfScope prof(tag, st, "k_attn_edge_bwd_rows_f32");
-  const bool owned = plan->info.rows_sorted != 0, dropped = drop != nullptr;
-  const ChunkGeometry geo = attn_rows_geometry(n_chunks);
-  GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
-    hipLaunchKernelGGL((k_attn_edge_bwd_rows_f32<H, D, COL, OWNED, DROP>), dim3(geo.blocks), dim3(kFastBlock), 0, st,
-                       (const i64*)plan->row, (const i64*)plan->indptr, eid, (const i64*)plan->indices, own, xt, st4, xe,
-                       out0, out1, dxe, n_chunks, (int)geo.cpg, drop_if_arg<DROP>(drop));
-  })));
-  GO_LAUNCH_CHECK();
-  return GRAPHOP_OK;
-}
 
 }  // namespace
 
@@ -75,23 +46,9 @@ extern "C" {
 int graphop_attention_edge_workspace_bytes(int dtype, int backward, int64_t n_edges, int64_t n_q, int64_t n_k, int64_t h,
                                            int64_t d, const graphop_plan_t* plan_r, const graphop_plan_t* plan_c,
                                            void* stream, int64_t* bytes_out) {
-  const char* fn = "attention_edge_workspace_bytes";
   (void)stream;
-  GO_CHECK_ARG(bytes_out != nullptr, "%s: bytes_out is NULL", fn);
-  GO_CHECK_ARG(dtype == GRAPHOP_F32 || dtype == GRAPHOP_F64, "%s: bad dtype", fn);
-  GO_CHECK_ARG(n_edges >= 0 && n_q >= 0 && n_k >= 0 && h >= 1 && d >= 0, "%s: negative size", fn);
-  *bytes_out = 0;
-  if (n_edges * h * d == 0 || n_q == 0 || n_k == 0) return GRAPHOP_OK;
-  if (!backward) {
-    ChunkGeometry geo;   // the generic forward keeps its sums in stats: no workspace
-    if (plan_r && edge_fwd_fast_shape(dtype, h, d, n_edges, n_q, n_k, plan_r, plan_r->info.n_chunks, &geo))
-      *bytes_out = (int64_t)AttnRowsFwdWs(nullptr, 2 * geo.groups, n_q, h, h * d).total;
-    return GRAPHOP_OK;
-  }
-  const bool fast = edge_shape_ok(dtype, h, d, n_edges, n_q, n_k) &&
-                    (edge_plan_ok(plan_r, n_q, n_k) || edge_plan_ok(plan_c, n_k, n_q));
-  *bytes_out = (int64_t)EdgeBwdWs(fast, esize(dtype), n_q, n_k, h, h * d).total;
-  return GRAPHOP_OK;
+  return attn_edge_workspace_bytes<EdgeForm>("attention_edge_workspace_bytes", dtype, backward, n_edges, n_q, n_k, h, d,
+                                             true, {}, plan_r, plan_c, bytes_out);
 }
 
 int graphop_attention_edge_forward(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
@@ -100,99 +57,9 @@ int graphop_attention_edge_forward(int dtype, const int64_t* row, const int64_t*
                                    int64_t h, int64_t d, void* workspace, int64_t workspace_bytes,
                                    const graphop_plan_t* plan, void* stream, double p, uint64_t seed, uint32_t offset,
                                    int64_t head0) {
-  const char* fn = "attention_edge_forward";
-  GO_TRY(check_async_error(false));
-  GO_TRY(attn_check(fn, dtype, n_chunks, 0, n_edges, n_q, n_k, h, d));
-  HostDrop hdrop;
-  GO_TRY(attn_drop_check(fn, DropIn{p, seed, offset, head0}, n_q, n_k, &hdrop));
-  GO_CHECK_ARG(n_edges * h * d == 0 || xe != nullptr, "%s: xe is NULL", fn);
-  const HostDrop* drop = p > 0.0 ? &hdrop : nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  const size_t es = esize(dtype);
-  const i64 F = h * d;
-  const graphop_plan* pm = plan_matches_full(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
-                                             (const i64*)indices, n_chunks, n_edges) ? plan : nullptr;
-  GO_TRY(gat_check_plan(fn, pm, "Q / o", n_q, "K / V", n_k));
-  const bool slots = edge_has_slots(n_chunks, n_edges, n_q, n_k, h, d);
-  ChunkGeometry geo{};
-  bool fast = slots && !(drop && head0 + h >= 0x7fffffffLL) &&
-              edge_fwd_fast_shape(dtype, h, d, n_edges, n_q, n_k, pm, n_chunks, &geo) &&
-              gat_hd_fast_ok(dtype, h, d, n_edges, n_q, n_k, {Q, K, V, xe, o, stats, workspace});
-  const AttnRowsFwdWs w(workspace, 2 * geo.groups, n_q, h, F);
-  GO_TRY(attn_ws_check(fn, "attention_edge_workspace_bytes", fast, w.total, workspace, workspace_bytes));
-  if (n_q == 0) return GRAPHOP_OK;
-  // rows without slots keep o = 0 and stats = (-1e9, 0)
-  GO_PTR(fn, stats);
-  GO_DISPATCH_FLOAT(dtype, T, {
-    hipLaunchKernelGGL((k_attn_edge_stats_init_generic<T>), dim3(grid_of(n_q * h)), dim3(256), 0, st, (T*)stats, n_q * h);
-  });
-  GO_LAUNCH_CHECK();
-  if (F > 0) {
-    GO_PTR(fn, o);
-    GO_HIP(zero_async(o, es * (size_t)(n_q * F), st));
-  }
-  if (!slots) return GRAPHOP_OK;
-  GO_PTR(fn, row); GO_PTR(fn, indptr); GO_PTR(fn, eid); GO_PTR(fn, indices);
-  GO_PTR(fn, Q); GO_PTR(fn, K); GO_PTR(fn, V);
-  const bool dropped = drop != nullptr;
-  if (fast) {
-    const AttnEdgeDrop hd{drop ? drop->as<float>() : DropArgs<float>{}, (int)head0};
-    AttnEdgeFwdArgs a;
-    a.Q = (const float*)Q; a.K = (const float*)K; a.V = (const float*)V; a.xe = (const float*)xe;
-    a.o = (float*)o; a.stats = (float*)stats;
-    a.p_row = w.p_row; a.p_ml = w.p_ml; a.p_o = w.p_o;
-    attn_pieces_fill("attn_edge_fwd_setup", w, kAttnNegBig, st);
-    GO_LAUNCH_CHECK();
-    {
-      ProfScope prof("attn_edge_fwd_rows", st, "k_attn_edge_fwd_rows_f32");
-      GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(dropped, DROP, {
-        hipLaunchKernelGGL((k_attn_edge_fwd_rows_f32<H, D, DROP>), dim3(geo.blocks), dim3(kFastBlock), 0, st,
-                           (const i64*)pm->row, (const i64*)pm->indptr, eid_arg(pm, eid), (const i64*)pm->indices, a,
-                           n_chunks, (int)geo.cpg, drop_if_arg<DROP>(drop ? &hd : nullptr));
-      }));
-      GO_LAUNCH_CHECK();
-    }
-    attn_pieces_merge(
-        "attn_edge_fwd_merge", "k_attn_edge_piece_add", w, geo.lanes, st,
-        [&](dim3 grid, dim3 block) {
-          hipLaunchKernelGGL(k_attn_edge_piece_max, grid, block, 0, st, w.p_row, w.p_ml, w.Mtmp, w.np * h, (int)h);
-        },
-        [&](dim3 grid, dim3 block) {
-          GO_DISPATCH_GAT_HD(h, d, {
-            hipLaunchKernelGGL((k_attn_edge_piece_add<H, D>), grid, block, 0, st, w.p_row, w.p_ml, w.p_o, w.Mtmp, w.Ltmp,
-                               a.o, w.np);
-          });
-        },
-        [&](dim3 grid, dim3 block) {
-          GO_DISPATCH_GAT_HD(h, d, {
-            hipLaunchKernelGGL((k_attn_edge_piece_fin<H, D>), grid, block, 0, st, w.p_row, w.Mtmp, w.Ltmp, a.o, a.stats,
-                               w.np);
-          });
-        });
-    GO_LAUNCH_CHECK();
-    return GRAPHOP_OK;
-  }
-  const dim3 grid((unsigned)ceil_div(n_chunks, kGenericWavesPerBlock));
-  GO_DISPATCH_FLOAT(dtype, T, {
-    {
-      ProfScope prof("attn_edge_generic_stats", st, "k_attn_edge_stats_generic");
-      hipLaunchKernelGGL((k_attn_edge_stats_generic<T, false>), grid, dim3(kGenericBlock), 0, st, (const i64*)row,
-                         (const i64*)indptr, (const i64*)eid, (const i64*)indices, (const T*)Q, (const T*)K, (const T*)xe,
-                         (T*)stats, n_chunks, h, d);   // the maxima
-      hipLaunchKernelGGL((k_attn_edge_stats_generic<T, true>), grid, dim3(kGenericBlock), 0, st, (const i64*)row,
-                         (const i64*)indptr, (const i64*)eid, (const i64*)indices, (const T*)Q, (const T*)K, (const T*)xe,
-                         (T*)stats, n_chunks, h, d);   // the sums of exp(s - m)
-      hipLaunchKernelGGL((k_attn_edge_stats_fin_generic<T>), dim3(grid_of(n_q * h)), dim3(256), 0, st, (T*)stats, n_q * h);
-    }
-    ProfScope prof("attn_edge_generic_fwd", st, "k_attn_edge_fwd_generic");
-    GO_DISPATCH_BOOL(dropped, DROP, {
-      hipLaunchKernelGGL((k_attn_edge_fwd_generic<T, DROP>), grid, dim3(kGenericBlock), 0, st, (const i64*)row,
-                         (const i64*)indptr, (const i64*)eid, (const i64*)indices, (const T*)Q, (const T*)K, (const T*)V,
-                         (const T*)xe, (const T*)stats, (T*)o, n_chunks, h, d, (i64)head0, drop_arg<DROP, T>(drop));
-    });
-  });
-  GO_LAUNCH_CHECK();
-  return GRAPHOP_OK;
+  return attn_edge_forward<EdgeForm>("attention_edge_forward", dtype, row, indptr, eid, indices, Q, K, V, {xe, nullptr},
+                                     o, stats, n_chunks, n_edges, n_q, n_k, h, d, workspace, workspace_bytes, plan,
+                                     stream, DropIn{p, seed, offset, head0});
 }
 
 int graphop_attention_edge_backward(int dtype, const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r,
@@ -203,103 +70,10 @@ int graphop_attention_edge_backward(int dtype, const int64_t* row, const int64_t
                                     int64_t n_edges, int64_t n_q, int64_t n_k, int64_t h, int64_t d, void* workspace,
                                     int64_t workspace_bytes, const graphop_plan_t* plan_r, const graphop_plan_t* plan_c,
                                     void* stream, double p, uint64_t seed, uint32_t offset, int64_t head0) {
-  const char* fn = "attention_edge_backward";
-  GO_TRY(check_async_error(false));
-  GO_TRY(attn_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_q, n_k, h, d));
-  HostDrop hdrop;
-  GO_TRY(attn_drop_check(fn, DropIn{p, seed, offset, head0}, n_q, n_k, &hdrop));
-  GO_CHECK_ARG(n_edges * h * d == 0 || xe != nullptr, "%s: xe is NULL", fn);
-  const HostDrop* drop = p > 0.0 ? &hdrop : nullptr;
-  hipStream_t st = (hipStream_t)stream;
-  const size_t es = esize(dtype);
-  const i64 F = h * d;
-  const graphop_plan* pr = plan_matches_full(plan_r, (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r,
-                                             (const i64*)indices_r, n_row_chunks, n_edges) ? plan_r : nullptr;
-  const graphop_plan* pc = plan_matches_full(plan_c, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c,
-                                             (const i64*)indices_c, n_col_chunks, n_edges) ? plan_c : nullptr;
-  GO_TRY(gat_check_plan(fn, pr, "Q / dQ", n_q, "K / V", n_k));
-  GO_TRY(gat_check_plan(fn, pc, "K / dK / dV", n_k, "Q", n_q));
-  const bool row_slots = edge_has_slots(n_row_chunks, n_edges, n_q, n_k, h, d);
-  const bool col_slots = edge_has_slots(n_col_chunks, n_edges, n_q, n_k, h, d);
-  const bool slots = row_slots || col_slots;
-  // the fast kernels: the shape, every operand 16-byte aligned, and a plan for at least one of the two passes
-  const bool ok = slots && !(drop && head0 + h >= 0x7fffffffLL) &&
-                  gat_hd_fast_ok(dtype, h, d, n_edges, n_q, n_k, {Q, K, V, xe, o, stats, dO, dQ, dK, dV, dxe, workspace});
-  const bool fast_r = ok && row_slots && edge_plan_ok(pr, n_q, n_k);
-  const bool fast_c = ok && col_slots && edge_plan_ok(pc, n_k, n_q);
-  const EdgeBwdWs w(fast_r || fast_c, es, n_q, n_k, h, F);
-  GO_TRY(attn_ws_check(fn, "attention_edge_workspace_bytes", slots, w.total, workspace, workspace_bytes));
-  if (n_q * F > 0) { GO_PTR(fn, dQ); GO_HIP(zero_async(dQ, es * (size_t)(n_q * F), st)); }
-  if (n_k * F > 0) {
-    GO_PTR(fn, dK); GO_PTR(fn, dV);
-    GO_HIP(zero_async(dK, es * (size_t)(n_k * F), st));
-    GO_HIP(zero_async(dV, es * (size_t)(n_k * F), st));
-  }
-  if (!slots) return GRAPHOP_OK;
-  GO_PTR(fn, Q); GO_PTR(fn, K); GO_PTR(fn, V); GO_PTR(fn, o); GO_PTR(fn, stats); GO_PTR(fn, dO);
-  const bool dropped = drop != nullptr;
-  const AttnEdgeDrop hd{drop ? drop->as<float>() : DropArgs<float>{}, (int)head0};
-  char* base = (char*)workspace;
-  void* P = base + w.o_st4;   // (m, 1 / l, D, 0) per (row, head): stats4 of the fast passes, P of the generic ones
-  float* kv = (float*)(base + w.o_kv);
-  float* qdo = (float*)(base + w.o_qdo);
-  if (fast_r || fast_c) {
-    ProfScope prof("attn_edge_pack", st, "k_attn_edge_pack");
-    constexpr int RPB = kFastBlock / kGatGroup;
-    GO_DISPATCH_GAT_HD(h, d, {
-      hipLaunchKernelGGL((k_attn_edge_pack<H, D, false>), dim3((unsigned)ceil_div(n_k, RPB)), dim3(kFastBlock), 0, st,
-                         (const float*)K, (const float*)V, kv, n_k, (const float*)nullptr, (const float*)nullptr,
-                         (float4*)nullptr);
-      hipLaunchKernelGGL((k_attn_edge_pack<H, D, true>), dim3((unsigned)ceil_div(n_q, RPB)), dim3(kFastBlock), 0, st,
-                         (const float*)Q, (const float*)dO, qdo, n_q, (const float*)o, (const float*)stats, (float4*)P);
-    });
-    GO_LAUNCH_CHECK();
-  } else {
-    ProfScope prof("attn_edge_generic_pack", st, "k_attn_edge_pack_generic");
-    GO_DISPATCH_FLOAT(dtype, T, {
-      hipLaunchKernelGGL((k_attn_edge_pack_generic<T>), dim3(grid_of(n_q * h)), dim3(256), 0, st, (const T*)stats,
-                         (const T*)dO, (const T*)o, (T*)P, n_q * h, d);
-    });
-    GO_LAUNCH_CHECK();
-  }
-  if (row_slots) {
-    GO_PTR(fn, row); GO_PTR(fn, indptr_r); GO_PTR(fn, eid_r); GO_PTR(fn, indices_r);
-    if (fast_r) {
-      GO_TRY((launch_edge_rows<false>("attn_edge_rows_row", pr, eid_arg(pr, eid_r), n_row_chunks, h, d, qdo, kv,
-                                      (const float4*)P, (const float*)xe, (float*)dQ, nullptr, (float*)dxe,
-                                      drop ? &hd : nullptr, st)));
-    } else {
-      ProfScope prof("attn_edge_generic_bwd_row", st, "k_attn_edge_bwd_row_generic");
-      const dim3 grid((unsigned)ceil_div(n_row_chunks, kGenericWavesPerBlock));
-      GO_DISPATCH_FLOAT(dtype, T, GO_DISPATCH_BOOL(dropped, DROP, {
-        hipLaunchKernelGGL((k_attn_edge_bwd_row_generic<T, DROP>), grid, dim3(kGenericBlock), 0, st, (const i64*)row,
-                           (const i64*)indptr_r, (const i64*)eid_r, (const i64*)indices_r, (const T*)Q, (const T*)K,
-                           (const T*)V, (const T*)xe, (const T*)P, (const T*)dO, (T*)dQ, (T*)dxe, n_row_chunks, h, d,
-                           (i64)head0, drop_arg<DROP, T>(drop));
-      }));
-      GO_LAUNCH_CHECK();
-    }
-  }
-  if (col_slots) {
-    GO_PTR(fn, col); GO_PTR(fn, indptr_c); GO_PTR(fn, eid_c); GO_PTR(fn, indices_c);
-    if (fast_c) {
-      // the column pass always reads eid_c: no eid_arg here
-      GO_TRY((launch_edge_rows<true>("attn_edge_rows_col", pc, (const i64*)eid_c, n_col_chunks, h, d, kv, qdo,
-                                     (const float4*)P, (const float*)xe, (float*)dK, (float*)dV, nullptr,
-                                     drop ? &hd : nullptr, st)));
-    } else {
-      ProfScope prof("attn_edge_generic_bwd_col", st, "k_attn_edge_bwd_col_generic");
-      const dim3 grid((unsigned)ceil_div(n_col_chunks, kGenericWavesPerBlock));
-      GO_DISPATCH_FLOAT(dtype, T, GO_DISPATCH_BOOL(dropped, DROP, {
-        hipLaunchKernelGGL((k_attn_edge_bwd_col_generic<T, DROP>), grid, dim3(kGenericBlock), 0, st, (const i64*)col,
-                           (const i64*)indptr_c, (const i64*)eid_c, (const i64*)indices_c, (const T*)Q, (const T*)K,
-                           (const T*)V, (const T*)xe, (const T*)P, (const T*)dO, (T*)dK, (T*)dV, n_col_chunks, h, d,
-                           (i64)head0, drop_arg<DROP, T>(drop));
-      }));
-      GO_LAUNCH_CHECK();
-    }
-  }
-  return GRAPHOP_OK;
+  return attn_edge_backward<EdgeForm>("attention_edge_backward", dtype, row, indptr_r, eid_r, indices_r, col, indptr_c,
+                                      eid_c, indices_c, Q, K, V, {xe, dxe}, o, stats, dO, dQ, dK, dV, n_row_chunks,
+                                      n_col_chunks, n_edges, n_q, n_k, h, d, workspace, workspace_bytes, plan_r, plan_c,
+                                      stream, DropIn{p, seed, offset, head0});
 }
 
 }  // extern "C"

@@ -1,8 +1,8 @@
 // Host side of the fused dot-product attention ops, stated once: the argument checks every entry point makes first, the
 // workspace check, the launch geometry of the chunk-driver passes, and the piece-record forward -- its workspace, its
 // fills and its merge -- that attn_fwd_walk, attn_bias_fwd_rows (graphop_hip.hip), attn_heads_fwd_rows
-// (attention_heads.hip), graphop_attention_edge_forward (attention_edge.hip) and graphop_attention_etype_forward
-// (attention_etype.hip) run around their own pass.
+// (attention_heads.hip) and attn_edge_forward (host_attn_edge_ops.h: the edge-row ops of attention_edge.hip and
+// attention_etype.hip) run around their own pass.
 #pragma once
 #include <type_traits>
 

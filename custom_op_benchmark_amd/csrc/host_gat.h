@@ -106,15 +106,22 @@ inline bool gat_hd_fast_ok(int dtype, i64 h, i64 d, i64 E, i64 n_l, i64 n_r, std
 // One launch statement for a kernel and its edge form, whose parameter list is the plain one with the edge arguments
 // spliced in (eid, ee / xe, dee / dxe): the call lists every argument in the edge kernel's order and wraps those that
 // only the edge kernel takes in arg_if<EDGE>(...).  arg_if<false>(x) adds nothing to the list (x is still evaluated).
+// A std::tuple in the list stands for its elements (host_attn_edge_ops.h: the arguments a form's edge rows arrive as);
+// go_launch_lds is go_launch with dynamic LDS.
 template <bool ON, class T> struct ArgIf { T v; };
 template <bool ON, class T> ArgIf<ON, T> arg_if(T v) { return {v}; }
 template <class T> std::tuple<T> launch_arg(T v) { return {v}; }
 template <class T> std::tuple<T> launch_arg(ArgIf<true, T> a) { return {a.v}; }
 template <class T> std::tuple<> launch_arg(ArgIf<false, T>) { return {}; }
+template <class... T> std::tuple<T...> launch_arg(std::tuple<T...> t) { return t; }   // a run of arguments, in place
+template <class K, class... A>
+void go_launch_lds(K kernel, dim3 grid, dim3 block, size_t lds, hipStream_t st, A... args) {
+  std::apply([&](auto... a) { hipLaunchKernelGGL(kernel, grid, block, lds, st, a...); },
+             std::tuple_cat(launch_arg(args)...));
+}
 template <class K, class... A>
 void go_launch(K kernel, dim3 grid, dim3 block, hipStream_t st, A... args) {
-  std::apply([&](auto... a) { hipLaunchKernelGGL(kernel, grid, block, 0, st, a...); },
-             std::tuple_cat(launch_arg(args)...));
+  go_launch_lds(kernel, grid, block, 0, st, args...);
 }
 static_assert(std::is_same_v<decltype(std::tuple_cat(launch_arg(arg_if<false>(1)), launch_arg(2.f))),
                              std::tuple<float>>, "arg_if<false> drops its argument");

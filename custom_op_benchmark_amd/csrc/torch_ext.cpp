@@ -561,75 +561,7 @@ void check_attn_edge_rows(const char* fn, const at::Tensor& xe, const at::Tensor
   CHECK_CONTIGUOUS(xe); CHECK_CUDA(xe);
 }
 
-std::vector<at::Tensor> attention_edge_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
-                                               const at::Tensor& indices, const at::Tensor& Q, const at::Tensor& K,
-                                               const at::Tensor& V, const at::Tensor& xe, double p, int64_t seed,
-                                               int64_t offset, int64_t head0) {
-  const char* fn = "attention_edge_forward";
-  const DropSpec drop = drop_spec(fn, p, seed, offset);
-  head0_checked(fn, head0);
-  CHECK_CSR(row, indptr, eid, indices);
-  CHECK_INPUT(Q); CHECK_INPUT(K); CHECK_INPUT(V);
-  TORCH_CHECK(K.sizes() == V.sizes() && Q.sizes().slice(1) == K.sizes().slice(1),
-              fn, ": Q (n_q,[h,]d), K and V (n_k,[h,]d) expected");
-  CHECK_SAME_DTYPE(Q, K); CHECK_SAME_DTYPE(Q, V);
-  const int64_t e = eid.size(0), d = Q.size(-1), h = Q.dim() == 2 ? 1 : Q.size(1), n_q = Q.size(0), n_k = K.size(0);
-  check_attn_edge_rows(fn, xe, Q, e);
-  DeviceGuard dg(Q);
-  auto o = at::empty_like(Q);
-  auto stats = at::empty({n_q, h, 2}, Q.options());
-  const auto pp = get_plan(row, indptr, eid, indices, n_k);
-  const auto& pl = *pp;
-  int64_t nbytes = 0;
-  check(graphop_attention_edge_workspace_bytes(dtype_code(Q), 0, e, n_q, n_k, h, d, pl.plan, nullptr, stream_of(Q), &nbytes));
-  auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, Q.options().dtype(at::kByte));
-  check(graphop_attention_edge_forward(dtype_code(Q), ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(V),
-                                       vp(xe), vp(o), vp(stats), row.size(0), e, n_q, n_k, h, d, ws.data_ptr(), nbytes,
-                                       pl.plan, stream_of(Q), drop.p, drop.seed, drop.offset, head0));
-  return {o, stats};
-}
-
-std::vector<at::Tensor> attention_edge_backward(const at::Tensor& row, const at::Tensor& indptr_r,
-                                                const at::Tensor& eid_r, const at::Tensor& indices_r,
-                                                const at::Tensor& col, const at::Tensor& indptr_c,
-                                                const at::Tensor& eid_c, const at::Tensor& indices_c, const at::Tensor& Q,
-                                                const at::Tensor& K, const at::Tensor& V, const at::Tensor& xe,
-                                                const at::Tensor& o, const at::Tensor& stats, const at::Tensor& dO_,
-                                                double p, int64_t seed, int64_t offset, int64_t head0, bool need_dxe) {
-  const char* fn = "attention_edge_backward";
-  const DropSpec drop = drop_spec(fn, p, seed, offset);
-  head0_checked(fn, head0);
-  CHECK_CSR(row, indptr_r, eid_r, indices_r);
-  CHECK_CSR(col, indptr_c, eid_c, indices_c);
-  CHECK_INPUT(Q); CHECK_INPUT(K); CHECK_INPUT(V); CHECK_INPUT(o); CHECK_INPUT(stats);
-  CHECK_CUDA(dO_);
-  const at::Tensor dO = dO_.contiguous();
-  CHECK_SAME_DTYPE(Q, K); CHECK_SAME_DTYPE(Q, V); CHECK_SAME_DTYPE(Q, o); CHECK_SAME_DTYPE(Q, stats); CHECK_SAME_DTYPE(Q, dO);
-  TORCH_CHECK(K.sizes() == V.sizes() && Q.sizes().slice(1) == K.sizes().slice(1),
-              fn, ": Q (n_q,[h,]d), K and V (n_k,[h,]d) expected");
-  const int64_t e = eid_r.size(0), d = Q.size(-1), h = Q.dim() == 2 ? 1 : Q.size(1), n_q = Q.size(0), n_k = K.size(0);
-  TORCH_CHECK(o.sizes() == Q.sizes() && dO.sizes() == Q.sizes() && stats.numel() == n_q * h * 2,
-              fn, ": o, dO must match Q and stats must be (n_q, h, 2)");
-  check_attn_edge_rows(fn, xe, Q, e);
-  DeviceGuard dg(Q);
-  auto dQ = at::empty_like(Q), dK = at::empty_like(K), dV = at::empty_like(V);
-  const auto ppr = get_plan(row, indptr_r, eid_r, indices_r, n_k);
-  const auto ppc = get_plan(col, indptr_c, eid_c, indices_c, n_q);
-  const auto &pr = *ppr, &pc = *ppc;
-  int64_t nbytes = 0;
-  check(graphop_attention_edge_workspace_bytes(dtype_code(Q), 1, e, n_q, n_k, h, d, pr.plan, pc.plan, stream_of(Q), &nbytes));
-  auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, Q.options().dtype(at::kByte));
-  // dxe[e] is written once per row-major slot: only a chunk list that leaves slots out needs the zeros
-  auto dxe = !need_dxe ? at::empty({0}, xe.options()) : (pr.info.full_coverage ? at::empty_like(xe) : at::zeros_like(xe));
-  check(graphop_attention_edge_backward(
-      dtype_code(Q), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c), ip(indices_c),
-      vp(Q), vp(K), vp(V), vp(xe), vp(o), vp(stats), vp(dO), vp(dQ), vp(dK), vp(dV), need_dxe ? vp(dxe) : nullptr,
-      row.size(0), col.size(0), e, n_q, n_k, h, d, ws.data_ptr(), nbytes, pr.plan, pc.plan, stream_of(Q), drop.p,
-      drop.seed, drop.offset, head0));
-  return {dQ, dK, dV, dxe};
-}
-
-// ---- edge-type embeddings of the fused attention step (include/graphop_hip.h: graphop_attention_etype_*) ---------------
+// edge-type embeddings (include/graphop_hip.h: graphop_attention_etype_*), the edge rows being R[etype[e]]:
 // R: a contiguous device tensor (n_types, d) for 2-D Q / K / V, else (n_types, h, d), in Q's dtype, n_types >= 1 unless
 // the graph has no edge; etype: a contiguous device int32 tensor (n_edges).  The values of etype are not looked at (that
 // would synchronise): the kernels clamp them.
@@ -645,11 +577,13 @@ void check_attn_etype_table(const char* fn, const at::Tensor& R, const at::Tenso
   CHECK_CONTIGUOUS(etype); CHECK_CUDA(etype);
 }
 
-std::vector<at::Tensor> attention_etype_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
-                                                const at::Tensor& indices, const at::Tensor& Q, const at::Tensor& K,
-                                                const at::Tensor& V, const at::Tensor& R, const at::Tensor& etype,
-                                                double p, int64_t seed, int64_t offset, int64_t head0) {
-  const char* fn = "attention_etype_forward";
+// The forward of the two ops with an edge row in key and value, as `fn`.  etype == nullptr: rows is xe
+// (graphop_attention_edge_forward); else rows is the table R (graphop_attention_etype_forward).
+std::vector<at::Tensor> attention_edge_forward_impl(const char* fn, const at::Tensor& row, const at::Tensor& indptr,
+                                                    const at::Tensor& eid, const at::Tensor& indices, const at::Tensor& Q,
+                                                    const at::Tensor& K, const at::Tensor& V, const at::Tensor& rows,
+                                                    const at::Tensor* etype, double p, int64_t seed, int64_t offset,
+                                                    int64_t head0) {
   const DropSpec drop = drop_spec(fn, p, seed, offset);
   head0_checked(fn, head0);
   CHECK_CSR(row, indptr, eid, indices);
@@ -658,33 +592,57 @@ std::vector<at::Tensor> attention_etype_forward(const at::Tensor& row, const at:
               fn, ": Q (n_q,[h,]d), K and V (n_k,[h,]d) expected");
   CHECK_SAME_DTYPE(Q, K); CHECK_SAME_DTYPE(Q, V);
   const int64_t e = eid.size(0), d = Q.size(-1), h = Q.dim() == 2 ? 1 : Q.size(1), n_q = Q.size(0), n_k = K.size(0);
-  check_attn_etype_table(fn, R, etype, Q, e);
-  const int64_t n_types = R.size(0);
+  if (etype) check_attn_etype_table(fn, rows, *etype, Q, e);
+  else check_attn_edge_rows(fn, rows, Q, e);
+  const int64_t n_types = rows.size(0);
   DeviceGuard dg(Q);
   auto o = at::empty_like(Q);
   auto stats = at::empty({n_q, h, 2}, Q.options());
   const auto pp = get_plan(row, indptr, eid, indices, n_k);
   const auto& pl = *pp;
   int64_t nbytes = 0;
-  check(graphop_attention_etype_workspace_bytes(dtype_code(Q), 0, e, n_q, n_k, h, d, n_types, pl.plan, nullptr,
-                                                stream_of(Q), &nbytes));
+  check(etype ? graphop_attention_etype_workspace_bytes(dtype_code(Q), 0, e, n_q, n_k, h, d, n_types, pl.plan, nullptr,
+                                                        stream_of(Q), &nbytes)
+              : graphop_attention_edge_workspace_bytes(dtype_code(Q), 0, e, n_q, n_k, h, d, pl.plan, nullptr,
+                                                       stream_of(Q), &nbytes));
   auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, Q.options().dtype(at::kByte));
-  check(graphop_attention_etype_forward(dtype_code(Q), ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(V),
-                                        vp(R), etype.data_ptr<int32_t>(), vp(o), vp(stats), row.size(0), e, n_q, n_k, h,
-                                        d, n_types, ws.data_ptr(), nbytes, pl.plan, stream_of(Q), drop.p, drop.seed,
-                                        drop.offset, head0));
+  if (etype)
+    check(graphop_attention_etype_forward(dtype_code(Q), ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(V),
+                                          vp(rows), etype->data_ptr<int32_t>(), vp(o), vp(stats), row.size(0), e, n_q, n_k,
+                                          h, d, n_types, ws.data_ptr(), nbytes, pl.plan, stream_of(Q), drop.p, drop.seed,
+                                          drop.offset, head0));
+  else
+    check(graphop_attention_edge_forward(dtype_code(Q), ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(V),
+                                         vp(rows), vp(o), vp(stats), row.size(0), e, n_q, n_k, h, d, ws.data_ptr(), nbytes,
+                                         pl.plan, stream_of(Q), drop.p, drop.seed, drop.offset, head0));
   return {o, stats};
 }
 
-std::vector<at::Tensor> attention_etype_backward(const at::Tensor& row, const at::Tensor& indptr_r,
-                                                 const at::Tensor& eid_r, const at::Tensor& indices_r,
-                                                 const at::Tensor& col, const at::Tensor& indptr_c,
-                                                 const at::Tensor& eid_c, const at::Tensor& indices_c, const at::Tensor& Q,
-                                                 const at::Tensor& K, const at::Tensor& V, const at::Tensor& R,
-                                                 const at::Tensor& etype, const at::Tensor& o, const at::Tensor& stats,
-                                                 const at::Tensor& dO_, double p, int64_t seed, int64_t offset,
-                                                 int64_t head0, bool need_dR) {
-  const char* fn = "attention_etype_backward";
+std::vector<at::Tensor> attention_edge_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
+                                               const at::Tensor& indices, const at::Tensor& Q, const at::Tensor& K,
+                                               const at::Tensor& V, const at::Tensor& xe, double p, int64_t seed,
+                                               int64_t offset, int64_t head0) {
+  return attention_edge_forward_impl("attention_edge_forward", row, indptr, eid, indices, Q, K, V, xe, nullptr, p, seed,
+                                     offset, head0);
+}
+
+std::vector<at::Tensor> attention_etype_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
+                                                const at::Tensor& indices, const at::Tensor& Q, const at::Tensor& K,
+                                                const at::Tensor& V, const at::Tensor& R, const at::Tensor& etype,
+                                                double p, int64_t seed, int64_t offset, int64_t head0) {
+  return attention_edge_forward_impl("attention_etype_forward", row, indptr, eid, indices, Q, K, V, R, &etype, p, seed,
+                                     offset, head0);
+}
+
+// The backward of the same two ops; the fourth tensor is the gradient of rows, empty with need_dx == false
+std::vector<at::Tensor> attention_edge_backward_impl(const char* fn, const at::Tensor& row, const at::Tensor& indptr_r,
+                                                     const at::Tensor& eid_r, const at::Tensor& indices_r,
+                                                     const at::Tensor& col, const at::Tensor& indptr_c,
+                                                     const at::Tensor& eid_c, const at::Tensor& indices_c,
+                                                     const at::Tensor& Q, const at::Tensor& K, const at::Tensor& V,
+                                                     const at::Tensor& rows, const at::Tensor* etype, const at::Tensor& o,
+                                                     const at::Tensor& stats, const at::Tensor& dO_, double p,
+                                                     int64_t seed, int64_t offset, int64_t head0, bool need_dx) {
   const DropSpec drop = drop_spec(fn, p, seed, offset);
   head0_checked(fn, head0);
   CHECK_CSR(row, indptr_r, eid_r, indices_r);
@@ -698,24 +656,60 @@ std::vector<at::Tensor> attention_etype_backward(const at::Tensor& row, const at
   const int64_t e = eid_r.size(0), d = Q.size(-1), h = Q.dim() == 2 ? 1 : Q.size(1), n_q = Q.size(0), n_k = K.size(0);
   TORCH_CHECK(o.sizes() == Q.sizes() && dO.sizes() == Q.sizes() && stats.numel() == n_q * h * 2,
               fn, ": o, dO must match Q and stats must be (n_q, h, 2)");
-  check_attn_etype_table(fn, R, etype, Q, e);
-  const int64_t n_types = R.size(0);
+  if (etype) check_attn_etype_table(fn, rows, *etype, Q, e);
+  else check_attn_edge_rows(fn, rows, Q, e);
+  const int64_t n_types = rows.size(0);
   DeviceGuard dg(Q);
   auto dQ = at::empty_like(Q), dK = at::empty_like(K), dV = at::empty_like(V);
   const auto ppr = get_plan(row, indptr_r, eid_r, indices_r, n_k);
   const auto ppc = get_plan(col, indptr_c, eid_c, indices_c, n_q);
   const auto &pr = *ppr, &pc = *ppc;
   int64_t nbytes = 0;
-  check(graphop_attention_etype_workspace_bytes(dtype_code(Q), 1, e, n_q, n_k, h, d, n_types, pr.plan, pc.plan,
-                                                stream_of(Q), &nbytes));
+  check(etype ? graphop_attention_etype_workspace_bytes(dtype_code(Q), 1, e, n_q, n_k, h, d, n_types, pr.plan, pc.plan,
+                                                        stream_of(Q), &nbytes)
+              : graphop_attention_edge_workspace_bytes(dtype_code(Q), 1, e, n_q, n_k, h, d, pr.plan, pc.plan,
+                                                       stream_of(Q), &nbytes));
   auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, Q.options().dtype(at::kByte));
-  auto dR = need_dR ? at::empty_like(R) : at::empty({0}, R.options());   // the call fills it
-  check(graphop_attention_etype_backward(
-      dtype_code(Q), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c), ip(indices_c),
-      vp(Q), vp(K), vp(V), vp(R), etype.data_ptr<int32_t>(), vp(o), vp(stats), vp(dO), vp(dQ), vp(dK), vp(dV),
-      need_dR ? vp(dR) : nullptr, row.size(0), col.size(0), e, n_q, n_k, h, d, n_types, ws.data_ptr(), nbytes, pr.plan,
-      pc.plan, stream_of(Q), drop.p, drop.seed, drop.offset, head0));
-  return {dQ, dK, dV, dR};
+  // dR: the call fills it.  dxe[e] is written once per row-major slot: only a chunk list that leaves slots out needs
+  // the zeros
+  auto dx = !need_dx ? at::empty({0}, rows.options())
+                     : (etype || pr.info.full_coverage ? at::empty_like(rows) : at::zeros_like(rows));
+  if (etype)
+    check(graphop_attention_etype_backward(
+        dtype_code(Q), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c), ip(indices_c),
+        vp(Q), vp(K), vp(V), vp(rows), etype->data_ptr<int32_t>(), vp(o), vp(stats), vp(dO), vp(dQ), vp(dK), vp(dV),
+        need_dx ? vp(dx) : nullptr, row.size(0), col.size(0), e, n_q, n_k, h, d, n_types, ws.data_ptr(), nbytes, pr.plan,
+        pc.plan, stream_of(Q), drop.p, drop.seed, drop.offset, head0));
+  else
+    check(graphop_attention_edge_backward(
+        dtype_code(Q), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c), ip(indices_c),
+        vp(Q), vp(K), vp(V), vp(rows), vp(o), vp(stats), vp(dO), vp(dQ), vp(dK), vp(dV), need_dx ? vp(dx) : nullptr,
+        row.size(0), col.size(0), e, n_q, n_k, h, d, ws.data_ptr(), nbytes, pr.plan, pc.plan, stream_of(Q), drop.p,
+        drop.seed, drop.offset, head0));
+  return {dQ, dK, dV, dx};
+}
+
+std::vector<at::Tensor> attention_edge_backward(const at::Tensor& row, const at::Tensor& indptr_r,
+                                                const at::Tensor& eid_r, const at::Tensor& indices_r,
+                                                const at::Tensor& col, const at::Tensor& indptr_c,
+                                                const at::Tensor& eid_c, const at::Tensor& indices_c, const at::Tensor& Q,
+                                                const at::Tensor& K, const at::Tensor& V, const at::Tensor& xe,
+                                                const at::Tensor& o, const at::Tensor& stats, const at::Tensor& dO,
+                                                double p, int64_t seed, int64_t offset, int64_t head0, bool need_dxe) {
+  return attention_edge_backward_impl("attention_edge_backward", row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
+                                      indices_c, Q, K, V, xe, nullptr, o, stats, dO, p, seed, offset, head0, need_dxe);
+}
+
+std::vector<at::Tensor> attention_etype_backward(const at::Tensor& row, const at::Tensor& indptr_r,
+                                                 const at::Tensor& eid_r, const at::Tensor& indices_r,
+                                                 const at::Tensor& col, const at::Tensor& indptr_c,
+                                                 const at::Tensor& eid_c, const at::Tensor& indices_c, const at::Tensor& Q,
+                                                 const at::Tensor& K, const at::Tensor& V, const at::Tensor& R,
+                                                 const at::Tensor& etype, const at::Tensor& o, const at::Tensor& stats,
+                                                 const at::Tensor& dO, double p, int64_t seed, int64_t offset,
+                                                 int64_t head0, bool need_dR) {
+  return attention_edge_backward_impl("attention_etype_backward", row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
+                                      indices_c, Q, K, V, R, &etype, o, stats, dO, p, seed, offset, head0, need_dR);
 }
 
 // ---- the weights of the fused attention ops from their row statistics (include/graphop_hip.h: graphop_attention_weights)

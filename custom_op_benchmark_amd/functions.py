@@ -355,6 +355,14 @@ class FusedAttention(Function):
         return None, None, None, None, None, None, None, None, dQ, dK, dV
 
 
+def _drop_seed(seed, p):
+    """the seed of a fused attention class: the caller's, or with seed=None one drawn from torch's default CPU generator
+    (only where p > 0 uses it; else 0)"""
+    if seed is not None:
+        return seed
+    return int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item()) if float(p) > 0.0 else 0
+
+
 class FusedAttentionDropout(Function):
     """FusedAttention with dropout on the attention weights, o[i] = sum_j softmax_j(<Q_i, K_j>) m_ij V[j] (extra op;
     TransformerConv(dropout=...), DotGatConv):
@@ -375,8 +383,7 @@ class FusedAttentionDropout(Function):
         ctx.drop = None
         if float(p) == 0.0:
             return FusedAttention.forward(ctx, *a8, Q, K, V)
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        seed = _drop_seed(seed, p)
         ctx.drop = (float(p), int(seed), int(offset))
         h = Q.size(1) if Q.dim() == 3 else 1
         hg = _heads_per_call(a8, Q, K, h)
@@ -420,8 +427,7 @@ class FusedAttentionBias(Function):
     def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, b, p=0.0, seed=None,
                 offset=0):
         a8 = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item()) if float(p) > 0.0 else 0
+        seed = _drop_seed(seed, p)
         ctx.drop = (float(p), int(seed), int(offset))
         h = Q.size(1) if Q.dim() == 3 else 1
         hg = _heads_per_call(a8, Q, K, h)
@@ -462,8 +468,7 @@ class FusedAttentionEdge(Function):
     def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, xe, p=0.0, seed=None,
                 offset=0):
         a8 = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item()) if float(p) > 0.0 else 0
+        seed = _drop_seed(seed, p)
         ctx.drop = (float(p), int(seed), int(offset))
         o, stats = _ops.attention_edge_forward(row, indptr_r, eid_r, indices_r, Q, K, V, xe, *ctx.drop, 0)
         ctx.save_for_backward(*a8, Q, K, V, xe, o, stats)
@@ -495,8 +500,7 @@ class FusedAttentionEdgeType(Function):
     def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, R, etype, p=0.0,
                 seed=None, offset=0):
         a8 = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item()) if float(p) > 0.0 else 0
+        seed = _drop_seed(seed, p)
         ctx.drop = (float(p), int(seed), int(offset))
         o, stats = _ops.attention_etype_forward(row, indptr_r, eid_r, indices_r, Q, K, V, R, etype, *ctx.drop, 0)
         ctx.save_for_backward(*a8, Q, K, V, R, etype, o, stats)
@@ -535,8 +539,7 @@ class FusedAttentionWeights(Function):
         a8 = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
         if b is not None and xe is not None:
             raise RuntimeError("FusedAttentionWeights: at most one of b and xe may be given")
-        if seed is None:
-            seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item()) if float(p) > 0.0 else 0
+        seed = _drop_seed(seed, p)
         ctx.drop = (float(p), int(seed), int(offset))
         ctx.set_materialize_grads(False)
         ctx.mode = "edge" if xe is not None else ("bias" if b is not None else "plain")

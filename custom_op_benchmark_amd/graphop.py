@@ -791,7 +791,9 @@ def attention_bias_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_
                                dO, _drop_args(fn, p, seed, offset) + (_head0(fn, head0),), b, need_db)
 
 
-# ---- edge features of the fused attention step: K_j + xe[e], V_j + xe[e] (extra ops) ----------------
+# ---- an edge row in key and value of the fused attention step (extra ops): K_j + xe[e], V_j + xe[e]
+# ---- and, for a categorical edge feature, K_j + R[t_e], V_j + R[t_e] (4.5o).  One body per direction: etype None is
+# ---- the first op (rows = xe), else the second (rows = R)
 def _attn_edge_rows(fn, xe, Q, n_edges):
     """xe checked against the graph and Q: a contiguous device tensor (n_edges, d) for 2-D Q / K / V, else
     (n_edges, h, d), in Q's dtype.  The C ABI takes a raw pointer: each of these would read out of bounds or garbage."""
@@ -805,85 +807,6 @@ def _attn_edge_rows(fn, xe, Q, n_edges):
         raise RuntimeError("xe must be a CUDA tensor")
 
 
-def _attn_edge_workspace(like, backward, e, n_q, n_k, h, d, plan_r, plan_c):
-    import ctypes
-    nbytes = ctypes.c_int64(0)
-    check(lib().graphop_attention_edge_workspace_bytes(
-        dtype_code(like), 1 if backward else 0, e, n_q, n_k, h, d, plan_r.handle,
-        plan_c.handle if plan_c is not None else _NULL, stream_of(like), ctypes.byref(nbytes)))
-    return torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=like.device), nbytes.value
-
-
-def attention_edge_forward(row, indptr, eid, indices, Q, K, V, xe, p=0.0, seed=0, offset=0, head0=0):
-    """-> [o, stats] of the fused attention step with a feature row per edge added to the key AND the value: for edge
-    e = (i, j),  kx = K[j] + xe[e],  vx = V[j] + xe[e],  s_e = <Q_i, kx_e>,  a = row-softmax(s),  o[i] = sum_e a_e m_e vx_e
-    (TransformerConv(edge_dim=...): out = alpha * (value_j + edge_attr); the Dwivedi-Bresson and GraphGPS edge-featured
-    graph transformers).  xe is indexed by edge id ((n_edges, d) for 2-D Q / K / V, else (n_edges, h, d)), has their
-    dtype and is contiguous; parallel edges share a dropout decision and have each their own row.  stats (n_q, h, 2) =
-    (row max floored at -1e9, 1 / sum exp) of the undropped scores, (-1e9, 0) and o = 0 for rows without edges;
-    (p, seed, offset, head0) as attention_dropout_forward, p = 0: no dropout.  Nothing edge-sized is made.  There is no
-    1 / sqrt(d) scale argument (fold it into Q) and no bias argument."""
-    fn = "attention_edge_forward"
-    drop = _drop_args(fn, p, seed, offset) + (_head0(fn, head0),)
-    _check_csr((row, indptr, eid, indices), _CSR, (Q, "Q"), (K, "K"), (V, "V"))
-    _same_dtype(Q, K, "Q", "K")
-    _same_dtype(Q, V, "Q", "V")
-    if K.shape != V.shape or Q.shape[1:] != K.shape[1:]:
-        raise RuntimeError("%s: Q (n_q,[h,]d), K and V (n_k,[h,]d) expected" % fn)
-    e, d = eid.size(0), Q.size(-1)
-    h = 1 if Q.dim() == 2 else Q.size(1)
-    n_q, n_k = Q.size(0), K.size(0)
-    _attn_edge_rows(fn, xe, Q, e)
-    o = torch.empty_like(Q)
-    stats = torch.empty((n_q, h, 2), dtype=Q.dtype, device=Q.device)
-    with _lib.device_guard(Q.device):
-        plan = get_plan(row, indptr, eid, indices, n_k)
-        ws, nbytes = _attn_edge_workspace(Q, False, e, n_q, n_k, h, d, plan, None)
-        check(lib().graphop_attention_edge_forward(
-            dtype_code(Q), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(Q), ptr(K), ptr(V), ptr(xe),
-            ptr(o), ptr(stats), row.size(0), e, n_q, n_k, h, d, ptr(ws), nbytes, plan.handle, stream_of(Q), *drop))
-    return [o, stats]
-
-
-def attention_edge_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, xe, o, stats, dO,
-                            p=0.0, seed=0, offset=0, head0=0, need_dxe=True):
-    """-> [dQ, dK, dV, dxe] of attention_edge_forward for the output gradient dO, with the same (p, seed, offset,
-    head0): the weights and their keep decisions are recomputed per slot.  dxe[e] = ds_e Q_i + a_e m_e dO_i in xe's
-    shape is the only edge-sized tensor made (edge ids that no row-major slot names get 0); with need_dxe=False it is
-    an empty (0,) tensor and nothing edge-sized is written."""
-    fn = "attention_edge_backward"
-    drop = _drop_args(fn, p, seed, offset) + (_head0(fn, head0),)
-    _check_csr((row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c), _CSR_RC,
-               (Q, "Q"), (K, "K"), (V, "V"), (o, "o"), (stats, "stats"))
-    _check_grad(dO, "dO")
-    for t, n in ((K, "K"), (V, "V"), (o, "o"), (stats, "stats"), (dO, "dO")):
-        _same_dtype(Q, t, "Q", n)
-    dO = dO.contiguous()
-    if K.shape != V.shape or Q.shape[1:] != K.shape[1:]:
-        raise RuntimeError("%s: Q (n_q,[h,]d), K and V (n_k,[h,]d) expected" % fn)
-    e, d = eid_r.size(0), Q.size(-1)
-    h = 1 if Q.dim() == 2 else Q.size(1)
-    n_q, n_k = Q.size(0), K.size(0)
-    if o.shape != Q.shape or dO.shape != Q.shape or stats.numel() != n_q * h * 2:
-        raise RuntimeError("%s: o, dO must match Q and stats must be (n_q, h, 2)" % fn)
-    _attn_edge_rows(fn, xe, Q, e)
-    dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
-    with _lib.device_guard(Q.device):
-        plan_r = get_plan(row, indptr_r, eid_r, indices_r, n_k)
-        plan_c = get_plan(col, indptr_c, eid_c, indices_c, n_q)
-        # dxe[e] is written once per row-major slot: only a chunk list that leaves slots out needs the zeros
-        dxe = (torch.empty_like(xe) if plan_r.info.full_coverage else torch.zeros_like(xe)) if need_dxe \
-            else torch.empty((0,), dtype=xe.dtype, device=xe.device)
-        ws, nbytes = _attn_edge_workspace(Q, True, e, n_q, n_k, h, d, plan_r, plan_c)
-        check(lib().graphop_attention_edge_backward(
-            dtype_code(Q), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c), ptr(eid_c),
-            ptr(indices_c), ptr(Q), ptr(K), ptr(V), ptr(xe), ptr(o), ptr(stats), ptr(dO), ptr(dQ), ptr(dK), ptr(dV),
-            ptr(dxe) if need_dxe else _NULL, row.size(0), col.size(0), e, n_q, n_k, h, d, ptr(ws), nbytes,
-            plan_r.handle, plan_c.handle, stream_of(Q), *drop))
-    return [dQ, dK, dV, dxe]
-
-
-# ---- edge-type embeddings of the fused attention step: K_j + R[t_e], V_j + R[t_e] (extra ops, DESIGN.md 4.5o) --------
 def _attn_etype_table(fn, R, etype, Q, n_edges):
     """R and etype checked against the graph and Q: R a contiguous device tensor (n_types, d) for 2-D Q / K / V, else
     (n_types, h, d), in Q's dtype, with n_types >= 1 unless the graph has no edge; etype a contiguous device int32
@@ -906,28 +829,26 @@ def _attn_etype_table(fn, R, etype, Q, n_edges):
             raise RuntimeError("%s must be a CUDA tensor" % n)
 
 
-def _attn_etype_workspace(like, backward, e, n_q, n_k, h, d, n_types, plan_r, plan_c):
+def _attn_edge_workspace(like, backward, sizes, plan_r, plan_c, typed):
+    """sizes: (e, n_q, n_k, h, d) and, typed, n_types"""
     import ctypes
     nbytes = ctypes.c_int64(0)
-    check(lib().graphop_attention_etype_workspace_bytes(
-        dtype_code(like), 1 if backward else 0, e, n_q, n_k, h, d, n_types, plan_r.handle,
-        plan_c.handle if plan_c is not None else _NULL, stream_of(like), ctypes.byref(nbytes)))
+    query = lib().graphop_attention_etype_workspace_bytes if typed else lib().graphop_attention_edge_workspace_bytes
+    check(query(dtype_code(like), 1 if backward else 0, *sizes, plan_r.handle,
+                plan_c.handle if plan_c is not None else _NULL, stream_of(like), ctypes.byref(nbytes)))
     return torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=like.device), nbytes.value
 
 
-def attention_etype_forward(row, indptr, eid, indices, Q, K, V, R, etype, p=0.0, seed=0, offset=0, head0=0):
-    """-> [o, stats] of attention_edge_forward for a categorical edge feature: edge e = (i, j) carries the type
-    t = etype[e] and the table row R[t] is added to its key AND its value,  kx = K[j] + R[t],  vx = V[j] + R[t],
-    s_e = <Q_i, kx_e>,  a = row-softmax(s),  o[i] = sum_e a_e m_e vx_e  (relation-aware attention, Shaw-type relative
-    positions, TransformerConv(edge_dim=...) behind an nn.Embedding).  etype is (n_edges) torch.int32, contiguous,
-    indexed by edge id, with values in [0, n_types); R is (n_types, d) for 2-D Q / K / V, else (n_types, h, d), in their
-    dtype and contiguous.  Nothing of size (n_edges, h, d) is made or read: this is attention_edge_forward on
-    R[etype.long()] without that tensor.  Parallel edges share a dropout decision and may differ in type.
-    Out-of-range types: etype is not scanned (a scan would synchronise the stream and break its capture); every kernel
-    clamps a type into [0, n_types - 1] before it forms an address, so a type outside [0, n_types) gives an undefined
-    value and never touches memory outside R.  stats, (p, seed, offset, head0), the missing 1 / sqrt(d) and bias
-    arguments: as attention_edge_forward."""
-    fn = "attention_etype_forward"
+def _attn_edge_operands(fn, rows, etype, Q, e, n_q, n_k, h, d):
+    """the form's operand check -> (its pointer arguments, the size arguments of its calls)"""
+    if etype is None:
+        _attn_edge_rows(fn, rows, Q, e)
+        return (ptr(rows),), (e, n_q, n_k, h, d)
+    _attn_etype_table(fn, rows, etype, Q, e)
+    return (ptr(rows), ptr(etype)), (e, n_q, n_k, h, d, rows.size(0))
+
+
+def _attn_edge_forward(fn, row, indptr, eid, indices, Q, K, V, rows, etype, p, seed, offset, head0):
     drop = _drop_args(fn, p, seed, offset) + (_head0(fn, head0),)
     _check_csr((row, indptr, eid, indices), _CSR, (Q, "Q"), (K, "K"), (V, "V"))
     _same_dtype(Q, K, "Q", "K")
@@ -937,28 +858,21 @@ def attention_etype_forward(row, indptr, eid, indices, Q, K, V, R, etype, p=0.0,
     e, d = eid.size(0), Q.size(-1)
     h = 1 if Q.dim() == 2 else Q.size(1)
     n_q, n_k = Q.size(0), K.size(0)
-    _attn_etype_table(fn, R, etype, Q, e)
-    n_types = R.size(0)
+    typed = etype is not None
+    operands, sizes = _attn_edge_operands(fn, rows, etype, Q, e, n_q, n_k, h, d)
     o = torch.empty_like(Q)
     stats = torch.empty((n_q, h, 2), dtype=Q.dtype, device=Q.device)
     with _lib.device_guard(Q.device):
         plan = get_plan(row, indptr, eid, indices, n_k)
-        ws, nbytes = _attn_etype_workspace(Q, False, e, n_q, n_k, h, d, n_types, plan, None)
-        check(lib().graphop_attention_etype_forward(
-            dtype_code(Q), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(Q), ptr(K), ptr(V), ptr(R), ptr(etype),
-            ptr(o), ptr(stats), row.size(0), e, n_q, n_k, h, d, n_types, ptr(ws), nbytes, plan.handle, stream_of(Q),
-            *drop))
+        ws, nbytes = _attn_edge_workspace(Q, False, sizes, plan, None, typed)
+        call = lib().graphop_attention_etype_forward if typed else lib().graphop_attention_edge_forward
+        check(call(dtype_code(Q), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(Q), ptr(K), ptr(V), *operands,
+                   ptr(o), ptr(stats), row.size(0), *sizes, ptr(ws), nbytes, plan.handle, stream_of(Q), *drop))
     return [o, stats]
 
 
-def attention_etype_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, R, etype, o,
-                             stats, dO, p=0.0, seed=0, offset=0, head0=0, need_dR=True):
-    """-> [dQ, dK, dV, dR] of attention_etype_forward for the output gradient dO, with the same (p, seed, offset,
-    head0): the weights and their keep decisions are recomputed per slot.  dR[t] = sum over the edges of type t of
-    (ds_e Q_i + a_e m_e dO_i) in R's shape is summed on chip -- no (n_edges, h, d) gradient exists -- and is 0 for a type
-    no edge carries; with need_dR=False it is an empty (0,) tensor and nothing is accumulated.  Out-of-range types are
-    clamped as in the forward: they never touch memory outside R / dR."""
-    fn = "attention_etype_backward"
+def _attn_edge_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, rows, etype, o,
+                        stats, dO, p, seed, offset, head0, need_dx):
     drop = _drop_args(fn, p, seed, offset) + (_head0(fn, head0),)
     _check_csr((row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c), _CSR_RC,
                (Q, "Q"), (K, "K"), (V, "V"), (o, "o"), (stats, "stats"))
@@ -973,20 +887,74 @@ def attention_etype_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid
     n_q, n_k = Q.size(0), K.size(0)
     if o.shape != Q.shape or dO.shape != Q.shape or stats.numel() != n_q * h * 2:
         raise RuntimeError("%s: o, dO must match Q and stats must be (n_q, h, 2)" % fn)
-    _attn_etype_table(fn, R, etype, Q, e)
-    n_types = R.size(0)
+    typed = etype is not None
+    operands, sizes = _attn_edge_operands(fn, rows, etype, Q, e, n_q, n_k, h, d)
     dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
-    dR = torch.empty_like(R) if need_dR else torch.empty((0,), dtype=R.dtype, device=R.device)   # the call fills it
     with _lib.device_guard(Q.device):
         plan_r = get_plan(row, indptr_r, eid_r, indices_r, n_k)
         plan_c = get_plan(col, indptr_c, eid_c, indices_c, n_q)
-        ws, nbytes = _attn_etype_workspace(Q, True, e, n_q, n_k, h, d, n_types, plan_r, plan_c)
-        check(lib().graphop_attention_etype_backward(
-            dtype_code(Q), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c), ptr(eid_c),
-            ptr(indices_c), ptr(Q), ptr(K), ptr(V), ptr(R), ptr(etype), ptr(o), ptr(stats), ptr(dO), ptr(dQ), ptr(dK),
-            ptr(dV), ptr(dR) if need_dR else _NULL, row.size(0), col.size(0), e, n_q, n_k, h, d, n_types, ptr(ws),
-            nbytes, plan_r.handle, plan_c.handle, stream_of(Q), *drop))
-    return [dQ, dK, dV, dR]
+        # dR: the call fills it.  dxe[e] is written once per row-major slot: only a chunk list that leaves slots out
+        # needs the zeros
+        if not need_dx:
+            dx = torch.empty((0,), dtype=rows.dtype, device=rows.device)
+        else:
+            dx = torch.empty_like(rows) if typed or plan_r.info.full_coverage else torch.zeros_like(rows)
+        ws, nbytes = _attn_edge_workspace(Q, True, sizes, plan_r, plan_c, typed)
+        call = lib().graphop_attention_etype_backward if typed else lib().graphop_attention_edge_backward
+        check(call(dtype_code(Q), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c),
+                   ptr(eid_c), ptr(indices_c), ptr(Q), ptr(K), ptr(V), *operands, ptr(o), ptr(stats), ptr(dO), ptr(dQ),
+                   ptr(dK), ptr(dV), ptr(dx) if need_dx else _NULL, row.size(0), col.size(0), *sizes, ptr(ws), nbytes,
+                   plan_r.handle, plan_c.handle, stream_of(Q), *drop))
+    return [dQ, dK, dV, dx]
+
+
+def attention_edge_forward(row, indptr, eid, indices, Q, K, V, xe, p=0.0, seed=0, offset=0, head0=0):
+    """-> [o, stats] of the fused attention step with a feature row per edge added to the key AND the value: for edge
+    e = (i, j),  kx = K[j] + xe[e],  vx = V[j] + xe[e],  s_e = <Q_i, kx_e>,  a = row-softmax(s),  o[i] = sum_e a_e m_e vx_e
+    (TransformerConv(edge_dim=...): out = alpha * (value_j + edge_attr); the Dwivedi-Bresson and GraphGPS edge-featured
+    graph transformers).  xe is indexed by edge id ((n_edges, d) for 2-D Q / K / V, else (n_edges, h, d)), has their
+    dtype and is contiguous; parallel edges share a dropout decision and have each their own row.  stats (n_q, h, 2) =
+    (row max floored at -1e9, 1 / sum exp) of the undropped scores, (-1e9, 0) and o = 0 for rows without edges;
+    (p, seed, offset, head0) as attention_dropout_forward, p = 0: no dropout.  Nothing edge-sized is made.  There is no
+    1 / sqrt(d) scale argument (fold it into Q) and no bias argument."""
+    return _attn_edge_forward("attention_edge_forward", row, indptr, eid, indices, Q, K, V, xe, None, p, seed, offset, head0)
+
+
+def attention_edge_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, xe, o, stats, dO,
+                            p=0.0, seed=0, offset=0, head0=0, need_dxe=True):
+    """-> [dQ, dK, dV, dxe] of attention_edge_forward for the output gradient dO, with the same (p, seed, offset,
+    head0): the weights and their keep decisions are recomputed per slot.  dxe[e] = ds_e Q_i + a_e m_e dO_i in xe's
+    shape is the only edge-sized tensor made (edge ids that no row-major slot names get 0); with need_dxe=False it is
+    an empty (0,) tensor and nothing edge-sized is written."""
+    return _attn_edge_backward("attention_edge_backward", row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c,
+                               Q, K, V, xe, None, o, stats, dO, p, seed, offset, head0, need_dxe)
+
+
+def attention_etype_forward(row, indptr, eid, indices, Q, K, V, R, etype, p=0.0, seed=0, offset=0, head0=0):
+    """-> [o, stats] of attention_edge_forward for a categorical edge feature: edge e = (i, j) carries the type
+    t = etype[e] and the table row R[t] is added to its key AND its value,  kx = K[j] + R[t],  vx = V[j] + R[t],
+    s_e = <Q_i, kx_e>,  a = row-softmax(s),  o[i] = sum_e a_e m_e vx_e  (relation-aware attention, Shaw-type relative
+    positions, TransformerConv(edge_dim=...) behind an nn.Embedding).  etype is (n_edges) torch.int32, contiguous,
+    indexed by edge id, with values in [0, n_types); R is (n_types, d) for 2-D Q / K / V, else (n_types, h, d), in their
+    dtype and contiguous.  Nothing of size (n_edges, h, d) is made or read: this is attention_edge_forward on
+    R[etype.long()] without that tensor.  Parallel edges share a dropout decision and may differ in type.
+    Out-of-range types: etype is not scanned (a scan would synchronise the stream and break its capture); every kernel
+    clamps a type into [0, n_types - 1] before it forms an address, so a type outside [0, n_types) gives an undefined
+    value and never touches memory outside R.  stats, (p, seed, offset, head0), the missing 1 / sqrt(d) and bias
+    arguments: as attention_edge_forward."""
+    return _attn_edge_forward("attention_etype_forward", row, indptr, eid, indices, Q, K, V, R, etype, p, seed, offset,
+                              head0)
+
+
+def attention_etype_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, R, etype, o,
+                             stats, dO, p=0.0, seed=0, offset=0, head0=0, need_dR=True):
+    """-> [dQ, dK, dV, dR] of attention_etype_forward for the output gradient dO, with the same (p, seed, offset,
+    head0): the weights and their keep decisions are recomputed per slot.  dR[t] = sum over the edges of type t of
+    (ds_e Q_i + a_e m_e dO_i) in R's shape is summed on chip -- no (n_edges, h, d) gradient exists -- and is 0 for a type
+    no edge carries; with need_dR=False it is an empty (0,) tensor and nothing is accumulated.  Out-of-range types are
+    clamped as in the forward: they never touch memory outside R / dR."""
+    return _attn_edge_backward("attention_etype_backward", row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
+                               indices_c, Q, K, V, R, etype, o, stats, dO, p, seed, offset, head0, need_dR)
 
 
 # ---- the weights of the fused attention ops from their row statistics (extra op, DESIGN.md 4.5n) ---------------------
