@@ -125,23 +125,22 @@ bool attn_rows_ok(int dtype, i64 h, i64 d, i64 n_edges, i64 n_q, i64 n_k, const 
 // k_attn_bias_bwd_rows_f32 (b and db by edge id; eid == nullptr: the plan has eid_identity).  Without BIAS eid, b and
 // db are not read.
 template <bool COL, bool DROP, bool BIAS>
-int launch_attn_rows(const char* tag, const graphop_plan* plan, const i64* eid, i64 n_chunks, int F, const float* own,
-                     const float* xt, const float4* st4, const float* b, float* out0, float* out1, float* db,
-                     const AttnDrop* drop, hipStream_t st) {
+int launch_attn_rows(const char* tag, const Csr& g, int F, const float* own, const float* xt, const float4* st4,
+                     const float* b, float* out0, float* out1, float* db, const AttnDrop* drop, hipStream_t st) {
+  const i64 n_chunks = g.n_chunks;
   if (n_chunks == 0) return GRAPHOP_OK;
+  const i64* eid = g.eid_or_null();
   ProfScope prof(tag, st, BIAS ? (DROP ? "k_attn_bias_bwd_rows_f32<DROP>" : "k_attn_bias_bwd_rows_f32")
                                : (DROP ? "k_attn_bwd_rows_f32<DROP>" : "k_attn_bwd_rows_f32"));
   const ChunkGeometry geo = attn_one_head_geometry(n_chunks, F);
   const dim3 grid(geo.blocks), block(kFastBlock);
-  GO_DISPATCH_LNV(F, GO_DISPATCH_BOOL(plan->info.rows_sorted != 0, OWNED, {
+  GO_DISPATCH_LNV(F, GO_DISPATCH_BOOL(g.owned(), OWNED, {
     if constexpr (BIAS)
-      hipLaunchKernelGGL((k_attn_bias_bwd_rows_f32<L, NV, COL, OWNED, DROP>), grid, block, 0, st, (const i64*)plan->row,
-                         (const i64*)plan->indptr, eid, (const i64*)plan->indices, own, xt, st4, b, out0, out1, db,
-                         n_chunks, (int)geo.cpg, drop_if_arg<DROP>(drop));
+      hipLaunchKernelGGL((k_attn_bias_bwd_rows_f32<L, NV, COL, OWNED, DROP>), grid, block, 0, st, g.row, g.indptr, eid,
+                         g.indices, own, xt, st4, b, out0, out1, db, n_chunks, (int)geo.cpg, drop_if_arg<DROP>(drop));
     else
-      hipLaunchKernelGGL((k_attn_bwd_rows_f32<L, NV, COL, OWNED, DROP>), grid, block, 0, st, (const i64*)plan->row,
-                         (const i64*)plan->indptr, (const i64*)plan->indices, own, xt, st4, out0, out1, n_chunks,
-                         (int)geo.cpg, drop_if_arg<DROP>(drop));
+      hipLaunchKernelGGL((k_attn_bwd_rows_f32<L, NV, COL, OWNED, DROP>), grid, block, 0, st, g.row, g.indptr, g.indices,
+                         own, xt, st4, out0, out1, n_chunks, (int)geo.cpg, drop_if_arg<DROP>(drop));
   }));
   GO_LAUNCH_CHECK();
   return GRAPHOP_OK;
@@ -266,17 +265,16 @@ int attn_bias_add(int dtype, void* s, const void* b, i64 n, hipStream_t st) {
 }
 
 // y = x * m over the row-major chunks (k_attn_drop_apply), in place or not
-int attn_drop_apply(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid, const int64_t* indices,
-                    const void* x, void* y, i64 n_chunks, i64 n_edges, i64 h, i64 head0, const HostDrop& drop,
+int attn_drop_apply(int dtype, const Csr& g, const void* x, void* y, i64 h, i64 head0, const HostDrop& drop,
                     hipStream_t st) {
-  if (n_chunks == 0 || n_edges * h == 0) return GRAPHOP_OK;
+  const i64 n_chunks = g.n_chunks;
+  if (n_chunks == 0 || g.n_edges * h == 0) return GRAPHOP_OK;
   ProfScope prof("attn_drop_apply", st, "k_attn_drop_apply");
   const unsigned nb = (unsigned)ceil_div(n_chunks, kGenericWavesPerBlock);
   auto launch = [&](auto zero) {
     using T = decltype(zero);
-    hipLaunchKernelGGL((k_attn_drop_apply<T>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)row,
-                       (const i64*)indptr, (const i64*)eid, (const i64*)indices, (const T*)x, (T*)y, n_chunks, h, head0,
-                       drop.as<T>());
+    hipLaunchKernelGGL((k_attn_drop_apply<T>), dim3(nb), dim3(kGenericBlock), 0, st, g.row, g.indptr, g.eid, g.indices,
+                       (const T*)x, (T*)y, n_chunks, h, head0, drop.as<T>());
   };
   if (dtype == GRAPHOP_F32) launch(0.f);
   else launch(0.0);
@@ -289,17 +287,16 @@ int attn_drop_apply(int dtype, const int64_t* row, const int64_t* indptr, const 
 // edge id); one head without on the walk (kernels_attn_walk.h).  The contract of the three: 1 = launched (dry_run:
 // applies), 0 = does not apply, < 0 = error, *needed = the workspace.  biased with b == NULL: a dry run of the op with a
 // bias.  Needs a plan of the call's arrays and n_edges * h > 0.
-int attn_fused_forward(const graphop_plan* pm, const i64* eid, i64 n_chunks, i64 n_edges, i64 n_q, i64 n_k, i64 h, i64 d,
-                       int dtype, const void* Q, const void* K, const void* V, bool biased, const void* b, void* o,
+int attn_fused_forward(const Csr& g, i64 n_q, i64 n_k, i64 h, i64 d, int dtype, const void* Q, const void* K, const void* V, bool biased, const void* b, void* o,
                        void* stats, void* ws, i64 ws_bytes, hipStream_t st, bool dry_run, size_t* needed,
                        const HostDrop* drop = nullptr, i64 head0 = 0, const AttnDrop* hd = nullptr) {
   if (h > 1)
-    return attn_heads_fwd_rows(pm, eid, n_chunks, n_edges, n_q, n_k, h, d, dtype, Q, K, V, b, o, stats, ws, ws_bytes, st,
+    return attn_heads_fwd_rows(g, n_q, n_k, h, d, dtype, Q, K, V, b, o, stats, ws, ws_bytes, st,
                                dry_run, needed, drop, head0);
   if (biased)
-    return attn_bias_fwd_rows(pm, eid, n_chunks, n_edges, n_q, n_k, h, d, dtype, Q, K, V, b, o, stats, ws, ws_bytes, st,
+    return attn_bias_fwd_rows(g, n_q, n_k, h, d, dtype, Q, K, V, b, o, stats, ws, ws_bytes, st,
                               dry_run, needed, hd);
-  return attn_fwd_walk(pm, n_q, n_k, h, d, dtype, Q, K, V, o, stats, ws, ws_bytes, st, dry_run, needed, hd);
+  return attn_fwd_walk(g.plan, n_q, n_k, h, d, dtype, Q, K, V, o, stats, ws, ws_bytes, st, dry_run, needed, hd);
 }
 
 // The form of a call's backward: the several-head chunk-driver passes (attention_heads.hip), the window-owner passes
@@ -334,8 +331,11 @@ int attn_workspace_bytes(const char* fn, int dtype, int backward, int64_t n_edge
     size_t need = 0;
     int fw = 0;
     if (plan_r && n_edges * h > 0)
-      fw = attn_fused_forward(plan_r, nullptr, plan_r->info.n_chunks, n_edges, n_q, n_k, h, d, dtype, nullptr, nullptr,
-                              nullptr, bias, nullptr, nullptr, nullptr, nullptr, 0, st, /*dry_run=*/true, &need);
+      // (the plan's own arrays: the plan of a forward with this n_edges, or of none)
+      fw = attn_fused_forward(Csr(plan_r->row, plan_r->indptr, plan_r->eid, plan_r->indices, plan_r->info.n_chunks,
+                                  n_edges, plan_r),
+                              n_q, n_k, h, d, dtype, nullptr, nullptr, nullptr, bias, nullptr, nullptr, nullptr, nullptr, 0,
+                              st, /*dry_run=*/true, &need);
     if (fw < 0) return -fw;
     // the one-pass forward only needs the piece records of shared rows; the composed forward keeps s and a here
     *bytes_out = fw == 1 ? (int64_t)need : (int64_t)SlowWs(nullptr, 2, es, n_edges, h, soft_rows_of(plan_r, n_q)).total;
@@ -398,15 +398,15 @@ int attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t* i
     GO_PTR(fn, stats);
     GO_HIP(zero_async(stats, es * (size_t)(n_q * h * 2), st));   // rows without edges: (0, 0)
   }
-  const graphop_plan* pm = plan_matches_full(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
-                                             (const i64*)indices, n_chunks, n_edges) ? plan : nullptr;
+  const Csr g(row, indptr, eid, indices, n_chunks, n_edges, plan);
+  const graphop_plan* pm = g.plan;
   // ONE fused pass where it applies: s and a never leave the chip; its workspace (piece records of the rows that bins or
   // lane groups share) is what the call's workspace query reported
   if (pm && n_edges * h > 0) {
     GO_PTR(fn, Q); GO_PTR(fn, K); GO_PTR(fn, V); GO_PTR(fn, o);
     size_t need = 0;
     auto fused_fwd = [&](void* w, int64_t w_bytes, bool dry_run, size_t* needed) {
-      return attn_fused_forward(pm, (const i64*)eid, n_chunks, n_edges, n_q, n_k, h, d, dtype, Q, K, V, bias != nullptr,
+      return attn_fused_forward(g, n_q, n_k, h, d, dtype, Q, K, V, bias != nullptr,
                                 bias ? bias->b : nullptr, o, stats, w, w_bytes, st, dry_run, needed, drop, head0, c.hdp);
     };
     const int ok = fused_fwd(nullptr, 0, /*dry_run=*/true, &need);
@@ -427,10 +427,9 @@ int attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t* i
                                       n_k, h, d, pm, stream));
   if (bias) GO_TRY(attn_bias_add(dtype, s, bias->b, n_edges * h, st));
   if (n_edges * h > 0)
-    GO_TRY(softmax_forward_stats(dtype, (const i64*)row, (const i64*)indptr, (const i64*)eid, s, a,
-                                 n_chunks, n_edges, h, soft_rows ? ws.soft : nullptr, soft_rows, pm, st,
-                                 stats));
-  if (drop) GO_TRY(attn_drop_apply(dtype, row, indptr, eid, indices, a, a, n_chunks, n_edges, h, head0, *drop, st));
+    GO_TRY(softmax_forward_stats(dtype, Csr(row, indptr, eid, nullptr, n_chunks, n_edges, pm), s, a, h,
+                                 soft_rows ? ws.soft : nullptr, soft_rows, st, stats));
+  if (drop) GO_TRY(attn_drop_apply(dtype, g, a, a, h, head0, *drop, st));
   return graphop_vector_spmm_forward(dtype, row, indptr, eid, indices, a, V, o, n_chunks, n_edges, n_k,
                                      n_q, h, d, pm, stream);
 }
@@ -451,10 +450,9 @@ int attn_backward(const char* fn, int dtype, const int64_t* row, const int64_t* 
   const int64_t head0 = c.head0;
   hipStream_t st = c.st;
   const size_t es = esize(dtype);
-  const graphop_plan* pr = plan_matches_full(plan_r, (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r,
-                                             (const i64*)indices_r, n_row_chunks, n_edges) ? plan_r : nullptr;
-  const graphop_plan* pc = plan_matches_full(plan_c, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c,
-                                             (const i64*)indices_c, n_col_chunks, n_edges) ? plan_c : nullptr;
+  const Csr gr(row, indptr_r, eid_r, indices_r, n_row_chunks, n_edges, plan_r, "row", "indptr_r", "eid_r", "indices_r");
+  const Csr gc(col, indptr_c, eid_c, indices_c, n_col_chunks, n_edges, plan_c, "col", "indptr_c", "eid_c", "indices_c");
+  const graphop_plan *pr = gr.plan, *pc = gc.plan;
   AttnFast af;
   AttnBwd form;
   GO_TRY(attn_backward_form(bias != nullptr, /*dry_run=*/false, dtype, h, d, n_edges, n_q, n_k, pr, pc, st, &af, &form));
@@ -468,7 +466,7 @@ int attn_backward(const char* fn, int dtype, const int64_t* row, const int64_t* 
     GO_PTR(fn, Q); GO_PTR(fn, K); GO_PTR(fn, V); GO_PTR(fn, o); GO_PTR(fn, stats); GO_PTR(fn, dO);
     GO_PTR(fn, dQ); GO_PTR(fn, dK); GO_PTR(fn, dV);
     if (form == AttnBwd::Heads)
-      return attn_heads_backward(pr, pc, (const i64*)eid_r, (const i64*)eid_c, n_row_chunks, n_col_chunks, n_q, n_k, h, d, Q,
+      return attn_heads_backward(gr, gc, n_q, n_k, h, d, Q,
                                  K, V, b, o, stats, dO, dQ, dK, dV, db, workspace, st, drop, head0);
     GO_HIP(zero_async(dQ, sizeof(float) * (size_t)(n_q * F), st));
     GO_HIP(zero_async(dK, sizeof(float) * (size_t)(n_k * F), st));
@@ -496,12 +494,10 @@ int attn_backward(const char* fn, int dtype, const int64_t* row, const int64_t* 
         return GRAPHOP_OK;
       }
       GO_DISPATCH_BOOL(bias != nullptr, BIAS, {
-        GO_TRY((launch_attn_rows<false, DROP, BIAS>(BIAS ? "attn_bias_rows_row" : "attn_rows_row", pr, eid_arg(pr, eid_r),
-                                                    n_row_chunks, (int)F, ws.qdo, ws.kv, ws.st4, b, (float*)dQ, nullptr,
-                                                    db, c.hdp, st)));
-        GO_TRY((launch_attn_rows<true, DROP, BIAS>(BIAS ? "attn_bias_rows_col" : "attn_rows_col", pc, eid_arg(pc, eid_c),
-                                                   n_col_chunks, (int)F, ws.kv, ws.qdo, ws.st4, b, (float*)dK, (float*)dV,
-                                                   nullptr, c.hdp, st)));
+        GO_TRY((launch_attn_rows<false, DROP, BIAS>(BIAS ? "attn_bias_rows_row" : "attn_rows_row", gr, (int)F, ws.qdo,
+                                                    ws.kv, ws.st4, b, (float*)dQ, nullptr, db, c.hdp, st)));
+        GO_TRY((launch_attn_rows<true, DROP, BIAS>(BIAS ? "attn_bias_rows_col" : "attn_rows_col", gc, (int)F, ws.kv,
+                                                   ws.qdo, ws.st4, b, (float*)dK, (float*)dV, nullptr, c.hdp, st)));
       });
     });
     return GRAPHOP_OK;
@@ -525,13 +521,13 @@ int attn_backward(const char* fn, int dtype, const int64_t* row, const int64_t* 
   // with dropout: am = a * m feeds the SpMM backward, and the gradient that comes back is that of am: da = d_am * m
   const void* w = a;
   if (drop) {
-    GO_TRY(attn_drop_apply(dtype, row, indptr_r, eid_r, indices_r, a, am, n_row_chunks, n_edges, h, head0, *drop, st));
+    GO_TRY(attn_drop_apply(dtype, gr, a, am, h, head0, *drop, st));
     w = am;
   }
   GO_TRY(graphop_vector_spmm_backward(dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
                                       indices_c, w, dO, V, da, dV, n_row_chunks, n_col_chunks, n_edges,
                                       n_k, n_q, h, d, pr, pc, stream));
-  if (drop) GO_TRY(attn_drop_apply(dtype, row, indptr_r, eid_r, indices_r, da, da, n_row_chunks, n_edges, h, head0, *drop, st));
+  if (drop) GO_TRY(attn_drop_apply(dtype, gr, da, da, h, head0, *drop, st));
   GO_TRY(graphop_sparse_softmax_backward(dtype, row, indptr_r, eid_r, a, da, ds, n_row_chunks, n_edges, h,
                                          soft_rows ? ws.soft : nullptr, soft_rows, pr, stream));
   return graphop_maskedmm_csr_backward(dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,

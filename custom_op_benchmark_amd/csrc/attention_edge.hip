@@ -25,7 +25,7 @@ struct EdgeForm {
     GO_CHECK_ARG(n_edges * h * d == 0 || x.xe != nullptr, "%s: xe is NULL", fn);
     return GRAPHOP_OK;
   }
-  static bool fast_ok(const Rows& x, i64, bool backward) { return a16(x.xe) && (!backward || a16(x.dxe)); }
+  static bool fast_ok(const Rows& x, i64, bool backward) { return aligned16(x.xe) && (!backward || aligned16(x.dxe)); }
   static bool row_fast_ok(const Rows&, i64) { return true; }
   static size_t ws_tail(const Rows&, i64) { return 0; }
   static int grad_fill(const Rows&, size_t, i64, bool, hipStream_t) { return GRAPHOP_OK; }

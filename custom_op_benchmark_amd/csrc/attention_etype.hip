@@ -36,7 +36,7 @@ struct EtypeForm {
     return GRAPHOP_OK;
   }
   static bool fast_ok(const Rows& x, i64 F, bool backward) {
-    return x.n_types < 0x7fffffffLL / (F > 0 ? F : 1) && a16(x.R) && a16(x.etype) && (!backward || a16(x.dR));
+    return x.n_types < 0x7fffffffLL / (F > 0 ? F : 1) && aligned16(x.R) && aligned16(x.etype) && (!backward || aligned16(x.dR));
   }
   // the row pass may sum dR on chip
   static bool table_ok(const Rows& x, i64 F) { return x.n_types <= attn_etype_max_types(F); }

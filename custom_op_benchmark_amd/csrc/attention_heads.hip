@@ -65,18 +65,18 @@ struct HeadsBwdWs {
 };
 
 template <bool COL>
-int launch_heads_rows(const char* tag, const graphop_plan* plan, const i64* eid, i64 n_chunks, i64 h, i64 d,
-                      const float* own, const float* xt, const float4* st4, const float* b, float* out0, float* out1,
-                      float* db, const AttnHeadsDrop* drop, hipStream_t st) {
+int launch_heads_rows(const char* tag, const Csr& g, i64 h, i64 d, const float* own, const float* xt, const float4* st4,
+                      const float* b, float* out0, float* out1, float* db, const AttnHeadsDrop* drop, hipStream_t st) {
+  const i64 n_chunks = g.n_chunks;
   if (n_chunks == 0) return GRAPHOP_OK;
   ProfScope prof(tag, st, "k_attn_heads_bwd_rows_f32");
-  const bool owned = plan->info.rows_sorted != 0, dropped = drop != nullptr, biased = b != nullptr;
+  const bool owned = g.owned(), dropped = drop != nullptr, biased = b != nullptr;
   const ChunkGeometry geo = attn_rows_geometry(n_chunks);
   GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, GO_DISPATCH_BOOL(biased, BIAS, {
     if constexpr (H > 1)
       hipLaunchKernelGGL((k_attn_heads_bwd_rows_f32<H, D, COL, OWNED, DROP, BIAS>), dim3(geo.blocks), dim3(kFastBlock), 0,
-                         st, (const i64*)plan->row, (const i64*)plan->indptr, eid, (const i64*)plan->indices, own, xt, st4,
-                         b, out0, out1, db, n_chunks, (int)geo.cpg, drop_if_arg<DROP>(drop));
+                         st, g.row, g.indptr, g.eid_or_null(), g.indices, own, xt, st4, b, out0, out1, db, n_chunks,
+                         (int)geo.cpg, drop_if_arg<DROP>(drop));
   }))));
   GO_LAUNCH_CHECK();
   return GRAPHOP_OK;
@@ -95,16 +95,17 @@ bool attn_heads_bwd_ok(int dtype, i64 h, i64 d, i64 n_edges, i64 n_q, i64 n_k, c
 
 size_t attn_heads_bwd_workspace(i64 n_q, i64 n_k, i64 h, i64 d) { return HeadsBwdWs(n_q, n_k, h, h * d).total; }
 
-int attn_heads_fwd_rows(const graphop_plan* plan, const i64* eid, i64 n_chunks, i64 n_edges, i64 n_q, i64 n_k, i64 h,
-                        i64 d, int dtype, const void* Q, const void* K, const void* V, const void* b, void* o,
-                        void* stats, void* ws, i64 ws_bytes, hipStream_t st, bool dry_run, size_t* ws_needed,
-                        const HostDrop* hdrop, i64 head0) {
+int attn_heads_fwd_rows(const Csr& g, i64 n_q, i64 n_k, i64 h, i64 d, int dtype, const void* Q, const void* K,
+                        const void* V, const void* b, void* o, void* stats, void* ws, i64 ws_bytes, hipStream_t st,
+                        bool dry_run, size_t* ws_needed, const HostDrop* hdrop, i64 head0) {
+  const graphop_plan* plan = g.plan;
+  const i64 n_chunks = g.n_chunks, n_edges = g.n_edges;
   if (ws_needed) *ws_needed = 0;
   if (hdrop && head0 + h >= 0x7fffffffLL) return 0;
   const AttnHeadsDrop hd{hdrop ? hdrop->as<float>() : DropArgs<float>{}, (int)head0};
   const AttnHeadsDrop* drop = hdrop ? &hd : nullptr;
   if (h <= 1 || n_chunks == 0 || !attn_heads_plan_ok(dtype, h, d, n_edges, n_q, n_k, plan)) return 0;
-  if (!plan->info.rows_sorted || n_q >= kWalkRowMask) return 0;
+  if (!g.owned() || n_q >= kWalkRowMask) return 0;
   if (tuning().attn_heads < 0 && !attn_heads_auto_ok(h, d, n_edges, n_q, n_k, plan, st)) return 0;
   const i64 F = h * d;
   const ChunkGeometry geo = attn_rows_geometry(n_chunks);
@@ -119,14 +120,13 @@ int attn_heads_fwd_rows(const graphop_plan* plan, const i64* eid, i64 n_chunks, 
   a.p_row = w.p_row; a.p_ml = w.p_ml; a.p_o = w.p_o;
   if (zero_async(o, sizeof(float) * (size_t)(n_q * F), st) != hipSuccess) return -GRAPHOP_ERR_HIP;
   attn_pieces_fill("attn_heads_fwd_setup", w, kAttnNegBig, st);
-  const i64* eids = plan->info.eid_identity ? nullptr : eid;
   const bool dropped = drop != nullptr, biased = b != nullptr;
   {
     ProfScope prof("attn_heads_fwd_rows", st, "k_attn_heads_fwd_rows_f32");
     GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(dropped, DROP, GO_DISPATCH_BOOL(biased, BIAS, {
       if constexpr (H > 1)
         hipLaunchKernelGGL((k_attn_heads_fwd_rows_f32<H, D, DROP, BIAS>), dim3(geo.blocks), dim3(kFastBlock), 0, st,
-                           (const i64*)plan->row, (const i64*)plan->indptr, eids, (const i64*)plan->indices, a, n_chunks,
+                           g.row, g.indptr, g.eid_or_null(), g.indices, a, n_chunks,
                            (int)geo.cpg, drop_if_arg<DROP>(drop));
     })));
   }
@@ -153,8 +153,7 @@ int attn_heads_fwd_rows(const graphop_plan* plan, const i64* eid, i64 n_chunks, 
   return 1;
 }
 
-int attn_heads_backward(const graphop_plan* pr, const graphop_plan* pc, const i64* eid_r, const i64* eid_c,
-                        i64 n_row_chunks, i64 n_col_chunks, i64 n_q, i64 n_k, i64 h, i64 d, const void* Q, const void* K,
+int attn_heads_backward(const Csr& r, const Csr& c, i64 n_q, i64 n_k, i64 h, i64 d, const void* Q, const void* K,
                         const void* V, const void* b, const void* o, const void* stats, const void* dO, void* dQ, void* dK,
                         void* dV, void* db, void* ws, hipStream_t st, const HostDrop* hdrop, i64 head0) {
   const AttnHeadsDrop hd{hdrop ? hdrop->as<float>() : DropArgs<float>{}, (int)head0};
@@ -184,11 +183,9 @@ int attn_heads_backward(const graphop_plan* pr, const graphop_plan* pc, const i6
     });
     GO_LAUNCH_CHECK();
   }
-  const i64* er = pr->info.eid_identity ? nullptr : eid_r;
-  const i64* ec = pc->info.eid_identity ? nullptr : eid_c;
-  GO_TRY((launch_heads_rows<false>("attn_heads_rows_row", pr, er, n_row_chunks, h, d, qdo, kv, st4, (const float*)b,
+  GO_TRY((launch_heads_rows<false>("attn_heads_rows_row", r, h, d, qdo, kv, st4, (const float*)b,
                                    (float*)dQ, nullptr, (float*)db, drop, st)));
-  GO_TRY((launch_heads_rows<true>("attn_heads_rows_col", pc, ec, n_col_chunks, h, d, kv, qdo, st4, (const float*)b,
+  GO_TRY((launch_heads_rows<true>("attn_heads_rows_col", c, h, d, kv, qdo, st4, (const float*)b,
                                   (float*)dK, (float*)dV, nullptr, drop, st)));
   return GRAPHOP_OK;
 }

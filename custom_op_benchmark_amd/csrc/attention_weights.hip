@@ -28,11 +28,11 @@ int graphop_attention_weights(int dtype, const int64_t* row, const int64_t* indp
   const bool slots = n_chunks > 0 && n_edges > 0 && n_q > 0 && n_k > 0 && h * d > 0;
   if (slots) { GO_PTR(fn, stats); GO_PTR(fn, a); }
   hipStream_t st = (hipStream_t)stream;
-  const graphop_plan* pm = plan_matches_full(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
-                                             (const i64*)indices, n_chunks, n_edges) ? plan : nullptr;
-  GO_TRY(gat_check_plan(fn, pm, "Q / stats", n_q, "K", n_k));
+  const Csr g(row, indptr, eid, indices, n_chunks, n_edges, plan);
+  const graphop_plan* pm = g.plan;
+  GO_TRY(Csr::check_bounds(fn, pm, "Q / stats", n_q, "K", n_k));
   if (!slots) return GRAPHOP_OK;   // nothing is written, nothing dereferenced
-  GO_PTR(fn, row); GO_PTR(fn, indptr); GO_PTR(fn, eid); GO_PTR(fn, indices); GO_PTR(fn, Q); GO_PTR(fn, K);
+  GO_TRY(g.require(fn)); GO_PTR(fn, Q); GO_PTR(fn, K);
 
   if (xe == nullptr) {
     // s into a.  A plan that covers every edge id lets the SDDMM entry point choose among all its drivers (any fill it
@@ -46,11 +46,11 @@ int graphop_attention_weights(int dtype, const int64_t* row, const int64_t* indp
                                                   n_q, n_k, h, d, stream));
     ProfScope prof("attn_weights_norm", st, "k_attn_weights_norm");
     const ChunkGeometry geo = chunk_geometry(n_chunks, kGatGroup, 16);
-    const i64* ids = pm ? eid_arg(pm, eid) : (const i64*)eid;
+    const i64* ids = pm ? g.eid_or_null() : g.eid;
     const bool bias = b != nullptr;
     GO_DISPATCH_FLOAT(dtype, T, GO_DISPATCH_BOOL(bias, BIAS, {
-      hipLaunchKernelGGL((k_attn_weights_norm<T, BIAS>), dim3(geo.blocks), dim3(kFastBlock), 0, st, (const i64*)row,
-                         (const i64*)indptr, ids, (const T*)stats, (const T*)b, (T*)a, n_chunks, (i64)h, (int)geo.cpg);
+      hipLaunchKernelGGL((k_attn_weights_norm<T, BIAS>), dim3(geo.blocks), dim3(kFastBlock), 0, st, g.row,
+                         g.indptr, ids, (const T*)stats, (const T*)b, (T*)a, n_chunks, (i64)h, (int)geo.cpg);
     }));
     GO_LAUNCH_CHECK();
     return GRAPHOP_OK;
@@ -61,15 +61,15 @@ int graphop_attention_weights(int dtype, const int64_t* row, const int64_t* indp
     const int cpg = gat_cpg(n_chunks, tuning().sddmm_cpg);
     GO_DISPATCH_GAT_HD(h, d, {
       hipLaunchKernelGGL((k_attn_weights_xe_f32<H, D>), dim3((unsigned)gat_grid(n_chunks, cpg)), dim3(kFastBlock), 0, st,
-                         (const i64*)row, (const i64*)indptr, eid_arg(pm, eid), (const i64*)indices, (const float*)Q,
+                         g.row, g.indptr, g.eid_or_null(), g.indices, (const float*)Q,
                          (const float*)K, (const float*)stats, (const float*)xe, (float*)a, n_chunks, cpg);
     });
   } else {
     ProfScope prof("attn_weights_xe_generic", st, "k_attn_weights_xe_generic");
     const dim3 grid((unsigned)ceil_div(n_chunks, kGenericWavesPerBlock));
     GO_DISPATCH_FLOAT(dtype, T, {
-      hipLaunchKernelGGL((k_attn_weights_xe_generic<T>), grid, dim3(kGenericBlock), 0, st, (const i64*)row,
-                         (const i64*)indptr, (const i64*)eid, (const i64*)indices, (const T*)Q, (const T*)K,
+      hipLaunchKernelGGL((k_attn_weights_xe_generic<T>), grid, dim3(kGenericBlock), 0, st, g.row,
+                         g.indptr, g.eid, g.indices, (const T*)Q, (const T*)K,
                          (const T*)stats, (const T*)xe, (T*)a, n_chunks, (i64)h, (i64)d);
     });
   }

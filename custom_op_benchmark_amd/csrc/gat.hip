@@ -33,10 +33,11 @@ inline bool gat_fast_ok(int dtype, i64 h, i64 E, i64 n_l, i64 n_r, const void* p
 
 // One backward pass (ROW: del over the row-major chunks; else der over the column-major chunks).
 template <bool ROW>
-int gat_bwd_pass(int dtype, const i64* seg, const i64* indptr, const i64* eid, const i64* indices, const void* el,
-                 const void* er, const void* dy, void* out, i64 C, i64 E, i64 n_l, i64 n_r, i64 h, double slope,
-                 const graphop_plan* plan, hipStream_t st) {
-  if (plan && gat_fast_ok(dtype, h, E, n_l, n_r, el, er, dy, out)) {
+int gat_bwd_pass(int dtype, const Csr& g, const void* el, const void* er, const void* dy, void* out, i64 n_l, i64 n_r,
+                 i64 h, double slope, hipStream_t st) {
+  const i64 *seg = g.row, *indptr = g.indptr, *eid = g.eid, *indices = g.indices;
+  const i64 C = g.n_chunks;
+  if (g.plan && gat_fast_ok(dtype, h, g.n_edges, n_l, n_r, el, er, dy, out)) {
     ProfScope prof(ROW ? "gat_bwd_row" : "gat_bwd_col", st, ROW ? "k_gat_bwd_row_f32" : "k_gat_bwd_col_f32");
     GO_DISPATCH_GAT_H(h, {
       constexpr int G = GatCfg<H>::G;
@@ -81,34 +82,31 @@ int graphop_gat_scores_forward(int dtype, const int64_t* row, const int64_t* ind
   hipStream_t st = (hipStream_t)stream;
   if (n_edges == 0) return GRAPHOP_OK;
   GO_PTR(fn, y);
-  const graphop_plan* pm = plan_matches_full(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
-                                             (const i64*)indices, n_chunks, n_edges) ? plan : nullptr;
-  GO_TRY(gat_check_plan(fn, pm, "el", n_l, "er", n_r));
-  const bool covered = pm && pm->info.full_coverage && pm->info.eid_identity && pm->info.indptr_monotone;
+  const Csr g(row, indptr, eid, indices, n_chunks, n_edges, plan);
+  const graphop_plan* pm = g.plan;
+  GO_TRY(Csr::check_bounds(fn, pm, "el", n_l, "er", n_r));
+  const bool covered = g.covered();
   if (!covered) GO_HIP(zero_async(y, esize(dtype) * (size_t)(n_edges * h), st));
   if (n_chunks == 0) return GRAPHOP_OK;
-  GO_PTR(fn, row); GO_PTR(fn, indptr); GO_PTR(fn, eid); GO_PTR(fn, indices); GO_PTR(fn, el); GO_PTR(fn, er);
+  GO_TRY(g.require(fn)); GO_PTR(fn, el); GO_PTR(fn, er);
   if (pm && gat_fast_ok(dtype, h, n_edges, n_l, n_r, el, er, y, nullptr)) {
     ProfScope prof("gat_fwd", st, "k_gat_fwd_f32");
     GO_DISPATCH_GAT_H(h, {
       constexpr int G = GatCfg<H>::G;
       const int cpg = gat_cpg(n_chunks, tuning().sddmm_cpg, G);
       const unsigned nb = (unsigned)gat_grid(n_chunks, cpg, G);
-      hipLaunchKernelGGL((k_gat_fwd_f32<H>), dim3(nb), dim3(kFastBlock), 0, st, (const i64*)row, (const i64*)indptr,
-                         (const i64*)eid, (const i64*)indices, (const float*)el, (const float*)er, (float*)y, n_chunks,
-                         cpg, (float)negative_slope);
+      hipLaunchKernelGGL((k_gat_fwd_f32<H>), dim3(nb), dim3(kFastBlock), 0, st, g.row, g.indptr, g.eid, g.indices,
+                         (const float*)el, (const float*)er, (float*)y, n_chunks, cpg, (float)negative_slope);
     });
   } else {
     ProfScope prof("gat_fwd", st, "k_gat_fwd_generic");
     const unsigned nb = (unsigned)ceil_div(n_chunks, kGenericWavesPerBlock);
     if (dtype == GRAPHOP_F32)
-      hipLaunchKernelGGL((k_gat_fwd_generic<float>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)row,
-                         (const i64*)indptr, (const i64*)eid, (const i64*)indices, (const float*)el, (const float*)er,
-                         (float*)y, n_chunks, h, (float)negative_slope);
+      hipLaunchKernelGGL((k_gat_fwd_generic<float>), dim3(nb), dim3(kGenericBlock), 0, st, g.row, g.indptr, g.eid,
+                         g.indices, (const float*)el, (const float*)er, (float*)y, n_chunks, h, (float)negative_slope);
     else
-      hipLaunchKernelGGL((k_gat_fwd_generic<double>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)row,
-                         (const i64*)indptr, (const i64*)eid, (const i64*)indices, (const double*)el, (const double*)er,
-                         (double*)y, n_chunks, h, negative_slope);
+      hipLaunchKernelGGL((k_gat_fwd_generic<double>), dim3(nb), dim3(kGenericBlock), 0, st, g.row, g.indptr, g.eid,
+                         g.indices, (const double*)el, (const double*)er, (double*)y, n_chunks, h, negative_slope);
   }
   GO_LAUNCH_CHECK();
   return GRAPHOP_OK;
@@ -124,12 +122,10 @@ int graphop_gat_scores_backward(int dtype, const int64_t* row, const int64_t* in
   GO_TRY(gat_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_l, n_r, h));
   hipStream_t st = (hipStream_t)stream;
   const size_t es = esize(dtype);
-  const graphop_plan* pr = plan_matches_full(plan_r, (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r,
-                                             (const i64*)indices_r, n_row_chunks, n_edges) ? plan_r : nullptr;
-  const graphop_plan* pc = plan_matches_full(plan_c, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c,
-                                             (const i64*)indices_c, n_col_chunks, n_edges) ? plan_c : nullptr;
-  GO_TRY(gat_check_plan(fn, pr, "el / del", n_l, "er", n_r));
-  GO_TRY(gat_check_plan(fn, pc, "er / der", n_r, "el", n_l));
+  const Csr r(row, indptr_r, eid_r, indices_r, n_row_chunks, n_edges, plan_r, "row", "indptr_r", "eid_r", "indices_r");
+  const Csr c(col, indptr_c, eid_c, indices_c, n_col_chunks, n_edges, plan_c, "col", "indptr_c", "eid_c", "indices_c");
+  GO_TRY(Csr::check_bounds(fn, r.plan, "el / del", n_l, "er", n_r));
+  GO_TRY(Csr::check_bounds(fn, c.plan, "er / der", n_r, "el", n_l));
   // an output whose orientation has no chunks may be NULL: that half of the op is skipped
   if (n_l > 0 && !(del == nullptr && n_row_chunks == 0)) {
     GO_PTR(fn, del);
@@ -141,16 +137,14 @@ int graphop_gat_scores_backward(int dtype, const int64_t* row, const int64_t* in
   }
   if (n_edges == 0) return GRAPHOP_OK;
   if (n_row_chunks > 0) {
-    GO_PTR(fn, row); GO_PTR(fn, indptr_r); GO_PTR(fn, eid_r); GO_PTR(fn, indices_r);
+    GO_TRY(r.require(fn));
     GO_PTR(fn, el); GO_PTR(fn, er); GO_PTR(fn, dy); GO_PTR(fn, del);
-    GO_TRY(gat_bwd_pass<true>(dtype, (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r, (const i64*)indices_r,
-                              el, er, dy, del, n_row_chunks, n_edges, n_l, n_r, h, negative_slope, pr, st));
+    GO_TRY(gat_bwd_pass<true>(dtype, r, el, er, dy, del, n_l, n_r, h, negative_slope, st));
   }
   if (n_col_chunks > 0) {
-    GO_PTR(fn, col); GO_PTR(fn, indptr_c); GO_PTR(fn, eid_c); GO_PTR(fn, indices_c);
+    GO_TRY(c.require(fn));
     GO_PTR(fn, el); GO_PTR(fn, er); GO_PTR(fn, dy); GO_PTR(fn, der);
-    GO_TRY(gat_bwd_pass<false>(dtype, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c, (const i64*)indices_c,
-                               el, er, dy, der, n_col_chunks, n_edges, n_l, n_r, h, negative_slope, pc, st));
+    GO_TRY(gat_bwd_pass<false>(dtype, c, el, er, dy, der, n_l, n_r, h, negative_slope, st));
   }
   return GRAPHOP_OK;
 }

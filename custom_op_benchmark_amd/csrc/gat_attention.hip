@@ -87,18 +87,18 @@ int graphop_edge_dropout_mask(int dtype, const int64_t* row, const int64_t* indp
   hipStream_t st = (hipStream_t)stream;
   if (n_edges == 0) return GRAPHOP_OK;
   GO_PTR(fn, y);
-  const graphop_plan* pm = plan_matches_full(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
-                                             (const i64*)indices, n_chunks, n_edges) ? plan : nullptr;
-  GO_TRY(gat_check_plan(fn, pm, "the row-major rows", n_l, "the neighbours", n_r));
-  const bool covered = pm && pm->info.full_coverage && pm->info.eid_identity && pm->info.indptr_monotone;
+  const Csr g(row, indptr, eid, indices, n_chunks, n_edges, plan);
+  const graphop_plan* pm = g.plan;
+  GO_TRY(Csr::check_bounds(fn, pm, "the row-major rows", n_l, "the neighbours", n_r));
+  const bool covered = g.covered();
   if (!covered) GO_HIP(zero_async(y, esize(dtype) * (size_t)(n_edges * h), st));   // edges no slot names get m = 0
   if (n_chunks == 0) return GRAPHOP_OK;
-  GO_PTR(fn, row); GO_PTR(fn, indptr); GO_PTR(fn, eid); GO_PTR(fn, indices);
+  GO_TRY(g.require(fn));
   ProfScope prof("edge_dropout_mask", st, "k_edge_dropout_mask");
   const unsigned nb = (unsigned)ceil_div(n_chunks, kGenericWavesPerBlock);
   GO_DISPATCH_FLOAT(dtype, T, {
-    hipLaunchKernelGGL((k_edge_dropout_mask<T>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)row,
-                       (const i64*)indptr, (const i64*)eid, (const i64*)indices, (T*)y, n_chunks, h, drop.as<T>());
+    hipLaunchKernelGGL((k_edge_dropout_mask<T>), dim3(nb), dim3(kGenericBlock), 0, st, g.row,
+                       g.indptr, g.eid, g.indices, (T*)y, n_chunks, h, drop.as<T>());
   });
   GO_LAUNCH_CHECK();
   return GRAPHOP_OK;

@@ -32,29 +32,28 @@ int graphop_gatv2_scores_forward(int dtype, const int64_t* row, const int64_t* i
   hipStream_t st = (hipStream_t)stream;
   if (n_edges == 0) return GRAPHOP_OK;
   GO_PTR(fn, y);
-  const graphop_plan* pm = plan_matches_full(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
-                                             (const i64*)indices, n_chunks, n_edges) ? plan : nullptr;
-  GO_TRY(gat_check_plan(fn, pm, "xl", n_l, "xr", n_r));
-  const bool covered = pm && pm->info.full_coverage && pm->info.eid_identity && pm->info.indptr_monotone;
+  const Csr g(row, indptr, eid, indices, n_chunks, n_edges, plan);
+  const graphop_plan* pm = g.plan;
+  GO_TRY(Csr::check_bounds(fn, pm, "xl", n_l, "xr", n_r));
+  const bool covered = g.covered();
   if (!covered) GO_HIP(zero_async(y, esize(dtype) * (size_t)(n_edges * h), st));
   if (n_chunks == 0) return GRAPHOP_OK;
-  GO_PTR(fn, row); GO_PTR(fn, indptr); GO_PTR(fn, eid); GO_PTR(fn, indices); GO_PTR(fn, xl); GO_PTR(fn, xr);
-  GO_PTR(fn, att);
+  GO_TRY(g.require(fn)); GO_PTR(fn, xl); GO_PTR(fn, xr); GO_PTR(fn, att);
   if (pm && gat_hd_fast_ok(dtype, h, d, n_edges, n_l, n_r, {xl, xr, att})) {
     ProfScope prof("gatv2_fwd", st, "k_gatv2_fwd_f32");
     const int cpg = gat_cpg(n_chunks, tuning().sddmm_cpg);
     GO_DISPATCH_GAT_HD(h, d, {
       hipLaunchKernelGGL((k_gatv2_fwd_f32<H, D>), dim3((unsigned)gat_grid(n_chunks, cpg)), dim3(kFastBlock), 0, st,
-                         (const i64*)row, (const i64*)indptr, (const i64*)eid, (const i64*)indices, (const float*)xl,
+                         g.row, g.indptr, g.eid, g.indices, (const float*)xl,
                          (const float*)xr, (const float*)att, (float*)y, n_chunks, cpg, (float)negative_slope);
     });
   } else {
     ProfScope prof("gatv2_fwd", st, "k_gatv2_fwd_generic");
     const unsigned nb = (unsigned)ceil_div(n_chunks, kGenericWavesPerBlock);
     GO_DISPATCH_FLOAT(dtype, T, {
-      hipLaunchKernelGGL((k_gatv2_fwd_generic<T>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)row,
-                         (const i64*)indptr, (const i64*)eid, (const i64*)indices, (const T*)xl, (const T*)xr,
-                         (const T*)att, (T*)y, n_chunks, h, d, gatv2_dp(d), (T)negative_slope);
+      hipLaunchKernelGGL((k_gatv2_fwd_generic<T>), dim3(nb), dim3(kGenericBlock), 0, st, g.row, g.indptr, g.eid,
+                         g.indices, (const T*)xl, (const T*)xr, (const T*)att, (T*)y, n_chunks, h, d, gatv2_dp(d),
+                         (T)negative_slope);
     });
   }
   GO_LAUNCH_CHECK();
@@ -80,23 +79,24 @@ int graphop_gatv2_scores_backward(int dtype, const int64_t* row, const int64_t* 
   GO_CHECK_ARG(workspace_bytes >= 0 && (size_t)workspace_bytes >= need,
                "%s: workspace of %lld bytes needed (min(ceil(n_row_chunks / 16), 8192) * h * d values), got %lld", fn,
                (long long)need, (long long)workspace_bytes);
-  const graphop_plan *pr, *pc;
-  GO_TRY(gatv2_bwd_open(fn, dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, dxl, dxr, datt,
-                        n_row_chunks, n_col_chunks, n_edges, n_l, n_r, f, plan_r, plan_c, st, &pr, &pc));
+  const Csr r(row, indptr_r, eid_r, indices_r, n_row_chunks, n_edges, plan_r, "row", "indptr_r", "eid_r", "indices_r");
+  const Csr c(col, indptr_c, eid_c, indices_c, n_col_chunks, n_edges, plan_c, "col", "indptr_c", "eid_c", "indices_c");
+  const graphop_plan *pr = r.plan, *pc = c.plan;
+  GO_TRY(gatv2_bwd_open(fn, dtype, r, c, dxl, dxr, datt, n_l, n_r, f, st));
   if (!row_slots && !col_slots) return GRAPHOP_OK;
   GO_PTR(fn, xl); GO_PTR(fn, xr); GO_PTR(fn, att); GO_PTR(fn, dy);
   if (need > 0) GO_PTR(fn, workspace);
   if (row_slots) {
-    GO_PTR(fn, row); GO_PTR(fn, indptr_r); GO_PTR(fn, eid_r); GO_PTR(fn, indices_r);
+    GO_TRY(r.require(fn));
     GO_PTR(fn, dxl); GO_PTR(fn, datt);
     const i64 C = n_row_chunks;
     if (pr && gat_hd_fast_ok(dtype, h, d, n_edges, n_l, n_r, {xl, xr, att, dxl, datt, workspace})) {
       ProfScope prof("gatv2_bwd_row", st, "k_gatv2_bwd_row_f32");
       const GatRowPass geo = gat_row_pass(C, tuning().spmm_cpg);   // n_blocks <= gat_part_rows(C)
-      const bool owned = pr->info.rows_sorted != 0;
+      const bool owned = r.owned();
       GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, {
         hipLaunchKernelGGL((k_gatv2_bwd_row_f32<H, D, OWNED>), dim3((unsigned)geo.n_blocks), dim3(kFastBlock), 0, st,
-                           (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r, (const i64*)indices_r,
+                           r.row, r.indptr, r.eid, r.indices,
                            (const float*)xl, (const float*)xr, (const float*)att, (const float*)dy, (float*)dxl,
                            (float4*)workspace, C, geo.cpg, (float)negative_slope);
       }));
@@ -107,24 +107,24 @@ int graphop_gatv2_scores_backward(int dtype, const int64_t* row, const int64_t* 
       ProfScope prof("gatv2_bwd_row", st, "k_gatv2_bwd_row_generic");
       const unsigned nb = (unsigned)ceil_div(C, kGenericWavesPerBlock);
       GO_DISPATCH_FLOAT(dtype, T, {
-        hipLaunchKernelGGL((k_gatv2_bwd_row_generic<T>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)row,
-                           (const i64*)indptr_r, (const i64*)eid_r, (const i64*)indices_r, (const T*)xl, (const T*)xr,
-                           (const T*)att, (const T*)dy, (T*)dxl, (T*)datt, C, h, d, (T)negative_slope);
+        hipLaunchKernelGGL((k_gatv2_bwd_row_generic<T>), dim3(nb), dim3(kGenericBlock), 0, st, r.row, r.indptr, r.eid,
+                           r.indices, (const T*)xl, (const T*)xr, (const T*)att, (const T*)dy, (T*)dxl, (T*)datt, C, h, d,
+                           (T)negative_slope);
       });
     }
     GO_LAUNCH_CHECK();
   }
   if (col_slots) {
-    GO_PTR(fn, col); GO_PTR(fn, indptr_c); GO_PTR(fn, eid_c); GO_PTR(fn, indices_c);
+    GO_TRY(c.require(fn));
     GO_PTR(fn, dxr);
     const i64 C = n_col_chunks;
     if (pc && gat_hd_fast_ok(dtype, h, d, n_edges, n_l, n_r, {xl, xr, att, dxr})) {
       ProfScope prof("gatv2_bwd_col", st, "k_gatv2_bwd_col_f32");
       const int cpg = gat_cpg(C, tuning().spmm_cpg);
-      const bool owned = pc->info.rows_sorted != 0;
+      const bool owned = c.owned();
       GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, {
         hipLaunchKernelGGL((k_gatv2_bwd_col_f32<H, D, OWNED>), dim3((unsigned)gat_grid(C, cpg)), dim3(kFastBlock), 0,
-                           st, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c, (const i64*)indices_c,
+                           st, c.row, c.indptr, c.eid, c.indices,
                            (const float*)xl, (const float*)xr, (const float*)att, (const float*)dy, (float*)dxr, C, cpg,
                            (float)negative_slope);
       }));
@@ -132,9 +132,9 @@ int graphop_gatv2_scores_backward(int dtype, const int64_t* row, const int64_t* 
       ProfScope prof("gatv2_bwd_col", st, "k_gatv2_bwd_col_generic");
       const unsigned nb = (unsigned)ceil_div(C, kGenericWavesPerBlock);
       GO_DISPATCH_FLOAT(dtype, T, {
-        hipLaunchKernelGGL((k_gatv2_bwd_col_generic<T>), dim3(nb), dim3(kGenericBlock), 0, st, (const i64*)col,
-                           (const i64*)indptr_c, (const i64*)eid_c, (const i64*)indices_c, (const T*)xl, (const T*)xr,
-                           (const T*)att, (const T*)dy, (T*)dxr, C, h, d, (T)negative_slope);
+        hipLaunchKernelGGL((k_gatv2_bwd_col_generic<T>), dim3(nb), dim3(kGenericBlock), 0, st, c.row, c.indptr, c.eid,
+                           c.indices, (const T*)xl, (const T*)xr, (const T*)att, (const T*)dy, (T*)dxr, C, h, d,
+                           (T)negative_slope);
       });
     }
     GO_LAUNCH_CHECK();

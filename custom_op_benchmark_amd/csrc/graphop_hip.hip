@@ -190,8 +190,6 @@ inline bool spmm_staged(int L, int NV, i64 h, i64 n_table_rows) {
   return (tuning().staged_ids & 2) && h == 1 && table_off32(n_table_rows, L, NV);
 }
 
-inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 // ---- walk drivers (kernels_walk.h) -----------------------------------------------------------------
 // The walk kernels take nearly all of a CU's LDS as dynamic shared memory: the limit is raised once per kernel function.
 inline void allow_full_lds(const void* fn) {
@@ -447,15 +445,16 @@ int attn_fwd_walk(const graphop_plan* plan, i64 n_q, i64 n_k, i64 h, i64 d, int 
 // Fused attention forward with a per-edge score bias, chunk-driver form (kernels_attn_bias_fwd.h): fp32, one head, d a
 // power of two in 16..1024, a plan with sorted rows and its neighbour ids, id ranges inside the tables.  Launch geometry:
 // attn_one_head_geometry, the chunk-driver backward's.  Workspace: 2 x groups piece records (AttnRowsFwdWs).
-int attn_bias_fwd_rows(const graphop_plan* plan, const i64* eid, i64 n_chunks, i64 n_edges, i64 n_q, i64 n_k, i64 h,
-                       i64 d, int dtype, const void* Q, const void* K, const void* V, const void* b, void* o,
-                       void* stats, void* ws, i64 ws_bytes, hipStream_t st, bool dry_run, size_t* ws_needed,
-                       const AttnDrop* drop) {
+int attn_bias_fwd_rows(const Csr& g, i64 n_q, i64 n_k, i64 h, i64 d, int dtype, const void* Q, const void* K,
+                       const void* V, const void* b, void* o, void* stats, void* ws, i64 ws_bytes, hipStream_t st,
+                       bool dry_run, size_t* ws_needed, const AttnDrop* drop) {
   const Tuning& t = tuning();
+  const graphop_plan* plan = g.plan;
+  const i64 n_chunks = g.n_chunks, n_edges = g.n_edges;
   if (ws_needed) *ws_needed = 0;
   if (!t.attn_fused || !t.attn_rows || t.force_generic || dtype != GRAPHOP_F32 || h != 1 || !plan) return 0;
   if (d % 4 != 0 || !pow2(d) || d < 16 || d > 1024 || n_edges == 0 || n_chunks == 0) return 0;
-  if (!plan->info.rows_sorted || !plan->indices) return 0;
+  if (!g.owned() || !plan->indices) return 0;
   if (plan->info.max_row >= n_q || plan->info.max_index >= n_k || n_q >= kWalkRowMask) return 0;
   const i64 F = d;
   const ChunkGeometry geo = attn_one_head_geometry(n_chunks, F);
@@ -470,17 +469,17 @@ int attn_bias_fwd_rows(const graphop_plan* plan, const i64* eid, i64 n_chunks, i
   a.p_row = w.p_row; a.p_ml = w.p_ml; a.p_o = w.p_o;
   if (zero_async(o, sizeof(float) * (size_t)(n_q * F), st) != hipSuccess) return -GRAPHOP_ERR_HIP;
   attn_pieces_fill("attn_bias_fwd_setup", w, kAttnNegBig, st);
-  const i64* eids = plan->info.eid_identity ? nullptr : eid;
+  const i64* eids = g.eid_or_null();
   {
     ProfScope prof("attn_bias_fwd_rows", st, drop ? "k_attn_bias_fwd_rows_f32<DROP>" : "k_attn_bias_fwd_rows_f32");
     GO_DISPATCH_LNV((int)F, {
       if (drop)
         hipLaunchKernelGGL((k_attn_bias_fwd_rows_f32<L, NV, true>), dim3(geo.blocks), dim3(kFastBlock), 0, st,
-                           (const i64*)plan->row, (const i64*)plan->indptr, eids, (const i64*)plan->indices, a, n_chunks,
+                           g.row, g.indptr, eids, g.indices, a, n_chunks,
                            (int)geo.cpg, *drop);
       else
         hipLaunchKernelGGL((k_attn_bias_fwd_rows_f32<L, NV, false>), dim3(geo.blocks), dim3(kFastBlock), 0, st,
-                           (const i64*)plan->row, (const i64*)plan->indptr, eids, (const i64*)plan->indices, a, n_chunks,
+                           g.row, g.indptr, eids, g.indices, a, n_chunks,
                            (int)geo.cpg, NoDrop{});
     });
   }
@@ -644,13 +643,10 @@ inline bool spmm_block_applies(int dtype, const graphop_plan* plan, i64 n_table_
 }
 // The block-dense SpMM writes every feature of every row that has a segment, with plain stores:
 // when the plan's segments are exactly the rows [0, n_out_rows) the output needs no zero fill.
-inline bool spmm_block_writes_all(int dtype, const i64* row, const i64* indptr, const i64* eid,
-                                  const i64* indices, i64 C, i64 E, const graphop_plan* plan,
-                                  i64 n_table_rows, const void* X, const void* out, i64 h, i64 d,
-                                  i64 n_out_rows) {
-  return plan_matches_full(plan, row, indptr, eid, indices, C, E) &&
-         spmm_block_applies(dtype, plan, n_table_rows, X, out, h, d) && plan->info.rows_sorted &&
-         plan->info.n_segments == n_out_rows && plan->info.max_row == n_out_rows - 1;
+inline bool spmm_block_writes_all(int dtype, const Csr& g, i64 n_table_rows, const void* X, const void* out, i64 h,
+                                  i64 d, i64 n_out_rows) {
+  return g.owned() && spmm_block_applies(dtype, g.plan, n_table_rows, X, out, h, d) &&
+         g.plan->info.n_segments == n_out_rows && g.plan->info.max_row == n_out_rows - 1;
 }
 
 inline int try_spmm_block(const char* tag, int dtype, const graphop_plan* plan, i64 n_table_rows,
@@ -676,12 +672,12 @@ inline int try_spmm_block(const char* tag, int dtype, const graphop_plan* plan, 
 // defined itself (k_spmm_f32<..., SELFZERO>) and the caller may skip the zero fill?  Only for outputs large enough for
 // the fill to matter, fp32 lane-group shapes, sorted rows, and when neither the block-dense, the walk nor the
 // window-owner drivers take the pass (asked with dry runs: what they build is what the pass would have built).
-inline bool spmm_selfzero(int dtype, const i64* row, const i64* indptr, const i64* eid, const i64* indices, i64 C, i64 E,
-                          const graphop_plan* plan, i64 n_table_rows, const void* w, const void* X, const void* out,
-                          i64 h, i64 d, i64 n_out_rows, hipStream_t st) {
+inline bool spmm_selfzero(int dtype, const Csr& g, i64 n_table_rows, const void* w, const void* X, const void* out, i64 h,
+                          i64 d, i64 n_out_rows, hipStream_t st) {
   const Tuning& t = tuning();
-  if (!t.spmm_selfzero || C == 0 || !plan_matches_full(plan, row, indptr, eid, indices, C, E)) return false;
-  if (!plan->info.rows_sorted || !fast_ok(dtype, h, d, E, n_table_rows) || !aligned16(out)) return false;
+  const graphop_plan* plan = g.plan;
+  if (!t.spmm_selfzero || g.n_chunks == 0 || !g.owned()) return false;
+  if (!fast_ok(dtype, h, d, g.n_edges, n_table_rows) || !aligned16(out)) return false;
   if (plan->info.max_row >= n_out_rows || n_out_rows >= 0x7fffffffLL) return false;
   if ((double)n_out_rows * (double)(h * d) * 4.0 < (double)t.spmm_selfzero_min_mb * 1048576.0) return false;
   if (spmm_block_applies(dtype, plan, n_table_rows, X, out, h, d)) return false;
@@ -722,11 +718,12 @@ inline bool spmm_flat(i64 C, i64 E, i64 h, i64 d) {
 
 // ---- launch helpers -------------------------------------------------------------------------------
 template <bool EDGE_B>
-int launch_sddmm(const char* tag, int dtype, const i64* row, const i64* indptr, const i64* eid,
-                 const i64* indices, const void* A, const void* B, void* y, i64 C, i64 E,
-                 i64 n_src_rows, i64 h, i64 d, const graphop_plan* plan, hipStream_t st) {
+int launch_sddmm(const char* tag, int dtype, const Csr& g, const void* A, const void* B, void* y, i64 n_src_rows, i64 h,
+                 i64 d, hipStream_t st) {
+  const i64 *row = g.row, *indptr = g.indptr, *eid = g.eid, *indices = g.indices;
+  const i64 C = g.n_chunks, E = g.n_edges;
+  const graphop_plan* plan = g.plan;
   if (C == 0) return GRAPHOP_OK;
-  if (!plan_matches_full(plan, row, indptr, eid, indices, C, E)) plan = nullptr;
   if constexpr (!EDGE_B) {
     if (try_sddmm_block(tag, dtype, plan, n_src_rows, A, B, y, h, d, st)) { GO_LAUNCH_CHECK(); return GRAPHOP_OK; }
   }
@@ -779,12 +776,13 @@ int launch_sddmm(const char* tag, int dtype, const i64* row, const i64* indptr, 
 }
 
 template <bool EDGE_X>
-int launch_spmm(const char* tag, int dtype, const i64* row, const i64* indptr, const i64* eid,
-                const i64* indices, const void* w, const void* X, void* out, i64 C, i64 E,
-                i64 n_src_rows, i64 h, i64 d, const graphop_plan* plan, hipStream_t st, i64 selfzero_rows = -1) {
+int launch_spmm(const char* tag, int dtype, const Csr& g, const void* w, const void* X, void* out, i64 n_src_rows, i64 h,
+                i64 d, hipStream_t st, i64 selfzero_rows = -1) {
   // selfzero_rows >= 0 (spmm_selfzero: the caller did NOT zero-fill `out`): straight to the self-zeroing chunk driver
+  const i64 *row = g.row, *indptr = g.indptr, *eid = g.eid, *indices = g.indices;
+  const i64 C = g.n_chunks, E = g.n_edges;
+  const graphop_plan* plan = g.plan;
   if (C == 0) return GRAPHOP_OK;
-  if (!plan_matches_full(plan, row, indptr, eid, indices, C, E)) plan = nullptr;
   if constexpr (!EDGE_X) {
     if (selfzero_rows >= 0) {
       const bool flat = spmm_flat(C, E, h, d);
@@ -846,7 +844,7 @@ int launch_spmm(const char* tag, int dtype, const i64* row, const i64* indptr, c
       if (use == 1) { GO_LAUNCH_CHECK(); return GRAPHOP_OK; }
     }
     // plan.rows_sorted: a row's chunks are adjacent, rows inside one group's range need no atomics
-    const bool owned = plan && plan->info.rows_sorted && ((uintptr_t)out & 15) == 0;
+    const bool owned = g.owned() && aligned16(out);
     if (owned && spmm_flat(C, E, h, d)) {      // short chunks: the slot-walking form of the same driver
       int done = 0;
       const int fcpg = cpg_for(C, tuning().spmm_flat_cpg, (int)(h * d));
@@ -905,12 +903,6 @@ inline bool nme_fast_ok(int dtype, i64 h, i64 d, i64 n_edges) {
     default: break;                                                          \
   }
 
-inline bool plan_matches(const graphop_plan* p, const i64* row, const i64* indptr, const i64* eid,
-                         i64 C, i64 E) {
-  return p && p->row == (const int64_t*)row && p->indptr == (const int64_t*)indptr &&
-         p->eid == (const int64_t*)eid && p->info.n_chunks == C && p->info.n_edges == E;
-}
-
 inline int seg_group_width(i64 items_per_seg, i64 h) {
   int g = items_per_seg >= 48 ? 64 : items_per_seg >= 24 ? 32 : items_per_seg >= 12 ? 16 : 8;
   while (g < h) g <<= 1;
@@ -918,8 +910,9 @@ inline int seg_group_width(i64 items_per_seg, i64 h) {
 }
 
 template <typename T, bool BWD>
-int launch_softmax_seg(const graphop_plan* p, const i64* indptr, const i64* eid, const T* in0,
-                       const T* in1, T* out, i64 h, hipStream_t st, T* stats = nullptr) {
+int launch_softmax_seg(const Csr& g, const T* in0, const T* in1, T* out, i64 h, hipStream_t st, T* stats = nullptr) {
+  const graphop_plan* p = g.plan_slots;   // (the caller found row_owned in it)
+  const i64 *indptr = g.indptr, *eid = g.eid;
   const i64 S = p->info.n_segments;
   if (S == 0) return GRAPHOP_OK;
   ProfScope prof(BWD ? "softmax_bwd" : "softmax_fwd", st, BWD ? "k_softmax_bwd_seg" : "k_softmax_fwd_seg");
@@ -991,14 +984,15 @@ int launch_softmax_seg(const graphop_plan* p, const i64* indptr, const i64* eid,
 }
 
 template <typename T>
-int softmax_forward_t(const i64* row, const i64* indptr, const i64* eid, const T* x, T* y, i64 C,
-                      i64 E, i64 h, T* ws, i64 ws_rows, const graphop_plan* plan, hipStream_t st,
-                      T* stats = nullptr) {
-  const bool owned = plan_matches(plan, row, indptr, eid, C, E) && plan->info.row_owned;
+int softmax_forward_t(const Csr& g, const T* x, T* y, i64 h, T* ws, i64 ws_rows, hipStream_t st, T* stats = nullptr) {
+  const i64 *row = g.row, *indptr = g.indptr, *eid = g.eid;
+  const i64 C = g.n_chunks, E = g.n_edges;
+  const graphop_plan* plan = g.plan_slots;   // (softmax has no neighbour ids)
+  const bool owned = plan && plan->info.row_owned;
   const bool covered = owned && plan->info.full_coverage && plan->info.eid_identity;
   if (!covered && E * h > 0) GO_HIP(zero_async(y, sizeof(T) * (size_t)(E * h), st));
   if (C == 0) return GRAPHOP_OK;
-  if (owned) return launch_softmax_seg<T, false>(plan, indptr, eid, x, (const T*)nullptr, y, h, st, stats);
+  if (owned) return launch_softmax_seg<T, false>(g, x, (const T*)nullptr, y, h, st, stats);
   GO_CHECK_ARG(ws != nullptr && ws_rows > 0,
                "sparse_softmax_forward: the general (plan-less) path needs a workspace of "
                "2*workspace_rows*h values with workspace_rows > max(row)");
@@ -1023,14 +1017,15 @@ int softmax_forward_t(const i64* row, const i64* indptr, const i64* eid, const T
 }
 
 template <typename T>
-int softmax_backward_t(const i64* row, const i64* indptr, const i64* eid, const T* y, const T* dy,
-                       T* dx, i64 C, i64 E, i64 h, T* ws, i64 ws_rows, const graphop_plan* plan,
-                       hipStream_t st) {
-  const bool owned = plan_matches(plan, row, indptr, eid, C, E) && plan->info.row_owned;
+int softmax_backward_t(const Csr& g, const T* y, const T* dy, T* dx, i64 h, T* ws, i64 ws_rows, hipStream_t st) {
+  const i64 *row = g.row, *indptr = g.indptr, *eid = g.eid;
+  const i64 C = g.n_chunks, E = g.n_edges;
+  const graphop_plan* plan = g.plan_slots;
+  const bool owned = plan && plan->info.row_owned;
   const bool covered = owned && plan->info.full_coverage && plan->info.eid_identity;
   if (!covered && E * h > 0) GO_HIP(zero_async(dx, sizeof(T) * (size_t)(E * h), st));
   if (C == 0) return GRAPHOP_OK;
-  if (owned) return launch_softmax_seg<T, true>(plan, indptr, eid, y, dy, dx, h, st);
+  if (owned) return launch_softmax_seg<T, true>(g, y, dy, dx, h, st);
   GO_CHECK_ARG(ws != nullptr && ws_rows > 0,
                "sparse_softmax_backward: the general (plan-less) path needs a workspace of "
                "workspace_rows*h values with workspace_rows > max(row)");
@@ -1053,33 +1048,14 @@ inline int check_common(const char* fn, int dtype, i64 C, i64 E, i64 h, i64 d) {
   return GRAPHOP_OK;
 }
 
-// Row ids address the row-side operand / output: with a plan the largest one is known, so an
-// operand with too few rows is an error here instead of an out-of-bounds access on the device.
-inline int check_rows(const char* fn, const char* what, const graphop_plan* plan, i64 n_rows) {
-  GO_CHECK_ARG(!plan || plan->info.max_row < n_rows,
-               "%s: row id %lld but %s has only %lld rows", fn, plan ? (long long)plan->info.max_row : 0LL,
-               what, (long long)n_rows);
-  return GRAPHOP_OK;
-}
-inline int check_cols(const char* fn, const char* what, const graphop_plan* plan, i64 n_rows) {
-  GO_CHECK_ARG(!plan || plan->info.max_index < n_rows,
-               "%s: neighbour id %lld but %s has only %lld rows", fn,
-               plan ? (long long)plan->info.max_index : 0LL, what, (long long)n_rows);
-  return GRAPHOP_OK;
-}
-
-
 }  // namespace
 
 // sparse_softmax_forward that also leaves the row statistics (max, 1 / sum) behind (attention.hip)
-int softmax_forward_stats(int dtype, const i64* row, const i64* indptr, const i64* eid, const void* x,
-                          void* y, i64 C, i64 E, i64 h, void* ws, i64 ws_rows,
-                          const graphop_plan* plan, hipStream_t st, void* stats) {
+int softmax_forward_stats(int dtype, const Csr& g, const void* x, void* y, i64 h, void* ws, i64 ws_rows, hipStream_t st,
+                          void* stats) {
   if (dtype == GRAPHOP_F32)
-    return softmax_forward_t<float>(row, indptr, eid, (const float*)x, (float*)y, C, E, h, (float*)ws,
-                                    ws_rows, plan, st, (float*)stats);
-  return softmax_forward_t<double>(row, indptr, eid, (const double*)x, (double*)y, C, E, h, (double*)ws,
-                                   ws_rows, plan, st, (double*)stats);
+    return softmax_forward_t<float>(g, (const float*)x, (float*)y, h, (float*)ws, ws_rows, st, (float*)stats);
+  return softmax_forward_t<double>(g, (const double*)x, (double*)y, h, (double*)ws, ws_rows, st, (double*)stats);
 }
 }  // namespace graphop
 
@@ -1144,20 +1120,13 @@ int graphop_maskedmm_csr_forward(int dtype, const int64_t* row, const int64_t* i
   hipStream_t st = (hipStream_t)stream;
   if (n_edges * h == 0) return GRAPHOP_OK;
   GO_PTR(fn, y);
-  const bool covered = plan_matches(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
-                                    n_chunks, n_edges) &&
-                       plan->info.full_coverage && plan->info.eid_identity &&
-                       plan->info.indptr_monotone;
-  if (!covered) GO_HIP(zero_async(y, esize(dtype) * (size_t)(n_edges * h), st));
+  const Csr g(row, indptr, eid, indices, n_chunks, n_edges, plan);
+  if (!g.covered(/*slots=*/true)) GO_HIP(zero_async(y, esize(dtype) * (size_t)(n_edges * h), st));
   if (n_chunks == 0) return GRAPHOP_OK;
-  GO_PTR(fn, row); GO_PTR(fn, indptr); GO_PTR(fn, eid); GO_PTR(fn, indices); GO_PTR(fn, A); GO_PTR(fn, B);
-  {
-    const graphop_plan* pm = plan_matches(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid, n_chunks, n_edges) ? plan : nullptr;
-    GO_TRY(check_rows(fn, "A", pm, n_a));
-    GO_TRY(check_cols(fn, "B", pm && pm->indices == indices ? pm : nullptr, n_b));
-  }
-  return launch_sddmm<false>("sddmm_fwd", dtype, (const i64*)row, (const i64*)indptr, (const i64*)eid,
-                             (const i64*)indices, A, B, y, n_chunks, n_edges, n_b, h, d, plan, st);
+  GO_TRY(g.require(fn)); GO_PTR(fn, A); GO_PTR(fn, B);
+  GO_TRY(Csr::check_bounds(fn, g.plan_slots, "A", n_a, nullptr, 0));   // (B only against the plan of these neighbour ids)
+  GO_TRY(Csr::check_bounds(fn, g.plan, "A", n_a, "B", n_b));
+  return launch_sddmm<false>("sddmm_fwd", dtype, g, A, B, y, n_b, h, d, st);
 }
 
 // SDDMM over a subset of the slots into a shared result array: no zero fill, eid indexes y (n_y entries).
@@ -1172,10 +1141,10 @@ int graphop_maskedmm_csr_forward_partial(int dtype, const int64_t* row, const in
                "entries of y", fn, (long long)n_y, (long long)n_slots);
   hipStream_t st = (hipStream_t)stream;
   if (n_slots * h == 0 || n_chunks == 0) return GRAPHOP_OK;
-  GO_PTR(fn, y); GO_PTR(fn, row); GO_PTR(fn, indptr); GO_PTR(fn, eid); GO_PTR(fn, indices); GO_PTR(fn, A); GO_PTR(fn, B);
   // E bounds the 32-bit forms of the kernels' edge offsets: the result array's size, not the sub-graph's
-  return launch_sddmm<false>("sddmm_fwd_part", dtype, (const i64*)row, (const i64*)indptr, (const i64*)eid,
-                             (const i64*)indices, A, B, y, n_chunks, n_y, n_b, h, d, nullptr, st);
+  const Csr g(row, indptr, eid, indices, n_chunks, n_y, nullptr);
+  GO_PTR(fn, y); GO_TRY(g.require(fn)); GO_PTR(fn, A); GO_PTR(fn, B);
+  return launch_sddmm<false>("sddmm_fwd_part", dtype, g, A, B, y, n_b, h, d, st);
 }
 
 int graphop_maskedmm_csr_backward(int dtype, const int64_t* row, const int64_t* indptr_r,
@@ -1192,44 +1161,34 @@ int graphop_maskedmm_csr_backward(int dtype, const int64_t* row, const int64_t* 
   GO_CHECK_ARG(n_col_chunks >= 0 && n_a >= 0 && n_b >= 0, "%s: negative size", fn);
   hipStream_t st = (hipStream_t)stream;
   const size_t es = esize(dtype);
-  {
-    const graphop_plan* pr = plan_matches_full(plan_r, (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r, (const i64*)indices_r, n_row_chunks, n_edges) ? plan_r : nullptr;
-    const graphop_plan* pc = plan_matches_full(plan_c, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c, (const i64*)indices_c, n_col_chunks, n_edges) ? plan_c : nullptr;
-    GO_TRY(check_rows(fn, "A / dA", pr, n_a)); GO_TRY(check_cols(fn, "B", pr, n_b));
-    GO_TRY(check_rows(fn, "B / dB", pc, n_b)); GO_TRY(check_cols(fn, "A", pc, n_a));
-  }
+  const Csr r(row, indptr_r, eid_r, indices_r, n_row_chunks, n_edges, plan_r, "row", "indptr_r", "eid_r", "indices_r");
+  const Csr c(col, indptr_c, eid_c, indices_c, n_col_chunks, n_edges, plan_c, "col", "indptr_c", "eid_c", "indices_c");
+  GO_TRY(Csr::check_bounds(fn, r.plan, "A / dA", n_a, "B", n_b));
+  GO_TRY(Csr::check_bounds(fn, c.plan, "B / dB", n_b, "A", n_a));
   // an output whose orientation has no chunks may be NULL: that half of the op is skipped entirely
   // (the sharded step calls the op once per orientation to overlap the dK exchange, dist.py)
   // (sz_*: the pass will run on the self-zeroing chunk driver, which leaves every output row defined: no fill)
   bool sz_a = false, sz_b = false;
   if (n_a * h * d > 0 && !(dA == nullptr && n_row_chunks == 0)) {
     GO_PTR(fn, dA);
-    sz_a = dy != nullptr && B != nullptr &&
-           spmm_selfzero(dtype, (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r, (const i64*)indices_r, n_row_chunks,
-                         n_edges, plan_r, n_b, dy, B, dA, h, d, n_a, st);
-    if (!sz_a && !spmm_block_writes_all(dtype, (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r, (const i64*)indices_r,
-                                        n_row_chunks, n_edges, plan_r, n_b, B, dA, h, d, n_a))
+    sz_a = dy != nullptr && B != nullptr && spmm_selfzero(dtype, r, n_b, dy, B, dA, h, d, n_a, st);
+    if (!sz_a && !spmm_block_writes_all(dtype, r, n_b, B, dA, h, d, n_a))
       GO_HIP(zero_async(dA, es * (size_t)(n_a * h * d), st));
   }
   if (n_b * h * d > 0 && !(dB == nullptr && n_col_chunks == 0)) {
     GO_PTR(fn, dB);
-    sz_b = dy != nullptr && A != nullptr &&
-           spmm_selfzero(dtype, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c, (const i64*)indices_c, n_col_chunks,
-                         n_edges, plan_c, n_a, dy, A, dB, h, d, n_b, st);
-    if (!sz_b && !spmm_block_writes_all(dtype, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c, (const i64*)indices_c,
-                                        n_col_chunks, n_edges, plan_c, n_a, A, dB, h, d, n_b))
+    sz_b = dy != nullptr && A != nullptr && spmm_selfzero(dtype, c, n_a, dy, A, dB, h, d, n_b, st);
+    if (!sz_b && !spmm_block_writes_all(dtype, c, n_a, A, dB, h, d, n_b))
       GO_HIP(zero_async(dB, es * (size_t)(n_b * h * d), st));
   }
   if (h * d == 0) return GRAPHOP_OK;
   if (n_row_chunks > 0) {
-    GO_PTR(fn, row); GO_PTR(fn, indptr_r); GO_PTR(fn, eid_r); GO_PTR(fn, indices_r); GO_PTR(fn, B); GO_PTR(fn, dy);
-    GO_TRY(launch_spmm<false>("sddmm_bwd_dA", dtype, (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r,
-                              (const i64*)indices_r, dy, B, dA, n_row_chunks, n_edges, n_b, h, d, plan_r, st, sz_a ? n_a : -1));
+    GO_TRY(r.require(fn)); GO_PTR(fn, B); GO_PTR(fn, dy);
+    GO_TRY(launch_spmm<false>("sddmm_bwd_dA", dtype, r, dy, B, dA, n_b, h, d, st, sz_a ? n_a : -1));
   }
   if (n_col_chunks > 0) {
-    GO_PTR(fn, col); GO_PTR(fn, indptr_c); GO_PTR(fn, eid_c); GO_PTR(fn, indices_c); GO_PTR(fn, A); GO_PTR(fn, dy);
-    GO_TRY(launch_spmm<false>("sddmm_bwd_dB", dtype, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c,
-                              (const i64*)indices_c, dy, A, dB, n_col_chunks, n_edges, n_a, h, d, plan_c, st, sz_b ? n_b : -1));
+    GO_TRY(c.require(fn)); GO_PTR(fn, A); GO_PTR(fn, dy);
+    GO_TRY(launch_spmm<false>("sddmm_bwd_dB", dtype, c, dy, A, dB, n_a, h, d, st, sz_b ? n_b : -1));
   }
   return GRAPHOP_OK;
 }
@@ -1243,14 +1202,9 @@ int graphop_sparse_softmax_forward(int dtype, const int64_t* row, const int64_t*
   GO_TRY(check_common(fn, dtype, n_chunks, n_edges, h, 0));
   if (n_edges * h == 0) return GRAPHOP_OK;
   GO_PTR(fn, y);
-  if (n_chunks > 0) { GO_PTR(fn, row); GO_PTR(fn, indptr); GO_PTR(fn, eid); GO_PTR(fn, x); }
-  if (dtype == GRAPHOP_F32)
-    return softmax_forward_t<float>((const i64*)row, (const i64*)indptr, (const i64*)eid,
-                                    (const float*)x, (float*)y, n_chunks, n_edges, h,
-                                    (float*)workspace, workspace_rows, plan, (hipStream_t)stream);
-  return softmax_forward_t<double>((const i64*)row, (const i64*)indptr, (const i64*)eid,
-                                   (const double*)x, (double*)y, n_chunks, n_edges, h,
-                                   (double*)workspace, workspace_rows, plan, (hipStream_t)stream);
+  const Csr g(row, indptr, eid, nullptr, n_chunks, n_edges, plan);
+  if (n_chunks > 0) { GO_TRY(g.require(fn, /*has_indices=*/false)); GO_PTR(fn, x); }
+  return softmax_forward_stats(dtype, g, x, y, h, workspace, workspace_rows, (hipStream_t)stream, nullptr);
 }
 
 int graphop_sparse_softmax_backward(int dtype, const int64_t* row, const int64_t* indptr,
@@ -1262,16 +1216,13 @@ int graphop_sparse_softmax_backward(int dtype, const int64_t* row, const int64_t
   GO_TRY(check_common(fn, dtype, n_chunks, n_edges, h, 0));
   if (n_edges * h == 0) return GRAPHOP_OK;
   GO_PTR(fn, dx);
-  if (n_chunks > 0) { GO_PTR(fn, row); GO_PTR(fn, indptr); GO_PTR(fn, eid); GO_PTR(fn, y); GO_PTR(fn, dy); }
+  const Csr g(row, indptr, eid, nullptr, n_chunks, n_edges, plan);
+  if (n_chunks > 0) { GO_TRY(g.require(fn, /*has_indices=*/false)); GO_PTR(fn, y); GO_PTR(fn, dy); }
   if (dtype == GRAPHOP_F32)
-    return softmax_backward_t<float>((const i64*)row, (const i64*)indptr, (const i64*)eid,
-                                     (const float*)y, (const float*)dy, (float*)dx, n_chunks,
-                                     n_edges, h, (float*)workspace, workspace_rows, plan,
-                                     (hipStream_t)stream);
-  return softmax_backward_t<double>((const i64*)row, (const i64*)indptr, (const i64*)eid,
-                                    (const double*)y, (const double*)dy, (double*)dx, n_chunks,
-                                    n_edges, h, (double*)workspace, workspace_rows, plan,
-                                    (hipStream_t)stream);
+    return softmax_backward_t<float>(g, (const float*)y, (const float*)dy, (float*)dx, h, (float*)workspace,
+                                     workspace_rows, (hipStream_t)stream);
+  return softmax_backward_t<double>(g, (const double*)y, (const double*)dy, (double*)dx, h, (double*)workspace,
+                                    workspace_rows, (hipStream_t)stream);
 }
 
 int graphop_vector_spmm_forward(int dtype, const int64_t* row, const int64_t* indptr,
@@ -1283,22 +1234,16 @@ int graphop_vector_spmm_forward(int dtype, const int64_t* row, const int64_t* in
   GO_TRY(check_common(fn, dtype, n_chunks, n_edges, h, d));
   GO_CHECK_ARG(n_x >= 0 && n_y >= 0, "%s: negative size", fn);
   hipStream_t st = (hipStream_t)stream;
-  {
-    const graphop_plan* pm = plan_matches_full(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid, (const i64*)indices, n_chunks, n_edges) ? plan : nullptr;
-    GO_TRY(check_rows(fn, "y", pm, n_y)); GO_TRY(check_cols(fn, "x", pm, n_x));
-  }
+  const Csr g(row, indptr, eid, indices, n_chunks, n_edges, plan);
+  GO_TRY(Csr::check_bounds(fn, g.plan, "y", n_y, "x", n_x));
   if (n_y * h * d == 0) return GRAPHOP_OK;
   GO_PTR(fn, y);
-  const bool sz = edata != nullptr && x != nullptr &&
-                  spmm_selfzero(dtype, (const i64*)row, (const i64*)indptr, (const i64*)eid, (const i64*)indices, n_chunks, n_edges,
-                                plan, n_x, edata, x, y, h, d, n_y, st);
-  if (!sz && !spmm_block_writes_all(dtype, (const i64*)row, (const i64*)indptr, (const i64*)eid, (const i64*)indices,
-                                    n_chunks, n_edges, plan, n_x, x, y, h, d, n_y))
+  const bool sz = edata != nullptr && x != nullptr && spmm_selfzero(dtype, g, n_x, edata, x, y, h, d, n_y, st);
+  if (!sz && !spmm_block_writes_all(dtype, g, n_x, x, y, h, d, n_y))
     GO_HIP(zero_async(y, esize(dtype) * (size_t)(n_y * h * d), st));
   if (n_chunks == 0) return GRAPHOP_OK;
-  GO_PTR(fn, row); GO_PTR(fn, indptr); GO_PTR(fn, eid); GO_PTR(fn, indices); GO_PTR(fn, edata); GO_PTR(fn, x);
-  return launch_spmm<false>("spmm_fwd", dtype, (const i64*)row, (const i64*)indptr, (const i64*)eid,
-                            (const i64*)indices, edata, x, y, n_chunks, n_edges, n_x, h, d, plan, st, sz ? n_y : -1);
+  GO_TRY(g.require(fn)); GO_PTR(fn, edata); GO_PTR(fn, x);
+  return launch_spmm<false>("spmm_fwd", dtype, g, edata, x, y, n_x, h, d, st, sz ? n_y : -1);
 }
 
 int graphop_vector_spmm_backward(int dtype, const int64_t* row, const int64_t* indptr,
@@ -1314,44 +1259,33 @@ int graphop_vector_spmm_backward(int dtype, const int64_t* row, const int64_t* i
   GO_CHECK_ARG(n_col_chunks >= 0 && n_x >= 0 && n_dy >= 0, "%s: negative size", fn);
   hipStream_t st = (hipStream_t)stream;
   const size_t es = esize(dtype);
-  {
-    const graphop_plan* pr = plan_matches_full(plan_r, (const i64*)row, (const i64*)indptr, (const i64*)eid, (const i64*)indices, n_row_chunks, n_edges) ? plan_r : nullptr;
-    const graphop_plan* pc = plan_matches_full(plan_c, (const i64*)col, (const i64*)indptr_t, (const i64*)eid_t, (const i64*)indices_t, n_col_chunks, n_edges) ? plan_c : nullptr;
-    GO_TRY(check_rows(fn, "dy", pr, n_dy)); GO_TRY(check_cols(fn, "x", pr, n_x));
-    GO_TRY(check_rows(fn, "x / dx", pc, n_x)); GO_TRY(check_cols(fn, "dy", pc, n_dy));
-  }
+  const Csr r(row, indptr, eid, indices, n_row_chunks, n_edges, plan_r);
+  const Csr c(col, indptr_t, eid_t, indices_t, n_col_chunks, n_edges, plan_c, "col", "indptr_t", "eid_t", "indices_t");
+  GO_TRY(Csr::check_bounds(fn, r.plan, "dy", n_dy, "x", n_x));
+  GO_TRY(Csr::check_bounds(fn, c.plan, "x / dx", n_x, "dy", n_dy));
   if (n_edges * h > 0) {
     GO_PTR(fn, dedata);
-    const bool covered = plan_matches(plan_r, (const i64*)row, (const i64*)indptr, (const i64*)eid,
-                                      n_row_chunks, n_edges) &&
-                         plan_r->info.full_coverage && plan_r->info.eid_identity &&
-                         plan_r->info.indptr_monotone;
-    if (!covered) GO_HIP(zero_async(dedata, es * (size_t)(n_edges * h), st));
+    if (!r.covered(/*slots=*/true)) GO_HIP(zero_async(dedata, es * (size_t)(n_edges * h), st));
   }
   bool sz_x = false;
   // (dx may be NULL when n_col_chunks == 0: that half of the op is skipped, as in maskedmm_csr_backward -- the sharded
   // step computes dx together with dK in one column-major launch, graphop_spmm_pair)
   if (n_x * h * d > 0 && !(dx == nullptr && n_col_chunks == 0)) {
     GO_PTR(fn, dx);
-    sz_x = edata != nullptr && dy != nullptr &&
-           spmm_selfzero(dtype, (const i64*)col, (const i64*)indptr_t, (const i64*)eid_t, (const i64*)indices_t, n_col_chunks,
-                         n_edges, plan_c, n_dy, edata, dy, dx, h, d, n_x, st);
-    if (!sz_x && !spmm_block_writes_all(dtype, (const i64*)col, (const i64*)indptr_t, (const i64*)eid_t, (const i64*)indices_t,
-                                        n_col_chunks, n_edges, plan_c, n_dy, dy, dx, h, d, n_x))
+    sz_x = edata != nullptr && dy != nullptr && spmm_selfzero(dtype, c, n_dy, edata, dy, dx, h, d, n_x, st);
+    if (!sz_x && !spmm_block_writes_all(dtype, c, n_dy, dy, dx, h, d, n_x))
       GO_HIP(zero_async(dx, es * (size_t)(n_x * h * d), st));
   }
   if (h * d == 0) return GRAPHOP_OK;
   if (n_row_chunks > 0 && n_edges > 0) {
-    GO_PTR(fn, row); GO_PTR(fn, indptr); GO_PTR(fn, eid); GO_PTR(fn, indices); GO_PTR(fn, dy); GO_PTR(fn, x);
+    GO_TRY(r.require(fn)); GO_PTR(fn, dy); GO_PTR(fn, x);
     // kernel_0: dedata = SDDMM(dy, x) over the row-major CSR (graphop_kernel.cu:135-149)
-    GO_TRY(launch_sddmm<false>("spmm_bwd_dedata", dtype, (const i64*)row, (const i64*)indptr, (const i64*)eid,
-                               (const i64*)indices, dy, x, dedata, n_row_chunks, n_edges, n_x, h, d, plan_r, st));
+    GO_TRY(launch_sddmm<false>("spmm_bwd_dedata", dtype, r, dy, x, dedata, n_x, h, d, st));
   }
   if (n_col_chunks > 0) {
-    GO_PTR(fn, col); GO_PTR(fn, indptr_t); GO_PTR(fn, eid_t); GO_PTR(fn, indices_t); GO_PTR(fn, edata); GO_PTR(fn, dy);
+    GO_TRY(c.require(fn)); GO_PTR(fn, edata); GO_PTR(fn, dy);
     // kernel_1: dx = SpMM(edata, dy) over the column-major CSR, all C' chunks (:151-163)
-    GO_TRY(launch_spmm<false>("spmm_bwd_dx", dtype, (const i64*)col, (const i64*)indptr_t, (const i64*)eid_t,
-                              (const i64*)indices_t, edata, dy, dx, n_col_chunks, n_edges, n_dy, h, d, plan_c, st, sz_x ? n_x : -1));
+    GO_TRY(launch_spmm<false>("spmm_bwd_dx", dtype, c, edata, dy, dx, n_dy, h, d, st, sz_x ? n_x : -1));
   }
   return GRAPHOP_OK;
 }
@@ -1370,8 +1304,8 @@ int graphop_spmm_pair(int dtype, const int64_t* row, const int64_t* indptr, cons
   const char* fn = "spmm_pair";
   GO_TRY(check_common(fn, dtype, n_chunks, n_edges, h, d));
   hipStream_t st = (hipStream_t)stream;
-  GO_CHECK_ARG(plan_matches_full(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid, (const i64*)indices, n_chunks, n_edges) &&
-               graphop_spmm_pair_supported(dtype, n_chunks, n_edges, n_x, h, d, plan) && aligned16(out0) && aligned16(out1),
+  const Csr g(row, indptr, eid, indices, n_chunks, n_edges, plan);
+  GO_CHECK_ARG(g.plan && graphop_spmm_pair_supported(dtype, n_chunks, n_edges, n_x, h, d, plan) && aligned16(out0) && aligned16(out1),
                "%s: not supported for these operands (fp32, one head, d in {64, 128, 256}, a plan of these arrays with sorted "
                "rows, 16-byte-aligned outputs): run the two passes separately", fn);
   GO_CHECK_ARG(n_out >= 0 && plan->info.max_row < n_out && n_out < 0x7fffffffLL, "%s: row id %lld but the outputs have %lld rows", fn,
@@ -1408,15 +1342,15 @@ int graphop_spmm_pair(int dtype, const int64_t* row, const int64_t* indptr, cons
       if (sz) {
         if (groups > 1) {
           const unsigned zb = blocks_for(groups - 1, kFastBlock / L);
-          hipLaunchKernelGGL((k_zero_shared_rows<L, NV>), dim3(zb), dim3(kFastBlock), 0, st, (const i64*)row, (float*)out0, n_chunks, cpg);
-          hipLaunchKernelGGL((k_zero_shared_rows<L, NV>), dim3(zb), dim3(kFastBlock), 0, st, (const i64*)row, (float*)out1, n_chunks, cpg);
+          hipLaunchKernelGGL((k_zero_shared_rows<L, NV>), dim3(zb), dim3(kFastBlock), 0, st, g.row, (float*)out0, n_chunks, cpg);
+          hipLaunchKernelGGL((k_zero_shared_rows<L, NV>), dim3(zb), dim3(kFastBlock), 0, st, g.row, (float*)out1, n_chunks, cpg);
         }
-        hipLaunchKernelGGL((k_spmm_flat2_f32<L, true>), dim3(nb), dim3(kFastBlock), 0, st, (const i64*)row, (const i64*)indptr,
-                           (const i64*)eid, (const i64*)indices, (const float2*)w2, (const float*)X0, (const float*)X1,
+        hipLaunchKernelGGL((k_spmm_flat2_f32<L, true>), dim3(nb), dim3(kFastBlock), 0, st, g.row, g.indptr, g.eid, g.indices,
+                           (const float2*)w2, (const float*)X0, (const float*)X1,
                            (float*)out0, (float*)out1, n_chunks, cpg, covered);
       } else {
-        hipLaunchKernelGGL((k_spmm_flat2_f32<L, false>), dim3(nb), dim3(kFastBlock), 0, st, (const i64*)row, (const i64*)indptr,
-                           (const i64*)eid, (const i64*)indices, (const float2*)w2, (const float*)X0, (const float*)X1,
+        hipLaunchKernelGGL((k_spmm_flat2_f32<L, false>), dim3(nb), dim3(kFastBlock), 0, st, g.row, g.indptr, g.eid, g.indices,
+                           (const float2*)w2, (const float*)X0, (const float*)X1,
                            (float*)out0, (float*)out1, n_chunks, cpg, (i64)0);
       }
     }
@@ -1432,29 +1366,27 @@ int graphop_node_mul_edge_forward(int dtype, const int64_t* row, const int64_t* 
   const char* fn = "node_mul_edge_forward";
   GO_TRY(check_common(fn, dtype, n_chunks, n_edges, h, d));
   hipStream_t st = (hipStream_t)stream;
-  GO_TRY(check_rows(fn, "A", plan_matches(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid, n_chunks, n_edges) ? plan : nullptr, n_a));
+  const Csr g(row, indptr, eid, nullptr, n_chunks, n_edges, plan);
+  GO_TRY(Csr::check_bounds(fn, g.plan_slots, "A", n_a, nullptr, 0));
   if (n_edges * h == 0) return GRAPHOP_OK;
   GO_PTR(fn, y);
-  const bool covered = plan_matches(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
-                                    n_chunks, n_edges) &&
-                       plan->info.full_coverage && plan->info.eid_identity && plan->info.indptr_monotone;
-  if (!covered) GO_HIP(zero_async(y, esize(dtype) * (size_t)(n_edges * h), st));
+  if (!g.covered(/*slots=*/true)) GO_HIP(zero_async(y, esize(dtype) * (size_t)(n_edges * h), st));
   if (n_chunks == 0) return GRAPHOP_OK;
-  GO_PTR(fn, row); GO_PTR(fn, indptr); GO_PTR(fn, eid); GO_PTR(fn, A); GO_PTR(fn, B);
+  GO_TRY(g.require(fn, /*has_indices=*/false)); GO_PTR(fn, A); GO_PTR(fn, B);
   if (nme_fast_ok(dtype, h, d, n_edges)) {
     ProfScope prof("node_mul_edge_fwd", st, "k_nme_fwd_f32");
     const int cpg = tuning().spmm_cpg;
     GO_DISPATCH_NME(d, h, {
       const unsigned nb = blocks_for(ceil_div(n_chunks, cpg), kFastBlock / LD);
-      hipLaunchKernelGGL((k_nme_fwd_f32<LD, H>), dim3(nb), dim3(kFastBlock), 0, st, (const i64*)row,
-                         (const i64*)indptr, (const i64*)eid, (const float*)A, (const float*)B,
-                         (float*)y, n_chunks, cpg);
+      hipLaunchKernelGGL((k_nme_fwd_f32<LD, H>), dim3(nb), dim3(kFastBlock), 0, st, g.row, g.indptr, g.eid,
+                         (const float*)A, (const float*)B, (float*)y, n_chunks, cpg);
     });
     GO_LAUNCH_CHECK();
     return GRAPHOP_OK;
   }
-  return launch_sddmm<true>("node_mul_edge_fwd", dtype, (const i64*)row, (const i64*)indptr, (const i64*)eid,
-                            (const i64*)eid, A, B, y, n_chunks, n_edges, n_edges, h, d, nullptr, st);
+  // (the edge rows are gathered through the edge ids, and no plan is a plan of those)
+  return launch_sddmm<true>("node_mul_edge_fwd", dtype, Csr(row, indptr, eid, eid, n_chunks, n_edges, nullptr), A, B, y,
+                            n_edges, h, d, st);
 }
 
 int graphop_node_mul_edge_backward(int dtype, const int64_t* row, const int64_t* indptr,
@@ -1466,42 +1398,37 @@ int graphop_node_mul_edge_backward(int dtype, const int64_t* row, const int64_t*
   GO_TRY(check_common(fn, dtype, n_chunks, n_edges, h, d));
   hipStream_t st = (hipStream_t)stream;
   const size_t es = esize(dtype);
-  const bool covered = plan_matches(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
-                                    n_chunks, n_edges) &&
-                       plan->info.full_coverage && plan->info.eid_identity && plan->info.indptr_monotone;
-  GO_TRY(check_rows(fn, "A / dA", plan_matches(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid, n_chunks, n_edges) ? plan : nullptr, n_a));
+  const Csr g(row, indptr, eid, nullptr, n_chunks, n_edges, plan);
+  GO_TRY(Csr::check_bounds(fn, g.plan_slots, "A / dA", n_a, nullptr, 0));
   if (n_a * h * d > 0) { GO_PTR(fn, dA); GO_HIP(zero_async(dA, es * (size_t)(n_a * h * d), st)); }
   if (n_edges * d > 0) {   // every edge row is written when the chunks cover all slots: skip the E*d zero-fill
     GO_PTR(fn, dB);
-    if (!covered) GO_HIP(zero_async(dB, es * (size_t)(n_edges * d), st));
+    if (!g.covered(/*slots=*/true)) GO_HIP(zero_async(dB, es * (size_t)(n_edges * d), st));
   }
   if (n_chunks == 0 || h * d == 0) return GRAPHOP_OK;
-  GO_PTR(fn, row); GO_PTR(fn, indptr); GO_PTR(fn, eid); GO_PTR(fn, A); GO_PTR(fn, B); GO_PTR(fn, dy);
+  GO_TRY(g.require(fn, /*has_indices=*/false)); GO_PTR(fn, A); GO_PTR(fn, B); GO_PTR(fn, dy);
   if (nme_fast_ok(dtype, h, d, n_edges)) {   // both gradients in one streaming pass over B and dy
     ProfScope prof("node_mul_edge_bwd", st, "k_nme_bwd_f32");
     const int cpg = tuning().spmm_cpg;
     GO_DISPATCH_NME(d, h, {
       const unsigned nb = blocks_for(ceil_div(n_chunks, cpg), kFastBlock / LD);
-      hipLaunchKernelGGL((k_nme_bwd_f32<LD, H>), dim3(nb), dim3(kFastBlock), 0, st, (const i64*)row,
-                         (const i64*)indptr, (const i64*)eid, (const float*)A, (const float*)B,
-                         (const float*)dy, (float*)dA, (float*)dB, n_chunks, cpg);
+      hipLaunchKernelGGL((k_nme_bwd_f32<LD, H>), dim3(nb), dim3(kFastBlock), 0, st, g.row, g.indptr, g.eid,
+                         (const float*)A, (const float*)B, (const float*)dy, (float*)dA, (float*)dB, n_chunks, cpg);
     });
     GO_LAUNCH_CHECK();
     return GRAPHOP_OK;
   }
   // kernel_0 (graphop_kernel.cu:61-73): dA[row] += sum_k dy[eid[k], j/d] * B[eid[k], j%d]
-  GO_TRY(launch_spmm<true>("node_mul_edge_bwd_dA", dtype, (const i64*)row, (const i64*)indptr, (const i64*)eid,
-                           (const i64*)eid, dy, B, dA, n_chunks, n_edges, n_edges, h, d, nullptr, st));
+  GO_TRY(launch_spmm<true>("node_mul_edge_bwd_dA", dtype, Csr(row, indptr, eid, eid, n_chunks, n_edges, nullptr), dy, B,
+                           dA, n_edges, h, d, st));
   // kernel_1 (:79-94): dB[eid[k], j] = sum_ki dy[eid[k], ki] * A[row, ki, j]
   const unsigned nb = (unsigned)ceil_div(n_chunks, kGenericWavesPerBlock);
   if (dtype == GRAPHOP_F32)
     hipLaunchKernelGGL((k_node_mul_edge_bwd_b<float>), dim3(nb), dim3(kGenericBlock), 0, st,
-                       (const i64*)row, (const i64*)indptr, (const i64*)eid, (const float*)A,
-                       (const float*)dy, (float*)dB, n_chunks, h, d);
+                       g.row, g.indptr, g.eid, (const float*)A, (const float*)dy, (float*)dB, n_chunks, h, d);
   else
     hipLaunchKernelGGL((k_node_mul_edge_bwd_b<double>), dim3(nb), dim3(kGenericBlock), 0, st,
-                       (const i64*)row, (const i64*)indptr, (const i64*)eid, (const double*)A,
-                       (const double*)dy, (double*)dB, n_chunks, h, d);
+                       g.row, g.indptr, g.eid, (const double*)A, (const double*)dy, (double*)dB, n_chunks, h, d);
   GO_LAUNCH_CHECK();
   return GRAPHOP_OK;
 }

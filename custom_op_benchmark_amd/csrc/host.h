@@ -1,5 +1,7 @@
 // Host-side helpers shared by the translation units of libgraphop_hip (graphop_hip.hip defines
-// them; attention.hip uses them).  Not part of the C ABI.
+// them; attention.hip uses them).  Not part of the C ABI.  What exists once, here: the tuning knobs, the chunk-driver
+// geometry, and Csr -- a chunked CSR orientation with its plan resolved (the two plan matches, the coverage rule, the
+// bounds check, the NULL checks of the four arrays) -- with the 16-byte alignment test.
 #pragma once
 #include "common.h"
 
@@ -222,43 +224,88 @@ int attn_fwd_walk(const graphop_plan* plan, i64 n_q, i64 n_k, i64 h, i64 d, int 
 // Fused attention forward WITH a per-edge score bias b (indexed by edge id), chunk-driver form (graphop_hip.hip;
 // kernels_attn_bias.h): a lane group walks consecutive chunks of a rows_sorted plan with an online
 // softmax; rows that groups share leave as piece records merged by the walk's piece kernels.  Same return values and
-// dry_run meaning as attn_fwd_walk.  eid: the call's edge ids (the plan's), unused where the plan has eid_identity.
-int attn_bias_fwd_rows(const graphop_plan* plan, const i64* eid, i64 n_chunks, i64 n_edges, i64 n_q, i64 n_k, i64 h,
-                       i64 d, int dtype, const void* Q, const void* K, const void* V, const void* b, void* o,
-                       void* stats, void* ws, i64 ws_bytes, hipStream_t st, bool dry_run, size_t* ws_needed,
-                       const AttnDrop* drop = nullptr);
+// dry_run meaning as attn_fwd_walk.  g: the call's row-major orientation (0 where g.plan is NULL).
+struct Csr;
+int attn_bias_fwd_rows(const Csr& g, i64 n_q, i64 n_k, i64 h, i64 d, int dtype, const void* Q, const void* K,
+                       const void* V, const void* b, void* o, void* stats, void* ws, i64 ws_bytes, hipStream_t st,
+                       bool dry_run, size_t* ws_needed, const AttnDrop* drop = nullptr);
 
 // Several-head forms of the fused attention passes (attention_heads.hip; kernels_attn_heads.h): fp32,
 // (h, d) a several-head pair of GO_DISPATCH_GAT_HD, plans with neighbour ids whose id ranges lie inside the tables.
 // attn_heads_fwd_rows: attn_bias_fwd_rows' contract (return values, dry_run, workspace) for h > 1; b == NULL: no bias.
 // attn_heads_bwd_ok: will attn_heads_backward run for this call?  Its workspace is attn_heads_bwd_workspace bytes.
 struct HostDrop;   // host_dropout.h; drop == NULL: no dropout, else the call's heads are the global heads head0 .. head0 + h - 1
-int attn_heads_fwd_rows(const graphop_plan* plan, const i64* eid, i64 n_chunks, i64 n_edges, i64 n_q, i64 n_k, i64 h,
-                        i64 d, int dtype, const void* Q, const void* K, const void* V, const void* b, void* o,
-                        void* stats, void* ws, i64 ws_bytes, hipStream_t st, bool dry_run, size_t* ws_needed,
-                        const HostDrop* drop = nullptr, i64 head0 = 0);
+int attn_heads_fwd_rows(const Csr& g, i64 n_q, i64 n_k, i64 h, i64 d, int dtype, const void* Q, const void* K,
+                        const void* V, const void* b, void* o, void* stats, void* ws, i64 ws_bytes, hipStream_t st,
+                        bool dry_run, size_t* ws_needed, const HostDrop* drop = nullptr, i64 head0 = 0);
 bool attn_heads_bwd_ok(int dtype, i64 h, i64 d, i64 n_edges, i64 n_q, i64 n_k, const graphop_plan* plan_r,
                        const graphop_plan* plan_c, hipStream_t st);
 size_t attn_heads_bwd_workspace(i64 n_q, i64 n_k, i64 h, i64 d);
-int attn_heads_backward(const graphop_plan* pr, const graphop_plan* pc, const i64* eid_r, const i64* eid_c,
-                        i64 n_row_chunks, i64 n_col_chunks, i64 n_q, i64 n_k, i64 h, i64 d, const void* Q, const void* K,
+int attn_heads_backward(const Csr& r, const Csr& c, i64 n_q, i64 n_k, i64 h, i64 d, const void* Q, const void* K,
                         const void* V, const void* b, const void* o, const void* stats, const void* dO, void* dQ, void* dK,
                         void* dV, void* db, void* ws, hipStream_t st, const HostDrop* drop, i64 head0);
-
-int softmax_forward_stats(int dtype, const i64* row, const i64* indptr, const i64* eid, const void* x,
-                          void* y, i64 C, i64 E, i64 h, void* ws, i64 ws_rows,
-                          const graphop_plan* plan, hipStream_t st, void* stats);
 
 inline size_t esize(int dtype) { return dtype == GRAPHOP_F64 ? 8 : 4; }
 inline bool pow2(i64 v) { return v > 0 && (v & (v - 1)) == 0; }
 inline i64 pow2ceil(i64 v) { i64 p = 1; while (p < v) p <<= 1; return p; }
 
-inline bool plan_matches_full(const graphop_plan* p, const i64* row, const i64* indptr,
-                              const i64* eid, const i64* indices, i64 C, i64 E) {
-  return p && p->row == (const int64_t*)row && p->indptr == (const int64_t*)indptr &&
-         p->eid == (const int64_t*)eid && p->indices == (const int64_t*)indices &&
-         p->info.n_chunks == C && p->info.n_edges == E;
-}
+inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// One chunked CSR orientation as an entry point receives it, with the caller's plan resolved against it.  Built once
+// per orientation where the C ABI's arguments arrive (the only place the ABI's int64_t* become the kernels' i64*) and
+// passed down by const reference.  Holds no memory and caches nothing but the two answers to "is this plan the plan of
+// these arrays?":
+//   plan        the caller's plan if it was made from row, indptr, eid, indices and both counts, else NULL
+//   plan_slots  ... from row, indptr, eid and both counts: what is true of the slots' rows and edge ids whatever the
+//               neighbour ids are (which edge-sized outputs are written in full; softmax and node_mul_edge, which have
+//               no neighbour ids)
+struct Csr {
+  const i64 *row, *indptr, *eid, *indices;
+  i64 n_chunks, n_edges;
+  const graphop_plan *plan, *plan_slots;
+  const char* names[4];   // of the four arrays in the entry point's signature, for require()
+
+  Csr(const int64_t* row_, const int64_t* indptr_, const int64_t* eid_, const int64_t* indices_, i64 C, i64 E,
+      const graphop_plan* p, const char* row_name = "row", const char* indptr_name = "indptr",
+      const char* eid_name = "eid", const char* indices_name = "indices")
+      : row((const i64*)row_), indptr((const i64*)indptr_), eid((const i64*)eid_), indices((const i64*)indices_),
+        n_chunks(C), n_edges(E), names{row_name, indptr_name, eid_name, indices_name} {
+    plan_slots = (p && p->row == row_ && p->indptr == indptr_ && p->eid == eid_ && p->info.n_chunks == C &&
+                  p->info.n_edges == E) ? p : nullptr;
+    plan = (plan_slots && p->indices == indices_) ? p : nullptr;
+  }
+
+  // every edge id is written by a pass over the slots: an edge-sized output needs no zero fill.  covered(true) asks
+  // plan_slots and is what the core ops use (graphop_hip.hip); covered() asks plan and is what the GAT family uses
+  bool covered(bool slots = false) const {
+    const graphop_plan* p = slots ? plan_slots : plan;
+    return p && p->info.full_coverage && p->info.eid_identity && p->info.indptr_monotone;
+  }
+  // a row's chunks are adjacent: rows inside one lane group's range need no atomics
+  bool owned() const { return plan && plan->info.rows_sorted; }
+  // the eid argument of a fast pass over `plan`: NULL where the plan says eid[slot] == slot
+  const i64* eid_or_null() const { return plan->info.eid_identity ? nullptr : eid; }
+
+  // the arrays the signature names, in its order; has_indices = false: an op without neighbour ids
+  int require(const char* fn, bool has_indices = true) const {
+    const void* ps[4] = {row, indptr, eid, indices};
+    for (int i = 0; i < (has_indices ? 4 : 3); ++i)
+      GO_CHECK_ARG(ps[i] != nullptr, "%s: %s is NULL", fn, names[i]);
+    return GRAPHOP_OK;
+  }
+  // Row ids address the row-side operand / output, neighbour ids the gathered one: with a plan (p: plan or plan_slots,
+  // NULL: no check) the largest of each is known, so an operand with too few rows is an error here instead of an
+  // out-of-bounds access on the device.  idx_name == NULL: row ids only.
+  static int check_bounds(const char* fn, const graphop_plan* p, const char* seg_name, i64 n_seg, const char* idx_name,
+                          i64 n_idx) {
+    if (!p) return GRAPHOP_OK;
+    GO_CHECK_ARG(p->info.max_row < n_seg, "%s: row id %lld but %s has only %lld rows", fn, (long long)p->info.max_row,
+                 seg_name, (long long)n_seg);
+    GO_CHECK_ARG(!idx_name || p->info.max_index < n_idx, "%s: neighbour id %lld but %s has only %lld rows", fn,
+                 (long long)p->info.max_index, idx_name, (long long)n_idx);
+    return GRAPHOP_OK;
+  }
+};
 
 #define GO_DISPATCH_LNV(F, ...)                                      \
   switch (F) {                                                       \
@@ -271,6 +318,10 @@ inline bool plan_matches_full(const graphop_plan* p, const i64* row, const i64* 
     case 1024: { constexpr int L = 64, NV = 4; __VA_ARGS__; } break; \
     default: break;                                                  \
   }
+
+// sparse_softmax_forward that also leaves the row statistics (max, 1 / sum) behind (stats == NULL: not); graphop_hip.hip
+int softmax_forward_stats(int dtype, const Csr& g, const void* x, void* y, i64 h, void* ws, i64 ws_rows, hipStream_t st,
+                          void* stats);
 
 #define GO_PTR(fn, p) GO_CHECK_ARG((p) != nullptr, "%s: " #p " is NULL", fn)
 #define GO_TRY(expr)                     \

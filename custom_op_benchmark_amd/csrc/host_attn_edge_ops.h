@@ -135,9 +135,9 @@ int attn_edge_forward(const char* fn, int dtype, const int64_t* row, const int64
   hipStream_t st = (hipStream_t)stream;
   const size_t es = esize(dtype);
   const i64 Fd = h * d;
-  const graphop_plan* pm = plan_matches_full(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
-                                             (const i64*)indices, n_chunks, n_edges) ? plan : nullptr;
-  GO_TRY(gat_check_plan(fn, pm, "Q / o", n_q, "K / V", n_k));
+  const Csr g(row, indptr, eid, indices, n_chunks, n_edges, plan);
+  const graphop_plan* pm = g.plan;
+  GO_TRY(Csr::check_bounds(fn, pm, "Q / o", n_q, "K / V", n_k));
   const bool slots = attn_edge_has_slots(n_chunks, n_edges, n_q, n_k, h, d);
   ChunkGeometry geo{};
   bool fast = slots && !(drop && head0 + h >= 0x7fffffffLL) && F::fast_ok(x, Fd, false) &&
@@ -157,7 +157,7 @@ int attn_edge_forward(const char* fn, int dtype, const int64_t* row, const int64
     GO_HIP(zero_async(o, es * (size_t)(n_q * Fd), st));
   }
   if (!slots) return GRAPHOP_OK;
-  GO_PTR(fn, row); GO_PTR(fn, indptr); GO_PTR(fn, eid); GO_PTR(fn, indices);
+  GO_TRY(g.require(fn));
   GO_PTR(fn, Q); GO_PTR(fn, K); GO_PTR(fn, V);
   const bool dropped = drop != nullptr;
   if (fast) {
@@ -173,7 +173,7 @@ int attn_edge_forward(const char* fn, int dtype, const int64_t* row, const int64
       ProfScope prof(F::l_fwd_rows.tag, st, F::l_fwd_rows.kernel);
       GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(dropped, DROP, {
         hipLaunchKernelGGL((F::template fwd_rows<H, D, DROP>), dim3(geo.blocks), dim3(kFastBlock), 0, st,
-                           (const i64*)pm->row, (const i64*)pm->indptr, eid_arg(pm, eid), (const i64*)pm->indices, a,
+                           g.row, g.indptr, g.eid_or_null(), g.indices, a,
                            n_chunks, (int)geo.cpg, drop_if_arg<DROP>(drop ? &hd : nullptr));
       }));
       GO_LAUNCH_CHECK();
@@ -203,8 +203,8 @@ int attn_edge_forward(const char* fn, int dtype, const int64_t* row, const int64
     {
       ProfScope prof(F::l_generic_stats.tag, st, F::l_generic_stats.kernel);
       auto pass = [&](auto sum) {
-        go_launch((F::template stats<T, decltype(sum)::value>), grid, dim3(kGenericBlock), st, (const i64*)row,
-                  (const i64*)indptr, (const i64*)eid, (const i64*)indices, (const T*)Q, (const T*)K,
+        go_launch((F::template stats<T, decltype(sum)::value>), grid, dim3(kGenericBlock), st, g.row,
+                  g.indptr, g.eid, g.indices, (const T*)Q, (const T*)K,
                   F::template generic_args<T>(x), (T*)stats, n_chunks, h, d);
       };
       pass(std::false_type{});   // the maxima
@@ -213,8 +213,8 @@ int attn_edge_forward(const char* fn, int dtype, const int64_t* row, const int64
     }
     ProfScope prof(F::l_generic_fwd.tag, st, F::l_generic_fwd.kernel);
     GO_DISPATCH_BOOL(dropped, DROP, {
-      go_launch((F::template fwd<T, DROP>), grid, dim3(kGenericBlock), st, (const i64*)row, (const i64*)indptr,
-                (const i64*)eid, (const i64*)indices, (const T*)Q, (const T*)K, (const T*)V,
+      go_launch((F::template fwd<T, DROP>), grid, dim3(kGenericBlock), st, g.row, g.indptr,
+                g.eid, g.indices, (const T*)Q, (const T*)K, (const T*)V,
                 F::template generic_args<T>(x), (const T*)stats, (T*)o, n_chunks, h, d, (i64)head0,
                 drop_arg<DROP, T>(drop));
     });
@@ -226,16 +226,17 @@ int attn_edge_forward(const char* fn, int dtype, const int64_t* row, const int64
 // one fast chunk-driver pass of the backward; grad: the rows' gradient argument of the row pass (COL = false), NULL
 // where it is not wanted and in the column pass
 template <class F, bool COL>
-int attn_edge_launch_rows(const AttnEdgeLabel& lab, const graphop_plan* plan, const i64* eid, i64 n_chunks, i64 h, i64 d,
-                          const float* own, const float* xt, const float4* st4, const typename F::Rows& x, float* out0,
-                          float* out1, float* grad, const typename F::Drop* drop, hipStream_t st) {
+int attn_edge_launch_rows(const AttnEdgeLabel& lab, const Csr& g, const i64* eid, i64 h, i64 d, const float* own,
+                          const float* xt, const float4* st4, const typename F::Rows& x, float* out0, float* out1,
+                          float* grad, const typename F::Drop* drop, hipStream_t st) {
   ProfScope prof(lab.tag, st, lab.kernel);
-  const bool owned = plan->info.rows_sorted != 0, dropped = drop != nullptr;
+  const bool owned = g.owned(), dropped = drop != nullptr;
+  const i64 n_chunks = g.n_chunks;
   const ChunkGeometry geo = attn_rows_geometry(n_chunks);
   const size_t lds = F::row_lds(x, grad, h * d);
   GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
     go_launch_lds((F::template bwd_rows<H, D, COL, OWNED, DROP>), dim3(geo.blocks), dim3(kFastBlock), lds, st,
-                  (const i64*)plan->row, (const i64*)plan->indptr, eid, (const i64*)plan->indices, own, xt, st4,
+                  g.row, g.indptr, eid, g.indices, own, xt, st4,
                   F::rows_args(x), out0, out1, grad, n_chunks, (int)geo.cpg, drop_if_arg<DROP>(drop));
   })));
   GO_LAUNCH_CHECK();
@@ -260,12 +261,11 @@ int attn_edge_backward(const char* fn, int dtype, const int64_t* row, const int6
   hipStream_t st = (hipStream_t)stream;
   const size_t es = esize(dtype);
   const i64 Fd = h * d;
-  const graphop_plan* pr = plan_matches_full(plan_r, (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r,
-                                             (const i64*)indices_r, n_row_chunks, n_edges) ? plan_r : nullptr;
-  const graphop_plan* pc = plan_matches_full(plan_c, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c,
-                                             (const i64*)indices_c, n_col_chunks, n_edges) ? plan_c : nullptr;
-  GO_TRY(gat_check_plan(fn, pr, "Q / dQ", n_q, "K / V", n_k));
-  GO_TRY(gat_check_plan(fn, pc, "K / dK / dV", n_k, "Q", n_q));
+  const Csr r(row, indptr_r, eid_r, indices_r, n_row_chunks, n_edges, plan_r, "row", "indptr_r", "eid_r", "indices_r");
+  const Csr c(col, indptr_c, eid_c, indices_c, n_col_chunks, n_edges, plan_c, "col", "indptr_c", "eid_c", "indices_c");
+  const graphop_plan *pr = r.plan, *pc = c.plan;
+  GO_TRY(Csr::check_bounds(fn, pr, "Q / dQ", n_q, "K / V", n_k));
+  GO_TRY(Csr::check_bounds(fn, pc, "K / dK / dV", n_k, "Q", n_q));
   const bool row_slots = attn_edge_has_slots(n_row_chunks, n_edges, n_q, n_k, h, d);
   const bool col_slots = attn_edge_has_slots(n_col_chunks, n_edges, n_q, n_k, h, d);
   const bool slots = row_slots || col_slots;
@@ -314,9 +314,9 @@ int attn_edge_backward(const char* fn, int dtype, const int64_t* row, const int6
   }
   if (fast_r) GO_TRY(F::row_open(x, grad_r, Fd, st));
   if (row_slots) {
-    GO_PTR(fn, row); GO_PTR(fn, indptr_r); GO_PTR(fn, eid_r); GO_PTR(fn, indices_r);
+    GO_TRY(r.require(fn));
     if (fast_r) {
-      GO_TRY((attn_edge_launch_rows<F, false>(F::l_rows_row, pr, eid_arg(pr, eid_r), n_row_chunks, h, d, qdo, kv,
+      GO_TRY((attn_edge_launch_rows<F, false>(F::l_rows_row, r, r.eid_or_null(), h, d, qdo, kv,
                                               (const float4*)P, x, (float*)dQ, nullptr, grad_r, drop ? &hd : nullptr,
                                               st)));
       GO_TRY(F::row_close(x, grad_r, Fd, st));
@@ -324,8 +324,8 @@ int attn_edge_backward(const char* fn, int dtype, const int64_t* row, const int6
       ProfScope prof(F::l_generic_bwd_row.tag, st, F::l_generic_bwd_row.kernel);
       const dim3 grid((unsigned)ceil_div(n_row_chunks, kGenericWavesPerBlock));
       GO_DISPATCH_FLOAT(dtype, T, GO_DISPATCH_BOOL(dropped, DROP, {
-        go_launch((F::template bwd_row<T, DROP>), grid, dim3(kGenericBlock), st, (const i64*)row, (const i64*)indptr_r,
-                  (const i64*)eid_r, (const i64*)indices_r, (const T*)Q, (const T*)K, (const T*)V,
+        go_launch((F::template bwd_row<T, DROP>), grid, dim3(kGenericBlock), st, r.row, r.indptr,
+                  r.eid, r.indices, (const T*)Q, (const T*)K, (const T*)V,
                   F::template generic_args<T>(x), (const T*)P, (const T*)dO, (T*)dQ, (T*)F::grad(x), n_row_chunks, h, d,
                   (i64)head0, drop_arg<DROP, T>(drop));
       }));
@@ -333,18 +333,18 @@ int attn_edge_backward(const char* fn, int dtype, const int64_t* row, const int6
     }
   }
   if (col_slots) {
-    GO_PTR(fn, col); GO_PTR(fn, indptr_c); GO_PTR(fn, eid_c); GO_PTR(fn, indices_c);
+    GO_TRY(c.require(fn));
     if (fast_c) {
-      // the column pass always reads eid_c: no eid_arg here
-      GO_TRY((attn_edge_launch_rows<F, true>(F::l_rows_col, pc, (const i64*)eid_c, n_col_chunks, h, d, kv, qdo,
+      // the column pass always reads eid_c: no eid_or_null() here
+      GO_TRY((attn_edge_launch_rows<F, true>(F::l_rows_col, c, c.eid, h, d, kv, qdo,
                                              (const float4*)P, x, (float*)dK, (float*)dV, nullptr,
                                              drop ? &hd : nullptr, st)));
     } else {
       ProfScope prof(F::l_generic_bwd_col.tag, st, F::l_generic_bwd_col.kernel);
       const dim3 grid((unsigned)ceil_div(n_col_chunks, kGenericWavesPerBlock));
       GO_DISPATCH_FLOAT(dtype, T, GO_DISPATCH_BOOL(dropped, DROP, {
-        go_launch((F::template bwd_col<T, DROP>), grid, dim3(kGenericBlock), st, (const i64*)col, (const i64*)indptr_c,
-                  (const i64*)eid_c, (const i64*)indices_c, (const T*)Q, (const T*)K, (const T*)V,
+        go_launch((F::template bwd_col<T, DROP>), grid, dim3(kGenericBlock), st, c.row, c.indptr,
+                  c.eid, c.indices, (const T*)Q, (const T*)K, (const T*)V,
                   F::template generic_args<T>(x), (const T*)P, (const T*)dO, (T*)dK, (T*)dV, n_col_chunks, h, d,
                   (i64)head0, drop_arg<DROP, T>(drop));
       }));

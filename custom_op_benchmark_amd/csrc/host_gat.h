@@ -1,7 +1,8 @@
 // Host-side helpers of the GAT family of entry points (gat.hip, gatv2.hip, gat_attention.hip, gat_edge_attention.hip,
 // gatv2_attention.hip, gatv2_edge_attention.hip, host_gat_attn_ops.h and host_gatv2_attn_ops.h): argument and plan
-// checks, the conditions of the fp32 fast kernels, the (h, d), bool and fp32 / fp64 dispatch, the one launch statement
-// of a kernel with and without edge term (go_launch, arg_if, GO_EDGE_KERNEL), the profile labels, the launch geometry
+// checks (the plan of an orientation, its bounds and its edge-id argument are host.h's Csr), the conditions of the fp32
+// fast kernels, the (h, d), bool and fp32 / fp64 dispatch, the one launch statement of a kernel with and without edge
+// term (go_launch, arg_if, GO_EDGE_KERNEL), the profile labels, the launch geometry
 // of the gather passes and the opening of the two GATv2 backwards.  Each exists once, here.  Not part of the C ABI.
 #pragma once
 #include <cstdio>
@@ -33,24 +34,6 @@ inline int gat_check(const char* fn, int dtype, i64 C, i64 C2, i64 E, i64 n_l, i
   return gat_check(fn, dtype, C, C2, E, n_l, n_r, h, 1, false);
 }
 
-// A plan of these arrays bounds its row ids and neighbour ids: an operand with too few rows is an error here.
-inline int gat_check_plan(const char* fn, const graphop_plan* p, const char* seg_name, i64 n_seg, const char* idx_name,
-                          i64 n_idx) {
-  if (!p) return GRAPHOP_OK;
-  GO_CHECK_ARG(p->info.max_row < n_seg, "%s: row id %lld but %s has only %lld rows", fn, (long long)p->info.max_row,
-               seg_name, (long long)n_seg);
-  GO_CHECK_ARG(p->info.max_index < n_idx, "%s: neighbour id %lld but %s has only %lld rows", fn,
-               (long long)p->info.max_index, idx_name, (long long)n_idx);
-  return GRAPHOP_OK;
-}
-
-inline bool a16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
-// the eid argument of a fast row-major pass with an edge operand: NULL where the plan says eid[slot] == slot
-inline const i64* eid_arg(const graphop_plan* p, const void* eid) {
-  return p->info.eid_identity ? nullptr : (const i64*)eid;
-}
-
 // a per-(node or edge, head) array as the fast kernels read and write it: aligned to its item width, 4 * min(h, 4) bytes
 inline bool gat_aligned(const void* p, i64 h) {
   const uintptr_t a = h >= 4 ? 16 : (uintptr_t)(4 * h);
@@ -65,7 +48,7 @@ inline bool gat_hd_fast_ok(int dtype, i64 h, i64 d, i64 E, i64 n_l, i64 n_r, std
   if (h * d != 64 && h * d != 128 && h * d != 256) return false;
   if (E >= 0x7fffffffLL || n_l >= 0x7fffffffLL || n_r >= 0x7fffffffLL) return false;
   for (const void* p : ps)
-    if (!a16(p)) return false;
+    if (!aligned16(p)) return false;
   return true;
 }
 
@@ -179,20 +162,14 @@ inline unsigned grid_of(i64 n) {
 }
 
 // The opening of the two GATv2 backwards (gatv2_scores_backward, gatv2_attention[_dropout]_backward), after their own
-// workspace check: the plans that match the arrays, checked against the operands' row counts, and the zero fills of
+// workspace check: the plans of the two orientations checked against the operands' row counts, and the zero fills of
 // the outputs.  The outputs of an orientation without chunks may be NULL: that half of the op is skipped.
-inline int gatv2_bwd_open(const char* fn, int dtype, const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r,
-                          const int64_t* indices_r, const int64_t* col, const int64_t* indptr_c, const int64_t* eid_c,
-                          const int64_t* indices_c, void* dxl, void* dxr, void* datt, i64 n_row_chunks,
-                          i64 n_col_chunks, i64 n_edges, i64 n_l, i64 n_r, i64 f, const graphop_plan* plan_r,
-                          const graphop_plan* plan_c, hipStream_t st, const graphop_plan** pr, const graphop_plan** pc) {
+inline int gatv2_bwd_open(const char* fn, int dtype, const Csr& r, const Csr& c, void* dxl, void* dxr, void* datt, i64 n_l,
+                          i64 n_r, i64 f, hipStream_t st) {
   const size_t es = esize(dtype);
-  *pr = plan_matches_full(plan_r, (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r, (const i64*)indices_r,
-                          n_row_chunks, n_edges) ? plan_r : nullptr;
-  *pc = plan_matches_full(plan_c, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c, (const i64*)indices_c,
-                          n_col_chunks, n_edges) ? plan_c : nullptr;
-  GO_TRY(gat_check_plan(fn, *pr, "xl / dxl", n_l, "xr", n_r));
-  GO_TRY(gat_check_plan(fn, *pc, "xr / dxr", n_r, "xl", n_l));
+  const i64 n_row_chunks = r.n_chunks, n_col_chunks = c.n_chunks;
+  GO_TRY(Csr::check_bounds(fn, r.plan, "xl / dxl", n_l, "xr", n_r));
+  GO_TRY(Csr::check_bounds(fn, c.plan, "xr / dxr", n_r, "xl", n_l));
   const bool row_half = !(dxl == nullptr && datt == nullptr && n_row_chunks == 0);
   const bool col_half = !(dxr == nullptr && n_col_chunks == 0);
   if (row_half) {

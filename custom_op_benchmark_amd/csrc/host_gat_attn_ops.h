@@ -22,9 +22,9 @@ namespace graphop {
 
 // stats = (m, 1 / l) per (row, head); rows without slots keep (-1e9, 0)
 template <bool EDGE>
-int gat_attn_stats(int dtype, const i64* row, const i64* indptr, const i64* eid, const i64* indices, const void* el,
-                   const void* er, const void* ee, void* stats, i64 C, i64 n_l, i64 h, double slope,
-                   const graphop_plan* pm, bool fast, hipStream_t st) {
+int gat_attn_stats(int dtype, const Csr& g, const void* el, const void* er, const void* ee, void* stats, i64 C, i64 n_l,
+                   i64 h, double slope, bool fast, hipStream_t st) {
+  const graphop_plan* pm = g.plan;   // (fast: not NULL)
   GO_DISPATCH_FLOAT(dtype, T, {
     hipLaunchKernelGGL((k_gat_attn_stats_init_generic<T>), dim3(grid_of(n_l * h)), dim3(256), 0, st, (T*)stats,
                        n_l * h);
@@ -44,7 +44,7 @@ int gat_attn_stats(int dtype, const i64* row, const i64* indptr, const i64* eid,
       const unsigned nbs = (unsigned)ceil_div(S, kFastBlock / G);
       const dim3 grid(nbs + (unsigned)n_long);
       go_launch(GO_EDGE_KERNEL(EDGE, k_gat_attn_stats_f32, k_gat_edge_attn_stats_f32, H, G), grid, dim3(kFastBlock), st,
-                row, indptr, arg_if<EDGE>(eid_arg(pm, eid)), indices, (const i64*)pm->seg_chunk, (const float*)el,
+                g.row, g.indptr, arg_if<EDGE>(g.eid_or_null()), g.indices, (const i64*)pm->seg_chunk, (const float*)el,
                 (const float*)er, arg_if<EDGE>((const float*)ee), (float2*)stats, S, nbs, long_len,
                 (const int*)pm->long_segs, (float)slope);
     }));
@@ -57,7 +57,7 @@ int gat_attn_stats(int dtype, const i64* row, const i64* indptr, const i64* eid,
     auto pass = [&](auto sum) {
       constexpr bool SUM = decltype(sum)::value;
       go_launch(GO_EDGE_KERNEL(EDGE, k_gat_attn_stats_generic, k_gat_edge_attn_stats_generic, T, SUM), grid,
-                dim3(kGenericBlock), st, row, indptr, arg_if<EDGE>(eid), indices, (const T*)el, (const T*)er,
+                dim3(kGenericBlock), st, g.row, g.indptr, arg_if<EDGE>(g.eid), g.indices, (const T*)el, (const T*)er,
                 arg_if<EDGE>((const T*)ee), (T*)stats, C, h, (T)slope);
     };
     pass(std::false_type{});   // the maxima
@@ -77,35 +77,34 @@ int gat_attn_forward(const char* fn, int dtype, const int64_t* row, const int64_
                      double negative_slope, const HostDrop* drop, const graphop_plan_t* plan, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const size_t es = esize(dtype);
-  const graphop_plan* pm = plan_matches_full(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
-                                             (const i64*)indices, n_chunks, n_edges) ? plan : nullptr;
-  GO_TRY(gat_check_plan(fn, pm, "el / o", n_l, "er / V", n_r));
+  const Csr g(row, indptr, eid, indices, n_chunks, n_edges, plan);
+  const graphop_plan* pm = g.plan;
+  GO_TRY(Csr::check_bounds(fn, pm, "el / o", n_l, "er / V", n_r));
   if (n_l == 0) return GRAPHOP_OK;
   GO_PTR(fn, o); GO_PTR(fn, stats);
   GO_HIP(zero_async(o, es * (size_t)(n_l * h * d), st));
   const bool slots = n_chunks > 0 && n_edges > 0;
   if (slots) {
-    GO_PTR(fn, row); GO_PTR(fn, indptr); GO_PTR(fn, eid); GO_PTR(fn, indices);
+    GO_TRY(g.require(fn));
     GO_PTR(fn, el); GO_PTR(fn, er);
     if constexpr (EDGE) GO_PTR(fn, ee);
     GO_PTR(fn, V);
   }
   const bool fast = pm && gat_hd_fast_ok(dtype, h, d, n_edges, n_l, n_r, {el, er, V, o, stats}) &&
                     (!EDGE || gat_aligned(ee, h));
-  GO_TRY(gat_attn_stats<EDGE>(dtype, (const i64*)row, (const i64*)indptr, (const i64*)eid, (const i64*)indices, el, er,
-                              ee, stats, slots ? n_chunks : 0, n_l, h, negative_slope, pm, fast, st));
+  GO_TRY(gat_attn_stats<EDGE>(dtype, g, el, er, ee, stats, slots ? n_chunks : 0, n_l, h, negative_slope, fast, st));
   if (!slots) return GRAPHOP_OK;
   const bool dropped = drop != nullptr;
   static const GatLabels lab = GO_GAT_ATTN_LABELS(EDGE, "fwd");
   ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][fast]);
   if (fast) {
     const int cpg = gat_cpg(n_chunks, tuning().spmm_cpg);
-    const bool owned = pm->info.rows_sorted != 0;
+    const bool owned = g.owned();
     const dim3 grid((unsigned)gat_grid(n_chunks, cpg));
     GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
       go_launch(GO_EDGE_KERNEL(EDGE, k_gat_attn_fwd_f32, k_gat_edge_attn_fwd_f32, H, D, OWNED, DROP), grid,
-                dim3(kFastBlock), st, (const i64*)row, (const i64*)indptr, arg_if<EDGE>(eid_arg(pm, eid)),
-                (const i64*)indices, (const float*)el, (const float*)er, arg_if<EDGE>((const float*)ee),
+                dim3(kFastBlock), st, g.row, g.indptr, arg_if<EDGE>(g.eid_or_null()),
+                g.indices, (const float*)el, (const float*)er, arg_if<EDGE>((const float*)ee),
                 (const float2*)stats, (const float*)V, (float*)o, n_chunks, cpg, (float)negative_slope,
                 drop_arg<DROP, float>(drop));
     })));
@@ -113,8 +112,8 @@ int gat_attn_forward(const char* fn, int dtype, const int64_t* row, const int64_
     const dim3 grid((unsigned)ceil_div(n_chunks, kGenericWavesPerBlock));
     GO_DISPATCH_FLOAT(dtype, T, GO_DISPATCH_BOOL(dropped, DROP, {
       go_launch(GO_EDGE_KERNEL(EDGE, k_gat_attn_fwd_generic, k_gat_edge_attn_fwd_generic, T, DROP), grid,
-                dim3(kGenericBlock), st, (const i64*)row, (const i64*)indptr, arg_if<EDGE>((const i64*)eid),
-                (const i64*)indices, (const T*)el, (const T*)er, arg_if<EDGE>((const T*)ee), (const T*)stats,
+                dim3(kGenericBlock), st, g.row, g.indptr, arg_if<EDGE>(g.eid),
+                g.indices, (const T*)el, (const T*)er, arg_if<EDGE>((const T*)ee), (const T*)stats,
                 (const T*)V, (T*)o, n_chunks, h, d, (T)negative_slope, drop_arg<DROP, T>(drop));
     }));
   }
@@ -137,12 +136,11 @@ int gat_attn_backward(const char* fn, int dtype, const int64_t* row, const int64
   GO_CHECK_ARG(workspace_bytes >= 0 && (size_t)workspace_bytes >= need,
                "%s: workspace of %lld bytes needed (n_l * h * 4 values), got %lld", fn, (long long)need,
                (long long)workspace_bytes);
-  const graphop_plan* pr = plan_matches_full(plan_r, (const i64*)row, (const i64*)indptr_r, (const i64*)eid_r,
-                                             (const i64*)indices_r, n_row_chunks, n_edges) ? plan_r : nullptr;
-  const graphop_plan* pc = plan_matches_full(plan_c, (const i64*)col, (const i64*)indptr_c, (const i64*)eid_c,
-                                             (const i64*)indices_c, n_col_chunks, n_edges) ? plan_c : nullptr;
-  GO_TRY(gat_check_plan(fn, pr, "el / del", n_l, "er / V", n_r));
-  GO_TRY(gat_check_plan(fn, pc, "er / der", n_r, "el", n_l));
+  const Csr r(row, indptr_r, eid_r, indices_r, n_row_chunks, n_edges, plan_r, "row", "indptr_r", "eid_r", "indices_r");
+  const Csr c(col, indptr_c, eid_c, indices_c, n_col_chunks, n_edges, plan_c, "col", "indptr_c", "eid_c", "indices_c");
+  const graphop_plan *pr = r.plan, *pc = c.plan;
+  GO_TRY(Csr::check_bounds(fn, pr, "el / del", n_l, "er / V", n_r));
+  GO_TRY(Csr::check_bounds(fn, pc, "er / der", n_r, "el", n_l));
   if (n_l > 0 && !(del == nullptr && n_row_chunks == 0)) {
     GO_PTR(fn, del);
     GO_HIP(zero_async(del, es * (size_t)(n_l * h), st));
@@ -155,7 +153,7 @@ int gat_attn_backward(const char* fn, int dtype, const int64_t* row, const int64
   if constexpr (EDGE) {
     // edge ids that no row-major slot names get dee = 0: skip the fill only where the plan proves every id is written
     const bool dee_run = slots && n_l > 0 && n_r > 0 && n_row_chunks > 0;
-    const bool covered = dee_run && pr && pr->info.full_coverage && pr->info.eid_identity && pr->info.indptr_monotone;
+    const bool covered = dee_run && r.covered();
     if (dee && n_edges > 0 && !covered) GO_HIP(zero_async(dee, es * (size_t)(n_edges * h), st));
   }
   if (!slots || n_l == 0 || n_r == 0) return GRAPHOP_OK;
@@ -187,19 +185,19 @@ int gat_attn_backward(const char* fn, int dtype, const int64_t* row, const int64
     GO_LAUNCH_CHECK();
   }
   if (n_row_chunks > 0) {
-    GO_PTR(fn, row); GO_PTR(fn, indptr_r); GO_PTR(fn, eid_r); GO_PTR(fn, indices_r);
+    GO_TRY(r.require(fn));
     const i64 C = n_row_chunks;
     const bool fast = ok && pr;
     static const GatLabels lab = GO_GAT_ATTN_LABELS(EDGE, "bwd_row");
     ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][fast]);
     if (fast) {
       const int cpg = gat_cpg(C, tuning().spmm_cpg);
-      const bool owned = pr->info.rows_sorted != 0;
+      const bool owned = r.owned();
       const dim3 grid((unsigned)gat_grid(C, cpg));
       GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
         go_launch(GO_EDGE_KERNEL(EDGE, k_gat_attn_bwd_row_f32, k_gat_edge_attn_bwd_row_f32, H, D, OWNED, DROP), grid,
-                  dim3(kFastBlock), st, (const i64*)row, (const i64*)indptr_r, arg_if<EDGE>(eid_arg(pr, eid_r)),
-                  (const i64*)indices_r, (const float*)er, arg_if<EDGE>((const float*)ee), (const float*)V,
+                  dim3(kFastBlock), st, r.row, r.indptr, arg_if<EDGE>(r.eid_or_null()),
+                  r.indices, (const float*)er, arg_if<EDGE>((const float*)ee), (const float*)V,
                   (const float4*)workspace, (const float*)dO, (float*)del, arg_if<EDGE>((float*)dee), C, cpg, slope,
                   drop_arg<DROP, float>(drop));
       })));
@@ -207,27 +205,27 @@ int gat_attn_backward(const char* fn, int dtype, const int64_t* row, const int64
       const dim3 grid((unsigned)ceil_div(C, kGenericWavesPerBlock));
       GO_DISPATCH_FLOAT(dtype, T, GO_DISPATCH_BOOL(dropped, DROP, {
         go_launch(GO_EDGE_KERNEL(EDGE, k_gat_attn_bwd_row_generic, k_gat_edge_attn_bwd_row_generic, T, DROP), grid,
-                  dim3(kGenericBlock), st, (const i64*)row, (const i64*)indptr_r, arg_if<EDGE>((const i64*)eid_r),
-                  (const i64*)indices_r, (const T*)er, arg_if<EDGE>((const T*)ee), (const T*)V, (const T*)workspace,
+                  dim3(kGenericBlock), st, r.row, r.indptr, arg_if<EDGE>(r.eid),
+                  r.indices, (const T*)er, arg_if<EDGE>((const T*)ee), (const T*)V, (const T*)workspace,
                   (const T*)dO, (T*)del, arg_if<EDGE>((T*)dee), C, h, d, (T)negative_slope, drop_arg<DROP, T>(drop));
       }));
     }
     GO_LAUNCH_CHECK();
   }
   if (n_col_chunks > 0) {
-    GO_PTR(fn, col); GO_PTR(fn, indptr_c); GO_PTR(fn, eid_c); GO_PTR(fn, indices_c);
+    GO_TRY(c.require(fn));
     const i64 C = n_col_chunks;
     const bool fast = ok && pc;
     static const GatLabels lab = GO_GAT_ATTN_LABELS(EDGE, "bwd_col");
     ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][fast]);
     if (fast) {
       const int cpg = gat_cpg(C, tuning().spmm_cpg);
-      const bool owned = pc->info.rows_sorted != 0;
+      const bool owned = c.owned();
       const dim3 grid((unsigned)gat_grid(C, cpg));
       GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
         go_launch(GO_EDGE_KERNEL(EDGE, k_gat_attn_bwd_col_f32, k_gat_edge_attn_bwd_col_f32, H, D, OWNED, DROP), grid,
-                  dim3(kFastBlock), st, (const i64*)col, (const i64*)indptr_c, arg_if<EDGE>(eid_arg(pc, eid_c)),
-                  (const i64*)indices_c, (const float*)er, arg_if<EDGE>((const float*)ee), (const float*)V,
+                  dim3(kFastBlock), st, c.row, c.indptr, arg_if<EDGE>(c.eid_or_null()),
+                  c.indices, (const float*)er, arg_if<EDGE>((const float*)ee), (const float*)V,
                   (const float4*)workspace, (const float*)dO, (float*)der, (float*)dV, C, cpg, slope,
                   drop_arg<DROP, float>(drop));
       })));
@@ -235,8 +233,8 @@ int gat_attn_backward(const char* fn, int dtype, const int64_t* row, const int64
       const dim3 grid((unsigned)ceil_div(C, kGenericWavesPerBlock));
       GO_DISPATCH_FLOAT(dtype, T, GO_DISPATCH_BOOL(dropped, DROP, {
         go_launch(GO_EDGE_KERNEL(EDGE, k_gat_attn_bwd_col_generic, k_gat_edge_attn_bwd_col_generic, T, DROP), grid,
-                  dim3(kGenericBlock), st, (const i64*)col, (const i64*)indptr_c, arg_if<EDGE>((const i64*)eid_c),
-                  (const i64*)indices_c, (const T*)er, arg_if<EDGE>((const T*)ee), (const T*)V, (const T*)workspace,
+                  dim3(kGenericBlock), st, c.row, c.indptr, arg_if<EDGE>(c.eid),
+                  c.indices, (const T*)er, arg_if<EDGE>((const T*)ee), (const T*)V, (const T*)workspace,
                   (const T*)dO, (T*)der, (T*)dV, C, h, d, (T)negative_slope, drop_arg<DROP, T>(drop));
       }));
     }

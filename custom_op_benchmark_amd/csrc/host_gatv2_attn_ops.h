@@ -64,9 +64,9 @@ int gv2attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t
                     double negative_slope, const HostDrop* drop, const graphop_plan_t* plan, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const size_t es = esize(dtype);
-  const graphop_plan* pm = plan_matches_full(plan, (const i64*)row, (const i64*)indptr, (const i64*)eid,
-                                             (const i64*)indices, n_chunks, n_edges) ? plan : nullptr;
-  GO_TRY(gat_check_plan(fn, pm, "xl / o", n_l, "xr", n_r));
+  const Csr g(row, indptr, eid, indices, n_chunks, n_edges, plan);
+  const graphop_plan* pm = g.plan;
+  GO_TRY(Csr::check_bounds(fn, pm, "xl / o", n_l, "xr", n_r));
   if (n_l == 0) return GRAPHOP_OK;
   GO_PTR(fn, o); GO_PTR(fn, stats);
   // rows without chunks keep o = 0 and stats = (-1e9, 0)
@@ -77,12 +77,12 @@ int gv2attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t
   });
   GO_LAUNCH_CHECK();
   if (n_chunks == 0 || n_edges == 0 || n_r == 0) return GRAPHOP_OK;
-  GO_PTR(fn, row); GO_PTR(fn, indptr); GO_PTR(fn, eid); GO_PTR(fn, indices);
+  GO_TRY(g.require(fn));
   GO_PTR(fn, xl); GO_PTR(fn, xr);
   if constexpr (EDGE) GO_PTR(fn, xe);
   GO_PTR(fn, att);
   const bool fast = pm && pm->info.row_owned && pm->seg_chunk &&
-                    gat_hd_fast_ok(dtype, h, d, n_edges, n_l, n_r, {xl, xr, att, o, stats}) && (!EDGE || a16(xe));
+                    gat_hd_fast_ok(dtype, h, d, n_edges, n_l, n_r, {xl, xr, att, o, stats}) && (!EDGE || aligned16(xe));
   const bool dropped = drop != nullptr;
   static const GatLabels lab = GO_GV2_ATTN_LABELS(EDGE, "fwd");
   if (fast) {
@@ -94,8 +94,8 @@ int gv2attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t
     const unsigned nbs = (unsigned)ceil_div(S, (i64)(kFastBlock / kGatGroup));
     const dim3 grid(nbs + (unsigned)n_long);
     GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(dropped, DROP, {
-      go_launch(gv2attn_fwd_kernel<H, D, DROP, EDGE>(), grid, dim3(kFastBlock), st, (const i64*)row,
-                (const i64*)indptr, arg_if<EDGE>(eid_arg(pm, eid)), (const i64*)indices, (const i64*)pm->seg_chunk,
+      go_launch(gv2attn_fwd_kernel<H, D, DROP, EDGE>(), grid, dim3(kFastBlock), st, g.row,
+                g.indptr, arg_if<EDGE>(g.eid_or_null()), g.indices, (const i64*)pm->seg_chunk,
                 (const float*)xl, (const float*)xr, arg_if<EDGE>((const float*)xe), (const float*)att, (float*)o,
                 (float2*)stats, S, nbs, long_len, (const int*)pm->long_segs, (float)negative_slope,
                 drop_arg<DROP, float>(drop));
@@ -109,8 +109,8 @@ int gv2attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t
     auto pass = [&](auto sum) {
       constexpr bool SUM = decltype(sum)::value;
       go_launch(GO_EDGE_KERNEL(EDGE, k_gv2attn_stats_generic, k_gv2edge_stats_generic, T, SUM), grid,
-                dim3(kGenericBlock), st, (const i64*)row, (const i64*)indptr, arg_if<EDGE>((const i64*)eid),
-                (const i64*)indices, (const T*)xl, (const T*)xr, arg_if<EDGE>((const T*)xe), (const T*)att, (T*)stats,
+                dim3(kGenericBlock), st, g.row, g.indptr, arg_if<EDGE>(g.eid),
+                g.indices, (const T*)xl, (const T*)xr, arg_if<EDGE>((const T*)xe), (const T*)att, (T*)stats,
                 n_chunks, h, d, (T)negative_slope);
     };
     pass(std::false_type{});   // the maxima
@@ -119,7 +119,7 @@ int gv2attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t
                        n_l * h);
     GO_DISPATCH_BOOL(dropped, DROP, {
       go_launch(GO_EDGE_KERNEL(EDGE, k_gv2attn_fwd_generic, k_gv2edge_fwd_generic, T, DROP), grid, dim3(kGenericBlock),
-                st, (const i64*)row, (const i64*)indptr, arg_if<EDGE>((const i64*)eid), (const i64*)indices,
+                st, g.row, g.indptr, arg_if<EDGE>(g.eid), g.indices,
                 (const T*)xl, (const T*)xr, arg_if<EDGE>((const T*)xe), (const T*)att, (const T*)stats, (T*)o, n_chunks,
                 h, d, (T)negative_slope, drop_arg<DROP, T>(drop));
     });
@@ -146,12 +146,13 @@ int gv2attn_backward(const char* fn, int dtype, const int64_t* row, const int64_
   GO_CHECK_ARG(workspace_bytes >= 0 && (size_t)workspace_bytes >= need,
                "%s: workspace of %lld bytes needed (n_l * h * 4 + min(ceil(n_row_chunks / 16), 8192) * h * d values), "
                "got %lld", fn, (long long)need, (long long)workspace_bytes);
-  const graphop_plan *pr, *pc;
-  GO_TRY(gatv2_bwd_open(fn, dtype, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, dxl, dxr, datt,
-                        n_row_chunks, n_col_chunks, n_edges, n_l, n_r, f, plan_r, plan_c, st, &pr, &pc));
+  const Csr r(row, indptr_r, eid_r, indices_r, n_row_chunks, n_edges, plan_r, "row", "indptr_r", "eid_r", "indices_r");
+  const Csr c(col, indptr_c, eid_c, indices_c, n_col_chunks, n_edges, plan_c, "col", "indptr_c", "eid_c", "indices_c");
+  const graphop_plan *pr = r.plan, *pc = c.plan;
+  GO_TRY(gatv2_bwd_open(fn, dtype, r, c, dxl, dxr, datt, n_l, n_r, f, st));
   if constexpr (EDGE) {
     // edge ids that no row-major slot names get dxe = 0: skip the fill only where the plan proves every id is written
-    const bool covered = row_slots && pr && pr->info.full_coverage && pr->info.eid_identity && pr->info.indptr_monotone;
+    const bool covered = row_slots && r.covered();
     if (dxe && n_edges > 0 && !covered) GO_HIP(zero_async(dxe, es * (size_t)(n_edges * f), st));
   }
   if (!slots) return GRAPHOP_OK;
@@ -160,7 +161,7 @@ int gv2attn_backward(const char* fn, int dtype, const int64_t* row, const int64_
   GO_PTR(fn, att); GO_PTR(fn, o); GO_PTR(fn, stats); GO_PTR(fn, dO);
   GO_PTR(fn, workspace);
   const bool ok = gat_hd_fast_ok(dtype, h, d, n_edges, n_l, n_r, {xl, xr, att, o, stats, dO, workspace}) &&
-                  (!EDGE || (a16(xe) && a16(dxe)));
+                  (!EDGE || (aligned16(xe) && aligned16(dxe)));
   const float slope = (float)negative_slope;
   const bool dropped = drop != nullptr;
   void* part = (char*)workspace + es * (size_t)p_values;
@@ -182,7 +183,7 @@ int gv2attn_backward(const char* fn, int dtype, const int64_t* row, const int64_
     GO_LAUNCH_CHECK();
   }
   if (row_slots) {
-    GO_PTR(fn, row); GO_PTR(fn, indptr_r); GO_PTR(fn, eid_r); GO_PTR(fn, indices_r);
+    GO_TRY(r.require(fn));
     GO_PTR(fn, dxl); GO_PTR(fn, datt);
     const i64 C = n_row_chunks;
     static const GatLabels lab = GO_GV2_ATTN_LABELS(EDGE, "bwd_row");
@@ -190,11 +191,11 @@ int gv2attn_backward(const char* fn, int dtype, const int64_t* row, const int64_
       const GatRowPass geo = gat_row_pass(C, tuning().spmm_cpg);   // n_blocks <= gat_part_rows(C)
       {
         ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][1]);
-        const bool owned = pr->info.rows_sorted != 0;
+        const bool owned = r.owned();
         const dim3 grid((unsigned)geo.n_blocks);
         GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
-          go_launch(gv2attn_bwd_row_kernel<H, D, OWNED, DROP, EDGE>(), grid, dim3(kFastBlock), st, (const i64*)row,
-                    (const i64*)indptr_r, arg_if<EDGE>(eid_arg(pr, eid_r)), (const i64*)indices_r, (const float*)xl,
+          go_launch(gv2attn_bwd_row_kernel<H, D, OWNED, DROP, EDGE>(), grid, dim3(kFastBlock), st, r.row,
+                    r.indptr, arg_if<EDGE>(r.eid_or_null()), r.indices, (const float*)xl,
                     (const float*)xr, arg_if<EDGE>((const float*)xe), (const float*)att, (const float4*)workspace,
                     (const float*)dO, (float*)dxl, arg_if<EDGE>((float*)dxe), (float4*)part, C, geo.cpg, slope,
                     drop_arg<DROP, float>(drop));
@@ -208,8 +209,8 @@ int gv2attn_backward(const char* fn, int dtype, const int64_t* row, const int64_
       const dim3 grid((unsigned)ceil_div(C, kGenericWavesPerBlock));
       GO_DISPATCH_FLOAT(dtype, T, GO_DISPATCH_BOOL(dropped, DROP, {
         go_launch(GO_EDGE_KERNEL(EDGE, k_gv2attn_bwd_row_generic, k_gv2edge_bwd_row_generic, T, DROP), grid,
-                  dim3(kGenericBlock), st, (const i64*)row, (const i64*)indptr_r, arg_if<EDGE>((const i64*)eid_r),
-                  (const i64*)indices_r, (const T*)xl, (const T*)xr, arg_if<EDGE>((const T*)xe), (const T*)att,
+                  dim3(kGenericBlock), st, r.row, r.indptr, arg_if<EDGE>(r.eid),
+                  r.indices, (const T*)xl, (const T*)xr, arg_if<EDGE>((const T*)xe), (const T*)att,
                   (const T*)workspace, (const T*)dO, (T*)dxl, arg_if<EDGE>((T*)dxe), (T*)datt, C, h, d,
                   (T)negative_slope, drop_arg<DROP, T>(drop));
       }));
@@ -217,19 +218,19 @@ int gv2attn_backward(const char* fn, int dtype, const int64_t* row, const int64_
     GO_LAUNCH_CHECK();
   }
   if (col_slots) {
-    GO_PTR(fn, col); GO_PTR(fn, indptr_c); GO_PTR(fn, eid_c); GO_PTR(fn, indices_c);
+    GO_TRY(c.require(fn));
     GO_PTR(fn, dxr);
     const i64 C = n_col_chunks;
     static const GatLabels lab = GO_GV2_ATTN_LABELS(EDGE, "bwd_col");
     if (ok && pc && ((uintptr_t)dxr & 15) == 0) {
       ProfScope prof(lab.tag[dropped], st, lab.kernel[dropped][1]);
       const int cpg = gat_cpg(C, tuning().spmm_cpg);
-      const bool owned = pc->info.rows_sorted != 0;
+      const bool owned = c.owned();
       const dim3 grid((unsigned)gat_grid(C, cpg));
       GO_DISPATCH_GAT_HD(h, d, GO_DISPATCH_BOOL(owned, OWNED, GO_DISPATCH_BOOL(dropped, DROP, {
-        // with the edge row the column pass always reads eid_c: no eid_arg here
-        go_launch(gv2attn_bwd_col_kernel<H, D, OWNED, DROP, EDGE>(), grid, dim3(kFastBlock), st, (const i64*)col,
-                  (const i64*)indptr_c, arg_if<EDGE>((const i64*)eid_c), (const i64*)indices_c, (const float*)xl,
+        // with the edge row the column pass always reads eid_c: no eid_or_null() here
+        go_launch(gv2attn_bwd_col_kernel<H, D, OWNED, DROP, EDGE>(), grid, dim3(kFastBlock), st, c.row,
+                  c.indptr, arg_if<EDGE>(c.eid), c.indices, (const float*)xl,
                   (const float*)xr, arg_if<EDGE>((const float*)xe), (const float*)att, (const float4*)workspace,
                   (const float*)dO, (float*)dxr, C, cpg, slope, drop_arg<DROP, float>(drop));
       })));
@@ -238,8 +239,8 @@ int gv2attn_backward(const char* fn, int dtype, const int64_t* row, const int64_
       const dim3 grid((unsigned)ceil_div(C, kGenericWavesPerBlock));
       GO_DISPATCH_FLOAT(dtype, T, GO_DISPATCH_BOOL(dropped, DROP, {
         go_launch(GO_EDGE_KERNEL(EDGE, k_gv2attn_bwd_col_generic, k_gv2edge_bwd_col_generic, T, DROP), grid,
-                  dim3(kGenericBlock), st, (const i64*)col, (const i64*)indptr_c, arg_if<EDGE>((const i64*)eid_c),
-                  (const i64*)indices_c, (const T*)xl, (const T*)xr, arg_if<EDGE>((const T*)xe), (const T*)att,
+                  dim3(kGenericBlock), st, c.row, c.indptr, arg_if<EDGE>(c.eid),
+                  c.indices, (const T*)xl, (const T*)xr, arg_if<EDGE>((const T*)xe), (const T*)att,
                   (const T*)workspace, (const T*)dO, (T*)dxr, C, h, d, (T)negative_slope, drop_arg<DROP, T>(drop));
       }));
     }
