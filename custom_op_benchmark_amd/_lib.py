@@ -143,6 +143,13 @@ _SIGNATURES = {
     + [ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _c64],
     "graphop_attention_etype_backward": [ctypes.c_int] + [_P] * 20 + [_c64] * 8 + [_P, _c64, _P, _P, _P]
     + [ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _c64],
+    # ... with an edge-type score bias: the argument lists of the etype entry points, B where R is, dB where dR is
+    "graphop_attention_tbias_workspace_bytes": [ctypes.c_int, ctypes.c_int] + [_c64] * 6 + [_P, _P, _P,
+                                                                                             ctypes.POINTER(_c64)],
+    "graphop_attention_tbias_forward": [ctypes.c_int] + [_P] * 11 + [_c64] * 7 + [_P, _c64, _P, _P]
+    + [ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _c64],
+    "graphop_attention_tbias_backward": [ctypes.c_int] + [_P] * 20 + [_c64] * 8 + [_P, _c64, _P, _P, _P]
+    + [ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _c64],
     # the weights of those ops from their row statistics: Q, K, stats, b | NULL, xe | NULL, a; no workspace
     "graphop_attention_weights": [ctypes.c_int] + [_P] * 10 + [_c64] * 6 + [_P, _P],
 }

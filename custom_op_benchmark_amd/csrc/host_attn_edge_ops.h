@@ -1,8 +1,10 @@
 // The workspace query, the forward and the backward of the fused dot-product attention ops that add a per-edge row to
 // the key and the value, behind the entry points of attention_edge.hip (the row is xe[e]) and
-// attention_etype.hip (the row is R[etype[e]]; 4.5o).  One implementation: the checks and their order, the early
+// attention_etype.hip (the row is R[etype[e]]; 4.5o), and of the op that adds a per-type scalar to the score instead,
+// behind those of attention_tbias.hip (the "row" is the h words B[etype[e], :]; 4.5p: that form carries h in its Rows
+// and ignores the F = h d it is handed).  One implementation: the checks and their order, the early
 // returns, the fast / generic decisions, the workspace layouts, the zero fills and the sequence of launches are the same
-// for both.  Each form's kernel header emits kernels without a template, so it belongs to its own translation unit and
+// for all.  Each form's kernel header emits kernels without a template, so it belongs to its own translation unit and
 // is not included here: the including unit describes its form in a struct F and this text is a template over it.
 // A form states
 //   GO_ATTN_EDGE_FORM_NAMES(edge, Edge)   its kernels, its record types (Drop, FwdArgs), its profile tags and labels;

@@ -577,13 +577,42 @@ void check_attn_etype_table(const char* fn, const at::Tensor& R, const at::Tenso
   CHECK_CONTIGUOUS(etype); CHECK_CUDA(etype);
 }
 
-// The forward of the two ops with an edge row in key and value, as `fn`.  etype == nullptr: rows is xe
-// (graphop_attention_edge_forward); else rows is the table R (graphop_attention_etype_forward).
+// an edge-type score bias (include/graphop_hip.h: graphop_attention_tbias_*), the score term being B[etype[e], k]:
+// B: a contiguous device tensor (n_types) for 2-D Q / K / V, else (n_types, h), in Q's dtype, n_types >= 1 unless the
+// graph has no edge; etype: a contiguous device int32 tensor (n_edges).  The values of etype are not looked at (that
+// would synchronise): the kernels clamp them.
+void check_attn_tbias_table(const char* fn, const at::Tensor& B, const at::Tensor& etype, const at::Tensor& Q, int64_t e) {
+  CHECK_SAME_DTYPE(Q, B);
+  TORCH_CHECK(B.dim() == Q.dim() - 1 && B.sizes().slice(1) == Q.sizes().slice(1, Q.dim() - 2),
+              fn, ": B must be (n_types) for 2-D Q / K / V, else (n_types, h), got B ", B.sizes(), ", Q ", Q.sizes());
+  TORCH_CHECK(B.size(0) > 0 || e == 0, fn, ": B must hold at least one type (n_edges = ", e, ")");
+  TORCH_CHECK(etype.scalar_type() == at::kInt, fn, ": etype must be torch.int32, got ", etype.scalar_type());
+  TORCH_CHECK(etype.dim() == 1 && etype.size(0) == e,
+              fn, ": etype must be (n_edges) with n_edges = ", e, ", got ", etype.sizes());
+  CHECK_CONTIGUOUS(B); CHECK_CUDA(B);
+  CHECK_CONTIGUOUS(etype); CHECK_CUDA(etype);
+}
+
+// The entry points of the two ops that take a table and the types: one argument list, so one pointer type each
+struct AttnTableAbi {
+  decltype(&graphop_attention_etype_workspace_bytes) query;
+  decltype(&graphop_attention_etype_forward) forward;
+  decltype(&graphop_attention_etype_backward) backward;
+  decltype(&check_attn_etype_table) check;
+};
+const AttnTableAbi kAttnEtypeAbi = {graphop_attention_etype_workspace_bytes, graphop_attention_etype_forward,
+                                    graphop_attention_etype_backward, check_attn_etype_table};
+const AttnTableAbi kAttnTbiasAbi = {graphop_attention_tbias_workspace_bytes, graphop_attention_tbias_forward,
+                                    graphop_attention_tbias_backward, check_attn_tbias_table};
+
+// The forward of the ops with an edge row in key and value and of the op with an edge-type score bias, as `fn`.
+// etype == nullptr: rows is xe (graphop_attention_edge_forward); else rows is the table of `abi`: R
+// (graphop_attention_etype_forward) or B (graphop_attention_tbias_forward).
 std::vector<at::Tensor> attention_edge_forward_impl(const char* fn, const at::Tensor& row, const at::Tensor& indptr,
                                                     const at::Tensor& eid, const at::Tensor& indices, const at::Tensor& Q,
                                                     const at::Tensor& K, const at::Tensor& V, const at::Tensor& rows,
                                                     const at::Tensor* etype, double p, int64_t seed, int64_t offset,
-                                                    int64_t head0) {
+                                                    int64_t head0, const AttnTableAbi& abi = kAttnEtypeAbi) {
   const DropSpec drop = drop_spec(fn, p, seed, offset);
   head0_checked(fn, head0);
   CHECK_CSR(row, indptr, eid, indices);
@@ -592,7 +621,7 @@ std::vector<at::Tensor> attention_edge_forward_impl(const char* fn, const at::Te
               fn, ": Q (n_q,[h,]d), K and V (n_k,[h,]d) expected");
   CHECK_SAME_DTYPE(Q, K); CHECK_SAME_DTYPE(Q, V);
   const int64_t e = eid.size(0), d = Q.size(-1), h = Q.dim() == 2 ? 1 : Q.size(1), n_q = Q.size(0), n_k = K.size(0);
-  if (etype) check_attn_etype_table(fn, rows, *etype, Q, e);
+  if (etype) abi.check(fn, rows, *etype, Q, e);
   else check_attn_edge_rows(fn, rows, Q, e);
   const int64_t n_types = rows.size(0);
   DeviceGuard dg(Q);
@@ -601,16 +630,14 @@ std::vector<at::Tensor> attention_edge_forward_impl(const char* fn, const at::Te
   const auto pp = get_plan(row, indptr, eid, indices, n_k);
   const auto& pl = *pp;
   int64_t nbytes = 0;
-  check(etype ? graphop_attention_etype_workspace_bytes(dtype_code(Q), 0, e, n_q, n_k, h, d, n_types, pl.plan, nullptr,
-                                                        stream_of(Q), &nbytes)
+  check(etype ? abi.query(dtype_code(Q), 0, e, n_q, n_k, h, d, n_types, pl.plan, nullptr, stream_of(Q), &nbytes)
               : graphop_attention_edge_workspace_bytes(dtype_code(Q), 0, e, n_q, n_k, h, d, pl.plan, nullptr,
                                                        stream_of(Q), &nbytes));
   auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, Q.options().dtype(at::kByte));
   if (etype)
-    check(graphop_attention_etype_forward(dtype_code(Q), ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(V),
-                                          vp(rows), etype->data_ptr<int32_t>(), vp(o), vp(stats), row.size(0), e, n_q, n_k,
-                                          h, d, n_types, ws.data_ptr(), nbytes, pl.plan, stream_of(Q), drop.p, drop.seed,
-                                          drop.offset, head0));
+    check(abi.forward(dtype_code(Q), ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(V), vp(rows),
+                      etype->data_ptr<int32_t>(), vp(o), vp(stats), row.size(0), e, n_q, n_k, h, d, n_types, ws.data_ptr(),
+                      nbytes, pl.plan, stream_of(Q), drop.p, drop.seed, drop.offset, head0));
   else
     check(graphop_attention_edge_forward(dtype_code(Q), ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(V),
                                          vp(rows), vp(o), vp(stats), row.size(0), e, n_q, n_k, h, d, ws.data_ptr(), nbytes,
@@ -642,7 +669,8 @@ std::vector<at::Tensor> attention_edge_backward_impl(const char* fn, const at::T
                                                      const at::Tensor& Q, const at::Tensor& K, const at::Tensor& V,
                                                      const at::Tensor& rows, const at::Tensor* etype, const at::Tensor& o,
                                                      const at::Tensor& stats, const at::Tensor& dO_, double p,
-                                                     int64_t seed, int64_t offset, int64_t head0, bool need_dx) {
+                                                     int64_t seed, int64_t offset, int64_t head0, bool need_dx,
+                                                     const AttnTableAbi& abi = kAttnEtypeAbi) {
   const DropSpec drop = drop_spec(fn, p, seed, offset);
   head0_checked(fn, head0);
   CHECK_CSR(row, indptr_r, eid_r, indices_r);
@@ -656,7 +684,7 @@ std::vector<at::Tensor> attention_edge_backward_impl(const char* fn, const at::T
   const int64_t e = eid_r.size(0), d = Q.size(-1), h = Q.dim() == 2 ? 1 : Q.size(1), n_q = Q.size(0), n_k = K.size(0);
   TORCH_CHECK(o.sizes() == Q.sizes() && dO.sizes() == Q.sizes() && stats.numel() == n_q * h * 2,
               fn, ": o, dO must match Q and stats must be (n_q, h, 2)");
-  if (etype) check_attn_etype_table(fn, rows, *etype, Q, e);
+  if (etype) abi.check(fn, rows, *etype, Q, e);
   else check_attn_edge_rows(fn, rows, Q, e);
   const int64_t n_types = rows.size(0);
   DeviceGuard dg(Q);
@@ -665,17 +693,16 @@ std::vector<at::Tensor> attention_edge_backward_impl(const char* fn, const at::T
   const auto ppc = get_plan(col, indptr_c, eid_c, indices_c, n_q);
   const auto &pr = *ppr, &pc = *ppc;
   int64_t nbytes = 0;
-  check(etype ? graphop_attention_etype_workspace_bytes(dtype_code(Q), 1, e, n_q, n_k, h, d, n_types, pr.plan, pc.plan,
-                                                        stream_of(Q), &nbytes)
+  check(etype ? abi.query(dtype_code(Q), 1, e, n_q, n_k, h, d, n_types, pr.plan, pc.plan, stream_of(Q), &nbytes)
               : graphop_attention_edge_workspace_bytes(dtype_code(Q), 1, e, n_q, n_k, h, d, pr.plan, pc.plan,
                                                        stream_of(Q), &nbytes));
   auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, Q.options().dtype(at::kByte));
-  // dR: the call fills it.  dxe[e] is written once per row-major slot: only a chunk list that leaves slots out needs
+  // dR, dB: the call fills it.  dxe[e] is written once per row-major slot: only a chunk list that leaves slots out needs
   // the zeros
   auto dx = !need_dx ? at::empty({0}, rows.options())
                      : (etype || pr.info.full_coverage ? at::empty_like(rows) : at::zeros_like(rows));
   if (etype)
-    check(graphop_attention_etype_backward(
+    check(abi.backward(
         dtype_code(Q), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c), ip(indices_c),
         vp(Q), vp(K), vp(V), vp(rows), etype->data_ptr<int32_t>(), vp(o), vp(stats), vp(dO), vp(dQ), vp(dK), vp(dV),
         need_dx ? vp(dx) : nullptr, row.size(0), col.size(0), e, n_q, n_k, h, d, n_types, ws.data_ptr(), nbytes, pr.plan,
@@ -710,6 +737,27 @@ std::vector<at::Tensor> attention_etype_backward(const at::Tensor& row, const at
                                                  int64_t head0, bool need_dR) {
   return attention_edge_backward_impl("attention_etype_backward", row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
                                       indices_c, Q, K, V, R, &etype, o, stats, dO, p, seed, offset, head0, need_dR);
+}
+
+std::vector<at::Tensor> attention_tbias_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
+                                                const at::Tensor& indices, const at::Tensor& Q, const at::Tensor& K,
+                                                const at::Tensor& V, const at::Tensor& B, const at::Tensor& etype,
+                                                double p, int64_t seed, int64_t offset, int64_t head0) {
+  return attention_edge_forward_impl("attention_tbias_forward", row, indptr, eid, indices, Q, K, V, B, &etype, p, seed,
+                                     offset, head0, kAttnTbiasAbi);
+}
+
+std::vector<at::Tensor> attention_tbias_backward(const at::Tensor& row, const at::Tensor& indptr_r,
+                                                 const at::Tensor& eid_r, const at::Tensor& indices_r,
+                                                 const at::Tensor& col, const at::Tensor& indptr_c,
+                                                 const at::Tensor& eid_c, const at::Tensor& indices_c, const at::Tensor& Q,
+                                                 const at::Tensor& K, const at::Tensor& V, const at::Tensor& B,
+                                                 const at::Tensor& etype, const at::Tensor& o, const at::Tensor& stats,
+                                                 const at::Tensor& dO, double p, int64_t seed, int64_t offset,
+                                                 int64_t head0, bool need_dB) {
+  return attention_edge_backward_impl("attention_tbias_backward", row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
+                                      indices_c, Q, K, V, B, &etype, o, stats, dO, p, seed, offset, head0, need_dB,
+                                      kAttnTbiasAbi);
 }
 
 // ---- the weights of the fused attention ops from their row statistics (include/graphop_hip.h: graphop_attention_weights)
@@ -1279,6 +1327,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("eid_c"), py::arg("indices_c"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("R"), py::arg("etype"),
         py::arg("o"), py::arg("stats"), py::arg("dO"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0,
         py::arg("head0") = 0, py::arg("need_dR") = true);
+  // (and its form with an edge-type score bias: <Q_i, K_j> + B[etype[e], k])
+  m.def("attention_tbias_forward", &attention_tbias_forward,
+        "Fused attention forward with an edge-type score bias (extra op)", py::arg("row"), py::arg("indptr"),
+        py::arg("eid"), py::arg("indices"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("B"),
+        py::arg("etype"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0, py::arg("head0") = 0);
+  m.def("attention_tbias_backward", &attention_tbias_backward,
+        "Fused attention backward with an edge-type score bias (extra op)", py::arg("row"),
+        py::arg("indptr_r"), py::arg("eid_r"), py::arg("indices_r"), py::arg("col"), py::arg("indptr_c"),
+        py::arg("eid_c"), py::arg("indices_c"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("B"), py::arg("etype"),
+        py::arg("o"), py::arg("stats"), py::arg("dO"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0,
+        py::arg("head0") = 0, py::arg("need_dB") = true);
   // (and the weights of all of these from their row statistics)
   m.def("attention_weights", &attention_weights,
         "Attention weights of the fused attention ops from their row statistics (extra op)", py::arg("row"),

@@ -414,7 +414,9 @@ class FusedAttentionBias(Function):
     bias (spatial and edge encodings), a relative positional bias, a weighted graph with b = log w, and the key-side
     edge term of TransformerConv(edge_dim=...), b = node_mul_edge_forward(Q, xe) (through NodeMulEdge, so that its
     backward turns db into the gradients of Q and xe) -- the key side ALONE: that layer also adds the edge row to the
-    value, which no bias can express; FusedAttentionEdge has both terms.  b must be finite: a bias at or below the -1e9 floor of the row
+    value, which no bias can express; FusedAttentionEdge has both terms.  For a CATEGORICAL bias (b = B[etype]: distance
+    buckets, bond types, relations) use FusedAttentionTypeBias, which takes the table and the types and makes neither b
+    nor db.  b must be finite: a bias at or below the -1e9 floor of the row
     maximum is not a mask.  Saves (Q, K, V, b, o, row statistics) and nothing edge-sized but b; the backward makes db
     = ds only where b needs a gradient.  m_e is FusedAttentionDropout's multiplier (1 at p = 0: no dropout); seed=None
     draws one from torch's default CPU generator.  There is no 1 / sqrt(d) scale argument: fold it into Q.
@@ -512,6 +514,38 @@ class FusedAttentionEdgeType(Function):
         need_dR = ctx.needs_input_grad[11]
         dQ, dK, dV, dR = _ops.attention_etype_backward(*a8, Q, K, V, R, etype, o, stats, dO, *ctx.drop, 0, need_dR)
         return (None,) * 8 + (dQ, dK, dV, dR if need_dR else None, None, None, None, None)
+
+
+class FusedAttentionTypeBias(Function):
+    """FusedAttentionBias for a categorical edge feature whose learned term is one scalar per (category, head) (extra
+    op): edge e = (i, j) carries the type t = etype[e] and, for head k,  s_e = <Q_i, K_j> + B[t, k],
+    o[i] = sum_e softmax_e(s) m_e V[j]:
+    apply(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, B, etype, p=0.0, seed=None, offset=0).
+    etype is (E) torch.int32 by edge id with values in [0, n_types); B is (n_types) with 2-D Q / K / V, (n_types, h) with
+    3-D ones, in their dtype, contiguous and finite: an nn.Embedding's weight (Graphormer's spatial encoding and its edge
+    encoding on bond types, T5 / Swin-type bucketed relative positions, relation biases).  It is FusedAttentionBias on
+    B[etype.long()] without that (E, h) tensor and without its gradient: B.grad[t] = sum over the edges of type t of ds
+    is summed on chip, and only where B needs a gradient.  One call whatever h: there are no head groups.  Saves the CSR
+    arrays, (Q, K, V, B, etype, o, row statistics) and nothing else; etype gets no gradient.  Types outside
+    [0, n_types) are not detected (that would synchronise): the kernels clamp them, so they give undefined values and
+    touch no memory outside B / B.grad.  m_e, seed=None and the missing 1 / sqrt(d) argument: as FusedAttentionBias."""
+
+    @staticmethod
+    def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, B, etype, p=0.0,
+                seed=None, offset=0):
+        a8 = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
+        seed = _drop_seed(seed, p)
+        ctx.drop = (float(p), int(seed), int(offset))
+        o, stats = _ops.attention_tbias_forward(row, indptr_r, eid_r, indices_r, Q, K, V, B, etype, *ctx.drop, 0)
+        ctx.save_for_backward(*a8, Q, K, V, B, etype, o, stats)
+        return o
+
+    @staticmethod
+    def backward(ctx, dO):
+        a8, (Q, K, V, B, etype, o, stats) = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
+        need_dB = ctx.needs_input_grad[11]
+        dQ, dK, dV, dB = _ops.attention_tbias_backward(*a8, Q, K, V, B, etype, o, stats, dO, *ctx.drop, 0, need_dB)
+        return (None,) * 8 + (dQ, dK, dV, dB if need_dB else None, None, None, None, None)
 
 
 class FusedAttentionWeights(Function):
@@ -784,6 +818,22 @@ def attention_etype_step(g, Q, K, V, R, etype, dO, p=0.0, seed=0, offset=0):
     """The composed yardstick of fused_attention_etype_step, for tests and timing only: attention_edge_step on the
     materialised R[etype.long()] under autograd, which index_adds the (E, h, d) gradient back into R.grad."""
     return attention_edge_step(g, Q, K, V, R.index_select(0, etype.long()), dO, p, seed, offset)
+
+
+def fused_attention_tbias_step(g, Q, K, V, B, etype, dO, p=0.0, seed=0, offset=0):
+    """fused_attention_bias_step for a categorical edge feature, through FusedAttentionTypeBias: the table B and the
+    int32 types etype (by edge id) stand where b = B[etype] would; returns o (nothing of size (E, h) exists, and B.grad
+    where B requires it has B's shape)."""
+    o = FusedAttentionTypeBias.apply(*g.csr_args(), Q, K, V, B, etype, p, seed, offset)
+    o.backward(dO)
+    _lib.check_errors(sync=False)     # as in attention_step
+    return o
+
+
+def attention_tbias_step(g, Q, K, V, B, etype, dO, p=0.0, seed=0, offset=0):
+    """The composed yardstick of fused_attention_tbias_step, for tests and timing only: fused_attention_bias_step on the
+    materialised B[etype.long()] under autograd, which index_adds the (E, h) gradient back into B.grad."""
+    return fused_attention_bias_step(g, Q, K, V, B.index_select(0, etype.long()), dO, p, seed, offset)
 
 
 def _backward_pairs(pairs):

@@ -32,6 +32,7 @@ __all__ = ["maskedmm_csr_forward", "maskedmm_csr_backward", "node_mul_edge_forwa
 # _backward) and with edge features in key and value (attention_edge_forward / _backward),
 # the attention weights of all of these from the row statistics they return (attention_weights),
 # the edge-feature form for a categorical feature: a table and an int32 type per edge (attention_etype_*),
+# the score bias for a categorical feature: a scalar per (type, head) and the same int32 (attention_tbias_*),
 # the GAT additive attention scores (LeakyReLU(el[i] + er[j]) per edge and head), the fused GAT attention layer and
 # its forms with attention dropout (plus the mask they apply, as an edge tensor, for the composed path), and the GATv2
 # scores (att . LeakyReLU(xl[i] + xr[j]) per edge and head), and the fused GAT layer with a per-edge score term
@@ -792,8 +793,8 @@ def attention_bias_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_
 
 
 # ---- an edge row in key and value of the fused attention step (extra ops): K_j + xe[e], V_j + xe[e]
-# ---- and, for a categorical edge feature, K_j + R[t_e], V_j + R[t_e] (4.5o).  One body per direction: etype None is
-# ---- the first op (rows = xe), else the second (rows = R)
+# ---- and, for a categorical edge feature, K_j + R[t_e], V_j + R[t_e] (4.5o) or <Q_i, K_j> + B[t_e] (4.5p).  One body
+# ---- per direction: etype None is the first op (rows = xe), else the op's name says which table rows is (R or B)
 def _attn_edge_rows(fn, xe, Q, n_edges):
     """xe checked against the graph and Q: a contiguous device tensor (n_edges, d) for 2-D Q / K / V, else
     (n_edges, h, d), in Q's dtype.  The C ABI takes a raw pointer: each of these would read out of bounds or garbage."""
@@ -829,11 +830,38 @@ def _attn_etype_table(fn, R, etype, Q, n_edges):
             raise RuntimeError("%s must be a CUDA tensor" % n)
 
 
-def _attn_edge_workspace(like, backward, sizes, plan_r, plan_c, typed):
-    """sizes: (e, n_q, n_k, h, d) and, typed, n_types"""
+def _attn_tbias_table(fn, B, etype, Q, n_edges):
+    """B and etype checked against the graph and Q: B a contiguous device tensor (n_types) for 2-D Q / K / V, else
+    (n_types, h), in Q's dtype, with n_types >= 1 unless the graph has no edge; etype a contiguous device int32 tensor
+    (n_edges).  The C ABI takes raw pointers: each of these would read out of bounds or garbage.  The VALUES of etype
+    are not looked at (that would synchronise): the kernels clamp them."""
+    _same_dtype(Q, B, "Q", "B")
+    if B.dim() != Q.dim() - 1 or tuple(B.shape[1:]) != tuple(Q.shape[1:-1]):
+        raise RuntimeError("%s: B must be (n_types) for 2-D Q / K / V, else (n_types, h), got B %s, Q %s"
+                           % (fn, tuple(B.shape), tuple(Q.shape)))
+    if B.size(0) == 0 and n_edges > 0:
+        raise RuntimeError("%s: B must hold at least one type (n_edges = %d)" % (fn, n_edges))
+    if etype.dtype != torch.int32:
+        raise RuntimeError("%s: etype must be torch.int32, got %s" % (fn, etype.dtype))
+    if tuple(etype.shape) != (n_edges,):
+        raise RuntimeError("%s: etype must be (n_edges) with n_edges = %d, got %s" % (fn, n_edges, tuple(etype.shape)))
+    for t, n in ((B, "B"), (etype, "etype")):
+        if not t.is_contiguous():
+            raise RuntimeError("%s must be contiguous" % n)
+        if not t.is_cuda:
+            raise RuntimeError("%s must be a CUDA tensor" % n)
+
+
+def _attn_edge_form(fn):
+    """"edge", "etype" or "tbias": the form an op's name attention_<form>_<direction> carries"""
+    return fn.split("_")[1]
+
+
+def _attn_edge_workspace(like, backward, sizes, plan_r, plan_c, form):
+    """sizes: (e, n_q, n_k, h, d) and, with a table, n_types"""
     import ctypes
     nbytes = ctypes.c_int64(0)
-    query = lib().graphop_attention_etype_workspace_bytes if typed else lib().graphop_attention_edge_workspace_bytes
+    query = getattr(lib(), "graphop_attention_%s_workspace_bytes" % form)
     check(query(dtype_code(like), 1 if backward else 0, *sizes, plan_r.handle,
                 plan_c.handle if plan_c is not None else _NULL, stream_of(like), ctypes.byref(nbytes)))
     return torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=like.device), nbytes.value
@@ -844,7 +872,7 @@ def _attn_edge_operands(fn, rows, etype, Q, e, n_q, n_k, h, d):
     if etype is None:
         _attn_edge_rows(fn, rows, Q, e)
         return (ptr(rows),), (e, n_q, n_k, h, d)
-    _attn_etype_table(fn, rows, etype, Q, e)
+    (_attn_tbias_table if _attn_edge_form(fn) == "tbias" else _attn_etype_table)(fn, rows, etype, Q, e)
     return (ptr(rows), ptr(etype)), (e, n_q, n_k, h, d, rows.size(0))
 
 
@@ -858,14 +886,14 @@ def _attn_edge_forward(fn, row, indptr, eid, indices, Q, K, V, rows, etype, p, s
     e, d = eid.size(0), Q.size(-1)
     h = 1 if Q.dim() == 2 else Q.size(1)
     n_q, n_k = Q.size(0), K.size(0)
-    typed = etype is not None
+    form = _attn_edge_form(fn)
     operands, sizes = _attn_edge_operands(fn, rows, etype, Q, e, n_q, n_k, h, d)
     o = torch.empty_like(Q)
     stats = torch.empty((n_q, h, 2), dtype=Q.dtype, device=Q.device)
     with _lib.device_guard(Q.device):
         plan = get_plan(row, indptr, eid, indices, n_k)
-        ws, nbytes = _attn_edge_workspace(Q, False, sizes, plan, None, typed)
-        call = lib().graphop_attention_etype_forward if typed else lib().graphop_attention_edge_forward
+        ws, nbytes = _attn_edge_workspace(Q, False, sizes, plan, None, form)
+        call = getattr(lib(), "graphop_" + fn)
         check(call(dtype_code(Q), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(Q), ptr(K), ptr(V), *operands,
                    ptr(o), ptr(stats), row.size(0), *sizes, ptr(ws), nbytes, plan.handle, stream_of(Q), *drop))
     return [o, stats]
@@ -887,20 +915,20 @@ def _attn_edge_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_
     n_q, n_k = Q.size(0), K.size(0)
     if o.shape != Q.shape or dO.shape != Q.shape or stats.numel() != n_q * h * 2:
         raise RuntimeError("%s: o, dO must match Q and stats must be (n_q, h, 2)" % fn)
-    typed = etype is not None
+    form = _attn_edge_form(fn)
     operands, sizes = _attn_edge_operands(fn, rows, etype, Q, e, n_q, n_k, h, d)
     dQ, dK, dV = torch.empty_like(Q), torch.empty_like(K), torch.empty_like(V)
     with _lib.device_guard(Q.device):
         plan_r = get_plan(row, indptr_r, eid_r, indices_r, n_k)
         plan_c = get_plan(col, indptr_c, eid_c, indices_c, n_q)
-        # dR: the call fills it.  dxe[e] is written once per row-major slot: only a chunk list that leaves slots out
+        # dR, dB: the call fills it.  dxe[e] is written once per row-major slot: only a chunk list that leaves slots out
         # needs the zeros
         if not need_dx:
             dx = torch.empty((0,), dtype=rows.dtype, device=rows.device)
         else:
-            dx = torch.empty_like(rows) if typed or plan_r.info.full_coverage else torch.zeros_like(rows)
-        ws, nbytes = _attn_edge_workspace(Q, True, sizes, plan_r, plan_c, typed)
-        call = lib().graphop_attention_etype_backward if typed else lib().graphop_attention_edge_backward
+            dx = torch.empty_like(rows) if form != "edge" or plan_r.info.full_coverage else torch.zeros_like(rows)
+        ws, nbytes = _attn_edge_workspace(Q, True, sizes, plan_r, plan_c, form)
+        call = getattr(lib(), "graphop_" + fn)
         check(call(dtype_code(Q), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c),
                    ptr(eid_c), ptr(indices_c), ptr(Q), ptr(K), ptr(V), *operands, ptr(o), ptr(stats), ptr(dO), ptr(dQ),
                    ptr(dK), ptr(dV), ptr(dx) if need_dx else _NULL, row.size(0), col.size(0), *sizes, ptr(ws), nbytes,
@@ -955,6 +983,36 @@ def attention_etype_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid
     clamped as in the forward: they never touch memory outside R / dR."""
     return _attn_edge_backward("attention_etype_backward", row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
                                indices_c, Q, K, V, R, etype, o, stats, dO, p, seed, offset, head0, need_dR)
+
+
+def attention_tbias_forward(row, indptr, eid, indices, Q, K, V, B, etype, p=0.0, seed=0, offset=0, head0=0):
+    """-> [o, stats] of attention_bias_forward for a categorical edge feature whose learned term is a scalar per
+    (category, head) inside the softmax: edge e = (i, j) carries the type t = etype[e] and
+    s_e = <Q_i, K_j> + B[t, k],  a = row-softmax(s),  o[i] = sum_e a_e m_e V[j]  (Graphormer's spatial encoding
+    b_phi(i, j) and its edge encoding on bond types, T5 / Swin-type bucketed relative-position biases, relation biases of
+    heterogeneous graphs).  etype is (n_edges) torch.int32, contiguous, indexed by edge id, with values in [0, n_types);
+    B is (n_types) for 2-D Q / K / V, else (n_types, h), in their dtype, contiguous and finite.  Nothing of size
+    (n_edges, h) is made or read: this is attention_bias_forward on B[etype.long()] without that tensor.  stats
+    (n_q, h, 2) = (row max floored at -1e9, 1 / sum exp) of the biased, undropped scores -- attention_weights(...,
+    b=B[etype.long()]) reproduces the weights from them -- and (-1e9, 0) with o = 0 for rows without edges.  Parallel
+    edges share a dropout decision and may differ in type.
+    Out-of-range types: etype is not scanned (a scan would synchronise the stream and break its capture); every kernel
+    clamps a type into [0, n_types - 1] before it forms an address, so a type outside [0, n_types) gives an undefined
+    value and never touches memory outside B.  (p, seed, offset, head0) as attention_dropout_forward, p = 0: no
+    dropout.  There is no 1 / sqrt(d) scale argument (fold it into Q), and no per-edge b, xe or R together with B."""
+    return _attn_edge_forward("attention_tbias_forward", row, indptr, eid, indices, Q, K, V, B, etype, p, seed, offset,
+                              head0)
+
+
+def attention_tbias_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, B, etype, o,
+                             stats, dO, p=0.0, seed=0, offset=0, head0=0, need_dB=True):
+    """-> [dQ, dK, dV, dB] of attention_tbias_forward for the output gradient dO, with the same (p, seed, offset,
+    head0): the weights and their keep decisions are recomputed per slot.  dB[t] = sum over the edges of type t of ds_e
+    in B's shape is summed on chip -- no (n_edges, h) gradient exists -- and is 0 for a type no edge carries; with
+    need_dB=False it is an empty (0,) tensor and nothing is accumulated.  Out-of-range types are clamped as in the
+    forward: they never touch memory outside B / dB."""
+    return _attn_edge_backward("attention_tbias_backward", row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
+                               indices_c, Q, K, V, B, etype, o, stats, dO, p, seed, offset, head0, need_dB)
 
 
 # ---- the weights of the fused attention ops from their row statistics (extra op, DESIGN.md 4.5n) ---------------------
@@ -1084,7 +1142,9 @@ EXTRA_OPS = [n for n in _SCHEMAS if n not in __all__] + ["attention_backward_is_
                                                          "attention_bias_backward", "attention_edge_forward",
                                                          "attention_edge_backward", "attention_weights",
                                                          # edge-type embeddings (attention_etype_*)
-                                                         "attention_etype_forward", "attention_etype_backward"]
+                                                         "attention_etype_forward", "attention_etype_backward",
+                                                         # an edge-type score bias (attention_tbias_*)
+                                                         "attention_tbias_forward", "attention_tbias_backward"]
 _torch_lib = None
 
 

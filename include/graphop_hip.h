@@ -865,6 +865,56 @@ GRAPHOP_API int graphop_attention_etype_backward(int dtype, const int64_t* row, 
                                      const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream, double p,
                                      uint64_t seed, uint32_t offset, int64_t head0);
 
+/* ---- an edge-type score bias in the fused attention step: <Q_i, K_j> + B[t_e, k] (ABI 8, additive; EXTRA ops) ---------
+ * The step of graphop_attention_bias_* for a CATEGORICAL edge feature whose learned term is one scalar per (category,
+ * head) inside the softmax: Graphormer's spatial encoding b_phi(i, j) (a shortest-path-distance bucket) and its edge
+ * encoding on bond types, T5 / Swin-type bucketed relative-position biases, relation biases of heterogeneous graphs.
+ * Edge e carries the type t_e = etype[e]; etype is (n_edges) int32, contiguous, indexed by EDGE ID, with values in
+ * [0, n_types); B is (n_types, h) in the dtype of Q / K / V, contiguous and finite.  DESIGN.md 4.5p.
+ *   s_e = <Q_i, K_j> + B[t_e, k]          one add, after the dot product's reduction
+ *   every other line of graphop_attention_bias_* with b[e, k] := B[t_e, k]
+ *   dB[t, k] = sum over the edges e with t_e = t of ds_e;  types no edge carries get dB[t] = 0
+ * stats are those of the biased, undropped scores (graphop_attention_weights with b = B[etype] reproduces the weights);
+ * rows without edges get o = 0 and stats = (-1e9, 0).  Nothing edge-sized is made in either direction: etype is the only
+ * edge-sized operand.  Parallel edges share a dropout decision and may differ in type.  No 1 / sqrt(d) argument, and no
+ * per-edge b, xe or R together with B.
+ * OUT-OF-RANGE TYPES: etype is NOT scanned (a scan would synchronise the stream and break its capture in a graph).
+ * Every kernel clamps the type it loads into [0, n_types - 1], as an unsigned value, before it forms an address: a type
+ * outside [0, n_types) gives an undefined value (that of some type of the table) and never touches memory outside B / dB.
+ * Arguments as graphop_attention_etype_* with B where R is and dB where dR is.  dB == NULL: the gradient of B is not
+ * wanted; nothing is accumulated for it.  Otherwise the call itself writes every element of dB (as it zero-fills dQ, dK,
+ * dV and what it accumulates into, with stream-ordered fills: a step can be captured).
+ * Checks, all before anything touches a device: those of graphop_attention_forward, then the dropout arguments (head0
+ * included), then n_types >= 1 (unless n_edges == 0), then B != NULL and etype != NULL (unless n_edges * h * d == 0),
+ * then the workspace.  Empty problems fill what they must and dereference nothing.  A matching plan must bound the ids by
+ * n_q and n_k (an error otherwise).
+ * Forms, chosen pass by pass: fp32 calls whose (h, d) is one of (1,64) (2,32) (2,64) (4,16) (4,32) (4,64) (8,8) (8,16)
+ * (8,32), with 16-byte aligned operands and ids below 2^31, run the chunk-driver passes k_attn_tbias_fwd_rows_f32 and
+ * k_attn_tbias_bwd_rows_f32 under the conditions graphop_attention_etype_* puts on the plans.  The row pass with
+ * dB != NULL sums dB in 4 n_types h bytes of LDS and so needs that to be at most 16 KiB (n_types * h <= 4096); beyond it
+ * that pass alone is the generic one.  Everything else runs the generic kernels k_attn_tbias_*_generic, one wave per chunk.
+ * workspace: graphop_attention_tbias_workspace_bytes bytes.  Backward with a fast form and a table that fits: its LAST
+ * up256(64 * 4 n_types h) bytes (up256: rounded up to 256) hold the 64 replicas of dB the row pass's workgroups add
+ * into; with dB == NULL they are not touched. */
+GRAPHOP_API int graphop_attention_tbias_workspace_bytes(int dtype, int backward, int64_t n_edges, int64_t n_q, int64_t n_k,
+                                            int64_t h, int64_t d, int64_t n_types, const graphop_plan_t* plan_r,
+                                            const graphop_plan_t* plan_c, void* stream, int64_t* bytes_out);
+GRAPHOP_API int graphop_attention_tbias_forward(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                                    const int64_t* indices, const void* Q, const void* K, const void* V, const void* B,
+                                    const int32_t* etype, void* o, void* stats, int64_t n_chunks, int64_t n_edges,
+                                    int64_t n_q, int64_t n_k, int64_t h, int64_t d, int64_t n_types, void* workspace,
+                                    int64_t workspace_bytes, const graphop_plan_t* plan, void* stream, double p,
+                                    uint64_t seed, uint32_t offset, int64_t head0);
+GRAPHOP_API int graphop_attention_tbias_backward(int dtype, const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r,
+                                     const int64_t* indices_r, const int64_t* col, const int64_t* indptr_c,
+                                     const int64_t* eid_c, const int64_t* indices_c, const void* Q, const void* K,
+                                     const void* V, const void* B, const int32_t* etype, const void* o, const void* stats,
+                                     const void* dO, void* dQ, void* dK, void* dV, void* dB, int64_t n_row_chunks,
+                                     int64_t n_col_chunks, int64_t n_edges, int64_t n_q, int64_t n_k, int64_t h, int64_t d,
+                                     int64_t n_types, void* workspace, int64_t workspace_bytes,
+                                     const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream, double p,
+                                     uint64_t seed, uint32_t offset, int64_t head0);
+
 /* ---- attention weights of the fused dot-product attention ops (not in the reference) --------------
  * The weights the layer used, as an edge tensor (PyG's return_attention_weights=True, DGL's get_attention=True), from
  * the row statistics stats (n_q, h, 2) = (m_i, linv_i) that graphop_attention_forward / _dropout_forward /
