@@ -111,6 +111,26 @@ struct Sweep {
   static constexpr int kMaxDealt = 4;
   Dealt dealt[kMaxDealt];
   int n_dealt = 0;
+  // Tile layouts of the window-owner tasks (tile_layout.h; kernels_tile.h): the slots of every (window, tile of R vrows)
+  // task grouped by neighbour id.  Built on the host on first use, one per (R, cap); an entry whose arrays are NULL
+  // remembers only the counts (the selection rule found the repeat fraction too low, or a vrow does not fit the buffer).
+  struct Tile {
+    int R = 0, cap = 0;     // vrows per tile, floats in the kernel's result buffer
+    int tiles = 0;          // tasks per window
+    int fits = 0;           // 0: a vrow has more slots inside one window than cap -- no layout for this geometry
+    long long slots = 0, distinct = 0, records = 0, batches = 0, n_parts = 0;   // summed over the tasks
+    long long bytes = 0;    // device bytes of the arrays below
+    int* part_ptr = nullptr;
+    int* parts = nullptr;   // int4
+    unsigned short* rec = nullptr;
+    int* bstart = nullptr;
+    int* slotw = nullptr;
+    int* rowtab = nullptr;  // int2
+    int* tdesc = nullptr;   // int4
+  };
+  static constexpr int kMaxTile = 4;
+  Tile tile[kMaxTile];
+  int n_tile = 0;
 };
 // Walk layout of one plan (kernels_walk.h): the slots of the CSR, read as one tape, are cut into
 // waves * rounds BINS of equal length; bin (round r, wave q) is what wave q of the resident grid

@@ -16,6 +16,8 @@
 #include "host_attn_rows.h"
 #include "kernels_fast.h"
 #include "kernels_walk.h"
+#include "kernels_tile.h"
+#include "tile_layout.h"
 #include "kernels_attn_walk.h"
 #include "kernels_attn_bias_fwd.h"
 #include "kernels_block.h"
@@ -153,7 +155,8 @@ int choose_sweep(const graphop_plan* plan, i64 n_table_rows, int L, int NV, hipS
       staged_ok = pi.eid_identity || dl->eids != nullptr || opts->no_eids;   // the staged kernels read the dealt copies and nothing else
     }
   }
-  if (!staged_ok) {
+  out->sweep = sw;
+  if (!staged_ok && !(opts && opts->tile)) {
     // a per-batch kernel will read the window tables and the 32-bit mirrors at run time: resident, and kept (plan.hip)
     const int rcp = plan_pin_sweep_tables(const_cast<graphop_plan*>(plan), sw, st);
     if (rcp != GRAPHOP_OK) return -rcp;
@@ -504,10 +507,95 @@ int attn_bias_fwd_rows(const Csr& g, i64 n_q, i64 n_k, i64 h, i64 d, int dtype, 
 
 namespace {
 
+// ---- tile driver of the SDDMM-type passes (kernels_tile.h) ---------------------------------------------------------------
+struct TileLaunch {
+  TileView view;
+  unsigned blocks;
+  size_t lds_bytes;
+  int nt;   // threads per workgroup
+};
+// Does the tile driver take an SDDMM-type pass over `plan` (fp32, one head, 256-B rows, identity eid, table < 4 GiB, a
+// window structure, and -- knob sddmm_tile = 1 -- a plan whose slots repeat their tile's neighbours often enough)?
+// Fetches / builds the layout.  1 = launch it, 0 = no (the window-owner strips decide next), < 0 = error (negated).
+// Rows per tile 128 / 192: two workgroups of 512 threads share a CU's LDS; 256 / 384: one workgroup of 1024.
+template <int L, int NV>
+int choose_tile(const graphop_plan* plan, i64 n_table_rows, i64 h, int dtype, hipStream_t st, TileLaunch* out, bool dry_run) {
+  if constexpr (L != 16 || NV != 1) {
+    return 0;
+  } else {
+    const Tuning& t = tuning();
+    if (!t.sddmm_tile || !plan || dtype != GRAPHOP_F32 || h != 1) return 0;
+    if (!plan->info.eid_identity || !table_off32(n_table_rows, L, NV)) return 0;
+    const int R = t.sddmm_tile_rows;
+    if (R != 128 && R != 192 && R != 256 && R != 384) return 0;
+    SweepLaunch sl;
+    SweepOpts so;
+    so.dry_run = 1;
+    so.tile = 1;
+    so.bpc = sweep_bpc(NV, true);   // (the strips' geometry: one window structure serves both drivers)
+    const int use = choose_sweep(plan, n_table_rows, L, NV, st, &sl, false, &so);
+    if (use != 1) return use;
+    const int per_cu = R <= 192 ? 2 : 1;
+    // a workgroup takes whole (window, tile) tasks, and the last round of tasks leaves CUs idle for up to one task: 1 / n
+    // of the pass at n tasks per workgroup.  The measured gain is 7 % of a pass: below 32 tasks per
+    // workgroup the tail can eat half of it -- such graphs stay on the strips (a wave's 32 vrows per task) unless forced
+    // (a bound reasoned from the tail, not a measured break-even)
+    if (t.sddmm_tile != 2 && (i64)sl.sweep->W * ceil_div((i64)sl.sweep->V, R) < 32LL * t.n_cu * per_cu) return 0;
+    const int lds_wg = (kTileLdsBytes / per_cu) & ~255;
+    int cap = (lds_wg - R * 16 * L * NV) / 4;
+    if (cap > kTileMaxCap) cap = kTileMaxCap;
+    const Sweep::Tile* tl = nullptr;
+    const int rc = plan_get_tile(const_cast<graphop_plan*>(plan), sl.sweep, R, cap, t.sddmm_tile == 2, t.sddmm_tile_min_repeat, st, &tl);
+    if (rc != GRAPHOP_OK) return -rc;
+    if (!tl) return 0;
+    plan_trim(const_cast<graphop_plan*>(plan));
+    TileView& v = out->view;
+    v = TileView{};
+    v.part_ptr = tl->part_ptr; v.parts = (const int4*)tl->parts; v.rec = tl->rec; v.bstart = tl->bstart; v.slotw = tl->slotw;
+    v.rowtab = (const int2*)tl->rowtab; v.tdesc = (const int4*)tl->tdesc; v.vr_row = sl.sweep->vr_row;
+    v.V = sl.sweep->V; v.W = sl.sweep->W; v.R = R; v.tiles = tl->tiles; v.win_cols = (int)sl.sweep->win_cols;
+    v.touch = t.sddmm_tile_touch ? 1 : 0;
+    v.sync = nullptr;
+    if (!dry_run) {
+      v.sync = plan_take_queue(const_cast<graphop_plan*>(plan), sl.sweep);
+      if (zero_async(v.sync, sizeof(int) * kQueueInts, st) != hipSuccess) return -GRAPHOP_ERR_HIP;
+    }
+    const i64 tasks = (i64)tl->tiles * v.W;
+    i64 nb = (i64)t.n_cu * per_cu;
+    if (nb > tasks) nb = tasks;
+    out->blocks = (unsigned)(nb < 1 ? 1 : nb);
+    out->lds_bytes = (size_t)R * 16 * L * NV + (size_t)cap * 4;
+    out->nt = per_cu == 2 ? 512 : 1024;
+    return 1;
+  }
+}
+template <int L, int NV>
+void launch_tile(const TileLaunch& tl, const float* a, const float* b, float* y, hipStream_t st) {
+  if constexpr (L == 16 && NV == 1) {
+    if (tl.nt == 512) {
+      allow_full_lds((const void*)k_sddmm_tile_f32<L, NV, 512>);
+      hipLaunchKernelGGL((k_sddmm_tile_f32<L, NV, 512>), dim3(tl.blocks), dim3(512), tl.lds_bytes, st, tl.view, a, b, y);
+    } else {
+      allow_full_lds((const void*)k_sddmm_tile_f32<L, NV, 1024>);
+      hipLaunchKernelGGL((k_sddmm_tile_f32<L, NV, 1024>), dim3(tl.blocks), dim3(1024), tl.lds_bytes, st, tl.view, a, b, y);
+    }
+  }
+}
+
 template <int L, int NV>
 int try_sddmm_sweep(const char* tag, int dtype, const graphop_plan* plan, i64 n_table_rows, const void* A,
                     const void* B, void* y, i64 h, int d4, hipStream_t st) {
   if (!plan) return 0;   // (plan-less calls -- the C ABI allows them, the partial SDDMM entry always makes them -- take the chunk drivers)
+  {
+    TileLaunch tl;
+    const int ut = choose_tile<L, NV>(plan, n_table_rows, h, dtype, st, &tl, /*dry_run=*/false);
+    if (ut < 0) return ut;
+    if (ut == 1) {
+      ProfScope prof(tag, st, "k_sddmm_tile_f32");
+      launch_tile<L, NV>(tl, (const float*)A, (const float*)B, (float*)y, st);
+      return 1;
+    }
+  }
   SweepLaunch sl;
   SweepOpts so;
   const bool f64 = dtype == GRAPHOP_F64;
@@ -1077,7 +1165,13 @@ int graphop_plan_prepare(graphop_plan_t* plan, int dtype, int64_t n_table_rows, 
     o.bpc = f64 ? 3 : sweep_bpc(NV, h == 1);
     o.staged = sddmm_staged(plan, L, NV, h, n_table_rows);
     o.stage_lds_per_group = StageCfg<L, 1>::kLdsIntsPerGroup * (int)sizeof(int) + (h > 1 ? 64 * (int)h : 0);
-    if (!f64 || (o.staged && NV == 1 && L >= 16))
+    int tiled = 0;   // the SDDMM-type passes take the tile driver: its layout instead of the strips' dealt one
+    if (!f64) {
+      TileLaunch tl;
+      tiled = choose_tile<L, NV>(plan, n_table_rows, h, dtype, st, &tl, /*dry_run=*/true);
+      if (tiled < 0) rc = tiled;
+    }
+    if (tiled == 0 && (!f64 || (o.staged && NV == 1 && L >= 16)))
       rc = choose_sweep(plan, n_table_rows, L, NV, st, &sl, /*accumulating=*/false, &o);
     o.staged = spmm_staged(L, NV, h, n_table_rows);
     if (rc >= 0 && !f64) rc = choose_sweep(plan, n_table_rows, L, NV, st, &sl, /*accumulating=*/true, &o);

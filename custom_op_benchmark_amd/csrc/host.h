@@ -67,6 +67,11 @@ struct Tuning {
   int walk_debug;         // 1: every walk launch is followed by a synchronisation and a line of pacing statistics on stderr
   int walk_fault;         // tests only: inject a hand-over fault into the walk kernel (kernels_walk.h: WalkView::fault)
   int walk_blocks;        // > 0: workgroups of the walk launches (tests: a small grid makes several rounds of sizeable bins)
+  int sddmm_tile;         // SDDMM-type passes on the tile driver (kernels_tile.h): 0 never, 1 where the plan's repeat fraction pays
+                          // (sddmm_tile_min_repeat), 2 wherever the shape is in scope
+  int sddmm_tile_rows;    // vrows per tile: 128, 192 (two workgroups of 512 threads per CU; 192 measured best), 256 or 384 (one of 1024)
+  int sddmm_tile_min_repeat;  // percent of a plan's slots that repeat a neighbour of their tile from which the tile driver is chosen
+  int sddmm_tile_touch;   // 1: a wave touches the next task's record lines (kernels_tile.h: TileView::touch)
   int plan_trim;          // 1: plans drop what only their layout builders read (32-bit mirrors, window tables) once an op has what
                           // it launches with; rebuilt on demand (plan.hip: plan_trim)
   int n_cu;
@@ -111,6 +116,10 @@ struct Tuning {
     walk_blocks = env_int("GRAPHOP_WALK_BLOCKS", 0);
     walk_debug = env_int("GRAPHOP_WALK_DEBUG", 0);
     walk_fault = 0;
+    sddmm_tile = env_int("GRAPHOP_SDDMM_TILE", 1);
+    sddmm_tile_rows = env_int("GRAPHOP_SDDMM_TILE_ROWS", 192);
+    sddmm_tile_min_repeat = env_int("GRAPHOP_SDDMM_TILE_MIN_REPEAT", 20);
+    sddmm_tile_touch = env_int("GRAPHOP_SDDMM_TILE_TOUCH", 1);
     plan_trim = env_int("GRAPHOP_PLAN_TRIM", 1);
     n_cu = 256;
     int dev = 0;
@@ -160,6 +169,7 @@ inline ChunkGeometry chunk_geometry(i64 n_chunks, int lanes, i64 cap, int rounds
 }
 
 struct SweepLaunch {
+  const Sweep* sweep = nullptr;   // the window structure the view was filled from
   SweepView view;
   unsigned blocks;
   size_t lds_bytes;
@@ -176,6 +186,7 @@ struct SweepOpts {
   int touch = 0;          // SweepView::touch of the launch
   int staged = 0;         // 1: also fetch / build the dealt (window-major) layout and put it in the view
   int stage_lds_per_group = 0;   // bytes of LDS each lane group needs for staging (added to lds_bytes)
+  int tile = 0;           // 1: the caller reads a tile layout (kernels_tile.h): neither a dealt layout nor the window tables at run time
   int no_eids = 0;        // 1: the kernels never read edge ids (fused attention passes): the dealt layout keeps no copy of them
 };
 
@@ -191,6 +202,7 @@ int plan_build(graphop_plan*, i64, hipStream_t, int);
 int plan_get_sweep(graphop_plan*, int, i64, int, hipStream_t, const Sweep**);
 int* plan_take_queue(graphop_plan*, const Sweep*);
 int plan_get_dealt(graphop_plan*, const Sweep*, int, int, hipStream_t, const Sweep::Dealt**, bool want_eids = true);
+int plan_get_tile(graphop_plan*, const Sweep*, int R, int cap, bool force, int min_repeat_pct, hipStream_t, const Sweep::Tile**);
 void plan_free_sweeps(graphop_plan*);
 int plan_get_walk(graphop_plan*, int, i64, int, int, int, int, hipStream_t, const Walk**, bool want_widx = true);
 int plan_build_seg_eptr(graphop_plan*, hipStream_t);

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "common.h"
+#include "tile_layout.h"
 
 namespace graphop {
 
@@ -847,11 +848,14 @@ void plan_trim(graphop_plan* p) {
     if (p->idx32 && p->indices) { go_free(p->idx32); p->idx32 = nullptr; }
     if (p->eid32 && p->eid) { go_free(p->eid32); p->eid32 = nullptr; }
   }
-  for (auto& s : *(std::vector<Sweep>*)p->sweeps)
-    if (!s.runtime_wp && s.n_dealt > 0) {
+  for (auto& s : *(std::vector<Sweep>*)p->sweeps) {
+    bool tiled = false;   // some tile layout of this structure holds its arrays
+    for (int i = 0; i < s.n_tile; ++i) tiled = tiled || s.tile[i].slotw != nullptr;
+    if (!s.runtime_wp && (s.n_dealt > 0 || tiled)) {
       go_free(s.wp_lo); go_free(s.wp_hi);
       s.wp_lo = s.wp_hi = nullptr;
     }
+  }
 }
 
 // Build (or fetch) the window-sweep structure for W windows of win_cols ids and vrows of <= T slots.
@@ -966,6 +970,98 @@ int plan_get_dealt(graphop_plan* p, const Sweep* sw, int L, int K, hipStream_t s
   if (hipGetLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) return fail(GRAPHOP_ERR_HIP);
   s->dealt[s->n_dealt] = d;
   *out = &s->dealt[s->n_dealt++];
+  return GRAPHOP_OK;
+}
+
+// ---- tile layout (tile_layout.h; kernels_tile.h) -------------------------------------------------------------------------
+static void tile_free_arrays(Sweep::Tile& t) {
+  go_free(t.part_ptr); go_free(t.parts); go_free(t.rec); go_free(t.bstart); go_free(t.slotw); go_free(t.rowtab); go_free(t.tdesc);
+  t.part_ptr = t.parts = t.bstart = t.slotw = t.rowtab = t.tdesc = nullptr;
+  t.rec = nullptr;
+  t.bytes = 0;
+}
+template <typename T>
+static int tile_upload(T** dst, const std::vector<T>& src, Sweep::Tile& t, hipStream_t st) {
+  const size_t bytes = sizeof(T) * (src.size() ? src.size() : 8);
+  GO_HIP(go_malloc((void**)dst, bytes, st));
+  if (!src.empty()) GO_HIP(hipMemcpyAsync(*dst, src.data(), sizeof(T) * src.size(), hipMemcpyHostToDevice, st));
+  t.bytes += (long long)bytes;
+  return GRAPHOP_OK;
+}
+
+// The tile layout of `sw` for tiles of R vrows and result buffers of `cap` floats.  The counts (slots, distinct neighbours
+// per task) are taken first and kept with the window structure and in the plan's info record; the arrays are built only
+// when `force` or when at least min_repeat_pct percent of the slots repeat a neighbour of their task.  *out = nullptr:
+// no layout (below the threshold, a vrow that does not fit the buffer, sizes beyond 31 bits, kMaxTile geometries).
+// The grouping runs on the HOST over copies of the window tables and the id mirror (setup path: a few seconds for 10^8 slots).
+int plan_get_tile(graphop_plan* p, const Sweep* sw, int R, int cap, bool force, int min_repeat_pct, hipStream_t st,
+                  const Sweep::Tile** out) {
+  std::lock_guard<std::mutex> lk(*(std::mutex*)p->sweep_mu);
+  Sweep* s = const_cast<Sweep*>(sw);
+  *out = nullptr;
+  Sweep::Tile* t = nullptr;
+  for (int i = 0; i < s->n_tile; ++i)
+    if (s->tile[i].R == R && s->tile[i].cap == cap) t = &s->tile[i];
+  auto wanted = [&](const Sweep::Tile& x) {
+    return x.fits && x.slots > 0 && (force || (x.slots - x.distinct) * 100 >= (long long)min_repeat_pct * x.slots);
+  };
+  if (t && (!wanted(*t) || t->slotw)) {
+    if (wanted(*t)) *out = t;
+    return GRAPHOP_OK;
+  }
+  if (!t && s->n_tile >= Sweep::kMaxTile) return GRAPHOP_OK;
+  {
+    const int rc_cap = check_not_capturing(st, "building the tile layout of a plan");
+    if (rc_cap != GRAPHOP_OK) return rc_cap;
+  }
+  const i64 E = p->info.n_edges;
+  if (R < 1 || R > kTileMaxRows || cap < 1 || cap > kTileMaxCap || E <= 0 || E + kTileSlotPad >= 0x7fffffffLL ||
+      s->win_cols > kTileMaxWinCols)
+    return GRAPHOP_OK;
+  {
+    int rc_in = plan_ensure_mirrors(p, st);                                            // (builder inputs: may have been trimmed)
+    if (rc_in == GRAPHOP_OK && (!s->wp_lo || !s->wp_hi || !s->vr_row)) rc_in = sweep_fill_arrays(p, *s, st);
+    if (rc_in != GRAPHOP_OK) return rc_in;
+  }
+  if (!p->idx32) return GRAPHOP_OK;
+  const size_t nwp = (size_t)s->V * (size_t)s->W;
+  std::vector<int> h_lo(nwp), h_hi(nwp), h_idx((size_t)E);
+  GO_HIP(hipMemcpyAsync(h_lo.data(), s->wp_lo, sizeof(int) * nwp, hipMemcpyDeviceToHost, st));
+  GO_HIP(hipMemcpyAsync(h_hi.data(), s->wp_hi, sizeof(int) * nwp, hipMemcpyDeviceToHost, st));
+  GO_HIP(hipMemcpyAsync(h_idx.data(), p->idx32, sizeof(int) * (size_t)E, hipMemcpyDeviceToHost, st));
+  GO_HIP(hipStreamSynchronize(st));
+  TileLayoutHost host;
+  std::vector<tile_detail::TaskCount> counts;   // per task, from the counting pass: the fill below does not count again
+  TileTotals tot = build_tile_layout(s->V, s->W, R, cap, s->win_cols, h_lo.data(), h_hi.data(), h_idx.data(),
+                                     force ? &host : nullptr, 0, &counts);
+  if (!t) {
+    t = &s->tile[s->n_tile++];
+    *t = Sweep::Tile();
+    t->R = R; t->cap = cap; t->tiles = (int)ceil_div((i64)s->V, R);
+  }
+  t->fits = tot.fits ? 1 : 0;
+  t->slots = tot.slots; t->distinct = tot.distinct; t->records = tot.records; t->batches = tot.batches; t->n_parts = tot.parts;
+  p->info.sddmm_tile_rows = R;
+  p->info.sddmm_tile_repeat_permille = tot.slots > 0 ? (int32_t)((tot.slots - tot.distinct) * 1000 / tot.slots) : 0;
+  if (!wanted(*t)) return GRAPHOP_OK;
+  if (!force) {
+    tot = build_tile_layout(s->V, s->W, R, cap, s->win_cols, h_lo.data(), h_hi.data(), h_idx.data(), &host, 0, &counts);
+    if (!tot.fits) { t->fits = 0; return GRAPHOP_OK; }
+  }
+  int rc = tile_upload(&t->part_ptr, host.part_ptr, *t, st);
+  if (rc == GRAPHOP_OK) rc = tile_upload(&t->parts, host.parts, *t, st);
+  if (rc == GRAPHOP_OK) rc = tile_upload(&t->rec, host.rec, *t, st);
+  if (rc == GRAPHOP_OK) rc = tile_upload(&t->bstart, host.bstart, *t, st);
+  if (rc == GRAPHOP_OK) rc = tile_upload(&t->slotw, host.slotw, *t, st);
+  if (rc == GRAPHOP_OK) rc = tile_upload(&t->rowtab, host.rowtab, *t, st);
+  if (rc == GRAPHOP_OK) rc = tile_upload(&t->tdesc, host.tdesc, *t, st);
+  if (rc == GRAPHOP_OK && hipStreamSynchronize(st) != hipSuccess) rc = GRAPHOP_ERR_HIP;   // (the host vectors go out of scope)
+  if (rc != GRAPHOP_OK) {
+    (void)hipStreamSynchronize(st);
+    tile_free_arrays(*t);   // (the message names the allocation or copy that failed: GO_HIP)
+    return rc;
+  }
+  *out = t;
   return GRAPHOP_OK;
 }
 
@@ -1122,6 +1218,7 @@ void plan_free_sweeps(graphop_plan* p) {
       go_free(s.vr_row); go_free(s.wp_lo); go_free(s.wp_hi);
       go_free(s.queues);
       for (int i = 0; i < s.n_dealt; ++i) { go_free(s.dealt[i].rec); go_free(s.dealt[i].ids); go_free(s.dealt[i].eids); }
+      for (int i = 0; i < s.n_tile; ++i) tile_free_arrays(s.tile[i]);
     }
     delete vec;
   }

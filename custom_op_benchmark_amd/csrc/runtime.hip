@@ -238,6 +238,8 @@ std::vector<TuneEntry> tune_table() {
       {"spmm_flat_min_chunks", &t.spmm_flat_min_chunks}, {"staged_ids", &t.staged_ids}, {"attn_max_d", &t.attn_max_d},
       {"touch_sddmm", &t.touch_sddmm}, {"walk", &t.walk}, {"walk_window_kb", &t.walk_window_kb}, {"walk_window_kb_col", &t.walk_window_kb_col},
       {"walk_drift", &t.walk_drift}, {"walk_min_bin", &t.walk_min_bin}, {"walk_blocks", &t.walk_blocks}, {"walk_debug", &t.walk_debug}, {"walk_fault", &t.walk_fault}, {"walk_steps", &t.walk_steps},
+      {"sddmm_tile", &t.sddmm_tile}, {"sddmm_tile_rows", &t.sddmm_tile_rows}, {"sddmm_tile_min_repeat", &t.sddmm_tile_min_repeat},
+      {"sddmm_tile_touch", &t.sddmm_tile_touch},
       {"plan_trim", &t.plan_trim}};
 }
 }  // namespace

@@ -82,6 +82,10 @@ typedef struct graphop_plan_info {
   int64_t n_geometry_fallbacks; /* ABI 7: passes that asked this plan for one window geometry more than it keeps (16) and
                               ran on the chunk drivers instead (2-3x slower on window-friendly shapes; also warned about
                               once per plan on stderr).  Live count: read it with graphop_plan_info after the passes. */
+  int32_t sddmm_tile_rows;            /* ABI 8, additive: vrows per tile of the last tile layout analysed for this plan
+                                         (csrc/tile_layout.h), 0 = none yet.  Live, like the count above. */
+  int32_t sddmm_tile_repeat_permille; /* ... and how many of 1000 slots repeat a neighbour id of their (window, tile) task:
+                                         what the tile driver of the SDDMM-type passes does not gather twice */
 } graphop_plan_info_t;
 
 GRAPHOP_API int graphop_abi_version(void);
@@ -110,6 +114,10 @@ GRAPHOP_API int graphop_check_device_errors(void);
  * flushed per window), walk_window_kb, walk_window_kb_col, walk_drift, walk_steps, walk_min_bin,
  * walk_blocks, walk_debug, walk_fault (tests: hand-over fault injection), spmm_selfzero, spmm_selfzero_min_mb
  * (row-owning chunk driver defines every output row itself: no zero fill of outputs of at least that many MB),
+ * sddmm_tile (SDDMM-type passes, fp32, one head, d = 64, identity eid: 0 window-owner strips, 1 the tile driver -- a
+ * workgroup gathers each neighbour row once per (window, tile of sddmm_tile_rows row pieces) -- where at least
+ * sddmm_tile_min_repeat percent of the plan's slots repeat a neighbour of their tile, 2 wherever the shape is in scope),
+ * sddmm_tile_rows (128, 192, 256, 384), sddmm_tile_min_repeat, sddmm_tile_touch (0/1: L2 touches of the next task's records),
  * plan_trim (0/1: plans drop builder inputs no kernel reads, see "device memory of plans"), spmm_flat (0/1), spmm_flat_max_mean, spmm_flat_min_chunks, spmm_flat_cpg (that driver in its slot-walking form below
  * that many slots per chunk on average, for chunk lists at least that long, with that many chunks per lane group).  Not thread-safe against
  * concurrent op calls; results never depend on them.  (Removed in ABI 6: sweep_mode, sweep_drift,
