@@ -31,7 +31,8 @@ class PlanInfo(ctypes.Structure):
                 ("has_idx32", ctypes.c_int32), ("dense_fill_pct", ctypes.c_int32),
                 ("sorted_in_rows", ctypes.c_int32), ("n_dense_blocks", _c64), ("max_row_gap", _c64),
                 ("n_geometry_fallbacks", _c64),
-                ("sddmm_tile_rows", ctypes.c_int32), ("sddmm_tile_repeat_permille", ctypes.c_int32)]
+                ("sddmm_tile_rows", ctypes.c_int32), ("sddmm_tile_repeat_permille", ctypes.c_int32),
+                ("sddmm_tile_max_parts", ctypes.c_int32)]
 
 
 class SweepInfo(ctypes.Structure):

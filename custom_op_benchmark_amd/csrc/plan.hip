@@ -1043,6 +1043,10 @@ int plan_get_tile(graphop_plan* p, const Sweep* sw, int R, int cap, bool force, 
   t->slots = tot.slots; t->distinct = tot.distinct; t->records = tot.records; t->batches = tot.batches; t->n_parts = tot.parts;
   p->info.sddmm_tile_rows = R;
   p->info.sddmm_tile_repeat_permille = tot.slots > 0 ? (int32_t)((tot.slots - tot.distinct) * 1000 / tot.slots) : 0;
+  int max_parts = 0;
+  if (tot.fits)
+    for (const tile_detail::TaskCount& c : counts) max_parts = std::max(max_parts, c.parts);
+  p->info.sddmm_tile_max_parts = max_parts;
   if (!wanted(*t)) return GRAPHOP_OK;
   if (!force) {
     tot = build_tile_layout(s->V, s->W, R, cap, s->win_cols, h_lo.data(), h_hi.data(), h_idx.data(), &host, 0, &counts);

@@ -106,6 +106,7 @@ int graphop_plan_import(const int64_t* row, const int64_t* indptr, const int64_t
   p->info.n_geometry_fallbacks = 0;   // (a live count of this plan object, not part of the persisted state)
   p->info.sddmm_tile_rows = 0;        // (likewise: what this plan object analysed)
   p->info.sddmm_tile_repeat_permille = 0;
+  p->info.sddmm_tile_max_parts = 0;
   (void)hipGetDevice(&p->device);
   plan_init_sweeps(p);
   int rc = plan_import_arrays(p, (const i64*)seg_chunk, idx32, eid32, long_segs, n_long, blk_seg, seg_e0,

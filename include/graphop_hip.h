@@ -86,6 +86,9 @@ typedef struct graphop_plan_info {
                                          (csrc/tile_layout.h), 0 = none yet.  Live, like the count above. */
   int32_t sddmm_tile_repeat_permille; /* ... and how many of 1000 slots repeat a neighbour id of their (window, tile) task:
                                          what the tile driver of the SDDMM-type passes does not gather twice */
+  int32_t sddmm_tile_max_parts;       /* ... and the largest number of parts (cuts of a task whose slots fit the kernel's LDS
+                                         result buffer) any (window, tile) task of that layout has; 0 = none analysed yet, or a
+                                         row piece that does not fit the buffer (no layout) */
 } graphop_plan_info_t;
 
 GRAPHOP_API int graphop_abi_version(void);

@@ -587,15 +587,25 @@ def test_misaligned_head_tensors_fall_back(dev):
         _lib.profile_enable(False); _lib.tune_reset(); _lib.clear_plan_cache()
 
 
-@pytest.mark.parametrize("seed", range(40))
-def test_fuzz_shapes_and_paths(dev, seed):
-    """Randomised battery: shape, heads, chunk size, degree profile, square / non-square, with
-    the sweep drivers forced on or off and random pacing / window knobs.  All vs the oracle."""
+FUZZ_SEEDS, FUZZ_TILE_SEEDS = 40, range(40, 48)
+
+
+def fuzz_case(seed):
+    """The draws of test_fuzz_shapes_and_paths for a seed -> (shape, {knob: value}, tile): pure, no library call.
+    Seeds 0 .. 39 draw what they always drew; a stream of its own (7300 + seed) gives those of them with one head of 64
+    floats the forced tile driver of the SDDMM-type passes (kernels_tile.h) with probability 1 / 2 and a tile height --
+    only seed 32 draws it, and its sweep drivers are not forced, so its table stays below the tile driver's reach --, and the
+    seeds 40 .. 47 take (h, d) = (1, 64), the tile knobs and window knobs under which the tile kernel must run (tile = True)
+    and otherwise the same draws."""
     rng = np.random.RandomState(1000 + seed)
+    k = {}
     h = int(rng.choice([1, 1, 2, 4, 8]))
     d = int(rng.choice([4, 8, 16, 32, 64, 128])) if h > 1 else int(rng.choice([16, 32, 64, 128, 256, 512]))
     while h * d > 1024:
         d //= 2
+    tile = seed in FUZZ_TILE_SEEDS
+    if tile:
+        h, d = 1, 64
     n_src = int(rng.randint(40, 700))
     n_dst = n_src if rng.rand() < 0.5 else int(rng.randint(40, 700))
     n_edges = int(rng.randint(1, 40) * n_src)
@@ -603,35 +613,61 @@ def test_fuzz_shapes_and_paths(dev, seed):
     hub = int(rng.choice([0, 0, 300, 1500]))
     forced = bool(rng.rand() < 0.6)
     if forced:
-        _lib.tune("sweep_min_kb", 0); _lib.tune("sweep_min_granule", 0); _lib.tune("max_windows", 128)
-        _lib.tune("window_kb", int(rng.choice([1, 4, 16]))); _lib.tune("vrow_t", int(rng.choice([0, 64, 256])))
-        rng.choice([0, 1, 2, 3]); _lib.tune("sweep_bpc", int(rng.choice([1, 2, 4])))   # (draws of the knobs removed in
-        rng.choice([0, 1]); rng.choice([0, 1]); rng.choice([0, 1])                      # round 4 kept: same graphs per seed)
-        _lib.tune("staged_ids", int(rng.choice([0, 7, 7]))); _lib.tune("sweep_k", int(rng.choice([0, 0, 1, 2, 4, 8])))
+        k.update(sweep_min_kb=0, sweep_min_granule=0, max_windows=128)
+        k.update(window_kb=int(rng.choice([1, 4, 16]))); k.update(vrow_t=int(rng.choice([0, 64, 256])))
+        rng.choice([0, 1, 2, 3]); k.update(sweep_bpc=int(rng.choice([1, 2, 4])))   # (draws of the knobs removed in
+        rng.choice([0, 1]); rng.choice([0, 1]); rng.choice([0, 1])                  # round 4 kept: same graphs per seed)
+        k.update(staged_ids=int(rng.choice([0, 7, 7]))); k.update(sweep_k=int(rng.choice([0, 0, 1, 2, 4, 8])))
         if rng.rand() < 0.6:     # walk drivers too (one head and several), tiny windows and grids
-            rng.choice([6, 7]); _lib.tune("walk", 6); _lib.tune("walk_min_bin", 0)
-            _lib.tune("walk_window_kb", int(rng.choice([2, 8, 32]))); _lib.tune("walk_window_kb_col", int(rng.choice([2, 8, 32])))
-            _lib.tune("walk_blocks", int(rng.choice([0, 8, 24]))); _lib.tune("walk_drift", int(rng.choice([0, 1, 2, 3])))
-            _lib.tune("walk_steps", int(rng.choice([1, 2, 3]))); _lib.tune("max_windows", 512)
+            rng.choice([6, 7]); k.update(walk=6, walk_min_bin=0)
+            k.update(walk_window_kb=int(rng.choice([2, 8, 32]))); k.update(walk_window_kb_col=int(rng.choice([2, 8, 32])))
+            k.update(walk_blocks=int(rng.choice([0, 8, 24]))); k.update(walk_drift=int(rng.choice([0, 1, 2, 3])))
+            k.update(walk_steps=int(rng.choice([1, 2, 3])), max_windows=512)
         else:
-            _lib.tune("walk", 0)
+            k.update(walk=0)
     if np.random.RandomState(7000 + seed).rand() < 0.5:      # (own stream: the draws above keep their graphs per seed)
-        _lib.tune("spmm_selfzero_min_mb", 0); _lib.tune("spmm_cpg", int(np.random.RandomState(7100 + seed).choice([1, 4, 16])))
-    _lib.tune("spmm_flat_cpg", int(np.random.RandomState(7200 + seed).choice([2, 16, 128])))   # (slot-walking chunk driver)
-    _lib.tune("spmm_flat_min_chunks", 0)
+        k.update(spmm_selfzero_min_mb=0, spmm_cpg=int(np.random.RandomState(7100 + seed).choice([1, 4, 16])))
+    k.update(spmm_flat_cpg=int(np.random.RandomState(7200 + seed).choice([2, 16, 128])))   # (slot-walking chunk driver)
+    k.update(spmm_flat_min_chunks=0)
+    trng = np.random.RandomState(7300 + seed)                # (own stream again)
+    tile_pick, tile_rows = bool(trng.rand() < 0.5), int(trng.choice([128, 192, 256, 384]))
+    if tile or (h == 1 and d == 64 and tile_pick):
+        k.update(sddmm_tile=2, sddmm_tile_rows=tile_rows)
+    if tile:   # a table of 40 .. 700 rows of 256 B in at least two windows, whatever the draws above left
+        k.update(sweep_min_kb=0, sweep_min_granule=0, max_windows=512, window_kb=k.get("window_kb", 4))
+    zero_rows = float(rng.choice([0, 0.2]))
+    shape = dict(h=h, d=d, n_src=n_src, n_dst=n_dst, n_edges=n_edges, cs=cs, hub=hub, zero_rows=zero_rows)
+    return shape, k, tile
+
+
+@pytest.mark.parametrize("seed", list(range(FUZZ_SEEDS)) + list(FUZZ_TILE_SEEDS))
+def test_fuzz_shapes_and_paths(dev, seed):
+    """Randomised battery: shape, heads, chunk size, degree profile, square / non-square, with
+    the sweep drivers forced on or off and random pacing / window knobs.  All vs the oracle.
+    Seeds 40 .. 47 (fuzz_case): one head of 64 floats with the tile driver of the SDDMM-type passes forced at a random tile
+    height under the battery's window knobs -- both SDDMM-type passes of the step must show k_sddmm_tile_f32."""
+    shape, knobs, tile = fuzz_case(seed)
+    h, d, n_src, n_dst, n_edges, cs, hub = (shape[x] for x in ("h", "d", "n_src", "n_dst", "n_edges", "cs", "hub"))
+    for key, value in knobs.items():
+        _lib.tune(key, value)
     _lib.clear_plan_cache()
     try:
-        g = random_graph(n_src, n_dst, n_edges, seed=seed, chunk_size=cs, zero_rows=float(rng.choice([0, 0.2])),
+        g = random_graph(n_src, n_dst, n_edges, seed=seed, chunk_size=cs, zero_rows=shape["zero_rows"],
                          hub=hub or None)
         # the reference's SpMM output is zeros_like(x): x (n_dst rows) must cover the row ids
         if g.n_dst < g.n_src:
             g = random_graph(n_src, n_src, n_edges, seed=seed, chunk_size=cs, hub=hub or None)
         inp = rand_inputs(g, h, d, seed=seed + 50, normal=True)
         want = oracle_step(oracle, g, inp["Q"], inp["K"], inp["V"], inp["dO"])
+        _lib.profile_enable(tile)
         got = hip_step(g.to(dev), *(inp[k].to(dev) for k in ("Q", "K", "V", "dO")))
+        if tile:
+            kern = {tag: r.get("kernel") for tag, r in _lib.profile_read().items()}
+            assert kern.get("sddmm_fwd") == "k_sddmm_tile_f32" and kern.get("spmm_bwd_dedata") == "k_sddmm_tile_f32", kern
         for k in ("s", "a", "o", "dQ", "dK", "dV"):
             close(got[k], want[k], rtol=2e-4, atol=2e-5)
     finally:
+        _lib.profile_enable(False)
         _lib.tune_reset()
         _lib.clear_plan_cache()
 
