@@ -65,6 +65,7 @@ _SIGNATURES = {
     "graphop_set_allocator": [ALLOC_FN, FREE_FN],
     "graphop_plan_prepare": [_P, ctypes.c_int, _c64, _c64, _c64, ctypes.c_int, _P],
     "graphop_plan_n_sweeps": [_P],
+    "graphop_sddmm_tile_cap": [ctypes.c_int],   # -> floats, not an error code
     "graphop_plan_sweep_info": [_P, ctypes.c_int, ctypes.POINTER(SweepInfo)],
     "graphop_plan_array": [_P, ctypes.c_char_p, ctypes.c_int, ctypes.POINTER(_vp), ctypes.POINTER(_c64)],
     "graphop_plan_import": [_P] * 4 + [ctypes.POINTER(PlanInfo)] + [_P] * 4 + [_c64] + [_P] * 4 + [ctypes.POINTER(_vp)],

@@ -514,6 +514,15 @@ struct TileLaunch {
   size_t lds_bytes;
   int nt;   // threads per workgroup
 };
+// Workgroups per CU at R vrows per tile (0: not a tile height), and the floats of a workgroup's result buffer: its share of
+// the CU's LDS, rounded down to 256 B, less the tile's A rows (256 B per vrow).
+int tile_per_cu(int R) { return (R == 128 || R == 192) ? 2 : (R == 256 || R == 384) ? 1 : 0; }
+int tile_cap(int R) {
+  const int per_cu = tile_per_cu(R);
+  if (!per_cu) return 0;
+  const int cap = (((kTileLdsBytes / per_cu) & ~255) - R * 256) / 4;
+  return cap > kTileMaxCap ? kTileMaxCap : cap;
+}
 // Does the tile driver take an SDDMM-type pass over `plan` (fp32, one head, 256-B rows, identity eid, table < 4 GiB, a
 // window structure, and -- knob sddmm_tile = 1 -- a plan whose slots repeat their tile's neighbours often enough)?
 // Fetches / builds the layout.  1 = launch it, 0 = no (the window-owner strips decide next), < 0 = error (negated).
@@ -527,7 +536,8 @@ int choose_tile(const graphop_plan* plan, i64 n_table_rows, i64 h, int dtype, hi
     if (!t.sddmm_tile || !plan || dtype != GRAPHOP_F32 || h != 1) return 0;
     if (!plan->info.eid_identity || !table_off32(n_table_rows, L, NV)) return 0;
     const int R = t.sddmm_tile_rows;
-    if (R != 128 && R != 192 && R != 256 && R != 384) return 0;
+    const int per_cu = tile_per_cu(R);
+    if (!per_cu) return 0;
     SweepLaunch sl;
     SweepOpts so;
     so.dry_run = 1;
@@ -535,15 +545,12 @@ int choose_tile(const graphop_plan* plan, i64 n_table_rows, i64 h, int dtype, hi
     so.bpc = sweep_bpc(NV, true);   // (the strips' geometry: one window structure serves both drivers)
     const int use = choose_sweep(plan, n_table_rows, L, NV, st, &sl, false, &so);
     if (use != 1) return use;
-    const int per_cu = R <= 192 ? 2 : 1;
     // a workgroup takes whole (window, tile) tasks, and the last round of tasks leaves CUs idle for up to one task: 1 / n
     // of the pass at n tasks per workgroup.  The measured gain is 7 % of a pass: below 32 tasks per
     // workgroup the tail can eat half of it -- such graphs stay on the strips (a wave's 32 vrows per task) unless forced
     // (a bound reasoned from the tail, not a measured break-even)
     if (t.sddmm_tile != 2 && (i64)sl.sweep->W * ceil_div((i64)sl.sweep->V, R) < 32LL * t.n_cu * per_cu) return 0;
-    const int lds_wg = (kTileLdsBytes / per_cu) & ~255;
-    int cap = (lds_wg - R * 16 * L * NV) / 4;
-    if (cap > kTileMaxCap) cap = kTileMaxCap;
+    const int cap = tile_cap(R);
     const Sweep::Tile* tl = nullptr;
     const int rc = plan_get_tile(const_cast<graphop_plan*>(plan), sl.sweep, R, cap, t.sddmm_tile == 2, t.sddmm_tile_min_repeat, st, &tl);
     if (rc != GRAPHOP_OK) return -rc;
@@ -572,12 +579,18 @@ int choose_tile(const graphop_plan* plan, i64 n_table_rows, i64 h, int dtype, hi
 template <int L, int NV>
 void launch_tile(const TileLaunch& tl, const float* a, const float* b, float* y, hipStream_t st) {
   if constexpr (L == 16 && NV == 1) {
-    if (tl.nt == 512) {
-      allow_full_lds((const void*)k_sddmm_tile_f32<L, NV, 512>);
-      hipLaunchKernelGGL((k_sddmm_tile_f32<L, NV, 512>), dim3(tl.blocks), dim3(512), tl.lds_bytes, st, tl.view, a, b, y);
-    } else {
-      allow_full_lds((const void*)k_sddmm_tile_f32<L, NV, 1024>);
-      hipLaunchKernelGGL((k_sddmm_tile_f32<L, NV, 1024>), dim3(tl.blocks), dim3(1024), tl.lds_bytes, st, tl.view, a, b, y);
+    auto go = [&](auto ntc, auto rpgc) {   // (threads, vrows per lane group): R = rpg * threads / 16
+      constexpr int NT = decltype(ntc)::value, RPG = decltype(rpgc)::value;
+      allow_full_lds((const void*)k_sddmm_tile_f32<L, NV, NT, RPG>);
+      hipLaunchKernelGGL((k_sddmm_tile_f32<L, NV, NT, RPG>), dim3(tl.blocks), dim3(NT), tl.lds_bytes, st, tl.view, a, b, y);
+    };
+    using std::integral_constant;
+    switch (tl.view.R) {
+      case 128: go(integral_constant<int, 512>{}, integral_constant<int, 4>{}); break;
+      case 192: go(integral_constant<int, 512>{}, integral_constant<int, 6>{}); break;
+      case 256: go(integral_constant<int, 1024>{}, integral_constant<int, 4>{}); break;
+      case 384: go(integral_constant<int, 1024>{}, integral_constant<int, 6>{}); break;
+      default: break;   // (choose_tile admits no other height)
     }
   }
 }
@@ -1150,6 +1163,8 @@ int softmax_forward_stats(int dtype, const Csr& g, const void* x, void* y, i64 h
 using namespace graphop;
 
 extern "C" {
+
+int graphop_sddmm_tile_cap(int rows) { return tile_cap(rows); }
 
 int graphop_plan_prepare(graphop_plan_t* plan, int dtype, int64_t n_table_rows, int64_t h, int64_t d,
                          int fused, void* stream) {

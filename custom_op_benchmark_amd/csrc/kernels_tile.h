@@ -48,23 +48,42 @@ __device__ __forceinline__ int row16_max(int v) {
   return v;
 }
 
-constexpr int kTileDescParts = 4;   // parts of a task whose records are handed over through LDS (a task rarely has two)
+// 16 bytes per lane from memory straight into LDS (gfx950: global_load_lds_dwordx4; no destination register).  src is per
+// lane; the destination is wave_base + lane x 16 B -- wave_base must be the same in every lane of the wave, and lanes that
+// are switched off neither load nor write.  The load counts on vmcnt: wait for it before the barrier in front of the readers.
+__device__ __forceinline__ void ld16_to_lds(const float* src, float4* wave_base) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src,
+                                   (__attribute__((address_space(3))) void*)wave_base, 16, 0, 0);
+}
+__device__ __forceinline__ void wait_vmem() { __builtin_amdgcn_s_waitcnt(0x0F70); }   // gfx9 encoding: vmcnt(0), the other counters free
+
+constexpr int kTileDescParts = 4;  // parts of a task whose records are handed over through LDS (a task rarely has two)
 
 // NT threads per workgroup: 1024 (one workgroup per CU) or 512 (two per CU where their LDS packs); 16 waves per CU either way.
 // Nothing a task needs first comes cold: its id is dequeued one task ahead (wave 0), its part records are fetched and the
 // lines of its record, slot-word and row-table streams are touched into L2 by the LAST wave while the task in front of
 // it runs; the lane groups take batches from an LDS counter, so that wave simply takes fewer.
-template <int L = 16, int NV = 1, int NT = 1024>
+//
+// The two phases around a task's batch loop issue their memory requests together, not one row at a time.  STAGING: a lane
+// group owns the RPG = R / G vrows g, g + G, ...; its lanes 0 .. RPG - 1 load one vrow's row-table entry and row id each
+// (one round trip), the group broadcasts them and requests all its A rows back to back (a second round trip, one wait),
+// straight into LDS.  WRITE-OUT: a group copies the vrows first + g, first + g + G, ... of a part, at most RPG of them; it
+// requests all their row-table entries together when it leaves the batch loop (they arrive while it stands at the
+// barrier) and then stores run after run with no load in between: loads and stores share vmcnt on gfx950, so a load per
+// vrow made every vrow wait for the store acknowledgements of the vrow before it.
+template <int L = 16, int NV = 1, int NT = 1024, int RPG = 4>
 __global__ __launch_bounds__(NT, 4) void k_sddmm_tile_f32(TileView tv, const float* __restrict__ A,
                                                           const float* __restrict__ B, float* __restrict__ y) {
   static_assert(L == 16 && NV == 1, "256-B rows: one float4 per lane of a 16-lane group");
+  static_assert(RPG >= 1 && RPG <= L, "one lane of a group per vrow entry");
   extern __shared__ float4 lds[];   // [R][L] A rows, then the result buffer
   __shared__ int task_sh[2][2];     // (window, tile) of the current and of the next task, by parity
   __shared__ int desc_sh[2][2 + 4 * kTileDescParts];   // first part, end part, the first parts' records, by parity
   __shared__ int ctr_sh;            // next batch of the part at hand
   constexpr int G = NT / L;
+  constexpr int R = RPG * G;        // (= tv.R: launch_tile picks the instance)
   const int l = threadIdx.x % L, g = threadIdx.x / L;
-  float* res = reinterpret_cast<float*>(lds + (i64)tv.R * L);
+  float* res = reinterpret_cast<float*>(lds + R * L);
   const char* lds_l = reinterpret_cast<const char*>(lds) + l * 16;
   SweepView qv{};
   qv.sync = tv.sync;
@@ -104,14 +123,27 @@ __global__ __launch_bounds__(NT, 4) void k_sddmm_tile_f32(TileView tv, const flo
       if (threadIdx.x == 0) { task_sh[par ^ 1][0] = more ? wn : -1; task_sh[par ^ 1][1] = tn; }
     }
     if (threadIdx.x == kWave) ctr_sh = 0;
-    const int v0 = t * tv.R;
-    const int nr = (tv.V - v0) < tv.R ? (tv.V - v0) : tv.R;
+    const int v0 = t * R;
+    const int nr = (tv.V - v0) < R ? (tv.V - v0) : R;
     const int2* rows = tv.rowtab + ((i64)w * tv.V + v0);
-    for (int i = g; i < nr; i += G) {   // A rows of the vrows that have slots in this window -> LDS
-      const int2 r = rows[i];
-      const i64 arow = tv.vr_row[v0 + i];
-      if (((unsigned)r.y >> 16) != 0) lds[i * L + l] = ld4(A, arow * L + l);
+    {   // the A rows of the vrows that have slots in this window -> LDS
+      const int mine = g + l * G;   // lane l < RPG: the group's l-th vrow (a vrow behind the tile's last: no slots)
+      int ey = 0, ar = 0;
+      if (l < RPG && mine < nr) {
+        ey = rows[mine].y;
+        ar = tv.vr_row[v0 + mine];
+      }
+      // The A rows go from memory to LDS without passing through registers (the batch loop leaves none to hold RPG rows
+      // in): a wave's four groups own four consecutive vrows, so its 64 lanes' 16 bytes are 1 KB in a row, which is the
+      // form the LDS-writing load takes -- wave-uniform LDS base, lane x 16 B added by the hardware, per-lane source.
+      float4* const wave_rows = lds + (threadIdx.x / kWave) * (kWave / L) * L;
+      static_for<RPG>([&](auto jc) {
+        constexpr int j = decltype(jc)::value;
+        const i64 arow = group_bcast<L, j>(ar);
+        if (((unsigned)group_bcast<L, j>(ey) >> 16) != 0) ld16_to_lds(A + (arow * L + l) * 4, wave_rows + j * G * L);
+      });
     }
+    wait_vmem();       // this wave's A rows are in LDS
     __syncthreads();
     if (threadIdx.x >= NT - kWave) {   // the next task's part records, and its streams' lines into L2 (speed only)
       const int wn = task_sh[par ^ 1][0], tn = task_sh[par ^ 1][1];
@@ -135,8 +167,8 @@ __global__ __launch_bounds__(NT, 4) void k_sddmm_tile_f32(TileView tv, const flo
             if (at < nd.w) tch[3 + q] = tv.slotw[(i64)nd.z + at];
           }
           if (lane * 32 < nd.y) tch[8] = tv.bstart[nd.x + lane * 32];
-          const int vn = tn * tv.R;
-          const int nrn = (tv.V - vn) < tv.R ? (tv.V - vn) : tv.R;
+          const int vn = tn * R;
+          const int nrn = (tv.V - vn) < R ? (tv.V - vn) : R;
           if (lane * 16 < nrn) tch[9] = tv.rowtab[(i64)wn * tv.V + vn + lane * 16].x;
           if (lane * 32 < nrn) tch[10] = tv.vr_row[vn + lane * 32];
           // (waited for here, by this wave alone, so that the landing registers are free again in the batch loop)
@@ -155,6 +187,9 @@ __global__ __launch_bounds__(NT, 4) void k_sddmm_tile_f32(TileView tv, const flo
       } else {
         pt = tv.parts[p];
       }
+      // (the same in every lane: kept in scalar registers across the batch loop)
+      pt = make_int4(__builtin_amdgcn_readfirstlane(pt.x), __builtin_amdgcn_readfirstlane(pt.y),
+                     __builtin_amdgcn_readfirstlane(pt.z), __builtin_amdgcn_readfirstlane(pt.w));
       const int nb = (pt.y + 15) >> 4;
       // batches come from the counter; the records of the batch after the one at hand are in flight behind its row requests
       int b = next_batch();
@@ -197,13 +232,18 @@ __global__ __launch_bounds__(NT, 4) void k_sddmm_tile_f32(TileView tv, const flo
         }
         b = bn;
       }
+      // the entries of the group's vrows of this part (pt.w <= R: at most RPG), one per lane, requested together; they
+      // arrive while the group stands at the barrier
+      int2 ent = make_int2(0, 0);
+      if (l < RPG && g + l * G < pt.w) ent = rows[pt.z + g + l * G];
       __syncthreads();   // the part's results are in the buffer; every group has left the batch loop
       if (threadIdx.x == kWave) ctr_sh = 0;
-      for (int i = pt.z + g; i < pt.z + pt.w; i += G) {   // every vrow's run -> y + its first edge id
-        const int2 r = rows[i];
-        const int len = (int)((unsigned)r.y >> 16), off = r.y & 0xffff;
-        for (int x = l; x < len; x += L) __builtin_nontemporal_store(res[off + x], y + ((i64)r.x + x));
-      }
+      static_for<RPG>([&](auto kc) {   // every vrow's run -> y + its first edge id (no load here: no wait for stores)
+        constexpr int k = decltype(kc)::value;
+        const int first = group_bcast<L, k>(ent.x), ry = group_bcast<L, k>(ent.y);
+        const int len = (int)((unsigned)ry >> 16), off = ry & 0xffff;
+        for (int x = l; x < len; x += L) __builtin_nontemporal_store(res[off + x], y + ((i64)first + x));
+      });
       if (p + 1 < p1) __syncthreads();   // the next part reuses the buffer and the counter
     }
     par ^= 1;

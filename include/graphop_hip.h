@@ -136,6 +136,10 @@ GRAPHOP_API const char* graphop_tune_key(int i);
 /* Device bytes currently held through the library's allocator hook / hipMalloc: plans, their window
  * structures and id layouts, setup temporaries.  What a binding's plan cache budgets against. */
 GRAPHOP_API int64_t graphop_memory_bytes(void);
+/* ABI 8, additive: floats of the LDS result buffer the tile driver of the SDDMM-type passes has at `rows` vrows per tile --
+ * the largest number of slots a part of a (window, tile) task holds (info.sddmm_tile_max_parts counts the parts); 0 where
+ * `rows` is not one of sddmm_tile_rows' values.  Not an error code. */
+GRAPHOP_API int graphop_sddmm_tile_cap(int rows);
 
 /* ---- device memory of plans ------------------------------------------------------------------
  * Plans own device arrays (per orientation: 8 B per chunk and 4-8 B per edge per dealt / walk layout in use; the 32-bit
