@@ -155,6 +155,10 @@ _SIGNATURES = {
     + [ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _c64],
     # the weights of those ops from their row statistics: Q, K, stats, b | NULL, xe | NULL, a; no workspace
     "graphop_attention_weights": [ctypes.c_int] + [_P] * 10 + [_c64] * 6 + [_P, _P],
+    # the weights of the fused GAT / GATv2 layers from their row statistics: el, er, ee | NULL, stats, a
+    # and xl, xr, xe | NULL, att, stats, a; no workspace
+    "graphop_gat_attention_weights": [ctypes.c_int] + [_P] * 9 + [_c64] * 5 + [ctypes.c_double, _P, _P],
+    "graphop_gatv2_attention_weights": [ctypes.c_int] + [_P] * 10 + [_c64] * 6 + [ctypes.c_double, _P, _P],
 }
 EXPORTED_SYMBOLS = sorted(list(_SIGNATURES) + ["graphop_abi_version", "graphop_last_error",
                                                "graphop_plan_destroy", "graphop_memory_bytes", "graphop_tune_key"])

@@ -1,6 +1,7 @@
 // Host-side helpers of the GAT family of entry points (gat.hip, gatv2.hip, gat_attention.hip, gat_edge_attention.hip,
-// gatv2_attention.hip, gatv2_edge_attention.hip, host_gat_attn_ops.h and host_gatv2_attn_ops.h): argument and plan
-// checks (the plan of an orientation, its bounds and its edge-id argument are host.h's Csr), the conditions of the fp32
+// gatv2_attention.hip, gatv2_edge_attention.hip, gat_weights.hip, host_gat_attn_ops.h and host_gatv2_attn_ops.h):
+// argument and plan checks (the plan of an orientation, its bounds and its edge-id argument are host.h's Csr), the
+// conditions of the fp32
 // fast kernels, the (h, d), bool and fp32 / fp64 dispatch, the one launch statement of a kernel with and without edge
 // term (go_launch, arg_if, GO_EDGE_KERNEL), the profile labels, the launch geometry
 // of the gather passes and the opening of the two GATv2 backwards.  Each exists once, here.  Not part of the C ABI.
@@ -50,6 +51,19 @@ inline bool gat_hd_fast_ok(int dtype, i64 h, i64 d, i64 E, i64 n_l, i64 n_r, std
   for (const void* p : ps)
     if (!aligned16(p)) return false;
   return true;
+}
+
+// fp32 fast kernels of an op without a feature width (gat_weights.hip): the head counts of GO_DISPATCH_GAT_ATTN_H, ids
+// that fit 31 bits, the per-(node or edge, head) arrays `items` aligned to their item width (NULL: an operand the call
+// does not have) and the (n, h, 2) statistics to the float2 they are loaded as
+inline bool gat_h_fast_ok(int dtype, i64 h, i64 E, i64 n_l, i64 n_r, std::initializer_list<const void*> items,
+                          const void* stats) {
+  if (tuning().force_generic || dtype != GRAPHOP_F32) return false;
+  if (h != 1 && h != 2 && h != 4 && h != 8) return false;
+  if (E >= 0x7fffffffLL || n_l >= 0x7fffffffLL || n_r >= 0x7fffffffLL) return false;
+  for (const void* p : items)
+    if (!gat_aligned(p, h)) return false;
+  return ((uintptr_t)stats % 8) == 0;
 }
 
 #define GO_DISPATCH_GAT_HD(h, d, ...)                                   \

@@ -1219,6 +1219,60 @@ std::vector<at::Tensor> gat_edge_attention_backward(const at::Tensor& row, const
                                      o, stats, dO, negative_slope, &drop, &ee, need_dee);
 }
 
+// ---- the weights of the fused GAT / GATv2 layers from their row statistics (include/graphop_hip.h:
+// graphop_gat_attention_weights, graphop_gatv2_attention_weights) ---------------------------------------------------
+// stats (n_src, h, 2) in the dtype of the row-side operand first (el or xl)
+#define CHECK_GAT_WEIGHTS_STATS(fn, first, stats, h)                                                              \
+  CHECK_SAME_DTYPE(first, stats);                                                                                 \
+  TORCH_CHECK((stats).dim() == 3 && (stats).size(0) == (first).size(0) && (stats).size(1) == (h) &&              \
+              (stats).size(2) == 2, fn, ": stats must be (n_src, h, 2) = (", (first).size(0), ", ", (h),         \
+              ", 2), got ", (stats).sizes())
+
+at::Tensor gat_attention_weights(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
+                                 const at::Tensor& indices, const at::Tensor& el, const at::Tensor& er,
+                                 const at::Tensor& stats, const c10::optional<at::Tensor>& ee, double negative_slope) {
+  const char* fn = "gat_attention_weights";
+  CHECK_CSR(row, indptr, eid, indices);
+  CHECK_INPUT(el); CHECK_INPUT(er); CHECK_INPUT(stats);
+  const int64_t h = gat_heads(el, er, fn);
+  const int64_t e = eid.size(0);
+  CHECK_GAT_WEIGHTS_STATS(fn, el, stats, h);
+  if (ee) gat_edge_term(el, *ee, e, h, fn);
+  DeviceGuard dg(el);
+  const auto pp = get_plan(row, indptr, eid, indices, er.size(0));
+  const auto& pl = *pp;
+  // a[e] is written once per row-major slot: only a chunk list that leaves slots out needs the zeros
+  const std::vector<int64_t> shape = el.dim() == 1 ? std::vector<int64_t>{e} : std::vector<int64_t>{e, h};
+  auto a = pl.info.full_coverage ? at::empty(shape, el.options()) : at::zeros(shape, el.options());
+  check(graphop_gat_attention_weights(dtype_code(el), ip(row), ip(indptr), ip(eid), ip(indices), vp(el), vp(er),
+                                      ee ? vp(*ee) : nullptr, vp(stats), vp(a), row.size(0), e, el.size(0), er.size(0),
+                                      h, negative_slope, pl.plan, stream_of(el)));
+  return a;
+}
+
+at::Tensor gatv2_attention_weights(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
+                                   const at::Tensor& indices, const at::Tensor& xl, const at::Tensor& xr,
+                                   const at::Tensor& att, const at::Tensor& stats,
+                                   const c10::optional<at::Tensor>& xe, double negative_slope) {
+  const char* fn = "gatv2_attention_weights";
+  CHECK_CSR(row, indptr, eid, indices);
+  CHECK_INPUT(xl); CHECK_INPUT(xr); CHECK_INPUT(att); CHECK_INPUT(stats);
+  const auto hd = gatv2_shapes(xl, xr, att, fn);
+  const int64_t h = hd.first, d = hd.second;
+  const int64_t e = eid.size(0);
+  CHECK_GAT_WEIGHTS_STATS(fn, xl, stats, h);
+  if (xe) gatv2_edge_rows(xl, *xe, e, h, d, fn);
+  DeviceGuard dg(xl);
+  const auto pp = get_plan(row, indptr, eid, indices, xr.size(0));
+  const auto& pl = *pp;
+  const std::vector<int64_t> shape = xl.dim() == 2 ? std::vector<int64_t>{e} : std::vector<int64_t>{e, h};
+  auto a = pl.info.full_coverage ? at::empty(shape, xl.options()) : at::zeros(shape, xl.options());
+  check(graphop_gatv2_attention_weights(dtype_code(xl), ip(row), ip(indptr), ip(eid), ip(indices), vp(xl), vp(xr),
+                                        xe ? vp(*xe) : nullptr, vp(att), vp(stats), vp(a), row.size(0), e, xl.size(0),
+                                        xr.size(0), h, d, negative_slope, pl.plan, stream_of(xl)));
+  return a;
+}
+
 // m[e, k] = keep(i, j, k) / (1 - p) of the dropout forms as an edge tensor, over the row-major CSR
 at::Tensor edge_dropout_mask(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
                              const at::Tensor& indices, int64_t h, double p, int64_t seed, int64_t offset,
@@ -1401,6 +1455,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("indices_c"), py::arg("el"), py::arg("er"), py::arg("ee"), py::arg("V"), py::arg("o"), py::arg("stats"),
         py::arg("dO"), py::arg("negative_slope") = 0.2, py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0,
         py::arg("need_dee") = true);
+  // (and the weights of the six fused GAT / GATv2 layers from their row statistics)
+  m.def("gat_attention_weights", &gat_attention_weights,
+        "Attention weights of the fused GAT layers from their row statistics (extra op)", py::arg("row"),
+        py::arg("indptr"), py::arg("eid"), py::arg("indices"), py::arg("el"), py::arg("er"), py::arg("stats"),
+        py::arg("ee") = py::none(), py::arg("negative_slope") = 0.2);
+  m.def("gatv2_attention_weights", &gatv2_attention_weights,
+        "Attention weights of the fused GATv2 layers from their row statistics (extra op)", py::arg("row"),
+        py::arg("indptr"), py::arg("eid"), py::arg("indices"), py::arg("xl"), py::arg("xr"), py::arg("att"),
+        py::arg("stats"), py::arg("xe") = py::none(), py::arg("negative_slope") = 0.2);
   m.def("clear_plan_cache", &clear_plan_cache, "Destroy every cached per-graph plan");
   m.def("release_plans", &release_plans, "Drop the cached plans of the orientation whose chunk list is `row`");
   m.def("plan_cache_size", &plan_cache_size, "Graph orientations in the plan cache");

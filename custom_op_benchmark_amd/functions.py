@@ -629,6 +629,135 @@ class FusedAttentionWeights(Function):
         return (None,) * 8 + (dQ, dK, dV, db if need_db else None, None, None, None, None)
 
 
+class FusedGATAttentionWeights(Function):
+    """The fused GAT layer that also returns its attention weights (extra op; PyG's
+    GATConv(..., return_attention_weights=True), DGL's get_attention=True):
+    apply(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V, ee=None, negative_slope=0.2, p=0.0,
+    seed=None, offset=0) -> (o, a).  ee=None is FusedGATAttentionDropout, ee is FusedGATEdgeAttention; o is that class's
+    o.  a holds the UNDROPPED weights by edge id -- (E) with 1-D el / er, else (E, h), SparseSoftmax's layout -- computed
+    from the row statistics the forward left (graphop.gat_attention_weights): one gather pass, not a second softmax.
+    The effective weights are a * graphop.edge_dropout_mask(...).
+    Saves what the matching class saves -- the CSR arrays, (el, er, [ee,] V, o, row statistics) -- and NOT a.  The backward
+    takes (dO, ga), either of which may be None.  dO goes through the matching fused backward; without it no fused pass
+    is launched.  ga goes through a recomputed a: ds' = a (ga - sum_row a ga) (sparse_softmax_backward; exact, because
+    a = softmax(s) whatever produced (m, l)), then without ee  d_el', d_er' = gat_scores_backward(ds', slope); with ee
+    z = gat_scores_forward(el, er, 1) + ee,  dz = z > 0 ? ds' : ds' * slope,  d_el', d_er' = gat_scores_backward(dz, 1)
+    and dee' = dz.  The (E, h) temporaries are inherent once a is an output.  The ga terms are added to the fused
+    backward's.  seed=None draws one from torch's default CPU generator."""
+
+    @staticmethod
+    def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, el, er, V, ee=None,
+                negative_slope=0.2, p=0.0, seed=None, offset=0):
+        a8 = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
+        ctx.drop = (float(negative_slope), float(p), int(_drop_seed(seed, p)), int(offset))
+        ctx.set_materialize_grads(False)
+        ctx.edge = ee is not None
+        csr = a8[:4]
+        if ctx.edge:
+            o, stats = _ops.gat_edge_attention_forward(*csr, el, er, ee, V, *ctx.drop)
+        else:
+            o, stats = _ops.gat_attention_dropout_forward(*csr, el, er, V, *ctx.drop)
+        a = _ops.gat_attention_weights(*csr, el, er, stats, ee, ctx.drop[0])
+        ctx.save_for_backward(*a8, el, er, *((ee,) if ctx.edge else ()), V, o, stats)
+        return o, a
+
+    @staticmethod
+    def backward(ctx, dO, ga):
+        a8, rest = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
+        csr = a8[:4]
+        slope = ctx.drop[0]
+        need_dee = ctx.edge and ctx.needs_input_grad[11]
+        d_ee = None
+        if ctx.edge:
+            el, er, ee, V, o, stats = rest
+        else:
+            (el, er, V, o, stats), ee = rest, None
+        if dO is None:          # nothing reaches V: its gradient stays None (set_materialize_grads(False))
+            d_el, d_er, dV = torch.zeros_like(el), torch.zeros_like(er), None
+        elif ctx.edge:
+            d_el, d_er, d_ee, dV = _ops.gat_edge_attention_backward(*a8, el, er, ee, V, o, stats, dO, *ctx.drop,
+                                                                    need_dee=need_dee)
+        else:
+            d_el, d_er, dV = _ops.gat_attention_dropout_backward(*a8, el, er, V, o, stats, dO, *ctx.drop)
+        if ga is not None:
+            a = _ops.gat_attention_weights(*csr, el, er, stats, ee, slope)
+            ds = _ops.sparse_softmax_backward(*csr[:3], a, ga.reshape(a.shape))
+            del a
+            if ctx.edge:
+                z = _ops.gat_scores_forward(*csr, el, er, 1.0) + ee
+                dz = torch.where(z > 0, ds, ds * slope)
+                del z, ds
+                d_el2, d_er2 = _ops.gat_scores_backward(*a8, el, er, dz, 1.0)
+                if need_dee:
+                    d_ee = dz.reshape(ee.shape) if dO is None else d_ee.add_(dz.reshape(ee.shape))
+            else:
+                d_el2, d_er2 = _ops.gat_scores_backward(*a8, el, er, ds, slope)
+            d_el += d_el2
+            d_er += d_er2
+        elif need_dee and dO is None:
+            d_ee = torch.zeros_like(ee)
+        return (None,) * 8 + (d_el, d_er, dV, d_ee if need_dee else None, None, None, None, None)
+
+
+class FusedGATv2AttentionWeights(Function):
+    """The fused GATv2 layer that also returns its attention weights (extra op; PyG's
+    GATv2Conv(..., return_attention_weights=True), DGL's get_attention=True):
+    apply(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, xe=None, negative_slope=0.2,
+    p=0.0, seed=None, offset=0) -> (o, a).  xe=None is FusedGATv2AttentionDropout, xe is FusedGATv2EdgeAttention; o is that
+    class's o.  a holds the UNDROPPED weights by edge id -- (E) with 2-D xl / xr, else (E, h) -- computed from the row
+    statistics the forward left (graphop.gatv2_attention_weights): one gather pass that fetches xr[j] per slot and
+    streams xe once, not a second softmax and nothing of size (E, h, d).
+    Saves what the matching class saves -- the CSR arrays, (xl, xr, [xe,] att, o, row statistics) -- and NOT a.  The
+    backward takes (dO, ga), either of which may be None.  dO goes through the matching fused backward; without it no
+    fused pass is launched.  Without xe, ga goes through a recomputed a: ds' = a (ga - sum_row a ga)
+    (sparse_softmax_backward), dxl', dxr', datt' = gatv2_scores_backward(ds', slope), added to the fused backward's.
+    With xe, a is marked non-differentiable: its gradient would need z = xl[i] + xr[j] + xe[e] per edge, (E, h, d)
+    temporaries, which is the memory the fused layer exists to avoid.  seed=None draws one from torch's default CPU
+    generator."""
+
+    @staticmethod
+    def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, xl, xr, att, xe=None,
+                negative_slope=0.2, p=0.0, seed=None, offset=0):
+        a8 = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
+        ctx.drop = (float(negative_slope), float(p), int(_drop_seed(seed, p)), int(offset))
+        ctx.set_materialize_grads(False)
+        ctx.edge = xe is not None
+        csr = a8[:4]
+        o, stats = _ops.gatv2_attention_dropout_forward(*csr, xl, xr, att, *ctx.drop, xe=xe)
+        a = _ops.gatv2_attention_weights(*csr, xl, xr, att, stats, xe, ctx.drop[0])
+        ctx.save_for_backward(*a8, xl, xr, *((xe,) if ctx.edge else ()), att, o, stats)
+        if ctx.edge:
+            ctx.mark_non_differentiable(a)
+        return o, a
+
+    @staticmethod
+    def backward(ctx, dO, ga):
+        a8, rest = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
+        csr = a8[:4]
+        need_dxe = ctx.edge and ctx.needs_input_grad[11]
+        dxe = None
+        if ctx.edge:
+            xl, xr, xe, att, o, stats = rest
+        else:
+            (xl, xr, att, o, stats), xe = rest, None
+        if dO is None:          # only ga is left, which does not reach xe: its gradient stays None, no (E, h, d) fill
+            dxl, dxr, datt = torch.zeros_like(xl), torch.zeros_like(xr), torch.zeros_like(att)
+        else:
+            dxl, dxr, datt, *more = _ops.gatv2_attention_dropout_backward(*a8, xl, xr, att, o, stats, dO, *ctx.drop,
+                                                                          xe=xe, need_dxe=need_dxe)
+            if need_dxe:
+                dxe = more[0]
+        if ga is not None and not ctx.edge:
+            a = _ops.gatv2_attention_weights(*csr, xl, xr, att, stats, None, ctx.drop[0])
+            ds = _ops.sparse_softmax_backward(*csr[:3], a, ga.reshape(a.shape))
+            del a
+            dxl2, dxr2, datt2 = _ops.gatv2_scores_backward(*a8, xl, xr, att, ds, ctx.drop[0])
+            dxl += dxl2
+            dxr += dxr2
+            datt += datt2
+        return (None,) * 8 + (dxl, dxr, datt, dxe, None, None, None, None)
+
+
 def _head_slice(x, g0, hg):
     """Heads [g0, g0 + hg) of a (n, h, d) tensor as a contiguous (n, hg, d) tensor ((n, d) for one head: the one-head
     kernels and the fused passes take that form)."""
@@ -887,6 +1016,27 @@ def attention_weights_step(g, Q, K, V, dO, ga=None, b=None, xe=None, p=0.0, seed
     _backward_pairs(((o, dO), (a, ga)))
     _lib.check_errors(sync=False)     # as in attention_step
     return s, a, o
+
+
+def fused_gat_attention_weights_step(g, el, er, V, dO, ga=None, ee=None, negative_slope=0.2, p=0.0, seed=0, offset=0):
+    """The fused GAT step that also returns its attention weights, through FusedGATAttentionWeights: backward of
+    <o, dO> + <a, ga> (either gradient may be None); returns (o, a).  The composed yardsticks are gat_attention_step,
+    gat_attention_dropout_step and gat_edge_attention_step, which return a already."""
+    o, a = FusedGATAttentionWeights.apply(*g.csr_args(), el, er, V, ee, negative_slope, p, seed, offset)
+    _backward_pairs(((o, dO), (a, ga)))
+    _lib.check_errors(sync=False)     # as in attention_step
+    return o, a
+
+
+def fused_gatv2_attention_weights_step(g, xl, xr, att, dO, ga=None, xe=None, negative_slope=0.2, p=0.0, seed=0,
+                                       offset=0):
+    """The fused GATv2 step that also returns its attention weights, through FusedGATv2AttentionWeights: backward of
+    <o, dO> + <a, ga> (either gradient may be None; ga needs xe=None); returns (o, a).  The composed yardsticks are
+    gatv2_attention_step, gatv2_attention_dropout_step and gatv2_edge_attention_step, which return a already."""
+    o, a = FusedGATv2AttentionWeights.apply(*g.csr_args(), xl, xr, att, xe, negative_slope, p, seed, offset)
+    _backward_pairs(((o, dO), (a, ga)))
+    _lib.check_errors(sync=False)     # as in attention_step
+    return o, a
 
 
 def attention_dropout_step(g, Q, K, V, dO, p, seed, offset=0):

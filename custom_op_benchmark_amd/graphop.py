@@ -38,7 +38,8 @@ __all__ = ["maskedmm_csr_forward", "maskedmm_csr_backward", "node_mul_edge_forwa
 # scores (att . LeakyReLU(xl[i] + xr[j]) per edge and head), and the fused GAT layer with a per-edge score term
 # (LeakyReLU(el[i] + er[j] + ee[e]), GATConv(edge_dim=...) / EGATConv), and the fused GATv2 layer with edge features
 # (att . LeakyReLU(xl[i] + xr[j] + xe[e]), GATv2Conv(edge_dim=...)): the optional xe / need_dxe arguments of the two
-# gatv2_attention_dropout_* ops.  EXTRA_OPS lists them, below _SCHEMAS.
+# gatv2_attention_dropout_* ops, and the attention weights of the six fused GAT / GATv2 layers from the row statistics
+# they return (gat_attention_weights, gatv2_attention_weights).  EXTRA_OPS lists them, below _SCHEMAS.
 
 _NULL = None
 # the index arrays of a call by argument name: one CSR orientation without and with `indices`, and the two spellings
@@ -1093,6 +1094,66 @@ def gat_edge_attention_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, 
                                    stats, dO, negative_slope, _drop_args(fn, p, seed, offset), ee, need_dee)
 
 
+# ---- the weights of the fused GAT / GATv2 layers from their row statistics (extra ops) ----------------
+def _gat_weights_stats(fn, first, name, stats, h):
+    """stats (n_src, h, 2) in the dtype of the row-side operand `first` (el or xl, called `name`)"""
+    _same_dtype(first, stats, name, "stats")
+    if tuple(stats.shape) != (first.size(0), h, 2):
+        raise RuntimeError("%s: stats must be (n_src, h, 2) = (%d, %d, 2), got %s"
+                           % (fn, first.size(0), h, tuple(stats.shape)))
+
+
+def gat_attention_weights(row, indptr, eid, indices, el, er, stats, ee=None, negative_slope=0.2):
+    """-> a, the attention weights of gat_attention_forward / gat_attention_dropout_forward (ee=None) or
+    gat_edge_attention_forward (ee) from the stats (n_src, h, 2) = (m_i, 1 / l_i) that op returned: for edge e = (i, j),
+    s_e = LeakyReLU((el[i] + er[j]) [+ ee[e]]),  a_e = exp(min(s_e - m_i, 0)) / l_i.  a is indexed by edge id, (n_edges)
+    for 1-D el / er, else (n_edges, h): the layout of sparse_softmax_forward's result (PyG's
+    return_attention_weights=True, DGL's get_attention=True).  These are the UNDROPPED weights; the effective ones are
+    a * edge_dropout_mask(...).  The clamp keeps a <= 1 whichever forward produced the statistics.  Edge ids that no
+    slot names read 0.  One gather pass: no second softmax, no workspace, no other (n_edges, h) tensor."""
+    fn = "gat_attention_weights"
+    _check_csr((row, indptr, eid, indices), _CSR, (el, "el"), (er, "er"), (stats, "stats"))
+    h = _gat_heads(el, er, fn)
+    e = eid.size(0)
+    _gat_weights_stats(fn, el, "el", stats, h)
+    if ee is not None:
+        _gat_edge_term(el, ee, e, h, fn)         # checks ee as an input too
+    with _lib.device_guard(el.device):
+        plan = get_plan(row, indptr, eid, indices, er.size(0))
+        # a[e] is written once per row-major slot: only a chunk list that leaves slots out needs the zeros
+        shape = (e,) if el.dim() == 1 else (e, h)
+        a = (torch.empty if plan.info.full_coverage else torch.zeros)(shape, dtype=el.dtype, device=el.device)
+        check(lib().graphop_gat_attention_weights(
+            dtype_code(el), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(el), ptr(er),
+            ptr(ee) if ee is not None else _NULL, ptr(stats), ptr(a), row.size(0), e, el.size(0), er.size(0), h,
+            float(negative_slope), plan.handle, stream_of(el)))
+    return a
+
+
+def gatv2_attention_weights(row, indptr, eid, indices, xl, xr, att, stats, xe=None, negative_slope=0.2):
+    """-> a, the attention weights of gatv2_attention_forward / gatv2_attention_dropout_forward (xe=None, or the edge
+    features xe of that call) from the stats (n_src, h, 2) = (m_i, 1 / l_i) that op returned: for edge e = (i, j),
+    s_e = att . LeakyReLU((xl[i] + xr[j]) [+ xe[e]]),  a_e = exp(min(s_e - m_i, 0)) / l_i.  a is indexed by edge id,
+    (n_edges) for 2-D xl / xr, else (n_edges, h); the UNDROPPED weights, as gat_attention_weights.  One gather pass that
+    fetches xr[j] per slot and streams xe once: no second softmax, no workspace, nothing of size (n_edges, h, d)."""
+    fn = "gatv2_attention_weights"
+    _check_csr((row, indptr, eid, indices), _CSR, (xl, "xl"), (xr, "xr"), (att, "att"), (stats, "stats"))
+    h, d = _gatv2_shapes(xl, xr, att, fn)
+    e = eid.size(0)
+    _gat_weights_stats(fn, xl, "xl", stats, h)
+    if xe is not None:
+        _gatv2_edge_rows(xl, xe, e, h, d, fn)         # checks xe as an input too
+    with _lib.device_guard(xl.device):
+        plan = get_plan(row, indptr, eid, indices, xr.size(0))
+        shape = (e,) if xl.dim() == 2 else (e, h)
+        a = (torch.empty if plan.info.full_coverage else torch.zeros)(shape, dtype=xl.dtype, device=xl.device)
+        check(lib().graphop_gatv2_attention_weights(
+            dtype_code(xl), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(xl), ptr(xr),
+            ptr(xe) if xe is not None else _NULL, ptr(att), ptr(stats), ptr(a), row.size(0), e, xl.size(0), xr.size(0),
+            h, d, float(negative_slope), plan.handle, stream_of(xl)))
+    return a
+
+
 
 def prepare(graph, h=1, d=64, dtype=torch.float32, fused=True):
     """Build a graph's plans and window structures ahead of the first op call (see graphs.prepare)."""
@@ -1144,7 +1205,9 @@ EXTRA_OPS = [n for n in _SCHEMAS if n not in __all__] + ["attention_backward_is_
                                                          # edge-type embeddings (attention_etype_*)
                                                          "attention_etype_forward", "attention_etype_backward",
                                                          # an edge-type score bias (attention_tbias_*)
-                                                         "attention_tbias_forward", "attention_tbias_backward"]
+                                                         "attention_tbias_forward", "attention_tbias_backward",
+                                                         # the weights of the fused GAT / GATv2 layers
+                                                         "gat_attention_weights", "gatv2_attention_weights"]
 _torch_lib = None
 
 

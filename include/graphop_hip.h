@@ -960,6 +960,39 @@ GRAPHOP_API int graphop_attention_weights(int dtype, const int64_t* row, const i
                               const void* xe, void* a, int64_t n_chunks, int64_t n_edges, int64_t n_q, int64_t n_k,
                               int64_t h, int64_t d, const graphop_plan_t* plan, void* stream);
 
+/* ---- attention weights of the fused GAT and GATv2 layers (not in the reference) -------------------
+ * The weights the layer used, as an edge tensor (PyG's return_attention_weights=True, DGL's get_attention=True), from
+ * the row statistics stats (n_l, h, 2) = (m_i, linv_i) that graphop_gat_attention_forward / _dropout_forward /
+ * graphop_gat_edge_attention_forward, or graphop_gatv2_attention_forward / _dropout_forward /
+ * graphop_gatv2_edge_attention_forward, left.  Edge e = (i, j), head k; i indexes el / xl and stats, j indexes er / xr;
+ * ee, xe and a are indexed by EDGE ID.  ee / xe == NULL: the layer without its edge operand.
+ *   GAT  :  s_e = LeakyReLU((el[i,k] + er[j,k]) [+ ee[e,k]])                              ee (n_edges, h)
+ *   GATv2:  s_e = sum_c att[k,c] * LeakyReLU((xl[i,k,c] + xr[j,k,c]) [+ xe[e,k,c]])       xe (n_edges, h, d)
+ *   a_e = exp(min(s_e - m_i, 0)) * linv_i     a (n_edges, h), the edge layout of sparse_softmax / vector_spmm
+ * The score is written with the expressions of the fused forwards.  a holds the UNDROPPED weights (the effective ones
+ * are a * graphop_edge_dropout_mask).  The min(..., 0) is that of graphop_attention_weights: the statistics may come from
+ * a kernel that summed in another order (the long-segment merge of the fused GATv2 forward, a generic kernel), and the
+ * clamp keeps a_e <= linv_i <= 1 whichever forward made them.  a[e] is written once for every edge id a row-major slot
+ * names; other entries are left untouched (zero-fill a first where the chunk list may leave slots out).  No atomics and
+ * no workspace: the result is reproducible bit for bit.
+ * Checks, all before anything touches a device, in this order: dtype and sizes; stats or a NULL (unless the problem is
+ * empty); a matching plan must bound the ids by n_l / n_r (an error, not a fall-back).  Empty problems (n_chunks,
+ * n_edges, n_l or n_r zero) return OK and dereference nothing.
+ * Forms: k_gatw_f32 for fp32 calls with h in {1, 2, 4, 8}, a matching plan, ids below 2^31 and el, er, ee, a aligned to
+ * 4 * min(h, 4) bytes (stats to 8); k_gv2w_f32 for fp32 calls whose (h, d) is one of (1,64) (2,32) (2,64) (4,16) (4,32)
+ * (4,64) (8,8) (8,16) (8,32) with a matching plan, 16-byte aligned xl, xr, xe, att, stats, a and ids below 2^31; neither
+ * owns a row, so any chunk order and partial chunk lists take them.  k_gatw_generic / k_gv2w_generic (one wave per chunk)
+ * for everything else (fp64, other shapes, no plan, misaligned operands, GRAPHOP_FORCE_GENERIC). */
+GRAPHOP_API int graphop_gat_attention_weights(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                              const int64_t* indices, const void* el, const void* er, const void* ee /* NULL ok */,
+                              const void* stats, void* a, int64_t n_chunks, int64_t n_edges, int64_t n_l, int64_t n_r,
+                              int64_t h, double negative_slope, const graphop_plan_t* plan, void* stream);
+GRAPHOP_API int graphop_gatv2_attention_weights(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                              const int64_t* indices, const void* xl, const void* xr, const void* xe /* NULL ok */,
+                              const void* att, const void* stats, void* a, int64_t n_chunks, int64_t n_edges,
+                              int64_t n_l, int64_t n_r, int64_t h, int64_t d, double negative_slope,
+                              const graphop_plan_t* plan, void* stream);
+
 /* ---- halo pack / unpack of the node-range sharded step (not in the reference: single GPU) --------
  * gather_rows:      dst[i, :] = src[idx[i], :]          (send buffer of the rows peers gather from)
  * scatter_add_rows: dst[idx[i], :] += src[i, :]         (partial gradient rows coming home; idx may
