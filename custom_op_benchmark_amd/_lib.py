@@ -18,6 +18,7 @@ LIB_PATH = os.environ.get("GRAPHOP_LIB") or os.path.join(_HERE, "libgraphop_hip.
 ABI_VERSION = 8
 
 F32, F64 = 0, 1
+BF16 = 2   # the plain attention_forward / attention_backward alone (attn_dtype_code)
 _c64 = ctypes.c_int64
 _vp = ctypes.c_void_p
 _lib = None
@@ -302,6 +303,19 @@ def dtype_code(t):
         return F64
     # the reference raises from AT_DISPATCH_FLOATING_TYPES (graphop_kernel.cu:291)
     raise RuntimeError('graphop: not implemented for \'%s\' (float32 / float64 only)' % t.dtype)
+
+
+def attn_dtype_code(fn, t):
+    """dtype_code for the fused attention ops: the plain step (attention_forward / attention_backward and its queries)
+    also takes torch.bfloat16; every other form keeps dtype_code's answer."""
+    if t.dtype == torch.bfloat16 and fn in ("attention_forward", "attention_backward"):
+        return BF16
+    return dtype_code(t)
+
+
+def attn_stats_dtype(t):
+    """the row statistics of a fused attention call on tables like t: fp32 for bfloat16 tables, else t's dtype"""
+    return torch.float32 if t.dtype == torch.bfloat16 else t.dtype
 
 
 # ---- plans: cached per (row, indptr, eid, indices) tensor identity ------------------------------

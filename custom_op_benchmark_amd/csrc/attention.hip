@@ -318,13 +318,21 @@ int attn_backward_form(bool biased, bool dry_run, int dtype, i64 h, i64 d, i64 n
   return GRAPHOP_OK;
 }
 
+// The plain op's four entry points (forward, backward, workspace query, is_fused) also take GRAPHOP_BF16
+// (attention_bf16.hip); every other one answers it with attn_check's "bad dtype" as before.  What attn_check is given:
+inline int attn_plain_dtype(bool plain, int dtype) { return plain && dtype == GRAPHOP_BF16 ? GRAPHOP_F32 : dtype; }
+
 // bwd_arrays: E-sized arrays of the composed backward (4; 5 with dropout: the masked weights; with a bias one fewer
 // where db takes the place of ds).  bias: the forms of the op with a bias are the ones decided on.
 int attn_workspace_bytes(const char* fn, int dtype, int backward, int64_t n_edges, int64_t n_q, int64_t n_k, int64_t h,
                          int64_t d, const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream,
-                         int bwd_arrays, int64_t* bytes_out, bool bias = false) {
+                         int bwd_arrays, int64_t* bytes_out, bool bias = false, bool plain = false) {
   GO_CHECK_ARG(bytes_out != nullptr, "%s: bytes_out is NULL", fn);
-  GO_TRY(attn_check(fn, dtype, 0, 0, n_edges, n_q, n_k, h, d));
+  GO_TRY(attn_check(fn, attn_plain_dtype(plain, dtype), 0, 0, n_edges, n_q, n_k, h, d));
+  if (dtype == GRAPHOP_BF16) {
+    *bytes_out = (int64_t)attn_bf16_workspace(backward != 0, h, d, n_edges, n_q, n_k, plan_r, plan_c);
+    return GRAPHOP_OK;
+  }
   const size_t es = esize(dtype);
   hipStream_t st = (hipStream_t)stream;
   if (!backward) {
@@ -366,7 +374,7 @@ struct AttnCall {
 int attn_open(const char* fn, int dtype, i64 n_row_chunks, i64 n_col_chunks, i64 n_edges, i64 n_q, i64 n_k, i64 h, i64 d,
               const DropIn* din, const BiasIn* bias, void* stream, AttnCall* c) {
   GO_TRY(check_async_error(false));
-  GO_TRY(attn_check(fn, dtype, n_row_chunks, n_col_chunks, n_edges, n_q, n_k, h, d));
+  GO_TRY(attn_check(fn, attn_plain_dtype(!din && !bias, dtype), n_row_chunks, n_col_chunks, n_edges, n_q, n_k, h, d));
   if (din) GO_TRY(attn_drop_check(fn, *din, n_q, n_k, &c->hdrop));
   if (bias) GO_TRY(attn_bias_check(fn, *bias, n_edges, h));
   c->st = (hipStream_t)stream;
@@ -393,6 +401,9 @@ int attn_forward(const char* fn, int dtype, const int64_t* row, const int64_t* i
   const HostDrop* drop = c.drop;
   const int64_t head0 = c.head0;
   hipStream_t st = c.st;
+  if (dtype == GRAPHOP_BF16)
+    return attn_bf16_forward(fn, Csr(row, indptr, eid, indices, n_chunks, n_edges, plan), n_q, n_k, h, d, Q, K, V, o, stats,
+                             workspace, workspace_bytes, st);
   const size_t es = esize(dtype);
   if (n_q * h > 0) {
     GO_PTR(fn, stats);
@@ -453,6 +464,8 @@ int attn_backward(const char* fn, int dtype, const int64_t* row, const int64_t* 
   const Csr gr(row, indptr_r, eid_r, indices_r, n_row_chunks, n_edges, plan_r, "row", "indptr_r", "eid_r", "indices_r");
   const Csr gc(col, indptr_c, eid_c, indices_c, n_col_chunks, n_edges, plan_c, "col", "indptr_c", "eid_c", "indices_c");
   const graphop_plan *pr = gr.plan, *pc = gc.plan;
+  if (dtype == GRAPHOP_BF16)
+    return attn_bf16_backward(fn, gr, gc, n_q, n_k, h, d, Q, K, V, o, stats, dO, dQ, dK, dV, workspace, workspace_bytes, st);
   AttnFast af;
   AttnBwd form;
   GO_TRY(attn_backward_form(bias != nullptr, /*dry_run=*/false, dtype, h, d, n_edges, n_q, n_k, pr, pc, st, &af, &form));
@@ -544,7 +557,7 @@ int graphop_attention_workspace_bytes(int dtype, int backward, int64_t n_edges, 
                                       const graphop_plan_t* plan_r, const graphop_plan_t* plan_c,
                                       void* stream, int64_t* bytes_out) {
   return attn_workspace_bytes("attention_workspace_bytes", dtype, backward, n_edges, n_q, n_k, h, d, plan_r, plan_c,
-                              stream, 4, bytes_out);
+                              stream, 4, bytes_out, /*bias=*/false, /*plain=*/true);
 }
 
 int graphop_attention_dropout_workspace_bytes(int dtype, int backward, int64_t n_edges, int64_t n_q, int64_t n_k,
@@ -558,6 +571,10 @@ int graphop_attention_backward_is_fused(int dtype, int64_t n_edges, int64_t n_q,
                                         int64_t d, const graphop_plan_t* plan_r,
                                         const graphop_plan_t* plan_c, void* stream, int* fused_out) {
   GO_CHECK_ARG(fused_out != nullptr, "attention_backward_is_fused: fused_out is NULL");
+  if (dtype == GRAPHOP_BF16) {   // one form: fused, or refused
+    *fused_out = attn_bf16_ok(h, d, n_edges, n_q, n_k, plan_r, plan_c) ? 1 : 0;
+    return GRAPHOP_OK;
+  }
   AttnFast af;
   AttnBwd form;
   GO_TRY(attn_backward_form(/*biased=*/false, /*dry_run=*/true, dtype, h, d, n_edges, n_q, n_k, plan_r, plan_c,

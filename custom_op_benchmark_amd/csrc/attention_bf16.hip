@@ -1,0 +1,242 @@
+// The plain fused attention step on bfloat16 tables (kernels_attn_bf16.h): what is supported, the
+// workspace layouts and the launches.  attention.hip calls these from the four entry points that take GRAPHOP_BF16
+// (graphop_attention_forward / _backward / _workspace_bytes / _backward_is_fused); there is one form and no composed
+// path behind it, so an unmet condition is an error that names it, and no knob steers anything.
+#include "common.h"
+#include "host.h"
+#include "host_attn_rows.h"
+#include "host_gat.h"
+#include "kernels_attn_bf16.h"
+
+namespace graphop {
+namespace {
+
+// the bf16 set: the pairs of GO_DISPATCH_GAT_HD, (1, 128) and (8, 64) -- rows of 64, 128, 256 or 512 elements
+#define GO_DISPATCH_ATTN_BF16_HD(h, d, ...)                              \
+  switch ((int)((h) * 1000 + (d))) {                                     \
+    case 1128: { constexpr int H = 1, D = 128; __VA_ARGS__; } break;     \
+    case 8064: { constexpr int H = 8, D = 64; __VA_ARGS__; } break;      \
+    default: GO_DISPATCH_GAT_HD(h, d, __VA_ARGS__); break;               \
+  }
+
+// lanes per group of a pair of the set, 0 outside it
+int bf16_lanes(i64 h, i64 d) {
+  int lanes = 0;
+  if (h >= 1 && h <= 8 && d >= 8 && d <= 128) GO_DISPATCH_ATTN_BF16_HD(h, d, { lanes = AttnBf16Cfg<H, D>::L; });
+  return lanes;
+}
+
+// what one direction asks of ONE plan (own rows n_own, gathered table n_tab); `why` gets the unmet condition
+bool bf16_plan_unmet(char* why, size_t cap, const char* name, const graphop_plan* plan, i64 n_edges, i64 n_own, i64 n_tab) {
+  if (!plan) snprintf(why, cap, "%s is NULL or not the plan of the call's arrays", name);
+  else if (!plan->indices) snprintf(why, cap, "%s was made without indices", name);
+  else if (!plan->info.row_owned) snprintf(why, cap, "%s is not row_owned (rows sorted, indptr monotone)", name);
+  else if (plan->info.max_row >= n_own || plan->info.max_index >= n_tab)
+    snprintf(why, cap, "%s holds row id %lld and neighbour id %lld but the tables have %lld and %lld rows", name,
+             (long long)plan->info.max_row, (long long)plan->info.max_index, (long long)n_own, (long long)n_tab);
+  else if (n_edges >= 0x7fffffffLL || n_tab >= 0x7fffffffLL || n_own > (i64)kBf16RecRow)
+    snprintf(why, cap, "%s: ids must lie below 2^31 and row ids below 2^30", name);
+  else if (2 * attn_rows_geometry(plan->info.n_chunks).groups >= 0x7fffffffLL)
+    snprintf(why, cap, "%s has too many chunks for 32-bit record slots", name);
+  else return false;
+  return true;
+}
+
+bool bf16_shape_unmet(char* why, size_t cap, i64 h, i64 d) {
+  if (bf16_lanes(h, d)) return false;
+  snprintf(why, cap, "(h, d) = (%lld, %lld) is not in the bfloat16 set: 1 x 64, 1 x 128, 8 x 64 and the several-head pairs",
+           (long long)h, (long long)d);
+  return true;
+}
+
+// the chunk geometry of a pass: attn_rows_geometry's chunks per group and groups, workgroups for this pair's lane groups
+struct Bf16Geo {
+  i64 cpg, groups, np;
+  int lanes;
+  Bf16Geo(i64 n_chunks, int lanes_) : lanes(lanes_) {
+    const ChunkGeometry geo = attn_rows_geometry(n_chunks);
+    cpg = geo.cpg; groups = geo.groups; np = 2 * geo.groups;
+  }
+  dim3 grid(i64 n_groups) const { return dim3((unsigned)ceil_div(n_groups, (i64)(kFastBlock / lanes))); }
+};
+
+struct Bf16Take {
+  char* base;
+  size_t total = 0;
+  void* operator()(size_t bytes) {
+    void* p = base ? base + total : nullptr;
+    total += up256(bytes);
+    return p;
+  }
+};
+
+// forward: 2 * groups records of (row word | (m, l) per head | o row), all fp32
+struct Bf16FwdWs {
+  unsigned* p_row;
+  float *p_ml, *p_o;
+  size_t total;
+  Bf16FwdWs(void* base, i64 np, i64 h, i64 F) {
+    Bf16Take take{(char*)base};
+    p_row = (unsigned*)take(sizeof(unsigned) * (size_t)np);
+    p_ml = (float*)take(sizeof(float) * 2 * (size_t)(np * h));
+    p_o = (float*)take(sizeof(float) * (size_t)(np * F));
+    total = take.total;
+  }
+};
+
+// backward: the packed (K | V) and (Q | dO) tables of 2 F bf16 per node, stats4 per (query row, head), and the records
+// of whichever pass is running -- the row pass's np_r of F floats, then the column pass's np_c of 2 F
+struct Bf16BwdWs {
+  uint4 *kv, *qdo;
+  float4* st4;
+  unsigned* p_row;
+  float* p_acc;
+  size_t total;
+  Bf16BwdWs(void* base, i64 n_q, i64 n_k, i64 h, i64 F, i64 np_r, i64 np_c) {
+    Bf16Take take{(char*)base};
+    kv = (uint4*)take(2 * (size_t)(n_k * 2 * F));
+    qdo = (uint4*)take(2 * (size_t)(n_q * 2 * F));
+    st4 = (float4*)take(sizeof(float4) * (size_t)(n_q * h));
+    p_row = (unsigned*)take(sizeof(unsigned) * (size_t)(np_r > np_c ? np_r : np_c));
+    p_acc = (float*)take(sizeof(float) * (size_t)(np_r > 2 * np_c ? np_r : 2 * np_c) * (size_t)F);
+    total = take.total;
+  }
+};
+
+void bf16_fill_rows(unsigned* p_row, i64 np, hipStream_t st) {
+  ProfScope prof("attn_bf16_setup", st, "k_fill");
+  const i64 want = ceil_div(np, 256);
+  hipLaunchKernelGGL((k_fill<int>), dim3((unsigned)(want > 4096 ? 4096 : want)), dim3(256), 0, st, (int*)p_row, np, -1);
+}
+
+int bf16_tables_aligned(const char* fn, std::initializer_list<const void*> ps) {
+  for (const void* p : ps) GO_CHECK_ARG(aligned16(p), "%s: bfloat16 tables must be 16-byte aligned", fn);
+  return GRAPHOP_OK;
+}
+
+template <bool COL>
+int bf16_bwd_pass(const char* tag, const Csr& g, i64 h, i64 d, const uint4* own, const uint4* xt, const float4* st4,
+                  uint4* out0, uint4* out1, const Bf16BwdWs& w, hipStream_t st) {
+  if (g.n_chunks == 0) return GRAPHOP_OK;
+  const Bf16Geo geo(g.n_chunks, bf16_lanes(h, d));
+  const AttnBf16BwdRec rec{w.p_row, w.p_acc};
+  bf16_fill_rows(w.p_row, geo.np, st);
+  {
+    ProfScope prof(tag, st, "k_attn_bf16_bwd_rows");
+    GO_DISPATCH_ATTN_BF16_HD(h, d, {
+      hipLaunchKernelGGL((k_attn_bf16_bwd_rows<H, D, COL>), geo.grid(geo.groups), dim3(kFastBlock), 0, st, g.row, g.indptr,
+                         g.indices, own, xt, st4, out0, out1, rec, g.n_chunks, (int)geo.cpg);
+    });
+    GO_LAUNCH_CHECK();
+  }
+  ProfScope prof("attn_bf16_bwd_merge", st, "k_attn_bf16_bwd_merge");
+  GO_DISPATCH_ATTN_BF16_HD(h, d, {
+    hipLaunchKernelGGL((k_attn_bf16_bwd_merge<H, D, COL>), geo.grid(geo.np), dim3(kFastBlock), 0, st, rec, out0, out1, geo.np);
+  });
+  GO_LAUNCH_CHECK();
+  return GRAPHOP_OK;
+}
+
+}  // namespace
+
+bool attn_bf16_ok(i64 h, i64 d, i64 n_edges, i64 n_q, i64 n_k, const graphop_plan* plan_r, const graphop_plan* plan_c) {
+  char why[256];
+  return n_edges > 0 && !bf16_shape_unmet(why, sizeof(why), h, d) &&
+         !bf16_plan_unmet(why, sizeof(why), "plan_r", plan_r, n_edges, n_q, n_k) &&
+         !bf16_plan_unmet(why, sizeof(why), "plan_c", plan_c, n_edges, n_k, n_q);
+}
+
+size_t attn_bf16_workspace(bool backward, i64 h, i64 d, i64 n_edges, i64 n_q, i64 n_k, const graphop_plan* plan_r,
+                           const graphop_plan* plan_c) {
+  char why[256];
+  if (n_edges == 0 || bf16_shape_unmet(why, sizeof(why), h, d) ||
+      bf16_plan_unmet(why, sizeof(why), "plan_r", plan_r, n_edges, n_q, n_k))
+    return 0;
+  const int lanes = bf16_lanes(h, d);
+  const i64 np_r = Bf16Geo(plan_r->info.n_chunks, lanes).np;
+  if (!backward) return Bf16FwdWs(nullptr, np_r, h, h * d).total;
+  if (bf16_plan_unmet(why, sizeof(why), "plan_c", plan_c, n_edges, n_k, n_q)) return 0;
+  return Bf16BwdWs(nullptr, n_q, n_k, h, h * d, np_r, Bf16Geo(plan_c->info.n_chunks, lanes).np).total;
+}
+
+int attn_bf16_forward(const char* fn, const Csr& g, i64 n_q, i64 n_k, i64 h, i64 d, const void* Q, const void* K,
+                      const void* V, void* o, void* stats, void* ws, i64 ws_bytes, hipStream_t st) {
+  const i64 F = h * d;
+  if (n_q * h == 0) return GRAPHOP_OK;
+  GO_PTR(fn, stats);
+  if (F > 0) GO_PTR(fn, o);
+  if (g.n_edges > 0 && g.n_chunks > 0) {
+    char why[256];
+    GO_CHECK_ARG(!bf16_shape_unmet(why, sizeof(why), h, d) &&
+                     !bf16_plan_unmet(why, sizeof(why), "plan", g.plan, g.n_edges, n_q, n_k),
+                 "%s: bfloat16 unsupported: %s", fn, why);
+    GO_PTR(fn, Q); GO_PTR(fn, K); GO_PTR(fn, V);
+    GO_TRY(bf16_tables_aligned(fn, {Q, K, V, o}));
+  }
+  // rows without slots: o = 0, stats = (0, 0)
+  GO_HIP(zero_async(stats, sizeof(float) * (size_t)(n_q * h * 2), st));
+  GO_HIP(zero_async(o, 2 * (size_t)(n_q * F), st));
+  if (g.n_edges == 0 || g.n_chunks == 0) return GRAPHOP_OK;
+  const Bf16Geo geo(g.n_chunks, bf16_lanes(h, d));
+  const Bf16FwdWs w(ws, geo.np, h, F);
+  GO_TRY(attn_ws_check(fn, "attention_workspace_bytes", true, w.total, ws, ws_bytes));
+  const AttnBf16FwdArgs a{(const uint4*)Q, (const uint4*)K, (const uint4*)V, (uint4*)o, (float*)stats, w.p_row, w.p_ml, w.p_o};
+  bf16_fill_rows(w.p_row, geo.np, st);
+  {
+    ProfScope prof("attn_bf16_fwd_rows", st, "k_attn_bf16_fwd_rows");
+    GO_DISPATCH_ATTN_BF16_HD(h, d, {
+      hipLaunchKernelGGL((k_attn_bf16_fwd_rows<H, D>), geo.grid(geo.groups), dim3(kFastBlock), 0, st, g.row, g.indptr,
+                         g.indices, a, g.n_chunks, (int)geo.cpg);
+    });
+    GO_LAUNCH_CHECK();
+  }
+  ProfScope prof("attn_bf16_fwd_merge", st, "k_attn_bf16_fwd_merge");
+  GO_DISPATCH_ATTN_BF16_HD(h, d, {
+    hipLaunchKernelGGL((k_attn_bf16_fwd_merge<H, D>), geo.grid(geo.np), dim3(kFastBlock), 0, st, a, geo.np);
+  });
+  GO_LAUNCH_CHECK();
+  return GRAPHOP_OK;
+}
+
+int attn_bf16_backward(const char* fn, const Csr& r, const Csr& c, i64 n_q, i64 n_k, i64 h, i64 d, const void* Q,
+                       const void* K, const void* V, const void* o, const void* stats, const void* dO, void* dQ, void* dK,
+                       void* dV, void* ws, i64 ws_bytes, hipStream_t st) {
+  const i64 F = h * d;
+  if ((n_q + n_k) * F == 0) return GRAPHOP_OK;
+  const bool empty = r.n_edges == 0 || (r.n_chunks == 0 && c.n_chunks == 0);
+  if (!empty) {
+    char why[256];
+    GO_CHECK_ARG(!bf16_shape_unmet(why, sizeof(why), h, d) &&
+                     !bf16_plan_unmet(why, sizeof(why), "plan_r", r.plan, r.n_edges, n_q, n_k) &&
+                     !bf16_plan_unmet(why, sizeof(why), "plan_c", c.plan, c.n_edges, n_k, n_q),
+                 "%s: bfloat16 unsupported: %s", fn, why);
+    GO_PTR(fn, Q); GO_PTR(fn, K); GO_PTR(fn, V); GO_PTR(fn, o); GO_PTR(fn, stats); GO_PTR(fn, dO);
+  }
+  if (n_q > 0) GO_PTR(fn, dQ);
+  if (n_k > 0) { GO_PTR(fn, dK); GO_PTR(fn, dV); }
+  if (!empty) GO_TRY(bf16_tables_aligned(fn, {Q, K, V, o, dO, dQ, dK, dV}));
+  GO_HIP(zero_async(dQ, 2 * (size_t)(n_q * F), st));
+  GO_HIP(zero_async(dK, 2 * (size_t)(n_k * F), st));
+  GO_HIP(zero_async(dV, 2 * (size_t)(n_k * F), st));
+  if (empty) return GRAPHOP_OK;
+  const int lanes = bf16_lanes(h, d);
+  const Bf16BwdWs w(ws, n_q, n_k, h, F, Bf16Geo(r.n_chunks, lanes).np, Bf16Geo(c.n_chunks, lanes).np);
+  GO_TRY(attn_ws_check(fn, "attention_workspace_bytes", true, w.total, ws, ws_bytes));
+  {
+    ProfScope prof("attn_bf16_pack", st, "k_attn_bf16_pack");
+    const i64 rpb = kFastBlock / lanes;
+    GO_DISPATCH_ATTN_BF16_HD(h, d, {
+      hipLaunchKernelGGL((k_attn_bf16_pack<H, D, false>), dim3((unsigned)ceil_div(n_k, rpb)), dim3(kFastBlock), 0, st,
+                         (const uint4*)K, (const uint4*)V, w.kv, n_k, (const uint4*)nullptr, (const float*)nullptr,
+                         (float4*)nullptr);
+      hipLaunchKernelGGL((k_attn_bf16_pack<H, D, true>), dim3((unsigned)ceil_div(n_q, rpb)), dim3(kFastBlock), 0, st,
+                         (const uint4*)Q, (const uint4*)dO, w.qdo, n_q, (const uint4*)o, (const float*)stats, w.st4);
+    });
+    GO_LAUNCH_CHECK();
+  }
+  GO_TRY((bf16_bwd_pass<false>("attn_bf16_rows_row", r, h, d, w.qdo, w.kv, w.st4, (uint4*)dQ, nullptr, w, st)));
+  GO_TRY((bf16_bwd_pass<true>("attn_bf16_rows_col", c, h, d, w.kv, w.qdo, w.st4, (uint4*)dK, (uint4*)dV, w, st)));
+  return GRAPHOP_OK;
+}
+
+}  // namespace graphop

@@ -257,6 +257,19 @@ int attn_heads_backward(const Csr& r, const Csr& c, i64 n_q, i64 n_k, i64 h, i64
                         const void* V, const void* b, const void* o, const void* stats, const void* dO, void* dQ, void* dK,
                         void* dV, void* db, void* ws, hipStream_t st, const HostDrop* drop, i64 head0);
 
+// The plain step on bfloat16 tables (attention_bf16.hip; kernels_attn_bf16.h): one form, no knob and no
+// composed path.  attn_bf16_ok: every condition holds (the answer of graphop_attention_backward_is_fused);
+// attn_bf16_workspace: the bytes of one direction, 0 where it would refuse; forward / backward return
+// GRAPHOP_ERR_INVALID_ARGUMENT naming the unmet condition, and touch nothing for an empty problem.
+bool attn_bf16_ok(i64 h, i64 d, i64 n_edges, i64 n_q, i64 n_k, const graphop_plan* plan_r, const graphop_plan* plan_c);
+size_t attn_bf16_workspace(bool backward, i64 h, i64 d, i64 n_edges, i64 n_q, i64 n_k, const graphop_plan* plan_r,
+                           const graphop_plan* plan_c);
+int attn_bf16_forward(const char* fn, const Csr& g, i64 n_q, i64 n_k, i64 h, i64 d, const void* Q, const void* K,
+                      const void* V, void* o, void* stats, void* ws, i64 ws_bytes, hipStream_t st);
+int attn_bf16_backward(const char* fn, const Csr& r, const Csr& c, i64 n_q, i64 n_k, i64 h, i64 d, const void* Q,
+                       const void* K, const void* V, const void* o, const void* stats, const void* dO, void* dQ, void* dK,
+                       void* dV, void* ws, i64 ws_bytes, hipStream_t st);
+
 inline size_t esize(int dtype) { return dtype == GRAPHOP_F64 ? 8 : 4; }
 inline bool pow2(i64 v) { return v > 0 && (v & (v - 1)) == 0; }
 inline i64 pow2ceil(i64 v) { i64 p = 1; while (p < v) p <<= 1; return p; }

@@ -50,6 +50,15 @@ int dtype_code(const at::Tensor& t) {
   TORCH_CHECK(false, "graphop: not implemented for '", t.scalar_type(), "' (float32 / float64 only)");   // AT_DISPATCH_FLOATING_TYPES, graphop_kernel.cu:291
 }
 
+// the plain fused attention step (`plain`: graphop_attention_forward / _backward and their queries) also takes bfloat16
+// tables, with fp32 row statistics; every other form keeps dtype_code's answer
+int attn_dtype_code(bool plain, const at::Tensor& t) {
+  return plain && t.scalar_type() == at::kBFloat16 ? GRAPHOP_BF16 : dtype_code(t);
+}
+at::ScalarType attn_stats_type(const at::Tensor& t) {
+  return t.scalar_type() == at::kBFloat16 ? at::kFloat : t.scalar_type();
+}
+
 void* stream_of(const at::Tensor& t) { return (void*)c10::hip::getCurrentHIPStream(t.get_device()).stream(); }
 
 const int64_t* ip(const at::Tensor& t) { return t.numel() ? t.data_ptr<int64_t>() : nullptr; }
@@ -398,7 +407,8 @@ std::vector<at::Tensor> attention_forward_impl(const char* fn, const at::Tensor&
   DeviceGuard dg(Q);
   const int64_t e = eid.size(0), d = Q.size(-1), h = Q.dim() == 2 ? 1 : Q.size(1), n_q = Q.size(0), n_k = K.size(0);
   auto o = at::empty_like(Q);
-  auto stats = at::empty({n_q, h, 2}, Q.options());
+  auto stats = at::empty({n_q, h, 2}, Q.options().dtype(attn_stats_type(Q)));
+  const bool plain = !drop && !b;
   const auto pp = get_plan(row, indptr, eid, indices, n_k);
   const auto& p = *pp;
   int64_t nbytes = 0;
@@ -407,7 +417,7 @@ std::vector<at::Tensor> attention_forward_impl(const char* fn, const at::Tensor&
     check(graphop_attention_bias_workspace_bytes(dtype_code(Q), 0, e, n_q, n_k, h, d, p.plan, nullptr, stream_of(Q), 0, &nbytes));
   } else {
     check((drop ? graphop_attention_dropout_workspace_bytes : graphop_attention_workspace_bytes)(
-        dtype_code(Q), 0, e, n_q, n_k, h, d, p.plan, nullptr, stream_of(Q), &nbytes));
+        attn_dtype_code(plain, Q), 0, e, n_q, n_k, h, d, p.plan, nullptr, stream_of(Q), &nbytes));
   }
   auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, Q.options().dtype(at::kByte));
   if (b)
@@ -419,7 +429,7 @@ std::vector<at::Tensor> attention_forward_impl(const char* fn, const at::Tensor&
                                             vp(o), vp(stats), row.size(0), e, n_q, n_k, h, d, ws.data_ptr(), nbytes,
                                             p.plan, stream_of(Q), drop->p, drop->seed, drop->offset, head0));
   else
-    check(graphop_attention_forward(dtype_code(Q), ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(V), vp(o),
+    check(graphop_attention_forward(attn_dtype_code(plain, Q), ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(V), vp(o),
                                     vp(stats), row.size(0), e, n_q, n_k, h, d, ws.data_ptr(), nbytes, p.plan, stream_of(Q)));
   return {o, stats};
 }
@@ -471,7 +481,14 @@ std::vector<at::Tensor> attention_backward_impl(const char* fn, const at::Tensor
   CHECK_INPUT(o); CHECK_INPUT(stats);
   CHECK_CUDA(dO_);
   const at::Tensor dO = dO_.contiguous();
-  CHECK_SAME_DTYPE(Q, K); CHECK_SAME_DTYPE(Q, V); CHECK_SAME_DTYPE(Q, o); CHECK_SAME_DTYPE(Q, stats); CHECK_SAME_DTYPE(Q, dO);
+  CHECK_SAME_DTYPE(Q, K); CHECK_SAME_DTYPE(Q, V); CHECK_SAME_DTYPE(Q, o);
+  if (Q.scalar_type() == at::kBFloat16) {   // fp32 statistics with bfloat16 tables
+    TORCH_CHECK(stats.scalar_type() == at::kFloat, "expected stats to be torch.float32 for bfloat16 Q, got ", stats.scalar_type());
+  } else {
+    CHECK_SAME_DTYPE(Q, stats);
+  }
+  CHECK_SAME_DTYPE(Q, dO);
+  const bool plain = !drop && !b;
   TORCH_CHECK(K.sizes() == V.sizes() && Q.sizes().slice(1) == K.sizes().slice(1),
               fn, ": Q (n_q,[h,]d), K and V (n_k,[h,]d) expected");
   DeviceGuard dg(Q);
@@ -489,7 +506,7 @@ std::vector<at::Tensor> attention_backward_impl(const char* fn, const at::Tensor
                                                  need_db ? 1 : 0, &nbytes));
   } else {
     check((drop ? graphop_attention_dropout_workspace_bytes : graphop_attention_workspace_bytes)(
-        dtype_code(Q), 1, e, n_q, n_k, h, d, pr.plan, pc.plan, stream_of(Q), &nbytes));
+        attn_dtype_code(plain, Q), 1, e, n_q, n_k, h, d, pr.plan, pc.plan, stream_of(Q), &nbytes));
   }
   auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, Q.options().dtype(at::kByte));
   if (b) {
@@ -508,7 +525,7 @@ std::vector<at::Tensor> attention_backward_impl(const char* fn, const at::Tensor
         vp(Q), vp(K), vp(V), vp(o), vp(stats), vp(dO), vp(dQ), vp(dK), vp(dV), row.size(0), col.size(0), e, n_q, n_k, h, d,
         ws.data_ptr(), nbytes, pr.plan, pc.plan, stream_of(Q), drop->p, drop->seed, drop->offset, head0));
   else
-    check(graphop_attention_backward(dtype_code(Q), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c),
+    check(graphop_attention_backward(attn_dtype_code(plain, Q), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c),
                                      ip(eid_c), ip(indices_c), vp(Q), vp(K), vp(V), vp(o), vp(stats), vp(dO), vp(dQ),
                                      vp(dK), vp(dV), row.size(0), col.size(0), e, n_q, n_k, h, d, ws.data_ptr(), nbytes,
                                      pr.plan, pc.plan, stream_of(Q)));

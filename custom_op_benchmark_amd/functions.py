@@ -315,8 +315,15 @@ class FusedAttention(Function):
     def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V):
         a8 = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
         h = Q.size(1) if Q.dim() == 3 else 1
-        hg = _heads_per_call(a8, Q, K, h)
         ctx.groups = None
+        if Q.dtype == torch.bfloat16:
+            # bfloat16: ONE fused call over all heads, bf16 gradients; the library refuses what its
+            # bf16 kernels do not cover (its message is the RuntimeError) -- nothing is upcast behind the caller's back
+            ctx.fused = True
+            o, stats = _ops.attention_forward(row, indptr_r, eid_r, indices_r, Q, K, V)
+            ctx.save_for_backward(*a8, Q, K, V, o, stats)
+            return o
+        hg = _heads_per_call(a8, Q, K, h)
         if h > 1 and hg < h:
             return _groups_forward(ctx, a8, Q, K, V, h, hg)
         # (fewer key rows than query rows: the unfused SpMM returns zeros_like(V) and cannot hold o; the raw op can, and

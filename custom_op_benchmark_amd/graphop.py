@@ -22,7 +22,7 @@ Deliberate, documented deviations from the reference:
 import torch
 
 from . import _lib
-from ._lib import check, dtype_code, get_plan, lib, ptr, stream_of
+from ._lib import attn_dtype_code, attn_stats_dtype, check, dtype_code, get_plan, lib, ptr, stream_of
 
 __all__ = ["maskedmm_csr_forward", "maskedmm_csr_backward", "node_mul_edge_forward",
            "node_mul_edge_backward", "sparse_softmax_forward", "sparse_softmax_backward",
@@ -285,7 +285,7 @@ def attention_backward_is_fused(row, indptr_r, eid_r, indices_r, col, indptr_c, 
     with _lib.device_guard(Q.device):
         plan_r = get_plan(row, indptr_r, eid_r, indices_r, K.size(0))
         plan_c = get_plan(col, indptr_c, eid_c, indices_c, Q.size(0))
-        check(lib().graphop_attention_backward_is_fused(dtype_code(Q), eid_r.size(0), Q.size(0), K.size(0), h, d,
+        check(lib().graphop_attention_backward_is_fused(attn_dtype_code("attention_backward", Q), eid_r.size(0), Q.size(0), K.size(0), h, d,
                                                         plan_r.handle, plan_c.handle, stream_of(Q), ctypes.byref(out)))
     return bool(out.value)
 
@@ -315,13 +315,14 @@ def _attention_forward(fn, row, indptr, eid, indices, Q, K, V, drop=(), b=None):
         _attn_bias(fn, b, Q, e, h)
         bias = (ptr(b),)
     o = torch.empty_like(Q)
-    stats = torch.empty((n_q, h, 2), dtype=Q.dtype, device=Q.device)
+    code = attn_dtype_code(fn, Q)
+    stats = torch.empty((n_q, h, 2), dtype=attn_stats_dtype(Q), device=Q.device)
     with _lib.device_guard(Q.device):
         plan = get_plan(row, indptr, eid, indices, n_k)
-        ws, nbytes = _workspace(Q, dtype_code(Q), False, e, n_q, n_k, h, d, plan, None, bool(drop),
+        ws, nbytes = _workspace(Q, code, False, e, n_q, n_k, h, d, plan, None, bool(drop),
                                 False if b is not None else None)
         check(getattr(lib(), "graphop_" + fn)(
-            dtype_code(Q), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(Q), ptr(K), ptr(V), *bias,
+            code, ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(Q), ptr(K), ptr(V), *bias,
             ptr(o), ptr(stats), row.size(0), e, n_q, n_k, h, d, ptr(ws), nbytes, plan.handle,
             stream_of(Q), *drop))
     return [o, stats]
@@ -342,7 +343,12 @@ def _attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_
                (Q, "Q"), (K, "K"), (V, "V"), *(((b, "b"),) if b is not None else ()), (o, "o"), (stats, "stats"))
     _check_grad(dO, "dO")
     for t, n in ((K, "K"), (V, "V"), (o, "o"), (stats, "stats"), (dO, "dO")):
-        _same_dtype(Q, t, "Q", n)
+        if n == "stats" and attn_stats_dtype(Q) != Q.dtype:          # fp32 statistics with bfloat16 tables
+            if t.dtype != attn_stats_dtype(Q):
+                raise RuntimeError("expected stats to be %s for Q of %s, got %s" % (attn_stats_dtype(Q), Q.dtype, t.dtype))
+        else:
+            _same_dtype(Q, t, "Q", n)
+    code = attn_dtype_code(fn, Q)
     dO = dO.contiguous()
     e, d = eid_r.size(0), Q.size(-1)
     h = 1 if Q.dim() == 2 else Q.size(1)
@@ -361,10 +367,10 @@ def _attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_
             db = (torch.empty_like(b) if plan_r.info.full_coverage else torch.zeros_like(b)) if need_db \
                 else torch.empty((0,), dtype=b.dtype, device=b.device)
             bias, dbias = (ptr(b),), (ptr(db) if need_db else _NULL,)
-        ws, nbytes = _workspace(Q, dtype_code(Q), True, e, n_q, n_k, h, d, plan_r, plan_c, bool(drop),
+        ws, nbytes = _workspace(Q, code, True, e, n_q, n_k, h, d, plan_r, plan_c, bool(drop),
                                 bool(need_db) if b is not None else None)
         check(getattr(lib(), "graphop_" + fn)(
-            dtype_code(Q), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col),
+            code, ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col),
             ptr(indptr_c), ptr(eid_c), ptr(indices_c), ptr(Q), ptr(K), ptr(V), *bias, ptr(o), ptr(stats),
             ptr(dO), ptr(dQ), ptr(dK), ptr(dV), *dbias, row.size(0), col.size(0), e, n_q, n_k, h, d,
             ptr(ws), nbytes, plan_r.handle, plan_c.handle, stream_of(Q), *drop))

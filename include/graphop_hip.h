@@ -53,6 +53,7 @@ extern "C" {
 
 #define GRAPHOP_F32 0
 #define GRAPHOP_F64 1
+#define GRAPHOP_BF16 2 /* bfloat16 tables, fp32 sums: the plain graphop_attention_* entry points only */
 
 #define GRAPHOP_OK 0
 #define GRAPHOP_ERR_INVALID_ARGUMENT 1 /* bad size / dtype / null pointer / plan mismatch   */
@@ -672,7 +673,16 @@ GRAPHOP_API int graphop_gatv2_edge_attention_backward(int dtype, const int64_t* 
  * walk's bins share, a few MB, for the one-pass form; s and a for the composed form;
  * backward: packed operand tables when the fused passes apply -- fp32, h == 1, both plans given;
  * window-owner drivers for sweepable plans and tables beyond the L2, chunk drivers otherwise --
- * else s, a, da, ds of the composed path). */
+ * else s, a, da, ds of the composed path).
+ * dtype GRAPHOP_BF16 (these four entry points alone; every other one answers it "bad dtype"; csrc/kernels_attn_bf16.h):
+ * Q, K, V, o, dO, dQ, dK, dV are bfloat16 [n][h][d], 16-byte aligned; stats (n_q, h, 2) stays fp32; sums are fp32, results
+ * are rounded once to nearest even, and no float atomic is used: results are bit-identical from run to run.  There is
+ * no composed path behind it.  Supported: (h, d) one of 1 x 64, 1 x 128, 8 x 64, 2 x 32, 2 x 64, 4 x 16, 4 x 32, 4 x 64,
+ * 8 x 8, 8 x 16, 8 x 32; the plan(s) given, made with indices, row_owned, with id ranges inside the tables, ids below 2^31
+ * and row ids below 2^30.  Otherwise graphop_attention_backward_is_fused answers 0, the workspace query 0 bytes, and
+ * forward / backward return GRAPHOP_ERR_INVALID_ARGUMENT with a message naming the unmet condition.  Workspace: forward,
+ * two fp32 piece records (row word, (m, l) per head, o row) per lane group; backward, the packed (K | V) and (Q | dO)
+ * tables in bf16, (m, 1 / l, D, -) per (query row, head), and the accumulator records of the pass that is running. */
 GRAPHOP_API int graphop_attention_workspace_bytes(int dtype, int backward, int64_t n_edges, int64_t n_q,
                                       int64_t n_k, int64_t h, int64_t d,
                                       const graphop_plan_t* plan_r, const graphop_plan_t* plan_c,
