@@ -1,8 +1,10 @@
 """GPU tier of the fused attention step on bfloat16 tables (kernels_attn_bf16.h) against the plain float64
 reference of attention_bf16_reference.py.
 
-Tolerances: a bf16 output is the round-to-nearest of an fp32 value, within 2**-9 relative of it; the bound takes twice
-that, plus TOL of test_fused_attention.py for the fp32 arithmetic underneath.  stats are fp32 and get TOL alone."""
+Tolerances: a bf16 output is the round-to-nearest of an fp32 value.  bfloat16 has an 8-bit significand, so half an ulp is
+up to 2**-8 relative: BF_TOL is that ONE rounding plus TOL of test_fused_attention.py for the fp32 arithmetic underneath.
+It is tight -- torch's own fp32 evaluation of the reference, rounded once, uses 0.96 to 0.98 of it
+(test_attention_bf16_fuzz_host.py).  stats are fp32 and get TOL alone."""
 import functools
 import gc
 
@@ -10,7 +12,7 @@ import pytest
 import torch
 
 import attention_bf16_reference as R
-from custom_op_benchmark_amd import functions, graphop as ops
+from custom_op_benchmark_amd import functions, graphop as ops, graphs
 from test_fused_attention import TOL, prof_tags, shuffled_chunk_arrays
 from util import random_graph
 
@@ -85,6 +87,72 @@ def test_several_chunks_per_lane_group(dev):
     _check(g, inp, got, "cpg=%d" % cpg)
     for x, y in zip(got, _step(a8, inp, dev)):
         assert torch.equal(x, y)
+
+
+# ---- edges of the batch loop and of the record / merge scheme, one pair per SB -------------------------------------------
+SB_PAIRS = [(4, 16, 8), (4, 32, 8), (4, 64, 4), (8, 64, 2)]          # (h, d, AttnBf16Cfg<h, d>::SB)
+
+
+def _rows_graph(rows, n_q, n_k, chunk_size):
+    """the graph whose row i holds the neighbour list rows[i] (repeats kept)"""
+    src = torch.tensor([i for i, js in rows.items() for _ in js], dtype=torch.int64)
+    dst = torch.tensor([j for js in rows.values() for j in js], dtype=torch.int64)
+    return graphs.graph_from_coo(src, dst, n_q, n_k, chunk_size)
+
+
+def _spread_inputs(g, h, d, seed):
+    """Q ~ 8 randn / sqrt(d), K, V ~ randn, dO ~ randn / (4 sqrt(d)): scores of spread 8, so the running maximum moves and
+    a wrong rescale or combine is a gross error (the wide8 recipe of attention_bf16_fuzz.py)"""
+    gen = torch.Generator().manual_seed(seed)
+    Q, K, V, dO = (torch.randn(n, h, d, generator=gen) for n in (g.n_src, g.n_dst, g.n_dst, g.n_src))
+    return (Q * 8 / d ** 0.5).to(BF), K.to(BF), V.to(BF), (dO / (4 * d ** 0.5)).to(BF)
+
+
+def _tails(sb):
+    """rows of 1, SB - 1, SB, SB + 1 and 2 SB + 1 slots over 40 neighbours, each ending at neighbour 39: slots are stored
+    by ascending neighbour id, so every row's last batch -- short in all but the row of SB slots -- re-reads the table's
+    last row for the slots it does not have"""
+    gen = torch.Generator().manual_seed(sb)
+    return {i: torch.randperm(39, generator=gen)[:n - 1].tolist() + [39]
+            for i, n in enumerate((1, max(sb - 1, 1), sb, sb + 1, 2 * sb + 1))}, 5, 40
+
+
+def _edge_graphs(name, sb):
+    """[(graph, what)] of one edge shape"""
+    gen = torch.Generator().manual_seed(len(name))
+    rnd = lambda n, n_k: torch.randint(0, n_k, (n,), generator=gen).tolist()
+    if name == "tails":
+        rows, n_q, n_k = _tails(sb)
+        return [(_rows_graph(rows, n_q, n_k, cs), "chunk_size %d" % cs) for cs in (1, sb, sb + 1)]
+    if name == "one_row":          # 600 chunks of one slot, one lane group each: every interior record has neither flag
+        return [(_rows_graph({1: rnd(600, 50)}, 3, 50, 1), "")]
+    if name == "two_rows":
+        return [(_rows_graph({0: rnd(7, 9), 1: rnd(13, 9)}, 2, 9, cs), "chunk_size %d" % cs) for cs in (1, 8)]
+    if name == "single_edge":
+        return [(_rows_graph({1: [2]}, 3, 4, 8), "")]
+    if name == "repeated":
+        return [(_rows_graph({0: [3] * 5 + [1, 6], 2: [6] * (2 * sb + 1), 3: [0, 0, 7, 7]}, 4, 8, cs), "chunk_size %d" % cs)
+                for cs in (1, 3)]
+    assert name == "empty_ends"          # rows 0 and n - 1 empty, rows 1 and n - 2 hubs; columns 0 and n_k - 1 empty too
+    rows = {1: [1 + j for j in rnd(200, 30)], 10: [1 + j for j in rnd(230, 30)]}
+    rows.update({i: [1 + j for j in rnd(1 + i % 4, 30)] for i in (3, 4, 6, 7, 9)})
+    return [(_rows_graph(rows, 12, 32, cs), "chunk_size %d" % cs) for cs in (1, 3)]
+
+
+@pytest.mark.parametrize("name", ["tails", "one_row", "two_rows", "single_edge", "repeated", "empty_ends"])
+@pytest.mark.parametrize("h,d,sb", SB_PAIRS)
+def test_edges_of_batches_and_records(dev, h, d, sb, name):
+    """against the reference, and bitwise the same twice"""
+    for g, what in _edge_graphs(name, sb):
+        if name == "empty_ends":
+            deg, cdeg = torch.bincount(g.src, minlength=g.n_src), torch.bincount(g.dst, minlength=g.n_dst)
+            assert deg[0] == deg[-1] == cdeg[0] == cdeg[-1] == 0 and deg[1] == 200 and deg[-2] == 230
+        inp = _spread_inputs(g, h, d, seed=h + d)
+        a8 = tuple(x.to(dev) for x in g.csr_args())
+        got = _step(a8, inp, dev)
+        _check(g, inp, got, "%s h=%d d=%d %s" % (name, h, d, what))
+        for x, y in zip(got, _step(a8, inp, dev)):
+            assert torch.equal(x, y), (name, what)
 
 
 def test_the_surface(dev):

@@ -15,6 +15,7 @@ import functools
 import pytest
 import torch
 
+import attention_bf16_fuzz as BF
 import attention_edge_reference as AE
 import attention_fuzz as AF
 import attention_tbias_reference as T
@@ -26,6 +27,7 @@ import gat_weights_reference as W
 import gatv2_edge_reference as G2
 import guarded as G
 import oracle
+import test_attention_bf16_fuzz as TBF
 import test_attention_fuzz as TAF
 import test_gat_edge_fuzz as TGE
 import test_gat_fuzz as TGF
@@ -133,6 +135,28 @@ def test_attention_family_under_guard(dev, seed):
         seen, forms = AF.seen_forms(profile), AF.expected_forms(case, built)
         assert len([f for f in forms if f.tags == seen]) == 1, "%s\nlaunched %s" % (what, seen)
         TAF._check(case, got, want, built, what)
+    finally:
+        _reset()
+
+
+@pytest.mark.parametrize("seed", range(BF.N_SUITE))
+def test_attention_bf16_under_guard(dev, seed):
+    """The bfloat16 battery's cases: 2-byte outputs, and the two hand-laid workspaces (Bf16FwdWs, Bf16BwdWs) whose record
+    slots are read only where a row word says so.  The five assertions of the family, and one the op's fixed summation
+    order allows: the guarded run, whose outputs start as NaN and whose workspaces as poison, returns bit for bit what
+    the unguarded run returned -- nothing depends on what an unwritten record slot or accumulator happened to hold."""
+    n_cu = torch.cuda.get_device_properties(dev).multi_processor_count
+    case, built, fwd = BF.case_data(seed, n_cu)
+    case = G.ctypes_entry(case)
+    what = "attention_bf16 seed %d %s" % (seed, case)
+    on_dev = BF.on_device(built, dev, G.banded)
+    try:
+        plain = BF.run(case, on_dev, dev)
+        got, profile = _under_guard(lambda: BF.run(case, on_dev, dev), [on_dev.csr, on_dev.t], what)
+        assert TBF.attn_tags(profile) == dict(BF.KERNELS, **BF.SETUP), "%s\nlaunched %s" % (what, profile)
+        for name in got:
+            assert torch.equal(got[name], plain[name]), "%s: %s under the guard differs from the unguarded run" % (what, name)
+        TBF.check(case, got, fwd, built, what)
     finally:
         _reset()
 

@@ -126,7 +126,11 @@ def test_every_allocation_of_the_binding_is_one_the_stand_in_replaces():
 # ---- the GPU tier's cases --------------------------------------------------------------------------------------------------------
 def test_the_guarded_cases_cover_odd_sized_edge_outputs_and_fp64():
     """For every edge-sized fp32 output name at least one guarded case returns it with a byte size that is no multiple of
-    16 (a 16-byte tail store would then cross its end), and every family that has fp64 kernels has an fp64 case."""
+    16 (a 16-byte tail store would then cross its end), and every family that has fp64 kernels has an fp64 case.  With the
+    bfloat16 battery (test_attention_bf16_under_guard) 2-byte outputs are among the guarded allocations: its 48 cases
+    return o, dQ, dK, dV of every pair of the bf16 set, whose rows are whole 16-byte pieces, so none of them ends off a
+    multiple of 16 -- a store past one lands in the band."""
+    import attention_bf16_fuzz as BF
     import attention_fuzz as AF
     import gat_fuzz as GF
     sizes, fp64 = G.edge_outputs()
@@ -139,3 +143,8 @@ def test_the_guarded_cases_cover_odd_sized_edge_outputs_and_fp64():
     assert (G.outside_graph().n_edges * 15 * 4) % 16 and "attention_edge 3 x 5" in odd["dxe"]
     families = {f for f, _ in fp64}
     assert families >= set(GF.FAMILIES) | set(AF.FAMILIES) | {"fused_gat_edge", "core"}, families
+    bf16 = [G.ctypes_entry(BF.draw(seed)) for seed in range(BF.N_SUITE)]
+    assert len(bf16) == 48 and {(c.h, c.d) for c in bf16} == set(BF.HD) and torch.bfloat16.itemsize == 2
+    assert all(c.entry == "ctypes" and (c.h * c.d * 2) % 16 == 0 for c in bf16)
+    assert {c.recipe for c in bf16} == set(BF.RECIPES) and sum(c.large for c in bf16) == 12
+    assert GF.N_SUITE + 24 + AF.N_SUITE + BF.N_SUITE == 168          # the battery seeds under guard
