@@ -18,7 +18,8 @@ LIB_PATH = os.environ.get("GRAPHOP_LIB") or os.path.join(_HERE, "libgraphop_hip.
 ABI_VERSION = 8
 
 F32, F64 = 0, 1
-BF16 = 2   # the plain attention_forward / attention_backward alone (attn_dtype_code)
+BF16 = 2   # the plain attention_forward / attention_backward alone (attn_dtype_code); the fused GAT layer's bf16 entry
+           # points take no dtype code (gat_attn_is_bf16)
 _c64 = ctypes.c_int64
 _vp = ctypes.c_void_p
 _lib = None
@@ -100,6 +101,11 @@ _SIGNATURES = {
     "graphop_gat_attention_dropout_forward": [ctypes.c_int] + [_P] * 9 + [_c64] * 6
     + [ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _P, _P],
     "graphop_gat_attention_dropout_backward": [ctypes.c_int] + [_P] * 18 + [_c64] * 8
+    + [ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _P, _P, _P],
+    "graphop_gat_attention_bf16_workspace_bytes": [ctypes.c_int] + [_c64] * 7 + [_P, _P, ctypes.POINTER(_c64)],
+    "graphop_gat_attention_bf16_forward": [_P] * 10 + [_c64] * 7
+    + [ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _P, _P],
+    "graphop_gat_attention_bf16_backward": [_P] * 18 + [_c64] * 8
     + [ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _P, _P, _P],
     "graphop_edge_dropout_mask": [ctypes.c_int] + [_P] * 5 + [_c64] * 5
     + [ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _P, _P],
@@ -311,6 +317,14 @@ def attn_dtype_code(fn, t):
     if t.dtype == torch.bfloat16 and fn in ("attention_forward", "attention_backward"):
         return BF16
     return dtype_code(t)
+
+
+def gat_attn_is_bf16(fn, t):
+    """True where the fused GAT layer's call `fn` on tables like t goes to the graphop_gat_attention_bf16_* entry points
+    (DESIGN.md 4.5u): torch.bfloat16 tables of gat_attention[_dropout]_forward / _backward.  Every other GAT op keeps
+    dtype_code's answer, a refusal."""
+    return t.dtype == torch.bfloat16 and fn in ("gat_attention_forward", "gat_attention_backward",
+                                                "gat_attention_dropout_forward", "gat_attention_dropout_backward")
 
 
 def attn_stats_dtype(t):

@@ -4,9 +4,8 @@
 // path behind it, so an unmet condition is an error that names it, and no knob steers anything.
 #include "common.h"
 #include "host.h"
-#include "host_attn_rows.h"
+#include "host_bf16.h"
 #include "host_gat.h"
-#include "kernels_attn_bf16.h"
 
 namespace graphop {
 namespace {
@@ -26,49 +25,12 @@ int bf16_lanes(i64 h, i64 d) {
   return lanes;
 }
 
-// what one direction asks of ONE plan (own rows n_own, gathered table n_tab); `why` gets the unmet condition
-bool bf16_plan_unmet(char* why, size_t cap, const char* name, const graphop_plan* plan, i64 n_edges, i64 n_own, i64 n_tab) {
-  if (!plan) snprintf(why, cap, "%s is NULL or not the plan of the call's arrays", name);
-  else if (!plan->indices) snprintf(why, cap, "%s was made without indices", name);
-  else if (!plan->info.row_owned) snprintf(why, cap, "%s is not row_owned (rows sorted, indptr monotone)", name);
-  else if (plan->info.max_row >= n_own || plan->info.max_index >= n_tab)
-    snprintf(why, cap, "%s holds row id %lld and neighbour id %lld but the tables have %lld and %lld rows", name,
-             (long long)plan->info.max_row, (long long)plan->info.max_index, (long long)n_own, (long long)n_tab);
-  else if (n_edges >= 0x7fffffffLL || n_tab >= 0x7fffffffLL || n_own > (i64)kBf16RecRow)
-    snprintf(why, cap, "%s: ids must lie below 2^31 and row ids below 2^30", name);
-  else if (2 * attn_rows_geometry(plan->info.n_chunks).groups >= 0x7fffffffLL)
-    snprintf(why, cap, "%s has too many chunks for 32-bit record slots", name);
-  else return false;
-  return true;
-}
-
 bool bf16_shape_unmet(char* why, size_t cap, i64 h, i64 d) {
   if (bf16_lanes(h, d)) return false;
   snprintf(why, cap, "(h, d) = (%lld, %lld) is not in the bfloat16 set: 1 x 64, 1 x 128, 8 x 64 and the several-head pairs",
            (long long)h, (long long)d);
   return true;
 }
-
-// the chunk geometry of a pass: attn_rows_geometry's chunks per group and groups, workgroups for this pair's lane groups
-struct Bf16Geo {
-  i64 cpg, groups, np;
-  int lanes;
-  Bf16Geo(i64 n_chunks, int lanes_) : lanes(lanes_) {
-    const ChunkGeometry geo = attn_rows_geometry(n_chunks);
-    cpg = geo.cpg; groups = geo.groups; np = 2 * geo.groups;
-  }
-  dim3 grid(i64 n_groups) const { return dim3((unsigned)ceil_div(n_groups, (i64)(kFastBlock / lanes))); }
-};
-
-struct Bf16Take {
-  char* base;
-  size_t total = 0;
-  void* operator()(size_t bytes) {
-    void* p = base ? base + total : nullptr;
-    total += up256(bytes);
-    return p;
-  }
-};
 
 // forward: 2 * groups records of (row word | (m, l) per head | o row), all fp32
 struct Bf16FwdWs {
@@ -103,24 +65,13 @@ struct Bf16BwdWs {
   }
 };
 
-void bf16_fill_rows(unsigned* p_row, i64 np, hipStream_t st) {
-  ProfScope prof("attn_bf16_setup", st, "k_fill");
-  const i64 want = ceil_div(np, 256);
-  hipLaunchKernelGGL((k_fill<int>), dim3((unsigned)(want > 4096 ? 4096 : want)), dim3(256), 0, st, (int*)p_row, np, -1);
-}
-
-int bf16_tables_aligned(const char* fn, std::initializer_list<const void*> ps) {
-  for (const void* p : ps) GO_CHECK_ARG(aligned16(p), "%s: bfloat16 tables must be 16-byte aligned", fn);
-  return GRAPHOP_OK;
-}
-
 template <bool COL>
 int bf16_bwd_pass(const char* tag, const Csr& g, i64 h, i64 d, const uint4* own, const uint4* xt, const float4* st4,
                   uint4* out0, uint4* out1, const Bf16BwdWs& w, hipStream_t st) {
   if (g.n_chunks == 0) return GRAPHOP_OK;
   const Bf16Geo geo(g.n_chunks, bf16_lanes(h, d));
   const AttnBf16BwdRec rec{w.p_row, w.p_acc};
-  bf16_fill_rows(w.p_row, geo.np, st);
+  bf16_fill_rows("attn_bf16_setup", w.p_row, geo.np, st);
   {
     ProfScope prof(tag, st, "k_attn_bf16_bwd_rows");
     GO_DISPATCH_ATTN_BF16_HD(h, d, {
@@ -181,7 +132,7 @@ int attn_bf16_forward(const char* fn, const Csr& g, i64 n_q, i64 n_k, i64 h, i64
   const Bf16FwdWs w(ws, geo.np, h, F);
   GO_TRY(attn_ws_check(fn, "attention_workspace_bytes", true, w.total, ws, ws_bytes));
   const AttnBf16FwdArgs a{(const uint4*)Q, (const uint4*)K, (const uint4*)V, (uint4*)o, (float*)stats, w.p_row, w.p_ml, w.p_o};
-  bf16_fill_rows(w.p_row, geo.np, st);
+  bf16_fill_rows("attn_bf16_setup", w.p_row, geo.np, st);
   {
     ProfScope prof("attn_bf16_fwd_rows", st, "k_attn_bf16_fwd_rows");
     GO_DISPATCH_ATTN_BF16_HD(h, d, {

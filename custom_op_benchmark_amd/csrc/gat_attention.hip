@@ -14,6 +14,13 @@
 
 using namespace graphop;
 
+// the fp32 stats pass for gat_attention_bf16.hip (host.h): this translation unit's k_gat_attn_stats_f32, so the
+// statistics of the bf16 op are those of the fp32 op on the same values bit for bit
+int graphop::gat_attn_stats_f32(const Csr& g, const float* el, const float* er, void* stats, i64 n_chunks, i64 n_l, i64 h,
+                                double slope, const char* tag, hipStream_t st) {
+  return gat_attn_stats<false>(GRAPHOP_F32, g, el, er, nullptr, stats, n_chunks, n_l, h, slope, true, st, tag);
+}
+
 extern "C" {
 
 int graphop_gat_attention_forward(int dtype, const int64_t* row, const int64_t* indptr, const int64_t* eid,

@@ -270,6 +270,13 @@ int attn_bf16_backward(const char* fn, const Csr& r, const Csr& c, i64 n_q, i64 
                        const void* K, const void* V, const void* o, const void* stats, const void* dO, void* dQ, void* dK,
                        void* dV, void* ws, i64 ws_bytes, hipStream_t st);
 
+// The stats pass of the fused GAT layer on fp32 tables over a row_owned plan with a segment table (gat_attention.hip: the
+// stats fill and k_gat_attn_stats_f32), under the profile tag `tag`; n_chunks == 0: the fill alone.  For
+// gat_attention_bf16.hip, whose statistics are the fp32 op's on the widened el / er bit for bit.
+struct Csr;
+int gat_attn_stats_f32(const Csr& g, const float* el, const float* er, void* stats, i64 n_chunks, i64 n_l, i64 h,
+                       double slope, const char* tag, hipStream_t st);
+
 inline size_t esize(int dtype) { return dtype == GRAPHOP_F64 ? 8 : 4; }
 inline bool pow2(i64 v) { return v > 0 && (v & (v - 1)) == 0; }
 inline i64 pow2ceil(i64 v) { i64 p = 1; while (p < v) p <<= 1; return p; }

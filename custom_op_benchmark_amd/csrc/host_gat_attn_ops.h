@@ -20,10 +20,11 @@ namespace graphop {
 #define GO_GAT_ATTN_LABELS(EDGE, pass) \
   (EDGE ? GO_GAT_LABELS_OF("gat_edge_attn", pass) : GO_GAT_LABELS_OF("gat_attn", pass))
 
-// stats = (m, 1 / l) per (row, head); rows without slots keep (-1e9, 0)
+// stats = (m, 1 / l) per (row, head); rows without slots keep (-1e9, 0).  tag_as: the profile tag of a caller that runs
+// the pass under a name of its own (gat_attention_bf16.hip), NULL: the op's
 template <bool EDGE>
 int gat_attn_stats(int dtype, const Csr& g, const void* el, const void* er, const void* ee, void* stats, i64 C, i64 n_l,
-                   i64 h, double slope, bool fast, hipStream_t st) {
+                   i64 h, double slope, bool fast, hipStream_t st, const char* tag_as = nullptr) {
   const graphop_plan* pm = g.plan;   // (fast: not NULL)
   GO_DISPATCH_FLOAT(dtype, T, {
     hipLaunchKernelGGL((k_gat_attn_stats_init_generic<T>), dim3(grid_of(n_l * h)), dim3(256), 0, st, (T*)stats,
@@ -31,7 +32,7 @@ int gat_attn_stats(int dtype, const Csr& g, const void* el, const void* er, cons
   });
   GO_LAUNCH_CHECK();
   if (C == 0) return GRAPHOP_OK;
-  const char* tag = EDGE ? "gat_edge_attn_stats" : "gat_attn_stats";
+  const char* tag = tag_as ? tag_as : EDGE ? "gat_edge_attn_stats" : "gat_attn_stats";
   if (fast && pm->info.row_owned && pm->seg_chunk) {
     const i64 S = pm->info.n_segments;
     if (S == 0) return GRAPHOP_OK;

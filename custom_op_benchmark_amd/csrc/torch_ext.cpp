@@ -55,6 +55,11 @@ int dtype_code(const at::Tensor& t) {
 int attn_dtype_code(bool plain, const at::Tensor& t) {
   return plain && t.scalar_type() == at::kBFloat16 ? GRAPHOP_BF16 : dtype_code(t);
 }
+// the fused GAT layer without edge term (graphop_gat_attention[_dropout]_forward / _backward) takes bfloat16 tables through
+// the graphop_gat_attention_bf16_* entry points; every other GAT op keeps dtype_code's refusal
+bool gat_attn_is_bf16(const at::Tensor& t, const at::Tensor* ee) {
+  return !ee && t.scalar_type() == at::kBFloat16;
+}
 at::ScalarType attn_stats_type(const at::Tensor& t) {
   return t.scalar_type() == at::kBFloat16 ? at::kFloat : t.scalar_type();
 }
@@ -1102,9 +1107,19 @@ std::vector<at::Tensor> gat_attention_forward_impl(const char* fn, const at::Ten
   if (ee) gat_edge_term(el, *ee, e, h, fn);
   DeviceGuard dg(el);
   auto o = at::empty(with_rows(V, n_l), V.options());
-  auto stats = at::empty({n_l, h, 2}, el.options());
+  auto stats = at::empty({n_l, h, 2}, el.options().dtype(attn_stats_type(el)));
   const auto pp = get_plan(row, indptr, eid, indices, er.size(0));
   const auto& p = *pp;
+  if (gat_attn_is_bf16(el, ee)) {
+    int64_t nbytes = 0;
+    check(graphop_gat_attention_bf16_workspace_bytes(0, row.size(0), 0, e, n_l, er.size(0), h, d, p.plan, nullptr, &nbytes));
+    auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, el.options().dtype(at::kByte));
+    check(graphop_gat_attention_bf16_forward(ip(row), ip(indptr), ip(eid), ip(indices), vp(el), vp(er), vp(V), vp(o),
+                                             vp(stats), vp(ws), nbytes, row.size(0), e, n_l, er.size(0), h, d,
+                                             negative_slope, drop ? drop->p : 0.0, drop ? drop->seed : 0,
+                                             drop ? drop->offset : 0, p.plan, stream_of(el)));
+    return {o, stats};
+  }
   if (ee)
     check(graphop_gat_edge_attention_forward(dtype_code(el), ip(row), ip(indptr), ip(eid), ip(indices), vp(el), vp(er),
                                              vp(*ee), vp(V), vp(o), vp(stats), row.size(0), e, n_l, er.size(0), h, d,
@@ -1165,14 +1180,28 @@ std::vector<at::Tensor> gat_attention_backward_impl(const char* fn, const at::Te
   const int64_t h = hd.first, d = hd.second;
   const int64_t e = eid_r.size(0), n_l = el.size(0);
   if (ee) gat_edge_term(el, *ee, e, h, fn);
-  CHECK_SAME_DTYPE(el, o); CHECK_SAME_DTYPE(el, stats); CHECK_SAME_DTYPE(el, dO_);
+  CHECK_SAME_DTYPE(el, o); CHECK_SAME_DTYPE(el, dO_);
+  TORCH_CHECK(stats.scalar_type() == attn_stats_type(el), "expected stats to be ", attn_stats_type(el), " for el of ",
+              el.scalar_type(), ", got ", stats.scalar_type());
   const at::Tensor dO = saved_checked(fn, with_rows(V, n_l), n_l, h, o, stats, dO_);
   DeviceGuard dg(el);
   auto d_el = at::empty_like(el), d_er = at::empty_like(er), dV = at::empty_like(V);
-  auto ws = at::empty({std::max<int64_t>(n_l * h * 4, 1)}, el.options());   // (el, m, 1 / l, D) per (node, head)
   const auto ppr = get_plan(row, indptr_r, eid_r, indices_r, er.size(0));
   const auto ppc = get_plan(col, indptr_c, eid_c, indices_c, n_l);
   const auto &pr = *ppr, &pc = *ppc;
+  if (gat_attn_is_bf16(el, ee)) {
+    int64_t nbytes = 0;
+    check(graphop_gat_attention_bf16_workspace_bytes(1, row.size(0), col.size(0), e, n_l, er.size(0), h, d, pr.plan,
+                                                     pc.plan, &nbytes));
+    auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, el.options().dtype(at::kByte));
+    check(graphop_gat_attention_bf16_backward(
+        ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c), ip(indices_c), vp(el), vp(er),
+        vp(V), vp(o), vp(stats), vp(dO), vp(d_el), vp(d_er), vp(dV), vp(ws), nbytes, row.size(0), col.size(0), e, n_l,
+        er.size(0), h, d, negative_slope, drop ? drop->p : 0.0, drop ? drop->seed : 0, drop ? drop->offset : 0, pr.plan,
+        pc.plan, stream_of(el)));
+    return {d_el, d_er, dV};
+  }
+  auto ws = at::empty({std::max<int64_t>(n_l * h * 4, 1)}, el.options());   // (el, m, 1 / l, D) per (node, head)
   if (ee) {
     auto d_ee = need_dee ? at::empty_like(*ee) : at::empty({0}, ee->options());   // the only edge-sized tensor made
     check(graphop_gat_edge_attention_backward(

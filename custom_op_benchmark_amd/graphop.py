@@ -22,7 +22,7 @@ Deliberate, documented deviations from the reference:
 import torch
 
 from . import _lib
-from ._lib import attn_dtype_code, attn_stats_dtype, check, dtype_code, get_plan, lib, ptr, stream_of
+from ._lib import attn_dtype_code, attn_stats_dtype, check, dtype_code, gat_attn_is_bf16, get_plan, lib, ptr, stream_of
 
 __all__ = ["maskedmm_csr_forward", "maskedmm_csr_backward", "node_mul_edge_forward",
            "node_mul_edge_backward", "sparse_softmax_forward", "sparse_softmax_backward",
@@ -603,6 +603,16 @@ def _gat_attn_shapes(el, er, V, fn):
     return h, V.size(-1)
 
 
+def _gat_bf16_workspace(like, backward, n_row_chunks, n_col_chunks, e, n_l, n_r, h, d, plan_r, plan_c):
+    """(uint8 workspace tensor, bytes) of graphop_gat_attention_bf16_workspace_bytes; 0 bytes where the op will refuse"""
+    import ctypes
+    nbytes = ctypes.c_int64(0)
+    check(lib().graphop_gat_attention_bf16_workspace_bytes(
+        1 if backward else 0, n_row_chunks, n_col_chunks, e, n_l, n_r, h, d, plan_r.handle,
+        plan_c.handle if plan_c is not None else _NULL, ctypes.byref(nbytes)))
+    return torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=like.device), nbytes.value
+
+
 def _gat_attention_forward(fn, row, indptr, eid, indices, el, er, V, negative_slope, drop=(), ee=None):
     """gat_attention_forward (drop = ()), gat_attention_dropout_forward or, with the edge term ee,
     gat_edge_attention_forward (drop = (p, seed, offset)) as `fn`."""
@@ -613,9 +623,16 @@ def _gat_attention_forward(fn, row, indptr, eid, indices, el, er, V, negative_sl
     if edge:
         _gat_edge_term(el, ee, e, h, fn)         # checks ee as an input too
     o = torch.empty((n_l,) + tuple(V.shape[1:]), dtype=V.dtype, device=V.device)
-    stats = torch.empty((n_l, h, 2), dtype=el.dtype, device=el.device)
+    stats = torch.empty((n_l, h, 2), dtype=attn_stats_dtype(el), device=el.device)
     with _lib.device_guard(el.device):
         plan = get_plan(row, indptr, eid, indices, er.size(0))
+        if gat_attn_is_bf16(fn, el):          # bfloat16 tables: fp32 stats, the library refuses what it must
+            ws, nbytes = _gat_bf16_workspace(el, False, row.size(0), 0, e, n_l, er.size(0), h, d, plan, None)
+            check(lib().graphop_gat_attention_bf16_forward(
+                ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(el), ptr(er), ptr(V), ptr(o), ptr(stats), ptr(ws),
+                nbytes, row.size(0), e, n_l, er.size(0), h, d, float(negative_slope), *(drop or (0.0, 0, 0)),
+                plan.handle, stream_of(el)))
+            return [o, stats]
         check(getattr(lib(), "graphop_" + fn)(
             dtype_code(el), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(el), ptr(er), *(ptr(t) for t in edge),
             ptr(V), ptr(o), ptr(stats), row.size(0), e, n_l, er.size(0), h, d, float(negative_slope), *drop,
@@ -635,10 +652,23 @@ def _gat_attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, 
     e, n_l = eid_r.size(0), el.size(0)
     if edge:
         _gat_edge_term(el, ee, e, h, fn)         # checks ee as an input too
-    for t, n in ((o, "o"), (stats, "stats"), (dO, "dO")):
+    for t, n in ((o, "o"), (dO, "dO")):
         _same_dtype(el, t, "el", n)
+    if stats.dtype != attn_stats_dtype(el):          # fp32 statistics with bfloat16 tables
+        raise RuntimeError("expected stats to be %s for el of %s, got %s" % (attn_stats_dtype(el), el.dtype, stats.dtype))
     dO = _saved_checked(fn, (n_l,) + tuple(V.shape[1:]), n_l, h, o, stats, dO)
     d_el, d_er, dV = torch.empty_like(el), torch.empty_like(er), torch.empty_like(V)
+    if gat_attn_is_bf16(fn, el):
+        with _lib.device_guard(el.device):
+            plan_r = get_plan(row, indptr_r, eid_r, indices_r, er.size(0))
+            plan_c = get_plan(col, indptr_c, eid_c, indices_c, n_l)
+            ws, nbytes = _gat_bf16_workspace(el, True, row.size(0), col.size(0), e, n_l, er.size(0), h, d, plan_r, plan_c)
+            check(lib().graphop_gat_attention_bf16_backward(
+                ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c), ptr(eid_c), ptr(indices_c),
+                ptr(el), ptr(er), ptr(V), ptr(o), ptr(stats), ptr(dO), ptr(d_el), ptr(d_er), ptr(dV), ptr(ws), nbytes,
+                row.size(0), col.size(0), e, n_l, er.size(0), h, d, float(negative_slope), *(drop or (0.0, 0, 0)),
+                plan_r.handle, plan_c.handle, stream_of(el)))
+        return [d_el, d_er, dV]
     d_ee = ()       # with ee: [dee], an empty (0,) tensor and a NULL pointer where it is not wanted
     if edge:
         d_ee = (torch.empty_like(ee) if need_dee else torch.empty((0,), dtype=ee.dtype, device=ee.device),)

@@ -550,6 +550,43 @@ GRAPHOP_API int graphop_edge_dropout_mask(int dtype, const int64_t* row, const i
                                   int64_t n_r, int64_t h, double p, uint64_t seed, uint32_t offset,
                                   const graphop_plan_t* plan, void* stream);
 
+/* ---- the fused GAT layer on bfloat16 tables (ABI 8, additive; EXTRA ops; csrc/kernels_gat_attn_bf16.h) -------------
+ * The op of the two blocks above -- with p == 0 the plain layer, else with attention dropout -- on bfloat16 tables: el,
+ * er, V, o, dO, del, der, dV are bf16, stats (n_l, h, 2) = (m, 1 / l) stay fp32.  The score is z = float(el_i) +
+ * float(er_j), one fp32 add of exactly widened values; every sum is fp32, every bf16 result is rounded once to nearest
+ * even, and no float atomic touches an output: results are bit-identical from run to run.  stats are bit for bit what
+ * graphop_gat_attention_forward leaves on the widened el and er.  The backward takes D_i = <dO_i, o_i> from the bf16 o
+ * it is given.  Nothing edge-sized exists in either direction.  The entry points above keep answering GRAPHOP_BF16 with
+ * an error; these take no dtype.
+ * Supported: (h, d) with h in {1, 2, 4, 8}, d in {8, 16, 32, 64}, h * d in {64, 128, 256}; the plan(s) given, made with
+ * indices, row_owned, with id ranges inside the tables, ids below 2^31 and row ids below 2^30; V, o, dO, dV 16-byte
+ * aligned (stats 8-byte).  Otherwise the workspace query answers 0 bytes and forward / backward return
+ * GRAPHOP_ERR_INVALID_ARGUMENT with a message naming the unmet condition: there is no generic path and no upcast.
+ * workspace: graphop_gat_attention_bf16_workspace_bytes(...) bytes, each term rounded up to 256.  With np_x = 2 * the
+ * lane groups of orientation x's chunk list (the chunk geometry of the several-head attention passes) and F = h * d:
+ *   forward : 4 n_l h + 4 n_r h (el and er widened for the stats pass) + 4 np_r (row words) + 4 np_r F (o records)
+ *   backward: 16 n_l h (P = (el, m, 1 / l, D)) + 4 max(np_r, np_c) (row words) + 4 h max(np_r, np_c) (del / der records)
+ *             + 4 F np_c (dV records) -- one record area for whichever pass is running
+ * A call without slots (n_edges == 0 or no chunks) needs none: o, del, der, dV = 0 and stats = (-1e9, 0). */
+GRAPHOP_API int graphop_gat_attention_bf16_workspace_bytes(int backward, int64_t n_row_chunks, int64_t n_col_chunks,
+                                   int64_t n_edges, int64_t n_l, int64_t n_r, int64_t h, int64_t d,
+                                   const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, int64_t* bytes_out);
+GRAPHOP_API int graphop_gat_attention_bf16_forward(const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                                   const int64_t* indices, const void* el, const void* er, const void* V, void* o,
+                                   void* stats, void* workspace, int64_t workspace_bytes, int64_t n_chunks,
+                                   int64_t n_edges, int64_t n_l, int64_t n_r, int64_t h, int64_t d,
+                                   double negative_slope, double p, uint64_t seed, uint32_t offset,
+                                   const graphop_plan_t* plan, void* stream);
+GRAPHOP_API int graphop_gat_attention_bf16_backward(const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r,
+                                   const int64_t* indices_r, const int64_t* col, const int64_t* indptr_c,
+                                   const int64_t* eid_c, const int64_t* indices_c, const void* el, const void* er,
+                                   const void* V, const void* o, const void* stats, const void* dO, void* del,
+                                   void* der, void* dV, void* workspace, int64_t workspace_bytes,
+                                   int64_t n_row_chunks, int64_t n_col_chunks, int64_t n_edges, int64_t n_l,
+                                   int64_t n_r, int64_t h, int64_t d, double negative_slope, double p, uint64_t seed,
+                                   uint32_t offset, const graphop_plan_t* plan_r, const graphop_plan_t* plan_c,
+                                   void* stream);
+
 /* ---- attention dropout for the fused GATv2 layer (ABI 8, additive; EXTRA ops) -------------------------------------
  * The fused GATv2 attention with dropout on the attention weights, attn_drop(edge_softmax(s)), still without any
  * E-sized tensor.  The keep decision and the multiplier m_ijk are exactly those of the block above (Philox4x32-10 over
