@@ -107,6 +107,11 @@ _SIGNATURES = {
     + [ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _P, _P],
     "graphop_gat_attention_bf16_backward": [_P] * 18 + [_c64] * 8
     + [ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _P, _P, _P],
+    "graphop_gatv2_attention_bf16_workspace_bytes": [ctypes.c_int] + [_c64] * 7 + [_P, _P, ctypes.POINTER(_c64)],
+    "graphop_gatv2_attention_bf16_forward": [_P] * 10 + [_c64] * 7
+    + [ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _P, _P],
+    "graphop_gatv2_attention_bf16_backward": [_P] * 18 + [_c64] * 8
+    + [ctypes.c_double, ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _P, _P, _P],
     "graphop_edge_dropout_mask": [ctypes.c_int] + [_P] * 5 + [_c64] * 5
     + [ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _P, _P],
     "graphop_gat_edge_attention_forward": [ctypes.c_int] + [_P] * 10 + [_c64] * 6
@@ -325,6 +330,15 @@ def gat_attn_is_bf16(fn, t):
     dtype_code's answer, a refusal."""
     return t.dtype == torch.bfloat16 and fn in ("gat_attention_forward", "gat_attention_backward",
                                                 "gat_attention_dropout_forward", "gat_attention_dropout_backward")
+
+
+def gatv2_attn_is_bf16(fn, t, xe=None):
+    """True where the fused GATv2 layer's call `fn` on tables like t goes to the graphop_gatv2_attention_bf16_* entry
+    points: torch.bfloat16 tables of gatv2_attention[_dropout]_forward / _backward without edge rows.
+    With xe, and in every other GATv2 op, dtype_code's answer stands, a refusal."""
+    return xe is None and t.dtype == torch.bfloat16 and fn in (
+        "gatv2_attention_forward", "gatv2_attention_backward", "gatv2_attention_dropout_forward",
+        "gatv2_attention_dropout_backward")
 
 
 def attn_stats_dtype(t):

@@ -12,6 +12,20 @@
 
 using namespace graphop;
 
+namespace graphop {
+
+// ---- widen: the fp32 copies of el and er the stats pass reads -------------------------------------------------------------
+__global__ void k_gat_attn_bf16_widen(const bf16_t* __restrict__ a, float* __restrict__ a32, i64 n_a,
+                                      const bf16_t* __restrict__ b, float* __restrict__ b32, i64 n_b) {
+  const i64 stride = (i64)gridDim.x * blockDim.x;
+  for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n_a + n_b; i += stride) {
+    if (i < n_a) a32[i] = bf16_widen(a[i]);
+    else b32[i - n_a] = bf16_widen(b[i - n_a]);
+  }
+}
+
+}  // namespace graphop
+
 namespace {
 
 // lanes per group of a pair of GO_DISPATCH_GAT_HD, 0 outside it

@@ -28,6 +28,7 @@
 // agree on every dz bit for bit.
 #pragma once
 #include "kernels_attn_bf16.h"
+#include "kernels_bf16_drop.h"
 #include "kernels_dropout.h"
 #include "kernels_gat.h"
 
@@ -46,47 +47,7 @@ struct GatBf16Cfg : AttnBf16Cfg<H, D> {
 __device__ __forceinline__ float bf16_widen(bf16_t x) { return __uint_as_float((unsigned)x << 16); }
 __device__ __forceinline__ bf16_t bf16_round1(float x) { return (bf16_t)(bf16_pack2(x, 0.f) & 0xffffu); }
 
-// ---- the keep decision in lane groups of L lanes, SB <= L slots per batch ------------------------------------------------
-// Lane l holds slot l % SB.  One Philox call covers four heads; with H = 8 lane SB + t takes the second block of slot t
-// where the group has room (2 SB <= L), else lane t makes both calls.
-template <int H, int SB, int L>
-struct GatBf16DropCfg {
-  static constexpr int NB = (H + 3) / 4;
-  static constexpr bool SPREAD = NB * SB <= L;
-};
-
-template <int H, int SB, int L, bool COL>
-__device__ __forceinline__ int gat_bf16_lane_bits(int l, i64 own, int oth, const DropArgs<float>& dr) {
-  using C = GatBf16DropCfg<H, SB, L>;
-  const unsigned i = COL ? (unsigned)oth : (unsigned)own, j = COL ? (unsigned)own : (unsigned)oth;
-  if constexpr (C::SPREAD) {
-    return drop_keep4<float>(i, j, (unsigned)(l / SB), dr);   // (lanes past NB * SB: a block nobody reads)
-  } else {
-    int bits = 0;
-#pragma unroll
-    for (int b = 0; b < C::NB; ++b) bits |= drop_keep4<float>(i, j, (unsigned)b, dr) << (4 * b);
-    return bits;
-  }
-}
-
-// keep bits of slot U's heads (bit k = head k), in every lane of the group
-template <int H, int SB, int L, int U>
-__device__ __forceinline__ int gat_bf16_slot_bits(int lane_bits) {
-  using C = GatBf16DropCfg<H, SB, L>;
-  int bits = group_bcast<L, U>(lane_bits);
-  if constexpr (C::SPREAD && C::NB == 2) bits |= group_bcast<L, SB + U>(lane_bits) << 4;
-  return bits;
-}
-
-// ---- widen: the fp32 copies of el and er the stats pass reads -------------------------------------------------------------
-__global__ void k_gat_attn_bf16_widen(const bf16_t* __restrict__ a, float* __restrict__ a32, i64 n_a,
-                                      const bf16_t* __restrict__ b, float* __restrict__ b32, i64 n_b) {
-  const i64 stride = (i64)gridDim.x * blockDim.x;
-  for (i64 i = (i64)blockIdx.x * blockDim.x + threadIdx.x; i < n_a + n_b; i += stride) {
-    if (i < n_a) a32[i] = bf16_widen(a[i]);
-    else b32[i - n_a] = bf16_widen(b[i - n_a]);
-  }
-}
+// ---- widen: k_gat_attn_bf16_widen, no template, is defined in gat_attention_bf16.hip alone (kernels_gatv2_attn_bf16.h includes this file)
 
 // ---- forward ----------------------------------------------------------------------------------------------------------------
 struct GatBf16FwdArgs {

@@ -60,6 +60,10 @@ int attn_dtype_code(bool plain, const at::Tensor& t) {
 bool gat_attn_is_bf16(const at::Tensor& t, const at::Tensor* ee) {
   return !ee && t.scalar_type() == at::kBFloat16;
 }
+// likewise the fused GATv2 layer without edge rows and the graphop_gatv2_attention_bf16_* entry points
+bool gatv2_attn_is_bf16(const at::Tensor& t, const at::Tensor* xe) {
+  return !xe && t.scalar_type() == at::kBFloat16;
+}
 at::ScalarType attn_stats_type(const at::Tensor& t) {
   return t.scalar_type() == at::kBFloat16 ? at::kFloat : t.scalar_type();
 }
@@ -952,10 +956,18 @@ std::vector<at::Tensor> gatv2_attention_forward_impl(const char* fn, const at::T
   const int64_t e = eid.size(0), n_l = xl.size(0);
   if (xe) gatv2_edge_rows(xl, *xe, e, h, d, fn);
   DeviceGuard dg(xl);
+  const bool bf16 = gatv2_attn_is_bf16(xl, xe);
   auto o = at::empty_like(xl);
-  auto stats = at::empty({n_l, h, 2}, xl.options());
+  auto stats = at::empty({n_l, h, 2}, bf16 ? xl.options().dtype(at::kFloat) : xl.options());
   const auto pp = get_plan(row, indptr, eid, indices, xr.size(0));
   const auto& p = *pp;
+  if (bf16) {          // (no workspace: a row is never split)
+    check(graphop_gatv2_attention_bf16_forward(ip(row), ip(indptr), ip(eid), ip(indices), vp(xl), vp(xr), vp(att), vp(o),
+                                               vp(stats), nullptr, 0, row.size(0), e, n_l, xr.size(0), h, d,
+                                               negative_slope, drop ? drop->p : 0.0, drop ? drop->seed : 0,
+                                               drop ? drop->offset : 0, p.plan, stream_of(xl)));
+    return {o, stats};
+  }
   if (xe)
     check(graphop_gatv2_edge_attention_forward(dtype_code(xl), ip(row), ip(indptr), ip(eid), ip(indices), vp(xl), vp(xr),
                                                vp(*xe), vp(att), vp(o), vp(stats), row.size(0), e, n_l, xr.size(0), h, d,
@@ -1009,10 +1021,31 @@ std::vector<at::Tensor> gatv2_attention_backward_impl(const char* fn, const at::
   const int64_t h = hd.first, d = hd.second;
   const int64_t e = eid_r.size(0), n_l = xl.size(0);
   if (xe) gatv2_edge_rows(xl, *xe, e, h, d, fn);
-  CHECK_SAME_DTYPE(xl, o); CHECK_SAME_DTYPE(xl, stats); CHECK_SAME_DTYPE(xl, dO_);
+  const bool bf16 = gatv2_attn_is_bf16(xl, xe);
+  CHECK_SAME_DTYPE(xl, o); CHECK_SAME_DTYPE(xl, dO_);
+  if (bf16) {
+    TORCH_CHECK(stats.scalar_type() == at::kFloat, "expected stats to be ", at::kFloat, " for xl of ", xl.scalar_type(),
+                ", got ", stats.scalar_type());
+  } else {
+    CHECK_SAME_DTYPE(xl, stats);
+  }
   const at::Tensor dO = saved_checked(fn, xl.sizes(), n_l, h, o, stats, dO_);
   DeviceGuard dg(xl);
   auto dxl = at::empty_like(xl), dxr = at::empty_like(xr), datt = at::empty_like(att);
+  if (bf16) {
+    const auto ppr = get_plan(row, indptr_r, eid_r, indices_r, xr.size(0));
+    const auto ppc = get_plan(col, indptr_c, eid_c, indices_c, n_l);
+    int64_t nbytes = 0;
+    check(graphop_gatv2_attention_bf16_workspace_bytes(1, row.size(0), col.size(0), e, n_l, xr.size(0), h, d, ppr->plan,
+                                                       ppc->plan, &nbytes));
+    auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, xl.options().dtype(at::kByte));
+    check(graphop_gatv2_attention_bf16_backward(
+        ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c), ip(indices_c), vp(xl), vp(xr),
+        vp(att), vp(o), vp(stats), vp(dO), vp(dxl), vp(dxr), vp(datt), vp(ws), nbytes, row.size(0), col.size(0), e, n_l,
+        xr.size(0), h, d, negative_slope, drop ? drop->p : 0.0, drop ? drop->seed : 0, drop ? drop->offset : 0, ppr->plan,
+        ppc->plan, stream_of(xl)));
+    return {dxl, dxr, datt};
+  }
   // the workspace minimum of include/graphop_hip.h: (m, 1 / l, D, 0) per (node, head), then the row-pass partials
   const int64_t ws_values = n_l * h * 4 + gatv2_row_pass_values(row.size(0), h, d);
   auto ws = at::empty({std::max<int64_t>(ws_values, 1)}, xl.options());

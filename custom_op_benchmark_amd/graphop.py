@@ -19,10 +19,13 @@ Deliberate, documented deviations from the reference:
     ``graphop_kernel.cu:566,588``).
   * non-square operands are allowed: B / x may have a different row count than A / y.
 """
+import ctypes
+
 import torch
 
 from . import _lib
-from ._lib import attn_dtype_code, attn_stats_dtype, check, dtype_code, gat_attn_is_bf16, get_plan, lib, ptr, stream_of
+from ._lib import (attn_dtype_code, attn_stats_dtype, check, dtype_code, gat_attn_is_bf16, gatv2_attn_is_bf16, get_plan, lib,
+                   ptr, stream_of)
 
 __all__ = ["maskedmm_csr_forward", "maskedmm_csr_backward", "node_mul_edge_forward",
            "node_mul_edge_backward", "sparse_softmax_forward", "sparse_softmax_backward",
@@ -524,6 +527,15 @@ def _gatv2_edge_rows(xl, xe, n_edges, h, d, fn):
                            "and d = %d, got xe %s, xl %s" % (fn, n_edges, h, d, tuple(xe.shape), tuple(xl.shape)))
 
 
+def _gatv2_bf16_backward_workspace(like, n_row_chunks, n_col_chunks, e, n_l, n_r, h, d, plan_r, plan_c):
+    """(uint8 workspace tensor, bytes) of graphop_gatv2_attention_bf16_workspace_bytes for the backward (the forward needs
+    none); 0 bytes where the op will refuse"""
+    nbytes = ctypes.c_int64(0)
+    check(lib().graphop_gatv2_attention_bf16_workspace_bytes(
+        1, n_row_chunks, n_col_chunks, e, n_l, n_r, h, d, plan_r.handle, plan_c.handle, ctypes.byref(nbytes)))
+    return torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=like.device), nbytes.value
+
+
 def _gatv2_attention_forward(fn, row, indptr, eid, indices, xl, xr, att, negative_slope, drop=(), xe=None):
     """gatv2_attention_forward (drop = ()) or gatv2_attention_dropout_forward (drop = (p, seed, offset)) as `fn`; with the
     edge rows xe (which need drop) the C entry point is graphop_gatv2_edge_attention_forward."""
@@ -533,10 +545,17 @@ def _gatv2_attention_forward(fn, row, indptr, eid, indices, xl, xr, att, negativ
     e, n_l = eid.size(0), xl.size(0)
     if edge:
         _gatv2_edge_rows(xl, xe, e, h, d, fn)         # checks xe as an input too
+    bf16 = gatv2_attn_is_bf16(fn, xl, xe)          # bfloat16 tables: fp32 stats, the library refuses what it must
     o = torch.empty_like(xl)
-    stats = torch.empty((n_l, h, 2), dtype=xl.dtype, device=xl.device)
+    stats = torch.empty((n_l, h, 2), dtype=attn_stats_dtype(xl) if bf16 else xl.dtype, device=xl.device)
     with _lib.device_guard(xl.device):
         plan = get_plan(row, indptr, eid, indices, xr.size(0))
+        if bf16:
+            check(lib().graphop_gatv2_attention_bf16_forward(          # (no workspace: a row is never split)
+                ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(xl), ptr(xr), ptr(att), ptr(o), ptr(stats), _NULL,
+                0, row.size(0), e, n_l, xr.size(0), h, d, float(negative_slope), *(drop or (0.0, 0, 0)),
+                plan.handle, stream_of(xl)))
+            return [o, stats]
         check(getattr(lib(), "graphop_gatv2_edge_attention_forward" if edge else "graphop_" + fn)(
             dtype_code(xl), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(xl), ptr(xr), *(ptr(t) for t in edge),
             ptr(att), ptr(o), ptr(stats), row.size(0), e, n_l, xr.size(0), h, d, float(negative_slope), *drop,
@@ -557,10 +576,24 @@ def _gatv2_attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c
     e, n_l = eid_r.size(0), xl.size(0)
     if edge:
         _gatv2_edge_rows(xl, xe, e, h, d, fn)         # checks xe as an input too
-    for t, n in ((o, "o"), (stats, "stats"), (dO, "dO")):
+    bf16 = gatv2_attn_is_bf16(fn, xl, xe)
+    for t, n in ((o, "o"), (dO, "dO")) + (() if bf16 else ((stats, "stats"),)):
         _same_dtype(xl, t, "xl", n)
+    if bf16 and stats.dtype != torch.float32:          # fp32 statistics with bfloat16 tables
+        raise RuntimeError("expected stats to be %s for xl of %s, got %s" % (torch.float32, xl.dtype, stats.dtype))
     dO = _saved_checked(fn, tuple(xl.shape), n_l, h, o, stats, dO)
     dxl, dxr, datt = torch.empty_like(xl), torch.empty_like(xr), torch.empty_like(att)
+    if bf16:
+        with _lib.device_guard(xl.device):
+            plan_r = get_plan(row, indptr_r, eid_r, indices_r, xr.size(0))
+            plan_c = get_plan(col, indptr_c, eid_c, indices_c, n_l)
+            ws, nbytes = _gatv2_bf16_backward_workspace(xl, row.size(0), col.size(0), e, n_l, xr.size(0), h, d, plan_r, plan_c)
+            check(lib().graphop_gatv2_attention_bf16_backward(
+                ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c), ptr(eid_c), ptr(indices_c),
+                ptr(xl), ptr(xr), ptr(att), ptr(o), ptr(stats), ptr(dO), ptr(dxl), ptr(dxr), ptr(datt), ptr(ws), nbytes,
+                row.size(0), col.size(0), e, n_l, xr.size(0), h, d, float(negative_slope), *(drop or (0.0, 0, 0)),
+                plan_r.handle, plan_c.handle, stream_of(xl)))
+        return [dxl, dxr, datt]
     dxe = ()        # with xe: [dxe], an empty (0,) tensor and a NULL pointer where it is not wanted
     if edge:
         dxe = (torch.empty_like(xe) if need_dxe else torch.empty((0,), dtype=xe.dtype, device=xe.device),)

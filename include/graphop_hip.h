@@ -620,6 +620,46 @@ GRAPHOP_API int graphop_gatv2_attention_dropout_backward(int dtype, const int64_
                                      double negative_slope, double p, uint64_t seed, uint32_t offset,
                                      const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream);
 
+/* ---- the fused GATv2 layer on bfloat16 tables (ABI 8, additive; EXTRA ops; csrc/kernels_gatv2_attn_bf16.h) ----------
+ * The op of the block above -- with p == 0 the plain layer, else with attention dropout -- on bfloat16 tables: xl, xr,
+ * att, o, dO, dxl, dxr, datt are bf16, stats (n_l, h, 2) = (m, 1 / l) stay fp32.  z = float(xl[i, k, c]) +
+ * float(xr[j, k, c]) is one fp32 add of exactly widened values, LeakyReLU(z) = max(z, 0) + slope * min(z, 0) and
+ * s = sum_c float(att[k, c]) LeakyReLU(z) in fp32, by one expression in one order in all three gather passes; every sum
+ * is fp32, every bf16 result is rounded once to nearest even, and no float atomic touches an output: results are
+ * bit-identical from run to run.  stats with dropout equal stats without.  The backward takes D_i = <dO_i, o_i> from the
+ * bf16 o it is given.  Nothing edge-sized exists in either direction.  graphop_gatv2_attention_* and the edge form keep
+ * answering GRAPHOP_BF16 with an error; these take no dtype.
+ * Supported: (h, d) with h in {1, 2, 4, 8}, d in {8, 16, 32, 64}, h * d in {64, 128, 256}; the plan(s) given, made with
+ * indices, row_owned, the forward's with the segment table, with id ranges inside the tables, ids below 2^31 and row ids
+ * below 2^30; every bf16 table 16-byte aligned (stats 8-byte).  Otherwise the workspace query answers 0 bytes and
+ * forward / backward return GRAPHOP_ERR_INVALID_ARGUMENT with a message naming the unmet condition: there is no generic
+ * path and no upcast.
+ * workspace: graphop_gatv2_attention_bf16_workspace_bytes(...) bytes, each term rounded up to 256.  With np_x = 2 * the
+ * lane groups of orientation x's chunk list (the chunk geometry of the several-head attention passes), nb_r the
+ * workgroups of the row pass (lane groups / (256 / min(16, F / 8)), rounded up) and F = h * d:
+ *   forward : 0 (a row is never split: registers and LDS)
+ *   backward: 16 n_l h (P = (m, 1 / l, D, 0)) + 4 max(np_r, np_c) (row words) + 4 F max(np_r, np_c) (dxl / dxr records,
+ *             one area for whichever pass is running) + 4 F nb_r (datt partials)
+ * A call without slots (n_edges == 0 or no chunks) needs none: o, dxl, dxr, datt = 0 and stats = (-1e9, 0). */
+GRAPHOP_API int graphop_gatv2_attention_bf16_workspace_bytes(int backward, int64_t n_row_chunks, int64_t n_col_chunks,
+                                   int64_t n_edges, int64_t n_l, int64_t n_r, int64_t h, int64_t d,
+                                   const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, int64_t* bytes_out);
+GRAPHOP_API int graphop_gatv2_attention_bf16_forward(const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                                   const int64_t* indices, const void* xl, const void* xr, const void* att, void* o,
+                                   void* stats, void* workspace, int64_t workspace_bytes, int64_t n_chunks,
+                                   int64_t n_edges, int64_t n_l, int64_t n_r, int64_t h, int64_t d,
+                                   double negative_slope, double p, uint64_t seed, uint32_t offset,
+                                   const graphop_plan_t* plan, void* stream);
+GRAPHOP_API int graphop_gatv2_attention_bf16_backward(const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r,
+                                   const int64_t* indices_r, const int64_t* col, const int64_t* indptr_c,
+                                   const int64_t* eid_c, const int64_t* indices_c, const void* xl, const void* xr,
+                                   const void* att, const void* o, const void* stats, const void* dO, void* dxl,
+                                   void* dxr, void* datt, void* workspace, int64_t workspace_bytes,
+                                   int64_t n_row_chunks, int64_t n_col_chunks, int64_t n_edges, int64_t n_l,
+                                   int64_t n_r, int64_t h, int64_t d, double negative_slope, double p, uint64_t seed,
+                                   uint32_t offset, const graphop_plan_t* plan_r, const graphop_plan_t* plan_c,
+                                   void* stream);
+
 /* ---- fused GAT attention with an edge term (ABI 8, additive; EXTRA ops) ------------------------------------------
  * The fused GAT layer for GATConv(edge_dim=...) / EGATConv, and for a fixed per-edge bias such as log edge weights: per
  * head k, for every slot of every chunk c with i = row[c], j = indices[slot], e = eid[slot],
