@@ -402,11 +402,12 @@ void check_attn_bias(const char* fn, const at::Tensor& b, const at::Tensor& Q, i
 }
 
 // drop == nullptr: graphop_attention_forward, else its dropout form for the heads head0 .. head0 + h - 1, as `fn`;
-// b != nullptr (with drop given): the form with a per-edge score bias
+// b != nullptr (with drop given): the form with a per-edge score bias; bf16_opts (with drop given): the
+// graphop_attention_bf16_opts_* entry points, which take bfloat16 tables and a b that may be absent
 std::vector<at::Tensor> attention_forward_impl(const char* fn, const at::Tensor& row, const at::Tensor& indptr,
                                                const at::Tensor& eid, const at::Tensor& indices, const at::Tensor& Q,
                                                const at::Tensor& K, const at::Tensor& V, const DropSpec* drop,
-                                               int64_t head0, const at::Tensor* b = nullptr) {
+                                               int64_t head0, const at::Tensor* b = nullptr, bool bf16_opts = false) {
   CHECK_CSR(row, indptr, eid, indices);
   CHECK_INPUT(Q); CHECK_INPUT(K); CHECK_INPUT(V);
   if (b) check_attn_bias_input(*b);
@@ -421,15 +422,23 @@ std::vector<at::Tensor> attention_forward_impl(const char* fn, const at::Tensor&
   const auto pp = get_plan(row, indptr, eid, indices, n_k);
   const auto& p = *pp;
   int64_t nbytes = 0;
-  if (b) {
-    check_attn_bias(fn, *b, Q, e, h);
+  if (b) check_attn_bias(fn, *b, Q, e, h);
+  if (bf16_opts) {
+    TORCH_CHECK(Q.scalar_type() == at::kBFloat16, fn, ": bfloat16 tensors only, got ", Q.scalar_type());
+    check(graphop_attention_bf16_opts_workspace_bytes(0, e, n_q, n_k, h, d, p.plan, nullptr, stream_of(Q), 0, &nbytes));
+  } else if (b) {
     check(graphop_attention_bias_workspace_bytes(dtype_code(Q), 0, e, n_q, n_k, h, d, p.plan, nullptr, stream_of(Q), 0, &nbytes));
   } else {
     check((drop ? graphop_attention_dropout_workspace_bytes : graphop_attention_workspace_bytes)(
         attn_dtype_code(plain, Q), 0, e, n_q, n_k, h, d, p.plan, nullptr, stream_of(Q), &nbytes));
   }
   auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, Q.options().dtype(at::kByte));
-  if (b)
+  if (bf16_opts)
+    check(graphop_attention_bf16_opts_forward(ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(V),
+                                              b ? vp(*b) : nullptr, vp(o), vp(stats), row.size(0), e, n_q, n_k, h, d,
+                                              ws.data_ptr(), nbytes, p.plan, stream_of(Q), drop->p, drop->seed,
+                                              drop->offset, head0));
+  else if (b)
     check(graphop_attention_bias_forward(dtype_code(Q), ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(V),
                                          vp(*b), vp(o), vp(stats), row.size(0), e, n_q, n_k, h, d, ws.data_ptr(), nbytes,
                                          p.plan, stream_of(Q), drop->p, drop->seed, drop->offset, head0));
@@ -473,6 +482,18 @@ std::vector<at::Tensor> attention_bias_forward(const at::Tensor& row, const at::
   return attention_forward_impl(fn, row, indptr, eid, indices, Q, K, V, &drop, head0_checked(fn, head0), &b);
 }
 
+// ... on bfloat16 tables; b = None: no bias
+std::vector<at::Tensor> attention_bf16_opts_forward(const at::Tensor& row, const at::Tensor& indptr,
+                                                    const at::Tensor& eid, const at::Tensor& indices, const at::Tensor& Q,
+                                                    const at::Tensor& K, const at::Tensor& V,
+                                                    const c10::optional<at::Tensor>& b, double p, int64_t seed,
+                                                    int64_t offset, int64_t head0) {
+  const char* fn = "attention_bf16_opts_forward";
+  const DropSpec drop = drop_spec(fn, p, seed, offset);
+  return attention_forward_impl(fn, row, indptr, eid, indices, Q, K, V, &drop, head0_checked(fn, head0),
+                                b ? &*b : nullptr, true);
+}
+
 // drop == nullptr: graphop_attention_backward, else its dropout form, as `fn`; b != nullptr (with drop given): the form
 // with a per-edge score bias, which returns db as a fourth tensor (empty with need_db == false)
 std::vector<at::Tensor> attention_backward_impl(const char* fn, const at::Tensor& row, const at::Tensor& indptr_r,
@@ -482,7 +503,7 @@ std::vector<at::Tensor> attention_backward_impl(const char* fn, const at::Tensor
                                                 const at::Tensor& Q, const at::Tensor& K, const at::Tensor& V,
                                                 const at::Tensor& o, const at::Tensor& stats, const at::Tensor& dO_,
                                                 const DropSpec* drop, int64_t head0, const at::Tensor* b = nullptr,
-                                                bool need_db = true) {
+                                                bool need_db = true, bool bf16_opts = false) {
   CHECK_CSR(row, indptr_r, eid_r, indices_r);
   CHECK_CSR(col, indptr_c, eid_c, indices_c);
   CHECK_INPUT(Q); CHECK_INPUT(K); CHECK_INPUT(V);
@@ -509,8 +530,12 @@ std::vector<at::Tensor> attention_backward_impl(const char* fn, const at::Tensor
   const auto ppc = get_plan(col, indptr_c, eid_c, indices_c, n_q);
   const auto &pr = *ppr, &pc = *ppc;
   int64_t nbytes = 0;
-  if (b) {
-    check_attn_bias(fn, *b, Q, e, h);
+  if (b) check_attn_bias(fn, *b, Q, e, h);
+  if (bf16_opts) {
+    TORCH_CHECK(Q.scalar_type() == at::kBFloat16, fn, ": bfloat16 tensors only, got ", Q.scalar_type());
+    check(graphop_attention_bf16_opts_workspace_bytes(1, e, n_q, n_k, h, d, pr.plan, pc.plan, stream_of(Q),
+                                                      b && need_db ? 1 : 0, &nbytes));
+  } else if (b) {
     check(graphop_attention_bias_workspace_bytes(dtype_code(Q), 1, e, n_q, n_k, h, d, pr.plan, pc.plan, stream_of(Q),
                                                  need_db ? 1 : 0, &nbytes));
   } else {
@@ -518,6 +543,16 @@ std::vector<at::Tensor> attention_backward_impl(const char* fn, const at::Tensor
         attn_dtype_code(plain, Q), 1, e, n_q, n_k, h, d, pr.plan, pc.plan, stream_of(Q), &nbytes));
   }
   auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, Q.options().dtype(at::kByte));
+  if (bf16_opts) {   // always four tensors; db is empty without b too
+    const bool with_db = b && need_db;
+    auto db = !with_db ? at::empty({0}, Q.options()) : (pr.info.full_coverage ? at::empty_like(*b) : at::zeros_like(*b));
+    check(graphop_attention_bf16_opts_backward(
+        ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c), ip(indices_c), vp(Q), vp(K),
+        vp(V), b ? vp(*b) : nullptr, vp(o), vp(stats), vp(dO), vp(dQ), vp(dK), vp(dV), with_db ? vp(db) : nullptr,
+        row.size(0), col.size(0), e, n_q, n_k, h, d, ws.data_ptr(), nbytes, pr.plan, pc.plan, stream_of(Q), drop->p,
+        drop->seed, drop->offset, head0));
+    return {dQ, dK, dV, db};
+  }
   if (b) {
     // db[e] is written once per row-major slot: only a chunk list that leaves slots out needs the zeros
     auto db = !need_db ? at::empty({0}, b->options()) : (pr.info.full_coverage ? at::empty_like(*b) : at::zeros_like(*b));
@@ -575,6 +610,20 @@ std::vector<at::Tensor> attention_bias_backward(const at::Tensor& row, const at:
   const DropSpec drop = drop_spec(fn, p, seed, offset);
   return attention_backward_impl(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, o, stats,
                                  dO, &drop, head0_checked(fn, head0), &b, need_db);
+}
+
+std::vector<at::Tensor> attention_bf16_opts_backward(const at::Tensor& row, const at::Tensor& indptr_r,
+                                                     const at::Tensor& eid_r, const at::Tensor& indices_r,
+                                                     const at::Tensor& col, const at::Tensor& indptr_c,
+                                                     const at::Tensor& eid_c, const at::Tensor& indices_c,
+                                                     const at::Tensor& Q, const at::Tensor& K, const at::Tensor& V,
+                                                     const c10::optional<at::Tensor>& b, const at::Tensor& o,
+                                                     const at::Tensor& stats, const at::Tensor& dO, double p, int64_t seed,
+                                                     int64_t offset, int64_t head0, bool need_db) {
+  const char* fn = "attention_bf16_opts_backward";
+  const DropSpec drop = drop_spec(fn, p, seed, offset);
+  return attention_backward_impl(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, o, stats,
+                                 dO, &drop, head0_checked(fn, head0), b ? &*b : nullptr, need_db, true);
 }
 
 // ---- edge features of the fused attention step (include/graphop_hip.h: graphop_attention_edge_*) ------------------------
@@ -1438,6 +1487,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("indices_c"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("b"), py::arg("o"), py::arg("stats"),
         py::arg("dO"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0, py::arg("head0") = 0,
         py::arg("need_db") = true);
+  // (likewise dropout and the score bias on bfloat16 tables; b may be None)
+  m.def("attention_bf16_opts_forward", &attention_bf16_opts_forward,
+        "Fused attention forward on bfloat16 tables with attention dropout and / or a per-edge score bias (extra op)",
+        py::arg("row"), py::arg("indptr"), py::arg("eid"), py::arg("indices"), py::arg("Q"), py::arg("K"), py::arg("V"),
+        py::arg("b") = py::none(), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0, py::arg("head0") = 0);
+  m.def("attention_bf16_opts_backward", &attention_bf16_opts_backward,
+        "Fused attention backward on bfloat16 tables with attention dropout and / or a per-edge score bias (extra op)",
+        py::arg("row"), py::arg("indptr_r"), py::arg("eid_r"), py::arg("indices_r"), py::arg("col"), py::arg("indptr_c"),
+        py::arg("eid_c"), py::arg("indices_c"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("b"), py::arg("o"),
+        py::arg("stats"), py::arg("dO"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0,
+        py::arg("head0") = 0, py::arg("need_db") = true);
   // (likewise its form with edge features: K_j + xe[e], V_j + xe[e])
   m.def("attention_edge_forward", &attention_edge_forward,
         "Fused attention forward with edge features in key and value (extra op)", py::arg("row"), py::arg("indptr"),

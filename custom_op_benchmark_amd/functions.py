@@ -393,8 +393,15 @@ class FusedAttentionDropout(Function):
         seed = _drop_seed(seed, p)
         ctx.drop = (float(p), int(seed), int(offset))
         h = Q.size(1) if Q.dim() == 3 else 1
-        hg = _heads_per_call(a8, Q, K, h)
         ctx.groups = None
+        ctx.bf16 = Q.dtype == torch.bfloat16
+        if ctx.bf16:
+            # bfloat16: ONE call over all heads with head0 = 0, bf16 gradients; the library's refusal is
+            # the RuntimeError, as in FusedAttention
+            o, stats = _ops.attention_bf16_opts_forward(row, indptr_r, eid_r, indices_r, Q, K, V, None, *ctx.drop, 0)
+            ctx.save_for_backward(*a8, Q, K, V, o, stats)
+            return o
+        hg = _heads_per_call(a8, Q, K, h)
         if h > 1 and hg < h:
             return _groups_forward(ctx, a8, Q, K, V, h, hg, ctx.drop)
         o, stats = _ops.attention_dropout_forward(row, indptr_r, eid_r, indices_r, Q, K, V, *ctx.drop, 0)
@@ -409,7 +416,10 @@ class FusedAttentionDropout(Function):
         if ctx.groups is not None:
             return (None,) * 8 + _groups_backward(ctx, a8, *rest, dO, ctx.drop) + (None, None, None)
         Q, K, V, o, stats = rest
-        dQ, dK, dV = _ops.attention_dropout_backward(*a8, Q, K, V, o, stats, dO, *ctx.drop, 0)
+        if ctx.bf16:
+            dQ, dK, dV, _ = _ops.attention_bf16_opts_backward(*a8, Q, K, V, None, o, stats, dO, *ctx.drop, 0)
+        else:
+            dQ, dK, dV = _ops.attention_dropout_backward(*a8, Q, K, V, o, stats, dO, *ctx.drop, 0)
         return (None,) * 8 + (dQ, dK, dV, None, None, None)
 
 
@@ -439,8 +449,13 @@ class FusedAttentionBias(Function):
         seed = _drop_seed(seed, p)
         ctx.drop = (float(p), int(seed), int(offset))
         h = Q.size(1) if Q.dim() == 3 else 1
-        hg = _heads_per_call(a8, Q, K, h)
         ctx.groups = None
+        ctx.bf16 = Q.dtype == torch.bfloat16
+        if ctx.bf16:   # (one call over all heads, as in FusedAttentionDropout)
+            o, stats = _ops.attention_bf16_opts_forward(row, indptr_r, eid_r, indices_r, Q, K, V, b, *ctx.drop, 0)
+            ctx.save_for_backward(*a8, Q, K, V, b, o, stats)
+            return o
+        hg = _heads_per_call(a8, Q, K, h)
         if h > 1 and hg < h:
             return _groups_forward(ctx, a8, Q, K, V, h, hg, ctx.drop, b)
         o, stats = _ops.attention_bias_forward(row, indptr_r, eid_r, indices_r, Q, K, V, b, *ctx.drop, 0)
@@ -456,7 +471,8 @@ class FusedAttentionBias(Function):
             dQ, dK, dV, db = _groups_backward(ctx, a8, Q, K, V, dO, ctx.drop, b, need_db)
         else:
             Q, K, V, b, o, stats = rest
-            dQ, dK, dV, db = _ops.attention_bias_backward(*a8, Q, K, V, b, o, stats, dO, *ctx.drop, 0, need_db)
+            backward = _ops.attention_bf16_opts_backward if ctx.bf16 else _ops.attention_bias_backward
+            dQ, dK, dV, db = backward(*a8, Q, K, V, b, o, stats, dO, *ctx.drop, 0, need_db)
         return (None,) * 8 + (dQ, dK, dV, db if need_db else None, None, None, None)
 
 

@@ -263,15 +263,18 @@ def node_mul_edge_backward(row, indptr, eid, A, B, dy):
 
 # ---- fused attention step (extra op; the composition wrapper.py:20-30, 8-18, 44-55) ------------------
 def _workspace(like, dtype, backward, e, n_q, n_k, h, d, plan_r, plan_c, dropout=False, bias=None):
-    """bias: None, or whether the call with a score bias is a backward that writes db"""
+    """bias: None, or whether the call with a score bias is a backward that writes db.  dtype None: the bfloat16 step
+    with options (attention_bf16_opts_*), whose query takes no dtype code and always a with_db"""
     import ctypes
     nbytes = ctypes.c_int64(0)
     query = lib().graphop_attention_dropout_workspace_bytes if dropout else lib().graphop_attention_workspace_bytes
     extra = ()
     if bias is not None:
         query, extra = lib().graphop_attention_bias_workspace_bytes, (1 if bias else 0,)
+    if dtype is None:
+        query, extra = lib().graphop_attention_bf16_opts_workspace_bytes, (1 if bias else 0,)
     check(query(
-        dtype, 1 if backward else 0, e, n_q, n_k, h, d, plan_r.handle if plan_r is not None else _NULL,
+        *(() if dtype is None else (dtype,)), 1 if backward else 0, e, n_q, n_k, h, d, plan_r.handle if plan_r is not None else _NULL,
         plan_c.handle if plan_c is not None else _NULL, stream_of(like), *extra, ctypes.byref(nbytes)))
     return torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=like.device), nbytes.value
 
@@ -302,9 +305,15 @@ def _attn_bias(fn, b, Q, n_edges, h):
                            "got b %s, Q %s" % (fn, n_edges, h, tuple(b.shape), tuple(Q.shape)))
 
 
-def _attention_forward(fn, row, indptr, eid, indices, Q, K, V, drop=(), b=None):
+def _bf16_only(fn, Q):
+    if attn_stats_dtype(Q) == Q.dtype:          # (bfloat16 tables are the ones with fp32 statistics)
+        raise RuntimeError("%s: bfloat16 tensors only, got %s" % (fn, Q.dtype))
+
+
+def _attention_forward(fn, row, indptr, eid, indices, Q, K, V, drop=(), b=None, bf16_opts=False):
     """attention_forward (drop = ()), attention_dropout_forward (drop = (p, seed, offset, head0)) or, with the score
-    bias b, attention_bias_forward as `fn`"""
+    bias b, attention_bias_forward as `fn`; bf16_opts: attention_bf16_opts_forward, which takes no dtype code and a b
+    that may be None"""
     _check_csr((row, indptr, eid, indices), _CSR, (Q, "Q"), (K, "K"), (V, "V"), *(((b, "b"),) if b is not None else ()))
     _same_dtype(Q, K, "Q", "K")
     _same_dtype(Q, V, "Q", "V")
@@ -317,15 +326,19 @@ def _attention_forward(fn, row, indptr, eid, indices, Q, K, V, drop=(), b=None):
     if b is not None:
         _attn_bias(fn, b, Q, e, h)
         bias = (ptr(b),)
+    elif bf16_opts:
+        bias = (_NULL,)
     o = torch.empty_like(Q)
-    code = attn_dtype_code(fn, Q)
+    if bf16_opts:
+        _bf16_only(fn, Q)
+    code = () if bf16_opts else (attn_dtype_code(fn, Q),)
     stats = torch.empty((n_q, h, 2), dtype=attn_stats_dtype(Q), device=Q.device)
     with _lib.device_guard(Q.device):
         plan = get_plan(row, indptr, eid, indices, n_k)
-        ws, nbytes = _workspace(Q, code, False, e, n_q, n_k, h, d, plan, None, bool(drop),
+        ws, nbytes = _workspace(Q, code[0] if code else None, False, e, n_q, n_k, h, d, plan, None, bool(drop),
                                 False if b is not None else None)
         check(getattr(lib(), "graphop_" + fn)(
-            code, ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(Q), ptr(K), ptr(V), *bias,
+            *code, ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(Q), ptr(K), ptr(V), *bias,
             ptr(o), ptr(stats), row.size(0), e, n_q, n_k, h, d, ptr(ws), nbytes, plan.handle,
             stream_of(Q), *drop))
     return [o, stats]
@@ -339,9 +352,11 @@ def attention_forward(row, indptr, eid, indices, Q, K, V):
 
 
 def _attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c,
-                        Q, K, V, o, stats, dO, drop=(), b=None, need_db=True):
+                        Q, K, V, o, stats, dO, drop=(), b=None, need_db=True, bf16_opts=False):
     """attention_backward (drop = ()), attention_dropout_backward (drop = (p, seed, offset, head0)) or, with the score
-    bias b, attention_bias_backward as `fn`: then -> [dQ, dK, dV, db], db an empty (0,) tensor with need_db=False"""
+    bias b, attention_bias_backward as `fn`: then -> [dQ, dK, dV, db], db an empty (0,) tensor with need_db=False.
+    bf16_opts: attention_bf16_opts_backward, which takes no dtype code and a b that may be None -> always four tensors,
+    db empty without b too"""
     _check_csr((row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c), _CSR_RC,
                (Q, "Q"), (K, "K"), (V, "V"), *(((b, "b"),) if b is not None else ()), (o, "o"), (stats, "stats"))
     _check_grad(dO, "dO")
@@ -351,7 +366,9 @@ def _attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_
                 raise RuntimeError("expected stats to be %s for Q of %s, got %s" % (attn_stats_dtype(Q), Q.dtype, t.dtype))
         else:
             _same_dtype(Q, t, "Q", n)
-    code = attn_dtype_code(fn, Q)
+    if bf16_opts:
+        _bf16_only(fn, Q)
+    code = () if bf16_opts else (attn_dtype_code(fn, Q),)
     dO = dO.contiguous()
     e, d = eid_r.size(0), Q.size(-1)
     h = 1 if Q.dim() == 2 else Q.size(1)
@@ -370,14 +387,17 @@ def _attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_
             db = (torch.empty_like(b) if plan_r.info.full_coverage else torch.zeros_like(b)) if need_db \
                 else torch.empty((0,), dtype=b.dtype, device=b.device)
             bias, dbias = (ptr(b),), (ptr(db) if need_db else _NULL,)
-        ws, nbytes = _workspace(Q, code, True, e, n_q, n_k, h, d, plan_r, plan_c, bool(drop),
+        elif bf16_opts:
+            db = torch.empty((0,), dtype=Q.dtype, device=Q.device)
+            bias, dbias = (_NULL,), (_NULL,)
+        ws, nbytes = _workspace(Q, code[0] if code else None, True, e, n_q, n_k, h, d, plan_r, plan_c, bool(drop),
                                 bool(need_db) if b is not None else None)
         check(getattr(lib(), "graphop_" + fn)(
-            code, ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col),
+            *code, ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col),
             ptr(indptr_c), ptr(eid_c), ptr(indices_c), ptr(Q), ptr(K), ptr(V), *bias, ptr(o), ptr(stats),
             ptr(dO), ptr(dQ), ptr(dK), ptr(dV), *dbias, row.size(0), col.size(0), e, n_q, n_k, h, d,
             ptr(ws), nbytes, plan_r.handle, plan_c.handle, stream_of(Q), *drop))
-    return [dQ, dK, dV] if b is None else [dQ, dK, dV, db]
+    return [dQ, dK, dV] if b is None and not bf16_opts else [dQ, dK, dV, db]
 
 
 def attention_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c,
@@ -862,6 +882,27 @@ def attention_bias_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_
                                dO, _drop_args(fn, p, seed, offset) + (_head0(fn, head0),), b, need_db)
 
 
+# ---- dropout and the score bias on bfloat16 tables (extra ops) --------------------------------------
+def attention_bf16_opts_forward(row, indptr, eid, indices, Q, K, V, b=None, p=0.0, seed=0, offset=0, head0=0):
+    """-> [o, stats] of attention_bias_forward on bfloat16 Q / K / V (and b, (n_edges, h) bfloat16, or None: no bias):
+    bf16 gathers, fp32 sums, o rounded once, fp32 stats of the biased, undropped scores, bit-reproducible.  p = 0 and
+    b = None is attention_forward on bfloat16 tensors bit for bit.  The library refuses what its bfloat16 kernels do not
+    cover with a message that names the condition; nothing is upcast."""
+    fn = "attention_bf16_opts_forward"
+    return _attention_forward(fn, row, indptr, eid, indices, Q, K, V,
+                              _drop_args(fn, p, seed, offset) + (_head0(fn, head0),), b, bf16_opts=True)
+
+
+def attention_bf16_opts_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, b, o, stats, dO,
+                                 p=0.0, seed=0, offset=0, head0=0, need_db=True):
+    """-> [dQ, dK, dV, db] of attention_bf16_opts_forward for the output gradient dO, all bfloat16, with the same (p,
+    seed, offset, head0).  db[e] = ds_e in b's shape, rounded once, is the only edge-sized tensor made; without b or with
+    need_db=False it is an empty (0,) tensor and nothing edge-sized is written.  stats must be the forward's fp32 ones."""
+    fn = "attention_bf16_opts_backward"
+    return _attention_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, o, stats,
+                               dO, _drop_args(fn, p, seed, offset) + (_head0(fn, head0),), b, need_db, bf16_opts=True)
+
+
 # ---- an edge row in key and value of the fused attention step (extra ops): K_j + xe[e], V_j + xe[e] (DESIGN.md 4.5m)
 # ---- and, for a categorical edge feature, K_j + R[t_e], V_j + R[t_e] (4.5o) or <Q_i, K_j> + B[t_e] (4.5p).  One body
 # ---- per direction: etype None is the first op (rows = xe), else the op's name says which table rows is (R or B)
@@ -1269,7 +1310,10 @@ _SCHEMAS = {
 # (attention_edge_*) and the weights of all of them (attention_weights): bound here and in the compiled extension, not registered under torch.ops.graphop (the registered set is the table above)
 EXTRA_OPS = [n for n in _SCHEMAS if n not in __all__] + ["attention_backward_is_fused", "attention_dropout_forward",
                                                          "attention_dropout_backward", "attention_bias_forward",
-                                                         "attention_bias_backward", "attention_edge_forward",
+                                                         "attention_bias_backward",
+                                                         # ... on bfloat16 tables (attention_bf16_opts_*)
+                                                         "attention_bf16_opts_forward", "attention_bf16_opts_backward",
+                                                         "attention_edge_forward",
                                                          "attention_edge_backward", "attention_weights",
                                                          # edge-type embeddings (attention_etype_*)
                                                          "attention_etype_forward", "attention_etype_backward",

@@ -872,6 +872,47 @@ GRAPHOP_API int graphop_attention_bias_backward(int dtype, const int64_t* row, c
                                     int64_t workspace_bytes, const graphop_plan_t* plan_r, const graphop_plan_t* plan_c,
                                     void* stream, double p, uint64_t seed, uint32_t offset, int64_t head0);
 
+/* ---- dropout and the per-edge score bias on bfloat16 tables (ABI 8, additive; EXTRA ops; csrc/kernels_attn_bf16_opts.h)
+ * graphop_attention_bias_forward / _backward as stated above, on the tables of the bfloat16 step (dtype GRAPHOP_BF16 of
+ * graphop_attention_forward): Q, K, V, o, dO, dQ, dK, dV are bf16 [n][h][d] and 16-byte aligned; b and db are bf16
+ * (n_edges, h), indexed by edge id, contiguous, with no alignment beyond their element; stats (n_q, h, 2) is fp32.  These
+ * entry points take no dtype; graphop_attention_dropout_* and graphop_attention_bias_* keep answering GRAPHOP_BF16 with
+ * "bad dtype".  b == NULL: no bias (db must then be NULL too).  db == NULL: the gradient of b is not wanted and no kernel
+ * stores anything edge-sized.  p == 0: no Philox path anywhere.  p == 0 and b == NULL: the kernels of
+ * graphop_attention_forward / _backward(GRAPHOP_BF16, ...), bit-identical results.
+ *   s_e = <Q_i, K_j> + float(b[e, k]): the bf16 step's dot product, then ONE fp32 add of the exactly widened value, the same
+ *   expression in the forward and in both backward passes, so the backward's s is the forward's bit for bit.  stats are
+ *   those of the biased, undropped scores (m floored at -1e9; (0, 0) for a row without slots).  D_i = <dO_i, o_i> from the
+ *   bf16 o as given.  The multiplier is graphop_edge_dropout_mask's for (i, j, head0 + k), 1 / (1 - p) in fp32.  db[e] is
+ *   written once, rounded once, for every edge id a row-major slot names; other entries are left untouched.
+ * Every sum is fp32, every bf16 result is rounded once to nearest even, and no float atomic touches an output, db
+ * included: two runs are bit-identical.  Nothing edge-sized exists but b and db.
+ * Supported: the (h, d) pairs and plans of the bfloat16 step (see graphop_attention_forward), and 0 <= p < 1,
+ * seed < 2^63, 0 <= head0, head0 + h < 2^31.  Otherwise the workspace query answers 0 bytes and forward / backward return
+ * GRAPHOP_ERR_INVALID_ARGUMENT with a message naming the unmet condition; nothing is upcast or composed.  Empty problems
+ * are no-ops that dereference nothing.
+ * workspace: graphop_attention_bf16_opts_workspace_bytes(...) bytes, which is what
+ * graphop_attention_workspace_bytes(GRAPHOP_BF16, ...) reports for the same direction: the options add nothing to the
+ * records or the packed tables, with or without db (with_db changes nothing). */
+GRAPHOP_API int graphop_attention_bf16_opts_workspace_bytes(int backward, int64_t n_edges, int64_t n_q, int64_t n_k,
+                                                int64_t h, int64_t d, const graphop_plan_t* plan_r,
+                                                const graphop_plan_t* plan_c, void* stream, int with_db,
+                                                int64_t* bytes_out);
+GRAPHOP_API int graphop_attention_bf16_opts_forward(const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                                        const int64_t* indices, const void* Q, const void* K, const void* V, const void* b,
+                                        void* o, void* stats, int64_t n_chunks, int64_t n_edges, int64_t n_q, int64_t n_k,
+                                        int64_t h, int64_t d, void* workspace, int64_t workspace_bytes,
+                                        const graphop_plan_t* plan, void* stream, double p, uint64_t seed,
+                                        uint32_t offset, int64_t head0);
+GRAPHOP_API int graphop_attention_bf16_opts_backward(const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r,
+                                         const int64_t* indices_r, const int64_t* col, const int64_t* indptr_c,
+                                         const int64_t* eid_c, const int64_t* indices_c, const void* Q, const void* K,
+                                         const void* V, const void* b, const void* o, const void* stats, const void* dO,
+                                         void* dQ, void* dK, void* dV, void* db, int64_t n_row_chunks, int64_t n_col_chunks,
+                                         int64_t n_edges, int64_t n_q, int64_t n_k, int64_t h, int64_t d, void* workspace,
+                                         int64_t workspace_bytes, const graphop_plan_t* plan_r, const graphop_plan_t* plan_c,
+                                         void* stream, double p, uint64_t seed, uint32_t offset, int64_t head0);
+
 /* ---- edge features in the fused attention step: K_j + xe[e], V_j + xe[e] (ABI 8, additive; EXTRA ops) --------------
  * The fused step with a feature row per edge added to the key AND the value (TransformerConv(edge_dim=...):
  * out = alpha * (value_j + edge_attr); the Dwivedi-Bresson and GraphGPS edge-featured graph transformers).  For edge
