@@ -674,11 +674,43 @@ struct AttnTableAbi {
   decltype(&graphop_attention_etype_forward) forward;
   decltype(&graphop_attention_etype_backward) backward;
   decltype(&check_attn_etype_table) check;
+  bool bf16 = false;   // bfloat16 tables and fp32 statistics: entry points that take no dtype code
+  int code(const at::Tensor& Q) const { return bf16 ? GRAPHOP_BF16 : dtype_code(Q); }
 };
 const AttnTableAbi kAttnEtypeAbi = {graphop_attention_etype_workspace_bytes, graphop_attention_etype_forward,
                                     graphop_attention_etype_backward, check_attn_etype_table};
 const AttnTableAbi kAttnTbiasAbi = {graphop_attention_tbias_workspace_bytes, graphop_attention_tbias_forward,
                                     graphop_attention_tbias_backward, check_attn_tbias_table};
+
+// ... on bfloat16 tables (graphop_attention_tbias_bf16_*): the same lists without the dtype code
+void check_attn_tbias_bf16_table(const char* fn, const at::Tensor& B, const at::Tensor& etype, const at::Tensor& Q, int64_t e) {
+  TORCH_CHECK(Q.scalar_type() == at::kBFloat16, fn, ": bfloat16 tensors only, got ", Q.scalar_type());
+  check_attn_tbias_table(fn, B, etype, Q, e);
+}
+const AttnTableAbi kAttnTbiasBf16Abi = {
+    [](int, int backward, int64_t e, int64_t n_q, int64_t n_k, int64_t h, int64_t d, int64_t n_types,
+       const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream, int64_t* bytes_out) {
+      return graphop_attention_tbias_bf16_workspace_bytes(backward, e, n_q, n_k, h, d, n_types, plan_r, plan_c, stream, bytes_out);
+    },
+    [](int, const int64_t* row, const int64_t* indptr, const int64_t* eid, const int64_t* indices, const void* Q,
+       const void* K, const void* V, const void* B, const int32_t* etype, void* o, void* stats, int64_t n_chunks, int64_t e,
+       int64_t n_q, int64_t n_k, int64_t h, int64_t d, int64_t n_types, void* ws, int64_t ws_bytes,
+       const graphop_plan_t* plan, void* stream, double p, uint64_t seed, uint32_t offset, int64_t head0) {
+      return graphop_attention_tbias_bf16_forward(row, indptr, eid, indices, Q, K, V, B, etype, o, stats, n_chunks, e, n_q,
+                                                  n_k, h, d, n_types, ws, ws_bytes, plan, stream, p, seed, offset, head0);
+    },
+    [](int, const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r, const int64_t* indices_r, const int64_t* col,
+       const int64_t* indptr_c, const int64_t* eid_c, const int64_t* indices_c, const void* Q, const void* K, const void* V,
+       const void* B, const int32_t* etype, const void* o, const void* stats, const void* dO, void* dQ, void* dK, void* dV,
+       void* dB, int64_t n_row_chunks, int64_t n_col_chunks, int64_t e, int64_t n_q, int64_t n_k, int64_t h, int64_t d,
+       int64_t n_types, void* ws, int64_t ws_bytes, const graphop_plan_t* plan_r, const graphop_plan_t* plan_c,
+       void* stream, double p, uint64_t seed, uint32_t offset, int64_t head0) {
+      return graphop_attention_tbias_bf16_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V,
+                                                   B, etype, o, stats, dO, dQ, dK, dV, dB, n_row_chunks, n_col_chunks, e,
+                                                   n_q, n_k, h, d, n_types, ws, ws_bytes, plan_r, plan_c, stream, p, seed,
+                                                   offset, head0);
+    },
+    check_attn_tbias_bf16_table, true};
 
 // The forward of the ops with an edge row in key and value and of the op with an edge-type score bias, as `fn`.
 // etype == nullptr: rows is xe (graphop_attention_edge_forward); else rows is the table of `abi`: R
@@ -701,16 +733,16 @@ std::vector<at::Tensor> attention_edge_forward_impl(const char* fn, const at::Te
   const int64_t n_types = rows.size(0);
   DeviceGuard dg(Q);
   auto o = at::empty_like(Q);
-  auto stats = at::empty({n_q, h, 2}, Q.options());
+  auto stats = at::empty({n_q, h, 2}, abi.bf16 ? Q.options().dtype(attn_stats_type(Q)) : Q.options());
   const auto pp = get_plan(row, indptr, eid, indices, n_k);
   const auto& pl = *pp;
   int64_t nbytes = 0;
-  check(etype ? abi.query(dtype_code(Q), 0, e, n_q, n_k, h, d, n_types, pl.plan, nullptr, stream_of(Q), &nbytes)
+  check(etype ? abi.query(abi.code(Q), 0, e, n_q, n_k, h, d, n_types, pl.plan, nullptr, stream_of(Q), &nbytes)
               : graphop_attention_edge_workspace_bytes(dtype_code(Q), 0, e, n_q, n_k, h, d, pl.plan, nullptr,
                                                        stream_of(Q), &nbytes));
   auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, Q.options().dtype(at::kByte));
   if (etype)
-    check(abi.forward(dtype_code(Q), ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(V), vp(rows),
+    check(abi.forward(abi.code(Q), ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(V), vp(rows),
                       etype->data_ptr<int32_t>(), vp(o), vp(stats), row.size(0), e, n_q, n_k, h, d, n_types, ws.data_ptr(),
                       nbytes, pl.plan, stream_of(Q), drop.p, drop.seed, drop.offset, head0));
   else
@@ -753,7 +785,12 @@ std::vector<at::Tensor> attention_edge_backward_impl(const char* fn, const at::T
   CHECK_INPUT(Q); CHECK_INPUT(K); CHECK_INPUT(V); CHECK_INPUT(o); CHECK_INPUT(stats);
   CHECK_CUDA(dO_);
   const at::Tensor dO = dO_.contiguous();
-  CHECK_SAME_DTYPE(Q, K); CHECK_SAME_DTYPE(Q, V); CHECK_SAME_DTYPE(Q, o); CHECK_SAME_DTYPE(Q, stats); CHECK_SAME_DTYPE(Q, dO);
+  CHECK_SAME_DTYPE(Q, K); CHECK_SAME_DTYPE(Q, V); CHECK_SAME_DTYPE(Q, o); CHECK_SAME_DTYPE(Q, dO);
+  if (abi.bf16 && Q.scalar_type() == at::kBFloat16) {   // fp32 statistics with bfloat16 tables
+    TORCH_CHECK(stats.scalar_type() == at::kFloat, "expected stats to be torch.float32 for bfloat16 Q, got ", stats.scalar_type());
+  } else {
+    CHECK_SAME_DTYPE(Q, stats);
+  }
   TORCH_CHECK(K.sizes() == V.sizes() && Q.sizes().slice(1) == K.sizes().slice(1),
               fn, ": Q (n_q,[h,]d), K and V (n_k,[h,]d) expected");
   const int64_t e = eid_r.size(0), d = Q.size(-1), h = Q.dim() == 2 ? 1 : Q.size(1), n_q = Q.size(0), n_k = K.size(0);
@@ -768,7 +805,7 @@ std::vector<at::Tensor> attention_edge_backward_impl(const char* fn, const at::T
   const auto ppc = get_plan(col, indptr_c, eid_c, indices_c, n_q);
   const auto &pr = *ppr, &pc = *ppc;
   int64_t nbytes = 0;
-  check(etype ? abi.query(dtype_code(Q), 1, e, n_q, n_k, h, d, n_types, pr.plan, pc.plan, stream_of(Q), &nbytes)
+  check(etype ? abi.query(abi.code(Q), 1, e, n_q, n_k, h, d, n_types, pr.plan, pc.plan, stream_of(Q), &nbytes)
               : graphop_attention_edge_workspace_bytes(dtype_code(Q), 1, e, n_q, n_k, h, d, pr.plan, pc.plan,
                                                        stream_of(Q), &nbytes));
   auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, Q.options().dtype(at::kByte));
@@ -778,7 +815,7 @@ std::vector<at::Tensor> attention_edge_backward_impl(const char* fn, const at::T
                      : (etype || pr.info.full_coverage ? at::empty_like(rows) : at::zeros_like(rows));
   if (etype)
     check(abi.backward(
-        dtype_code(Q), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c), ip(indices_c),
+        abi.code(Q), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c), ip(indices_c),
         vp(Q), vp(K), vp(V), vp(rows), etype->data_ptr<int32_t>(), vp(o), vp(stats), vp(dO), vp(dQ), vp(dK), vp(dV),
         need_dx ? vp(dx) : nullptr, row.size(0), col.size(0), e, n_q, n_k, h, d, n_types, ws.data_ptr(), nbytes, pr.plan,
         pc.plan, stream_of(Q), drop.p, drop.seed, drop.offset, head0));
@@ -833,6 +870,29 @@ std::vector<at::Tensor> attention_tbias_backward(const at::Tensor& row, const at
   return attention_edge_backward_impl("attention_tbias_backward", row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
                                       indices_c, Q, K, V, B, &etype, o, stats, dO, p, seed, offset, head0, need_dB,
                                       kAttnTbiasAbi);
+}
+
+// ... on bfloat16 tables
+std::vector<at::Tensor> attention_tbias_bf16_forward(const at::Tensor& row, const at::Tensor& indptr,
+                                                     const at::Tensor& eid, const at::Tensor& indices, const at::Tensor& Q,
+                                                     const at::Tensor& K, const at::Tensor& V, const at::Tensor& B,
+                                                     const at::Tensor& etype, double p, int64_t seed, int64_t offset,
+                                                     int64_t head0) {
+  return attention_edge_forward_impl("attention_tbias_bf16_forward", row, indptr, eid, indices, Q, K, V, B, &etype, p,
+                                     seed, offset, head0, kAttnTbiasBf16Abi);
+}
+
+std::vector<at::Tensor> attention_tbias_bf16_backward(const at::Tensor& row, const at::Tensor& indptr_r,
+                                                      const at::Tensor& eid_r, const at::Tensor& indices_r,
+                                                      const at::Tensor& col, const at::Tensor& indptr_c,
+                                                      const at::Tensor& eid_c, const at::Tensor& indices_c,
+                                                      const at::Tensor& Q, const at::Tensor& K, const at::Tensor& V,
+                                                      const at::Tensor& B, const at::Tensor& etype, const at::Tensor& o,
+                                                      const at::Tensor& stats, const at::Tensor& dO, double p,
+                                                      int64_t seed, int64_t offset, int64_t head0, bool need_dB) {
+  return attention_edge_backward_impl("attention_tbias_bf16_backward", row, indptr_r, eid_r, indices_r, col, indptr_c,
+                                      eid_c, indices_c, Q, K, V, B, &etype, o, stats, dO, p, seed, offset, head0, need_dB,
+                                      kAttnTbiasBf16Abi);
 }
 
 // ---- the weights of the fused attention ops from their row statistics (include/graphop_hip.h: graphop_attention_weights)
@@ -1527,6 +1587,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("etype"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0, py::arg("head0") = 0);
   m.def("attention_tbias_backward", &attention_tbias_backward,
         "Fused attention backward with an edge-type score bias (extra op)", py::arg("row"),
+        py::arg("indptr_r"), py::arg("eid_r"), py::arg("indices_r"), py::arg("col"), py::arg("indptr_c"),
+        py::arg("eid_c"), py::arg("indices_c"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("B"), py::arg("etype"),
+        py::arg("o"), py::arg("stats"), py::arg("dO"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0,
+        py::arg("head0") = 0, py::arg("need_dB") = true);
+  // (likewise on bfloat16 tables)
+  m.def("attention_tbias_bf16_forward", &attention_tbias_bf16_forward,
+        "Fused attention forward on bfloat16 tables with an edge-type score bias (extra op)", py::arg("row"),
+        py::arg("indptr"), py::arg("eid"), py::arg("indices"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("B"),
+        py::arg("etype"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0, py::arg("head0") = 0);
+  m.def("attention_tbias_bf16_backward", &attention_tbias_bf16_backward,
+        "Fused attention backward on bfloat16 tables with an edge-type score bias (extra op)", py::arg("row"),
         py::arg("indptr_r"), py::arg("eid_r"), py::arg("indices_r"), py::arg("col"), py::arg("indptr_c"),
         py::arg("eid_c"), py::arg("indices_c"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("B"), py::arg("etype"),
         py::arg("o"), py::arg("stats"), py::arg("dO"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0,

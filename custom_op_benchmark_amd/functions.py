@@ -551,7 +551,9 @@ class FusedAttentionTypeBias(Function):
     is summed on chip, and only where B needs a gradient.  One call whatever h: there are no head groups.  Saves the CSR
     arrays, (Q, K, V, B, etype, o, row statistics) and nothing else; etype gets no gradient.  Types outside
     [0, n_types) are not detected (that would synchronise): the kernels clamp them, so they give undefined values and
-    touch no memory outside B / B.grad.  m_e, seed=None and the missing 1 / sqrt(d) argument: as FusedAttentionBias."""
+    touch no memory outside B / B.grad.  m_e, seed=None and the missing 1 / sqrt(d) argument: as FusedAttentionBias.
+    bfloat16 Q / K / V / B run graphop.attention_tbias_bf16_* (DESIGN.md 4.5x): n_types * h <= 512, B.grad bfloat16 in B's
+    shape, summed in fp32 without atomics and rounded once; what those kernels do not cover is refused by name."""
 
     @staticmethod
     def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, B, etype, p=0.0,
@@ -559,7 +561,9 @@ class FusedAttentionTypeBias(Function):
         a8 = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
         seed = _drop_seed(seed, p)
         ctx.drop = (float(p), int(seed), int(offset))
-        o, stats = _ops.attention_tbias_forward(row, indptr_r, eid_r, indices_r, Q, K, V, B, etype, *ctx.drop, 0)
+        ctx.bf16 = Q.dtype == torch.bfloat16          # (bfloat16 tables, B.grad bfloat16 in B's shape)
+        forward = _ops.attention_tbias_bf16_forward if ctx.bf16 else _ops.attention_tbias_forward
+        o, stats = forward(row, indptr_r, eid_r, indices_r, Q, K, V, B, etype, *ctx.drop, 0)
         ctx.save_for_backward(*a8, Q, K, V, B, etype, o, stats)
         return o
 
@@ -567,7 +571,8 @@ class FusedAttentionTypeBias(Function):
     def backward(ctx, dO):
         a8, (Q, K, V, B, etype, o, stats) = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
         need_dB = ctx.needs_input_grad[11]
-        dQ, dK, dV, dB = _ops.attention_tbias_backward(*a8, Q, K, V, B, etype, o, stats, dO, *ctx.drop, 0, need_dB)
+        backward = _ops.attention_tbias_bf16_backward if ctx.bf16 else _ops.attention_tbias_backward
+        dQ, dK, dV, dB = backward(*a8, Q, K, V, B, etype, o, stats, dO, *ctx.drop, 0, need_dB)
         return (None,) * 8 + (dQ, dK, dV, dB if need_dB else None, None, None, None, None)
 
 

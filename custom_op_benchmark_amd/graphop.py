@@ -968,12 +968,13 @@ def _attn_edge_form(fn):
     return fn.split("_")[1]
 
 
-def _attn_edge_workspace(like, backward, sizes, plan_r, plan_c, form):
-    """sizes: (e, n_q, n_k, h, d) and, with a table, n_types"""
+def _attn_edge_workspace(like, backward, sizes, plan_r, plan_c, form, bf16=False):
+    """sizes: (e, n_q, n_k, h, d) and, with a table, n_types; bf16: the form's entry points on bfloat16 tables, which
+    take no dtype code"""
     import ctypes
     nbytes = ctypes.c_int64(0)
-    query = getattr(lib(), "graphop_attention_%s_workspace_bytes" % form)
-    check(query(dtype_code(like), 1 if backward else 0, *sizes, plan_r.handle,
+    query = getattr(lib(), "graphop_attention_%s_workspace_bytes" % (form + "_bf16" if bf16 else form))
+    check(query(*(() if bf16 else (dtype_code(like),)), 1 if backward else 0, *sizes, plan_r.handle,
                 plan_c.handle if plan_c is not None else _NULL, stream_of(like), ctypes.byref(nbytes)))
     return torch.empty(max(1, nbytes.value), dtype=torch.uint8, device=like.device), nbytes.value
 
@@ -987,8 +988,11 @@ def _attn_edge_operands(fn, rows, etype, Q, e, n_q, n_k, h, d):
     return (ptr(rows), ptr(etype)), (e, n_q, n_k, h, d, rows.size(0))
 
 
-def _attn_edge_forward(fn, row, indptr, eid, indices, Q, K, V, rows, etype, p, seed, offset, head0):
+def _attn_edge_forward(fn, row, indptr, eid, indices, Q, K, V, rows, etype, p, seed, offset, head0, bf16=False):
     drop = _drop_args(fn, p, seed, offset) + (_head0(fn, head0),)
+    if bf16:
+        _bf16_only(fn, Q)
+    code = () if bf16 else (dtype_code(Q),)
     _check_csr((row, indptr, eid, indices), _CSR, (Q, "Q"), (K, "K"), (V, "V"))
     _same_dtype(Q, K, "Q", "K")
     _same_dtype(Q, V, "Q", "V")
@@ -1000,24 +1004,31 @@ def _attn_edge_forward(fn, row, indptr, eid, indices, Q, K, V, rows, etype, p, s
     form = _attn_edge_form(fn)
     operands, sizes = _attn_edge_operands(fn, rows, etype, Q, e, n_q, n_k, h, d)
     o = torch.empty_like(Q)
-    stats = torch.empty((n_q, h, 2), dtype=Q.dtype, device=Q.device)
+    stats = torch.empty((n_q, h, 2), dtype=attn_stats_dtype(Q) if bf16 else Q.dtype, device=Q.device)
     with _lib.device_guard(Q.device):
         plan = get_plan(row, indptr, eid, indices, n_k)
-        ws, nbytes = _attn_edge_workspace(Q, False, sizes, plan, None, form)
+        ws, nbytes = _attn_edge_workspace(Q, False, sizes, plan, None, form, bf16)
         call = getattr(lib(), "graphop_" + fn)
-        check(call(dtype_code(Q), ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(Q), ptr(K), ptr(V), *operands,
+        check(call(*code, ptr(row), ptr(indptr), ptr(eid), ptr(indices), ptr(Q), ptr(K), ptr(V), *operands,
                    ptr(o), ptr(stats), row.size(0), *sizes, ptr(ws), nbytes, plan.handle, stream_of(Q), *drop))
     return [o, stats]
 
 
 def _attn_edge_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, rows, etype, o,
-                        stats, dO, p, seed, offset, head0, need_dx):
+                        stats, dO, p, seed, offset, head0, need_dx, bf16=False):
     drop = _drop_args(fn, p, seed, offset) + (_head0(fn, head0),)
+    if bf16:
+        _bf16_only(fn, Q)
+    code = () if bf16 else (dtype_code(Q),)
     _check_csr((row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c), _CSR_RC,
                (Q, "Q"), (K, "K"), (V, "V"), (o, "o"), (stats, "stats"))
     _check_grad(dO, "dO")
     for t, n in ((K, "K"), (V, "V"), (o, "o"), (stats, "stats"), (dO, "dO")):
-        _same_dtype(Q, t, "Q", n)
+        if bf16 and n == "stats":          # fp32 statistics with bfloat16 tables
+            if t.dtype != attn_stats_dtype(Q):
+                raise RuntimeError("expected stats to be %s for Q of %s, got %s" % (attn_stats_dtype(Q), Q.dtype, t.dtype))
+        else:
+            _same_dtype(Q, t, "Q", n)
     dO = dO.contiguous()
     if K.shape != V.shape or Q.shape[1:] != K.shape[1:]:
         raise RuntimeError("%s: Q (n_q,[h,]d), K and V (n_k,[h,]d) expected" % fn)
@@ -1038,9 +1049,9 @@ def _attn_edge_backward(fn, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_
             dx = torch.empty((0,), dtype=rows.dtype, device=rows.device)
         else:
             dx = torch.empty_like(rows) if form != "edge" or plan_r.info.full_coverage else torch.zeros_like(rows)
-        ws, nbytes = _attn_edge_workspace(Q, True, sizes, plan_r, plan_c, form)
+        ws, nbytes = _attn_edge_workspace(Q, True, sizes, plan_r, plan_c, form, bf16)
         call = getattr(lib(), "graphop_" + fn)
-        check(call(dtype_code(Q), ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c),
+        check(call(*code, ptr(row), ptr(indptr_r), ptr(eid_r), ptr(indices_r), ptr(col), ptr(indptr_c),
                    ptr(eid_c), ptr(indices_c), ptr(Q), ptr(K), ptr(V), *operands, ptr(o), ptr(stats), ptr(dO), ptr(dQ),
                    ptr(dK), ptr(dV), ptr(dx) if need_dx else _NULL, row.size(0), col.size(0), *sizes, ptr(ws), nbytes,
                    plan_r.handle, plan_c.handle, stream_of(Q), *drop))
@@ -1124,6 +1135,27 @@ def attention_tbias_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid
     forward: they never touch memory outside B / dB."""
     return _attn_edge_backward("attention_tbias_backward", row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
                                indices_c, Q, K, V, B, etype, o, stats, dO, p, seed, offset, head0, need_dB)
+
+
+# ---- the edge-type score bias on bfloat16 tables (extra ops, DESIGN.md 4.5x) ------------------------------------------
+def attention_tbias_bf16_forward(row, indptr, eid, indices, Q, K, V, B, etype, p=0.0, seed=0, offset=0, head0=0):
+    """-> [o, stats] of attention_tbias_forward on bfloat16 Q / K / V and B ((n_types, h) bfloat16, or (n_types) with 2-D
+    tables): bf16 gathers, fp32 sums, B widened into on-chip memory once per workgroup, o rounded once, fp32 stats of the
+    biased, undropped scores, bit-reproducible.  n_types * h may be at most 512; beyond that, and for whatever else the
+    bfloat16 kernels do not cover, the library refuses with a message that names the condition (attention_bf16_opts_* on
+    B[etype.long()] serves a larger table); nothing is upcast."""
+    return _attn_edge_forward("attention_tbias_bf16_forward", row, indptr, eid, indices, Q, K, V, B, etype, p, seed,
+                              offset, head0, bf16=True)
+
+
+def attention_tbias_bf16_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, B, etype, o,
+                                  stats, dO, p=0.0, seed=0, offset=0, head0=0, need_dB=True):
+    """-> [dQ, dK, dV, dB] of attention_tbias_bf16_forward for the output gradient dO, all bfloat16, with the same (p,
+    seed, offset, head0).  dB[t] = sum over the edges of type t of ds_e in B's shape is summed on chip in fp32, in one
+    fixed order and without atomics, and rounded once; it is 0 for a type no edge carries.  With need_dB=False it is an
+    empty (0,) tensor and nothing is accumulated.  stats must be the forward's fp32 ones."""
+    return _attn_edge_backward("attention_tbias_bf16_backward", row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
+                               indices_c, Q, K, V, B, etype, o, stats, dO, p, seed, offset, head0, need_dB, bf16=True)
 
 
 # ---- the weights of the fused attention ops from their row statistics (extra op, DESIGN.md 4.5n) ---------------------
@@ -1319,6 +1351,8 @@ EXTRA_OPS = [n for n in _SCHEMAS if n not in __all__] + ["attention_backward_is_
                                                          "attention_etype_forward", "attention_etype_backward",
                                                          # an edge-type score bias (attention_tbias_*)
                                                          "attention_tbias_forward", "attention_tbias_backward",
+                                                         # ... on bfloat16 tables (attention_tbias_bf16_*)
+                                                         "attention_tbias_bf16_forward", "attention_tbias_bf16_backward",
                                                          # the weights of the fused GAT / GATv2 layers
                                                          "gat_attention_weights", "gatv2_attention_weights"]
 _torch_lib = None
