@@ -712,6 +712,14 @@ const AttnTableAbi kAttnTbiasBf16Abi = {
     },
     check_attn_tbias_bf16_table, true};
 
+// ... and the edge rows themselves on bfloat16 tables (graphop_attention_edge_bf16_*): no table and no
+// types, so only the flag of the record counts; the calls are written out where etype == nullptr
+void check_attn_edge_bf16_rows(const char* fn, const at::Tensor& xe, const at::Tensor& Q, int64_t e) {
+  TORCH_CHECK(Q.scalar_type() == at::kBFloat16, fn, ": bfloat16 tensors only, got ", Q.scalar_type());
+  check_attn_edge_rows(fn, xe, Q, e);
+}
+const AttnTableAbi kAttnEdgeBf16Abi = {nullptr, nullptr, nullptr, nullptr, true};
+
 // The forward of the ops with an edge row in key and value and of the op with an edge-type score bias, as `fn`.
 // etype == nullptr: rows is xe (graphop_attention_edge_forward); else rows is the table of `abi`: R
 // (graphop_attention_etype_forward) or B (graphop_attention_tbias_forward).
@@ -729,6 +737,7 @@ std::vector<at::Tensor> attention_edge_forward_impl(const char* fn, const at::Te
   CHECK_SAME_DTYPE(Q, K); CHECK_SAME_DTYPE(Q, V);
   const int64_t e = eid.size(0), d = Q.size(-1), h = Q.dim() == 2 ? 1 : Q.size(1), n_q = Q.size(0), n_k = K.size(0);
   if (etype) abi.check(fn, rows, *etype, Q, e);
+  else if (abi.bf16) check_attn_edge_bf16_rows(fn, rows, Q, e);
   else check_attn_edge_rows(fn, rows, Q, e);
   const int64_t n_types = rows.size(0);
   DeviceGuard dg(Q);
@@ -738,13 +747,18 @@ std::vector<at::Tensor> attention_edge_forward_impl(const char* fn, const at::Te
   const auto& pl = *pp;
   int64_t nbytes = 0;
   check(etype ? abi.query(abi.code(Q), 0, e, n_q, n_k, h, d, n_types, pl.plan, nullptr, stream_of(Q), &nbytes)
-              : graphop_attention_edge_workspace_bytes(dtype_code(Q), 0, e, n_q, n_k, h, d, pl.plan, nullptr,
-                                                       stream_of(Q), &nbytes));
+        : abi.bf16 ? graphop_attention_edge_bf16_workspace_bytes(0, e, n_q, n_k, h, d, pl.plan, nullptr, stream_of(Q), &nbytes)
+                   : graphop_attention_edge_workspace_bytes(dtype_code(Q), 0, e, n_q, n_k, h, d, pl.plan, nullptr,
+                                                            stream_of(Q), &nbytes));
   auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, Q.options().dtype(at::kByte));
   if (etype)
     check(abi.forward(abi.code(Q), ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(V), vp(rows),
                       etype->data_ptr<int32_t>(), vp(o), vp(stats), row.size(0), e, n_q, n_k, h, d, n_types, ws.data_ptr(),
                       nbytes, pl.plan, stream_of(Q), drop.p, drop.seed, drop.offset, head0));
+  else if (abi.bf16)
+    check(graphop_attention_edge_bf16_forward(ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(V), vp(rows),
+                                              vp(o), vp(stats), row.size(0), e, n_q, n_k, h, d, ws.data_ptr(), nbytes,
+                                              pl.plan, stream_of(Q), drop.p, drop.seed, drop.offset, head0));
   else
     check(graphop_attention_edge_forward(dtype_code(Q), ip(row), ip(indptr), ip(eid), ip(indices), vp(Q), vp(K), vp(V),
                                          vp(rows), vp(o), vp(stats), row.size(0), e, n_q, n_k, h, d, ws.data_ptr(), nbytes,
@@ -797,6 +811,7 @@ std::vector<at::Tensor> attention_edge_backward_impl(const char* fn, const at::T
   TORCH_CHECK(o.sizes() == Q.sizes() && dO.sizes() == Q.sizes() && stats.numel() == n_q * h * 2,
               fn, ": o, dO must match Q and stats must be (n_q, h, 2)");
   if (etype) abi.check(fn, rows, *etype, Q, e);
+  else if (abi.bf16) check_attn_edge_bf16_rows(fn, rows, Q, e);
   else check_attn_edge_rows(fn, rows, Q, e);
   const int64_t n_types = rows.size(0);
   DeviceGuard dg(Q);
@@ -806,8 +821,9 @@ std::vector<at::Tensor> attention_edge_backward_impl(const char* fn, const at::T
   const auto &pr = *ppr, &pc = *ppc;
   int64_t nbytes = 0;
   check(etype ? abi.query(abi.code(Q), 1, e, n_q, n_k, h, d, n_types, pr.plan, pc.plan, stream_of(Q), &nbytes)
-              : graphop_attention_edge_workspace_bytes(dtype_code(Q), 1, e, n_q, n_k, h, d, pr.plan, pc.plan,
-                                                       stream_of(Q), &nbytes));
+        : abi.bf16 ? graphop_attention_edge_bf16_workspace_bytes(1, e, n_q, n_k, h, d, pr.plan, pc.plan, stream_of(Q), &nbytes)
+                   : graphop_attention_edge_workspace_bytes(dtype_code(Q), 1, e, n_q, n_k, h, d, pr.plan, pc.plan,
+                                                            stream_of(Q), &nbytes));
   auto ws = at::empty({std::max<int64_t>(nbytes, 1)}, Q.options().dtype(at::kByte));
   // dR, dB: the call fills it.  dxe[e] is written once per row-major slot: only a chunk list that leaves slots out needs
   // the zeros
@@ -819,6 +835,12 @@ std::vector<at::Tensor> attention_edge_backward_impl(const char* fn, const at::T
         vp(Q), vp(K), vp(V), vp(rows), etype->data_ptr<int32_t>(), vp(o), vp(stats), vp(dO), vp(dQ), vp(dK), vp(dV),
         need_dx ? vp(dx) : nullptr, row.size(0), col.size(0), e, n_q, n_k, h, d, n_types, ws.data_ptr(), nbytes, pr.plan,
         pc.plan, stream_of(Q), drop.p, drop.seed, drop.offset, head0));
+  else if (abi.bf16)
+    check(graphop_attention_edge_bf16_backward(
+        ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c), ip(indices_c), vp(Q), vp(K),
+        vp(V), vp(rows), vp(o), vp(stats), vp(dO), vp(dQ), vp(dK), vp(dV), need_dx ? vp(dx) : nullptr, row.size(0),
+        col.size(0), e, n_q, n_k, h, d, ws.data_ptr(), nbytes, pr.plan, pc.plan, stream_of(Q), drop.p, drop.seed,
+        drop.offset, head0));
   else
     check(graphop_attention_edge_backward(
         dtype_code(Q), ip(row), ip(indptr_r), ip(eid_r), ip(indices_r), ip(col), ip(indptr_c), ip(eid_c), ip(indices_c),
@@ -893,6 +915,28 @@ std::vector<at::Tensor> attention_tbias_bf16_backward(const at::Tensor& row, con
   return attention_edge_backward_impl("attention_tbias_bf16_backward", row, indptr_r, eid_r, indices_r, col, indptr_c,
                                       eid_c, indices_c, Q, K, V, B, &etype, o, stats, dO, p, seed, offset, head0, need_dB,
                                       kAttnTbiasBf16Abi);
+}
+
+// ... and the edge rows on bfloat16 tables
+std::vector<at::Tensor> attention_edge_bf16_forward(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
+                                                    const at::Tensor& indices, const at::Tensor& Q, const at::Tensor& K,
+                                                    const at::Tensor& V, const at::Tensor& xe, double p, int64_t seed,
+                                                    int64_t offset, int64_t head0) {
+  return attention_edge_forward_impl("attention_edge_bf16_forward", row, indptr, eid, indices, Q, K, V, xe, nullptr, p,
+                                     seed, offset, head0, kAttnEdgeBf16Abi);
+}
+
+std::vector<at::Tensor> attention_edge_bf16_backward(const at::Tensor& row, const at::Tensor& indptr_r,
+                                                     const at::Tensor& eid_r, const at::Tensor& indices_r,
+                                                     const at::Tensor& col, const at::Tensor& indptr_c,
+                                                     const at::Tensor& eid_c, const at::Tensor& indices_c,
+                                                     const at::Tensor& Q, const at::Tensor& K, const at::Tensor& V,
+                                                     const at::Tensor& xe, const at::Tensor& o, const at::Tensor& stats,
+                                                     const at::Tensor& dO, double p, int64_t seed, int64_t offset,
+                                                     int64_t head0, bool need_dxe) {
+  return attention_edge_backward_impl("attention_edge_bf16_backward", row, indptr_r, eid_r, indices_r, col, indptr_c,
+                                      eid_c, indices_c, Q, K, V, xe, nullptr, o, stats, dO, p, seed, offset, head0,
+                                      need_dxe, kAttnEdgeBf16Abi);
 }
 
 // ---- the weights of the fused attention ops from their row statistics (include/graphop_hip.h: graphop_attention_weights)
@@ -1602,6 +1646,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("eid_c"), py::arg("indices_c"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("B"), py::arg("etype"),
         py::arg("o"), py::arg("stats"), py::arg("dO"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0,
         py::arg("head0") = 0, py::arg("need_dB") = true);
+  // (and the edge rows on bfloat16 tables)
+  m.def("attention_edge_bf16_forward", &attention_edge_bf16_forward,
+        "Fused attention forward on bfloat16 tables with edge features in key and value (extra op)", py::arg("row"),
+        py::arg("indptr"), py::arg("eid"), py::arg("indices"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("xe"),
+        py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0, py::arg("head0") = 0);
+  m.def("attention_edge_bf16_backward", &attention_edge_bf16_backward,
+        "Fused attention backward on bfloat16 tables with edge features in key and value (extra op)", py::arg("row"),
+        py::arg("indptr_r"), py::arg("eid_r"), py::arg("indices_r"), py::arg("col"), py::arg("indptr_c"),
+        py::arg("eid_c"), py::arg("indices_c"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("xe"), py::arg("o"),
+        py::arg("stats"), py::arg("dO"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0,
+        py::arg("head0") = 0, py::arg("need_dxe") = true);
   // (and the weights of all of these from their row statistics)
   m.def("attention_weights", &attention_weights,
         "Attention weights of the fused attention ops from their row statistics (extra op)", py::arg("row"),

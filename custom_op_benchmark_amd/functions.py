@@ -487,7 +487,9 @@ class FusedAttentionEdge(Function):
     dropout); seed=None draws one from torch's default CPU generator.  There is no 1 / sqrt(d) scale argument: fold it
     into Q.  One call whatever h: there are no head groups.  For a CATEGORICAL edge feature (xe = R[etype]: relations,
     bond types, clipped relative positions) use FusedAttentionEdgeType, which takes the table and the types and makes
-    neither xe nor dxe."""
+    neither xe nor dxe.
+    bfloat16 Q / K / V / xe run graphop.attention_edge_bf16_* (DESIGN.md 4.5y): xe is streamed as bf16, xe.grad is bfloat16
+    in xe's shape and rounded once; what those kernels do not cover is refused by name, nothing is upcast."""
 
     @staticmethod
     def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, xe, p=0.0, seed=None,
@@ -495,7 +497,9 @@ class FusedAttentionEdge(Function):
         a8 = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
         seed = _drop_seed(seed, p)
         ctx.drop = (float(p), int(seed), int(offset))
-        o, stats = _ops.attention_edge_forward(row, indptr_r, eid_r, indices_r, Q, K, V, xe, *ctx.drop, 0)
+        ctx.bf16 = Q.dtype == torch.bfloat16          # (bfloat16 tables, xe.grad bfloat16 in xe's shape)
+        forward = _ops.attention_edge_bf16_forward if ctx.bf16 else _ops.attention_edge_forward
+        o, stats = forward(row, indptr_r, eid_r, indices_r, Q, K, V, xe, *ctx.drop, 0)
         ctx.save_for_backward(*a8, Q, K, V, xe, o, stats)
         return o
 
@@ -503,7 +507,8 @@ class FusedAttentionEdge(Function):
     def backward(ctx, dO):
         a8, (Q, K, V, xe, o, stats) = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
         need_dxe = ctx.needs_input_grad[11]
-        dQ, dK, dV, dxe = _ops.attention_edge_backward(*a8, Q, K, V, xe, o, stats, dO, *ctx.drop, 0, need_dxe)
+        backward = _ops.attention_edge_bf16_backward if ctx.bf16 else _ops.attention_edge_backward
+        dQ, dK, dV, dxe = backward(*a8, Q, K, V, xe, o, stats, dO, *ctx.drop, 0, need_dxe)
         return (None,) * 8 + (dQ, dK, dV, dxe if need_dxe else None, None, None, None)
 
 

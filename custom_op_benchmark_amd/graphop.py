@@ -1158,6 +1158,27 @@ def attention_tbias_bf16_backward(row, indptr_r, eid_r, indices_r, col, indptr_c
                                indices_c, Q, K, V, B, etype, o, stats, dO, p, seed, offset, head0, need_dB, bf16=True)
 
 
+# ---- edge features on bfloat16 tables (extra ops) ------------------------------------------------------
+def attention_edge_bf16_forward(row, indptr, eid, indices, Q, K, V, xe, p=0.0, seed=0, offset=0, head0=0):
+    """-> [o, stats] of attention_edge_forward on bfloat16 Q / K / V and xe ((n_edges, h, d) bfloat16 by edge id, or
+    (n_edges, d) with 2-D tables): bf16 gathers and a bf16 edge stream, fp32 sums, the score one fp32 chain over K_j's and
+    then xe[e]'s words -- K_j + xe[e] is never rounded to bf16 -- o rounded once, fp32 stats of the undropped scores
+    ((0, 0) for rows without edges), bit-reproducible.  Nothing edge-sized is made.  What the bfloat16 kernels do not
+    cover is refused with a message that names the condition; nothing is upcast."""
+    return _attn_edge_forward("attention_edge_bf16_forward", row, indptr, eid, indices, Q, K, V, xe, None, p, seed, offset,
+                              head0, bf16=True)
+
+
+def attention_edge_bf16_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, xe, o, stats,
+                                 dO, p=0.0, seed=0, offset=0, head0=0, need_dxe=True):
+    """-> [dQ, dK, dV, dxe] of attention_edge_bf16_forward for the output gradient dO, all bfloat16, with the same (p,
+    seed, offset, head0).  dxe[e] = ds_e Q_i + a_e m_e dO_i in xe's shape, rounded once, is the only edge-sized tensor made
+    (edge ids that no row-major slot names get 0); with need_dxe=False it is an empty (0,) tensor and nothing edge-sized
+    is written.  stats must be the forward's fp32 ones."""
+    return _attn_edge_backward("attention_edge_bf16_backward", row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
+                               indices_c, Q, K, V, xe, None, o, stats, dO, p, seed, offset, head0, need_dxe, bf16=True)
+
+
 # ---- the weights of the fused attention ops from their row statistics (extra op, DESIGN.md 4.5n) ---------------------
 def _attn_weights_operands(fn, Q, K, stats, b, xe, n_edges):
     """-> (h, d): the mode (at most one of b and xe), then Q, K and stats against each other, then b or xe against the
@@ -1353,6 +1374,8 @@ EXTRA_OPS = [n for n in _SCHEMAS if n not in __all__] + ["attention_backward_is_
                                                          "attention_tbias_forward", "attention_tbias_backward",
                                                          # ... on bfloat16 tables (attention_tbias_bf16_*)
                                                          "attention_tbias_bf16_forward", "attention_tbias_bf16_backward",
+                                                         # edge features on bfloat16 tables (attention_edge_bf16_*)
+                                                         "attention_edge_bf16_forward", "attention_edge_bf16_backward",
                                                          # the weights of the fused GAT / GATv2 layers
                                                          "gat_attention_weights", "gatv2_attention_weights"]
 _torch_lib = None

@@ -1104,6 +1104,46 @@ GRAPHOP_API int graphop_attention_tbias_bf16_backward(const int64_t* row, const 
                                           const graphop_plan_t* plan_c, void* stream, double p, uint64_t seed,
                                           uint32_t offset, int64_t head0);
 
+/* ---- edge features on bfloat16 tables (ABI 8, additive; EXTRA ops; csrc/kernels_attn_edge_bf16.h) ----------------------
+ * graphop_attention_edge_forward / _backward as stated above, on the tables of the bfloat16 step (dtype GRAPHOP_BF16 of
+ * graphop_attention_forward) and with the arithmetic of graphop_attention_bf16_opts_*: Q, K, V, xe, o, dO, dQ, dK, dV, dxe
+ * are bf16 and 16-byte aligned, xe and dxe (n_edges, h, d) by edge id; stats (n_q, h, 2) is fp32.  These entry points
+ * take no dtype; graphop_attention_edge_* keeps answering GRAPHOP_BF16 with "bad dtype".  DESIGN.md 4.5y.
+ *   s_e = <Q_i, K_j + xe[e]>: ONE fp32 chain of packed dot products, Q's words first, over K_j's words and then over
+ *   xe[e]'s; K_j + xe[e] and V_j + xe[e] are never formed in bf16, so nothing is rounded twice.  The same expression in the
+ *   forward and in both backward passes.  stats are those of the undropped scores; rows without edges get o = 0 and
+ *   stats = (0, 0), as in the bfloat16 step.
+ *   dxe[e] = bf16(ds_e Q_i + a_e mult_e dO_i), rounded once, written by the row-major pass for every edge id a row-major
+ *   slot names (each once; the others are left untouched).  dxe == NULL: not wanted; nothing edge-sized is then written.
+ * Every sum is fp32, every bf16 result is rounded once to nearest even, and no float atomic touches anything: two runs are
+ * bit-identical.  Nothing edge-sized is made but dxe.
+ * Supported: the (h, d) pairs and plans of the bfloat16 step (see graphop_attention_forward) and the dropout arguments of
+ * graphop_attention_bf16_opts_*.  Otherwise the workspace query answers 0 bytes and forward / backward return
+ * GRAPHOP_ERR_INVALID_ARGUMENT with a message naming the unmet condition; nothing is upcast or composed.
+ * Checks, all before anything touches a device: those of graphop_attention_forward, then the dropout arguments (head0
+ * included), then xe != NULL (unless n_edges * h * d == 0), then the pair and the plans, then the pointers, the alignment
+ * (xe and dxe included) and the workspace.  Empty problems fill what they must and dereference nothing.
+ * workspace: graphop_attention_edge_bf16_workspace_bytes bytes: exactly what
+ * graphop_attention_workspace_bytes(GRAPHOP_BF16, ...) reports for the direction. */
+GRAPHOP_API int graphop_attention_edge_bf16_workspace_bytes(int backward, int64_t n_edges, int64_t n_q, int64_t n_k,
+                                                int64_t h, int64_t d, const graphop_plan_t* plan_r,
+                                                const graphop_plan_t* plan_c, void* stream, int64_t* bytes_out);
+GRAPHOP_API int graphop_attention_edge_bf16_forward(const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                                        const int64_t* indices, const void* Q, const void* K, const void* V,
+                                        const void* xe, void* o, void* stats, int64_t n_chunks, int64_t n_edges,
+                                        int64_t n_q, int64_t n_k, int64_t h, int64_t d, void* workspace,
+                                        int64_t workspace_bytes, const graphop_plan_t* plan, void* stream, double p,
+                                        uint64_t seed, uint32_t offset, int64_t head0);
+GRAPHOP_API int graphop_attention_edge_bf16_backward(const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r,
+                                         const int64_t* indices_r, const int64_t* col, const int64_t* indptr_c,
+                                         const int64_t* eid_c, const int64_t* indices_c, const void* Q, const void* K,
+                                         const void* V, const void* xe, const void* o, const void* stats, const void* dO,
+                                         void* dQ, void* dK, void* dV, void* dxe, int64_t n_row_chunks,
+                                         int64_t n_col_chunks, int64_t n_edges, int64_t n_q, int64_t n_k, int64_t h,
+                                         int64_t d, void* workspace, int64_t workspace_bytes,
+                                         const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream,
+                                         double p, uint64_t seed, uint32_t offset, int64_t head0);
+
 /* ---- attention weights of the fused dot-product attention ops (not in the reference) --------------
  * The weights the layer used, as an edge tensor (PyG's return_attention_weights=True, DGL's get_attention=True), from
  * the row statistics stats (n_q, h, 2) = (m_i, linv_i) that graphop_attention_forward / _dropout_forward /
