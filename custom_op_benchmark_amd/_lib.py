@@ -184,6 +184,12 @@ _SIGNATURES = {
     + [ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _c64],
     "graphop_attention_edge_bf16_backward": [_P] * 19 + [_c64] * 7 + [_P, _c64, _P, _P, _P]
     + [ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _c64],
+    # edge-type embeddings on bfloat16 tables: the tbias_bf16 lists, R where B is, dR where dB is
+    "graphop_attention_etype_bf16_workspace_bytes": [ctypes.c_int] + [_c64] * 6 + [_P, _P, _P, ctypes.POINTER(_c64)],
+    "graphop_attention_etype_bf16_forward": [_P] * 11 + [_c64] * 7 + [_P, _c64, _P, _P]
+    + [ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _c64],
+    "graphop_attention_etype_bf16_backward": [_P] * 20 + [_c64] * 8 + [_P, _c64, _P, _P, _P]
+    + [ctypes.c_double, ctypes.c_uint64, ctypes.c_uint32, _c64],
     # the weights of those ops from their row statistics: Q, K, stats, b | NULL, xe | NULL, a; no workspace
     "graphop_attention_weights": [ctypes.c_int] + [_P] * 10 + [_c64] * 6 + [_P, _P],
     # the weights of the fused GAT / GATv2 layers from their row statistics: el, er, ee | NULL, stats, a

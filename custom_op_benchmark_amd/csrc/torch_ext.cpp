@@ -939,6 +939,59 @@ std::vector<at::Tensor> attention_edge_bf16_backward(const at::Tensor& row, cons
                                       need_dxe, kAttnEdgeBf16Abi);
 }
 
+// ... and edge-type embeddings on bfloat16 tables (graphop_attention_etype_bf16_*): the etype lists without
+// the dtype code
+void check_attn_etype_bf16_table(const char* fn, const at::Tensor& R, const at::Tensor& etype, const at::Tensor& Q, int64_t e) {
+  TORCH_CHECK(Q.scalar_type() == at::kBFloat16, fn, ": bfloat16 tensors only, got ", Q.scalar_type());
+  check_attn_etype_table(fn, R, etype, Q, e);
+}
+const AttnTableAbi kAttnEtypeBf16Abi = {
+    [](int, int backward, int64_t e, int64_t n_q, int64_t n_k, int64_t h, int64_t d, int64_t n_types,
+       const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream, int64_t* bytes_out) {
+      return graphop_attention_etype_bf16_workspace_bytes(backward, e, n_q, n_k, h, d, n_types, plan_r, plan_c, stream, bytes_out);
+    },
+    [](int, const int64_t* row, const int64_t* indptr, const int64_t* eid, const int64_t* indices, const void* Q,
+       const void* K, const void* V, const void* R, const int32_t* etype, void* o, void* stats, int64_t n_chunks, int64_t e,
+       int64_t n_q, int64_t n_k, int64_t h, int64_t d, int64_t n_types, void* ws, int64_t ws_bytes,
+       const graphop_plan_t* plan, void* stream, double p, uint64_t seed, uint32_t offset, int64_t head0) {
+      return graphop_attention_etype_bf16_forward(row, indptr, eid, indices, Q, K, V, R, etype, o, stats, n_chunks, e, n_q,
+                                                  n_k, h, d, n_types, ws, ws_bytes, plan, stream, p, seed, offset, head0);
+    },
+    [](int, const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r, const int64_t* indices_r, const int64_t* col,
+       const int64_t* indptr_c, const int64_t* eid_c, const int64_t* indices_c, const void* Q, const void* K, const void* V,
+       const void* R, const int32_t* etype, const void* o, const void* stats, const void* dO, void* dQ, void* dK, void* dV,
+       void* dR, int64_t n_row_chunks, int64_t n_col_chunks, int64_t e, int64_t n_q, int64_t n_k, int64_t h, int64_t d,
+       int64_t n_types, void* ws, int64_t ws_bytes, const graphop_plan_t* plan_r, const graphop_plan_t* plan_c,
+       void* stream, double p, uint64_t seed, uint32_t offset, int64_t head0) {
+      return graphop_attention_etype_bf16_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V,
+                                                   R, etype, o, stats, dO, dQ, dK, dV, dR, n_row_chunks, n_col_chunks, e,
+                                                   n_q, n_k, h, d, n_types, ws, ws_bytes, plan_r, plan_c, stream, p, seed,
+                                                   offset, head0);
+    },
+    check_attn_etype_bf16_table, true};
+
+std::vector<at::Tensor> attention_etype_bf16_forward(const at::Tensor& row, const at::Tensor& indptr,
+                                                     const at::Tensor& eid, const at::Tensor& indices, const at::Tensor& Q,
+                                                     const at::Tensor& K, const at::Tensor& V, const at::Tensor& R,
+                                                     const at::Tensor& etype, double p, int64_t seed, int64_t offset,
+                                                     int64_t head0) {
+  return attention_edge_forward_impl("attention_etype_bf16_forward", row, indptr, eid, indices, Q, K, V, R, &etype, p,
+                                     seed, offset, head0, kAttnEtypeBf16Abi);
+}
+
+std::vector<at::Tensor> attention_etype_bf16_backward(const at::Tensor& row, const at::Tensor& indptr_r,
+                                                      const at::Tensor& eid_r, const at::Tensor& indices_r,
+                                                      const at::Tensor& col, const at::Tensor& indptr_c,
+                                                      const at::Tensor& eid_c, const at::Tensor& indices_c,
+                                                      const at::Tensor& Q, const at::Tensor& K, const at::Tensor& V,
+                                                      const at::Tensor& R, const at::Tensor& etype, const at::Tensor& o,
+                                                      const at::Tensor& stats, const at::Tensor& dO, double p,
+                                                      int64_t seed, int64_t offset, int64_t head0, bool need_dR) {
+  return attention_edge_backward_impl("attention_etype_bf16_backward", row, indptr_r, eid_r, indices_r, col, indptr_c,
+                                      eid_c, indices_c, Q, K, V, R, &etype, o, stats, dO, p, seed, offset, head0, need_dR,
+                                      kAttnEtypeBf16Abi);
+}
+
 // ---- the weights of the fused attention ops from their row statistics (include/graphop_hip.h: graphop_attention_weights)
 at::Tensor attention_weights(const at::Tensor& row, const at::Tensor& indptr, const at::Tensor& eid,
                              const at::Tensor& indices, const at::Tensor& Q, const at::Tensor& K, const at::Tensor& stats,
@@ -1657,6 +1710,17 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
         py::arg("eid_c"), py::arg("indices_c"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("xe"), py::arg("o"),
         py::arg("stats"), py::arg("dO"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0,
         py::arg("head0") = 0, py::arg("need_dxe") = true);
+  // (and edge-type embeddings on bfloat16 tables)
+  m.def("attention_etype_bf16_forward", &attention_etype_bf16_forward,
+        "Fused attention forward on bfloat16 tables with edge-type embeddings in key and value (extra op)", py::arg("row"),
+        py::arg("indptr"), py::arg("eid"), py::arg("indices"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("R"),
+        py::arg("etype"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0, py::arg("head0") = 0);
+  m.def("attention_etype_bf16_backward", &attention_etype_bf16_backward,
+        "Fused attention backward on bfloat16 tables with edge-type embeddings in key and value (extra op)", py::arg("row"),
+        py::arg("indptr_r"), py::arg("eid_r"), py::arg("indices_r"), py::arg("col"), py::arg("indptr_c"),
+        py::arg("eid_c"), py::arg("indices_c"), py::arg("Q"), py::arg("K"), py::arg("V"), py::arg("R"), py::arg("etype"),
+        py::arg("o"), py::arg("stats"), py::arg("dO"), py::arg("p") = 0.0, py::arg("seed") = 0, py::arg("offset") = 0,
+        py::arg("head0") = 0, py::arg("need_dR") = true);
   // (and the weights of all of these from their row statistics)
   m.def("attention_weights", &attention_weights,
         "Attention weights of the fused attention ops from their row statistics (extra op)", py::arg("row"),

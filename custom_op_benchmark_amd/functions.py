@@ -524,7 +524,10 @@ class FusedAttentionEdgeType(Function):
     summed on chip, and only where R needs a gradient.  Saves the CSR arrays, (Q, K, V, R, etype, o, row statistics) and
     nothing else; etype gets no gradient.  Types outside [0, n_types) are not detected (that would synchronise): the
     kernels clamp them, so they give undefined values and touch no memory outside R / R.grad.  m_e, seed=None and the
-    missing 1 / sqrt(d) argument: as FusedAttentionEdge.  One call whatever h."""
+    missing 1 / sqrt(d) argument: as FusedAttentionEdge.  One call whatever h.
+    bfloat16 Q / K / V / R run graphop.attention_etype_bf16_* (DESIGN.md 4.5z): n_types * h * d <= 4096, R kept packed on
+    chip, R.grad bfloat16 in R's shape, summed in fp32 without atomics and rounded once; what those kernels do not cover
+    is refused by name, nothing is upcast."""
 
     @staticmethod
     def forward(ctx, row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, R, etype, p=0.0,
@@ -532,7 +535,9 @@ class FusedAttentionEdgeType(Function):
         a8 = (row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c)
         seed = _drop_seed(seed, p)
         ctx.drop = (float(p), int(seed), int(offset))
-        o, stats = _ops.attention_etype_forward(row, indptr_r, eid_r, indices_r, Q, K, V, R, etype, *ctx.drop, 0)
+        ctx.bf16 = Q.dtype == torch.bfloat16          # (bfloat16 tables, R.grad bfloat16 in R's shape)
+        forward = _ops.attention_etype_bf16_forward if ctx.bf16 else _ops.attention_etype_forward
+        o, stats = forward(row, indptr_r, eid_r, indices_r, Q, K, V, R, etype, *ctx.drop, 0)
         ctx.save_for_backward(*a8, Q, K, V, R, etype, o, stats)
         return o
 
@@ -540,7 +545,8 @@ class FusedAttentionEdgeType(Function):
     def backward(ctx, dO):
         a8, (Q, K, V, R, etype, o, stats) = ctx.saved_tensors[:8], ctx.saved_tensors[8:]
         need_dR = ctx.needs_input_grad[11]
-        dQ, dK, dV, dR = _ops.attention_etype_backward(*a8, Q, K, V, R, etype, o, stats, dO, *ctx.drop, 0, need_dR)
+        backward = _ops.attention_etype_bf16_backward if ctx.bf16 else _ops.attention_etype_backward
+        dQ, dK, dV, dR = backward(*a8, Q, K, V, R, etype, o, stats, dO, *ctx.drop, 0, need_dR)
         return (None,) * 8 + (dQ, dK, dV, dR if need_dR else None, None, None, None, None)
 
 

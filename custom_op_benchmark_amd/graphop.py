@@ -1179,6 +1179,30 @@ def attention_edge_bf16_backward(row, indptr_r, eid_r, indices_r, col, indptr_c,
                                indices_c, Q, K, V, xe, None, o, stats, dO, p, seed, offset, head0, need_dxe, bf16=True)
 
 
+# ---- edge-type embeddings on bfloat16 tables (extra ops) -----------------------------------------------
+def attention_etype_bf16_forward(row, indptr, eid, indices, Q, K, V, R, etype, p=0.0, seed=0, offset=0, head0=0):
+    """-> [o, stats] of attention_etype_forward on bfloat16 Q / K / V and R ((n_types, h, d) bfloat16, or (n_types, d) with
+    2-D tables): attention_edge_bf16_forward on R[etype.long()] without that (n_edges, h, d) tensor.  R is kept packed in
+    on-chip memory by every workgroup, so a slot reads its 4-byte type and nothing else edge-sized; the score is one fp32
+    chain over K_j's and then R[t]'s words -- K_j + R[t] is never rounded to bf16 -- o is rounded once, stats are the fp32
+    ones of the undropped scores, and runs are bit-reproducible.  n_types * h * d may be at most 4096; beyond that, and
+    for whatever else the bfloat16 kernels do not cover, the library refuses with a message that names the condition
+    (attention_edge_bf16_* on R[etype.long()] serves a larger table); nothing is upcast."""
+    return _attn_edge_forward("attention_etype_bf16_forward", row, indptr, eid, indices, Q, K, V, R, etype, p, seed,
+                              offset, head0, bf16=True)
+
+
+def attention_etype_bf16_backward(row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c, indices_c, Q, K, V, R, etype, o,
+                                  stats, dO, p=0.0, seed=0, offset=0, head0=0, need_dR=True):
+    """-> [dQ, dK, dV, dR] of attention_etype_bf16_forward for the output gradient dO, all bfloat16, with the same (p,
+    seed, offset, head0).  dR[t] = sum over the edges of type t of (ds_e Q_i + a_e m_e dO_i) in R's shape is summed on chip
+    in fp32, in one fixed order and without atomics, and rounded once; it is 0 for a type no edge carries.  No
+    (n_edges, h, d) gradient exists.  With need_dR=False it is an empty (0,) tensor and nothing is accumulated.  stats must
+    be the forward's fp32 ones."""
+    return _attn_edge_backward("attention_etype_bf16_backward", row, indptr_r, eid_r, indices_r, col, indptr_c, eid_c,
+                               indices_c, Q, K, V, R, etype, o, stats, dO, p, seed, offset, head0, need_dR, bf16=True)
+
+
 # ---- the weights of the fused attention ops from their row statistics (extra op, DESIGN.md 4.5n) ---------------------
 def _attn_weights_operands(fn, Q, K, stats, b, xe, n_edges):
     """-> (h, d): the mode (at most one of b and xe), then Q, K and stats against each other, then b or xe against the
@@ -1376,6 +1400,8 @@ EXTRA_OPS = [n for n in _SCHEMAS if n not in __all__] + ["attention_backward_is_
                                                          "attention_tbias_bf16_forward", "attention_tbias_bf16_backward",
                                                          # edge features on bfloat16 tables (attention_edge_bf16_*)
                                                          "attention_edge_bf16_forward", "attention_edge_bf16_backward",
+                                                         # edge-type embeddings on bfloat16 tables (attention_etype_bf16_*)
+                                                         "attention_etype_bf16_forward", "attention_etype_bf16_backward",
                                                          # the weights of the fused GAT / GATv2 layers
                                                          "gat_attention_weights", "gatv2_attention_weights"]
 _torch_lib = None

@@ -1144,6 +1144,57 @@ GRAPHOP_API int graphop_attention_edge_bf16_backward(const int64_t* row, const i
                                          const graphop_plan_t* plan_r, const graphop_plan_t* plan_c, void* stream,
                                          double p, uint64_t seed, uint32_t offset, int64_t head0);
 
+/* ---- edge-type embeddings on bfloat16 tables (ABI 8, additive; EXTRA ops; csrc/kernels_attn_etype_bf16.h) --------------
+ * graphop_attention_etype_forward / _backward as stated above, on the tables of the bfloat16 step (dtype GRAPHOP_BF16 of
+ * graphop_attention_forward) and with the arithmetic of graphop_attention_edge_bf16_* on xe[e] := R[t_e], word for word:
+ * Q, K, V, o, dO, dQ, dK, dV are bf16 [n][h][d] and 16-byte aligned; R is bf16 (n_types, h, d), contiguous and 16-byte
+ * aligned; dR is bf16 in R's shape with no alignment beyond its element; etype is int32 by edge id; stats (n_q, h, 2) is
+ * fp32.  These entry points take no dtype; graphop_attention_etype_* keeps answering GRAPHOP_BF16 with "bad dtype".
+ * DESIGN.md 4.5z.
+ *   t_e = min((unsigned) etype[e], n_types - 1), clamped before any address is formed
+ *   s_e = <Q_i, K_j + R[t_e]>: ONE fp32 chain of packed dot products, Q's words first, over K_j's words and then over
+ *   R[t_e]'s; K_j + R[t_e] and V_j + R[t_e] are never formed in bf16.  The same expression in the forward and in both
+ *   backward passes.  stats are those of the undropped scores; rows without edges get o = 0 and stats = (0, 0).
+ *   dR[t] = bf16(sum over the edges with t_e = t of (ds_e Q_i + a_e mult_e dO_i)): summed in fp32 in one fixed order,
+ *   rounded once, exactly 0 for a type no edge carries.  The call itself writes every element of dR.  dR == NULL: the
+ *   gradient of R is not wanted; the row pass then holds no table for it, asks for no LDS for one and leaves the partial
+ *   tables untouched.
+ * Every sum is fp32, every bf16 result is rounded once to nearest even, and no float atomic touches anything, dR
+ * included, in LDS or in global memory: two runs are bit-identical.  Nothing edge-sized is read but etype (and the edge
+ * ids), and nothing edge-sized is written.
+ * Supported: the (h, d) pairs and plans of the bfloat16 step (see graphop_attention_forward), the dropout arguments of
+ * graphop_attention_bf16_opts_*, and n_types * h * d <= 4096: every workgroup keeps R packed in LDS (8 KiB at the bound),
+ * and the row pass with dR one fp32 table of dR per wave (72 KiB in all).  Otherwise the workspace query answers 0 bytes
+ * and forward / backward return GRAPHOP_ERR_INVALID_ARGUMENT with a message naming the unmet condition
+ * ("n_types * h * d = ... is above 4096" above the bound, in both directions: use graphop_attention_edge_bf16_* on the
+ * gathered rows R[etype] there); nothing is upcast or composed.
+ * Checks, all before anything touches a device: those of graphop_attention_forward, then the dropout arguments (head0
+ * included), then n_types >= 1 (unless n_edges == 0), then the bound, then the pair and the plans, then the pointers, the
+ * alignment and the workspace.  Empty problems fill what they must and dereference nothing.
+ * workspace: graphop_attention_etype_bf16_workspace_bytes bytes: what graphop_attention_workspace_bytes(GRAPHOP_BF16, ...)
+ * reports for the direction, plus, LAST in the backward's, parts * up256(4 n_types h d) bytes for the partial tables of
+ * dR, parts = min(1024, the row pass's workgroups): the row pass with dR runs at most 1024 workgroups, each of which
+ * walks a run of the plain launch's workgroups and leaves one table.  At most 16 MiB. */
+GRAPHOP_API int graphop_attention_etype_bf16_workspace_bytes(int backward, int64_t n_edges, int64_t n_q, int64_t n_k,
+                                                 int64_t h, int64_t d, int64_t n_types, const graphop_plan_t* plan_r,
+                                                 const graphop_plan_t* plan_c, void* stream, int64_t* bytes_out);
+GRAPHOP_API int graphop_attention_etype_bf16_forward(const int64_t* row, const int64_t* indptr, const int64_t* eid,
+                                         const int64_t* indices, const void* Q, const void* K, const void* V,
+                                         const void* R, const int32_t* etype, void* o, void* stats, int64_t n_chunks,
+                                         int64_t n_edges, int64_t n_q, int64_t n_k, int64_t h, int64_t d, int64_t n_types,
+                                         void* workspace, int64_t workspace_bytes, const graphop_plan_t* plan, void* stream,
+                                         double p, uint64_t seed, uint32_t offset, int64_t head0);
+GRAPHOP_API int graphop_attention_etype_bf16_backward(const int64_t* row, const int64_t* indptr_r, const int64_t* eid_r,
+                                          const int64_t* indices_r, const int64_t* col, const int64_t* indptr_c,
+                                          const int64_t* eid_c, const int64_t* indices_c, const void* Q, const void* K,
+                                          const void* V, const void* R, const int32_t* etype, const void* o,
+                                          const void* stats, const void* dO, void* dQ, void* dK, void* dV, void* dR,
+                                          int64_t n_row_chunks, int64_t n_col_chunks, int64_t n_edges, int64_t n_q,
+                                          int64_t n_k, int64_t h, int64_t d, int64_t n_types, void* workspace,
+                                          int64_t workspace_bytes, const graphop_plan_t* plan_r,
+                                          const graphop_plan_t* plan_c, void* stream, double p, uint64_t seed,
+                                          uint32_t offset, int64_t head0);
+
 /* ---- attention weights of the fused dot-product attention ops (not in the reference) --------------
  * The weights the layer used, as an edge tensor (PyG's return_attention_weights=True, DGL's get_attention=True), from
  * the row statistics stats (n_q, h, 2) = (m_i, linv_i) that graphop_attention_forward / _dropout_forward /
